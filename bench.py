@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — makeup-transfer images/sec at 256x256, 50 DDIM steps (BASELINE.json metric), MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--cfg] [--res 256|512] [--batch 8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--cfg] [--res 256|512] [--batch 8] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch: mkd_prepare (hint embedding + cross-attn K/V caches)
 + the full 50-step DDIM reverse loop x_T -> latent (ControlNet + UNet every step), inputs resident in HBM.
@@ -10,6 +10,11 @@ images per step.  Either launched by torch.distributed.run (RANK / WORLD_SIZE in
 `python bench.py --gpus N` starts its N ranks as fresh child processes before touching the GPU.  With fewer than N devices
 visible the N ranks share card 0 over gloo (a REHEARSAL of the N > 1 code path, flagged in the JSON, not a measurement).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`) with the loop figures derived
+from the timed region.  `--full` adds what takes work of its own after the timed region: per-kernel-class times and the two
+roofline blocks (eps evaluations with an event pair per launch), the live rocprofv3 PMC passes, the L2 traffic from the
+committed profiles and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -73,7 +78,7 @@ def live_pmc_passes(args):
         return None, 'rocprofv3 not on PATH'
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR', 'MKD_DIST_BACKEND')}
     env['TMPDIR'] = '/tmp'
-    work = ['--steps', '1', '--warmup', '0', '--ddim-steps', '2', '--no-cpu-baseline', '--graph', '0', '--decode', '0', '--live-pmc', '0',
+    work = ['--steps', '1', '--warmup', '0', '--ddim-steps', '2', '--full', '--no-cpu-baseline', '--graph', '0', '--decode', '0', '--live-pmc', '0',
             '--batch', str(args.batch), '--res', str(args.res)] + (['--cfg'] if args.cfg else []) + (['--interp', str(args.interp)] if args.interp else [])
     out = {}
     base = tempfile.mkdtemp(prefix='mkd_pmc_', dir='/tmp')
@@ -268,6 +273,87 @@ def cpu_baseline(sd_cpu, res, x1, hint1, ctx1, gpu_eps1, gpu_lat, cpu_steps, ddi
             'gpu_vs_cpu_latent_cos_after_config1': lat_cos}
 
 
+def full_figures(args, eng, sch, x_T, dev, world):
+    """--full, rank 0, after the timed region: per-kernel-class device times of one eps evaluation (eps evaluations of their own,
+    an event pair per launch), the MFMA and HBM roofline blocks and, with --live-pmc, the live PMC passes behind their traffic."""
+    # per-kernel-class device time of ONE eps evaluation, HIP events around every launch on the same stream
+    tt = torch.full((eng.batch,), int(sch.ddim_timesteps[-1]), dtype=torch.int64, device=dev)
+    x_in = torch.cat([x_T, x_T]) if args.cfg else x_T
+    eng.eps_profile(x_in, tt)
+    prof = eng.eps_profile(x_in, tt, csv_path=args.ops_csv)
+    tot_ms = sum(v['ms'] for v in prof.values())
+    # kernel FUNCTIONS behind the classes: the implicit-GEMM gather kernel (all tile configs), the LDS-staged
+    # 3x3 conv kernel, the attention kernel.  The dominant one (by device time) carries the roofline.
+    fam = {'gemm_kernel': lambda k: k.startswith('gemm_') and 'patch' not in k,
+           'conv3x3_patch_kernel': lambda k: k.startswith('gemm_') and 'patch' in k,
+           'attention_kernel': lambda k: k == 'attention',
+           'tfm_tail_kernel': lambda k: k == 'tfm_tail'}
+    agg = {f: {'ms': sum(v['ms'] for k, v in prof.items() if sel(k)), 'flops': sum(v['flops'] for k, v in prof.items() if sel(k)),
+               'launches': sum(v['launches'] for k, v in prof.items() if sel(k))} for f, sel in fam.items()}
+    dom = max(agg, key=lambda f: agg[f]['ms'])
+    d = agg[dom]
+    ach = d['flops'] / (d['ms'] * 1e-3) / 1e12 if d['ms'] > 0 else 0.0
+    live, live_note = live_pmc_passes(args) if (args.live_pmc and world == 1) else (None, 'not attempted (--live-pmc 0 or more than one rank)')
+    if live is None:
+        log(f'live PMC: {live_note}; roofline.traffic from the committed summaries')
+    traffic, traffic_src = pmc_traffic_bytes_per_launch(dom, live, live_note, config_tag(args))
+    b2b_ms = sum(v['ms_b2b'] for k, v in prof.items() if fam[dom](k))
+    roofline = {'bound': 'mfma', 'kernel': dom + ' (all tile configurations, one eps evaluation)', 'achieved': ach,
+                'peak': PEAK_BF16_TFLOPS, 'unit': 'TFLOP/s', 'frac': ach / PEAK_BF16_TFLOPS,
+                'traffic': traffic, 'traffic_source': traffic_src,
+                'launches_per_eval': d['launches'], 'avg_launch_us': 1e3 * d['ms'] / max(1, d['launches']),
+                'flops_per_launch': d['flops'] / max(1, d['launches']),
+                'share_of_eval_time': d['ms'] / tot_ms if tot_ms else None,
+                # the same launches replayed back to back between ONE event pair: no 3-5 us of event overhead per launch
+                'avg_launch_us_back_to_back': 1e3 * b2b_ms / max(1, d['launches']),
+                'achieved_back_to_back': d['flops'] / (b2b_ms * 1e-3) / 1e12 if b2b_ms > 0 else None,
+                'other_kernels_tflops': {f: (v['flops'] / (v['ms'] * 1e-3) / 1e12 if v['ms'] else 0.0) for f, v in agg.items() if f != dom}}
+    # the dominant HBM-bound class (north_star: "HBM GB/s AND MFMA utilisation against peak"): algorithmic bytes from the plan
+    hbm_fn = {'groupnorm': 'gn_fused_kernel / gn_slab_kernel', 'layernorm': 'layernorm_kernel'}
+    hb = {k: v for k, v in prof.items() if k in hbm_fn and v['launches'] > 0 and v['ms'] > 0}
+    roofline_hbm = None
+    if hb:
+        hk = max(hb, key=lambda k: hb[k]['ms'])
+        hv = hb[hk]
+        gbs = hv['bytes'] / (hv['ms'] * 1e-3) / 1e9
+        gbs_b2b = hv['bytes'] / (hv['ms_b2b'] * 1e-3) / 1e9 if hv['ms_b2b'] > 0 else None
+        h_traffic, h_src = pmc_traffic_bytes_per_launch(tuple(hbm_fn[hk].split(' / ')), live, live_note, config_tag(args))      # (every kernel function of the class)
+        roofline_hbm = {'bound': 'hbm', 'kernel': f'{hbm_fn[hk]} ({hk} class, one eps evaluation)', 'achieved': gbs, 'peak': PEAK_HBM_GBS,
+                        'unit': 'GB/s', 'frac': gbs / PEAK_HBM_GBS, 'traffic': h_traffic, 'traffic_source': h_src,
+                        'launches_per_eval': hv['launches'], 'avg_launch_us': 1e3 * hv['ms'] / hv['launches'],
+                        'bytes_per_launch': hv['bytes'] / hv['launches'], 'share_of_eval_time': hv['ms'] / tot_ms if tot_ms else None,
+                        'avg_launch_us_back_to_back': 1e3 * hv['ms_b2b'] / hv['launches'],
+                        'achieved_back_to_back': gbs_b2b, 'frac_back_to_back': gbs_b2b / PEAK_HBM_GBS if gbs_b2b else None,
+                        'other_classes_gbs': {k: v['bytes'] / (v['ms'] * 1e-3) / 1e9 for k, v in hb.items() if k != hk}}
+    return {'prof': prof, 'roofline': roofline, 'roofline_hbm': roofline_hbm}
+
+
+DUMP_MAX_BYTES = 60_000_000      # all files of --dump-outputs together stay under 64 MB
+
+
+def dump_outputs(out, name, path, max_bytes=DUMP_MAX_BYTES):
+    """Writes `out` (what one step returns, [N, ...]) as path/<name>.npy in float32.  When it is larger than `max_bytes`, a fixed
+    seeded sample is written instead - whole samples along the batch dimension, or single elements of the flattened tensor when
+    one sample alone is too large - and the sampled indices as <name>_index.npy (float64, exact).  Returns {file name: shape}."""
+    os.makedirs(path, exist_ok=True)
+    out = out.detach().float()
+    files = {}
+    if out.numel() * 4 > max_bytes:
+        if out[0].numel() * 12 <= max_bytes:          # (4 bytes per value + 8 per index, over-counted for whole samples)
+            n, k = out.shape[0], int(max_bytes // (out[0].numel() * 4 + 8))
+        else:
+            out = out.reshape(-1)
+            n, k = out.numel(), int(max_bytes // 12)
+        idx = np.sort(np.random.default_rng(0).permutation(n)[:k])
+        out = out[torch.as_tensor(idx, device=out.device)]
+        np.save(os.path.join(path, f'{name}_index.npy'), idx.astype(np.float64))
+        files[f'{name}_index.npy'] = [int(k)]
+    arr = out.cpu().numpy()
+    np.save(os.path.join(path, f'{name}.npy'), arr)
+    files[f'{name}.npy'] = list(arr.shape)
+    return files
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -283,11 +369,20 @@ def main():
     ap.add_argument('--cpu-steps', type=int, default=20, help='DDIM steps of the CPU baseline run (BASELINE config 1: 20; ~1.2 s each on 16 cores)')
     ap.add_argument('--graph', type=int, default=1, help='replay the DDIM step as a hipGraph (0 = eager launches)')
     ap.add_argument('--decode', type=int, default=1, help='1: VAE-decode the latents to images inside the timed step (images out)')
-    ap.add_argument('--live-pmc', type=int, default=-1, help='1 (one GPU): after the timed region, two rocprofv3 --pmc child runs of a 2-step '
-                    'eager run measure FETCH_SIZE / WRITE_SIZE for roofline.traffic on this box; 0 / failure: the committed summaries; '
-                    '-1 (default): on for the full run (CPU baseline on, not itself under a profiler), off for --no-cpu-baseline experiment runs')
-    ap.add_argument('--ops-csv', default=None, help='write per-launch-group device times of one eps evaluation')
+    ap.add_argument('--live-pmc', type=int, default=-1, help='with --full, 1 (one GPU): after the timed region, two rocprofv3 --pmc child runs '
+                    'of a 2-step eager run measure FETCH_SIZE / WRITE_SIZE for roofline.traffic on this box; 0 / failure: the committed '
+                    'summaries; -1 (default): on for the full run (CPU baseline on, not itself under a profiler), off for --no-cpu-baseline '
+                    'experiment runs')
+    ap.add_argument('--ops-csv', default=None, help='with --full: write per-launch-group device times of one eps evaluation')
+    ap.add_argument('--full', action='store_true', help='after the timed region also measure what the headline does not need: '
+                    'per-kernel-class times, rooflines, live PMC passes, L2 traffic, the CPU baseline (--no-cpu-baseline drops it)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write what the last timed step returned as DIR/<name>.npy '
+                    '(float32; a fixed seeded sample when larger than 60 MB)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be >= 1 and --warmup >= 0')
+    if args.ops_csv and not args.full:
+        raise SystemExit('--ops-csv is part of the --full measurements')
     if args.live_pmc < 0:
         profiled = any(k.startswith('ROCPROF') for k in os.environ) or 'rocprof' in os.environ.get('LD_PRELOAD', '')
         args.live_pmc = int(not args.no_cpu_baseline and not profiled)
@@ -317,7 +412,7 @@ def main():
     eng = MkdEngine(cfg, dev)
     if args.decode:
         eng.configure_vae(VaeConfig())
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline      # (the CPU baseline is timed at N = 1 only)
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline      # (the CPU baseline is timed at N = 1 only)
     log(f'rank {rank}/{world}: generating 1.22 G synthetic weights on {dev}')
     sd_cpu = gen_weights(eng, seed=0, keep_cpu=want_cpu)
     log('weights loaded')
@@ -370,6 +465,9 @@ def main():
     dt = mdist.max_over_ranks(dt, dev)
     assert torch.isfinite(out).all() or os.environ.get('MKD_BENCH_ALLOW_NONFINITE') == '1', 'non-finite latents'      # (timing experiments with stubbed kernels only)
     log(f'timed {args.steps} steps in {dt:.2f} s')
+    if args.dump_outputs and rank == 0:      # (every rank holds the gathered batch; before anything else runs on the engine)
+        files = dump_outputs(out, 'images' if args.decode else 'latents', args.dump_outputs)
+        log(f'outputs of the last timed step -> {args.dump_outputs}: {files}')
 
     # which device every rank ran on (gathered over the process group: shows N distinct GPUs, or one in a rehearsal)
     me = f'{torch.cuda.get_device_name(local)} #{local}' + (f' pci {torch.cuda.get_device_properties(local).pci_bus_id}'
@@ -382,55 +480,7 @@ def main():
         evals_per_step = args.ddim_steps
         eps_flops = eng.eps_flops()                      # executed FLOPs of one eval at the prepared batch
         loop_ms = ev0.elapsed_time(ev1) / args.steps
-        # per-kernel-class device time of ONE eps evaluation, HIP events around every launch on the same stream
-        tt = torch.full((eng.batch,), int(sch.ddim_timesteps[-1]), dtype=torch.int64, device=dev)
-        x_in = torch.cat([x_T, x_T]) if args.cfg else x_T
-        eng.eps_profile(x_in, tt)
-        prof = eng.eps_profile(x_in, tt, csv_path=args.ops_csv)
-        tot_ms = sum(v['ms'] for v in prof.values())
-        # kernel FUNCTIONS behind the classes: the implicit-GEMM gather kernel (all tile configs), the LDS-staged
-        # 3x3 conv kernel, the attention kernel.  The dominant one (by device time) carries the roofline.
-        fam = {'gemm_kernel': lambda k: k.startswith('gemm_') and 'patch' not in k,
-               'conv3x3_patch_kernel': lambda k: k.startswith('gemm_') and 'patch' in k,
-               'attention_kernel': lambda k: k == 'attention',
-               'tfm_tail_kernel': lambda k: k == 'tfm_tail'}
-        agg = {f: {'ms': sum(v['ms'] for k, v in prof.items() if sel(k)), 'flops': sum(v['flops'] for k, v in prof.items() if sel(k)),
-                   'launches': sum(v['launches'] for k, v in prof.items() if sel(k))} for f, sel in fam.items()}
-        dom = max(agg, key=lambda f: agg[f]['ms'])
-        d = agg[dom]
-        ach = d['flops'] / (d['ms'] * 1e-3) / 1e12 if d['ms'] > 0 else 0.0
-        live, live_note = live_pmc_passes(args) if (args.live_pmc and world == 1) else (None, 'not attempted (--live-pmc 0 or more than one rank)')
-        if live is None:
-            log(f'live PMC: {live_note}; roofline.traffic from the committed summaries')
-        traffic, traffic_src = pmc_traffic_bytes_per_launch(dom, live, live_note, config_tag(args))
-        b2b_ms = sum(v['ms_b2b'] for k, v in prof.items() if fam[dom](k))
-        roofline = {'bound': 'mfma', 'kernel': dom + ' (all tile configurations, one eps evaluation)', 'achieved': ach,
-                    'peak': PEAK_BF16_TFLOPS, 'unit': 'TFLOP/s', 'frac': ach / PEAK_BF16_TFLOPS,
-                    'traffic': traffic, 'traffic_source': traffic_src,
-                    'launches_per_eval': d['launches'], 'avg_launch_us': 1e3 * d['ms'] / max(1, d['launches']),
-                    'flops_per_launch': d['flops'] / max(1, d['launches']),
-                    'share_of_eval_time': d['ms'] / tot_ms if tot_ms else None,
-                    # the same launches replayed back to back between ONE event pair: no 3-5 us of event overhead per launch
-                    'avg_launch_us_back_to_back': 1e3 * b2b_ms / max(1, d['launches']),
-                    'achieved_back_to_back': d['flops'] / (b2b_ms * 1e-3) / 1e12 if b2b_ms > 0 else None,
-                    'other_kernels_tflops': {f: (v['flops'] / (v['ms'] * 1e-3) / 1e12 if v['ms'] else 0.0) for f, v in agg.items() if f != dom}}
-        # the dominant HBM-bound class (north_star: "HBM GB/s AND MFMA utilisation against peak"): algorithmic bytes from the plan
-        hbm_fn = {'groupnorm': 'gn_fused_kernel / gn_slab_kernel', 'layernorm': 'layernorm_kernel'}
-        hb = {k: v for k, v in prof.items() if k in hbm_fn and v['launches'] > 0 and v['ms'] > 0}
-        roofline_hbm = None
-        if hb:
-            hk = max(hb, key=lambda k: hb[k]['ms'])
-            hv = hb[hk]
-            gbs = hv['bytes'] / (hv['ms'] * 1e-3) / 1e9
-            gbs_b2b = hv['bytes'] / (hv['ms_b2b'] * 1e-3) / 1e9 if hv['ms_b2b'] > 0 else None
-            h_traffic, h_src = pmc_traffic_bytes_per_launch(tuple(hbm_fn[hk].split(' / ')), live, live_note, config_tag(args))      # (every kernel function of the class)
-            roofline_hbm = {'bound': 'hbm', 'kernel': f'{hbm_fn[hk]} ({hk} class, one eps evaluation)', 'achieved': gbs, 'peak': PEAK_HBM_GBS,
-                            'unit': 'GB/s', 'frac': gbs / PEAK_HBM_GBS, 'traffic': h_traffic, 'traffic_source': h_src,
-                            'launches_per_eval': hv['launches'], 'avg_launch_us': 1e3 * hv['ms'] / hv['launches'],
-                            'bytes_per_launch': hv['bytes'] / hv['launches'], 'share_of_eval_time': hv['ms'] / tot_ms if tot_ms else None,
-                            'avg_launch_us_back_to_back': 1e3 * hv['ms_b2b'] / hv['launches'],
-                            'achieved_back_to_back': gbs_b2b, 'frac_back_to_back': gbs_b2b / PEAK_HBM_GBS if gbs_b2b else None,
-                            'other_classes_gbs': {k: v['bytes'] / (v['ms'] * 1e-3) / 1e9 for k, v in hb.items() if k != hk}}
+        full = full_figures(args, eng, sch, x_T, dev, world) if args.full else {}
         loop_tflops = eps_flops * evals_per_step / (loop_ms * 1e-3) / 1e12
         result = {
             'metric': 'makeup-transfer images/sec @256x256, 50 DDIM steps' if args.res == 256 and args.ddim_steps == 50
@@ -449,8 +499,8 @@ def main():
             'backend': torch.distributed.get_backend() if torch.distributed.is_initialized() else None,
             'rehearsal_single_device': os.environ.get('MKD_BENCH_SINGLE_DEVICE') == '1',
             'devices': sorted(set(dev_names)),
-            'roofline': roofline,
-            'roofline_hbm': roofline_hbm,
+            'roofline': full.get('roofline'),
+            'roofline_hbm': full.get('roofline_hbm'),
             'loop': {'ms_per_eval': loop_ms / evals_per_step, 'executed_tflop_per_eval': eps_flops / 1e12,
                      'mfma_tflops_whole_loop': loop_tflops, 'mfma_frac_whole_loop': loop_tflops / PEAK_BF16_TFLOPS,
                      'launches_per_eval': eng.step_launches(use_graph=bool(args.graph), cfg=bool(args.cfg)) / (2 if args.cfg else 1), 'launches_per_step': eng.step_launches(use_graph=bool(args.graph), cfg=bool(args.cfg)),
@@ -458,14 +508,15 @@ def main():
                      'launches_per_standalone_eps': eng.eps_launches(),
                      'device_gb': eng.device_bytes() / 1e9,
                      'hipgraph': bool(args.graph), 'vae_decode': bool(args.decode),
-                     'vae_decode_tflop_per_batch': eng.decode_flops() / 1e12 if args.decode else None,
-                     # what the cache hierarchy moves per evaluation (committed PMC summaries of the default workload)
-                     'l2_traffic': (lambda t: None if t is None else dict(t, tb_per_s_over_the_loop=t['gb_per_eval'] / (loop_ms / evals_per_step)))(
-                         l2_traffic_per_eval(config_tag(args), prof.get('attention', {}).get('launches', 0)))},
-            'kernel_classes_ms_per_eval': {k: round(v['ms'], 4) for k, v in prof.items() if v['ms'] > 0},
-            # the same classes with their launches replayed back to back between one event pair (no per-launch event overhead)
-            'kernel_classes_ms_per_eval_back_to_back': {k: round(v['ms_b2b'], 4) for k, v in prof.items() if v['ms_b2b'] > 0},
+                     'vae_decode_tflop_per_batch': eng.decode_flops() / 1e12 if args.decode else None},
         }
+        if args.full:
+            # what the cache hierarchy moves per evaluation (committed PMC summaries of the default workload)
+            result['loop']['l2_traffic'] = (lambda t: None if t is None else dict(t, tb_per_s_over_the_loop=t['gb_per_eval'] / (loop_ms / evals_per_step)))(
+                l2_traffic_per_eval(config_tag(args), full['prof'].get('attention', {}).get('launches', 0)))
+            result['kernel_classes_ms_per_eval'] = {k: round(v['ms'], 4) for k, v in full['prof'].items() if v['ms'] > 0}
+            # the same classes with their launches replayed back to back between one event pair (no per-launch event overhead)
+            result['kernel_classes_ms_per_eval_back_to_back'] = {k: round(v['ms_b2b'], 4) for k, v in full['prof'].items() if v['ms_b2b'] > 0}
         if want_cpu:
             eng.prepare(hint[:1], ctx[:1])
             g1 = eng.eps(x_T[:1], torch.tensor([981], device=dev))

@@ -91,7 +91,7 @@ def test_bench_self_launches_two_ranks_on_one_card_in_rehearsal_mode():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR')}
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '0', '--ddim-steps', '2',
-                        '--batch', '2', '--no-cpu-baseline'], capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
+                        '--batch', '2', '--full', '--no-cpu-baseline'], capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout
@@ -127,7 +127,7 @@ def test_rccl_group_of_one_on_the_card():
     assert r.returncode == 0 and 'RCCL_OK' in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
     env['MASTER_PORT'] = str(mdist.free_port())
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '1', '--warmup', '0', '--ddim-steps', '2',
-                        '--batch', '2', '--no-cpu-baseline', '--live-pmc', '0'], capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
+                        '--batch', '2', '--full', '--no-cpu-baseline', '--live-pmc', '0'], capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout
@@ -146,7 +146,7 @@ def test_bench_measures_its_hbm_counters_live():
         pytest.skip('rocprofv3 not installed')
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR')}
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '1', '--warmup', '0', '--ddim-steps', '2', '--batch', '2',
-                        '--no-cpu-baseline', '--decode', '0', '--live-pmc', '1'], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
+                        '--full', '--no-cpu-baseline', '--decode', '0', '--live-pmc', '1'], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
     for key in ('roofline', 'roofline_hbm'):
@@ -155,3 +155,29 @@ def test_bench_measures_its_hbm_counters_live():
         assert out[key]['traffic'] > 0
     h = out['roofline_hbm']
     assert 0.2 * h["bytes_per_launch"] < h["traffic"] < 8 * h["bytes_per_launch"], h
+
+
+def test_plain_bench_run_reports_the_headline_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, reports the headline and nothing that needs work of its own
+    (no per-kernel classes, rooflines or CPU baseline), and --dump-outputs writes the images of its last timed step.  Two runs with
+    the same arguments get the same inputs, so their outputs agree."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR')}
+    imgs = []
+    for run in ('a', 'b'):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--ddim-steps', '2',
+                            '--batch', '2', '--dump-outputs', str(tmp_path / run)], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out['steps'] == 2 and out['warmup'] == 1 and out['unit'] == 'images/s' and out['higher_is_better'] is True
+        assert out['dtype'] == 'bf16' and out['value'] > 0 and out['ms_per_step'] > 0
+        assert abs(out['value'] * out['ms_per_step'] / 1e3 - out['config']['global_batch']) < 1e-6 * out['config']['global_batch']
+        assert out['roofline'] is None and out['roofline_hbm'] is None and out['cpu_baseline'] is None
+        assert 'kernel_classes_ms_per_eval' not in out and 'l2_traffic' not in out['loop']
+        assert sorted(os.listdir(tmp_path / run)) == ['images.npy']
+        a = np.load(tmp_path / run / 'images.npy')
+        assert a.dtype == np.float32 and a.shape == (2, 3, 256, 256) and np.isfinite(a).all() and a.std() > 0
+        imgs.append(a)
+    assert np.linalg.norm(imgs[0] - imgs[1]) <= 1e-3 * np.linalg.norm(imgs[1])

@@ -420,3 +420,29 @@ def test_multi_entry_cond_lists_are_concatenated_once_per_distinct_set():
     m.reset_conditioning_cache()
     m.apply_model(x, t, {'c_crossattn': [a], 'c_concat': [r]})
     assert len(eng.prepared) == 4
+
+
+# ---- bench.py --dump-outputs ------------------------------------------------------------------------------------
+def test_bench_dump_outputs_writes_float32_within_the_size_cap(tmp_path):
+    """bench.py --dump-outputs: what one step returns, as float32 .npy; a larger output becomes a fixed seeded sample of whole
+    samples (same rows every run) with their batch indices, and all files together stay under 64 MB."""
+    sys.path.insert(0, ROOT)
+    import bench
+    out = torch.randn(6, 3, 8, 8, generator=torch.Generator().manual_seed(0))
+    files = bench.dump_outputs(out, 'images', str(tmp_path / 'small'))
+    assert files == {'images.npy': [6, 3, 8, 8]}
+    got = np.load(tmp_path / 'small' / 'images.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, out.numpy())
+    cap = 4 * 3 * 8 * 8 * 4 + 100                                          # room for four samples
+    for run in ('a', 'b'):
+        files = bench.dump_outputs(out.double(), 'images', str(tmp_path / run), max_bytes=cap)
+        assert files == {'images_index.npy': [4], 'images.npy': [4, 3, 8, 8]}
+    idx = np.load(tmp_path / 'a' / 'images_index.npy')
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.load(tmp_path / 'b' / 'images_index.npy'))
+    assert np.all(np.diff(idx) > 0) and idx.min() >= 0 and idx.max() < 6
+    got = np.load(tmp_path / 'a' / 'images.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, out[torch.as_tensor(idx.astype(np.int64))].numpy())
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in os.listdir(tmp_path / 'a')) <= cap + 2 * 128   # (+ .npy headers)
+    files = bench.dump_outputs(out, 'images', str(tmp_path / 'flat'), max_bytes=600)                     # one sample alone is too large
+    assert files == {'images_index.npy': [50], 'images.npy': [50]}
+    assert bench.DUMP_MAX_BYTES + 2 * 128 <= 64_000_000

@@ -34,7 +34,7 @@ def test_tuned_table_merge_rules(tmp_path, monkeypatch):
     assert rows == ['{64, 1280, 1280, 0, 0, 0, 19, 4},', '{128, 640, 640, 0, 0, 0, 16, 1},']
 
 
-def test_committed_table_matches_its_sources():
+def test_committed_table_matches_its_sources(tmp_path):
     """gemm_tuned.inc is reproducible from the committed sweep files (profiles/tune/*.json)."""
     import glob
     srcs = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'tune', '*.json')))
@@ -42,12 +42,12 @@ def test_committed_table_matches_its_sources():
     env = dict(os.environ)
     r = subprocess.run([sys.executable, '-c', (
         'import sys, os; sys.path.insert(0, %r); import gen_tuned_table as g; g.OUT = os.devnull if False else %r; '
-        'sys.argv = ["x"] + %r; g.main()') % (os.path.join(ROOT, 'tools'), '/tmp/_mkd_table_check.inc', srcs)],
+        'sys.argv = ["x"] + %r; g.main()') % (os.path.join(ROOT, 'tools'), str(tmp_path / 'table.inc'), srcs)],
         capture_output=True, text=True, env=env)
     assert r.returncode == 0, r.stderr
     strip = lambda t: [l.split('//')[0].strip() for l in t.splitlines() if l.startswith('{')]
     have = strip(open(os.path.join(ROOT, 'makeupdiffuse_amd', 'csrc', 'gemm_tuned.inc')).read())
-    want = strip(open('/tmp/_mkd_table_check.inc').read())
+    want = strip((tmp_path / 'table.inc').read_text())
     assert have == want
 
 

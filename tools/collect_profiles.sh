@@ -18,7 +18,7 @@ src = b''.join(open('makeupdiffuse_amd/csrc/' + f, 'rb').read() for f in ('engin
 print(json.dumps({'commit': '${MKD_HEAD:-unknown}', 'utc': time.strftime('%Y-%m-%dT%H:%M:%SZ', time.gmtime()), 'csrc_sha256_16': hashlib.sha256(src).hexdigest()[:16],
                   'bench_args': '${EXTRA}', 'commands': 'tools/collect_profiles.sh (rocprofv3 --kernel-trace --stats of bench.py; one --pmc pass per counter set, kernel-trace only)'}))
 PY
-BENCH="bench.py --steps 2 --warmup 1 --no-cpu-baseline --graph 0 $EXTRA"
+BENCH="bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --graph 0 $EXTRA"
 rm -rf /tmp/prof_stats
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o p -- python3 $BENCH > $OUT/${R}_rocprof_run_${TAG}.log 2>&1
 F=$(find /tmp/prof_stats -name 'p_kernel_stats.csv' | head -1); cp "$F" $OUT/${R}_kernel_stats_bench_${TAG}.csv
@@ -26,7 +26,7 @@ grep "^{" $OUT/${R}_rocprof_run_${TAG}.log | tail -1 > $OUT/${R}_bench_line_unde
 pmc() {  # name, counters...
   local name=$1; shift
   rm -rf /tmp/prof_$name
-  rocprofv3 --kernel-trace --output-format csv --pmc "$@" -d /tmp/prof_$name -o p -- python3 bench.py --steps 1 --warmup 0 --ddim-steps 4 --no-cpu-baseline --graph 0 --decode 0 $EXTRA > /tmp/prof_$name.log 2>&1
+  rocprofv3 --kernel-trace --output-format csv --pmc "$@" -d /tmp/prof_$name -o p -- python3 bench.py --full --steps 1 --warmup 0 --ddim-steps 4 --no-cpu-baseline --graph 0 --decode 0 $EXTRA > /tmp/prof_$name.log 2>&1
   local D=$(dirname $(find /tmp/prof_$name -name 'p_counter_collection.csv' | head -1))
   python3 tools/summarize_prof.py "$D" p --out $OUT/${R}_pmc_${name}_${TAG}.csv
   echo "pmc $name done"
@@ -39,8 +39,8 @@ if [ -z "$LIGHT" ]; then
   pmc lds_wait SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE
   # stream timeline of the eager 2-stream loop: queue busy / overlap / gaps (tools/timeline.py)
   rm -rf /tmp/prof_tl
-  rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_tl -o p -- python3 bench.py --steps 1 --warmup 1 --ddim-steps 10 --no-cpu-baseline --graph 0 --decode 0 $EXTRA > /tmp/prof_tl.log 2>&1
+  rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_tl -o p -- python3 bench.py --full --steps 1 --warmup 1 --ddim-steps 10 --no-cpu-baseline --graph 0 --decode 0 $EXTRA > /tmp/prof_tl.log 2>&1
   python3 tools/timeline.py $(find /tmp/prof_tl -name 'p_kernel_trace.csv' | head -1) --out $OUT/${R}_timeline_eager_${TAG}.txt > /dev/null
-  python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --graph 0 --decode 0 $EXTRA --ops-csv $OUT/${R}_ops_per_launch_${TAG}.csv > /dev/null 2>&1
+  python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --graph 0 --decode 0 $EXTRA --ops-csv $OUT/${R}_ops_per_launch_${TAG}.csv > /dev/null 2>&1
 fi
 ls -la $OUT

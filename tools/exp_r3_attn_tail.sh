@@ -8,5 +8,5 @@ for i in 1 2; do
 done
 for i in 1 2; do for v in default tail; do
 if [ $v = tail ]; then export MKD_LIB_PATH=$PWD/makeupdiffuse_amd/libmkd_tail.so; else unset MKD_LIB_PATH; fi
-python bench.py --steps 3 --warmup 1 --no-cpu-baseline --decode 0 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); k=d['kernel_classes_ms_per_eval']; print('$v', round(d['value'],3), 'ms/eval', round(d['loop']['ms_per_eval'],3), 'attention serial ms', k.get('attention'))"
+python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --decode 0 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); k=d['kernel_classes_ms_per_eval']; print('$v', round(d['value'],3), 'ms/eval', round(d['loop']['ms_per_eval'],3), 'attention serial ms', k.get('attention'))"
 done; done
