@@ -74,7 +74,8 @@ void mkd_ctx_destroy(mkd_ctx* ctx);
 int mkd_load_weight(mkd_ctx* ctx, const char* name, const float* data, int ndim, const int64_t* shape);
 /* Checks every expected tensor was loaded, builds fused/packed weights. Synchronous. */
 int mkd_weights_finalize(mkd_ctx* ctx);
-/* Number of parameters expected (for the 859.5 M / 361.3 M check); which: 0 unet, 1 control. */
+/* Number of parameters expected (for the 859.5 M / 361.3 M check); which: 0 unet, 1 control, 2 first-stage decoder,
+ * 3 text encoder, 4 first-stage encoder. */
 int64_t mkd_param_count(const mkd_ctx* ctx, int which);
 /* Enumerate the expected state_dict entries (sorted by name): count, name, shape (returns ndim <= 4). */
 int mkd_param_total(const mkd_ctx* ctx);
@@ -139,7 +140,11 @@ int mkd_ddim_step(const float* x, const float* eps_c, const float* eps_u, float 
  * Tables are host arrays of length n_steps indexed like ddim_alphas[index]; the loop runs
  * index = n_steps-1 .. 0 with timestep = timesteps[index].  x_T, x_out: [B,4,h,w] fp32.
  * use_graph != 0 captures one step into a hipGraph and replays it; such a call first waits (host) until the previous
- * graph-replayed loop of this context has finished, see "host synchronisation points" above. */
+ * graph-replayed loop of this context has finished, see "host synchronisation points" above.
+ * DDIM inversion (UPSTREAM DDIMSampler.encode, eta 0) is the same update with a_t := ddim_alphas_prev[i] and
+ * a_prev := ddim_alphas[i], executed in increasing i: pass MIRRORED tables, entry j = inversion step t_enc-1-j with
+ * timesteps = ddim_timesteps, alphas = ddim_alphas_prev, alphas_prev = ddim_alphas, sqrt_one_minus = sqrt(1 - ddim_alphas_prev)
+ * (makeupdiffuse_amd/ddim.py DDIMSampler.encode is the one place that builds them). */
 int mkd_sample(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps,
                const float* alphas, const float* alphas_prev, const float* sqrt_one_minus_alphas,
                float cfg_scale, float* x_out, int use_graph, void* stream);
@@ -174,6 +179,23 @@ int mkd_vae_finalize(mkd_ctx* ctx);
  * post_quant_conv -> Decoder.  z [B,4,h,w] fp32 NCHW -> images [B,3,8h,8w] fp32 NCHW (unclamped, nominally [-1,1]). */
 int mkd_decode(mkd_ctx* ctx, const float* z, int batch, int h, int w, float scale_factor, float* images, void* stream);
 double mkd_decode_flops(const mkd_ctx* ctx);
+
+/* ---- first-stage encoder ----------------------------------------------------------------------- */
+/* Opt-in (a context that only calls mkd_vae_configure expects no encoder key).  Adds "first_stage_model.encoder.*" and
+ * "first_stage_model.quant_conv.*" (upstream names) to the expected state_dict; the encoder's input is the yaml's fixed
+ * in_channels 3.  Uses ch, ch_mult, n_levels, num_res_blocks, z_channels (4) and embed_dim (4) of `cfg`; out_ch is ignored.
+ * Encoder weights are mkd_param_count's which = 4; loading one invalidates the encoder's finalize only. */
+int mkd_vae_encoder_configure(mkd_ctx* ctx, const mkd_vae_config* cfg);
+int mkd_vae_encoder_finalize(mkd_ctx* ctx);
+/* Replaces get_first_stage_encoding(encode_first_stage(x)) (diffmk/makeup_diffuse.py get_z): Encoder -> quant_conv ->
+ * DiagonalGaussianDistribution -> sample() (noise != NULL: mean + exp(0.5 clamp(logvar, -30, 20)) * noise) or mode() (noise NULL)
+ * -> x scale_factor.  images [B,3,H,W] fp32 NCHW (caller's range, upstream feeds [-1,1]); noise [B,4,H/8,W/8] fp32 device or NULL;
+ * z_out [B,4,H/f,W/f] and moments_out [B,8,H/f,W/f] fp32 NCHW (f = 2^(n_levels-1)), each may be NULL but not both.
+ * H, W must be multiples of f (else MKD_ERR_ARG); MKD_ERR_STATE when the encoder is not configured.  Its workspace is its own:
+ * encoding never moves the decoder's. */
+int mkd_encode(mkd_ctx* ctx, const float* images, int batch, int H, int W, float scale_factor, const float* noise, float* z_out,
+               float* moments_out, void* stream);
+double mkd_encode_flops(const mkd_ctx* ctx);
 
 /* ---- CLIP text encoder -------------------------------------------------- */
 /* yaml cond_stage_config FrozenCLIPEmbedder (diffmodels/base_diffusion_makeup.yaml:109-110), i.e. UPSTREAM transformers
@@ -239,6 +261,11 @@ int mkd_gemm_bf16(const uint16_t* A, int lda, const uint16_t* W, int ldw, const 
                   void* C, int ldc, int out_f32, int M, int N, int K,
                   int conv3x3, int batch, int Hin, int Win, int Cin, int Hout, int Wout,
                   int stride, int up, int splitk, void* stream);
+/* The VAE encoder's Downsample on the gather kernel: y = conv3x3(F.pad(x, (0,1,0,1)), stride 2, pad 0) + bias.  x NHWC
+ * [B,H,W,Cin] (pixel stride ldx), H and W even; w_packed [Cout][3][3][Cin] (mkd_pack_conv_weight); y NHWC [B,H/2,W/2,Cout]
+ * (pixel stride ldy).  splitk 0 = auto. */
+int mkd_conv3x3_down_bf16(const uint16_t* x, int ldx, const uint16_t* w_packed, const float* bias, uint16_t* y, int ldy,
+                          int batch, int H, int W, int Cin, int Cout, int splitk, void* stream);
 /* LayerNorm fused into a linear GEMM: C = act(LN(A) . W^T + b) computed as rstd*(A.W'^T - mu*s) + b' on the RAW rows of A.
  * mkd_fold_layernorm builds W' = bf16(W*gamma) (written to rows dst_row0 + n*dst_row_mul of w_out), s = rowsum(W'),
  * b' = bias + W.beta from fp32 W [N,K] (device).  mkd_gemm_ln_bf16 runs the fused GEMM (no split-K).  row_stats == NULL (the

@@ -260,6 +260,14 @@ struct mkd_ctx {
     std::vector<Op> plan_vae; int vae_B = 0, vae_h = 0, vae_w = 0;
     const float* io_z = nullptr; float* io_img = nullptr; float io_inv_scale = 1.f;
     double flops_vae = 0;
+    // ---- first-stage encoder (AutoencoderKL.encode + get_first_stage_encoding), opt-in; weights are `which` 4.  Its own arena: the
+    // decoder plan holds pointers into varena, which an encoder growing that buffer would free under it ----
+    bool venc_configured = false, venc_finalized = false;
+    Arena earena; char* earena_base = nullptr; size_t earena_cap = 0;
+    std::vector<Op> plan_venc; int venc_B = 0, venc_H = 0, venc_W = 0;
+    const float* io_enc_img = nullptr; const float* io_enc_noise = nullptr; float* io_enc_z = nullptr; float* io_enc_mom = nullptr;
+    float io_enc_scale = 1.f;
+    double flops_venc = 0;
     // per-call io
     const float* io_x = nullptr; const int64_t* io_t = nullptr; float* io_out = nullptr;
     // sampler buffers
@@ -490,7 +498,8 @@ struct mkd_ctx {
         if (rc) return rc;
         if (e != hipSuccess) return mkd_fail(MKD_ERR_HIP, std::string("load_weight sync: ") + hipGetErrorString(e));
         p.loaded = true;
-        if (p.which == 2) vae_finalized = false; else if (p.which == 3) clip_finalized = false; else { finalized = false; prepared = false; }
+        if (p.which == 2) vae_finalized = false; else if (p.which == 3) clip_finalized = false; else if (p.which == 4) venc_finalized = false;
+        else { finalized = false; prepared = false; }
         return 0;
     }
 
@@ -750,17 +759,18 @@ struct mkd_ctx {
         op_gemm(a, force_splitk);
     }
     // 3x3 conv, pad 1
-    void op_conv(const Tensor& in, const bf16_t* W, int N, int stride, int up, const Epi& e, bf16_t* C, int ldc) {
-        op_gemm(conv_args(in, W, N, stride, up, e, C, ldc));
+    // pad_tl 0: the VAE encoder's Downsample (pad bottom / right only, stride 2; GemmArgs::pad_tl).  Even H, W: the same H/2 x W/2 grid
+    void op_conv(const Tensor& in, const bf16_t* W, int N, int stride, int up, const Epi& e, bf16_t* C, int ldc, int pad_tl = 1) {
+        op_gemm(conv_args(in, W, N, stride, up, e, C, ldc, pad_tl));
     }
-    GemmArgs conv_args(const Tensor& in, const bf16_t* W, int N, int stride, int up, const Epi& e, bf16_t* C, int ldc) {
+    GemmArgs conv_args(const Tensor& in, const bf16_t* W, int N, int stride, int up, const Epi& e, bf16_t* C, int ldc, int pad_tl = 1) {
         GemmArgs a; memset(&a, 0, sizeof(a));
         const int Hs = in.H << up, Ws = in.W << up;
         const int Ho = (Hs - 1) / stride + 1, Wo = (Ws - 1) / stride + 1;
         a.A = in.p; a.lda = in.ld; a.W = W; a.ldw = 9 * in.C; a.bias = e.bias; a.rowbias = e.rowbias; a.ldrb = e.ldrb;
         a.rows_per_batch = e.rpb; a.R = e.R; a.ldr = e.ldr; a.scale = e.scale; a.act = e.act;
         a.C = C; a.ldc = ldc; a.out_f32 = 0; a.M = in.B * Ho * Wo; a.N = N; a.K = 9 * in.C; a.conv = 1;
-        a.Hin = in.H; a.Win = in.W; a.Cin = in.C; a.Hout = Ho; a.Wout = Wo; a.stride = stride; a.up = up;
+        a.Hin = in.H; a.Win = in.W; a.Cin = in.C; a.Hout = Ho; a.Wout = Wo; a.stride = stride; a.up = up; a.pad_tl = pad_tl;
         a.gn_stat = e.gn.gst; a.gn_cg = e.gn.cg; a.gn_coff = e.gn.coff; a.gn_hw = e.gn.hw;
         return a;
     }
@@ -2039,12 +2049,12 @@ struct mkd_ctx {
     // first-stage decoder
     // ---------------------------------------------------------------------------------------------------------------
     static std::string vae_prefix() { return "first_stage_model."; }
-    void vae_add_res(const std::string& p, int cin, int cout) {
-        add_param(p + ".norm1.weight", {cin}, 2); add_param(p + ".norm1.bias", {cin}, 2);
-        add_param(p + ".conv1.weight", {cout, cin, 3, 3}, 2); add_param(p + ".conv1.bias", {cout}, 2);
-        add_param(p + ".norm2.weight", {cout}, 2); add_param(p + ".norm2.bias", {cout}, 2);
-        add_param(p + ".conv2.weight", {cout, cout, 3, 3}, 2); add_param(p + ".conv2.bias", {cout}, 2);
-        if (cin != cout) { add_param(p + ".nin_shortcut.weight", {cout, cin, 1, 1}, 2); add_param(p + ".nin_shortcut.bias", {cout}, 2); }
+    void vae_add_res(const std::string& p, int cin, int cout, int which = 2) {
+        add_param(p + ".norm1.weight", {cin}, which); add_param(p + ".norm1.bias", {cin}, which);
+        add_param(p + ".conv1.weight", {cout, cin, 3, 3}, which); add_param(p + ".conv1.bias", {cout}, which);
+        add_param(p + ".norm2.weight", {cout}, which); add_param(p + ".norm2.bias", {cout}, which);
+        add_param(p + ".conv2.weight", {cout, cout, 3, 3}, which); add_param(p + ".conv2.bias", {cout}, which);
+        if (cin != cout) { add_param(p + ".nin_shortcut.weight", {cout, cin, 1, 1}, which); add_param(p + ".nin_shortcut.bias", {cout}, which); }
     }
     int vae_configure(const mkd_vae_config* c) {
         if (vae_configured) return mkd_fail(MKD_ERR_STATE, "mkd_vae_configure: already configured");
@@ -2087,7 +2097,13 @@ struct mkd_ctx {
             MKD_HIP_CHECK(hipMemset(z, 0, 4096));
             zero_page = (bf16_t*)z;
         }
-        const std::string A = vae_prefix() + "decoder.mid.attn_1";
+        int rc = vae_fuse_attn(vae_prefix() + "decoder.mid.attn_1"); if (rc) return rc;
+        MKD_HIP_CHECK(hipDeviceSynchronize());
+        vae_finalized = true;
+        return 0;
+    }
+    // the mid attention's fused [Wq;Wk] (+ bias) of the decoder or the encoder
+    int vae_fuse_attn(const std::string& A) {
         bf16_t* qk = nullptr;
         int rc = concat_rows(&qk, {A + ".q.weight", A + ".k.weight"}); if (rc) return rc;
         vae_fused[A] = qk;
@@ -2097,15 +2113,14 @@ struct mkd_ctx {
         MKD_HIP_CHECK(hipMemcpy(b, params.at(A + ".q.bias").dev, c * sizeof(float), hipMemcpyDeviceToDevice));
         MKD_HIP_CHECK(hipMemcpy((float*)b + c, params.at(A + ".k.bias").dev, c * sizeof(float), hipMemcpyDeviceToDevice));
         vae_fused_b[A] = (float*)b;
-        MKD_HIP_CHECK(hipDeviceSynchronize());
-        vae_finalized = true;
         return 0;
     }
 
     // VAE ResnetBlock: GN(eps 1e-6)+SiLU -> conv3x3 -> GN+SiLU -> conv3x3 (+ x or nin_shortcut(x))
-    void vae_resblock(const std::string& p, const Tensor& x, int cout, bf16_t* out) {
-        const size_t mk = varena.mark();
-        auto tal = [&](int C_) { Tensor t = x; t.C = C_; t.ld = C_; t.p = (bf16_t*)varena.alloc((size_t)x.rows() * C_ * sizeof(bf16_t)); return t; };
+    // (ar: the arena of the plan being built - the decoder's varena or the encoder's earena)
+    void vae_resblock(Arena& ar, const std::string& p, const Tensor& x, int cout, bf16_t* out) {
+        const size_t mk = ar.mark();
+        auto tal = [&](int C_) { Tensor t = x; t.C = C_; t.ld = C_; t.p = (bf16_t*)ar.alloc((size_t)x.rows() * C_ * sizeof(bf16_t)); return t; };
         Tensor t1 = tal(x.C);
         op_gn(x, wf(p + ".norm1.weight"), wf(p + ".norm1.bias"), 1e-6f, 1, t1.p, t1.ld);
         Tensor t2 = tal(cout);
@@ -2120,14 +2135,14 @@ struct mkd_ctx {
             e2.R = t4.p; e2.ldr = t4.ld;
         } else { e2.R = x.p; e2.ldr = x.ld; }
         op_conv(t3, wb(p + ".conv2.weight"), cout, 1, 0, e2, out, cout);
-        varena.release(mk);
+        ar.release(mk);
     }
 
     // single-head attention over the hw tokens of each sample, built from GEMMs (c = 512 does not fit the flash kernel)
-    void vae_attn(const std::string& p, const Tensor& x, bf16_t* out) {
-        const size_t mk = varena.mark();
+    void vae_attn(Arena& ar, const std::string& p, const Tensor& x, bf16_t* out) {
+        const size_t mk = ar.mark();
         const int c = x.C, T = x.H * x.W, M = x.rows();
-        auto buf = [&](size_t n) { return (bf16_t*)varena.alloc(n * sizeof(bf16_t)); };
+        auto buf = [&](size_t n) { return (bf16_t*)ar.alloc(n * sizeof(bf16_t)); };
         bf16_t* g = buf((size_t)M * c);
         op_gn(x, wf(p + ".norm.weight"), wf(p + ".norm.bias"), 1e-6f, 0, g, c);
         bf16_t* qk = buf((size_t)M * 2 * c);
@@ -2154,7 +2169,7 @@ struct mkd_ctx {
             op_linear(pr + (size_t)b * T * T, T, T, T, vt + (size_t)b * c * T, c, e, o + (size_t)b * T * c, c);
         }
         { Epi e; e.bias = wf(p + ".proj_out.bias"); e.R = x.p; e.ldr = x.ld; op_linear(o, c, M, c, wb(p + ".proj_out.weight"), c, e, out, c); }
-        varena.release(mk);
+        ar.release(mk);
     }
 
     void build_vae_plan(int Bn, int hh, int ww) {
@@ -2192,14 +2207,14 @@ struct mkd_ctx {
                 2.0 * Bn * hh * ww * bi * 9 * zc, K_CONV_DIRECT);
         }
         auto step = [&](int cout) { cur ^= 1; Tensor o = h; o.C = cout; o.ld = cout; o.p = X[cur]; return o; };
-        { Tensor o = step(bi); vae_resblock(D + "mid.block_1", h, bi, o.p); h = o; }
-        { Tensor o = step(bi); vae_attn(D + "mid.attn_1", h, o.p); h = o; }
-        { Tensor o = step(bi); vae_resblock(D + "mid.block_2", h, bi, o.p); h = o; }
+        { Tensor o = step(bi); vae_resblock(varena, D + "mid.block_1", h, bi, o.p); h = o; }
+        { Tensor o = step(bi); vae_attn(varena, D + "mid.attn_1", h, o.p); h = o; }
+        { Tensor o = step(bi); vae_resblock(varena, D + "mid.block_2", h, bi, o.p); h = o; }
         for (int lvl = vcfg.n_levels - 1; lvl >= 0; --lvl) {
             const int bo = vcfg.ch * vcfg.ch_mult[lvl];
             for (int j = 0; j <= vcfg.num_res_blocks; ++j) {
                 Tensor o = step(bo);
-                vae_resblock(D + "up." + std::to_string(lvl) + ".block." + std::to_string(j), h, bo, o.p);
+                vae_resblock(varena, D + "up." + std::to_string(lvl) + ".block." + std::to_string(j), h, bo, o.p);
                 h = o;
             }
             if (lvl != 0) {
@@ -2244,6 +2259,142 @@ struct mkd_ctx {
         return 0;
     }
 
+
+    // ---------------------------------------------------------------------------------------------------------------
+    // first-stage encoder (UPSTREAM ldm Encoder + AutoencoderKL.quant_conv; yaml ddconfig with in_channels 3, double_z)
+    // ---------------------------------------------------------------------------------------------------------------
+    int venc_configure(const mkd_vae_config* c) {
+        if (venc_configured) return mkd_fail(MKD_ERR_STATE, "mkd_vae_encoder_configure: already configured");
+        if (c->n_levels < 1 || c->n_levels > 8 || c->ch % 32 || c->z_channels != 4 || c->embed_dim != 4 || c->num_res_blocks < 1)
+            return mkd_fail(MKD_ERR_UNSUPPORTED, "mkd_vae_encoder_configure: unsupported encoder configuration");
+        for (int i = 0; i < c->n_levels; ++i)
+            if (c->ch_mult[i] < 1) return mkd_fail(MKD_ERR_UNSUPPORTED, "mkd_vae_encoder_configure: ch_mult entries must be >= 1");
+        ecfg = *c;
+        const std::string P = vae_prefix(), E = P + "encoder.";
+        const int W4 = 4;
+        add_param(E + "conv_in.weight", {c->ch, 3, 3, 3}, W4); add_param(E + "conv_in.bias", {c->ch}, W4);
+        int bi = c->ch;
+        for (int lvl = 0; lvl < c->n_levels; ++lvl) {
+            const int bo = c->ch * c->ch_mult[lvl];
+            const std::string L = E + "down." + std::to_string(lvl);
+            for (int j = 0; j < c->num_res_blocks; ++j) { vae_add_res(L + ".block." + std::to_string(j), bi, bo, W4); bi = bo; }
+            if (lvl != c->n_levels - 1) { add_param(L + ".downsample.conv.weight", {bi, bi, 3, 3}, W4); add_param(L + ".downsample.conv.bias", {bi}, W4); }
+        }
+        vae_add_res(E + "mid.block_1", bi, bi, W4);
+        for (const char* n : {"q", "k", "v", "proj_out"}) {
+            add_param(E + "mid.attn_1." + n + ".weight", {bi, bi, 1, 1}, W4); add_param(E + "mid.attn_1." + n + ".bias", {bi}, W4);
+        }
+        add_param(E + "mid.attn_1.norm.weight", {bi}, W4); add_param(E + "mid.attn_1.norm.bias", {bi}, W4);
+        vae_add_res(E + "mid.block_2", bi, bi, W4);
+        add_param(E + "norm_out.weight", {bi}, W4); add_param(E + "norm_out.bias", {bi}, W4);
+        add_param(E + "conv_out.weight", {2 * c->z_channels, bi, 3, 3}, W4); add_param(E + "conv_out.bias", {2 * c->z_channels}, W4);
+        add_param(P + "quant_conv.weight", {2 * c->embed_dim, 2 * c->z_channels, 1, 1}, W4); add_param(P + "quant_conv.bias", {2 * c->embed_dim}, W4);
+        venc_configured = true;
+        return 0;
+    }
+    mkd_vae_config ecfg{};
+    int venc_finalize() {
+        if (!venc_configured) return mkd_fail(MKD_ERR_STATE, "encoder not configured (mkd_vae_encoder_configure)");
+        for (auto& kv : params)
+            if (kv.second.which == 4 && !kv.second.loaded) return mkd_fail(MKD_ERR_MISSING, "weight not loaded: " + kv.first);
+        if (venc_finalized) return 0;
+        if (!zero_page) {
+            void* z = nullptr;
+            int rc = dev_alloc(&z, 4096); if (rc) return rc;
+            MKD_HIP_CHECK(hipMemset(z, 0, 4096));
+            zero_page = (bf16_t*)z;
+        }
+        int rc = vae_fuse_attn(vae_prefix() + "encoder.mid.attn_1"); if (rc) return rc;
+        MKD_HIP_CHECK(hipDeviceSynchronize());
+        venc_finalized = true;
+        venc_B = 0;                 // the plan holds pointers to the fused weights: rebuild it
+        return 0;
+    }
+
+    void build_venc_plan(int Bn, int H, int W) {
+        cur_plan = &plan_venc; cur_sid = SID_AUX; counting_eps = false;
+        mkd_ctx* self = this;
+        const std::string P = vae_prefix(), E = P + "encoder.";
+        // largest activation: full resolution x max(ch * ch_mult[0], ch) channels, then halved pixels per level
+        size_t max_act = 0;
+        {
+            int h = H, w = W, bi = ecfg.ch;
+            max_act = (size_t)Bn * h * w * bi;
+            for (int lvl = 0; lvl < ecfg.n_levels; ++lvl) {
+                const int bo = ecfg.ch * ecfg.ch_mult[lvl];
+                max_act = std::max(max_act, (size_t)Bn * h * w * std::max(bi, bo));
+                bi = bo;
+                if (lvl != ecfg.n_levels - 1) { h /= 2; w /= 2; }
+            }
+        }
+        bf16_t* X[2] = {(bf16_t*)earena.alloc(max_act * sizeof(bf16_t)), (bf16_t*)earena.alloc(max_act * sizeof(bf16_t))};
+        int cur = 0;
+        Tensor h; h.B = Bn; h.H = H; h.W = W; h.C = ecfg.ch; h.ld = ecfg.ch; h.p = X[cur];
+        {
+            const bf16_t* w_ = wb(E + "conv_in.weight"); const float* b_ = wf(E + "conv_in.bias"); bf16_t* dst = h.p; const int co = ecfg.ch;
+            push(*cur_plan, [self, w_, b_, dst, Bn, H, W, co](hipStream_t st) {
+                return launch_conv3x3_direct(self->io_enc_img, 1, w_, b_, dst, 0, 0, nullptr, Bn, H, W, 3, co, 1, st); }, 1,
+                2.0 * Bn * H * W * co * 9 * 3, K_CONV_DIRECT, "conv_in 3->" + std::to_string(co));
+        }
+        auto step = [&](int cout) { cur ^= 1; Tensor o = h; o.C = cout; o.ld = cout; o.p = X[cur]; return o; };
+        for (int lvl = 0; lvl < ecfg.n_levels; ++lvl) {
+            const int bo = ecfg.ch * ecfg.ch_mult[lvl];
+            const std::string L = E + "down." + std::to_string(lvl);
+            for (int j = 0; j < ecfg.num_res_blocks; ++j) {
+                Tensor o = step(bo);
+                vae_resblock(earena, L + ".block." + std::to_string(j), h, bo, o.p);
+                h = o;
+            }
+            if (lvl != ecfg.n_levels - 1) {          // Downsample: F.pad(x, (0,1,0,1)) + 3x3 stride-2 pad-0 conv
+                Tensor o = step(h.C); o.H = h.H / 2; o.W = h.W / 2;
+                Epi e; e.bias = wf(L + ".downsample.conv.bias");
+                op_conv(h, wb(L + ".downsample.conv.weight"), h.C, 2, 0, e, o.p, o.ld, /*pad_tl=*/0);
+                h = o;
+            }
+        }
+        { Tensor o = step(h.C); vae_resblock(earena, E + "mid.block_1", h, h.C, o.p); h = o; }
+        { Tensor o = step(h.C); vae_attn(earena, E + "mid.attn_1", h, o.p); h = o; }
+        { Tensor o = step(h.C); vae_resblock(earena, E + "mid.block_2", h, h.C, o.p); h = o; }
+        {
+            Tensor o = step(h.C);
+            op_gn(h, wf(E + "norm_out.weight"), wf(E + "norm_out.bias"), 1e-6f, 1, o.p, o.ld);
+            const bf16_t* w_ = wb(E + "conv_out.weight"); const float* b_ = wf(E + "conv_out.bias");
+            const bf16_t* wq = wb(P + "quant_conv.weight"); const float* bq = wf(P + "quant_conv.bias");
+            const int h2 = h.H, w2 = h.W, cin = h.C, zc = ecfg.z_channels;
+            push(*cur_plan, [self, o, w_, b_, wq, bq, Bn, h2, w2, cin, zc](hipStream_t st) {
+                return launch_vae_enc_tail(o.p, w_, b_, wq, bq, self->io_enc_noise, self->io_enc_scale, self->io_enc_z, self->io_enc_mom,
+                                           Bn, h2, w2, cin, zc, st); }, 1,
+                2.0 * Bn * h2 * w2 * 2 * zc * (9.0 * cin + 2 * zc), K_CONV_DIRECT, "enc_tail");
+        }
+    }
+
+    int encode(const float* images, int Bn, int H, int W, float scale_factor, const float* noise, float* z_out, float* moments_out,
+               hipStream_t stream) {
+        if (!venc_configured) return mkd_fail(MKD_ERR_STATE, "mkd_encode: encoder not configured (mkd_vae_encoder_configure)");
+        const int f = 1 << (ecfg.n_levels - 1);
+        if (!images || Bn <= 0 || H <= 0 || W <= 0 || H % f || W % f || (!z_out && !moments_out))
+            return mkd_fail(MKD_ERR_ARG, "mkd_encode: bad arguments (H, W must be multiples of " + std::to_string(f) + "; z_out or moments_out needed)");
+        if (!venc_finalized) { int rc = venc_finalize(); if (rc) return rc; }
+        if (Bn != venc_B || H != venc_H || W != venc_W) {
+            // two-pass scheme of mkd_decode on the encoder's own arena; split-K / GroupNorm workspaces of SID_AUX are shared (read at run time)
+            const size_t keep_sk = splitk_need, keep_gn = gn_need;
+            splitk_need = 0; gn_need = 0;
+            dry = true; earena.base = nullptr; earena.reset(); plan_venc.clear(); flops_venc = 0;
+            build_venc_plan(Bn, H, W);
+            int rc = ensure((void**)&earena_base, &earena_cap, earena.high + 256); if (rc) return rc;
+            rc = ensure((void**)&splitk_ws[SID_AUX], &splitk_ws_bytes[SID_AUX], std::max(splitk_need, splitk_ws_bytes[SID_AUX])); if (rc) return rc;
+            rc = ensure((void**)&gn_ws[SID_AUX], &gn_ws_bytes[SID_AUX], std::max(gn_need, gn_ws_bytes[SID_AUX])); if (rc) return rc;
+            splitk_need = keep_sk; gn_need = keep_gn;
+            dry = false; earena.base = earena_base; earena.reset(); plan_venc.clear();
+            build_venc_plan(Bn, H, W);
+            splitk_need = keep_sk; gn_need = keep_gn;
+            for (auto& op : plan_venc) flops_venc += op.flops;
+            venc_B = Bn; venc_H = H; venc_W = W;
+        }
+        io_enc_img = images; io_enc_noise = noise; io_enc_z = z_out; io_enc_mom = moments_out; io_enc_scale = scale_factor;
+        for (auto& op : plan_venc) { int rc = op.fn(stream); if (rc) return rc; }
+        return 0;
+    }
 
     // ---- CLIP text encoder ---------------------------------------------------------------
     // cond_stage_config FrozenCLIPEmbedder (reference diffmodels/base_diffusion_makeup.yaml:109-110; called through
@@ -2403,7 +2554,7 @@ struct mkd_ctx {
     }
 
     int64_t device_bytes() const {
-        return weight_bytes + (int64_t)varena_cap + (int64_t)carena_cap + (int64_t)persist_cap + (int64_t)gstat_cap + [&] { int64_t t = 0; for (int i = 0; i < NA; ++i) t += (int64_t)(temp_cap[i] + splitk_ws_bytes[i] + gn_ws_bytes[i]); return t; }();
+        return weight_bytes + (int64_t)varena_cap + (int64_t)earena_cap + (int64_t)carena_cap + (int64_t)persist_cap + (int64_t)gstat_cap + [&] { int64_t t = 0; for (int i = 0; i < NA; ++i) t += (int64_t)(temp_cap[i] + splitk_ws_bytes[i] + gn_ws_bytes[i]); return t; }();
     }
 
     ~mkd_ctx() {
@@ -2411,6 +2562,7 @@ struct mkd_ctx {
         for (void* p : derived) hipFree(p);
         if (gstat_base) hipFree(gstat_base);
         if (varena_base) hipFree(varena_base);
+        if (earena_base) hipFree(earena_base);
         if (carena_base) hipFree(carena_base);
         for (auto& kv : f32_keep) hipFree(kv.second);
         drop_graph();
@@ -2598,7 +2750,7 @@ int mkd_gemm_cfg_supported(int cfg, int M, int N, int K, int conv3x3, int Hin, i
     if (cfg < 0 || cfg >= gemm_num_tile_cfgs()) return 0;
     if (!((cfg >= 6 && cfg <= 11) || (cfg >= 38 && cfg <= 40) || cfg == 42 || cfg == 43)) return 1;          // (only the LDS-staged conv tiles depend on the geometry)
     GemmArgs a; memset(&a, 0, sizeof(a));
-    a.M = M; a.N = N; a.K = K; a.conv = conv3x3; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = Hout; a.Wout = Wout; a.stride = stride; a.up = up;
+    a.M = M; a.N = N; a.K = K; a.conv = conv3x3; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = Hout; a.Wout = Wout; a.stride = stride; a.up = up; a.pad_tl = 1;
     return conv_patch_supported(a, cfg) ? 1 : 0;
 }
 int mkd_kind_count(void) { return K_COUNT; }
@@ -2629,6 +2781,17 @@ int mkd_decode(mkd_ctx* ctx, const float* z, int batch, int h, int w, float scal
     return ctx->decode(z, batch, h, w, scale_factor, images, (hipStream_t)stream);
 }
 double mkd_decode_flops(const mkd_ctx* ctx) { return ctx ? ctx->flops_vae : 0.0; }
+int mkd_vae_encoder_configure(mkd_ctx* ctx, const mkd_vae_config* cfg) {
+    if (!ctx || !cfg) return mkd_fail(MKD_ERR_ARG, "mkd_vae_encoder_configure: null argument");
+    return ctx->venc_configure(cfg);
+}
+int mkd_vae_encoder_finalize(mkd_ctx* ctx) { return ctx ? ctx->venc_finalize() : mkd_fail(MKD_ERR_ARG, "null ctx"); }
+int mkd_encode(mkd_ctx* ctx, const float* images, int batch, int H, int W, float scale_factor, const float* noise, float* z_out,
+               float* moments_out, void* stream) {
+    if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
+    return ctx->encode(images, batch, H, W, scale_factor, noise, z_out, moments_out, (hipStream_t)stream);
+}
+double mkd_encode_flops(const mkd_ctx* ctx) { return ctx ? ctx->flops_venc : 0.0; }
 int mkd_clip_configure(mkd_ctx* ctx, const mkd_clip_config* cfg) {
     if (!ctx || !cfg) return mkd_fail(MKD_ERR_ARG, "mkd_clip_configure: null argument");
     return ctx->clip_configure(cfg);
@@ -2677,7 +2840,7 @@ static int gemm_entry(const uint16_t* A, int lda, const uint16_t* W, int ldw, co
     GemmArgs a; memset(&a, 0, sizeof(a));
     a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.bias = bias; a.rowbias = rowbias; a.ldrb = ldrb; a.rows_per_batch = rows_per_batch;
     a.R = R; a.ldr = ldr; a.scale = scale; a.act = act; a.C = C; a.ldc = ldc; a.out_f32 = out_f32; a.M = M; a.N = N; a.K = K;
-    a.conv = conv3x3 ? 1 : 0; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = Hout; a.Wout = Wout; a.stride = stride; a.up = up;
+    a.conv = conv3x3 ? 1 : 0; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = Hout; a.Wout = Wout; a.stride = stride; a.up = up; a.pad_tl = 1;
     a.zero = g_zero;
     a.gn_stat = gn_stat; a.gn_cg = gn_cg; a.gn_coff = gn_coff; a.gn_hw = gn_hw;
     a.splitk = splitk > 0 ? splitk : 0;
@@ -2696,6 +2859,27 @@ int mkd_gemm_bf16(const uint16_t* A, int lda, const uint16_t* W, int ldw, const 
     return gemm_entry(A, lda, W, ldw, bias, rowbias, ldrb, rows_per_batch, R, ldr, scale, act, C, ldc, out_f32, M, N, K, conv3x3, batch,
                       Hin, Win, Cin, Hout, Wout, stride, up, splitk, nullptr, 0, 0, 0, stream);
 }
+int mkd_conv3x3_down_bf16(const uint16_t* x, int ldx, const uint16_t* w_packed, const float* bias, uint16_t* y, int ldy, int batch, int H, int W,
+                          int Cin, int Cout, int splitk, void* stream) {
+    if (!x || !w_packed || !y) return mkd_fail(MKD_ERR_ARG, "mkd_conv3x3_down_bf16: null pointer");
+    if (batch <= 0 || H <= 0 || W <= 0 || H % 2 || W % 2) return mkd_fail(MKD_ERR_ARG, "mkd_conv3x3_down_bf16: H, W must be even");
+    if (!g_zero) {
+        MKD_HIP_CHECK(hipMalloc((void**)&g_zero, 4096));
+        MKD_HIP_CHECK(hipMemset(g_zero, 0, 4096));
+    }
+    GemmArgs a; memset(&a, 0, sizeof(a));
+    a.A = x; a.lda = ldx; a.W = w_packed; a.ldw = 9 * Cin; a.bias = bias; a.scale = 1.0f; a.C = y; a.ldc = ldy;
+    a.M = batch * (H / 2) * (W / 2); a.N = Cout; a.K = 9 * Cin; a.conv = 1;
+    a.Hin = H; a.Win = W; a.Cin = Cin; a.Hout = H / 2; a.Wout = W / 2; a.stride = 2; a.up = 0; a.pad_tl = 0;
+    a.zero = g_zero; a.splitk = splitk > 0 ? splitk : 0;
+    int cfg_i = 0, s = 1;
+    int rc = gemm_resolve(a, &cfg_i, &s);
+    if (rc) return rc;
+    rc = scratch(&g_ws, &g_ws_bytes, gemm_ws_bytes(a.M, Cout, s > 1 ? s : 2));
+    if (rc) return rc;
+    a.ws = g_ws; a.ws_bytes = g_ws_bytes;
+    return launch_gemm(a, (hipStream_t)stream);
+}
 int mkd_conv3x3_fold_bf16(const uint16_t* x, int ldx, const uint16_t* w_fold, const float* bias, const uint16_t* x2, int ldx2, int K2, uint16_t* y,
                           int ldy, int batch, int H, int W, int Cin, int N, int splitk, void* stream) {
     if (!x || !w_fold || !x2 || !y) return mkd_fail(MKD_ERR_ARG, "mkd_conv3x3_fold_bf16: null pointer");
@@ -2705,7 +2889,7 @@ int mkd_conv3x3_fold_bf16(const uint16_t* x, int ldx, const uint16_t* w_fold, co
     }
     GemmArgs a; memset(&a, 0, sizeof(a));
     a.A = x; a.lda = ldx; a.W = w_fold; a.ldw = 9 * Cin + K2; a.bias = bias; a.scale = 1.0f; a.C = y; a.ldc = ldy; a.M = batch * H * W; a.N = N;
-    a.K = 9 * Cin + K2; a.conv = 1; a.Hin = H; a.Win = W; a.Cin = Cin; a.Hout = H; a.Wout = W; a.stride = 1; a.up = 0;
+    a.K = 9 * Cin + K2; a.conv = 1; a.Hin = H; a.Win = W; a.Cin = Cin; a.Hout = H; a.Wout = W; a.stride = 1; a.up = 0; a.pad_tl = 1;
     a.A2 = x2; a.lda2 = ldx2; a.K2 = K2; a.zero = g_zero; a.splitk = splitk > 0 ? splitk : 0;
     int cfg_i = 0, s = 1;
     int rc = gemm_resolve(a, &cfg_i, &s);
@@ -2740,7 +2924,7 @@ int mkd_gemm_groupnorm_bf16(const uint16_t* A, int lda, const uint16_t* W, int l
     GemmArgs a; memset(&a, 0, sizeof(a));
     a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.bias = bias; a.rowbias = rowbias; a.ldrb = ldrb; a.rows_per_batch = rows_per_batch;
     a.R = R; a.ldr = ldr; a.scale = scale; a.act = 0; a.C = C; a.ldc = ldc; a.out_f32 = 0; a.M = M; a.N = N; a.K = K;
-    a.conv = conv3x3 ? 1 : 0; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = Hout; a.Wout = Wout; a.stride = stride; a.up = up;
+    a.conv = conv3x3 ? 1 : 0; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = Hout; a.Wout = Wout; a.stride = stride; a.up = up; a.pad_tl = 1;
     a.zero = g_zero; a.splitk = splitk > 0 ? splitk : 0;
     int cfg_i = 0, s = 1;
     int rc = gemm_resolve(a, &cfg_i, &s);

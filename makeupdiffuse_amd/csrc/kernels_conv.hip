@@ -428,7 +428,7 @@ static bool patch_cfg_shape(int cfg, int* tm, int* tn, int* nw) {
 }
 
 bool conv_patch_supported(const GemmArgs& a, int cfg) {
-    if (!a.conv || a.stride != 1 || a.up != 0 || a.Cin % 64 || a.Hin != a.Hout || a.Win != a.Wout) return false;
+    if (!a.conv || a.stride != 1 || a.up != 0 || a.pad_tl != 1 || a.Cin % 64 || a.Hin != a.Hout || a.Win != a.Wout) return false;
     int tm, tn, nw;
     if (!patch_cfg_shape(cfg, &tm, &tn, &nw)) return false;
     int th, tw, im, pp;

@@ -5,7 +5,8 @@
 //   C[m, n] = act((sum_k X[m, k] * W[n, k] + bias[n] + rowbias[m / rpb][n]) * scale + R[m, n])
 //
 // X rows are either plain rows (1x1 conv / linear) or gathered on the fly from an NHWC bf16
-// image (3x3, pad 1, stride 1|2, optional nearest x2 upsample of the input), K ordered (ky,kx,ci).
+// image (3x3, pad 1, stride 1|2, optional nearest x2 upsample of the input; or the VAE Downsample's
+// bottom/right-only pad with stride 2: GemmArgs::pad_tl = 0), K ordered (ky,kx,ci).
 //
 // Design (CDNA4):
 //   * block tile 128 (m) x TN (n, 64|128) x 64 (k); 4 waves as 2x2, each wave owns 64 x TN/2.
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(64 * WM * WN * KW) void gemm_kernel(const GemmArgs2
     // hoist the argument block into registers (keeps it out of scratch)
     const bf16_t* const gA = p.A; const bf16_t* const gW = p.W; const bf16_t* const gZ = p.zero;
     const int lda = p.lda, ldw = p.ldw, M = p.M, N = p.N, K = p.K;
-    const int Hin = p.Hin, Win = p.Win, Cin = p.Cin, Hout = p.Hout, Wout = p.Wout, cstride = p.stride, up = p.up;
+    const int Hin = p.Hin, Win = p.Win, Cin = p.Cin, Hout = p.Hout, Wout = p.Wout, cstride = p.stride, up = p.up, pad_tl = p.pad_tl;
     const bf16_t* const gA2 = p.A2; const int lda2 = p.lda2; const int Kc = K - p.K2;      // CONV: columns [Kc, K) contract with the second input (folded 1x1)
     const int splitk = p.splitk, per = p.ksteps_per_split;
     float* const ws = p.ws;
@@ -108,8 +109,8 @@ __global__ __launch_bounds__(64 * WM * WN * KW) void gemm_kernel(const GemmArgs2
             const int oy = rem / Wout;
             const int ox = rem - oy * Wout;
             xoff[i] = (size_t)b * Hin * Win;
-            uy0[i] = oy * cstride - 1;
-            ux0[i] = ox * cstride - 1;
+            uy0[i] = oy * cstride - pad_tl;
+            ux0[i] = ox * cstride - pad_tl;
         } else {
             xoff[i] = (size_t)m * lda;
             uy0[i] = ux0[i] = 0;
@@ -529,7 +530,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_ra_kernel(const GemmArgs2 pg) {
 
     const bf16_t* const gA = p.A; const bf16_t* const gW = p.W; const bf16_t* const gZ = p.zero;
     const int lda = p.lda, ldw = p.ldw, M = p.M, N = p.N, K = p.K;
-    const int Hin = p.Hin, Win = p.Win, Cin = p.Cin, Hout = p.Hout, Wout = p.Wout, cstride = p.stride, up = p.up;
+    const int Hin = p.Hin, Win = p.Win, Cin = p.Cin, Hout = p.Hout, Wout = p.Wout, cstride = p.stride, up = p.up, pad_tl = p.pad_tl;
     const int splitk = p.splitk, per = p.ksteps_per_split;
     float* const ws = p.ws;
     const Epilogue epi = make_epilogue(p);
@@ -575,8 +576,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_ra_kernel(const GemmArgs2 pg) {
             const int oy = rem / Wout;
             const int ox = rem - oy * Wout;
             aoff[mi] = (size_t)b * Hin * Win;
-            uy0[mi] = oy * cstride - 1;
-            ux0[mi] = ox * cstride - 1;
+            uy0[mi] = oy * cstride - pad_tl;
+            ux0[mi] = ox * cstride - pad_tl;
         } else {
             aoff[mi] = (size_t)m * lda + fq * 8;
             uy0[mi] = ux0[mi] = 0;
@@ -1187,7 +1188,7 @@ static int launch_tile(const GemmArgs& a, int splitk, hipStream_t stream, const 
 
 bool gemm_same_geometry(const GemmArgs& a, const GemmArgs& b) {
     return a.M == b.M && a.N == b.N && a.K == b.K && a.lda == b.lda && a.ldw == b.ldw && a.conv == b.conv && a.Hin == b.Hin && a.Win == b.Win &&
-           a.Cin == b.Cin && a.Hout == b.Hout && a.Wout == b.Wout && a.stride == b.stride && a.up == b.up && a.splitk == b.splitk &&
+           a.Cin == b.Cin && a.Hout == b.Hout && a.Wout == b.Wout && a.stride == b.stride && a.up == b.up && a.pad_tl == b.pad_tl && a.splitk == b.splitk &&
            a.out_f32 == b.out_f32 && a.act == b.act && a.ldc == b.ldc && a.defer_epilogue == b.defer_epilogue && a.rows_per_batch == b.rows_per_batch &&
            (a.ln_s != nullptr) == (b.ln_s != nullptr) && a.ln_eps == b.ln_eps && !a.stat_in && !b.stat_in && !a.stat_out && !b.stat_out &&
            !a.gn_stat && !b.gn_stat && (a.R != nullptr) == (b.R != nullptr) && a.ldr == b.ldr && (a.rowbias != nullptr) == (b.rowbias != nullptr) &&
@@ -1219,6 +1220,8 @@ int launch_gemm(GemmArgs a, hipStream_t stream, const GemmArgs* second) {
     if (a.A2 && (!a.conv || a.stride != 1 || a.up != 0 || a.K2 <= 0 || a.K2 % BK || (9 * a.Cin) % BK || a.lda2 % 8 || a.Hin != a.Hout || a.Win != a.Wout))
         return mkd_fail(-1, "gemm: a folded second input needs a stride-1 conv3x3 and K2, 9 * Cin multiples of 64");
     if (!a.A2) a.K2 = 0;
+    if (a.conv && !(a.pad_tl == 1 || (a.pad_tl == 0 && a.stride == 2 && a.up == 0 && !a.A2)))
+        return mkd_fail(-1, "gemm: conv pad origin must be 1, or 0 (bottom/right-only pad) with stride 2, no upsampling, no folded input");
     if (a.conv && (a.Cin % 8 || a.K != 9 * a.Cin + a.K2)) return mkd_fail(-1, "gemm: conv needs Cin % 8 == 0 and K == 9*Cin (+ K2)");
     if (!a.zero) return mkd_fail(-1, "gemm: zero page missing");
     if (!a.out_f32 && (a.ldc % 4)) return mkd_fail(-1, "gemm: ldc must be a multiple of 4");

@@ -231,6 +231,78 @@ __global__ __launch_bounds__(256) void conv3x3_fewout_kernel(const bf16_t* __res
     }
 }
 
+// ---- fused tail of the VAE encoder (UPSTREAM Encoder.conv_out -> AutoencoderKL.quant_conv -> DiagonalGaussianDistribution ->
+// sample() / mode() -> get_first_stage_encoding's x scale_factor): one wavefront per latent pixel.  conv_out (3x3 pad 1, Cin -> 2Z,
+// bf16 NHWC in) is reduced as in conv3x3_fewout_kernel; then lane 0 holds the 2Z conv outputs and applies quant_conv (a 2Z x 2Z
+// matrix-vector product in registers): moments = (mean | logvar), std = exp(0.5 clamp(logvar, -30, 20)),
+// z = (mean + std * noise) * scale (noise == null: mode() = mean).  z [B,Z,h,w] and moments [B,2Z,h,w] fp32 NCHW, either may be null.
+template <int Z>
+__global__ __launch_bounds__(256) void vae_enc_tail_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
+                                                           const float* __restrict__ bias, const bf16_t* __restrict__ wq,
+                                                           const float* __restrict__ bq, const float* __restrict__ noise, float scale,
+                                                           float* __restrict__ z_out, float* __restrict__ mom_out,
+                                                           int batch, int H, int W, int Cin) {
+    constexpr int C2 = 2 * Z;
+    const int lane = threadIdx.x & 63;
+    const int pix = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int npix = batch * H * W;
+    if (pix >= npix) return;
+    const int b = pix / (H * W);
+    const int rem = pix - b * H * W;
+    const int oy = rem / W, ox = rem - oy * W;
+    const int V = Cin >> 3;
+    float acc[C2];
+#pragma unroll
+    for (int c = 0; c < C2; ++c) acc[c] = 0.f;
+    for (int idx = lane; idx < 9 * V; idx += 64) {
+        const int tap = idx / V, v = idx - tap * V;
+        const int ky = (tap * 11) >> 5, kx = tap - 3 * ky;
+        const int iy = oy + ky - 1, ix = ox + kx - 1;
+        if ((unsigned)iy >= (unsigned)H || (unsigned)ix >= (unsigned)W) continue;
+        const U16x8 xv = *(const U16x8*)(x + ((size_t)(b * H + iy) * W + ix) * Cin + v * 8);
+        float xf[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) xf[j] = bf16_to_f32(xv.v[j]);
+#pragma unroll
+        for (int c = 0; c < C2; ++c) {
+            const U16x8 wv = *(const U16x8*)(w + ((size_t)c * 9 + tap) * Cin + v * 8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[c] += xf[j] * bf16_to_f32(wv.v[j]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < C2; ++c) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc[c] += __shfl_xor(acc[c], o, 64);
+        acc[c] += bias[c];
+    }
+    if (lane != 0) return;
+    float m[C2];
+#pragma unroll
+    for (int o = 0; o < C2; ++o) {
+        float s = bq[o];
+#pragma unroll
+        for (int i = 0; i < C2; ++i) s += bf16_to_f32(wq[o * C2 + i]) * acc[i];
+        m[o] = s;
+    }
+    const size_t hw = (size_t)H * W, p = (size_t)oy * W + ox;
+    if (mom_out) {
+#pragma unroll
+        for (int o = 0; o < C2; ++o) mom_out[((size_t)b * C2 + o) * hw + p] = m[o];
+    }
+    if (z_out) {
+#pragma unroll
+        for (int c = 0; c < Z; ++c) {
+            float v = m[c];
+            if (noise) {
+                const float lv = fminf(fmaxf(m[Z + c], -30.0f), 20.0f);
+                v += expf(0.5f * lv) * noise[((size_t)b * Z + c) * hw + p];
+            }
+            z_out[((size_t)b * Z + c) * hw + p] = v * scale;
+        }
+    }
+}
+
 // ---- row softmax over bf16 [rows, cols] (VAE mid-block attention scores), one 256-thread block per row ----------
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int cols) {
     __shared__ float red[4];
@@ -410,15 +482,20 @@ int launch_conv3x3_direct(const void* x, int in_nchw_f32, const bf16_t* w, const
                           int out_nchw_f32, int act, const bf16_t* add, int batch, int Hin, int Win,
                           int Cin, int Cout, int stride, hipStream_t stream, const ConvInIo* second) {
     if (stride != 1 && stride != 2) return mkd_fail(-1, "conv3x3_direct: stride must be 1 or 2");
-    if (in_nchw_f32 && !out_nchw_f32 && stride == 1 && Cin == 4 && Cout >= 64 && Cout <= 512) {
+    // 4 -> C: the UNet / ControlNet input conv; 3 -> C: the VAE encoder's conv_in on the image (full resolution)
+    if (in_nchw_f32 && !out_nchw_f32 && stride == 1 && ((Cin == 4 && Cout >= 64) || (Cin == 3 && Cout >= 8)) && Cout <= 512 && (Cin == 4 || !second)) {
         const int npix = batch * Hin * Win;
         const int ppb = 16;            // <= PPB_MAX of the kernel
         const int threads = (Cout + 63) / 64 * 64;
         Pair<ConvInIo> io;
         io.g[0] = ConvInIo{w, bias, (bf16_t*)y, add};
         MKD_PAIR_SET2(io, second ? *second : io.g[0]);
-        hipLaunchKernelGGL(conv3x3_fewin_kernel<4>, dim3((npix + ppb - 1) / ppb, second ? 2 : 1), dim3(threads), 0, stream, (const float*)x, io,
-                           act, batch, Hin, Win, Cout, ppb);
+        if (Cin == 4)
+            hipLaunchKernelGGL(conv3x3_fewin_kernel<4>, dim3((npix + ppb - 1) / ppb, second ? 2 : 1), dim3(threads), 0, stream, (const float*)x, io,
+                               act, batch, Hin, Win, Cout, ppb);
+        else
+            hipLaunchKernelGGL(conv3x3_fewin_kernel<3>, dim3((npix + ppb - 1) / ppb, 1), dim3(threads), 0, stream, (const float*)x, io,
+                               act, batch, Hin, Win, Cout, ppb);
         MKD_LAUNCH_CHECK("conv3x3_fewin_kernel");
         return 0;
     }
@@ -439,6 +516,17 @@ int launch_conv3x3_direct(const void* x, int in_nchw_f32, const bf16_t* w, const
     hipLaunchKernelGGL(conv3x3_direct_kernel, dim3(grid_for(total, 256, 1 << 20)), dim3(256), 0, stream, x, in_nchw_f32, w, bias,
                        y, out_nchw_f32, act, add, batch, Hin, Win, Cin, Cout, Hout, Wout, stride);
     MKD_LAUNCH_CHECK("conv3x3_direct_kernel");
+    return 0;
+}
+
+int launch_vae_enc_tail(const bf16_t* x, const bf16_t* w, const float* bias, const bf16_t* wq, const float* bq, const float* noise,
+                        float scale, float* z_out, float* moments_out, int batch, int H, int W, int Cin, int z_channels, hipStream_t stream) {
+    if (z_channels != 4) return mkd_fail(-1, "vae_enc_tail: z_channels must be 4");
+    if (Cin % 8 || !x || !w || !bias || !wq || !bq || (!z_out && !moments_out)) return mkd_fail(-1, "vae_enc_tail: bad arguments");
+    const int npix = batch * H * W;
+    hipLaunchKernelGGL(vae_enc_tail_kernel<4>, dim3((npix + 3) / 4), dim3(256), 0, stream, x, w, bias, wq, bq, noise, scale, z_out,
+                       moments_out, batch, H, W, Cin);
+    MKD_LAUNCH_CHECK("vae_enc_tail_kernel");
     return 0;
 }
 

@@ -77,6 +77,10 @@ struct GemmArgs {
     void* C; int ldc; int out_f32;
     int M, N, K;
     int conv; int Hin, Win, Cin, Hout, Wout, stride, up;
+    // conv: top/left padding of the 3x3 window (its origin is (oy * stride - pad_tl, ox * stride - pad_tl)).  1: pad 1 on every side,
+    // the only form before the VAE encoder and what every conv builder sets; 0: UPSTREAM Downsample (F.pad(x, (0,1,0,1)) + a
+    // stride-2 pad-0 conv), stride 2 without upsampling only, gather / linear and register-A kernels only (launch_gemm checks)
+    int pad_tl;                             // (fills the 4-byte hole before ws: the block does not grow)
     float* ws; size_t ws_bytes; int splitk; int ksteps_per_split;     // split-K fp32 partial slabs: pointer and capacity
     int tile_h, tile_w, tile_imgs;          // spatial tile of the LDS-staged conv kernel (set by its launcher)
     const float* ln_s; float ln_eps;        // fused LayerNorm on the A rows: ln_s[n] = sum_k W'[n][k] (W' = W*gamma), else null
@@ -224,6 +228,10 @@ int launch_conv3x3_direct(const void* x, int in_nchw_f32, const bf16_t* w, const
                           int out_nchw_f32, int act, const bf16_t* add, int batch, int Hin, int Win,
                           int Cin, int Cout, int stride, hipStream_t stream, const ConvInIo* second = nullptr);   // second: 4 -> C form only
 int launch_pack_conv_weight(const float* w, bf16_t* out, int Cout, int Cin, int kh, int kw, hipStream_t stream);
+// VAE encoder tail: conv_out (3x3, bf16 NHWC [B,H,W,Cin] -> 2 z_channels) + quant_conv + DiagonalGaussianDistribution sample / mode
+// (noise [B,z,H,W] fp32 or null) x scale -> z_out [B,z,H,W] / moments_out [B,2z,H,W] fp32 NCHW (either may be null)
+int launch_vae_enc_tail(const bf16_t* x, const bf16_t* w, const float* bias, const bf16_t* wq, const float* bq, const float* noise,
+                        float scale, float* z_out, float* moments_out, int batch, int H, int W, int Cin, int z_channels, hipStream_t stream);
 int launch_f32_to_bf16(const float* x, bf16_t* y, int64_t n, hipStream_t stream);
 int launch_timestep_embedding(const int64_t* t, bf16_t* out, int batch, int dim, hipStream_t stream);
 int launch_copy_strided(const bf16_t* src, int ld_src, bf16_t* dst, int ld_dst, int rows, int cols,

@@ -26,6 +26,8 @@ def _cat_cond(uncond, c):
         for k in c:
             if isinstance(c[k], list):
                 out[k] = [torch.cat([uncond[k][i], c[k][i]]) for i in range(len(c[k]))]
+            elif c[k] is None:              # c_concat None (the inversion runs the UNet alone)
+                out[k] = None
             else:
                 out[k] = torch.cat([uncond[k], c[k]])
         return out
@@ -154,15 +156,7 @@ class DDIMSampler:
             raise NotImplementedError('quantize_denoised needs first_stage_model.quantize (VAE: SURVEY §8f)')
         if dynamic_threshold is not None:
             raise NotImplementedError()
-        cfg_on = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
-        if not cfg_on:
-            e_c, e_u = self.model.apply_model(x, t, c), None
-        else:
-            x_in = torch.cat([x] * 2)
-            t_in = torch.cat([t] * 2)
-            binder = getattr(self.model, 'cfg_conditioning', None)
-            c_in = binder(unconditional_conditioning, c) if binder is not None else _cat_cond(unconditional_conditioning, c)
-            e_u, e_c = self.model.apply_model(x_in, t_in, c_in).chunk(2)
+        e_c, e_u = self._eps(x, c, t, unconditional_guidance_scale, unconditional_conditioning)
         alphas = self.model.alphas_cumprod if use_original_steps else self.ddim_alphas
         alphas_prev = self.model.alphas_cumprod_prev if use_original_steps else self.ddim_alphas_prev
         s1m = self.model.sqrt_one_minus_alphas_cumprod if use_original_steps else self.ddim_sqrt_one_minus_alphas
@@ -173,6 +167,22 @@ class DDIMSampler:
             noise = noise_like(x.shape, device, repeat_noise)
             if noise_dropout > 0.0:
                 noise = torch.nn.functional.dropout(noise, p=noise_dropout)
+        return self._update(x, e_c, e_u, unconditional_guidance_scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature)
+
+    # (e_c, e_u) of one step: CFG batches [uncond; cond] through ONE apply_model; e_u None without guidance
+    def _eps(self, x, c, t, unconditional_guidance_scale, unconditional_conditioning):
+        cfg_on = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
+        if not cfg_on:
+            return self.model.apply_model(x, t, c), None
+        x_in = torch.cat([x] * 2)
+        t_in = torch.cat([t] * 2)
+        binder = getattr(self.model, 'cfg_conditioning', None)
+        c_in = binder(unconditional_conditioning, c) if binder is not None else _cat_cond(unconditional_conditioning, c)
+        e_u, e_c = self.model.apply_model(x_in, t_in, c_in).chunk(2)
+        return e_c, e_u
+
+    # the eta-DDIM update x_prev(x, eps) with the coefficients of one step: on the device through the model's hook
+    def _update(self, x, e_c, e_u, unconditional_guidance_scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature):
         step_fn = getattr(self.model, 'ddim_step', None)
         if step_fn is not None and x.is_cuda:
             return step_fn(x, e_c, e_u, unconditional_guidance_scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature)
@@ -184,3 +194,80 @@ class DDIMSampler:
         if noise is not None:
             x_prev = x_prev + sigma_t * noise * temperature
         return x_prev, pred_x0
+
+    # -- DDIM inversion (UPSTREAM DDIMSampler.encode; reference pre_dataset.py InvRec) and its reverse loop --
+    @torch.no_grad()
+    def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None, unconditional_guidance_scale=1.0,
+               unconditional_conditioning=None, callback=None):
+        """Deterministic DDIM inversion x0 -> x_{t_enc}: for i < t_enc, with a_next = alphas[i], a = alphas_prev[i],
+        x <- sqrt(a_next / a) x + sqrt(a_next) (sqrt(1 / a_next - 1) - sqrt(1 / a - 1)) eps(x, ddim_timesteps[i]).
+        That is the eta = 0 DDIM update with a_t := a and a_prev := a_next, executed in the opposite order.  The in-library
+        loop (model.sample_loop_fast / mkd_sample) runs index n-1 .. 0, so it is handed MIRRORED tables: entry j is inversion
+        step t_enc - 1 - j, with alphas = ddim_alphas_prev, alphas_prev = ddim_alphas, sqrt_one_minus = sqrt(1 - ddim_alphas_prev).
+        callback / return_intermediates / use_original_steps take the eager step loop.  The model is evaluated at
+        ddim_timesteps[i], the timestep whose coefficients step i uses.  Returns (x_next, {'x_encoded',
+        'intermediate_steps'[, 'intermediates']})."""
+        n_ref = self.ddpm_num_timesteps if use_original_steps else self.ddim_timesteps.shape[0]
+        if t_enc > n_ref:
+            raise ValueError(f'DDIMSampler.encode: t_enc {t_enc} > {n_ref} reference steps')
+        num_steps = int(t_enc)
+        if use_original_steps:
+            alphas_next = self.model.alphas_cumprod[:num_steps]
+            alphas = self.model.alphas_cumprod_prev[:num_steps]
+            timesteps = np.arange(num_steps)
+        else:
+            alphas_next = self.ddim_alphas[:num_steps]
+            alphas = torch.tensor(np.asarray(self.ddim_alphas_prev[:num_steps]), dtype=torch.float32)
+            timesteps = self.ddim_timesteps[:num_steps]
+        fast = getattr(self.model, 'sample_loop_fast', None)
+        if fast is not None and callback is None and not return_intermediates and not use_original_steps and num_steps > 0:
+            a = [float(v) for v in alphas][::-1]
+            a_next = [float(v) for v in alphas_next][::-1]
+            x_next = fast(x0, c, [int(v) for v in timesteps][::-1], a, a_next, [float(np.sqrt(1.0 - np.float32(v))) for v in a],
+                          unconditional_guidance_scale, unconditional_conditioning)
+            return x_next, {'x_encoded': x_next, 'intermediate_steps': []}
+        x_next = x0
+        intermediates, inter_steps = [], []
+        for i in range(num_steps):
+            t = torch.full((x0.shape[0],), int(timesteps[i]), device=x0.device, dtype=torch.long)
+            e_c, e_u = self._eps(x_next, c, t, unconditional_guidance_scale, unconditional_conditioning)
+            a_t, a_n = float(alphas[i]), float(alphas_next[i])
+            x_next, _ = self._update(x_next, e_c, e_u, unconditional_guidance_scale, a_t, a_n, 0.0,
+                                     float(np.sqrt(1.0 - np.float32(a_t))), None, 1.0)
+            if return_intermediates and i % (num_steps // return_intermediates) == 0 and i < num_steps - 1:
+                intermediates.append(x_next)
+                inter_steps.append(i)
+            elif return_intermediates and i >= num_steps - 2:
+                intermediates.append(x_next)
+                inter_steps.append(i)
+            if callback:
+                callback(i)
+        out = {'x_encoded': x_next, 'intermediate_steps': inter_steps}
+        if return_intermediates:
+            out['intermediates'] = intermediates
+        return x_next, out
+
+    @torch.no_grad()
+    def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
+               use_original_steps=False, callback=None):
+        """Reverse loop over ddim_timesteps[:t_start], newest first (UPSTREAM DDIMSampler.decode; the loop
+        MKDDIMSampler.reconstruct runs): inverts encode(x0, t_enc=t_start) for an eps that does not depend on x."""
+        timesteps = np.arange(self.ddpm_num_timesteps) if use_original_steps else self.ddim_timesteps
+        timesteps = timesteps[:t_start]
+        time_range = np.flip(timesteps)
+        total_steps = timesteps.shape[0]
+        fast = getattr(self.model, 'sample_loop_fast', None)
+        if (fast is not None and callback is None and not use_original_steps and total_steps > 0
+                and float(self.ddim_sigmas[:total_steps].abs().max()) == 0.0):
+            return fast(x_latent, cond, timesteps, self.ddim_alphas[:total_steps], self.ddim_alphas_prev[:total_steps],
+                        self.ddim_sqrt_one_minus_alphas[:total_steps], unconditional_guidance_scale,
+                        unconditional_conditioning)
+        x_dec = x_latent
+        for i, step in enumerate(time_range):
+            index = total_steps - i - 1
+            ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
+            x_dec, _ = self._step(x_dec, cond, ts, index, False, use_original_steps, False, 1.0, 0.0, None, None,
+                                  unconditional_guidance_scale, unconditional_conditioning, None)
+            if callback:
+                callback(i)
+        return x_dec

@@ -24,24 +24,7 @@ class MKDDIMSampler(DDIMSampler):
     @torch.no_grad()
     def reconstruct(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
                     use_original_steps=False, callback=None):
-        """Reverse loop over ddim_timesteps[:t_start], newest first; returns the decoded latent."""
-        timesteps = np.arange(self.ddpm_num_timesteps) if use_original_steps else self.ddim_timesteps
-        timesteps = timesteps[:t_start]
-        time_range = np.flip(timesteps)
-        total_steps = timesteps.shape[0]
-        fast = getattr(self.model, 'sample_loop_fast', None)
-        if (fast is not None and callback is None and not use_original_steps and total_steps > 0
-                and float(self.ddim_sigmas[:total_steps].abs().max()) == 0.0):
-            return fast(x_latent, cond, timesteps, self.ddim_alphas[:total_steps], self.ddim_alphas_prev[:total_steps],
-                        self.ddim_sqrt_one_minus_alphas[:total_steps], unconditional_guidance_scale,
-                        unconditional_conditioning)
-        x_dec = x_latent
-        for i, step in enumerate(time_range):
-            index = total_steps - i - 1
-            ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
-            x_dec, _ = self.denoising_step(x_dec, cond, ts, index=index, use_original_steps=use_original_steps,
-                                           unconditional_guidance_scale=unconditional_guidance_scale,
-                                           unconditional_conditioning=unconditional_conditioning)
-            if callback:
-                callback(i)
-        return x_dec
+        """Reverse loop over ddim_timesteps[:t_start], newest first; returns the decoded latent (= DDIMSampler.decode)."""
+        return self.decode(x_latent, cond, t_start, unconditional_guidance_scale=unconditional_guidance_scale,
+                           unconditional_conditioning=unconditional_conditioning, use_original_steps=use_original_steps,
+                           callback=callback)

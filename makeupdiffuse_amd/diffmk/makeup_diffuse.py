@@ -45,7 +45,7 @@ class BaseMakeUpDiffuse:
                  only_mid_control: bool = False, parameterization: str = 'eps', channels: int = 4, image_size: int = 64,
                  conditioning_key: str = 'crossattn', first_stage_key: str = 'jpg', cond_stage_key: str = 'txt',
                  control_key: str = 'ref_img', src_key: str = 'src_img', src_img_key: str = 'src_img',
-                 ref_img_key: str = 'ref_img', use_ema: bool = False, **unused_training_params):
+                 ref_img_key: str = 'ref_img', use_ema: bool = False, first_stage_encoder: bool = False, **unused_training_params):
         if parameterization != 'eps':
             raise NotImplementedError("parameterization must be 'eps' (base_diffusion_makeup.yaml:50)")
         self.net_config = NetConfig.from_yaml_params(dict(control_stage_config.get('params', control_stage_config)),
@@ -54,6 +54,10 @@ class BaseMakeUpDiffuse:
         self.vae_config = None
         if first_stage_config is not None:
             self.vae_config = VaeConfig.from_yaml_params(dict(first_stage_config.get('params', first_stage_config)))
+        # opt-in first-stage ENCODER (encode_first_stage / get_z): configured on the device next to the decoder
+        self.first_stage_encoder = bool(first_stage_encoder)
+        if self.first_stage_encoder and self.vae_config is None:
+            raise ValueError('first_stage_encoder=True needs a first_stage_config (its ddconfig describes the encoder)')
         self.clip_config = None
         if cond_stage_config is not None:
             self.clip_config = ClipConfig.from_yaml_params(cond_stage_config.get('params'))
@@ -111,6 +115,8 @@ class BaseMakeUpDiffuse:
                 self.engine = MkdEngine(self.net_config, device)
                 if self.vae_config is not None:
                     self.engine.configure_vae(self.vae_config)
+                if self.first_stage_encoder:
+                    self.engine.configure_vae_encoder(self.vae_config)
                 if self.clip_config is not None:
                     from ..clip import FrozenCLIPEmbedder, load_tokenizer
                     self.engine.configure_clip(self.clip_config)
@@ -137,6 +143,7 @@ class BaseMakeUpDiffuse:
             self._pending_sd = {k: v for k, v in sd.items()
                                 if k.startswith(MkdEngine.UNET_PREFIX) or k.startswith(MkdEngine.CONTROL_PREFIX)
                                 or k.startswith('first_stage_model.post_quant_conv.') or k.startswith('first_stage_model.decoder.')
+                                or (self.first_stage_encoder and k.startswith(MkdEngine.VAE_ENCODER_PREFIXES))
                                 or (k.startswith(MkdEngine.CLIP_PREFIX) and not k.endswith('position_ids'))}
             unused = [k for k in sd if k not in self._pending_sd]
         return [], unused
@@ -289,6 +296,40 @@ class BaseMakeUpDiffuse:
             raise NotImplementedError('no first_stage_config in the yaml: the decoder was not configured')
         return eng.decode(z, self.scale_factor)
 
+    # ---- first-stage encoder (opt-in: first_stage_encoder=True) ----------------------------------------------------
+    def _require_encoder(self) -> MkdEngine:
+        eng = self._require_engine()
+        if eng.vae_enc_cfg is None:
+            raise NotImplementedError('the first-stage encoder was not configured (construct with first_stage_encoder=True '
+                                      'and a first_stage_config)')
+        return eng
+
+    @torch.no_grad()
+    def encode_first_stage(self, x: torch.Tensor) -> 'DiagonalGaussianPosterior':
+        """UPSTREAM AutoencoderKL.encode: Encoder -> quant_conv -> DiagonalGaussianDistribution over the moments (on the device)."""
+        _, mom = self._require_encoder().encode(x, 1.0, None, moments=True)
+        return DiagonalGaussianPosterior(mom)
+
+    def get_first_stage_encoding(self, encoder_posterior) -> torch.Tensor:
+        """UPSTREAM LatentDiffusion.get_first_stage_encoding: scale_factor * posterior.sample() (or * the tensor itself)."""
+        if isinstance(encoder_posterior, DiagonalGaussianPosterior):
+            z = encoder_posterior.sample()
+        elif isinstance(encoder_posterior, torch.Tensor):
+            z = encoder_posterior
+        else:
+            raise NotImplementedError(f"encoder_posterior of type '{type(encoder_posterior)}' not yet implemented")
+        return self.scale_factor * z
+
+    @torch.no_grad()
+    def get_z(self, x: torch.Tensor) -> torch.Tensor:
+        """reference diffmk/makeup_diffuse.py:37-39 = get_first_stage_encoding(encode_first_stage(x)) as ONE mkd_encode; the noise of
+        sample() is drawn as DiagonalGaussianDistribution.sample draws it (torch.randn on the default CPU generator)."""
+        eng = self._require_encoder()
+        f = 2 ** (len(eng.vae_enc_cfg.ch_mult) - 1)
+        B, _, H, W = x.shape
+        noise = torch.randn((B, eng.vae_enc_cfg.z_channels, H // f, W // f))
+        return eng.encode(x, self.scale_factor, noise)
+
     def decode_latent_code(self, z: torch.Tensor, predict_cids: bool = False, force_not_quantize: bool = False) -> torch.Tensor:
         """reference diffmk/makeups.py:260-262: ``first_stage_model.decode(z / scale_factor)`` (unclamped)."""
         return self.decode_first_stage(z)
@@ -304,6 +345,24 @@ class BaseMakeUpDiffuse:
     @property
     def has_first_stage(self) -> bool:
         return self.engine is not None and self.engine.vae_cfg is not None
+
+
+class DiagonalGaussianPosterior:
+    """UPSTREAM ldm DiagonalGaussianDistribution over device moments [B, 2z, h, w] (mean | logvar), deterministic=False."""
+
+    def __init__(self, parameters: torch.Tensor):
+        self.parameters = parameters
+        self.mean, self.logvar = torch.chunk(parameters, 2, dim=1)
+        self.logvar = torch.clamp(self.logvar, -30.0, 20.0)
+        self.std = torch.exp(0.5 * self.logvar)
+        self.var = torch.exp(self.logvar)
+
+    def sample(self) -> torch.Tensor:
+        # drawn on the default CPU generator and moved, as upstream's sample() does: RNG consumption matches
+        return self.mean + self.std * torch.randn(self.mean.shape).to(device=self.parameters.device)
+
+    def mode(self) -> torch.Tensor:
+        return self.mean
 
 
 class TestDiffuseModel(BaseMakeUpDiffuse):

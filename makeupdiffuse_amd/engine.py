@@ -153,6 +153,7 @@ class MkdEngine:
             _lib.check(self.lib.mkd_ctx_create(C.byref(cfg.to_c()), C.byref(self._ctx)), 'mkd_ctx_create')
         self._keep: list = []          # tensors the prepared plan points at
         self.vae_cfg: Optional[VaeConfig] = None
+        self.vae_enc_cfg: Optional[VaeConfig] = None
         self.clip_cfg: Optional[ClipConfig] = None
         self._prepared_key = None
         self.batch = 0
@@ -181,7 +182,7 @@ class MkdEngine:
         return out
 
     def param_count(self, which: str) -> int:
-        return int(self.lib.mkd_param_count(self._ctx, 0 if which == 'unet' else 1))
+        return int(self.lib.mkd_param_count(self._ctx, 0 if which == 'unet' else 4 if which == 'vae_encoder' else 1))
 
     def load_weight(self, name: str, tensor: torch.Tensor) -> None:
         t = tensor.detach()
@@ -210,8 +211,11 @@ class MkdEngine:
             raise _lib.MkdError(f'{len(core_missing)} weights missing from state_dict, e.g. {core_missing[:3]}')
         if not core_missing:
             self.finalize()
-        if getattr(self, 'vae_cfg', None) is not None and not [k for k in missing if k.startswith('first_stage_model.')]:
+        enc = [k for k in missing if k.startswith(self.VAE_ENCODER_PREFIXES)]
+        if getattr(self, 'vae_cfg', None) is not None and not [k for k in missing if k.startswith('first_stage_model.') and k not in enc]:
             self.finalize_vae()
+        if getattr(self, 'vae_enc_cfg', None) is not None and not enc:
+            self.finalize_vae_encoder()
         if getattr(self, 'clip_cfg', None) is not None and not [k for k in missing if k.startswith('cond_stage_model.')]:
             self.finalize_clip()
         return unused
@@ -263,6 +267,44 @@ class MkdEngine:
             _lib.check(self.lib.mkd_decode(self._ctx, C.c_void_p(z.data_ptr()), B, h, w, float(scale_factor),
                                            C.c_void_p(out.data_ptr()), C.c_void_p(_stream())), 'mkd_decode')
         return out
+
+    # ---- first-stage encoder (opt-in) ---------------------------------------------------------------------
+    VAE_ENCODER_PREFIXES = ('first_stage_model.encoder.', 'first_stage_model.quant_conv.')
+
+    def configure_vae_encoder(self, vcfg: VaeConfig) -> None:
+        """Adds the first_stage_model.{encoder,quant_conv}.* entries to expected_params(); load them like the rest."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mkd_vae_encoder_configure(self._ctx, C.byref(vcfg.to_c())), 'mkd_vae_encoder_configure')
+        self.vae_enc_cfg = vcfg
+
+    def finalize_vae_encoder(self) -> None:
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mkd_vae_encoder_finalize(self._ctx), 'mkd_vae_encoder_finalize')
+
+    def encode(self, images: torch.Tensor, scale_factor: float = 0.18215, noise: Optional[torch.Tensor] = None,
+               moments: bool = False):
+        """get_first_stage_encoding(encode_first_stage(images)): images [B,3,H,W] -> z [B,4,H/f,W/f] fp32 (f = 2^(levels-1)).
+        noise [B,4,H/f,W/f]: posterior sample() = mean + std * noise, None: mode().  moments=True: returns (z, moments
+        [B,8,H/f,W/f]), the posterior's parameters before scaling."""
+        if self.vae_enc_cfg is None:
+            raise _lib.MkdError('encode: the first-stage encoder is not configured (configure_vae_encoder)')
+        x = _f32c(images, self.device)
+        B, _, H, W = x.shape
+        f = 2 ** (len(self.vae_enc_cfg.ch_mult) - 1)
+        zc = self.vae_enc_cfg.z_channels
+        z = torch.empty((B, zc, H // f, W // f), device=self.device, dtype=torch.float32)
+        mom = torch.empty((B, 2 * zc, H // f, W // f), device=self.device, dtype=torch.float32) if moments else None
+        nz = _f32c(noise, self.device) if noise is not None else None
+        if nz is not None and tuple(nz.shape) != tuple(z.shape):
+            raise ValueError(f'encode: noise shape {tuple(nz.shape)} != latent shape {tuple(z.shape)}')
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mkd_encode(self._ctx, C.c_void_p(x.data_ptr()), B, H, W, float(scale_factor),
+                                           C.c_void_p(_ptr(nz)), C.c_void_p(z.data_ptr()), C.c_void_p(_ptr(mom)),
+                                           C.c_void_p(_stream())), 'mkd_encode')
+        return (z, mom) if moments else z
+
+    def encode_flops(self) -> float:
+        return float(self.lib.mkd_encode_flops(self._ctx))
 
     # ---- CLIP text encoder ----------------------------------------------------------------------------
     CLIP_PREFIX = 'cond_stage_model.transformer.text_model.'

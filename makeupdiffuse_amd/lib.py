@@ -69,6 +69,10 @@ SIGNATURES = {
     'mkd_vae_finalize': (_I, [_P]),
     'mkd_decode': (_I, [_P, _P, _I, _I, _I, _F, _P, _P]),
     'mkd_decode_flops': (C.c_double, [_P]),
+    'mkd_vae_encoder_configure': (_I, [_P, C.POINTER(VaeConfigC)]),
+    'mkd_vae_encoder_finalize': (_I, [_P]),
+    'mkd_encode': (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _P]),
+    'mkd_encode_flops': (C.c_double, [_P]),
     'mkd_clip_configure': (_I, [_P, C.POINTER(ClipConfigC)]),
     'mkd_clip_finalize': (_I, [_P]),
     'mkd_clip_encode': (_I, [_P, _P, _I, _I, _P, _P]),
@@ -85,6 +89,7 @@ SIGNATURES = {
     'mkd_gemm_bf16': (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _P, _I, _F, _I, _P, _I, _I, _I, _I, _I,
                            _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'mkd_conv3x3_fold_bf16': (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    'mkd_conv3x3_down_bf16': (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     'mkd_gemm_gnstat_bf16': (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _P, _I, _F, _I, _P, _I, _I, _I, _I, _I,
                                   _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
     'mkd_gemm_groupnorm_bf16': (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _P, _I, _F, _P, _I, _I, _I, _I, _I,
