@@ -160,6 +160,46 @@ int mkd_sample_eta(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const
                    const float* sigmas, const float* noise, float temperature,
                    float cfg_scale, float* x_out, int use_graph, void* stream);
 
+/* ---- masked sampling: background-preserving transfer (UPSTREAM DDIMSampler.ddim_sampling mask / x0) ------------------ */
+/* Before every executed step (index i, timestep ts = timesteps[i]; before the model is evaluated) the latent is blended with a
+ * forward-diffused x0:  img = (sqrt_alphas_cumprod[i] x0 + sqrt_one_minus_alphas_cumprod[i] n_k) mask + (1 - mask) img,
+ * mask = 1 keeps x0.  There is no blend after the last step.  The tables are host arrays indexed like ddim_alphas[index], holding
+ * the DDPM schedule's values at the step's timestep (model.sqrt_alphas_cumprod[ts]).  x0 [B,4,h,w] fp32 device: the un-doubled
+ * batch, also with guidance; mask [mask_batch, mask_channels, h, w] fp32 device, mask_batch in {1, B}, mask_channels in {1, 4},
+ * broadcast.  noise: DEVICE array [n_steps][B*4*h*w], row k = the blend's draw of the k-th executed step (upstream q_sample's
+ * randn_like(x0); a caller that also passes eta > 0 noise draws the blend's row before the step's eta draw). */
+typedef struct mkd_sample_mask {
+    const float* x0;
+    const float* mask;
+    int32_t mask_batch;
+    int32_t mask_channels;
+    const float* sqrt_alphas_cumprod;              /* host [n_steps] */
+    const float* sqrt_one_minus_alphas_cumprod;    /* host [n_steps] */
+    const float* noise;                            /* device [n_steps][B*4*h*w] */
+} mkd_sample_mask;
+/* mkd_sample_eta with the blend above; m == NULL is exactly mkd_sample_eta.  All three loop forms (graph replay, its per-stream
+ * segments, use_graph == 0) run it, with or without guidance, eta > 0 included.  The graph replays unchanged: its first kernel
+ * reads x0 / mask / the noise row / the coefficients from the device-resident step state, so masked and unmasked calls share one
+ * capture and the per-step launch count (mkd_step_launches) is the same; the eager loop (use_graph == 0) adds one launch per
+ * step.  Bad shapes or a missing pointer in `m`: MKD_ERR_ARG.  x0, mask and noise are read by the enqueued loop: they must stay
+ * valid until the work on `stream` has completed. */
+int mkd_sample_masked(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps,
+                      const float* alphas, const float* alphas_prev, const float* sqrt_one_minus_alphas,
+                      const float* sigmas, const float* noise, float temperature, const mkd_sample_mask* m,
+                      float cfg_scale, float* x_out, int use_graph, void* stream);
+/* One blend / q_sample (the eager step loop's and DDIMSampler.stochastic_encode's kernel; the same device arithmetic as the loop):
+ * out = (sqrt_ac x0 + sqrt_one_minus_ac noise) mask + (1 - mask) x over [batch, channels, hw] fp32 device tensors, mask as in
+ * mkd_sample_mask (mask_batch in {1, batch}, mask_channels in {1, channels}); mask == NULL: out = the q_sample alone (x unused).
+ * out may alias x.  Bad shapes: MKD_ERR_ARG. */
+int mkd_q_sample_blend(const float* x0, const float* noise, float sqrt_ac, float sqrt_one_minus_ac, const float* mask,
+                       int mask_batch, int mask_channels, const float* x, float* out, int batch, int channels, int hw, void* stream);
+/* Latent mask from a label map (reference Fixbackground: labels 0 background, 11 teeth, 12 hair): labels [batch, H, W] uint8
+ * device -> out [batch, 1, H/factor, W/factor] fp32 device = the fraction of each factor x factor block whose label l has bit l set
+ * in `classes` (labels >= 64 never match): F.interpolate(mode='area') of the binary mask.  threshold > 0: 1 where that fraction
+ * >= threshold, else 0.  H, W must be multiples of factor (1..64), else MKD_ERR_ARG. */
+int mkd_latent_mask_from_labels(const uint8_t* labels, int batch, int H, int W, uint64_t classes, int factor, float threshold,
+                                float* out, void* stream);
+
 /* ---- first-stage decoder ------------------------------------------------ */
 /* yaml first_stage_config.params.ddconfig (diffmodels/base_diffusion_makeup.yaml:86-107), decoder half only. */
 typedef struct mkd_vae_config {

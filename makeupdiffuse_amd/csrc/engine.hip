@@ -1785,9 +1785,9 @@ struct mkd_ctx {
         struct Item { OpFn fn; int sid; int from, to; };
         std::vector<Item> items;
         const int Bn = B;
-        items.push_back({[self, Bn](hipStream_t st) {
+        items.push_back({[self, Bn, n](hipStream_t st) {
             const TembSel ts = self->temb_sel();
-            return launch_step_setup(self->s_state, self->s_t, Bn, st, self->temb_skip ? &ts : nullptr); }, 0, -1, -1});
+            return launch_step_setup(self->s_state, self->s_t, Bn, self->s_xa, n, st, self->temb_skip ? &ts : nullptr); }, 0, -1, -1});
         const float* ec; const float* eu = nullptr;
         if (cfg_on) {
             items.push_back({[self, n](hipStream_t st) { return launch_repeat_batch(self->s_xa, self->s_xin, n, 2, st); }, 0, -1, -1});
@@ -1888,7 +1888,7 @@ struct mkd_ctx {
     int enqueue_state_step(int batch, bool cfg_on, float cfg_scale, hipStream_t stream) {
         const int64_t n = (int64_t)batch * cfg.in_channels * h * w;
         const TembSel ts = temb_sel();
-        int rc = launch_step_setup(s_state, s_t, B, stream, temb_skip ? &ts : nullptr); if (rc) return rc;
+        int rc = launch_step_setup(s_state, s_t, B, s_xa, n, stream, temb_skip ? &ts : nullptr); if (rc) return rc;
         const float* ec; const float* eu = nullptr;
         if (cfg_on) {
             rc = launch_repeat_batch(s_xa, s_xin, n, 2, stream); if (rc) return rc;
@@ -1903,14 +1903,15 @@ struct mkd_ctx {
 
     int sample(const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
                const float* alphas_prev, const float* s1m, float cfg_scale, float* x_out, int use_graph, hipStream_t stream,
-               const float* sigmas = nullptr, const float* noise = nullptr, float temperature = 1.0f) {
-        const int rc = sample_impl(x_T, batch, n_steps, timesteps, alphas, alphas_prev, s1m, cfg_scale, x_out, use_graph, stream, sigmas, noise, temperature);
+               const float* sigmas = nullptr, const float* noise = nullptr, float temperature = 1.0f, const mkd_sample_mask* qm = nullptr) {
+        const int rc = sample_impl(x_T, batch, n_steps, timesteps, alphas, alphas_prev, s1m, cfg_scale, x_out, use_graph, stream, sigmas, noise,
+                                   temperature, qm);
         temb_skip = false;          // (a later mkd_eps runs its own time-embedding chain)
         return rc;
     }
     int sample_impl(const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
                const float* alphas_prev, const float* s1m, float cfg_scale, float* x_out, int use_graph, hipStream_t stream,
-               const float* sigmas, const float* noise, float temperature) {
+               const float* sigmas, const float* noise, float temperature, const mkd_sample_mask* qm) {
         if (!prepared) return mkd_fail(MKD_ERR_STATE, "mkd_sample before mkd_prepare");
         bool stochastic = false;
         if (sigmas) for (int i = 0; i < n_steps; ++i) {
@@ -1923,7 +1924,12 @@ struct mkd_ctx {
             return mkd_fail(MKD_ERR_ARG, "mkd_sample: prepared batch must be B (cfg_scale == 1) or 2B (uncond first)");
         if (n_steps <= 0 || !timesteps || !alphas || !alphas_prev || !s1m || !x_T || !x_out)
             return mkd_fail(MKD_ERR_ARG, "mkd_sample: bad arguments");
+        if (qm && (!qm->x0 || !qm->mask || !qm->noise || !qm->sqrt_alphas_cumprod || !qm->sqrt_one_minus_alphas_cumprod))
+            return mkd_fail(MKD_ERR_ARG, "mkd_sample_masked: x0, mask, noise and both tables are required");
+        if (qm && ((qm->mask_batch != 1 && qm->mask_batch != batch) || (qm->mask_channels != 1 && qm->mask_channels != cfg.in_channels)))
+            return mkd_fail(MKD_ERR_ARG, "mkd_sample_masked: mask must be [1 or B, 1 or C, h, w]");
         const int64_t n = (int64_t)batch * cfg.in_channels * h * w;
+        const int hw = h * w;
         MKD_HIP_CHECK(hipMemcpyAsync(s_xa, x_T, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
         if (use_graph) {
             // --- hipGraph path: one captured step (both streams, fork/join included), replayed n_steps times ---
@@ -1950,6 +1956,15 @@ struct mkd_ctx {
             }
             h_state->noise = stochastic ? noise : nullptr; h_state->temperature = temperature; h_state->n_steps = n_steps;
             h_state->cur_sigma = 0.f; h_state->cur_row = 0;
+            // masked sampling: read by step_setup_kernel; x0 null leaves the (shared) captured step unmasked
+            h_state->x0 = qm ? qm->x0 : nullptr; h_state->mask = qm ? qm->mask : nullptr; h_state->q_noise = qm ? qm->noise : nullptr;
+            h_state->q_hw = hw; h_state->q_chw = cfg.in_channels * hw;
+            h_state->mask_bstride = (qm && qm->mask_batch != 1) ? qm->mask_channels * hw : 0;
+            h_state->mask_cstride = (qm && qm->mask_channels != 1) ? hw : 0;
+            for (int i = 0; i < n_steps; ++i) {
+                h_state->q[2 * i] = qm ? qm->sqrt_alphas_cumprod[i] : 0.f;
+                h_state->q[2 * i + 1] = qm ? qm->sqrt_one_minus_alphas_cumprod[i] : 0.f;
+            }
             MKD_HIP_CHECK(hipEventRecord(ev_loop_in, stream));
             MKD_HIP_CHECK(hipStreamWaitEvent(loop_stream, ev_loop_in, 0));
             MKD_HIP_CHECK(hipMemcpyAsync(s_state, h_state, sizeof(StepState), hipMemcpyHostToDevice, loop_stream));
@@ -2025,6 +2040,11 @@ struct mkd_ctx {
         for (int i = 0; i < n_steps; ++i) {
             const int index = n_steps - 1 - i;
             int rc = launch_fill_i64(s_t, timesteps[index], B, stream); if (rc) return rc;
+            if (qm) {           // (the eager loop's one extra launch per step: the graph folds this blend into its step setup)
+                rc = launch_q_sample_blend(qm->x0, qm->noise + (int64_t)i * n, qm->sqrt_alphas_cumprod[index], qm->sqrt_one_minus_alphas_cumprod[index],
+                                           qm->mask, qm->mask_batch, qm->mask_channels, xa, xa, batch, cfg.in_channels, hw, stream);
+                if (rc) return rc;
+            }
             if (temb_skip) { rc = launch_temb_select(temb_sel(), index, stream); if (rc) return rc; }
             const float* ec; const float* eu = nullptr;
             if (cfg_on) {
@@ -2699,6 +2719,29 @@ int mkd_sample_eta(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const
     if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
     return ctx->sample(x_T, batch, n_steps, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas, cfg_scale, x_out, use_graph,
                        (hipStream_t)stream, sigmas, noise, temperature);
+}
+int mkd_sample_masked(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
+                      const float* alphas_prev, const float* sqrt_one_minus_alphas, const float* sigmas, const float* noise, float temperature,
+                      const mkd_sample_mask* m, float cfg_scale, float* x_out, int use_graph, void* stream) {
+    if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
+    return ctx->sample(x_T, batch, n_steps, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas, cfg_scale, x_out, use_graph,
+                       (hipStream_t)stream, sigmas, noise, temperature, m);
+}
+int mkd_q_sample_blend(const float* x0, const float* noise, float sqrt_ac, float sqrt_one_minus_ac, const float* mask, int mask_batch,
+                       int mask_channels, const float* x, float* out, int batch, int channels, int hw, void* stream) {
+    if (!x0 || !noise || !out || (mask && !x)) return mkd_fail(MKD_ERR_ARG, "mkd_q_sample_blend: null pointer");
+    if (batch <= 0 || channels <= 0 || hw <= 0) return mkd_fail(MKD_ERR_ARG, "mkd_q_sample_blend: empty tensor");
+    if (mask && ((mask_batch != 1 && mask_batch != batch) || (mask_channels != 1 && mask_channels != channels)))
+        return mkd_fail(MKD_ERR_ARG, "mkd_q_sample_blend: mask must be [1 or B, 1 or C, h, w]");
+    return launch_q_sample_blend(x0, noise, sqrt_ac, sqrt_one_minus_ac, mask, mask_batch, mask_channels, x, out, batch, channels, hw,
+                                 (hipStream_t)stream);
+}
+int mkd_latent_mask_from_labels(const uint8_t* labels, int batch, int H, int W, uint64_t classes, int factor, float threshold, float* out,
+                                void* stream) {
+    if (!labels || !out) return mkd_fail(MKD_ERR_ARG, "mkd_latent_mask_from_labels: null pointer");
+    if (batch <= 0 || factor < 1 || factor > 64 || H < factor || W < factor || H % factor || W % factor)
+        return mkd_fail(MKD_ERR_ARG, "mkd_latent_mask_from_labels: H, W must be positive multiples of factor (1..64)");
+    return launch_latent_mask_from_labels(labels, batch, H, W, classes, factor, threshold, out, (hipStream_t)stream);
 }
 // The tile tuner's state (forced tile, XCD mode, per-shape overrides) is PROCESS-global by design: it belongs to the single-kernel
 // entries and to the tuners.  A change bumps the global plan epoch, so EVERY live context re-plans at its next mkd_prepare and a plan

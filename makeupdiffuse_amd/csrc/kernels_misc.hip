@@ -40,7 +40,47 @@ __device__ __forceinline__ void temb_copy_rows(const TembSel& ts, int step, int 
     }
 }
 
-__global__ void step_setup_kernel(StepState* st, int64_t* t_out, int batch, const TembSel ts) {
+// ---- masked sampling (UPSTREAM DDIMSampler.ddim_sampling: img = q_sample(x0, ts) * mask + (1 - mask) * img) ------------------
+// Element i of a [B, C, hw] latent; the mask is read at b * mbs + c * mcs + p (stride 0 broadcasts).  mask null: the q_sample alone.
+// Explicit fmas: the loop kernel and the stand-alone kernel give the same bits whatever the compiler contracts.
+__device__ __forceinline__ float q_sample_blend_at(const float* __restrict__ x0, const float* __restrict__ nz, const float* __restrict__ mask,
+                                                   const float* img, float sa, float s1m, int64_t i, int hw, int chw, int mbs, int mcs) {
+    const float q = fmaf(sa, x0[i], s1m * nz[i]);
+    if (!mask) return q;
+    const int64_t b = i / chw;
+    const int r = (int)(i - b * chw);
+    const int c = r / hw;
+    const float m = mask[b * mbs + (int64_t)c * mcs + (r - c * hw)];
+    return fmaf(m, q, (1.0f - m) * img[i]);
+}
+
+__global__ void q_sample_blend_kernel(const float* __restrict__ x0, const float* __restrict__ nz, float sa, float s1m,
+                                      const float* __restrict__ mask, const float* x, float* out, int64_t n, int hw, int chw, int mbs, int mcs) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = q_sample_blend_at(x0, nz, mask, x, sa, s1m, i, hw, chw, mbs, mcs);
+}
+
+// ---- uint8 label map -> latent mask: fraction of each f x f block whose label is in the class set (area average) ----------------
+__global__ void latent_mask_from_labels_kernel(const uint8_t* __restrict__ labels, int batch, int H, int W, unsigned long long classes,
+                                               int f, float threshold, float* __restrict__ out) {
+    const int h = H / f, w = W / f;
+    const int64_t total = (int64_t)batch * h * w;
+    for (int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (int64_t)gridDim.x * blockDim.x) {
+        const int x = (int)(o % w), y = (int)((o / w) % h);
+        const int64_t b = o / ((int64_t)h * w);
+        const uint8_t* src = labels + (b * H + (int64_t)y * f) * W + (int64_t)x * f;
+        int cnt = 0;
+        for (int dy = 0; dy < f; ++dy)
+            for (int dx = 0; dx < f; ++dx) {
+                const unsigned l = src[(int64_t)dy * W + dx];
+                cnt += (l < 64u) ? (int)((classes >> l) & 1ull) : 0;
+            }
+        const float frac = (float)cnt / (float)(f * f);
+        out[o] = threshold > 0.f ? (frac >= threshold ? 1.0f : 0.0f) : frac;
+    }
+}
+
+__global__ void step_setup_kernel(StepState* st, int64_t* t_out, int batch, const TembSel ts, float* x, int64_t n) {
     const int i = st->counter;          // read-only in this kernel: ddim_step_state_kernel, the step's last, advances it
     if (blockIdx.x == 0) {
         for (int b = threadIdx.x; b < batch; b += blockDim.x) t_out[b] = st->timesteps[i];
@@ -50,7 +90,17 @@ __global__ void step_setup_kernel(StepState* st, int64_t* t_out, int batch, cons
             st->cur_sigma = st->sigma[i]; st->cur_row = st->n_steps - 1 - i;
         }
     }
-    temb_copy_rows(ts, i, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+    const int gtid = blockIdx.x * blockDim.x + threadIdx.x, gthreads = gridDim.x * blockDim.x;
+    temb_copy_rows(ts, i, gtid, gthreads);
+    const float* x0 = st->x0;
+    if (x0) {           // masked: this step's blend.  Coefficients and noise row from the tables through the counter, never from
+                        // cur[] / cur_row, which block 0 of this same kernel writes while the other blocks run
+        const float sa = st->q[2 * i], s1m = st->q[2 * i + 1];
+        const float* nz = st->q_noise + (int64_t)(st->n_steps - 1 - i) * n;
+        const float* mask = st->mask;
+        const int hw = st->q_hw, chw = st->q_chw, mbs = st->mask_bstride, mcs = st->mask_cstride;
+        for (int64_t k = gtid; k < n; k += gthreads) x[k] = q_sample_blend_at(x0, nz, mask, x, sa, s1m, k, hw, chw, mbs, mcs);
+    }
 }
 
 __global__ void temb_select_kernel(const TembSel ts, int step) {
@@ -597,12 +647,16 @@ int launch_temb_select(const TembSel& ts, int step, hipStream_t stream) {
     MKD_LAUNCH_CHECK("temb_select_kernel");
     return 0;
 }
-int launch_step_setup(StepState* st, int64_t* t_out, int batch, hipStream_t stream, const TembSel* tsp) {
+int launch_step_setup(StepState* st, int64_t* t_out, int batch, float* x, int64_t n, hipStream_t stream, const TembSel* tsp) {
     TembSel ts; memset(&ts, 0, sizeof(ts));
     if (tsp) ts = *tsp;
     if ((ts.n[0] | ts.n[1]) & 3) return mkd_fail(-1, "step_setup: row lengths must be multiples of 4");
-    const int blocks = (ts.n[0] || ts.n[1]) ? temb_blocks(ts) : 1;
-    hipLaunchKernelGGL(step_setup_kernel, dim3(blocks), dim3(256), 0, stream, st, t_out, batch, ts);
+    if (!x || n <= 0) return mkd_fail(-1, "step_setup: no latent");
+    int blocks = (ts.n[0] || ts.n[1]) ? temb_blocks(ts) : 1;
+    // (the latent of a masked step: ~8 elements per thread; at the benchmark's shapes the time-embedding rows already need more)
+    const int xb = grid_for((n + 7) / 8, 256, 512);
+    if (xb > blocks) blocks = xb;
+    hipLaunchKernelGGL(step_setup_kernel, dim3(blocks), dim3(256), 0, stream, st, t_out, batch, ts, x, n);
     MKD_LAUNCH_CHECK("step_setup_kernel");
     return 0;
 }
@@ -632,5 +686,30 @@ int launch_blend(const bf16_t* a, const bf16_t* b, const float* alpha, bf16_t* y
     if (per_sample % 8) return mkd_fail(-1, "blend: per-sample size must be a multiple of 8");
     hipLaunchKernelGGL(blend_kernel, dim3(grid_for(per_sample * batch / 8)), dim3(256), 0, stream, a, b, alpha, y, per_sample, batch);
     MKD_LAUNCH_CHECK("blend_kernel");
+    return 0;
+}
+
+int launch_q_sample_blend(const float* x0, const float* noise, float sqrt_ac, float sqrt_1m_ac, const float* mask, int mask_batch,
+                          int mask_channels, const float* x, float* out, int batch, int channels, int hw, hipStream_t stream) {
+    if (!x0 || !noise || !out || batch <= 0 || channels <= 0 || hw <= 0) return mkd_fail(-1, "q_sample_blend: bad arguments");
+    if (mask && (!x || (mask_batch != 1 && mask_batch != batch) || (mask_channels != 1 && mask_channels != channels)))
+        return mkd_fail(-1, "q_sample_blend: mask must be [1 or B, 1 or C, h, w] and needs x");
+    const int64_t n = (int64_t)batch * channels * hw;
+    const int mcs = mask_channels == 1 ? 0 : hw;
+    const int mbs = mask_batch == 1 ? 0 : mask_channels * hw;
+    hipLaunchKernelGGL(q_sample_blend_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x0, noise, sqrt_ac, sqrt_1m_ac, mask, x, out, n, hw,
+                       channels * hw, mbs, mcs);
+    MKD_LAUNCH_CHECK("q_sample_blend_kernel");
+    return 0;
+}
+
+int launch_latent_mask_from_labels(const uint8_t* labels, int batch, int H, int W, uint64_t classes, int f, float threshold, float* out,
+                                   hipStream_t stream) {
+    if (!labels || !out || batch <= 0 || f < 1 || f > 64 || H < f || W < f || H % f || W % f)
+        return mkd_fail(-1, "latent_mask_from_labels: labels [B, H, W] with H, W multiples of the factor (1..64)");
+    const int64_t total = (int64_t)batch * (H / f) * (W / f);
+    hipLaunchKernelGGL(latent_mask_from_labels_kernel, dim3(grid_for(total)), dim3(256), 0, stream, labels, batch, H, W,
+                       (unsigned long long)classes, f, threshold, out);
+    MKD_LAUNCH_CHECK("latent_mask_from_labels_kernel");
     return 0;
 }

@@ -135,6 +135,12 @@ struct StepState {
     float sigma[MKD_MAX_STEPS];
     const float* noise; float temperature; int n_steps;
     float cur_sigma; int cur_row;
+    // masked sampling (UPSTREAM DDIMSampler.ddim_sampling mask / x0): step_setup_kernel first blends the latent with q_sample(x0),
+    // x <- (q[2i] x0 + q[2i+1] q_noise[row]) mask + (1 - mask) x, row = the executed step (n_steps - 1 - i).  x0 null: unmasked.
+    // mask [mB, mC, h, w] is read at b * mask_bstride + c * mask_cstride + p (stride 0 broadcasts); q_hw = h * w, q_chw = C * h * w
+    const float* x0; const float* mask; const float* q_noise;
+    int mask_bstride, mask_cstride, q_hw, q_chw;
+    float q[2 * MKD_MAX_STEPS];            // sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod of table entry i
 };
 
 // Time embedding of a sampling call: row `step` of tab[k] ([steps, n[k]] fp32, one table per net) is copied into every one of
@@ -241,9 +247,18 @@ int launch_ddim_step(const float* x, const float* eps_c, const float* eps_u, flo
                      float* x_prev, float* pred_x0, int64_t n, hipStream_t stream);
 int launch_repeat_batch(const float* x, float* y, int64_t n_per, int reps, hipStream_t stream);
 int launch_fill_i64(int64_t* p, int64_t v, int n, hipStream_t stream);
-// first kernel of a replayed step: timestep / coefficients of step st->counter (+ the step's time-embedding rows when ts != null).
+// first kernel of a replayed step: timestep / coefficients of step st->counter (+ the step's time-embedding rows when ts != null,
+// + the masked-sampling blend of the latent x [n] when st->x0 != null; the grid always covers x, so one capture serves both).
 // The counter itself is advanced by the step's LAST kernel (launch_ddim_step_state), so every workgroup here reads the same value.
-int launch_step_setup(StepState* st, int64_t* t_out, int batch, hipStream_t stream, const TembSel* ts = nullptr);
+int launch_step_setup(StepState* st, int64_t* t_out, int batch, float* x, int64_t n, hipStream_t stream, const TembSel* ts = nullptr);
+// out = (sqrt_ac x0 + sqrt_1m_ac noise) mask + (1 - mask) x over [batch, channels, hw]; mask [mask_batch, mask_channels, hw] broadcast
+// (mask_batch in {1, batch}, mask_channels in {1, channels}); mask null: out = the q_sample alone (x unused).  out may be x.
+int launch_q_sample_blend(const float* x0, const float* noise, float sqrt_ac, float sqrt_1m_ac, const float* mask, int mask_batch,
+                          int mask_channels, const float* x, float* out, int batch, int channels, int hw, hipStream_t stream);
+// labels [batch, H, W] uint8 -> out [batch, 1, H/f, W/f]: the fraction of each f x f block whose label is in `classes` (bit l = label l);
+// threshold > 0: 1 where that fraction >= threshold, else 0
+int launch_latent_mask_from_labels(const uint8_t* labels, int batch, int H, int W, uint64_t classes, int f, float threshold, float* out,
+                                   hipStream_t stream);
 int launch_temb_select(const TembSel& ts, int step, hipStream_t stream);          // the same copy with a host-side step index (eager loop)
 int launch_ddim_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
                            hipStream_t stream);

@@ -18,6 +18,19 @@ def noise_like(shape, device, repeat=False):
     return torch.randn(shape, device=device)
 
 
+def _check_mask(mask, x0, shape):
+    """mask / x0 of masked sampling: x0 [B,C,h,w] (the un-doubled batch), mask [1|B, 1|C, h, w]; a mask needs an x0"""
+    if mask is None:
+        return
+    if x0 is None:
+        raise ValueError('DDIMSampler: mask needs x0 (the latent to keep where mask = 1)')
+    B, C, H, W = shape
+    if tuple(x0.shape) != (B, C, H, W):
+        raise ValueError(f'DDIMSampler: x0 must be {(B, C, H, W)}, got {tuple(x0.shape)}')
+    if mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, C) or tuple(mask.shape[2:]) != (H, W):
+        raise ValueError(f'DDIMSampler: mask must be [1 or {B}, 1 or {C}, {H}, {W}], got {tuple(mask.shape)}')
+
+
 def _cat_cond(uncond, c):
     """CFG batching, unconditional FIRST (diffmk/cddim.py:18-38)."""
     if isinstance(c, dict):
@@ -74,22 +87,27 @@ class DDIMSampler:
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, eta=0.0, temperature=1.0, noise_dropout=0.0,
                x_T=None, log_every_t=100, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
                verbose=True, **kwargs):
-        for k in ('mask', 'x0', 'score_corrector', 'corrector_kwargs', 'dynamic_threshold', 'ucg_schedule'):
+        for k in ('score_corrector', 'corrector_kwargs', 'dynamic_threshold', 'ucg_schedule'):
             if kwargs.get(k) is not None:
                 raise NotImplementedError(f'DDIMSampler.sample option {k} is not on the MakeupDiffuse path')
         if kwargs.get('quantize_x0', False):
             raise NotImplementedError('quantize_x0')
-        self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
         size = (batch_size, C, H, W)
+        mask, x0 = kwargs.get('mask'), kwargs.get('x0')
+        _check_mask(mask, x0, size)
+        self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         return self.ddim_sampling(conditioning, size, callback=callback, x_T=x_T, log_every_t=log_every_t,
                                   temperature=temperature, noise_dropout=noise_dropout,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning)
+                                  unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, callback=None, log_every_t=100, temperature=1.0, noise_dropout=0.0,
-                      unconditional_guidance_scale=1.0, unconditional_conditioning=None, timesteps=None):
+                      unconditional_guidance_scale=1.0, unconditional_conditioning=None, timesteps=None, mask=None, x0=None):
+        """mask / x0 (UPSTREAM): before step i, img = q_sample(x0, ts) * mask + (1 - mask) * img with a fresh randn_like(x0) drawn
+        BEFORE the step's eta draw; mask = 1 keeps x0, no blend after the last step."""
+        _check_mask(mask, x0, tuple(shape))
         device = self.model.device
         b = shape[0]
         img = torch.randn(shape, device=device) if x_T is None else x_T
@@ -103,11 +121,18 @@ class DDIMSampler:
             # the whole loop runs inside libmkd (mkd_sample / mkd_sample_eta); no per-step host work.  eta > 0: the draws of the
             # stochastic branch (cddim.py:74-78) are taken here, one per step with sigma_t != 0 in loop order - the generator is
             # consumed exactly as by the step-by-step loop below - and handed over as one [steps, ...] tensor
+            # masked: the blend's draws too, each step's BEFORE its eta draw (the step loop's order), with the DDPM tables at the
+            # step's timestep
             sig = self.ddim_sigmas[:total_steps]
             kw = {}
-            if float(sig.abs().max()) != 0.0:
-                draws = []
+            stochastic = float(sig.abs().max()) != 0.0
+            if stochastic or mask is not None:
+                draws, q_draws = [], []
                 for i in range(total_steps):
+                    if mask is not None:
+                        q_draws.append(torch.randn_like(x0))
+                    if not stochastic:
+                        continue
                     if float(sig[total_steps - i - 1]) != 0.0:
                         nz = noise_like(tuple(shape), device, False)
                         if noise_dropout > 0.0:
@@ -115,7 +140,12 @@ class DDIMSampler:
                     else:
                         nz = torch.zeros(tuple(shape), device=device)
                     draws.append(nz)
-                kw = dict(sigmas=sig, noise=torch.stack(draws), temperature=temperature)
+                if stochastic:
+                    kw = dict(sigmas=sig, noise=torch.stack(draws), temperature=temperature)
+                if mask is not None:
+                    sa, s1 = self._q_tables()
+                    kw.update(x0=x0, mask=mask, q_sqrt_ac=[float(sa[int(t)]) for t in timesteps],
+                              q_sqrt_1m_ac=[float(s1[int(t)]) for t in timesteps], q_noise=torch.stack(q_draws))
             img = fast(img, cond, timesteps, self.ddim_alphas[:total_steps], self.ddim_alphas_prev[:total_steps],
                        self.ddim_sqrt_one_minus_alphas[:total_steps], unconditional_guidance_scale,
                        unconditional_conditioning, **kw)
@@ -124,6 +154,8 @@ class DDIMSampler:
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
+            if mask is not None:
+                img = self._q_blend(x0, int(step), mask, img)
             img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, temperature=temperature,
                                               noise_dropout=noise_dropout,
                                               unconditional_guidance_scale=unconditional_guidance_scale,
@@ -194,6 +226,45 @@ class DDIMSampler:
         if noise is not None:
             x_prev = x_prev + sigma_t * noise * temperature
         return x_prev, pred_x0
+
+    # -- masked sampling / q_sample (UPSTREAM LatentDiffusion.q_sample as ddim_sampling uses it, DDIMSampler.stochastic_encode) --
+    def _q_tables(self):
+        return self.model.sqrt_alphas_cumprod, self.model.sqrt_one_minus_alphas_cumprod
+
+    def _q_blend(self, x0, step, mask, img):
+        """img = q_sample(x0, step) * mask + (1 - mask) * img with a fresh randn_like(x0); on the device through the model's hook"""
+        sa, s1 = self._q_tables()
+        a, b = float(sa[step]), float(s1[step])
+        noise = torch.randn_like(x0)
+        return self._q_sample_blend(x0, noise, a, b, mask, img)
+
+    def _q_sample_blend(self, x0, noise, a, b, mask=None, img=None):
+        hook = getattr(self.model, 'q_sample_blend', None)
+        if hook is not None and x0.is_cuda:
+            return hook(x0, noise, a, b, mask, img)
+        # host tensors (a stand-in model, e.g. CPU tests): the same formula in torch
+        q = a * x0 + b * noise
+        return q if mask is None else q * mask + (1.0 - mask) * img
+
+    @torch.no_grad()
+    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None):
+        """UPSTREAM DDIMSampler.stochastic_encode: sqrt(ddim_alphas)[t] x0 + ddim_sqrt_one_minus_alphas[t] noise (the full DDPM tables
+        with use_original_steps); t [B] indexes the table.  With decode(x, cond, t_start) it gives img2img."""
+        if use_original_steps:
+            sa, s1 = self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod
+        else:
+            sa, s1 = torch.sqrt(self.ddim_alphas), self.ddim_sqrt_one_minus_alphas
+        if noise is None:
+            noise = torch.randn_like(x0)
+        t = torch.as_tensor(t).reshape(-1).cpu().long()
+        if t.numel() == 1:
+            t = t.expand(x0.shape[0])
+        if t.numel() != x0.shape[0]:
+            raise ValueError(f'stochastic_encode: t has {t.numel()} entries for a batch of {x0.shape[0]}')
+        if bool((t == t[0]).all()):
+            return self._q_sample_blend(x0, noise, float(sa[int(t[0])]), float(s1[int(t[0])]))
+        return torch.cat([self._q_sample_blend(x0[i:i + 1], noise[i:i + 1], float(sa[int(t[i])]), float(s1[int(t[i])]))
+                          for i in range(x0.shape[0])])
 
     # -- DDIM inversion (UPSTREAM DDIMSampler.encode; reference pre_dataset.py InvRec) and its reverse loop --
     @torch.no_grad()

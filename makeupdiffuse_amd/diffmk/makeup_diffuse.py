@@ -265,18 +265,31 @@ class BaseMakeUpDiffuse:
     def ddim_step(self, x, e_c, e_u, scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature):
         return self._require_engine().ddim_step(x, e_c, e_u, scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature)
 
+    def q_sample_blend(self, x0, noise, sqrt_ac, sqrt_1m_ac, mask=None, x=None):
+        """(sqrt_ac x0 + sqrt_1m_ac noise) * mask + (1 - mask) * x: the masked sampler's blend (mask None: q_sample), same kernel
+        arithmetic as the in-library loop"""
+        return self._require_engine().q_sample_blend(x0, noise, sqrt_ac, sqrt_1m_ac, mask, x)
+
     # hipGraph replay of the sampling loop (one captured step, five steps per graph): the configuration bench.py measures.  False: eager
     sample_use_graph = True
 
     def sample_loop_fast(self, x_latent, cond, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas,
-                         unconditional_guidance_scale=1.0, unconditional_conditioning=None, sigmas=None, noise=None, temperature=1.0):
+                         unconditional_guidance_scale=1.0, unconditional_conditioning=None, sigmas=None, noise=None, temperature=1.0,
+                         x0=None, mask=None, q_sqrt_ac=None, q_sqrt_1m_ac=None, q_noise=None):
         cfg_on = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
         c = self.cfg_conditioning(unconditional_conditioning, cond) if cfg_on else cond
         eng = self._bind_cond(c, x_latent.shape[2:])
         return eng.sample(x_latent, [int(v) for v in timesteps], [float(v) for v in alphas], [float(v) for v in alphas_prev],
                           [float(v) for v in sqrt_one_minus_alphas],
                           cfg_scale=float(unconditional_guidance_scale) if cfg_on else 1.0, use_graph=bool(self.sample_use_graph),
-                          sigmas=None if sigmas is None else [float(v) for v in sigmas], noise=noise, temperature=float(temperature))
+                          sigmas=None if sigmas is None else [float(v) for v in sigmas], noise=noise, temperature=float(temperature),
+                          x0=x0, mask=mask, q_sqrt_ac=q_sqrt_ac, q_sqrt_1m_ac=q_sqrt_1m_ac, q_noise=q_noise)
+
+    def latent_mask_from_labels(self, seg: torch.Tensor, classes: Sequence[int] = (0, 11, 12), factor: int = 8,
+                                threshold: float = 0.5) -> torch.Tensor:
+        """Label map [B,H,W] (uint8) -> latent mask [B,1,H/factor,W/factor] on the device: the area fraction of each block whose label
+        is in ``classes``; threshold > 0 makes it binary (fraction >= threshold)."""
+        return self._require_engine().latent_mask_from_labels(seg, classes, factor, threshold)
 
     # ---- sampling drivers ----------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -372,8 +385,15 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
 
     def __init__(self, saved_dir: str = './results', model_name: str = 'makeupdiffuse', img_name_key: str = 'img_name',
                  unconditional_guidance_scale: float = 9, ddim_steps: int = 50, ddim_eta: float = 0.0, sample: bool = True,
-                 *args, **kwargs):
+                 fix_background: bool = False, background_classes: Sequence[int] = (0, 11, 12), background_threshold: float = 0.5,
+                 seg_key: str = 'nonmakeup_seg', *args, **kwargs):
         super().__init__(*args, **kwargs)
+        # background-preserving transfer (reference Fixbackground classes: background 0, teeth 11, hair 12): both sampling passes
+        # keep the source's latent where the label map says so (DDIMSampler mask / x0)
+        self.fix_background = bool(fix_background)
+        self.background_classes = tuple(int(c) for c in background_classes)
+        self.background_threshold = float(background_threshold)
+        self.seg_key = seg_key
         self.unconditional_guidance_scale = unconditional_guidance_scale
         self.ddim_steps, self.ddim_eta, self.sample = ddim_steps, ddim_eta, sample
         self.saved_dir, self.model_name, self.img_name_key = saved_dir, model_name, img_name_key
@@ -412,6 +432,10 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                                         'makeup/%s.png' % nm.split('&')[1]])
         b = c_cat.shape[0]
         extra = {} if x_T is None else {'x_T': x_T}
+        if self.fix_background:
+            x0, mask = self.background_latents(batch, c['src_img'])
+            extra.update(x0=x0, mask=mask)
+            log['mask_latent'] = mask
         cond = {'c_concat': [c_cat], 'c_crossattn': [c_txt]}
         if self.sample:
             samples, _ = self.sample_log(cond=cond, batch_size=b, ddim=use_ddim, ddim_steps=self.ddim_steps,
@@ -429,6 +453,21 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             if self.has_first_stage:
                 log[name] = self.decode_first_stage(samples_cfg)
         return log
+
+    @torch.no_grad()
+    def background_latents(self, batch: dict, src: torch.Tensor):
+        """fix_background: x0 = get_z(src * 2 - 1) and the latent mask of batch[seg_key] over background_classes."""
+        if not self.first_stage_encoder:
+            raise ValueError('fix_background needs the first-stage encoder: construct with first_stage_encoder=True')
+        if self.seg_key not in batch:
+            raise KeyError(f"fix_background: the batch has no label map under '{self.seg_key}'")
+        seg = batch[self.seg_key]
+        lw = src.shape[-1] // 8
+        if lw <= 0 or seg.shape[-1] % lw:
+            raise ValueError(f'fix_background: label map width {seg.shape[-1]} is not a multiple of the latent width {lw}')
+        mask = self.latent_mask_from_labels(seg, self.background_classes, seg.shape[-1] // lw, self.background_threshold)
+        x0 = self.get_z(src * 2.0 - 1.0)
+        return x0, mask
 
     @torch.no_grad()
     def interpolate(self, batch: dict, alphas, x_T: Optional[torch.Tensor] = None, ref2_key: str = 'ref_img2',

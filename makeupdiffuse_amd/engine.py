@@ -427,9 +427,13 @@ class MkdEngine:
 
     def sample(self, x_T: torch.Tensor, timesteps: Sequence[int], alphas: Sequence[float], alphas_prev: Sequence[float],
                sqrt_one_minus_alphas: Sequence[float], cfg_scale: float = 1.0, use_graph: bool = False,
-               sigmas: Optional[Sequence[float]] = None, noise: Optional[torch.Tensor] = None, temperature: float = 1.0) -> torch.Tensor:
+               sigmas: Optional[Sequence[float]] = None, noise: Optional[torch.Tensor] = None, temperature: float = 1.0,
+               x0: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, q_sqrt_ac: Optional[Sequence[float]] = None,
+               q_sqrt_1m_ac: Optional[Sequence[float]] = None, q_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Whole reverse loop in one call (cddim.py:81-100). Prepared batch must be B or 2B (CFG).  eta > 0 (cddim.py:74-78):
-        ``sigmas`` like the other tables and ``noise`` [n_steps, B, 4, h, w], row k = the draw of the k-th executed step."""
+        ``sigmas`` like the other tables and ``noise`` [n_steps, B, 4, h, w], row k = the draw of the k-th executed step.
+        Masked sampling (include/mkd.h mkd_sample_masked): ``x0`` [B,4,h,w], ``mask`` [1|B, 1|4, h, w] (1 keeps x0), the DDPM
+        tables at each entry's timestep ``q_sqrt_ac`` / ``q_sqrt_1m_ac`` (indexed like ``alphas``) and ``q_noise`` [n_steps, B, 4, h, w]."""
         x_T = _f32c(x_T, self.device)
         cfg_on = float(cfg_scale) != 1.0
         want_b = self.batch // 2 if cfg_on else self.batch
@@ -447,6 +451,10 @@ class MkdEngine:
         ap = (C.c_float * n)(*[float(v) for v in alphas_prev])
         s1 = (C.c_float * n)(*[float(v) for v in sqrt_one_minus_alphas])
         out = torch.empty_like(x_T)
+        qm = None
+        if mask is not None or x0 is not None:
+            qm, keep = self._sample_mask(x_T, n, x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise)
+        sg = None
         if sigmas is not None and any(float(v) != 0.0 for v in sigmas):
             if len(sigmas) != n:
                 raise ValueError('sigmas must be as long as timesteps')
@@ -454,17 +462,104 @@ class MkdEngine:
                 raise ValueError(f'eta > 0 needs noise of shape {(n, *x_T.shape)} (one draw per executed step)')
             noise = _f32c(noise, self.device)
             sg = (C.c_float * n)(*[float(v) for v in sigmas])
-            with torch.cuda.device(self.device):
+        else:
+            noise = None
+        with torch.cuda.device(self.device):
+            if qm is not None:
+                _lib.check(self.lib.mkd_sample_masked(self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, s1, sg,
+                                                      C.c_void_p(_ptr(noise)), float(temperature), C.byref(qm), float(cfg_scale),
+                                                      C.c_void_p(out.data_ptr()), int(use_graph), C.c_void_p(_stream())), 'mkd_sample_masked')
+                # no host wait: the caller's stream waits for the replayed loop, so the caching allocator can only hand these blocks to
+                # work ordered after it; they are also held until the next masked call
+                self._loop_keep = (keep, noise)
+            elif sg is not None:
                 _lib.check(self.lib.mkd_sample_eta(self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, s1, sg,
                                                    C.c_void_p(noise.data_ptr()), float(temperature), float(cfg_scale),
                                                    C.c_void_p(out.data_ptr()), int(use_graph), C.c_void_p(_stream())), 'mkd_sample_eta')
                 if use_graph:
                     torch.cuda.synchronize(self.device)          # the replayed loop reads `noise` after this call returns: keep it alive
-            return out
+            else:
+                _lib.check(self.lib.mkd_sample(self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, s1,
+                                               float(cfg_scale), C.c_void_p(out.data_ptr()), int(use_graph),
+                                               C.c_void_p(_stream())), 'mkd_sample')
+        return out
+
+    def _mask_geometry(self, mask: torch.Tensor, B: int, Cn: int, hw) -> Tuple[int, int]:
+        if mask.dim() != 4 or tuple(mask.shape[2:]) != tuple(hw) or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, Cn):
+            raise ValueError(f'mask must be [1 or {B}, 1 or {Cn}, {hw[0]}, {hw[1]}], got {tuple(mask.shape)}')
+        return int(mask.shape[0]), int(mask.shape[1])
+
+    def _sample_mask(self, x_T, n, x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise):
+        """Validated mkd_sample_mask for sample(); returns it with the tensors / arrays it points at."""
+        if x0 is None or mask is None:
+            raise ValueError('masked sampling needs both mask and x0')
+        x0 = _f32c(x0, self.device)
+        if tuple(x0.shape) != tuple(x_T.shape):
+            raise ValueError(f'x0 must be [{", ".join(map(str, x_T.shape))}] (the un-doubled batch), got {tuple(x0.shape)}')
+        mb, mc = self._mask_geometry(mask, x_T.shape[0], x_T.shape[1], x_T.shape[2:])
+        mask = _f32c(mask, self.device)
+        if q_sqrt_ac is None or q_sqrt_1m_ac is None or len(q_sqrt_ac) != n or len(q_sqrt_1m_ac) != n:
+            raise ValueError('masked sampling needs q_sqrt_ac and q_sqrt_1m_ac as long as timesteps')
+        if q_noise is None or tuple(q_noise.shape) != (n, *x_T.shape):
+            raise ValueError(f'masked sampling needs q_noise of shape {(n, *x_T.shape)} (one draw per executed step)')
+        q_noise = _f32c(q_noise, self.device)
+        qa = (C.c_float * n)(*[float(v) for v in q_sqrt_ac])
+        qb = (C.c_float * n)(*[float(v) for v in q_sqrt_1m_ac])
+        qm = _lib.SampleMaskC(x0.data_ptr(), mask.data_ptr(), mb, mc, C.cast(qa, C.POINTER(C.c_float)), C.cast(qb, C.POINTER(C.c_float)),
+                              q_noise.data_ptr())
+        return qm, (x0, mask, q_noise, qa, qb)
+
+    def q_sample_blend(self, x0: torch.Tensor, noise: torch.Tensor, sqrt_ac: float, sqrt_1m_ac: float,
+                       mask: Optional[torch.Tensor] = None, x: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(sqrt_ac x0 + sqrt_1m_ac noise) * mask + (1 - mask) * x on the device (mkd_q_sample_blend); mask None: the q_sample alone.
+        x0, noise, x [B,C,h,w]; mask [1|B, 1|C, h, w]."""
+        x0 = _f32c(x0, self.device)
+        noise = _f32c(noise, self.device)
+        if x0.dim() != 4 or tuple(noise.shape) != tuple(x0.shape):
+            raise ValueError(f'x0 and noise must be equal [B,C,h,w] tensors, got {tuple(x0.shape)} and {tuple(noise.shape)}')
+        B, Cn, h, w = x0.shape
+        mb = mc = 1
+        if mask is not None:
+            if x is None or tuple(x.shape) != tuple(x0.shape):
+                raise ValueError('a masked blend needs x of the shape of x0')
+            mb, mc = self._mask_geometry(mask, B, Cn, (h, w))
+            mask = _f32c(mask, self.device)
+            x = _f32c(x, self.device)
+        else:
+            x = None
+        out = torch.empty_like(x0)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.mkd_sample(self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, s1,
-                                           float(cfg_scale), C.c_void_p(out.data_ptr()), int(use_graph),
-                                           C.c_void_p(_stream())), 'mkd_sample')
+            _lib.check(self.lib.mkd_q_sample_blend(C.c_void_p(x0.data_ptr()), C.c_void_p(noise.data_ptr()), float(sqrt_ac), float(sqrt_1m_ac),
+                                                   C.c_void_p(_ptr(mask)), mb, mc, C.c_void_p(_ptr(x)), C.c_void_p(out.data_ptr()),
+                                                   B, Cn, h * w, C.c_void_p(_stream())), 'mkd_q_sample_blend')
+        return out
+
+    def latent_mask_from_labels(self, seg: torch.Tensor, classes: Iterable[int] = (0, 11, 12), factor: int = 8,
+                                threshold: float = 0.5) -> torch.Tensor:
+        """Label map [B,H,W] or [B,1,H,W] (uint8, labels 0..63) -> [B,1,H/factor,W/factor] fp32: the fraction of each factor x factor
+        block whose label is in ``classes`` (F.interpolate(mode='area') of the binary mask); threshold > 0: that fraction >= threshold."""
+        if seg.dim() == 4 and seg.shape[1] == 1:
+            seg = seg[:, 0]
+        if seg.dim() != 3:
+            raise ValueError(f'seg must be [B,H,W] or [B,1,H,W], got {tuple(seg.shape)}')
+        if seg.dtype != torch.uint8:
+            if seg.is_floating_point() or int(seg.min()) < 0 or int(seg.max()) > 255:
+                raise ValueError('seg must hold integer labels 0..255')
+            seg = seg.to(torch.uint8)
+        bits = 0
+        for c in classes:
+            if not 0 <= int(c) < 64:
+                raise ValueError(f'class {c} outside 0..63')
+            bits |= 1 << int(c)
+        B, H, W = seg.shape
+        if factor < 1 or H % factor or W % factor:
+            raise ValueError(f'seg {H}x{W} is not a multiple of factor {factor}')
+        lab = seg.to(self.device).contiguous()
+        out = torch.empty((B, 1, H // factor, W // factor), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mkd_latent_mask_from_labels(C.c_void_p(lab.data_ptr()), B, H, W, C.c_uint64(bits), int(factor),
+                                                            float(threshold), C.c_void_p(out.data_ptr()), C.c_void_p(_stream())),
+                       'mkd_latent_mask_from_labels')
         return out
 
     def eps_profile(self, x: torch.Tensor, t: torch.Tensor, csv_path: Optional[str] = None) -> Dict[str, Dict[str, float]]:

@@ -78,7 +78,8 @@ def read_pairs(path: str) -> List[Tuple[str, str]]:
 
 
 class PairFolderDataset:
-    """root/images/<name> + a pairs file -> dicts with the keys get_input reads."""
+    """root/images/<name> + a pairs file -> dicts with the keys get_input reads.  When root/scgan_segs/ exists (reference
+    TestFixed_Dataset layout: one label map per image, labels 0..14) the pair also carries nonmakeup_seg / makeup_seg, uint8 [H, W]."""
 
     def __init__(self, root: str, pairs_file: str = 'test_0412.txt', dim: Sequence[int] = (256, 256), prompt: str = 'makeup transfer'):
         self.root = root
@@ -97,12 +98,24 @@ class PairFolderDataset:
         a = np.asarray(img, dtype=np.float32) / 255.0
         return torch.from_numpy(a).permute(2, 0, 1).contiguous()
 
+    def _load_seg(self, name: str) -> torch.Tensor:
+        from PIL import Image
+        seg = Image.open(os.path.join(self.root, 'scgan_segs', name))
+        if seg.mode not in ('L', 'P'):
+            seg = seg.convert('L')
+        if self.dim and seg.size != (self.dim[1], self.dim[0]):
+            seg = seg.resize((self.dim[1], self.dim[0]), Image.NEAREST)          # labels: no interpolation between classes
+        return torch.from_numpy(np.array(seg, dtype=np.uint8))
+
     def __getitem__(self, i: int) -> Dict[str, object]:
         s, r = self.pairs[i]
         src, ref = self._load(s), self._load(r)
         base = lambda n: os.path.basename(n).split('.')[0]
-        return {'src_img': src, 'ref_img': ref, 'nonmakeup_img': src * 2 - 1, 'makeup_img': ref * 2 - 1,
-                'txt': self.prompt, 'img_name': f'{base(s)}&{base(r)}'}
+        out = {'src_img': src, 'ref_img': ref, 'nonmakeup_img': src * 2 - 1, 'makeup_img': ref * 2 - 1,
+               'txt': self.prompt, 'img_name': f'{base(s)}&{base(r)}'}
+        if os.path.isdir(os.path.join(self.root, 'scgan_segs')):
+            out['nonmakeup_seg'], out['makeup_seg'] = self._load_seg(s), self._load_seg(r)
+        return out
 
 
 def collate(items: Sequence[Dict[str, object]]) -> Dict[str, object]:

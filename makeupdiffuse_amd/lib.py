@@ -36,6 +36,12 @@ class NetConfigC(C.Structure):
     ]
 
 
+class SampleMaskC(C.Structure):
+    _fields_ = [('x0', C.c_void_p), ('mask', C.c_void_p), ('mask_batch', C.c_int32), ('mask_channels', C.c_int32),
+                ('sqrt_alphas_cumprod', C.POINTER(C.c_float)), ('sqrt_one_minus_alphas_cumprod', C.POINTER(C.c_float)),
+                ('noise', C.c_void_p)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -65,6 +71,10 @@ SIGNATURES = {
     'mkd_ddim_step': (_I, [_P, _P, _P, _F, _F, _F, _F, _F, _P, _F, _P, _P, _L, _P]),
     'mkd_sample': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _F, _P, _I, _P]),
     'mkd_sample_eta': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _P, _F, _F, _P, _I, _P]),
+    'mkd_sample_masked': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _P, _F,
+                               C.POINTER(SampleMaskC), _F, _P, _I, _P]),
+    'mkd_q_sample_blend': (_I, [_P, _P, _F, _F, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
+    'mkd_latent_mask_from_labels': (_I, [_P, _I, _I, _I, C.c_uint64, _I, _F, _P, _P]),
     'mkd_vae_configure': (_I, [_P, C.POINTER(VaeConfigC)]),
     'mkd_vae_finalize': (_I, [_P]),
     'mkd_decode': (_I, [_P, _P, _I, _I, _I, _F, _P, _P]),

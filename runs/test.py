@@ -20,15 +20,29 @@ from makeupdiffuse_amd import dist as mdist  # noqa: E402
 from makeupdiffuse_amd.config import create_model, load_state_dict  # noqa: E402
 
 
-def synthetic_batch(lo, hi, res, ctx_dim):
+def synthetic_seg(i, res):
+    """a stand-in face-parsing map for pair i: background (0) outside an ellipse, hair (12) on its top, skin (1) inside"""
+    g = torch.Generator().manual_seed(1213 + i)
+    cy, cx = res * (0.5 + 0.1 * (torch.rand(2, generator=g) - 0.5))
+    yy, xx = torch.meshgrid(torch.arange(res, dtype=torch.float32), torch.arange(res, dtype=torch.float32), indexing='ij')
+    inside = ((yy - cy) / (0.4 * res)) ** 2 + ((xx - cx) / (0.3 * res)) ** 2 <= 1.0
+    seg = torch.where(inside, torch.ones((), dtype=torch.uint8), torch.zeros((), dtype=torch.uint8))
+    seg[inside & (yy < cy - 0.25 * res)] = 12
+    return seg
+
+
+def synthetic_batch(lo, hi, res, ctx_dim, with_seg=False):
     src, ref, txt = [], [], []
     for i in range(lo, hi):
         g = torch.Generator().manual_seed(5678 + i)
         src.append(torch.rand(1, 3, res, res, generator=g)); ref.append(torch.rand(1, 3, res, res, generator=g))
         g = torch.Generator().manual_seed(91011 + i)
         txt.append(torch.randn(1, 77, ctx_dim, generator=g))
-    return {'src_img': torch.cat(src), 'ref_img': torch.cat(ref), 'txt_emb': torch.cat(txt),
-            'txt': ['makeup transfer'] * (hi - lo), 'img_name': [f'{i:04d}&{i:04d}' for i in range(lo, hi)]}
+    batch = {'src_img': torch.cat(src), 'ref_img': torch.cat(ref), 'txt_emb': torch.cat(txt),
+             'txt': ['makeup transfer'] * (hi - lo), 'img_name': [f'{i:04d}&{i:04d}' for i in range(lo, hi)]}
+    if with_seg:
+        batch['nonmakeup_seg'] = torch.stack([synthetic_seg(i, res) for i in range(lo, hi)])
+    return batch
 
 
 def main():
@@ -47,10 +61,16 @@ def main():
     ap.add_argument('--seed', type=int, default=None, help='start noise x_T drawn per PAIR from seed + pair index (results independent of '
                     'batch size / sharding); default: torch.randn like the reference')
     ap.add_argument('--txt-emb', default=None, help='.pt/.safetensors with a [1,77,768] tensor: the CLIP embedding of the prompt (offline stand-in)')
+    ap.add_argument('--fix-background', action='store_true', help="keep the source's background, teeth and hair (label map "
+                    "nonmakeup_seg from <data-root>/scgan_segs, a synthetic one otherwise; needs the first-stage encoder)")
     args = ap.parse_args()
 
     rank, world, local = mdist.init_from_env()
     model = create_model(args.config).cpu()
+    if args.fix_background:
+        if not getattr(model, 'first_stage_encoder', False):
+            model.first_stage_encoder = True          # (configured on the device by .cuda() below)
+        model.fix_background = True
     if args.ddim_steps is not None:
         model.ddim_steps = args.ddim_steps
     if args.ckpt:
@@ -91,7 +111,7 @@ def main():
                 e = txt_emb if txt_emb is not None else torch.randn(1, 77, model.net_config.context_dim, generator=g)
                 batch['txt_emb'] = e.expand(b1 - b0, -1, -1).contiguous()
         else:
-            batch = synthetic_batch(b0, b1, args.res, model.net_config.context_dim)
+            batch = synthetic_batch(b0, b1, args.res, model.net_config.context_dim, with_seg=args.fix_background)
             if use_clip:
                 del batch['txt_emb']          # 'txt' -> tokenizer -> mkd_clip_encode
         x_T = None
