@@ -200,6 +200,34 @@ int mkd_q_sample_blend(const float* x0, const float* noise, float sqrt_ac, float
 int mkd_latent_mask_from_labels(const uint8_t* labels, int batch, int H, int W, uint64_t classes, int factor, float threshold,
                                 float* out, void* stream);
 
+/* ---- makeup score: region-wise histogram matching (reference diffmk/makeups.py:147-245, diffmk/histogram_matching.py:41-66) ---- */
+/* Region mask of a label map (get_msk_lip / get_msk_skin / get_msk_eye, makeups.py:179-230): labels [batch, H, W] uint8 device ->
+ * mask_out [batch, H, W] uint8 (1 where label l has bit l set in `classes`; labels >= 64 never match) and count_out [batch] int32, the
+ * number of mask pixels.  box_classes != 0 (the eye rule): the mask is kept only inside the bounding box of the labels in box_classes,
+ * grown by `margin` pixels on every side and clipped to the image; box_out [batch, 4] int32 (required then) receives that box before
+ * growing as (row min, row max, col min, col max), or (INT32_MAX, -1, INT32_MAX, -1) when no pixel carries such a label (the mask is
+ * then empty, count 0).  No context, no host sync, no allocation; 2 launches (3 with a box).  batch <= 65535, H * W <= 2^24, else MKD_ERR_ARG. */
+int mkd_region_mask_from_labels(const uint8_t* labels, int batch, int H, int W, uint64_t classes, uint64_t box_classes, int margin,
+                                uint8_t* mask_out, int32_t* count_out, int32_t* box_out, void* stream);
+/* Bytes of device scratch mkd_hist_match needs for n terms (0 for n <= 0).  The scratch must be 256-byte aligned; its contents
+ * before the call do not matter and it may be reused by the next call on the same stream. */
+size_t mkd_hist_match_scratch_bytes(int n);
+/* Launches one mkd_hist_match call enqueues (memset included) for the outputs asked for: independent of n, at most 5. */
+int mkd_hist_match_launches(int want_matched, int want_loss);
+/* n independent histogram-matching terms (criterionHis, makeups.py:232-245) in one set of launches.  Term t reads the images
+ * dst[index[4t]] and ref[index[4t+1]] (fp32 [3, H, W] each, values clamped to [0, 1]) under the masks mask_dst[index[4t+2]] and
+ * mask_ref[index[4t+3]] (uint8 [H, W], non-zero = inside); index == NULL: all four are t.  The caller guarantees that every index
+ * lies inside its array.  Per term: v = x * 255 (fp32); per channel 256-bin counts under each mask; pdf = count / total, cdf by
+ * sequential fp32 adds; table[i] = the first j in 1..255 with cdf_ref[j-1] <= cdf_dst[i] <= cdf_ref[j], else i (table[0] = 0,
+ * table[255] = 255); matched = table[int(v)] under the dst mask, 0 elsewhere; loss = mean over 3 H W of |v mask - matched|.
+ * Outputs (each may be NULL, not all of matched / tables / loss): matched [n, 3, H, W] fp32 in 0..255, tables [n, 3, 256] uint8,
+ * loss [n] fp32, counts [n, 2] int32 (dst, ref mask pixels).  Tables, matched values and counts equal the reference's; the loss is a
+ * fixed-order fp64 sum: the same bits on every run, for every batching of the same terms
+ * and for every alignment of the operands (the 16-byte and the scalar load form add a lane's terms in one order).  A term with an empty side (count 0):
+ * identity table, matched = 0, loss 0.  Only enqueues.  n <= 65535, H * W <= 2^24, else MKD_ERR_ARG. */
+int mkd_hist_match(const float* dst, const float* ref, const uint8_t* mask_dst, const uint8_t* mask_ref, const int32_t* index,
+                   int n, int H, int W, float* matched, uint8_t* tables, float* loss, int32_t* counts, void* scratch, void* stream);
+
 /* ---- first-stage decoder ------------------------------------------------ */
 /* yaml first_stage_config.params.ddconfig (diffmodels/base_diffusion_makeup.yaml:86-107), decoder half only. */
 typedef struct mkd_vae_config {

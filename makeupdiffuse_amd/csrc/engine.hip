@@ -2743,6 +2743,17 @@ int mkd_latent_mask_from_labels(const uint8_t* labels, int batch, int H, int W, 
         return mkd_fail(MKD_ERR_ARG, "mkd_latent_mask_from_labels: H, W must be positive multiples of factor (1..64)");
     return launch_latent_mask_from_labels(labels, batch, H, W, classes, factor, threshold, out, (hipStream_t)stream);
 }
+int mkd_region_mask_from_labels(const uint8_t* labels, int batch, int H, int W, uint64_t classes, uint64_t box_classes, int margin,
+                                uint8_t* mask_out, int32_t* count_out, int32_t* box_out, void* stream) {
+    if (!labels || !mask_out || !count_out) return mkd_fail(MKD_ERR_ARG, "mkd_region_mask_from_labels: null pointer");
+    return launch_region_mask_from_labels(labels, batch, H, W, classes, box_classes, margin, mask_out, count_out, box_out, (hipStream_t)stream);
+}
+size_t mkd_hist_match_scratch_bytes(int n) { return hist_match_scratch_bytes(n); }
+int mkd_hist_match_launches(int want_matched, int want_loss) { return hist_match_launches(want_matched, want_loss); }
+int mkd_hist_match(const float* dst, const float* ref, const uint8_t* mask_dst, const uint8_t* mask_ref, const int32_t* index, int n, int H, int W,
+                   float* matched, uint8_t* tables, float* loss, int32_t* counts, void* scratch, void* stream) {
+    return launch_hist_match(dst, ref, mask_dst, mask_ref, index, n, H, W, matched, tables, loss, counts, scratch, (hipStream_t)stream);
+}
 // The tile tuner's state (forced tile, XCD mode, per-shape overrides) is PROCESS-global by design: it belongs to the single-kernel
 // entries and to the tuners.  A change bumps the global plan epoch, so EVERY live context re-plans at its next mkd_prepare and a plan
 // never runs with decisions of another setting (launch_gemm also checks planned slab counts).  Per-context plan switches:

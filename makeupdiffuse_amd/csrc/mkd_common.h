@@ -259,6 +259,17 @@ int launch_q_sample_blend(const float* x0, const float* noise, float sqrt_ac, fl
 // threshold > 0: 1 where that fraction >= threshold, else 0
 int launch_latent_mask_from_labels(const uint8_t* labels, int batch, int H, int W, uint64_t classes, int f, float threshold, float* out,
                                    hipStream_t stream);
+// ---- makeup score (kernels_hist.hip) --------------------------------------------------------------------------------------------
+// labels [batch, H, W] uint8 -> mask [batch, H, W] uint8 (1 where the label is in `classes`) + count [batch].  box_classes != 0: only
+// inside the bounding box of the box_classes labels grown by `margin` pixels per side and clipped to the image; box_out [batch, 4] =
+// (row min, row max, col min, col max) of that box before growing, (INT_MAX, -1, INT_MAX, -1) when no pixel has such a label
+int launch_region_mask_from_labels(const uint8_t* labels, int batch, int H, int W, uint64_t classes, uint64_t box_classes, int margin,
+                                   uint8_t* mask_out, int32_t* count_out, int32_t* box_out, hipStream_t stream);
+// n histogram-matching terms in at most five launches; index [n][4] (dst image, ref image, dst mask, ref mask) or null (term t uses t)
+size_t hist_match_scratch_bytes(int n);
+int hist_match_launches(int want_apply, int want_loss);
+int launch_hist_match(const float* dst, const float* ref, const uint8_t* mask_dst, const uint8_t* mask_ref, const int32_t* index, int n, int H,
+                      int W, float* matched, uint8_t* tables, float* loss, int32_t* counts, void* scratch, hipStream_t stream);
 int launch_temb_select(const TembSel& ts, int step, hipStream_t stream);          // the same copy with a host-side step index (eager loop)
 int launch_ddim_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
                            hipStream_t stream);

@@ -386,8 +386,11 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
     def __init__(self, saved_dir: str = './results', model_name: str = 'makeupdiffuse', img_name_key: str = 'img_name',
                  unconditional_guidance_scale: float = 9, ddim_steps: int = 50, ddim_eta: float = 0.0, sample: bool = True,
                  fix_background: bool = False, background_classes: Sequence[int] = (0, 11, 12), background_threshold: float = 0.5,
-                 seg_key: str = 'nonmakeup_seg', *args, **kwargs):
+                 seg_key: str = 'nonmakeup_seg', makeup_score: bool = False, ref_seg_key: str = 'makeup_seg', *args, **kwargs):
         super().__init__(*args, **kwargs)
+        # makeup score of every decoded sample (makeup_score.transfer_score): off by default, then log_results is unchanged
+        self.makeup_score = bool(makeup_score)
+        self.ref_seg_key = ref_seg_key
         # background-preserving transfer (reference Fixbackground classes: background 0, teeth 11, hair 12): both sampling passes
         # keep the source's latent where the label map says so (DDIMSampler mask / x0)
         self.fix_background = bool(fix_background)
@@ -443,6 +446,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             log['samples_latent'] = samples
             if self.has_first_stage:
                 log['samples'] = self.decode_first_stage(samples)
+                if self.makeup_score:
+                    log['makeup_hist'] = self.makeup_hist(batch, log['samples'], c['ref_img'])
         if self.unconditional_guidance_scale > 1.0:
             uc_full = {'c_concat': [c_cat], 'c_crossattn': [self.get_unconditional_conditioning(b)]}
             samples_cfg, _ = self.sample_log(cond=cond, batch_size=b, ddim=use_ddim, ddim_steps=self.ddim_steps,
@@ -452,7 +457,20 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             log[name + '_latent'] = samples_cfg
             if self.has_first_stage:
                 log[name] = self.decode_first_stage(samples_cfg)
+                if self.makeup_score:
+                    log[f'makeup_hist_cfg_scale_{self.unconditional_guidance_scale:.2f}'] = self.makeup_hist(batch, log[name], c['ref_img'])
         return log
+
+    @torch.no_grad()
+    def makeup_hist(self, batch: dict, sample: torch.Tensor, ref: torch.Tensor) -> torch.Tensor:
+        """makeup_score: [B,4] = lip, skin, eye_left, eye_right histogram-matching distance of a decoded sample ([-1,1]) against the
+        makeup reference ([0,1]) under batch[seg_key] / batch[ref_seg_key] (reference criterionHis, diffmk/makeups.py:232-245)."""
+        from .. import makeup_score as ms
+        for k in (self.seg_key, self.ref_seg_key):
+            if k not in batch:
+                raise KeyError(f"makeup_score: the batch has no label map under '{k}'")
+        img = ((sample.float() + 1.0) / 2.0).clamp(0, 1)
+        return ms.transfer_score(img, ref, batch[self.seg_key], batch[self.ref_seg_key])
 
     @torch.no_grad()
     def background_latents(self, batch: dict, src: torch.Tensor):
@@ -513,7 +531,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         for k in images:
             if isinstance(images[k], torch.Tensor):
                 images[k] = images[k].detach().cpu()
-                if self.clamp and not k.endswith('_latent'):
+                if self.clamp and not k.endswith('_latent') and not k.startswith('makeup_hist'):
                     images[k] = torch.clamp(images[k], -1.0, 1.0)
         if self.save_images:
             self.save_local(images, batch_idx)
@@ -524,7 +542,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         reference's nrow = number of log entries is kept).  Latents (4 channels) are not images and are skipped."""
         from ..imageio import save_grid_png
         root = os.path.join(self.saved_dir, self.model_name)
-        nrow = len(images)
+        nrow = len([k for k in images if not k.startswith('makeup_hist')])       # (the scores are not log rows: the grids keep their layout)
         written = []
         for k, v in images.items():
             if not isinstance(v, torch.Tensor) or v.dim() != 4 or v.shape[1] not in (1, 3):

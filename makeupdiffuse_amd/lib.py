@@ -75,6 +75,10 @@ SIGNATURES = {
                                C.POINTER(SampleMaskC), _F, _P, _I, _P]),
     'mkd_q_sample_blend': (_I, [_P, _P, _F, _F, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
     'mkd_latent_mask_from_labels': (_I, [_P, _I, _I, _I, C.c_uint64, _I, _F, _P, _P]),
+    'mkd_region_mask_from_labels': (_I, [_P, _I, _I, _I, C.c_uint64, C.c_uint64, _I, _P, _P, _P, _P]),
+    'mkd_hist_match_scratch_bytes': (C.c_size_t, [_I]),
+    'mkd_hist_match_launches': (_I, [_I, _I]),
+    'mkd_hist_match': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     'mkd_vae_configure': (_I, [_P, C.POINTER(VaeConfigC)]),
     'mkd_vae_finalize': (_I, [_P]),
     'mkd_decode': (_I, [_P, _P, _I, _I, _I, _F, _P, _P]),

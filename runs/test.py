@@ -20,18 +20,25 @@ from makeupdiffuse_amd import dist as mdist  # noqa: E402
 from makeupdiffuse_amd.config import create_model, load_state_dict  # noqa: E402
 
 
-def synthetic_seg(i, res):
-    """a stand-in face-parsing map for pair i: background (0) outside an ellipse, hair (12) on its top, skin (1) inside"""
+def synthetic_seg(i, res, features=False):
+    """a stand-in face-parsing map for pair i: background (0) outside an ellipse, hair (12) on its top, skin (1) inside;
+    features: also eyes (4, 5) and lips (7, 9), the regions the makeup score reads"""
     g = torch.Generator().manual_seed(1213 + i)
     cy, cx = res * (0.5 + 0.1 * (torch.rand(2, generator=g) - 0.5))
     yy, xx = torch.meshgrid(torch.arange(res, dtype=torch.float32), torch.arange(res, dtype=torch.float32), indexing='ij')
     inside = ((yy - cy) / (0.4 * res)) ** 2 + ((xx - cx) / (0.3 * res)) ** 2 <= 1.0
     seg = torch.where(inside, torch.ones((), dtype=torch.uint8), torch.zeros((), dtype=torch.uint8))
     seg[inside & (yy < cy - 0.25 * res)] = 12
+    if features:
+        blob = lambda dy, dx, ry, rx: ((yy - cy - dy * res) / (ry * res)) ** 2 + ((xx - cx - dx * res) / (rx * res)) ** 2 <= 1.0
+        seg[blob(-0.08, -0.11, 0.025, 0.05)] = 4
+        seg[blob(-0.08, 0.11, 0.025, 0.05)] = 5
+        seg[blob(0.18, 0.0, 0.035, 0.09) & (yy <= cy + 0.18 * res)] = 7
+        seg[blob(0.18, 0.0, 0.035, 0.09) & (yy > cy + 0.18 * res)] = 9
     return seg
 
 
-def synthetic_batch(lo, hi, res, ctx_dim, with_seg=False):
+def synthetic_batch(lo, hi, res, ctx_dim, with_seg=False, with_makeup_seg=False):
     src, ref, txt = [], [], []
     for i in range(lo, hi):
         g = torch.Generator().manual_seed(5678 + i)
@@ -42,10 +49,13 @@ def synthetic_batch(lo, hi, res, ctx_dim, with_seg=False):
              'txt': ['makeup transfer'] * (hi - lo), 'img_name': [f'{i:04d}&{i:04d}' for i in range(lo, hi)]}
     if with_seg:
         batch['nonmakeup_seg'] = torch.stack([synthetic_seg(i, res) for i in range(lo, hi)])
+    if with_makeup_seg:
+        batch['nonmakeup_seg'] = torch.stack([synthetic_seg(i, res, True) for i in range(lo, hi)])
+        batch['makeup_seg'] = torch.stack([synthetic_seg(7000 + i, res, True) for i in range(lo, hi)])
     return batch
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', default=os.path.join(os.path.dirname(__file__), '..', 'diffmodels', 'test_diffusion_makeup.yaml'))
     ap.add_argument('--ckpt', default=None, help='upstream-named state_dict (.safetensors / tensor-only .ckpt); default: seeded random init')
@@ -63,7 +73,26 @@ def main():
     ap.add_argument('--txt-emb', default=None, help='.pt/.safetensors with a [1,77,768] tensor: the CLIP embedding of the prompt (offline stand-in)')
     ap.add_argument('--fix-background', action='store_true', help="keep the source's background, teeth and hair (label map "
                     "nonmakeup_seg from <data-root>/scgan_segs, a synthetic one otherwise; needs the first-stage encoder)")
-    args = ap.parse_args()
+    ap.add_argument('--makeup-score', action='store_true', help='score every decoded sample against its makeup reference: per region '
+                    '(lip, skin, eye_left, eye_right) the L1 distance to its histogram match, one row per pair in <out>/makeup_score.csv '
+                    '(label maps nonmakeup_seg / makeup_seg from <data-root>/scgan_segs, synthetic ones otherwise)')
+    return ap
+
+
+def write_makeup_scores(path, names, out, first):
+    """one makeup_score.csv row per pair and makeup_hist* entry of a test_step result; the first batch of a run rewrites the file"""
+    from makeupdiffuse_amd.makeup_score import REGIONS
+    with open(path, 'w' if first else 'a') as f:
+        if first:
+            f.write('pair,entry,' + ','.join(REGIONS) + '\n')
+        for k in sorted(out):
+            if k.startswith('makeup_hist'):
+                for i, row in enumerate(out[k].tolist()):
+                    f.write('%s,%s,%s\n' % (names[i], k, ','.join('%.6f' % v for v in row)))
+
+
+def main():
+    args = build_parser().parse_args()
 
     rank, world, local = mdist.init_from_env()
     model = create_model(args.config).cpu()
@@ -71,6 +100,8 @@ def main():
         if not getattr(model, 'first_stage_encoder', False):
             model.first_stage_encoder = True          # (configured on the device by .cuda() below)
         model.fix_background = True
+    if args.makeup_score:
+        model.makeup_score = True
     if args.ddim_steps is not None:
         model.ddim_steps = args.ddim_steps
     if args.ckpt:
@@ -111,7 +142,8 @@ def main():
                 e = txt_emb if txt_emb is not None else torch.randn(1, 77, model.net_config.context_dim, generator=g)
                 batch['txt_emb'] = e.expand(b1 - b0, -1, -1).contiguous()
         else:
-            batch = synthetic_batch(b0, b1, args.res, model.net_config.context_dim, with_seg=args.fix_background)
+            batch = synthetic_batch(b0, b1, args.res, model.net_config.context_dim, with_seg=args.fix_background,
+                                    with_makeup_seg=args.makeup_score)
             if use_clip:
                 del batch['txt_emb']          # 'txt' -> tokenizer -> mkd_clip_encode
         x_T = None
@@ -121,6 +153,9 @@ def main():
                              for i in range(b0, b1)]).cuda(local)
         out = model.test_step(batch, b0, x_T=x_T)
         model.on_test_batch_end(out, batch, b0)
+        if args.makeup_score:
+            write_makeup_scores(os.path.join(args.out, f'makeup_score_rank{rank}.csv' if world > 1 else 'makeup_score.csv'),
+                                batch.get('img_name') or [str(i) for i in range(b0, b1)], out, first=b0 == lo)
         torch.save({k: v for k, v in out.items() if isinstance(v, torch.Tensor)},
                    os.path.join(args.out, f'latents_{b0:04d}.pt'))
         print(f'[rank {rank}] pairs {b0}..{min(hi, b0 + args.batch_size) - 1}: ' +
