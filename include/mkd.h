@@ -193,6 +193,34 @@ int mkd_sample_masked(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, co
  * out may alias x.  Bad shapes: MKD_ERR_ARG. */
 int mkd_q_sample_blend(const float* x0, const float* noise, float sqrt_ac, float sqrt_one_minus_ac, const float* mask,
                        int mask_batch, int mask_channels, const float* x, float* out, int batch, int channels, int hw, void* stream);
+/* ---- DPM-Solver++ multistep sampler (Lu et al. 2022, Algorithm 2; UPSTREAM ldm.models.diffusion.dpm_solver, data prediction) ---- */
+/* Deterministic, eps parameterisation, on the step grid and tables of DDIMSampler.make_schedule: table entry i goes from
+ * a_t = alphas[i] to a_prev = alphas_prev[i] with the model evaluated at the integer timesteps[i]; the loop runs i = n_steps-1 .. 0
+ * (upstream's wrapper evaluates at fractional timesteps of a continuous schedule; the engine's are int64, that form is not built).
+ * With alpha = sqrt(a), sigma = sqrt(1 - a), lambda = log(alpha / sigma), h = lambda(a_prev) - lambda(a_t) and m_k = (x - sigma_t e) / alpha_t
+ * the x0-prediction of executed step k, every step is  x <- c_x x + c_0 m_k + c_1 m_{k-1} + c_2 m_{k-2}:
+ *   order 1: x <- (sigma_prev / sigma_t) x - alpha_prev expm1(-h) m_k        (algebraically the eta = 0 DDIM step)
+ *   order 2: the same with D = (1 + 1/(2r)) m_k - 1/(2r) m_{k-1} for m_k, r = (lambda_t - lambda of the previous evaluation) / h
+ *   order 3: multistep_dpm_solver_third_update (phi_1 = expm1(-h), phi_2 = phi_1 / h + 1, phi_3 = phi_2 / h - 1/2)
+ * Executed step k uses order min(order, k + 1), and with lower_order_final != 0 and n_steps < 10 also at most n_steps - k.
+ *
+ * mkd_dpmpp_table: HOST only (no device, no context).  out [n_steps][6] = 1/alpha_t, sigma_t, c_x, c_0, c_1, c_2 of table entry i, computed in
+ * double and stored as float; step_order [n_steps] (may be NULL) = the order entry i runs at.  MKD_ERR_ARG: order outside 1..3, an alpha
+ * outside (0, 1), lambda not increasing along the executed steps. */
+int mkd_dpmpp_table(int n_steps, const float* alphas, const float* alphas_prev, int order, int lower_order_final, float* out,
+                    int* step_order);
+/* One update: e = eps_u + cfg_scale (eps_c - eps_u) (eps_u NULL: eps_c); m0_out = (x - coef6[1] e) coef6[0];
+ * x_prev = coef6[2] x + coef6[3] m0 + coef6[4] m1 + coef6[5] m2.  coef6: HOST, one row of mkd_dpmpp_table; m1 / m2 (the previous two
+ * x0-predictions) are read only where their coefficient is non-zero and may be NULL otherwise; x_prev may alias x.  All fp32 [n]. */
+int mkd_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, const float* coef6, const float* m1,
+                   const float* m2, float* x_prev, float* m0_out, int64_t n, void* stream);
+/* The whole loop: mkd_sample's contract (prepared batch B or 2B with the unconditional conditioning first, host tables, all three
+ * loop forms: graph replay, its per-stream segments, use_graph == 0) with the update above as the step's last kernel and a device
+ * history ring [3][B*4*h*w] fp32 owned by the context.  m != NULL: the masked blend of mkd_sample_masked before every step.  The
+ * per-step launch count equals mkd_step_launches_ex.  Captured steps are keyed on the solver, so DDIM and DPM calls may alternate. */
+int mkd_sample_dpmpp(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
+                     const float* alphas_prev, int order, int lower_order_final, const mkd_sample_mask* m, float cfg_scale,
+                     float* x_out, int use_graph, void* stream);
 /* Latent mask from a label map (reference Fixbackground: labels 0 background, 11 teeth, 12 hair): labels [batch, H, W] uint8
  * device -> out [batch, 1, H/factor, W/factor] fp32 device = the fraction of each factor x factor block whose label l has bit l set
  * in `classes` (labels >= 64 never match): F.interpolate(mode='area') of the binary mask.  threshold > 0: 1 where that fraction

@@ -274,10 +274,12 @@ struct mkd_ctx {
     float* s_xa = nullptr; float* s_xb = nullptr; float* s_xin = nullptr; float* s_eps = nullptr;
     int64_t* s_t = nullptr;
     StepState* s_state = nullptr; StepState* h_state = nullptr;
+    float* s_ring = nullptr; int64_t s_ring_n = 0;        // DPM-Solver++ history ring [3][n] fp32: allocated on first use, grown with the batch
     hipStream_t loop_stream = nullptr; hipEvent_t ev_loop_in = nullptr, ev_loop_out = nullptr;
     hipGraphExec_t multi_graph = nullptr; int multi_graph_steps = 0;      // MKD_GRAPH_STEPS consecutive steps as one graph
     hipGraphExec_t step_graph = nullptr; int step_graph_cfg = -1; float step_graph_scale = 0.f; int plan_generation = 0, step_graph_gen = -1;
     int step_graph_temb = -1, step_graph_batch = -1;
+    int step_graph_solver = -1, seg_solver = -1;          // solver kind of the captured step: 0 DDIM, 1 DPM-Solver++ (its order lives in the table)
     // Graph mode 2 (MKD_GRAPH_MODE=2; default 1 = one captured graph per step): one step = LINEAR graphs, one per (stream, stretch
     // between two cross-stream edges), launched on their own streams and ordered by events.  A captured graph with two BRANCHES is
     // replayed with its branches serialised node by node (tools/micro/launch_floor.hip: 3.2 us per pair of empty nodes, 5.3-5.9 us
@@ -1778,7 +1780,7 @@ struct mkd_ctx {
     }
     // One reverse step as per-stream linear graphs (graph mode 2).  Walks the step's launches in plan order; every cross-stream edge
     // that the single-graph capture keeps (in_graph) closes the pending stretch of both its streams.
-    int build_segments(int batch, bool cfg_on, float cfg_scale) {
+    int build_segments(int batch, bool cfg_on, float cfg_scale, bool dpm_on) {
         drop_segments();
         const int64_t n = (int64_t)batch * cfg.in_channels * h * w;
         mkd_ctx* self = this;
@@ -1816,7 +1818,8 @@ struct mkd_ctx {
 #endif
             items.push_back({op.fn, arena_of(op.cap_sid >= 0 ? op.cap_sid : op.sid), -1, -1});
         }
-        items.push_back({[self, ec, eu, cfg_scale, n](hipStream_t st) { return launch_ddim_step_state(self->s_xa, ec, eu, cfg_scale, self->s_state, n, st); }, 0, -1, -1});
+        if (dpm_on) items.push_back({[self, ec, eu, cfg_scale, n](hipStream_t st) { return launch_dpmpp_step_state(self->s_xa, ec, eu, cfg_scale, self->s_state, n, st); }, 0, -1, -1});
+        else items.push_back({[self, ec, eu, cfg_scale, n](hipStream_t st) { return launch_ddim_step_state(self->s_xa, ec, eu, cfg_scale, self->s_state, n, st); }, 0, -1, -1});
         std::vector<OpFn> pend[NS];
         int rc = 0;
         auto flush = [&](int sid) -> int {
@@ -1862,6 +1865,7 @@ struct mkd_ctx {
         capturing = false;
         if (rc) { drop_segments(); return rc; }
         seg_gen = plan_generation; seg_cfg = (int)cfg_on; seg_scale = cfg_scale; seg_temb = (int)temb_skip; seg_batch = batch;
+        seg_solver = (int)dpm_on;
         return 0;
     }
     int run_segments() {
@@ -1885,7 +1889,7 @@ struct mkd_ctx {
     }
 
     // enqueue ONE reverse step that reads its timestep / coefficients from the device step state (graph body)
-    int enqueue_state_step(int batch, bool cfg_on, float cfg_scale, hipStream_t stream) {
+    int enqueue_state_step(int batch, bool cfg_on, float cfg_scale, bool dpm_on, hipStream_t stream) {
         const int64_t n = (int64_t)batch * cfg.in_channels * h * w;
         const TembSel ts = temb_sel();
         int rc = launch_step_setup(s_state, s_t, B, s_xa, n, stream, temb_skip ? &ts : nullptr); if (rc) return rc;
@@ -1898,20 +1902,36 @@ struct mkd_ctx {
             rc = eps(s_xa, s_t, s_eps, stream); if (rc) return rc;
             ec = s_eps;
         }
+        if (dpm_on) return launch_dpmpp_step_state(s_xa, ec, eu, cfg_scale, s_state, n, stream);
         return launch_ddim_step_state(s_xa, ec, eu, cfg_scale, s_state, n, stream);
+    }
+
+    // the DPM-Solver++ history ring for latents of n elements (the captured step reads its address from the step state, so growing
+    // it invalidates no graph)
+    int ensure_ring(int64_t n) {
+        if (s_ring && s_ring_n >= n) return 0;
+        MKD_HIP_CHECK(hipDeviceSynchronize());          // an enqueued loop may still use the old ring
+        if (s_ring) { MKD_HIP_CHECK(hipFree(s_ring)); s_ring = nullptr; s_ring_n = 0; }
+        MKD_HIP_CHECK(hipMalloc((void**)&s_ring, (size_t)(3 * n) * sizeof(float)));
+        s_ring_n = n;
+        return 0;
     }
 
     int sample(const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
                const float* alphas_prev, const float* s1m, float cfg_scale, float* x_out, int use_graph, hipStream_t stream,
-               const float* sigmas = nullptr, const float* noise = nullptr, float temperature = 1.0f, const mkd_sample_mask* qm = nullptr) {
+               const float* sigmas = nullptr, const float* noise = nullptr, float temperature = 1.0f, const mkd_sample_mask* qm = nullptr,
+               const float* dpm = nullptr) {
         const int rc = sample_impl(x_T, batch, n_steps, timesteps, alphas, alphas_prev, s1m, cfg_scale, x_out, use_graph, stream, sigmas, noise,
-                                   temperature, qm);
+                                   temperature, qm, dpm);
         temb_skip = false;          // (a later mkd_eps runs its own time-embedding chain)
         return rc;
     }
     int sample_impl(const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
                const float* alphas_prev, const float* s1m, float cfg_scale, float* x_out, int use_graph, hipStream_t stream,
-               const float* sigmas, const float* noise, float temperature, const mkd_sample_mask* qm) {
+               const float* sigmas, const float* noise, float temperature, const mkd_sample_mask* qm, const float* dpm) {
+        // dpm: host [n_steps][6] of mkd_dpmpp_table -> the DPM-Solver++ multistep loop (deterministic: sigmas / noise / s1m unused);
+        // null: DDIM.  Setup, evaluation and the masked blend are shared; only the step's last kernel differs.
+        const bool dpm_on = dpm != nullptr;
         if (!prepared) return mkd_fail(MKD_ERR_STATE, "mkd_sample before mkd_prepare");
         bool stochastic = false;
         if (sigmas) for (int i = 0; i < n_steps; ++i) {
@@ -1922,7 +1942,7 @@ struct mkd_ctx {
         const bool cfg_on = cfg_scale != 1.0f;
         if (cfg_on ? (B != 2 * batch) : (B != batch))
             return mkd_fail(MKD_ERR_ARG, "mkd_sample: prepared batch must be B (cfg_scale == 1) or 2B (uncond first)");
-        if (n_steps <= 0 || !timesteps || !alphas || !alphas_prev || !s1m || !x_T || !x_out)
+        if (n_steps <= 0 || !timesteps || !alphas || !alphas_prev || (!s1m && !dpm_on) || !x_T || !x_out)
             return mkd_fail(MKD_ERR_ARG, "mkd_sample: bad arguments");
         if (qm && (!qm->x0 || !qm->mask || !qm->noise || !qm->sqrt_alphas_cumprod || !qm->sqrt_one_minus_alphas_cumprod))
             return mkd_fail(MKD_ERR_ARG, "mkd_sample_masked: x0, mask, noise and both tables are required");
@@ -1930,6 +1950,7 @@ struct mkd_ctx {
             return mkd_fail(MKD_ERR_ARG, "mkd_sample_masked: mask must be [1 or B, 1 or C, h, w]");
         const int64_t n = (int64_t)batch * cfg.in_channels * h * w;
         const int hw = h * w;
+        if (dpm_on) { int rc = ensure_ring(n); if (rc) return rc; }
         MKD_HIP_CHECK(hipMemcpyAsync(s_xa, x_T, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
         if (use_graph) {
             // --- hipGraph path: one captured step (both streams, fork/join included), replayed n_steps times ---
@@ -1951,9 +1972,13 @@ struct mkd_ctx {
                 h_state->coef[4 * i + 1] = sqrtf(alphas_prev[i]);
                 const float sg = stochastic ? sigmas[i] : 0.f;
                 h_state->coef[4 * i + 2] = sqrtf(1.0f - alphas_prev[i] - sg * sg);
-                h_state->coef[4 * i + 3] = s1m[i];
+                h_state->coef[4 * i + 3] = s1m ? s1m[i] : 0.f;
                 h_state->sigma[i] = sg;
+                for (int j = 0; j < 6; ++j) h_state->dpm[6 * i + j] = dpm_on ? dpm[6 * i + j] : 0.f;
             }
+            h_state->ring = dpm_on ? s_ring : nullptr;
+            for (int j = 0; j < 6; ++j) h_state->cur_dpm[j] = 0.f;
+            h_state->cur_slot[0] = h_state->cur_slot[1] = h_state->cur_slot[2] = 0;
             h_state->noise = stochastic ? noise : nullptr; h_state->temperature = temperature; h_state->n_steps = n_steps;
             h_state->cur_sigma = 0.f; h_state->cur_row = 0;
             // masked sampling: read by step_setup_kernel; x0 null leaves the (shared) captured step unmasked
@@ -1974,8 +1999,9 @@ struct mkd_ctx {
             }
             if (graph_mode == 2 && dual_stream) {
                 run_main = loop_stream; run_serial = false;
-                if (segs.empty() || seg_gen != plan_generation || seg_cfg != (int)cfg_on || seg_scale != cfg_scale || seg_temb != (int)temb_skip || seg_batch != batch) {
-                    int rc = build_segments(batch, cfg_on, cfg_scale); if (rc) return rc;
+                if (segs.empty() || seg_gen != plan_generation || seg_cfg != (int)cfg_on || seg_scale != cfg_scale || seg_temb != (int)temb_skip || seg_batch != batch ||
+                    seg_solver != (int)dpm_on) {
+                    int rc = build_segments(batch, cfg_on, cfg_scale, dpm_on); if (rc) return rc;
                 }
                 for (int i = 0; i < n_steps; ++i) { int rc = run_segments(); if (rc) return rc; }
                 MKD_HIP_CHECK(hipMemcpyAsync(x_out, s_xa, n * sizeof(float), hipMemcpyDeviceToDevice, loop_stream));
@@ -1983,14 +2009,15 @@ struct mkd_ctx {
                 MKD_HIP_CHECK(hipStreamWaitEvent(stream, ev_loop_out, 0));
                 return 0;
             }
-            // both graphs are keyed on everything their nodes depend on (plan, guidance, batch, where the time embedding comes from)
+            // both graphs are keyed on everything their nodes depend on (plan, guidance, batch, where the time embedding comes from,
+            // the solver whose kernel ends the step)
             if (!step_graph || step_graph_gen != plan_generation || step_graph_cfg != (int)cfg_on || step_graph_scale != cfg_scale ||
-                step_graph_temb != (int)temb_skip || step_graph_batch != batch) {
+                step_graph_temb != (int)temb_skip || step_graph_batch != batch || step_graph_solver != (int)dpm_on) {
                 drop_graph();
                 hipGraph_t g = nullptr;
                 MKD_HIP_CHECK(hipStreamBeginCapture(loop_stream, hipStreamCaptureModeRelaxed));
                 capturing = true;
-                int rc = enqueue_state_step(batch, cfg_on, cfg_scale, loop_stream);
+                int rc = enqueue_state_step(batch, cfg_on, cfg_scale, dpm_on, loop_stream);
                 capturing = false;
                 hipError_t e = hipStreamEndCapture(loop_stream, &g);
                 if (rc) { if (g) hipGraphDestroy(g); return rc; }
@@ -1999,7 +2026,7 @@ struct mkd_ctx {
                 hipGraphDestroy(g);
                 if (e != hipSuccess) { step_graph = nullptr; return mkd_fail(MKD_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
                 step_graph_gen = plan_generation; step_graph_cfg = (int)cfg_on; step_graph_scale = cfg_scale;
-                step_graph_temb = (int)temb_skip; step_graph_batch = batch;
+                step_graph_temb = (int)temb_skip; step_graph_batch = batch; step_graph_solver = (int)dpm_on;
             }
             // (multi_graph needs no key of its own: whenever step_graph's key above changes, drop_graph() destroys both)
             // MKD_GRAPH_STEPS = k > 1: k consecutive steps captured as ONE graph (the step reads its index from the device-resident
@@ -2014,7 +2041,7 @@ struct mkd_ctx {
                     MKD_HIP_CHECK(hipStreamBeginCapture(loop_stream, hipStreamCaptureModeRelaxed));
                     capturing = true;
                     int rc = 0;
-                    for (int k = 0; k < gsteps && !rc; ++k) rc = enqueue_state_step(batch, cfg_on, cfg_scale, loop_stream);
+                    for (int k = 0; k < gsteps && !rc; ++k) rc = enqueue_state_step(batch, cfg_on, cfg_scale, dpm_on, loop_stream);
                     capturing = false;
                     hipError_t e = hipStreamEndCapture(loop_stream, &g);
                     if (rc) { if (g) hipGraphDestroy(g); return rc; }
@@ -2054,6 +2081,15 @@ struct mkd_ctx {
             } else {
                 rc = eps(xa, s_t, s_eps, stream); if (rc) return rc;
                 ec = s_eps;
+            }
+            if (dpm_on) {           // m_k into ring slot k mod 3; m_{k-1}, m_{k-2} from the other two (k = i, the executed step)
+                const float* d = dpm + 6 * index;
+                const DpmCoef kc = {d[0], d[1], d[2], d[3], d[4], d[5]};
+                rc = launch_dpmpp_step(xa, ec, eu, cfg_scale, kc, s_ring + (int64_t)((i + 2) % 3) * n, s_ring + (int64_t)((i + 1) % 3) * n, xb,
+                                       s_ring + (int64_t)(i % 3) * n, n, stream);
+                if (rc) return rc;
+                float* tmp = xa; xa = xb; xb = tmp;
+                continue;
             }
             const float sg = stochastic ? sigmas[index] : 0.f;
             rc = launch_ddim_step(xa, ec, eu, cfg_scale, alphas[index], alphas_prev[index], sg, s1m[index], sg != 0.f ? noise + (int64_t)i * n : nullptr,
@@ -2564,6 +2600,7 @@ struct mkd_ctx {
         MKD_HIP_CHECK(hipDeviceSynchronize());
         if (persist_cap > persist_eps_begin) MKD_HIP_CHECK(hipMemset(persist_base + persist_eps_begin, 0xFF, persist_cap - persist_eps_begin));
         if (gstat_base) MKD_HIP_CHECK(hipMemset(gstat_base, 0xFF, gstat_cap));
+        if (s_ring) MKD_HIP_CHECK(hipMemset(s_ring, 0xFF, (size_t)(3 * s_ring_n) * sizeof(float)));
         for (int i = 0; i < NS; ++i) {
             if (temp_base[i]) MKD_HIP_CHECK(hipMemset(temp_base[i], 0xFF, temp_cap[i]));
             if (splitk_ws[i]) MKD_HIP_CHECK(hipMemset(splitk_ws[i], 0xFF, splitk_ws_bytes[i]));
@@ -2574,7 +2611,7 @@ struct mkd_ctx {
     }
 
     int64_t device_bytes() const {
-        return weight_bytes + (int64_t)varena_cap + (int64_t)earena_cap + (int64_t)carena_cap + (int64_t)persist_cap + (int64_t)gstat_cap + [&] { int64_t t = 0; for (int i = 0; i < NA; ++i) t += (int64_t)(temp_cap[i] + splitk_ws_bytes[i] + gn_ws_bytes[i]); return t; }();
+        return weight_bytes + 3 * s_ring_n * (int64_t)sizeof(float) + (int64_t)varena_cap + (int64_t)earena_cap + (int64_t)carena_cap + (int64_t)persist_cap + (int64_t)gstat_cap + [&] { int64_t t = 0; for (int i = 0; i < NA; ++i) t += (int64_t)(temp_cap[i] + splitk_ws_bytes[i] + gn_ws_bytes[i]); return t; }();
     }
 
     ~mkd_ctx() {
@@ -2592,6 +2629,7 @@ struct mkd_ctx {
         if (loop_stream) { hipStreamSynchronize(loop_stream); hipStreamDestroy(loop_stream); hipEventDestroy(ev_loop_in); hipEventDestroy(ev_loop_out); }
         if (h_state) hipHostFree(h_state);
         if (s_state) hipFree(s_state);
+        if (s_ring) hipFree(s_ring);
         for (int i = 1; i < NS; ++i)
             if (side_streams[i]) { hipStreamSynchronize(side_streams[i]); hipStreamDestroy(side_streams[i]); }
         for (int i = 0; i < NA; ++i)
@@ -2726,6 +2764,70 @@ int mkd_sample_masked(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, co
     if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
     return ctx->sample(x_T, batch, n_steps, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas, cfg_scale, x_out, use_graph,
                        (hipStream_t)stream, sigmas, noise, temperature, m);
+}
+// Schedule-only coefficients of the multistep DPM-Solver++ (data prediction), in double; host only.  With alpha = sqrt(a),
+// sigma = sqrt(1 - a), lambda = log(alpha / sigma) and h = lambda(a_prev) - lambda(a_t) of table entry i, executed step k = n_steps - 1 - i:
+//   x <- (sigma_prev / sigma_t) x - alpha_prev (phi_1 m_k - phi_2 D1 + phi_3 D2),  phi_1 = expm1(-h), phi_2 = phi_1 / h + 1, phi_3 = phi_2 / h - 1/2
+// (order 2: - alpha_prev phi_1 (m_k + D1_0 / 2)), D1_0 = (m_k - m_{k-1}) / r0, D1_1 = (m_{k-1} - m_{k-2}) / r1 the difference quotients
+// over the previous evaluations' lambda spacings r0 h, r1 h; written out as coefficients of x, m_k, m_{k-1}, m_{k-2}.
+int mkd_dpmpp_table(int n_steps, const float* alphas, const float* alphas_prev, int order, int lower_order_final, float* out, int* step_order) {
+    if (n_steps <= 0 || !alphas || !alphas_prev || !out) return mkd_fail(MKD_ERR_ARG, "mkd_dpmpp_table: bad arguments");
+    if (order < 1 || order > 3) return mkd_fail(MKD_ERR_ARG, "mkd_dpmpp_table: order must be 1, 2 or 3");
+    auto lambda_of = [](double a) { return 0.5 * std::log(a / (1.0 - a)); };
+    for (int i = 0; i < n_steps; ++i)
+        if (!(alphas[i] > 0.f && alphas[i] < 1.f && alphas_prev[i] > 0.f && alphas_prev[i] < 1.f))
+            return mkd_fail(MKD_ERR_ARG, "mkd_dpmpp_table: every alpha must lie in (0, 1)");
+    double lam1 = 0.0, lam2 = 0.0;          // lambda at the evaluations of executed steps k - 1, k - 2
+    for (int k = 0; k < n_steps; ++k) {
+        const int i = n_steps - 1 - k;
+        const double a_t = alphas[i], a_p = alphas_prev[i];
+        const double lam_t = lambda_of(a_t), lam_p = lambda_of(a_p), hh = lam_p - lam_t;
+        if (!(hh > 0.0) || (k > 0 && !(lam_t > lam1)))
+            return mkd_fail(MKD_ERR_ARG, "mkd_dpmpp_table: lambda must increase along the executed steps (alphas_prev > alphas, newest entry last)");
+        int p = order < k + 1 ? order : k + 1;
+        if (lower_order_final && n_steps < 10 && p > n_steps - k) p = n_steps - k;
+        const double alpha_p = std::sqrt(a_p), phi1 = std::expm1(-hh);
+        double c0 = -alpha_p * phi1, c1 = 0.0, c2 = 0.0;
+        if (p == 2) {
+            const double r0 = (lam_t - lam1) / hh;
+            c0 = -alpha_p * phi1 * (1.0 + 0.5 / r0);
+            c1 = alpha_p * phi1 * 0.5 / r0;
+        } else if (p == 3) {
+            const double r0 = (lam_t - lam1) / hh, r1 = (lam1 - lam2) / hh;
+            const double phi2 = phi1 / hh + 1.0, phi3 = phi2 / hh - 0.5;
+            const double wq = r0 / (r0 + r1), q = 1.0 / (r0 + r1);
+            const double g0 = alpha_p * (phi2 * (1.0 + wq) - phi3 * q);          // coefficient of D1_0
+            const double g1 = alpha_p * (phi3 * q - phi2 * wq);                   // coefficient of D1_1
+            c0 = -alpha_p * phi1 + g0 / r0;
+            c1 = g1 / r1 - g0 / r0;
+            c2 = -g1 / r1;
+        }
+        float* o = out + 6 * (size_t)i;
+        o[0] = (float)(1.0 / std::sqrt(a_t)); o[1] = (float)std::sqrt(1.0 - a_t);
+        o[2] = (float)(std::sqrt(1.0 - a_p) / std::sqrt(1.0 - a_t));
+        o[3] = (float)c0; o[4] = (float)c1; o[5] = (float)c2;
+        if (step_order) step_order[i] = p;
+        lam2 = lam1; lam1 = lam_t;
+    }
+    return 0;
+}
+int mkd_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, const float* coef6, const float* m1, const float* m2,
+                   float* x_prev, float* m0_out, int64_t n, void* stream) {
+    if (!x || !eps_c || !coef6 || !x_prev || !m0_out || n <= 0) return mkd_fail(MKD_ERR_ARG, "mkd_dpmpp_step: null pointer or empty tensor");
+    if ((coef6[4] != 0.f && !m1) || (coef6[5] != 0.f && !m2)) return mkd_fail(MKD_ERR_ARG, "mkd_dpmpp_step: a non-zero c_1 / c_2 needs m1 / m2");
+    const DpmCoef k = {coef6[0], coef6[1], coef6[2], coef6[3], coef6[4], coef6[5]};
+    return launch_dpmpp_step(x, eps_c, eps_u, cfg_scale, k, m1, m2, x_prev, m0_out, n, (hipStream_t)stream);
+}
+int mkd_sample_dpmpp(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
+                     const float* alphas_prev, int order, int lower_order_final, const mkd_sample_mask* m, float cfg_scale, float* x_out,
+                     int use_graph, void* stream) {
+    if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
+    if (n_steps <= 0 || !alphas || !alphas_prev) return mkd_fail(MKD_ERR_ARG, "mkd_sample_dpmpp: bad arguments");
+    std::vector<float> tab((size_t)n_steps * 6);
+    const int rc = mkd_dpmpp_table(n_steps, alphas, alphas_prev, order, lower_order_final, tab.data(), nullptr);
+    if (rc) return rc;
+    return ctx->sample(x_T, batch, n_steps, timesteps, alphas, alphas_prev, nullptr, cfg_scale, x_out, use_graph, (hipStream_t)stream,
+                       nullptr, nullptr, 1.0f, m, tab.data());
 }
 int mkd_q_sample_blend(const float* x0, const float* noise, float sqrt_ac, float sqrt_one_minus_ac, const float* mask, int mask_batch,
                        int mask_channels, const float* x, float* out, int batch, int channels, int hw, void* stream) {

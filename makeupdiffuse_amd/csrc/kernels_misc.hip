@@ -88,6 +88,10 @@ __global__ void step_setup_kernel(StepState* st, int64_t* t_out, int batch, cons
             st->cur[0] = st->coef[4 * i + 0]; st->cur[1] = st->coef[4 * i + 1];
             st->cur[2] = st->coef[4 * i + 2]; st->cur[3] = st->coef[4 * i + 3];
             st->cur_sigma = st->sigma[i]; st->cur_row = st->n_steps - 1 - i;
+            // DPM-Solver++ loop: the step's six numbers and the ring slots of m_k, m_{k-1}, m_{k-2} (k = the executed step)
+            for (int j = 0; j < 6; ++j) st->cur_dpm[j] = st->dpm[6 * i + j];
+            const int k = st->n_steps - 1 - i;
+            st->cur_slot[0] = k % 3; st->cur_slot[1] = (k + 2) % 3; st->cur_slot[2] = (k + 1) % 3;
         }
     }
     const int gtid = blockIdx.x * blockDim.x + threadIdx.x, gthreads = gridDim.x * blockDim.x;
@@ -122,6 +126,76 @@ __global__ void ddim_step_state_kernel(float* __restrict__ x, const float* __res
         x[i] = xp;
     }
 
+}
+
+// ---- DPM-Solver++ multistep update (Lu et al. 2022, Algorithm 2; data prediction, eps parameterisation) -----------------------
+// One element: m0 = (x - sigma_t e) / alpha_t, x' = c_x x + c_0 m0 + c_1 m1 + c_2 m2.  Explicit fmas (at most eight roundings with the
+// guidance combine): the stand-alone kernel and the step-state kernel give the same bits whatever the compiler contracts.
+__device__ __forceinline__ float dpmpp_eps_at(float ec, float eu, float cfg_scale) { return fmaf(cfg_scale, ec - eu, eu); }
+__device__ __forceinline__ float dpmpp_update_at(float x, float e, const DpmCoef& k, float m1, float m2, float& m0) {
+    m0 = fmaf(-k.sigma, e, x) * k.inv_alpha;
+    float r = fmaf(k.c0, m0, k.cx * x);
+    if (k.c1 != 0.f) r = fmaf(k.c1, m1, r);
+    if (k.c2 != 0.f) r = fmaf(k.c2, m2, r);
+    return r;
+}
+// The grid-stride body both kernels run.  16-byte accesses when n is a multiple of 4 and every pointer is 16-byte aligned, scalar
+// otherwise (same per-element arithmetic).  m1 / m2 are loaded only where their coefficient is non-zero: the branch is uniform,
+// so an order-1 or order-2 step issues no loads for the unused ring slots.  x_prev may alias x (element i is read before it is written).
+__device__ __forceinline__ void dpmpp_update_range(const float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u,
+                                                   float cfg_scale, const DpmCoef k, const float* __restrict__ m1, const float* __restrict__ m2,
+                                                   float* x_prev, float* __restrict__ m0_out, int64_t n) {
+    const bool use1 = k.c1 != 0.f, use2 = k.c2 != 0.f;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+    uintptr_t al = (uintptr_t)x | (uintptr_t)eps_c | (uintptr_t)eps_u | (uintptr_t)x_prev | (uintptr_t)m0_out;
+    if (use1) al |= (uintptr_t)m1;
+    if (use2) al |= (uintptr_t)m2;
+    if (!(n & 3) && !(al & 15)) {
+        const int64_t n4 = n >> 2;
+        for (int64_t i = tid; i < n4; i += nth) {
+            const f32x4 xv = ((const f32x4*)x)[i];
+            f32x4 ev = ((const f32x4*)eps_c)[i];
+            if (eps_u) {
+                const f32x4 uv = ((const f32x4*)eps_u)[i];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) ev[j] = dpmpp_eps_at(ev[j], uv[j], cfg_scale);
+            }
+            f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f}, mv, rv;
+            if (use1) a = ((const f32x4*)m1)[i];
+            if (use2) b = ((const f32x4*)m2)[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { float m0; rv[j] = dpmpp_update_at(xv[j], ev[j], k, a[j], b[j], m0); mv[j] = m0; }
+            ((f32x4*)m0_out)[i] = mv;
+            ((f32x4*)x_prev)[i] = rv;
+        }
+        return;
+    }
+    for (int64_t i = tid; i < n; i += nth) {
+        float e = eps_c[i];
+        if (eps_u) e = dpmpp_eps_at(e, eps_u[i], cfg_scale);
+        float m0;
+        const float r = dpmpp_update_at(x[i], e, k, use1 ? m1[i] : 0.f, use2 ? m2[i] : 0.f, m0);
+        m0_out[i] = m0;
+        x_prev[i] = r;
+    }
+}
+
+__global__ void dpmpp_step_kernel(const float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u, float cfg_scale,
+                                  const DpmCoef k, const float* __restrict__ m1, const float* __restrict__ m2, float* x_prev,
+                                  float* __restrict__ m0_out, int64_t n) {
+    dpmpp_update_range(x, eps_c, eps_u, cfg_scale, k, m1, m2, x_prev, m0_out, n);
+}
+
+// in-place x <- x_{t-1} with the coefficients and ring slots step_setup_kernel published; ends the step: the counter moves on
+__global__ void dpmpp_step_state_kernel(float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u, float cfg_scale,
+                                        StepState* st, int64_t n) {
+    const DpmCoef k = {st->cur_dpm[0], st->cur_dpm[1], st->cur_dpm[2], st->cur_dpm[3], st->cur_dpm[4], st->cur_dpm[5]};
+    float* const ring = st->ring;
+    float* const m0 = ring + (int64_t)st->cur_slot[0] * n;
+    const float* const m1 = ring + (int64_t)st->cur_slot[1] * n;
+    const float* const m2 = ring + (int64_t)st->cur_slot[2] * n;
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->counter = st->counter - 1;      // (nothing else in this kernel reads it)
+    dpmpp_update_range(x, eps_c, eps_u, cfg_scale, k, m1, m2, x, m0, n);
 }
 
 // ---- GEGLU: y = a * gelu_erf(gate) ----------------------------------------------------------------
@@ -665,6 +739,22 @@ int launch_ddim_step_state(float* x, const float* eps_c, const float* eps_u, flo
                            hipStream_t stream) {
     hipLaunchKernelGGL(ddim_step_state_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale, st, n);
     MKD_LAUNCH_CHECK("ddim_step_state_kernel");
+    return 0;
+}
+
+int launch_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, const DpmCoef& k, const float* m1,
+                      const float* m2, float* x_prev, float* m0_out, int64_t n, hipStream_t stream) {
+    if (!x || !eps_c || !x_prev || !m0_out || n <= 0) return mkd_fail(-1, "dpmpp_step: bad arguments");
+    if ((k.c1 != 0.f && !m1) || (k.c2 != 0.f && !m2)) return mkd_fail(-1, "dpmpp_step: a non-zero history coefficient needs its x0-prediction");
+    hipLaunchKernelGGL(dpmpp_step_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale, k, m1, m2, x_prev, m0_out, n);
+    MKD_LAUNCH_CHECK("dpmpp_step_kernel");
+    return 0;
+}
+
+int launch_dpmpp_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
+                            hipStream_t stream) {
+    hipLaunchKernelGGL(dpmpp_step_state_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale, st, n);
+    MKD_LAUNCH_CHECK("dpmpp_step_state_kernel");
     return 0;
 }
 

@@ -141,7 +141,16 @@ struct StepState {
     const float* x0; const float* mask; const float* q_noise;
     int mask_bstride, mask_cstride, q_hw, q_chw;
     float q[2 * MKD_MAX_STEPS];            // sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod of table entry i
+    // DPM-Solver++ multistep loop (mkd_sample_dpmpp): x <- c_x x + c_0 m_k + c_1 m_{k-1} + c_2 m_{k-2}, m_k = (x - sigma_t e) / alpha_t the
+    // x0-prediction of executed step k.  dpm[6 i ..] = 1/alpha_t, sigma_t, c_x, c_0, c_1, c_2 of table entry i (mkd_dpmpp_table);
+    // ring [3][n] fp32 holds m_k in slot k mod 3.  cur_dpm / cur_slot (slots of m_k, m_{k-1}, m_{k-2}): this step's, set by
+    // step_setup_kernel like cur[].  ring null: a DDIM loop
+    float dpm[6 * MKD_MAX_STEPS];
+    float* ring;
+    float cur_dpm[6]; int cur_slot[3];
 };
+// the six schedule-only numbers of one DPM-Solver++ step
+struct DpmCoef { float inv_alpha, sigma, cx, c0, c1, c2; };
 
 // Time embedding of a sampling call: row `step` of tab[k] ([steps, n[k]] fp32, one table per net) is copied into every one of
 // the `batch` rows of proj[k] ([batch, n[k]]: what the ResBlock epilogues read as their per-sample row bias).  n[k] % 4 == 0; n[k] = 0: absent.
@@ -273,6 +282,13 @@ int launch_hist_match(const float* dst, const float* ref, const uint8_t* mask_ds
 int launch_temb_select(const TembSel& ts, int step, hipStream_t stream);          // the same copy with a host-side step index (eager loop)
 int launch_ddim_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
                            hipStream_t stream);
+// DPM-Solver++ multistep update (kernels_misc.hip): m0_out <- (x - sigma e) / alpha, x_prev <- c_x x + c_0 m0 + c_1 m1 + c_2 m2 with
+// e = eps_u + cfg_scale (eps_c - eps_u) (eps_u null: eps_c).  m1 / m2 are read only where their coefficient is non-zero; x_prev may be x.
+int launch_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, const DpmCoef& k, const float* m1,
+                      const float* m2, float* x_prev, float* m0_out, int64_t n, hipStream_t stream);
+// the same update in place with the coefficients / ring slots step_setup_kernel published; the step's LAST kernel: advances the counter
+int launch_dpmpp_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
+                            hipStream_t stream);
 int launch_softmax_rows(const bf16_t* x, bf16_t* y, int rows, int cols, hipStream_t stream);
 int launch_post_quant(const float* z, const bf16_t* w, const float* bias, float inv_scale, float* out, int batch, int C, int hw,
                       hipStream_t stream);

@@ -15,6 +15,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from ..ddim import DDIMSampler
+from ..dpm_solver import DPMSolverSampler
 from ..engine import ClipConfig, MkdEngine, NetConfig, VaeConfig
 from ..lib import MkdError
 from ..schedule import DDIMSchedule
@@ -285,6 +286,23 @@ class BaseMakeUpDiffuse:
                           sigmas=None if sigmas is None else [float(v) for v in sigmas], noise=noise, temperature=float(temperature),
                           x0=x0, mask=mask, q_sqrt_ac=q_sqrt_ac, q_sqrt_1m_ac=q_sqrt_1m_ac, q_noise=q_noise)
 
+    def dpmpp_step(self, x, e_c, e_u, scale, coef6, m1=None, m2=None):
+        """one DPM-Solver++ multistep update on the device (DPMSolverSampler's per-step loop): (x_prev, x0-prediction), the kernel
+        arithmetic of the in-library loop"""
+        return self._require_engine().dpmpp_step(x, e_c, e_u, scale, coef6, m1, m2)
+
+    def sample_loop_dpmpp(self, x_latent, cond, timesteps, alphas, alphas_prev, order=2, lower_order_final=True,
+                          unconditional_guidance_scale=1.0, unconditional_conditioning=None, x0=None, mask=None, q_sqrt_ac=None,
+                          q_sqrt_1m_ac=None, q_noise=None):
+        """the whole DPM-Solver++ multistep loop inside libmkd (mkd_sample_dpmpp), on the tables sample_loop_fast takes"""
+        cfg_on = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
+        c = self.cfg_conditioning(unconditional_conditioning, cond) if cfg_on else cond
+        eng = self._bind_cond(c, x_latent.shape[2:])
+        return eng.sample_dpmpp(x_latent, [int(v) for v in timesteps], [float(v) for v in alphas], [float(v) for v in alphas_prev],
+                                order=int(order), lower_order_final=bool(lower_order_final),
+                                cfg_scale=float(unconditional_guidance_scale) if cfg_on else 1.0, use_graph=bool(self.sample_use_graph),
+                                x0=x0, mask=mask, q_sqrt_ac=q_sqrt_ac, q_sqrt_1m_ac=q_sqrt_1m_ac, q_noise=q_noise)
+
     def latent_mask_from_labels(self, seg: torch.Tensor, classes: Sequence[int] = (0, 11, 12), factor: int = 8,
                                 threshold: float = 0.5) -> torch.Tensor:
         """Label map [B,H,W] (uint8) -> latent mask [B,1,H/factor,W/factor] on the device: the area fraction of each block whose label
@@ -292,14 +310,23 @@ class BaseMakeUpDiffuse:
         return self._require_engine().latent_mask_from_labels(seg, classes, factor, threshold)
 
     # ---- sampling drivers ----------------------------------------------------------------------------------------
+    # the sampler sample_log runs: 'ddim' (the reference's) or 'dpmpp' (DPM-Solver++ multistep of order solver_order on the same grid)
+    sampler = 'ddim'
+    solver_order = 2
+
     @torch.no_grad()
     def sample_log(self, cond: dict, batch_size: int, ddim: bool, ddim_steps: int, **kwargs):
-        """UPSTREAM ControlLDM.sample_log: latent shape from the hint, x_T ~ N(0, I) unless given."""
+        """UPSTREAM ControlLDM.sample_log: latent shape from the hint, x_T ~ N(0, I) unless given.  Upstream ignores ``ddim`` beyond
+        picking DDIM; the ``sampler`` attribute is the switch between the two solvers."""
         if not ddim:
             raise NotImplementedError('only the DDIM sampler is on the MakeupDiffuse test path')
-        sampler = DDIMSampler(self)
         _, _, h, w = cond['c_concat'][0].shape
         shape = (self.channels, h // 8, w // 8)
+        if self.sampler == 'dpmpp':
+            return DPMSolverSampler(self).sample(ddim_steps, batch_size, shape, cond, order=self.solver_order, verbose=False, **kwargs)
+        if self.sampler != 'ddim':
+            raise ValueError(f"sampler must be 'ddim' or 'dpmpp', got {self.sampler!r}")
+        sampler = DDIMSampler(self)
         return sampler.sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
 
     def decode_first_stage(self, z: torch.Tensor) -> torch.Tensor:
@@ -386,8 +413,15 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
     def __init__(self, saved_dir: str = './results', model_name: str = 'makeupdiffuse', img_name_key: str = 'img_name',
                  unconditional_guidance_scale: float = 9, ddim_steps: int = 50, ddim_eta: float = 0.0, sample: bool = True,
                  fix_background: bool = False, background_classes: Sequence[int] = (0, 11, 12), background_threshold: float = 0.5,
-                 seg_key: str = 'nonmakeup_seg', makeup_score: bool = False, ref_seg_key: str = 'makeup_seg', *args, **kwargs):
+                 seg_key: str = 'nonmakeup_seg', makeup_score: bool = False, ref_seg_key: str = 'makeup_seg', sampler: str = 'ddim',
+                 solver_order: int = 2, *args, **kwargs):
+        if sampler not in ('ddim', 'dpmpp'):
+            raise ValueError(f"sampler must be 'ddim' or 'dpmpp', got {sampler!r}")
+        if solver_order not in (1, 2, 3):
+            raise ValueError('solver_order must be 1, 2 or 3')
         super().__init__(*args, **kwargs)
+        # log_results' sampler: 'dpmpp' runs both passes on DPM-Solver++ multistep (ddim_steps is then its number of evaluations)
+        self.sampler, self.solver_order = sampler, int(solver_order)
         # makeup score of every decoded sample (makeup_score.transfer_score): off by default, then log_results is unchanged
         self.makeup_score = bool(makeup_score)
         self.ref_seg_key = ref_seg_key

@@ -136,8 +136,25 @@ def _f32c(t: torch.Tensor, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+def dpmpp_table(alphas: Sequence[float], alphas_prev: Sequence[float], order: int = 2,
+                lower_order_final: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+    """Coefficients of the multistep DPM-Solver++ on a DDIM step grid (include/mkd.h mkd_dpmpp_table; host only, needs no device):
+    ``(coef [n, 6] float32, step_order [n] int32)``, row i = 1/alpha_t, sigma_t, c_x, c_0, c_1, c_2 of table entry i."""
+    n = len(alphas)
+    if n <= 0 or len(alphas_prev) != n:
+        raise ValueError('alphas / alphas_prev must be non-empty and equally long')
+    a = (C.c_float * n)(*[float(v) for v in alphas])
+    ap = (C.c_float * n)(*[float(v) for v in alphas_prev])
+    out = (C.c_float * (6 * n))()
+    so = (C.c_int * n)()
+    _lib.check(_lib.load().mkd_dpmpp_table(n, a, ap, int(order), int(bool(lower_order_final)), out, so), 'mkd_dpmpp_table')
+    return np.ctypeslib.as_array(out).reshape(n, 6).copy(), np.ctypeslib.as_array(so).astype(np.int32)
+
+
 class MkdEngine:
     """Owns one mkd_ctx on the current CUDA(HIP) device."""
+
+    dpmpp_table = staticmethod(dpmpp_table)
 
     UNET_PREFIX = 'model.diffusion_model.'
     CONTROL_PREFIX = 'control_model.'
@@ -482,6 +499,62 @@ class MkdEngine:
                 _lib.check(self.lib.mkd_sample(self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, s1,
                                                float(cfg_scale), C.c_void_p(out.data_ptr()), int(use_graph),
                                                C.c_void_p(_stream())), 'mkd_sample')
+        return out
+
+    def dpmpp_step(self, x, eps_c, eps_u, cfg_scale, coef6, m1=None, m2=None):
+        """One DPM-Solver++ multistep update (mkd_dpmpp_step): ``coef6`` = a row of ``dpmpp_table``; m1 / m2 = the x0-predictions
+        of the previous two steps, needed where coef6[4] / coef6[5] is non-zero.  Returns (x_prev, m0)."""
+        x = _f32c(x, self.device); eps_c = _f32c(eps_c, self.device)
+        eps_u = None if eps_u is None else _f32c(eps_u, self.device)
+        k = [float(np.float32(v)) for v in coef6]
+        if len(k) != 6:
+            raise ValueError('coef6 must have six entries (a row of dpmpp_table)')
+        if (k[4] != 0.0 and m1 is None) or (k[5] != 0.0 and m2 is None):
+            raise ValueError('dpmpp_step: a non-zero history coefficient needs its x0-prediction')
+        m1 = None if (m1 is None or k[4] == 0.0) else _f32c(m1, self.device)
+        m2 = None if (m2 is None or k[5] == 0.0) else _f32c(m2, self.device)
+        for t in (eps_c, eps_u, m1, m2):
+            if t is not None and t.numel() != x.numel():
+                raise ValueError('dpmpp_step: every tensor must have the size of x')
+        x_prev = torch.empty_like(x)
+        m0 = torch.empty_like(x)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mkd_dpmpp_step(C.c_void_p(x.data_ptr()), C.c_void_p(eps_c.data_ptr()), C.c_void_p(_ptr(eps_u)),
+                                               float(cfg_scale), (C.c_float * 6)(*k), C.c_void_p(_ptr(m1)), C.c_void_p(_ptr(m2)),
+                                               C.c_void_p(x_prev.data_ptr()), C.c_void_p(m0.data_ptr()), x.numel(),
+                                               C.c_void_p(_stream())), 'mkd_dpmpp_step')
+        return x_prev, m0
+
+    def sample_dpmpp(self, x_T: torch.Tensor, timesteps: Sequence[int], alphas: Sequence[float], alphas_prev: Sequence[float],
+                     order: int = 2, lower_order_final: bool = True, cfg_scale: float = 1.0, use_graph: bool = False,
+                     x0: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, q_sqrt_ac: Optional[Sequence[float]] = None,
+                     q_sqrt_1m_ac: Optional[Sequence[float]] = None, q_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The whole DPM-Solver++ multistep loop in one call (mkd_sample_dpmpp): ``sample``'s contract on the same DDIM tables
+        (prepared batch B or 2B with guidance, masked sampling through x0 / mask / q_*), deterministic."""
+        x_T = _f32c(x_T, self.device)
+        cfg_on = float(cfg_scale) != 1.0
+        want_b = self.batch // 2 if cfg_on else self.batch
+        if (x_T.dim() != 4 or tuple(x_T.shape[1:]) != (self.cfg.in_channels, *self.latent_hw) or x_T.shape[0] != want_b
+                or (cfg_on and self.batch % 2)):
+            raise ValueError(f'x_T {tuple(x_T.shape)} does not match the prepared conditioning: expected '
+                             f'({want_b}, {self.cfg.in_channels}, {self.latent_hw[0]}, {self.latent_hw[1]})'
+                             + (' (CFG: prepared batch is [uncond; cond])' if cfg_on else ''))
+        n = len(timesteps)
+        if n <= 0 or not (len(alphas) == len(alphas_prev) == n):
+            raise ValueError('timesteps / alphas / alphas_prev must be non-empty and equally long')
+        ts = (C.c_int64 * n)(*[int(v) for v in timesteps])
+        a = (C.c_float * n)(*[float(v) for v in alphas])
+        ap = (C.c_float * n)(*[float(v) for v in alphas_prev])
+        out = torch.empty_like(x_T)
+        qm = keep = None
+        if mask is not None or x0 is not None:
+            qm, keep = self._sample_mask(x_T, n, x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mkd_sample_dpmpp(self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, int(order),
+                                                 int(bool(lower_order_final)), None if qm is None else C.byref(qm), float(cfg_scale),
+                                                 C.c_void_p(out.data_ptr()), int(use_graph), C.c_void_p(_stream())), 'mkd_sample_dpmpp')
+        if keep is not None:
+            self._loop_keep = (keep, None)          # (as in sample(): held until the next masked call)
         return out
 
     def _mask_geometry(self, mask: torch.Tensor, B: int, Cn: int, hw) -> Tuple[int, int]:

@@ -63,6 +63,9 @@ def build_parser():
     ap.add_argument('--batch-size', type=int, default=1)
     ap.add_argument('--res', type=int, default=256)
     ap.add_argument('--ddim-steps', type=int, default=None)
+    ap.add_argument('--sampler', choices=('ddim', 'dpmpp'), default='ddim', help='dpmpp: DPM-Solver++ multistep on the DDIM step grid '
+                    '(--ddim-steps is then its number of evaluations, typically 15-25)')
+    ap.add_argument('--solver-order', type=int, choices=(1, 2, 3), default=2, help='order of --sampler dpmpp')
     ap.add_argument('--only-mid-control', action='store_true')
     ap.add_argument('--out', default='./results')
     ap.add_argument('--data-root', default=None, help='folder with images/ and a pairs file (reference TestFixed_Dataset layout)')
@@ -104,6 +107,7 @@ def main():
         model.makeup_score = True
     if args.ddim_steps is not None:
         model.ddim_steps = args.ddim_steps
+    model.sampler, model.solver_order = args.sampler, args.solver_order
     if args.ckpt:
         model.load_state_dict(load_state_dict(args.ckpt, location='cpu'))
     torch.cuda.set_device(local)
