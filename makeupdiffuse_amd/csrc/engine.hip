@@ -87,6 +87,16 @@ struct Epi {
 
 typedef std::function<int(hipStream_t)> OpFn;
 
+// One call of the in-library reverse loop: the mkd_sample* entries fill in what they have
+struct SampleReq {
+    const float* x_T = nullptr; int batch = 0, n_steps = 0;
+    const int64_t* timesteps = nullptr; const float* alphas = nullptr; const float* alphas_prev = nullptr; const float* s1m = nullptr;
+    const float* sigmas = nullptr; const float* noise = nullptr; float temperature = 1.0f;          // eta > 0
+    const mkd_sample_mask* qm = nullptr;          // masked sampling
+    const float* dpm = nullptr;                   // host [n_steps][6] of mkd_dpmpp_table: the DPM-Solver++ loop; null: DDIM
+    float cfg_scale = 1.0f; float* x_out = nullptr; int use_graph = 0;
+};
+
 // What a plan op launches, kept beside its closure for the ops that have a GROUPED form (mkd_common.h: Pair): when the ControlNet
 // and the UNet encoder emit the same op on the same geometry, the pair becomes one launch (mkd_ctx::group_ops).
 enum DescType { D_NONE = 0, D_GEMM, D_GN, D_GN_SLAB, D_LN, D_ATTN, D_CONV_IN };
@@ -277,9 +287,13 @@ struct mkd_ctx {
     float* s_ring = nullptr; int64_t s_ring_n = 0;        // DPM-Solver++ history ring [3][n] fp32: allocated on first use, grown with the batch
     hipStream_t loop_stream = nullptr; hipEvent_t ev_loop_in = nullptr, ev_loop_out = nullptr;
     hipGraphExec_t multi_graph = nullptr; int multi_graph_steps = 0;      // MKD_GRAPH_STEPS consecutive steps as one graph
-    hipGraphExec_t step_graph = nullptr; int step_graph_cfg = -1; float step_graph_scale = 0.f; int plan_generation = 0, step_graph_gen = -1;
-    int step_graph_temb = -1, step_graph_batch = -1;
-    int step_graph_solver = -1, seg_solver = -1;          // solver kind of the captured step: 0 DDIM, 1 DPM-Solver++ (its order lives in the table)
+    // everything the nodes of a captured step depend on: plan, guidance (on, scale), where the time embedding comes from, batch, and
+    // the solver whose kernel ends the step (0 DDIM, 1 DPM-Solver++; its order lives in the table)
+    struct StepKey {
+        int gen = -1, cfg = -1, temb = -1, batch = -1, solver = -1; float scale = 0.f;
+        bool operator==(const StepKey& o) const { return gen == o.gen && cfg == o.cfg && temb == o.temb && batch == o.batch && solver == o.solver && scale == o.scale; }
+    };
+    hipGraphExec_t step_graph = nullptr; StepKey step_key; int plan_generation = 0;
     // Graph mode 2 (MKD_GRAPH_MODE=2; default 1 = one captured graph per step): one step = LINEAR graphs, one per (stream, stretch
     // between two cross-stream edges), launched on their own streams and ordered by events.  A captured graph with two BRANCHES is
     // replayed with its branches serialised node by node (tools/micro/launch_floor.hip: 3.2 us per pair of empty nodes, 5.3-5.9 us
@@ -291,7 +305,7 @@ struct mkd_ctx {
     struct SegAction { int type; int sid; int idx; };      // type 0: launch seg_graphs[idx] / seg_eager[idx] on stream sid; 1: record event idx on sid; 2: sid waits for event idx
     struct Segment { hipGraphExec_t graph = nullptr; std::vector<OpFn> eager; };
     std::vector<Segment> segs; std::vector<SegAction> seg_actions; std::vector<hipEvent_t> seg_events;
-    int seg_gen = -1, seg_cfg = -1, seg_temb = -1, seg_batch = -1; float seg_scale = 0.f;
+    StepKey seg_key;
     int graph_mode = getenv("MKD_GRAPH_MODE") ? atoi(getenv("MKD_GRAPH_MODE")) : 1;
 
     // ---------------------------------------------------------------------------------------------
@@ -1125,11 +1139,13 @@ struct mkd_ctx {
         ts.batch = B;
         return ts;
     }
-    // fills the table for this call's timesteps (host array) on `stream`
+    // table on: fills it for this call's timesteps (host array) on `stream`; the call's steps then leave the plan's own chain out
     int run_temb_table(int n_steps, const int64_t* timesteps, hipStream_t stream) {
+        if (!temb_table) return 0;
         int rc = build_temb_table(n_steps); if (rc) return rc;
         MKD_HIP_CHECK(hipMemcpyAsync(temb_t, timesteps, (size_t)n_steps * sizeof(int64_t), hipMemcpyHostToDevice, stream));
         for (auto& op : plan_temb_tab) { rc = op.fn(stream); if (rc) return rc; }
+        temb_skip = true;
         return 0;
     }
 
@@ -1776,26 +1792,64 @@ struct mkd_ctx {
 
     void drop_segments() {
         for (auto& sg : segs) if (sg.graph) hipGraphExecDestroy(sg.graph);
-        segs.clear(); seg_actions.clear(); seg_gen = -1;
+        segs.clear(); seg_actions.clear(); seg_key = StepKey{};
     }
+    int64_t latent_n(int batch) const { return (int64_t)batch * cfg.in_channels * h * w; }
+    // what the evaluation of a step on the latents x reads, and where eps_cond / eps_uncond land (guidance: [uncond; cond] of s_xin)
+    struct StepIo { const float* x; const float* ec; const float* eu; };
+    StepIo step_io(bool cfg_on, const float* x, int64_t n) const { return cfg_on ? StepIo{s_xin, s_eps + n, s_eps} : StepIo{x, s_eps, nullptr}; }
+    // ONE reverse step that reads its timestep / coefficients from the device step state (the graph body), around the evaluation:
+    // head = step setup (+ the batch doubling with guidance), tail = the solver's last kernel
+    struct StateStep { std::vector<OpFn> head; StepIo io; OpFn tail; };
+    StateStep state_step(const StepKey& k) {
+        mkd_ctx* self = this;
+        const int64_t n = latent_n(k.batch);
+        StateStep s; s.io = step_io(k.cfg != 0, s_xa, n);
+        s.head.push_back([self, Bn = B, n](hipStream_t st) {
+            const TembSel ts = self->temb_sel();
+            return launch_step_setup(self->s_state, self->s_t, Bn, self->s_xa, n, st, self->temb_skip ? &ts : nullptr); });
+        if (k.cfg) s.head.push_back([self, n](hipStream_t st) { return launch_repeat_batch(self->s_xa, self->s_xin, n, 2, st); });
+        s.tail = [self, io = s.io, n, dpm_on = k.solver != 0, scale = k.scale](hipStream_t st) {
+            return dpm_on ? launch_dpmpp_step_state(self->s_xa, io.ec, io.eu, scale, self->s_state, n, st)
+                          : launch_ddim_step_state(self->s_xa, io.ec, io.eu, scale, self->s_state, n, st); };
+        return s;
+    }
+    int enqueue_state_steps(const StepKey& k, int steps, hipStream_t stream) {
+        const StateStep s = state_step(k);
+        for (int i = 0; i < steps; ++i) {
+            for (auto& f : s.head) { int rc = f(stream); if (rc) return rc; }
+            int rc = eps(s.io.x, s_t, s_eps, stream); if (rc) return rc;
+            rc = s.tail(stream); if (rc) return rc;
+        }
+        return 0;
+    }
+
+    // Captures what `body` enqueues on `st` into an executable graph (`capturing` set meanwhile).  The capture is always ended and
+    // the hipGraph_t destroyed; on any failure *out is left null.
+    int capture(hipStream_t st, const OpFn& body, hipGraphExec_t* out, const char* what) {
+        *out = nullptr;
+        hipGraph_t g = nullptr;
+        MKD_HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+        capturing = true;
+        int rc = body(st);
+        capturing = false;
+        hipError_t e = hipStreamEndCapture(st, &g);
+        if (!rc && e != hipSuccess) rc = mkd_fail(MKD_ERR_HIP, std::string("hipStreamEndCapture") + what + ": " + hipGetErrorString(e));
+        if (!rc && (e = hipGraphInstantiate(out, g, nullptr, nullptr, 0)) != hipSuccess)
+            { *out = nullptr; rc = mkd_fail(MKD_ERR_HIP, std::string("hipGraphInstantiate") + what + ": " + hipGetErrorString(e)); }
+        if (g) hipGraphDestroy(g);
+        return rc;
+    }
+
     // One reverse step as per-stream linear graphs (graph mode 2).  Walks the step's launches in plan order; every cross-stream edge
     // that the single-graph capture keeps (in_graph) closes the pending stretch of both its streams.
-    int build_segments(int batch, bool cfg_on, float cfg_scale, bool dpm_on) {
+    int build_segments(const StepKey& k) {
         drop_segments();
-        const int64_t n = (int64_t)batch * cfg.in_channels * h * w;
-        mkd_ctx* self = this;
         struct Item { OpFn fn; int sid; int from, to; };
         std::vector<Item> items;
-        const int Bn = B;
-        items.push_back({[self, Bn, n](hipStream_t st) {
-            const TembSel ts = self->temb_sel();
-            return launch_step_setup(self->s_state, self->s_t, Bn, self->s_xa, n, st, self->temb_skip ? &ts : nullptr); }, 0, -1, -1});
-        const float* ec; const float* eu = nullptr;
-        if (cfg_on) {
-            items.push_back({[self, n](hipStream_t st) { return launch_repeat_batch(self->s_xa, self->s_xin, n, 2, st); }, 0, -1, -1});
-            io_x = s_xin; eu = s_eps; ec = s_eps + n;
-        } else { io_x = s_xa; ec = s_eps; }
-        io_t = s_t; io_out = s_eps;
+        const StateStep s = state_step(k);
+        for (auto& f : s.head) items.push_back({f, 0, -1, -1});
+        io_x = s.io.x; io_t = s_t; io_out = s_eps;
         for (auto& op : plan_eps) {
             if (op.edge_from >= 0) { if (op.edge_in_graph) items.push_back({nullptr, 0, arena_of(op.edge_from), arena_of(op.edge_to)}); continue; }
             if (op.launches == 0 && op.kind == K_MISC && op.label.rfind("edge", 0) == 0) continue;
@@ -1818,26 +1872,18 @@ struct mkd_ctx {
 #endif
             items.push_back({op.fn, arena_of(op.cap_sid >= 0 ? op.cap_sid : op.sid), -1, -1});
         }
-        if (dpm_on) items.push_back({[self, ec, eu, cfg_scale, n](hipStream_t st) { return launch_dpmpp_step_state(self->s_xa, ec, eu, cfg_scale, self->s_state, n, st); }, 0, -1, -1});
-        else items.push_back({[self, ec, eu, cfg_scale, n](hipStream_t st) { return launch_ddim_step_state(self->s_xa, ec, eu, cfg_scale, self->s_state, n, st); }, 0, -1, -1});
+        items.push_back({s.tail, 0, -1, -1});
         std::vector<OpFn> pend[NS];
         int rc = 0;
         auto flush = [&](int sid) -> int {
             if (pend[sid].empty()) return 0;
             Segment sg;
             if (pend[sid].size() <= 2) sg.eager = pend[sid];
-            else {
-                hipStream_t st = stream_of(sid);
-                hipGraph_t g = nullptr;
-                MKD_HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-                int r = 0;
-                for (auto& f : pend[sid]) { r = f(st); if (r) break; }
-                hipError_t e = hipStreamEndCapture(st, &g);
-                if (r) { if (g) hipGraphDestroy(g); return r; }
-                if (e != hipSuccess) return mkd_fail(MKD_ERR_HIP, std::string("hipStreamEndCapture (segment): ") + hipGetErrorString(e));
-                e = hipGraphInstantiate(&sg.graph, g, nullptr, nullptr, 0);
-                hipGraphDestroy(g);
-                if (e != hipSuccess) return mkd_fail(MKD_ERR_HIP, std::string("hipGraphInstantiate (segment): ") + hipGetErrorString(e));
+            else {          // (under capture(), ops that look at `capturing` behave as in the single-graph capture)
+                const int r = capture(stream_of(sid), [&](hipStream_t st) {
+                    for (auto& f : pend[sid]) { int r = f(st); if (r) return r; }
+                    return 0; }, &sg.graph, " (segment)");
+                if (r) return r;
             }
             segs.push_back(std::move(sg));
             seg_actions.push_back({0, sid, (int)segs.size() - 1});
@@ -1845,7 +1891,6 @@ struct mkd_ctx {
             return 0;
         };
         int n_ev = 0;
-        capturing = true;          // (ops that look at the flag behave as in the single-graph capture)
         for (auto& it : items) {
             if (it.from >= 0) {
                 if (it.from == it.to) continue;
@@ -1862,10 +1907,8 @@ struct mkd_ctx {
             } else pend[it.sid].push_back(it.fn);
         }
         for (int sid = NS - 1; sid >= 0 && !rc; --sid) rc = flush(sid);      // (every side stream was joined by an edge: only stream 0 has work left)
-        capturing = false;
         if (rc) { drop_segments(); return rc; }
-        seg_gen = plan_generation; seg_cfg = (int)cfg_on; seg_scale = cfg_scale; seg_temb = (int)temb_skip; seg_batch = batch;
-        seg_solver = (int)dpm_on;
+        seg_key = k;
         return 0;
     }
     int run_segments() {
@@ -1885,25 +1928,7 @@ struct mkd_ctx {
         drop_segments();
         if (step_graph) { hipGraphExecDestroy(step_graph); step_graph = nullptr; }
         if (multi_graph) { hipGraphExecDestroy(multi_graph); multi_graph = nullptr; multi_graph_steps = 0; }
-        step_graph_gen = -1;
-    }
-
-    // enqueue ONE reverse step that reads its timestep / coefficients from the device step state (graph body)
-    int enqueue_state_step(int batch, bool cfg_on, float cfg_scale, bool dpm_on, hipStream_t stream) {
-        const int64_t n = (int64_t)batch * cfg.in_channels * h * w;
-        const TembSel ts = temb_sel();
-        int rc = launch_step_setup(s_state, s_t, B, s_xa, n, stream, temb_skip ? &ts : nullptr); if (rc) return rc;
-        const float* ec; const float* eu = nullptr;
-        if (cfg_on) {
-            rc = launch_repeat_batch(s_xa, s_xin, n, 2, stream); if (rc) return rc;
-            rc = eps(s_xin, s_t, s_eps, stream); if (rc) return rc;
-            eu = s_eps; ec = s_eps + n;
-        } else {
-            rc = eps(s_xa, s_t, s_eps, stream); if (rc) return rc;
-            ec = s_eps;
-        }
-        if (dpm_on) return launch_dpmpp_step_state(s_xa, ec, eu, cfg_scale, s_state, n, stream);
-        return launch_ddim_step_state(s_xa, ec, eu, cfg_scale, s_state, n, stream);
+        step_key = StepKey{};
     }
 
     // the DPM-Solver++ history ring for latents of n elements (the captured step reads its address from the step state, so growing
@@ -1917,187 +1942,161 @@ struct mkd_ctx {
         return 0;
     }
 
-    int sample(const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
-               const float* alphas_prev, const float* s1m, float cfg_scale, float* x_out, int use_graph, hipStream_t stream,
-               const float* sigmas = nullptr, const float* noise = nullptr, float temperature = 1.0f, const mkd_sample_mask* qm = nullptr,
-               const float* dpm = nullptr) {
-        const int rc = sample_impl(x_T, batch, n_steps, timesteps, alphas, alphas_prev, s1m, cfg_scale, x_out, use_graph, stream, sigmas, noise,
-                                   temperature, qm, dpm);
-        temb_skip = false;          // (a later mkd_eps runs its own time-embedding chain)
-        return rc;
-    }
-    int sample_impl(const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
-               const float* alphas_prev, const float* s1m, float cfg_scale, float* x_out, int use_graph, hipStream_t stream,
-               const float* sigmas, const float* noise, float temperature, const mkd_sample_mask* qm, const float* dpm) {
-        // dpm: host [n_steps][6] of mkd_dpmpp_table -> the DPM-Solver++ multistep loop (deterministic: sigmas / noise / s1m unused);
-        // null: DDIM.  Setup, evaluation and the masked blend are shared; only the step's last kernel differs.
-        const bool dpm_on = dpm != nullptr;
+    // the checks of a sampling call; *stochastic: some sigma is non-zero (eta > 0)
+    int validate(const SampleReq& r, bool* stochastic) const {
         if (!prepared) return mkd_fail(MKD_ERR_STATE, "mkd_sample before mkd_prepare");
-        bool stochastic = false;
-        if (sigmas) for (int i = 0; i < n_steps; ++i) {
-            if (!(sigmas[i] >= 0.f) || 1.0f - alphas_prev[i] - sigmas[i] * sigmas[i] < 0.f) return mkd_fail(MKD_ERR_ARG, "mkd_sample_eta: sigma out of range");
-            stochastic = stochastic || sigmas[i] != 0.f;
+        *stochastic = false;
+        if (r.sigmas) for (int i = 0; i < r.n_steps; ++i) {
+            if (!(r.sigmas[i] >= 0.f) || 1.0f - r.alphas_prev[i] - r.sigmas[i] * r.sigmas[i] < 0.f) return mkd_fail(MKD_ERR_ARG, "mkd_sample_eta: sigma out of range");
+            *stochastic = *stochastic || r.sigmas[i] != 0.f;
         }
-        if (stochastic && !noise) return mkd_fail(MKD_ERR_ARG, "mkd_sample_eta: sigma > 0 needs the noise draws");
-        const bool cfg_on = cfg_scale != 1.0f;
-        if (cfg_on ? (B != 2 * batch) : (B != batch))
+        if (*stochastic && !r.noise) return mkd_fail(MKD_ERR_ARG, "mkd_sample_eta: sigma > 0 needs the noise draws");
+        if (r.cfg_scale != 1.0f ? (B != 2 * r.batch) : (B != r.batch))
             return mkd_fail(MKD_ERR_ARG, "mkd_sample: prepared batch must be B (cfg_scale == 1) or 2B (uncond first)");
-        if (n_steps <= 0 || !timesteps || !alphas || !alphas_prev || (!s1m && !dpm_on) || !x_T || !x_out)
+        if (r.n_steps <= 0 || !r.timesteps || !r.alphas || !r.alphas_prev || (!r.s1m && !r.dpm) || !r.x_T || !r.x_out)
             return mkd_fail(MKD_ERR_ARG, "mkd_sample: bad arguments");
+        const mkd_sample_mask* qm = r.qm;
         if (qm && (!qm->x0 || !qm->mask || !qm->noise || !qm->sqrt_alphas_cumprod || !qm->sqrt_one_minus_alphas_cumprod))
             return mkd_fail(MKD_ERR_ARG, "mkd_sample_masked: x0, mask, noise and both tables are required");
-        if (qm && ((qm->mask_batch != 1 && qm->mask_batch != batch) || (qm->mask_channels != 1 && qm->mask_channels != cfg.in_channels)))
+        if (qm && ((qm->mask_batch != 1 && qm->mask_batch != r.batch) || (qm->mask_channels != 1 && qm->mask_channels != cfg.in_channels)))
             return mkd_fail(MKD_ERR_ARG, "mkd_sample_masked: mask must be [1 or B, 1 or C, h, w]");
-        const int64_t n = (int64_t)batch * cfg.in_channels * h * w;
-        const int hw = h * w;
-        if (dpm_on) { int rc = ensure_ring(n); if (rc) return rc; }
-        MKD_HIP_CHECK(hipMemcpyAsync(s_xa, x_T, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
-        if (use_graph) {
-            // --- hipGraph path: one captured step (both streams, fork/join included), replayed n_steps times ---
-            if (n_steps > MKD_MAX_STEPS) return mkd_fail(MKD_ERR_ARG, "mkd_sample: too many steps for the graph path");
-            if (!h_state) MKD_HIP_CHECK(hipHostMalloc((void**)&h_state, sizeof(StepState)));
-            if (!s_state) MKD_HIP_CHECK(hipMalloc((void**)&s_state, sizeof(StepState)));
-            if (!loop_stream) {
-                // the caller's stream may be the legacy null stream, which cannot be captured: run the loop on a
-                // private stream ordered against the caller's with events
-                MKD_HIP_CHECK(hipStreamCreateWithFlags(&loop_stream, hipStreamNonBlocking));
-                MKD_HIP_CHECK(hipEventCreateWithFlags(&ev_loop_in, hipEventDisableTiming));
-                MKD_HIP_CHECK(hipEventCreateWithFlags(&ev_loop_out, hipEventDisableTiming));
-            }
-            MKD_HIP_CHECK(hipStreamSynchronize(loop_stream));     // h_state may still feed a previous call's copy
-            h_state->counter = n_steps - 1;
-            for (int i = 0; i < n_steps; ++i) {
-                h_state->timesteps[i] = timesteps[i];
-                h_state->coef[4 * i + 0] = 1.0f / sqrtf(alphas[i]);
-                h_state->coef[4 * i + 1] = sqrtf(alphas_prev[i]);
-                const float sg = stochastic ? sigmas[i] : 0.f;
-                h_state->coef[4 * i + 2] = sqrtf(1.0f - alphas_prev[i] - sg * sg);
-                h_state->coef[4 * i + 3] = s1m ? s1m[i] : 0.f;
-                h_state->sigma[i] = sg;
-                for (int j = 0; j < 6; ++j) h_state->dpm[6 * i + j] = dpm_on ? dpm[6 * i + j] : 0.f;
-            }
-            h_state->ring = dpm_on ? s_ring : nullptr;
-            for (int j = 0; j < 6; ++j) h_state->cur_dpm[j] = 0.f;
-            h_state->cur_slot[0] = h_state->cur_slot[1] = h_state->cur_slot[2] = 0;
-            h_state->noise = stochastic ? noise : nullptr; h_state->temperature = temperature; h_state->n_steps = n_steps;
-            h_state->cur_sigma = 0.f; h_state->cur_row = 0;
-            // masked sampling: read by step_setup_kernel; x0 null leaves the (shared) captured step unmasked
-            h_state->x0 = qm ? qm->x0 : nullptr; h_state->mask = qm ? qm->mask : nullptr; h_state->q_noise = qm ? qm->noise : nullptr;
-            h_state->q_hw = hw; h_state->q_chw = cfg.in_channels * hw;
-            h_state->mask_bstride = (qm && qm->mask_batch != 1) ? qm->mask_channels * hw : 0;
-            h_state->mask_cstride = (qm && qm->mask_channels != 1) ? hw : 0;
-            for (int i = 0; i < n_steps; ++i) {
-                h_state->q[2 * i] = qm ? qm->sqrt_alphas_cumprod[i] : 0.f;
-                h_state->q[2 * i + 1] = qm ? qm->sqrt_one_minus_alphas_cumprod[i] : 0.f;
-            }
-            MKD_HIP_CHECK(hipEventRecord(ev_loop_in, stream));
-            MKD_HIP_CHECK(hipStreamWaitEvent(loop_stream, ev_loop_in, 0));
-            MKD_HIP_CHECK(hipMemcpyAsync(s_state, h_state, sizeof(StepState), hipMemcpyHostToDevice, loop_stream));
-            if (temb_table) {
-                int rc = run_temb_table(n_steps, timesteps, loop_stream); if (rc) return rc;
-                temb_skip = true;
-            }
-            if (graph_mode == 2 && dual_stream) {
-                run_main = loop_stream; run_serial = false;
-                if (segs.empty() || seg_gen != plan_generation || seg_cfg != (int)cfg_on || seg_scale != cfg_scale || seg_temb != (int)temb_skip || seg_batch != batch ||
-                    seg_solver != (int)dpm_on) {
-                    int rc = build_segments(batch, cfg_on, cfg_scale, dpm_on); if (rc) return rc;
-                }
-                for (int i = 0; i < n_steps; ++i) { int rc = run_segments(); if (rc) return rc; }
-                MKD_HIP_CHECK(hipMemcpyAsync(x_out, s_xa, n * sizeof(float), hipMemcpyDeviceToDevice, loop_stream));
-                MKD_HIP_CHECK(hipEventRecord(ev_loop_out, loop_stream));
-                MKD_HIP_CHECK(hipStreamWaitEvent(stream, ev_loop_out, 0));
-                return 0;
-            }
-            // both graphs are keyed on everything their nodes depend on (plan, guidance, batch, where the time embedding comes from,
-            // the solver whose kernel ends the step)
-            if (!step_graph || step_graph_gen != plan_generation || step_graph_cfg != (int)cfg_on || step_graph_scale != cfg_scale ||
-                step_graph_temb != (int)temb_skip || step_graph_batch != batch || step_graph_solver != (int)dpm_on) {
-                drop_graph();
-                hipGraph_t g = nullptr;
-                MKD_HIP_CHECK(hipStreamBeginCapture(loop_stream, hipStreamCaptureModeRelaxed));
-                capturing = true;
-                int rc = enqueue_state_step(batch, cfg_on, cfg_scale, dpm_on, loop_stream);
-                capturing = false;
-                hipError_t e = hipStreamEndCapture(loop_stream, &g);
-                if (rc) { if (g) hipGraphDestroy(g); return rc; }
-                if (e != hipSuccess) return mkd_fail(MKD_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-                e = hipGraphInstantiate(&step_graph, g, nullptr, nullptr, 0);
-                hipGraphDestroy(g);
-                if (e != hipSuccess) { step_graph = nullptr; return mkd_fail(MKD_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
-                step_graph_gen = plan_generation; step_graph_cfg = (int)cfg_on; step_graph_scale = cfg_scale;
-                step_graph_temb = (int)temb_skip; step_graph_batch = batch; step_graph_solver = (int)dpm_on;
-            }
-            // (multi_graph needs no key of its own: whenever step_graph's key above changes, drop_graph() destroys both)
-            // MKD_GRAPH_STEPS = k > 1: k consecutive steps captured as ONE graph (the step reads its index from the device-resident
-            // counter, so the same capture repeated k times is k different steps); the remainder runs on the single-step graph
-            // (default 5: a graph boundary costs ~30 us; batch 8: 5.85 -> 5.82 ms per evaluation, batch 1: 2.99 -> 2.97)
-            const int gsteps = graph_steps;
-            int done = 0;
-            if (gsteps > 1 && n_steps >= gsteps) {
-                if (!multi_graph || multi_graph_steps != gsteps) {
-                    if (multi_graph) { hipGraphExecDestroy(multi_graph); multi_graph = nullptr; }
-                    hipGraph_t g = nullptr;
-                    MKD_HIP_CHECK(hipStreamBeginCapture(loop_stream, hipStreamCaptureModeRelaxed));
-                    capturing = true;
-                    int rc = 0;
-                    for (int k = 0; k < gsteps && !rc; ++k) rc = enqueue_state_step(batch, cfg_on, cfg_scale, dpm_on, loop_stream);
-                    capturing = false;
-                    hipError_t e = hipStreamEndCapture(loop_stream, &g);
-                    if (rc) { if (g) hipGraphDestroy(g); return rc; }
-                    if (e != hipSuccess) return mkd_fail(MKD_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-                    e = hipGraphInstantiate(&multi_graph, g, nullptr, nullptr, 0);
-                    hipGraphDestroy(g);
-                    if (e != hipSuccess) { multi_graph = nullptr; return mkd_fail(MKD_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
-                    multi_graph_steps = gsteps;
-                }
-                for (; done + gsteps <= n_steps; done += gsteps) MKD_HIP_CHECK(hipGraphLaunch(multi_graph, loop_stream));
-            }
-            for (int i = done; i < n_steps; ++i) MKD_HIP_CHECK(hipGraphLaunch(step_graph, loop_stream));
-            MKD_HIP_CHECK(hipMemcpyAsync(x_out, s_xa, n * sizeof(float), hipMemcpyDeviceToDevice, loop_stream));
-            MKD_HIP_CHECK(hipEventRecord(ev_loop_out, loop_stream));
-            MKD_HIP_CHECK(hipStreamWaitEvent(stream, ev_loop_out, 0));
+        if (r.use_graph && r.n_steps > MKD_MAX_STEPS) return mkd_fail(MKD_ERR_ARG, "mkd_sample: too many steps for the graph path");
+        return 0;
+    }
+
+    // the host copy of the step state that the captured step reads: per-step tables, the noise, the mask, the DPM-Solver++ ring
+    void fill_step_state(const SampleReq& r, bool stochastic) {
+        const int n_steps = r.n_steps, hw = h * w;
+        const mkd_sample_mask* qm = r.qm;
+        h_state->counter = n_steps - 1;
+        for (int i = 0; i < n_steps; ++i) {
+            h_state->timesteps[i] = r.timesteps[i];
+            h_state->coef[4 * i + 0] = 1.0f / sqrtf(r.alphas[i]);
+            h_state->coef[4 * i + 1] = sqrtf(r.alphas_prev[i]);
+            const float sg = stochastic ? r.sigmas[i] : 0.f;
+            h_state->coef[4 * i + 2] = sqrtf(1.0f - r.alphas_prev[i] - sg * sg);
+            h_state->coef[4 * i + 3] = r.s1m ? r.s1m[i] : 0.f;
+            h_state->sigma[i] = sg;
+            for (int j = 0; j < 6; ++j) h_state->dpm[6 * i + j] = r.dpm ? r.dpm[6 * i + j] : 0.f;
+        }
+        h_state->ring = r.dpm ? s_ring : nullptr;
+        for (int j = 0; j < 6; ++j) h_state->cur_dpm[j] = 0.f;
+        h_state->cur_slot[0] = h_state->cur_slot[1] = h_state->cur_slot[2] = 0;
+        h_state->noise = stochastic ? r.noise : nullptr; h_state->temperature = r.temperature; h_state->n_steps = n_steps;
+        h_state->cur_sigma = 0.f; h_state->cur_row = 0;
+        // masked sampling: read by step_setup_kernel; x0 null leaves the (shared) captured step unmasked
+        h_state->x0 = qm ? qm->x0 : nullptr; h_state->mask = qm ? qm->mask : nullptr; h_state->q_noise = qm ? qm->noise : nullptr;
+        h_state->q_hw = hw; h_state->q_chw = cfg.in_channels * hw;
+        h_state->mask_bstride = (qm && qm->mask_batch != 1) ? qm->mask_channels * hw : 0;
+        h_state->mask_cstride = (qm && qm->mask_channels != 1) ? hw : 0;
+        for (int i = 0; i < n_steps; ++i) {
+            h_state->q[2 * i] = qm ? qm->sqrt_alphas_cumprod[i] : 0.f;
+            h_state->q[2 * i + 1] = qm ? qm->sqrt_one_minus_alphas_cumprod[i] : 0.f;
+        }
+    }
+
+    // graph path, before the steps: order the loop against the caller's stream, upload the step state, run the table
+    int graph_prologue(const SampleReq& r, bool stochastic, hipStream_t stream) {
+        if (!h_state) MKD_HIP_CHECK(hipHostMalloc((void**)&h_state, sizeof(StepState)));
+        if (!s_state) MKD_HIP_CHECK(hipMalloc((void**)&s_state, sizeof(StepState)));
+        if (!loop_stream) {
+            // the caller's stream may be the legacy null stream, which cannot be captured: run the loop on a
+            // private stream ordered against the caller's with events
+            MKD_HIP_CHECK(hipStreamCreateWithFlags(&loop_stream, hipStreamNonBlocking));
+            MKD_HIP_CHECK(hipEventCreateWithFlags(&ev_loop_in, hipEventDisableTiming));
+            MKD_HIP_CHECK(hipEventCreateWithFlags(&ev_loop_out, hipEventDisableTiming));
+        }
+        MKD_HIP_CHECK(hipStreamSynchronize(loop_stream));     // h_state may still feed a previous call's copy
+        fill_step_state(r, stochastic);
+        MKD_HIP_CHECK(hipEventRecord(ev_loop_in, stream));
+        MKD_HIP_CHECK(hipStreamWaitEvent(loop_stream, ev_loop_in, 0));
+        MKD_HIP_CHECK(hipMemcpyAsync(s_state, h_state, sizeof(StepState), hipMemcpyHostToDevice, loop_stream));
+        return run_temb_table(r.n_steps, r.timesteps, loop_stream);
+    }
+
+    // the n_steps steps on loop_stream.  Graph mode 1: one captured step (both streams, fork/join included), replayed; mode 2: its linear graphs
+    int replay_steps(int n_steps, const StepKey& key) {
+        if (graph_mode == 2 && dual_stream) {
+            run_main = loop_stream; run_serial = false;
+            if (segs.empty() || !(seg_key == key)) { int rc = build_segments(key); if (rc) return rc; }
+            for (int i = 0; i < n_steps; ++i) { int rc = run_segments(); if (rc) return rc; }
             return 0;
         }
-        if (temb_table) {
-            int rc = run_temb_table(n_steps, timesteps, stream); if (rc) return rc;
-            temb_skip = true;
+        if (!step_graph || !(step_key == key)) {
+            drop_graph();
+            int rc = capture(loop_stream, [&](hipStream_t st) { return enqueue_state_steps(key, 1, st); }, &step_graph, ""); if (rc) return rc;
+            step_key = key;
         }
+        // (multi_graph needs no key of its own: whenever step_graph's key above changes, drop_graph() destroys both)
+        // MKD_GRAPH_STEPS = k > 1: k consecutive steps captured as ONE graph (the step reads its index from the device-resident
+        // counter, so the same capture repeated k times is k different steps); the remainder runs on the single-step graph
+        // (default 5: a graph boundary costs ~30 us; batch 8: 5.85 -> 5.82 ms per evaluation, batch 1: 2.99 -> 2.97)
+        int done = 0;
+        if (graph_steps > 1 && n_steps >= graph_steps) {
+            if (!multi_graph || multi_graph_steps != graph_steps) {
+                if (multi_graph) { hipGraphExecDestroy(multi_graph); multi_graph = nullptr; }
+                int rc = capture(loop_stream, [&](hipStream_t st) { return enqueue_state_steps(key, graph_steps, st); }, &multi_graph, ""); if (rc) return rc;
+                multi_graph_steps = graph_steps;
+            }
+            for (; done + graph_steps <= n_steps; done += graph_steps) MKD_HIP_CHECK(hipGraphLaunch(multi_graph, loop_stream));
+        }
+        for (int i = done; i < n_steps; ++i) MKD_HIP_CHECK(hipGraphLaunch(step_graph, loop_stream));
+        return 0;
+    }
+
+    // eager launches on the caller's stream, coefficients from the host tables
+    int sample_eager(const SampleReq& r, const StepKey& key, bool stochastic, hipStream_t stream) {
+        const int n_steps = r.n_steps, hw = h * w;
+        const int64_t n = latent_n(r.batch);
+        const mkd_sample_mask* qm = r.qm;
+        int rc = run_temb_table(n_steps, r.timesteps, stream); if (rc) return rc;
         float* xa = s_xa; float* xb = s_xb;
         for (int i = 0; i < n_steps; ++i) {
             const int index = n_steps - 1 - i;
-            int rc = launch_fill_i64(s_t, timesteps[index], B, stream); if (rc) return rc;
+            rc = launch_fill_i64(s_t, r.timesteps[index], B, stream); if (rc) return rc;
             if (qm) {           // (the eager loop's one extra launch per step: the graph folds this blend into its step setup)
                 rc = launch_q_sample_blend(qm->x0, qm->noise + (int64_t)i * n, qm->sqrt_alphas_cumprod[index], qm->sqrt_one_minus_alphas_cumprod[index],
-                                           qm->mask, qm->mask_batch, qm->mask_channels, xa, xa, batch, cfg.in_channels, hw, stream);
+                                           qm->mask, qm->mask_batch, qm->mask_channels, xa, xa, r.batch, cfg.in_channels, hw, stream);
                 if (rc) return rc;
             }
             if (temb_skip) { rc = launch_temb_select(temb_sel(), index, stream); if (rc) return rc; }
-            const float* ec; const float* eu = nullptr;
-            if (cfg_on) {
-                rc = launch_repeat_batch(xa, s_xin, n, 2, stream); if (rc) return rc;
-                rc = eps(s_xin, s_t, s_eps, stream); if (rc) return rc;
-                eu = s_eps; ec = s_eps + n;
-            } else {
-                rc = eps(xa, s_t, s_eps, stream); if (rc) return rc;
-                ec = s_eps;
-            }
-            if (dpm_on) {           // m_k into ring slot k mod 3; m_{k-1}, m_{k-2} from the other two (k = i, the executed step)
-                const float* d = dpm + 6 * index;
+            const StepIo io = step_io(key.cfg != 0, xa, n);
+            if (key.cfg) { rc = launch_repeat_batch(xa, s_xin, n, 2, stream); if (rc) return rc; }
+            rc = eps(io.x, s_t, s_eps, stream); if (rc) return rc;
+            if (key.solver) {           // m_k into ring slot k mod 3; m_{k-1}, m_{k-2} from the other two (k = i, the executed step)
+                const float* d = r.dpm + 6 * index;
                 const DpmCoef kc = {d[0], d[1], d[2], d[3], d[4], d[5]};
-                rc = launch_dpmpp_step(xa, ec, eu, cfg_scale, kc, s_ring + (int64_t)((i + 2) % 3) * n, s_ring + (int64_t)((i + 1) % 3) * n, xb,
+                rc = launch_dpmpp_step(xa, io.ec, io.eu, key.scale, kc, s_ring + (int64_t)((i + 2) % 3) * n, s_ring + (int64_t)((i + 1) % 3) * n, xb,
                                        s_ring + (int64_t)(i % 3) * n, n, stream);
-                if (rc) return rc;
-                float* tmp = xa; xa = xb; xb = tmp;
-                continue;
+            } else {
+                const float sg = stochastic ? r.sigmas[index] : 0.f;
+                rc = launch_ddim_step(xa, io.ec, io.eu, key.scale, r.alphas[index], r.alphas_prev[index], sg, r.s1m[index],
+                                      sg != 0.f ? r.noise + (int64_t)i * n : nullptr, r.temperature, xb, nullptr, n, stream);
             }
-            const float sg = stochastic ? sigmas[index] : 0.f;
-            rc = launch_ddim_step(xa, ec, eu, cfg_scale, alphas[index], alphas_prev[index], sg, s1m[index], sg != 0.f ? noise + (int64_t)i * n : nullptr,
-                                  temperature, xb, nullptr, n, stream);
             if (rc) return rc;
             float* tmp = xa; xa = xb; xb = tmp;
         }
-        MKD_HIP_CHECK(hipMemcpyAsync(x_out, xa, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        MKD_HIP_CHECK(hipMemcpyAsync(r.x_out, xa, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        return 0;
+    }
+
+    // The whole reverse loop.  DPM-Solver++ is deterministic (sigmas / noise / s1m unused); setup, evaluation and the masked blend are
+    // shared with DDIM, only the step's last kernel differs.
+    int sample(const SampleReq& r, hipStream_t stream) {
+        struct Clear { bool& flag; ~Clear() { flag = false; } } clear_temb_skip{temb_skip};      // on every exit: a later mkd_eps runs its own time-embedding chain
+        bool stochastic = false;
+        int rc = validate(r, &stochastic); if (rc) return rc;
+        StepKey key; key.gen = plan_generation; key.cfg = r.cfg_scale != 1.0f; key.scale = r.cfg_scale; key.batch = r.batch; key.solver = r.dpm != nullptr;
+        key.temb = temb_table;          // (the steps take the time embedding from the table exactly when the table is on)
+        const int64_t n = latent_n(r.batch);
+        if (key.solver) { rc = ensure_ring(n); if (rc) return rc; }
+        MKD_HIP_CHECK(hipMemcpyAsync(s_xa, r.x_T, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        if (!r.use_graph) return sample_eager(r, key, stochastic, stream);
+        rc = graph_prologue(r, stochastic, stream); if (rc) return rc;
+        rc = replay_steps(r.n_steps, key); if (rc) return rc;
+        MKD_HIP_CHECK(hipMemcpyAsync(r.x_out, s_xa, n * sizeof(float), hipMemcpyDeviceToDevice, loop_stream));      // the result; the caller's stream waits for the loop
+        MKD_HIP_CHECK(hipEventRecord(ev_loop_out, loop_stream));
+        MKD_HIP_CHECK(hipStreamWaitEvent(stream, ev_loop_out, 0));
         return 0;
     }
 
@@ -2748,22 +2747,25 @@ int mkd_sample(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int
                const float* alphas_prev, const float* sqrt_one_minus_alphas, float cfg_scale, float* x_out, int use_graph,
                void* stream) {
     if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
-    return ctx->sample(x_T, batch, n_steps, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas, cfg_scale, x_out, use_graph,
-                       (hipStream_t)stream);
+    SampleReq r{x_T, batch, n_steps, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas};
+    r.cfg_scale = cfg_scale; r.x_out = x_out; r.use_graph = use_graph;
+    return ctx->sample(r, (hipStream_t)stream);
 }
 int mkd_sample_eta(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
                    const float* alphas_prev, const float* sqrt_one_minus_alphas, const float* sigmas, const float* noise, float temperature,
                    float cfg_scale, float* x_out, int use_graph, void* stream) {
     if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
-    return ctx->sample(x_T, batch, n_steps, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas, cfg_scale, x_out, use_graph,
-                       (hipStream_t)stream, sigmas, noise, temperature);
+    SampleReq r{x_T, batch, n_steps, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas};
+    r.sigmas = sigmas; r.noise = noise; r.temperature = temperature; r.cfg_scale = cfg_scale; r.x_out = x_out; r.use_graph = use_graph;
+    return ctx->sample(r, (hipStream_t)stream);
 }
 int mkd_sample_masked(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
                       const float* alphas_prev, const float* sqrt_one_minus_alphas, const float* sigmas, const float* noise, float temperature,
                       const mkd_sample_mask* m, float cfg_scale, float* x_out, int use_graph, void* stream) {
     if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
-    return ctx->sample(x_T, batch, n_steps, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas, cfg_scale, x_out, use_graph,
-                       (hipStream_t)stream, sigmas, noise, temperature, m);
+    SampleReq r{x_T, batch, n_steps, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas};
+    r.sigmas = sigmas; r.noise = noise; r.temperature = temperature; r.qm = m; r.cfg_scale = cfg_scale; r.x_out = x_out; r.use_graph = use_graph;
+    return ctx->sample(r, (hipStream_t)stream);
 }
 // Schedule-only coefficients of the multistep DPM-Solver++ (data prediction), in double; host only.  With alpha = sqrt(a),
 // sigma = sqrt(1 - a), lambda = log(alpha / sigma) and h = lambda(a_prev) - lambda(a_t) of table entry i, executed step k = n_steps - 1 - i:
@@ -2826,8 +2828,9 @@ int mkd_sample_dpmpp(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, con
     std::vector<float> tab((size_t)n_steps * 6);
     const int rc = mkd_dpmpp_table(n_steps, alphas, alphas_prev, order, lower_order_final, tab.data(), nullptr);
     if (rc) return rc;
-    return ctx->sample(x_T, batch, n_steps, timesteps, alphas, alphas_prev, nullptr, cfg_scale, x_out, use_graph, (hipStream_t)stream,
-                       nullptr, nullptr, 1.0f, m, tab.data());
+    SampleReq r{x_T, batch, n_steps, timesteps, alphas, alphas_prev};
+    r.qm = m; r.dpm = tab.data(); r.cfg_scale = cfg_scale; r.x_out = x_out; r.use_graph = use_graph;
+    return ctx->sample(r, (hipStream_t)stream);
 }
 int mkd_q_sample_blend(const float* x0, const float* noise, float sqrt_ac, float sqrt_one_minus_ac, const float* mask, int mask_batch,
                        int mask_channels, const float* x, float* out, int batch, int channels, int hw, void* stream) {
@@ -2959,7 +2962,7 @@ int mkd_clip_encode(mkd_ctx* ctx, const int32_t* tokens, int batch, int n_tokens
 }
 double mkd_eps_flops(const mkd_ctx* ctx) { return ctx ? ctx->flops_eps : 0.0; }
 int mkd_eps_launches(const mkd_ctx* ctx) { return ctx ? ctx->launches_eps : 0; }
-// what sample_impl / build_segments enqueue per step: the evaluation (without its own time-embedding chain when the per-call table
+// what the step of sample() (state_step / build_segments, the eager loop) enqueues: the evaluation (without its own time-embedding chain when the per-call table
 // is on) + graph replay: step setup (timestep, coefficients, table rows) and the state update; eager: timestep fill, table-row
 // select (table on) and the update; + the batch doubling of x with guidance
 int mkd_step_launches_ex(const mkd_ctx* ctx, int use_graph, int cfg_on) {

@@ -274,15 +274,19 @@ class BaseMakeUpDiffuse:
     # hipGraph replay of the sampling loop (one captured step, five steps per graph): the configuration bench.py measures.  False: eager
     sample_use_graph = True
 
+    def _bind_guided(self, cond, uncond, scale, latent_hw):
+        """(engine bound to cond, or to [uncond; cond] when guidance is on; the cfg_scale to run it with)"""
+        cfg_on = not (uncond is None or scale == 1.0)
+        c = self.cfg_conditioning(uncond, cond) if cfg_on else cond
+        return self._bind_cond(c, latent_hw), float(scale) if cfg_on else 1.0
+
     def sample_loop_fast(self, x_latent, cond, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas,
                          unconditional_guidance_scale=1.0, unconditional_conditioning=None, sigmas=None, noise=None, temperature=1.0,
                          x0=None, mask=None, q_sqrt_ac=None, q_sqrt_1m_ac=None, q_noise=None):
-        cfg_on = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
-        c = self.cfg_conditioning(unconditional_conditioning, cond) if cfg_on else cond
-        eng = self._bind_cond(c, x_latent.shape[2:])
+        eng, cfg_scale = self._bind_guided(cond, unconditional_conditioning, unconditional_guidance_scale, x_latent.shape[2:])
         return eng.sample(x_latent, [int(v) for v in timesteps], [float(v) for v in alphas], [float(v) for v in alphas_prev],
                           [float(v) for v in sqrt_one_minus_alphas],
-                          cfg_scale=float(unconditional_guidance_scale) if cfg_on else 1.0, use_graph=bool(self.sample_use_graph),
+                          cfg_scale=cfg_scale, use_graph=bool(self.sample_use_graph),
                           sigmas=None if sigmas is None else [float(v) for v in sigmas], noise=noise, temperature=float(temperature),
                           x0=x0, mask=mask, q_sqrt_ac=q_sqrt_ac, q_sqrt_1m_ac=q_sqrt_1m_ac, q_noise=q_noise)
 
@@ -295,12 +299,10 @@ class BaseMakeUpDiffuse:
                           unconditional_guidance_scale=1.0, unconditional_conditioning=None, x0=None, mask=None, q_sqrt_ac=None,
                           q_sqrt_1m_ac=None, q_noise=None):
         """the whole DPM-Solver++ multistep loop inside libmkd (mkd_sample_dpmpp), on the tables sample_loop_fast takes"""
-        cfg_on = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
-        c = self.cfg_conditioning(unconditional_conditioning, cond) if cfg_on else cond
-        eng = self._bind_cond(c, x_latent.shape[2:])
+        eng, cfg_scale = self._bind_guided(cond, unconditional_conditioning, unconditional_guidance_scale, x_latent.shape[2:])
         return eng.sample_dpmpp(x_latent, [int(v) for v in timesteps], [float(v) for v in alphas], [float(v) for v in alphas_prev],
                                 order=int(order), lower_order_final=bool(lower_order_final),
-                                cfg_scale=float(unconditional_guidance_scale) if cfg_on else 1.0, use_graph=bool(self.sample_use_graph),
+                                cfg_scale=cfg_scale, use_graph=bool(self.sample_use_graph),
                                 x0=x0, mask=mask, q_sqrt_ac=q_sqrt_ac, q_sqrt_1m_ac=q_sqrt_1m_ac, q_noise=q_noise)
 
     def latent_mask_from_labels(self, seg: torch.Tensor, classes: Sequence[int] = (0, 11, 12), factor: int = 8,

@@ -451,26 +451,10 @@ class MkdEngine:
         ``sigmas`` like the other tables and ``noise`` [n_steps, B, 4, h, w], row k = the draw of the k-th executed step.
         Masked sampling (include/mkd.h mkd_sample_masked): ``x0`` [B,4,h,w], ``mask`` [1|B, 1|4, h, w] (1 keeps x0), the DDPM
         tables at each entry's timestep ``q_sqrt_ac`` / ``q_sqrt_1m_ac`` (indexed like ``alphas``) and ``q_noise`` [n_steps, B, 4, h, w]."""
-        x_T = _f32c(x_T, self.device)
-        cfg_on = float(cfg_scale) != 1.0
-        want_b = self.batch // 2 if cfg_on else self.batch
-        if (x_T.dim() != 4 or tuple(x_T.shape[1:]) != (self.cfg.in_channels, *self.latent_hw) or x_T.shape[0] != want_b
-                or (cfg_on and self.batch % 2)):
-            # libmkd copies batch * C * h * w floats using the PREPARED h, w: a smaller latent would be read out of bounds
-            raise ValueError(f'x_T {tuple(x_T.shape)} does not match the prepared conditioning: expected '
-                             f'({want_b}, {self.cfg.in_channels}, {self.latent_hw[0]}, {self.latent_hw[1]})'
-                             + (' (CFG: prepared batch is [uncond; cond])' if cfg_on else ''))
-        n = len(timesteps)
-        if n <= 0 or not (len(alphas) == len(alphas_prev) == len(sqrt_one_minus_alphas) == n):
-            raise ValueError('timesteps / alphas / alphas_prev / sqrt_one_minus_alphas must be non-empty and equally long')
-        ts = (C.c_int64 * n)(*[int(v) for v in timesteps])
-        a = (C.c_float * n)(*[float(v) for v in alphas])
-        ap = (C.c_float * n)(*[float(v) for v in alphas_prev])
-        s1 = (C.c_float * n)(*[float(v) for v in sqrt_one_minus_alphas])
+        x_T = self._check_x_T(x_T, cfg_scale)
+        n, ts, (a, ap, s1) = self._sample_tables(timesteps, alphas=alphas, alphas_prev=alphas_prev, sqrt_one_minus_alphas=sqrt_one_minus_alphas)
         out = torch.empty_like(x_T)
-        qm = None
-        if mask is not None or x0 is not None:
-            qm, keep = self._sample_mask(x_T, n, x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise)
+        qm, keep = self._sample_mask(x_T, n, x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise)
         sg = None
         if sigmas is not None and any(float(v) != 0.0 for v in sigmas):
             if len(sigmas) != n:
@@ -482,23 +466,17 @@ class MkdEngine:
         else:
             noise = None
         with torch.cuda.device(self.device):
+            head = (self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, s1)
+            tail = (float(cfg_scale), C.c_void_p(out.data_ptr()), int(use_graph), C.c_void_p(_stream()))
             if qm is not None:
-                _lib.check(self.lib.mkd_sample_masked(self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, s1, sg,
-                                                      C.c_void_p(_ptr(noise)), float(temperature), C.byref(qm), float(cfg_scale),
-                                                      C.c_void_p(out.data_ptr()), int(use_graph), C.c_void_p(_stream())), 'mkd_sample_masked')
-                # no host wait: the caller's stream waits for the replayed loop, so the caching allocator can only hand these blocks to
-                # work ordered after it; they are also held until the next masked call
-                self._loop_keep = (keep, noise)
+                _lib.check(self.lib.mkd_sample_masked(*head, sg, C.c_void_p(_ptr(noise)), float(temperature), C.byref(qm), *tail), 'mkd_sample_masked')
+                self._hold(keep, noise)
             elif sg is not None:
-                _lib.check(self.lib.mkd_sample_eta(self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, s1, sg,
-                                                   C.c_void_p(noise.data_ptr()), float(temperature), float(cfg_scale),
-                                                   C.c_void_p(out.data_ptr()), int(use_graph), C.c_void_p(_stream())), 'mkd_sample_eta')
+                _lib.check(self.lib.mkd_sample_eta(*head, sg, C.c_void_p(noise.data_ptr()), float(temperature), *tail), 'mkd_sample_eta')
                 if use_graph:
                     torch.cuda.synchronize(self.device)          # the replayed loop reads `noise` after this call returns: keep it alive
             else:
-                _lib.check(self.lib.mkd_sample(self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, s1,
-                                               float(cfg_scale), C.c_void_p(out.data_ptr()), int(use_graph),
-                                               C.c_void_p(_stream())), 'mkd_sample')
+                _lib.check(self.lib.mkd_sample(*head, *tail), 'mkd_sample')
         return out
 
     def dpmpp_step(self, x, eps_c, eps_u, cfg_scale, coef6, m1=None, m2=None):
@@ -531,31 +509,43 @@ class MkdEngine:
                      q_sqrt_1m_ac: Optional[Sequence[float]] = None, q_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The whole DPM-Solver++ multistep loop in one call (mkd_sample_dpmpp): ``sample``'s contract on the same DDIM tables
         (prepared batch B or 2B with guidance, masked sampling through x0 / mask / q_*), deterministic."""
+        x_T = self._check_x_T(x_T, cfg_scale)
+        n, ts, (a, ap) = self._sample_tables(timesteps, alphas=alphas, alphas_prev=alphas_prev)
+        out = torch.empty_like(x_T)
+        qm, keep = self._sample_mask(x_T, n, x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mkd_sample_dpmpp(self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, int(order),
+                                                 int(bool(lower_order_final)), None if qm is None else C.byref(qm), float(cfg_scale),
+                                                 C.c_void_p(out.data_ptr()), int(use_graph), C.c_void_p(_stream())), 'mkd_sample_dpmpp')
+        self._hold(keep, None)
+        return out
+
+    def _check_x_T(self, x_T: torch.Tensor, cfg_scale: float) -> torch.Tensor:
+        """x_T as the fp32 device tensor, checked against the prepared conditioning (batch B, or 2B = [uncond; cond] with guidance)."""
         x_T = _f32c(x_T, self.device)
         cfg_on = float(cfg_scale) != 1.0
         want_b = self.batch // 2 if cfg_on else self.batch
         if (x_T.dim() != 4 or tuple(x_T.shape[1:]) != (self.cfg.in_channels, *self.latent_hw) or x_T.shape[0] != want_b
                 or (cfg_on and self.batch % 2)):
+            # libmkd copies batch * C * h * w floats using the PREPARED h, w: a smaller latent would be read out of bounds
             raise ValueError(f'x_T {tuple(x_T.shape)} does not match the prepared conditioning: expected '
                              f'({want_b}, {self.cfg.in_channels}, {self.latent_hw[0]}, {self.latent_hw[1]})'
                              + (' (CFG: prepared batch is [uncond; cond])' if cfg_on else ''))
+        return x_T
+
+    @staticmethod
+    def _sample_tables(timesteps, **tables):
+        """(n, timesteps as c_int64[n], the named per-step tables as c_float[n] each); all must be non-empty and equally long."""
         n = len(timesteps)
-        if n <= 0 or not (len(alphas) == len(alphas_prev) == n):
-            raise ValueError('timesteps / alphas / alphas_prev must be non-empty and equally long')
-        ts = (C.c_int64 * n)(*[int(v) for v in timesteps])
-        a = (C.c_float * n)(*[float(v) for v in alphas])
-        ap = (C.c_float * n)(*[float(v) for v in alphas_prev])
-        out = torch.empty_like(x_T)
-        qm = keep = None
-        if mask is not None or x0 is not None:
-            qm, keep = self._sample_mask(x_T, n, x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.mkd_sample_dpmpp(self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, int(order),
-                                                 int(bool(lower_order_final)), None if qm is None else C.byref(qm), float(cfg_scale),
-                                                 C.c_void_p(out.data_ptr()), int(use_graph), C.c_void_p(_stream())), 'mkd_sample_dpmpp')
+        if n <= 0 or any(len(v) != n for v in tables.values()):
+            raise ValueError(f'{" / ".join(["timesteps", *tables])} must be non-empty and equally long')
+        return n, (C.c_int64 * n)(*[int(v) for v in timesteps]), [(C.c_float * n)(*[float(v) for v in t]) for t in tables.values()]
+
+    def _hold(self, keep, noise) -> None:
+        """A masked call's tensors / arrays stay referenced until the next masked call.  No host wait: the caller's stream waits for
+        the replayed loop, so the caching allocator can only hand these blocks to work ordered after it."""
         if keep is not None:
-            self._loop_keep = (keep, None)          # (as in sample(): held until the next masked call)
-        return out
+            self._loop_keep = (keep, noise)
 
     def _mask_geometry(self, mask: torch.Tensor, B: int, Cn: int, hw) -> Tuple[int, int]:
         if mask.dim() != 4 or tuple(mask.shape[2:]) != tuple(hw) or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, Cn):
@@ -563,7 +553,9 @@ class MkdEngine:
         return int(mask.shape[0]), int(mask.shape[1])
 
     def _sample_mask(self, x_T, n, x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise):
-        """Validated mkd_sample_mask for sample(); returns it with the tensors / arrays it points at."""
+        """Validated mkd_sample_mask for sample(); returns it with the tensors / arrays it points at ((None, None): no masking)."""
+        if x0 is None and mask is None:
+            return None, None
         if x0 is None or mask is None:
             raise ValueError('masked sampling needs both mask and x0')
         x0 = _f32c(x0, self.device)
