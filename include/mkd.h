@@ -377,8 +377,11 @@ int mkd_gemm_ln_bf16(const uint16_t* A, int lda, const uint16_t* Wfold, int ldw,
 int mkd_gemm_rowstats_bf16(const uint16_t* A, int lda, const uint16_t* W, int ldw, const float* bias, const uint16_t* R, int ldr,
                            uint16_t* C, int ldc, int M, int N, int K, float* stat_out, int stat_capacity_slots, int* slots_out,
                            void* stream);
-/* Tuner / tests only: force the GEMM tile configuration (index into the table in kernels_gemm.hip; -1 = heuristic). */
+/* Tuner / tests only: force the GEMM tile configuration (row index of makeupdiffuse_amd/csrc/gemm_tiles.inc; -1 = heuristic). */
 int mkd_gemm_force_tile(int cfg);
+/* Row `cfg` of the tile-configuration table: block tile (rows x columns), 1 when it is an LDS-staged 3x3 conv tile, its name (static
+ * storage).  Returns the number of configurations; fills the outputs (each may be null) only when 0 <= cfg < that.  Needs no device. */
+int mkd_gemm_tile_info(int cfg, int* tile_m, int* tile_n, int* lds_staged_conv, const char** name);
 /* Tests / experiments: workgroup -> tile order of the GEMM and LDS-staged conv kernels with respect to the 8 XCDs (each has its own
  * L2; workgroups are dealt to them round-robin in launch order).  0 (default): launch order; 1: every XCD gets one contiguous run
  * of the tile sequence with M-tiles fastest (a weight tile lives in one L2); 2: the same with N-tiles fastest.  Results do not

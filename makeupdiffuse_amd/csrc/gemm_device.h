@@ -30,6 +30,22 @@ inline GemmArgs2 gemm_pack2(const GemmArgs& a, const GemmArgs* b, int gz) {
     return r;
 }
 
+// host side: the ONE place that raises a kernel's dynamic-LDS limit (once per kernel instantiation: the flag belongs to the kernel, not
+// to the launcher that reached it) and launches it.  The limit is raised when the launch needs more than the 64 KiB every kernel may
+// use anyway, or `always`; `what` prefixes the error text.
+template <auto Kernel>
+int launch_lds_kernel(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const GemmArgs2& ag, bool always = false,
+                      const char* what = "hipFuncSetAttribute(max dynamic LDS): ") {
+    static bool attr_set = false;
+    if ((always || lds > 64 * 1024) && !attr_set) {
+        const hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return mkd_fail(-2, std::string(what) + hipGetErrorString(e));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, stream, ag);
+    return 0;
+}
+
 constexpr int BK = 64;
 
 typedef __attribute__((address_space(3))) void lds_void;

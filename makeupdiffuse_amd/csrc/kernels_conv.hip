@@ -346,43 +346,38 @@ __global__ __launch_bounds__(64 * WM * WN) void conv3x3_patch_kernel(const GemmA
     }
 }
 
-template <int TM, int TN, int WM, int WN, int PP>
+template <int TM, int TN, int WM, int WN, int STAGES, int PP>
 int launch_patch(const GemmArgs& a, dim3 grid, hipStream_t stream, const GemmArgs* second) {
     const GemmArgs2 ag = gemm_pack2(a, second, (int)grid.z);
     if (second) grid.z *= 2;
-    constexpr int STAGES = 3;
     constexpr int NW = WM * WN;
     const bool gns = a.gn_stat != nullptr && a.splitk == 1;
     const size_t lds = (size_t)2 * PP * NW * 1024 + (size_t)conv_stages(TN, NW, PP, STAGES) * conv_tps(TN, NW, PP) * TN * 128 + (gns ? 4096 : 0);      // (+ GroupNorm statistics accumulator)
     if (lds > 160 * 1024) return mkd_fail(-4, "conv3x3_patch: LDS budget exceeded");
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[gns]) {
-        hipError_t e = gns ? hipFuncSetAttribute((const void*)conv3x3_patch_kernel<TM, TN, WM, WN, STAGES, PP, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                           : hipFuncSetAttribute((const void*)conv3x3_patch_kernel<TM, TN, WM, WN, STAGES, PP, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return mkd_fail(-2, std::string("hipFuncSetAttribute(conv patch LDS): ") + hipGetErrorString(e));
-        attr_set[gns] = true;
-    }
-    if (gns) hipLaunchKernelGGL((conv3x3_patch_kernel<TM, TN, WM, WN, STAGES, PP, 1>), grid, dim3(64 * NW), lds, stream, ag);
-    else     hipLaunchKernelGGL((conv3x3_patch_kernel<TM, TN, WM, WN, STAGES, PP, 0>), grid, dim3(64 * NW), lds, stream, ag);
-    return 0;
+    const char* const what = "hipFuncSetAttribute(conv patch LDS): ";          // (the limit is always raised: most of these tiles need it)
+    return gns ? launch_lds_kernel<conv3x3_patch_kernel<TM, TN, WM, WN, STAGES, PP, 1>>(grid, dim3(64 * NW), lds, stream, ag, true, what)
+               : launch_lds_kernel<conv3x3_patch_kernel<TM, TN, WM, WN, STAGES, PP, 0>>(grid, dim3(64 * NW), lds, stream, ag, true, what);
 }
 
-template <int TM, int TN, int WM, int WN>
+// rows of gemm_tiles.inc of another family never get here (conv_patch_supported)
+template <TileFamily FAM, int TM, int TN, int WM, int WN, int STAGES>
 int launch_patch_pp(const GemmArgs& a, int pp, dim3 grid, hipStream_t stream, const GemmArgs* second) {
-    if constexpr (WM * WN == 16) {                      // 16 waves: 2 or 3 pieces per wave hold a 256- / 128-pixel patch
-        if (pp <= 2) return launch_patch<TM, TN, WM, WN, 2>(a, grid, stream, second);
-        if (pp == 3) return launch_patch<TM, TN, WM, WN, 3>(a, grid, stream, second);
+    if constexpr (FAM != TILE_PATCH) {
+        return mkd_fail(-4, "conv3x3_patch: not an LDS-staged conv tile");
+    } else if constexpr (WM * WN == 16) {                      // 16 waves: 2 or 3 pieces per wave hold a 256- / 128-pixel patch
+        if (pp <= 2) return launch_patch<TM, TN, WM, WN, STAGES, 2>(a, grid, stream, second);
+        if (pp == 3) return launch_patch<TM, TN, WM, WN, STAGES, 3>(a, grid, stream, second);
         return mkd_fail(-4, "conv3x3_patch: patch too large for the 16-wave tile");
     } else {
         if constexpr (WM * WN == 8 && TM <= 128) {      // 8 waves on a 64- / 128-pixel tile: 2 or 3 pieces per wave hold the patch
-            if (pp <= 2) return launch_patch<TM, TN, WM, WN, 2>(a, grid, stream, second);
-            if (pp == 3) return launch_patch<TM, TN, WM, WN, 3>(a, grid, stream, second);
+            if (pp <= 2) return launch_patch<TM, TN, WM, WN, STAGES, 2>(a, grid, stream, second);
+            if (pp == 3) return launch_patch<TM, TN, WM, WN, STAGES, 3>(a, grid, stream, second);
         }
-        if (pp <= 4) return launch_patch<TM, TN, WM, WN, 4>(a, grid, stream, second);
-        if (pp == 5) return launch_patch<TM, TN, WM, WN, 5>(a, grid, stream, second);
-        if (pp == 6) return launch_patch<TM, TN, WM, WN, 6>(a, grid, stream, second);
-        if (pp == 7) return launch_patch<TM, TN, WM, WN, 7>(a, grid, stream, second);
-        if (pp <= 9) return launch_patch<TM, TN, WM, WN, 9>(a, grid, stream, second);
+        if (pp <= 4) return launch_patch<TM, TN, WM, WN, STAGES, 4>(a, grid, stream, second);
+        if (pp == 5) return launch_patch<TM, TN, WM, WN, STAGES, 5>(a, grid, stream, second);
+        if (pp == 6) return launch_patch<TM, TN, WM, WN, STAGES, 6>(a, grid, stream, second);
+        if (pp == 7) return launch_patch<TM, TN, WM, WN, STAGES, 7>(a, grid, stream, second);
+        if (pp <= 9) return launch_patch<TM, TN, WM, WN, STAGES, 9>(a, grid, stream, second);
         return mkd_fail(-4, "conv3x3_patch: patch too large");
     }
 }
@@ -410,38 +405,28 @@ bool conv_patch_geometry(int tm, int batch, int H, int W, int* th, int* tw, int*
     return true;
 }
 
-// cfg: 6: 256x128 (8 waves), 7: 256x64 (8 waves), 8: 128x128, 9: 128x64, 10: 64x128, 11: 64x64 (4 waves);
-// 38: 128x64, 39: 64x128, 40: 128x128 with EIGHT waves (32x32 / 32x32 / 32x64 per wave): a wave's LDS-DMA transfers complete one
-// after the other (~1 KiB per 200-300 cycles, tools/micro/stream_rate3.hip), and with four waves each tap asks 2.7 pieces of every
-// wave for 16 MFMAs - the tap waits for the transfers, not for the matrix cores; eight waves halve the pieces per wave
-static bool patch_cfg_shape(int cfg, int* tm, int* tn, int* nw) {
-    static const int tms[11] = {256, 256, 128, 128, 64, 64, 128, 64, 128, 256, 128};
-    static const int tns[11] = {128, 64, 128, 64, 128, 64, 64, 128, 128, 128, 128};
-    static const int nws[11] = {8, 8, 4, 4, 4, 4, 8, 8, 8, 16, 16};
-    int i;
-    if (cfg >= 6 && cfg <= 11) i = cfg - 6;
-    else if (cfg >= 38 && cfg <= 40) i = cfg - 38 + 6;
-    else if (cfg >= 42 && cfg <= 43) i = cfg - 42 + 9;          // 42: 256x128, 43: 128x128 with SIXTEEN waves (32x64 / 32x32 per wave)
-    else return false;
-    *tm = tms[i]; *tn = tns[i]; *nw = nws[i];
-    return true;
+// the row of an LDS-staged conv tile (gemm_tiles.inc), null for every other configuration
+static const TileCfg* patch_cfg(int cfg) {
+    const TileCfg* const t = gemm_tile_cfg(cfg);
+    return t && t->family == TILE_PATCH ? t : nullptr;
 }
 
 bool conv_patch_supported(const GemmArgs& a, int cfg) {
     if (!a.conv || a.stride != 1 || a.up != 0 || a.pad_tl != 1 || a.Cin % 64 || a.Hin != a.Hout || a.Win != a.Wout) return false;
-    int tm, tn, nw;
-    if (!patch_cfg_shape(cfg, &tm, &tn, &nw)) return false;
+    const TileCfg* const t = patch_cfg(cfg);
+    if (!t) return false;
+    const int tn = t->tn, nw = t->wm * t->wn;
     int th, tw, im, pp;
-    if (!conv_patch_geometry(tm, a.M / (a.Hin * a.Win), a.Hin, a.Win, &th, &tw, &im, &pp, nw)) return false;
-    const size_t lds = (size_t)2 * pp * nw * 1024 + (size_t)conv_stages(tn, nw, pp, 3) * conv_tps(tn, nw, pp) * tn * 128 + (a.gn_stat ? 4096 : 0);
+    if (!conv_patch_geometry(t->tm, a.M / (a.Hin * a.Win), a.Hin, a.Win, &th, &tw, &im, &pp, nw)) return false;
+    const size_t lds = (size_t)2 * pp * nw * 1024 + (size_t)conv_stages(tn, nw, pp, t->stages) * conv_tps(tn, nw, pp) * tn * 128 + (a.gn_stat ? 4096 : 0);
     return lds <= 160 * 1024;
 }
 
 int launch_conv_patch(GemmArgs a, int cfg, int splitk, hipStream_t stream, const GemmArgs* second) {
     if (!conv_patch_supported(a, cfg)) return mkd_fail(-4, "conv3x3_patch: unsupported shape for this tile");
     if (second && !gemm_same_geometry(a, *second)) return mkd_fail(-1, "conv3x3_patch: a grouped launch needs two problems of identical geometry");
-    int tm, tn, nw;
-    patch_cfg_shape(cfg, &tm, &tn, &nw);
+    const TileCfg* const t = patch_cfg(cfg);
+    const int tm = t->tm, tn = t->tn, nw = t->wm * t->wn;
     const int batch = a.M / (a.Hin * a.Win);
     int pp;
     conv_patch_geometry(tm, batch, a.Hin, a.Win, &a.tile_h, &a.tile_w, &a.tile_imgs, &pp, nw);
@@ -469,17 +454,11 @@ int launch_conv_patch(GemmArgs a, int cfg, int splitk, hipStream_t stream, const
     dim3 grid(groups * (a.Hin / a.tile_h) * (a.Win / a.tile_w), (a.N + tn - 1) / tn, s);
     int rc;
     switch (cfg) {
-        case 6: rc = launch_patch_pp<256, 128, 4, 2>(a, pp, grid, stream, sp); break;
-        case 7: rc = launch_patch_pp<256, 64, 4, 2>(a, pp, grid, stream, sp); break;
-        case 8: rc = launch_patch_pp<128, 128, 2, 2>(a, pp, grid, stream, sp); break;
-        case 9: rc = launch_patch_pp<128, 64, 2, 2>(a, pp, grid, stream, sp); break;
-        case 10: rc = launch_patch_pp<64, 128, 2, 2>(a, pp, grid, stream, sp); break;
-        case 38: rc = launch_patch_pp<128, 64, 4, 2>(a, pp, grid, stream, sp); break;
-        case 39: rc = launch_patch_pp<64, 128, 2, 4>(a, pp, grid, stream, sp); break;
-        case 40: rc = launch_patch_pp<128, 128, 4, 2>(a, pp, grid, stream, sp); break;
-        case 42: rc = launch_patch_pp<256, 128, 8, 2>(a, pp, grid, stream, sp); break;
-        case 43: rc = launch_patch_pp<128, 128, 4, 4>(a, pp, grid, stream, sp); break;
-        default: rc = launch_patch_pp<64, 64, 2, 2>(a, pp, grid, stream, sp); break;
+#define MKD_TILE(INDEX, NAME, FAMILY, TM, TN, WM, WN, STAGES, KW, BASE) \
+        case INDEX: rc = launch_patch_pp<TILE_##FAMILY, TM, TN, WM, WN, STAGES>(a, pp, grid, stream, sp); break;
+#include "gemm_tiles.inc"
+#undef MKD_TILE
+        default: return mkd_fail(-4, "conv3x3_patch: tile configuration " + std::to_string(cfg) + " is not in the table");
     }
     if (rc) return rc;
     MKD_LAUNCH_CHECK("conv3x3_patch_kernel");

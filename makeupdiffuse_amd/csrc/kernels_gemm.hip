@@ -506,7 +506,7 @@ __global__ __launch_bounds__(64 * WM * WN * KW) void gemm_kernel(const GemmArgs2
 // forms of this kernel that issued the loads as inline asm with hand-counted waits (a copy of a register whose load is still in
 // flight reads stale bits, and nothing tells the compiler that the load is pending: sporadic NaNs, tools/dbg_ra.py).
 // One s_barrier per K-step.  Epilogue as gemm_kernel's plain forms (bias, per-sample row bias, scale, residual, SiLU / quick-GELU /
-// GEGLU, fp32 output, split-K slabs); fused LayerNorm / statistics variants stay on gemm_kernel (kTileBase).
+// GEGLU, fp32 output, split-K slabs); fused LayerNorm / statistics variants stay on gemm_kernel (the row's base configuration).
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // (explicitly GLOBAL: a pointer that went through select_src's opaque integer select would otherwise be loaded with flat_load, which
@@ -863,58 +863,40 @@ __global__ __launch_bounds__(256) void splitk_epilogue_gn_kernel(const GemmArgs2
 
 }  // namespace
 
-// tile configurations: index -> (TM, TN, waves m x n, stages)
-//   0: 256x128 8 waves (4x2) 3 stages  144 KiB LDS   1 block/CU   85 FLOP per staged byte
-//   1: 128x128 4 waves (2x2) 3 stages   96 KiB        1 block/CU   64
-//   2: 128x128 4 waves (2x2) 2 stages   64 KiB        2 blocks/CU  64
-//   3: 128x64  4 waves (2x2) 3 stages   72 KiB        2 blocks/CU  43
-//   4: 64x128  4 waves (2x2) 3 stages   72 KiB        2 blocks/CU  43
-//   5: 64x64   4 waves (2x2) 4 stages   64 KiB        2 blocks/CU  32
-//   6..11: LDS-staged 3x3 conv tiles (kernels_conv.hip): 256x128, 256x64 (8 waves), 128x128, 128x64, 64x128, 64x64
-//   12: 64x64 6 stages (96 KiB), 13: 64x128 5 stages (120 KiB): short-K layers, (nearly) every K-step in flight at once
-//   14: 64x160 3 stages (86 KiB), 15: 128x160 3 stages (110 KiB), 16: 64x160 2 stages (57 KiB, 2 blocks/CU): every channel
-//       count of the nets is a multiple of 320, so 160-wide column tiles never run a partly empty tile (N = 320 -> 2 x 160
-//       instead of 3 x 128 with 17 % of the MFMA work wasted)
-//   17: 32x64, 18: 64x32, 19: 32x32 (4 stages): one CU streams at most ~55 GB/s (tools/micro/stream_rate.hip), so a GEMM with
-//       fewer blocks than CUs finishes sooner when each block pulls FEWER operand bytes ((TM + TN) * K * 2), not more
-//   20..29: in-block K split (KW groups of 4 waves, see gemm_kernel): 32x32 x2 / x4, 64x32 x2 / x4, 64x64 x2 / x4, 32x64 x2 / x4,
-//       128x64 x2, 64x128 x2
-//   30..37: more waves per CU pulling operands.  A 4-wave workgroup streams ~48 GB/s whatever its ring depth (2, 4 or 8 stages), a CU
-//       with 8 waves ~94 GB/s, with 16 waves ~122 GB/s (tools/micro/stream_rate2.hip): the limit is per WAVE.  So: the same tiles with
-//       2-stage rings (half the LDS -> twice the resident workgroups): 64x64, 128x64, 64x128, 64x32; and 8-wave workgroups:
-//       128x128 (2 stages), 128x64, 64x128 (3), 64x64 (4).  Plain epilogue only (anything else runs on the base configuration).
-//   38..40: LDS-staged 3x3 conv tiles with EIGHT waves (kernels_conv.hip): 128x64, 64x128, 128x128; 41: 256x64 with 8 waves (gather /
-//       linear, plain epilogue only); 42 / 43: LDS-staged 256x128 / 128x128 with SIXTEEN waves.  Inside the sampling loop the whole-loop tuner (tools/tune_wall.py) moves the heavy shapes onto the
-//       eight-wave tiles although they are not faster alone: half the LDS-DMA pieces per wave and K-step.
-//   44..49: register-A tiles (gemm_ra_kernel: activations straight into the MFMA's registers, only the weight tile through LDS):
-//       256x64 and 256x128 with 8 waves (32 rows each), 128x128 / 128x64 / 128x160 with 4 waves, 256x64 with 4 waves (64 rows each).
-//   50: 256x256 with SIXTEEN waves (64x64 each), 2 stages (128 KiB LDS): 128 FLOP per byte pulled out of L2, for the few GEMMs whose M and N
-//       both allow it (the K loops of the gather / linear kernel run at three quarters of the L2 -> CU rate: DESIGN.md 4.5); plain epilogue only.
-constexpr int N_TILE_CFG = 51;
-static const int kTileM[N_TILE_CFG] = {256, 128, 128, 128, 64, 64, 256, 256, 128, 128, 64, 64, 64, 64, 64, 128, 64, 32, 64, 32,
-                                       32, 32, 64, 64, 64, 64, 32, 32, 128, 64, 64, 128, 64, 64, 128, 128, 64, 64, 128, 64, 128, 256, 256, 128,
-                                       256, 256, 128, 128, 128, 256, 256};
-static const int kTileN[N_TILE_CFG] = {128, 128, 128, 64, 128, 64, 128, 64, 128, 64, 128, 64, 64, 128, 160, 160, 160, 64, 32, 32,
-                                       32, 32, 32, 32, 64, 64, 64, 64, 64, 128, 64, 64, 128, 32, 128, 64, 128, 64, 64, 128, 128, 64, 128, 128,
-                                       64, 128, 128, 64, 160, 64, 256};
-static const int kTileKW[N_TILE_CFG] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 4, 2, 4, 2, 4, 2, 4, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1,
-                                        1, 1, 1, 1, 1, 1, 1};
-static const int kTileLight[N_TILE_CFG] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 1, 0, 0,
-                                           1, 1, 1, 1, 1, 1, 1};
-static const int kTileBase[N_TILE_CFG] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 19, 19, 18, 18, 5, 5, 17, 17, 3, 4,
-                                          5, 3, 4, 18, 2, 3, 4, 5, 38, 39, 40, 3, 42, 43,
-                                          3, 1, 1, 3, 14, 3, 0};
-static const char* const kTileName[N_TILE_CFG] = {"256x128", "128x128_s3", "128x128_s2", "128x64", "64x128", "64x64",
-                                                  "patch256x128", "patch256x64", "patch128x128", "patch128x64",
-                                                  "patch64x128", "patch64x64", "64x64_s6", "64x128_s5", "64x160", "128x160", "64x160_s2", "32x64", "64x32", "32x32",
-                                                  "32x32_k2", "32x32_k4", "64x32_k2", "64x32_k4", "64x64_k2", "64x64_k4", "32x64_k2", "32x64_k4", "128x64_k2", "64x128_k2",
-                                                  "64x64_s2", "128x64_s2", "64x128_s2", "64x32_s2", "128x128_w8", "128x64_w8", "64x128_w8", "64x64_w8",
-                                                  "patch128x64_w8", "patch64x128_w8", "patch128x128_w8", "256x64_w8", "patch256x128_w16", "patch128x128_w16",
-                                                  "ra256x64_w8", "ra256x128_w8", "ra128x128", "ra128x64", "ra128x160", "ra256x64", "256x256_w16"};
-static bool is_patch_cfg(int c) { return (c >= 6 && c <= 11) || (c >= 38 && c <= 40) || c == 42 || c == 43; }
-bool gemm_cfg_folds_second_input(int c) { return c >= 0 && c < N_TILE_CFG && !is_patch_cfg(c) && !(c >= 44 && c <= 49); }      // gemm_kernel (GemmArgs::A2)
+// the tile configurations: one row of gemm_tiles.inc each (the measured rationale of every row is there)
+static constexpr TileCfg kTiles[] = {
+#define MKD_TILE(INDEX, NAME, FAMILY, TM, TN, WM, WN, STAGES, KW, BASE) {INDEX, #NAME, TILE_##FAMILY, TM, TN, WM, WN, STAGES, KW, BASE},
+#include "gemm_tiles.inc"
+#undef MKD_TILE
+};
+constexpr int N_TILE_CFG = sizeof(kTiles) / sizeof(kTiles[0]);
+enum : int {
+#define MKD_TILE(INDEX, NAME, ...) CFG_##NAME = INDEX,
+#include "gemm_tiles.inc"
+#undef MKD_TILE
+};
+constexpr bool tile_is_full(int c) { return kTiles[c].family == TILE_GEMM || kTiles[c].family == TILE_PATCH; }      // every epilogue variant
+constexpr bool tile_table_ok() {
+    for (int i = 0; i < N_TILE_CFG; ++i)
+        if (kTiles[i].index != i || kTiles[i].base < 0 || kTiles[i].base >= N_TILE_CFG || !tile_is_full(kTiles[i].base)) return false;
+    return true;
+}
+static_assert(N_TILE_CFG == 51 && tile_table_ok(), "gemm_tiles.inc: row i must carry index i, fall back to a full-epilogue row, and rows are only ever appended (update this count)");
+
+const TileCfg* gemm_tile_cfg(int c) { return (c >= 0 && c < N_TILE_CFG) ? &kTiles[c] : nullptr; }
+static bool is_patch_cfg(int c) { const TileCfg* t = gemm_tile_cfg(c); return t && t->family == TILE_PATCH; }
+bool gemm_cfg_folds_second_input(int c) { const TileCfg* t = gemm_tile_cfg(c); return t && t->family != TILE_PATCH && t->family != TILE_RA; }      // gemm_kernel (GemmArgs::A2)
 int gemm_num_tile_cfgs() { return N_TILE_CFG; }
-const char* gemm_tile_cfg_name(int cfg) { return (cfg >= 0 && cfg < N_TILE_CFG) ? kTileName[cfg] : "?"; }
+const char* gemm_tile_cfg_name(int cfg) { const TileCfg* t = gemm_tile_cfg(cfg); return t ? t->name : "?"; }
+int gemm_tile_info(int cfg, int* tile_m, int* tile_n, int* lds_staged_conv, const char** name) {
+    if (const TileCfg* t = gemm_tile_cfg(cfg)) {
+        if (tile_m) *tile_m = t->tm;
+        if (tile_n) *tile_n = t->tn;
+        if (lds_staged_conv) *lds_staged_conv = t->family == TILE_PATCH;
+        if (name) *name = t->name;
+    }
+    return N_TILE_CFG;
+}
 
 struct GemmPlan { int cfg, splitk, per; };
 
@@ -941,7 +923,7 @@ void gemm_set_override(int M, int N, int K, int conv, int stride, int up, int cf
     ++g_plan_epoch;
     if (M <= 0) { g_override.clear(); return; }
     const ShapeKey k{M, N, K, conv, stride, up};
-    if (cfg < 0 || cfg >= N_TILE_CFG) { g_override.erase(k); return; }
+    if (!gemm_tile_cfg(cfg)) { g_override.erase(k); return; }
     TunedEntry e{}; e.M = M; e.N = N; e.K = K; e.conv = conv; e.stride = stride; e.up = up; e.cfg = cfg; e.splitk = splitk < 1 ? 1 : splitk;
     g_override[k] = e;
 }
@@ -956,7 +938,7 @@ void gemm_set_splitk_cap(int cap) { if (cap != g_splitk_cap) ++g_plan_epoch; g_s
 static int g_xcd_mode = getenv("MKD_XCD_MODE") ? atoi(getenv("MKD_XCD_MODE")) : 0;
 void gemm_set_xcd_mode(int mode) { g_xcd_mode = (mode >= 0 && mode <= 2) ? mode : 0; }
 void gemm_force_tile_cfg(int cfg) {
-    const int c = (cfg >= 0 && cfg < N_TILE_CFG) ? cfg : -1;
+    const int c = gemm_tile_cfg(cfg) ? cfg : -1;
     if (c != g_force_cfg) ++g_plan_epoch;       // launch plans hold decisions taken with the previous setting (slab counts of deferred epilogues): re-build
     g_force_cfg = c;
 }
@@ -968,7 +950,7 @@ void gemm_force_tile_cfg(int cfg) {
 static GemmPlan gemm_plan(int M, int N, int K, int force_splitk, int conv = 0, int stride = 0, int up = 0, int pin_cfg = -1, int K2 = 0) {
     const int nk = (K + BK - 1) / BK;
     const int KL = K - K2;          // the tables know the plain convolution (GemmArgs::K2)
-    auto tiles = [&](int c) { return ((M + kTileM[c] - 1) / kTileM[c]) * ((N + kTileN[c] - 1) / kTileN[c]); };
+    auto tiles = [&](int c) { return ((M + kTiles[c].tm - 1) / kTiles[c].tm) * ((N + kTiles[c].tn - 1) / kTiles[c].tn); };
     int cfg;
     const int g_force_cfg = pin_cfg >= 0 ? pin_cfg : ::g_force_cfg;          // (shadows the global on purpose)
     const TunedEntry* te = (g_force_cfg < 0 && force_splitk <= 0) ? tuned_lookup(M, N, KL, conv, stride, up) : nullptr;
@@ -1000,16 +982,17 @@ static GemmPlan gemm_plan(int M, int N, int K, int force_splitk, int conv = 0, i
     else {
         const bool n128 = (N % 128 == 0);
         const int want = 224;
-        if (n128 && tiles(1) >= want) cfg = 1;
-        else if (tiles(3) >= want || (!n128 && M > 64)) cfg = (n128 || tiles(3) >= want) ? 3 : 3;
-        else cfg = 5;
-        if (!n128 && cfg == 1) cfg = 3;
-        if (cfg == 3 && tiles(3) < want && n128) cfg = 5;
-        if (M <= 64) cfg = 5;
+        constexpr int big = CFG_128x128_s3, mid = CFG_128x64, small = CFG_64x64;
+        if (n128 && tiles(big) >= want) cfg = big;
+        else if (tiles(mid) >= want || (!n128 && M > 64)) cfg = (n128 || tiles(mid) >= want) ? mid : mid;
+        else cfg = small;
+        if (!n128 && cfg == big) cfg = mid;
+        if (cfg == mid && tiles(mid) < want && n128) cfg = small;
+        if (M <= 64) cfg = small;
         // shapes the tuned table does not know: the eight-wave siblings of the middle tiles (the whole-loop tuner moved most heavy
-        // shapes onto eight-wave tiles: DESIGN.md 4.4); launches that need more than the plain epilogue fall back to kTileBase
+        // shapes onto eight-wave tiles: DESIGN.md 4.4); launches that need more than the plain epilogue fall back to the row's base configuration
         static const bool heur_w8 = getenv("MKD_HEUR_W8") ? atoi(getenv("MKD_HEUR_W8")) != 0 : true;      // (batch 6: +4.7 %, batch 12: +10.7 %, batch 3: +1.4 % images/s)
-        if (heur_w8 && M >= 256) cfg = cfg == 1 ? 34 : (cfg == 3 ? 35 : (cfg == 5 ? 37 : cfg));
+        if (heur_w8 && M >= 256) cfg = cfg == big ? CFG_128x128_w8 : (cfg == mid ? CFG_128x64_w8 : (cfg == small ? CFG_64x64_w8 : cfg));
     }
     int s = 1;
     if (force_splitk > 0) s = force_splitk;
@@ -1035,7 +1018,7 @@ int gemm_pick_splitk(int M, int N, int K, int conv, int stride, int up) { return
 
 // producers of fused-LayerNorm row statistics keep column tiles >= 64 wide (one statistics slot per column tile, <= 20 slots)
 static GemmPlan stat_producer_plan(GemmPlan g) {
-    if (kTileN[g.cfg] < 64) g.cfg = 5;
+    if (kTiles[g.cfg].tn < 64) g.cfg = CFG_64x64;
     return g;
 }
 
@@ -1051,11 +1034,12 @@ static int gemm_resolve_plan(const GemmArgs& a, GemmPlan* out) {
         g.per = (a.K + BK - 1) / BK;
     }
     if (a.stat_out) g = stat_producer_plan(g);
-    if (kTileKW[g.cfg] > 1 && ((a.ln_s && a.stat_in) || a.stat_out || (a.gn_stat && g.splitk == 1))) g.cfg = kTileBase[g.cfg];     // plain epilogue (or on-the-fly LayerNorm) only
-    if (kTileLight[g.cfg] && (a.ln_s || a.stat_out || (a.gn_stat && g.splitk == 1))) g.cfg = kTileBase[g.cfg];                     // plain epilogue only
+    const TileFamily fam = kTiles[g.cfg].family;
+    if (fam == TILE_KSPLIT && ((a.ln_s && a.stat_in) || a.stat_out || (a.gn_stat && g.splitk == 1))) g.cfg = kTiles[g.cfg].base;     // plain epilogue (or on-the-fly LayerNorm) only
+    if ((fam == TILE_LIGHT || fam == TILE_RA) && (a.ln_s || a.stat_out || (a.gn_stat && g.splitk == 1))) g.cfg = kTiles[g.cfg].base;   // plain epilogue only
     if (is_patch_cfg(g.cfg) && !conv_patch_supported(a, g.cfg)) {
         if (is_patch_cfg(g_force_cfg)) return mkd_fail(-4, "gemm: forced LDS-staged conv tile does not fit this shape");
-        g = gemm_plan(a.M, a.N, a.K, 0, 0, 0, 0, /*pin_cfg=*/1);
+        g = gemm_plan(a.M, a.N, a.K, 0, 0, 0, 0, /*pin_cfg=*/CFG_128x128_s3);
     }
     *out = g;
     return 0;
@@ -1078,7 +1062,7 @@ int gemm_max_splitk() { return 32; }
 int gemm_stat_slots(int M, int N, int K) {
     const GemmPlan g = stat_producer_plan(gemm_plan(M, N, K, 0));
     if (g.splitk > 1) return (N + 255) / 256;
-    return (N + kTileN[g.cfg] - 1) / kTileN[g.cfg];            // one slot per column tile
+    return (N + kTiles[g.cfg].tn - 1) / kTiles[g.cfg].tn;            // one slot per column tile
 }
 int gemm_tile_index(int M, int N, int K, int conv, int stride, int up) { return gemm_plan(M, N, K, 0, conv, stride, up).cfg; }
 
@@ -1086,104 +1070,35 @@ size_t gemm_ws_bytes(int M, int N, int splitk) {
     return splitk > 1 ? (size_t)splitk * M * N * sizeof(float) : 0;
 }
 
-template <int TM, int TN, int WM, int WN, int STAGES, int KW>
-static int launch_tile_kw(const GemmArgs& a, int splitk, hipStream_t stream, const GemmArgs* second) {
-    const GemmArgs2 ag = gemm_pack2(a, second, splitk);
-    const size_t lds = (size_t)KW * STAGES * (TM * 128 + TN * 128);
-    static bool attr_set[2] = {false, false};
-    if (lds > 64 * 1024 && !attr_set[a.conv ? 1 : 0]) {
-        hipError_t e = a.conv ? hipFuncSetAttribute((const void*)gemm_kernel<TM, TN, WM, WN, 1, STAGES, 0, 0, KW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                              : hipFuncSetAttribute((const void*)gemm_kernel<TM, TN, WM, WN, 0, STAGES, 0, 0, KW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return mkd_fail(-2, std::string("hipFuncSetAttribute(max dynamic LDS): ") + hipGetErrorString(e));
-        attr_set[a.conv ? 1 : 0] = true;
-    }
-    dim3 grid((a.M + TM - 1) / TM, (a.N + TN - 1) / TN, splitk * (second ? 2 : 1));
-    dim3 block(64 * WM * WN * KW);
-    if (a.ln_s) {          // on-the-fly LayerNorm (resolve keeps in-block K split only for that form)
-        static bool lattr = false;
-        if (lds > 64 * 1024 && !lattr) {
-            hipError_t e = hipFuncSetAttribute((const void*)gemm_kernel<TM, TN, WM, WN, 0, STAGES, -1, 0, KW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return mkd_fail(-2, std::string("hipFuncSetAttribute(max dynamic LDS): ") + hipGetErrorString(e));
-            lattr = true;
-        }
-        hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 0, STAGES, -1, 0, KW>), grid, block, lds, stream, ag);
-        return 0;
-    }
-    if (a.conv) hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 1, STAGES, 0, 0, KW>), grid, block, lds, stream, ag);
-    else        hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 0, STAGES, 0, 0, KW>), grid, block, lds, stream, ag);
-    return 0;
-}
-
-// plain-epilogue-only launcher (tile configurations 30..37): two instantiations per configuration
-template <int TM, int TN, int WM, int WN, int STAGES>
-static int launch_tile_light(const GemmArgs& a, int splitk, hipStream_t stream, const GemmArgs* second) {
-    const GemmArgs2 ag = gemm_pack2(a, second, splitk);
-    const size_t lds = (size_t)STAGES * (TM * 128 + TN * 128) + (size_t)WN * TM * 2 * sizeof(float);
-    static bool attr_set[2] = {false, false};
-    if (lds > 64 * 1024 && !attr_set[a.conv ? 1 : 0]) {
-        hipError_t e = a.conv ? hipFuncSetAttribute((const void*)gemm_kernel<TM, TN, WM, WN, 1, STAGES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                              : hipFuncSetAttribute((const void*)gemm_kernel<TM, TN, WM, WN, 0, STAGES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return mkd_fail(-2, std::string("hipFuncSetAttribute(max dynamic LDS): ") + hipGetErrorString(e));
-        attr_set[a.conv ? 1 : 0] = true;
-    }
-    dim3 grid((a.M + TM - 1) / TM, (a.N + TN - 1) / TN, splitk * (second ? 2 : 1));
-    dim3 block(64 * WM * WN);
-    if (a.conv) hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 1, STAGES>), grid, block, lds, stream, ag);
-    else        hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 0, STAGES>), grid, block, lds, stream, ag);
-    return 0;
-}
-
-template <int TM, int TN, int WM, int WN, int STAGES>
+// One launcher for every row of gemm_tiles.inc that launch_gemm dispatches: it picks the kernel variant the launch asks for - conv or
+// linear, GroupNorm statistics, LayerNorm on the fly or producer-fed with 1 / 3 / 5 statistics loads per lane - among the ones the
+// row's family instantiates: GEMM eight, KSPLIT three, LIGHT and RA two (gemm_resolve_plan moved everything else to the base row).
+template <TileFamily FAM, int TM, int TN, int WM, int WN, int STAGES, int KW>
 static int launch_tile(const GemmArgs& a, int splitk, hipStream_t stream, const GemmArgs* second) {
     const GemmArgs2 ag = gemm_pack2(a, second, splitk);
-    const bool gns = a.gn_stat != nullptr && splitk == 1;
-    const size_t lds = (size_t)STAGES * (TM * 128 + TN * 128) + (gns ? (size_t)4096 : (size_t)WN * TM * 2 * sizeof(float));   // ring + tail
-    static bool attr_set[2] = {false, false};
-    if (lds > 64 * 1024 && !attr_set[a.conv ? 1 : 0]) {
-        hipError_t e = a.conv ? hipFuncSetAttribute((const void*)gemm_kernel<TM, TN, WM, WN, 1, STAGES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                              : hipFuncSetAttribute((const void*)gemm_kernel<TM, TN, WM, WN, 0, STAGES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return mkd_fail(-2, std::string("hipFuncSetAttribute(max dynamic LDS): ") + hipGetErrorString(e));
-        attr_set[a.conv ? 1 : 0] = true;
-    }
-    dim3 grid((a.M + TM - 1) / TM, (a.N + TN - 1) / TN, splitk * (second ? 2 : 1));
-    dim3 block(64 * WM * WN);
-    if (gns) {
-        static bool gattr[2] = {false, false};
-        if (lds > 64 * 1024 && !gattr[a.conv ? 1 : 0]) {
-            hipError_t e = a.conv ? hipFuncSetAttribute((const void*)gemm_kernel<TM, TN, WM, WN, 1, STAGES, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                                  : hipFuncSetAttribute((const void*)gemm_kernel<TM, TN, WM, WN, 0, STAGES, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return mkd_fail(-2, std::string("hipFuncSetAttribute(max dynamic LDS): ") + hipGetErrorString(e));
-            gattr[a.conv ? 1 : 0] = true;
+    const dim3 grid((a.M + TM - 1) / TM, (a.N + TN - 1) / TN, splitk * (second ? 2 : 1));
+    const dim3 block(64 * WM * WN * KW);
+    if constexpr (FAM == TILE_PATCH) {
+        return mkd_fail(-1, "gemm: LDS-staged conv tiles are launched by launch_conv_patch");
+    } else if constexpr (FAM == TILE_RA) {
+        const size_t lds = (size_t)2 * TN * 128;
+        return a.conv ? launch_lds_kernel<gemm_ra_kernel<TM, TN, WM, 1, STAGES>>(grid, block, lds, stream, ag)
+                      : launch_lds_kernel<gemm_ra_kernel<TM, TN, WM, 0, STAGES>>(grid, block, lds, stream, ag);
+    } else {
+#define MKD_GO(CONV, LN, GNS) launch_lds_kernel<gemm_kernel<TM, TN, WM, WN, CONV, STAGES, LN, GNS, KW>>(grid, block, lds, stream, ag)
+        const bool gns = FAM == TILE_GEMM && a.gn_stat != nullptr && splitk == 1;
+        const size_t ring = (size_t)KW * STAGES * (TM * 128 + TN * 128);
+        const size_t lds = ring + (FAM == TILE_KSPLIT ? 0 : gns ? (size_t)4096 : (size_t)WN * TM * 2 * sizeof(float));      // KSPLIT: the rings alone
+        if constexpr (FAM == TILE_GEMM) {
+            if (gns) return a.conv ? MKD_GO(1, 0, 1) : MKD_GO(0, 0, 1);
+            if (a.ln_s && a.stat_in) return a.stat_in_slots <= 4 ? MKD_GO(0, 1, 0) : a.stat_in_slots <= 12 ? MKD_GO(0, 3, 0) : MKD_GO(0, 5, 0);
         }
-        if (a.conv) hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 1, STAGES, 0, 1>), grid, block, lds, stream, ag);
-        else        hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 0, STAGES, 0, 1>), grid, block, lds, stream, ag);
-        return 0;
-    }
-    if (a.ln_s && !a.stat_in) {          // LayerNorm statistics taken by the GEMM itself
-        static bool lf_attr = false;
-        if (lds > 64 * 1024 && !lf_attr) {
-            hipError_t e = hipFuncSetAttribute((const void*)gemm_kernel<TM, TN, WM, WN, 0, STAGES, -1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return mkd_fail(-2, std::string("hipFuncSetAttribute(max dynamic LDS): ") + hipGetErrorString(e));
-            lf_attr = true;
+        if constexpr (FAM != TILE_LIGHT) {
+            if (a.ln_s) return MKD_GO(0, -1, 0);          // LayerNorm statistics taken by the GEMM itself
         }
-        hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 0, STAGES, -1>), grid, block, lds, stream, ag);
-        return 0;
+        return a.conv ? MKD_GO(1, 0, 0) : MKD_GO(0, 0, 0);
+#undef MKD_GO
     }
-    if (a.ln_s) {
-        static bool ln_attr = false;
-        if (lds > 64 * 1024 && !ln_attr) {
-            hipError_t e = hipFuncSetAttribute((const void*)gemm_kernel<TM, TN, WM, WN, 0, STAGES, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_kernel<TM, TN, WM, WN, 0, STAGES, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_kernel<TM, TN, WM, WN, 0, STAGES, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return mkd_fail(-2, std::string("hipFuncSetAttribute(max dynamic LDS): ") + hipGetErrorString(e));
-            ln_attr = true;
-        }
-        if (a.stat_in_slots <= 4) hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 0, STAGES, 1>), grid, block, lds, stream, ag);
-        else if (a.stat_in_slots <= 12) hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 0, STAGES, 3>), grid, block, lds, stream, ag);
-        else hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 0, STAGES, 5>), grid, block, lds, stream, ag);
-    } else if (a.conv) hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 1, STAGES>), grid, block, lds, stream, ag);
-    else        hipLaunchKernelGGL((gemm_kernel<TM, TN, WM, WN, 0, STAGES>), grid, block, lds, stream, ag);
-    return 0;
 }
 
 bool gemm_same_geometry(const GemmArgs& a, const GemmArgs& b) {
@@ -1193,17 +1108,6 @@ bool gemm_same_geometry(const GemmArgs& a, const GemmArgs& b) {
            (a.ln_s != nullptr) == (b.ln_s != nullptr) && a.ln_eps == b.ln_eps && !a.stat_in && !b.stat_in && !a.stat_out && !b.stat_out &&
            !a.gn_stat && !b.gn_stat && (a.R != nullptr) == (b.R != nullptr) && a.ldr == b.ldr && (a.rowbias != nullptr) == (b.rowbias != nullptr) &&
            (a.bias != nullptr) == (b.bias != nullptr) && (a.A2 != nullptr) == (b.A2 != nullptr) && a.K2 == b.K2 && a.lda2 == b.lda2;
-}
-
-template <int TM, int TN, int NW, int STAGES>
-static int launch_tile_ra(const GemmArgs& a, int splitk, hipStream_t stream, const GemmArgs* second) {
-    const GemmArgs2 ag = gemm_pack2(a, second, splitk);
-    const size_t lds = (size_t)2 * TN * 128;
-    dim3 grid((a.M + TM - 1) / TM, (a.N + TN - 1) / TN, splitk * (second ? 2 : 1));
-    dim3 block(64 * NW);
-    if (a.conv) hipLaunchKernelGGL((gemm_ra_kernel<TM, TN, NW, 1, STAGES>), grid, block, lds, stream, ag);
-    else        hipLaunchKernelGGL((gemm_ra_kernel<TM, TN, NW, 0, STAGES>), grid, block, lds, stream, ag);
-    return 0;
 }
 
 int launch_gemm(GemmArgs a, hipStream_t stream, const GemmArgs* second) {
@@ -1251,46 +1155,11 @@ int launch_gemm(GemmArgs a, hipStream_t stream, const GemmArgs* second) {
     if (second) { b.splitk = a.splitk; b.ksteps_per_split = a.ksteps_per_split; b.xcd_mode = a.xcd_mode; }
     int rc;
     switch (g.cfg) {
-        case 0: rc = launch_tile<256, 128, 4, 2, 3>(a, g.splitk, stream, sp); break;
-        case 1: rc = launch_tile<128, 128, 2, 2, 3>(a, g.splitk, stream, sp); break;
-        case 2: rc = launch_tile<128, 128, 2, 2, 2>(a, g.splitk, stream, sp); break;
-        case 3: rc = launch_tile<128, 64, 2, 2, 3>(a, g.splitk, stream, sp); break;
-        case 4: rc = launch_tile<64, 128, 2, 2, 3>(a, g.splitk, stream, sp); break;
-        case 12: rc = launch_tile<64, 64, 2, 2, 6>(a, g.splitk, stream, sp); break;
-        case 13: rc = launch_tile<64, 128, 2, 2, 5>(a, g.splitk, stream, sp); break;
-        case 14: rc = launch_tile<64, 160, 2, 2, 3>(a, g.splitk, stream, sp); break;
-        case 15: rc = launch_tile<128, 160, 2, 2, 3>(a, g.splitk, stream, sp); break;
-        case 16: rc = launch_tile<64, 160, 2, 2, 2>(a, g.splitk, stream, sp); break;
-        case 17: rc = launch_tile<32, 64, 2, 2, 4>(a, g.splitk, stream, sp); break;
-        case 18: rc = launch_tile<64, 32, 2, 2, 4>(a, g.splitk, stream, sp); break;
-        case 19: rc = launch_tile<32, 32, 2, 2, 4>(a, g.splitk, stream, sp); break;
-        case 20: rc = launch_tile_kw<32, 32, 2, 2, 4, 2>(a, g.splitk, stream, sp); break;
-        case 21: rc = launch_tile_kw<32, 32, 2, 2, 4, 4>(a, g.splitk, stream, sp); break;
-        case 22: rc = launch_tile_kw<64, 32, 2, 2, 4, 2>(a, g.splitk, stream, sp); break;
-        case 23: rc = launch_tile_kw<64, 32, 2, 2, 3, 4>(a, g.splitk, stream, sp); break;
-        case 24: rc = launch_tile_kw<64, 64, 2, 2, 4, 2>(a, g.splitk, stream, sp); break;
-        case 25: rc = launch_tile_kw<64, 64, 2, 2, 2, 4>(a, g.splitk, stream, sp); break;
-        case 26: rc = launch_tile_kw<32, 64, 2, 2, 4, 2>(a, g.splitk, stream, sp); break;
-        case 27: rc = launch_tile_kw<32, 64, 2, 2, 3, 4>(a, g.splitk, stream, sp); break;
-        case 28: rc = launch_tile_kw<128, 64, 2, 2, 3, 2>(a, g.splitk, stream, sp); break;
-        case 29: rc = launch_tile_kw<64, 128, 2, 2, 3, 2>(a, g.splitk, stream, sp); break;
-        case 30: rc = launch_tile_light<64, 64, 2, 2, 2>(a, g.splitk, stream, sp); break;
-        case 31: rc = launch_tile_light<128, 64, 2, 2, 2>(a, g.splitk, stream, sp); break;
-        case 32: rc = launch_tile_light<64, 128, 2, 2, 2>(a, g.splitk, stream, sp); break;
-        case 33: rc = launch_tile_light<64, 32, 2, 2, 2>(a, g.splitk, stream, sp); break;
-        case 34: rc = launch_tile_light<128, 128, 4, 2, 2>(a, g.splitk, stream, sp); break;
-        case 35: rc = launch_tile_light<128, 64, 4, 2, 3>(a, g.splitk, stream, sp); break;
-        case 36: rc = launch_tile_light<64, 128, 2, 4, 3>(a, g.splitk, stream, sp); break;
-        case 37: rc = launch_tile_light<64, 64, 2, 4, 4>(a, g.splitk, stream, sp); break;
-        case 41: rc = launch_tile_light<256, 64, 4, 2, 3>(a, g.splitk, stream, sp); break;
-        case 50: rc = launch_tile_light<256, 256, 4, 4, 2>(a, g.splitk, stream, sp); break;
-        case 44: rc = launch_tile_ra<256, 64, 8, 4>(a, g.splitk, stream, sp); break;
-        case 45: rc = launch_tile_ra<256, 128, 8, 3>(a, g.splitk, stream, sp); break;
-        case 46: rc = launch_tile_ra<128, 128, 4, 3>(a, g.splitk, stream, sp); break;
-        case 47: rc = launch_tile_ra<128, 64, 4, 4>(a, g.splitk, stream, sp); break;
-        case 48: rc = launch_tile_ra<128, 160, 4, 3>(a, g.splitk, stream, sp); break;
-        case 49: rc = launch_tile_ra<256, 64, 4, 3>(a, g.splitk, stream, sp); break;
-        default: rc = launch_tile<64, 64, 2, 2, 4>(a, g.splitk, stream, sp); break;
+#define MKD_TILE(INDEX, NAME, FAMILY, TM, TN, WM, WN, STAGES, KW, BASE) \
+        case INDEX: rc = launch_tile<TILE_##FAMILY, TM, TN, WM, WN, STAGES, KW>(a, g.splitk, stream, sp); break;
+#include "gemm_tiles.inc"
+#undef MKD_TILE
+        default: return mkd_fail(-1, "gemm: tile configuration " + std::to_string(g.cfg) + " is not in the table");
     }
     if (rc) return rc;
     MKD_LAUNCH_CHECK("gemm_kernel");

@@ -164,7 +164,12 @@ int  gemm_pick_splitk(int M, int N, int K, int conv, int stride, int up);
 bool gemm_cfg_folds_second_input(int cfg);     // may this tile configuration take GemmArgs::A2 (gather / linear kernel)?
 int  gemm_resolve(const GemmArgs& a, int* cfg, int* splitk);       // the (tile, split-K) launch_gemm will use for exactly these arguments
 int  gemm_stat_slots(int M, int N, int K);   // column slots a linear GEMM of this shape writes row statistics in
-int  gemm_tile_index(int M, int N, int K, int conv, int stride, int up);   // index into the tile-config table of kernels_gemm.hip
+int  gemm_tile_index(int M, int N, int K, int conv, int stride, int up);   // index into the tile-configuration table (gemm_tiles.inc)
+// one row of gemm_tiles.inc (the columns are described there)
+enum TileFamily { TILE_GEMM, TILE_KSPLIT, TILE_LIGHT, TILE_PATCH, TILE_RA };
+struct TileCfg { int index; const char* name; TileFamily family; int tm, tn, wm, wn, stages, kw, base; };
+const TileCfg* gemm_tile_cfg(int cfg);       // null when cfg is not in the table
+int  gemm_tile_info(int cfg, int* tile_m, int* tile_n, int* lds_staged_conv, const char** name);      // mkd_gemm_tile_info (include/mkd.h)
 void gemm_set_xcd_mode(int mode);         // tests / experiments: 0 launch order, 1 / 2 contiguous runs per XCD (GemmArgs::xcd_mode)
 void gemm_force_tile_cfg(int cfg);           // tuner/tests: force a tile config (-1 = heuristic)
 void gemm_set_splitk_cap(int cap);

@@ -114,6 +114,7 @@ SIGNATURES = {
     'mkd_gn_colstats': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     'mkd_gn_apply_stats': (_I, [_P, _I, _P, _P, _F, _I, _P, _I, _I, _I, _I, _P, _P]),
     'mkd_gemm_force_tile': (_I, [_I]),
+    'mkd_gemm_tile_info': (_I, [_I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_char_p)]),
     'mkd_gemm_set_xcd_mode': (_I, [_I]),
     'mkd_debug_poison': (_I, [_P]),
     'mkd_gemm_set_override': (_I, [_I, _I, _I, _I, _I, _I, _I, _I]),
@@ -164,3 +165,14 @@ def check(rc: int, what: str = '') -> None:
     if rc != 0:
         msg = load().mkd_last_error()
         raise MkdError(f'{what} failed ({rc}): {msg.decode() if msg else "?"}')
+
+
+def tile_table() -> list:
+    """[(tile_m, tile_n, lds_staged_conv, name)] of every GEMM tile configuration, in index order (mkd_gemm_tile_info; needs no GPU)."""
+    lib = load()
+    m, n, patch, name = _I(), _I(), _I(), C.c_char_p()
+    rows = []
+    for cfg in range(lib.mkd_gemm_tile_info(-1, None, None, None, None)):
+        lib.mkd_gemm_tile_info(cfg, C.byref(m), C.byref(n), C.byref(patch), C.byref(name))
+        rows.append((m.value, n.value, bool(patch.value), name.value.decode()))
+    return rows

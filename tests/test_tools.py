@@ -52,27 +52,40 @@ def test_committed_table_matches_its_sources(tmp_path):
 
 
 def test_tuner_scripts_know_the_librarys_tile_table():
-    """tools/tune_*.py carry their own copies of the tile sizes (candidate filtering, reports): they must match kTileM / kTileN of
-    kernels_gemm.hip entry for entry, and treat the same configurations as LDS-staged conv tiles as is_patch_cfg does."""
-    import ast
+    """Configuration indices are persistent: gemm_tuned.inc and profiles/tune/*.json hold them.  So mkd_gemm_tile_info (host only, no GPU)
+    must report exactly these 51 rows - tile M, tile N, LDS-staged conv flag, name, pinned here as literals - and the tuner scripts must
+    take the table from the library instead of carrying copies of it."""
+    import ctypes as C
     import re
-    src = open(os.path.join(ROOT, 'makeupdiffuse_amd', 'csrc', 'kernels_gemm.hip')).read()
-
-    def c_array(name):
-        body = re.search(r'static const int ' + name + r'\[N_TILE_CFG\] = \{([^}]*)\}', src).group(1)
-        return [int(v) for v in body.replace('\n', ' ').split(',')]
-    n = int(re.search(r'constexpr int N_TILE_CFG = (\d+);', src).group(1))
-    tm, tn = c_array('kTileM'), c_array('kTileN')
-    assert len(tm) == n and len(tn) == n and len(c_array('kTileKW')) == n and len(c_array('kTileLight')) == n and len(c_array('kTileBase')) == n
-    names = re.search(r'kTileName\[N_TILE_CFG\] = \{(.*?)\};', src, re.S).group(1)
-    assert len(re.findall(r'"[^"]+"', names)) == n
-    patch_c = re.search(r'static bool is_patch_cfg\(int c\) \{ return (.*?); \}', src).group(1)
-    is_patch = lambda c: eval(patch_c.replace('&&', ' and ').replace('||', ' or '), {'c': c})
+    tile_m = [256, 128, 128, 128, 64, 64, 256, 256, 128, 128, 64, 64, 64, 64, 64, 128, 64, 32, 64, 32,
+              32, 32, 64, 64, 64, 64, 32, 32, 128, 64, 64, 128, 64, 64, 128, 128, 64, 64, 128, 64, 128, 256, 256, 128,
+              256, 256, 128, 128, 128, 256, 256]
+    tile_n = [128, 128, 128, 64, 128, 64, 128, 64, 128, 64, 128, 64, 64, 128, 160, 160, 160, 64, 32, 32,
+              32, 32, 32, 32, 64, 64, 64, 64, 64, 128, 64, 64, 128, 32, 128, 64, 128, 64, 64, 128, 128, 64, 128, 128,
+              64, 128, 128, 64, 160, 64, 256]
+    names = ["256x128", "128x128_s3", "128x128_s2", "128x64", "64x128", "64x64",
+             "patch256x128", "patch256x64", "patch128x128", "patch128x64",
+             "patch64x128", "patch64x64", "64x64_s6", "64x128_s5", "64x160", "128x160", "64x160_s2", "32x64", "64x32", "32x32",
+             "32x32_k2", "32x32_k4", "64x32_k2", "64x32_k4", "64x64_k2", "64x64_k4", "32x64_k2", "32x64_k4", "128x64_k2", "64x128_k2",
+             "64x64_s2", "128x64_s2", "64x128_s2", "64x32_s2", "128x128_w8", "128x64_w8", "64x128_w8", "64x64_w8",
+             "patch128x64_w8", "patch64x128_w8", "patch128x128_w8", "256x64_w8", "patch256x128_w16", "patch128x128_w16",
+             "ra256x64_w8", "ra256x128_w8", "ra128x128", "ra128x64", "ra128x160", "ra256x64", "256x256_w16"]
+    patch = {6, 7, 8, 9, 10, 11, 38, 39, 40, 42, 43}
+    assert len(tile_m) == len(tile_n) == len(names) == 51
+    sys.path.insert(0, ROOT)
+    from makeupdiffuse_amd import lib as mlib
+    lib = mlib.load()
+    assert lib.mkd_gemm_tile_info(-1, None, None, None, None) == 51
+    for cfg in range(51):
+        m, n, p, nm = C.c_int(-1), C.c_int(-1), C.c_int(-1), C.c_char_p()
+        assert lib.mkd_gemm_tile_info(cfg, C.byref(m), C.byref(n), C.byref(p), C.byref(nm)) == 51
+        assert (m.value, n.value, p.value, nm.value.decode()) == (tile_m[cfg], tile_n[cfg], int(cfg in patch), names[cfg]), f'configuration {cfg}'
+    for cfg in (-1, 51):          # out of range: the count, outputs untouched
+        m = C.c_int(-7)
+        assert lib.mkd_gemm_tile_info(cfg, C.byref(m), None, None, None) == 51 and m.value == -7
+    assert mlib.tile_table() == [(tile_m[c], tile_n[c], c in patch, names[c]) for c in range(51)]
     for script in ('tune_gemm.py', 'tune_ineval.py', 'tune_wall.py'):
         text = open(os.path.join(ROOT, 'tools', script)).read()
-        for var, want in (('TILE_M', tm), ('TILE_N', tn)):
-            got = ast.literal_eval(re.search(r'^' + var + r' = (\[.*\])$', text, re.M).group(1))
-            assert got == want, f'{script}: {var} differs from the library table'
-        expr = re.search(r'patch = (.*)$', text, re.M).group(1)
-        for cfg in range(n):
-            assert bool(eval(expr, {'cfg': cfg})) == bool(is_patch(cfg)), f'{script}: configuration {cfg} patch / gather mismatch'
+        assert 'tile_table()' in text, f'{script}: does not read the library table'
+        assert not re.search(r'\[\s*\d+\s*(,\s*\d+\s*){7,}', text), f'{script}: carries a literal list of numbers'
+        assert not re.search(r'\d+\s*<=?\s*cfg|cfg\s*[<>]=?\s*\d+|cfg\s+in\s*[(\[{]\s*\d', text), f'{script}: selects configurations by literal index'

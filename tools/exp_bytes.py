@@ -17,8 +17,7 @@ from makeupdiffuse_amd import lib as mlib  # noqa: E402
 from makeupdiffuse_amd.engine import MkdEngine, NetConfig  # noqa: E402
 from makeupdiffuse_amd.schedule import DDIMSchedule  # noqa: E402
 
-TILE_M = [256, 128, 128, 128, 64, 64, 256, 256, 128, 128, 64, 64, 64, 64, 64, 128, 64, 32, 64, 32, 32, 32, 64, 64, 64, 64, 32, 32, 128, 64]
-TILE_N = [128, 128, 128, 64, 128, 64, 128, 64, 128, 64, 128, 64, 64, 128, 160, 160, 160, 64, 32, 32, 32, 32, 32, 32, 64, 64, 64, 64, 64, 128]
+TILE_M, TILE_N, PATCH, _ = zip(*mlib.tile_table())      # the library's tile table, by configuration index (needs no GPU)
 KEYS = ('M', 'N', 'K', 'conv', 'stride', 'up', 'Hin', 'Win', 'Cin', 'Hout', 'Wout', 'splitk')
 
 
@@ -67,7 +66,7 @@ def main():
             for cfg in range(20):
                 if not lib.mkd_gemm_cfg_supported(cfg, M, N, K, conv, Hin, Win, Cin, Hout, Wout, stride, up):
                     continue
-                patch = 6 <= cfg <= 11
+                patch = PATCH[cfg]
                 if patch and not (conv and stride == 1 and up == 0 and Cin % 64 == 0):
                     continue
                 tiles = -(-M // TILE_M[cfg]) * -(-N // TILE_N[cfg])

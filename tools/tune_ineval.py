@@ -27,8 +27,7 @@ from makeupdiffuse_amd import lib as mlib  # noqa: E402
 from makeupdiffuse_amd.engine import MkdEngine, NetConfig  # noqa: E402
 from makeupdiffuse_amd.schedule import DDIMSchedule  # noqa: E402
 
-TILE_M = [256, 128, 128, 128, 64, 64, 256, 256, 128, 128, 64, 64, 64, 64, 64, 128, 64, 32, 64, 32, 32, 32, 64, 64, 64, 64, 32, 32, 128, 64, 64, 128, 64, 64, 128, 128, 64, 64, 128, 64, 128, 256, 256, 128, 256, 256, 128, 128, 128, 256, 256]
-TILE_N = [128, 128, 128, 64, 128, 64, 128, 64, 128, 64, 128, 64, 64, 128, 160, 160, 160, 64, 32, 32, 32, 32, 32, 32, 64, 64, 64, 64, 64, 128, 64, 64, 128, 32, 128, 64, 128, 64, 64, 128, 128, 64, 128, 128, 64, 128, 128, 64, 160, 64, 256]
+TILE_M, TILE_N, PATCH, _ = zip(*mlib.tile_table())      # the library's tile table, by configuration index (needs no GPU)
 SPLITS = (1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 24)
 KEYS = ('M', 'N', 'K', 'conv', 'stride', 'up', 'Hin', 'Win', 'Cin', 'Hout', 'Wout')
 
@@ -57,7 +56,7 @@ def valid(lib, shape, cfg, s):
     M, N, K, conv, stride, up, Hin, Win, Cin, Hout, Wout = shape
     if not lib.mkd_gemm_cfg_supported(cfg, M, N, K, conv, Hin, Win, Cin, Hout, Wout, stride, up):
         return False
-    patch = 6 <= cfg <= 11 or 38 <= cfg <= 40 or cfg in (42, 43)
+    patch = PATCH[cfg]
     tiles = -(-M // TILE_M[cfg]) * -(-N // TILE_N[cfg])
     units = Cin // 64 if patch else (K + 63) // 64
     if s == 1:
