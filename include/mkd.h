@@ -120,6 +120,36 @@ int mkd_prepare(mkd_ctx* ctx, int batch, int h, int w, const float* hint, const 
 int mkd_prepare_interp(mkd_ctx* ctx, int batch, int h, int w, const float* hint_a, const float* hint_b, const float* alpha,
                        const float* context, const float* control_scales, int only_mid_control, void* stream);
 
+/* Region-wise makeup transfer from SEVERAL references (BUILD-DEFINED like interpolation, DESIGN.md §0: lips from one reference, eye
+ * shadow from another, skin from a third, each with its own strength).  Like mkd_prepare, but the cached ControlNet hint embedding is
+ * the spatial blend  E[b,y,x,:] = sum_r weights[b,r,y,x] * E(hints[r])[b,y,x,:]  of n_hints = R (1..8) embeddings, hints[r] = src||ref_r,
+ * index 0 the base (src||src as hint 0 fades towards "no makeup").  hints: HOST array of R device pointers, each [B,hint_channels,8h,8w];
+ * weights: DEVICE fp32 [B,R,h,w], arbitrary values (mkd_region_weights builds them from region masks), read when the call runs: new
+ * weights with the same R do not re-plan.  The sum is fp32 in the order r = 0, 1, ... (w0 e0, then fma(w_r, e_r, acc)), rounded to bf16
+ * once.  Costs R - 1 hint-block passes and one launch more than mkd_prepare, and nothing per step: guidance (prepare 2B with hints and
+ * weights doubled), masked sampling, inversion and the DPM-Solver++ loop start from the prepared conditioning unchanged.
+ * n_hints outside 1..8, a null pointer or a bad shape: MKD_ERR_ARG before anything is enqueued. */
+int mkd_prepare_regions(mkd_ctx* ctx, int batch, int h, int w, const float* const* hints, int n_hints, const float* weights,
+                        const float* context, const float* control_scales, int only_mid_control, void* stream);
+/* Blend weights from region masks.  masks uint8 [n_masks][batch][H][W] (n_masks = K = R - 1 in 1..7, non-zero = inside; the layout of
+ * mkd_region_mask_from_labels outputs stacked region-major), factor f in 1..64 with H, W multiples of it, feather rho in 0..4 latent
+ * pixels, strength DEVICE fp32 [batch][K] or NULL (all ones) -> out [batch][K+1][H/f][W/f] fp32:
+ *   a pixel belongs to the LOWEST k whose mask is non-zero (priority resolves overlaps), else to nobody;
+ *   cnt_k(y,x) = owned pixels of latent block (y,x); S_k = sum of cnt_k over the (2 rho + 1)^2 window, indices clamped to the edge;
+ *   a_k = float(S_k) / float((2 rho + 1)^2 f^2);  w_{k+1} = strength[b,k] * a_k;  w_0 = max(0, ((1 - w_1) - w_2) - ...), fp32 in that order.
+ * Integer counts and one correctly rounded operation per step: the output has the bits of a numpy float32 restatement.  One launch,
+ * the block counts of a sample staged in LDS (K * (H/f) * (W/f) <= 32768, else MKD_ERR_ARG); no scratch, no atomics, no host sync.
+ * Bad shapes, n_masks outside 1..7, a null masks / out or feather outside 0..4: MKD_ERR_ARG before anything is enqueued. */
+int mkd_region_weights(const uint8_t* masks, int n_masks, int batch, int H, int W, int factor, int feather, const float* strength,
+                       float* out, void* stream);
+/* The blend of mkd_prepare_regions as a stand-alone kernel (unit tests): e_ptrs HOST array of R (1..8) device pointers to bf16 NHWC
+ * [batch, hw, C] embeddings (16-byte aligned, C a multiple of 8), weights fp32 [batch, R, hw], out bf16 [batch, hw, C]; out may alias
+ * e_ptrs[0].  MKD_ERR_ARG as above. */
+int mkd_region_blend_bf16(const uint16_t* const* e_ptrs, const float* weights, uint16_t* out, int batch, int hw, int C, int R, void* stream);
+/* Tests only, like mkd_debug_poison: copies the cached ControlNet hint embedding [B,h,w,model_channels] bf16 out (enqueued on `stream`).
+ * MKD_ERR_STATE when no conditioning with a hint is prepared. */
+int mkd_debug_hint_embedding(mkd_ctx* ctx, uint16_t* out_bf16, void* stream);
+
 /* ---- one eps evaluation ----------------------------------------------------------------- */
 /* Replaces apply_model (makeup_diffuse.py:152-170): ControlNet -> 13 residuals x scale ->
  * ControlledUnet.  x [B,4,h,w] fp32 NCHW, t [B] int64 (device), eps_out [B,4,h,w] fp32. */

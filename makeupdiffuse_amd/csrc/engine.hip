@@ -254,8 +254,9 @@ struct mkd_ctx {
     std::map<std::string, Tensor> kv_cache;       // transformer prefix -> [B*77, 2d]
     Tensor hint_emb;
     bf16_t* ctx_bf16 = nullptr;
-    const float* in_hint = nullptr; const float* in_context = nullptr;
-    const float* in_hint2 = nullptr; const float* in_alpha = nullptr; bool has_interp = false;   // makeup interpolation (build-defined)
+    const float* in_hints[8] = {}; const float* in_context = nullptr;      // [0]: the hint; [1]: interpolation's second; [0..R): region transfer
+    const float* in_alpha = nullptr; bool has_interp = false;   // makeup interpolation (build-defined)
+    const float* in_weights = nullptr; int n_region_hints = 0;  // region-wise transfer (build-defined): weights [B, R, h, w], R hints (0: off)
     // ---- first-stage decoder (AutoencoderKL.decode) ----
     bool vae_configured = false, vae_finalized = false;
     bool clip_configured = false, clip_finalized = false; mkd_clip_config ccfg{};
@@ -1269,7 +1270,7 @@ struct mkd_ctx {
             for (int j = 0; j < 7; ++j) widths[j + 1] = cfg.hint_widths[j];
             widths[8] = cfg.model_channels;
             const int H0 = 8 * h, W0 = 8 * w;
-            // input_hint_block on hint (which == 0) or on the second reference's hint (which == 1, interpolation)
+            // input_hint_block on in_hints[which2]: 0 the hint, 1 interpolation's second reference, 0..R-1 the references of a region transfer
             auto hint_chain = [&](int which2) -> Tensor {
                 const size_t mk = TA().mark();
                 Tensor cur = talloc(TA(), B, H0, W0, widths[1]);
@@ -1277,7 +1278,7 @@ struct mkd_ctx {
                     const bf16_t* wgt = wb(P + "input_hint_block.0.weight"); const float* bias = wf(P + "input_hint_block.0.bias");
                     const int Bn = B, cin = widths[0], cout = widths[1];
                     push(*cur_plan, [self, wgt, bias, cur, Bn, H0, W0, cin, cout, which2](hipStream_t st) {
-                        return launch_conv3x3_direct(which2 ? self->in_hint2 : self->in_hint, 1, wgt, bias, cur.p, 0, 1, nullptr, Bn, H0,
+                        return launch_conv3x3_direct(self->in_hints[which2], 1, wgt, bias, cur.p, 0, 1, nullptr, Bn, H0,
                                                      W0, cin, cout, 1, st);
                     }, 1, 0.0);
                 }
@@ -1299,6 +1300,17 @@ struct mkd_ctx {
                 const int64_t per = (int64_t)he.H * he.W * he.C;
                 push(*cur_plan, [self, he, e2, per, Bn](hipStream_t st) {
                     return launch_blend(he.p, e2.p, self->in_alpha, he.p, per, Bn, st);
+                }, 1, 0.0);
+            }
+            if (n_region_hints) {
+                // all R embeddings stay live for the spatial blend, which writes the persistent hint_emb (out aliases e[0]); the
+                // weights pointer is read when the plan runs, like in_alpha: new weights with the same R do not re-plan
+                struct { const bf16_t* e[8]; } tab = {};
+                tab.e[0] = hint_emb.p;
+                for (int r = 1; r < n_region_hints; ++r) tab.e[r] = hint_chain(r).p;
+                Tensor he = hint_emb; const int Bn = B, R = n_region_hints;
+                push(*cur_plan, [self, he, tab, Bn, R](hipStream_t st) {
+                    return launch_region_blend(tab.e, self->in_weights, he.p, Bn, he.H * he.W, he.C, R, st);
                 }, 1, 0.0);
             }
         }
@@ -1619,7 +1631,8 @@ struct mkd_ctx {
     }
 
     int prepare(int batch, int hh, int ww, const float* hint, const float* context, const float* control_scales,
-                int only_mid_control, hipStream_t stream, const float* hint2 = nullptr, const float* alpha = nullptr) {
+                int only_mid_control, hipStream_t stream, const float* hint2 = nullptr, const float* alpha = nullptr,
+                const float* const* region_hints = nullptr, int n_regions = 0, const float* region_weights = nullptr) {
         if (!finalized) return mkd_fail(MKD_ERR_STATE, "mkd_prepare before mkd_weights_finalize");
         if (batch <= 0 || hh <= 0 || ww <= 0 || !context) return mkd_fail(MKD_ERR_ARG, "mkd_prepare: bad arguments");
         const int down = 1 << (cfg.n_levels - 1);
@@ -1628,13 +1641,15 @@ struct mkd_ctx {
         const bool interp = hint2 != nullptr;
         if (interp && (!ctrl || !alpha)) return mkd_fail(MKD_ERR_ARG, "mkd_prepare_interp: needs hint, hint2 and alpha");
         const bool same = prepared && batch == B && hh == h && ww == w && ctrl == has_control && (only_mid_control != 0) == only_mid &&
-                          interp == has_interp && plan_epoch == gemm_plan_epoch() && opt_epoch_planned == opt_epoch;
+                          interp == has_interp && n_regions == n_region_hints && plan_epoch == gemm_plan_epoch() && opt_epoch_planned == opt_epoch;
         bool same_scales = same;
         for (int i = 0; i < n_ctrl() && same_scales; ++i) same_scales = scales[i] == (control_scales ? control_scales[i] : 1.f);
-        in_hint = hint; in_context = context; in_hint2 = hint2; in_alpha = alpha;
+        for (int r = 0; r < 8; ++r) in_hints[r] = r < n_regions ? region_hints[r] : nullptr;
+        if (!n_regions) { in_hints[0] = hint; in_hints[1] = hint2; }
+        in_context = context; in_alpha = alpha; in_weights = region_weights;
         if (!same_scales) {
             plan_epoch = gemm_plan_epoch(); opt_epoch_planned = opt_epoch;
-            B = batch; h = hh; w = ww; has_control = ctrl; only_mid = only_mid_control != 0; has_interp = interp;
+            B = batch; h = hh; w = ww; has_control = ctrl; only_mid = only_mid_control != 0; has_interp = interp; n_region_hints = n_regions;
             for (int i = 0; i < n_ctrl(); ++i) scales[i] = control_scales ? control_scales[i] : 1.f;
             prepared = false;
             // pass 1: dry run to size the arenas (pointers are offsets from null and never dereferenced)
@@ -2609,6 +2624,13 @@ struct mkd_ctx {
         return 0;
     }
 
+    // tests only: the cached ControlNet hint embedding [B, h, w, model_channels] bf16, copied out on `stream`
+    int debug_hint_embedding(bf16_t* out, hipStream_t stream) {
+        if (!prepared || !has_control) return mkd_fail(MKD_ERR_STATE, "mkd_debug_hint_embedding: no conditioning with a hint is prepared");
+        if (!out) return mkd_fail(MKD_ERR_ARG, "mkd_debug_hint_embedding: null pointer");
+        return launch_copy_strided(hint_emb.p, hint_emb.ld, out, hint_emb.C, hint_emb.B * hint_emb.H * hint_emb.W, hint_emb.C, stream);
+    }
+
     int64_t device_bytes() const {
         return weight_bytes + 3 * s_ring_n * (int64_t)sizeof(float) + (int64_t)varena_cap + (int64_t)earena_cap + (int64_t)carena_cap + (int64_t)persist_cap + (int64_t)gstat_cap + [&] { int64_t t = 0; for (int i = 0; i < NA; ++i) t += (int64_t)(temp_cap[i] + splitk_ws_bytes[i] + gn_ws_bytes[i]); return t; }();
     }
@@ -2731,6 +2753,30 @@ int mkd_prepare_interp(mkd_ctx* ctx, int batch, int h, int w, const float* hint_
     if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
     if (!hint_a || !hint_b || !alpha) return mkd_fail(MKD_ERR_ARG, "mkd_prepare_interp: null pointer");
     return ctx->prepare(batch, h, w, hint_a, context, control_scales, only_mid_control, (hipStream_t)stream, hint_b, alpha);
+}
+int mkd_prepare_regions(mkd_ctx* ctx, int batch, int h, int w, const float* const* hints, int n_hints, const float* weights,
+                        const float* context, const float* control_scales, int only_mid_control, void* stream) {
+    // (arguments first, the context last: nothing of it is touched, and nothing is enqueued, on a bad call)
+    if (n_hints < 1 || n_hints > 8) return mkd_fail(MKD_ERR_ARG, "mkd_prepare_regions: n_hints must be 1..8");
+    if (!hints || !weights || !context) return mkd_fail(MKD_ERR_ARG, "mkd_prepare_regions: null pointer");
+    for (int r = 0; r < n_hints; ++r)
+        if (!hints[r]) return mkd_fail(MKD_ERR_ARG, "mkd_prepare_regions: null hint");
+    if (batch <= 0 || h <= 0 || w <= 0) return mkd_fail(MKD_ERR_ARG, "mkd_prepare_regions: bad shape");
+    if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
+    return ctx->prepare(batch, h, w, hints[0], context, control_scales, only_mid_control, (hipStream_t)stream, nullptr, nullptr, hints, n_hints,
+                        weights);
+}
+int mkd_debug_hint_embedding(mkd_ctx* ctx, uint16_t* out_bf16, void* stream) {
+    return ctx ? ctx->debug_hint_embedding(out_bf16, (hipStream_t)stream) : mkd_fail(MKD_ERR_ARG, "null ctx");
+}
+int mkd_region_weights(const uint8_t* masks, int n_masks, int batch, int H, int W, int factor, int feather, const float* strength, float* out,
+                       void* stream) {
+    if (!masks || !out) return mkd_fail(MKD_ERR_ARG, "mkd_region_weights: null pointer");
+    return launch_region_weights(masks, n_masks, batch, H, W, factor, feather, strength, out, (hipStream_t)stream);
+}
+int mkd_region_blend_bf16(const uint16_t* const* e_ptrs, const float* weights, uint16_t* out, int batch, int hw, int C, int R, void* stream) {
+    if (!e_ptrs || !weights || !out) return mkd_fail(MKD_ERR_ARG, "mkd_region_blend_bf16: null pointer");
+    return launch_region_blend(e_ptrs, weights, out, batch, hw, C, R, (hipStream_t)stream);
 }
 int mkd_eps(mkd_ctx* ctx, const float* x, const int64_t* t, float* eps_out, void* stream) {
     if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");

@@ -301,3 +301,11 @@ int launch_clip_embed(const int32_t* tokens, const bf16_t* tok_emb, const bf16_t
                       int vocab, hipStream_t stream);
 int launch_bf16_to_f32(const bf16_t* x, float* y, int64_t n, hipStream_t stream);
 int launch_blend(const bf16_t* a, const bf16_t* b, const float* alpha, bf16_t* y, int64_t per_sample, int batch, hipStream_t stream);
+// ---- region-wise transfer from several references (kernels_region.hip) -----------------------------------------------------------
+// out[b, p, :] = sum_r weights[b, r, p] * e[r][b, p, :] over R <= 8 bf16 NHWC embeddings (e: HOST array of R device pointers), fp32 in the
+// order r = 0, 1, ... (product, then fused multiply-adds), one bf16 rounding; out may be e[0].  C % 8 == 0, 16-byte aligned pointers
+int launch_region_blend(const bf16_t* const* e, const float* weights, bf16_t* out, int batch, int hw, int C, int R, hipStream_t stream);
+// masks [K, B, H, W] uint8 (K = 1..7, a pixel belongs to the lowest k with a non-zero mask) -> out [B, K + 1, H/f, W/f] fp32: plane k + 1 =
+// strength[b, k] (null: 1) x the owned fraction of the (2 feather + 1)^2 block window (clamped at the edges), plane 0 = max(0, 1 - the others)
+int launch_region_weights(const uint8_t* masks, int n_masks, int batch, int H, int W, int f, int feather, const float* strength, float* out,
+                          hipStream_t stream);

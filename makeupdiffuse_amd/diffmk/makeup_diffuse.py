@@ -560,6 +560,70 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             out['samples'] = self.decode_first_stage(lat)
         return out
 
+    @torch.no_grad()
+    def transfer_regions(self, batch: dict, refs: Dict[str, str], strengths: Optional[dict] = None, base: str = 'ref', feather: int = 1,
+                         x_T: Optional[torch.Tensor] = None, unconditional_guidance_scale: float = 1.0) -> Dict[str, torch.Tensor]:
+        """Region-wise makeup transfer from several references (partial transfer as SCGAN / EleGANt / PSGAN offer it; the reference
+        has no code for it, so the definition is this build's): ``refs`` maps the user regions 'eye', 'lip', 'skin' to the
+        batch keys of their reference images; the ControlNet hint embeddings E(src||ref_r) are blended PER LATENT PIXEL with the
+        weights that regions.region_weights_from_seg takes from batch[seg_key] (priority eye > lip > skin, ``feather`` latent pixels
+        of box smoothing, ``strengths`` {region: a number or one per sample}, default 1).  Pixels of no region, and what a strength
+        below 1 leaves, follow the base hint: src||ref_img (base='ref') or src||src (base='source': towards no makeup).  Runs the
+        ``sampler`` attribute's solver for ddim_steps from x_T.  Returns samples_latent, weights [B, 1 + regions, h, w] (plane 0 the
+        base, then the regions in priority order) and, with a first-stage decoder, samples."""
+        from .. import regions as rg
+        regs = rg.ordered(refs)
+        if base not in ('ref', 'source'):
+            raise ValueError(f"base must be 'ref' or 'source', got {base!r}")
+        if not 0 <= int(feather) <= rg.MAX_FEATHER:
+            raise ValueError(f'feather must be 0..{rg.MAX_FEATHER} latent pixels, got {feather}')
+        if self.seg_key not in batch:
+            raise KeyError(f"transfer_regions: the batch has no label map under '{self.seg_key}'")
+        for r in regs:
+            if refs[r] not in batch:
+                raise KeyError(f"transfer_regions: the batch has no reference image under '{refs[r]}' (region '{r}')")
+        n = int(batch[self.src_img_key].shape[0])
+        rg.strength_rows(strengths, regs, n)                  # (validates before anything reaches the device)
+        eng = self._require_engine()
+        src = self.get_origin_img_input(batch, self.src_img_key)
+        base_img = src if base == 'source' else self.get_origin_img_input(batch, self.ref_img_key)
+        hints = [torch.cat((src, base_img), 1)] + [torch.cat((src, self.get_origin_img_input(batch, refs[r])), 1) for r in regs]
+        ctx = self.get_cond_txt_coding(batch)
+        h, w = src.shape[2] // 8, src.shape[3] // 8
+        seg = batch[self.seg_key]
+        seg = rg.ms.label_map(seg)
+        factor = seg.shape[-1] // w if w > 0 else 0
+        if factor < 1 or (seg.shape[-2], seg.shape[-1]) != (factor * h, factor * w):
+            raise ValueError(f'transfer_regions: label map {tuple(seg.shape[-2:])} is not a multiple of the latent {(h, w)}')
+        weights = rg.region_weights_from_seg(seg.to(self.device), regs, factor, int(feather), strengths)
+        if x_T is None:
+            x_T = torch.randn(n, self.channels, h, w, device=self.device)
+        x_T = x_T.to(self.device)
+        scale = float(unconditional_guidance_scale)
+        if scale != 1.0:          # [uncond; cond] with the SAME hints and weights in both halves (log_results: uc_cat = c_cat)
+            u = self.get_unconditional_conditioning(n)
+            eng.prepare_regions([torch.cat([t, t]) for t in hints], torch.cat([weights, weights]), torch.cat([u, ctx]),
+                                control_scales=self.control_scales, only_mid_control=self.only_mid_control)
+        else:
+            eng.prepare_regions(hints, weights, ctx, control_scales=self.control_scales, only_mid_control=self.only_mid_control)
+        self.reset_conditioning_cache()
+        sch = self.schedule
+        sch.make_ddim(self.ddim_steps, ddim_eta=0.0)
+        ts = [int(v) for v in sch.ddim_timesteps]
+        a, ap = [float(v) for v in sch.ddim_alphas], [float(v) for v in sch.ddim_alphas_prev]
+        if self.sampler == 'dpmpp':
+            lat = eng.sample_dpmpp(x_T, ts, a, ap, order=self.solver_order, lower_order_final=True, cfg_scale=scale,
+                                   use_graph=bool(self.sample_use_graph))
+        elif self.sampler == 'ddim':
+            lat = eng.sample(x_T, ts, a, ap, [float(v) for v in sch.ddim_sqrt_one_minus_alphas], cfg_scale=scale,
+                             use_graph=bool(self.sample_use_graph))
+        else:
+            raise ValueError(f"sampler must be 'ddim' or 'dpmpp', got {self.sampler!r}")
+        out = {'samples_latent': lat, 'weights': weights}
+        if self.has_first_stage:
+            out['samples'] = self.decode_first_stage(lat)
+        return out
+
     def test_step(self, batch: dict, batch_idx: int, x_T: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """reference diffusion_makeup.py:332-341.  x_T (not in the reference, which always draws fresh noise): fixed start
         noise for both sampling passes, so that runs can be compared."""

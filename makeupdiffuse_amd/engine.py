@@ -414,6 +414,71 @@ class MkdEngine:
         self._keep = [hint_t, ctx, hint2_t, alpha_t]
         self.batch, self.latent_hw = B, (h, w)
 
+    def prepare_regions(self, hints: Sequence[torch.Tensor], weights: torch.Tensor, context: torch.Tensor,
+                        control_scales: Optional[Sequence[float]] = None, only_mid_control: bool = False) -> None:
+        """Region-wise transfer from several references (include/mkd.h mkd_prepare_regions): ``hints`` R <= 8 tensors
+        [B,6,8h,8w] (src || ref_r, index 0 the base), ``weights`` fp32 [B,R,h,w]; the ControlNet sees sum_r weights[:, r] * E(hints[r])."""
+        hints = list(hints)
+        R = len(hints)
+        if not 1 <= R <= 8:
+            raise ValueError(f'prepare_regions takes 1..8 hints, got {R}')
+        B = context.shape[0]
+        ctx = _f32c(context, self.device)
+        if ctx.dim() != 3 or ctx.shape[1] != 77 or ctx.shape[2] != self.cfg.context_dim:
+            raise ValueError(f'context must be [B,77,{self.cfg.context_dim}], got {tuple(ctx.shape)}')
+        hs = [_f32c(t, self.device) for t in hints]
+        shp = tuple(hs[0].shape)
+        if len(shp) != 4 or shp[0] != B or shp[1] != self.cfg.hint_channels or shp[2] % 8 or shp[3] % 8 or any(tuple(t.shape) != shp for t in hs):
+            raise ValueError(f'every hint must be [B,{self.cfg.hint_channels},8h,8w] with equal shapes, got {[tuple(t.shape) for t in hs]}')
+        h, w = shp[2] // 8, shp[3] // 8
+        wt = _f32c(weights, self.device)
+        if tuple(wt.shape) != (B, R, h, w):
+            raise ValueError(f'weights must be [{B},{R},{h},{w}], got {tuple(wt.shape)}')
+        scales = None
+        if control_scales is not None:
+            if len(control_scales) != self.cfg.n_control:
+                raise ValueError(f'control_scales must have {self.cfg.n_control} entries')
+            scales = (C.c_float * len(control_scales))(*[float(s) for s in control_scales])
+        ptrs = (C.c_void_p * R)(*[t.data_ptr() for t in hs])
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mkd_prepare_regions(self._ctx, B, h, w, ptrs, R, C.c_void_p(wt.data_ptr()), C.c_void_p(ctx.data_ptr()),
+                                                    scales, int(bool(only_mid_control)), C.c_void_p(_stream())), 'mkd_prepare_regions')
+        self._keep = [hs, ctx, wt]
+        self.batch, self.latent_hw = B, (h, w)
+
+    def region_weights(self, masks: torch.Tensor, factor: int = 8, feather: int = 1, strength: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Region masks uint8 [K,B,H,W] (K = 1..7; a pixel belongs to the lowest k whose mask is non-zero) -> blend weights fp32
+        [B,K+1,H/factor,W/factor] on the device (include/mkd.h mkd_region_weights): plane k+1 = strength[b,k] x the owned fraction of the
+        (2 feather + 1)^2 block window, plane 0 = what is left of 1.  ``strength`` [B,K] or None (all ones)."""
+        if masks.dim() != 4 or masks.dtype != torch.uint8:
+            raise ValueError(f'masks must be uint8 [K,B,H,W], got {masks.dtype} {tuple(masks.shape)}')
+        K, B, H, W = masks.shape
+        if not 1 <= K <= 7:
+            raise ValueError(f'1..7 region masks, got {K}')
+        if not 1 <= int(factor) <= 64 or H % int(factor) or W % int(factor):
+            raise ValueError(f'masks {H}x{W} are not a multiple of factor {factor} (1..64)')
+        if not 0 <= int(feather) <= 4:
+            raise ValueError(f'feather must be 0..4 latent pixels, got {feather}')
+        m = masks.to(self.device).contiguous()
+        st = None
+        if strength is not None:
+            st = _f32c(strength, self.device)
+            if tuple(st.shape) != (B, K):
+                raise ValueError(f'strength must be [{B},{K}], got {tuple(st.shape)}')
+        out = torch.empty((B, K + 1, H // int(factor), W // int(factor)), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mkd_region_weights(C.c_void_p(m.data_ptr()), K, B, H, W, int(factor), int(feather), C.c_void_p(_ptr(st)),
+                                                   C.c_void_p(out.data_ptr()), C.c_void_p(_stream())), 'mkd_region_weights')
+        return out
+
+    def debug_hint_embedding(self) -> torch.Tensor:
+        """Tests only: the cached ControlNet hint embedding [B,h,w,model_channels] bf16 (see mkd_debug_hint_embedding)."""
+        out = torch.empty((self.batch, *self.latent_hw, self.cfg.model_channels), device=self.device, dtype=torch.bfloat16)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mkd_debug_hint_embedding(self._ctx, C.c_void_p(out.data_ptr()), C.c_void_p(_stream())),
+                       'mkd_debug_hint_embedding')
+        return out
+
     def eps(self, x: torch.Tensor, t: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One apply_model evaluation on the prepared conditioning. x [B,4,h,w] fp32, t [B] int64."""
         x = _f32c(x, self.device)

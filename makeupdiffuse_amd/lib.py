@@ -67,6 +67,10 @@ SIGNATURES = {
     'mkd_live_contexts': (_I, []),
     'mkd_prepare': (_I, [_P, _I, _I, _I, _P, _P, C.POINTER(_F), _I, _P]),
     'mkd_prepare_interp': (_I, [_P, _I, _I, _I, _P, _P, _P, _P, C.POINTER(_F), _I, _P]),
+    'mkd_prepare_regions': (_I, [_P, _I, _I, _I, C.POINTER(_P), _I, _P, _P, C.POINTER(_F), _I, _P]),
+    'mkd_region_weights': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    'mkd_region_blend_bf16': (_I, [C.POINTER(_P), _P, _P, _I, _I, _I, _I, _P]),
+    'mkd_debug_hint_embedding': (_I, [_P, _P, _P]),
     'mkd_eps': (_I, [_P, _P, _P, _P, _P]),
     'mkd_ddim_step': (_I, [_P, _P, _P, _F, _F, _F, _F, _F, _P, _F, _P, _P, _L, _P]),
     'mkd_sample': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _F, _P, _I, _P]),

@@ -79,7 +79,28 @@ def build_parser():
     ap.add_argument('--makeup-score', action='store_true', help='score every decoded sample against its makeup reference: per region '
                     '(lip, skin, eye_left, eye_right) the L1 distance to its histogram match, one row per pair in <out>/makeup_score.csv '
                     '(label maps nonmakeup_seg / makeup_seg from <data-root>/scgan_segs, synthetic ones otherwise)')
+    ap.add_argument('--region-refs', default=None, metavar='lip=NAME,eye=NAME,skin=NAME', help='region-wise transfer from several '
+                    'references: after the usual passes every pair is also sampled with the named regions following these images '
+                    '(names under <data-root>/images, the same for every pair; the rest of the face follows the pair\'s own reference) '
+                    'and a samples_regions grid is written; needs <data-root>/scgan_segs')
+    ap.add_argument('--region-strength', default=None, metavar='lip=0.7,...', help='strength per region of --region-refs (default 1)')
+    ap.add_argument('--region-feather', type=int, default=1, help='box smoothing of the region weights, 0..4 latent pixels')
     return ap
+
+
+def parse_region_map(text, cast=str):
+    """'lip=a.png,eye=b.png' -> {'lip': 'a.png', 'eye': 'b.png'} (values through ``cast``)"""
+    out = {}
+    for part in (text or '').split(','):
+        if not part.strip():
+            continue
+        if '=' not in part:
+            raise ValueError(f"expected region=value, got '{part}'")
+        k, v = part.split('=', 1)
+        if k.strip() in out:
+            raise ValueError(f"region '{k.strip()}' is given twice")
+        out[k.strip()] = cast(v.strip())
+    return out
 
 
 def write_makeup_scores(path, names, out, first):
@@ -97,6 +118,15 @@ def write_makeup_scores(path, names, out, first):
 def main():
     args = build_parser().parse_args()
 
+    region_refs = parse_region_map(args.region_refs)
+    region_strength = parse_region_map(args.region_strength, float) or None
+    if region_refs:
+        from makeupdiffuse_amd.regions import ordered
+        ordered(region_refs)                              # unknown region names fail here, before the model is built
+        if not args.data_root or not os.path.isdir(os.path.join(args.data_root, 'scgan_segs')):
+            raise SystemExit('--region-refs needs --data-root with images/ and scgan_segs/ (the label maps pick the regions)')
+    elif region_strength or args.region_feather != 1:
+        raise SystemExit('--region-strength / --region-feather only apply with --region-refs')
     rank, world, local = mdist.init_from_env()
     model = create_model(args.config).cpu()
     if args.fix_background:
@@ -134,6 +164,7 @@ def main():
     if args.txt_emb:
         t = load_state_dict(args.txt_emb)
         txt_emb = (next(iter(t.values())) if isinstance(t, dict) else t).float().reshape(1, 77, -1)
+    region_imgs = {r: dataset._load(name) for r, name in region_refs.items()}
     lo, hi = mdist.shard_range(args.pairs, rank, world)
     os.makedirs(args.out, exist_ok=True)
     model.on_test_epoch_start()
@@ -157,6 +188,15 @@ def main():
                              for i in range(b0, b1)]).cuda(local)
         out = model.test_step(batch, b0, x_T=x_T)
         model.on_test_batch_end(out, batch, b0)
+        if region_refs:
+            for r, img in region_imgs.items():
+                batch['region_ref_' + r] = img.unsqueeze(0).expand(b1 - b0, -1, -1, -1).contiguous()
+            reg = model.transfer_regions(batch, {r: 'region_ref_' + r for r in region_refs}, strengths=region_strength,
+                                         feather=args.region_feather, x_T=x_T)
+            out['samples_regions_latent'] = reg['samples_latent'].detach().cpu()
+            if 'samples' in reg:
+                out['samples_regions'] = torch.clamp(reg['samples'].detach().cpu(), -1.0, 1.0)
+                model.save_local({'samples_regions': out['samples_regions']}, b0)
         if args.makeup_score:
             write_makeup_scores(os.path.join(args.out, f'makeup_score_rank{rank}.csv' if world > 1 else 'makeup_score.csv'),
                                 batch.get('img_name') or [str(i) for i in range(b0, b1)], out, first=b0 == lo)
