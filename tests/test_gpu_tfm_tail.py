@@ -1,54 +1,26 @@
-"""-m gpu: the fused row-local transformer tail (csrc/kernels_tfm.hip) against a plain torch fp32 chain of the same ops
-(UPSTREAM cldm BasicTransformerBlock after the self-attention product + SpatialTransformer.proj_out; the two
-net calls it serves: /root/reference/diffmk/makeup_diffuse.py:164-168), called through the C ABI."""
+"""-m gpu: the fused row-local transformer tail and head (csrc/kernels_tfm.hip), called through the C ABI, per stage and per row.
+
+Three things are compared (tests/tfm_ref.py): the fused kernel, a float64 CPU reference that rounds to bf16 where the kernel stores
+bf16, and the same block as a chain of the single kernels the suite tests one by one (the yardstick).  Every test asserts, for every
+token row, err_fused <= 3 x err_unfused + 2e-3 (the rule of test_gemm_layernorm_on_the_fly_rows_with_mean_far_above_std), with
+err = ||out_r - ref_r|| / ||ref_r||; the tests on ordinary inputs with full random weights keep their global limits as well.
+The stage-isolating weight sets (fp32 weights, all values exact) make one stage the whole output:
+  X  to_out1 = 0, norm2 = (1, 0), to_q2 = to_out2 = proj_out = I, ff2 = 0, x_in = 0:  out = h0 + a2(LN(h0))
+  F  to_out1 = to_out2 = 0, proj_out = I, x_in = -h0:                                 out = ff2(GEGLU(ff0(LN3(h0))))
+(UPSTREAM cldm BasicTransformerBlock after the self-attention product + SpatialTransformer.proj_in / proj_out)"""
 import ctypes as C
-import math
 
 import pytest
 import torch
-import torch.nn.functional as F
 
+from tests import tfm_ref as R
 from tests.gpu_util import DEV, L, P, bf, rel_l2, sync
+from tests.tfm_ref import ORDER, block_weights, torch_chain      # noqa: F401  (tools/bench_tfm_tail.py imports them from here)
 from makeupdiffuse_amd import lib as mlib
 
 pytestmark = pytest.mark.gpu
 
-
-def block_weights(d, seed, norm_jitter=0.2):
-    g = torch.Generator().manual_seed(seed)
-    r = lambda *s: torch.randn(*s, generator=g)
-    w = {
-        'to_out1_w': r(d, d) / math.sqrt(d), 'to_out1_b': 0.1 * r(d),
-        'norm2_g': 1 + norm_jitter * r(d), 'norm2_b': norm_jitter * r(d),
-        'to_q2_w': r(d, d) / math.sqrt(d),
-        'to_out2_w': r(d, d) / math.sqrt(d), 'to_out2_b': 0.1 * r(d),
-        'norm3_g': 1 + norm_jitter * r(d), 'norm3_b': norm_jitter * r(d),
-        'ff0_w': r(8 * d, d) / math.sqrt(d), 'ff0_b': 0.1 * r(8 * d),
-        'ff2_w': r(d, 4 * d) / math.sqrt(4 * d), 'ff2_b': 0.1 * r(d),
-        'proj_out_w': r(d, d) / math.sqrt(d), 'proj_out_b': 0.1 * r(d),
-    }
-    return w
-
-
-ORDER = ['to_out1_w', 'to_out1_b', 'norm2_g', 'norm2_b', 'to_q2_w', 'to_out2_w', 'to_out2_b', 'norm3_g', 'norm3_b', 'ff0_w', 'ff0_b',
-         'ff2_w', 'ff2_b', 'proj_out_w', 'proj_out_b']
-
-
-def torch_chain(w, a1, h0, xin, kv, B, T, Tk, d, heads=8):
-    """fp32 reference on the bf16-rounded INPUTS (a1, h0, x_in, K | V); weights fp32 as given."""
-    dh = d // heads
-    h1 = a1 @ w['to_out1_w'].T + w['to_out1_b'] + h0
-    q = F.layer_norm(h1, (d,), w['norm2_g'], w['norm2_b'], 1e-5) @ w['to_q2_w'].T
-    k = kv[:, :d].reshape(B, Tk, heads, dh).permute(0, 2, 1, 3)
-    v = kv[:, d:].reshape(B, Tk, heads, dh).permute(0, 2, 1, 3)
-    qh = q.reshape(B, T, heads, dh).permute(0, 2, 1, 3)
-    att = torch.softmax(qh @ k.transpose(-1, -2) * dh ** -0.5, dim=-1) @ v
-    a2 = att.permute(0, 2, 1, 3).reshape(B * T, d)
-    h2 = a2 @ w['to_out2_w'].T + w['to_out2_b'] + h1
-    u = F.layer_norm(h2, (d,), w['norm3_g'], w['norm3_b'], 1e-5) @ w['ff0_w'].T + w['ff0_b']
-    gg = u[:, :4 * d] * F.gelu(u[:, 4 * d:])
-    h3 = gg @ w['ff2_w'].T + w['ff2_b'] + h2
-    return h3 @ w['proj_out_w'].T + w['proj_out_b'] + xin
+D = 320
 
 
 def make_handle(w, d):
@@ -59,18 +31,9 @@ def make_handle(w, d):
     return h
 
 
-@pytest.mark.parametrize('B,T,Tk,pad', [(1, 64, 77, 0), (2, 256, 77, 0), (3, 192, 77, 64), (2, 1024, 77, 0), (1, 128, 16, 0), (2, 64, 80, 8), (1, 320, 1, 0)])
-def test_tfm_tail_matches_the_torch_fp32_chain(B, T, Tk, pad):
-    d = 320
-    w = block_weights(d, seed=B * 1000 + T + Tk)
-    g = torch.Generator().manual_seed(7 + T)
-    M = B * T
-    ld = d + pad
-    # activations of the scale the block sees (h0 / x_in: O(1) residual streams with a per-channel offset; a1: attention output)
-    a1 = bf(torch.randn(M, ld, generator=g))
-    h0 = bf(torch.randn(M, ld, generator=g) + 0.5 * torch.randn(1, ld, generator=g))
-    xin = bf(torch.randn(M, ld, generator=g))
-    kv = bf(torch.randn(B * Tk, 2 * d, generator=g))
+def run_tail(w, a1, h0, xin, kv, B, T, Tk, d):
+    """bf16 device inputs [B*T, ld].  Two runs into NaN-filled outputs: bit-repeatable, nothing written outside the d columns."""
+    M, ld = a1.shape
     out = torch.full((M, ld), float('nan'), device=DEV, dtype=torch.bfloat16)
     h = make_handle(w, d)
     try:
@@ -84,21 +47,62 @@ def test_tfm_tail_matches_the_torch_fp32_chain(B, T, Tk, pad):
     finally:
         L().mkd_tfm_tail_destroy(h)
     assert torch.equal(first[:, :d].view(torch.int16), out[:, :d].view(torch.int16)), 'not bit-repeatable'
-    if pad:
+    if ld > d:
         assert torch.isnan(out[:, d:].float()).all(), 'wrote outside its columns'
-    ref = torch_chain(w, a1[:, :d].float().cpu(), h0[:, :d].float().cpu(), xin[:, :d].float().cpu(), kv.float().cpu(), B, T, Tk, d)
+    assert torch.isfinite(out[:, :d].float()).all()
+    return out
+
+
+def check_rows(what, got, unf, ref, d, cls=None, names=None):
+    """per row: fused <= 3 x unfused + 2e-3.  Prints the worst row (per row class when cls is given)."""
+    ef, eu = R.row_err(got, ref, d), R.row_err(unf, ref, d)
+    groups = [('all', torch.ones_like(ef, dtype=torch.bool))] if cls is None else [(names[c], cls == c) for c in sorted(set(cls.tolist()))]
+    for name, sel in groups:
+        i = int(torch.argmax(torch.where(sel, ef, -1.0)))
+        flag = '' if eu[sel].max() <= 2e-2 else '   [the unfused chain exceeds 2e-2 here]'
+        print(f'{what} rows {name}: fused worst {ef[i]:.3e} (row {i}, unfused there {eu[i]:.3e}), median {ef[sel].median():.3e}; '
+              f'unfused worst {eu[sel].max():.3e}, median {eu[sel].median():.3e}{flag}')
+    # measured on MI355X, worst row fused / unfused (the two agree to 3 digits on nearly every row: the bf16 rounding of the weights,
+    # which both share, is most of the distance to the fp32-weight reference; the unfused chain nowhere exceeds 2e-2):
+    #   full random weights 4.4e-3 - 5.1e-3 / the same (median 3.7e-3)
+    #   X every key designated 0 (Tk = 64: 3.2e-6) / the same;  X soft scores 1.8e-3, 1.6e-3 / the same;  X padded keys 0, 7.9e-4, 2.5e-5 / the same
+    #   F 4.5e-3 / 4.5e-3
+    #   S/F ordinary 4.6e-3 / 4.6e-3, offset 50 std 0.5: 4.3e-3 / 4.3e-3, offset 100 std 1: 4.3e-3 / 4.4e-3, offset -30 std 0.25: 4.3e-3 / 4.8e-3,
+    #       constant 7.0e-4 / 7.0e-4
+    #   S/X ordinary 2.2e-3 / 2.2e-3, offset 50: 5.6e-4 / 4.8e-4, offset 100: 4.0e-4 / 4.8e-4, offset -30: 5.7e-4 / 7.4e-4, constant 0 / 0
+    #   head h0 3.2e-3 - 3.5e-3 / the same (proj_in bias 30: 8.1e-4), q | k | v from x 4.3e-3 - 4.9e-3 / the same
+    bad = ef > 3.0 * eu + 2e-3
+    assert not bad.any(), f'{what}: {int(bad.sum())} rows over 3 x unfused + 2e-3, first {int(bad.nonzero()[0])}: {ef[bad][0]:.3e} vs {eu[bad][0]:.3e}'
+    return ef, eu
+
+
+def tail_three_ways(w, a1, h0, xin, kv, B, T, Tk, d):
+    a1, h0, xin, kv = bf(a1), bf(h0), bf(xin), bf(kv)
+    out = run_tail(w, a1, h0, xin, kv, B, T, Tk, d)
+    unf = R.tail_unfused(w, a1, a1.shape[1], h0, xin, kv, B, T, Tk, d)
+    ref = R.tail_ref(w, a1, h0, xin, kv, B, T, Tk, d)
+    return out, unf, ref
+
+
+@pytest.mark.parametrize('B,T,Tk,pad', [(1, 64, 77, 0), (2, 256, 77, 0), (3, 192, 77, 64), (2, 1024, 77, 0), (1, 128, 16, 0), (2, 64, 80, 8), (1, 320, 1, 0)])
+def test_tfm_tail_matches_the_torch_fp32_chain(B, T, Tk, pad):
+    d = D
+    w = block_weights(d, seed=B * 1000 + T + Tk)
+    a1, h0, xin, kv = R.random_inputs(B, T, Tk, d, pad, seed=7 + T)
+    out, unf, mref = tail_three_ways(w, a1, h0, xin, kv, B, T, Tk, d)
+    ref = torch_chain(w, a1[:, :d], h0[:, :d], xin[:, :d], kv, B, T, Tk, d)
     got = out[:, :d].float().cpu()
-    assert torch.isfinite(got).all()
     r = rel_l2(got, ref)
     mx = (got - ref).abs().max().item()
     print(f'tfm_tail B={B} T={T} Tk={Tk}: rel-L2 {r:.3e} max-abs {mx:.3e} (|ref|inf {ref.abs().max().item():.2f})')
     # five chained bf16 GEMMs with two LayerNorms between them: per-kernel budget 4e-3 each (SURVEY.md §8c); measured ~3e-3 for the chain
     assert r <= 8e-3, f'rel-L2 {r:.3e}'
     assert mx <= ref.abs().max().item() * 2 ** -4
+    check_rows(f'tfm_tail B={B} T={T} Tk={Tk}', out, unf, mref, d)
 
 
 def test_tfm_tail_rejects_shapes_it_does_not_cover():
-    d = 320
+    d = D
     w = block_weights(d, seed=1)
     h = make_handle(w, d)
     try:
@@ -115,38 +119,154 @@ def test_tfm_tail_rejects_shapes_it_does_not_cover():
         L().mkd_tfm_tail_destroy(h)
 
 
-@pytest.mark.parametrize('B,T,pad', [(1, 64, 0), (2, 1024, 0), (3, 256, 64), (2, 4096, 0)])
-def test_tfm_head_matches_the_torch_fp32_chain(B, T, pad):
-    """The head of the block as one kernel behind a GroupNorm statistics launch: GroupNorm(32, 1e-6) -> proj_in (1x1 conv = per-token
-    linear) -> LayerNorm 1 -> to_q | to_k | to_v (no bias), against torch fp32 on the bf16-rounded input."""
-    d = 320
-    g = torch.Generator().manual_seed(B * 100 + T)
-    r = lambda *s: torch.randn(*s, generator=g)
-    w = {'gn_g': 1 + 0.2 * r(d), 'gn_b': 0.2 * r(d), 'pi_w': r(d, d) / math.sqrt(d), 'pi_b': 0.1 * r(d), 'n1_g': 1 + 0.2 * r(d), 'n1_b': 0.2 * r(d),
-         'q_w': r(d, d) / math.sqrt(d), 'k_w': r(d, d) / math.sqrt(d), 'v_w': r(d, d) / math.sqrt(d)}
-    order = ['gn_g', 'gn_b', 'pi_w', 'pi_b', 'n1_g', 'n1_b', 'q_w', 'k_w', 'v_w']
-    dev = {k: w[k].to(DEV).float().contiguous() for k in order}
-    ld = d + pad
-    x = bf((r(B * T, ld) * (1 + 0.5 * r(1, ld)) + 0.3 * r(1, ld)))          # per-channel scale / offset: the group statistics matter
-    h0 = torch.full((B * T, d), float('nan'), device=DEV, dtype=torch.bfloat16)
-    qkv = torch.full((B * T, 3 * d), float('nan'), device=DEV, dtype=torch.bfloat16)
+# ---- set X: cross-attention alone ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('Tk,pad', [(1, 0), (15, 0), (16, 0), (17, 0), (31, 0), (32, 0), (33, 0), (64, 0), (65, 0), (77, 0), (79, 0), (80, 0), (77, 64)])
+def test_tfm_tail_cross_attention_alone_every_key_designated(Tk, pad):
+    """Every (token, head) puts >= 0.95 of its softmax weight on one key and every key 0 .. Tk-1 is some token's in every (sample,
+    head) (asserted in test_tfm_ref_host.py): a key dropped, shifted or taken from the other sample moves whole rows by tens of percent.
+    Tk on both sides of the 16-key fragment and 32-key P.V step boundaries; two workgroups per sample; V differs per sample."""
+    B, T, d = 2, 128, D
+    w = R.weights_x(d, seed=11)
+    a1, h0, xin, kv, _ = R.spiked_inputs(B, T, Tk, d, pad, seed=100 + Tk)
+    out, unf, ref = tail_three_ways(w, a1, h0, xin, kv, B, T, Tk, d)
+    check_rows(f'X spiked Tk={Tk} pad={pad}', out, unf, ref, d)
+
+
+@pytest.mark.parametrize('Tk', [77, 80])
+def test_tfm_tail_cross_attention_alone_soft_scores(Tk):
+    """K = 4 randn: scores with std ~ 4 over all the keys - where the softmax scale (and the exp2 / running-max arithmetic) shows."""
+    B, T, d = 2, 128, D
+    w = R.weights_x(d, seed=12)
+    a1, h0, xin, kv = R.soft_inputs(B, T, Tk, d, 0, seed=200 + Tk)
+    out, unf, ref = tail_three_ways(w, a1, h0, xin, kv, B, T, Tk, d)
+    check_rows(f'X soft Tk={Tk}', out, unf, ref, d)
+
+
+@pytest.mark.parametrize('Tk', [1, 17, 79])
+def test_tfm_tail_cross_attention_alone_padded_keys_would_win(Tk):
+    """norm2_b = 1, keys = -3 ones: every real score is ~ -19, the zero-padded keys of the packed context score 0.  Only the
+    `< Tk` mask keeps them out."""
+    B, T, d = 2, 128, D
+    w = R.weights_x(d, seed=13, norm2_b=1.0)
+    a1, h0, xin, kv = R.padding_inputs(B, T, Tk, d, 0, seed=300 + Tk)
+    out, unf, ref = tail_three_ways(w, a1, h0, xin, kv, B, T, Tk, d)
+    check_rows(f'X padding Tk={Tk}', out, unf, ref, d)
+
+
+# ---- set F: feed-forward alone; set S: LayerNorm statistics on hard rows ---------------------------------------------------------
+@pytest.mark.parametrize('pad', [0, 8])
+def test_tfm_tail_feed_forward_alone(pad):
+    """x_in = -h0 cancels the residual in the fp32 epilogue: LayerNorm 3 and all five GEGLU chunks at full strength."""
+    B, T, Tk, d = 2, 128, 77, D
+    w = R.weights_f(d, seed=14)
+    a1, h0, xin, kv = R.ff_inputs(B, T, Tk, d, pad, seed=400)
+    out, unf, ref = tail_three_ways(w, a1, h0, xin, kv, B, T, Tk, d)
+    check_rows(f'F pad={pad}', out, unf, ref, d)
+
+
+CLS_NAMES = ['ordinary'] + [f'offset {o:g} std {s:g}' for o, s in R.HARD_LEVELS] + ['constant']
+
+
+@pytest.mark.parametrize('which', ['F', 'X'])
+def test_tfm_tail_layernorm_statistics_on_hard_rows(which):
+    """The kernel takes var = E[x^2] - mean^2 from fp32 partials and applies rstd (acc - mean s) to accumulators of RAW rows.  Rows at
+    mean / std = 100 - 120 interleaved with ordinary rows in the same 16-token fragments, one fragment of constant rows; through
+    LayerNorm 3 with the feed-forward as the whole output (F), and through LayerNorm 2 into soft-score cross-attention (X: there
+    out = h0 + a2 keeps the row's offset, so the hard rows weigh a2 lightly - F is the sharp one)."""
+    B, T, Tk, d = 2, 128, 77, D
+    if which == 'F':
+        w = R.weights_f(d, seed=15)
+        a1, h0, xin, kv = R.ff_inputs(B, T, Tk, d, 0, seed=500, hard=True)
+        cls = R.hard_rows(B * T, d, 501)[1]
+    else:
+        w = R.weights_x(d, seed=16)
+        a1, h0, xin, kv = R.soft_inputs(B, T, Tk, d, 0, seed=600, hard=True)
+        cls = R.hard_rows(B * T, d, 601, zero_row=False)[1]
+    out, unf, ref = tail_three_ways(w, a1, h0, xin, kv, B, T, Tk, d)
+    check_rows(f'S/{which}', out, unf, ref, d, cls, CLS_NAMES)
+
+
+# ---- the head -------------------------------------------------------------------------------------------------------------------
+def run_head(w, x, B, T, d, eps=1e-6):
+    M, ld = x.shape
+    dev = {k: w[k].to(DEV).float().contiguous() for k in R.HEAD_ORDER}
+    h0 = torch.full((M, d), float('nan'), device=DEV, dtype=torch.bfloat16)
+    qkv = torch.full((M, 3 * d), float('nan'), device=DEV, dtype=torch.bfloat16)
     h = C.c_void_p()
-    mlib.check(L().mkd_tfm_head_create(d, *[P(dev[k]) for k in order], C.byref(h)), 'mkd_tfm_head_create')
+    mlib.check(L().mkd_tfm_head_create(d, *[P(dev[k]) for k in R.HEAD_ORDER], C.byref(h)), 'mkd_tfm_head_create')
     try:
-        mlib.check(L().mkd_tfm_head_run(h, P(x), ld, 1e-6, P(h0), P(qkv), B, T, None), 'run')
+        mlib.check(L().mkd_tfm_head_run(h, P(x), ld, eps, P(h0), P(qkv), B, T, None), 'run')
         sync()
         first = (h0.clone(), qkv.clone())
-        mlib.check(L().mkd_tfm_head_run(h, P(x), ld, 1e-6, P(h0), P(qkv), B, T, None), 'run')
+        mlib.check(L().mkd_tfm_head_run(h, P(x), ld, eps, P(h0), P(qkv), B, T, None), 'run')
         sync()
     finally:
         L().mkd_tfm_head_destroy(h)
     assert torch.equal(first[0].view(torch.int16), h0.view(torch.int16)) and torch.equal(first[1].view(torch.int16), qkv.view(torch.int16))
-    xf = x[:, :d].float().cpu().view(B, T, d).permute(0, 2, 1)                    # [B, C, T]
-    gn = F.group_norm(xf, 32, w['gn_g'], w['gn_b'], 1e-6).permute(0, 2, 1).reshape(B * T, d)
-    h0_ref = gn @ w['pi_w'].T + w['pi_b']
-    ln = F.layer_norm(h0_ref, (d,), w['n1_g'], w['n1_b'], 1e-5)
-    qkv_ref = torch.cat([ln @ w['q_w'].T, ln @ w['k_w'].T, ln @ w['v_w'].T], 1)
+    assert torch.isfinite(h0.float()).all() and torch.isfinite(qkv.float()).all()
+    return h0, qkv
+
+
+def head_three_ways(what, w, x, B, T, d, chain_rows=True):
+    """h0 per row from x; q | k | v per row from each path's OWN stored h0 (the second stage alone) and, chain_rows, from x."""
+    x = bf(x)
+    h0, qkv = run_head(w, x, B, T, d)
+    h0u, qkvu = R.head_unfused(w, x, x.shape[1], B, T, d)
+    h0r, qkvr = R.head_ref(w, x, B, T, d)
+    check_rows(f'{what} h0', h0, h0u, h0r, d)
+    # one comparison needs one reference: err(qkv | own h0) of the fused kernel against the same figure of the chain
+    ef = R.row_err(qkv, R.head_ref(w, None, B, T, d, h0=h0)[1])
+    eu = R.row_err(qkvu, R.head_ref(w, None, B, T, d, h0=h0u)[1])
+    i = int(ef.argmax())
+    print(f'{what} qkv from the stored h0: fused worst {ef[i]:.3e} (row {i}, unfused there {eu[i]:.3e}), unfused worst {eu.max():.3e}'
+          + ('' if eu.max() <= 2e-2 else '   [the unfused chain exceeds 2e-2 here]'))
+    # measured on MI355X: worst row 2.8e-3 - 3.1e-3 fused and unfused alike, every shape; proj_in bias 30: 2.94e-3 / 2.95e-3
+    bad = ef > 3.0 * eu + 2e-3
+    assert not bad.any(), f'{what}: qkv of {int(bad.sum())} rows over 3 x unfused + 2e-3, first {int(bad.nonzero()[0])}: {ef[bad][0]:.3e} vs {eu[bad][0]:.3e}'
+    if chain_rows:
+        check_rows(f'{what} qkv from x', qkv, qkvu, qkvr, 3 * d)
+    return h0, qkv, h0r, qkvr
+
+
+@pytest.mark.parametrize('B,T,pad', [(1, 64, 0), (2, 1024, 0), (3, 256, 64), (2, 4096, 0)])
+def test_tfm_head_matches_the_torch_fp32_chain(B, T, pad):
+    """The head of the block as one kernel behind a GroupNorm statistics launch: GroupNorm(32, 1e-6) -> proj_in (1x1 conv = per-token
+    linear) -> LayerNorm 1 -> to_q | to_k | to_v (no bias), against torch on the bf16-rounded input."""
+    d = D
+    g = torch.Generator().manual_seed(B * 100 + T)
+    w = R.head_weights(d, None, g=g)
+    r = lambda *s: torch.randn(*s, generator=g)
+    x = R.q16(r(B * T, d + pad) * (1 + 0.5 * r(1, d + pad)) + 0.3 * r(1, d + pad))          # per-channel scale / offset: the group statistics matter
+    h0, qkv, _, _ = head_three_ways(f'tfm_head B={B} T={T}', w, x, B, T, d)
+    h0_ref, qkv_ref = R.head_ref(w, x, B, T, d, mirror=False)
     r0, r1 = rel_l2(h0, h0_ref), rel_l2(qkv, qkv_ref)
     print(f'tfm_head B={B} T={T}: h0 rel-L2 {r0:.3e}, qkv rel-L2 {r1:.3e}')
-    assert torch.isfinite(h0.float()).all() and torch.isfinite(qkv.float()).all()
-    assert r0 <= 4e-3 and r1 <= 8e-3
+    assert r0 <= 4e-3 and r1 <= 8e-3          # measured on MI355X: 2.9e-3, 3.7e-3
+
+
+@pytest.mark.parametrize('T,pad', [(64, 0), (192, 0), (256, 0), (320, 0), (576, 0), (832, 0), (1024, 0), (320, 64)])
+def test_tfm_head_every_chunk_count_samples_with_their_own_statistics(T, pad):
+    """GroupNorm partials of 4, 12, 16, 20, 36, 52 and 64 row chunks per sample: the 16-slice reduction with a partly filled last
+    slice; three samples whose statistics differ by design (scale b + 1, offset b - 1), so a wrong sample index shows."""
+    B, d = 3, D
+    w = R.head_weights(d, seed=900 + T)
+    x = R.head_inputs(B, T, d, pad, seed=901 + T)
+    h0, qkv, h0r, qkvr = head_three_ways(f'head T={T} pad={pad}', w, x, B, T, d)
+    r0, r1 = rel_l2(h0, h0r), rel_l2(qkv, qkvr)
+    print(f'head T={T} pad={pad}: h0 rel-L2 {r0:.3e}, qkv rel-L2 {r1:.3e}')
+    assert r0 <= 4e-3 and r1 <= 8e-3          # measured on MI355X: 2.5e-3 - 2.6e-3, 3.7e-3
+
+
+@pytest.mark.parametrize('kind', ['group_mean_50_std', 'proj_in_bias_30'])
+def test_tfm_head_hard_statistics(kind):
+    """A GroupNorm group at mean / std ~ 50 (var = E[x^2] - mean^2 from fp32 partials), and proj_in.bias = 30: every LayerNorm-1 row
+    with a common offset of ~ 30 std.  There one bf16 step of h0 (0.125 - 0.25) is a visible fraction of the row's std, so q | k | v is
+    judged from each path's own stored h0 only; the chain from x would measure where a rounding of h0 fell."""
+    B, T, d = 3, 320, D
+    if kind == 'group_mean_50_std':
+        w = R.head_weights(d, seed=31)
+        x = R.head_inputs(B, T, d, 0, seed=32, hard_group=5)
+    else:
+        w = R.head_weights(d, seed=33, pi_b=30.0)
+        x = R.head_inputs(B, T, d, 0, seed=34)
+    head_three_ways(f'head {kind}', w, x, B, T, d, chain_rows=kind == 'group_mean_50_std')
