@@ -257,6 +257,22 @@ int mkd_sample_dpmpp(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, con
  * >= threshold, else 0.  H, W must be multiples of factor (1..64), else MKD_ERR_ARG. */
 int mkd_latent_mask_from_labels(const uint8_t* labels, int batch, int H, int W, uint64_t classes, int factor, float threshold,
                                 float* out, void* stream);
+/* Pixel-space background paste after the decode (reference Fixbackground.get_target, diffmk/makeup_teacher.py:254-262): image (the decoded
+ * sample) and src (the source, both fp32 [batch, channels, H, W] device, nominally [-1, 1]) -> out, per element with ONE correctly rounded
+ * fp32 operation per step, in this order (the reference's expression; nothing is contracted to an fma):
+ *   u = (s + 1) / 2;  v = (t + 1) / 2;  p = a u;  q = (1 - a) v;  r = p + q;  o = r 2 - 1;  out = min(max(o, -1), 1)
+ * with the keep weight a[b,y,x] (1 keeps the source) from exactly ONE of
+ *   labels: uint8 [batch, factor H, factor W] device, factor 1..8, `classes` the bit set of mkd_latent_mask_from_labels, feather rho 0..16
+ *     image pixels: cnt(y,x) = the label pixels of block (y,x) whose label is in the set; S = sum of cnt over the (2 rho + 1)^2 window,
+ *     indices clamped to the image edge; a = float(S) / float((2 rho + 1)^2 factor^2) -- the rule of mkd_region_weights at pixel
+ *     resolution.  rho = 0, factor = 1 is the reference's hard mask; rho > 0 is BUILD-DEFINED (the reference has no feather);
+ *   mask: fp32 [mask_batch, 1, H, W] device read as is, mask_batch in {1, batch} (1: broadcast); feather must be 0.
+ * alpha_out: [batch, 1, H, W] fp32 receives a, or NULL.  out may alias image.  No context; one launch, no scratch buffer, no atomics, no
+ * host sync, no allocation: the call only enqueues.  Inputs are finite (NaN behaviour is not specified).  MKD_ERR_ARG before anything
+ * is enqueued: both labels and mask or neither, a null image / src / out, factor outside 1..8, feather outside 0..16 or non-zero with a
+ * mask, mask_batch not in {1, batch}, channels outside 1..8, batch outside 1..65535, H or W < 1, H * W > 2^24. */
+int mkd_paste_background(const float* image, const float* src, const uint8_t* labels, uint64_t classes, int factor, int feather,
+                         const float* mask, int mask_batch, float* out, float* alpha_out, int batch, int channels, int H, int W, void* stream);
 
 /* ---- makeup score: region-wise histogram matching (reference diffmk/makeups.py:147-245, diffmk/histogram_matching.py:41-66) ---- */
 /* Region mask of a label map (get_msk_lip / get_msk_skin / get_msk_eye, makeups.py:179-230): labels [batch, H, W] uint8 device ->

@@ -2894,6 +2894,11 @@ int mkd_latent_mask_from_labels(const uint8_t* labels, int batch, int H, int W, 
         return mkd_fail(MKD_ERR_ARG, "mkd_latent_mask_from_labels: H, W must be positive multiples of factor (1..64)");
     return launch_latent_mask_from_labels(labels, batch, H, W, classes, factor, threshold, out, (hipStream_t)stream);
 }
+int mkd_paste_background(const float* image, const float* src, const uint8_t* labels, uint64_t classes, int factor, int feather, const float* mask,
+                         int mask_batch, float* out, float* alpha_out, int batch, int channels, int H, int W, void* stream) {
+    return launch_paste_background(image, src, labels, classes, factor, feather, mask, mask_batch, out, alpha_out, batch, channels, H, W,
+                                   (hipStream_t)stream);
+}
 int mkd_region_mask_from_labels(const uint8_t* labels, int batch, int H, int W, uint64_t classes, uint64_t box_classes, int margin,
                                 uint8_t* mask_out, int32_t* count_out, int32_t* box_out, void* stream) {
     if (!labels || !mask_out || !count_out) return mkd_fail(MKD_ERR_ARG, "mkd_region_mask_from_labels: null pointer");

@@ -309,3 +309,8 @@ int launch_region_blend(const bf16_t* const* e, const float* weights, bf16_t* ou
 // strength[b, k] (null: 1) x the owned fraction of the (2 feather + 1)^2 block window (clamped at the edges), plane 0 = max(0, 1 - the others)
 int launch_region_weights(const uint8_t* masks, int n_masks, int batch, int H, int W, int f, int feather, const float* strength, float* out,
                           hipStream_t stream);
+// pixel-space background paste after the decode: out = clamp((a (src + 1) / 2 + (1 - a) (image + 1) / 2) 2 - 1) over fp32 [batch, channels, H, W];
+// a from labels [batch, f H, f W] (class fraction of the (2 feather + 1)^2 window of f x f blocks, clamped at the edges) or from mask
+// [mask_batch, 1, H, W] as is (exactly one of the two); alpha_out [batch, 1, H, W] or null; out may be image.  One launch
+int launch_paste_background(const float* image, const float* src, const uint8_t* labels, uint64_t classes, int f, int feather, const float* mask,
+                            int mask_batch, float* out, float* alpha_out, int batch, int channels, int H, int W, hipStream_t stream);

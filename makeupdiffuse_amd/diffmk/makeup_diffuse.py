@@ -416,7 +416,9 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                  unconditional_guidance_scale: float = 9, ddim_steps: int = 50, ddim_eta: float = 0.0, sample: bool = True,
                  fix_background: bool = False, background_classes: Sequence[int] = (0, 11, 12), background_threshold: float = 0.5,
                  seg_key: str = 'nonmakeup_seg', makeup_score: bool = False, ref_seg_key: str = 'makeup_seg', sampler: str = 'ddim',
-                 solver_order: int = 2, *args, **kwargs):
+                 solver_order: int = 2, paste_background: bool = False, paste_feather: int = 0, *args, **kwargs):
+        if not 0 <= int(paste_feather) <= 16:
+            raise ValueError(f'paste_feather must be 0..16 image pixels, got {paste_feather}')
         if sampler not in ('ddim', 'dpmpp'):
             raise ValueError(f"sampler must be 'ddim' or 'dpmpp', got {sampler!r}")
         if solver_order not in (1, 2, 3):
@@ -433,6 +435,11 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         self.background_classes = tuple(int(c) for c in background_classes)
         self.background_threshold = float(background_threshold)
         self.seg_key = seg_key
+        # pixel-space paste after the decode (reference Fixbackground.get_target): every decoded sample keeps the SOURCE's pixels over
+        # background_classes of batch[seg_key], mixed over paste_feather image pixels on both sides of the boundary (0: the reference's hard
+        # mask).  Independent of fix_background (needs neither the encoder nor masked sampling); off: log_results is unchanged
+        self.paste_background = bool(paste_background)
+        self.paste_feather = int(paste_feather)
         self.unconditional_guidance_scale = unconditional_guidance_scale
         self.ddim_steps, self.ddim_eta, self.sample = ddim_steps, ddim_eta, sample
         self.saved_dir, self.model_name, self.img_name_key = saved_dir, model_name, img_name_key
@@ -475,6 +482,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             x0, mask = self.background_latents(batch, c['src_img'])
             extra.update(x0=x0, mask=mask)
             log['mask_latent'] = mask
+        if self.paste_background:
+            self._check_paste(batch, 'paste_background')
         cond = {'c_concat': [c_cat], 'c_crossattn': [c_txt]}
         if self.sample:
             samples, _ = self.sample_log(cond=cond, batch_size=b, ddim=use_ddim, ddim_steps=self.ddim_steps,
@@ -482,6 +491,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             log['samples_latent'] = samples
             if self.has_first_stage:
                 log['samples'] = self.decode_first_stage(samples)
+                if self.paste_background:
+                    log['samples'], log['mask_pixel'] = self.paste_source(batch, log['samples'], log['control_src'])
                 if self.makeup_score:
                     log['makeup_hist'] = self.makeup_hist(batch, log['samples'], c['ref_img'])
         if self.unconditional_guidance_scale > 1.0:
@@ -493,6 +504,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             log[name + '_latent'] = samples_cfg
             if self.has_first_stage:
                 log[name] = self.decode_first_stage(samples_cfg)
+                if self.paste_background:
+                    log[name], log['mask_pixel'] = self.paste_source(batch, log[name], log['control_src'])
                 if self.makeup_score:
                     log[f'makeup_hist_cfg_scale_{self.unconditional_guidance_scale:.2f}'] = self.makeup_hist(batch, log[name], c['ref_img'])
         return log
@@ -507,6 +520,21 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                 raise KeyError(f"makeup_score: the batch has no label map under '{k}'")
         img = ((sample.float() + 1.0) / 2.0).clamp(0, 1)
         return ms.transfer_score(img, ref, batch[self.seg_key], batch[self.ref_seg_key])
+
+    def _check_paste(self, batch: dict, what: str) -> None:
+        """what a pixel-space paste needs, checked before anything is sampled"""
+        if not self.has_first_stage:
+            raise ValueError(f'{what} pastes decoded images: it needs a first stage (first_stage_config)')
+        if self.seg_key not in batch:
+            raise KeyError(f"{what}: the batch has no label map under '{self.seg_key}'")
+
+    @torch.no_grad()
+    def paste_source(self, batch: dict, image: torch.Tensor, src: torch.Tensor):
+        """paste_background: (the decoded ``image`` with the pixels of ``src`` ([-1, 1]) over background_classes of batch[seg_key], feathered
+        by paste_feather; the keep weights [B,1,H,W]) -- one mkd_paste_background launch"""
+        self._check_paste(batch, 'paste_background')
+        return self._require_engine().paste_background(image, src, seg=batch[self.seg_key], classes=self.background_classes,
+                                                       feather=self.paste_feather, return_alpha=True)
 
     @torch.no_grad()
     def background_latents(self, batch: dict, src: torch.Tensor):
@@ -544,6 +572,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         if x_T is None:
             x_T = torch.randn(n, self.channels, h, w, device=self.device)
         x_T = rep(x_T.to(self.device))           # the same start noise for every alpha of a pair
+        if self.paste_background:
+            self._check_paste(batch, 'paste_background')
         sch = self.schedule
         sch.make_ddim(self.ddim_steps, ddim_eta=0.0)
         if unconditional_guidance_scale != 1.0:
@@ -558,11 +588,16 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         out = {'samples_latent': lat, 'alpha': al}
         if self.has_first_stage:
             out['samples'] = self.decode_first_stage(lat)
+            if self.paste_background:          # every alpha of a pair keeps that pair's source
+                out['samples'], out['mask_pixel'] = self._require_engine().paste_background(
+                    out['samples'], rep(src) * 2.0 - 1.0, seg=rep(batch[self.seg_key].to(self.device)), classes=self.background_classes,
+                    feather=self.paste_feather, return_alpha=True)
         return out
 
     @torch.no_grad()
     def transfer_regions(self, batch: dict, refs: Dict[str, str], strengths: Optional[dict] = None, base: str = 'ref', feather: int = 1,
-                         x_T: Optional[torch.Tensor] = None, unconditional_guidance_scale: float = 1.0) -> Dict[str, torch.Tensor]:
+                         x_T: Optional[torch.Tensor] = None, unconditional_guidance_scale: float = 1.0,
+                         paste_outside: bool = False) -> Dict[str, torch.Tensor]:
         """Region-wise makeup transfer from several references (partial transfer as SCGAN / EleGANt / PSGAN offer it; the reference
         has no code for it, so the definition is this build's): ``refs`` maps the user regions 'eye', 'lip', 'skin' to the
         batch keys of their reference images; the ControlNet hint embeddings E(src||ref_r) are blended PER LATENT PIXEL with the
@@ -570,15 +605,22 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         of box smoothing, ``strengths`` {region: a number or one per sample}, default 1).  Pixels of no region, and what a strength
         below 1 leaves, follow the base hint: src||ref_img (base='ref') or src||src (base='source': towards no makeup).  Runs the
         ``sampler`` attribute's solver for ddim_steps from x_T.  Returns samples_latent, weights [B, 1 + regions, h, w] (plane 0 the
-        base, then the regions in priority order) and, with a first-stage decoder, samples."""
+        base, then the regions in priority order) and, with a first-stage decoder, samples.  With the paste_background option the samples
+        keep the source's pixels over background_classes (mask_pixel holds the weights); ``paste_outside`` (base='source' only) then also
+        pastes the source over everything that belongs to NONE of the chosen regions, feathered by paste_feather (weights: mask_outside),
+        so that "lips only" leaves the rest of the face alone."""
         from .. import regions as rg
         regs = rg.ordered(refs)
         if base not in ('ref', 'source'):
             raise ValueError(f"base must be 'ref' or 'source', got {base!r}")
+        if paste_outside and base != 'source':
+            raise ValueError("paste_outside keeps the source outside the chosen regions: it needs base='source'")
         if not 0 <= int(feather) <= rg.MAX_FEATHER:
             raise ValueError(f'feather must be 0..{rg.MAX_FEATHER} latent pixels, got {feather}')
         if self.seg_key not in batch:
             raise KeyError(f"transfer_regions: the batch has no label map under '{self.seg_key}'")
+        if paste_outside or self.paste_background:
+            self._check_paste(batch, 'paste_outside' if paste_outside else 'paste_background')
         for r in regs:
             if refs[r] not in batch:
                 raise KeyError(f"transfer_regions: the batch has no reference image under '{refs[r]}' (region '{r}')")
@@ -622,6 +664,12 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         out = {'samples_latent': lat, 'weights': weights}
         if self.has_first_stage:
             out['samples'] = self.decode_first_stage(lat)
+            if self.paste_background:
+                out['samples'], out['mask_pixel'] = self.paste_source(batch, out['samples'], src * 2.0 - 1.0)
+            if paste_outside:                  # a 0/1 map is itself a label map: the same launch with classes = (1,)
+                keep = 1 - rg.user_region_masks(seg.to(self.device), regs).amax(0)
+                out['samples'], out['mask_outside'] = eng.paste_background(out['samples'], src * 2.0 - 1.0, seg=keep, classes=(1,),
+                                                                           feather=self.paste_feather, return_alpha=True)
         return out
 
     def test_step(self, batch: dict, batch_idx: int, x_T: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
@@ -642,10 +690,11 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         reference's nrow = number of log entries is kept).  Latents (4 channels) are not images and are skipped."""
         from ..imageio import save_grid_png
         root = os.path.join(self.saved_dir, self.model_name)
-        nrow = len([k for k in images if not k.startswith('makeup_hist')])       # (the scores are not log rows: the grids keep their layout)
+        # (the scores and the paste weights are not log rows: the grids keep their layout, the PNG names stay the usual ones)
+        nrow = len([k for k in images if not k.startswith('makeup_hist') and k != 'mask_pixel'])
         written = []
         for k, v in images.items():
-            if not isinstance(v, torch.Tensor) or v.dim() != 4 or v.shape[1] not in (1, 3):
+            if not isinstance(v, torch.Tensor) or v.dim() != 4 or v.shape[1] not in (1, 3) or k == 'mask_pixel':
                 continue
             written.append(save_grid_png(v, os.path.join(root, '{}_{:04}.png'.format(k, batch_idx)), nrow, self.rescale))
         return written

@@ -692,6 +692,60 @@ class MkdEngine:
                        'mkd_latent_mask_from_labels')
         return out
 
+    def paste_background(self, image: torch.Tensor, src: torch.Tensor, seg: Optional[torch.Tensor] = None,
+                         classes: Iterable[int] = (0, 11, 12), feather: int = 0, mask: Optional[torch.Tensor] = None,
+                         return_alpha: bool = False):
+        """Pixel-space background paste after the decode (include/mkd.h mkd_paste_background): ``image`` (the decoded sample) and ``src``
+        (the source), fp32 [B,C,H,W] in [-1, 1] -> clamp((a (src + 1) / 2 + (1 - a) (image + 1) / 2) 2 - 1), the reference's
+        Fixbackground.get_target.  The keep weight a comes from exactly one of ``seg`` (label map [B,fH,fW] or [B,1,fH,fW], f = 1..8
+        derived from the shapes: the fraction of ``classes`` in the (2 feather + 1)^2 pixel window, feather 0..16) and ``mask`` (fp32
+        [1|B,1,H,W], read as is).  Returns the pasted image, with ``return_alpha`` also a as [B,1,H,W]."""
+        if (seg is None) == (mask is None):
+            raise ValueError('paste_background needs exactly one of seg and mask')
+        if image.dim() != 4 or tuple(src.shape) != tuple(image.shape):
+            raise ValueError(f'image and src must be equal [B,C,H,W] tensors, got {tuple(image.shape)} and {tuple(src.shape)}')
+        B, Cn, H, W = (int(v) for v in image.shape)
+        if not 1 <= Cn <= 8 or not 1 <= B <= 65535 or H < 1 or W < 1 or H * W > 1 << 24:
+            raise ValueError(f'paste_background: batch 1..65535, channels 1..8, H * W <= 2^24, got {tuple(image.shape)}')
+        rho = int(feather)
+        if not 0 <= rho <= 16:
+            raise ValueError(f'feather must be 0..16 image pixels, got {feather}')
+        lab = mk = None
+        bits, factor, mb = 0, 1, 1
+        if seg is not None:
+            if seg.dim() == 4 and seg.shape[1] == 1:
+                seg = seg[:, 0]
+            if seg.dim() != 3:
+                raise ValueError(f'seg must be [B,H,W] or [B,1,H,W], got {tuple(seg.shape)}')
+            if seg.dtype != torch.uint8:
+                if seg.is_floating_point() or int(seg.min()) < 0 or int(seg.max()) > 255:
+                    raise ValueError('seg must hold integer labels 0..255')
+                seg = seg.to(torch.uint8)
+            for c in classes:
+                if not 0 <= int(c) < 64:
+                    raise ValueError(f'class {c} outside 0..63')
+                bits |= 1 << int(c)
+            factor = int(seg.shape[-1]) // W
+            if seg.shape[0] != B or not 1 <= factor <= 8 or (int(seg.shape[-2]), int(seg.shape[-1])) != (factor * H, factor * W):
+                raise ValueError(f'seg {tuple(seg.shape)} is not [B = {B}] label maps at an integer multiple 1..8 of the image {H}x{W}')
+            lab = seg.to(self.device).contiguous()
+        else:
+            if rho:
+                raise ValueError('feather applies to a label map only: a mask is read as is')
+            if mask.dim() != 4 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (1, H, W):
+                raise ValueError(f'mask must be [1 or {B}, 1, {H}, {W}], got {tuple(mask.shape)}')
+            mk = _f32c(mask, self.device)
+            mb = int(mk.shape[0])
+        image = _f32c(image, self.device)
+        src = _f32c(src, self.device)
+        out = torch.empty_like(image)
+        alpha = torch.empty((B, 1, H, W), device=self.device, dtype=torch.float32) if return_alpha else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mkd_paste_background(C.c_void_p(image.data_ptr()), C.c_void_p(src.data_ptr()), C.c_void_p(_ptr(lab)),
+                                                     C.c_uint64(bits), factor, rho, C.c_void_p(_ptr(mk)), mb, C.c_void_p(out.data_ptr()),
+                                                     C.c_void_p(_ptr(alpha)), B, Cn, H, W, C.c_void_p(_stream())), 'mkd_paste_background')
+        return (out, alpha) if return_alpha else out
+
     def eps_profile(self, x: torch.Tensor, t: torch.Tensor, csv_path: Optional[str] = None) -> Dict[str, Dict[str, float]]:
         """One eps with HIP events around every launch group -> {kernel class: {ms, flops, launches, bytes, ms_b2b}}: ``bytes`` =
         algorithmic HBM bytes of the memory-bound classes, ``ms_b2b`` = the class's launches replayed back to back between one

@@ -82,6 +82,7 @@ SIGNATURES = {
     'mkd_dpmpp_step': (_I, [_P, _P, _P, _F, C.POINTER(_F), _P, _P, _P, _P, _L, _P]),
     'mkd_sample_dpmpp': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), _I, _I, C.POINTER(SampleMaskC), _F, _P, _I, _P]),
     'mkd_latent_mask_from_labels': (_I, [_P, _I, _I, _I, C.c_uint64, _I, _F, _P, _P]),
+    'mkd_paste_background': (_I, [_P, _P, _P, C.c_uint64, _I, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
     'mkd_region_mask_from_labels': (_I, [_P, _I, _I, _I, C.c_uint64, C.c_uint64, _I, _P, _P, _P, _P]),
     'mkd_hist_match_scratch_bytes': (C.c_size_t, [_I]),
     'mkd_hist_match_launches': (_I, [_I, _I]),

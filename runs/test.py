@@ -85,6 +85,15 @@ def build_parser():
                     'and a samples_regions grid is written; needs <data-root>/scgan_segs')
     ap.add_argument('--region-strength', default=None, metavar='lip=0.7,...', help='strength per region of --region-refs (default 1)')
     ap.add_argument('--region-feather', type=int, default=1, help='box smoothing of the region weights, 0..4 latent pixels')
+    ap.add_argument('--region-base', choices=('ref', 'source'), default='ref', help="what the rest of the face follows with --region-refs: "
+                    "the pair's own reference, or the source itself (towards no makeup)")
+    ap.add_argument('--region-paste-outside', action='store_true', help='with --region-refs and --region-base source: every pixel outside '
+                    'the chosen regions keeps the source pixels (pasted after the decode, feathered by --paste-feather)')
+    ap.add_argument('--paste-background', action='store_true', help="paste the source's pixels over background, teeth and hair into every "
+                    'decoded sample (pixel space, after the decode; label map nonmakeup_seg from <data-root>/scgan_segs, a synthetic one '
+                    'otherwise).  Independent of --fix-background; the two combine')
+    ap.add_argument('--paste-feather', type=int, default=0, help='mix source and sample over this many image pixels on both sides of the '
+                    'paste boundary, 0..16 (0: the hard mask of the reference)')
     return ap
 
 
@@ -125,8 +134,14 @@ def main():
         ordered(region_refs)                              # unknown region names fail here, before the model is built
         if not args.data_root or not os.path.isdir(os.path.join(args.data_root, 'scgan_segs')):
             raise SystemExit('--region-refs needs --data-root with images/ and scgan_segs/ (the label maps pick the regions)')
-    elif region_strength or args.region_feather != 1:
-        raise SystemExit('--region-strength / --region-feather only apply with --region-refs')
+    elif region_strength or args.region_feather != 1 or args.region_base != 'ref' or args.region_paste_outside:
+        raise SystemExit('--region-strength / --region-feather / --region-base / --region-paste-outside only apply with --region-refs')
+    if args.region_paste_outside and args.region_base != 'source':
+        raise SystemExit('--region-paste-outside needs --region-base source')
+    if not 0 <= args.paste_feather <= 16:
+        raise SystemExit('--paste-feather must be 0..16 image pixels')
+    if args.paste_feather and not (args.paste_background or args.region_paste_outside):
+        raise SystemExit('--paste-feather only applies with --paste-background or --region-paste-outside')
     rank, world, local = mdist.init_from_env()
     model = create_model(args.config).cpu()
     if args.fix_background:
@@ -135,6 +150,7 @@ def main():
         model.fix_background = True
     if args.makeup_score:
         model.makeup_score = True
+    model.paste_background, model.paste_feather = args.paste_background, args.paste_feather
     if args.ddim_steps is not None:
         model.ddim_steps = args.ddim_steps
     model.sampler, model.solver_order = args.sampler, args.solver_order
@@ -177,7 +193,7 @@ def main():
                 e = txt_emb if txt_emb is not None else torch.randn(1, 77, model.net_config.context_dim, generator=g)
                 batch['txt_emb'] = e.expand(b1 - b0, -1, -1).contiguous()
         else:
-            batch = synthetic_batch(b0, b1, args.res, model.net_config.context_dim, with_seg=args.fix_background,
+            batch = synthetic_batch(b0, b1, args.res, model.net_config.context_dim, with_seg=args.fix_background or args.paste_background,
                                     with_makeup_seg=args.makeup_score)
             if use_clip:
                 del batch['txt_emb']          # 'txt' -> tokenizer -> mkd_clip_encode
@@ -192,7 +208,8 @@ def main():
             for r, img in region_imgs.items():
                 batch['region_ref_' + r] = img.unsqueeze(0).expand(b1 - b0, -1, -1, -1).contiguous()
             reg = model.transfer_regions(batch, {r: 'region_ref_' + r for r in region_refs}, strengths=region_strength,
-                                         feather=args.region_feather, x_T=x_T)
+                                         feather=args.region_feather, x_T=x_T, base=args.region_base,
+                                         paste_outside=args.region_paste_outside)
             out['samples_regions_latent'] = reg['samples_latent'].detach().cpu()
             if 'samples' in reg:
                 out['samples_regions'] = torch.clamp(reg['samples'].detach().cpu(), -1.0, 1.0)
