@@ -302,6 +302,57 @@ int mkd_hist_match_launches(int want_matched, int want_loss);
 int mkd_hist_match(const float* dst, const float* ref, const uint8_t* mask_dst, const uint8_t* mask_ref, const int32_t* index,
                    int n, int H, int W, float* matched, uint8_t* tables, float* loss, int32_t* counts, void* scratch, void* stream);
 
+/* ---- full-resolution photos: crop-resize in, detail-keeping paste out (reference diffdata/preprocessing.py:131-169 crops the face and
+ * resizes it to the network size; the paste back is BUILD-DEFINED after the Laplacian detail transfer of PSGAN / EleGANt) ---- */
+/* One photo of a batch: interleaved RGB uint8 rows on the device, `pitch_bytes` apart (>= 3 W; NO alignment of pixels or of the pitch
+ * is assumed), and the box [x0, x0 + bw) x [y0, y0 + bh) inside it.  labels: uint8 [H][W] contiguous, or NULL.  The HOST array of at
+ * most MKD_PHOTO_MAX_BATCH descriptors is copied into the kernel argument block by value; photos of one batch may differ in size.
+ * Limits (else MKD_ERR_ARG before anything is enqueued): 1 <= n <= 16, 8 <= S <= 1024, 1 <= H, W <= 16384, pitch_bytes >= 3 W,
+ * bw, bh >= 1, the box inside the photo, bw, bh <= 32 S, pixels not NULL. */
+#define MKD_PHOTO_MAX_BATCH 16
+#define MKD_PHOTO_MAX_FEATHER 64
+typedef struct mkd_photo_desc {
+    const uint8_t* pixels;
+    int32_t pitch_bytes;
+    int32_t H, W;
+    int32_t x0, y0, bw, bh;
+    const uint8_t* labels;
+} mkd_photo_desc;
+/* Bytes of device scratch mkd_crop_resize needs for these descriptors (0 for bad arguments): per photo the horizontally resized
+ * rows the vertical pass reads, uint8 [rows][S][3] with rows <= bh + 2 ceil(max(bh / S, 1)) + 2 (the vertical filter reaches up to
+ * its support beyond the box, as the horizontal one does), each slab rounded up to 256 bytes.  The scratch must be 256-byte aligned;
+ * its contents before the call do not matter and it may be reused by the next call on the same stream. */
+size_t mkd_crop_resize_scratch_bytes(const mkd_photo_desc* descs, int n, int S);
+/* Photo box -> S x S with the BYTES of PIL's Image.resize((S, S), Image.BILINEAR, box=(x0, y0, x0 + bw, y0 + bh)) (Pillow's
+ * antialiased two-pass integer resampler).  Per axis (input length N, box [in0, in0 + len), output S), in IEEE double, nothing
+ * contracted: scale = len / S; fs = max(scale, 1); support = fs; for output index xx: center = in0 + (xx + 0.5) scale;
+ * xmin = max(0, (int)(center - support + 0.5)); xmax = min(N, (int)(center + support + 0.5)); for x in xmin .. xmax - 1:
+ * w = 1 - |(x - center + 0.5) (1 / fs)| when that absolute value is < 1, else 0; ww = their sum in index order; k = w / ww; integer
+ * coefficient (int)(0.5 + k 2^22).  Horizontal pass first (over the photo rows the vertical pass reads), then vertical; every output
+ * value is clip((2^21 + sum pixel * coef) >> 22, 0, 255) in 32-bit integers and the intermediate between the passes is uint8.  Both
+ * passes always run (at scale 1 with an integer box the coefficients are exactly (1, 0): the same bytes as Pillow's skipped pass).
+ * Outputs: img01 fp32 [n, 3, S, S] = float(u8) / 255.0f (one division); u8_out uint8 [n, S, S, 3] or NULL; labels_out uint8 [n, S, S]
+ * or NULL (then every descriptor needs labels): labels_out[y][x] = labels[y0 + ((2 y + 1) bh) / (2 S)][x0 + ((2 x + 1) bw) / (2 S)],
+ * integer division, no interpolation between classes (BUILD-DEFINED; not Pillow's NEAREST).  img01 and u8_out not both NULL.
+ * No context; two launches, no allocation, no host sync, no atomics. */
+int mkd_crop_resize(const mkd_photo_desc* descs, int n, int S, float* img01, uint8_t* u8_out, uint8_t* labels_out, void* scratch,
+                    void* stream);
+/* Debug export of the coefficient table of ONE axis (the device function both passes of mkd_crop_resize run): bounds_out int32
+ * [S][2] = (xmin, xmax), coef_out int32 [S][ksize] with ksize = 2 ceil(max(len / S, 1)) + 1, entries past xmax - xmin zero.
+ * 1 <= N <= 16384, the box inside, len <= 32 S, 8 <= S <= 1024, else MKD_ERR_ARG. */
+int mkd_resize_coeffs(int N, int in0, int len, int S, int32_t* bounds_out, int32_t* coef_out, void* stream);
+/* The decoded sample back into the photo, IN PLACE, keeping the photo's fine detail (BUILD-DEFINED): t fp32 [n, 3, S, S] the decoded
+ * sample (nominally [-1, 1]), s01 fp32 [n, 3, S, S] the img01 the model saw, the descriptors of mkd_crop_resize (labels unused);
+ * pixels is read and WRITTEN inside the box only, every byte outside stays.  feather rho: 0..64 photo pixels.  Every line ONE correctly
+ * rounded fp32 operation, nothing contracted.  At model resolution r = (t + 1) 0.5; d = (r - s01) 255.  Per photo pixel and axis, with
+ * j = X - x0: num = (2 j + 1) S - bw; den = 2 bw; i0 = floor(num / den); rem = num - i0 den; w = float(rem) / float(den); neighbours
+ * clamp(i0, 0, S - 1) and clamp(i0 + 1, 0, S - 1) (half-pixel centres, clamped to the edge).  top = d00 + wx (d01 - d00); bot likewise;
+ * u = top + wy (bot - top).  e = distance in pixels to the nearest box side that does not lie on the photo's border (no such side:
+ * a = 1); a = float(min(e + 1, rho + 1)) / float(rho + 1); o = float(photo) + a u; out = uint8(clip(rint(o), 0, 255)), ties to even.
+ * Bilinear is linear, so this is up(result) + (photo - up(small source)): only the difference is interpolated.  Inputs are finite.
+ * No context; one launch, no scratch, no allocation, no host sync, no atomics. */
+int mkd_paste_photo(const mkd_photo_desc* descs, int n, int S, const float* t, const float* s01, int feather, void* stream);
+
 /* ---- first-stage decoder ------------------------------------------------ */
 /* yaml first_stage_config.params.ddconfig (diffmodels/base_diffusion_makeup.yaml:86-107), decoder half only. */
 typedef struct mkd_vae_config {

@@ -672,6 +672,49 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                                                                            feather=self.paste_feather, return_alpha=True)
         return out
 
+    @torch.no_grad()
+    def transfer_photos(self, src_photos, ref_photos, src_boxes, ref_boxes, src_segs=None, feather: int = 8,
+                        x_T: Optional[torch.Tensor] = None, size: int = 256, batch: Optional[dict] = None) -> List[torch.Tensor]:
+        """Makeup transfer on photographs at their own resolution: ``src_photos`` / ``ref_photos`` are uint8 [H,W,3] tensors of any
+        size (lists; the photos of a call may differ in size) with a face box (x0, y0, w, h) each.  Both boxes are crop-resized to
+        ``size`` on the device (photo.crop_resize: Pillow's antialiased bilinear bytes / 255, what PairFolderDataset gives for that
+        crop), ONE sampling pass runs as in transfer_regions -- the ``sampler`` attribute's solver for ddim_steps from x_T, guided when
+        unconditional_guidance_scale > 1, with the fix_background / paste_background settings on the crop-resized ``src_segs`` (label
+        maps at photo resolution) -- the latent is decoded and pasted into CLONES of the source photos with their fine detail kept
+        (photo.paste_photos, ``feather`` photo pixels at the box sides).  ``batch`` carries the text fields get_input reads (txt_emb /
+        txt_tokens / txt); without it the prompt is 'makeup transfer'.  Returns the uint8 [H,W,3] device tensors."""
+        from .. import photo
+        if not self.has_first_stage:
+            raise ValueError('transfer_photos pastes decoded images: it needs a first stage (first_stage_config)')
+        if (self.fix_background or self.paste_background) and src_segs is None:
+            raise KeyError('transfer_photos: fix_background / paste_background need src_segs (label maps at photo resolution)')
+        eng = self._require_engine()
+        src_photos = [p.to(self.device) for p in src_photos]
+        n = len(src_photos)
+        cs = eng.crop_resize(src_photos, src_boxes, size, labels=src_segs)
+        cr = eng.crop_resize(ref_photos, ref_boxes, size)
+        if cr.img01.shape[0] != n:
+            raise ValueError(f'{n} source photos but {cr.img01.shape[0]} reference photos')
+        src, ref = cs.img01, cr.img01
+        ctx = self.get_cond_txt_coding(batch if batch is not None else {self.cond_stage_key: ['makeup transfer'] * n})
+        cond = {'c_concat': [torch.cat((src, ref), 1)], 'c_crossattn': [ctx]}
+        extra = {} if x_T is None else {'x_T': x_T.to(self.device)}
+        seg_batch = {self.seg_key: cs.labels}
+        if self.fix_background:
+            x0, mask = self.background_latents(seg_batch, src)
+            extra.update(x0=x0, mask=mask)
+        scale = float(self.unconditional_guidance_scale)
+        if scale > 1.0:           # log_results' guided pass: the unconditional branch keeps the SAME hint
+            extra.update(unconditional_guidance_scale=scale,
+                         unconditional_conditioning={'c_concat': cond['c_concat'], 'c_crossattn': [self.get_unconditional_conditioning(n)]})
+        lat, _ = self.sample_log(cond=cond, batch_size=n, ddim=True, ddim_steps=self.ddim_steps, eta=self.ddim_eta, **extra)
+        img = self.decode_first_stage(lat)
+        if self.paste_background:
+            img, _ = self.paste_source(seg_batch, img, src * 2.0 - 1.0)
+        out = [p.clone(memory_format=torch.contiguous_format) for p in src_photos]
+        eng.paste_photos(out, src_boxes, img, src, feather)
+        return out
+
     def test_step(self, batch: dict, batch_idx: int, x_T: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """reference diffusion_makeup.py:332-341.  x_T (not in the reference, which always draws fresh noise): fixed start
         noise for both sampling passes, so that runs can be compared."""

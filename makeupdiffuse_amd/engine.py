@@ -746,6 +746,23 @@ class MkdEngine:
                                                      C.c_void_p(_ptr(alpha)), B, Cn, H, W, C.c_void_p(_stream())), 'mkd_paste_background')
         return (out, alpha) if return_alpha else out
 
+    def crop_resize(self, photos, boxes, size: int, labels=None, want_u8: bool = False):
+        """Full-resolution photos in (include/mkd.h mkd_crop_resize; photo.crop_resize on this engine's device): uint8 [H,W,3]
+        photos and their boxes (x0, y0, w, h) -> Cropped(img01 [B,3,S,S], labels [B,S,S] or None, u8 [B,S,S,3] or None), the bytes
+        of Pillow's antialiased bilinear resize of each box."""
+        from . import photo
+        def to_dev(ts, single_dim):          # one tensor, a stacked batch or a list -> a list on this engine's device
+            if isinstance(ts, torch.Tensor):
+                ts = [ts] if ts.dim() == single_dim else ts.unbind(0)
+            return [t.to(self.device) for t in ts]
+        return photo.crop_resize(to_dev(photos, 3), boxes, size, labels=None if labels is None else to_dev(labels, 2), want_u8=want_u8)
+
+    def paste_photos(self, photos, boxes, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8):
+        """Full-resolution photos out (include/mkd.h mkd_paste_photo; photo.paste_photos): the decoded samples pasted into the
+        device photos IN PLACE, inside their boxes, with the photos' fine detail kept."""
+        from . import photo
+        return photo.paste_photos(photos, boxes, samples, src01, feather)
+
     def eps_profile(self, x: torch.Tensor, t: torch.Tensor, csv_path: Optional[str] = None) -> Dict[str, Dict[str, float]]:
         """One eps with HIP events around every launch group -> {kernel class: {ms, flops, launches, bytes, ms_b2b}}: ``bytes`` =
         algorithmic HBM bytes of the memory-bound classes, ``ms_b2b`` = the class's launches replayed back to back between one

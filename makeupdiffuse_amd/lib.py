@@ -36,6 +36,11 @@ class NetConfigC(C.Structure):
     ]
 
 
+class PhotoDescC(C.Structure):
+    _fields_ = [('pixels', C.c_void_p), ('pitch_bytes', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('x0', C.c_int32), ('y0', C.c_int32),
+                ('bw', C.c_int32), ('bh', C.c_int32), ('labels', C.c_void_p)]
+
+
 class SampleMaskC(C.Structure):
     _fields_ = [('x0', C.c_void_p), ('mask', C.c_void_p), ('mask_batch', C.c_int32), ('mask_channels', C.c_int32),
                 ('sqrt_alphas_cumprod', C.POINTER(C.c_float)), ('sqrt_one_minus_alphas_cumprod', C.POINTER(C.c_float)),
@@ -87,6 +92,10 @@ SIGNATURES = {
     'mkd_hist_match_scratch_bytes': (C.c_size_t, [_I]),
     'mkd_hist_match_launches': (_I, [_I, _I]),
     'mkd_hist_match': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'mkd_crop_resize_scratch_bytes': (C.c_size_t, [C.POINTER(PhotoDescC), _I, _I]),
+    'mkd_crop_resize': (_I, [C.POINTER(PhotoDescC), _I, _I, _P, _P, _P, _P, _P]),
+    'mkd_resize_coeffs': (_I, [_I, _I, _I, _I, _P, _P, _P]),
+    'mkd_paste_photo': (_I, [C.POINTER(PhotoDescC), _I, _I, _P, _P, _I, _P]),
     'mkd_vae_configure': (_I, [_P, C.POINTER(VaeConfigC)]),
     'mkd_vae_finalize': (_I, [_P]),
     'mkd_decode': (_I, [_P, _P, _I, _I, _I, _F, _P, _P]),

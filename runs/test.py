@@ -94,6 +94,10 @@ def build_parser():
                     'otherwise).  Independent of --fix-background; the two combine')
     ap.add_argument('--paste-feather', type=int, default=0, help='mix source and sample over this many image pixels on both sides of the '
                     'paste boundary, 0..16 (0: the hard mask of the reference)')
+    ap.add_argument('--photos', action='store_true', help='after the usual passes, also transfer every pair at the photos\' NATIVE resolution: '
+                    'the face box (<data-root>/boxes.txt, lines "name x0 y0 w h"; else the centred largest square) is crop-resized to --res on '
+                    'the device, sampled once, and pasted back into the source photo with its fine detail kept; writes <out>/photos/<pair>.png')
+    ap.add_argument('--photo-feather', type=int, default=8, help='fade the pasted face in over this many photo pixels at the box sides, 0..64')
     return ap
 
 
@@ -142,6 +146,12 @@ def main():
         raise SystemExit('--paste-feather must be 0..16 image pixels')
     if args.paste_feather and not (args.paste_background or args.region_paste_outside):
         raise SystemExit('--paste-feather only applies with --paste-background or --region-paste-outside')
+    if args.photos and not args.data_root:
+        raise SystemExit('--photos needs --data-root with images/ and a pairs file (the photos are read at their own resolution)')
+    if not 0 <= args.photo_feather <= 64:
+        raise SystemExit('--photo-feather must be 0..64 photo pixels')
+    if args.photo_feather != 8 and not args.photos:
+        raise SystemExit('--photo-feather only applies with --photos')
     rank, world, local = mdist.init_from_env()
     model = create_model(args.config).cpu()
     if args.fix_background:
@@ -176,6 +186,10 @@ def main():
         from makeupdiffuse_amd.imageio import PairFolderDataset, collate
         dataset = PairFolderDataset(args.data_root, args.pairs_file, (args.res, args.res))
         args.pairs = len(dataset)
+    photo_ds = None
+    if args.photos:
+        from makeupdiffuse_amd.photo import PhotoPairDataset, collate_photos
+        photo_ds = PhotoPairDataset(args.data_root, args.pairs_file)
     txt_emb = None
     if args.txt_emb:
         t = load_state_dict(args.txt_emb)
@@ -214,6 +228,15 @@ def main():
             if 'samples' in reg:
                 out['samples_regions'] = torch.clamp(reg['samples'].detach().cpu(), -1.0, 1.0)
                 model.save_local({'samples_regions': out['samples_regions']}, b0)
+        if photo_ds is not None:
+            from PIL import Image
+            items = collate_photos([photo_ds[i] for i in range(b0, b1)])
+            text = {k: batch[k] for k in ('txt_emb', 'txt') if k in batch}
+            photos = model.transfer_photos(items['src_photo'], items['ref_photo'], items['src_box'], items['ref_box'],
+                                           src_segs=items.get('src_seg'), feather=args.photo_feather, x_T=x_T, size=args.res, batch=text)
+            os.makedirs(os.path.join(args.out, 'photos'), exist_ok=True)
+            for name, img in zip(items['img_name'], photos):
+                Image.fromarray(img.cpu().numpy()).save(os.path.join(args.out, 'photos', name + '.png'))
         if args.makeup_score:
             write_makeup_scores(os.path.join(args.out, f'makeup_score_rank{rank}.csv' if world > 1 else 'makeup_score.csv'),
                                 batch.get('img_name') or [str(i) for i in range(b0, b1)], out, first=b0 == lo)
