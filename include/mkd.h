@@ -163,6 +163,24 @@ int mkd_ddim_step(const float* x, const float* eps_c, const float* eps_u, float 
                   const float* noise, float temperature,
                   float* x_prev, float* pred_x0, int64_t n, void* stream);
 
+/* ---- guidance rescale (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed", section 3.4; rescale_noise_cfg
+ * of published samplers).  BUILD-DEFINED on eps: with g = eps_u + scale (eps_c - eps_u), per sample b over its
+ * n_per_sample elements  k[b] = phi std(eps_c[b]) / std(g[b]) + (1 - phi)  and the step uses e = g k[b]; std(g[b]) == 0 gives k[b] = 1.
+ * mkd_cfg_rescale_factor: eps_c, eps_u [batch][n_per_sample] fp32 -> k_out [batch] fp32.  One launch, one workgroup per sample;
+ * g = fmaf(scale, eps_c - eps_u, eps_u) in fp32, the sums of eps_c, eps_c^2, g, g^2 in fp64 in a fixed order (the same bits on every
+ * run, for every batch), k in double, rounded once; a variance of g not above the rounding error of its own sums
+ * (4 n_per_sample 2^-52 sum g^2) counts as zero.  No context, no atomics, no scratch, no host sync.
+ * phi outside [0, 1], batch outside 1..65535, n_per_sample < 1, a null pointer: MKD_ERR_ARG. */
+int mkd_cfg_rescale_factor(const float* eps_c, const float* eps_u, float scale, float phi, int batch, int n_per_sample,
+                           float* k_out, void* stream);
+/* mkd_ddim_step with the rescaled eps: k non-null (device [n / n_per_sample], needs eps_u and n_per_sample > 0 dividing n, else
+ * MKD_ERR_ARG): e = fmaf(cfg_scale, eps_c - eps_u, eps_u) * k[i / n_per_sample], the expression the in-library loop uses.
+ * k == NULL is exactly mkd_ddim_step. */
+int mkd_ddim_step_ex(const float* x, const float* eps_c, const float* eps_u, float cfg_scale,
+                     float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at,
+                     const float* noise, float temperature, const float* k, int n_per_sample,
+                     float* x_prev, float* pred_x0, int64_t n, void* stream);
+
 /* ---- whole reverse loop ------------------------------------------------------------------ */
 /* Replaces MKDDIMSampler.reconstruct (cddim.py:81-100) / DDIMSampler.ddim_sampling reached from
  * sample_log (diffusion_makeup.py:393-408) for eta == 0.  The context must have been prepared with
@@ -217,6 +235,32 @@ int mkd_sample_masked(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, co
                       const float* alphas, const float* alphas_prev, const float* sqrt_one_minus_alphas,
                       const float* sigmas, const float* noise, float temperature, const mkd_sample_mask* m,
                       float cfg_scale, float* x_out, int use_graph, void* stream);
+/* ---- extras of the in-library loop: the sampler's intermediates and guidance rescale -------------------------------------------
+ * Trace (UPSTREAM DDIMSampler.ddim_sampling's intermediates): executed step k = 0 .. n_steps-1 runs table entry i = n_steps-1-k; entry i
+ * is logged when i % log_every_t == 0 or i == n_steps-1; logged steps fill rows 0, 1, ... in execution order.  Row r of trace_x is the
+ * latent after that step (masked sampling: before the next step's blend), row r of trace_x0 the step's x0-prediction
+ * ((x - sqrt(1 - a_t) e) / sqrt(a_t) for DDIM, m_k for DPM-Solver++; e is the eps the update itself uses, guided and rescaled).
+ * trace_x / trace_x0: DEVICE [rows][B*4*h*w] fp32, each may be NULL (that list is not kept); with either, rows must equal
+ * mkd_sample_log_rows(n_steps, log_every_t) and log_every_t >= 1, else MKD_ERR_ARG.  The rows are written by the step's last kernel
+ * (no extra launch; traced and untraced calls share one capture).  They are WRITTEN by the enqueued loop: they must stay valid until
+ * the work on `stream` has completed, like `noise` of mkd_sample_eta.
+ * guidance_rescale = phi in [0, 1] (else MKD_ERR_ARG): see mkd_cfg_rescale_factor; per sample, inside every step.  Engaged only with
+ * guidance (cfg_scale != 1) and phi > 0: one extra launch per step (mkd_step_launches_ex cfg_on = 2), captured steps are keyed on it,
+ * phi itself is read from the device-resident step state (a new phi does not re-capture).  phi = 0 or cfg_scale == 1: today's step. */
+typedef struct mkd_sample_extras {
+    int32_t log_every_t;
+    int32_t rows;
+    float*  trace_x;              /* device [rows][B*4*h*w] or NULL */
+    float*  trace_x0;             /* device [rows][B*4*h*w] or NULL */
+    float   guidance_rescale;     /* phi */
+} mkd_sample_extras;
+/* HOST only: the number of rows the rule above logs; n_steps < 1 or log_every_t < 1: MKD_ERR_ARG. */
+int mkd_sample_log_rows(int n_steps, int log_every_t);
+/* mkd_sample_masked with the extras; ex == NULL is exactly mkd_sample_masked (m == NULL as there).  All three loop forms. */
+int mkd_sample_masked_ex(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps,
+                         const float* alphas, const float* alphas_prev, const float* sqrt_one_minus_alphas,
+                         const float* sigmas, const float* noise, float temperature, const mkd_sample_mask* m,
+                         const mkd_sample_extras* ex, float cfg_scale, float* x_out, int use_graph, void* stream);
 /* One blend / q_sample (the eager step loop's and DDIMSampler.stochastic_encode's kernel; the same device arithmetic as the loop):
  * out = (sqrt_ac x0 + sqrt_one_minus_ac noise) mask + (1 - mask) x over [batch, channels, hw] fp32 device tensors, mask as in
  * mkd_sample_mask (mask_batch in {1, batch}, mask_channels in {1, channels}); mask == NULL: out = the q_sample alone (x unused).
@@ -244,6 +288,9 @@ int mkd_dpmpp_table(int n_steps, const float* alphas, const float* alphas_prev, 
  * x0-predictions) are read only where their coefficient is non-zero and may be NULL otherwise; x_prev may alias x.  All fp32 [n]. */
 int mkd_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, const float* coef6, const float* m1,
                    const float* m2, float* x_prev, float* m0_out, int64_t n, void* stream);
+/* ... with the rescaled eps: k / n_per_sample as in mkd_ddim_step_ex; k == NULL is exactly mkd_dpmpp_step. */
+int mkd_dpmpp_step_ex(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, const float* coef6, const float* m1,
+                      const float* m2, const float* k, int n_per_sample, float* x_prev, float* m0_out, int64_t n, void* stream);
 /* The whole loop: mkd_sample's contract (prepared batch B or 2B with the unconditional conditioning first, host tables, all three
  * loop forms: graph replay, its per-stream segments, use_graph == 0) with the update above as the step's last kernel and a device
  * history ring [3][B*4*h*w] fp32 owned by the context.  m != NULL: the masked blend of mkd_sample_masked before every step.  The
@@ -251,6 +298,10 @@ int mkd_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, float
 int mkd_sample_dpmpp(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
                      const float* alphas_prev, int order, int lower_order_final, const mkd_sample_mask* m, float cfg_scale,
                      float* x_out, int use_graph, void* stream);
+/* mkd_sample_dpmpp with the extras of mkd_sample_masked_ex (trace_x0 rows are m_k); ex == NULL is exactly mkd_sample_dpmpp. */
+int mkd_sample_dpmpp_ex(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
+                        const float* alphas_prev, int order, int lower_order_final, const mkd_sample_mask* m,
+                        const mkd_sample_extras* ex, float cfg_scale, float* x_out, int use_graph, void* stream);
 /* Latent mask from a label map (reference Fixbackground: labels 0 background, 11 teeth, 12 hair): labels [batch, H, W] uint8
  * device -> out [batch, 1, H/factor, W/factor] fp32 device = the fraction of each factor x factor block whose label l has bit l set
  * in `classes` (labels >= 64 never match): F.interpolate(mode='area') of the binary mask.  threshold > 0: 1 where that fraction
@@ -418,7 +469,7 @@ int     mkd_eps_launches(const mkd_ctx* ctx);
 /* Number of kernel launches of one DDIM step inside mkd_sample at the prepared shape (the time-embedding chain of mkd_eps is
  * computed once per call there, see mkd_sample; + the step setup and the x_{t-1} update). */
 int     mkd_step_launches(const mkd_ctx* ctx);                           /* graph replay, no guidance */
-int     mkd_step_launches_ex(const mkd_ctx* ctx, int use_graph, int cfg_on); /* as the loop is run: eager adds the timestep fill / table-row select, guidance the batch doubling */
+int     mkd_step_launches_ex(const mkd_ctx* ctx, int use_graph, int cfg_on); /* as the loop is run: eager adds the timestep fill / table-row select, guidance (cfg_on != 0) the batch doubling, cfg_on == 2 (guidance with rescale) the factor launch */
 /* Kernel classes of the launch plan, and one mkd_eps with a hipEvent pair around every launch group:
  * per-class device milliseconds, executed FLOPs and launch counts (arrays of mkd_kind_count()). Synchronous.
  * csv_path (host string, may be NULL): also write one line per launch group (op,kind,label,ms,gflop). */

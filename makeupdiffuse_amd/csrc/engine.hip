@@ -95,7 +95,22 @@ struct SampleReq {
     const mkd_sample_mask* qm = nullptr;          // masked sampling
     const float* dpm = nullptr;                   // host [n_steps][6] of mkd_dpmpp_table: the DPM-Solver++ loop; null: DDIM
     float cfg_scale = 1.0f; float* x_out = nullptr; int use_graph = 0;
+    const mkd_sample_extras* ex = nullptr;        // intermediates trace / guidance rescale; null: neither
+    const char* who = "mkd_sample";
 };
+
+// mkd_sample_log_rows / the row table of a traced call: entry i (executed as step n_steps - 1 - i) is logged when
+// i % log_every_t == 0 or i == n_steps - 1 (UPSTREAM DDIMSampler.ddim_sampling), rows in execution order
+static int sample_log_rows(int n_steps, int log_every_t, short* row_of_entry) {
+    int rows = 0;
+    for (int k = 0; k < n_steps; ++k) {
+        const int i = n_steps - 1 - k;
+        const bool logged = i % log_every_t == 0 || i == n_steps - 1;
+        if (row_of_entry) row_of_entry[i] = logged ? (short)rows : (short)-1;
+        rows += logged;
+    }
+    return rows;
+}
 
 // What a plan op launches, kept beside its closure for the ops that have a GROUPED form (mkd_common.h: Pair): when the ControlNet
 // and the UNet encoder emit the same op on the same geometry, the pair becomes one launch (mkd_ctx::group_ops).
@@ -285,14 +300,16 @@ struct mkd_ctx {
     float* s_xa = nullptr; float* s_xb = nullptr; float* s_xin = nullptr; float* s_eps = nullptr;
     int64_t* s_t = nullptr;
     StepState* s_state = nullptr; StepState* h_state = nullptr;
+    float* s_kfac = nullptr;          // guidance rescale: this step's per-sample factors [B] (allocated with the buffers above)
     float* s_ring = nullptr; int64_t s_ring_n = 0;        // DPM-Solver++ history ring [3][n] fp32: allocated on first use, grown with the batch
     hipStream_t loop_stream = nullptr; hipEvent_t ev_loop_in = nullptr, ev_loop_out = nullptr;
     hipGraphExec_t multi_graph = nullptr; int multi_graph_steps = 0;      // MKD_GRAPH_STEPS consecutive steps as one graph
     // everything the nodes of a captured step depend on: plan, guidance (on, scale), where the time embedding comes from, batch, and
-    // the solver whose kernel ends the step (0 DDIM, 1 DPM-Solver++; its order lives in the table)
+    // the solver whose kernel ends the step (0 DDIM, 1 DPM-Solver++; its order lives in the table), and whether the guided eps is
+    // rescaled (one more launch, another expression in the last kernel; phi itself lives in the step state)
     struct StepKey {
-        int gen = -1, cfg = -1, temb = -1, batch = -1, solver = -1; float scale = 0.f;
-        bool operator==(const StepKey& o) const { return gen == o.gen && cfg == o.cfg && temb == o.temb && batch == o.batch && solver == o.solver && scale == o.scale; }
+        int gen = -1, cfg = -1, temb = -1, batch = -1, solver = -1, rescale = -1; float scale = 0.f;
+        bool operator==(const StepKey& o) const { return gen == o.gen && cfg == o.cfg && temb == o.temb && batch == o.batch && solver == o.solver && rescale == o.rescale && scale == o.scale; }
     };
     hipGraphExec_t step_graph = nullptr; StepKey step_key; int plan_generation = 0;
     // Graph mode 2 (MKD_GRAPH_MODE=2; default 1 = one captured graph per step): one step = LINEAR graphs, one per (stream, stretch
@@ -1688,6 +1705,8 @@ struct mkd_ctx {
             }
             if (s_t) { hipFree(s_t); s_t = nullptr; }
             MKD_HIP_CHECK(hipMalloc((void**)&s_t, (size_t)B * sizeof(int64_t)));
+            if (s_kfac) { hipFree(s_kfac); s_kfac = nullptr; }
+            MKD_HIP_CHECK(hipMalloc((void**)&s_kfac, (size_t)B * sizeof(float)));
         }
         for (auto& op : plan_prepare) { int rc = op.fn(stream); if (rc) return rc; }
         prepared = true;
@@ -1814,8 +1833,10 @@ struct mkd_ctx {
     struct StepIo { const float* x; const float* ec; const float* eu; };
     StepIo step_io(bool cfg_on, const float* x, int64_t n) const { return cfg_on ? StepIo{s_xin, s_eps + n, s_eps} : StepIo{x, s_eps, nullptr}; }
     // ONE reverse step that reads its timestep / coefficients from the device step state (the graph body), around the evaluation:
-    // head = step setup (+ the batch doubling with guidance), tail = the solver's last kernel
-    struct StateStep { std::vector<OpFn> head; StepIo io; OpFn tail; };
+    // head = step setup (+ the batch doubling with guidance), factor = the guidance-rescale factors (null unless the key asks for
+    // them), tail = the solver's last kernel
+    struct StateStep { std::vector<OpFn> head; StepIo io; OpFn factor; OpFn tail; };
+    int sample_elems() const { return cfg.in_channels * h * w; }          // elements of one sample's latent
     StateStep state_step(const StepKey& k) {
         mkd_ctx* self = this;
         const int64_t n = latent_n(k.batch);
@@ -1824,9 +1845,13 @@ struct mkd_ctx {
             const TembSel ts = self->temb_sel();
             return launch_step_setup(self->s_state, self->s_t, Bn, self->s_xa, n, st, self->temb_skip ? &ts : nullptr); });
         if (k.cfg) s.head.push_back([self, n](hipStream_t st) { return launch_repeat_batch(self->s_xa, self->s_xin, n, 2, st); });
-        s.tail = [self, io = s.io, n, dpm_on = k.solver != 0, scale = k.scale](hipStream_t st) {
-            return dpm_on ? launch_dpmpp_step_state(self->s_xa, io.ec, io.eu, scale, self->s_state, n, st)
-                          : launch_ddim_step_state(self->s_xa, io.ec, io.eu, scale, self->s_state, n, st); };
+        const float* kf = k.rescale > 0 ? s_kfac : nullptr;
+        const int per = sample_elems();
+        if (kf) s.factor = [self, io = s.io, per, batch = k.batch, scale = k.scale](hipStream_t st) {
+            return launch_cfg_rescale_factor(io.ec, io.eu, scale, 0.f, self->s_state, batch, per, self->s_kfac, st); };
+        s.tail = [self, io = s.io, n, dpm_on = k.solver != 0, scale = k.scale, kf, per](hipStream_t st) {
+            return dpm_on ? launch_dpmpp_step_state(self->s_xa, io.ec, io.eu, scale, self->s_state, n, st, kf, per)
+                          : launch_ddim_step_state(self->s_xa, io.ec, io.eu, scale, self->s_state, n, st, kf, per); };
         return s;
     }
     int enqueue_state_steps(const StepKey& k, int steps, hipStream_t stream) {
@@ -1834,6 +1859,7 @@ struct mkd_ctx {
         for (int i = 0; i < steps; ++i) {
             for (auto& f : s.head) { int rc = f(stream); if (rc) return rc; }
             int rc = eps(s.io.x, s_t, s_eps, stream); if (rc) return rc;
+            if (s.factor) { rc = s.factor(stream); if (rc) return rc; }
             rc = s.tail(stream); if (rc) return rc;
         }
         return 0;
@@ -1887,6 +1913,7 @@ struct mkd_ctx {
 #endif
             items.push_back({op.fn, arena_of(op.cap_sid >= 0 ? op.cap_sid : op.sid), -1, -1});
         }
+        if (s.factor) items.push_back({s.factor, 0, -1, -1});
         items.push_back({s.tail, 0, -1, -1});
         std::vector<OpFn> pend[NS];
         int rc = 0;
@@ -1976,6 +2003,16 @@ struct mkd_ctx {
         if (qm && ((qm->mask_batch != 1 && qm->mask_batch != r.batch) || (qm->mask_channels != 1 && qm->mask_channels != cfg.in_channels)))
             return mkd_fail(MKD_ERR_ARG, "mkd_sample_masked: mask must be [1 or B, 1 or C, h, w]");
         if (r.use_graph && r.n_steps > MKD_MAX_STEPS) return mkd_fail(MKD_ERR_ARG, "mkd_sample: too many steps for the graph path");
+        if (const mkd_sample_extras* ex = r.ex) {
+            const std::string who = r.who;
+            if (!(ex->guidance_rescale >= 0.f && ex->guidance_rescale <= 1.f)) return mkd_fail(MKD_ERR_ARG, who + ": guidance_rescale must lie in [0, 1]");
+            if (ex->trace_x || ex->trace_x0) {
+                if (ex->log_every_t < 1) return mkd_fail(MKD_ERR_ARG, who + ": log_every_t must be >= 1");
+                if (r.n_steps > MKD_MAX_STEPS) return mkd_fail(MKD_ERR_ARG, who + ": too many steps for the trace");
+                if (ex->rows != sample_log_rows(r.n_steps, ex->log_every_t, nullptr))
+                    return mkd_fail(MKD_ERR_ARG, who + ": rows must be mkd_sample_log_rows(n_steps, log_every_t)");
+            }
+        }
         return 0;
     }
 
@@ -2008,7 +2045,15 @@ struct mkd_ctx {
             h_state->q[2 * i] = qm ? qm->sqrt_alphas_cumprod[i] : 0.f;
             h_state->q[2 * i + 1] = qm ? qm->sqrt_one_minus_alphas_cumprod[i] : 0.f;
         }
+        // intermediates trace and guidance rescale: read by the step's last kernel(s); null pointers leave the (shared) capture untraced
+        const mkd_sample_extras* ex = r.ex;
+        h_state->trace_x = ex ? ex->trace_x : nullptr; h_state->trace_x0 = ex ? ex->trace_x0 : nullptr;
+        h_state->cur_trace = -1;
+        if (traced(r)) sample_log_rows(n_steps, ex->log_every_t, h_state->trace_row);
+        else for (int i = 0; i < n_steps; ++i) h_state->trace_row[i] = -1;
+        h_state->phi = ex ? ex->guidance_rescale : 0.f;
     }
+    static bool traced(const SampleReq& r) { return r.ex && (r.ex->trace_x || r.ex->trace_x0); }
 
     // graph path, before the steps: order the loop against the caller's stream, upload the step state, run the table
     int graph_prologue(const SampleReq& r, bool stochastic, hipStream_t stream) {
@@ -2066,8 +2111,15 @@ struct mkd_ctx {
         const mkd_sample_mask* qm = r.qm;
         int rc = run_temb_table(n_steps, r.timesteps, stream); if (rc) return rc;
         float* xa = s_xa; float* xb = s_xb;
+        const float* kf = key.rescale > 0 ? s_kfac : nullptr;
+        const int per = sample_elems();
+        std::vector<short> row_of(n_steps, (short)-1);
+        if (traced(r)) sample_log_rows(n_steps, r.ex->log_every_t, row_of.data());
         for (int i = 0; i < n_steps; ++i) {
             const int index = n_steps - 1 - i;
+            // this step's trace rows (null: not logged, or that list was not asked for): written by the update kernel itself
+            float* tx = (row_of[index] >= 0 && r.ex->trace_x) ? r.ex->trace_x + (int64_t)row_of[index] * n : nullptr;
+            float* tx0 = (row_of[index] >= 0 && r.ex->trace_x0) ? r.ex->trace_x0 + (int64_t)row_of[index] * n : nullptr;
             rc = launch_fill_i64(s_t, r.timesteps[index], B, stream); if (rc) return rc;
             if (qm) {           // (the eager loop's one extra launch per step: the graph folds this blend into its step setup)
                 rc = launch_q_sample_blend(qm->x0, qm->noise + (int64_t)i * n, qm->sqrt_alphas_cumprod[index], qm->sqrt_one_minus_alphas_cumprod[index],
@@ -2078,15 +2130,16 @@ struct mkd_ctx {
             const StepIo io = step_io(key.cfg != 0, xa, n);
             if (key.cfg) { rc = launch_repeat_batch(xa, s_xin, n, 2, stream); if (rc) return rc; }
             rc = eps(io.x, s_t, s_eps, stream); if (rc) return rc;
+            if (kf) { rc = launch_cfg_rescale_factor(io.ec, io.eu, key.scale, r.ex->guidance_rescale, nullptr, r.batch, per, s_kfac, stream); if (rc) return rc; }
             if (key.solver) {           // m_k into ring slot k mod 3; m_{k-1}, m_{k-2} from the other two (k = i, the executed step)
                 const float* d = r.dpm + 6 * index;
                 const DpmCoef kc = {d[0], d[1], d[2], d[3], d[4], d[5]};
                 rc = launch_dpmpp_step(xa, io.ec, io.eu, key.scale, kc, s_ring + (int64_t)((i + 2) % 3) * n, s_ring + (int64_t)((i + 1) % 3) * n, xb,
-                                       s_ring + (int64_t)(i % 3) * n, n, stream);
+                                       s_ring + (int64_t)(i % 3) * n, n, stream, kf, per, tx, tx0);
             } else {
                 const float sg = stochastic ? r.sigmas[index] : 0.f;
                 rc = launch_ddim_step(xa, io.ec, io.eu, key.scale, r.alphas[index], r.alphas_prev[index], sg, r.s1m[index],
-                                      sg != 0.f ? r.noise + (int64_t)i * n : nullptr, r.temperature, xb, nullptr, n, stream);
+                                      sg != 0.f ? r.noise + (int64_t)i * n : nullptr, r.temperature, xb, tx0, n, stream, kf, per, tx);
             }
             if (rc) return rc;
             float* tmp = xa; xa = xb; xb = tmp;
@@ -2102,6 +2155,7 @@ struct mkd_ctx {
         bool stochastic = false;
         int rc = validate(r, &stochastic); if (rc) return rc;
         StepKey key; key.gen = plan_generation; key.cfg = r.cfg_scale != 1.0f; key.scale = r.cfg_scale; key.batch = r.batch; key.solver = r.dpm != nullptr;
+        key.rescale = (key.cfg && r.ex && r.ex->guidance_rescale > 0.f) ? 1 : 0;          // (phi = 0, scale 1: not engaged, today's step)
         key.temb = temb_table;          // (the steps take the time embedding from the table exactly when the table is on)
         const int64_t n = latent_n(r.batch);
         if (key.solver) { rc = ensure_ring(n); if (rc) return rc; }
@@ -2615,6 +2669,7 @@ struct mkd_ctx {
         if (persist_cap > persist_eps_begin) MKD_HIP_CHECK(hipMemset(persist_base + persist_eps_begin, 0xFF, persist_cap - persist_eps_begin));
         if (gstat_base) MKD_HIP_CHECK(hipMemset(gstat_base, 0xFF, gstat_cap));
         if (s_ring) MKD_HIP_CHECK(hipMemset(s_ring, 0xFF, (size_t)(3 * s_ring_n) * sizeof(float)));
+        if (s_kfac) MKD_HIP_CHECK(hipMemset(s_kfac, 0xFF, (size_t)B * sizeof(float)));
         for (int i = 0; i < NS; ++i) {
             if (temp_base[i]) MKD_HIP_CHECK(hipMemset(temp_base[i], 0xFF, temp_cap[i]));
             if (splitk_ws[i]) MKD_HIP_CHECK(hipMemset(splitk_ws[i], 0xFF, splitk_ws_bytes[i]));
@@ -2657,7 +2712,7 @@ struct mkd_ctx {
             for (void* p : {(void*)temp_base[i], (void*)splitk_ws[i], (void*)gn_ws[i]})
                 if (p) hipFree(p);
         for (void* p : {(void*)persist_base, (void*)s_xa, (void*)s_xb,
-                        (void*)s_xin, (void*)s_eps, (void*)s_t})
+                        (void*)s_xin, (void*)s_eps, (void*)s_t, (void*)s_kfac})
             if (p) hipFree(p);
     }
 };
@@ -2789,6 +2844,30 @@ int mkd_ddim_step(const float* x, const float* eps_c, const float* eps_u, float 
     return launch_ddim_step(x, eps_c, eps_u, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, noise, temperature, x_prev,
                             pred_x0, n, (hipStream_t)stream);
 }
+static int check_rescale_args(const float* k, const float* eps_u, int64_t n, int n_per_sample, const char* who) {
+    if (k && (!eps_u || n_per_sample <= 0 || n % n_per_sample))
+        return mkd_fail(MKD_ERR_ARG, std::string(who) + ": k needs eps_u and an n_per_sample > 0 that divides n");
+    return 0;
+}
+int mkd_ddim_step_ex(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, float a_t, float a_prev,
+                     float sigma_t, float sqrt_one_minus_at, const float* noise, float temperature, const float* k, int n_per_sample,
+                     float* x_prev, float* pred_x0, int64_t n, void* stream) {
+    if (!x || !eps_c || !x_prev) return mkd_fail(MKD_ERR_ARG, "mkd_ddim_step_ex: null pointer");
+    if (int rc = check_rescale_args(k, eps_u, n, n_per_sample, "mkd_ddim_step_ex")) return rc;
+    return launch_ddim_step(x, eps_c, eps_u, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, noise, temperature, x_prev,
+                            pred_x0, n, (hipStream_t)stream, k, n_per_sample);
+}
+int mkd_cfg_rescale_factor(const float* eps_c, const float* eps_u, float scale, float phi, int batch, int n_per_sample, float* k_out,
+                           void* stream) {
+    if (!eps_c || !eps_u || !k_out) return mkd_fail(MKD_ERR_ARG, "mkd_cfg_rescale_factor: null pointer");
+    if (batch <= 0 || batch > 65535 || n_per_sample <= 0) return mkd_fail(MKD_ERR_ARG, "mkd_cfg_rescale_factor: batch must be 1..65535, n_per_sample > 0");
+    if (!(phi >= 0.f && phi <= 1.f)) return mkd_fail(MKD_ERR_ARG, "mkd_cfg_rescale_factor: phi must lie in [0, 1]");
+    return launch_cfg_rescale_factor(eps_c, eps_u, scale, phi, nullptr, batch, n_per_sample, k_out, (hipStream_t)stream);
+}
+int mkd_sample_log_rows(int n_steps, int log_every_t) {
+    if (n_steps <= 0 || log_every_t < 1) return mkd_fail(MKD_ERR_ARG, "mkd_sample_log_rows: n_steps >= 1 and log_every_t >= 1");
+    return sample_log_rows(n_steps, log_every_t, nullptr);
+}
 int mkd_sample(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
                const float* alphas_prev, const float* sqrt_one_minus_alphas, float cfg_scale, float* x_out, int use_graph,
                void* stream) {
@@ -2808,9 +2887,16 @@ int mkd_sample_eta(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const
 int mkd_sample_masked(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
                       const float* alphas_prev, const float* sqrt_one_minus_alphas, const float* sigmas, const float* noise, float temperature,
                       const mkd_sample_mask* m, float cfg_scale, float* x_out, int use_graph, void* stream) {
+    return mkd_sample_masked_ex(ctx, x_T, batch, n_steps, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas, sigmas, noise, temperature, m,
+                                nullptr, cfg_scale, x_out, use_graph, stream);
+}
+int mkd_sample_masked_ex(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
+                         const float* alphas_prev, const float* sqrt_one_minus_alphas, const float* sigmas, const float* noise, float temperature,
+                         const mkd_sample_mask* m, const mkd_sample_extras* ex, float cfg_scale, float* x_out, int use_graph, void* stream) {
     if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
     SampleReq r{x_T, batch, n_steps, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas};
     r.sigmas = sigmas; r.noise = noise; r.temperature = temperature; r.qm = m; r.cfg_scale = cfg_scale; r.x_out = x_out; r.use_graph = use_graph;
+    r.ex = ex; r.who = ex ? "mkd_sample_masked_ex" : "mkd_sample_masked";
     return ctx->sample(r, (hipStream_t)stream);
 }
 // Schedule-only coefficients of the multistep DPM-Solver++ (data prediction), in double; host only.  With alpha = sqrt(a),
@@ -2866,9 +2952,23 @@ int mkd_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, float
     const DpmCoef k = {coef6[0], coef6[1], coef6[2], coef6[3], coef6[4], coef6[5]};
     return launch_dpmpp_step(x, eps_c, eps_u, cfg_scale, k, m1, m2, x_prev, m0_out, n, (hipStream_t)stream);
 }
+int mkd_dpmpp_step_ex(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, const float* coef6, const float* m1, const float* m2,
+                      const float* k, int n_per_sample, float* x_prev, float* m0_out, int64_t n, void* stream) {
+    if (!x || !eps_c || !coef6 || !x_prev || !m0_out || n <= 0) return mkd_fail(MKD_ERR_ARG, "mkd_dpmpp_step_ex: null pointer or empty tensor");
+    if ((coef6[4] != 0.f && !m1) || (coef6[5] != 0.f && !m2)) return mkd_fail(MKD_ERR_ARG, "mkd_dpmpp_step_ex: a non-zero c_1 / c_2 needs m1 / m2");
+    if (int rc = check_rescale_args(k, eps_u, n, n_per_sample, "mkd_dpmpp_step_ex")) return rc;
+    const DpmCoef kc = {coef6[0], coef6[1], coef6[2], coef6[3], coef6[4], coef6[5]};
+    return launch_dpmpp_step(x, eps_c, eps_u, cfg_scale, kc, m1, m2, x_prev, m0_out, n, (hipStream_t)stream, k, n_per_sample);
+}
 int mkd_sample_dpmpp(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
                      const float* alphas_prev, int order, int lower_order_final, const mkd_sample_mask* m, float cfg_scale, float* x_out,
                      int use_graph, void* stream) {
+    return mkd_sample_dpmpp_ex(ctx, x_T, batch, n_steps, timesteps, alphas, alphas_prev, order, lower_order_final, m, nullptr, cfg_scale, x_out,
+                               use_graph, stream);
+}
+int mkd_sample_dpmpp_ex(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
+                        const float* alphas_prev, int order, int lower_order_final, const mkd_sample_mask* m, const mkd_sample_extras* ex,
+                        float cfg_scale, float* x_out, int use_graph, void* stream) {
     if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
     if (n_steps <= 0 || !alphas || !alphas_prev) return mkd_fail(MKD_ERR_ARG, "mkd_sample_dpmpp: bad arguments");
     std::vector<float> tab((size_t)n_steps * 6);
@@ -2876,6 +2976,7 @@ int mkd_sample_dpmpp(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, con
     if (rc) return rc;
     SampleReq r{x_T, batch, n_steps, timesteps, alphas, alphas_prev};
     r.qm = m; r.dpm = tab.data(); r.cfg_scale = cfg_scale; r.x_out = x_out; r.use_graph = use_graph;
+    r.ex = ex; r.who = ex ? "mkd_sample_dpmpp_ex" : "mkd_sample_dpmpp";
     return ctx->sample(r, (hipStream_t)stream);
 }
 int mkd_q_sample_blend(const float* x0, const float* noise, float sqrt_ac, float sqrt_one_minus_ac, const float* mask, int mask_batch,
@@ -3017,11 +3118,11 @@ double mkd_eps_flops(const mkd_ctx* ctx) { return ctx ? ctx->flops_eps : 0.0; }
 int mkd_eps_launches(const mkd_ctx* ctx) { return ctx ? ctx->launches_eps : 0; }
 // what the step of sample() (state_step / build_segments, the eager loop) enqueues: the evaluation (without its own time-embedding chain when the per-call table
 // is on) + graph replay: step setup (timestep, coefficients, table rows) and the state update; eager: timestep fill, table-row
-// select (table on) and the update; + the batch doubling of x with guidance
+// select (table on) and the update; + the batch doubling of x with guidance; + the factor launch of a rescaled guided step (cfg_on == 2)
 int mkd_step_launches_ex(const mkd_ctx* ctx, int use_graph, int cfg_on) {
     if (!ctx) return 0;
     const int eval = ctx->launches_eps - (ctx->temb_table ? ctx->launches_temb : 0);
-    return eval + (use_graph ? 2 : (ctx->temb_table ? 3 : 2)) + (cfg_on ? 1 : 0);
+    return eval + (use_graph ? 2 : (ctx->temb_table ? 3 : 2)) + (cfg_on ? 1 : 0) + (cfg_on == 2 ? 1 : 0);
 }
 int mkd_step_launches(const mkd_ctx* ctx) { return mkd_step_launches_ex(ctx, 1, 0); }
 int64_t mkd_device_bytes(const mkd_ctx* ctx) { return ctx ? ctx->device_bytes() : 0; }

@@ -5,17 +5,69 @@
 
 namespace {
 
+// ---- guidance rescale (Lin et al. 2023, section 3.4): the guided eps of element i scaled by its sample's factor ----------------
+// The one expression of the engaged path (every step kernel, stand-alone or in the loop): explicit fma, then one multiply, so the
+// bits do not depend on what the compiler contracts.  kfac[b] comes from cfg_rescale_factor_kernel.
+__device__ __forceinline__ float cfg_rescaled_eps_at(float ec, float eu, float cfg_scale, const float* __restrict__ kfac, int64_t i,
+                                                     int n_per_sample) {
+    return fmaf(cfg_scale, ec - eu, eu) * kfac[i / n_per_sample];
+}
+
+// One workgroup of 256 threads per sample.  Thread t takes elements t, t + 256, ... of its sample and keeps fp64 sums of e_c, e_c^2,
+// g, g^2 (a product of two floats is exact in double); the sums are reduced inside each wave by shuffles (offsets 32 .. 1), then
+// thread 0 adds the four waves' values from LDS in wave order: an order fixed by n_per_sample alone, whatever the grid or the loop
+// form.  k = phi sqrt(var(e_c) / var(g)) + (1 - phi) in double, rounded once, one store.  var = sum(v^2) - sum(v)^2 / n (the 1 / (n - 1)
+// of the unbiased estimate cancels in the ratio); a var(g) that is not above the rounding error of its own sums
+// (3 n roundings of 2^-53 at most: 4 n 2^-52 sum(g^2) bounds it) counts as zero: k = 1.  No atomics, no scratch.
+__global__ void __launch_bounds__(256) cfg_rescale_factor_kernel(const float* __restrict__ eps_c, const float* __restrict__ eps_u,
+                                                                 float cfg_scale, float phi_arg, const StepState* __restrict__ st,
+                                                                 int n_per_sample, float* __restrict__ k_out) {
+    __shared__ double red[4][4];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const float* __restrict__ ec = eps_c + (int64_t)b * n_per_sample;
+    const float* __restrict__ eu = eps_u + (int64_t)b * n_per_sample;
+    double sc = 0.0, scc = 0.0, sg = 0.0, sgg = 0.0;
+    for (int i = t; i < n_per_sample; i += 256) {
+        const float c = ec[i], u = eu[i];
+        const float g = fmaf(cfg_scale, c - u, u);
+        sc += (double)c; scc += (double)c * (double)c;
+        sg += (double)g; sgg += (double)g * (double)g;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        sc += __shfl_down(sc, off, 64); scc += __shfl_down(scc, off, 64);
+        sg += __shfl_down(sg, off, 64); sgg += __shfl_down(sgg, off, 64);
+    }
+    if ((t & 63) == 0) { red[t >> 6][0] = sc; red[t >> 6][1] = scc; red[t >> 6][2] = sg; red[t >> 6][3] = sgg; }
+    __syncthreads();
+    if (t == 0) {
+        double a[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a[j] = ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j];
+        const double n = (double)n_per_sample;
+        const double phi = (double)(st ? st->phi : phi_arg);
+        double vc = a[1] - a[0] * a[0] / n, vg = a[3] - a[2] * a[2] / n;
+        if (!(vc > 0.0)) vc = 0.0;
+        double k = 1.0;
+        if (vg > 4.0 * n * 2.220446049250313e-16 * a[3]) k = phi * sqrt(vc / vg) + (1.0 - phi);
+        k_out[b] = (float)k;
+    }
+}
+
 // ---- DDIM x0 / x_{t-1} update, reference diffmk/cddim.py:39-40 (CFG) and :63,74-78 ----------------
+// kfac non-null (with eps_u): the guidance-rescaled eps; x_copy non-null: x_prev once more (a trace row of the eager loop)
 __global__ void ddim_step_kernel(const float* __restrict__ x, const float* __restrict__ eps_c,
                                  const float* __restrict__ eps_u, float cfg_scale, float sqrt_at_inv,
                                  float sqrt_aprev, float dir_coef, float sigma_t, float s1m,
                                  const float* __restrict__ noise, float temperature,
-                                 float* __restrict__ x_prev, float* __restrict__ pred_x0, int64_t n) {
+                                 float* __restrict__ x_prev, float* __restrict__ pred_x0, int64_t n,
+                                 const float* __restrict__ kfac, int n_per_sample, float* __restrict__ x_copy) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         float e = eps_c[i];
         if (eps_u) {
             const float u = eps_u[i];
-            e = u + cfg_scale * (e - u);            // model_uncond + s * (model_t - model_uncond)
+            if (kfac) e = cfg_rescaled_eps_at(e, u, cfg_scale, kfac, i, n_per_sample);
+            else e = u + cfg_scale * (e - u);       // model_uncond + s * (model_t - model_uncond)
         }
         const float xv = x[i];
         const float p0 = (xv - s1m * e) * sqrt_at_inv;   // (x - sqrt(1-a_t) e) / sqrt(a_t)
@@ -23,6 +75,7 @@ __global__ void ddim_step_kernel(const float* __restrict__ x, const float* __res
         if (noise) xp += sigma_t * noise[i] * temperature;
         x_prev[i] = xp;
         if (pred_x0) pred_x0[i] = p0;
+        if (x_copy) x_copy[i] = xp;
     }
 }
 
@@ -88,6 +141,7 @@ __global__ void step_setup_kernel(StepState* st, int64_t* t_out, int batch, cons
             st->cur[0] = st->coef[4 * i + 0]; st->cur[1] = st->coef[4 * i + 1];
             st->cur[2] = st->coef[4 * i + 2]; st->cur[3] = st->coef[4 * i + 3];
             st->cur_sigma = st->sigma[i]; st->cur_row = st->n_steps - 1 - i;
+            st->cur_trace = st->trace_row[i];
             // DPM-Solver++ loop: the step's six numbers and the ring slots of m_k, m_{k-1}, m_{k-2} (k = the executed step)
             for (int j = 0; j < 6; ++j) st->cur_dpm[j] = st->dpm[6 * i + j];
             const int k = st->n_steps - 1 - i;
@@ -112,20 +166,30 @@ __global__ void temb_select_kernel(const TembSel ts, int step) {
 }
 
 // in-place x <- x_{t-1} (eta == 0), coefficients from the step state; ends the step: the counter moves to the next one
+// The trace row (cur_trace, published by step_setup_kernel) and both trace pointers are read from the state: uniform over the grid
 __global__ void ddim_step_state_kernel(float* __restrict__ x, const float* __restrict__ eps_c, const float* __restrict__ eps_u,
-                                       float cfg_scale, StepState* __restrict__ st, int64_t n) {
+                                       float cfg_scale, StepState* __restrict__ st, int64_t n,
+                                       const float* __restrict__ kfac, int n_per_sample) {
     const float sqrt_at_inv = st->cur[0], sqrt_aprev = st->cur[1], dir_coef = st->cur[2], s1m = st->cur[3];
     const float* __restrict__ const nz = (st->noise && st->cur_sigma != 0.f) ? st->noise + (int64_t)st->cur_row * n : nullptr;
+    const int row = st->cur_trace;
+    float* __restrict__ const tx = (st->trace_x && row >= 0) ? st->trace_x + (int64_t)row * n : nullptr;
+    float* __restrict__ const tx0 = (st->trace_x0 && row >= 0) ? st->trace_x0 + (int64_t)row * n : nullptr;
     if (blockIdx.x == 0 && threadIdx.x == 0) st->counter = st->counter - 1;      // (nothing else in this kernel reads it)
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         float e = eps_c[i];
-        if (eps_u) { const float u = eps_u[i]; e = u + cfg_scale * (e - u); }
+        if (eps_u) {
+            const float u = eps_u[i];
+            if (kfac) e = cfg_rescaled_eps_at(e, u, cfg_scale, kfac, i, n_per_sample);
+            else e = u + cfg_scale * (e - u);
+        }
         const float p0 = (x[i] - s1m * e) * sqrt_at_inv;
         float xp = sqrt_aprev * p0 + dir_coef * e;
         if (nz) xp += st->cur_sigma * nz[i] * st->temperature;          // (ddim_step_kernel's order of operations: same bits as the eager loop)
         x[i] = xp;
+        if (tx) tx[i] = xp;
+        if (tx0) tx0[i] = p0;
     }
-
 }
 
 // ---- DPM-Solver++ multistep update (Lu et al. 2022, Algorithm 2; data prediction, eps parameterisation) -----------------------
@@ -144,10 +208,14 @@ __device__ __forceinline__ float dpmpp_update_at(float x, float e, const DpmCoef
 // so an order-1 or order-2 step issues no loads for the unused ring slots.  x_prev may alias x (element i is read before it is written).
 __device__ __forceinline__ void dpmpp_update_range(const float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u,
                                                    float cfg_scale, const DpmCoef k, const float* __restrict__ m1, const float* __restrict__ m2,
-                                                   float* x_prev, float* __restrict__ m0_out, int64_t n) {
+                                                   float* x_prev, float* __restrict__ m0_out, int64_t n,
+                                                   const float* __restrict__ kfac, int n_per_sample,
+                                                   float* __restrict__ x_copy, float* __restrict__ m0_copy) {
+    // kfac non-null (with eps_u): the guidance-rescaled eps; x_copy / m0_copy non-null: x_prev / m0 once more (a trace row)
     const bool use1 = k.c1 != 0.f, use2 = k.c2 != 0.f;
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
-    uintptr_t al = (uintptr_t)x | (uintptr_t)eps_c | (uintptr_t)eps_u | (uintptr_t)x_prev | (uintptr_t)m0_out;
+    uintptr_t al = (uintptr_t)x | (uintptr_t)eps_c | (uintptr_t)eps_u | (uintptr_t)x_prev | (uintptr_t)m0_out | (uintptr_t)x_copy |
+                   (uintptr_t)m0_copy;
     if (use1) al |= (uintptr_t)m1;
     if (use2) al |= (uintptr_t)m2;
     if (!(n & 3) && !(al & 15)) {
@@ -157,8 +225,13 @@ __device__ __forceinline__ void dpmpp_update_range(const float* x, const float* 
             f32x4 ev = ((const f32x4*)eps_c)[i];
             if (eps_u) {
                 const f32x4 uv = ((const f32x4*)eps_u)[i];
+                if (kfac) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) ev[j] = dpmpp_eps_at(ev[j], uv[j], cfg_scale);
+                    for (int j = 0; j < 4; ++j) ev[j] = cfg_rescaled_eps_at(ev[j], uv[j], cfg_scale, kfac, 4 * i + j, n_per_sample);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) ev[j] = dpmpp_eps_at(ev[j], uv[j], cfg_scale);
+                }
             }
             f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f}, mv, rv;
             if (use1) a = ((const f32x4*)m1)[i];
@@ -167,35 +240,43 @@ __device__ __forceinline__ void dpmpp_update_range(const float* x, const float* 
             for (int j = 0; j < 4; ++j) { float m0; rv[j] = dpmpp_update_at(xv[j], ev[j], k, a[j], b[j], m0); mv[j] = m0; }
             ((f32x4*)m0_out)[i] = mv;
             ((f32x4*)x_prev)[i] = rv;
+            if (m0_copy) ((f32x4*)m0_copy)[i] = mv;
+            if (x_copy) ((f32x4*)x_copy)[i] = rv;
         }
         return;
     }
     for (int64_t i = tid; i < n; i += nth) {
         float e = eps_c[i];
-        if (eps_u) e = dpmpp_eps_at(e, eps_u[i], cfg_scale);
+        if (eps_u) e = kfac ? cfg_rescaled_eps_at(e, eps_u[i], cfg_scale, kfac, i, n_per_sample) : dpmpp_eps_at(e, eps_u[i], cfg_scale);
         float m0;
         const float r = dpmpp_update_at(x[i], e, k, use1 ? m1[i] : 0.f, use2 ? m2[i] : 0.f, m0);
         m0_out[i] = m0;
         x_prev[i] = r;
+        if (m0_copy) m0_copy[i] = m0;
+        if (x_copy) x_copy[i] = r;
     }
 }
 
 __global__ void dpmpp_step_kernel(const float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u, float cfg_scale,
                                   const DpmCoef k, const float* __restrict__ m1, const float* __restrict__ m2, float* x_prev,
-                                  float* __restrict__ m0_out, int64_t n) {
-    dpmpp_update_range(x, eps_c, eps_u, cfg_scale, k, m1, m2, x_prev, m0_out, n);
+                                  float* __restrict__ m0_out, int64_t n, const float* __restrict__ kfac, int n_per_sample,
+                                  float* __restrict__ x_copy, float* __restrict__ m0_copy) {
+    dpmpp_update_range(x, eps_c, eps_u, cfg_scale, k, m1, m2, x_prev, m0_out, n, kfac, n_per_sample, x_copy, m0_copy);
 }
 
 // in-place x <- x_{t-1} with the coefficients and ring slots step_setup_kernel published; ends the step: the counter moves on
 __global__ void dpmpp_step_state_kernel(float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u, float cfg_scale,
-                                        StepState* st, int64_t n) {
+                                        StepState* st, int64_t n, const float* __restrict__ kfac, int n_per_sample) {
     const DpmCoef k = {st->cur_dpm[0], st->cur_dpm[1], st->cur_dpm[2], st->cur_dpm[3], st->cur_dpm[4], st->cur_dpm[5]};
+    const int row = st->cur_trace;          // (published by step_setup_kernel; uniform over the grid, like both trace pointers)
+    float* const tx = (st->trace_x && row >= 0) ? st->trace_x + (int64_t)row * n : nullptr;
+    float* const tx0 = (st->trace_x0 && row >= 0) ? st->trace_x0 + (int64_t)row * n : nullptr;
     float* const ring = st->ring;
     float* const m0 = ring + (int64_t)st->cur_slot[0] * n;
     const float* const m1 = ring + (int64_t)st->cur_slot[1] * n;
     const float* const m2 = ring + (int64_t)st->cur_slot[2] * n;
     if (blockIdx.x == 0 && threadIdx.x == 0) st->counter = st->counter - 1;      // (nothing else in this kernel reads it)
-    dpmpp_update_range(x, eps_c, eps_u, cfg_scale, k, m1, m2, x, m0, n);
+    dpmpp_update_range(x, eps_c, eps_u, cfg_scale, k, m1, m2, x, m0, n, kfac, n_per_sample, tx, tx0);
 }
 
 // ---- GEGLU: y = a * gelu_erf(gate) ----------------------------------------------------------------
@@ -574,15 +655,24 @@ inline int grid_for(int64_t total, int block = 256, int cap = 2048) {
 
 }  // namespace
 
+static int check_kfac(const float* kfac, const float* eps_u, int n_per_sample, int64_t n, const char* who) {
+    if (kfac && (!eps_u || n_per_sample <= 0 || n % n_per_sample))
+        return mkd_fail(-1, std::string(who) + ": a rescale factor needs eps_u and n_per_sample > 0 dividing n");
+    return 0;
+}
+
 int launch_ddim_step(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, float a_t,
                      float a_prev, float sigma_t, float s1m, const float* noise, float temperature,
-                     float* x_prev, float* pred_x0, int64_t n, hipStream_t stream) {
+                     float* x_prev, float* pred_x0, int64_t n, hipStream_t stream,
+                     const float* kfac, int n_per_sample, float* x_copy) {
     if (n <= 0) return mkd_fail(-1, "ddim_step: empty");
+    if (int rc = check_kfac(kfac, eps_u, n_per_sample, n, "ddim_step")) return rc;
     const float sqrt_at_inv = 1.0f / sqrtf(a_t);
     const float sqrt_aprev = sqrtf(a_prev);
     const float dir_coef = sqrtf(1.0f - a_prev - sigma_t * sigma_t);
     hipLaunchKernelGGL(ddim_step_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale,
-                       sqrt_at_inv, sqrt_aprev, dir_coef, sigma_t, s1m, noise, temperature, x_prev, pred_x0, n);
+                       sqrt_at_inv, sqrt_aprev, dir_coef, sigma_t, s1m, noise, temperature, x_prev, pred_x0, n,
+                       kfac, n_per_sample, x_copy);
     MKD_LAUNCH_CHECK("ddim_step_kernel");
     return 0;
 }
@@ -735,25 +825,38 @@ int launch_step_setup(StepState* st, int64_t* t_out, int batch, float* x, int64_
     return 0;
 }
 
+int launch_cfg_rescale_factor(const float* eps_c, const float* eps_u, float cfg_scale, float phi, const StepState* st, int batch,
+                              int n_per_sample, float* k_out, hipStream_t stream) {
+    if (!eps_c || !eps_u || !k_out || batch <= 0 || n_per_sample <= 0) return mkd_fail(-1, "cfg_rescale_factor: bad arguments");
+    hipLaunchKernelGGL(cfg_rescale_factor_kernel, dim3(batch), dim3(256), 0, stream, eps_c, eps_u, cfg_scale, phi, st, n_per_sample, k_out);
+    MKD_LAUNCH_CHECK("cfg_rescale_factor_kernel");
+    return 0;
+}
+
 int launch_ddim_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
-                           hipStream_t stream) {
-    hipLaunchKernelGGL(ddim_step_state_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale, st, n);
+                           hipStream_t stream, const float* kfac, int n_per_sample) {
+    if (int rc = check_kfac(kfac, eps_u, n_per_sample, n, "ddim_step_state")) return rc;
+    hipLaunchKernelGGL(ddim_step_state_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale, st, n, kfac, n_per_sample);
     MKD_LAUNCH_CHECK("ddim_step_state_kernel");
     return 0;
 }
 
 int launch_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, const DpmCoef& k, const float* m1,
-                      const float* m2, float* x_prev, float* m0_out, int64_t n, hipStream_t stream) {
+                      const float* m2, float* x_prev, float* m0_out, int64_t n, hipStream_t stream,
+                      const float* kfac, int n_per_sample, float* x_copy, float* m0_copy) {
     if (!x || !eps_c || !x_prev || !m0_out || n <= 0) return mkd_fail(-1, "dpmpp_step: bad arguments");
+    if (int rc = check_kfac(kfac, eps_u, n_per_sample, n, "dpmpp_step")) return rc;
     if ((k.c1 != 0.f && !m1) || (k.c2 != 0.f && !m2)) return mkd_fail(-1, "dpmpp_step: a non-zero history coefficient needs its x0-prediction");
-    hipLaunchKernelGGL(dpmpp_step_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale, k, m1, m2, x_prev, m0_out, n);
+    hipLaunchKernelGGL(dpmpp_step_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale, k, m1, m2, x_prev, m0_out, n,
+                       kfac, n_per_sample, x_copy, m0_copy);
     MKD_LAUNCH_CHECK("dpmpp_step_kernel");
     return 0;
 }
 
 int launch_dpmpp_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
-                            hipStream_t stream) {
-    hipLaunchKernelGGL(dpmpp_step_state_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale, st, n);
+                            hipStream_t stream, const float* kfac, int n_per_sample) {
+    if (int rc = check_kfac(kfac, eps_u, n_per_sample, n, "dpmpp_step_state")) return rc;
+    hipLaunchKernelGGL(dpmpp_step_state_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale, st, n, kfac, n_per_sample);
     MKD_LAUNCH_CHECK("dpmpp_step_state_kernel");
     return 0;
 }

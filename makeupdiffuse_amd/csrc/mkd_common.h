@@ -148,6 +148,15 @@ struct StepState {
     float dpm[6 * MKD_MAX_STEPS];
     float* ring;
     float cur_dpm[6]; int cur_slot[3];
+    // intermediates trace (mkd_sample_extras): entry i is logged into row trace_row[i] (-1: not logged) of trace_x (the latent after the
+    // step) and trace_x0 (the step's x0-prediction), each [rows][n] fp32 and each null when not asked for.  cur_trace: this step's row,
+    // published by step_setup_kernel next to cur_row (the step's last kernel moves the counter, so it cannot look the row up itself)
+    float* trace_x; float* trace_x0;
+    int cur_trace;
+    short trace_row[MKD_MAX_STEPS];
+    // guidance rescale (mkd_sample_extras.guidance_rescale): the phi cfg_rescale_factor_kernel reads inside a replayed step, so a new
+    // phi needs no new capture
+    float phi;
 };
 // the six schedule-only numbers of one DPM-Solver++ step
 struct DpmCoef { float inv_alpha, sigma, cx, c0, c1, c2; };
@@ -256,9 +265,17 @@ int launch_f32_to_bf16(const float* x, bf16_t* y, int64_t n, hipStream_t stream)
 int launch_timestep_embedding(const int64_t* t, bf16_t* out, int batch, int dim, hipStream_t stream);
 int launch_copy_strided(const bf16_t* src, int ld_src, bf16_t* dst, int ld_dst, int rows, int cols,
                         hipStream_t stream);
+// kfac non-null (guidance rescale, needs eps_u): e = fmaf(cfg_scale, eps_c - eps_u, eps_u) * kfac[i / n_per_sample]; x_copy non-null: x_prev
+// is stored there too (the eager loop's trace row)
 int launch_ddim_step(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, float a_t,
                      float a_prev, float sigma_t, float s1m, const float* noise, float temperature,
-                     float* x_prev, float* pred_x0, int64_t n, hipStream_t stream);
+                     float* x_prev, float* pred_x0, int64_t n, hipStream_t stream,
+                     const float* kfac = nullptr, int n_per_sample = 0, float* x_copy = nullptr);
+// guidance rescale factor, one workgroup per sample: k[b] = phi std(eps_c[b]) / std(g[b]) + (1 - phi), g = fmaf(cfg_scale, eps_c - eps_u, eps_u)
+// over the sample's n_per_sample elements; std(g) == 0: 1.  st non-null: phi is read from the step state (replayed steps).  fp64 sums in a
+// fixed order: the bits depend on nothing but the inputs
+int launch_cfg_rescale_factor(const float* eps_c, const float* eps_u, float cfg_scale, float phi, const StepState* st, int batch,
+                              int n_per_sample, float* k_out, hipStream_t stream);
 int launch_repeat_batch(const float* x, float* y, int64_t n_per, int reps, hipStream_t stream);
 int launch_fill_i64(int64_t* p, int64_t v, int n, hipStream_t stream);
 // first kernel of a replayed step: timestep / coefficients of step st->counter (+ the step's time-embedding rows when ts != null,
@@ -286,14 +303,16 @@ int launch_hist_match(const float* dst, const float* ref, const uint8_t* mask_ds
                       int W, float* matched, uint8_t* tables, float* loss, int32_t* counts, void* scratch, hipStream_t stream);
 int launch_temb_select(const TembSel& ts, int step, hipStream_t stream);          // the same copy with a host-side step index (eager loop)
 int launch_ddim_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
-                           hipStream_t stream);
+                           hipStream_t stream, const float* kfac = nullptr, int n_per_sample = 0);
 // DPM-Solver++ multistep update (kernels_misc.hip): m0_out <- (x - sigma e) / alpha, x_prev <- c_x x + c_0 m0 + c_1 m1 + c_2 m2 with
 // e = eps_u + cfg_scale (eps_c - eps_u) (eps_u null: eps_c).  m1 / m2 are read only where their coefficient is non-zero; x_prev may be x.
+// kfac / n_per_sample as in launch_ddim_step; x_copy / m0_copy non-null: x_prev / m0 are stored there too (the eager loop's trace rows)
 int launch_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, const DpmCoef& k, const float* m1,
-                      const float* m2, float* x_prev, float* m0_out, int64_t n, hipStream_t stream);
+                      const float* m2, float* x_prev, float* m0_out, int64_t n, hipStream_t stream,
+                      const float* kfac = nullptr, int n_per_sample = 0, float* x_copy = nullptr, float* m0_copy = nullptr);
 // the same update in place with the coefficients / ring slots step_setup_kernel published; the step's LAST kernel: advances the counter
 int launch_dpmpp_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
-                            hipStream_t stream);
+                            hipStream_t stream, const float* kfac = nullptr, int n_per_sample = 0);
 int launch_softmax_rows(const bf16_t* x, bf16_t* y, int rows, int cols, hipStream_t stream);
 int launch_post_quant(const float* z, const bf16_t* w, const float* bias, float inv_scale, float* out, int batch, int C, int hw,
                       hipStream_t stream);

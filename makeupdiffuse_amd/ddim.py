@@ -31,6 +31,24 @@ def _check_mask(mask, x0, shape):
         raise ValueError(f'DDIMSampler: mask must be [1 or {B}, 1 or {C}, {H}, {W}], got {tuple(mask.shape)}')
 
 
+def _check_rescale(phi) -> float:
+    """guidance_rescale (phi of Lin et al. 2023, section 3.4) as a float in [0, 1]"""
+    phi = float(phi)
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f'guidance_rescale must lie in [0, 1], got {phi}')
+    return phi
+
+
+def rescale_guided_eps(e_c, e_u, scale, phi):
+    """The guided eps with guidance rescale, in torch (host tensors; the device path is mkd_cfg_rescale_factor + the step kernels):
+    g = e_u + scale (e_c - e_u), per sample k = phi std(e_c) / std(g) + (1 - phi) (std(g) == 0: 1), returns g k."""
+    g = e_u + scale * (e_c - e_u)
+    dims = tuple(range(1, g.dim()))
+    s_c, s_g = e_c.std(dim=dims, keepdim=True), g.std(dim=dims, keepdim=True)
+    k = torch.where(s_g > 0, phi * s_c / torch.where(s_g > 0, s_g, torch.ones_like(s_g)) + (1.0 - phi), torch.ones_like(s_g))
+    return g * k
+
+
 def _cat_cond(uncond, c):
     """CFG batching, unconditional FIRST (diffmk/cddim.py:18-38)."""
     if isinstance(c, dict):
@@ -86,7 +104,7 @@ class DDIMSampler:
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, eta=0.0, temperature=1.0, noise_dropout=0.0,
                x_T=None, log_every_t=100, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
-               verbose=True, **kwargs):
+               verbose=True, guidance_rescale=0.0, **kwargs):
         for k in ('score_corrector', 'corrector_kwargs', 'dynamic_threshold', 'ucg_schedule'):
             if kwargs.get(k) is not None:
                 raise NotImplementedError(f'DDIMSampler.sample option {k} is not on the MakeupDiffuse path')
@@ -96,18 +114,26 @@ class DDIMSampler:
         size = (batch_size, C, H, W)
         mask, x0 = kwargs.get('mask'), kwargs.get('x0')
         _check_mask(mask, x0, size)
+        _check_rescale(guidance_rescale)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         return self.ddim_sampling(conditioning, size, callback=callback, x_T=x_T, log_every_t=log_every_t,
                                   temperature=temperature, noise_dropout=noise_dropout,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0)
+                                  unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0,
+                                  guidance_rescale=guidance_rescale)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, callback=None, log_every_t=100, temperature=1.0, noise_dropout=0.0,
-                      unconditional_guidance_scale=1.0, unconditional_conditioning=None, timesteps=None, mask=None, x0=None):
+                      unconditional_guidance_scale=1.0, unconditional_conditioning=None, timesteps=None, mask=None, x0=None,
+                      guidance_rescale=0.0):
         """mask / x0 (UPSTREAM): before step i, img = q_sample(x0, ts) * mask + (1 - mask) * img with a fresh randn_like(x0) drawn
-        BEFORE the step's eta draw; mask = 1 keeps x0, no blend after the last step."""
+        BEFORE the step's eta draw; mask = 1 keeps x0, no blend after the last step.  intermediates: x_inter / pred_x0 =
+        [x_T, one entry per step with index % log_every_t == 0 or index == total_steps - 1], from the in-library loop's trace or the
+        step loop alike.  guidance_rescale = phi in [0, 1], engaged with guidance and phi > 0."""
         _check_mask(mask, x0, tuple(shape))
+        phi = _check_rescale(guidance_rescale)
+        if unconditional_conditioning is None or unconditional_guidance_scale == 1.0:
+            phi = 0.0          # no unconditional half: not engaged
         device = self.model.device
         b = shape[0]
         img = torch.randn(shape, device=device) if x_T is None else x_T
@@ -146,10 +172,19 @@ class DDIMSampler:
                     sa, s1 = self._q_tables()
                     kw.update(x0=x0, mask=mask, q_sqrt_ac=[float(sa[int(t)]) for t in timesteps],
                               q_sqrt_1m_ac=[float(s1[int(t)]) for t in timesteps], q_noise=torch.stack(q_draws))
-            img = fast(img, cond, timesteps, self.ddim_alphas[:total_steps], self.ddim_alphas_prev[:total_steps],
+            kw['log_every_t'] = int(log_every_t)          # the loop's trace: the rows the step loop below appends
+            if phi != 0.0:
+                kw['guidance_rescale'] = phi
+            res = fast(img, cond, timesteps, self.ddim_alphas[:total_steps], self.ddim_alphas_prev[:total_steps],
                        self.ddim_sqrt_one_minus_alphas[:total_steps], unconditional_guidance_scale,
                        unconditional_conditioning, **kw)
-            intermediates['x_inter'].append(img)
+            if isinstance(res, tuple):          # (latent, x_inter rows, pred_x0 rows); the latent stays the last x_inter entry
+                img, x_rows, x0_rows = res
+                intermediates['x_inter'] += [*x_rows[:-1], img]
+                intermediates['pred_x0'] += list(x0_rows)
+            else:                               # a hook that keeps no trace
+                img = res
+                intermediates['x_inter'].append(img)
             return img, intermediates
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
@@ -159,7 +194,7 @@ class DDIMSampler:
             img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, temperature=temperature,
                                               noise_dropout=noise_dropout,
                                               unconditional_guidance_scale=unconditional_guidance_scale,
-                                              unconditional_conditioning=unconditional_conditioning)
+                                              unconditional_conditioning=unconditional_conditioning, guidance_rescale=phi)
             if callback:
                 callback(i)
             if index % log_every_t == 0 or index == total_steps - 1:
@@ -170,15 +205,16 @@ class DDIMSampler:
     @torch.no_grad()
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1.0, noise_dropout=0.0, score_corrector=None, corrector_kwargs=None,
-                      unconditional_guidance_scale=1.0, unconditional_conditioning=None, dynamic_threshold=None):
+                      unconditional_guidance_scale=1.0, unconditional_conditioning=None, dynamic_threshold=None,
+                      guidance_rescale=0.0):
         return self._step(x, c, t, index, repeat_noise, use_original_steps, quantize_denoised, temperature, noise_dropout,
                           score_corrector, corrector_kwargs, unconditional_guidance_scale, unconditional_conditioning,
-                          dynamic_threshold)
+                          dynamic_threshold, _check_rescale(guidance_rescale))
 
     # One DDIM step; shared by p_sample_ddim and MKDDIMSampler.denoising_step (same arithmetic, SURVEY.md finding 6).
     def _step(self, x, c, t, index, repeat_noise, use_original_steps, quantize_denoised, temperature, noise_dropout,
               score_corrector, corrector_kwargs, unconditional_guidance_scale, unconditional_conditioning,
-              dynamic_threshold):
+              dynamic_threshold, guidance_rescale=0.0):
         b, device = x.shape[0], x.device
         if getattr(self.model, 'parameterization', 'eps') != 'eps':
             raise NotImplementedError("only parameterization 'eps' (yaml :50) is supported")
@@ -199,7 +235,8 @@ class DDIMSampler:
             noise = noise_like(x.shape, device, repeat_noise)
             if noise_dropout > 0.0:
                 noise = torch.nn.functional.dropout(noise, p=noise_dropout)
-        return self._update(x, e_c, e_u, unconditional_guidance_scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature)
+        return self._update(x, e_c, e_u, unconditional_guidance_scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature,
+                            guidance_rescale)
 
     # (e_c, e_u) of one step: CFG batches [uncond; cond] through ONE apply_model; e_u None without guidance
     def _eps(self, x, c, t, unconditional_guidance_scale, unconditional_conditioning):
@@ -214,12 +251,18 @@ class DDIMSampler:
         return e_c, e_u
 
     # the eta-DDIM update x_prev(x, eps) with the coefficients of one step: on the device through the model's hook
-    def _update(self, x, e_c, e_u, unconditional_guidance_scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature):
+    def _update(self, x, e_c, e_u, unconditional_guidance_scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature,
+                guidance_rescale=0.0):
+        rescale = e_u is not None and guidance_rescale != 0.0
         step_fn = getattr(self.model, 'ddim_step', None)
         if step_fn is not None and x.is_cuda:
-            return step_fn(x, e_c, e_u, unconditional_guidance_scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature)
+            kw = {'guidance_rescale': guidance_rescale} if rescale else {}
+            return step_fn(x, e_c, e_u, unconditional_guidance_scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature, **kw)
         # host tensors (plumbing with a stand-in model, e.g. CPU tests): same formulae in torch
-        e_t = e_c if e_u is None else e_u + unconditional_guidance_scale * (e_c - e_u)
+        if rescale:
+            e_t = rescale_guided_eps(e_c, e_u, unconditional_guidance_scale, guidance_rescale)
+        else:
+            e_t = e_c if e_u is None else e_u + unconditional_guidance_scale * (e_c - e_u)
         pred_x0 = (x - s1m_t * e_t) / a_t ** 0.5
         dir_xt = (1.0 - a_prev - sigma_t ** 2) ** 0.5 * e_t
         x_prev = a_prev ** 0.5 * pred_x0 + dir_xt

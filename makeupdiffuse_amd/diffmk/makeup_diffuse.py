@@ -263,8 +263,9 @@ class BaseMakeUpDiffuse:
         return a * x_t - b * noise
 
     # hooks the samplers use to stay on the device ----------------------------------------------------------------
-    def ddim_step(self, x, e_c, e_u, scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature):
-        return self._require_engine().ddim_step(x, e_c, e_u, scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature)
+    def ddim_step(self, x, e_c, e_u, scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature, guidance_rescale=0.0):
+        return self._require_engine().ddim_step(x, e_c, e_u, scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature,
+                                                guidance_rescale=guidance_rescale)
 
     def q_sample_blend(self, x0, noise, sqrt_ac, sqrt_1m_ac, mask=None, x=None):
         """(sqrt_ac x0 + sqrt_1m_ac noise) * mask + (1 - mask) * x: the masked sampler's blend (mask None: q_sample), same kernel
@@ -282,28 +283,34 @@ class BaseMakeUpDiffuse:
 
     def sample_loop_fast(self, x_latent, cond, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas,
                          unconditional_guidance_scale=1.0, unconditional_conditioning=None, sigmas=None, noise=None, temperature=1.0,
-                         x0=None, mask=None, q_sqrt_ac=None, q_sqrt_1m_ac=None, q_noise=None):
+                         x0=None, mask=None, q_sqrt_ac=None, q_sqrt_1m_ac=None, q_noise=None, log_every_t=None, guidance_rescale=0.0):
+        """log_every_t not None: (latent, x_inter rows, pred_x0 rows) with the loop's trace (MkdEngine.sample want_trace)"""
         eng, cfg_scale = self._bind_guided(cond, unconditional_conditioning, unconditional_guidance_scale, x_latent.shape[2:])
+        trace = {} if log_every_t is None else dict(log_every_t=int(log_every_t), want_trace=True)
         return eng.sample(x_latent, [int(v) for v in timesteps], [float(v) for v in alphas], [float(v) for v in alphas_prev],
                           [float(v) for v in sqrt_one_minus_alphas],
                           cfg_scale=cfg_scale, use_graph=bool(self.sample_use_graph),
                           sigmas=None if sigmas is None else [float(v) for v in sigmas], noise=noise, temperature=float(temperature),
-                          x0=x0, mask=mask, q_sqrt_ac=q_sqrt_ac, q_sqrt_1m_ac=q_sqrt_1m_ac, q_noise=q_noise)
+                          x0=x0, mask=mask, q_sqrt_ac=q_sqrt_ac, q_sqrt_1m_ac=q_sqrt_1m_ac, q_noise=q_noise,
+                          guidance_rescale=float(guidance_rescale), **trace)
 
-    def dpmpp_step(self, x, e_c, e_u, scale, coef6, m1=None, m2=None):
+    def dpmpp_step(self, x, e_c, e_u, scale, coef6, m1=None, m2=None, guidance_rescale=0.0):
         """one DPM-Solver++ multistep update on the device (DPMSolverSampler's per-step loop): (x_prev, x0-prediction), the kernel
         arithmetic of the in-library loop"""
-        return self._require_engine().dpmpp_step(x, e_c, e_u, scale, coef6, m1, m2)
+        return self._require_engine().dpmpp_step(x, e_c, e_u, scale, coef6, m1, m2, guidance_rescale=guidance_rescale)
 
     def sample_loop_dpmpp(self, x_latent, cond, timesteps, alphas, alphas_prev, order=2, lower_order_final=True,
                           unconditional_guidance_scale=1.0, unconditional_conditioning=None, x0=None, mask=None, q_sqrt_ac=None,
-                          q_sqrt_1m_ac=None, q_noise=None):
-        """the whole DPM-Solver++ multistep loop inside libmkd (mkd_sample_dpmpp), on the tables sample_loop_fast takes"""
+                          q_sqrt_1m_ac=None, q_noise=None, log_every_t=None, guidance_rescale=0.0):
+        """the whole DPM-Solver++ multistep loop inside libmkd (mkd_sample_dpmpp), on the tables sample_loop_fast takes; log_every_t
+        as there"""
         eng, cfg_scale = self._bind_guided(cond, unconditional_conditioning, unconditional_guidance_scale, x_latent.shape[2:])
+        trace = {} if log_every_t is None else dict(log_every_t=int(log_every_t), want_trace=True)
         return eng.sample_dpmpp(x_latent, [int(v) for v in timesteps], [float(v) for v in alphas], [float(v) for v in alphas_prev],
                                 order=int(order), lower_order_final=bool(lower_order_final),
                                 cfg_scale=cfg_scale, use_graph=bool(self.sample_use_graph),
-                                x0=x0, mask=mask, q_sqrt_ac=q_sqrt_ac, q_sqrt_1m_ac=q_sqrt_1m_ac, q_noise=q_noise)
+                                x0=x0, mask=mask, q_sqrt_ac=q_sqrt_ac, q_sqrt_1m_ac=q_sqrt_1m_ac, q_noise=q_noise,
+                                guidance_rescale=float(guidance_rescale), **trace)
 
     def latent_mask_from_labels(self, seg: torch.Tensor, classes: Sequence[int] = (0, 11, 12), factor: int = 8,
                                 threshold: float = 0.5) -> torch.Tensor:
@@ -416,7 +423,12 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                  unconditional_guidance_scale: float = 9, ddim_steps: int = 50, ddim_eta: float = 0.0, sample: bool = True,
                  fix_background: bool = False, background_classes: Sequence[int] = (0, 11, 12), background_threshold: float = 0.5,
                  seg_key: str = 'nonmakeup_seg', makeup_score: bool = False, ref_seg_key: str = 'makeup_seg', sampler: str = 'ddim',
-                 solver_order: int = 2, paste_background: bool = False, paste_feather: int = 0, *args, **kwargs):
+                 solver_order: int = 2, paste_background: bool = False, paste_feather: int = 0, denoise_rows: bool = False,
+                 log_every_t: int = 100, guidance_rescale: float = 0.0, *args, **kwargs):
+        if int(log_every_t) < 1:
+            raise ValueError(f'log_every_t must be >= 1, got {log_every_t}')
+        if not 0.0 <= float(guidance_rescale) <= 1.0:
+            raise ValueError(f'guidance_rescale must lie in [0, 1], got {guidance_rescale}')
         if not 0 <= int(paste_feather) <= 16:
             raise ValueError(f'paste_feather must be 0..16 image pixels, got {paste_feather}')
         if sampler not in ('ddim', 'dpmpp'):
@@ -440,6 +452,12 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         # mask).  Independent of fix_background (needs neither the encoder nor masked sampling); off: log_results is unchanged
         self.paste_background = bool(paste_background)
         self.paste_feather = int(paste_feather)
+        # denoise rows (reference log_images plot_denoise_rows / _get_denoise_row_from_list): log_results also returns the decoded pred_x0
+        # list of each pass, logged every log_every_t table entries by the in-library loop's trace.  Off: log_results is unchanged
+        self.denoise_rows = bool(denoise_rows)
+        self.log_every_t = int(log_every_t)
+        # guidance rescale phi of the guided pass(es) (per-sample std ratio inside every step); 0: off, today's path
+        self.guidance_rescale = float(guidance_rescale)
         self.unconditional_guidance_scale = unconditional_guidance_scale
         self.ddim_steps, self.ddim_eta, self.sample = ddim_steps, ddim_eta, sample
         self.saved_dir, self.model_name, self.img_name_key = saved_dir, model_name, img_name_key
@@ -485,10 +503,14 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         if self.paste_background:
             self._check_paste(batch, 'paste_background')
         cond = {'c_concat': [c_cat], 'c_crossattn': [c_txt]}
+        if self.denoise_rows:
+            extra['log_every_t'] = self.log_every_t
         if self.sample:
-            samples, _ = self.sample_log(cond=cond, batch_size=b, ddim=use_ddim, ddim_steps=self.ddim_steps,
-                                         eta=self.ddim_eta, **extra)
+            samples, inter = self.sample_log(cond=cond, batch_size=b, ddim=use_ddim, ddim_steps=self.ddim_steps,
+                                             eta=self.ddim_eta, **extra)
             log['samples_latent'] = samples
+            if self.denoise_rows:
+                self._log_denoise_row(log, 'denoise_row', inter['pred_x0'])
             if self.has_first_stage:
                 log['samples'] = self.decode_first_stage(samples)
                 if self.paste_background:
@@ -497,11 +519,15 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                     log['makeup_hist'] = self.makeup_hist(batch, log['samples'], c['ref_img'])
         if self.unconditional_guidance_scale > 1.0:
             uc_full = {'c_concat': [c_cat], 'c_crossattn': [self.get_unconditional_conditioning(b)]}
-            samples_cfg, _ = self.sample_log(cond=cond, batch_size=b, ddim=use_ddim, ddim_steps=self.ddim_steps,
-                                             eta=self.ddim_eta, unconditional_guidance_scale=self.unconditional_guidance_scale,
-                                             unconditional_conditioning=uc_full, **extra)
+            if self.guidance_rescale != 0.0:
+                extra['guidance_rescale'] = self.guidance_rescale
+            samples_cfg, inter = self.sample_log(cond=cond, batch_size=b, ddim=use_ddim, ddim_steps=self.ddim_steps,
+                                                 eta=self.ddim_eta, unconditional_guidance_scale=self.unconditional_guidance_scale,
+                                                 unconditional_conditioning=uc_full, **extra)
             name = f'samples_cfg_scale_{self.unconditional_guidance_scale:.2f}'
             log[name + '_latent'] = samples_cfg
+            if self.denoise_rows:
+                self._log_denoise_row(log, f'denoise_row_cfg_scale_{self.unconditional_guidance_scale:.2f}', inter['pred_x0'])
             if self.has_first_stage:
                 log[name] = self.decode_first_stage(samples_cfg)
                 if self.paste_background:
@@ -509,6 +535,16 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                 if self.makeup_score:
                     log[f'makeup_hist_cfg_scale_{self.unconditional_guidance_scale:.2f}'] = self.makeup_hist(batch, log[name], c['ref_img'])
         return log
+
+    def _log_denoise_row(self, log: dict, name: str, pred_x0: list) -> None:
+        """reference _get_denoise_row_from_list before its make_grid: the pred_x0 list of a pass (x_T first, then one entry per logged
+        step) stacked 'n b c h w -> (b n) c h w', samples as rows and list entries as columns: entry [i * n + j] is sample i at list
+        entry j.  name_latent holds the latents, name their decode_first_stage images (each list entry decoded as one batch)."""
+        lat = torch.stack(list(pred_x0), dim=1)
+        log[name + '_latent'] = lat.reshape(-1, *lat.shape[2:])
+        if self.has_first_stage:
+            img = torch.stack([self.decode_first_stage(z) for z in pred_x0], dim=1)
+            log[name] = img.reshape(-1, *img.shape[2:])
 
     @torch.no_grad()
     def makeup_hist(self, batch: dict, sample: torch.Tensor, ref: torch.Tensor) -> torch.Tensor:
@@ -597,7 +633,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
     @torch.no_grad()
     def transfer_regions(self, batch: dict, refs: Dict[str, str], strengths: Optional[dict] = None, base: str = 'ref', feather: int = 1,
                          x_T: Optional[torch.Tensor] = None, unconditional_guidance_scale: float = 1.0,
-                         paste_outside: bool = False) -> Dict[str, torch.Tensor]:
+                         paste_outside: bool = False, guidance_rescale: Optional[float] = None) -> Dict[str, torch.Tensor]:
         """Region-wise makeup transfer from several references (partial transfer as SCGAN / EleGANt / PSGAN offer it; the reference
         has no code for it, so the definition is this build's): ``refs`` maps the user regions 'eye', 'lip', 'skin' to the
         batch keys of their reference images; the ControlNet hint embeddings E(src||ref_r) are blended PER LATENT PIXEL with the
@@ -608,8 +644,12 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         base, then the regions in priority order) and, with a first-stage decoder, samples.  With the paste_background option the samples
         keep the source's pixels over background_classes (mask_pixel holds the weights); ``paste_outside`` (base='source' only) then also
         pastes the source over everything that belongs to NONE of the chosen regions, feathered by paste_feather (weights: mask_outside),
-        so that "lips only" leaves the rest of the face alone."""
+        so that "lips only" leaves the rest of the face alone.  ``guidance_rescale`` (default: the model's setting) is the phi of the
+        guided pass, engaged with unconditional_guidance_scale != 1 and phi > 0."""
         from .. import regions as rg
+        phi = float(self.guidance_rescale if guidance_rescale is None else guidance_rescale)
+        if not 0.0 <= phi <= 1.0:
+            raise ValueError(f'guidance_rescale must lie in [0, 1], got {phi}')
         regs = rg.ordered(refs)
         if base not in ('ref', 'source'):
             raise ValueError(f"base must be 'ref' or 'source', got {base!r}")
@@ -655,10 +695,10 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         a, ap = [float(v) for v in sch.ddim_alphas], [float(v) for v in sch.ddim_alphas_prev]
         if self.sampler == 'dpmpp':
             lat = eng.sample_dpmpp(x_T, ts, a, ap, order=self.solver_order, lower_order_final=True, cfg_scale=scale,
-                                   use_graph=bool(self.sample_use_graph))
+                                   use_graph=bool(self.sample_use_graph), guidance_rescale=phi)
         elif self.sampler == 'ddim':
             lat = eng.sample(x_T, ts, a, ap, [float(v) for v in sch.ddim_sqrt_one_minus_alphas], cfg_scale=scale,
-                             use_graph=bool(self.sample_use_graph))
+                             use_graph=bool(self.sample_use_graph), guidance_rescale=phi)
         else:
             raise ValueError(f"sampler must be 'ddim' or 'dpmpp', got {self.sampler!r}")
         out = {'samples_latent': lat, 'weights': weights}
@@ -674,7 +714,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
 
     @torch.no_grad()
     def transfer_photos(self, src_photos, ref_photos, src_boxes, ref_boxes, src_segs=None, feather: int = 8,
-                        x_T: Optional[torch.Tensor] = None, size: int = 256, batch: Optional[dict] = None) -> List[torch.Tensor]:
+                        x_T: Optional[torch.Tensor] = None, size: int = 256, batch: Optional[dict] = None,
+                        guidance_rescale: Optional[float] = None) -> List[torch.Tensor]:
         """Makeup transfer on photographs at their own resolution: ``src_photos`` / ``ref_photos`` are uint8 [H,W,3] tensors of any
         size (lists; the photos of a call may differ in size) with a face box (x0, y0, w, h) each.  Both boxes are crop-resized to
         ``size`` on the device (photo.crop_resize: Pillow's antialiased bilinear bytes / 255, what PairFolderDataset gives for that
@@ -682,8 +723,12 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         unconditional_guidance_scale > 1, with the fix_background / paste_background settings on the crop-resized ``src_segs`` (label
         maps at photo resolution) -- the latent is decoded and pasted into CLONES of the source photos with their fine detail kept
         (photo.paste_photos, ``feather`` photo pixels at the box sides).  ``batch`` carries the text fields get_input reads (txt_emb /
-        txt_tokens / txt); without it the prompt is 'makeup transfer'.  Returns the uint8 [H,W,3] device tensors."""
+        txt_tokens / txt); without it the prompt is 'makeup transfer'.  ``guidance_rescale`` (default: the model's setting): the phi
+        of the guided pass.  Returns the uint8 [H,W,3] device tensors."""
         from .. import photo
+        phi = float(self.guidance_rescale if guidance_rescale is None else guidance_rescale)
+        if not 0.0 <= phi <= 1.0:
+            raise ValueError(f'guidance_rescale must lie in [0, 1], got {phi}')
         if not self.has_first_stage:
             raise ValueError('transfer_photos pastes decoded images: it needs a first stage (first_stage_config)')
         if (self.fix_background or self.paste_background) and src_segs is None:
@@ -707,6 +752,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         if scale > 1.0:           # log_results' guided pass: the unconditional branch keeps the SAME hint
             extra.update(unconditional_guidance_scale=scale,
                          unconditional_conditioning={'c_concat': cond['c_concat'], 'c_crossattn': [self.get_unconditional_conditioning(n)]})
+            if phi != 0.0:
+                extra['guidance_rescale'] = phi
         lat, _ = self.sample_log(cond=cond, batch_size=n, ddim=True, ddim_steps=self.ddim_steps, eta=self.ddim_eta, **extra)
         img = self.decode_first_stage(lat)
         if self.paste_background:

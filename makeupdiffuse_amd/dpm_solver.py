@@ -14,7 +14,7 @@ import math
 import numpy as np
 import torch
 
-from .ddim import DDIMSampler, _check_mask
+from .ddim import DDIMSampler, _check_mask, _check_rescale, rescale_guided_eps
 
 __all__ = ['DPMSolverSampler', 'dpmpp_coefficients']
 
@@ -82,7 +82,10 @@ class DPMSolverSampler:
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, x_T=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
-               order=2, lower_order_final=True, callback=None, mask=None, x0=None, **kw):
+               order=2, lower_order_final=True, callback=None, mask=None, x0=None, log_every_t=100, guidance_rescale=0.0, **kw):
+        """intermediates as DDIMSampler's: x_inter / pred_x0 = [x_T, one entry per step with index % log_every_t == 0 or the first
+        executed one] (pred_x0: the solver's m_k), from the in-library loop's trace or the step loop alike.  guidance_rescale = phi in
+        [0, 1], engaged with guidance and phi > 0."""
         if kw.get('eta') not in (None, 0, 0.0):
             raise NotImplementedError('DPMSolverSampler is deterministic: eta is not an option of DPM-Solver++')
         for k in self._REJECTED:
@@ -95,12 +98,18 @@ class DPMSolverSampler:
         C, H, W = shape
         size = (batch_size, C, H, W)
         _check_mask(mask, x0, size)
+        phi = _check_rescale(guidance_rescale)
+        if unconditional_conditioning is None or unconditional_guidance_scale == 1.0:
+            phi = 0.0          # no unconditional half: not engaged
+        if int(log_every_t) < 1:
+            raise ValueError(f'log_every_t must be >= 1, got {log_every_t}')
         self.make_schedule(S, verbose=False)
         img = torch.randn(size, device=self.model.device) if x_T is None else x_T
-        intermediates = {'x_inter': [img]}
+        intermediates = {'x_inter': [img], 'pred_x0': [img]}
         img = self._loop(img, conditioning, len(self.ddim_timesteps), unconditional_guidance_scale, unconditional_conditioning, order,
-                         lower_order_final, callback, mask, x0)
-        intermediates['x_inter'].append(img)
+                         lower_order_final, callback, mask, x0, trace=(int(log_every_t), intermediates), phi=phi)
+        if len(intermediates['x_inter']) == 1:          # (a hook that keeps no trace)
+            intermediates['x_inter'].append(img)
         return img, intermediates
 
     @torch.no_grad()
@@ -116,7 +125,8 @@ class DPMSolverSampler:
                           callback, None, None)
 
     # the loop over the first n table entries, newest first
-    def _loop(self, img, cond, n, scale, uc, order, lower_order_final, callback, mask, x0):
+    # trace = (log_every_t, the intermediates dict to append to) or None; phi: the engaged guidance rescale (0: off)
+    def _loop(self, img, cond, n, scale, uc, order, lower_order_final, callback, mask, x0, trace=None, phi=0.0):
         timesteps = self.ddim_timesteps[:n]
         a = [float(v) for v in self.ddim_alphas[:n]]
         ap = [float(v) for v in self.ddim_alphas_prev[:n]]
@@ -130,7 +140,17 @@ class DPMSolverSampler:
                 kw = dict(x0=x0, mask=mask, q_sqrt_ac=[float(sa[int(t)]) for t in timesteps],
                           q_sqrt_1m_ac=[float(s1[int(t)]) for t in timesteps],
                           q_noise=torch.stack([torch.randn_like(x0) for _ in range(n)]))
-            return fast(img, cond, timesteps, a, ap, order, lower_order_final, scale, uc, **kw)
+            if trace is not None:
+                kw['log_every_t'] = trace[0]
+            if phi != 0.0:
+                kw['guidance_rescale'] = phi
+            res = fast(img, cond, timesteps, a, ap, order, lower_order_final, scale, uc, **kw)
+            if not isinstance(res, tuple):
+                return res
+            img, x_rows, x0_rows = res          # (latent, x_inter rows, pred_x0 rows); the latent stays the last x_inter entry
+            trace[1]['x_inter'] += [*x_rows[:-1], img]
+            trace[1]['pred_x0'] += list(x0_rows)
+            return img
         step_fn = getattr(self.model, 'dpmpp_step', None)
         on_device = step_fn is not None and img.is_cuda
         if on_device:
@@ -146,12 +166,16 @@ class DPMSolverSampler:
             if mask is not None:
                 img = self._ddim._q_blend(x0, step, mask, img)
             e_c, e_u = self._ddim._eps(img, cond, ts, scale, uc)
+            rescale = e_u is not None and phi != 0.0
             if on_device:
-                img, m0 = step_fn(img, e_c, e_u, scale, coef[index], hist[0], hist[1])
+                img, m0 = step_fn(img, e_c, e_u, scale, coef[index], hist[0], hist[1], **({'guidance_rescale': phi} if rescale else {}))
             else:
                 # host tensors (plumbing with a stand-in model, e.g. CPU tests): the same formulae in torch
                 inv_alpha, sigma, cx, c0, c1, c2 = (float(v) for v in coef[index])
-                e_t = e_c if e_u is None else e_u + scale * (e_c - e_u)
+                if rescale:
+                    e_t = rescale_guided_eps(e_c, e_u, scale, phi)
+                else:
+                    e_t = e_c if e_u is None else e_u + scale * (e_c - e_u)
                 m0 = (img - sigma * e_t) * inv_alpha
                 img = cx * img + c0 * m0
                 if c1 != 0.0:
@@ -161,4 +185,7 @@ class DPMSolverSampler:
             hist = [m0, hist[0]]
             if callback:
                 callback(k)
+            if trace is not None and (index % trace[0] == 0 or index == n - 1):
+                trace[1]['x_inter'].append(img)
+                trace[1]['pred_x0'].append(m0)
         return img

@@ -151,6 +151,23 @@ def dpmpp_table(alphas: Sequence[float], alphas_prev: Sequence[float], order: in
     return np.ctypeslib.as_array(out).reshape(n, 6).copy(), np.ctypeslib.as_array(so).astype(np.int32)
 
 
+def sample_log_rows(n_steps: int, log_every_t: int) -> int:
+    """Rows the in-library loop's trace keeps (include/mkd.h mkd_sample_log_rows; host only): the table entries i of an n_steps loop
+    with ``i % log_every_t == 0 or i == n_steps - 1``."""
+    rows = _lib.load().mkd_sample_log_rows(int(n_steps), int(log_every_t))
+    if rows < 0:
+        raise ValueError('sample_log_rows: n_steps >= 1 and log_every_t >= 1')
+    return rows
+
+
+def check_guidance_rescale(phi) -> float:
+    """phi of the guidance rescale as a float in [0, 1] (ValueError otherwise)"""
+    phi = float(phi)
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f'guidance_rescale must lie in [0, 1], got {phi}')
+    return phi
+
+
 class MkdEngine:
     """Owns one mkd_ctx on the current CUDA(HIP) device."""
 
@@ -492,13 +509,43 @@ class MkdEngine:
                                         C.c_void_p(out.data_ptr()), C.c_void_p(_stream())), 'mkd_eps')
         return out
 
+    def cfg_rescale_factor(self, eps_c: torch.Tensor, eps_u: torch.Tensor, cfg_scale: float, phi: float) -> torch.Tensor:
+        """Guidance-rescale factors (mkd_cfg_rescale_factor): k [B] = phi std(eps_c[b]) / std(g[b]) + (1 - phi) per sample of
+        [B, ...] tensors, g = eps_u + cfg_scale (eps_c - eps_u)."""
+        phi = check_guidance_rescale(phi)
+        eps_c = _f32c(eps_c, self.device); eps_u = _f32c(eps_u, self.device)
+        if eps_c.dim() < 2 or eps_u.shape != eps_c.shape:
+            raise ValueError('cfg_rescale_factor: eps_c and eps_u must be [B, ...] tensors of one shape')
+        k = torch.empty(eps_c.shape[0], device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mkd_cfg_rescale_factor(C.c_void_p(eps_c.data_ptr()), C.c_void_p(eps_u.data_ptr()), float(cfg_scale), phi,
+                                                       eps_c.shape[0], eps_c[0].numel(), C.c_void_p(k.data_ptr()), C.c_void_p(_stream())),
+                       'mkd_cfg_rescale_factor')
+        return k
+
+    def _rescale_k(self, eps_c, eps_u, cfg_scale, guidance_rescale):
+        """(k [B] or None, elements per sample) of one stand-alone step: engaged only with an unconditional half and phi > 0"""
+        phi = check_guidance_rescale(guidance_rescale)
+        if eps_u is None or phi == 0.0:
+            return None, 0
+        return self.cfg_rescale_factor(eps_c, eps_u, cfg_scale, phi), eps_c[0].numel()
+
     def ddim_step(self, x, eps_c, eps_u, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, noise=None,
-                  temperature: float = 1.0, want_x0: bool = True):
+                  temperature: float = 1.0, want_x0: bool = True, guidance_rescale: float = 0.0):
         x = _f32c(x, self.device); eps_c = _f32c(eps_c, self.device)
         eps_u = None if eps_u is None else _f32c(eps_u, self.device)
         noise = None if noise is None else _f32c(noise, self.device)
         x_prev = torch.empty_like(x)
         x0 = torch.empty_like(x) if want_x0 else None
+        k, per = self._rescale_k(eps_c, eps_u, cfg_scale, guidance_rescale)
+        if k is not None:           # the rescaled eps: the factor launch, then the step with k (the in-library loop's two kernels)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.mkd_ddim_step_ex(C.c_void_p(x.data_ptr()), C.c_void_p(eps_c.data_ptr()), C.c_void_p(eps_u.data_ptr()),
+                                                     float(cfg_scale), float(a_t), float(a_prev), float(sigma_t),
+                                                     float(sqrt_one_minus_at), C.c_void_p(_ptr(noise)), float(temperature),
+                                                     C.c_void_p(k.data_ptr()), per, C.c_void_p(x_prev.data_ptr()), C.c_void_p(_ptr(x0)),
+                                                     x.numel(), C.c_void_p(_stream())), 'mkd_ddim_step_ex')
+            return x_prev, x0
         with torch.cuda.device(self.device):
             _lib.check(self.lib.mkd_ddim_step(C.c_void_p(x.data_ptr()), C.c_void_p(eps_c.data_ptr()), C.c_void_p(_ptr(eps_u)),
                                               float(cfg_scale), float(a_t), float(a_prev), float(sigma_t),
@@ -511,15 +558,19 @@ class MkdEngine:
                sqrt_one_minus_alphas: Sequence[float], cfg_scale: float = 1.0, use_graph: bool = False,
                sigmas: Optional[Sequence[float]] = None, noise: Optional[torch.Tensor] = None, temperature: float = 1.0,
                x0: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, q_sqrt_ac: Optional[Sequence[float]] = None,
-               q_sqrt_1m_ac: Optional[Sequence[float]] = None, q_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+               q_sqrt_1m_ac: Optional[Sequence[float]] = None, q_noise: Optional[torch.Tensor] = None,
+               log_every_t: int = 100, want_trace: bool = False, guidance_rescale: float = 0.0):
         """Whole reverse loop in one call (cddim.py:81-100). Prepared batch must be B or 2B (CFG).  eta > 0 (cddim.py:74-78):
         ``sigmas`` like the other tables and ``noise`` [n_steps, B, 4, h, w], row k = the draw of the k-th executed step.
         Masked sampling (include/mkd.h mkd_sample_masked): ``x0`` [B,4,h,w], ``mask`` [1|B, 1|4, h, w] (1 keeps x0), the DDPM
-        tables at each entry's timestep ``q_sqrt_ac`` / ``q_sqrt_1m_ac`` (indexed like ``alphas``) and ``q_noise`` [n_steps, B, 4, h, w]."""
+        tables at each entry's timestep ``q_sqrt_ac`` / ``q_sqrt_1m_ac`` (indexed like ``alphas``) and ``q_noise`` [n_steps, B, 4, h, w].
+        ``want_trace``: returns ``(latent, x_inter, pred_x0)``, the two [rows, B, 4, h, w] tensors of the sampler's intermediates
+        logged by ``log_every_t`` (mkd_sample_extras); ``guidance_rescale`` = phi in [0, 1], engaged with guidance and phi > 0."""
         x_T = self._check_x_T(x_T, cfg_scale)
         n, ts, (a, ap, s1) = self._sample_tables(timesteps, alphas=alphas, alphas_prev=alphas_prev, sqrt_one_minus_alphas=sqrt_one_minus_alphas)
         out = torch.empty_like(x_T)
         qm, keep = self._sample_mask(x_T, n, x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise)
+        ex, rows = self._sample_extras(x_T, n, log_every_t, want_trace, guidance_rescale)
         sg = None
         if sigmas is not None and any(float(v) != 0.0 for v in sigmas):
             if len(sigmas) != n:
@@ -533,7 +584,14 @@ class MkdEngine:
         with torch.cuda.device(self.device):
             head = (self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, s1)
             tail = (float(cfg_scale), C.c_void_p(out.data_ptr()), int(use_graph), C.c_void_p(_stream()))
-            if qm is not None:
+            if ex is not None:
+                _lib.check(self.lib.mkd_sample_masked_ex(*head, sg, C.c_void_p(_ptr(noise)), float(temperature),
+                                                         None if qm is None else C.byref(qm), C.byref(ex), *tail), 'mkd_sample_masked_ex')
+                if qm is not None:
+                    self._hold(keep, noise)
+                elif sg is not None and use_graph:
+                    torch.cuda.synchronize(self.device)          # (as below: the replayed loop reads `noise` after this call returns)
+            elif qm is not None:
                 _lib.check(self.lib.mkd_sample_masked(*head, sg, C.c_void_p(_ptr(noise)), float(temperature), C.byref(qm), *tail), 'mkd_sample_masked')
                 self._hold(keep, noise)
             elif sg is not None:
@@ -542,9 +600,26 @@ class MkdEngine:
                     torch.cuda.synchronize(self.device)          # the replayed loop reads `noise` after this call returns: keep it alive
             else:
                 _lib.check(self.lib.mkd_sample(*head, *tail), 'mkd_sample')
-        return out
+        return (out, *rows) if want_trace else out
 
-    def dpmpp_step(self, x, eps_c, eps_u, cfg_scale, coef6, m1=None, m2=None):
+    def _sample_extras(self, x_T, n, log_every_t, want_trace, guidance_rescale):
+        """(mkd_sample_extras or None when neither feature is asked for: today's entry is called; the trace tensors or ()).  The rows
+        are returned to the caller, whose stream waits for the loop: they outlive the enqueued work."""
+        phi = check_guidance_rescale(guidance_rescale)
+        if not want_trace and phi == 0.0:
+            return None, ()
+        rows = ()
+        ex = _lib.SampleExtrasC(1, 0, None, None, phi)
+        if want_trace:
+            if int(log_every_t) < 1:
+                raise ValueError(f'log_every_t must be >= 1, got {log_every_t}')
+            r = sample_log_rows(n, int(log_every_t))
+            rows = (torch.empty((r, *x_T.shape), device=self.device, dtype=torch.float32),
+                    torch.empty((r, *x_T.shape), device=self.device, dtype=torch.float32))
+            ex = _lib.SampleExtrasC(int(log_every_t), r, rows[0].data_ptr(), rows[1].data_ptr(), phi)
+        return ex, rows
+
+    def dpmpp_step(self, x, eps_c, eps_u, cfg_scale, coef6, m1=None, m2=None, guidance_rescale: float = 0.0):
         """One DPM-Solver++ multistep update (mkd_dpmpp_step): ``coef6`` = a row of ``dpmpp_table``; m1 / m2 = the x0-predictions
         of the previous two steps, needed where coef6[4] / coef6[5] is non-zero.  Returns (x_prev, m0)."""
         x = _f32c(x, self.device); eps_c = _f32c(eps_c, self.device)
@@ -561,6 +636,14 @@ class MkdEngine:
                 raise ValueError('dpmpp_step: every tensor must have the size of x')
         x_prev = torch.empty_like(x)
         m0 = torch.empty_like(x)
+        kf, per = self._rescale_k(eps_c, eps_u, cfg_scale, guidance_rescale)
+        if kf is not None:
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.mkd_dpmpp_step_ex(C.c_void_p(x.data_ptr()), C.c_void_p(eps_c.data_ptr()), C.c_void_p(eps_u.data_ptr()),
+                                                      float(cfg_scale), (C.c_float * 6)(*k), C.c_void_p(_ptr(m1)), C.c_void_p(_ptr(m2)),
+                                                      C.c_void_p(kf.data_ptr()), per, C.c_void_p(x_prev.data_ptr()),
+                                                      C.c_void_p(m0.data_ptr()), x.numel(), C.c_void_p(_stream())), 'mkd_dpmpp_step_ex')
+            return x_prev, m0
         with torch.cuda.device(self.device):
             _lib.check(self.lib.mkd_dpmpp_step(C.c_void_p(x.data_ptr()), C.c_void_p(eps_c.data_ptr()), C.c_void_p(_ptr(eps_u)),
                                                float(cfg_scale), (C.c_float * 6)(*k), C.c_void_p(_ptr(m1)), C.c_void_p(_ptr(m2)),
@@ -571,19 +654,26 @@ class MkdEngine:
     def sample_dpmpp(self, x_T: torch.Tensor, timesteps: Sequence[int], alphas: Sequence[float], alphas_prev: Sequence[float],
                      order: int = 2, lower_order_final: bool = True, cfg_scale: float = 1.0, use_graph: bool = False,
                      x0: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, q_sqrt_ac: Optional[Sequence[float]] = None,
-                     q_sqrt_1m_ac: Optional[Sequence[float]] = None, q_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     q_sqrt_1m_ac: Optional[Sequence[float]] = None, q_noise: Optional[torch.Tensor] = None,
+                     log_every_t: int = 100, want_trace: bool = False, guidance_rescale: float = 0.0):
         """The whole DPM-Solver++ multistep loop in one call (mkd_sample_dpmpp): ``sample``'s contract on the same DDIM tables
-        (prepared batch B or 2B with guidance, masked sampling through x0 / mask / q_*), deterministic."""
+        (prepared batch B or 2B with guidance, masked sampling through x0 / mask / q_*), deterministic.  ``want_trace`` /
+        ``log_every_t`` / ``guidance_rescale`` as in ``sample`` (the pred_x0 rows are the solver's m_k)."""
         x_T = self._check_x_T(x_T, cfg_scale)
         n, ts, (a, ap) = self._sample_tables(timesteps, alphas=alphas, alphas_prev=alphas_prev)
         out = torch.empty_like(x_T)
         qm, keep = self._sample_mask(x_T, n, x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise)
+        ex, rows = self._sample_extras(x_T, n, log_every_t, want_trace, guidance_rescale)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.mkd_sample_dpmpp(self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, int(order),
-                                                 int(bool(lower_order_final)), None if qm is None else C.byref(qm), float(cfg_scale),
-                                                 C.c_void_p(out.data_ptr()), int(use_graph), C.c_void_p(_stream())), 'mkd_sample_dpmpp')
+            head = (self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, int(order), int(bool(lower_order_final)),
+                    None if qm is None else C.byref(qm))
+            tail = (float(cfg_scale), C.c_void_p(out.data_ptr()), int(use_graph), C.c_void_p(_stream()))
+            if ex is not None:
+                _lib.check(self.lib.mkd_sample_dpmpp_ex(*head, C.byref(ex), *tail), 'mkd_sample_dpmpp_ex')
+            else:
+                _lib.check(self.lib.mkd_sample_dpmpp(*head, *tail), 'mkd_sample_dpmpp')
         self._hold(keep, None)
-        return out
+        return (out, *rows) if want_trace else out
 
     def _check_x_T(self, x_T: torch.Tensor, cfg_scale: float) -> torch.Tensor:
         """x_T as the fp32 device tensor, checked against the prepared conditioning (batch B, or 2B = [uncond; cond] with guidance)."""
@@ -786,9 +876,10 @@ class MkdEngine:
     def eps_launches(self) -> int:
         return int(self.lib.mkd_eps_launches(self._ctx))
 
-    def step_launches(self, use_graph: bool = True, cfg: bool = False) -> int:
-        """Kernel launches of one DDIM step inside ``sample`` (time embedding hoisted out of the loop), as that loop is run."""
-        return int(self.lib.mkd_step_launches_ex(self._ctx, int(use_graph), int(cfg)))
+    def step_launches(self, use_graph: bool = True, cfg: bool = False, rescale: bool = False) -> int:
+        """Kernel launches of one DDIM step inside ``sample`` (time embedding hoisted out of the loop), as that loop is run;
+        ``rescale``: a guided step with guidance rescale (its factor launch)."""
+        return int(self.lib.mkd_step_launches_ex(self._ctx, int(use_graph), 2 if (cfg and rescale) else int(bool(cfg))))
 
     def device_bytes(self) -> int:
         return int(self.lib.mkd_device_bytes(self._ctx))

@@ -47,6 +47,11 @@ class SampleMaskC(C.Structure):
                 ('noise', C.c_void_p)]
 
 
+class SampleExtrasC(C.Structure):
+    _fields_ = [('log_every_t', C.c_int32), ('rows', C.c_int32), ('trace_x', C.c_void_p), ('trace_x0', C.c_void_p),
+                ('guidance_rescale', C.c_float)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -78,13 +83,21 @@ SIGNATURES = {
     'mkd_debug_hint_embedding': (_I, [_P, _P, _P]),
     'mkd_eps': (_I, [_P, _P, _P, _P, _P]),
     'mkd_ddim_step': (_I, [_P, _P, _P, _F, _F, _F, _F, _F, _P, _F, _P, _P, _L, _P]),
+    'mkd_ddim_step_ex': (_I, [_P, _P, _P, _F, _F, _F, _F, _F, _P, _F, _P, _I, _P, _P, _L, _P]),
+    'mkd_cfg_rescale_factor': (_I, [_P, _P, _F, _F, _I, _I, _P, _P]),
+    'mkd_sample_log_rows': (_I, [_I, _I]),
     'mkd_sample': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _F, _P, _I, _P]),
     'mkd_sample_eta': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _P, _F, _F, _P, _I, _P]),
     'mkd_sample_masked': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _P, _F,
                                C.POINTER(SampleMaskC), _F, _P, _I, _P]),
+    'mkd_sample_masked_ex': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _P, _F,
+                                  C.POINTER(SampleMaskC), C.POINTER(SampleExtrasC), _F, _P, _I, _P]),
     'mkd_q_sample_blend': (_I, [_P, _P, _F, _F, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
     'mkd_dpmpp_table': (_I, [_I, C.POINTER(_F), C.POINTER(_F), _I, _I, C.POINTER(_F), C.POINTER(_I)]),
     'mkd_dpmpp_step': (_I, [_P, _P, _P, _F, C.POINTER(_F), _P, _P, _P, _P, _L, _P]),
+    'mkd_dpmpp_step_ex': (_I, [_P, _P, _P, _F, C.POINTER(_F), _P, _P, _P, _I, _P, _P, _L, _P]),
+    'mkd_sample_dpmpp_ex': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), _I, _I, C.POINTER(SampleMaskC),
+                                 C.POINTER(SampleExtrasC), _F, _P, _I, _P]),
     'mkd_sample_dpmpp': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), _I, _I, C.POINTER(SampleMaskC), _F, _P, _I, _P]),
     'mkd_latent_mask_from_labels': (_I, [_P, _I, _I, _I, C.c_uint64, _I, _F, _P, _P]),
     'mkd_paste_background': (_I, [_P, _P, _P, C.c_uint64, _I, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P]),

@@ -98,6 +98,12 @@ def build_parser():
                     'the face box (<data-root>/boxes.txt, lines "name x0 y0 w h"; else the centred largest square) is crop-resized to --res on '
                     'the device, sampled once, and pasted back into the source photo with its fine detail kept; writes <out>/photos/<pair>.png')
     ap.add_argument('--photo-feather', type=int, default=8, help='fade the pasted face in over this many photo pixels at the box sides, 0..64')
+    ap.add_argument('--denoise-rows', action='store_true', help='also write the denoise rows of both passes (denoise_row*.png: the decoded '
+                    'x0-predictions, samples as rows, x_T and the logged steps as columns), traced inside the sampling loop')
+    ap.add_argument('--log-every-t', type=int, default=100, metavar='N', help='with --denoise-rows: log every table entry i with i %% N == 0 '
+                    '(and the first executed step), the rule of the sampler\'s log_every_t')
+    ap.add_argument('--guidance-rescale', type=float, default=0.0, metavar='PHI', help='guidance rescale of the guided pass, 0..1: per sample '
+                    'and step the guided eps is scaled by PHI std(eps_cond) / std(eps_guided) + 1 - PHI (0: off)')
     return ap
 
 
@@ -152,6 +158,12 @@ def main():
         raise SystemExit('--photo-feather must be 0..64 photo pixels')
     if args.photo_feather != 8 and not args.photos:
         raise SystemExit('--photo-feather only applies with --photos')
+    if args.log_every_t < 1:
+        raise SystemExit('--log-every-t must be >= 1')
+    if args.log_every_t != 100 and not args.denoise_rows:
+        raise SystemExit('--log-every-t only applies with --denoise-rows')
+    if not 0.0 <= args.guidance_rescale <= 1.0:
+        raise SystemExit('--guidance-rescale must lie in 0..1')
     rank, world, local = mdist.init_from_env()
     model = create_model(args.config).cpu()
     if args.fix_background:
@@ -164,6 +176,7 @@ def main():
     if args.ddim_steps is not None:
         model.ddim_steps = args.ddim_steps
     model.sampler, model.solver_order = args.sampler, args.solver_order
+    model.denoise_rows, model.log_every_t, model.guidance_rescale = args.denoise_rows, args.log_every_t, args.guidance_rescale
     if args.ckpt:
         model.load_state_dict(load_state_dict(args.ckpt, location='cpu'))
     torch.cuda.set_device(local)
