@@ -17,7 +17,8 @@
  *   - host synchronisation points (everything else only enqueues): mkd_ctx_create / mkd_weights_finalize / mkd_vae_finalize / mkd_clip_finalize
  *     and the first mkd_prepare of a new shape (plan building, hipDeviceSynchronize); mkd_sample(use_graph != 0), which waits on the host
  *     for the context's PREVIOUS graph-replayed loop before it rewrites the pinned step table (hipStreamSynchronize of the
- *     private loop stream) and then returns with the new loop enqueued; mkd_eps_profile (measures, so it waits); mkd_ctx_destroy.
+ *     private loop stream) and then returns with the new loop enqueued (mkd_sample_rows likewise; with use_graph == 0 it also waits
+ *     for `stream` up to the upload of its own step table); mkd_eps_profile (measures, so it waits); mkd_ctx_destroy.
  */
 #ifndef MKD_H
 #define MKD_H
@@ -302,6 +303,67 @@ int mkd_sample_dpmpp(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, con
 int mkd_sample_dpmpp_ex(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
                         const float* alphas_prev, int order, int lower_order_final, const mkd_sample_mask* m,
                         const mkd_sample_extras* ex, float cfg_scale, float* x_out, int use_graph, void* stream);
+/* ---- per-sample requests in one batch (build-defined) ----------------------------------------------------------
+ * One request row per sample b: its own schedule (n_steps, 1 <= n_steps <= MKD_MAX_STEPS, and HOST tables laid out as for mkd_sample /
+ * mkd_sample_eta: entry n_steps - 1 is executed first) and its own guidance scale.  DDIM (solver 0) reads timesteps, alphas, alphas_prev,
+ * sqrt_one_minus_alphas and the optional sigmas; DPM-Solver++ (solver 1) reads timesteps and dpm, the [n_steps][6] table of mkd_dpmpp_table
+ * (which carries the sample's order).  The solver is per call. */
+#ifndef MKD_MAX_STEPS
+#define MKD_MAX_STEPS 1024
+#endif
+typedef struct mkd_sample_row {
+    int32_t n_steps;
+    float cfg_scale;
+    const int64_t* timesteps;
+    const float* alphas; const float* alphas_prev; const float* sqrt_one_minus_alphas;
+    const float* sigmas;                 /* NULL: eta = 0 */
+    const float* dpm;                    /* solver 1: mkd_dpmpp_table's rows */
+} mkd_sample_row;
+/* One entry of the per-sample step table: what a sample does in one executed step (64 bytes).  coef = sqrt(1/a_t), sqrt(a_prev),
+ * sqrt(1 - a_prev - sigma^2), sqrt(1 - a_t); dpm = a row of mkd_dpmpp_table; temb_row = the row of the call's time-embedding table
+ * (one row per distinct timestep of the call, first seen first, steps outer, samples inner) that holds t; active 0: the sample has
+ * finished: t / temb_row are those of its entry 0 and its rows are not touched. */
+typedef struct mkd_step_row {
+    int64_t t;
+    float coef[4];
+    float sigma;
+    float dpm[6];
+    int32_t temb_row;
+    int32_t active;
+    float scale;
+} mkd_step_row;
+/* HOST only: the step table of a call, out [S_max][batch] with S_max = max_b n_steps (returned in *s_max; pass out NULL to get the
+ * sizes alone).  Executed step k = 0 .. S_max - 1; sample b is active while k < n_steps_b and applies its entry n_steps_b - 1 - k
+ * (left-aligned: all samples start together, short ones finish first).  distinct [<= MKD_MAX_STEPS] (may be NULL) / *n_distinct: the
+ * call's distinct timesteps in first-seen order.  Checks every row first (counts, NULL tables, then with each sample's own tables the
+ * sigma range rule of mkd_sample_eta); more than MKD_MAX_STEPS distinct timesteps: MKD_ERR_ARG. */
+int mkd_step_table(const mkd_sample_row* rows, int batch, int solver, mkd_step_row* out, int* s_max, int64_t* distinct, int* n_distinct);
+/* The whole loop with one request row per sample, all three loop forms (graph replay, its per-stream segments, use_graph == 0, which
+ * enqueues the same step kernels uncaptured on `stream` after waiting on the host for the context's previous loop).
+ *   - Finished samples: their latent rows (and ring rows) are not written again, whatever the model returns for them; the model is
+ *     still evaluated for them at the timestep of their entry 0.
+ *   - Guidance: every cfg_scale == 1: the prepared batch is `batch`, nothing is doubled; otherwise it is 2 * batch, unconditional half
+ *     first, and every sample uses the guided expression of the uniform kernels with its own scale (a scale of 1 is allowed there).
+ *   - eta: noise [S_max][batch * C * h * w] (DDIM; needed when any sigma is non-zero); sample b takes its slice of row k in executed
+ *     step k where its sigma is non-zero.  temperature is per call.
+ *   - m and ex must be NULL (ex: or ask for neither a trace nor a rescale): masked sampling, the intermediates trace and guidance
+ *     rescale are not combined with per-sample rows: MKD_ERR_UNSUPPORTED, the message names the combination.
+ * Bit contract: on one context, prepared batch and loop form, row b has the bits of row b of mkd_sample / mkd_sample_eta /
+ * mkd_sample_dpmpp run with sample b's request (and rows 0 .. n_steps_b - 1 of the noise).  The per-step launch count is that of the
+ * uniform step of the same guidance form under graph replay (mkd_step_launches_ex with MKD_STEP_PER_SAMPLE).  Captured steps are keyed
+ * on the per-sample form: uniform and per-sample calls may alternate.  rows and their tables are read before the call returns. */
+int mkd_sample_rows(mkd_ctx* ctx, const float* x_T, int batch, const mkd_sample_row* rows, int solver, const float* noise, float temperature,
+                    const mkd_sample_mask* m, const mkd_sample_extras* ex, float* x_out, int use_graph, void* stream);
+/* The two per-sample updates alone (the eager host-driven loop, tests): rows = DEVICE [batch] entries of one executed step; sample b
+ * covers elements [b * n_per_sample, (b + 1) * n_per_sample) of every tensor.  Active samples: the arithmetic of mkd_ddim_step /
+ * mkd_dpmpp_step with coef / dpm, scale and sigma of their entry (eps_u NULL: eps_c; noise [batch * n_per_sample] or NULL, read where
+ * sigma != 0; pred_x0 may be NULL; x_prev may alias x).  Finished samples: no byte of x_prev / pred_x0 / m0_out is written and nothing
+ * of their rows is read.  16-byte accesses when n_per_sample % 4 == 0 and every pointer is 16-byte aligned, scalar otherwise, the same
+ * bits.  DPM: m1, m2 (read where the entry's c_1 / c_2 is non-zero) and m0_out are required.  batch <= 65535. */
+int mkd_ddim_step_rows(const float* x, const float* eps_c, const float* eps_u, const mkd_step_row* rows, const float* noise, float temperature,
+                       float* x_prev, float* pred_x0, int batch, int n_per_sample, void* stream);
+int mkd_dpmpp_step_rows(const float* x, const float* eps_c, const float* eps_u, const mkd_step_row* rows, const float* m1, const float* m2,
+                        float* x_prev, float* m0_out, int batch, int n_per_sample, void* stream);
 /* Latent mask from a label map (reference Fixbackground: labels 0 background, 11 teeth, 12 hair): labels [batch, H, W] uint8
  * device -> out [batch, 1, H/factor, W/factor] fp32 device = the fraction of each factor x factor block whose label l has bit l set
  * in `classes` (labels >= 64 never match): F.interpolate(mode='area') of the binary mask.  threshold > 0: 1 where that fraction
@@ -470,6 +532,9 @@ int     mkd_eps_launches(const mkd_ctx* ctx);
  * computed once per call there, see mkd_sample; + the step setup and the x_{t-1} update). */
 int     mkd_step_launches(const mkd_ctx* ctx);                           /* graph replay, no guidance */
 int     mkd_step_launches_ex(const mkd_ctx* ctx, int use_graph, int cfg_on); /* as the loop is run: eager adds the timestep fill / table-row select, guidance (cfg_on != 0) the batch doubling, cfg_on == 2 (guidance with rescale) the factor launch */
+/* ... cfg_on | MKD_STEP_PER_SAMPLE: a step of mkd_sample_rows (cfg_on & 3 as above; 2 is not built): setup, evaluation, update (+ the batch
+ * doubling), the count of the replayed uniform step, whatever use_graph (the per-sample eager loop enqueues the same kernels) */
+#define MKD_STEP_PER_SAMPLE 4
 /* Kernel classes of the launch plan, and one mkd_eps with a hipEvent pair around every launch group:
  * per-class device milliseconds, executed FLOPs and launch counts (arrays of mkd_kind_count()). Synchronous.
  * csv_path (host string, may be NULL): also write one line per launch group (op,kind,label,ms,gflop). */

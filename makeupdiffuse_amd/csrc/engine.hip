@@ -13,6 +13,7 @@
 #include "../../include/mkd.h"
 
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -97,7 +98,79 @@ struct SampleReq {
     float cfg_scale = 1.0f; float* x_out = nullptr; int use_graph = 0;
     const mkd_sample_extras* ex = nullptr;        // intermediates trace / guidance rescale; null: neither
     const char* who = "mkd_sample";
+    // per-sample call (mkd_sample_rows): one request row per sample, the solver (0 DDIM, 1 DPM-Solver++) per call; the uniform tables
+    // above stay null and n_steps / cfg_scale are unused
+    const mkd_sample_row* rows = nullptr; int solver = 0;
 };
+
+static_assert(sizeof(StepRow) == sizeof(mkd_step_row) && sizeof(StepRow) == 64, "StepRow is mkd_step_row of include/mkd.h");
+static_assert(offsetof(StepRow, sigma) == offsetof(mkd_step_row, sigma) && offsetof(StepRow, dpm) == offsetof(mkd_step_row, dpm) &&
+              offsetof(StepRow, temb_row) == offsetof(mkd_step_row, temb_row) && offsetof(StepRow, scale) == offsetof(mkd_step_row, scale),
+              "StepRow is mkd_step_row of include/mkd.h");
+
+// The step table of a per-sample call (include/mkd.h mkd_step_table).  Every argument check comes before the first dereference of a
+// table: counts and pointers of all rows, then each sample's sigmas.  tab [S_max][batch] (null: sizes only)
+static int build_step_table(const mkd_sample_row* rows, int batch, int solver, std::vector<StepRow>* tab, int* s_max_out,
+                            std::vector<int64_t>* distinct_out, bool* stochastic, bool* guided) {
+    const std::string who = "mkd_sample_rows: ";
+    if (!rows || batch <= 0) return mkd_fail(MKD_ERR_ARG, who + "rows must hold one request per sample (batch >= 1)");
+    if (solver != 0 && solver != 1) return mkd_fail(MKD_ERR_ARG, who + "solver must be 0 (DDIM) or 1 (DPM-Solver++)");
+    int s_max = 0;
+    for (int b = 0; b < batch; ++b) {
+        const mkd_sample_row& q = rows[b];
+        const std::string at = who + "sample " + std::to_string(b) + ": ";
+        if (q.n_steps < 1) return mkd_fail(MKD_ERR_ARG, at + "n_steps must be >= 1");
+        if (q.n_steps > MKD_MAX_STEPS) return mkd_fail(MKD_ERR_ARG, at + "n_steps exceeds MKD_MAX_STEPS");
+        if (!q.timesteps) return mkd_fail(MKD_ERR_ARG, at + "null timesteps table");
+        if (solver == 0 && (!q.alphas || !q.alphas_prev || !q.sqrt_one_minus_alphas))
+            return mkd_fail(MKD_ERR_ARG, at + "null table (alphas, alphas_prev and sqrt_one_minus_alphas are required)");
+        if (solver == 1 && !q.dpm) return mkd_fail(MKD_ERR_ARG, at + "null table (the mkd_dpmpp_table rows are required)");
+        if (!(q.cfg_scale == q.cfg_scale)) return mkd_fail(MKD_ERR_ARG, at + "cfg_scale is not a number");
+        s_max = std::max(s_max, q.n_steps);
+    }
+    bool any_sigma = false, any_cfg = false;
+    for (int b = 0; b < batch; ++b) {
+        const mkd_sample_row& q = rows[b];
+        any_cfg = any_cfg || q.cfg_scale != 1.0f;
+        if (solver == 0 && q.sigmas) for (int i = 0; i < q.n_steps; ++i) {          // (mkd_sample_eta's rule, with the sample's own tables)
+            if (!(q.sigmas[i] >= 0.f) || 1.0f - q.alphas_prev[i] - q.sigmas[i] * q.sigmas[i] < 0.f)
+                return mkd_fail(MKD_ERR_ARG, who + "sample " + std::to_string(b) + ": sigma out of range");
+            any_sigma = any_sigma || q.sigmas[i] != 0.f;
+        }
+    }
+    std::vector<int64_t> distinct;
+    std::map<int64_t, int> row_of;
+    if (tab) tab->assign((size_t)s_max * batch, StepRow{});
+    for (int k = 0; k < s_max; ++k)
+        for (int b = 0; b < batch; ++b) {
+            const mkd_sample_row& q = rows[b];
+            const bool active = k < q.n_steps;
+            const int i = active ? q.n_steps - 1 - k : 0;          // finished: evaluated at the timestep of entry 0, result discarded
+            const int64_t t = q.timesteps[i];
+            auto it = row_of.find(t);
+            if (it == row_of.end()) {
+                if ((int)distinct.size() == MKD_MAX_STEPS) return mkd_fail(MKD_ERR_ARG, who + "more than MKD_MAX_STEPS distinct timesteps in one call");
+                it = row_of.emplace(t, (int)distinct.size()).first;
+                distinct.push_back(t);
+            }
+            if (!tab) continue;
+            StepRow& e = (*tab)[(size_t)k * batch + b];
+            e.t = t; e.temb_row = it->second; e.active = active ? 1 : 0; e.scale = q.cfg_scale;
+            if (solver == 0) {          // (fill_step_state's expressions)
+                const float sg = q.sigmas ? q.sigmas[i] : 0.f;
+                e.coef[0] = 1.0f / sqrtf(q.alphas[i]);
+                e.coef[1] = sqrtf(q.alphas_prev[i]);
+                e.coef[2] = sqrtf(1.0f - q.alphas_prev[i] - sg * sg);
+                e.coef[3] = q.sqrt_one_minus_alphas[i];
+                e.sigma = sg;
+            } else for (int j = 0; j < 6; ++j) e.dpm[j] = q.dpm[6 * i + j];
+        }
+    if (s_max_out) *s_max_out = s_max;
+    if (distinct_out) *distinct_out = std::move(distinct);
+    if (stochastic) *stochastic = any_sigma;
+    if (guided) *guided = any_cfg;
+    return 0;
+}
 
 // mkd_sample_log_rows / the row table of a traced call: entry i (executed as step n_steps - 1 - i) is logged when
 // i % log_every_t == 0 or i == n_steps - 1 (UPSTREAM DDIMSampler.ddim_sampling), rows in execution order
@@ -301,6 +374,7 @@ struct mkd_ctx {
     int64_t* s_t = nullptr;
     StepState* s_state = nullptr; StepState* h_state = nullptr;
     float* s_kfac = nullptr;          // guidance rescale: this step's per-sample factors [B] (allocated with the buffers above)
+    StepRow* s_rows = nullptr; StepRow* h_rows = nullptr; size_t rows_cap = 0;      // per-sample step table [S_max][batch]: device / pinned host, grown on demand
     float* s_ring = nullptr; int64_t s_ring_n = 0;        // DPM-Solver++ history ring [3][n] fp32: allocated on first use, grown with the batch
     hipStream_t loop_stream = nullptr; hipEvent_t ev_loop_in = nullptr, ev_loop_out = nullptr;
     hipGraphExec_t multi_graph = nullptr; int multi_graph_steps = 0;      // MKD_GRAPH_STEPS consecutive steps as one graph
@@ -309,7 +383,8 @@ struct mkd_ctx {
     // rescaled (one more launch, another expression in the last kernel; phi itself lives in the step state)
     struct StepKey {
         int gen = -1, cfg = -1, temb = -1, batch = -1, solver = -1, rescale = -1; float scale = 0.f;
-        bool operator==(const StepKey& o) const { return gen == o.gen && cfg == o.cfg && temb == o.temb && batch == o.batch && solver == o.solver && rescale == o.rescale && scale == o.scale; }
+        int rows = 0;          // per-sample step (mkd_sample_rows): other setup / update kernels, the scales come from the step table (scale stays 0)
+        bool operator==(const StepKey& o) const { return gen == o.gen && cfg == o.cfg && temb == o.temb && batch == o.batch && solver == o.solver && rescale == o.rescale && scale == o.scale && rows == o.rows; }
     };
     hipGraphExec_t step_graph = nullptr; StepKey step_key; int plan_generation = 0;
     // Graph mode 2 (MKD_GRAPH_MODE=2; default 1 = one captured graph per step): one step = LINEAR graphs, one per (stream, stretch
@@ -1841,6 +1916,16 @@ struct mkd_ctx {
         mkd_ctx* self = this;
         const int64_t n = latent_n(k.batch);
         StateStep s; s.io = step_io(k.cfg != 0, s_xa, n);
+        if (k.rows) {          // per-sample: its own setup and update kernels around the same evaluation, the same number of launches
+            s.head.push_back([self, Bn = B, samples = k.batch](hipStream_t st) {
+                const TembSel ts = self->temb_sel();
+                return launch_step_setup_rows(self->s_state, self->s_t, Bn, samples, st, self->temb_skip ? &ts : nullptr); });
+            if (k.cfg) s.head.push_back([self, n](hipStream_t st) { return launch_repeat_batch(self->s_xa, self->s_xin, n, 2, st); });
+            s.tail = [self, io = s.io, dpm_on = k.solver != 0, samples = k.batch, per = sample_elems()](hipStream_t st) {
+                return dpm_on ? launch_dpmpp_step_rows(self->s_xa, io.ec, io.eu, nullptr, self->s_state, nullptr, nullptr, self->s_xa, nullptr, samples, per, st)
+                              : launch_ddim_step_rows(self->s_xa, io.ec, io.eu, nullptr, self->s_state, nullptr, 0.f, self->s_xa, nullptr, samples, per, st); };
+            return s;
+        }
         s.head.push_back([self, Bn = B, n](hipStream_t st) {
             const TembSel ts = self->temb_sel();
             return launch_step_setup(self->s_state, self->s_t, Bn, self->s_xa, n, st, self->temb_skip ? &ts : nullptr); });
@@ -2052,6 +2137,7 @@ struct mkd_ctx {
         if (traced(r)) sample_log_rows(n_steps, ex->log_every_t, h_state->trace_row);
         else for (int i = 0; i < n_steps; ++i) h_state->trace_row[i] = -1;
         h_state->phi = ex ? ex->guidance_rescale : 0.f;
+        h_state->rows = nullptr; h_state->rows_batch = 0;
     }
     static bool traced(const SampleReq& r) { return r.ex && (r.ex->trace_x || r.ex->trace_x0); }
 
@@ -2166,6 +2252,80 @@ struct mkd_ctx {
         MKD_HIP_CHECK(hipMemcpyAsync(r.x_out, s_xa, n * sizeof(float), hipMemcpyDeviceToDevice, loop_stream));      // the result; the caller's stream waits for the loop
         MKD_HIP_CHECK(hipEventRecord(ev_loop_out, loop_stream));
         MKD_HIP_CHECK(hipStreamWaitEvent(stream, ev_loop_out, 0));
+        return 0;
+    }
+
+    // ---- per-sample requests (include/mkd.h mkd_sample_rows) ----------------------------------------------------------------
+    int ensure_rows(size_t entries) {
+        if (h_rows && s_rows && rows_cap >= entries) return 0;
+        MKD_HIP_CHECK(hipDeviceSynchronize());          // an enqueued loop may still read the old table
+        if (h_rows) { hipHostFree(h_rows); h_rows = nullptr; }
+        if (s_rows) { hipFree(s_rows); s_rows = nullptr; }
+        rows_cap = 0;
+        const size_t cap = std::max<size_t>(entries, 256);
+        MKD_HIP_CHECK(hipHostMalloc((void**)&h_rows, cap * sizeof(StepRow)));
+        MKD_HIP_CHECK(hipMalloc((void**)&s_rows, cap * sizeof(StepRow)));
+        rows_cap = cap;
+        return 0;
+    }
+    // The whole reverse loop with one request row per sample.  Only the step-state kernels differ from sample(): the evaluation, the
+    // capture helpers and the loop forms are shared (StepKey::rows).  use_graph == 0 enqueues the same step kernels uncaptured on the
+    // caller's stream (they read the device step table, so there is no host-table form of this loop)
+    int sample_rows(const SampleReq& r, hipStream_t stream) {
+        struct Clear { bool& flag; ~Clear() { flag = false; } } clear_temb_skip{temb_skip};
+        const std::string who = "mkd_sample_rows: ";
+        if (!prepared) return mkd_fail(MKD_ERR_STATE, "mkd_sample_rows before mkd_prepare");
+        if (!r.x_T || !r.x_out) return mkd_fail(MKD_ERR_ARG, who + "null latent pointer");
+        if (r.qm) return mkd_fail(MKD_ERR_UNSUPPORTED, who + "per-sample rows combined with masked sampling are not built");
+        if (r.ex && (r.ex->trace_x || r.ex->trace_x0)) return mkd_fail(MKD_ERR_UNSUPPORTED, who + "per-sample rows combined with the intermediates trace are not built");
+        if (r.ex && !(r.ex->guidance_rescale == 0.f)) return mkd_fail(MKD_ERR_UNSUPPORTED, who + "per-sample rows combined with guidance rescale are not built");
+        std::vector<StepRow> tab; std::vector<int64_t> distinct;
+        int s_max = 0; bool stochastic = false, guided = false;
+        int rc = build_step_table(r.rows, r.batch, r.solver, &tab, &s_max, &distinct, &stochastic, &guided); if (rc) return rc;
+        if (guided ? (B != 2 * r.batch) : (B != r.batch))
+            return mkd_fail(MKD_ERR_ARG, who + "prepared batch must be B (every cfg_scale == 1) or 2B (uncond first)");
+        if (stochastic && !r.noise) return mkd_fail(MKD_ERR_ARG, who + "sigma > 0 needs the noise draws");
+        StepKey key; key.gen = plan_generation; key.cfg = guided; key.scale = 0.f; key.batch = r.batch; key.solver = r.solver; key.rescale = 0;
+        key.temb = temb_table; key.rows = 1;
+        const int64_t n = latent_n(r.batch);
+        if (key.solver) { rc = ensure_ring(n); if (rc) return rc; }
+        rc = ensure_rows(tab.size()); if (rc) return rc;
+        if (!h_state) MKD_HIP_CHECK(hipHostMalloc((void**)&h_state, sizeof(StepState)));
+        if (!s_state) MKD_HIP_CHECK(hipMalloc((void**)&s_state, sizeof(StepState)));
+        if (r.use_graph && !loop_stream) {
+            MKD_HIP_CHECK(hipStreamCreateWithFlags(&loop_stream, hipStreamNonBlocking));
+            MKD_HIP_CHECK(hipEventCreateWithFlags(&ev_loop_in, hipEventDisableTiming));
+            MKD_HIP_CHECK(hipEventCreateWithFlags(&ev_loop_out, hipEventDisableTiming));
+        }
+        // the pinned state / table may still feed a previous replayed call's copy (an uncaptured call waits for its own copies below)
+        if (loop_stream) MKD_HIP_CHECK(hipStreamSynchronize(loop_stream));
+        memset(h_state, 0, sizeof(StepState));
+        h_state->counter = s_max - 1; h_state->n_steps = s_max;
+        h_state->noise = stochastic ? r.noise : nullptr; h_state->temperature = r.temperature;
+        h_state->ring = key.solver ? s_ring : nullptr;
+        h_state->cur_trace = -1;
+        for (int i = 0; i < MKD_MAX_STEPS; ++i) h_state->trace_row[i] = -1;
+        h_state->rows = s_rows; h_state->rows_batch = r.batch;
+        memcpy(h_rows, tab.data(), tab.size() * sizeof(StepRow));
+        MKD_HIP_CHECK(hipMemcpyAsync(s_xa, r.x_T, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        hipStream_t ls = stream;
+        if (r.use_graph) {
+            ls = loop_stream;
+            MKD_HIP_CHECK(hipEventRecord(ev_loop_in, stream));
+            MKD_HIP_CHECK(hipStreamWaitEvent(loop_stream, ev_loop_in, 0));
+        }
+        MKD_HIP_CHECK(hipMemcpyAsync(s_state, h_state, sizeof(StepState), hipMemcpyHostToDevice, ls));
+        MKD_HIP_CHECK(hipMemcpyAsync(s_rows, h_rows, tab.size() * sizeof(StepRow), hipMemcpyHostToDevice, ls));
+        if (!r.use_graph) MKD_HIP_CHECK(hipStreamSynchronize(stream));          // (no later call of any form finds the pinned copies in flight)
+        rc = run_temb_table((int)distinct.size(), distinct.data(), ls); if (rc) return rc;
+        if (r.use_graph) rc = replay_steps(s_max, key);
+        else rc = enqueue_state_steps(key, s_max, stream);
+        if (rc) return rc;
+        MKD_HIP_CHECK(hipMemcpyAsync(r.x_out, s_xa, n * sizeof(float), hipMemcpyDeviceToDevice, ls));
+        if (r.use_graph) {
+            MKD_HIP_CHECK(hipEventRecord(ev_loop_out, loop_stream));
+            MKD_HIP_CHECK(hipStreamWaitEvent(stream, ev_loop_out, 0));
+        }
         return 0;
     }
 
@@ -2705,6 +2865,8 @@ struct mkd_ctx {
         if (loop_stream) { hipStreamSynchronize(loop_stream); hipStreamDestroy(loop_stream); hipEventDestroy(ev_loop_in); hipEventDestroy(ev_loop_out); }
         if (h_state) hipHostFree(h_state);
         if (s_state) hipFree(s_state);
+        if (h_rows) hipHostFree(h_rows);
+        if (s_rows) hipFree(s_rows);
         if (s_ring) hipFree(s_ring);
         for (int i = 1; i < NS; ++i)
             if (side_streams[i]) { hipStreamSynchronize(side_streams[i]); hipStreamDestroy(side_streams[i]); }
@@ -2979,6 +3141,36 @@ int mkd_sample_dpmpp_ex(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, 
     r.ex = ex; r.who = ex ? "mkd_sample_dpmpp_ex" : "mkd_sample_dpmpp";
     return ctx->sample(r, (hipStream_t)stream);
 }
+int mkd_step_table(const mkd_sample_row* rows, int batch, int solver, mkd_step_row* out, int* s_max, int64_t* distinct, int* n_distinct) {
+    std::vector<StepRow> tab; std::vector<int64_t> ts;
+    int sm = 0;
+    const int rc = build_step_table(rows, batch, solver, out ? &tab : nullptr, &sm, &ts, nullptr, nullptr);
+    if (rc) return rc;
+    if (out) memcpy(out, tab.data(), tab.size() * sizeof(StepRow));
+    if (s_max) *s_max = sm;
+    if (distinct) memcpy(distinct, ts.data(), ts.size() * sizeof(int64_t));
+    if (n_distinct) *n_distinct = (int)ts.size();
+    return 0;
+}
+int mkd_sample_rows(mkd_ctx* ctx, const float* x_T, int batch, const mkd_sample_row* rows, int solver, const float* noise, float temperature,
+                    const mkd_sample_mask* m, const mkd_sample_extras* ex, float* x_out, int use_graph, void* stream) {
+    if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
+    SampleReq r; r.x_T = x_T; r.batch = batch; r.rows = rows; r.solver = solver; r.noise = noise; r.temperature = temperature;
+    r.qm = m; r.ex = ex; r.x_out = x_out; r.use_graph = use_graph; r.who = "mkd_sample_rows";
+    return ctx->sample_rows(r, (hipStream_t)stream);
+}
+int mkd_ddim_step_rows(const float* x, const float* eps_c, const float* eps_u, const mkd_step_row* rows, const float* noise, float temperature,
+                       float* x_prev, float* pred_x0, int batch, int n_per_sample, void* stream) {
+    if (!x || !eps_c || !rows || !x_prev) return mkd_fail(MKD_ERR_ARG, "mkd_ddim_step_rows: null pointer");
+    if (batch <= 0 || batch > 65535 || n_per_sample <= 0) return mkd_fail(MKD_ERR_ARG, "mkd_ddim_step_rows: batch must be 1..65535, n_per_sample > 0");
+    return launch_ddim_step_rows(x, eps_c, eps_u, (const StepRow*)rows, nullptr, noise, temperature, x_prev, pred_x0, batch, n_per_sample, (hipStream_t)stream);
+}
+int mkd_dpmpp_step_rows(const float* x, const float* eps_c, const float* eps_u, const mkd_step_row* rows, const float* m1, const float* m2,
+                        float* x_prev, float* m0_out, int batch, int n_per_sample, void* stream) {
+    if (!x || !eps_c || !rows || !m1 || !m2 || !x_prev || !m0_out) return mkd_fail(MKD_ERR_ARG, "mkd_dpmpp_step_rows: null pointer");
+    if (batch <= 0 || batch > 65535 || n_per_sample <= 0) return mkd_fail(MKD_ERR_ARG, "mkd_dpmpp_step_rows: batch must be 1..65535, n_per_sample > 0");
+    return launch_dpmpp_step_rows(x, eps_c, eps_u, (const StepRow*)rows, nullptr, m1, m2, x_prev, m0_out, batch, n_per_sample, (hipStream_t)stream);
+}
 int mkd_q_sample_blend(const float* x0, const float* noise, float sqrt_ac, float sqrt_one_minus_ac, const float* mask, int mask_batch,
                        int mask_channels, const float* x, float* out, int batch, int channels, int hw, void* stream) {
     if (!x0 || !noise || !out || (mask && !x)) return mkd_fail(MKD_ERR_ARG, "mkd_q_sample_blend: null pointer");
@@ -3122,6 +3314,7 @@ int mkd_eps_launches(const mkd_ctx* ctx) { return ctx ? ctx->launches_eps : 0; }
 int mkd_step_launches_ex(const mkd_ctx* ctx, int use_graph, int cfg_on) {
     if (!ctx) return 0;
     const int eval = ctx->launches_eps - (ctx->temb_table ? ctx->launches_temb : 0);
+    if (cfg_on & MKD_STEP_PER_SAMPLE) return eval + 2 + ((cfg_on & 3) ? 1 : 0);      // setup, update (+ the doubling), captured or not
     return eval + (use_graph ? 2 : (ctx->temb_table ? 3 : 2)) + (cfg_on ? 1 : 0) + (cfg_on == 2 ? 1 : 0);
 }
 int mkd_step_launches(const mkd_ctx* ctx) { return mkd_step_launches_ex(ctx, 1, 0); }

@@ -55,6 +55,21 @@ __global__ void __launch_bounds__(256) cfg_rescale_factor_kernel(const float* __
 }
 
 // ---- DDIM x0 / x_{t-1} update, reference diffmk/cddim.py:39-40 (CFG) and :63,74-78 ----------------
+// One element, the ONE expression of every DDIM kernel (stand-alone, step state, per-sample rows): the guided eps, then x0 and
+// x_{t-1}, then the eta term.  The library is built with -ffp-contract=fast, and what the compiler fuses depends on the code around
+// an expression (a 16-byte loop body fused sqrt(a_prev) x0 + dir e into an fma for two of its four elements, a scalar one for none),
+// so every rounding is spelled out: explicit fmas, and the two products of the sum pass through an empty asm statement (no
+// instruction; the value is opaque and cannot be folded into an fma).  These are the operations the uniform kernels compiled to
+// before they were spelled out.
+struct DdimCoef { float sqrt_at_inv, sqrt_aprev, dir_coef, s1m; };
+__device__ __forceinline__ float ddim_keep_product(float p) { asm("" : "+v"(p)); return p; }
+__device__ __forceinline__ float ddim_eps_at(float ec, float eu, float cfg_scale) { return fmaf(cfg_scale, ec - eu, eu); }      // model_uncond + s * (model_t - model_uncond)
+__device__ __forceinline__ float ddim_update_at(float xv, float e, const DdimCoef& k, float& p0) {
+    p0 = fmaf(-k.s1m, e, xv) * k.sqrt_at_inv;          // (x - sqrt(1-a_t) e) / sqrt(a_t)
+    return ddim_keep_product(k.sqrt_aprev * p0) + ddim_keep_product(k.dir_coef * e);      // sqrt(a_prev) x0 + sqrt(1-a_prev-sigma^2) e
+}
+__device__ __forceinline__ float ddim_noise_at(float xp, float sigma, float nz, float temperature) { return fmaf(sigma * nz, temperature, xp); }
+
 // kfac non-null (with eps_u): the guidance-rescaled eps; x_copy non-null: x_prev once more (a trace row of the eager loop)
 __global__ void ddim_step_kernel(const float* __restrict__ x, const float* __restrict__ eps_c,
                                  const float* __restrict__ eps_u, float cfg_scale, float sqrt_at_inv,
@@ -62,17 +77,17 @@ __global__ void ddim_step_kernel(const float* __restrict__ x, const float* __res
                                  const float* __restrict__ noise, float temperature,
                                  float* __restrict__ x_prev, float* __restrict__ pred_x0, int64_t n,
                                  const float* __restrict__ kfac, int n_per_sample, float* __restrict__ x_copy) {
+    const DdimCoef k = {sqrt_at_inv, sqrt_aprev, dir_coef, s1m};
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         float e = eps_c[i];
         if (eps_u) {
             const float u = eps_u[i];
             if (kfac) e = cfg_rescaled_eps_at(e, u, cfg_scale, kfac, i, n_per_sample);
-            else e = u + cfg_scale * (e - u);       // model_uncond + s * (model_t - model_uncond)
+            else e = ddim_eps_at(e, u, cfg_scale);
         }
-        const float xv = x[i];
-        const float p0 = (xv - s1m * e) * sqrt_at_inv;   // (x - sqrt(1-a_t) e) / sqrt(a_t)
-        float xp = sqrt_aprev * p0 + dir_coef * e;       // sqrt(a_prev) x0 + sqrt(1-a_prev-sigma^2) e
-        if (noise) xp += sigma_t * noise[i] * temperature;
+        float p0;
+        float xp = ddim_update_at(x[i], e, k, p0);
+        if (noise) xp = ddim_noise_at(xp, sigma_t, noise[i], temperature);
         x_prev[i] = xp;
         if (pred_x0) pred_x0[i] = p0;
         if (x_copy) x_copy[i] = xp;
@@ -170,7 +185,7 @@ __global__ void temb_select_kernel(const TembSel ts, int step) {
 __global__ void ddim_step_state_kernel(float* __restrict__ x, const float* __restrict__ eps_c, const float* __restrict__ eps_u,
                                        float cfg_scale, StepState* __restrict__ st, int64_t n,
                                        const float* __restrict__ kfac, int n_per_sample) {
-    const float sqrt_at_inv = st->cur[0], sqrt_aprev = st->cur[1], dir_coef = st->cur[2], s1m = st->cur[3];
+    const DdimCoef k = {st->cur[0], st->cur[1], st->cur[2], st->cur[3]};
     const float* __restrict__ const nz = (st->noise && st->cur_sigma != 0.f) ? st->noise + (int64_t)st->cur_row * n : nullptr;
     const int row = st->cur_trace;
     float* __restrict__ const tx = (st->trace_x && row >= 0) ? st->trace_x + (int64_t)row * n : nullptr;
@@ -181,11 +196,11 @@ __global__ void ddim_step_state_kernel(float* __restrict__ x, const float* __res
         if (eps_u) {
             const float u = eps_u[i];
             if (kfac) e = cfg_rescaled_eps_at(e, u, cfg_scale, kfac, i, n_per_sample);
-            else e = u + cfg_scale * (e - u);
+            else e = ddim_eps_at(e, u, cfg_scale);
         }
-        const float p0 = (x[i] - s1m * e) * sqrt_at_inv;
-        float xp = sqrt_aprev * p0 + dir_coef * e;
-        if (nz) xp += st->cur_sigma * nz[i] * st->temperature;          // (ddim_step_kernel's order of operations: same bits as the eager loop)
+        float p0;
+        float xp = ddim_update_at(x[i], e, k, p0);
+        if (nz) xp = ddim_noise_at(xp, st->cur_sigma, nz[i], st->temperature);
         x[i] = xp;
         if (tx) tx[i] = xp;
         if (tx0) tx0[i] = p0;
@@ -277,6 +292,118 @@ __global__ void dpmpp_step_state_kernel(float* x, const float* __restrict__ eps_
     const float* const m2 = ring + (int64_t)st->cur_slot[2] * n;
     if (blockIdx.x == 0 && threadIdx.x == 0) st->counter = st->counter - 1;      // (nothing else in this kernel reads it)
     dpmpp_update_range(x, eps_c, eps_u, cfg_scale, k, m1, m2, x, m0, n, kfac, n_per_sample, tx, tx0);
+}
+
+// ---- per-sample loop (mkd_sample_rows): every sample of the batch has its own schedule, guidance scale and sigmas -------------------
+// Grid (x, sample): what a workgroup needs of its sample (one StepRow) has a workgroup-uniform address, so it is read once into
+// scalars, and no element is divided by the sample size.  The element updates are ddim_update_at / dpmpp_update_range above: row b
+// has the bits of the uniform kernels run with sample b's numbers.
+//
+// First kernel of a per-sample step.  Block (0, b) writes t_out[b]; every block copies its share of row b's time-embedding rows (row
+// temb_row of sample b % samples: with guidance both halves of the doubled batch take their sample's row).  The executed step k goes
+// to st->cur_row for the step's last kernel, which moves the counter (read-only here, as in step_setup_kernel).
+__global__ void step_setup_rows_kernel(StepState* st, int64_t* t_out, int samples, const TembSel ts) {
+    const int k = st->n_steps - 1 - st->counter;
+    const int b = blockIdx.y;
+    const StepRow* __restrict__ r = st->rows + (int64_t)k * samples + (b % samples);
+    const int64_t t = r->t;
+    const int row = r->temb_row;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        t_out[b] = t;
+        if (b == 0) st->cur_row = k;
+    }
+    const int gtid = blockIdx.x * blockDim.x + threadIdx.x, gthreads = gridDim.x * blockDim.x;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int nv = ts.n[j] >> 2;
+        if (!nv) continue;
+        const f32x4* __restrict__ src = (const f32x4*)(ts.tab[j] + (size_t)row * ts.n[j]);
+        f32x4* __restrict__ dst = (f32x4*)(ts.proj[j] + (size_t)b * ts.n[j]);
+        for (int i = gtid; i < nv; i += gthreads) dst[i] = src[i];
+    }
+}
+
+// One sample's DDIM update over its `per` elements (pointers already at the sample).  16-byte accesses when per is a multiple of 4
+// and every pointer is 16-byte aligned, scalar otherwise: the same arithmetic per element.  x_prev may alias x.
+__device__ __forceinline__ void ddim_update_range(const float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u,
+                                                  float scale, const DdimCoef k, float sigma, const float* __restrict__ nz, float temperature,
+                                                  float* x_prev, float* __restrict__ pred_x0, int per) {
+    const int tid = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
+    const uintptr_t al = (uintptr_t)x | (uintptr_t)eps_c | (uintptr_t)eps_u | (uintptr_t)nz | (uintptr_t)x_prev | (uintptr_t)pred_x0;
+    if (!(per & 3) && !(al & 15)) {
+        for (int i = tid; i < (per >> 2); i += nth) {
+            const f32x4 xv = ((const f32x4*)x)[i];
+            f32x4 ev = ((const f32x4*)eps_c)[i], pv, rv;
+            if (eps_u) {
+                const f32x4 uv = ((const f32x4*)eps_u)[i];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) ev[j] = ddim_eps_at(ev[j], uv[j], scale);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { float p0; rv[j] = ddim_update_at(xv[j], ev[j], k, p0); pv[j] = p0; }
+            if (nz) {
+                const f32x4 zv = ((const f32x4*)nz)[i];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) rv[j] = ddim_noise_at(rv[j], sigma, zv[j], temperature);
+            }
+            ((f32x4*)x_prev)[i] = rv;
+            if (pred_x0) ((f32x4*)pred_x0)[i] = pv;
+        }
+        return;
+    }
+    for (int i = tid; i < per; i += nth) {
+        float e = eps_c[i];
+        if (eps_u) e = ddim_eps_at(e, eps_u[i], scale);
+        float p0;
+        float xp = ddim_update_at(x[i], e, k, p0);
+        if (nz) xp = ddim_noise_at(xp, sigma, nz[i], temperature);
+        x_prev[i] = xp;
+        if (pred_x0) pred_x0[i] = p0;
+    }
+}
+
+// st non-null: the step's last kernel, in place (x_prev == x), entries / noise row of the executed step st->cur_row; st null: the
+// stand-alone form on `rows` [gridDim.y].  A finished sample's blocks return before any load or store of its rows.
+__global__ void ddim_step_rows_kernel(const float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u,
+                                      const StepRow* __restrict__ rows, StepState* st, const float* __restrict__ noise, float temperature,
+                                      float* x_prev, float* __restrict__ pred_x0, int per) {
+    const int b = blockIdx.y, nb = gridDim.y;
+    if (st) {
+        const int k = st->cur_row;
+        rows = st->rows + (int64_t)k * nb;
+        noise = st->noise ? st->noise + (int64_t)k * nb * per : nullptr;
+        temperature = st->temperature;
+        if (blockIdx.x == 0 && b == 0 && threadIdx.x == 0) st->counter = st->counter - 1;      // (nothing else in this kernel reads it)
+    }
+    const StepRow r = rows[b];
+    if (!r.active) return;
+    const int64_t off = (int64_t)b * per;
+    const DdimCoef k = {r.coef[0], r.coef[1], r.coef[2], r.coef[3]};
+    ddim_update_range(x + off, eps_c + off, eps_u ? eps_u + off : nullptr, r.scale, k, r.sigma,
+                      (noise && r.sigma != 0.f) ? noise + off : nullptr, temperature, x_prev + off, pred_x0 ? pred_x0 + off : nullptr, per);
+}
+
+// ... and the DPM-Solver++ update: dpmpp_update_range over the sample's elements.  st non-null: in place, ring slots of the executed
+// step (m_k into slot k mod 3); st null: m1 / m2 / m0_out / x_prev as given
+__global__ void dpmpp_step_rows_kernel(const float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u,
+                                       const StepRow* __restrict__ rows, StepState* st, const float* m1, const float* m2,
+                                       float* x_prev, float* m0_out, int per) {
+    const int b = blockIdx.y, nb = gridDim.y;
+    if (st) {
+        const int k = st->cur_row;
+        const int64_t n = (int64_t)nb * per;
+        rows = st->rows + (int64_t)k * nb;
+        m0_out = st->ring + (int64_t)(k % 3) * n;
+        m1 = st->ring + (int64_t)((k + 2) % 3) * n;
+        m2 = st->ring + (int64_t)((k + 1) % 3) * n;
+        if (blockIdx.x == 0 && b == 0 && threadIdx.x == 0) st->counter = st->counter - 1;      // (nothing else in this kernel reads it)
+    }
+    const StepRow r = rows[b];
+    if (!r.active) return;
+    const int64_t off = (int64_t)b * per;
+    const DpmCoef k = {r.dpm[0], r.dpm[1], r.dpm[2], r.dpm[3], r.dpm[4], r.dpm[5]};
+    dpmpp_update_range(x + off, eps_c + off, eps_u ? eps_u + off : nullptr, r.scale, k, m1 ? m1 + off : nullptr, m2 ? m2 + off : nullptr,
+                       x_prev + off, m0_out + off, per, nullptr, 0, nullptr, nullptr);
 }
 
 // ---- GEGLU: y = a * gelu_erf(gate) ----------------------------------------------------------------
@@ -858,6 +985,43 @@ int launch_dpmpp_step_state(float* x, const float* eps_c, const float* eps_u, fl
     if (int rc = check_kfac(kfac, eps_u, n_per_sample, n, "dpmpp_step_state")) return rc;
     hipLaunchKernelGGL(dpmpp_step_state_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale, st, n, kfac, n_per_sample);
     MKD_LAUNCH_CHECK("dpmpp_step_state_kernel");
+    return 0;
+}
+
+// blocks along x for one sample of `per` elements: ~4 elements per thread (one 16-byte access), at most 64 per sample
+static int rows_blocks(int per) {
+    const int b = (per + 1023) / 1024;
+    return b < 1 ? 1 : (b > 64 ? 64 : b);
+}
+int launch_step_setup_rows(StepState* st, int64_t* t_out, int batch, int samples, hipStream_t stream, const TembSel* tsp) {
+    TembSel ts; memset(&ts, 0, sizeof(ts));
+    if (tsp) ts = *tsp;
+    if ((ts.n[0] | ts.n[1]) & 3) return mkd_fail(-1, "step_setup_rows: row lengths must be multiples of 4");
+    if (!st || !t_out || samples <= 0 || batch <= 0 || batch > 65535 || batch % samples) return mkd_fail(-1, "step_setup_rows: bad arguments");
+    if ((ts.n[0] || ts.n[1]) && ts.batch != batch) return mkd_fail(-1, "step_setup_rows: the time-embedding rows are not of this batch");
+    const int nv = (ts.n[0] > ts.n[1] ? ts.n[0] : ts.n[1]) >> 2;
+    int blocks = (nv + 1023) / 1024;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(step_setup_rows_kernel, dim3(blocks, batch), dim3(256), 0, stream, st, t_out, samples, ts);
+    MKD_LAUNCH_CHECK("step_setup_rows_kernel");
+    return 0;
+}
+int launch_ddim_step_rows(const float* x, const float* eps_c, const float* eps_u, const StepRow* rows, StepState* st, const float* noise,
+                          float temperature, float* x_prev, float* pred_x0, int samples, int n_per_sample, hipStream_t stream) {
+    if (!x || !eps_c || !x_prev || (!rows && !st) || (st && x_prev != x) || samples <= 0 || samples > 65535 || n_per_sample <= 0)
+        return mkd_fail(-1, "ddim_step_rows: bad arguments");
+    hipLaunchKernelGGL(ddim_step_rows_kernel, dim3(rows_blocks(n_per_sample), samples), dim3(256), 0, stream, x, eps_c, eps_u, rows, st, noise,
+                       temperature, x_prev, pred_x0, n_per_sample);
+    MKD_LAUNCH_CHECK("ddim_step_rows_kernel");
+    return 0;
+}
+int launch_dpmpp_step_rows(const float* x, const float* eps_c, const float* eps_u, const StepRow* rows, StepState* st, const float* m1,
+                           const float* m2, float* x_prev, float* m0_out, int samples, int n_per_sample, hipStream_t stream) {
+    if (!x || !eps_c || !x_prev || (!rows && !st) || (!st && (!m1 || !m2 || !m0_out)) || (st && x_prev != x) || samples <= 0 || samples > 65535 || n_per_sample <= 0)
+        return mkd_fail(-1, "dpmpp_step_rows: bad arguments");
+    hipLaunchKernelGGL(dpmpp_step_rows_kernel, dim3(rows_blocks(n_per_sample), samples), dim3(256), 0, stream, x, eps_c, eps_u, rows, st, m1, m2,
+                       x_prev, m0_out, n_per_sample);
+    MKD_LAUNCH_CHECK("dpmpp_step_rows_kernel");
     return 0;
 }
 

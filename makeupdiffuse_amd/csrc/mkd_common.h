@@ -124,7 +124,21 @@ struct AttnIo { const bf16_t* q; const bf16_t* k; const bf16_t* v; bf16_t* o; };
 struct ConvInIo { const bf16_t* w; const float* bias; bf16_t* y; const bf16_t* add; };     // 4 -> C input convolution (same x for both nets)
 
 // device-resident DDIM step state (hipGraph replay): tables of n_steps entries, counter runs n_steps-1 .. 0
-constexpr int MKD_MAX_STEPS = 1024;
+#ifndef MKD_MAX_STEPS
+#define MKD_MAX_STEPS 1024          // (include/mkd.h has the same definition)
+#endif
+// One entry of the per-sample step table (mkd_sample_rows): what sample b does in executed step k, at [k * batch + b] of a device
+// buffer [S_max][batch] filled on the host per call.  64 bytes; the layout is mkd_step_row of include/mkd.h (engine.hip asserts it).
+// A sample that has run all its steps keeps the timestep / table row of its entry 0 (the model is still evaluated for it) with active = 0
+struct StepRow {
+    int64_t t;
+    float coef[4];          // sqrt(1/a_t), sqrt(a_prev), sqrt(1-a_prev-sigma^2), sqrt(1-a_t): StepState::coef of the sample's entry
+    float sigma;
+    float dpm[6];           // DpmCoef of the sample's entry (a DPM-Solver++ call)
+    int temb_row;           // row of the call's time-embedding table that holds t
+    int active;             // 0: the sample is finished, its rows are not touched
+    float scale;            // the sample's guidance scale
+};
 struct StepState {
     int counter;
     float cur[4];                          // sqrt(1/a_t), sqrt(a_prev), sqrt(1-a_prev), sqrt(1-a_t) of the current step
@@ -157,6 +171,10 @@ struct StepState {
     // guidance rescale (mkd_sample_extras.guidance_rescale): the phi cfg_rescale_factor_kernel reads inside a replayed step, so a new
     // phi needs no new capture
     float phi;
+    // per-sample loop (mkd_sample_rows): rows [n_steps][rows_batch] on the device, n_steps = the longest sample's; the step's kernels
+    // take timestep, coefficients, scale and sigma of sample b in executed step k = n_steps - 1 - counter from rows[k * rows_batch + b]
+    // instead of the tables above.  null: the uniform loop
+    const StepRow* rows; int rows_batch;
 };
 // the six schedule-only numbers of one DPM-Solver++ step
 struct DpmCoef { float inv_alpha, sigma, cx, c0, c1, c2; };
@@ -313,6 +331,17 @@ int launch_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, fl
 // the same update in place with the coefficients / ring slots step_setup_kernel published; the step's LAST kernel: advances the counter
 int launch_dpmpp_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
                             hipStream_t stream, const float* kfac = nullptr, int n_per_sample = 0);
+// ---- per-sample loop (kernels_misc.hip) ----
+// first kernel of a per-sample step (st->rows non-null): t_out[b] = the timestep of sample b % samples in this executed step (`batch` rows:
+// both halves with guidance), row temb_row of the tables into row b of each proj, and the executed step into st->cur_row
+int launch_step_setup_rows(StepState* st, int64_t* t_out, int batch, int samples, hipStream_t stream, const TembSel* ts = nullptr);
+// The per-sample updates, one grid row per sample; a finished sample's blocks return before any load or store.  st non-null: in place
+// on x with the entries of this executed step, noise row / ring slots by the step, the step's LAST kernel (moves the counter).
+// st null: rows = `samples` device entries, x_prev (/ m0_out) written for active samples only; DDIM: noise [samples * per] or null, pred_x0 or null
+int launch_ddim_step_rows(const float* x, const float* eps_c, const float* eps_u, const StepRow* rows, StepState* st, const float* noise,
+                          float temperature, float* x_prev, float* pred_x0, int samples, int n_per_sample, hipStream_t stream);
+int launch_dpmpp_step_rows(const float* x, const float* eps_c, const float* eps_u, const StepRow* rows, StepState* st, const float* m1,
+                           const float* m2, float* x_prev, float* m0_out, int samples, int n_per_sample, hipStream_t stream);
 int launch_softmax_rows(const bf16_t* x, bf16_t* y, int rows, int cols, hipStream_t stream);
 int launch_post_quant(const float* z, const bf16_t* w, const float* bias, float inv_scale, float* out, int batch, int C, int hw,
                       hipStream_t stream);

@@ -122,6 +122,38 @@ class DDIMSampler:
                                   unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0,
                                   guidance_rescale=guidance_rescale)
 
+    # -- per-sample requests in one batch (batching.SampleSpec; the in-library per-sample loop, mkd_sample_rows) --
+    def _rows_hook(self, what):
+        fast = getattr(self.model, 'sample_rows_fast', None)
+        if fast is None:
+            raise NotImplementedError(f'{what} runs inside libmkd only: the model has no sample_rows_fast hook')
+        return fast
+
+    @torch.no_grad()
+    def sample_specs(self, specs, shape, conditioning, x_T=None, unconditional_guidance_scale=None, unconditional_conditioning=None,
+                     temperature=1.0):
+        """One ``SampleSpec`` (steps, eta, guidance, t_start) per sample of the batch, all in ONE loop of max(steps) executed steps:
+        every sample starts at once and stops after its own steps.  Sample b gets what ``sample(S=steps_b, eta=eta_b,
+        unconditional_guidance_scale=guidance_b)`` gives it, bit for bit, with rows 0 .. n_b - 1 of the noise.  Host draw order: x_T
+        (unless given), then for each executed step in order one randn of the full batch shape when some active sample has a non-zero
+        sigma in it.  The scales come from the specs (``unconditional_guidance_scale`` must stay None); a guided spec needs
+        ``unconditional_conditioning``.  No registered buffer of this sampler is touched."""
+        from .batching import build_rows, draw_noise, guided
+        if unconditional_guidance_scale is not None:
+            raise ValueError('sample_specs: the guidance scale is per sample (SampleSpec.guidance)')
+        rows = build_rows(specs, self.model.alphas_cumprod, 'ddim', self.ddpm_num_timesteps)
+        if guided(rows) and unconditional_conditioning is None:
+            raise ValueError('sample_specs: a spec with guidance != 1 needs unconditional_conditioning')
+        fast = self._rows_hook('sample_specs')
+        C, H, W = shape
+        size = (len(rows), C, H, W)
+        device = self.model.device
+        img = torch.randn(size, device=device) if x_T is None else x_T
+        if tuple(img.shape) != size:
+            raise ValueError(f'sample_specs: x_T must be {size}, got {tuple(img.shape)}')
+        noise = draw_noise(rows, size, device)
+        return fast(img, conditioning, rows, 'ddim', unconditional_conditioning, noise, temperature)
+
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, callback=None, log_every_t=100, temperature=1.0, noise_dropout=0.0,
                       unconditional_guidance_scale=1.0, unconditional_conditioning=None, timesteps=None, mask=None, x0=None,
@@ -365,7 +397,23 @@ class DDIMSampler:
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
                use_original_steps=False, callback=None):
         """Reverse loop over ddim_timesteps[:t_start], newest first (UPSTREAM DDIMSampler.decode; the loop
-        MKDDIMSampler.reconstruct runs): inverts encode(x0, t_enc=t_start) for an eps that does not depend on x."""
+        MKDDIMSampler.reconstruct runs): inverts encode(x0, t_enc=t_start) for an eps that does not depend on x.
+        ``t_start`` as a sequence / tensor of length B: sample b runs entries t_start_b - 1 .. 0 of the current schedule in one
+        per-sample loop (the edit strength per sample after an inversion) and gets the bits of the scalar call with t_start_b; it
+        needs the in-library loop (eta = 0, no callback, no use_original_steps).  A scalar takes the path below unchanged."""
+        if isinstance(t_start, (list, tuple, np.ndarray)) or (isinstance(t_start, torch.Tensor) and t_start.dim() > 0):
+            from .batching import start_rows
+            if use_original_steps or callback is not None:
+                raise NotImplementedError('a per-sample t_start runs inside libmkd: no use_original_steps, no callback')
+            cfg_on = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.0)
+            rows = start_rows(t_start, self.ddim_timesteps, self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sqrt_one_minus_alphas,
+                              cfg_scale=float(unconditional_guidance_scale) if cfg_on else 1.0)
+            if len(rows) != x_latent.shape[0]:
+                raise ValueError(f't_start has {len(rows)} entries for a batch of {x_latent.shape[0]}')
+            if float(self.ddim_sigmas[:max(r.n for r in rows)].abs().max()) != 0.0:
+                raise NotImplementedError('a per-sample t_start is deterministic: make_schedule with ddim_eta = 0')
+            return self._rows_hook('a per-sample t_start')(x_latent, cond, rows, 'ddim', unconditional_conditioning if cfg_on else None,
+                                                           None, 1.0)
         timesteps = np.arange(self.ddpm_num_timesteps) if use_original_steps else self.ddim_timesteps
         timesteps = timesteps[:t_start]
         time_range = np.flip(timesteps)

@@ -294,6 +294,17 @@ class BaseMakeUpDiffuse:
                           x0=x0, mask=mask, q_sqrt_ac=q_sqrt_ac, q_sqrt_1m_ac=q_sqrt_1m_ac, q_noise=q_noise,
                           guidance_rescale=float(guidance_rescale), **trace)
 
+    def sample_rows_fast(self, x_latent, cond, rows, solver='ddim', unconditional_conditioning=None, noise=None, temperature=1.0):
+        """the whole loop with one request row per sample inside libmkd (mkd_sample_rows; rows: batching.RowTables).  The engine is
+        bound to [uncond; cond] exactly when some row's scale is not 1"""
+        from ..batching import guided
+        g = guided(rows)
+        if g and unconditional_conditioning is None:
+            raise ValueError('a row with a guidance scale != 1 needs the unconditional conditioning')
+        c = self.cfg_conditioning(unconditional_conditioning, cond) if g else cond
+        eng = self._bind_cond(c, x_latent.shape[2:])
+        return eng.sample_rows(x_latent, rows, solver=solver, noise=noise, temperature=float(temperature), use_graph=bool(self.sample_use_graph))
+
     def dpmpp_step(self, x, e_c, e_u, scale, coef6, m1=None, m2=None, guidance_rescale=0.0):
         """one DPM-Solver++ multistep update on the device (DPMSolverSampler's per-step loop): (x_prev, x0-prediction), the kernel
         arithmetic of the in-library loop"""
@@ -535,6 +546,47 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                 if self.makeup_score:
                     log[f'makeup_hist_cfg_scale_{self.unconditional_guidance_scale:.2f}'] = self.makeup_hist(batch, log[name], c['ref_img'])
         return log
+
+    @torch.no_grad()
+    def transfer_specs(self, batch: dict, specs, x_T: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """One ``batching.SampleSpec`` per pair of the batch (steps, eta, guidance, t_start, order), sampled together: requests that
+        differ in step count, strength, guidance scale or eta share one batch.  As in log_results the conditioning is the pair's hint
+        and text, and a guided sample's unconditional branch keeps the SAME hint.  One pass per prepared-batch form: the samples whose
+        guidance is 1 run as one per-sample loop on the batch-B conditioning, the others as one on [uncond; cond]; each pass is one
+        loop of its longest member.  The ``sampler`` attribute picks the solver.  Returns samples_latent (rows in batch order) and,
+        with a first stage, the decoded samples."""
+        from ..batching import SampleSpec
+        specs = list(specs)
+        _, c = self.get_input(batch, self.first_stage_key)
+        c_cat, c_txt = c['c_concat'][0], c['c_crossattn'][0]
+        b = c_cat.shape[0]
+        if len(specs) != b or not all(isinstance(s, SampleSpec) for s in specs):
+            raise ValueError(f'transfer_specs: one SampleSpec per pair is needed ({len(specs)} for a batch of {b})')
+        if self.sampler not in ('ddim', 'dpmpp'):
+            raise ValueError(f"sampler must be 'ddim' or 'dpmpp', got {self.sampler!r}")
+        h, w = c_cat.shape[2] // 8, c_cat.shape[3] // 8
+        if x_T is None:
+            x_T = torch.randn(b, self.channels, h, w, device=self.device)
+        x_T = x_T.to(self.device)
+        if tuple(x_T.shape) != (b, self.channels, h, w):
+            raise ValueError(f'transfer_specs: x_T must be {(b, self.channels, h, w)}, got {tuple(x_T.shape)}')
+        smp = DPMSolverSampler(self) if self.sampler == 'dpmpp' else DDIMSampler(self)
+        lat = torch.empty_like(x_T)
+        for want_guided in (False, True):
+            idx = [i for i, s in enumerate(specs) if (float(s.guidance) != 1.0) == want_guided]
+            if not idx:
+                continue
+            sel = torch.as_tensor(idx, device=self.device)
+            cond = {'c_concat': [c_cat[sel].contiguous()], 'c_crossattn': [c_txt[sel].contiguous()]}
+            uc = None
+            if want_guided:
+                uc = {'c_concat': cond['c_concat'], 'c_crossattn': [self.get_unconditional_conditioning(len(idx))]}
+            lat[sel] = smp.sample_specs([specs[i] for i in idx], (self.channels, h, w), cond, x_T=x_T[sel].contiguous(),
+                                        unconditional_conditioning=uc)
+        out = {'samples_latent': lat}
+        if self.has_first_stage:
+            out['samples'] = self.decode_first_stage(lat)
+        return out
 
     def _log_denoise_row(self, log: dict, name: str, pred_x0: list) -> None:
         """reference _get_denoise_row_from_list before its make_grid: the pred_x0 list of a pass (x_T first, then one entry per logged

@@ -113,6 +113,28 @@ class DPMSolverSampler:
         return img, intermediates
 
     @torch.no_grad()
+    def sample_specs(self, specs, shape, conditioning, x_T=None, unconditional_guidance_scale=None, unconditional_conditioning=None,
+                     temperature=1.0):
+        """``DDIMSampler.sample_specs`` on this solver: one ``SampleSpec`` (steps, guidance, order, t_start; eta must be 0) per sample
+        in one loop of max(steps) evaluations.  Sample b gets the bits of ``sample(S=steps_b, order=order_b,
+        unconditional_guidance_scale=guidance_b)``."""
+        from .batching import build_rows, guided
+        if unconditional_guidance_scale is not None:
+            raise ValueError('sample_specs: the guidance scale is per sample (SampleSpec.guidance)')
+        if temperature != 1.0:
+            raise NotImplementedError('DPMSolverSampler draws no noise: temperature does not apply')
+        rows = build_rows(specs, self.model.alphas_cumprod, 'dpmpp', self.ddpm_num_timesteps)
+        if guided(rows) and unconditional_conditioning is None:
+            raise ValueError('sample_specs: a spec with guidance != 1 needs unconditional_conditioning')
+        fast = self._ddim._rows_hook('sample_specs')
+        C, H, W = shape
+        size = (len(rows), C, H, W)
+        img = torch.randn(size, device=self.model.device) if x_T is None else x_T
+        if tuple(img.shape) != size:
+            raise ValueError(f'sample_specs: x_T must be {size}, got {tuple(img.shape)}')
+        return fast(img, conditioning, rows, 'dpmpp', unconditional_conditioning, None, 1.0)
+
+    @torch.no_grad()
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1., unconditional_conditioning=None, order=2,
                lower_order_final=True, callback=None):
         """Reverse loop over ddim_timesteps[:t_start], newest first (the loop MKDDIMSampler.reconstruct runs, on the schedule of the

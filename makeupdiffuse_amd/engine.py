@@ -151,6 +151,73 @@ def dpmpp_table(alphas: Sequence[float], alphas_prev: Sequence[float], order: in
     return np.ctypeslib.as_array(out).reshape(n, 6).copy(), np.ctypeslib.as_array(so).astype(np.int32)
 
 
+SOLVERS = {'ddim': 0, 'dpmpp': 1}
+# numpy view of mkd_step_row (include/mkd.h), 64 bytes
+STEP_ROW_DTYPE = np.dtype([('t', '<i8'), ('coef', '<f4', (4,)), ('sigma', '<f4'), ('dpm', '<f4', (6,)), ('temb_row', '<i4'),
+                           ('active', '<i4'), ('scale', '<f4')])
+assert STEP_ROW_DTYPE.itemsize == C.sizeof(_lib.StepRowC) == 64
+
+
+def _solver_id(solver) -> int:
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be 'ddim' or 'dpmpp', got {solver!r}")
+    return SOLVERS[solver]
+
+
+def _row_field(row, name, default=None):
+    return row.get(name, default) if isinstance(row, dict) else getattr(row, name, default)
+
+
+def pack_sample_rows(rows, solver: str = 'ddim'):
+    """``rows``: one request per sample, each an object (or dict) with ``timesteps`` and ``cfg_scale`` (default 1), for 'ddim'
+    ``alphas`` / ``alphas_prev`` / ``sqrt_one_minus_alphas`` and optionally ``sigmas``, for 'dpmpp' ``dpm`` (the [n, 6] rows of
+    ``dpmpp_table``); batching.build_rows makes them.  Returns (mkd_sample_row array, the host arrays it points at).  A table that is
+    None stays a NULL pointer and a wrong length is the caller's error here (ValueError); everything else is checked by libmkd."""
+    _solver_id(solver)
+    rows = list(rows)
+    if not rows:
+        raise ValueError('rows must hold one request per sample')
+    arr = (_lib.SampleRowC * len(rows))()
+    keep = []
+    for b, row in enumerate(rows):
+        ts = _row_field(row, 'timesteps')
+        n = 0 if ts is None else len(ts)
+        arr[b].n_steps = n
+        arr[b].cfg_scale = float(_row_field(row, 'cfg_scale', 1.0))
+        if ts is not None:
+            a = (C.c_int64 * max(n, 1))(*[int(v) for v in ts]); keep.append(a)
+            arr[b].timesteps = C.cast(a, C.POINTER(C.c_int64))
+        for name in ('alphas', 'alphas_prev', 'sqrt_one_minus_alphas', 'sigmas', 'dpm'):
+            v = _row_field(row, name)
+            if v is None:
+                continue
+            flat = np.asarray(v, dtype=np.float32).reshape(-1)
+            if ts is not None and flat.size != (6 * n if name == 'dpm' else n):
+                raise ValueError(f'rows[{b}].{name} has {flat.size} entries for {n} steps')
+            a = (C.c_float * max(flat.size, 1))(*flat.tolist()); keep.append(a)
+            setattr(arr[b], name, C.cast(a, C.POINTER(C.c_float)))
+        n_over = _row_field(row, 'n_steps')          # (tests: a count that disagrees with the tables, e.g. 0 or beyond the limit)
+        if n_over is not None:
+            arr[b].n_steps = int(n_over)
+    return arr, keep
+
+
+def step_table(rows, solver: str = 'ddim') -> Tuple[np.ndarray, List[int]]:
+    """The step table of a per-sample call (include/mkd.h mkd_step_table; host only, needs no device): ``(entries [S_max, B] of
+    STEP_ROW_DTYPE, the call's distinct timesteps in first-seen order)``.  Executed step k, sample b: active while k < n_steps_b, table
+    entry n_steps_b - 1 - k; a finished sample keeps the timestep / table row of its entry 0."""
+    arr, keep = pack_sample_rows(rows, solver)
+    lib = _lib.load()
+    sm, nd = C.c_int(), C.c_int()
+    _lib.check(lib.mkd_step_table(arr, len(arr), _solver_id(solver), None, C.byref(sm), None, C.byref(nd)), 'mkd_step_table')
+    out = np.zeros((sm.value, len(arr)), dtype=STEP_ROW_DTYPE)
+    ts = (C.c_int64 * max(nd.value, 1))()
+    _lib.check(lib.mkd_step_table(arr, len(arr), _solver_id(solver), out.ctypes.data_as(C.POINTER(_lib.StepRowC)), None, ts, None),
+               'mkd_step_table')
+    del keep
+    return out, [int(v) for v in ts[:nd.value]]
+
+
 def sample_log_rows(n_steps: int, log_every_t: int) -> int:
     """Rows the in-library loop's trace keeps (include/mkd.h mkd_sample_log_rows; host only): the table entries i of an n_steps loop
     with ``i % log_every_t == 0 or i == n_steps - 1``."""
@@ -675,6 +742,111 @@ class MkdEngine:
         self._hold(keep, None)
         return (out, *rows) if want_trace else out
 
+    # ---- per-sample requests in one batch (include/mkd.h mkd_sample_rows) ------------------------------------------------------
+    def sample_rows(self, x_T: torch.Tensor, rows, solver: str = 'ddim', noise: Optional[torch.Tensor] = None, temperature: float = 1.0,
+                    use_graph: bool = False, x0: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                    want_trace: bool = False, guidance_rescale: float = 0.0) -> torch.Tensor:
+        """The whole reverse loop with one request per sample: ``rows`` as for ``pack_sample_rows`` (batching.build_rows), each with its
+        own schedule, guidance scale and sigmas.  All samples start together, short ones finish first and are not touched again.  The
+        prepared batch is B when every scale is 1, else 2B (unconditional half first).  eta > 0: ``noise`` [S_max, B, 4, h, w], row k =
+        the draw of executed step k.  Row b has the bits of the uniform call with sample b's request.  ``x0`` / ``mask`` /
+        ``want_trace`` / ``guidance_rescale`` are not combined with per-sample rows: libmkd refuses them (MkdError)."""
+        x_T = _f32c(x_T, self.device)
+        rows = list(rows)
+        arr, keep = pack_sample_rows(rows, solver)
+        if x_T.dim() != 4 or tuple(x_T.shape[1:]) != (self.cfg.in_channels, *self.latent_hw) or x_T.shape[0] != len(arr):
+            # libmkd copies batch * C * h * w floats using the PREPARED h, w: a smaller latent would be read out of bounds
+            raise ValueError(f'x_T {tuple(x_T.shape)} does not match the rows / the prepared latent: expected '
+                             f'({len(arr)}, {self.cfg.in_channels}, {self.latent_hw[0]}, {self.latent_hw[1]})')
+        rows = list(rows)
+        lens = [0 if _row_field(r, 'timesteps') is None else len(_row_field(r, 'timesteps')) for r in rows]
+        s_max = max(lens)
+        stochastic = solver == 'ddim' and any(_row_field(r, 'sigmas') is not None and any(float(v) != 0.0 for v in _row_field(r, 'sigmas'))
+                                              for r in rows)
+        if stochastic:
+            if noise is None or tuple(noise.shape) != (s_max, *x_T.shape):
+                raise ValueError(f'eta > 0 needs noise of shape {(s_max, *x_T.shape)} (one draw per executed step)')
+            noise = _f32c(noise, self.device)
+        else:
+            noise = None
+        qm = None
+        if x0 is not None or mask is not None:
+            qm = _lib.SampleMaskC(_ptr(x0), _ptr(mask), 1, 1, None, None, None)
+        ex = None
+        phi = check_guidance_rescale(guidance_rescale)
+        if want_trace or phi != 0.0:
+            dummy = torch.empty_like(x_T) if want_trace else None
+            ex = _lib.SampleExtrasC(1, 1, _ptr(dummy), None, phi)
+        out = torch.empty_like(x_T)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mkd_sample_rows(self._ctx, C.c_void_p(x_T.data_ptr()), len(arr), arr, _solver_id(solver),
+                                                C.c_void_p(_ptr(noise)), float(temperature), None if qm is None else C.byref(qm),
+                                                None if ex is None else C.byref(ex), C.c_void_p(out.data_ptr()), int(use_graph),
+                                                C.c_void_p(_stream())), 'mkd_sample_rows')
+        # the replayed loop reads `noise` after this call returns: it stays referenced until the next per-sample call.  No host wait:
+        # the caller's stream waits for the loop, so the caching allocator can only hand the block to work ordered after it
+        self._rows_keep = noise
+        del keep
+        return out
+
+    def _step_entries(self, entries, B: int) -> torch.Tensor:
+        """[B] step-table entries (STEP_ROW_DTYPE array, or a uint8 device tensor [B, 64]) on the device"""
+        if isinstance(entries, torch.Tensor):
+            e = entries.to(self.device).contiguous()
+        else:
+            e = np.ascontiguousarray(np.asarray(entries, dtype=STEP_ROW_DTYPE).reshape(-1))
+            e = torch.from_numpy(e.view(np.uint8).reshape(-1, STEP_ROW_DTYPE.itemsize).copy()).to(self.device)
+        if e.dtype != torch.uint8 or tuple(e.shape) != (B, STEP_ROW_DTYPE.itemsize):
+            raise ValueError(f'entries must be {B} step-table entries of {STEP_ROW_DTYPE.itemsize} bytes')
+        return e
+
+    @staticmethod
+    def _same_numel(x, **named):
+        for name, t in named.items():
+            if t is not None and (t.numel() != x.numel() or t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device):
+                raise ValueError(f'{name} must be a contiguous fp32 tensor of the size of x on its device')
+
+    def ddim_step_rows(self, x, eps_c, eps_u, entries, noise=None, temperature: float = 1.0, x_prev=None, pred_x0=None, want_x0: bool = True):
+        """One per-sample DDIM update (mkd_ddim_step_rows): sample b of the [B, ...] tensors uses ``entries[b]`` (a row of
+        ``step_table``); finished samples (active = 0) are not read and no byte of their ``x_prev`` / ``pred_x0`` rows is written
+        (pass the tensors in to see that).  Returns (x_prev, pred_x0)."""
+        x = _f32c(x, self.device); eps_c = _f32c(eps_c, self.device)
+        eps_u = None if eps_u is None else _f32c(eps_u, self.device)
+        noise = None if noise is None else _f32c(noise, self.device)
+        B = x.shape[0]
+        e = self._step_entries(entries, B)
+        if x_prev is None:
+            x_prev = torch.zeros_like(x)
+        if pred_x0 is None and want_x0:
+            pred_x0 = torch.zeros_like(x)
+        self._same_numel(x, eps_c=eps_c, eps_u=eps_u, noise=noise, x_prev=x_prev, pred_x0=pred_x0)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mkd_ddim_step_rows(C.c_void_p(x.data_ptr()), C.c_void_p(eps_c.data_ptr()), C.c_void_p(_ptr(eps_u)),
+                                                   C.c_void_p(e.data_ptr()), C.c_void_p(_ptr(noise)), float(temperature),
+                                                   C.c_void_p(x_prev.data_ptr()), C.c_void_p(_ptr(pred_x0)), B, x[0].numel(),
+                                                   C.c_void_p(_stream())), 'mkd_ddim_step_rows')
+        return x_prev, pred_x0
+
+    def dpmpp_step_rows(self, x, eps_c, eps_u, entries, m1, m2, x_prev=None, m0=None):
+        """One per-sample DPM-Solver++ update (mkd_dpmpp_step_rows), as ``ddim_step_rows``: m1 / m2 = the previous two
+        x0-predictions (read where the entry's c_1 / c_2 is non-zero).  Returns (x_prev, m0)."""
+        x = _f32c(x, self.device); eps_c = _f32c(eps_c, self.device)
+        eps_u = None if eps_u is None else _f32c(eps_u, self.device)
+        m1 = _f32c(m1, self.device); m2 = _f32c(m2, self.device)
+        B = x.shape[0]
+        e = self._step_entries(entries, B)
+        if x_prev is None:
+            x_prev = torch.zeros_like(x)
+        if m0 is None:
+            m0 = torch.zeros_like(x)
+        self._same_numel(x, eps_c=eps_c, eps_u=eps_u, m1=m1, m2=m2, x_prev=x_prev, m0=m0)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mkd_dpmpp_step_rows(C.c_void_p(x.data_ptr()), C.c_void_p(eps_c.data_ptr()), C.c_void_p(_ptr(eps_u)),
+                                                    C.c_void_p(e.data_ptr()), C.c_void_p(m1.data_ptr()), C.c_void_p(m2.data_ptr()),
+                                                    C.c_void_p(x_prev.data_ptr()), C.c_void_p(m0.data_ptr()), B, x[0].numel(),
+                                                    C.c_void_p(_stream())), 'mkd_dpmpp_step_rows')
+        return x_prev, m0
+
     def _check_x_T(self, x_T: torch.Tensor, cfg_scale: float) -> torch.Tensor:
         """x_T as the fp32 device tensor, checked against the prepared conditioning (batch B, or 2B = [uncond; cond] with guidance)."""
         x_T = _f32c(x_T, self.device)
@@ -876,9 +1048,13 @@ class MkdEngine:
     def eps_launches(self) -> int:
         return int(self.lib.mkd_eps_launches(self._ctx))
 
-    def step_launches(self, use_graph: bool = True, cfg: bool = False, rescale: bool = False) -> int:
+    def step_launches(self, use_graph: bool = True, cfg: bool = False, rescale: bool = False, per_sample: bool = False) -> int:
         """Kernel launches of one DDIM step inside ``sample`` (time embedding hoisted out of the loop), as that loop is run;
-        ``rescale``: a guided step with guidance rescale (its factor launch)."""
+        ``rescale``: a guided step with guidance rescale (its factor launch); ``per_sample``: a step of ``sample_rows``."""
+        if per_sample:
+            if rescale:
+                raise ValueError('guidance rescale is not combined with per-sample rows')
+            return int(self.lib.mkd_step_launches_ex(self._ctx, int(use_graph), _lib.STEP_PER_SAMPLE | int(bool(cfg))))
         return int(self.lib.mkd_step_launches_ex(self._ctx, int(use_graph), 2 if (cfg and rescale) else int(bool(cfg))))
 
     def device_bytes(self) -> int:

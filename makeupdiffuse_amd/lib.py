@@ -52,6 +52,22 @@ class SampleExtrasC(C.Structure):
                 ('guidance_rescale', C.c_float)]
 
 
+class SampleRowC(C.Structure):
+    """mkd_sample_row: one sample's request of a per-sample call (host tables)"""
+    _fields_ = [('n_steps', C.c_int32), ('cfg_scale', C.c_float), ('timesteps', C.POINTER(C.c_int64)),
+                ('alphas', C.POINTER(C.c_float)), ('alphas_prev', C.POINTER(C.c_float)), ('sqrt_one_minus_alphas', C.POINTER(C.c_float)),
+                ('sigmas', C.POINTER(C.c_float)), ('dpm', C.POINTER(C.c_float))]
+
+
+class StepRowC(C.Structure):
+    """mkd_step_row: one entry of the per-sample step table (64 bytes)"""
+    _fields_ = [('t', C.c_int64), ('coef', C.c_float * 4), ('sigma', C.c_float), ('dpm', C.c_float * 6), ('temb_row', C.c_int32),
+                ('active', C.c_int32), ('scale', C.c_float)]
+
+
+MAX_STEPS = 1024          # MKD_MAX_STEPS
+STEP_PER_SAMPLE = 4       # MKD_STEP_PER_SAMPLE
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -99,6 +115,10 @@ SIGNATURES = {
     'mkd_sample_dpmpp_ex': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), _I, _I, C.POINTER(SampleMaskC),
                                  C.POINTER(SampleExtrasC), _F, _P, _I, _P]),
     'mkd_sample_dpmpp': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), _I, _I, C.POINTER(SampleMaskC), _F, _P, _I, _P]),
+    'mkd_step_table': (_I, [C.POINTER(SampleRowC), _I, _I, C.POINTER(StepRowC), C.POINTER(_I), C.POINTER(_L), C.POINTER(_I)]),
+    'mkd_sample_rows': (_I, [_P, _P, _I, C.POINTER(SampleRowC), _I, _P, _F, C.POINTER(SampleMaskC), C.POINTER(SampleExtrasC), _P, _I, _P]),
+    'mkd_ddim_step_rows': (_I, [_P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _P]),
+    'mkd_dpmpp_step_rows': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     'mkd_latent_mask_from_labels': (_I, [_P, _I, _I, _I, C.c_uint64, _I, _F, _P, _P]),
     'mkd_paste_background': (_I, [_P, _P, _P, C.c_uint64, _I, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
     'mkd_region_mask_from_labels': (_I, [_P, _I, _I, _I, C.c_uint64, C.c_uint64, _I, _P, _P, _P, _P]),

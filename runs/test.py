@@ -104,7 +104,24 @@ def build_parser():
                     '(and the first executed step), the rule of the sampler\'s log_every_t')
     ap.add_argument('--guidance-rescale', type=float, default=0.0, metavar='PHI', help='guidance rescale of the guided pass, 0..1: per sample '
                     'and step the guided eps is scaled by PHI std(eps_cond) / std(eps_guided) + 1 - PHI (0: off)')
+    ap.add_argument('--steps-list', default=None, metavar='20,50,...', help='per-sample requests in one batch: also sample every batch '
+                    'with these step counts, cycled over its pairs, in ONE loop of the longest (samples_specs*.png)')
+    ap.add_argument('--guidance-list', default=None, metavar='1.5,9,...', help='... and these guidance scales, cycled over the pairs '
+                    '(alone: every pair at --ddim-steps)')
     return ap
+
+
+def parse_number_list(text, cast, what):
+    """'20,50' -> [20, 50]; SystemExit on anything else"""
+    if text is None:
+        return None
+    try:
+        vals = [cast(v) for v in text.split(',')]
+    except ValueError:
+        raise SystemExit(f'{what} takes comma-separated numbers, got {text!r}')
+    if not vals:
+        raise SystemExit(f'{what} is empty')
+    return vals
 
 
 def parse_region_map(text, cast=str):
@@ -164,6 +181,10 @@ def main():
         raise SystemExit('--log-every-t only applies with --denoise-rows')
     if not 0.0 <= args.guidance_rescale <= 1.0:
         raise SystemExit('--guidance-rescale must lie in 0..1')
+    steps_list = parse_number_list(args.steps_list, int, '--steps-list')
+    guidance_list = parse_number_list(args.guidance_list, float, '--guidance-list')
+    if steps_list and not all(1 <= s <= 1024 for s in steps_list):
+        raise SystemExit('--steps-list: every step count must lie in 1..1024')
     rank, world, local = mdist.init_from_env()
     model = create_model(args.config).cpu()
     if args.fix_background:
@@ -241,6 +262,17 @@ def main():
             if 'samples' in reg:
                 out['samples_regions'] = torch.clamp(reg['samples'].detach().cpu(), -1.0, 1.0)
                 model.save_local({'samples_regions': out['samples_regions']}, b0)
+        if steps_list or guidance_list:
+            from makeupdiffuse_amd.batching import SampleSpec
+            n = b1 - b0
+            specs = [SampleSpec(steps=(steps_list[i % len(steps_list)] if steps_list else model.ddim_steps),
+                                guidance=(guidance_list[i % len(guidance_list)] if guidance_list else 1.0), order=model.solver_order)
+                     for i in range(n)]
+            sp = model.transfer_specs(batch, specs, x_T=x_T)
+            out['samples_specs_latent'] = sp['samples_latent'].detach().cpu()
+            if 'samples' in sp:
+                out['samples_specs'] = torch.clamp(sp['samples'].detach().cpu(), -1.0, 1.0)
+                model.save_local({'samples_specs': out['samples_specs']}, b0)
         if photo_ds is not None:
             from PIL import Image
             items = collate_photos([photo_ds[i] for i in range(b0, b1)])
