@@ -563,7 +563,7 @@ int mkd_conv3x3_fold_bf16(const uint16_t* x, int ldx, const uint16_t* w_fold, co
 /* C[M,N] = act((A[M,K] . W[N,K]^T + bias[N] + rowbias[m / rows_per_batch][n]) * scale + R[M,N]).
  * conv3x3 != 0: A is NHWC [B,Hin,Win,Cin] (pixel stride lda), K = 9*Cin ordered (ky,kx,ci),
  * output pixel grid Hout x Wout with `stride`, input nearest-upsampled by 2^up first; pad 1.
- * out_f32 selects an fp32 C.  splitk 0 = auto. */
+ * out_f32 selects an fp32 C.  splitk 0 = auto.  act: 0 none, 1 SiLU, 2 GEGLU, 3 quick-GELU, 4 ReLU (applied after the residual). */
 int mkd_gemm_bf16(const uint16_t* A, int lda, const uint16_t* W, int ldw, const float* bias,
                   const float* rowbias, int ldrb, int rows_per_batch,
                   const uint16_t* R, int ldr, float scale, int act,
@@ -691,6 +691,76 @@ int mkd_conv3x3_direct(const void* x, int in_nchw_f32, const uint16_t* w, const 
                        int batch, int Hin, int Win, int Cin, int Cout, int stride, void* stream);
 /* fp32 [Cout,Cin,kh,kw] -> bf16 [Cout][kh][kw][Cin]. */
 int mkd_pack_conv_weight(const float* w, uint16_t* out, int Cout, int Cin, int kh, int kw, void* stream);
+
+/* ---- face parsing: label maps from images (csrc/parser.hip, csrc/kernels_parser.hip) --------------------------------------------
+ * UPSTREAM zllrunning/face-parsing.PyTorch model.py / resnet.py (BiSeNet, ResNet-18 context path) as vendored by PSGAN / EleGANt
+ * faceutils/mask; the reference runs it in diffdata/preprocessing.py:38,151-157.  A stand-alone handle like mkd_tfm_tail, not a plan
+ * of mkd_ctx.  Widths, blocks per layer, the context-path / fusion widths and the class count are configuration: every width a
+ * multiple of 8 (widths[0] <= 128: the stem's weights live in LDS), n_classes 2..32, ffm_channels a multiple of 8 (its inner width
+ * is ffm_channels / 4).  State-dict names are upstream's (cp.resnet.*, cp.arm16|arm32.*, cp.conv_head16|conv_head32|conv_avg.*,
+ * ffm.*, conv_out.*); the training-only heads conv_out16.* / conv_out32.* and *.num_batches_tracked are accepted and ignored.
+ *
+ * mkd_parser_create, _param_*: HOST only, no device call.  mkd_parser_load_weight takes fp32 HOST data; an unknown or wrongly shaped
+ * tensor is MKD_ERR_ARG; loading after a finalize asks for another finalize.  mkd_parser_finalize checks completeness
+ * (MKD_ERR_MISSING names the first missing tensor), folds every BatchNorm in fp32 (W' = W g / sqrt(var + eps), b' = beta - mean g /
+ * sqrt(var + eps)), rounds the GEMM weights to bf16 and uploads them; synchronous.
+ *
+ * mkd_parser_logits: images01 fp32 NCHW [batch,3,H,W] in [0,1] (device) -> logits_nchw fp32 [batch,n_classes,H/8,W/8] (device).
+ * mkd_parser_parse: the same, then the head below at parse size (H, W) -> labels uint8 [batch,out_h,out_w] (device); lut is a HOST
+ * table of n_classes bytes or NULL; logits_nchw may be NULL.  batch 1..64, H and W multiples of 32 in 64..1024, out_h / out_w >= 1,
+ * else MKD_ERR_ARG before anything is enqueued; MKD_ERR_STATE before finalize.  Calls only enqueue, except that a call whose
+ * (batch, H, W) needs more than the handle's workspace holds re-allocates it first (synchronising), as mkd_prepare does.
+ * mkd_parser_flops: 2 x the multiply-accumulates of one image; mkd_parser_launches: kernels the last call enqueued. */
+typedef struct mkd_parser mkd_parser;
+typedef struct mkd_parser_config {
+    int32_t n_classes;      /* 19 */
+    int32_t widths[4];      /* 64,128,256,512 */
+    int32_t blocks[4];      /* 2,2,2,2 */
+    int32_t cp_channels;    /* 128 */
+    int32_t ffm_channels;   /* 256 (FFM inner = /4) */
+    float   bn_eps;         /* 1e-5 */
+    float   mean[3], std[3];
+} mkd_parser_config;
+int  mkd_parser_create(const mkd_parser_config* cfg, mkd_parser** out);
+void mkd_parser_destroy(mkd_parser* p);
+int  mkd_parser_param_total(const mkd_parser* p);                          /* sorted by name */
+const char* mkd_parser_param_name(const mkd_parser* p, int i);
+int  mkd_parser_param_shape(const mkd_parser* p, int i, int64_t* shape4);   /* returns ndim <= 4 */
+int64_t mkd_parser_param_count(const mkd_parser* p);
+int  mkd_parser_load_weight(mkd_parser* p, const char* name, const float* data, int ndim, const int64_t* shape);
+int  mkd_parser_finalize(mkd_parser* p);
+int  mkd_parser_logits(mkd_parser* p, const float* images01, int batch, int H, int W, float* logits_nchw, void* stream);
+int  mkd_parser_parse(mkd_parser* p, const float* images01, int batch, int H, int W, int out_h, int out_w, const uint8_t* lut, uint8_t* labels,
+                      float* logits_nchw, void* stream);
+double mkd_parser_flops(const mkd_parser* p, int H, int W);
+int  mkd_parser_launches(const mkd_parser* p);
+/* The head alone, context-free, one launch, no H x W x classes tensor.  logits[b, c, y, x] is read at b s_batch + c s_class + y s_row +
+ * x s_col (element strides: NCHW and NHWC run the same code).  For output pixel (oy, ox) of the out_h x out_w map: the parse-resolution
+ * pixel is py = (oy P_h) / out_h, px = (ox P_w) / out_w (integer division: the reference's nearest resize, preprocessing.py:154-157);
+ * ry = (h8 > 1 && P_h > 1) ? float(h8 - 1) / float(P_h - 1) : 0, fy = float(py) ry, y0 = min((int)fy, h8 - 1), y1 = min(y0 + 1, h8 - 1),
+ * wy = fy - float(y0), likewise x (bilinear, align_corners = True); per class top = v00 + wx (v01 - v00), bot = v10 + wx (v11 - v10),
+ * val = top + wy (bot - top), every operation one correctly rounded fp32 operation, nothing contracted.  The label is the FIRST class
+ * with the largest val, passed through lut (HOST, n_classes bytes) when given.  This arithmetic is build-defined: torch weighs the four
+ * corners in another order, so labels can differ from torch's at near-ties only.  Inputs are finite.  n_classes 2..32, batch 1..65535,
+ * sizes 1..16384, else MKD_ERR_ARG before anything is enqueued. */
+int  mkd_parse_labels(const float* logits, int64_t s_class, int64_t s_row, int64_t s_col, int64_t s_batch, int batch, int n_classes,
+                      int h8, int w8, int P_h, int P_w, int out_h, int out_w, const uint8_t* lut, uint8_t* labels, void* stream);
+/* Single kernels of the network (unit tests), device pointers:
+ * mkd_parser_stem: images01 fp32 NCHW [batch,3,H,W] -> y bf16 NHWC [batch,H/4,W/4,C0] = maxpool3x3_s2_p1(relu(conv7x7_s2_p3((x - mean) /
+ *   std) + bias)); the zero padding applies to the normalised image.  w_packed bf16 [(ky*7+kx)*3+c][C0] and bias [C0] carry the folded
+ *   BatchNorm; mean3 / std3 are HOST; half_res is scratch for bf16 [batch,H/2,W/2,C0].  Two launches.  C0 % 8 == 0, <= 128; H, W % 32 == 0.
+ * mkd_channel_gate: x bf16 NHWC [batch,pixels,C] (pixel stride ldx) -> out fp32 [batch, n2 or n1]: the per-channel mean over the pixels
+ *   in fp32 in a FIXED order (same bits every run and for every batch size), then act1(W1 mean + b1) and, when w2 is given,
+ *   act2(W2 . + b2); w1 [n1][C], w2 [n2][n1] fp32, biases may be NULL; act 0 none, 1 ReLU, 2 1 / (1 + expf(-x)).  One workgroup per sample.
+ * mkd_gate_apply_bf16: y[b,Y,X,c] = bf16(float(x[b,Y>>u,X>>u,c]) a[b,c] + add), x [batch,h,w,C], y [batch,h<<u,w<<u,C], u 0 or 1;
+ *   mode 0: add = the fp32 vector add[b,c]; 1: add = the bf16 tensor add[b,Y>>u,X>>u,c] (pixel stride ldadd); 2: add = x itself.  One fp32
+ *   product, one fp32 sum, one bf16 rounding. */
+int  mkd_parser_stem(const float* images01, const uint16_t* w_packed, const float* bias, const float* mean3, const float* std3, uint16_t* half_res,
+                     uint16_t* y, int batch, int H, int W, int C0, void* stream);
+int  mkd_channel_gate(const uint16_t* x, int ldx, int batch, int pixels, int C, const float* w1, const float* b1, int n1, int act1, const float* w2,
+                      const float* b2, int n2, int act2, float* out, void* stream);
+int  mkd_gate_apply_bf16(const uint16_t* x, int ldx, const float* a, int mode, const void* add, int ldadd, uint16_t* y, int ldy, int batch, int h, int w,
+                         int C, int u, void* stream);
 
 #ifdef __cplusplus
 }

@@ -219,6 +219,10 @@ __device__ __forceinline__ f32x4 epilogue_value(const Epilogue& e, int m, int n,
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = quick_gelu_f(v[j]);
     }
+    if (e.act == 4) {          // ReLU, after the residual (BasicBlock: relu(shortcut + bn2(conv2)))
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
+    }
     return v;
 }
 
@@ -236,6 +240,10 @@ __device__ __forceinline__ f32x4 epilogue_value_pre(const Epilogue& e, int m, in
     if (e.act == 3) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = quick_gelu_f(v[j]);
+    }
+    if (e.act == 4) {          // ReLU, after the residual (BasicBlock: relu(shortcut + bn2(conv2)))
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
     }
     return v;
 }

@@ -435,7 +435,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                  fix_background: bool = False, background_classes: Sequence[int] = (0, 11, 12), background_threshold: float = 0.5,
                  seg_key: str = 'nonmakeup_seg', makeup_score: bool = False, ref_seg_key: str = 'makeup_seg', sampler: str = 'ddim',
                  solver_order: int = 2, paste_background: bool = False, paste_feather: int = 0, denoise_rows: bool = False,
-                 log_every_t: int = 100, guidance_rescale: float = 0.0, *args, **kwargs):
+                 log_every_t: int = 100, guidance_rescale: float = 0.0, face_parser=None, parser_lut=None, parse_size: int = 512,
+                 *args, **kwargs):
         if int(log_every_t) < 1:
             raise ValueError(f'log_every_t must be >= 1, got {log_every_t}')
         if not 0.0 <= float(guidance_rescale) <= 1.0:
@@ -446,7 +447,16 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             raise ValueError(f"sampler must be 'ddim' or 'dpmpp', got {sampler!r}")
         if solver_order not in (1, 2, 3):
             raise ValueError('solver_order must be 1, 2 or 3')
+        if int(parse_size) != parse_size or int(parse_size) % 32 or not 64 <= int(parse_size) <= 1024:
+            raise ValueError(f'parse_size must be a multiple of 32 in 64..1024, got {parse_size!r}')
         super().__init__(*args, **kwargs)
+        # label maps from the images themselves (face_parser.FaceParser, or anything with its parse()): a batch that lacks seg_key /
+        # ref_seg_key gets them from the source / reference image parsed at parse_size; label maps the caller brings always win.
+        # None: every path is as before (a missing label map is a KeyError)
+        from ..face_parser import LUT_SEG
+        self.face_parser = face_parser
+        self.parser_lut = tuple(LUT_SEG if parser_lut is None else parser_lut)
+        self.parse_size = int(parse_size)
         # log_results' sampler: 'dpmpp' runs both passes on DPM-Solver++ multistep (ddim_steps is then its number of evaluations)
         self.sampler, self.solver_order = sampler, int(solver_order)
         # makeup score of every decoded sample (makeup_score.transfer_score): off by default, then log_results is unchanged
@@ -489,12 +499,40 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                 f.write('%s %s %s\n' % (tp[0], tp[1], tp[2]))
 
     @torch.no_grad()
+    def parse_images(self, img01: torch.Tensor) -> torch.Tensor:
+        """label maps uint8 [B,H,W] of images [B,3,H,W] in [0,1] from the attached face parser: parsed at parse_size x parse_size (the
+        reference parses at 512 x 512, diffdata/preprocessing.py:151-157; images of another size are resized with antialiased bilinear
+        interpolation first), the label map brought to the images' size by the head's nearest rule, classes remapped by parser_lut"""
+        if self.face_parser is None:
+            raise ValueError('no face parser is attached (face_parser=...)')
+        H, W = int(img01.shape[-2]), int(img01.shape[-1])
+        S = self.parse_size
+        x = img01.float()
+        if (H, W) != (S, S):
+            x = torch.nn.functional.interpolate(x, size=(S, S), mode='bilinear', align_corners=False, antialias=True).clamp(0.0, 1.0)
+        return self.face_parser.parse(x, out_size=(H, W), lut=self.parser_lut)
+
+    def _fill_segs(self, batch: dict, ref: bool = False) -> None:
+        """with a face parser attached: batch[seg_key] (and batch[ref_seg_key] when ``ref``) from the batch's own images where the
+        batch does not bring them.  The maps are written INTO the caller's dict, on purpose: log_results, paste_source, background_latents,
+        makeup_hist and transfer_regions all pass through here, and a batch parsed once is not parsed again by the next of them (nor by
+        the caller's next call on the same batch).  Without a parser nothing happens and the callers' KeyErrors stand."""
+        if self.face_parser is None:
+            return
+        for seg_k, img_k in ((self.seg_key, self.src_img_key),) + (((self.ref_seg_key, self.ref_img_key),) if ref else ()):
+            if seg_k not in batch and img_k in batch:
+                batch[seg_k] = self.parse_images(self.get_origin_img_input(batch, img_k))
+
+    @torch.no_grad()
     def log_results(self, batch: dict, batch_idx: int, x_T: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """The sampler calls of reference log_results (:391-410): a plain 50-step pass and a CFG pass whose
         unconditional branch keeps the SAME hint (uc_cat = c_cat, :401).  Returns latents (and decoded images
-        once a first_stage_model is attached); the teacher / reconstruction rows are out of scope."""
+        once a first_stage_model is attached); the teacher / reconstruction rows are out of scope.  With a face parser attached, label
+        maps the batch lacks are added to ``batch`` (_fill_segs)."""
         use_ddim = self.ddim_steps is not None
         log: Dict[str, torch.Tensor] = {}
+        if self.fix_background or self.paste_background or self.makeup_score:
+            self._fill_segs(batch, ref=self.makeup_score)
         _, c = self.get_input(batch, self.first_stage_key)
         c_cat, c_txt = c['c_concat'][0], c['c_crossattn'][0]
         src, ref = torch.chunk(c_cat, 2, dim=1)
@@ -603,6 +641,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         """makeup_score: [B,4] = lip, skin, eye_left, eye_right histogram-matching distance of a decoded sample ([-1,1]) against the
         makeup reference ([0,1]) under batch[seg_key] / batch[ref_seg_key] (reference criterionHis, diffmk/makeups.py:232-245)."""
         from .. import makeup_score as ms
+        self._fill_segs(batch, ref=True)
         for k in (self.seg_key, self.ref_seg_key):
             if k not in batch:
                 raise KeyError(f"makeup_score: the batch has no label map under '{k}'")
@@ -613,6 +652,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         """what a pixel-space paste needs, checked before anything is sampled"""
         if not self.has_first_stage:
             raise ValueError(f'{what} pastes decoded images: it needs a first stage (first_stage_config)')
+        self._fill_segs(batch)
         if self.seg_key not in batch:
             raise KeyError(f"{what}: the batch has no label map under '{self.seg_key}'")
 
@@ -629,6 +669,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         """fix_background: x0 = get_z(src * 2 - 1) and the latent mask of batch[seg_key] over background_classes."""
         if not self.first_stage_encoder:
             raise ValueError('fix_background needs the first-stage encoder: construct with first_stage_encoder=True')
+        self._fill_segs(batch)
         if self.seg_key not in batch:
             raise KeyError(f"fix_background: the batch has no label map under '{self.seg_key}'")
         seg = batch[self.seg_key]
@@ -709,6 +750,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             raise ValueError("paste_outside keeps the source outside the chosen regions: it needs base='source'")
         if not 0 <= int(feather) <= rg.MAX_FEATHER:
             raise ValueError(f'feather must be 0..{rg.MAX_FEATHER} latent pixels, got {feather}')
+        self._fill_segs(batch)
         if self.seg_key not in batch:
             raise KeyError(f"transfer_regions: the batch has no label map under '{self.seg_key}'")
         if paste_outside or self.paste_background:
@@ -765,7 +807,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         return out
 
     @torch.no_grad()
-    def transfer_photos(self, src_photos, ref_photos, src_boxes, ref_boxes, src_segs=None, feather: int = 8,
+    def transfer_photos(self, src_photos, ref_photos, src_boxes=None, ref_boxes=None, src_segs=None, feather: int = 8,
                         x_T: Optional[torch.Tensor] = None, size: int = 256, batch: Optional[dict] = None,
                         guidance_rescale: Optional[float] = None) -> List[torch.Tensor]:
         """Makeup transfer on photographs at their own resolution: ``src_photos`` / ``ref_photos`` are uint8 [H,W,3] tensors of any
@@ -776,18 +818,29 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         maps at photo resolution) -- the latent is decoded and pasted into CLONES of the source photos with their fine detail kept
         (photo.paste_photos, ``feather`` photo pixels at the box sides).  ``batch`` carries the text fields get_input reads (txt_emb /
         txt_tokens / txt); without it the prompt is 'makeup transfer'.  ``guidance_rescale`` (default: the model's setting): the phi
-        of the guided pass.  Returns the uint8 [H,W,3] device tensors."""
+        of the guided pass.  With a face parser attached, ``src_segs`` may be None (the crop-resized source is parsed instead) and so
+        may ``src_boxes`` / ``ref_boxes`` (face_parser.find_boxes: single-face localisation on the squashed photo).  Returns the uint8
+        [H,W,3] device tensors."""
         from .. import photo
         phi = float(self.guidance_rescale if guidance_rescale is None else guidance_rescale)
         if not 0.0 <= phi <= 1.0:
             raise ValueError(f'guidance_rescale must lie in [0, 1], got {phi}')
+        if (src_boxes is None or ref_boxes is None) and self.face_parser is None:
+            raise ValueError('transfer_photos: src_boxes and ref_boxes are needed (only an attached face parser can find them)')
         if not self.has_first_stage:
             raise ValueError('transfer_photos pastes decoded images: it needs a first stage (first_stage_config)')
-        if (self.fix_background or self.paste_background) and src_segs is None:
+        need_seg = self.fix_background or self.paste_background
+        if need_seg and src_segs is None and self.face_parser is None:
             raise KeyError('transfer_photos: fix_background / paste_background need src_segs (label maps at photo resolution)')
         eng = self._require_engine()
         src_photos = [p.to(self.device) for p in src_photos]
         n = len(src_photos)
+        if src_boxes is None or ref_boxes is None:
+            from ..face_parser import find_boxes
+            if src_boxes is None:
+                src_boxes = find_boxes(self.face_parser, src_photos, parse_size=self.parse_size, lut=self.parser_lut)
+            if ref_boxes is None:
+                ref_boxes = find_boxes(self.face_parser, [p.to(self.device) for p in ref_photos], parse_size=self.parse_size, lut=self.parser_lut)
         cs = eng.crop_resize(src_photos, src_boxes, size, labels=src_segs)
         cr = eng.crop_resize(ref_photos, ref_boxes, size)
         if cr.img01.shape[0] != n:
@@ -796,7 +849,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         ctx = self.get_cond_txt_coding(batch if batch is not None else {self.cond_stage_key: ['makeup transfer'] * n})
         cond = {'c_concat': [torch.cat((src, ref), 1)], 'c_crossattn': [ctx]}
         extra = {} if x_T is None else {'x_T': x_T.to(self.device)}
-        seg_batch = {self.seg_key: cs.labels}
+        seg_batch = {self.seg_key: cs.labels if (src_segs is not None or not need_seg) else self.parse_images(src)}
         if self.fix_background:
             x0, mask = self.background_latents(seg_batch, src)
             extra.update(x0=x0, mask=mask)

@@ -36,6 +36,11 @@ class NetConfigC(C.Structure):
     ]
 
 
+class ParserConfigC(C.Structure):
+    _fields_ = [('n_classes', C.c_int32), ('widths', C.c_int32 * 4), ('blocks', C.c_int32 * 4), ('cp_channels', C.c_int32),
+                ('ffm_channels', C.c_int32), ('bn_eps', C.c_float), ('mean', C.c_float * 3), ('std', C.c_float * 3)]
+
+
 class PhotoDescC(C.Structure):
     _fields_ = [('pixels', C.c_void_p), ('pitch_bytes', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('x0', C.c_int32), ('y0', C.c_int32),
                 ('bw', C.c_int32), ('bh', C.c_int32), ('labels', C.c_void_p)]
@@ -184,6 +189,22 @@ SIGNATURES = {
     'mkd_geglu': (_I, [_P, _P, _I, _I, _P]),
     'mkd_conv3x3_direct': (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     'mkd_pack_conv_weight': (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    'mkd_parser_create': (_I, [C.POINTER(ParserConfigC), C.POINTER(_P)]),
+    'mkd_parser_destroy': (None, [_P]),
+    'mkd_parser_param_total': (_I, [_P]),
+    'mkd_parser_param_name': (C.c_char_p, [_P, _I]),
+    'mkd_parser_param_shape': (_I, [_P, _I, C.POINTER(_L)]),
+    'mkd_parser_param_count': (_L, [_P]),
+    'mkd_parser_load_weight': (_I, [_P, C.c_char_p, _P, _I, C.POINTER(_L)]),
+    'mkd_parser_finalize': (_I, [_P]),
+    'mkd_parser_logits': (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    'mkd_parser_parse': (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    'mkd_parser_flops': (C.c_double, [_P, _I, _I]),
+    'mkd_parser_launches': (_I, [_P]),
+    'mkd_parse_labels': (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    'mkd_parser_stem': (_I, [_P, _P, _P, C.POINTER(_F), C.POINTER(_F), _P, _P, _I, _I, _I, _I, _P]),
+    'mkd_channel_gate': (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P]),
+    'mkd_gate_apply_bf16': (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -98,6 +98,10 @@ def build_parser():
                     'the face box (<data-root>/boxes.txt, lines "name x0 y0 w h"; else the centred largest square) is crop-resized to --res on '
                     'the device, sampled once, and pasted back into the source photo with its fine detail kept; writes <out>/photos/<pair>.png')
     ap.add_argument('--photo-feather', type=int, default=8, help='fade the pasted face in over this many photo pixels at the box sides, 0..64')
+    ap.add_argument('--face-parser', default=None, metavar='PATH|random', help='attach the face-parsing network (upstream face-parsing.PyTorch '
+                    'state dict, e.g. 79999_iter.pth; "random": seeded random weights, for plumbing runs): label maps that --fix-background, '
+                    '--paste-background, --makeup-score, --region-refs and --photos need and <data-root>/scgan_segs does not give are parsed '
+                    'from the images, and --photos without a boxes file finds the face boxes itself')
     ap.add_argument('--denoise-rows', action='store_true', help='also write the denoise rows of both passes (denoise_row*.png: the decoded '
                     'x0-predictions, samples as rows, x_T and the logged steps as columns), traced inside the sampling loop')
     ap.add_argument('--log-every-t', type=int, default=100, metavar='N', help='with --denoise-rows: log every table entry i with i %% N == 0 '
@@ -159,8 +163,8 @@ def main():
     if region_refs:
         from makeupdiffuse_amd.regions import ordered
         ordered(region_refs)                              # unknown region names fail here, before the model is built
-        if not args.data_root or not os.path.isdir(os.path.join(args.data_root, 'scgan_segs')):
-            raise SystemExit('--region-refs needs --data-root with images/ and scgan_segs/ (the label maps pick the regions)')
+        if not args.data_root or not (args.face_parser or os.path.isdir(os.path.join(args.data_root, 'scgan_segs'))):
+            raise SystemExit('--region-refs needs --data-root with images/ and scgan_segs/ or --face-parser (the label maps pick the regions)')
     elif region_strength or args.region_feather != 1 or args.region_base != 'ref' or args.region_paste_outside:
         raise SystemExit('--region-strength / --region-feather / --region-base / --region-paste-outside only apply with --region-refs')
     if args.region_paste_outside and args.region_base != 'source':
@@ -205,6 +209,11 @@ def main():
     if not args.ckpt:
         model.engine.init_random(seed=0)
     model.only_mid_control = args.only_mid_control
+    if args.face_parser:
+        from makeupdiffuse_amd.face_parser import FaceParser
+        parser = FaceParser(device=model.device)
+        (parser.init_random(seed=0) if args.face_parser == 'random' else parser.load(args.face_parser)).finalize()
+        model.face_parser = parser
     if args.tokenizer and model.cond_stage_model is not None:
         from makeupdiffuse_amd.clip import load_tokenizer
         model.cond_stage_model.tokenizer = load_tokenizer(args.tokenizer)
@@ -241,8 +250,8 @@ def main():
                 e = txt_emb if txt_emb is not None else torch.randn(1, 77, model.net_config.context_dim, generator=g)
                 batch['txt_emb'] = e.expand(b1 - b0, -1, -1).contiguous()
         else:
-            batch = synthetic_batch(b0, b1, args.res, model.net_config.context_dim, with_seg=args.fix_background or args.paste_background,
-                                    with_makeup_seg=args.makeup_score)
+            batch = synthetic_batch(b0, b1, args.res, model.net_config.context_dim, with_seg=(args.fix_background or args.paste_background) and not args.face_parser,
+                                    with_makeup_seg=args.makeup_score and not args.face_parser)
             if use_clip:
                 del batch['txt_emb']          # 'txt' -> tokenizer -> mkd_clip_encode
         x_T = None
@@ -277,7 +286,8 @@ def main():
             from PIL import Image
             items = collate_photos([photo_ds[i] for i in range(b0, b1)])
             text = {k: batch[k] for k in ('txt_emb', 'txt') if k in batch}
-            photos = model.transfer_photos(items['src_photo'], items['ref_photo'], items['src_box'], items['ref_box'],
+            find = bool(args.face_parser) and not photo_ds.boxes          # no boxes file: the parser finds the faces
+            photos = model.transfer_photos(items['src_photo'], items['ref_photo'], None if find else items['src_box'], None if find else items['ref_box'],
                                            src_segs=items.get('src_seg'), feather=args.photo_feather, x_T=x_T, size=args.res, batch=text)
             os.makedirs(os.path.join(args.out, 'photos'), exist_ok=True)
             for name, img in zip(items['img_name'], photos):
