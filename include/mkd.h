@@ -396,6 +396,25 @@ int mkd_paste_background(const float* image, const float* src, const uint8_t* la
  * then empty, count 0).  No context, no host sync, no allocation; 2 launches (3 with a box).  batch <= 65535, H * W <= 2^24, else MKD_ERR_ARG. */
 int mkd_region_mask_from_labels(const uint8_t* labels, int batch, int H, int W, uint64_t classes, uint64_t box_classes, int margin,
                                 uint8_t* mask_out, int32_t* count_out, int32_t* box_out, void* stream);
+/* ---- connected components of a label map: every face of a group photo (BUILD-DEFINED; the reference crops ONE detected face) ---- */
+/* One component: id = the smallest linear index y W + x of its pixels, area = its pixel count, (r0, r1, c0, c1) = its inclusive
+ * bounding box (row min, row max, col min, col max).  24 bytes. */
+typedef struct mkd_component { int32_t id, area, r0, r1, c0, c1; } mkd_component;
+/* Bytes of device scratch mkd_label_components needs (0 for bad arguments: the limits below).  The scratch must be 256-byte aligned;
+ * its contents before the call do not matter (the call initialises what it reads) and it may be reused by the next call on the
+ * same stream. */
+size_t mkd_label_components_scratch_bytes(int batch, int H, int W);
+/* labels [batch, H, W] uint8 device.  A pixel is IN when its label l < 64 has bit l set in `classes` (the rule of
+ * mkd_region_mask_from_labels).  Components are the 8-connected sets of in-pixels of one image (4-connectivity is not offered).
+ * count [batch] int32 = the number of components of image b with area >= min_area (NOT capped).  table [batch][max_out] =
+ * those components ordered by area descending, ties by id ascending, rows 0 .. min(count[b], max_out) - 1; the remaining rows are
+ * {-1, 0, INT32_MAX, -1, INT32_MAX, -1} (the empty box of mkd_region_mask_from_labels).  ids_out [batch, H, W] int32 or NULL: the
+ * component id at every in-pixel, -1 elsewhere, for ALL components (also those below min_area).  Integer arithmetic only: the outputs
+ * are exact and the same bytes on every run.  No context, no host sync, no allocation; 4 launches whatever the data, and no workgroup
+ * waits for another.  MKD_ERR_ARG before anything is enqueued unless 1 <= batch <= 65535, H, W >= 1, H * W <= 2^24,
+ * 1 <= max_out <= 64, min_area >= 1, labels / table / count / scratch non-null and the scratch 256-byte aligned. */
+int mkd_label_components(const uint8_t* labels, int batch, int H, int W, uint64_t classes, int min_area, int max_out,
+                         mkd_component* table, int32_t* count, int32_t* ids_out, void* scratch, void* stream);
 /* Bytes of device scratch mkd_hist_match needs for n terms (0 for n <= 0).  The scratch must be 256-byte aligned; its contents
  * before the call do not matter and it may be reused by the next call on the same stream. */
 size_t mkd_hist_match_scratch_bytes(int n);

@@ -806,43 +806,14 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                                                                            feather=self.paste_feather, return_alpha=True)
         return out
 
-    @torch.no_grad()
-    def transfer_photos(self, src_photos, ref_photos, src_boxes=None, ref_boxes=None, src_segs=None, feather: int = 8,
-                        x_T: Optional[torch.Tensor] = None, size: int = 256, batch: Optional[dict] = None,
-                        guidance_rescale: Optional[float] = None) -> List[torch.Tensor]:
-        """Makeup transfer on photographs at their own resolution: ``src_photos`` / ``ref_photos`` are uint8 [H,W,3] tensors of any
-        size (lists; the photos of a call may differ in size) with a face box (x0, y0, w, h) each.  Both boxes are crop-resized to
-        ``size`` on the device (photo.crop_resize: Pillow's antialiased bilinear bytes / 255, what PairFolderDataset gives for that
-        crop), ONE sampling pass runs as in transfer_regions -- the ``sampler`` attribute's solver for ddim_steps from x_T, guided when
-        unconditional_guidance_scale > 1, with the fix_background / paste_background settings on the crop-resized ``src_segs`` (label
-        maps at photo resolution) -- the latent is decoded and pasted into CLONES of the source photos with their fine detail kept
-        (photo.paste_photos, ``feather`` photo pixels at the box sides).  ``batch`` carries the text fields get_input reads (txt_emb /
-        txt_tokens / txt); without it the prompt is 'makeup transfer'.  ``guidance_rescale`` (default: the model's setting): the phi
-        of the guided pass.  With a face parser attached, ``src_segs`` may be None (the crop-resized source is parsed instead) and so
-        may ``src_boxes`` / ``ref_boxes`` (face_parser.find_boxes: single-face localisation on the squashed photo).  Returns the uint8
-        [H,W,3] device tensors."""
-        from .. import photo
-        phi = float(self.guidance_rescale if guidance_rescale is None else guidance_rescale)
-        if not 0.0 <= phi <= 1.0:
-            raise ValueError(f'guidance_rescale must lie in [0, 1], got {phi}')
-        if (src_boxes is None or ref_boxes is None) and self.face_parser is None:
-            raise ValueError('transfer_photos: src_boxes and ref_boxes are needed (only an attached face parser can find them)')
-        if not self.has_first_stage:
-            raise ValueError('transfer_photos pastes decoded images: it needs a first stage (first_stage_config)')
-        need_seg = self.fix_background or self.paste_background
-        if need_seg and src_segs is None and self.face_parser is None:
-            raise KeyError('transfer_photos: fix_background / paste_background need src_segs (label maps at photo resolution)')
+    def _photo_pass(self, src_photos, ref_photos, src_boxes, ref_boxes, src_segs, x_T, size, batch, phi):
+        """the single pass of transfer_photos for one batch of (photo, box) pairs on the device: crop-resize both, sample, decode,
+        paste_source -> (the decoded images [n,3,size,size], the source crops img01 the paste needs)"""
         eng = self._require_engine()
-        src_photos = [p.to(self.device) for p in src_photos]
-        n = len(src_photos)
-        if src_boxes is None or ref_boxes is None:
-            from ..face_parser import find_boxes
-            if src_boxes is None:
-                src_boxes = find_boxes(self.face_parser, src_photos, parse_size=self.parse_size, lut=self.parser_lut)
-            if ref_boxes is None:
-                ref_boxes = find_boxes(self.face_parser, [p.to(self.device) for p in ref_photos], parse_size=self.parse_size, lut=self.parser_lut)
+        need_seg = self.fix_background or self.paste_background
         cs = eng.crop_resize(src_photos, src_boxes, size, labels=src_segs)
         cr = eng.crop_resize(ref_photos, ref_boxes, size)
+        n = len(src_photos)
         if cr.img01.shape[0] != n:
             raise ValueError(f'{n} source photos but {cr.img01.shape[0]} reference photos')
         src, ref = cs.img01, cr.img01
@@ -863,6 +834,141 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         img = self.decode_first_stage(lat)
         if self.paste_background:
             img, _ = self.paste_source(seg_batch, img, src * 2.0 - 1.0)
+        return img, src
+
+    def _transfer_faces(self, src_photos, ref_photos, src_boxes, ref_boxes, src_segs, feather, x_T, size, batch, phi, max_faces,
+                        face_batch, return_faces):
+        """transfer_photos(max_faces=K): see there"""
+        K, fb = int(max_faces), int(face_batch)
+        if K != max_faces or not 1 <= K <= 64:
+            raise ValueError(f'max_faces must be an integer 1..64, got {max_faces!r}')
+        if fb != face_batch or fb < 1:
+            raise ValueError(f'face_batch must be an integer >= 1, got {face_batch!r}')
+        src_photos, ref_photos = list(src_photos), list(ref_photos)
+        n = len(src_photos)
+        if len(ref_photos) != n:
+            raise ValueError(f'{n} source photos but {len(ref_photos)} reference photos')
+        if (src_boxes is None or ref_boxes is None) and self.face_parser is None:
+            raise ValueError('transfer_photos: src_boxes and ref_boxes are needed (only an attached face parser can find the faces)')
+        is_box = lambda b: isinstance(b, (tuple, list)) and len(b) == 4 and not any(isinstance(v, (tuple, list)) for v in b)
+        if src_boxes is not None:
+            src_boxes = list(src_boxes)
+            if len(src_boxes) != n:
+                raise ValueError(f'max_faces: src_boxes must hold one LIST of boxes per source photo ({n}), got {len(src_boxes)} entries')
+            for i, bl in enumerate(src_boxes):
+                if not isinstance(bl, (tuple, list)) or not all(is_box(b) for b in bl):
+                    raise ValueError(f'max_faces: src_boxes[{i}] must be a list of boxes (x0, y0, w, h), got {bl!r}')
+                if len(bl) > K:
+                    raise ValueError(f'max_faces: src_boxes[{i}] holds {len(bl)} boxes, more than max_faces = {K}')
+        if ref_boxes is not None:
+            ref_boxes = list(ref_boxes)
+            if len(ref_boxes) != n or not all(is_box(b) for b in ref_boxes):
+                raise ValueError(f'max_faces: ref_boxes must hold one box (x0, y0, w, h) per reference photo ({n}), got {ref_boxes!r}')
+        known = None if src_boxes is None else sum(len(bl) for bl in src_boxes)
+        if x_T is not None and known is not None and int(x_T.shape[0]) != known:
+            raise ValueError(f'x_T must hold one start latent per face, [{known},4,h,w] in photo-major order, got {tuple(x_T.shape)}')
+        if src_segs is not None and len(src_segs) != n:
+            raise ValueError(f'{n} source photos but {len(src_segs)} label maps')
+        if not self.has_first_stage:
+            raise ValueError('transfer_photos pastes decoded images: it needs a first stage (first_stage_config)')
+        if (self.fix_background or self.paste_background) and src_segs is None and self.face_parser is None:
+            raise KeyError('transfer_photos: fix_background / paste_background need src_segs (label maps at photo resolution)')
+        from ..face_parser import find_faces
+        eng = self._require_engine()
+        src_photos = [p.to(self.device) for p in src_photos]
+        ref_photos = [p.to(self.device) for p in ref_photos]
+        if src_boxes is None:
+            src_boxes = find_faces(self.face_parser, src_photos, max_faces=K, parse_size=self.parse_size, lut=self.parser_lut)
+        faces = [[tuple(int(v) for v in b) for b in bl] for bl in src_boxes]
+        if ref_boxes is None:
+            found = find_faces(self.face_parser, ref_photos, max_faces=1, parse_size=self.parse_size, lut=self.parser_lut)
+            for i, f in enumerate(found):
+                if not f:
+                    raise ValueError(f'transfer_photos: reference photo {i} shows no face')
+            ref_boxes = [f[0] for f in found]
+        items = [(i, k) for i, bl in enumerate(faces) for k in range(len(bl))]          # photo-major, rank-minor
+        N = len(items)
+        if x_T is not None and int(x_T.shape[0]) != N:
+            raise ValueError(f'x_T must hold one start latent per face, [{N},4,h,w] in photo-major order, got {tuple(x_T.shape)}')
+        out = [p.clone(memory_format=torch.contiguous_format) for p in src_photos]
+        imgs, srcs = [], []
+        for c0 in range(0, N, fb):
+            chunk = items[c0:c0 + fb]
+            pick = [i for i, _ in chunk]
+            text = None
+            if batch is not None:          # the text fields get_input reads, one row per face
+                idx = torch.tensor(pick)
+                text = {k: (v[idx.to(v.device)] if isinstance(v, torch.Tensor) else [v[i] for i in pick])
+                        for k, v in batch.items() if k in ('txt_emb', 'txt_tokens', self.cond_stage_key)}
+            img, src = self._photo_pass([src_photos[i] for i in pick], [ref_photos[i] for i in pick], [faces[i][k] for i, k in chunk],
+                                        [ref_boxes[i] for i in pick], None if src_segs is None else [src_segs[i] for i in pick],
+                                        None if x_T is None else x_T[c0:c0 + len(chunk)], size, text, phi)
+            imgs.append(img)
+            srcs.append(src)
+        if N:
+            img, src = torch.cat(imgs), torch.cat(srcs)
+            for rank in range(max(len(bl) for bl in faces)):
+                sel = [j for j, (_, k) in enumerate(items) if k == rank]
+                at = torch.tensor(sel, device=img.device)
+                eng.paste_photos([out[items[j][0]] for j in sel], [faces[items[j][0]][rank] for j in sel], img[at], src[at], feather)
+        return (out, faces) if return_faces else out
+
+    @torch.no_grad()
+    def transfer_photos(self, src_photos, ref_photos, src_boxes=None, ref_boxes=None, src_segs=None, feather: int = 8,
+                        x_T: Optional[torch.Tensor] = None, size: int = 256, batch: Optional[dict] = None,
+                        guidance_rescale: Optional[float] = None, max_faces: Optional[int] = None, face_batch: int = 8,
+                        return_faces: bool = False):
+        """Makeup transfer on photographs at their own resolution: ``src_photos`` / ``ref_photos`` are uint8 [H,W,3] tensors of any
+        size (lists; the photos of a call may differ in size) with a face box (x0, y0, w, h) each.  Both boxes are crop-resized to
+        ``size`` on the device (photo.crop_resize: Pillow's antialiased bilinear bytes / 255, what PairFolderDataset gives for that
+        crop), ONE sampling pass runs as in transfer_regions -- the ``sampler`` attribute's solver for ddim_steps from x_T, guided when
+        unconditional_guidance_scale > 1, with the fix_background / paste_background settings on the crop-resized ``src_segs`` (label
+        maps at photo resolution) -- the latent is decoded and pasted into CLONES of the source photos with their fine detail kept
+        (photo.paste_photos, ``feather`` photo pixels at the box sides).  ``batch`` carries the text fields get_input reads (txt_emb /
+        txt_tokens / txt); without it the prompt is 'makeup transfer'.  ``guidance_rescale`` (default: the model's setting): the phi
+        of the guided pass.  With a face parser attached, ``src_segs`` may be None (the crop-resized source is parsed instead) and so
+        may ``src_boxes`` / ``ref_boxes`` (face_parser.find_boxes: single-face localisation on the squashed photo).  Returns the uint8
+        [H,W,3] device tensors.
+
+        GROUP PHOTOS, ``max_faces`` = K >= 1 (None: everything above, unchanged; this rule is this build's).  Every source photo is
+        fanned out into up to K crops, one per face: ``src_boxes`` None takes face_parser.find_faces(max_faces=K) (connected components
+        of the face classes, largest first); else entry i of ``src_boxes`` is a LIST of 0..K boxes of photo i and no parser is needed.
+        ``ref_boxes`` None takes the LARGEST face of every reference (find_faces(max_faces=1); a reference without one raises
+        ValueError naming its index); else one box per reference.  Every face of source photo i uses reference i, label map
+        src_segs[i] and the text of entry i of ``batch``.  The work items are the N = sum of faces crops in photo-major, rank-minor
+        order; ``x_T`` is [N,4,h,w] in that order.  Sampling, decode and paste_source run in chunks of at most ``face_batch`` items, the
+        ragged last chunk as a call of its own, each chunk exactly the single pass above for a batch of that size.  The results are
+        pasted into ONE clone per source photo rank by rank (one paste_photos call for rank 0 of every photo that has one, then rank 1,
+        ...), so a photo never appears twice in a launch and stream order fixes what overlapping boxes give: the larger face is pasted
+        first, and a smaller face that overlaps it adds ITS difference (against its crop of the ORIGINAL photo) on top of pixels the
+        first paste may already have changed.  A crop may show part of a neighbouring face, which the model is free to change: the
+        paste is not restricted to the face's own component.  A photo without a face comes back as an unchanged clone; N = 0 samples
+        nothing.  ``return_faces``: (photos, the list of box lists) instead of the photos."""
+        from .. import photo
+        phi = float(self.guidance_rescale if guidance_rescale is None else guidance_rescale)
+        if not 0.0 <= phi <= 1.0:
+            raise ValueError(f'guidance_rescale must lie in [0, 1], got {phi}')
+        if max_faces is not None:
+            return self._transfer_faces(src_photos, ref_photos, src_boxes, ref_boxes, src_segs, feather, x_T, size, batch, phi,
+                                        max_faces, face_batch, return_faces)
+        if return_faces or face_batch != 8:
+            raise ValueError('return_faces / face_batch only apply with max_faces')
+        if (src_boxes is None or ref_boxes is None) and self.face_parser is None:
+            raise ValueError('transfer_photos: src_boxes and ref_boxes are needed (only an attached face parser can find them)')
+        if not self.has_first_stage:
+            raise ValueError('transfer_photos pastes decoded images: it needs a first stage (first_stage_config)')
+        need_seg = self.fix_background or self.paste_background
+        if need_seg and src_segs is None and self.face_parser is None:
+            raise KeyError('transfer_photos: fix_background / paste_background need src_segs (label maps at photo resolution)')
+        eng = self._require_engine()
+        src_photos = [p.to(self.device) for p in src_photos]
+        if src_boxes is None or ref_boxes is None:
+            from ..face_parser import find_boxes
+            if src_boxes is None:
+                src_boxes = find_boxes(self.face_parser, src_photos, parse_size=self.parse_size, lut=self.parser_lut)
+            if ref_boxes is None:
+                ref_boxes = find_boxes(self.face_parser, [p.to(self.device) for p in ref_photos], parse_size=self.parse_size, lut=self.parser_lut)
+        img, src = self._photo_pass(src_photos, ref_photos, src_boxes, ref_boxes, src_segs, x_T, size, batch, phi)
         out = [p.clone(memory_format=torch.contiguous_format) for p in src_photos]
         eng.paste_photos(out, src_boxes, img, src, feather)
         return out

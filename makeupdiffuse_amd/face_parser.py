@@ -195,6 +195,10 @@ class FaceParser:
     def find_boxes(self, photos, grow: float = 1.0, parse_size: int = 512, lut=LUT_SEG) -> List[Tuple[int, int, int, int]]:
         return find_boxes(self, photos, grow=grow, parse_size=parse_size, lut=lut)
 
+    def find_faces(self, photos, max_faces: int = 8, min_area: Optional[int] = None, grow: float = 1.0, parse_size: int = 512,
+                   lut=LUT_SEG) -> List[List[Tuple[int, int, int, int]]]:
+        return find_faces(self, photos, max_faces=max_faces, min_area=min_area, grow=grow, parse_size=parse_size, lut=lut)
+
     def flops(self, H: int = 512, W: int = 512) -> float:
         return float(self.lib.mkd_parser_flops(self._h, int(H), int(W)))
 
@@ -249,4 +253,48 @@ def find_boxes(parser, photos, grow: float = 1.0, parse_size: int = 512, lut=LUT
                 raise ValueError(f'find_boxes: photo {b0 + i} has no pixel of the face classes {tuple(classes)}')
             scaled = (r0 * H // S, min(H, -(-(r1 + 1) * H // S)) - 1, c0 * W // S, min(W, -(-(c1 + 1) * W // S)) - 1)
             out.append(photo.grow_square_box(scaled, H, W, grow))
+    return out
+
+
+def find_faces(parser, photos, max_faces: int = 8, min_area: Optional[int] = None, grow: float = 1.0, parse_size: int = 512, lut=LUT_SEG,
+               classes: Sequence[int] = FACE_CLASSES, resize=None, components_of=None) -> List[List[Tuple[int, int, int, int]]]:
+    """EVERY face of whole photos (uint8 [H,W,3] device tensors): one list of boxes (x0, y0, side, side) per photo, largest face first.
+    Every photo is squashed to parse_size x parse_size and parsed exactly as find_boxes does; a face is an 8-connected component of the
+    face classes with at least ``min_area`` pixels of the squashed map (components.label_components; default (parse_size // 32)^2,
+    which drops parser speckle); the ``max_faces`` largest are kept in the table's order (area descending, ties by the smallest
+    linear index).  Each component's box is scaled back to photo pixels with find_boxes' expression (outwards, BEFORE it is grown:
+    the squash changes the aspect ratio) and grown, squared and clipped by photo.grow_square_box.  A photo without such a component
+    gives [] and does not raise.  One device-to-host copy (table and count together) per chunk of MAX_BATCH photos; no component
+    data is read back per pixel.  The crop of one face may show part of a neighbouring face: crops are not restricted to their
+    component.  This rule is this build's.  ``resize`` and ``components_of`` (the signature of components.label_components) replace
+    the two device calls (tests of the box arithmetic without a device)."""
+    from . import components, photo
+    K = int(max_faces)
+    if K != max_faces or not 1 <= K <= components.MAX_OUT:
+        raise ValueError(f'max_faces must be an integer 1..{components.MAX_OUT}, got {max_faces!r}')
+    if isinstance(photos, torch.Tensor):
+        photos = [photos] if photos.dim() == 3 else list(photos.unbind(0))
+    photos = list(photos)
+    resize = resize or photo.crop_resize
+    components_of = components_of or components.label_components
+    S = int(parse_size)
+    area = (S // 32) ** 2 if min_area is None else int(min_area)
+    if area < 1:
+        raise ValueError(f'min_area must be >= 1, got {min_area!r} (parse_size {parse_size})')
+    out: List[List[Tuple[int, int, int, int]]] = []
+    for b0 in range(0, len(photos), MAX_BATCH):
+        chunk = photos[b0:b0 + MAX_BATCH]
+        whole = [(0, 0, int(p.shape[1]), int(p.shape[0])) for p in chunk]
+        labels = parser.parse(resize(chunk, whole, S).img01, out_size=None, lut=lut)
+        table, count = components_of(labels, classes, min_area=area, max_out=K)[:2]
+        table, count = torch.as_tensor(table), torch.as_tensor(count)
+        both = torch.cat((table.reshape(len(chunk), -1), count.reshape(len(chunk), 1).to(table.dtype)), 1).cpu().tolist()
+        for p, row in zip(chunk, both):
+            H, W = int(p.shape[0]), int(p.shape[1])
+            faces = []
+            for k in range(min(int(row[-1]), K)):
+                r0, r1, c0, c1 = row[6 * k + 2:6 * k + 6]
+                scaled = (r0 * H // S, min(H, -(-(r1 + 1) * H // S)) - 1, c0 * W // S, min(W, -(-(c1 + 1) * W // S)) - 1)
+                faces.append(photo.grow_square_box(scaled, H, W, grow))
+            out.append(faces)
     return out

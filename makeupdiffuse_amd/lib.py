@@ -127,6 +127,8 @@ SIGNATURES = {
     'mkd_latent_mask_from_labels': (_I, [_P, _I, _I, _I, C.c_uint64, _I, _F, _P, _P]),
     'mkd_paste_background': (_I, [_P, _P, _P, C.c_uint64, _I, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
     'mkd_region_mask_from_labels': (_I, [_P, _I, _I, _I, C.c_uint64, C.c_uint64, _I, _P, _P, _P, _P]),
+    'mkd_label_components_scratch_bytes': (C.c_size_t, [_I, _I, _I]),
+    'mkd_label_components': (_I, [_P, _I, _I, _I, C.c_uint64, _I, _I, _P, _P, _P, _P, _P]),
     'mkd_hist_match_scratch_bytes': (C.c_size_t, [_I]),
     'mkd_hist_match_launches': (_I, [_I, _I]),
     'mkd_hist_match': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),

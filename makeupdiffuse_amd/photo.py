@@ -225,9 +225,10 @@ def centred_square(H: int, W: int) -> Tuple[int, int, int, int]:
     return (W - side) // 2, (H - side) // 2, side, side
 
 
-def read_boxes(path: str) -> Dict[str, Tuple[int, int, int, int]]:
-    """Lines of '<image name> x0 y0 w h' -> {name: (x0, y0, w, h)}; blank lines and lines starting with # are skipped."""
-    out: Dict[str, Tuple[int, int, int, int]] = {}
+def read_boxes_multi(path: str) -> Dict[str, List[Tuple[int, int, int, int]]]:
+    """Lines of '<image name> x0 y0 w h' -> {name: [(x0, y0, w, h), ...]}: a name may repeat, one line per face, kept in file order;
+    blank lines and lines starting with # are skipped."""
+    out: Dict[str, List[Tuple[int, int, int, int]]] = {}
     with open(path, 'r') as f:
         for ln, line in enumerate(f, 1):
             parts = line.split()
@@ -236,10 +237,16 @@ def read_boxes(path: str) -> Dict[str, Tuple[int, int, int, int]]:
             if len(parts) != 5:
                 raise ValueError(f'{path}:{ln}: expected "name x0 y0 w h", got {line.strip()!r}')
             try:
-                out[parts[0]] = tuple(int(v) for v in parts[1:])
+                out.setdefault(parts[0], []).append(tuple(int(v) for v in parts[1:]))
             except ValueError:
                 raise ValueError(f'{path}:{ln}: the box of {parts[0]} must hold four integers') from None
     return out
+
+
+def read_boxes(path: str) -> Dict[str, Tuple[int, int, int, int]]:
+    """Lines of '<image name> x0 y0 w h' -> {name: (x0, y0, w, h)}; blank lines and lines starting with # are skipped.  Of a name
+    that repeats (a multi-face file, read_boxes_multi) the FIRST line counts."""
+    return {name: boxes[0] for name, boxes in read_boxes_multi(path).items()}
 
 
 class PhotoPairDataset:
@@ -252,7 +259,8 @@ class PhotoPairDataset:
         self.root = root
         self.pairs = read_pairs(pairs_file if os.path.isabs(pairs_file) else os.path.join(root, pairs_file))
         bp = boxes_file if os.path.isabs(boxes_file) else os.path.join(root, boxes_file)
-        self.boxes = read_boxes(bp) if os.path.exists(bp) else {}
+        self.faces = read_boxes_multi(bp) if os.path.exists(bp) else {}          # every line of a name (multi-face files)
+        self.boxes = {name: boxes[0] for name, boxes in self.faces.items()}
         self.prompt = prompt
         self.has_segs = os.path.isdir(os.path.join(root, 'scgan_segs'))
 

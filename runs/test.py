@@ -97,6 +97,9 @@ def build_parser():
     ap.add_argument('--photos', action='store_true', help='after the usual passes, also transfer every pair at the photos\' NATIVE resolution: '
                     'the face box (<data-root>/boxes.txt, lines "name x0 y0 w h"; else the centred largest square) is crop-resized to --res on '
                     'the device, sampled once, and pasted back into the source photo with its fine detail kept; writes <out>/photos/<pair>.png')
+    ap.add_argument('--max-faces', type=int, default=None, metavar='K', help='with --photos: group photos -- make up to K faces of every source '
+                    'photo (largest first), each against the largest face of its reference; the faces come from --face-parser (connected '
+                    'components of the parsed face classes) or from a boxes file that repeats an image name, one line per face')
     ap.add_argument('--photo-feather', type=int, default=8, help='fade the pasted face in over this many photo pixels at the box sides, 0..64')
     ap.add_argument('--face-parser', default=None, metavar='PATH|random', help='attach the face-parsing network (upstream face-parsing.PyTorch '
                     'state dict, e.g. 79999_iter.pth; "random": seeded random weights, for plumbing runs): label maps that --fix-background, '
@@ -175,6 +178,13 @@ def main():
         raise SystemExit('--paste-feather only applies with --paste-background or --region-paste-outside')
     if args.photos and not args.data_root:
         raise SystemExit('--photos needs --data-root with images/ and a pairs file (the photos are read at their own resolution)')
+    if args.max_faces is not None:
+        if not args.photos:
+            raise SystemExit('--max-faces only applies with --photos')
+        if not 1 <= args.max_faces <= 64:
+            raise SystemExit('--max-faces must be 1..64')
+        if not args.face_parser and not os.path.exists(os.path.join(args.data_root, 'boxes.txt')):
+            raise SystemExit('--max-faces needs --face-parser or <data-root>/boxes.txt (one line per face)')
     if not 0 <= args.photo_feather <= 64:
         raise SystemExit('--photo-feather must be 0..64 photo pixels')
     if args.photo_feather != 8 and not args.photos:
@@ -287,8 +297,29 @@ def main():
             items = collate_photos([photo_ds[i] for i in range(b0, b1)])
             text = {k: batch[k] for k in ('txt_emb', 'txt') if k in batch}
             find = bool(args.face_parser) and not photo_ds.boxes          # no boxes file: the parser finds the faces
-            photos = model.transfer_photos(items['src_photo'], items['ref_photo'], None if find else items['src_box'], None if find else items['ref_box'],
-                                           src_segs=items.get('src_seg'), feather=args.photo_feather, x_T=x_T, size=args.res, batch=text)
+            if args.max_faces is None:
+                photos = model.transfer_photos(items['src_photo'], items['ref_photo'], None if find else items['src_box'], None if find else items['ref_box'],
+                                               src_segs=items.get('src_seg'), feather=args.photo_feather, x_T=x_T, size=args.res, batch=text)
+            else:
+                K = args.max_faces
+                ref_boxes = items['ref_box']
+                if find:          # (a reference in which the parser finds no face keeps its centred largest square)
+                    look = lambda ps, k: model.face_parser.find_faces([p.cuda(local) for p in ps], max_faces=k, parse_size=model.parse_size,
+                                                                      lut=model.parser_lut)
+                    faces = look(items['src_photo'], K)
+                    ref_boxes = [f[0] if f else b for f, b in zip(look(items['ref_photo'], 1), ref_boxes)]
+                else:          # the lines of the source's name, else the one box the single-face run uses
+                    faces = [photo_ds.faces.get(photo_ds.pairs[i][0], [items['src_box'][i - b0]])[:K] for i in range(b0, b1)]
+                x_F = None
+                if args.seed is not None:          # one start latent per face: seed + pair index, then the face's rank
+                    h8 = args.res // 8
+                    x_F = [torch.randn(1, model.channels, h8, h8, generator=torch.Generator().manual_seed((args.seed + i) * 64 + k))
+                           for i in range(b0, b1) for k in range(len(faces[i - b0]))]
+                    x_F = torch.cat(x_F).cuda(local) if x_F else None
+                photos, faces = model.transfer_photos(items['src_photo'], items['ref_photo'], faces, ref_boxes,
+                                                      src_segs=items.get('src_seg'), feather=args.photo_feather, x_T=x_F, size=args.res, batch=text,
+                                                      max_faces=K, return_faces=True)
+                print(f'[rank {rank}] faces per photo: {[len(f) for f in faces]}', flush=True)
             os.makedirs(os.path.join(args.out, 'photos'), exist_ok=True)
             for name, img in zip(items['img_name'], photos):
                 Image.fromarray(img.cpu().numpy()).save(os.path.join(args.out, 'photos', name + '.png'))
