@@ -225,6 +225,79 @@ std::string kind_name(int k) {
     return rest[k - K_GROUPNORM];
 }
 
+// Weight forms DERIVED at a finalize (concatenated / folded / packed copies): one list per net, freed by that net's next finalize
+struct Derived {
+    std::vector<void*> blocks; int64_t bytes = 0;
+};
+
+// A side network beside the UNet pair (`which` code of its weights: 2 first-stage decoder, 3 CLIP text encoder, 4 first-stage
+// encoder): its own arena (a plan holds pointers into it, which another net growing that buffer would free under it), plan and
+// derived weights; the split-K / GroupNorm workspaces of SID_AUX are shared (read at run time)
+enum { W_DEC = 2, W_CLIP = 3, W_ENC = 4 };
+struct FusedRows { bf16_t* w = nullptr; float* b = nullptr; };
+struct SideNet {
+    bool configured = false, finalized = false;
+    Arena arena; char* base = nullptr; size_t cap = 0;
+    std::vector<Op> plan; int shape[3] = {0, 0, 0};       // the shape the plan was built for; all zeros: no plan
+    double flops = 0;
+    Derived derived;
+    std::map<std::string, FusedRows> fused;               // by attention prefix: [Wq;Wk] (first stage) or q|k|v (CLIP) rows + bias
+};
+
+// LayerNorm folded into its consumer GEMM: W' = W*gamma (bf16), s = rowsum(W'), b' = b + W.beta
+struct Folded { bf16_t* w = nullptr; float* s = nullptr; float* b = nullptr; };
+// Everything finalize() derives for one SpatialTransformer; null: not built for this block
+struct TfmBlock {
+    bf16_t* kv_w = nullptr;                                       // [attn2.to_k; attn2.to_v]
+    bf16_t* qkv_plain = nullptr; bf16_t* ffp_w = nullptr; float* ffp_b = nullptr;     // unfolded [to_q; to_k; to_v] and (value, gate)-interleaved GEGLU projection
+    Folded qkv, q2, ffg;                                          // LayerNorm 1 . q|k|v, LayerNorm 2 . attn2.to_q, LayerNorm 3 . interleaved GEGLU projection
+    bf16_t* ffm_w = nullptr; float* ffm_b = nullptr;              // [P.W2 | P], P.b2 + bp: FF2 + proj_out as one GEMM (merge_ffout)
+    bf16_t* tail_w = nullptr; float* tail_v = nullptr;            // fused tail: the block's weights in the order a wave consumes them
+    bf16_t* tail_kv = nullptr;                                    // ... and the cached context K / V in MFMA-operand order (prepare plan)
+    bf16_t* head_w = nullptr; float* head_v = nullptr;            // fused head
+};
+// conv2 and the 1x1 skip of a ResBlock as one implicit GEMM: [W_conv2 | W_skip], b_conv2 + b_skip
+struct SkipFold { bf16_t* w = nullptr; float* b = nullptr; };
+
+// The fold recipe of a transformer block, on fp32 device pointers; mkd_ctx::finalize and the stand-alone mkd_tfm_tail / mkd_tfm_head
+// handles both build their weights here
+typedef std::function<int(void**, size_t)> AllocFn;
+static int alloc_folded(const AllocFn& al, size_t n, size_t k, Folded* f) {
+    int rc = al((void**)&f->w, n * k * sizeof(bf16_t));
+    if (!rc) rc = al((void**)&f->s, n * sizeof(float));
+    if (!rc) rc = al((void**)&f->b, n * sizeof(float));
+    return rc;
+}
+// attn1: [to_q; to_k; to_v] . LN1
+static int fold_ln1_qkv(const float* to_q, const float* to_k, const float* to_v, const float* gamma, const float* beta, int d, const AllocFn& al, Folded* f) {
+    int rc = alloc_folded(al, (size_t)3 * d, d, f);
+    const float* parts[3] = {to_q, to_k, to_v};
+    for (int j = 0; j < 3 && !rc; ++j) rc = launch_fold_layernorm(parts[j], gamma, beta, nullptr, d, d, f->w, j * d, 1, f->s, f->b, 0);
+    return rc;
+}
+// attn2.to_q . LN2
+static int fold_ln2_q(const float* to_q, const float* gamma, const float* beta, int d, const AllocFn& al, Folded* f) {
+    int rc = alloc_folded(al, d, d, f);
+    if (!rc) rc = launch_fold_layernorm(to_q, gamma, beta, nullptr, d, d, f->w, 0, 1, f->s, f->b, 0);
+    return rc;
+}
+// ff.net.0.proj [8d][d] . LN3: rows [0,4d) = value, [4d,8d) = gate  ->  row 2j = value_j, row 2j+1 = gate_j
+static int fold_ln3_geglu(const float* w, const float* bias, const float* gamma, const float* beta, int d, const AllocFn& al, Folded* f) {
+    const int inner = 4 * d;
+    int rc = alloc_folded(al, (size_t)2 * inner, d, f);
+    for (int half = 0; half < 2 && !rc; ++half)
+        rc = launch_fold_layernorm(w + (size_t)half * inner * d, gamma, beta, bias + half * inner, inner, d, f->w, half, 2, f->s, f->b, 0);
+    return rc;
+}
+// FF2 and proj_out are both linear with nothing in between: one GEMM over [gg | h2] (K = 5d)
+static int merge_ff_out(const float* proj_out_w, const float* ff2_w, const float* ff2_b, const float* proj_out_b, int d, const AllocFn& al,
+                        bf16_t** wm, float** bm) {
+    int rc = al((void**)wm, (size_t)d * 5 * d * sizeof(bf16_t));
+    if (!rc) rc = al((void**)bm, (size_t)d * sizeof(float));
+    if (!rc) rc = launch_merge_ff_out(proj_out_w, ff2_w, ff2_b, proj_out_b, *wm, *bm, d, 0);
+    return rc;
+}
+
 }  // namespace
 
 struct mkd_ctx {
@@ -259,28 +332,21 @@ struct mkd_ctx {
     bool gn_colstats_only = getenv("MKD_GN_FUSED") && atoi(getenv("MKD_GN_FUSED")) == 2;      // experiment: statistics by a stand-alone kernel after every producer
     Arena gstat; char* gstat_base = nullptr; size_t gstat_cap = 0;
 
-    // fused weights (built in finalize)
-    std::map<std::string, bf16_t*> qkv_w, kv_w;   // by transformer prefix
-    std::map<std::string, bf16_t*> ffg_w; std::map<std::string, float*> ffg_b;   // GEGLU proj with (value, gate) rows interleaved
-    // LayerNorm folded into its consumer GEMMs: W' = W*gamma (bf16), s = rowsum(W'), b' = b + W.beta
-    std::map<std::string, bf16_t*> q2_w; std::map<std::string, float*> qkv_s, qkv_b, q2_s, q2_b, ffg_s;
-    std::map<std::string, bf16_t*> qkv_plain, ffp_w; std::map<std::string, float*> ffp_b;     // the unfolded counterparts
-    std::map<std::string, bf16_t*> ffm_w; std::map<std::string, float*> ffm_b;                // [P.W2 | P], P.b2 + bp: FF2 + proj_out as one GEMM
+    // fused weights (built in finalize), by transformer prefix
+    std::map<std::string, TfmBlock> tfm;
     bool merge_ffout = getenv("MKD_MERGE_FFOUT") ? atoi(getenv("MKD_MERGE_FFOUT")) != 0 : true;
     // Fused row-local tail of the d = 320 transformer blocks (kernels_tfm.hip): everything after the self-attention product as ONE
-    // launch per block instead of 7.  tfm_w / tfm_v: the block's weights re-packed in the order a wave consumes them (built in
-    // finalize from the SAME folded tensors the unfused plan uses), tfm_kv: the cached context K / V in MFMA-operand order (built in
-    // the prepare plan).  tfm_tail: 0 off, 1 on where the kernel covers the shape, -1 (default) the shape policy of use_tfm_tail().
+    // launch per block instead of 7.  TfmBlock::tail_w / tail_v are built in finalize from the SAME folded tensors the unfused plan
+    // uses, tail_kv in the prepare plan.  tfm_tail: 0 off, 1 on where the kernel covers the shape, -1 (default) the shape policy of
+    // use_tfm_tail().
     int tfm_tail = getenv("MKD_TFM_TAIL") ? atoi(getenv("MKD_TFM_TAIL")) : -1;
-    std::map<std::string, bf16_t*> tfm_w; std::map<std::string, float*> tfm_v; std::map<std::string, bf16_t*> tfm_kv;
     // ... and the head of the same blocks (GroupNorm apply + proj_in + LayerNorm 1 . q|k|v as one launch behind a GroupNorm statistics
     // launch: 4 launches -> 2): tfm_head 0 off, 1 wherever the tail is fused (default)
     int tfm_head = getenv("MKD_TFM_HEAD") ? atoi(getenv("MKD_TFM_HEAD")) : 1;
-    std::map<std::string, bf16_t*> tfm_hw; std::map<std::string, float*> tfm_hv;
     // ResBlocks with a 1x1 skip_connection: conv2 and the skip as ONE implicit GEMM over K = 9 Cout + Cin_block (GemmArgs::A2) where
-    // conv2's plan is the gather kernel - [W_conv2 | W_skip] and b_conv2 + b_skip built at load time.  skip_fold: 0 off, 1 on (default)
+    // conv2's plan is the gather kernel - built at load time, by ResBlock prefix.  skip_fold: 0 off, 1 on (default)
     int skip_fold = getenv("MKD_SKIP_FOLD") ? atoi(getenv("MKD_SKIP_FOLD")) : 1;
-    std::map<std::string, bf16_t*> fold_w; std::map<std::string, float*> fold_b;
+    std::map<std::string, SkipFold> skip_folds;
     std::map<std::string, float*> f32_keep;      // fp32 copies of the weights that get folded (kept for re-finalize)
     bf16_t* emb_w[2] = {nullptr, nullptr};
     float* emb_b[2] = {nullptr, nullptr};
@@ -345,28 +411,16 @@ struct mkd_ctx {
     const float* in_hints[8] = {}; const float* in_context = nullptr;      // [0]: the hint; [1]: interpolation's second; [0..R): region transfer
     const float* in_alpha = nullptr; bool has_interp = false;   // makeup interpolation (build-defined)
     const float* in_weights = nullptr; int n_region_hints = 0;  // region-wise transfer (build-defined): weights [B, R, h, w], R hints (0: off)
-    // ---- first-stage decoder (AutoencoderKL.decode) ----
-    bool vae_configured = false, vae_finalized = false;
-    bool clip_configured = false, clip_finalized = false; mkd_clip_config ccfg{};
-    Arena carena; char* carena_base = nullptr; size_t carena_cap = 0;
-    std::vector<Op> plan_clip; int clip_B = 0, clip_T = 0;
+    // ---- side networks: first-stage decoder (AutoencoderKL.decode), CLIP text encoder, first-stage encoder
+    // (AutoencoderKL.encode + get_first_stage_encoding, opt-in) ----
+    SideNet side[3];
+    SideNet& net(int which) { return side[which - W_DEC]; }
+    const SideNet& net(int which) const { return side[which - W_DEC]; }
+    mkd_vae_config dec_cfg{}, enc_cfg{}; mkd_clip_config txt_cfg{};
     const int32_t* io_tokens = nullptr; float* io_ctx_out = nullptr;
-    std::map<std::string, bf16_t*> clip_qkv_w; std::map<std::string, float*> clip_qkv_b;
-    mkd_vae_config vcfg;
-    std::map<std::string, bf16_t*> vae_fused;           // mid attention [Wq;Wk]
-    std::map<std::string, float*> vae_fused_b;
-    Arena varena; char* varena_base = nullptr; size_t varena_cap = 0;
-    std::vector<Op> plan_vae; int vae_B = 0, vae_h = 0, vae_w = 0;
     const float* io_z = nullptr; float* io_img = nullptr; float io_inv_scale = 1.f;
-    double flops_vae = 0;
-    // ---- first-stage encoder (AutoencoderKL.encode + get_first_stage_encoding), opt-in; weights are `which` 4.  Its own arena: the
-    // decoder plan holds pointers into varena, which an encoder growing that buffer would free under it ----
-    bool venc_configured = false, venc_finalized = false;
-    Arena earena; char* earena_base = nullptr; size_t earena_cap = 0;
-    std::vector<Op> plan_venc; int venc_B = 0, venc_H = 0, venc_W = 0;
     const float* io_enc_img = nullptr; const float* io_enc_noise = nullptr; float* io_enc_z = nullptr; float* io_enc_mom = nullptr;
     float io_enc_scale = 1.f;
-    double flops_venc = 0;
     // per-call io
     const float* io_x = nullptr; const int64_t* io_t = nullptr; float* io_out = nullptr;
     // sampler buffers
@@ -549,12 +603,30 @@ struct mkd_ctx {
     // ---- weights ----------------------------------------------------------------------------------
     // Weight forms DERIVED at finalize() (concatenated / folded / packed copies) are rebuilt by every finalize after a weight was
     // loaded: they live in their own list and the previous generation is freed first (a reloaded checkpoint must not leave 1-2 GB of
-    // stale copies behind; no plan can still use them: mkd_load_weight invalidates the prepared plan)
-    std::vector<void*> derived; int64_t derived_bytes = 0; bool deriving = false;
+    // stale copies behind; no plan can still use them: mkd_load_weight invalidates the prepared plan, a side net's finalize its own)
+    Derived derived;                  // of the UNet pair; a side net's list is in its record
+    Derived* deriving = nullptr;      // the list allocations go to while a finalize runs (null: `owned`)
     int dev_alloc(void** out, size_t bytes) {
         MKD_HIP_CHECK(hipMalloc(out, bytes ? bytes : 16));
-        if (deriving) { derived.push_back(*out); derived_bytes += (int64_t)bytes; } else owned.push_back(*out);
+        if (deriving) { deriving->blocks.push_back(*out); deriving->bytes += (int64_t)bytes; } else owned.push_back(*out);
         weight_bytes += (int64_t)bytes;
+        return 0;
+    }
+    struct DerivingTo { Derived*& f; DerivingTo(Derived*& slot, Derived* d) : f(slot) { f = d; } ~DerivingTo() { f = nullptr; } };
+    int free_derived(Derived& d) {
+        if (d.blocks.empty()) return 0;
+        MKD_HIP_CHECK(hipDeviceSynchronize());
+        for (void* q : d.blocks) hipFree(q);
+        d.blocks.clear(); weight_bytes -= d.bytes; d.bytes = 0;
+        return 0;
+    }
+    int ensure_zero_page() {
+        if (zero_page) return 0;
+        void* z = nullptr;
+        int rc = dev_alloc(&z, 4096);
+        if (rc) return rc;
+        MKD_HIP_CHECK(hipMemset(z, 0, 4096));
+        zero_page = (bf16_t*)z;
         return 0;
     }
     const bf16_t* wb(const std::string& name) const {
@@ -607,7 +679,7 @@ struct mkd_ctx {
         if (rc) return rc;
         if (e != hipSuccess) return mkd_fail(MKD_ERR_HIP, std::string("load_weight sync: ") + hipGetErrorString(e));
         p.loaded = true;
-        if (p.which == 2) vae_finalized = false; else if (p.which == 3) clip_finalized = false; else if (p.which == 4) venc_finalized = false;
+        if (p.which >= W_DEC) net(p.which).finalized = false;
         else { finalized = false; prepared = false; }
         return 0;
     }
@@ -632,34 +704,21 @@ struct mkd_ctx {
         for (auto& kv : params)
             if (kv.second.which < 2 && !kv.second.loaded) return mkd_fail(MKD_ERR_MISSING, "weight not loaded: " + kv.first);
         if (finalized) return 0;
-        if (!zero_page) {
-            void* z = nullptr;
-            int rc = dev_alloc(&z, 4096);
-            if (rc) return rc;
-            MKD_HIP_CHECK(hipMemset(z, 0, 4096));
-            zero_page = (bf16_t*)z;
-        }
-        if (!derived.empty()) {
-            MKD_HIP_CHECK(hipDeviceSynchronize());
-            for (void* q : derived) hipFree(q);
-            derived.clear(); weight_bytes -= derived_bytes; derived_bytes = 0;
-        }
-        struct Guard { bool& f; Guard(bool& b) : f(b) { f = true; } ~Guard() { f = false; } } guard(deriving);
-        qkv_w.clear(); kv_w.clear(); emb_off.clear(); ffg_w.clear(); ffg_b.clear();
-        q2_w.clear(); qkv_s.clear(); qkv_b.clear(); q2_s.clear(); q2_b.clear(); ffg_s.clear(); qkv_plain.clear(); ffp_w.clear(); ffp_b.clear(); ffm_w.clear(); ffm_b.clear();
-        tfm_w.clear(); tfm_v.clear(); tfm_hw.clear(); tfm_hv.clear(); fold_w.clear(); fold_b.clear();
+        int rc = ensure_zero_page(); if (rc) return rc;
+        rc = free_derived(derived); if (rc) return rc;
+        DerivingTo guard(deriving, &derived);
+        tfm.clear(); skip_folds.clear(); emb_off.clear();
+        const AllocFn al = [this](void** out, size_t bytes) { return dev_alloc(out, bytes); };
         for (int which = 0; which < 2; ++which) {
             for (auto& p : st_prefixes[which]) {
                 const std::string t = p + ".transformer_blocks.0";
-                bf16_t* k = nullptr;
-                int rc = concat_rows(&k, {t + ".attn2.to_k.weight", t + ".attn2.to_v.weight"});
+                TfmBlock& tb = tfm[p];
+                rc = concat_rows(&tb.kv_w, {t + ".attn2.to_k.weight", t + ".attn2.to_v.weight"});
                 if (rc) return rc;
-                kv_w[p] = k;
-                {   // unfolded: [to_q; to_k; to_v] and the (value, gate)-interleaved GEGLU projection
-                    bf16_t* q = nullptr;
-                    rc = concat_rows(&q, {t + ".attn1.to_q.weight", t + ".attn1.to_k.weight", t + ".attn1.to_v.weight"});
-                    if (rc) return rc;
-                    qkv_plain[p] = q;
+                // unfolded: [to_q; to_k; to_v] and the (value, gate)-interleaved GEGLU projection
+                rc = concat_rows(&tb.qkv_plain, {t + ".attn1.to_q.weight", t + ".attn1.to_k.weight", t + ".attn1.to_v.weight"});
+                if (rc) return rc;
+                {
                     const Param& pw = params.at(t + ".ff.net.0.proj.weight");
                     const Param& pb = params.at(t + ".ff.net.0.proj.bias");
                     const int64_t inner = pw.shape[0] / 2, kd = pw.shape[1];
@@ -671,88 +730,41 @@ struct mkd_ctx {
                     MKD_HIP_CHECK(hipMemcpy2D((char*)w2 + rowb, 2 * rowb, (const char*)pw.dev + inner * rowb, rowb, rowb, inner, hipMemcpyDeviceToDevice));
                     MKD_HIP_CHECK(hipMemcpy2D(b2, 8, pb.dev, 4, 4, inner, hipMemcpyDeviceToDevice));
                     MKD_HIP_CHECK(hipMemcpy2D((char*)b2 + 4, 8, (const char*)pb.dev + inner * 4, 4, 4, inner, hipMemcpyDeviceToDevice));
-                    ffp_w[p] = (bf16_t*)w2; ffp_b[p] = (float*)b2;
-                    // FF2 and proj_out are both linear with nothing in between: one GEMM over [gg | h2] (K = 5d)
-                    auto kp = f32_keep.find(p + ".proj_out.weight"); auto kw = f32_keep.find(t + ".ff.net.2.weight");
-                    if (merge_ffout && kp != f32_keep.end() && kw != f32_keep.end()) {
-                        const int dd = (int)params.at(p + ".norm.weight").numel();
-                        void* wm = nullptr; void* bm = nullptr;
-                        rc = dev_alloc(&wm, (size_t)dd * 5 * dd * sizeof(bf16_t)); if (rc) return rc;
-                        rc = dev_alloc(&bm, (size_t)dd * sizeof(float)); if (rc) return rc;
-                        rc = launch_merge_ff_out(kp->second, kw->second, wf(t + ".ff.net.2.bias"), wf(p + ".proj_out.bias"), (bf16_t*)wm, (float*)bm, dd, 0);
-                        if (rc) return rc;
-                        ffm_w[p] = (bf16_t*)wm; ffm_b[p] = (float*)bm;
-                    }
+                    tb.ffp_w = (bf16_t*)w2; tb.ffp_b = (float*)b2;
                 }
                 const int d = (int)params.at(p + ".norm.weight").numel();
                 auto keep = [&](const std::string& n) -> const float* {
                     auto it = f32_keep.find(n);
                     return it == f32_keep.end() ? nullptr : it->second;
                 };
-                auto fvec = [&](int n, float** out) { void* v = nullptr; int r = dev_alloc(&v, (size_t)n * sizeof(float)); *out = (float*)v; return r; };
-                // attn1: [to_q; to_k; to_v] . LN1
-                {
-                    void* wq = nullptr; float* sv = nullptr; float* bv = nullptr;
-                    rc = dev_alloc(&wq, (size_t)3 * d * d * sizeof(bf16_t)); if (rc) return rc;
-                    rc = fvec(3 * d, &sv); if (rc) return rc;
-                    rc = fvec(3 * d, &bv); if (rc) return rc;
-                    const char* parts[3] = {".attn1.to_q.weight", ".attn1.to_k.weight", ".attn1.to_v.weight"};
-                    for (int j = 0; j < 3; ++j) {
-                        const float* wsrc = keep(t + parts[j]);
-                        if (!wsrc) return mkd_fail(MKD_ERR_MISSING, "fp32 copy missing for " + t + parts[j]);
-                        rc = launch_fold_layernorm(wsrc, wf(t + ".norm1.weight"), wf(t + ".norm1.bias"), nullptr, d, d, (bf16_t*)wq,
-                                                   j * d, 1, sv, bv, 0);
-                        if (rc) return rc;
-                    }
-                    qkv_w[p] = (bf16_t*)wq; qkv_s[p] = sv; qkv_b[p] = bv;
-                }
-                // attn2.to_q . LN2
-                {
-                    void* wq = nullptr; float* sv = nullptr; float* bv = nullptr;
-                    rc = dev_alloc(&wq, (size_t)d * d * sizeof(bf16_t)); if (rc) return rc;
-                    rc = fvec(d, &sv); if (rc) return rc;
-                    rc = fvec(d, &bv); if (rc) return rc;
-                    const float* wsrc = keep(t + ".attn2.to_q.weight");
-                    if (!wsrc) return mkd_fail(MKD_ERR_MISSING, "fp32 copy missing for " + t + ".attn2.to_q.weight");
-                    rc = launch_fold_layernorm(wsrc, wf(t + ".norm2.weight"), wf(t + ".norm2.bias"), nullptr, d, d, (bf16_t*)wq, 0, 1, sv, bv, 0);
+                const float* kp = keep(p + ".proj_out.weight"); const float* kw = keep(t + ".ff.net.2.weight");
+                if (merge_ffout && kp && kw) {
+                    rc = merge_ff_out(kp, kw, wf(t + ".ff.net.2.bias"), wf(p + ".proj_out.bias"), d, al, &tb.ffm_w, &tb.ffm_b);
                     if (rc) return rc;
-                    q2_w[p] = (bf16_t*)wq; q2_s[p] = sv; q2_b[p] = bv;
                 }
-                // ff.net.0.proj [8d][d] . LN3: rows [0,4d) = value, [4d,8d) = gate  ->  row 2j = value_j, row 2j+1 = gate_j
-                {
-                    const int inner = 4 * d;
-                    void* w2 = nullptr; float* sv = nullptr; float* bv = nullptr;
-                    rc = dev_alloc(&w2, (size_t)2 * inner * d * sizeof(bf16_t)); if (rc) return rc;
-                    rc = fvec(2 * inner, &sv); if (rc) return rc;
-                    rc = fvec(2 * inner, &bv); if (rc) return rc;
-                    const float* wsrc = keep(t + ".ff.net.0.proj.weight");
-                    if (!wsrc) return mkd_fail(MKD_ERR_MISSING, "fp32 copy missing for " + t + ".ff.net.0.proj.weight");
-                    const float* bsrc = wf(t + ".ff.net.0.proj.bias");
-                    for (int half = 0; half < 2; ++half) {
-                        rc = launch_fold_layernorm(wsrc + (size_t)half * inner * d, wf(t + ".norm3.weight"), wf(t + ".norm3.bias"),
-                                                   bsrc + half * inner, inner, d, (bf16_t*)w2, half, 2, sv, bv, 0);
-                        if (rc) return rc;
-                    }
-                    ffg_w[p] = (bf16_t*)w2; ffg_b[p] = bv; ffg_s[p] = sv;
+                const char* folded[5] = {".attn1.to_q.weight", ".attn1.to_k.weight", ".attn1.to_v.weight", ".attn2.to_q.weight", ".ff.net.0.proj.weight"};
+                const float* src[5];
+                for (int j = 0; j < 5; ++j) {
+                    src[j] = keep(t + folded[j]);
+                    if (!src[j]) return mkd_fail(MKD_ERR_MISSING, "fp32 copy missing for " + t + folded[j]);
                 }
-                if (tfm_tail_weight_bytes(d) && cfg.num_heads == 8 && ffm_w.count(p)) {
-                    void* wp = nullptr; void* vp = nullptr;
-                    rc = dev_alloc(&wp, tfm_tail_weight_bytes(d)); if (rc) return rc;
-                    rc = dev_alloc(&vp, tfm_tail_vec_bytes(d)); if (rc) return rc;
-                    TfmTailWeights tw{wb(t + ".attn1.to_out.0.weight"), wf(t + ".attn1.to_out.0.bias"), q2_w.at(p), q2_s.at(p), q2_b.at(p),
-                                      wb(t + ".attn2.to_out.0.weight"), wf(t + ".attn2.to_out.0.bias"), ffg_w.at(p), ffg_s.at(p), ffg_b.at(p),
-                                      ffm_w.at(p), ffm_b.at(p)};
-                    rc = tfm_tail_pack_weights(d, tw, (bf16_t*)wp, (float*)vp, 0);
+                rc = fold_ln1_qkv(src[0], src[1], src[2], wf(t + ".norm1.weight"), wf(t + ".norm1.bias"), d, al, &tb.qkv); if (rc) return rc;
+                rc = fold_ln2_q(src[3], wf(t + ".norm2.weight"), wf(t + ".norm2.bias"), d, al, &tb.q2); if (rc) return rc;
+                rc = fold_ln3_geglu(src[4], wf(t + ".ff.net.0.proj.bias"), wf(t + ".norm3.weight"), wf(t + ".norm3.bias"), d, al, &tb.ffg); if (rc) return rc;
+                if (tfm_tail_weight_bytes(d) && cfg.num_heads == 8 && tb.ffm_w) {
+                    rc = dev_alloc((void**)&tb.tail_w, tfm_tail_weight_bytes(d)); if (rc) return rc;
+                    rc = dev_alloc((void**)&tb.tail_v, tfm_tail_vec_bytes(d)); if (rc) return rc;
+                    TfmTailWeights tw{wb(t + ".attn1.to_out.0.weight"), wf(t + ".attn1.to_out.0.bias"), tb.q2.w, tb.q2.s, tb.q2.b,
+                                      wb(t + ".attn2.to_out.0.weight"), wf(t + ".attn2.to_out.0.bias"), tb.ffg.w, tb.ffg.s, tb.ffg.b,
+                                      tb.ffm_w, tb.ffm_b};
+                    rc = tfm_tail_pack_weights(d, tw, tb.tail_w, tb.tail_v, 0);
                     if (rc) return rc;
-                    tfm_w[p] = (bf16_t*)wp; tfm_v[p] = (float*)vp;
-                    void* hwp = nullptr; void* hvp = nullptr;
-                    rc = dev_alloc(&hwp, tfm_head_weight_bytes(d)); if (rc) return rc;
-                    rc = dev_alloc(&hvp, tfm_head_vec_bytes(d)); if (rc) return rc;
+                    rc = dev_alloc((void**)&tb.head_w, tfm_head_weight_bytes(d)); if (rc) return rc;
+                    rc = dev_alloc((void**)&tb.head_v, tfm_head_vec_bytes(d)); if (rc) return rc;
                     TfmHeadWeights hw{wf(p + ".norm.weight"), wf(p + ".norm.bias"), wb(p + ".proj_in.weight"), wf(p + ".proj_in.bias"),
-                                      qkv_w.at(p), qkv_s.at(p), qkv_b.at(p)};
-                    rc = tfm_head_pack_weights(d, hw, (bf16_t*)hwp, (float*)hvp, 0);
+                                      tb.qkv.w, tb.qkv.s, tb.qkv.b};
+                    rc = tfm_head_pack_weights(d, hw, tb.head_w, tb.head_v, 0);
                     if (rc) return rc;
-                    tfm_hw[p] = (bf16_t*)hwp; tfm_hv[p] = (float*)hvp;
                 }
             }
             for (auto& p : res_prefixes[which]) {
@@ -763,7 +775,7 @@ struct mkd_ctx {
                 if (cw.shape[1] != cout || (9 * cout) % 64 || cs % 64) continue;
                 const size_t kc = (size_t)9 * cout, kt = kc + cs;
                 void* wm = nullptr; void* bm = nullptr;
-                int rc = dev_alloc(&wm, (size_t)cout * kt * sizeof(bf16_t)); if (rc) return rc;
+                rc = dev_alloc(&wm, (size_t)cout * kt * sizeof(bf16_t)); if (rc) return rc;
                 rc = dev_alloc(&bm, (size_t)cout * sizeof(float)); if (rc) return rc;
                 MKD_HIP_CHECK(hipMemcpy2D(wm, kt * sizeof(bf16_t), cw.dev, kc * sizeof(bf16_t), kc * sizeof(bf16_t), cout, hipMemcpyDeviceToDevice));
                 MKD_HIP_CHECK(hipMemcpy2D((char*)wm + kc * sizeof(bf16_t), kt * sizeof(bf16_t), sk->second.dev, (size_t)cs * sizeof(bf16_t), (size_t)cs * sizeof(bf16_t), cout,
@@ -773,7 +785,7 @@ struct mkd_ctx {
                 MKD_HIP_CHECK(hipMemcpy(b2.data(), wf(p + ".skip_connection.bias"), cout * sizeof(float), hipMemcpyDeviceToHost));
                 for (int i = 0; i < cout; ++i) b1[i] += b2[i];
                 MKD_HIP_CHECK(hipMemcpy(bm, b1.data(), cout * sizeof(float), hipMemcpyHostToDevice));
-                fold_w[p] = (bf16_t*)wm; fold_b[p] = (float*)bm;
+                skip_folds[p] = SkipFold{(bf16_t*)wm, (float*)bm};
             }
             std::vector<std::string> wn;
             int off = 0;
@@ -783,7 +795,7 @@ struct mkd_ctx {
                 off += (int)params.at(p + ".emb_layers.1.bias").numel();
             }
             emb_total[which] = off;
-            int rc = concat_rows(&emb_w[which], wn);
+            rc = concat_rows(&emb_w[which], wn);
             if (rc) return rc;
             void* b = nullptr;
             rc = dev_alloc(&b, off * sizeof(float));
@@ -973,10 +985,11 @@ struct mkd_ctx {
         // conv2 + skip as one implicit GEMM when conv2's plan for this shape is the gather kernel (the decoder lanes' shapes)
         GemmArgs fa; memset(&fa, 0, sizeof(fa));
         bool fold = false;
-        if (x.C != cout && skip_fold && !no_skip && fold_w.count(p) && x.ld % 8 == 0) {
+        const auto sf = skip_folds.find(p);
+        if (x.C != cout && skip_fold && !no_skip && sf != skip_folds.end() && x.ld % 8 == 0) {
             Tensor t3s; t3s.p = nullptr; t3s.B = x.B; t3s.H = x.H; t3s.W = x.W; t3s.C = cout; t3s.ld = cout;
-            Epi ef; ef.bias = fold_b.at(p); ef.gn = go;
-            fa = conv_args(t3s, fold_w.at(p), cout, 1, 0, ef, out, ldo);
+            Epi ef; ef.bias = sf->second.b; ef.gn = go;
+            fa = conv_args(t3s, sf->second.w, cout, 1, 0, ef, out, ldo);
             fa.A2 = x.p; fa.lda2 = x.ld; fa.K2 = x.C; fa.K += x.C; fa.ldw = fa.K; fa.zero = zero_page;
             int cfg_i = 0, sk_i = 1;
             fold = gemm_resolve(fa, &cfg_i, &sk_i) == 0;
@@ -1028,15 +1041,15 @@ struct mkd_ctx {
 
     // Where the fused tail replaces the 7 launches (tools/bench_tfm_tail.py, profiles/exp_r4_tfm_tail_standalone.txt: 0.49 of the
     // chain's time at M >= 16384 rows, 0.73 at 8192, 1.08 at 4096 - a workgroup streams the block's 3.3 MB of weights whatever M is).
-    bool use_tfm_tail(const std::string& p, int d, int M, int T, bool producer_ln, const GnOut& go) const {
-        if (tfm_tail == 0 || producer_ln || go.gst || !tfm_w.count(p) || !tfm_kv.count(p)) return false;
+    bool use_tfm_tail(const TfmBlock& tb, int d, int M, int T, bool producer_ln, const GnOut& go) const {
+        if (tfm_tail == 0 || producer_ln || go.gst || !tb.tail_w || !tb.tail_kv) return false;
         if (!tfm_tail_supported(d, cfg.num_heads, T, ctx_len()) || M % 64) return false;
         return tfm_tail > 0 || M >= tfm_tail_min_rows;
     }
     int tfm_tail_min_rows = getenv("MKD_TFM_TAIL_MINROWS") ? atoi(getenv("MKD_TFM_TAIL_MINROWS")) : 4096;
-    void emit_tfm_tail(const std::string& p, int d, int M, int T, const bf16_t* a1, const bf16_t* h0, const Tensor& x, bf16_t* out, int ldo, int b0) {
-        const bf16_t* wpk = tfm_w.at(p); const float* vec = tfm_v.at(p);
-        const bf16_t* kvp = tfm_kv.at(p) + (size_t)b0 * (tfm_tail_kv_bytes(d, 1) / sizeof(bf16_t));
+    void emit_tfm_tail(const TfmBlock& tb, int d, int M, int T, const bf16_t* a1, const bf16_t* h0, const Tensor& x, bf16_t* out, int ldo, int b0) {
+        const bf16_t* wpk = tb.tail_w; const float* vec = tb.tail_v;
+        const bf16_t* kvp = tb.tail_kv + (size_t)b0 * (tfm_tail_kv_bytes(d, 1) / sizeof(bf16_t));
         const bf16_t* xin = x.p; const int ldx = x.ld, Tk = ctx_len();
         push(*cur_plan, [=](hipStream_t st) { return launch_tfm_tail(d, wpk, vec, a1, d, h0, d, xin, ldx, kvp, out, ldo, M, T, Tk, st); },
              1, tfm_tail_flops(d, M, Tk), K_TFM_TAIL, "M=" + std::to_string(M) + " d=" + std::to_string(d) + " T=" + std::to_string(T));
@@ -1048,9 +1061,10 @@ struct mkd_ctx {
         const size_t mk = TA().mark();
         const int d = x.C, M = x.rows(), T = x.H * x.W, heads = cfg.num_heads, dh = d / heads;
         const std::string t = p + ".transformer_blocks.0";
+        const TfmBlock& tb = tfm.at(p);
         auto buf = [&](int cols) { return (bf16_t*)TA().alloc((size_t)M * cols * sizeof(bf16_t)); };
-        const bool fused_tail = use_tfm_tail(p, d, M, T, fuse_ln && gemm_stat_slots(M, d, d) <= 20, go);
-        if (fused_tail && tfm_head != 0 && tfm_hw.count(p) && !x.gst) {
+        const bool fused_tail = use_tfm_tail(tb, d, M, T, fuse_ln && gemm_stat_slots(M, d, d) <= 20, go);
+        if (fused_tail && tfm_head != 0 && tb.head_w && !x.gst) {
             // head as two launches: GroupNorm statistics (full chip), then GroupNorm apply + proj_in + LayerNorm 1 . q|k|v per 64-token tile
             bf16_t* h0f = buf(d); bf16_t* qkvf = buf(3 * d);
             const size_t need = groupnorm_partials_bytes(x.B, T, 32);
@@ -1058,7 +1072,7 @@ struct mkd_ctx {
             mkd_ctx* self = this;
             const int sid = cur_sid;
             const Tensor xt = x;
-            const bf16_t* hwp = tfm_hw.at(p); const float* hvp = tfm_hv.at(p);
+            const bf16_t* hwp = tb.head_w; const float* hvp = tb.head_v;
             push(*cur_plan, [self, xt, T, d, sid, hwp, hvp, h0f, qkvf, M](hipStream_t st) {
                 int nch = 0;
                 int rc = launch_gn_stats(xt.p, xt.ld, xt.B, T, d, 32, self->gn_ws[arena_of(sid)], st, &nch);
@@ -1067,7 +1081,7 @@ struct mkd_ctx {
             }, 2, 2.0 * M * 4.0 * d * d, K_TFM_TAIL, "head M=" + std::to_string(M) + " d=" + std::to_string(d) + " T=" + std::to_string(T));
             bf16_t* a1f = buf(d);
             op_attn(qkvf, 3 * d, qkvf + d, 3 * d, qkvf + 2 * d, 3 * d, a1f, d, x.B, T, T, heads, dh);
-            emit_tfm_tail(p, d, M, T, a1f, h0f, x, out, ldo, b0);
+            emit_tfm_tail(tb, d, M, T, a1f, h0f, x, out, ldo, b0);
             TA().release(mk);
             return;
         }
@@ -1091,19 +1105,19 @@ struct mkd_ctx {
             op_ln(hsrc, wf(t + norm + ".weight"), wf(t + norm + ".bias"), y, M, d, ldh);
             return y;
         };
-        const bool mf = !fl && ffm_w.count(p);              // FF2 + proj_out as one GEMM over [gg | h2]
+        const bool mf = !fl && tb.ffm_w;              // FF2 + proj_out as one GEMM over [gg | h2]
         bf16_t* cat5 = mf ? buf(5 * d) : nullptr;
         bf16_t* h0 = buf(d);
         { Epi e; e.bias = wf(p + ".proj_in.bias"); e.stat_out = st0; op_linear(g, d, M, d, wb(p + ".proj_in.weight"), d, e, h0, d); }
         // self attention
         bf16_t* qkv = buf(3 * d);
         { Epi e; const bool f = fl || fy1; const bf16_t* a_in = ln_input(h0, ".norm1", 0, f);
-          if (f) { e.bias = qkv_b.at(p); e.ln_s = qkv_s.at(p); e.stat_in = fl ? st0 : nullptr; e.stat_slots = fl ? slots : 0; }
-          op_linear(a_in, d, M, d, f ? qkv_w.at(p) : qkv_plain.at(p), 3 * d, e, qkv, 3 * d); }
+          if (f) { e.bias = tb.qkv.b; e.ln_s = tb.qkv.s; e.stat_in = fl ? st0 : nullptr; e.stat_slots = fl ? slots : 0; }
+          op_linear(a_in, d, M, d, f ? tb.qkv.w : tb.qkv_plain, 3 * d, e, qkv, 3 * d); }
         bf16_t* a1 = buf(d);
         op_attn(qkv, 3 * d, qkv + d, 3 * d, qkv + 2 * d, 3 * d, a1, d, x.B, T, T, heads, dh);
         if (fused_tail) {          // everything below as one launch per 64-token tile
-            emit_tfm_tail(p, d, M, T, a1, h0, x, out, ldo, b0);
+            emit_tfm_tail(tb, d, M, T, a1, h0, x, out, ldo, b0);
             TA().release(mk);
             return;
         }
@@ -1113,8 +1127,8 @@ struct mkd_ctx {
         // cross attention (K/V cached at prepare)
         bf16_t* q2 = buf(d);
         { Epi e; const bool f = fl || fy2; const bf16_t* a_in = ln_input(h1, ".norm2", 0, f);
-          if (f) { e.bias = q2_b.at(p); e.ln_s = q2_s.at(p); e.stat_in = fl ? st1 : nullptr; e.stat_slots = fl ? slots : 0; }
-          op_linear(a_in, d, M, d, f ? q2_w.at(p) : wb(t + ".attn2.to_q.weight"), d, e, q2, d); }
+          if (f) { e.bias = tb.q2.b; e.ln_s = tb.q2.s; e.stat_in = fl ? st1 : nullptr; e.stat_slots = fl ? slots : 0; }
+          op_linear(a_in, d, M, d, f ? tb.q2.w : wb(t + ".attn2.to_q.weight"), d, e, q2, d); }
         Tensor kv = kv_cache.at(p);
         kv.p += (size_t)b0 * ctx_len() * kv.ld;
         bf16_t* a2 = buf(d);
@@ -1127,12 +1141,12 @@ struct mkd_ctx {
         bf16_t* gg = mf ? cat5 : buf(4 * d);
         const int ldg = mf ? 5 * d : 4 * d;
         { Epi e; const bool f = fl || fy3; const bf16_t* a_in = ln_input(h2, ".norm3", ldh2, f); e.act = 2;
-          if (f) { e.bias = ffg_b.at(p); e.ln_s = ffg_s.at(p); e.stat_in = fl ? st2 : nullptr; e.stat_slots = fl ? slots : 0; }
-          else e.bias = ffp_b.at(p);
-          op_linear(a_in, f ? ldh2 : d, M, d, f ? ffg_w.at(p) : ffp_w.at(p), 8 * d, e, gg, ldg); }
+          if (f) { e.bias = tb.ffg.b; e.ln_s = tb.ffg.s; e.stat_in = fl ? st2 : nullptr; e.stat_slots = fl ? slots : 0; }
+          else e.bias = tb.ffp_b;
+          op_linear(a_in, f ? ldh2 : d, M, d, f ? tb.ffg.w : tb.ffp_w, 8 * d, e, gg, ldg); }
         if (mf) {
-            Epi e; e.bias = ffm_b.at(p); e.R = x.p; e.ldr = x.ld; e.gn = go;
-            op_linear(cat5, 5 * d, M, 5 * d, ffm_w.at(p), d, e, out, ldo);
+            Epi e; e.bias = tb.ffm_b; e.R = x.p; e.ldr = x.ld; e.gn = go;
+            op_linear(cat5, 5 * d, M, 5 * d, tb.ffm_w, d, e, out, ldo);
         } else {
             bf16_t* h3 = buf(d);
             { Epi e; e.bias = wf(t + ".ff.net.2.bias"); e.R = h2; e.ldr = d;
@@ -1336,21 +1350,23 @@ struct mkd_ctx {
             bf16_t* dst = ctx_bf16; const int64_t n = (int64_t)B * L * cd;
             push(*cur_plan, [self, dst, n](hipStream_t st) { return launch_f32_to_bf16(self->in_context, dst, n, st); }, 1, 0.0);
         }
-        kv_cache.clear(); tfm_kv.clear();
+        kv_cache.clear();
+        for (auto& kv : tfm) kv.second.tail_kv = nullptr;
         for (int which = 0; which < 2; ++which) {
             if (which == 1 && !has_control) continue;
             for (auto& p : st_prefixes[which]) {
                 const int d = (int)params.at(p + ".norm.weight").numel();
+                TfmBlock& tb = tfm.at(p);
                 Tensor kv; kv.B = B; kv.H = 1; kv.W = L; kv.C = 2 * d; kv.ld = 2 * d;
                 kv.p = (bf16_t*)persist.alloc((size_t)B * L * 2 * d * sizeof(bf16_t));
                 Epi e;
-                op_linear(ctx_bf16, cd, B * L, cd, kv_w.at(p), 2 * d, e, kv.p, 2 * d);
+                op_linear(ctx_bf16, cd, B * L, cd, tb.kv_w, 2 * d, e, kv.p, 2 * d);
                 kv_cache[p] = kv;
-                if (tfm_w.count(p) && tfm_tail != 0 && L <= 80) {
+                if (tb.tail_w && tfm_tail != 0 && L <= 80) {
                     bf16_t* kp = (bf16_t*)persist.alloc(tfm_tail_kv_bytes(d, B));
                     const bf16_t* src = kv.p; const int Bn = B;
                     push(*cur_plan, [src, d, Bn, L, kp](hipStream_t st) { return launch_tfm_tail_pack_kv(d, src, 2 * d, Bn, L, kp, st); }, 1, 0.0, K_MISC, "tfm_kv_pack");
-                    tfm_kv[p] = kp;
+                    tb.tail_kv = kp;
                 }
             }
         }
@@ -2340,23 +2356,27 @@ struct mkd_ctx {
         add_param(p + ".conv2.weight", {cout, cout, 3, 3}, which); add_param(p + ".conv2.bias", {cout}, which);
         if (cin != cout) { add_param(p + ".nin_shortcut.weight", {cout, cin, 1, 1}, which); add_param(p + ".nin_shortcut.bias", {cout}, which); }
     }
+    // mid.block_1, mid.attn_1, mid.block_2 of the decoder or the encoder (P: its prefix)
+    void vae_add_mid(const std::string& P, int c, int which) {
+        vae_add_res(P + "mid.block_1", c, c, which);
+        for (const char* n : {"q", "k", "v", "proj_out"}) {
+            add_param(P + "mid.attn_1." + n + ".weight", {c, c, 1, 1}, which); add_param(P + "mid.attn_1." + n + ".bias", {c}, which);
+        }
+        add_param(P + "mid.attn_1.norm.weight", {c}, which); add_param(P + "mid.attn_1.norm.bias", {c}, which);
+        vae_add_res(P + "mid.block_2", c, c, which);
+    }
     int vae_configure(const mkd_vae_config* c) {
-        if (vae_configured) return mkd_fail(MKD_ERR_STATE, "mkd_vae_configure: already configured");
+        if (net(W_DEC).configured) return mkd_fail(MKD_ERR_STATE, "mkd_vae_configure: already configured");
         if (c->n_levels < 1 || c->n_levels > 8 || c->ch % 32 || c->z_channels != c->embed_dim || c->z_channels > 8 ||
             (c->out_ch != 3 && c->out_ch != 4))
             return mkd_fail(MKD_ERR_UNSUPPORTED, "mkd_vae_configure: unsupported decoder configuration");
-        vcfg = *c;
+        dec_cfg = *c;
         const std::string P = vae_prefix(), D = P + "decoder.";
         add_param(P + "post_quant_conv.weight", {c->z_channels, c->embed_dim, 1, 1}, 2);
         add_param(P + "post_quant_conv.bias", {c->z_channels}, 2);
         int bi = c->ch * c->ch_mult[c->n_levels - 1];
         add_param(D + "conv_in.weight", {bi, c->z_channels, 3, 3}, 2); add_param(D + "conv_in.bias", {bi}, 2);
-        vae_add_res(D + "mid.block_1", bi, bi);
-        for (const char* n : {"q", "k", "v", "proj_out"}) {
-            add_param(D + "mid.attn_1." + n + ".weight", {bi, bi, 1, 1}, 2); add_param(D + "mid.attn_1." + n + ".bias", {bi}, 2);
-        }
-        add_param(D + "mid.attn_1.norm.weight", {bi}, 2); add_param(D + "mid.attn_1.norm.bias", {bi}, 2);
-        vae_add_res(D + "mid.block_2", bi, bi);
+        vae_add_mid(D, bi, W_DEC);
         for (int lvl = c->n_levels - 1; lvl >= 0; --lvl) {
             const int bo = c->ch * c->ch_mult[lvl];
             for (int j = 0; j <= c->num_res_blocks; ++j) { vae_add_res(D + "up." + std::to_string(lvl) + ".block." + std::to_string(j), bi, bo); bi = bo; }
@@ -2367,41 +2387,72 @@ struct mkd_ctx {
         }
         add_param(D + "norm_out.weight", {bi}, 2); add_param(D + "norm_out.bias", {bi}, 2);
         add_param(D + "conv_out.weight", {c->out_ch, bi, 3, 3}, 2); add_param(D + "conv_out.bias", {c->out_ch}, 2);
-        vae_configured = true;
+        net(W_DEC).configured = true;
         return 0;
     }
-    int vae_finalize() {
-        if (!vae_configured) return mkd_fail(MKD_ERR_STATE, "decoder not configured (mkd_vae_configure)");
+    // One life cycle for the three side nets.  `derive` builds the net's fused weights into its own list: the previous generation is
+    // freed first, and the plan, which holds pointers to it, is dropped
+    int side_finalize(int which, const char* not_configured, const std::function<int(SideNet&)>& derive) {
+        SideNet& n = net(which);
+        if (!n.configured) return mkd_fail(MKD_ERR_STATE, not_configured);
         for (auto& kv : params)
-            if (kv.second.which == 2 && !kv.second.loaded) return mkd_fail(MKD_ERR_MISSING, "weight not loaded: " + kv.first);
-        if (vae_finalized) return 0;
-        if (!zero_page) {
-            void* z = nullptr;
-            int rc = dev_alloc(&z, 4096); if (rc) return rc;
-            MKD_HIP_CHECK(hipMemset(z, 0, 4096));
-            zero_page = (bf16_t*)z;
+            if (kv.second.which == which && !kv.second.loaded) return mkd_fail(MKD_ERR_MISSING, "weight not loaded: " + kv.first);
+        if (n.finalized) return 0;
+        int rc = ensure_zero_page(); if (rc) return rc;
+        rc = free_derived(n.derived); if (rc) return rc;
+        n.fused.clear();
+        {
+            DerivingTo guard(deriving, &n.derived);
+            rc = derive(n); if (rc) return rc;
         }
-        int rc = vae_fuse_attn(vae_prefix() + "decoder.mid.attn_1"); if (rc) return rc;
         MKD_HIP_CHECK(hipDeviceSynchronize());
-        vae_finalized = true;
+        n.finalized = true;
+        n.shape[0] = n.shape[1] = n.shape[2] = 0;
         return 0;
+    }
+    // A plan for another shape, in two passes as in mkd_prepare: a dry run of `build` sizes the net's arena and the SID_AUX workspaces,
+    // the second binds pointers.  The evaluation plans keep their own workspace maxima
+    int side_replan(SideNet& n, int Bn, int a, int b, const std::function<void()>& build) {
+        const size_t keep_sk = splitk_need, keep_gn = gn_need;
+        splitk_need = 0; gn_need = 0;
+        n.shape[0] = n.shape[1] = n.shape[2] = 0; n.flops = 0;
+        dry = true; n.arena.base = nullptr; n.arena.reset(); n.plan.clear();
+        build();
+        dry = false;
+        int rc = ensure((void**)&n.base, &n.cap, n.arena.high + 256);
+        if (!rc) rc = ensure((void**)&splitk_ws[SID_AUX], &splitk_ws_bytes[SID_AUX], std::max(splitk_need, splitk_ws_bytes[SID_AUX]));
+        if (!rc) rc = ensure((void**)&gn_ws[SID_AUX], &gn_ws_bytes[SID_AUX], std::max(gn_need, gn_ws_bytes[SID_AUX]));
+        if (!rc) {
+            n.arena.base = n.base; n.arena.reset(); n.plan.clear();
+            build();
+            for (auto& op : n.plan) n.flops += op.flops;
+            n.shape[0] = Bn; n.shape[1] = a; n.shape[2] = b;
+        }
+        splitk_need = keep_sk; gn_need = keep_gn;
+        return rc;
+    }
+    int side_run(SideNet& n, hipStream_t stream) {
+        for (auto& op : n.plan) { int rc = op.fn(stream); if (rc) return rc; }
+        return 0;
+    }
+
+    int vae_finalize() {
+        return side_finalize(W_DEC, "decoder not configured (mkd_vae_configure)",
+                             [this](SideNet& n) { return vae_fuse_attn(n, vae_prefix() + "decoder.mid.attn_1"); });
     }
     // the mid attention's fused [Wq;Wk] (+ bias) of the decoder or the encoder
-    int vae_fuse_attn(const std::string& A) {
-        bf16_t* qk = nullptr;
-        int rc = concat_rows(&qk, {A + ".q.weight", A + ".k.weight"}); if (rc) return rc;
-        vae_fused[A] = qk;
+    int vae_fuse_attn(SideNet& n, const std::string& A) {
+        FusedRows& f = n.fused[A];
+        int rc = concat_rows(&f.w, {A + ".q.weight", A + ".k.weight"}); if (rc) return rc;
         const int c = (int)params.at(A + ".q.bias").numel();
-        void* b = nullptr;
-        rc = dev_alloc(&b, 2 * c * sizeof(float)); if (rc) return rc;
-        MKD_HIP_CHECK(hipMemcpy(b, params.at(A + ".q.bias").dev, c * sizeof(float), hipMemcpyDeviceToDevice));
-        MKD_HIP_CHECK(hipMemcpy((float*)b + c, params.at(A + ".k.bias").dev, c * sizeof(float), hipMemcpyDeviceToDevice));
-        vae_fused_b[A] = (float*)b;
+        rc = dev_alloc((void**)&f.b, 2 * c * sizeof(float)); if (rc) return rc;
+        MKD_HIP_CHECK(hipMemcpy(f.b, params.at(A + ".q.bias").dev, c * sizeof(float), hipMemcpyDeviceToDevice));
+        MKD_HIP_CHECK(hipMemcpy(f.b + c, params.at(A + ".k.bias").dev, c * sizeof(float), hipMemcpyDeviceToDevice));
         return 0;
     }
 
     // VAE ResnetBlock: GN(eps 1e-6)+SiLU -> conv3x3 -> GN+SiLU -> conv3x3 (+ x or nin_shortcut(x))
-    // (ar: the arena of the plan being built - the decoder's varena or the encoder's earena)
+    // (ar: the arena of the plan being built - the decoder's or the encoder's)
     void vae_resblock(Arena& ar, const std::string& p, const Tensor& x, int cout, bf16_t* out) {
         const size_t mk = ar.mark();
         auto tal = [&](int C_) { Tensor t = x; t.C = C_; t.ld = C_; t.p = (bf16_t*)ar.alloc((size_t)x.rows() * C_ * sizeof(bf16_t)); return t; };
@@ -2423,14 +2474,15 @@ struct mkd_ctx {
     }
 
     // single-head attention over the hw tokens of each sample, built from GEMMs (c = 512 does not fit the flash kernel)
-    void vae_attn(Arena& ar, const std::string& p, const Tensor& x, bf16_t* out) {
+    void vae_attn(SideNet& n, const std::string& p, const Tensor& x, bf16_t* out) {
+        Arena& ar = n.arena;
         const size_t mk = ar.mark();
         const int c = x.C, T = x.H * x.W, M = x.rows();
         auto buf = [&](size_t n) { return (bf16_t*)ar.alloc(n * sizeof(bf16_t)); };
         bf16_t* g = buf((size_t)M * c);
         op_gn(x, wf(p + ".norm.weight"), wf(p + ".norm.bias"), 1e-6f, 0, g, c);
         bf16_t* qk = buf((size_t)M * 2 * c);
-        { Epi e; e.bias = vae_fused_b.at(p); op_linear(g, c, M, c, vae_fused.at(p), 2 * c, e, qk, 2 * c); }
+        { const FusedRows& f = n.fused.at(p); Epi e; e.bias = f.b; op_linear(g, c, M, c, f.w, 2 * c, e, qk, 2 * c); }
         bf16_t* vt = buf((size_t)x.B * c * T);          // V^T per sample: [c][T] = Wv . g_b^T  (v bias added after PV: softmax rows sum to 1)
         bf16_t* sc = buf((size_t)x.B * T * T);
         bf16_t* pr = buf((size_t)x.B * T * T);
@@ -2457,31 +2509,32 @@ struct mkd_ctx {
     }
 
     void build_vae_plan(int Bn, int hh, int ww) {
-        cur_plan = &plan_vae; cur_sid = SID_AUX; counting_eps = false;
+        SideNet& n = net(W_DEC);
+        cur_plan = &n.plan; cur_sid = SID_AUX; counting_eps = false;
         mkd_ctx* self = this;
         const std::string P = vae_prefix(), D = P + "decoder.";
-        const int zc = vcfg.z_channels;
+        const int zc = dec_cfg.z_channels;
         // largest activation of the decoder: (2^(L-1) h)^2 pixels x ch*ch_mult[1 or 0] channels
         size_t max_act = 0;
         {
-            int bi = vcfg.ch * vcfg.ch_mult[vcfg.n_levels - 1], H = hh, W = ww;
+            int bi = dec_cfg.ch * dec_cfg.ch_mult[dec_cfg.n_levels - 1], H = hh, W = ww;
             max_act = (size_t)Bn * H * W * bi;
-            for (int lvl = vcfg.n_levels - 1; lvl >= 0; --lvl) {
-                const int bo = vcfg.ch * vcfg.ch_mult[lvl];
+            for (int lvl = dec_cfg.n_levels - 1; lvl >= 0; --lvl) {
+                const int bo = dec_cfg.ch * dec_cfg.ch_mult[lvl];
                 max_act = std::max(max_act, (size_t)Bn * H * W * std::max(bi, bo));
                 bi = bo;
                 if (lvl != 0) { H *= 2; W *= 2; max_act = std::max(max_act, (size_t)Bn * H * W * bi); }
             }
         }
-        bf16_t* X[2] = {(bf16_t*)varena.alloc(max_act * sizeof(bf16_t)), (bf16_t*)varena.alloc(max_act * sizeof(bf16_t))};
-        float* zq = (float*)varena.alloc((size_t)Bn * zc * hh * ww * sizeof(float));
+        bf16_t* X[2] = {(bf16_t*)n.arena.alloc(max_act * sizeof(bf16_t)), (bf16_t*)n.arena.alloc(max_act * sizeof(bf16_t))};
+        float* zq = (float*)n.arena.alloc((size_t)Bn * zc * hh * ww * sizeof(float));
         {
             const bf16_t* w_ = wb(P + "post_quant_conv.weight"); const float* b_ = wf(P + "post_quant_conv.bias");
             const int hw = hh * ww;
             push(*cur_plan, [self, w_, b_, zq, Bn, zc, hw](hipStream_t st) {
                 return launch_post_quant(self->io_z, w_, b_, self->io_inv_scale, zq, Bn, zc, hw, st); }, 1, 0.0, K_MISC, "post_quant");
         }
-        int bi = vcfg.ch * vcfg.ch_mult[vcfg.n_levels - 1];
+        int bi = dec_cfg.ch * dec_cfg.ch_mult[dec_cfg.n_levels - 1];
         int cur = 0;
         Tensor h; h.B = Bn; h.H = hh; h.W = ww; h.C = bi; h.ld = bi; h.p = X[cur];
         {
@@ -2491,14 +2544,14 @@ struct mkd_ctx {
                 2.0 * Bn * hh * ww * bi * 9 * zc, K_CONV_DIRECT);
         }
         auto step = [&](int cout) { cur ^= 1; Tensor o = h; o.C = cout; o.ld = cout; o.p = X[cur]; return o; };
-        { Tensor o = step(bi); vae_resblock(varena, D + "mid.block_1", h, bi, o.p); h = o; }
-        { Tensor o = step(bi); vae_attn(varena, D + "mid.attn_1", h, o.p); h = o; }
-        { Tensor o = step(bi); vae_resblock(varena, D + "mid.block_2", h, bi, o.p); h = o; }
-        for (int lvl = vcfg.n_levels - 1; lvl >= 0; --lvl) {
-            const int bo = vcfg.ch * vcfg.ch_mult[lvl];
-            for (int j = 0; j <= vcfg.num_res_blocks; ++j) {
+        { Tensor o = step(bi); vae_resblock(n.arena, D + "mid.block_1", h, bi, o.p); h = o; }
+        { Tensor o = step(bi); vae_attn(n, D + "mid.attn_1", h, o.p); h = o; }
+        { Tensor o = step(bi); vae_resblock(n.arena, D + "mid.block_2", h, bi, o.p); h = o; }
+        for (int lvl = dec_cfg.n_levels - 1; lvl >= 0; --lvl) {
+            const int bo = dec_cfg.ch * dec_cfg.ch_mult[lvl];
+            for (int j = 0; j <= dec_cfg.num_res_blocks; ++j) {
                 Tensor o = step(bo);
-                vae_resblock(varena, D + "up." + std::to_string(lvl) + ".block." + std::to_string(j), h, bo, o.p);
+                vae_resblock(n.arena, D + "up." + std::to_string(lvl) + ".block." + std::to_string(j), h, bo, o.p);
                 h = o;
             }
             if (lvl != 0) {
@@ -2512,7 +2565,7 @@ struct mkd_ctx {
             Tensor o = step(h.C);
             op_gn(h, wf(D + "norm_out.weight"), wf(D + "norm_out.bias"), 1e-6f, 1, o.p, o.ld);
             const bf16_t* w_ = wb(D + "conv_out.weight"); const float* b_ = wf(D + "conv_out.bias");
-            const int H2 = h.H, W2 = h.W, cin = h.C, cout = vcfg.out_ch;
+            const int H2 = h.H, W2 = h.W, cin = h.C, cout = dec_cfg.out_ch;
             push(*cur_plan, [self, o, w_, b_, Bn, H2, W2, cin, cout](hipStream_t st) {
                 return launch_conv3x3_direct(o.p, 0, w_, b_, self->io_img, 1, 0, nullptr, Bn, H2, W2, cin, cout, 1, st); }, 1,
                 2.0 * Bn * H2 * W2 * cout * 9 * cin, K_CONV_DIRECT);
@@ -2520,42 +2573,28 @@ struct mkd_ctx {
     }
 
     int decode(const float* z, int Bn, int hh, int ww, float scale_factor, float* images, hipStream_t stream) {
-        if (!vae_finalized) { int rc = vae_finalize(); if (rc) return rc; }
+        SideNet& n = net(W_DEC);
+        if (!n.finalized) { int rc = vae_finalize(); if (rc) return rc; }
         if (!z || !images || Bn <= 0 || hh <= 0 || ww <= 0 || scale_factor == 0.f) return mkd_fail(MKD_ERR_ARG, "mkd_decode: bad arguments");
-        if (Bn != vae_B || hh != vae_h || ww != vae_w) {
-            // same two-pass scheme as mkd_prepare: dry run sizes the arena, second pass binds pointers
-            const size_t keep_sk = splitk_need, keep_gn = gn_need;
-            splitk_need = 0; gn_need = 0;
-            dry = true; varena.base = nullptr; varena.reset(); plan_vae.clear(); flops_vae = 0;
-            build_vae_plan(Bn, hh, ww);
-            int rc = ensure((void**)&varena_base, &varena_cap, varena.high + 256); if (rc) return rc;
-            rc = ensure((void**)&splitk_ws[SID_AUX], &splitk_ws_bytes[SID_AUX], std::max(splitk_need, splitk_ws_bytes[SID_AUX])); if (rc) return rc;
-            rc = ensure((void**)&gn_ws[SID_AUX], &gn_ws_bytes[SID_AUX], std::max(gn_need, gn_ws_bytes[SID_AUX])); if (rc) return rc;
-            splitk_need = keep_sk; gn_need = keep_gn;          // (the evaluation plans keep their own maxima)
-            dry = false; varena.base = varena_base; varena.reset(); plan_vae.clear();
-            build_vae_plan(Bn, hh, ww);
-            splitk_need = keep_sk; gn_need = keep_gn;
-            for (auto& op : plan_vae) flops_vae += op.flops;
-            vae_B = Bn; vae_h = hh; vae_w = ww;
+        if (Bn != n.shape[0] || hh != n.shape[1] || ww != n.shape[2]) {
+            int rc = side_replan(n, Bn, hh, ww, [&] { build_vae_plan(Bn, hh, ww); }); if (rc) return rc;
         }
         io_z = z; io_img = images; io_inv_scale = 1.0f / scale_factor;
-        for (auto& op : plan_vae) { int rc = op.fn(stream); if (rc) return rc; }
-        return 0;
+        return side_run(n, stream);
     }
-
 
     // ---------------------------------------------------------------------------------------------------------------
     // first-stage encoder (UPSTREAM ldm Encoder + AutoencoderKL.quant_conv; yaml ddconfig with in_channels 3, double_z)
     // ---------------------------------------------------------------------------------------------------------------
     int venc_configure(const mkd_vae_config* c) {
-        if (venc_configured) return mkd_fail(MKD_ERR_STATE, "mkd_vae_encoder_configure: already configured");
+        if (net(W_ENC).configured) return mkd_fail(MKD_ERR_STATE, "mkd_vae_encoder_configure: already configured");
         if (c->n_levels < 1 || c->n_levels > 8 || c->ch % 32 || c->z_channels != 4 || c->embed_dim != 4 || c->num_res_blocks < 1)
             return mkd_fail(MKD_ERR_UNSUPPORTED, "mkd_vae_encoder_configure: unsupported encoder configuration");
         for (int i = 0; i < c->n_levels; ++i)
             if (c->ch_mult[i] < 1) return mkd_fail(MKD_ERR_UNSUPPORTED, "mkd_vae_encoder_configure: ch_mult entries must be >= 1");
-        ecfg = *c;
+        enc_cfg = *c;
         const std::string P = vae_prefix(), E = P + "encoder.";
-        const int W4 = 4;
+        const int W4 = W_ENC;
         add_param(E + "conv_in.weight", {c->ch, 3, 3, 3}, W4); add_param(E + "conv_in.bias", {c->ch}, W4);
         int bi = c->ch;
         for (int lvl = 0; lvl < c->n_levels; ++lvl) {
@@ -2564,87 +2603,69 @@ struct mkd_ctx {
             for (int j = 0; j < c->num_res_blocks; ++j) { vae_add_res(L + ".block." + std::to_string(j), bi, bo, W4); bi = bo; }
             if (lvl != c->n_levels - 1) { add_param(L + ".downsample.conv.weight", {bi, bi, 3, 3}, W4); add_param(L + ".downsample.conv.bias", {bi}, W4); }
         }
-        vae_add_res(E + "mid.block_1", bi, bi, W4);
-        for (const char* n : {"q", "k", "v", "proj_out"}) {
-            add_param(E + "mid.attn_1." + n + ".weight", {bi, bi, 1, 1}, W4); add_param(E + "mid.attn_1." + n + ".bias", {bi}, W4);
-        }
-        add_param(E + "mid.attn_1.norm.weight", {bi}, W4); add_param(E + "mid.attn_1.norm.bias", {bi}, W4);
-        vae_add_res(E + "mid.block_2", bi, bi, W4);
+        vae_add_mid(E, bi, W4);
         add_param(E + "norm_out.weight", {bi}, W4); add_param(E + "norm_out.bias", {bi}, W4);
         add_param(E + "conv_out.weight", {2 * c->z_channels, bi, 3, 3}, W4); add_param(E + "conv_out.bias", {2 * c->z_channels}, W4);
         add_param(P + "quant_conv.weight", {2 * c->embed_dim, 2 * c->z_channels, 1, 1}, W4); add_param(P + "quant_conv.bias", {2 * c->embed_dim}, W4);
-        venc_configured = true;
+        net(W_ENC).configured = true;
         return 0;
     }
-    mkd_vae_config ecfg{};
     int venc_finalize() {
-        if (!venc_configured) return mkd_fail(MKD_ERR_STATE, "encoder not configured (mkd_vae_encoder_configure)");
-        for (auto& kv : params)
-            if (kv.second.which == 4 && !kv.second.loaded) return mkd_fail(MKD_ERR_MISSING, "weight not loaded: " + kv.first);
-        if (venc_finalized) return 0;
-        if (!zero_page) {
-            void* z = nullptr;
-            int rc = dev_alloc(&z, 4096); if (rc) return rc;
-            MKD_HIP_CHECK(hipMemset(z, 0, 4096));
-            zero_page = (bf16_t*)z;
-        }
-        int rc = vae_fuse_attn(vae_prefix() + "encoder.mid.attn_1"); if (rc) return rc;
-        MKD_HIP_CHECK(hipDeviceSynchronize());
-        venc_finalized = true;
-        venc_B = 0;                 // the plan holds pointers to the fused weights: rebuild it
-        return 0;
+        return side_finalize(W_ENC, "encoder not configured (mkd_vae_encoder_configure)",
+                             [this](SideNet& n) { return vae_fuse_attn(n, vae_prefix() + "encoder.mid.attn_1"); });
     }
 
     void build_venc_plan(int Bn, int H, int W) {
-        cur_plan = &plan_venc; cur_sid = SID_AUX; counting_eps = false;
+        SideNet& n = net(W_ENC);
+        cur_plan = &n.plan; cur_sid = SID_AUX; counting_eps = false;
         mkd_ctx* self = this;
         const std::string P = vae_prefix(), E = P + "encoder.";
         // largest activation: full resolution x max(ch * ch_mult[0], ch) channels, then halved pixels per level
         size_t max_act = 0;
         {
-            int h = H, w = W, bi = ecfg.ch;
+            int h = H, w = W, bi = enc_cfg.ch;
             max_act = (size_t)Bn * h * w * bi;
-            for (int lvl = 0; lvl < ecfg.n_levels; ++lvl) {
-                const int bo = ecfg.ch * ecfg.ch_mult[lvl];
+            for (int lvl = 0; lvl < enc_cfg.n_levels; ++lvl) {
+                const int bo = enc_cfg.ch * enc_cfg.ch_mult[lvl];
                 max_act = std::max(max_act, (size_t)Bn * h * w * std::max(bi, bo));
                 bi = bo;
-                if (lvl != ecfg.n_levels - 1) { h /= 2; w /= 2; }
+                if (lvl != enc_cfg.n_levels - 1) { h /= 2; w /= 2; }
             }
         }
-        bf16_t* X[2] = {(bf16_t*)earena.alloc(max_act * sizeof(bf16_t)), (bf16_t*)earena.alloc(max_act * sizeof(bf16_t))};
+        bf16_t* X[2] = {(bf16_t*)n.arena.alloc(max_act * sizeof(bf16_t)), (bf16_t*)n.arena.alloc(max_act * sizeof(bf16_t))};
         int cur = 0;
-        Tensor h; h.B = Bn; h.H = H; h.W = W; h.C = ecfg.ch; h.ld = ecfg.ch; h.p = X[cur];
+        Tensor h; h.B = Bn; h.H = H; h.W = W; h.C = enc_cfg.ch; h.ld = enc_cfg.ch; h.p = X[cur];
         {
-            const bf16_t* w_ = wb(E + "conv_in.weight"); const float* b_ = wf(E + "conv_in.bias"); bf16_t* dst = h.p; const int co = ecfg.ch;
+            const bf16_t* w_ = wb(E + "conv_in.weight"); const float* b_ = wf(E + "conv_in.bias"); bf16_t* dst = h.p; const int co = enc_cfg.ch;
             push(*cur_plan, [self, w_, b_, dst, Bn, H, W, co](hipStream_t st) {
                 return launch_conv3x3_direct(self->io_enc_img, 1, w_, b_, dst, 0, 0, nullptr, Bn, H, W, 3, co, 1, st); }, 1,
                 2.0 * Bn * H * W * co * 9 * 3, K_CONV_DIRECT, "conv_in 3->" + std::to_string(co));
         }
         auto step = [&](int cout) { cur ^= 1; Tensor o = h; o.C = cout; o.ld = cout; o.p = X[cur]; return o; };
-        for (int lvl = 0; lvl < ecfg.n_levels; ++lvl) {
-            const int bo = ecfg.ch * ecfg.ch_mult[lvl];
+        for (int lvl = 0; lvl < enc_cfg.n_levels; ++lvl) {
+            const int bo = enc_cfg.ch * enc_cfg.ch_mult[lvl];
             const std::string L = E + "down." + std::to_string(lvl);
-            for (int j = 0; j < ecfg.num_res_blocks; ++j) {
+            for (int j = 0; j < enc_cfg.num_res_blocks; ++j) {
                 Tensor o = step(bo);
-                vae_resblock(earena, L + ".block." + std::to_string(j), h, bo, o.p);
+                vae_resblock(n.arena, L + ".block." + std::to_string(j), h, bo, o.p);
                 h = o;
             }
-            if (lvl != ecfg.n_levels - 1) {          // Downsample: F.pad(x, (0,1,0,1)) + 3x3 stride-2 pad-0 conv
+            if (lvl != enc_cfg.n_levels - 1) {          // Downsample: F.pad(x, (0,1,0,1)) + 3x3 stride-2 pad-0 conv
                 Tensor o = step(h.C); o.H = h.H / 2; o.W = h.W / 2;
                 Epi e; e.bias = wf(L + ".downsample.conv.bias");
                 op_conv(h, wb(L + ".downsample.conv.weight"), h.C, 2, 0, e, o.p, o.ld, /*pad_tl=*/0);
                 h = o;
             }
         }
-        { Tensor o = step(h.C); vae_resblock(earena, E + "mid.block_1", h, h.C, o.p); h = o; }
-        { Tensor o = step(h.C); vae_attn(earena, E + "mid.attn_1", h, o.p); h = o; }
-        { Tensor o = step(h.C); vae_resblock(earena, E + "mid.block_2", h, h.C, o.p); h = o; }
+        { Tensor o = step(h.C); vae_resblock(n.arena, E + "mid.block_1", h, h.C, o.p); h = o; }
+        { Tensor o = step(h.C); vae_attn(n, E + "mid.attn_1", h, o.p); h = o; }
+        { Tensor o = step(h.C); vae_resblock(n.arena, E + "mid.block_2", h, h.C, o.p); h = o; }
         {
             Tensor o = step(h.C);
             op_gn(h, wf(E + "norm_out.weight"), wf(E + "norm_out.bias"), 1e-6f, 1, o.p, o.ld);
             const bf16_t* w_ = wb(E + "conv_out.weight"); const float* b_ = wf(E + "conv_out.bias");
             const bf16_t* wq = wb(P + "quant_conv.weight"); const float* bq = wf(P + "quant_conv.bias");
-            const int h2 = h.H, w2 = h.W, cin = h.C, zc = ecfg.z_channels;
+            const int h2 = h.H, w2 = h.W, cin = h.C, zc = enc_cfg.z_channels;
             push(*cur_plan, [self, o, w_, b_, wq, bq, Bn, h2, w2, cin, zc](hipStream_t st) {
                 return launch_vae_enc_tail(o.p, w_, b_, wq, bq, self->io_enc_noise, self->io_enc_scale, self->io_enc_z, self->io_enc_mom,
                                            Bn, h2, w2, cin, zc, st); }, 1,
@@ -2654,30 +2675,17 @@ struct mkd_ctx {
 
     int encode(const float* images, int Bn, int H, int W, float scale_factor, const float* noise, float* z_out, float* moments_out,
                hipStream_t stream) {
-        if (!venc_configured) return mkd_fail(MKD_ERR_STATE, "mkd_encode: encoder not configured (mkd_vae_encoder_configure)");
-        const int f = 1 << (ecfg.n_levels - 1);
+        SideNet& n = net(W_ENC);
+        if (!n.configured) return mkd_fail(MKD_ERR_STATE, "mkd_encode: encoder not configured (mkd_vae_encoder_configure)");
+        const int f = 1 << (enc_cfg.n_levels - 1);
         if (!images || Bn <= 0 || H <= 0 || W <= 0 || H % f || W % f || (!z_out && !moments_out))
             return mkd_fail(MKD_ERR_ARG, "mkd_encode: bad arguments (H, W must be multiples of " + std::to_string(f) + "; z_out or moments_out needed)");
-        if (!venc_finalized) { int rc = venc_finalize(); if (rc) return rc; }
-        if (Bn != venc_B || H != venc_H || W != venc_W) {
-            // two-pass scheme of mkd_decode on the encoder's own arena; split-K / GroupNorm workspaces of SID_AUX are shared (read at run time)
-            const size_t keep_sk = splitk_need, keep_gn = gn_need;
-            splitk_need = 0; gn_need = 0;
-            dry = true; earena.base = nullptr; earena.reset(); plan_venc.clear(); flops_venc = 0;
-            build_venc_plan(Bn, H, W);
-            int rc = ensure((void**)&earena_base, &earena_cap, earena.high + 256); if (rc) return rc;
-            rc = ensure((void**)&splitk_ws[SID_AUX], &splitk_ws_bytes[SID_AUX], std::max(splitk_need, splitk_ws_bytes[SID_AUX])); if (rc) return rc;
-            rc = ensure((void**)&gn_ws[SID_AUX], &gn_ws_bytes[SID_AUX], std::max(gn_need, gn_ws_bytes[SID_AUX])); if (rc) return rc;
-            splitk_need = keep_sk; gn_need = keep_gn;
-            dry = false; earena.base = earena_base; earena.reset(); plan_venc.clear();
-            build_venc_plan(Bn, H, W);
-            splitk_need = keep_sk; gn_need = keep_gn;
-            for (auto& op : plan_venc) flops_venc += op.flops;
-            venc_B = Bn; venc_H = H; venc_W = W;
+        if (!n.finalized) { int rc = venc_finalize(); if (rc) return rc; }
+        if (Bn != n.shape[0] || H != n.shape[1] || W != n.shape[2]) {
+            int rc = side_replan(n, Bn, H, W, [&] { build_venc_plan(Bn, H, W); }); if (rc) return rc;
         }
         io_enc_img = images; io_enc_noise = noise; io_enc_z = z_out; io_enc_mom = moments_out; io_enc_scale = scale_factor;
-        for (auto& op : plan_venc) { int rc = op.fn(stream); if (rc) return rc; }
-        return 0;
+        return side_run(n, stream);
     }
 
     // ---- CLIP text encoder ---------------------------------------------------------------
@@ -2687,15 +2695,15 @@ struct mkd_ctx {
     static std::string clip_prefix() { return "cond_stage_model.transformer.text_model."; }
 
     int clip_configure(const mkd_clip_config* c) {
-        if (clip_configured) return mkd_fail(MKD_ERR_STATE, "mkd_clip_configure: already configured");
+        if (net(W_CLIP).configured) return mkd_fail(MKD_ERR_STATE, "mkd_clip_configure: already configured");
         if (c->vocab_size <= 0 || c->max_positions <= 0 || c->width <= 0 || c->layers <= 0 || c->heads <= 0 || c->intermediate <= 0 ||
             c->width % c->heads || c->width % 8 || c->intermediate % 8)
             return mkd_fail(MKD_ERR_UNSUPPORTED, "mkd_clip_configure: unsupported text-encoder configuration");
         const int dh = c->width / c->heads;
         if (!(dh == 8 || dh == 16 || dh == 32 || dh == 40 || dh == 64 || dh == 80 || dh == 160))
             return mkd_fail(MKD_ERR_UNSUPPORTED, "mkd_clip_configure: head dim " + std::to_string(dh) + " has no attention kernel");
-        ccfg = *c;
-        if (ccfg.ln_eps <= 0.f) ccfg.ln_eps = 1e-5f;
+        txt_cfg = *c;
+        if (txt_cfg.ln_eps <= 0.f) txt_cfg.ln_eps = 1e-5f;
         const std::string P = clip_prefix();
         const int64_t W = c->width, I = c->intermediate;
         add_param(P + "embeddings.token_embedding.weight", {c->vocab_size, W}, 3);
@@ -2711,75 +2719,54 @@ struct mkd_ctx {
             add_param(L + ".layer_norm2.weight", {W}, 3); add_param(L + ".layer_norm2.bias", {W}, 3);
         }
         add_param(P + "final_layer_norm.weight", {W}, 3); add_param(P + "final_layer_norm.bias", {W}, 3);
-        clip_configured = true;
+        net(W_CLIP).configured = true;
         return 0;
     }
 
     int clip_finalize() {
-        if (!clip_configured) return mkd_fail(MKD_ERR_STATE, "text encoder not configured (mkd_clip_configure)");
-        for (auto& kv : params)
-            if (kv.second.which == 3 && !kv.second.loaded) return mkd_fail(MKD_ERR_MISSING, "weight not loaded: " + kv.first);
-        if (clip_finalized) return 0;
-        if (!zero_page) {
-            void* z = nullptr;
-            int rc = dev_alloc(&z, 4096); if (rc) return rc;
-            MKD_HIP_CHECK(hipMemset(z, 0, 4096));
-            zero_page = (bf16_t*)z;
-        }
-        const int W = ccfg.width;
-        for (int l = 0; l < ccfg.layers; ++l) {          // one [3W, W] projection per layer: rows q | k | v
-            const std::string A = clip_prefix() + "encoder.layers." + std::to_string(l) + ".self_attn";
-            if (clip_qkv_w.count(A)) {                   // re-finalize after a weight reload: refresh in place
-                bf16_t* d = clip_qkv_w[A]; float* b = clip_qkv_b[A]; int j = 0;
-                for (const char* n : {".q_proj", ".k_proj", ".v_proj"}) {
-                    MKD_HIP_CHECK(hipMemcpy(d + (size_t)j * W * W, params.at(A + n + ".weight").dev, (size_t)W * W * sizeof(bf16_t), hipMemcpyDeviceToDevice));
-                    MKD_HIP_CHECK(hipMemcpy(b + (size_t)j * W, params.at(A + n + ".bias").dev, W * sizeof(float), hipMemcpyDeviceToDevice));
+        return side_finalize(W_CLIP, "text encoder not configured (mkd_clip_configure)", [this](SideNet& n) {
+            const int W = txt_cfg.width;
+            for (int l = 0; l < txt_cfg.layers; ++l) {          // one [3W, W] projection per layer: rows q | k | v
+                const std::string A = clip_prefix() + "encoder.layers." + std::to_string(l) + ".self_attn";
+                FusedRows& f = n.fused[A];
+                int rc = concat_rows(&f.w, {A + ".q_proj.weight", A + ".k_proj.weight", A + ".v_proj.weight"}); if (rc) return rc;
+                rc = dev_alloc((void**)&f.b, 3 * W * sizeof(float)); if (rc) return rc;
+                int j = 0;
+                for (const char* nm : {".q_proj.bias", ".k_proj.bias", ".v_proj.bias"}) {
+                    MKD_HIP_CHECK(hipMemcpy(f.b + (size_t)j * W, params.at(A + nm).dev, W * sizeof(float), hipMemcpyDeviceToDevice));
                     ++j;
                 }
-                continue;
             }
-            bf16_t* w = nullptr;
-            int rc = concat_rows(&w, {A + ".q_proj.weight", A + ".k_proj.weight", A + ".v_proj.weight"}); if (rc) return rc;
-            void* b = nullptr;
-            rc = dev_alloc(&b, 3 * W * sizeof(float)); if (rc) return rc;
-            int j = 0;
-            for (const char* n : {".q_proj.bias", ".k_proj.bias", ".v_proj.bias"}) {
-                MKD_HIP_CHECK(hipMemcpy((float*)b + (size_t)j * W, params.at(A + n).dev, W * sizeof(float), hipMemcpyDeviceToDevice));
-                ++j;
-            }
-            clip_qkv_w[A] = w; clip_qkv_b[A] = (float*)b;
-        }
-        MKD_HIP_CHECK(hipDeviceSynchronize());
-        clip_finalized = true;
-        clip_B = 0;
-        return 0;
+            return 0;
+        });
     }
 
     void build_clip_plan(int Bn, int T) {
-        cur_plan = &plan_clip; cur_sid = SID_AUX; counting_eps = false;
+        SideNet& n = net(W_CLIP);
+        cur_plan = &n.plan; cur_sid = SID_AUX; counting_eps = false;
         mkd_ctx* self = this;
         const std::string P = clip_prefix();
-        const int W = ccfg.width, I = ccfg.intermediate, heads = ccfg.heads, dh = W / heads, rows = Bn * T;
-        auto buf = [&](int cols) { return (bf16_t*)carena.alloc((size_t)rows * cols * sizeof(bf16_t)); };
+        const int W = txt_cfg.width, I = txt_cfg.intermediate, heads = txt_cfg.heads, dh = W / heads, rows = Bn * T;
+        auto buf = [&](int cols) { return (bf16_t*)n.arena.alloc((size_t)rows * cols * sizeof(bf16_t)); };
         bf16_t* X[2] = {buf(W), buf(W)};
         bf16_t* ln = buf(W); bf16_t* qkv = buf(3 * W); bf16_t* att = buf(W); bf16_t* hid = buf(I);
         {
             const bf16_t* te = wb(P + "embeddings.token_embedding.weight"); const bf16_t* pe = wb(P + "embeddings.position_embedding.weight");
-            bf16_t* dst = X[0]; const int V = ccfg.vocab_size;
+            bf16_t* dst = X[0]; const int V = txt_cfg.vocab_size;
             push(*cur_plan, [self, te, pe, dst, Bn, T, W, V](hipStream_t st) {
                 return launch_clip_embed(self->io_tokens, te, pe, dst, Bn, T, W, V, st); }, 1, 0.0, K_MISC, "clip_embed");
         }
         int cur = 0;
-        const float eps = ccfg.ln_eps;
+        const float eps = txt_cfg.ln_eps;
         auto op_ln_eps = [&](const bf16_t* x, const std::string& n, bf16_t* y) {
             const float* g = wf(n + ".weight"); const float* b = wf(n + ".bias");
             push(*cur_plan, [=](hipStream_t st) { return launch_layernorm(x, g, b, eps, y, rows, W, st); }, 1, 0.0, K_LAYERNORM,
                  "rows=" + std::to_string(rows) + " d=" + std::to_string(W));
         };
-        for (int l = 0; l < ccfg.layers; ++l) {
+        for (int l = 0; l < txt_cfg.layers; ++l) {
             const std::string L = P + "encoder.layers." + std::to_string(l), A = L + ".self_attn";
             op_ln_eps(X[cur], L + ".layer_norm1", ln);
-            { Epi e; e.bias = dry ? nullptr : clip_qkv_b.at(A); op_linear(ln, W, rows, W, dry ? nullptr : clip_qkv_w.at(A), 3 * W, e, qkv, 3 * W); }
+            { const FusedRows& f = n.fused.at(A); Epi e; e.bias = f.b; op_linear(ln, W, rows, W, f.w, 3 * W, e, qkv, 3 * W); }
             {   // causal self-attention over the T padded tokens (CLIP applies no padding mask, only the causal one)
                 const float scale = 1.0f / sqrtf((float)dh);
                 const bf16_t* q = qkv; bf16_t* o = att;
@@ -2801,24 +2788,15 @@ struct mkd_ctx {
     }
 
     int clip_encode(const int32_t* tokens, int Bn, int T, float* out, hipStream_t stream) {
-        if (!clip_finalized) { int rc = clip_finalize(); if (rc) return rc; }
+        SideNet& n = net(W_CLIP);
+        if (!n.finalized) { int rc = clip_finalize(); if (rc) return rc; }
         if (!tokens || !out || Bn <= 0 || T <= 0) return mkd_fail(MKD_ERR_ARG, "mkd_clip_encode: bad arguments");
-        if (T > ccfg.max_positions) return mkd_fail(MKD_ERR_ARG, "mkd_clip_encode: more tokens than position embeddings");
-        if (Bn != clip_B || T != clip_T) {
-            const size_t keep_sk = splitk_need;
-            splitk_need = 0;
-            dry = true; carena.base = nullptr; carena.reset(); plan_clip.clear();
-            build_clip_plan(Bn, T);
-            int rc = ensure((void**)&carena_base, &carena_cap, carena.high + 256); if (rc) return rc;
-            rc = ensure((void**)&splitk_ws[SID_AUX], &splitk_ws_bytes[SID_AUX], std::max(splitk_need, splitk_ws_bytes[SID_AUX])); if (rc) return rc;
-            dry = false; carena.base = carena_base; carena.reset(); plan_clip.clear();
-            build_clip_plan(Bn, T);
-            splitk_need = keep_sk;
-            clip_B = Bn; clip_T = T;
+        if (T > txt_cfg.max_positions) return mkd_fail(MKD_ERR_ARG, "mkd_clip_encode: more tokens than position embeddings");
+        if (Bn != n.shape[0] || T != n.shape[1]) {
+            int rc = side_replan(n, Bn, T, 0, [&] { build_clip_plan(Bn, T); }); if (rc) return rc;
         }
         io_tokens = tokens; io_ctx_out = out;
-        for (auto& op : plan_clip) { int rc = op.fn(stream); if (rc) return rc; }
-        return 0;
+        return side_run(n, stream);
     }
 
     // race detector for the tests: fill every buffer that one mkd_eps produces (activations, temporaries, workspaces) with
@@ -2847,16 +2825,17 @@ struct mkd_ctx {
     }
 
     int64_t device_bytes() const {
-        return weight_bytes + 3 * s_ring_n * (int64_t)sizeof(float) + (int64_t)varena_cap + (int64_t)earena_cap + (int64_t)carena_cap + (int64_t)persist_cap + (int64_t)gstat_cap + [&] { int64_t t = 0; for (int i = 0; i < NA; ++i) t += (int64_t)(temp_cap[i] + splitk_ws_bytes[i] + gn_ws_bytes[i]); return t; }();
+        return weight_bytes + 3 * s_ring_n * (int64_t)sizeof(float) + (int64_t)(side[0].cap + side[1].cap + side[2].cap) + (int64_t)persist_cap + (int64_t)gstat_cap + [&] { int64_t t = 0; for (int i = 0; i < NA; ++i) t += (int64_t)(temp_cap[i] + splitk_ws_bytes[i] + gn_ws_bytes[i]); return t; }();
     }
 
     ~mkd_ctx() {
         for (void* p : owned) hipFree(p);
-        for (void* p : derived) hipFree(p);
+        for (void* p : derived.blocks) hipFree(p);
+        for (SideNet& n : side) {
+            for (void* p : n.derived.blocks) hipFree(p);
+            if (n.base) hipFree(n.base);
+        }
         if (gstat_base) hipFree(gstat_base);
-        if (varena_base) hipFree(varena_base);
-        if (earena_base) hipFree(earena_base);
-        if (carena_base) hipFree(carena_base);
         for (auto& kv : f32_keep) hipFree(kv.second);
         drop_graph();
         drop_temb_table();
@@ -3285,7 +3264,7 @@ int mkd_decode(mkd_ctx* ctx, const float* z, int batch, int h, int w, float scal
     if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
     return ctx->decode(z, batch, h, w, scale_factor, images, (hipStream_t)stream);
 }
-double mkd_decode_flops(const mkd_ctx* ctx) { return ctx ? ctx->flops_vae : 0.0; }
+double mkd_decode_flops(const mkd_ctx* ctx) { return ctx ? ctx->net(W_DEC).flops : 0.0; }
 int mkd_vae_encoder_configure(mkd_ctx* ctx, const mkd_vae_config* cfg) {
     if (!ctx || !cfg) return mkd_fail(MKD_ERR_ARG, "mkd_vae_encoder_configure: null argument");
     return ctx->venc_configure(cfg);
@@ -3296,7 +3275,7 @@ int mkd_encode(mkd_ctx* ctx, const float* images, int batch, int H, int W, float
     if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
     return ctx->encode(images, batch, H, W, scale_factor, noise, z_out, moments_out, (hipStream_t)stream);
 }
-double mkd_encode_flops(const mkd_ctx* ctx) { return ctx ? ctx->flops_venc : 0.0; }
+double mkd_encode_flops(const mkd_ctx* ctx) { return ctx ? ctx->net(W_ENC).flops : 0.0; }
 int mkd_clip_configure(mkd_ctx* ctx, const mkd_clip_config* cfg) {
     if (!ctx || !cfg) return mkd_fail(MKD_ERR_ARG, "mkd_clip_configure: null argument");
     return ctx->clip_configure(cfg);
@@ -3540,25 +3519,21 @@ int mkd_tfm_tail_create(int d, const float* to_out1_w, const float* to_out1_b, c
     if (!out) return mkd_fail(MKD_ERR_ARG, "null out");
     if (!tfm_tail_weight_bytes(d)) return mkd_fail(MKD_ERR_UNSUPPORTED, "tfm_tail: only d = 320 is built");
     mkd_tfm_tail* h = new mkd_tfm_tail; h->d = d;
-    auto dal = [&](size_t bytes, void** o) -> int { MKD_HIP_CHECK(hipMalloc(o, bytes)); h->owned.push_back(*o); return 0; };
-    void *wo1 = nullptr, *wq = nullptr, *sq = nullptr, *bq = nullptr, *wo2 = nullptr, *wg = nullptr, *sg = nullptr, *bg = nullptr, *wm = nullptr, *bm = nullptr;
+    const AllocFn dal = [h](void** o, size_t bytes) -> int { MKD_HIP_CHECK(hipMalloc(o, bytes)); h->owned.push_back(*o); return 0; };
+    void *wo1 = nullptr, *wo2 = nullptr;
+    Folded q2, ffg; bf16_t* wm = nullptr; float* bm = nullptr;
     const size_t dd = (size_t)d * d;
-    int rc = dal(dd * 2, &wo1);
-    if (!rc) rc = dal(dd * 2, &wq); if (!rc) rc = dal(d * 4, &sq); if (!rc) rc = dal(d * 4, &bq);
-    if (!rc) rc = dal(dd * 2, &wo2);
-    if (!rc) rc = dal(8 * dd * 2, &wg); if (!rc) rc = dal(8 * d * 4, &sg); if (!rc) rc = dal(8 * d * 4, &bg);
-    if (!rc) rc = dal(5 * dd * 2, &wm); if (!rc) rc = dal(d * 4, &bm);
-    if (!rc) rc = dal(tfm_tail_weight_bytes(d), (void**)&h->wpk);
-    if (!rc) rc = dal(tfm_tail_vec_bytes(d), (void**)&h->vec);
+    int rc = dal(&wo1, dd * 2);
+    if (!rc) rc = dal(&wo2, dd * 2);
+    if (!rc) rc = dal((void**)&h->wpk, tfm_tail_weight_bytes(d));
+    if (!rc) rc = dal((void**)&h->vec, tfm_tail_vec_bytes(d));
     if (!rc) rc = launch_f32_to_bf16(to_out1_w, (bf16_t*)wo1, (int64_t)dd, 0);
     if (!rc) rc = launch_f32_to_bf16(to_out2_w, (bf16_t*)wo2, (int64_t)dd, 0);
-    if (!rc) rc = launch_fold_layernorm(to_q2_w, norm2_g, norm2_b, nullptr, d, d, (bf16_t*)wq, 0, 1, (float*)sq, (float*)bq, 0);
-    for (int half = 0; half < 2 && !rc; ++half)      // rows [0, 4d) value, [4d, 8d) gate -> row 2 j = value_j, 2 j + 1 = gate_j (as mkd_ctx::finalize)
-        rc = launch_fold_layernorm(ff0_w + (size_t)half * 4 * dd, norm3_g, norm3_b, ff0_b + half * 4 * d, 4 * d, d, (bf16_t*)wg, half, 2, (float*)sg, (float*)bg, 0);
-    if (!rc) rc = launch_merge_ff_out(proj_out_w, ff2_w, ff2_b, proj_out_b, (bf16_t*)wm, (float*)bm, d, 0);
+    if (!rc) rc = fold_ln2_q(to_q2_w, norm2_g, norm2_b, d, dal, &q2);
+    if (!rc) rc = fold_ln3_geglu(ff0_w, ff0_b, norm3_g, norm3_b, d, dal, &ffg);
+    if (!rc) rc = merge_ff_out(proj_out_w, ff2_w, ff2_b, proj_out_b, d, dal, &wm, &bm);
     if (!rc) {
-        TfmTailWeights s{(const bf16_t*)wo1, to_out1_b, (const bf16_t*)wq, (const float*)sq, (const float*)bq, (const bf16_t*)wo2, to_out2_b,
-                         (const bf16_t*)wg, (const float*)sg, (const float*)bg, (const bf16_t*)wm, (const float*)bm};
+        TfmTailWeights s{(const bf16_t*)wo1, to_out1_b, q2.w, q2.s, q2.b, (const bf16_t*)wo2, to_out2_b, ffg.w, ffg.s, ffg.b, wm, bm};
         rc = tfm_tail_pack_weights(d, s, h->wpk, h->vec, 0);
     }
     if (rc) { mkd_tfm_tail_destroy(h); return rc; }
@@ -3597,19 +3572,16 @@ int mkd_tfm_head_create(int d, const float* gn_g, const float* gn_b, const float
     if (!out) return mkd_fail(MKD_ERR_ARG, "null out");
     if (!tfm_head_weight_bytes(d)) return mkd_fail(MKD_ERR_UNSUPPORTED, "tfm_head: only d = 320 is built");
     mkd_tfm_head* h = new mkd_tfm_head; h->d = d;
-    auto dal = [&](size_t bytes, void** o) -> int { MKD_HIP_CHECK(hipMalloc(o, bytes)); h->owned.push_back(*o); return 0; };
-    void *wpi = nullptr, *wq = nullptr, *sq = nullptr, *bq = nullptr;
+    const AllocFn dal = [h](void** o, size_t bytes) -> int { MKD_HIP_CHECK(hipMalloc(o, bytes)); h->owned.push_back(*o); return 0; };
+    void* wpi = nullptr; Folded qkv;
     const size_t dd = (size_t)d * d;
-    int rc = dal(dd * 2, &wpi);
-    if (!rc) rc = dal(3 * dd * 2, &wq); if (!rc) rc = dal(3 * d * 4, &sq); if (!rc) rc = dal(3 * d * 4, &bq);
-    if (!rc) rc = dal(tfm_head_weight_bytes(d), (void**)&h->wpk);
-    if (!rc) rc = dal(tfm_head_vec_bytes(d), (void**)&h->vec);
+    int rc = dal(&wpi, dd * 2);
+    if (!rc) rc = dal((void**)&h->wpk, tfm_head_weight_bytes(d));
+    if (!rc) rc = dal((void**)&h->vec, tfm_head_vec_bytes(d));
     if (!rc) rc = launch_f32_to_bf16(proj_in_w, (bf16_t*)wpi, (int64_t)dd, 0);
-    const float* parts[3] = {to_q_w, to_k_w, to_v_w};
-    for (int j = 0; j < 3 && !rc; ++j)
-        rc = launch_fold_layernorm(parts[j], norm1_g, norm1_b, nullptr, d, d, (bf16_t*)wq, j * d, 1, (float*)sq, (float*)bq, 0);
+    if (!rc) rc = fold_ln1_qkv(to_q_w, to_k_w, to_v_w, norm1_g, norm1_b, d, dal, &qkv);
     if (!rc) {
-        TfmHeadWeights s{gn_g, gn_b, (const bf16_t*)wpi, proj_in_b, (const bf16_t*)wq, (const float*)sq, (const float*)bq};
+        TfmHeadWeights s{gn_g, gn_b, (const bf16_t*)wpi, proj_in_b, qkv.w, qkv.s, qkv.b};
         rc = tfm_head_pack_weights(d, s, h->wpk, h->vec, 0);
     }
     if (rc) { mkd_tfm_head_destroy(h); return rc; }
