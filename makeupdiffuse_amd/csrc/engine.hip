@@ -10,6 +10,7 @@
 //   step-invariant caches (built in mkd_prepare): hint embedding, cross-attention K/V of every
 //                 transformer (context is constant over steps, SURVEY.md finding 5).
 #include "mkd_common.h"
+#include "tfm_fold.h"
 #include "../../include/mkd.h"
 
 #include <cmath>
@@ -214,6 +215,24 @@ struct Op {
     int edge_from = -1, edge_to = -1; bool edge_in_graph = false;       // cross-stream edge ops (op_edge)
 };
 
+// Where the planner emits: the list an op is appended to and what it is stamped with (mkd_ctx::emit; defaults: the caller's stream, no
+// lanes).  Nothing assigns these fields but the methods here, which derive an inner scope's target, and the Emit guard, which installs it
+struct EmitTarget {
+    std::vector<Op>* plan = nullptr;
+    int sid = 0, cap_sid = -1; bool temb = false; // Op::sid (its arena holds the temporaries), Op::cap_sid, Op::temb
+    int lane_main = 0, helper_stream = 1;         // the lane being emitted and the stream its helpers use
+    EmitTarget into(std::vector<Op>* p, int s) const { EmitTarget t = *this; t.plan = p; t.sid = s; return t; }
+    EmitTarget on(int s, int cap) const { EmitTarget t = *this; t.sid = s; t.cap_sid = cap; return t; }
+    EmitTarget lane(int l, int helper) const { EmitTarget t = *this; t.lane_main = l; t.helper_stream = helper; return t; }
+    EmitTarget time_embedding() const { EmitTarget t = *this; t.temb = true; return t; }
+};
+// a changed target for one scope; the previous one comes back on every exit
+struct Emit {
+    EmitTarget& slot; const EmitTarget outer;
+    Emit(EmitTarget& s, const EmitTarget& t) : slot(s), outer(s) { slot = t; }
+    ~Emit() { slot = outer; }
+};
+
 // kinds: [K_GEMM_CONV, K_GEMM_LIN) conv GEMM by tile config, [K_GEMM_LIN, K_GROUPNORM) linear GEMM by tile config (both ranges
 // must hold gemm_num_tile_cfgs() entries: checked in mkd_ctx_create), then the rest
 enum OpKind { K_GEMM_CONV = 0, K_GEMM_LIN = 64, K_GROUPNORM = 128, K_LAYERNORM, K_ATTENTION, K_GEGLU, K_CONV_DIRECT, K_TFM_TAIL, K_MISC, K_COUNT };
@@ -244,8 +263,6 @@ struct SideNet {
     std::map<std::string, FusedRows> fused;               // by attention prefix: [Wq;Wk] (first stage) or q|k|v (CLIP) rows + bias
 };
 
-// LayerNorm folded into its consumer GEMM: W' = W*gamma (bf16), s = rowsum(W'), b' = b + W.beta
-struct Folded { bf16_t* w = nullptr; float* s = nullptr; float* b = nullptr; };
 // Everything finalize() derives for one SpatialTransformer; null: not built for this block
 struct TfmBlock {
     bf16_t* kv_w = nullptr;                                       // [attn2.to_k; attn2.to_v]
@@ -259,57 +276,36 @@ struct TfmBlock {
 // conv2 and the 1x1 skip of a ResBlock as one implicit GEMM: [W_conv2 | W_skip], b_conv2 + b_skip
 struct SkipFold { bf16_t* w = nullptr; float* b = nullptr; };
 
-// The fold recipe of a transformer block, on fp32 device pointers; mkd_ctx::finalize and the stand-alone mkd_tfm_tail / mkd_tfm_head
-// handles both build their weights here
-typedef std::function<int(void**, size_t)> AllocFn;
-static int alloc_folded(const AllocFn& al, size_t n, size_t k, Folded* f) {
-    int rc = al((void**)&f->w, n * k * sizeof(bf16_t));
-    if (!rc) rc = al((void**)&f->s, n * sizeof(float));
-    if (!rc) rc = al((void**)&f->b, n * sizeof(float));
-    return rc;
-}
-// attn1: [to_q; to_k; to_v] . LN1
-static int fold_ln1_qkv(const float* to_q, const float* to_k, const float* to_v, const float* gamma, const float* beta, int d, const AllocFn& al, Folded* f) {
-    int rc = alloc_folded(al, (size_t)3 * d, d, f);
-    const float* parts[3] = {to_q, to_k, to_v};
-    for (int j = 0; j < 3 && !rc; ++j) rc = launch_fold_layernorm(parts[j], gamma, beta, nullptr, d, d, f->w, j * d, 1, f->s, f->b, 0);
-    return rc;
-}
-// attn2.to_q . LN2
-static int fold_ln2_q(const float* to_q, const float* gamma, const float* beta, int d, const AllocFn& al, Folded* f) {
-    int rc = alloc_folded(al, d, d, f);
-    if (!rc) rc = launch_fold_layernorm(to_q, gamma, beta, nullptr, d, d, f->w, 0, 1, f->s, f->b, 0);
-    return rc;
-}
-// ff.net.0.proj [8d][d] . LN3: rows [0,4d) = value, [4d,8d) = gate  ->  row 2j = value_j, row 2j+1 = gate_j
-static int fold_ln3_geglu(const float* w, const float* bias, const float* gamma, const float* beta, int d, const AllocFn& al, Folded* f) {
-    const int inner = 4 * d;
-    int rc = alloc_folded(al, (size_t)2 * inner, d, f);
-    for (int half = 0; half < 2 && !rc; ++half)
-        rc = launch_fold_layernorm(w + (size_t)half * inner * d, gamma, beta, bias + half * inner, inner, d, f->w, half, 2, f->s, f->b, 0);
-    return rc;
-}
-// FF2 and proj_out are both linear with nothing in between: one GEMM over [gg | h2] (K = 5d)
-static int merge_ff_out(const float* proj_out_w, const float* ff2_w, const float* ff2_b, const float* proj_out_b, int d, const AllocFn& al,
-                        bf16_t** wm, float** bm) {
-    int rc = al((void**)wm, (size_t)d * 5 * d * sizeof(bf16_t));
-    if (!rc) rc = al((void**)bm, (size_t)d * sizeof(float));
-    if (!rc) rc = launch_merge_ff_out(proj_out_w, ff2_w, ff2_b, proj_out_b, *wm, *bm, d, 0);
-    return rc;
-}
-
 }  // namespace
 
 struct mkd_ctx {
+    // ---- weights (every data member is declared in this block, every environment switch with its default and its getenv) ----------------------------------------------------------------------------------
     mkd_net_config cfg;
     std::map<std::string, Param> params;
     std::vector<std::string> res_prefixes[2];     // per net, in execution order
     std::vector<std::string> st_prefixes[2];
     bool finalized = false;
+    // fused weights (built in finalize), by transformer prefix
+    std::map<std::string, TfmBlock> tfm;
+    std::map<std::string, SkipFold> skip_folds;
+    std::map<std::string, float*> f32_keep;      // fp32 copies of the weights that get folded (kept for re-finalize)
+    bf16_t* emb_w[2] = {nullptr, nullptr};
+    float* emb_b[2] = {nullptr, nullptr};
+    int emb_total[2] = {0, 0};
+    std::map<std::string, int> emb_off;           // resblock prefix -> column offset in emb projection
+    std::vector<void*> owned;                     // every hipMalloc'd weight block
+    int64_t weight_bytes = 0;
+    bf16_t* zero_page = nullptr;
+    // Weight forms DERIVED at finalize() (concatenated / folded / packed copies) are rebuilt by every finalize after a weight was
+    // loaded: they live in their own list and the previous generation is freed first (a reloaded checkpoint must not leave 1-2 GB of
+    // stale copies behind; no plan can still use them: mkd_load_weight invalidates the prepared plan, a side net's finalize its own)
+    Derived derived;                  // of the UNet pair; a side net's list is in its record
+    Derived* deriving = nullptr;      // the list allocations go to while a finalize runs (null: `owned`)
+    // ---- options: environment switches, read once when the context is created (mkd_ctx_set_option changes ten of them later) ----
     // LayerNorm folded into its consumer GEMMs (row sums emitted by the producer GEMM's epilogue).  Correct and tested,
     // but measured neutral-to-slower in the pipeline (the consumer inherits the producer's write-back wait that the
     // LayerNorm kernel used to absorb), so it is opt-in: MKD_FUSE_LN=1.
-    bool fuse_ln = false;
+    bool fuse_ln = getenv("MKD_FUSE_LN") ? getenv("MKD_FUSE_LN")[0] == '1' : false;
     // LayerNorm "on the fly" (MKD_LN_FLY): the consumer GEMM (attn1 q|k|v, attn2 to_q, the GEGLU projection) runs on the raw rows with
     // the gamma-folded weights and takes the row statistics itself from its A fragments (two extra MFMAs per row fragment and
     // k-step); no LayerNorm kernel, nothing asked of the producer.  Removes 96 launches per evaluation.
@@ -317,6 +313,7 @@ struct mkd_ctx {
     // (images/s): 0: 26.13, 2: 26.53, 3: 26.41, 7: 25.78 - every column tile of a wide consumer (N = 3d, 8d) repeats the statistics
     // MFMAs (+26 % on the M = 8192, N = 2560 GEGLU projection), the d x d to_q GEMM pays 2-7 % for a 5 us LayerNorm launch -> 2.
     int ln_fly = getenv("MKD_LN_FLY") ? atoi(getenv("MKD_LN_FLY")) : 2;
+    bool ln_fly_explicit = getenv("MKD_LN_FLY") != nullptr;      // an explicit MKD_LN_FLY applies to every size
     // Transformers of at most ln_fly_rows rows (lane batch x tokens) take the mask ln_fly_small instead: with few rows the repeated
     // statistics cost nothing and only the removed launch counts.  The default threshold follows the evaluated batch (MKD_LN_FLY_ROWS
     // overrides; tools/exp_lnrows.sh, images/s without / with): batch 1 -> every transformer (6.51 / 6.70), batch 2 -> 256 rows
@@ -330,57 +327,38 @@ struct mkd_ctx {
     // out the same plan takes 6.06 ms: DESIGN.md §4.3).
     bool gn_fused = getenv("MKD_GN_FUSED") ? atoi(getenv("MKD_GN_FUSED")) != 0 : false;
     bool gn_colstats_only = getenv("MKD_GN_FUSED") && atoi(getenv("MKD_GN_FUSED")) == 2;      // experiment: statistics by a stand-alone kernel after every producer
-    Arena gstat; char* gstat_base = nullptr; size_t gstat_cap = 0;
-
-    // fused weights (built in finalize), by transformer prefix
-    std::map<std::string, TfmBlock> tfm;
     bool merge_ffout = getenv("MKD_MERGE_FFOUT") ? atoi(getenv("MKD_MERGE_FFOUT")) != 0 : true;
     // Fused row-local tail of the d = 320 transformer blocks (kernels_tfm.hip): everything after the self-attention product as ONE
     // launch per block instead of 7.  TfmBlock::tail_w / tail_v are built in finalize from the SAME folded tensors the unfused plan
     // uses, tail_kv in the prepare plan.  tfm_tail: 0 off, 1 on where the kernel covers the shape, -1 (default) the shape policy of
     // use_tfm_tail().
     int tfm_tail = getenv("MKD_TFM_TAIL") ? atoi(getenv("MKD_TFM_TAIL")) : -1;
+    // Where the fused tail replaces the 7 launches (tools/bench_tfm_tail.py, profiles/exp_r4_tfm_tail_standalone.txt: 0.49 of the
+    // chain's time at M >= 16384 rows, 0.73 at 8192, 1.08 at 4096 - a workgroup streams the block's 3.3 MB of weights whatever M is).
+    int tfm_tail_min_rows = getenv("MKD_TFM_TAIL_MINROWS") ? atoi(getenv("MKD_TFM_TAIL_MINROWS")) : 4096;
     // ... and the head of the same blocks (GroupNorm apply + proj_in + LayerNorm 1 . q|k|v as one launch behind a GroupNorm statistics
     // launch: 4 launches -> 2): tfm_head 0 off, 1 wherever the tail is fused (default)
     int tfm_head = getenv("MKD_TFM_HEAD") ? atoi(getenv("MKD_TFM_HEAD")) : 1;
     // ResBlocks with a 1x1 skip_connection: conv2 and the skip as ONE implicit GEMM over K = 9 Cout + Cin_block (GemmArgs::A2) where
     // conv2's plan is the gather kernel - built at load time, by ResBlock prefix.  skip_fold: 0 off, 1 on (default)
     int skip_fold = getenv("MKD_SKIP_FOLD") ? atoi(getenv("MKD_SKIP_FOLD")) : 1;
-    std::map<std::string, SkipFold> skip_folds;
-    std::map<std::string, float*> f32_keep;      // fp32 copies of the weights that get folded (kept for re-finalize)
-    bf16_t* emb_w[2] = {nullptr, nullptr};
-    float* emb_b[2] = {nullptr, nullptr};
-    int emb_total[2] = {0, 0};
-    std::map<std::string, int> emb_off;           // resblock prefix -> column offset in emb projection
-    std::vector<void*> owned;                     // every hipMalloc'd weight block
-    int64_t weight_bytes = 0;
-    bf16_t* zero_page = nullptr;
-
-    // prepared state
-    bool prepared = false;
-    int B = 0, h = 0, w = 0;
-    bool has_control = false, only_mid = false;
-    float scales[64];
-    int n_ctrl() const { return (int)encoder_spec().size() + 1; }
-    static constexpr int NS = 4;              // streams / temp arenas: 0 = caller's stream, 1..3 = side streams
-    static constexpr int HELPER_BASE = 16;    // sid HELPER_BASE + k: decoder helper GEMMs on side stream k (arena k); while capturing a
-                                              // graph they run on their lane's own stream (Op::cap_sid)
-    int lane_main = 0, helper_stream = 1;     // the lane being emitted and the stream its helpers use
-    int cur_cap_sid = -1;
-    static constexpr int SID_AUX = 4;         // first-stage decoder / text encoder plans: private workspaces, so that they may run
-                                              // on another stream concurrently with an evaluation (pipelined decode)
-    static constexpr int NA = NS + 1;         // workspace sets: one per stream + SID_AUX
-    Arena persist, temp_arena[NA];
-    int cur_sid = 0;
-    static int arena_of(int sid) { return sid >= HELPER_BASE ? sid - HELPER_BASE : sid; }
-    Arena& TA() { return temp_arena[arena_of(cur_sid)]; }
-    char* persist_base = nullptr; char* temp_base[NA] = {};
-    size_t persist_cap = 0, temp_cap[NA] = {};
-    float* splitk_ws[NA] = {}; size_t splitk_ws_bytes[NA] = {}, splitk_need = 0;
-    float* gn_ws[NA] = {}; size_t gn_ws_bytes[NA] = {}, gn_need = 0;
-    hipStream_t side_streams[NS] = {};        // [0] unused (the caller's stream)
-    hipStream_t stream_of(int sid) const { return (arena_of(sid) == 0 || run_serial) ? run_main : side_streams[arena_of(sid)]; }
-    hipStream_t run_main = nullptr; bool run_serial = false;
+    // Per-launch XCD tile order (GemmArgs::xcd_mode).  In launch order workgroup (m-tile x, n-tile y) runs on XCD (x + gx y) mod 8: an A
+    // tile is pulled through ONE of the 8 non-coherent L2s (all its n-tiles run there), but every XCD walks ALL n-tiles, i.e. each L2
+    // streams the whole weight matrix from the Infinity Cache - and L2 misses are what this loop waits for (19 GB per evaluation,
+    // DESIGN.md 4.5).  Mode 1 gives every XCD one contiguous run of the tile sequence with m-tiles fastest: a weight tile lives in ONE L2,
+    // an A tile in up to gy of them.  So: mode 1 where the weights outweigh the activations, M <= xcd_auto_ratio * N (both operands have
+    // K columns).  MKD_XCD_AUTO_RATIO (0 = launch order everywhere); measured at batch 8, 256x256, ms per evaluation, two rounds
+    // (tools/exp_r3_xcd_auto.sh): off 5.604 / 5.610, ratio 1 5.557 / 5.549, 2 5.547 / 5.548, 4 5.557 / 5.579, 8 5.570 / 5.564, 16 5.637 /
+    // 5.648 (= mode 1 everywhere, MKD_XCD_MODE=1: 5.645); by M alone (N >= 640): M <= 512 5.576 / 5.564, <= 2048 5.565 / 5.544.
+    // Results do not depend on the order (bit-identical: test_xcd_auto_order_changes_no_bit).
+    // round 4: default 1 (was 2): equal at batch 8 / guidance / interpolation, +0.8 % at 512x512 (profiles/exp_r4_bigcfg_switches.txt, exp_r3_xcd_configs.txt)
+    float xcd_auto_ratio = getenv("MKD_XCD_AUTO_RATIO") ? (float)atof(getenv("MKD_XCD_AUTO_RATIO")) : 1.0f;
+    // A split-K GEMM feeds the GroupNorm that reads it straight from its slabs (op_gemm_then_gn).
+    // MKD_GN_SLAB=0 turns it off; MKD_GN_SLAB_MINC: only for at least this many channels.  Measured at batch
+    // 8, 256x256 (ms per evaluation): off 6.12, all ResBlocks 6.14 (40 launches fewer, but with C = 320 / 640 the GroupNorm grid of
+    // 64 / 128 workgroups reads 31 MB of slabs slower than the full-chip reduce kernel), C >= 1280 only 6.10 -> default 1280.
+    bool gn_slab = getenv("MKD_GN_SLAB") ? atoi(getenv("MKD_GN_SLAB")) != 0 : true;
+    int gn_slab_minc = getenv("MKD_GN_SLAB_MINC") ? atoi(getenv("MKD_GN_SLAB_MINC")) : 1280;
     bool dual_stream = getenv("MKD_DUAL_STREAM") ? atoi(getenv("MKD_DUAL_STREAM")) != 0 : true;      // 0: the whole plan on the caller's stream (experiments)
     // measured at batch 8, 256x256 (ms per evaluation): no lanes 6.78, 2 decoder lanes 6.58, 4 decoder lanes 6.89, encoder lanes
     // on top +0.25: the encoder phase already runs two nets side by side, a third and fourth stream only add contention
@@ -391,39 +369,86 @@ struct mkd_ctx {
     int dec_lanes_from = getenv("MKD_DEC_LANES_FROM") ? atoi(getenv("MKD_DEC_LANES_FROM")) : 0;   // deepest blocks as one full-batch chain first
     bool enc_lanes = getenv("MKD_ENC_LANES") ? atoi(getenv("MKD_ENC_LANES")) != 0 : false;
     bool dec_overlap = getenv("MKD_DEC_OVERLAP") ? atoi(getenv("MKD_DEC_OVERLAP")) != 0 : true;
-    bool capturing = false;
-    int plan_epoch = 0;
-    int opt_epoch = 0, opt_epoch_planned = 0;      // bumped by mkd_ctx_set_option: the next mkd_prepare re-plans
+    // MKD_ENC_GROUP=1: ControlNet and UNet encoder + middle block as one chain of 2-problem launches on the caller's stream; 0 (the
+    // default): two chains on two streams.  Measured at batch 8, 256x256, graph replay, latents only (tools/exp_r3_group.sh, two
+    // alternating rounds on one box): two chains 5.64 ms per evaluation (728 launches), grouped 6.19-6.25 ms (576-582 launches) -
+    // 146 launches fewer and 10 % SLOWER.  A grouped kernel takes twice the time of one of its halves (the serial sum of kernel
+    // times barely moves: 10.35 -> 9.4 ms with ~4 us of event overhead per launch in both), so what grouping removes is one
+    // fixed cost per pair - and that is exactly what the second chain already hides: while one chain's kernel drains, dispatches and
+    // fills its first tiles, the other chain's kernel has the CUs (pair = max(L + W, 2 W) on two chains, L + 2 W grouped).
+    bool enc_group = getenv("MKD_ENC_GROUP") ? atoi(getenv("MKD_ENC_GROUP")) != 0 : false;
     int graph_steps = getenv("MKD_GRAPH_STEPS") ? atoi(getenv("MKD_GRAPH_STEPS")) : 5;      // DDIM steps per captured graph
     // Shape policy (round 4, profiles/exp_r4_bigcfg_switches.txt): a GroupNorm over >= gn_2k_min_hw pixels per sample runs as the two
     // full-chip launches (statistics, apply) instead of the single launch that keeps a (sample, group chunk) slab in registers on
     // 32-128 workgroups: at 64x64 latents (512x512 images) the single launch holds too few CUs for too long (16.51 -> 16.26 ms per
     // evaluation); at 32x32 it is the other way round (8.36 -> 8.63 ms with guidance), so the rule is by tensor size.
     int gn_2k_min_hw = getenv("MKD_GN_2K_MINHW") ? atoi(getenv("MKD_GN_2K_MINHW")) : 4096;
+    // The timesteps of mkd_sample are a host table (reference diffmk/cddim.py:83-95: ts = full((b,), step)), every sample of a step
+    // shares one, and the embedding chain (sinusoid -> 2 linear layers -> every ResBlock's emb_layers projection: 75 MB of weights
+    // for 8 rows) depends on nothing else.  So one pass computes [n_steps, emb_total] per net before the loop, and a step only copies
+    // its row into the [B, emb_total] buffers the ResBlock epilogues read (step_setup_kernel / temb_select_kernel): 8-10 dependent
+    // launches leave every step.  MKD_TEMB_TABLE=0: per-step chain as in mkd_eps.
+    bool temb_table = getenv("MKD_TEMB_TABLE") ? atoi(getenv("MKD_TEMB_TABLE")) != 0 : true;
+    // Graph mode 2 (MKD_GRAPH_MODE=2; default 1 = one captured graph per step): one step = LINEAR graphs, one per (stream, stretch
+    // between two cross-stream edges), launched on their own streams and ordered by events.  A captured graph with two BRANCHES is
+    // replayed with its branches serialised node by node (tools/micro/launch_floor.hip: 3.2 us per pair of empty nodes, 5.3-5.9 us
+    // per pair of small kernels; tools/micro/two_phase.hip: 1836 us for a 720-launch step of small kernels), two linear graphs on two
+    // streams run side by side (1.7 / 1.9-3.4 us per pair; 725 us per step).  In the real evaluation the launch floor does drop
+    // (every kernel empty: 1.65 -> 0.93 ms) but the GroupNorm / LayerNorm / attention kernels no longer hide in the dispatcher's
+    // gaps (0.09 -> 1.0 ms) and the GEMM work is 4.0 ms either way: 5.96 vs 5.75 ms per evaluation at batch 8, 3.12 vs 2.96 at
+    // batch 1 - measured, kept as a switch, off.
+    int graph_mode = getenv("MKD_GRAPH_MODE") ? atoi(getenv("MKD_GRAPH_MODE")) : 1;
+    // ---- prepared state ---------------------------------------------------------------------------
+    bool prepared = false;
+    int B = 0, h = 0, w = 0;
+    bool has_control = false, only_mid = false;
+    float scales[64];
+    int n_ctrl() const { return (int)encoder_spec().size() + 1; }
+    static constexpr int NS = 4;              // streams / temp arenas: 0 = caller's stream, 1..3 = side streams
+    static constexpr int HELPER_BASE = 16;    // sid HELPER_BASE + k: decoder helper GEMMs on side stream k (arena k); while capturing a
+                                              // graph they run on their lane's own stream (Op::cap_sid)
+    static constexpr int SID_AUX = 4;         // first-stage decoder / text encoder plans: private workspaces, so that they may run
+                                              // on another stream concurrently with an evaluation (pipelined decode)
+    static constexpr int NA = NS + 1;         // workspace sets: one per stream + SID_AUX
+    Arena persist, temp_arena[NA];
+    Arena gstat; char* gstat_base = nullptr; size_t gstat_cap = 0;
+    static int arena_of(int sid) { return sid >= HELPER_BASE ? sid - HELPER_BASE : sid; }
+    Arena& TA() { return temp_arena[arena_of(emit.sid)]; }
+    char* persist_base = nullptr; char* temp_base[NA] = {};
+    size_t persist_cap = 0, temp_cap[NA] = {};
+    float* splitk_ws[NA] = {}; size_t splitk_ws_bytes[NA] = {}, splitk_need = 0;
+    float* gn_ws[NA] = {}; size_t gn_ws_bytes[NA] = {}, gn_need = 0;
+    hipStream_t side_streams[NS] = {};        // [0] unused (the caller's stream)
+    hipStream_t stream_of(int sid) const { return (arena_of(sid) == 0 || run_serial) ? run_main : side_streams[arena_of(sid)]; }
+    hipStream_t run_main = nullptr; bool run_serial = false;
+    bool capturing = false;
+    int plan_epoch = 0;
+    int opt_epoch = 0, opt_epoch_planned = 0;      // bumped by mkd_ctx_set_option: the next mkd_prepare re-plans
     size_t persist_eps_begin = 0;
     std::vector<hipEvent_t> aux_ev; int aux_used = 0;        // cross-stream edges inside the decoder (re-used across plan rebuilds)
     std::vector<Op> plan_prepare, plan_eps;
-    double flops_eps = 0; int launches_eps = 0;
-    bool dry = false; bool counting_eps = false;
+    double flops_eps = 0; int launches_eps = 0, launches_temb = 0;
     std::map<std::string, Tensor> kv_cache;       // transformer prefix -> [B*77, 2d]
     Tensor hint_emb;
     bf16_t* ctx_bf16 = nullptr;
     const float* in_hints[8] = {}; const float* in_context = nullptr;      // [0]: the hint; [1]: interpolation's second; [0..R): region transfer
     const float* in_alpha = nullptr; bool has_interp = false;   // makeup interpolation (build-defined)
     const float* in_weights = nullptr; int n_region_hints = 0;  // region-wise transfer (build-defined): weights [B, R, h, w], R hints (0: off)
-    // ---- side networks: first-stage decoder (AutoencoderKL.decode; SURVEY.md §8f rank 1), CLIP text encoder, first-stage encoder
-    // (AutoencoderKL.encode + get_first_stage_encoding, opt-in) ----
-    SideNet side[3];
-    SideNet& net(int which) { return side[which - W_DEC]; }
-    const SideNet& net(int which) const { return side[which - W_DEC]; }
-    mkd_vae_config dec_cfg{}, enc_cfg{}; mkd_clip_config txt_cfg{};
-    const int32_t* io_tokens = nullptr; float* io_ctx_out = nullptr;
-    const float* io_z = nullptr; float* io_img = nullptr; float io_inv_scale = 1.f;
-    const float* io_enc_img = nullptr; const float* io_enc_noise = nullptr; float* io_enc_z = nullptr; float* io_enc_mom = nullptr;
-    float io_enc_scale = 1.f;
     // per-call io
     const float* io_x = nullptr; const int64_t* io_t = nullptr; float* io_out = nullptr;
-    // sampler buffers
+    // ---- planner scratch --------------------------------------------------------------------------
+    bool dry = false;
+    EmitTarget emit;                  // where push() appends; changed for a scope by an Emit guard only
+    // ---- time-embedding table of a whole sampling call ----------------------------------------------
+    bool temb_skip = false;                       // set while a sampling loop runs from the table: the plan's own chain is left out
+    float* temb_proj[2] = {nullptr, nullptr};     // [B, emb_total] per net (persistent arena)
+    float* temb_tab[2] = {nullptr, nullptr};      // [steps, emb_total] per net
+    int64_t* temb_t = nullptr;                    // device copy of the call's timesteps
+    int temb_steps = 0, temb_gen = -1, temb_cap = 0;
+    bf16_t* temb_s[2][3] = {};                    // sinusoid and the two hidden layers of the table pass, [temb_cap, .]
+    std::vector<void*> temb_owned;
+    std::vector<Op> plan_temb_tab;
+    // ---- sampler buffers --------------------------------------------------------------------------
     float* s_xa = nullptr; float* s_xb = nullptr; float* s_xin = nullptr; float* s_eps = nullptr;
     int64_t* s_t = nullptr;
     StepState* s_state = nullptr; StepState* h_state = nullptr;
@@ -441,19 +466,21 @@ struct mkd_ctx {
         bool operator==(const StepKey& o) const { return gen == o.gen && cfg == o.cfg && temb == o.temb && batch == o.batch && solver == o.solver && rescale == o.rescale && scale == o.scale && rows == o.rows; }
     };
     hipGraphExec_t step_graph = nullptr; StepKey step_key; int plan_generation = 0;
-    // Graph mode 2 (MKD_GRAPH_MODE=2; default 1 = one captured graph per step): one step = LINEAR graphs, one per (stream, stretch
-    // between two cross-stream edges), launched on their own streams and ordered by events.  A captured graph with two BRANCHES is
-    // replayed with its branches serialised node by node (tools/micro/launch_floor.hip: 3.2 us per pair of empty nodes, 5.3-5.9 us
-    // per pair of small kernels; tools/micro/two_phase.hip: 1836 us for a 720-launch step of small kernels), two linear graphs on two
-    // streams run side by side (1.7 / 1.9-3.4 us per pair; 725 us per step).  In the real evaluation the launch floor does drop
-    // (every kernel empty: 1.65 -> 0.93 ms) but the GroupNorm / LayerNorm / attention kernels no longer hide in the dispatcher's
-    // gaps (0.09 -> 1.0 ms) and the GEMM work is 4.0 ms either way: 5.96 vs 5.75 ms per evaluation at batch 8, 3.12 vs 2.96 at
-    // batch 1 - measured, kept as a switch, off.
+    // the linear graphs of graph mode 2 (graph_mode above)
     struct SegAction { int type; int sid; int idx; };      // type 0: launch seg_graphs[idx] / seg_eager[idx] on stream sid; 1: record event idx on sid; 2: sid waits for event idx
     struct Segment { hipGraphExec_t graph = nullptr; std::vector<OpFn> eager; };
     std::vector<Segment> segs; std::vector<SegAction> seg_actions; std::vector<hipEvent_t> seg_events;
     StepKey seg_key;
-    int graph_mode = getenv("MKD_GRAPH_MODE") ? atoi(getenv("MKD_GRAPH_MODE")) : 1;
+    // ---- side networks: first-stage decoder (AutoencoderKL.decode; SURVEY.md §8f rank 1), CLIP text encoder, first-stage encoder
+    // (AutoencoderKL.encode + get_first_stage_encoding, opt-in) ----
+    SideNet side[3];
+    SideNet& net(int which) { return side[which - W_DEC]; }
+    const SideNet& net(int which) const { return side[which - W_DEC]; }
+    mkd_vae_config dec_cfg{}, enc_cfg{}; mkd_clip_config txt_cfg{};
+    const int32_t* io_tokens = nullptr; float* io_ctx_out = nullptr;
+    const float* io_z = nullptr; float* io_img = nullptr; float io_inv_scale = 1.f;
+    const float* io_enc_img = nullptr; const float* io_enc_noise = nullptr; float* io_enc_z = nullptr; float* io_enc_mom = nullptr;
+    float io_enc_scale = 1.f;
 
     // ---------------------------------------------------------------------------------------------
     int ctx_len() const { return 77; }
@@ -601,11 +628,6 @@ struct mkd_ctx {
     }
 
     // ---- weights ----------------------------------------------------------------------------------
-    // Weight forms DERIVED at finalize() (concatenated / folded / packed copies) are rebuilt by every finalize after a weight was
-    // loaded: they live in their own list and the previous generation is freed first (a reloaded checkpoint must not leave 1-2 GB of
-    // stale copies behind; no plan can still use them: mkd_load_weight invalidates the prepared plan, a side net's finalize its own)
-    Derived derived;                  // of the UNet pair; a side net's list is in its record
-    Derived* deriving = nullptr;      // the list allocations go to while a finalize runs (null: `owned`)
     int dev_alloc(void** out, size_t bytes) {
         MKD_HIP_CHECK(hipMalloc(out, bytes ? bytes : 16));
         if (deriving) { deriving->blocks.push_back(*out); deriving->bytes += (int64_t)bytes; } else owned.push_back(*out);
@@ -813,17 +835,14 @@ struct mkd_ctx {
     }
 
     // ---- plan building ------------------------------------------------------------------------------
-    void push(std::vector<Op>& plan, OpFn f, int launches, double flops, int kind = K_MISC, const std::string& label = "") {
-        if (counting_eps) { launches_eps += launches; flops_eps += flops; }
+    void push(OpFn f, int launches, double flops, int kind = K_MISC, const std::string& label = "") {
         if (!dry) {
-            Op o; o.fn = std::move(f); o.kind = kind; o.flops = flops; o.launches = launches; o.label = label; o.sid = cur_sid; o.cap_sid = cur_cap_sid;
-            o.temb = cur_temb;
-            plan.push_back(std::move(o));
+            Op o; o.fn = std::move(f); o.kind = kind; o.flops = flops; o.launches = launches; o.label = label; o.sid = emit.sid; o.cap_sid = emit.cap_sid;
+            o.temb = emit.temb;
+            emit.plan->push_back(std::move(o));
         }
     }
-    std::vector<Op>* cur_plan = nullptr;
-    bool cur_temb = false;
-    OpDesc& last_desc() { static OpDesc dummy; return dry ? dummy : cur_plan->back().d; }      // descriptor of the op just pushed
+    OpDesc& last_desc() { static OpDesc dummy; return dry ? dummy : emit.plan->back().d; }      // descriptor of the op just pushed
 
     Tensor talloc(Arena& a, int B_, int H_, int W_, int C_) {
         Tensor t; t.B = B_; t.H = H_; t.W = W_; t.C = C_; t.ld = C_;
@@ -831,17 +850,6 @@ struct mkd_ctx {
         return t;
     }
 
-    // Per-launch XCD tile order (GemmArgs::xcd_mode).  In launch order workgroup (m-tile x, n-tile y) runs on XCD (x + gx y) mod 8: an A
-    // tile is pulled through ONE of the 8 non-coherent L2s (all its n-tiles run there), but every XCD walks ALL n-tiles, i.e. each L2
-    // streams the whole weight matrix from the Infinity Cache - and L2 misses are what this loop waits for (19 GB per evaluation,
-    // DESIGN.md 4.5).  Mode 1 gives every XCD one contiguous run of the tile sequence with m-tiles fastest: a weight tile lives in ONE L2,
-    // an A tile in up to gy of them.  So: mode 1 where the weights outweigh the activations, M <= xcd_auto_ratio * N (both operands have
-    // K columns).  MKD_XCD_AUTO_RATIO (0 = launch order everywhere); measured at batch 8, 256x256, ms per evaluation, two rounds
-    // (tools/exp_r3_xcd_auto.sh): off 5.604 / 5.610, ratio 1 5.557 / 5.549, 2 5.547 / 5.548, 4 5.557 / 5.579, 8 5.570 / 5.564, 16 5.637 /
-    // 5.648 (= mode 1 everywhere, MKD_XCD_MODE=1: 5.645); by M alone (N >= 640): M <= 512 5.576 / 5.564, <= 2048 5.565 / 5.544.
-    // Results do not depend on the order (bit-identical: test_xcd_auto_order_changes_no_bit).
-    // round 4: default 1 (was 2): equal at batch 8 / guidance / interpolation, +0.8 % at 512x512 (profiles/exp_r4_bigcfg_switches.txt, exp_r3_xcd_configs.txt)
-    float xcd_auto_ratio = getenv("MKD_XCD_AUTO_RATIO") ? (float)atof(getenv("MKD_XCD_AUTO_RATIO")) : 1.0f;
     void op_gemm(GemmArgs a, int force_splitk = 0) {
         a.zero = zero_page;
         a.splitk = force_splitk;
@@ -858,8 +866,8 @@ struct mkd_ctx {
         const size_t need = gemm_ws_bytes(a.M, a.N, s);
         if (need > splitk_need) splitk_need = need;
         mkd_ctx* self = this;
-        const int sid = cur_sid;
-        push(*cur_plan, [self, a, sid](hipStream_t st) {
+        const int sid = emit.sid;
+        push([self, a, sid](hipStream_t st) {
                  GemmArgs b = a; b.ws = self->splitk_ws[arena_of(sid)]; b.ws_bytes = self->splitk_ws_bytes[arena_of(sid)];
                  return launch_gemm(b, st); },
              s > 1 ? 2 : 1, 2.0 * a.M * a.N * a.K, (a.conv ? K_GEMM_CONV : K_GEMM_LIN) + cfg_i,
@@ -898,36 +906,31 @@ struct mkd_ctx {
     // A split-K GEMM whose output is read by a GroupNorm: instead of [GEMM -> partial slabs][reduce + epilogue -> tensor][GroupNorm]
     // emit [GEMM -> partial slabs][one kernel: reduce + epilogue + GroupNorm (+ the raw tensor when `raw` says it is needed)].
     // Returns false (nothing emitted) when the GEMM of this shape is not split or the geometry does not fit: the caller then
-    // emits the separate ops.  MKD_GN_SLAB=0 turns it off; MKD_GN_SLAB_MINC: only for at least this many channels.  Measured at batch
-    // 8, 256x256 (ms per evaluation): off 6.12, all ResBlocks 6.14 (40 launches fewer, but with C = 320 / 640 the GroupNorm grid of
-    // 64 / 128 workgroups reads 31 MB of slabs slower than the full-chip reduce kernel), C >= 1280 only 6.10 -> default 1280.
-    bool gn_slab = getenv("MKD_GN_SLAB") ? atoi(getenv("MKD_GN_SLAB")) != 0 : true;
-    int gn_slab_minc = getenv("MKD_GN_SLAB_MINC") ? atoi(getenv("MKD_GN_SLAB_MINC")) : 1280;
+    // emits the separate ops.  Switches and measurement: gn_slab, gn_slab_minc.
     bool op_gemm_then_gn(GemmArgs a, bool raw, int nb, int hw, const float* gamma, const float* beta, float eps, int silu, bf16_t* y, int ld_y) {
         if (!gn_slab || a.gn_stat || a.N < gn_slab_minc || !gn_from_slabs_supported(nb, hw, a.N) || a.M != nb * hw) return false;
         a.zero = zero_page; a.splitk = 0;
         int cfg_i = 0, sk = 1;
         if (gemm_resolve(a, &cfg_i, &sk) || sk < 2) return false;
         a.defer_epilogue = 1; a.expect_splitk = sk;   // (launch_gemm fails if it would resolve to another slab count than the one planned here)
-        op_gemm(a);                                   // (counts 2 launches for a split GEMM: corrected below)
-        if (counting_eps) --launches_eps;
-        if (!dry) cur_plan->back().launches = 1;
+        op_gemm(a);                                   // (counts 2 launches for a split GEMM: its reduce runs in the kernel below)
+        if (!dry) emit.plan->back().launches = 1;
         mkd_ctx* self = this;
-        const int sid = cur_sid;
-        push(*cur_plan, [self, a, sid, sk, raw, nb, hw, gamma, beta, eps, silu, y, ld_y](hipStream_t st) {
+        const int sid = emit.sid;
+        push([self, a, sid, sk, raw, nb, hw, gamma, beta, eps, silu, y, ld_y](hipStream_t st) {
             GemmArgs b = a; b.ws = self->splitk_ws[arena_of(sid)]; b.splitk = sk;
             if (!raw) b.C = nullptr;
             return launch_gn_from_slabs(b, gamma, beta, eps, silu, y, ld_y, nb, hw, st);
         }, 1, 0.0, K_GROUPNORM, "slab B=" + std::to_string(nb) + " HW=" + std::to_string(hw) + " C=" + std::to_string(a.N) + " splitk=" + std::to_string(sk));
         OpDesc& d = last_desc(); d.type = D_GN_SLAB; d.sid = sid; d.gemm = a; d.sk = sk; d.raw = raw ? 1 : 0; d.nio = NormIo{nullptr, y, gamma, beta};
         d.eps = eps; d.silu = silu; d.ld_out = ld_y; d.nb = nb; d.hw = hw;
-        if (!dry) cur_plan->back().bytes = (double)a.M * a.N * (sizeof(float) * sk + sizeof(bf16_t) * (raw ? 2 : 1));      // sk fp32 slabs in, bf16 out
+        if (!dry) emit.plan->back().bytes = (double)a.M * a.N * (sizeof(float) * sk + sizeof(bf16_t) * (raw ? 2 : 1));      // sk fp32 slabs in, bf16 out
         return true;
     }
     void op_gn(const Tensor& in, const float* gamma, const float* beta, float eps, int silu, bf16_t* out, int ld_out) {
         if (in.gst) {          // statistics were accumulated by the producers of `in`: element-wise apply
             Tensor t = in;
-            push(*cur_plan, [t, gamma, beta, eps, silu, out, ld_out](hipStream_t st) {
+            push([t, gamma, beta, eps, silu, out, ld_out](hipStream_t st) {
                 return launch_gn_apply_stats(t.p, t.ld, gamma, beta, eps, silu, out, ld_out, t.B, t.H * t.W, t.C, t.gst, st);
             }, 1, 0.0, K_GROUPNORM, "apply B=" + std::to_string(in.B) + " HW=" + std::to_string(in.H * in.W) + " C=" + std::to_string(in.C));
             return;
@@ -936,34 +939,34 @@ struct mkd_ctx {
         if (need > gn_need) gn_need = need;
         mkd_ctx* self = this;
         Tensor t = in;
-        const int sid = cur_sid;
-        push(*cur_plan, [self, t, gamma, beta, eps, silu, out, ld_out, sid](hipStream_t st) {
+        const int sid = emit.sid;
+        push([self, t, gamma, beta, eps, silu, out, ld_out, sid](hipStream_t st) {
             return launch_groupnorm(t.p, t.ld, gamma, beta, eps, silu, out, ld_out, t.B, t.H * t.W, t.C, 32, self->gn_ws[arena_of(sid)], st, nullptr, self->gn_2k_min_hw);
         }, 1, 0.0, K_GROUPNORM, "B=" + std::to_string(in.B) + " HW=" + std::to_string(in.H * in.W) + " C=" + std::to_string(in.C));
         OpDesc& d = last_desc(); d.type = D_GN; d.sid = sid; d.nio = NormIo{in.p, out, gamma, beta}; d.eps = eps; d.silu = silu;
         d.ld_in = in.ld; d.ld_out = ld_out; d.nb = in.B; d.hw = in.H * in.W; d.C = in.C;
-        if (!dry) cur_plan->back().bytes = 2.0 * sizeof(bf16_t) * in.B * in.H * in.W * (double)in.C;          // one read + one write of the tensor
+        if (!dry) emit.plan->back().bytes = 2.0 * sizeof(bf16_t) * in.B * in.H * in.W * (double)in.C;          // one read + one write of the tensor
     }
     void op_ln(const bf16_t* x, const float* gamma, const float* beta, bf16_t* y, int rows, int d, int ldx = 0) {
-        push(*cur_plan, [=](hipStream_t st) { return launch_layernorm(x, gamma, beta, 1e-5f, y, rows, d, st, ldx); }, 1, 0.0, K_LAYERNORM,
+        push([=](hipStream_t st) { return launch_layernorm(x, gamma, beta, 1e-5f, y, rows, d, st, ldx); }, 1, 0.0, K_LAYERNORM,
              "rows=" + std::to_string(rows) + " d=" + std::to_string(d));
         OpDesc& ds = last_desc(); ds.type = D_LN; ds.nio = NormIo{x, y, gamma, beta}; ds.eps = 1e-5f; ds.nb = rows; ds.C = d; ds.ld_in = ldx;
-        if (!dry) cur_plan->back().bytes = 2.0 * sizeof(bf16_t) * rows * (double)d;
+        if (!dry) emit.plan->back().bytes = 2.0 * sizeof(bf16_t) * rows * (double)d;
     }
     void op_attn(const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* v, int ldv, bf16_t* o, int ldo,
                  int B_, int Tq, int Tk, int heads, int dh) {
         const float scale = 1.0f / sqrtf((float)dh);
-        push(*cur_plan, [=](hipStream_t st) { return launch_attention(q, ldq, k, ldk, v, ldv, o, ldo, B_, Tq, Tk, heads, dh, scale, st); },
+        push([=](hipStream_t st) { return launch_attention(q, ldq, k, ldk, v, ldv, o, ldo, B_, Tq, Tk, heads, dh, scale, st); },
              1, 4.0 * B_ * heads * (double)Tq * Tk * dh, K_ATTENTION,
              "B=" + std::to_string(B_) + " Tq=" + std::to_string(Tq) + " Tk=" + std::to_string(Tk) + " heads=" + std::to_string(heads) + " dh=" + std::to_string(dh));
         OpDesc& d = last_desc(); d.type = D_ATTN; d.aio = AttnIo{q, k, v, o}; d.ldq = ldq; d.ldk = ldk; d.ldv = ldv; d.ldo = ldo; d.nb = B_; d.Tq = Tq; d.Tk = Tk;
         d.heads = heads; d.dh = dh;
     }
     void op_geglu(const bf16_t* x, bf16_t* y, int rows, int inner) {
-        push(*cur_plan, [=](hipStream_t st) { return launch_geglu(x, y, rows, inner, st); }, 1, 0.0, K_GEGLU, "rows=" + std::to_string(rows) + " inner=" + std::to_string(inner));
+        push([=](hipStream_t st) { return launch_geglu(x, y, rows, inner, st); }, 1, 0.0, K_GEGLU, "rows=" + std::to_string(rows) + " inner=" + std::to_string(inner));
     }
     void op_copy(const bf16_t* src, int ld_src, bf16_t* dst, int ld_dst, int rows, int cols) {
-        push(*cur_plan, [=](hipStream_t st) { return launch_copy_strided(src, ld_src, dst, ld_dst, rows, cols, st); }, 1, 0.0);
+        push([=](hipStream_t st) { return launch_copy_strided(src, ld_src, dst, ld_dst, rows, cols, st); }, 1, 0.0);
     }
 
     // ResBlock (App. A.2).  x may be a concat buffer (ld == C).  Writes [rows, cout] at (out, ldo).
@@ -997,11 +1000,10 @@ struct mkd_ctx {
         if (fold) side_skip = false;
         if (x.C != cout && side_skip) {
             t4 = talloc(TA(), x.B, x.H, x.W, cout);
-            op_edge(lane_main, helper_stream);           // helper stream waits for the block input (written on the lane's stream)
-            cur_sid = HELPER_BASE + helper_stream; cur_cap_sid = lane_main;
+            op_edge(emit.lane_main, emit.helper_stream);           // helper stream waits for the block input (written on the lane's stream)
+            Emit helper(emit, emit.on(HELPER_BASE + emit.helper_stream, emit.lane_main));
             Epi es; es.bias = wf(p + ".skip_connection.bias");
             op_linear(x.p, x.ld, rows, x.C, wb(p + ".skip_connection.weight"), cout, es, t4.p, t4.ld);
-            cur_sid = lane_main; cur_cap_sid = -1;
         }
         Tensor t1 = talloc(TA(), x.B, x.H, x.W, x.C);
         op_gn(x, wf(p + ".in_layers.0.weight"), wf(p + ".in_layers.0.bias"), 1e-5f, 1, t1.p, t1.ld);
@@ -1023,7 +1025,7 @@ struct mkd_ctx {
         }
         Epi e2; e2.bias = wf(p + ".out_layers.3.bias"); e2.gn = go;
         if (x.C != cout && side_skip) {
-            op_edge(helper_stream, lane_main);           // the lane waits for the skip GEMM
+            op_edge(emit.helper_stream, emit.lane_main);           // the lane waits for the skip GEMM
             e2.R = t4.p; e2.ldr = t4.ld;
         } else if (x.C != cout && no_skip) {
             e2.R = t3.p; e2.ldr = t3.ld;
@@ -1039,19 +1041,17 @@ struct mkd_ctx {
         TA().release(mk);
     }
 
-    // Where the fused tail replaces the 7 launches (tools/bench_tfm_tail.py, profiles/exp_r4_tfm_tail_standalone.txt: 0.49 of the
-    // chain's time at M >= 16384 rows, 0.73 at 8192, 1.08 at 4096 - a workgroup streams the block's 3.3 MB of weights whatever M is).
+    // the shape policy of the fused tail (measurement at tfm_tail_min_rows)
     bool use_tfm_tail(const TfmBlock& tb, int d, int M, int T, bool producer_ln, const GnOut& go) const {
         if (tfm_tail == 0 || producer_ln || go.gst || !tb.tail_w || !tb.tail_kv) return false;
         if (!tfm_tail_supported(d, cfg.num_heads, T, ctx_len()) || M % 64) return false;
         return tfm_tail > 0 || M >= tfm_tail_min_rows;
     }
-    int tfm_tail_min_rows = getenv("MKD_TFM_TAIL_MINROWS") ? atoi(getenv("MKD_TFM_TAIL_MINROWS")) : 4096;
     void emit_tfm_tail(const TfmBlock& tb, int d, int M, int T, const bf16_t* a1, const bf16_t* h0, const Tensor& x, bf16_t* out, int ldo, int b0) {
         const bf16_t* wpk = tb.tail_w; const float* vec = tb.tail_v;
         const bf16_t* kvp = tb.tail_kv + (size_t)b0 * (tfm_tail_kv_bytes(d, 1) / sizeof(bf16_t));
         const bf16_t* xin = x.p; const int ldx = x.ld, Tk = ctx_len();
-        push(*cur_plan, [=](hipStream_t st) { return launch_tfm_tail(d, wpk, vec, a1, d, h0, d, xin, ldx, kvp, out, ldo, M, T, Tk, st); },
+        push([=](hipStream_t st) { return launch_tfm_tail(d, wpk, vec, a1, d, h0, d, xin, ldx, kvp, out, ldo, M, T, Tk, st); },
              1, tfm_tail_flops(d, M, Tk), K_TFM_TAIL, "M=" + std::to_string(M) + " d=" + std::to_string(d) + " T=" + std::to_string(T));
     }
     // SpatialTransformer, depth 1 (App. A.2). x: [B,H,W,d] contiguous or strided. Writes at (out, ldo).
@@ -1070,10 +1070,10 @@ struct mkd_ctx {
             const size_t need = groupnorm_partials_bytes(x.B, T, 32);
             if (need > gn_need) gn_need = need;
             mkd_ctx* self = this;
-            const int sid = cur_sid;
+            const int sid = emit.sid;
             const Tensor xt = x;
             const bf16_t* hwp = tb.head_w; const float* hvp = tb.head_v;
-            push(*cur_plan, [self, xt, T, d, sid, hwp, hvp, h0f, qkvf, M](hipStream_t st) {
+            push([self, xt, T, d, sid, hwp, hvp, h0f, qkvf, M](hipStream_t st) {
                 int nch = 0;
                 int rc = launch_gn_stats(xt.p, xt.ld, xt.B, T, d, 32, self->gn_ws[arena_of(sid)], st, &nch);
                 if (rc) return rc;
@@ -1094,7 +1094,7 @@ struct mkd_ctx {
         const int slots = gemm_stat_slots(M, d, d);
         const bool fo = fuse_ln && slots <= 20;                  // producer-statistics form, all three norms
         const int fly_rows = ln_fly_rows >= 0 ? ln_fly_rows : (B <= 1 ? 1 << 30 : (B == 2 ? 256 : 128));
-        const int fly = getenv("MKD_LN_FLY") ? ln_fly : (M <= fly_rows ? ln_fly_small : ln_fly);      // an explicit MKD_LN_FLY applies to every size
+        const int fly = ln_fly_explicit ? ln_fly : (M <= fly_rows ? ln_fly_small : ln_fly);
         const bool fy1 = !fuse_ln && (fly & 1), fy2 = !fuse_ln && (fly & 2), fy3 = !fuse_ln && (fly & 4);
         const bool fl = fo;
         auto sbuf = [&]() { return fl ? (float*)TA().alloc((size_t)slots * M * 2 * sizeof(float)) : nullptr; };
@@ -1163,14 +1163,12 @@ struct mkd_ctx {
     void emit_time_embedding(int which, int rows, const int64_t* const* tsrc, bf16_t* s0, bf16_t* s1, bf16_t* s2, float* proj) {
         const std::string P = net_prefix(which);
         const int mc = cfg.model_channels, te = temb_dim();
-        const bool keep = cur_temb;
-        cur_temb = true;
-        push(*cur_plan, [tsrc, s0, rows, mc](hipStream_t st) { return launch_timestep_embedding(*tsrc, s0, rows, mc, st); }, 1, 0.0);
+        Emit chain(emit, emit.time_embedding());
+        push([tsrc, s0, rows, mc](hipStream_t st) { return launch_timestep_embedding(*tsrc, s0, rows, mc, st); }, 1, 0.0);
         { Epi e; e.bias = wf(P + "time_embed.0.bias"); e.act = 1; op_linear(s0, mc, rows, mc, wb(P + "time_embed.0.weight"), te, e, s1, te, false, 1); }
         // every consumer applies SiLU to emb first (emb_layers = [SiLU, Linear]) -> fold it here
         { Epi e; e.bias = wf(P + "time_embed.2.bias"); e.act = 1; op_linear(s1, te, rows, te, wb(P + "time_embed.2.weight"), te, e, s2, te, false, 1); }
         { Epi e; e.bias = emb_b[which]; op_linear(s2, te, rows, te, emb_w[which], emb_total[which], e, proj, emb_total[which], true, 1); }
-        cur_temb = keep;
     }
     // ... of the evaluated batch, from the caller's t (one mkd_eps): buffers in the persistent arena
     float* time_embedding(int which) {
@@ -1184,21 +1182,7 @@ struct mkd_ctx {
         return proj;
     }
 
-    // ---- time embedding of a whole sampling call ---------------------------------------------------------------------------
-    // The timesteps of mkd_sample are a host table (reference diffmk/cddim.py:83-95: ts = full((b,), step)), every sample of a step
-    // shares one, and the embedding chain (sinusoid -> 2 linear layers -> every ResBlock's emb_layers projection: 75 MB of weights
-    // for 8 rows) depends on nothing else.  So one pass computes [n_steps, emb_total] per net before the loop, and a step only copies
-    // its row into the [B, emb_total] buffers the ResBlock epilogues read (step_setup_kernel / temb_select_kernel): 8-10 dependent
-    // launches leave every step.  MKD_TEMB_TABLE=0: per-step chain as in mkd_eps.
-    bool temb_table = getenv("MKD_TEMB_TABLE") ? atoi(getenv("MKD_TEMB_TABLE")) != 0 : true;
-    bool temb_skip = false;                       // set while a sampling loop runs from the table: the plan's own chain is left out
-    float* temb_proj[2] = {nullptr, nullptr};     // [B, emb_total] per net (persistent arena)
-    float* temb_tab[2] = {nullptr, nullptr};      // [steps, emb_total] per net
-    int64_t* temb_t = nullptr;                    // device copy of the call's timesteps
-    int temb_steps = 0, temb_gen = -1, temb_cap = 0;
-    bf16_t* temb_s[2][3] = {};                    // sinusoid and the two hidden layers of the table pass, [temb_cap, .]
-    std::vector<void*> temb_owned;
-    std::vector<Op> plan_temb_tab;
+    // ---- time embedding of a whole sampling call (what it is and why: at temb_table) ----------------------------------------
     void drop_temb_table() {
         for (void* q : temb_owned) hipFree(q);
         temb_owned.clear(); plan_temb_tab.clear();
@@ -1232,11 +1216,11 @@ struct mkd_ctx {
             temb_cap = cap;
         }
         plan_temb_tab.clear();
-        std::vector<Op>* keep_plan = cur_plan; const int keep_sid = cur_sid; const bool keep_count = counting_eps;
-        cur_plan = &plan_temb_tab; cur_sid = 0; counting_eps = false;
-        for (int which = 0; which < nets; ++which)
-            emit_time_embedding(which, n_steps, &temb_t, temb_s[which][0], temb_s[which][1], temb_s[which][2], temb_tab[which]);
-        cur_plan = keep_plan; cur_sid = keep_sid; counting_eps = keep_count;
+        {
+            Emit table(emit, EmitTarget{&plan_temb_tab});
+            for (int which = 0; which < nets; ++which)
+                emit_time_embedding(which, n_steps, &temb_t, temb_s[which][0], temb_s[which][1], temb_s[which][2], temb_tab[which]);
+        }
         temb_steps = n_steps; temb_gen = plan_generation;
         return 0;
     }
@@ -1271,7 +1255,7 @@ struct mkd_ctx {
     // producers that cannot emit statistics themselves (direct convolution, copies): a stand-alone pass over what they wrote
     void op_colstats(const bf16_t* x, int ld, int nb, int hw, int ncols, const GnOut& g) {
         if (!g.gst) return;
-        push(*cur_plan, [=](hipStream_t st) { return launch_gn_colstats(x, ld, nb, hw, ncols, g.cg, g.coff, g.gst, st); }, 1, 0.0, K_GROUPNORM,
+        push([=](hipStream_t st) { return launch_gn_colstats(x, ld, nb, hw, ncols, g.cg, g.coff, g.gst, st); }, 1, 0.0, K_GROUPNORM,
              "colstats B=" + std::to_string(nb) + " HW=" + std::to_string(hw) + " C=" + std::to_string(ncols));
     }
 
@@ -1305,7 +1289,7 @@ struct mkd_ctx {
                 const bf16_t* add = which == 1 ? slice(hint_emb, b0, nb).p : nullptr;
                 const int hh = h, ww = w, cin = b.cin, cout = b.cout;
                 const size_t xoff = (size_t)b0 * cin * hh * ww;
-                push(*cur_plan, [self, wgt, bias, o, add, nb, hh, ww, cin, cout, xoff](hipStream_t st) {
+                push([self, wgt, bias, o, add, nb, hh, ww, cin, cout, xoff](hipStream_t st) {
                     return launch_conv3x3_direct(self->io_x + xoff, 1, wgt, bias, o.p, 0, 0, add, nb, hh, ww, cin, cout, 1, st);
                 }, 1, 2.0 * nb * h * w * b.cout * 9 * b.cin, K_CONV_DIRECT);
                 { OpDesc& d = last_desc(); d.type = D_CONV_IN; d.cio = ConvInIo{wgt, bias, o.p, add}; d.xoff = xoff; d.nb = nb; d.hh = hh; d.ww = ww; d.cin = cin; d.cout = cout; }
@@ -1341,14 +1325,13 @@ struct mkd_ctx {
     }
 
     void build_prepare_plan() {
-        cur_plan = &plan_prepare;
-        counting_eps = false;
+        Emit plan(emit, EmitTarget{&plan_prepare});
         mkd_ctx* self = this;
         const int L = ctx_len(), cd = cfg.context_dim;
         ctx_bf16 = (bf16_t*)persist.alloc((size_t)B * L * cd * sizeof(bf16_t));
         {
             bf16_t* dst = ctx_bf16; const int64_t n = (int64_t)B * L * cd;
-            push(*cur_plan, [self, dst, n](hipStream_t st) { return launch_f32_to_bf16(self->in_context, dst, n, st); }, 1, 0.0);
+            push([self, dst, n](hipStream_t st) { return launch_f32_to_bf16(self->in_context, dst, n, st); }, 1, 0.0);
         }
         kv_cache.clear();
         for (auto& kv : tfm) kv.second.tail_kv = nullptr;
@@ -1365,7 +1348,7 @@ struct mkd_ctx {
                 if (tb.tail_w && tfm_tail != 0 && L <= 80) {
                     bf16_t* kp = (bf16_t*)persist.alloc(tfm_tail_kv_bytes(d, B));
                     const bf16_t* src = kv.p; const int Bn = B;
-                    push(*cur_plan, [src, d, Bn, L, kp](hipStream_t st) { return launch_tfm_tail_pack_kv(d, src, 2 * d, Bn, L, kp, st); }, 1, 0.0, K_MISC, "tfm_kv_pack");
+                    push([src, d, Bn, L, kp](hipStream_t st) { return launch_tfm_tail_pack_kv(d, src, 2 * d, Bn, L, kp, st); }, 1, 0.0, K_MISC, "tfm_kv_pack");
                     tb.tail_kv = kp;
                 }
             }
@@ -1385,7 +1368,7 @@ struct mkd_ctx {
                 {
                     const bf16_t* wgt = wb(P + "input_hint_block.0.weight"); const float* bias = wf(P + "input_hint_block.0.bias");
                     const int Bn = B, cin = widths[0], cout = widths[1];
-                    push(*cur_plan, [self, wgt, bias, cur, Bn, H0, W0, cin, cout, which2](hipStream_t st) {
+                    push([self, wgt, bias, cur, Bn, H0, W0, cin, cout, which2](hipStream_t st) {
                         return launch_conv3x3_direct(self->in_hints[which2], 1, wgt, bias, cur.p, 0, 1, nullptr, Bn, H0,
                                                      W0, cin, cout, 1, st);
                     }, 1, 0.0);
@@ -1406,7 +1389,7 @@ struct mkd_ctx {
                 Tensor e2 = hint_chain(1);
                 Tensor he = hint_emb; const int Bn = B;
                 const int64_t per = (int64_t)he.H * he.W * he.C;
-                push(*cur_plan, [self, he, e2, per, Bn](hipStream_t st) {
+                push([self, he, e2, per, Bn](hipStream_t st) {
                     return launch_blend(he.p, e2.p, self->in_alpha, he.p, per, Bn, st);
                 }, 1, 0.0);
             }
@@ -1417,7 +1400,7 @@ struct mkd_ctx {
                 tab.e[0] = hint_emb.p;
                 for (int r = 1; r < n_region_hints; ++r) tab.e[r] = hint_chain(r).p;
                 Tensor he = hint_emb; const int Bn = B, R = n_region_hints;
-                push(*cur_plan, [self, he, tab, Bn, R](hipStream_t st) {
+                push([self, he, tab, Bn, R](hipStream_t st) {
                     return launch_region_blend(tab.e, self->in_weights, he.p, Bn, he.H * he.W, he.C, R, st);
                 }, 1, 0.0);
             }
@@ -1425,9 +1408,7 @@ struct mkd_ctx {
     }
 
     void build_eps_plan() {
-        cur_plan = &plan_eps;
-        counting_eps = true;
-        flops_eps = 0; launches_eps = 0;
+        Emit plan(emit, EmitTarget{&plan_eps});          // the caller's stream; the lanes below are scopes inside it
         mkd_ctx* self = this;
         std::vector<Tensor> cn_feats, hs;
         Tensor cn_mid, u_mid;
@@ -1442,18 +1423,15 @@ struct mkd_ctx {
         const int EL = (!grouped && enc_lanes && B >= 2) ? 2 : 1;
         float* ep0 = nullptr; float* ep1 = nullptr;
         temb_proj[0] = temb_proj[1] = nullptr;
-        cur_plan = &plan_eps;
-        cur_sid = 0;
-        if (gn_fused)           // the GroupNorm statistics of this evaluation start from zero (one memset node for all of them)
-            push(*cur_plan, [self](hipStream_t st) {
+        if (gn_fused)          // the GroupNorm statistics of this evaluation start from zero (one memset node for all of them)
+            push([self](hipStream_t st) {
                 // a kernel, not hipMemsetAsync: as a memset NODE of the captured step graph it costs 1.6 ms per replay (measured)
                 return self->gstat.high ? launch_fill_i64((int64_t*)self->gstat_base, 0, (int)(self->gstat.high / 8), st) : 0;
             }, 1, 0.0, K_MISC, "gn_stat_zero");
         if (has_control && !grouped) op_edge(0, 1, true, true);      // side stream starts after everything already enqueued by the caller
         std::vector<Op> lists[NS];
-        cur_plan = &lists[0]; cur_sid = 0; ep0 = time_embedding(0);
-        if (has_control) { cur_plan = &lists[1]; cur_sid = 1; ep1 = time_embedding(1); }
-        cur_plan = &plan_eps; cur_sid = 0;
+        { Emit net(emit, emit.into(&lists[0], 0)); ep0 = time_embedding(0); }
+        if (has_control) { Emit net(emit, emit.into(&lists[1], 1)); ep1 = time_embedding(1); }
         if (EL == 2) {          // (the lanes fork after the time embedding of their net)
             for (int k = 0; k < 2; ++k) { for (auto& o : lists[k]) plan_eps.push_back(std::move(o)); lists[k].clear(); }
             op_edge(0, 2, true, true); if (has_control) op_edge(1, 3, true, true);
@@ -1463,10 +1441,9 @@ struct mkd_ctx {
         for (int l = 0; l < EL; ++l) {
             const int nb0 = EL == 2 ? B / 2 : B;
             const int b0 = l ? nb0 : 0, nb = l ? B - nb0 : nb0;
-            if (has_control) { cur_plan = &lists[2 * l + 1]; cur_sid = 2 * l + 1; encoder_lane(1, ep1, cn_feats, cn_mid, b0, nb); }
-            cur_plan = &lists[2 * l]; cur_sid = 2 * l; encoder_lane(0, ep0, hs, u_mid, b0, nb);
+            if (has_control) { Emit lane(emit, emit.into(&lists[2 * l + 1], 2 * l + 1)); encoder_lane(1, ep1, cn_feats, cn_mid, b0, nb); }
+            { Emit lane(emit, emit.into(&lists[2 * l], 2 * l)); encoder_lane(0, ep0, hs, u_mid, b0, nb); }
         }
-        cur_plan = &plan_eps; cur_sid = 0;
         if (grouped) group_ops(lists[0], lists[1], plan_eps);
         else {
             size_t idx[NS] = {};
@@ -1500,10 +1477,11 @@ struct mkd_ctx {
         // on the encoders / the block input, so they run on the side stream under the main GN -> conv -> GN chain.
         // blocks [i0, i1); first_combined: block i0's concat input was already completed by the previous phase
         auto emit_decoder = [&](int b0, int nb, bool helpers_on_side, size_t i0, size_t i1, bool first_combined) {
-            const int main_sid = cur_sid;
-            const int help_sid = helpers_on_side ? HELPER_BASE + helper_stream : main_sid;
-            const int help_cap = helpers_on_side ? main_sid : -1;
-            auto combine = [&](size_t i) {          // emits on the CURRENT sid
+            const int main_sid = emit.sid;
+            const int helper_stream = emit.helper_stream;
+            const EmitTarget helper = helpers_on_side ? emit.on(HELPER_BASE + helper_stream, main_sid) : emit;
+            auto combine = [&](size_t i) {          // emits on the helper's sid
+                Emit scope(emit, helper);
                 const BlockSpec& bs = dec[i];
                 const int si = n_skip - 1 - (int)i;
                 const Tensor skip = slice(hs[si], b0, nb);
@@ -1532,13 +1510,13 @@ struct mkd_ctx {
                 }
             };
             if (helpers_on_side) op_edge(main_sid, helper_stream);     // helper: both encoders are complete (joined on the lane's stream)
-            if (!first_combined) { cur_sid = help_sid; cur_cap_sid = help_cap; combine(i0); cur_sid = main_sid; cur_cap_sid = -1; }
+            if (!first_combined) combine(i0);
             Tensor cat;
             for (size_t i = i0; i < i1; ++i) {
                 const BlockSpec& bs = dec[i];
                 cat = slice(cats[i], b0, nb);
                 if (helpers_on_side) op_edge(helper_stream, main_sid);  // lane: this block's concat input is complete
-                if (i + 1 < dec.size()) { cur_sid = help_sid; cur_cap_sid = help_cap; combine(i + 1); cur_sid = main_sid; cur_cap_sid = -1; }   // next block's combine runs under this block
+                if (i + 1 < dec.size()) combine(i + 1);   // next block's combine runs under this block
                 // where does this block's output go?  next concat buffer's h half (or the final tensor)
                 const std::string p = P + "output_blocks." + std::to_string(i);
                 const Tensor nxt = slice(i + 1 < dec.size() ? cats[i + 1] : final_t, b0, nb);
@@ -1585,7 +1563,7 @@ struct mkd_ctx {
                 const bf16_t* wgt = wb(P + "out.2.weight"); const float* bias = wf(P + "out.2.bias");
                 const int hh = h, ww = w, cin = fin.C, cout = cfg.out_channels;
                 const size_t out_off = (size_t)b0 * cout * hh * ww;
-                push(*cur_plan, [self, g, wgt, bias, nb, hh, ww, cin, cout, out_off](hipStream_t st) {
+                push([self, g, wgt, bias, nb, hh, ww, cin, cout, out_off](hipStream_t st) {
                     return launch_conv3x3_direct(g.p, 0, wgt, bias, self->io_out + out_off, 1, 0, nullptr, nb, hh, ww, cin, cout, 1, st);
                 }, 1, 2.0 * nb * h * w * cfg.out_channels * 9 * fin.C, K_CONV_DIRECT);
                 TA().release(mk);
@@ -1605,13 +1583,10 @@ struct mkd_ctx {
             std::vector<Op> lane_ops[NS];
             for (int l = 0; l < DL; ++l) {
                 const int b0 = (int)((int64_t)B * l / DL), b1 = (int)((int64_t)B * (l + 1) / DL);
-                cur_plan = &lane_ops[l]; cur_sid = l;
                 const bool lh = lane_helpers && DL == 2;          // lane l's helper GEMMs on stream 2 + l
-                lane_main = l; helper_stream = lh ? 2 + l : 1;
+                Emit lane(emit, emit.into(&lane_ops[l], l).lane(l, lh ? 2 + l : 1));
                 emit_decoder(b0, b1 - b0, lh, from, dec.size(), from > 0);
-                lane_main = 0; helper_stream = 1;
             }
-            cur_plan = &plan_eps; cur_sid = 0;
             for (int l = 1; l < DL; ++l) op_edge(0, l, true, true);     // lanes start after the encoders (all joined on main)
             size_t idx[NS] = {};
             for (bool more = true; more;) {
@@ -1623,23 +1598,13 @@ struct mkd_ctx {
         } else {
             emit_decoder(0, B, dec_overlap, 0, dec.size(), false);
         }
-        counting_eps = false;
-        if (!dry) {          // (grouping changed the launch count: take it from the plan itself)
+        if (!dry) {          // launches and flops of the evaluation, counted on the plan itself (grouped ops count once)
             launches_eps = 0; launches_temb = 0; flops_eps = 0;
             for (auto& op : plan_eps) { launches_eps += op.launches; flops_eps += op.flops; if (op.temb) launches_temb += op.launches; }
         }
     }
 
-    // ---- grouped launches of the encoder phase ----------------------------------------------------------------------------------
-    // MKD_ENC_GROUP=1: ControlNet and UNet encoder + middle block as one chain of 2-problem launches on the caller's stream; 0 (the
-    // default): two chains on two streams.  Measured at batch 8, 256x256, graph replay, latents only (tools/exp_r3_group.sh, two
-    // alternating rounds on one box): two chains 5.64 ms per evaluation (728 launches), grouped 6.19-6.25 ms (576-582 launches) -
-    // 146 launches fewer and 10 % SLOWER.  A grouped kernel takes twice the time of one of its halves (the serial sum of kernel
-    // times barely moves: 10.35 -> 9.4 ms with ~4 us of event overhead per launch in both), so what grouping removes is one
-    // fixed cost per pair - and that is exactly what the second chain already hides: while one chain's kernel drains, dispatches and
-    // fills its first tiles, the other chain's kernel has the CUs (pair = max(L + W, 2 W) on two chains, L + 2 W grouped).
-    bool enc_group = getenv("MKD_ENC_GROUP") ? atoi(getenv("MKD_ENC_GROUP")) != 0 : false;
-    int launches_temb = 0;
+    // ---- grouped launches of the encoder phase (the switch and its measurement: enc_group) ---------------------------------
     // u / c: the op lists of the UNet and the ControlNet encoder (same architecture, emitted by the same code).  Ops whose
     // descriptors agree in kind and geometry become ONE launch over both problems; anything else runs one after the other.  Either
     // way everything lands on stream 0: the ControlNet keeps its own temporaries and workspaces (arena 1), only its stream goes.
@@ -1767,7 +1732,6 @@ struct mkd_ctx {
             for (int i = 0; i < NS; ++i) { temp_arena[i].base = nullptr; temp_arena[i].reset(); }
             splitk_need = 0; gn_need = 0;
             plan_prepare.clear(); plan_eps.clear();
-            cur_sid = 0;
             build_prepare_plan(); build_eps_plan();
             int rc = ensure((void**)&persist_base, &persist_cap, persist.high + 256); if (rc) return rc;
             rc = ensure((void**)&gstat_base, &gstat_cap, gstat.high + 256); if (rc) return rc;
@@ -1783,7 +1747,7 @@ struct mkd_ctx {
             persist.base = persist_base; persist.reset();
             gstat.base = gstat_base; gstat.reset();
             for (int i = 0; i < NS; ++i) { temp_arena[i].base = temp_base[i]; temp_arena[i].reset(); }
-            cur_sid = 0; aux_used = 0;
+            aux_used = 0;
             build_prepare_plan();
             persist_eps_begin = persist.off;           // everything above this is written by mkd_eps itself
             build_eps_plan();
@@ -1852,13 +1816,13 @@ struct mkd_ctx {
         if (!always && !dec_overlap && !dec_lanes) return;
         const int e = ev_new();
         mkd_ctx* self = this;
-        push(*cur_plan, [self, e, from_sid, to_sid, in_graph](hipStream_t) {
+        push([self, e, from_sid, to_sid, in_graph](hipStream_t) {
             if (self->run_serial || (self->capturing && !in_graph) || e < 0) return 0;      // graph nodes pay for every cross-stream edge: keep the decoder linear there
             MKD_HIP_CHECK(hipEventRecord(self->aux_ev[e], self->stream_of(from_sid)));
             MKD_HIP_CHECK(hipStreamWaitEvent(self->stream_of(to_sid), self->aux_ev[e], 0));
             return 0;
         }, 0, 0.0, K_MISC, "edge " + std::to_string(from_sid) + "->" + std::to_string(to_sid));
-        if (!dry) { Op& o = cur_plan->back(); o.edge_from = from_sid; o.edge_to = to_sid; o.edge_in_graph = in_graph; }
+        if (!dry) { Op& o = emit.plan->back(); o.edge_from = from_sid; o.edge_to = to_sid; o.edge_in_graph = in_graph; }
     }
 
     // one eps with a hipEvent pair around every plan op: per-kernel-class device time (bench roofline)
@@ -2157,23 +2121,35 @@ struct mkd_ctx {
     }
     static bool traced(const SampleReq& r) { return r.ex && (r.ex->trace_x || r.ex->trace_x0); }
 
-    // graph path, before the steps: order the loop against the caller's stream, upload the step state, run the table
-    int graph_prologue(const SampleReq& r, bool stochastic, hipStream_t stream) {
+    // Before the steps that read the device step state: the pinned and the device state exist (a replayed loop's stream and events too),
+    // the start latent is in s_xa, a replayed loop's stream is ordered after the caller's.  *ls: where the uploads and the steps go
+    int loop_begin(const float* x_T, int64_t n, bool replayed, hipStream_t stream, hipStream_t* ls) {
         if (!h_state) MKD_HIP_CHECK(hipHostMalloc((void**)&h_state, sizeof(StepState)));
         if (!s_state) MKD_HIP_CHECK(hipMalloc((void**)&s_state, sizeof(StepState)));
-        if (!loop_stream) {
+        if (replayed && !loop_stream) {
             // the caller's stream may be the legacy null stream, which cannot be captured: run the loop on a
             // private stream ordered against the caller's with events
             MKD_HIP_CHECK(hipStreamCreateWithFlags(&loop_stream, hipStreamNonBlocking));
             MKD_HIP_CHECK(hipEventCreateWithFlags(&ev_loop_in, hipEventDisableTiming));
             MKD_HIP_CHECK(hipEventCreateWithFlags(&ev_loop_out, hipEventDisableTiming));
         }
-        MKD_HIP_CHECK(hipStreamSynchronize(loop_stream));     // h_state may still feed a previous call's copy
-        fill_step_state(r, stochastic);
-        MKD_HIP_CHECK(hipEventRecord(ev_loop_in, stream));
-        MKD_HIP_CHECK(hipStreamWaitEvent(loop_stream, ev_loop_in, 0));
-        MKD_HIP_CHECK(hipMemcpyAsync(s_state, h_state, sizeof(StepState), hipMemcpyHostToDevice, loop_stream));
-        return run_temb_table(r.n_steps, r.timesteps, loop_stream);
+        if (loop_stream) MKD_HIP_CHECK(hipStreamSynchronize(loop_stream));     // the pinned state / table may still feed a previous replayed call's copy
+        MKD_HIP_CHECK(hipMemcpyAsync(s_xa, x_T, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        *ls = replayed ? loop_stream : stream;
+        if (replayed) {
+            MKD_HIP_CHECK(hipEventRecord(ev_loop_in, stream));
+            MKD_HIP_CHECK(hipStreamWaitEvent(loop_stream, ev_loop_in, 0));
+        }
+        return 0;
+    }
+    // After the steps: the result out of s_xa; the caller's stream waits for a replayed loop
+    int loop_end(float* x_out, int64_t n, bool replayed, hipStream_t stream) {
+        MKD_HIP_CHECK(hipMemcpyAsync(x_out, s_xa, n * sizeof(float), hipMemcpyDeviceToDevice, replayed ? loop_stream : stream));
+        if (replayed) {
+            MKD_HIP_CHECK(hipEventRecord(ev_loop_out, loop_stream));
+            MKD_HIP_CHECK(hipStreamWaitEvent(stream, ev_loop_out, 0));
+        }
+        return 0;
     }
 
     // the n_steps steps on loop_stream.  Graph mode 1: one captured step (both streams, fork/join included), replayed; mode 2: its linear graphs
@@ -2211,6 +2187,7 @@ struct mkd_ctx {
         const int n_steps = r.n_steps, hw = h * w;
         const int64_t n = latent_n(r.batch);
         const mkd_sample_mask* qm = r.qm;
+        MKD_HIP_CHECK(hipMemcpyAsync(s_xa, r.x_T, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
         int rc = run_temb_table(n_steps, r.timesteps, stream); if (rc) return rc;
         float* xa = s_xa; float* xb = s_xb;
         const float* kf = key.rescale > 0 ? s_kfac : nullptr;
@@ -2261,14 +2238,14 @@ struct mkd_ctx {
         key.temb = temb_table;          // (the steps take the time embedding from the table exactly when the table is on)
         const int64_t n = latent_n(r.batch);
         if (key.solver) { rc = ensure_ring(n); if (rc) return rc; }
-        MKD_HIP_CHECK(hipMemcpyAsync(s_xa, r.x_T, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
         if (!r.use_graph) return sample_eager(r, key, stochastic, stream);
-        rc = graph_prologue(r, stochastic, stream); if (rc) return rc;
+        hipStream_t ls = nullptr;
+        rc = loop_begin(r.x_T, n, true, stream, &ls); if (rc) return rc;
+        fill_step_state(r, stochastic);
+        MKD_HIP_CHECK(hipMemcpyAsync(s_state, h_state, sizeof(StepState), hipMemcpyHostToDevice, ls));
+        rc = run_temb_table(r.n_steps, r.timesteps, ls); if (rc) return rc;
         rc = replay_steps(r.n_steps, key); if (rc) return rc;
-        MKD_HIP_CHECK(hipMemcpyAsync(r.x_out, s_xa, n * sizeof(float), hipMemcpyDeviceToDevice, loop_stream));      // the result; the caller's stream waits for the loop
-        MKD_HIP_CHECK(hipEventRecord(ev_loop_out, loop_stream));
-        MKD_HIP_CHECK(hipStreamWaitEvent(stream, ev_loop_out, 0));
-        return 0;
+        return loop_end(r.x_out, n, true, stream);
     }
 
     // ---- per-sample requests (include/mkd.h mkd_sample_rows) ----------------------------------------------------------------
@@ -2306,15 +2283,8 @@ struct mkd_ctx {
         const int64_t n = latent_n(r.batch);
         if (key.solver) { rc = ensure_ring(n); if (rc) return rc; }
         rc = ensure_rows(tab.size()); if (rc) return rc;
-        if (!h_state) MKD_HIP_CHECK(hipHostMalloc((void**)&h_state, sizeof(StepState)));
-        if (!s_state) MKD_HIP_CHECK(hipMalloc((void**)&s_state, sizeof(StepState)));
-        if (r.use_graph && !loop_stream) {
-            MKD_HIP_CHECK(hipStreamCreateWithFlags(&loop_stream, hipStreamNonBlocking));
-            MKD_HIP_CHECK(hipEventCreateWithFlags(&ev_loop_in, hipEventDisableTiming));
-            MKD_HIP_CHECK(hipEventCreateWithFlags(&ev_loop_out, hipEventDisableTiming));
-        }
-        // the pinned state / table may still feed a previous replayed call's copy (an uncaptured call waits for its own copies below)
-        if (loop_stream) MKD_HIP_CHECK(hipStreamSynchronize(loop_stream));
+        hipStream_t ls = nullptr;          // uncaptured: the caller's stream, uploads included
+        rc = loop_begin(r.x_T, n, r.use_graph != 0, stream, &ls); if (rc) return rc;
         memset(h_state, 0, sizeof(StepState));
         h_state->counter = s_max - 1; h_state->n_steps = s_max;
         h_state->noise = stochastic ? r.noise : nullptr; h_state->temperature = r.temperature;
@@ -2323,13 +2293,6 @@ struct mkd_ctx {
         for (int i = 0; i < MKD_MAX_STEPS; ++i) h_state->trace_row[i] = -1;
         h_state->rows = s_rows; h_state->rows_batch = r.batch;
         memcpy(h_rows, tab.data(), tab.size() * sizeof(StepRow));
-        MKD_HIP_CHECK(hipMemcpyAsync(s_xa, r.x_T, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
-        hipStream_t ls = stream;
-        if (r.use_graph) {
-            ls = loop_stream;
-            MKD_HIP_CHECK(hipEventRecord(ev_loop_in, stream));
-            MKD_HIP_CHECK(hipStreamWaitEvent(loop_stream, ev_loop_in, 0));
-        }
         MKD_HIP_CHECK(hipMemcpyAsync(s_state, h_state, sizeof(StepState), hipMemcpyHostToDevice, ls));
         MKD_HIP_CHECK(hipMemcpyAsync(s_rows, h_rows, tab.size() * sizeof(StepRow), hipMemcpyHostToDevice, ls));
         if (!r.use_graph) MKD_HIP_CHECK(hipStreamSynchronize(stream));          // (no later call of any form finds the pinned copies in flight)
@@ -2337,12 +2300,7 @@ struct mkd_ctx {
         if (r.use_graph) rc = replay_steps(s_max, key);
         else rc = enqueue_state_steps(key, s_max, stream);
         if (rc) return rc;
-        MKD_HIP_CHECK(hipMemcpyAsync(r.x_out, s_xa, n * sizeof(float), hipMemcpyDeviceToDevice, ls));
-        if (r.use_graph) {
-            MKD_HIP_CHECK(hipEventRecord(ev_loop_out, loop_stream));
-            MKD_HIP_CHECK(hipStreamWaitEvent(stream, ev_loop_out, 0));
-        }
-        return 0;
+        return loop_end(r.x_out, n, r.use_graph != 0, stream);
     }
 
     // ---------------------------------------------------------------------------------------------------------------
@@ -2498,7 +2456,7 @@ struct mkd_ctx {
         }
         {
             bf16_t* s_ = sc; bf16_t* p_ = pr; const int rows = x.B * T, cols = T;
-            push(*cur_plan, [=](hipStream_t st) { return launch_softmax_rows(s_, p_, rows, cols, st); }, 1, 0.0, K_MISC, "softmax_rows");
+            push([=](hipStream_t st) { return launch_softmax_rows(s_, p_, rows, cols, st); }, 1, 0.0, K_MISC, "softmax_rows");
         }
         for (int b = 0; b < x.B; ++b) {
             Epi e; e.bias = wf(p + ".v.bias");
@@ -2510,7 +2468,7 @@ struct mkd_ctx {
 
     void build_vae_plan(int Bn, int hh, int ww) {
         SideNet& n = net(W_DEC);
-        cur_plan = &n.plan; cur_sid = SID_AUX; counting_eps = false;
+        Emit plan(emit, EmitTarget{&n.plan, SID_AUX});
         mkd_ctx* self = this;
         const std::string P = vae_prefix(), D = P + "decoder.";
         const int zc = dec_cfg.z_channels;
@@ -2531,7 +2489,7 @@ struct mkd_ctx {
         {
             const bf16_t* w_ = wb(P + "post_quant_conv.weight"); const float* b_ = wf(P + "post_quant_conv.bias");
             const int hw = hh * ww;
-            push(*cur_plan, [self, w_, b_, zq, Bn, zc, hw](hipStream_t st) {
+            push([self, w_, b_, zq, Bn, zc, hw](hipStream_t st) {
                 return launch_post_quant(self->io_z, w_, b_, self->io_inv_scale, zq, Bn, zc, hw, st); }, 1, 0.0, K_MISC, "post_quant");
         }
         int bi = dec_cfg.ch * dec_cfg.ch_mult[dec_cfg.n_levels - 1];
@@ -2539,7 +2497,7 @@ struct mkd_ctx {
         Tensor h; h.B = Bn; h.H = hh; h.W = ww; h.C = bi; h.ld = bi; h.p = X[cur];
         {
             const bf16_t* w_ = wb(D + "conv_in.weight"); const float* b_ = wf(D + "conv_in.bias"); bf16_t* dst = h.p;
-            push(*cur_plan, [w_, b_, zq, dst, Bn, hh, ww, zc, bi](hipStream_t st) {
+            push([w_, b_, zq, dst, Bn, hh, ww, zc, bi](hipStream_t st) {
                 return launch_conv3x3_direct(zq, 1, w_, b_, dst, 0, 0, nullptr, Bn, hh, ww, zc, bi, 1, st); }, 1,
                 2.0 * Bn * hh * ww * bi * 9 * zc, K_CONV_DIRECT);
         }
@@ -2566,7 +2524,7 @@ struct mkd_ctx {
             op_gn(h, wf(D + "norm_out.weight"), wf(D + "norm_out.bias"), 1e-6f, 1, o.p, o.ld);
             const bf16_t* w_ = wb(D + "conv_out.weight"); const float* b_ = wf(D + "conv_out.bias");
             const int H2 = h.H, W2 = h.W, cin = h.C, cout = dec_cfg.out_ch;
-            push(*cur_plan, [self, o, w_, b_, Bn, H2, W2, cin, cout](hipStream_t st) {
+            push([self, o, w_, b_, Bn, H2, W2, cin, cout](hipStream_t st) {
                 return launch_conv3x3_direct(o.p, 0, w_, b_, self->io_img, 1, 0, nullptr, Bn, H2, W2, cin, cout, 1, st); }, 1,
                 2.0 * Bn * H2 * W2 * cout * 9 * cin, K_CONV_DIRECT);
         }
@@ -2617,7 +2575,7 @@ struct mkd_ctx {
 
     void build_venc_plan(int Bn, int H, int W) {
         SideNet& n = net(W_ENC);
-        cur_plan = &n.plan; cur_sid = SID_AUX; counting_eps = false;
+        Emit plan(emit, EmitTarget{&n.plan, SID_AUX});
         mkd_ctx* self = this;
         const std::string P = vae_prefix(), E = P + "encoder.";
         // largest activation: full resolution x max(ch * ch_mult[0], ch) channels, then halved pixels per level
@@ -2637,7 +2595,7 @@ struct mkd_ctx {
         Tensor h; h.B = Bn; h.H = H; h.W = W; h.C = enc_cfg.ch; h.ld = enc_cfg.ch; h.p = X[cur];
         {
             const bf16_t* w_ = wb(E + "conv_in.weight"); const float* b_ = wf(E + "conv_in.bias"); bf16_t* dst = h.p; const int co = enc_cfg.ch;
-            push(*cur_plan, [self, w_, b_, dst, Bn, H, W, co](hipStream_t st) {
+            push([self, w_, b_, dst, Bn, H, W, co](hipStream_t st) {
                 return launch_conv3x3_direct(self->io_enc_img, 1, w_, b_, dst, 0, 0, nullptr, Bn, H, W, 3, co, 1, st); }, 1,
                 2.0 * Bn * H * W * co * 9 * 3, K_CONV_DIRECT, "conv_in 3->" + std::to_string(co));
         }
@@ -2666,7 +2624,7 @@ struct mkd_ctx {
             const bf16_t* w_ = wb(E + "conv_out.weight"); const float* b_ = wf(E + "conv_out.bias");
             const bf16_t* wq = wb(P + "quant_conv.weight"); const float* bq = wf(P + "quant_conv.bias");
             const int h2 = h.H, w2 = h.W, cin = h.C, zc = enc_cfg.z_channels;
-            push(*cur_plan, [self, o, w_, b_, wq, bq, Bn, h2, w2, cin, zc](hipStream_t st) {
+            push([self, o, w_, b_, wq, bq, Bn, h2, w2, cin, zc](hipStream_t st) {
                 return launch_vae_enc_tail(o.p, w_, b_, wq, bq, self->io_enc_noise, self->io_enc_scale, self->io_enc_z, self->io_enc_mom,
                                            Bn, h2, w2, cin, zc, st); }, 1,
                 2.0 * Bn * h2 * w2 * 2 * zc * (9.0 * cin + 2 * zc), K_CONV_DIRECT, "enc_tail");
@@ -2743,7 +2701,7 @@ struct mkd_ctx {
 
     void build_clip_plan(int Bn, int T) {
         SideNet& n = net(W_CLIP);
-        cur_plan = &n.plan; cur_sid = SID_AUX; counting_eps = false;
+        Emit plan(emit, EmitTarget{&n.plan, SID_AUX});
         mkd_ctx* self = this;
         const std::string P = clip_prefix();
         const int W = txt_cfg.width, I = txt_cfg.intermediate, heads = txt_cfg.heads, dh = W / heads, rows = Bn * T;
@@ -2753,14 +2711,14 @@ struct mkd_ctx {
         {
             const bf16_t* te = wb(P + "embeddings.token_embedding.weight"); const bf16_t* pe = wb(P + "embeddings.position_embedding.weight");
             bf16_t* dst = X[0]; const int V = txt_cfg.vocab_size;
-            push(*cur_plan, [self, te, pe, dst, Bn, T, W, V](hipStream_t st) {
+            push([self, te, pe, dst, Bn, T, W, V](hipStream_t st) {
                 return launch_clip_embed(self->io_tokens, te, pe, dst, Bn, T, W, V, st); }, 1, 0.0, K_MISC, "clip_embed");
         }
         int cur = 0;
         const float eps = txt_cfg.ln_eps;
         auto op_ln_eps = [&](const bf16_t* x, const std::string& n, bf16_t* y) {
             const float* g = wf(n + ".weight"); const float* b = wf(n + ".bias");
-            push(*cur_plan, [=](hipStream_t st) { return launch_layernorm(x, g, b, eps, y, rows, W, st); }, 1, 0.0, K_LAYERNORM,
+            push([=](hipStream_t st) { return launch_layernorm(x, g, b, eps, y, rows, W, st); }, 1, 0.0, K_LAYERNORM,
                  "rows=" + std::to_string(rows) + " d=" + std::to_string(W));
         };
         for (int l = 0; l < txt_cfg.layers; ++l) {
@@ -2770,7 +2728,7 @@ struct mkd_ctx {
             {   // causal self-attention over the T padded tokens (CLIP applies no padding mask, only the causal one)
                 const float scale = 1.0f / sqrtf((float)dh);
                 const bf16_t* q = qkv; bf16_t* o = att;
-                push(*cur_plan, [=](hipStream_t st) { return launch_attention(q, 3 * W, q + W, 3 * W, q + 2 * W, 3 * W, o, W, Bn, T, T, heads, dh, scale, st, 1); },
+                push([=](hipStream_t st) { return launch_attention(q, 3 * W, q + W, 3 * W, q + 2 * W, 3 * W, o, W, Bn, T, T, heads, dh, scale, st, 1); },
                      1, 4.0 * Bn * heads * (double)T * T * dh, K_ATTENTION, "clip causal B=" + std::to_string(Bn) + " T=" + std::to_string(T));
             }
             { Epi e; e.bias = wf(A + ".out_proj.bias"); e.R = X[cur]; e.ldr = W; op_linear(att, W, rows, W, wb(A + ".out_proj.weight"), W, e, X[cur ^ 1], W); }
@@ -2783,7 +2741,7 @@ struct mkd_ctx {
         op_ln_eps(X[cur], P + "final_layer_norm", ln);
         {
             const int64_t n = (int64_t)rows * W;
-            push(*cur_plan, [self, ln, n](hipStream_t st) { return launch_bf16_to_f32(ln, self->io_ctx_out, n, st); }, 1, 0.0, K_MISC, "clip_out");
+            push([self, ln, n](hipStream_t st) { return launch_bf16_to_f32(ln, self->io_ctx_out, n, st); }, 1, 0.0, K_MISC, "clip_out");
         }
     }
 
@@ -2901,7 +2859,6 @@ int mkd_ctx_create(const mkd_net_config* cfg, mkd_ctx** out) {
         return mkd_fail(MKD_ERR_STATE, "kernel-class table too small for the tile configurations of kernels_gemm.hip (OpKind)");
     mkd_ctx* c = new mkd_ctx();
     c->cfg = *cfg;
-    if (const char* fl = getenv("MKD_FUSE_LN")) c->fuse_ln = fl[0] == '1';
     if (const char* sc = getenv("MKD_SPLITK_CAP")) gemm_set_splitk_cap(atoi(sc));
     c->build_param_spec();
     *out = c;
@@ -3298,308 +3255,5 @@ int mkd_step_launches_ex(const mkd_ctx* ctx, int use_graph, int cfg_on) {
 }
 int mkd_step_launches(const mkd_ctx* ctx) { return mkd_step_launches_ex(ctx, 1, 0); }
 int64_t mkd_device_bytes(const mkd_ctx* ctx) { return ctx ? ctx->device_bytes() : 0; }
-
-// ---- single-kernel entry points ----------------------------------------------------------------------
-static bf16_t* g_zero = nullptr;
-static float* g_ws = nullptr; static size_t g_ws_bytes = 0;
-static float* g_gn = nullptr; static size_t g_gn_bytes = 0;
-
-static int scratch(float** p, size_t* have, size_t need) {
-    if (*have >= need && *p) return 0;
-    if (*p) { hipDeviceSynchronize(); hipFree(*p); *p = nullptr; }
-    MKD_HIP_CHECK(hipMalloc((void**)p, need ? need : 256));
-    *have = need;
-    return 0;
-}
-
-static int gemm_entry(const uint16_t* A, int lda, const uint16_t* W, int ldw, const float* bias, const float* rowbias, int ldrb,
-                      int rows_per_batch, const uint16_t* R, int ldr, float scale, int act, void* C, int ldc, int out_f32, int M,
-                      int N, int K, int conv3x3, int batch, int Hin, int Win, int Cin, int Hout, int Wout, int stride, int up,
-                      int splitk, long long* gn_stat, int gn_cg, int gn_coff, int gn_hw, void* stream) {
-    if (!A || !W || !C) return mkd_fail(MKD_ERR_ARG, "mkd_gemm_bf16: null pointer");
-    if (!g_zero) {
-        MKD_HIP_CHECK(hipMalloc((void**)&g_zero, 4096));
-        MKD_HIP_CHECK(hipMemset(g_zero, 0, 4096));
-    }
-    if (conv3x3 && M != batch * Hout * Wout) return mkd_fail(MKD_ERR_ARG, "mkd_gemm_bf16: M != batch*Hout*Wout");
-    GemmArgs a; memset(&a, 0, sizeof(a));
-    a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.bias = bias; a.rowbias = rowbias; a.ldrb = ldrb; a.rows_per_batch = rows_per_batch;
-    a.R = R; a.ldr = ldr; a.scale = scale; a.act = act; a.C = C; a.ldc = ldc; a.out_f32 = out_f32; a.M = M; a.N = N; a.K = K;
-    a.conv = conv3x3 ? 1 : 0; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = Hout; a.Wout = Wout; a.stride = stride; a.up = up; a.pad_tl = 1;
-    a.zero = g_zero;
-    a.gn_stat = gn_stat; a.gn_cg = gn_cg; a.gn_coff = gn_coff; a.gn_hw = gn_hw;
-    a.splitk = splitk > 0 ? splitk : 0;
-    int cfg_i = 0, s = 1;
-    int rc = gemm_resolve(a, &cfg_i, &s);          // the decision launch_gemm will take, fallbacks included
-    if (rc) return rc;
-    rc = scratch(&g_ws, &g_ws_bytes, gemm_ws_bytes(M, N, s > 1 ? s : 2));
-    if (rc) return rc;
-    a.ws = g_ws; a.ws_bytes = g_ws_bytes;
-    return launch_gemm(a, (hipStream_t)stream);
-}
-int mkd_gemm_bf16(const uint16_t* A, int lda, const uint16_t* W, int ldw, const float* bias, const float* rowbias, int ldrb,
-                  int rows_per_batch, const uint16_t* R, int ldr, float scale, int act, void* C, int ldc, int out_f32, int M,
-                  int N, int K, int conv3x3, int batch, int Hin, int Win, int Cin, int Hout, int Wout, int stride, int up,
-                  int splitk, void* stream) {
-    return gemm_entry(A, lda, W, ldw, bias, rowbias, ldrb, rows_per_batch, R, ldr, scale, act, C, ldc, out_f32, M, N, K, conv3x3, batch,
-                      Hin, Win, Cin, Hout, Wout, stride, up, splitk, nullptr, 0, 0, 0, stream);
-}
-int mkd_conv3x3_down_bf16(const uint16_t* x, int ldx, const uint16_t* w_packed, const float* bias, uint16_t* y, int ldy, int batch, int H, int W,
-                          int Cin, int Cout, int splitk, void* stream) {
-    if (!x || !w_packed || !y) return mkd_fail(MKD_ERR_ARG, "mkd_conv3x3_down_bf16: null pointer");
-    if (batch <= 0 || H <= 0 || W <= 0 || H % 2 || W % 2) return mkd_fail(MKD_ERR_ARG, "mkd_conv3x3_down_bf16: H, W must be even");
-    if (!g_zero) {
-        MKD_HIP_CHECK(hipMalloc((void**)&g_zero, 4096));
-        MKD_HIP_CHECK(hipMemset(g_zero, 0, 4096));
-    }
-    GemmArgs a; memset(&a, 0, sizeof(a));
-    a.A = x; a.lda = ldx; a.W = w_packed; a.ldw = 9 * Cin; a.bias = bias; a.scale = 1.0f; a.C = y; a.ldc = ldy;
-    a.M = batch * (H / 2) * (W / 2); a.N = Cout; a.K = 9 * Cin; a.conv = 1;
-    a.Hin = H; a.Win = W; a.Cin = Cin; a.Hout = H / 2; a.Wout = W / 2; a.stride = 2; a.up = 0; a.pad_tl = 0;
-    a.zero = g_zero; a.splitk = splitk > 0 ? splitk : 0;
-    int cfg_i = 0, s = 1;
-    int rc = gemm_resolve(a, &cfg_i, &s);
-    if (rc) return rc;
-    rc = scratch(&g_ws, &g_ws_bytes, gemm_ws_bytes(a.M, Cout, s > 1 ? s : 2));
-    if (rc) return rc;
-    a.ws = g_ws; a.ws_bytes = g_ws_bytes;
-    return launch_gemm(a, (hipStream_t)stream);
-}
-int mkd_conv3x3_fold_bf16(const uint16_t* x, int ldx, const uint16_t* w_fold, const float* bias, const uint16_t* x2, int ldx2, int K2, uint16_t* y,
-                          int ldy, int batch, int H, int W, int Cin, int N, int splitk, void* stream) {
-    if (!x || !w_fold || !x2 || !y) return mkd_fail(MKD_ERR_ARG, "mkd_conv3x3_fold_bf16: null pointer");
-    if (!g_zero) {
-        MKD_HIP_CHECK(hipMalloc((void**)&g_zero, 4096));
-        MKD_HIP_CHECK(hipMemset(g_zero, 0, 4096));
-    }
-    GemmArgs a; memset(&a, 0, sizeof(a));
-    a.A = x; a.lda = ldx; a.W = w_fold; a.ldw = 9 * Cin + K2; a.bias = bias; a.scale = 1.0f; a.C = y; a.ldc = ldy; a.M = batch * H * W; a.N = N;
-    a.K = 9 * Cin + K2; a.conv = 1; a.Hin = H; a.Win = W; a.Cin = Cin; a.Hout = H; a.Wout = W; a.stride = 1; a.up = 0; a.pad_tl = 1;
-    a.A2 = x2; a.lda2 = ldx2; a.K2 = K2; a.zero = g_zero; a.splitk = splitk > 0 ? splitk : 0;
-    int cfg_i = 0, s = 1;
-    int rc = gemm_resolve(a, &cfg_i, &s);
-    if (rc) return rc;
-    rc = scratch(&g_ws, &g_ws_bytes, gemm_ws_bytes(a.M, N, s > 1 ? s : 2));
-    if (rc) return rc;
-    a.ws = g_ws; a.ws_bytes = g_ws_bytes;
-    return launch_gemm(a, (hipStream_t)stream);
-}
-int mkd_gemm_gnstat_bf16(const uint16_t* A, int lda, const uint16_t* W, int ldw, const float* bias, const float* rowbias, int ldrb,
-                         int rows_per_batch, const uint16_t* R, int ldr, float scale, int act, void* C, int ldc, int out_f32, int M,
-                         int N, int K, int conv3x3, int batch, int Hin, int Win, int Cin, int Hout, int Wout, int stride, int up,
-                         int splitk, int64_t* gn_stat, int gn_cg, int gn_coff, int gn_hw, void* stream) {
-    if (!gn_stat) return mkd_fail(MKD_ERR_ARG, "mkd_gemm_gnstat_bf16: null statistics buffer");
-    return gemm_entry(A, lda, W, ldw, bias, rowbias, ldrb, rows_per_batch, R, ldr, scale, act, C, ldc, out_f32, M, N, K, conv3x3, batch,
-                      Hin, Win, Cin, Hout, Wout, stride, up, splitk, (long long*)gn_stat, gn_cg, gn_coff, gn_hw, stream);
-}
-int mkd_gemm_groupnorm_bf16(const uint16_t* A, int lda, const uint16_t* W, int ldw, const float* bias, const float* rowbias, int ldrb,
-                            int rows_per_batch, const uint16_t* R, int ldr, float scale, void* C, int ldc, int write_raw, int M, int N,
-                            int K, int conv3x3, int batch, int Hin, int Win, int Cin, int Hout, int Wout, int stride, int up, int splitk,
-                            int rows_per_sample, const float* gamma, const float* beta, float eps, int silu, uint16_t* y, int ld_y,
-                            void* stream) {
-    if (!A || !W || (!C && write_raw) || !gamma || !beta || !y) return mkd_fail(MKD_ERR_ARG, "mkd_gemm_groupnorm_bf16: null pointer");
-    if (rows_per_sample <= 0 || M % rows_per_sample) return mkd_fail(MKD_ERR_ARG, "mkd_gemm_groupnorm_bf16: M must be a multiple of rows_per_sample");
-    if (!g_zero) {
-        MKD_HIP_CHECK(hipMalloc((void**)&g_zero, 4096));
-        MKD_HIP_CHECK(hipMemset(g_zero, 0, 4096));
-    }
-    if (conv3x3 && M != batch * Hout * Wout) return mkd_fail(MKD_ERR_ARG, "mkd_gemm_groupnorm_bf16: M != batch*Hout*Wout");
-    const int nb = M / rows_per_sample;
-    if (!gn_from_slabs_supported(nb, rows_per_sample, N)) return mkd_fail(MKD_ERR_UNSUPPORTED, "mkd_gemm_groupnorm_bf16: GroupNorm geometry does not fit the single-pass kernel");
-    GemmArgs a; memset(&a, 0, sizeof(a));
-    a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.bias = bias; a.rowbias = rowbias; a.ldrb = ldrb; a.rows_per_batch = rows_per_batch;
-    a.R = R; a.ldr = ldr; a.scale = scale; a.act = 0; a.C = C; a.ldc = ldc; a.out_f32 = 0; a.M = M; a.N = N; a.K = K;
-    a.conv = conv3x3 ? 1 : 0; a.Hin = Hin; a.Win = Win; a.Cin = Cin; a.Hout = Hout; a.Wout = Wout; a.stride = stride; a.up = up; a.pad_tl = 1;
-    a.zero = g_zero; a.splitk = splitk > 0 ? splitk : 0;
-    int cfg_i = 0, s = 1;
-    int rc = gemm_resolve(a, &cfg_i, &s);
-    if (rc) return rc;
-    if (s < 2) return mkd_fail(MKD_ERR_UNSUPPORTED, "mkd_gemm_groupnorm_bf16: this shape is not split over K");
-    rc = scratch(&g_ws, &g_ws_bytes, gemm_ws_bytes(M, N, s));
-    if (rc) return rc;
-    a.ws = g_ws; a.ws_bytes = g_ws_bytes; a.defer_epilogue = 1;
-    rc = launch_gemm(a, (hipStream_t)stream);
-    if (rc) return rc;
-    a.splitk = s;
-    if (!write_raw) a.C = nullptr;
-    return launch_gn_from_slabs(a, gamma, beta, eps, silu, y, ld_y, nb, rows_per_sample, (hipStream_t)stream);
-}
-int mkd_gn_colstats(const uint16_t* x, int ld, int batch, int hw, int ncols, int cg, int coff, int64_t* gstat, void* stream) {
-    if (!x || !gstat) return mkd_fail(MKD_ERR_ARG, "mkd_gn_colstats: null pointer");
-    return launch_gn_colstats(x, ld, batch, hw, ncols, cg, coff, (long long*)gstat, (hipStream_t)stream);
-}
-int mkd_gn_apply_stats(const uint16_t* x, int ld_in, const float* gamma, const float* beta, float eps, int silu, uint16_t* y,
-                       int ld_out, int batch, int hw, int C, const int64_t* gstat, void* stream) {
-    if (!x || !y || !gamma || !beta || !gstat) return mkd_fail(MKD_ERR_ARG, "mkd_gn_apply_stats: null pointer");
-    return launch_gn_apply_stats(x, ld_in, gamma, beta, eps, silu, y, ld_out, batch, hw, C, (const long long*)gstat, (hipStream_t)stream);
-}
-int mkd_fold_layernorm(const float* w, const float* gamma, const float* beta, const float* bias, int N, int K, uint16_t* w_out,
-                       int dst_row0, int dst_row_mul, float* s_out, float* b_out, void* stream) {
-    if (!w || !gamma || !beta || !w_out || !s_out || !b_out) return mkd_fail(MKD_ERR_ARG, "mkd_fold_layernorm: null pointer");
-    return launch_fold_layernorm(w, gamma, beta, bias, N, K, w_out, dst_row0, dst_row_mul, s_out, b_out, (hipStream_t)stream);
-}
-int mkd_gemm_ln_bf16(const uint16_t* A, int lda, const uint16_t* Wfold, int ldw, const float* bias_fold, const float* ln_s,
-                     const float* row_stats, int stat_slots, float eps, int act, void* C, int ldc, int M, int N, int K, void* stream) {
-    if (!A || !Wfold || !C || !ln_s) return mkd_fail(MKD_ERR_ARG, "mkd_gemm_ln_bf16: null pointer");          // row_stats null: on the fly
-    if (!g_zero) {
-        MKD_HIP_CHECK(hipMalloc((void**)&g_zero, 4096));
-        MKD_HIP_CHECK(hipMemset(g_zero, 0, 4096));
-    }
-    GemmArgs a; memset(&a, 0, sizeof(a));
-    a.A = A; a.lda = lda; a.W = Wfold; a.ldw = ldw; a.bias = bias_fold; a.scale = 1.f; a.act = act; a.C = C; a.ldc = ldc;
-    a.M = M; a.N = N; a.K = K; a.rows_per_batch = 1; a.zero = g_zero; a.ln_s = ln_s; a.ln_eps = eps;
-    a.stat_in = row_stats; a.stat_in_slots = stat_slots;
-    return launch_gemm(a, (hipStream_t)stream);
-}
-int mkd_gemm_rowstats_bf16(const uint16_t* A, int lda, const uint16_t* W, int ldw, const float* bias, const uint16_t* R, int ldr,
-                           uint16_t* C, int ldc, int M, int N, int K, float* stat_out, int stat_capacity_slots, int* slots_out,
-                           void* stream) {
-    if (!A || !W || !C || !stat_out || !slots_out) return mkd_fail(MKD_ERR_ARG, "mkd_gemm_rowstats_bf16: null pointer");
-    if (!g_zero) {
-        MKD_HIP_CHECK(hipMalloc((void**)&g_zero, 4096));
-        MKD_HIP_CHECK(hipMemset(g_zero, 0, 4096));
-    }
-    const int slots = gemm_stat_slots(M, N, K);
-    if (slots > stat_capacity_slots) return mkd_fail(MKD_ERR_ARG, "mkd_gemm_rowstats_bf16: statistics buffer too small");
-    *slots_out = slots;
-    GemmArgs a; memset(&a, 0, sizeof(a));
-    a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.bias = bias; a.R = R; a.ldr = ldr; a.scale = 1.f; a.C = C; a.ldc = ldc;
-    a.M = M; a.N = N; a.K = K; a.rows_per_batch = 1; a.zero = g_zero; a.stat_out = stat_out;
-    int cfg_i = 0, s = 1;
-    int rc = gemm_resolve(a, &cfg_i, &s);
-    if (rc) return rc;
-    rc = scratch(&g_ws, &g_ws_bytes, gemm_ws_bytes(M, N, s > 1 ? s : 2));
-    if (rc) return rc;
-    a.ws = g_ws; a.ws_bytes = g_ws_bytes;
-    return launch_gemm(a, (hipStream_t)stream);
-}
-int mkd_groupnorm(const uint16_t* x, int ld_in, const float* gamma, const float* beta, float eps, int silu, uint16_t* y,
-                  int ld_out, int batch, int hw, int C, int groups, void* stream) {
-    int rc = scratch(&g_gn, &g_gn_bytes, groupnorm_partials_bytes(batch, hw, groups));
-    if (rc) return rc;
-    return launch_groupnorm(x, ld_in, gamma, beta, eps, silu, y, ld_out, batch, hw, C, groups, g_gn, (hipStream_t)stream);
-}
-int mkd_layernorm(const uint16_t* x, const float* gamma, const float* beta, float eps, uint16_t* y, int rows, int d, void* stream) {
-    return launch_layernorm(x, gamma, beta, eps, y, rows, d, (hipStream_t)stream);
-}
-int mkd_layernorm_ld(const uint16_t* x, int ldx, const float* gamma, const float* beta, float eps, uint16_t* y, int rows, int d, void* stream) {
-    return launch_layernorm(x, gamma, beta, eps, y, rows, d, (hipStream_t)stream, ldx);
-}
-int mkd_attention(const uint16_t* q, int ldq, const uint16_t* k, int ldk, const uint16_t* v, int ldv, uint16_t* o, int ldo,
-                  int batch, int Tq, int Tk, int heads, int dh, float scale, void* stream) {
-    return launch_attention(q, ldq, k, ldk, v, ldv, o, ldo, batch, Tq, Tk, heads, dh, scale, (hipStream_t)stream);
-}
-int mkd_attention_causal(const uint16_t* q, int ldq, const uint16_t* k, int ldk, const uint16_t* v, int ldv, uint16_t* o, int ldo,
-                         int batch, int Tq, int Tk, int heads, int dh, float scale, void* stream) {
-    return launch_attention(q, ldq, k, ldk, v, ldv, o, ldo, batch, Tq, Tk, heads, dh, scale, (hipStream_t)stream, 1);
-}
-int mkd_geglu(const uint16_t* x, uint16_t* y, int rows, int inner, void* stream) {
-    return launch_geglu(x, y, rows, inner, (hipStream_t)stream);
-}
-int mkd_conv3x3_direct(const void* x, int in_nchw_f32, const uint16_t* w, const float* bias, void* y, int out_nchw_f32, int act,
-                       const uint16_t* add, int batch, int Hin, int Win, int Cin, int Cout, int stride, void* stream) {
-    return launch_conv3x3_direct(x, in_nchw_f32, w, bias, y, out_nchw_f32, act, add, batch, Hin, Win, Cin, Cout, stride,
-                                 (hipStream_t)stream);
-}
-int mkd_pack_conv_weight(const float* w, uint16_t* out, int Cout, int Cin, int kh, int kw, void* stream) {
-    return launch_pack_conv_weight(w, out, Cout, Cin, kh, kw, (hipStream_t)stream);
-}
-
-// ---- fused transformer tail, stand-alone (unit parity test, tools/bench_tfm_tail.py) ------------------------------------------
-struct mkd_tfm_tail { int d = 0; bf16_t* wpk = nullptr; float* vec = nullptr; bf16_t* kvp = nullptr; int kv_batch = 0, Tk = 0; std::vector<void*> owned; };
-void mkd_tfm_tail_destroy(mkd_tfm_tail* h) {
-    if (!h) return;
-    for (void* p : h->owned) hipFree(p);
-    delete h;
-}
-int mkd_tfm_tail_create(int d, const float* to_out1_w, const float* to_out1_b, const float* norm2_g, const float* norm2_b,
-                        const float* to_q2_w, const float* to_out2_w, const float* to_out2_b, const float* norm3_g, const float* norm3_b,
-                        const float* ff0_w, const float* ff0_b, const float* ff2_w, const float* ff2_b, const float* proj_out_w,
-                        const float* proj_out_b, mkd_tfm_tail** out) {
-    if (!out) return mkd_fail(MKD_ERR_ARG, "null out");
-    if (!tfm_tail_weight_bytes(d)) return mkd_fail(MKD_ERR_UNSUPPORTED, "tfm_tail: only d = 320 is built");
-    mkd_tfm_tail* h = new mkd_tfm_tail; h->d = d;
-    const AllocFn dal = [h](void** o, size_t bytes) -> int { MKD_HIP_CHECK(hipMalloc(o, bytes)); h->owned.push_back(*o); return 0; };
-    void *wo1 = nullptr, *wo2 = nullptr;
-    Folded q2, ffg; bf16_t* wm = nullptr; float* bm = nullptr;
-    const size_t dd = (size_t)d * d;
-    int rc = dal(&wo1, dd * 2);
-    if (!rc) rc = dal(&wo2, dd * 2);
-    if (!rc) rc = dal((void**)&h->wpk, tfm_tail_weight_bytes(d));
-    if (!rc) rc = dal((void**)&h->vec, tfm_tail_vec_bytes(d));
-    if (!rc) rc = launch_f32_to_bf16(to_out1_w, (bf16_t*)wo1, (int64_t)dd, 0);
-    if (!rc) rc = launch_f32_to_bf16(to_out2_w, (bf16_t*)wo2, (int64_t)dd, 0);
-    if (!rc) rc = fold_ln2_q(to_q2_w, norm2_g, norm2_b, d, dal, &q2);
-    if (!rc) rc = fold_ln3_geglu(ff0_w, ff0_b, norm3_g, norm3_b, d, dal, &ffg);
-    if (!rc) rc = merge_ff_out(proj_out_w, ff2_w, ff2_b, proj_out_b, d, dal, &wm, &bm);
-    if (!rc) {
-        TfmTailWeights s{(const bf16_t*)wo1, to_out1_b, q2.w, q2.s, q2.b, (const bf16_t*)wo2, to_out2_b, ffg.w, ffg.s, ffg.b, wm, bm};
-        rc = tfm_tail_pack_weights(d, s, h->wpk, h->vec, 0);
-    }
-    if (rc) { mkd_tfm_tail_destroy(h); return rc; }
-    *out = h;
-    return 0;
-}
-/* experiment builds (-DMKD_TFM_TRACE) only: device buffer [workgroups][8][32] of int64 time stamps; a no-op in the product build */
-int mkd_debug_tfm_trace(long long* buf) { tfm_tail_set_trace(buf); return 0; }
-int mkd_debug_attn_trace(long long* buf) { return attn_set_trace(buf); }
-int mkd_tfm_tail_set_context(mkd_tfm_tail* h, const uint16_t* kv, int ldkv, int batch, int Tk, void* stream) {
-    if (!h) return mkd_fail(MKD_ERR_ARG, "null handle");
-    if (batch > h->kv_batch) {
-        void* p = nullptr;
-        MKD_HIP_CHECK(hipMalloc(&p, tfm_tail_kv_bytes(h->d, batch)));
-        h->owned.push_back(p); h->kvp = (bf16_t*)p; h->kv_batch = batch;
-    }
-    h->Tk = Tk;
-    return launch_tfm_tail_pack_kv(h->d, kv, ldkv, batch, Tk, h->kvp, (hipStream_t)stream);
-}
-int mkd_tfm_tail_run(mkd_tfm_tail* h, const uint16_t* a1, int lda, const uint16_t* h0, int ldh, const uint16_t* xin, int ldx, uint16_t* out,
-                     int ldo, int M, int T, void* stream) {
-    if (!h || !h->kvp) return mkd_fail(MKD_ERR_STATE, "tfm_tail: set the context first");
-    if (T <= 0 || M % T || M / T > h->kv_batch) return mkd_fail(MKD_ERR_ARG, "tfm_tail: M must be samples x T within the packed context");
-    return launch_tfm_tail(h->d, h->wpk, h->vec, a1, lda, h0, ldh, xin, ldx, h->kvp, out, ldo, M, T, h->Tk, (hipStream_t)stream);
-}
-
-// ---- fused transformer head, stand-alone (unit parity test) ---------------------------------------------------------------------
-struct mkd_tfm_head { int d = 0; bf16_t* wpk = nullptr; float* vec = nullptr; float* part = nullptr; size_t part_bytes = 0; std::vector<void*> owned; };
-void mkd_tfm_head_destroy(mkd_tfm_head* h) {
-    if (!h) return;
-    for (void* p : h->owned) hipFree(p);
-    delete h;
-}
-int mkd_tfm_head_create(int d, const float* gn_g, const float* gn_b, const float* proj_in_w, const float* proj_in_b, const float* norm1_g,
-                        const float* norm1_b, const float* to_q_w, const float* to_k_w, const float* to_v_w, mkd_tfm_head** out) {
-    if (!out) return mkd_fail(MKD_ERR_ARG, "null out");
-    if (!tfm_head_weight_bytes(d)) return mkd_fail(MKD_ERR_UNSUPPORTED, "tfm_head: only d = 320 is built");
-    mkd_tfm_head* h = new mkd_tfm_head; h->d = d;
-    const AllocFn dal = [h](void** o, size_t bytes) -> int { MKD_HIP_CHECK(hipMalloc(o, bytes)); h->owned.push_back(*o); return 0; };
-    void* wpi = nullptr; Folded qkv;
-    const size_t dd = (size_t)d * d;
-    int rc = dal(&wpi, dd * 2);
-    if (!rc) rc = dal((void**)&h->wpk, tfm_head_weight_bytes(d));
-    if (!rc) rc = dal((void**)&h->vec, tfm_head_vec_bytes(d));
-    if (!rc) rc = launch_f32_to_bf16(proj_in_w, (bf16_t*)wpi, (int64_t)dd, 0);
-    if (!rc) rc = fold_ln1_qkv(to_q_w, to_k_w, to_v_w, norm1_g, norm1_b, d, dal, &qkv);
-    if (!rc) {
-        TfmHeadWeights s{gn_g, gn_b, (const bf16_t*)wpi, proj_in_b, qkv.w, qkv.s, qkv.b};
-        rc = tfm_head_pack_weights(d, s, h->wpk, h->vec, 0);
-    }
-    if (rc) { mkd_tfm_head_destroy(h); return rc; }
-    *out = h;
-    return 0;
-}
-int mkd_tfm_head_run(mkd_tfm_head* h, const uint16_t* x, int ldx, float gn_eps, uint16_t* h0, uint16_t* qkv, int batch, int T, void* stream) {
-    if (!h) return mkd_fail(MKD_ERR_ARG, "null handle");
-    const size_t need = groupnorm_partials_bytes(batch, T, 32);
-    if (need > h->part_bytes) {
-        void* p = nullptr;
-        MKD_HIP_CHECK(hipMalloc(&p, need));
-        h->owned.push_back(p); h->part = (float*)p; h->part_bytes = need;
-    }
-    int nch = 0;
-    int rc = launch_gn_stats(x, ldx, batch, T, h->d, 32, h->part, (hipStream_t)stream, &nch);
-    if (rc) return rc;
-    return launch_tfm_head(h->d, h->wpk, h->vec, x, ldx, h->part, nch, gn_eps, h0, qkv, batch * T, T, (hipStream_t)stream);
-}
 
 }  // extern "C"
