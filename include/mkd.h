@@ -415,6 +415,36 @@ size_t mkd_label_components_scratch_bytes(int batch, int H, int W);
  * 1 <= max_out <= 64, min_area >= 1, labels / table / count / scratch non-null and the scratch 256-byte aligned. */
 int mkd_label_components(const uint8_t* labels, int batch, int H, int W, uint64_t classes, int min_area, int max_out,
                          mkd_component* table, int32_t* count, int32_t* ids_out, void* scratch, void* stream);
+/* ---- which face owns which pixel: the nearest table component of every pixel (BUILD-DEFINED, as the rest of the group-photo path) ---- */
+/* Bytes of device scratch mkd_owner_map needs (0 for bad arguments: the limits below): the column pass's distance (uint16) and rank
+ * (uint8) per pixel, each rounded up to 256 bytes.  The scratch must be 256-byte aligned; its contents before the call do not matter
+ * and it may be reused by the next call on the same stream. */
+size_t mkd_owner_map_scratch_bytes(int batch, int H, int W);
+/* Exact Euclidean feature transform.  ids [batch, H, W] int32 device in the form mkd_label_components writes it (the component id at
+ * in-pixels, -1 elsewhere), table [batch][max_out] the table of the same call.  The SEEDS of rank r (0 <= r < max_out) of image b are
+ * the pixels whose id equals table[b][r].id, for rows with id >= 0; pixels of components that are not in the table (below min_area, or
+ * cut off by max_out) are not seeds; of rows that repeat an id the lowest counts.  owner [batch, H, W] uint8 = the rank r that
+ * minimises D_r = min over the seeds (v, u) of rank r of (y - v)^2 + (x - u)^2, ties between ranks to the LOWER rank; dist2_out
+ * [batch, H, W] int32 or NULL = that minimum.  An image without seeds: owner 255, dist2 INT32_MAX.  The metric is that of the grid
+ * the ids live on: face_parser.find_faces squashes a photo to parse_size x parse_size, so in PHOTO pixels the metric is anisotropic
+ * (a non-square photo's nearer face is the nearer one of the squashed map).  Integer arithmetic only: the outputs are exact and the
+ * same bytes on every run.  No context, no host sync, no allocation, no atomics; 2 launches (per column the nearest seed up or down
+ * into the scratch, then per row the smallest (distance, rank) over the columns, scanned outwards from the pixel until the column
+ * offset alone exceeds the best distance), and no workgroup waits for another.  MKD_ERR_ARG before anything is enqueued unless
+ * 1 <= batch <= 65535, 1 <= H, W <= 2048 (d^2 < 2^23; a row of the intermediate fits in LDS), 1 <= max_out <= 64, ids / table / owner /
+ * scratch non-null and the scratch 256-byte aligned. */
+int mkd_owner_map(const int32_t* ids, const mkd_component* table, int batch, int H, int W, int max_out, uint8_t* owner,
+                  int32_t* dist2_out, void* scratch, void* stream);
+/* One face's share of its neighbourhood: items HOST int32 [n][2] = (image, rank), copied into the kernel argument block by value;
+ * w_out [n, H, W] fp32: w_out[i][y][x] = float(S) / float((2 rho + 1)^2) with S = the pixels of the (2 rho + 1)^2 window around (y, x),
+ * indices clamped to the edge, whose owner [batch, H, W] (mkd_owner_map) equals item i's rank in item i's image -- the window-fraction
+ * rule of mkd_region_weights and mkd_paste_background; integers and one division.  feather rho = 0 is the 0 / 1 indicator.  No context;
+ * one launch, no scratch, no atomics, no host sync, no allocation.  MKD_ERR_ARG before anything is enqueued unless 1 <= n <=
+ * MKD_OWNER_MAX_ITEMS, 0 <= feather <= 16, 1 <= batch <= 65535, 1 <= H, W <= 2048, every image in 0 .. batch - 1 and every rank in
+ * 0 .. 63, owner / items / w_out non-null. */
+#define MKD_OWNER_MAX_ITEMS 16          /* = MKD_PHOTO_MAX_BATCH: one weight plane per descriptor of a paste */
+int mkd_owner_weights(const uint8_t* owner, int batch, int H, int W, const int32_t* items, int n, int feather, float* w_out,
+                      void* stream);
 /* Bytes of device scratch mkd_hist_match needs for n terms (0 for n <= 0).  The scratch must be 256-byte aligned; its contents
  * before the call do not matter and it may be reused by the next call on the same stream. */
 size_t mkd_hist_match_scratch_bytes(int n);
@@ -484,6 +514,15 @@ int mkd_resize_coeffs(int N, int in0, int len, int S, int32_t* bounds_out, int32
  * Bilinear is linear, so this is up(result) + (photo - up(small source)): only the difference is interpolated.  Inputs are finite.
  * No context; one launch, no scratch, no allocation, no host sync, no atomics. */
 int mkd_paste_photo(const mkd_photo_desc* descs, int n, int S, const float* t, const float* s01, int feather, void* stream);
+/* mkd_paste_photo with one more factor: w fp32 [n, wh, ww] device, a low-resolution weight over the WHOLE photo of descriptor b (not
+ * over its box; e.g. mkd_owner_weights on the squashed photo's grid).  Per photo pixel (X, Y) the axis rule above runs on the photo:
+ * numx = (2 X + 1) ww - W; denx = 2 W (likewise Y, H, wh; |num| < 2^27 and rem < den <= 32768 hold for W <= 16384, ww <= 2048), which
+ * gives the four neighbours w00 .. w11 and the weights ux, uy; then, every line ONE correctly rounded fp32 operation,
+ * g = lerp(lerp(w00, w01, ux), lerp(w10, w11, ux), uy) with lerp(p, q, v) = p + v (q - p);  a' = a g;  o = float(photo) + a' u, and the
+ * rest as above.  g = 0 leaves the photo's byte as it is (rint(photo + 0) is the byte); w = 1 everywhere gives mkd_paste_photo's
+ * bytes.  1 <= wh, ww <= 2048, w non-null, else MKD_ERR_ARG; everything else as mkd_paste_photo.  One launch. */
+int mkd_paste_photo_weighted(const mkd_photo_desc* descs, int n, int S, const float* t, const float* s01, int feather, const float* w,
+                             int wh, int ww, void* stream);
 
 /* ---- first-stage decoder ------------------------------------------------ */
 /* yaml first_stage_config.params.ddconfig (diffmodels/base_diffusion_makeup.yaml:86-107), decoder half only. */

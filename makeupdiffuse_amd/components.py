@@ -1,7 +1,9 @@
 """Connected components of a label map on the device (include/mkd.h mkd_label_components): the 8-connected sets of the pixels whose
 label is in a class set, with id (smallest linear index), area and inclusive bounding box each, the largest ``max_out`` as a table.
-What face_parser.find_faces builds on: one component of the face classes is one face.  Integer arithmetic only, so the outputs are
-exact and the same bytes on every run.  The arithmetic is libmkd's: there is no CPU path."""
+What face_parser.find_faces builds on: one component of the face classes is one face.  owner_map (mkd_owner_map) then gives every
+pixel the table component nearest to it and owner_weights (mkd_owner_weights) each component's share of a pixel's neighbourhood:
+what keeps one face's paste off its neighbour.  Integer arithmetic only (one division per weight), so the outputs are exact and the
+same bytes on every run.  The arithmetic is libmkd's: there is no CPU path."""
 from __future__ import annotations
 
 import ctypes as C
@@ -64,3 +66,73 @@ def label_components(labels: torch.Tensor, classes: Sequence[int], min_area: int
                                             C.c_void_p(None if ids is None else ids.data_ptr()), C.c_void_p(base),
                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'mkd_label_components')
     return table, count, ids
+
+
+NO_OWNER = 255                                   # owner of every pixel of an image without seeds
+NO_DIST = 2 ** 31 - 1
+MAX_SIDE = 2048                                  # mkd_owner_map / mkd_owner_weights: H, W
+MAX_ITEMS = 16                                   # (image, rank) planes per mkd_owner_weights call; more are split here
+MAX_OWNER_FEATHER = 16
+
+
+def owner_map(ids: torch.Tensor, table: torch.Tensor, want_dist: bool = False):
+    """ids int32 [B,H,W] and table int32 [B,max_out,6] of ONE label_components call (device tensors) -> owner uint8 [B,H,W]: the rank
+    (table row) of the component nearest to every pixel in the exact Euclidean metric of the ids' own grid, ties to the lower rank;
+    NO_OWNER in an image whose table is empty.  Only components IN the table are seeds.  want_dist: (owner, dist2 int32 [B,H,W]), the
+    squared distance (NO_DIST without seeds).  Nothing is read back: the call only enqueues (two launches)."""
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 3:
+        raise ValueError(f'ids must be int32 [B,H,W], got {getattr(ids, "dtype", type(ids))} {tuple(getattr(ids, "shape", ()))}')
+    B, H, W = (int(v) for v in ids.shape)
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 3 or table.shape[0] != B or table.shape[2] != ROW \
+            or not 1 <= table.shape[1] <= MAX_OUT:
+        raise ValueError(f'table must be int32 [{B},1..{MAX_OUT},{ROW}], got {getattr(table, "dtype", type(table))} {tuple(getattr(table, "shape", ()))}')
+    if ids.device.type != 'cuda' or table.device != ids.device:
+        raise _lib.MkdError('owner_map: ids and table must be on one HIP device (there is no CPU implementation)')
+    if B < 1 or not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        raise ValueError(f'ids {tuple(ids.shape)}: B >= 1 and H, W in 1..{MAX_SIDE}')
+    ids, table = ids.contiguous(), table.contiguous()
+    dev = ids.device
+    lib = _lib.load()
+    owner = torch.empty((B, H, W), device=dev, dtype=torch.uint8)
+    dist = torch.empty((B, H, W), device=dev, dtype=torch.int32) if want_dist else None
+    nbytes = int(lib.mkd_owner_map_scratch_bytes(B, H, W))
+    if nbytes <= 0:
+        raise _lib.MkdError('mkd_owner_map_scratch_bytes refused the shape')
+    scratch = torch.empty((nbytes + 256,), device=dev, dtype=torch.uint8)          # (the stream keeps it alive until the kernels ran)
+    base = (scratch.data_ptr() + 255) & ~255
+    with torch.cuda.device(dev):
+        _lib.check(lib.mkd_owner_map(C.c_void_p(ids.data_ptr()), C.c_void_p(table.data_ptr()), B, H, W, int(table.shape[1]),
+                                     C.c_void_p(owner.data_ptr()), C.c_void_p(None if dist is None else dist.data_ptr()), C.c_void_p(base),
+                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'mkd_owner_map')
+    return (owner, dist) if want_dist else owner
+
+
+def owner_weights(owner: torch.Tensor, items: Sequence[Tuple[int, int]], feather: int = 2) -> torch.Tensor:
+    """owner uint8 [B,H,W] (owner_map) and items [(image, rank), ...] -> fp32 [len(items),H,W]: per item the fraction of the
+    (2 feather + 1)^2 window around every pixel (indices clamped to the edge) that image's rank owns; feather 0 is the 0 / 1
+    indicator.  One launch per MAX_ITEMS items; nothing is read back."""
+    if not isinstance(owner, torch.Tensor) or owner.dtype != torch.uint8 or owner.dim() != 3:
+        raise ValueError(f'owner must be uint8 [B,H,W], got {getattr(owner, "dtype", type(owner))} {tuple(getattr(owner, "shape", ()))}')
+    if owner.device.type != 'cuda':
+        raise _lib.MkdError('owner_weights: owner must be on a HIP device (there is no CPU implementation)')
+    rho = int(feather)
+    if rho != feather or not 0 <= rho <= MAX_OWNER_FEATHER:
+        raise ValueError(f'feather must be an integer 0..{MAX_OWNER_FEATHER}, got {feather!r}')
+    B, H, W = (int(v) for v in owner.shape)
+    items = [(int(i), int(r)) for i, r in items]
+    if not items:
+        raise ValueError('owner_weights: no items')
+    for i, r in items:
+        if not 0 <= i < B or not 0 <= r < MAX_OUT:
+            raise ValueError(f'item {(i, r)}: the image must lie in 0..{B - 1} and the rank in 0..{MAX_OUT - 1}')
+    owner = owner.contiguous()
+    dev = owner.device
+    lib = _lib.load()
+    out = torch.empty((len(items), H, W), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        for n0 in range(0, len(items), MAX_ITEMS):
+            part = items[n0:n0 + MAX_ITEMS]
+            flat = (C.c_int32 * (2 * len(part)))(*[v for it in part for v in it])
+            _lib.check(lib.mkd_owner_weights(C.c_void_p(owner.data_ptr()), B, H, W, flat, len(part), rho, C.c_void_p(out[n0:].data_ptr()),
+                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'mkd_owner_weights')
+    return out

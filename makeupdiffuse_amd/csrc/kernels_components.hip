@@ -14,6 +14,7 @@
 //      roots append themselves to the image's root list (the ORDER of that list is arrival-dependent, nothing read from it is).
 //   4. cc_select_kernel: one workgroup per image: keys (area << 32) | ~id of the roots with area >= min_area, then max_out rounds of a
 //      block-wide maximum below the previous round's key: area descending, ties by id ascending.
+// Further down: mkd_owner_map (the nearest table component of every pixel, two launches) and mkd_owner_weights (its window fractions).
 #include "mkd_common.h"
 #include "../../include/mkd.h"
 
@@ -337,7 +338,265 @@ const char* cc_check(int batch, int H, int W) {
     return nullptr;
 }
 
+// ---- owner map (mkd_owner_map): the nearest table component of every pixel ------------------------------------------------------------
+// Exact Euclidean feature transform in two separable passes with a kernel boundary between them.  For pixel (y, x) and column u the
+// nearest seed OF COLUMN u is g[y][u] rows away, so min over all seeds of (d^2, rank) = min over u of ((x - u)^2 + g[y][u]^2, the lowest
+// rank among column u's seeds at that distance) -- at most two seeds of a column are g rows away (one up, one down), and a seed
+// further than g from row y in its column never attains the minimum over its column.
+//   1. om_column_kernel: a workgroup owns 64 consecutive columns (one per lane: every row access is coalesced) and OM_SEG row segments,
+//      one wave each, so a column's sweeps are OM_SEG times shorter than its height.  Sweep down over the own segment: g = rows since
+//      the segment's last seed; the segment's first and last seed go to LDS.  After the barrier, sweep up over what the first sweep
+//      wrote (a seed is g == 0), starting from the first seed of the segments below and with the last seed of the segments above
+//      standing in where the own segment had none yet: the nearer of the two, on a tie the lower rank.  The id -> rank lookup runs
+//      over the image's table rows in LDS (up to the last row that holds an id), only where the id changes along the column.
+//   2. om_row_kernel: one workgroup per (row, image) with the row's g and rank in LDS; a thread scans u = x, x -+ 1, x -+ 2, ... and keeps
+//      the smallest key (d^2 << 8) | rank; it stops once off^2 alone exceeds the best d^2 (a column at an equal off^2 may still hold
+//      the same d^2 with a lower rank, so equality goes on).  d^2 <= 2 * 2047^2 < 2^23: the key fits 31 bits.
+constexpr int OM_MAX_SIDE = 2048;
+constexpr int OM_COLS = 64;               // columns of a workgroup of the column pass: one per lane
+constexpr int OM_SEG = 8;                 // row segments of a column: one wave each
+constexpr int OM_COL_NT = OM_COLS * OM_SEG;
+constexpr int OM_ROW_NT = 256;
+constexpr int OM_CHUNK = 8;               // rows whose loads the column pass issues together
+constexpr unsigned OM_NONE = 0xffffu;     // g: the column holds no seed (in that direction)
+constexpr unsigned OM_NO_RANK = 255u;
+
+__host__ __device__ inline size_t om_round256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+__global__ __launch_bounds__(OM_COL_NT) void om_column_kernel(const int32_t* __restrict__ ids, const mkd_component* __restrict__ table, int H, int W,
+                                                              int max_out, uint16_t* __restrict__ g_out, uint8_t* __restrict__ rank_out) {
+    __shared__ int s_id[CC_MAX_OUT];
+    __shared__ int s_rows;                                 // 1 + the last table row that holds an id
+    __shared__ int s_first[OM_SEG][OM_COLS], s_last[OM_SEG][OM_COLS];          // a segment's first / last seed: (y << 8) | rank, -1: none
+    const int b = blockIdx.y;
+    if (threadIdx.x < OM_COLS) {                           // (wave 0)
+        const int id = (int)threadIdx.x < max_out ? table[(size_t)b * max_out + threadIdx.x].id : -1;
+        s_id[threadIdx.x] = id;
+        const unsigned long long held = __ballot(id >= 0);
+        if (threadIdx.x == 0) s_rows = held ? 64 - __clzll((long long)held) : 0;
+    }
+    __syncthreads();
+    const int rows = s_rows;
+    const int lane = threadIdx.x & (OM_COLS - 1), seg = threadIdx.x / OM_COLS;
+    const int x = blockIdx.x * OM_COLS + lane;
+    const int per = (H + OM_SEG - 1) / OM_SEG;
+    const int ya = min(seg * per, H), yb = min(ya + per, H);          // this thread's rows [ya, yb): empty past the image
+    const bool active = x < W;
+    const size_t base = (size_t)b * H * W + (active ? x : 0);
+    const int32_t* idc = ids + base;
+    uint16_t* gc = g_out + base;
+    uint8_t* rc = rank_out + base;
+    int first = -1, last = -1;
+    if (active) {
+        int last_id = -1;
+        unsigned last_rank = OM_NO_RANK;                   // the rank of last_id
+        for (int y0 = ya; y0 < yb; y0 += OM_CHUNK) {
+            int v[OM_CHUNK];
+#pragma unroll
+            for (int k = 0; k < OM_CHUNK; ++k) v[k] = y0 + k < yb ? idc[(size_t)(y0 + k) * W] : -1;
+#pragma unroll
+            for (int k = 0; k < OM_CHUNK; ++k) {
+                const int y = y0 + k;
+                if (y >= yb) break;
+                if (v[k] >= 0) {
+                    if (v[k] != last_id) {
+                        last_id = v[k];
+                        last_rank = OM_NO_RANK;
+                        for (int r = 0; r < rows; ++r)
+                            if (s_id[r] == last_id) {      // the lowest row of a repeated id
+                                last_rank = (unsigned)r;
+                                break;
+                            }
+                    }
+                    if (last_rank != OM_NO_RANK) {
+                        last = (y << 8) | (int)last_rank;
+                        if (first < 0) first = last;
+                    }
+                }
+                gc[(size_t)y * W] = (uint16_t)(last < 0 ? OM_NONE : (unsigned)(y - (last >> 8)));
+                rc[(size_t)y * W] = (uint8_t)(last < 0 ? OM_NO_RANK : (unsigned)(last & 255));
+            }
+        }
+    }
+    s_first[seg][lane] = first;
+    s_last[seg][lane] = last;
+    __syncthreads();
+    if (!active) return;                                   // (after the last barrier)
+    int above = -1, below = -1;                            // the nearest seed of the segments above / below this one
+    for (int s = seg - 1; s >= 0 && above < 0; --s) above = s_last[s][lane];
+    for (int s = seg + 1; s < OM_SEG && below < 0; ++s) below = s_first[s][lane];
+    // up: a thread reads back its own stores only
+    for (int y1 = yb - 1; y1 >= ya; y1 -= OM_CHUNK) {
+        unsigned gd[OM_CHUNK], rd[OM_CHUNK];
+#pragma unroll
+        for (int k = 0; k < OM_CHUNK; ++k) {
+            gd[k] = y1 - k >= ya ? gc[(size_t)(y1 - k) * W] : OM_NONE;
+            rd[k] = y1 - k >= ya ? rc[(size_t)(y1 - k) * W] : OM_NO_RANK;
+        }
+#pragma unroll
+        for (int k = 0; k < OM_CHUNK; ++k) {
+            const int y = y1 - k;
+            if (y < ya) break;
+            if (gd[k] == 0u) {
+                below = (y << 8) | (int)rd[k];
+                continue;
+            }
+            unsigned g = gd[k], r = rd[k];
+            if (g == OM_NONE && above >= 0) {              // no seed of the own segment above this row
+                g = (unsigned)(y - (above >> 8));
+                r = (unsigned)(above & 255);
+            }
+            if (below >= 0) {
+                const unsigned du = (unsigned)((below >> 8) - y), ru = (unsigned)(below & 255);
+                if (du < g || (du == g && ru < r)) {       // OM_NONE is larger than every distance
+                    g = du;
+                    r = ru;
+                }
+            }
+            if (g != gd[k] || r != rd[k]) {
+                gc[(size_t)y * W] = (uint16_t)g;
+                rc[(size_t)y * W] = (uint8_t)r;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(OM_ROW_NT) void om_row_kernel(const uint16_t* __restrict__ g_in, const uint8_t* __restrict__ rank_in, int H, int W,
+                                                           uint8_t* __restrict__ owner, int32_t* __restrict__ dist2_out) {
+    __shared__ uint16_t s_g[OM_MAX_SIDE];
+    __shared__ uint8_t s_r[OM_MAX_SIDE];
+    const size_t row = ((size_t)blockIdx.y * H + blockIdx.x) * W;
+    for (int x = threadIdx.x; x < W; x += OM_ROW_NT) {
+        s_g[x] = g_in[row + x];
+        s_r[x] = rank_in[row + x];
+    }
+    __syncthreads();
+    for (int x = threadIdx.x; x < W; x += OM_ROW_NT) {
+        unsigned best = 0xffffffffu;                       // (best >> 8 = 2^24 - 1 exceeds every off^2 <= 2047^2)
+        const int reach = max(x, W - 1 - x);
+        for (int off = 0; off <= reach; ++off) {
+            const unsigned o2 = (unsigned)(off * off);
+            if (o2 > (best >> 8)) break;
+            const int l = x - off, r = x + off;
+            if (l >= 0) {
+                const unsigned g = s_g[l];
+                if (g != OM_NONE) best = min(best, ((o2 + g * g) << 8) | s_r[l]);
+            }
+            if (off > 0 && r < W) {
+                const unsigned g = s_g[r];
+                if (g != OM_NONE) best = min(best, ((o2 + g * g) << 8) | s_r[r]);
+            }
+        }
+        const bool none = best == 0xffffffffu;
+        owner[row + x] = (uint8_t)(none ? OM_NO_RANK : (best & 255u));
+        if (dist2_out) dist2_out[row + x] = none ? INT_MAX : (int32_t)(best >> 8);
+    }
+}
+
+const char* om_check(int batch, int H, int W) {
+    if (batch < 1 || batch > 65535) return "batch must be 1..65535";
+    if (H < 1 || W < 1 || H > OM_MAX_SIDE || W > OM_MAX_SIDE) return "H, W must be 1..2048";
+    return nullptr;
+}
+
+// ---- owner weights (mkd_owner_weights): the window fraction of one (image, rank) per plane -----------------------------------------
+// The three phases of paste_background_kernel (kernels_region.hip) on an indicator: the tile's owner == rank flags plus a halo of
+// rho, clamped to the edge once, here (uint8 [(16 + 2 rho)][(64 + 2 rho)]); horizontal window sums (uint16 [(16 + 2 rho)][64]); 2 rho + 1
+// rows of those per output pixel.  S <= 33^2: exact in fp32, one division.
+constexpr int OW_TW = 64, OW_TH = 16, OW_MAX_FEATHER = 16;
+struct OwArgs {
+    int image[MKD_OWNER_MAX_ITEMS];
+    int rank[MKD_OWNER_MAX_ITEMS];
+};
+
+__global__ __launch_bounds__(256) void owner_weights_kernel(const uint8_t* __restrict__ owner, const OwArgs a, int H, int W, int rho, int tiles_x,
+                                                            float* __restrict__ w_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char ow_smem[];
+    const int i = blockIdx.y;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int y0 = ty * OW_TH, x0 = tx * OW_TW;
+    const int cw = OW_TW + 2 * rho, ch = OW_TH + 2 * rho, win = 2 * rho + 1;
+    uint16_t* hs = (uint16_t*)ow_smem;                                       // [ch][64]
+    uint8_t* flag = ow_smem + (size_t)ch * OW_TW * sizeof(uint16_t);         // [ch][cw]
+    const uint8_t* ob = owner + (size_t)a.image[i] * H * W;
+    const unsigned rank = (unsigned)a.rank[i];
+    for (int e = threadIdx.x; e < ch * cw; e += 256) {
+        const int ly = e / cw, lx = e - ly * cw;
+        const int py = min(max(y0 - rho + ly, 0), H - 1), px = min(max(x0 - rho + lx, 0), W - 1);
+        flag[e] = ob[(size_t)py * W + px] == rank ? 1 : 0;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < ch * OW_TW; e += 256) {
+        const int ly = e >> 6, lx = e & 63;
+        const uint8_t* row = flag + ly * cw + lx;
+        unsigned s = 0;
+        for (int d = 0; d < win; ++d) s += row[d];
+        hs[e] = (uint16_t)s;
+    }
+    __syncthreads();
+    const float D = (float)(win * win);
+    for (int e = threadIdx.x; e < OW_TH * OW_TW; e += 256) {
+        const int ly = e >> 6, lx = e & 63;
+        const int y = y0 + ly, x = x0 + lx;
+        if (y >= H || x >= W) continue;
+        unsigned s = 0;
+        for (int d = 0; d < win; ++d) s += hs[(ly + d) * OW_TW + lx];
+        w_out[((size_t)i * H + y) * W + x] = __fdiv_rn((float)s, D);
+    }
+}
+
 }  // namespace
+
+size_t mkd_owner_map_scratch_bytes(int batch, int H, int W) {
+    if (const char* e = om_check(batch, H, W)) {
+        mkd_set_error(std::string("mkd_owner_map_scratch_bytes: ") + e);
+        return 0;
+    }
+    const size_t px = (size_t)batch * H * W;
+    return om_round256(px * sizeof(uint16_t)) + om_round256(px);
+}
+
+int mkd_owner_map(const int32_t* ids, const mkd_component* table, int batch, int H, int W, int max_out, uint8_t* owner, int32_t* dist2_out,
+                  void* scratch, void* stream) {
+    const std::string who = "mkd_owner_map: ";
+    if (const char* e = om_check(batch, H, W)) return mkd_fail(MKD_ERR_ARG, who + e);
+    if (max_out < 1 || max_out > CC_MAX_OUT) return mkd_fail(MKD_ERR_ARG, who + "max_out must be 1..64");
+    if (!ids || !table || !owner) return mkd_fail(MKD_ERR_ARG, who + "null ids / table / owner");
+    if (!scratch || ((uintptr_t)scratch & 255)) return mkd_fail(MKD_ERR_ARG, who + "the scratch must be a 256-byte aligned device buffer");
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t px = (size_t)batch * H * W;
+    uint16_t* g = (uint16_t*)scratch;
+    uint8_t* rk = (uint8_t*)scratch + om_round256(px * sizeof(uint16_t));
+    hipLaunchKernelGGL(om_column_kernel, dim3((unsigned)((W + OM_COLS - 1) / OM_COLS), (unsigned)batch), dim3(OM_COL_NT), 0, st, ids, table, H, W,
+                       max_out, g, rk);
+    MKD_LAUNCH_CHECK("om_column_kernel");
+    hipLaunchKernelGGL(om_row_kernel, dim3((unsigned)H, (unsigned)batch), dim3(OM_ROW_NT), 0, st, (const uint16_t*)g, (const uint8_t*)rk, H, W, owner,
+                       dist2_out);
+    MKD_LAUNCH_CHECK("om_row_kernel");
+    return 0;
+}
+
+int mkd_owner_weights(const uint8_t* owner, int batch, int H, int W, const int32_t* items, int n, int feather, float* w_out, void* stream) {
+    const std::string who = "mkd_owner_weights: ";
+    if (const char* e = om_check(batch, H, W)) return mkd_fail(MKD_ERR_ARG, who + e);
+    if (!owner || !items || !w_out) return mkd_fail(MKD_ERR_ARG, who + "null owner / items / w_out");
+    if (n < 1 || n > MKD_OWNER_MAX_ITEMS) return mkd_fail(MKD_ERR_ARG, who + "1..16 items per call");
+    if (feather < 0 || feather > OW_MAX_FEATHER) return mkd_fail(MKD_ERR_ARG, who + "feather must be 0..16");
+    OwArgs a = {};
+    for (int i = 0; i < n; ++i) {
+        a.image[i] = items[2 * i];
+        a.rank[i] = items[2 * i + 1];
+        if (a.image[i] < 0 || a.image[i] >= batch) return mkd_fail(MKD_ERR_ARG, who + "an item's image lies outside the batch");
+        if (a.rank[i] < 0 || a.rank[i] >= CC_MAX_OUT) return mkd_fail(MKD_ERR_ARG, who + "an item's rank must be 0..63");
+    }
+    const int tiles_x = (W + OW_TW - 1) / OW_TW, tiles_y = (H + OW_TH - 1) / OW_TH;          // <= 32 * 128 tiles
+    const int ch = OW_TH + 2 * feather, cw = OW_TW + 2 * feather;
+    const size_t lds = ((size_t)ch * OW_TW * sizeof(uint16_t) + (size_t)ch * cw + 15) & ~(size_t)15;          // <= 10752
+    hipLaunchKernelGGL(owner_weights_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)n), dim3(256), lds, (hipStream_t)stream, owner, a, H, W,
+                       feather, tiles_x, w_out);
+    MKD_LAUNCH_CHECK("owner_weights_kernel");
+    return 0;
+}
 
 size_t mkd_label_components_scratch_bytes(int batch, int H, int W) {
     if (const char* e = cc_check(batch, H, W)) {

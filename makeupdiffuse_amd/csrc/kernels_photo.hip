@@ -13,6 +13,7 @@
 // Paste: one launch, a thread owns one photo pixel column of a 64 x 16 box tile (4 rows); the model-resolution difference
 // d = ((t + 1) 0.5 - s01) 255 is formed on the fly from the L2-resident tensors.  Every fp32 operation is one correctly rounded step:
 // products that feed an addition pass through an empty asm statement (kernels_region.hip, paste_background_kernel).
+// mkd_paste_photo_weighted is the same kernel's second instantiation: the feather weight times a bilinear sample of a photo-wide plane.
 #include "mkd_common.h"
 #include "../../include/mkd.h"
 
@@ -204,8 +205,11 @@ __device__ __forceinline__ float pp_lerp(float a, float b, float w) {
     return __fadd_rn(a, pp_rounded(__fmul_rn(w, __fsub_rn(b, a))));
 }
 
+// WEIGHTED (mkd_paste_photo_weighted): the feather weight is multiplied by g, the bilinear sample of the photo-wide weight plane
+// w [n][wh][ww] at the photo pixel (pp_axis on the photo's own axes); w, wh and ww are not read otherwise.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void paste_photo_kernel(const PpArgs a, int S, const float* __restrict__ t, const float* __restrict__ s01,
-                                                          int rho) {
+                                                          int rho, const float* __restrict__ w, int wh, int ww) {
     const int b = blockIdx.z;
     const mkd_photo_desc d = a.d[b];
     const int j = blockIdx.x * PP_TW + (threadIdx.x & (PP_TW - 1));
@@ -219,6 +223,13 @@ __global__ __launch_bounds__(256) void paste_photo_kernel(const PpArgs a, int S,
     if (d.x0 + d.bw < d.W) ex = min(ex, d.bw - 1 - j);
     const bool top_counts = d.y0 > 0, bottom_counts = d.y0 + d.bh < d.H;
     const float fr = (float)(rho + 1);
+    int gx0 = 0, gx1 = 0;
+    float ux = 0.0f;
+    const float* wb = nullptr;
+    if (WEIGHTED) {
+        pp_axis(d.x0 + j, d.W, ww, &gx0, &gx1, &ux);
+        wb = w + (size_t)b * wh * ww;
+    }
     const size_t plane = (size_t)S * S;
     const float* tb = t + (size_t)b * 3 * plane;
     const float* sb = s01 + (size_t)b * 3 * plane;
@@ -231,7 +242,16 @@ __global__ __launch_bounds__(256) void paste_photo_kernel(const PpArgs a, int S,
         int e = ex;
         if (top_counts) e = min(e, i);
         if (bottom_counts) e = min(e, d.bh - 1 - i);
-        const float al = __fdiv_rn((float)(min(e, rho) + 1), fr);               // min(e + 1, rho + 1) without the overflow of big + 1
+        float al = __fdiv_rn((float)(min(e, rho) + 1), fr);                     // min(e + 1, rho + 1) without the overflow of big + 1
+        if (WEIGHTED) {
+            int gy0, gy1;
+            float uy;
+            pp_axis(d.y0 + i, d.H, wh, &gy0, &gy1, &uy);
+            const float* r0 = wb + (size_t)gy0 * ww;
+            const float* r1 = wb + (size_t)gy1 * ww;
+            const float g = pp_lerp(pp_lerp(r0[gx0], r0[gx1], ux), pp_lerp(r1[gx0], r1[gx1], ux), uy);
+            al = pp_rounded(__fmul_rn(al, g));
+        }
         unsigned char* p = px + (size_t)(d.y0 + i) * d.pitch_bytes + (size_t)(d.x0 + j) * 3;
         const int o00 = y0i * S + x0i, o01 = y0i * S + x1i, o10 = y1i * S + x0i, o11 = y1i * S + x1i;
 #pragma unroll
@@ -269,6 +289,28 @@ size_t slab_bytes(const mkd_photo_desc& d, int S) {
     int rbase, rows;
     rs_rows(d.H, d.y0, d.bh, S, &rbase, &rows);
     return ((size_t)rows * S * 3 + 255) & ~(size_t)255;
+}
+
+// the one launcher of both paste entries: w == nullptr is mkd_paste_photo
+int paste_photo(const char* who, const mkd_photo_desc* descs, int n, int S, const float* t, const float* s01, int feather, const float* w,
+                int wh, int ww, void* stream) {
+    if (int rc = check_descs(who, descs, n, S, false)) return rc;
+    if (!t || !s01) return mkd_fail(-1, std::string(who) + ": null t / s01");
+    if (feather < 0 || feather > MKD_PHOTO_MAX_FEATHER) return mkd_fail(-1, std::string(who) + ": feather must be 0..64 photo pixels");
+    PpArgs a = {};
+    int mw = 0, mh = 0;
+    for (int i = 0; i < n; ++i) {
+        a.d[i] = descs[i];
+        mw = descs[i].bw > mw ? descs[i].bw : mw;
+        mh = descs[i].bh > mh ? descs[i].bh : mh;
+    }
+    const dim3 grid((unsigned)((mw + PP_TW - 1) / PP_TW), (unsigned)((mh + PP_TH - 1) / PP_TH), (unsigned)n);      // y <= 1024
+    if (w)
+        hipLaunchKernelGGL(paste_photo_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a, S, t, s01, feather, w, wh, ww);
+    else
+        hipLaunchKernelGGL(paste_photo_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a, S, t, s01, feather, w, wh, ww);
+    MKD_LAUNCH_CHECK("paste_photo_kernel");
+    return 0;
 }
 
 }  // namespace
@@ -320,20 +362,14 @@ int mkd_resize_coeffs(int N, int in0, int len, int S, int32_t* bounds_out, int32
 }
 
 int mkd_paste_photo(const mkd_photo_desc* descs, int n, int S, const float* t, const float* s01, int feather, void* stream) {
-    if (int rc = check_descs("mkd_paste_photo", descs, n, S, false)) return rc;
-    if (!t || !s01) return mkd_fail(-1, "mkd_paste_photo: null t / s01");
-    if (feather < 0 || feather > MKD_PHOTO_MAX_FEATHER) return mkd_fail(-1, "mkd_paste_photo: feather must be 0..64 photo pixels");
-    PpArgs a = {};
-    int mw = 0, mh = 0;
-    for (int i = 0; i < n; ++i) {
-        a.d[i] = descs[i];
-        mw = descs[i].bw > mw ? descs[i].bw : mw;
-        mh = descs[i].bh > mh ? descs[i].bh : mh;
-    }
-    const dim3 grid((unsigned)((mw + PP_TW - 1) / PP_TW), (unsigned)((mh + PP_TH - 1) / PP_TH), (unsigned)n);      // y <= 1024
-    hipLaunchKernelGGL(paste_photo_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, S, t, s01, feather);
-    MKD_LAUNCH_CHECK("paste_photo_kernel");
-    return 0;
+    return paste_photo("mkd_paste_photo", descs, n, S, t, s01, feather, nullptr, 0, 0, stream);
+}
+
+int mkd_paste_photo_weighted(const mkd_photo_desc* descs, int n, int S, const float* t, const float* s01, int feather, const float* w,
+                             int wh, int ww, void* stream) {
+    if (!w) return mkd_fail(-1, "mkd_paste_photo_weighted: null w");
+    if (wh < 1 || ww < 1 || wh > 2048 || ww > 2048) return mkd_fail(-1, "mkd_paste_photo_weighted: wh, ww must be 1..2048");
+    return paste_photo("mkd_paste_photo_weighted", descs, n, S, t, s01, feather, w, wh, ww, stream);
 }
 
 }  // extern "C"

@@ -837,9 +837,13 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         return img, src
 
     def _transfer_faces(self, src_photos, ref_photos, src_boxes, ref_boxes, src_segs, feather, x_T, size, batch, phi, max_faces,
-                        face_batch, return_faces):
+                        face_batch, return_faces, own_pixels=False, own_feather=2):
         """transfer_photos(max_faces=K): see there"""
         K, fb = int(max_faces), int(face_batch)
+        if own_pixels and (src_boxes is not None or self.face_parser is None):
+            raise ValueError('own_pixels needs the faces from the attached face parser (src_boxes None): a box has no component to own pixels')
+        if own_pixels and (int(own_feather) != own_feather or not 0 <= int(own_feather) <= 16):
+            raise ValueError(f'own_feather must be an integer 0..16 parse pixels, got {own_feather!r}')
         if K != max_faces or not 1 <= K <= 64:
             raise ValueError(f'max_faces must be an integer 1..64, got {max_faces!r}')
         if fb != face_batch or fb < 1:
@@ -873,11 +877,16 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             raise ValueError('transfer_photos pastes decoded images: it needs a first stage (first_stage_config)')
         if (self.fix_background or self.paste_background) and src_segs is None and self.face_parser is None:
             raise KeyError('transfer_photos: fix_background / paste_background need src_segs (label maps at photo resolution)')
+        from ..components import owner_weights
         from ..face_parser import find_faces
         eng = self._require_engine()
         src_photos = [p.to(self.device) for p in src_photos]
         ref_photos = [p.to(self.device) for p in ref_photos]
-        if src_boxes is None:
+        owner = None
+        if own_pixels:
+            src_boxes, owner = find_faces(self.face_parser, src_photos, max_faces=K, parse_size=self.parse_size, lut=self.parser_lut,
+                                          return_owner=True)
+        elif src_boxes is None:
             src_boxes = find_faces(self.face_parser, src_photos, max_faces=K, parse_size=self.parse_size, lut=self.parser_lut)
         faces = [[tuple(int(v) for v in b) for b in bl] for bl in src_boxes]
         if ref_boxes is None:
@@ -910,14 +919,16 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             for rank in range(max(len(bl) for bl in faces)):
                 sel = [j for j, (_, k) in enumerate(items) if k == rank]
                 at = torch.tensor(sel, device=img.device)
-                eng.paste_photos([out[items[j][0]] for j in sel], [faces[items[j][0]][rank] for j in sel], img[at], src[at], feather)
+                # own_pixels: rank k of photo i is row k of its table, the weight that row's share of every neighbourhood
+                weights = None if owner is None else owner_weights(owner, [(items[j][0], rank) for j in sel], own_feather)
+                eng.paste_photos([out[items[j][0]] for j in sel], [faces[items[j][0]][rank] for j in sel], img[at], src[at], feather, weights)
         return (out, faces) if return_faces else out
 
     @torch.no_grad()
     def transfer_photos(self, src_photos, ref_photos, src_boxes=None, ref_boxes=None, src_segs=None, feather: int = 8,
                         x_T: Optional[torch.Tensor] = None, size: int = 256, batch: Optional[dict] = None,
                         guidance_rescale: Optional[float] = None, max_faces: Optional[int] = None, face_batch: int = 8,
-                        return_faces: bool = False):
+                        return_faces: bool = False, own_pixels: bool = False, own_feather: int = 2):
         """Makeup transfer on photographs at their own resolution: ``src_photos`` / ``ref_photos`` are uint8 [H,W,3] tensors of any
         size (lists; the photos of a call may differ in size) with a face box (x0, y0, w, h) each.  Both boxes are crop-resized to
         ``size`` on the device (photo.crop_resize: Pillow's antialiased bilinear bytes / 255, what PairFolderDataset gives for that
@@ -941,16 +952,25 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         pasted into ONE clone per source photo rank by rank (one paste_photos call for rank 0 of every photo that has one, then rank 1,
         ...), so a photo never appears twice in a launch and stream order fixes what overlapping boxes give: the larger face is pasted
         first, and a smaller face that overlaps it adds ITS difference (against its crop of the ORIGINAL photo) on top of pixels the
-        first paste may already have changed.  A crop may show part of a neighbouring face, which the model is free to change: the
-        paste is not restricted to the face's own component.  A photo without a face comes back as an unchanged clone; N = 0 samples
-        nothing.  ``return_faces``: (photos, the list of box lists) instead of the photos."""
+        first paste may already have changed.  A crop may show part of a neighbouring face, which the model is free to change: by
+        default the paste is not restricted to the face's own component.  A photo without a face comes back as an unchanged clone;
+        N = 0 samples nothing.  ``return_faces``: (photos, the list of box lists) instead of the photos.
+
+        ``own_pixels`` (with max_faces, faces from the attached parser only: src_boxes None, else ValueError): every face's paste
+        stays on its own pixels.  find_faces(return_owner=True) also gives the owner map, the nearest component of every pixel of
+        the squashed map (every component of at least min_area pixels is a seed, also those beyond K); the paste of rank k of photo
+        i is weighted by components.owner_weights (the fraction of the (2 own_feather + 1)^2 parse-pixel window that rank k owns,
+        upsampled to the photo by mkd_paste_photo_weighted), so what a crop shows of a neighbour is not written, a face beyond K
+        keeps its bytes, and the weights of neighbouring faces sum to one across their border."""
         from .. import photo
         phi = float(self.guidance_rescale if guidance_rescale is None else guidance_rescale)
         if not 0.0 <= phi <= 1.0:
             raise ValueError(f'guidance_rescale must lie in [0, 1], got {phi}')
         if max_faces is not None:
             return self._transfer_faces(src_photos, ref_photos, src_boxes, ref_boxes, src_segs, feather, x_T, size, batch, phi,
-                                        max_faces, face_batch, return_faces)
+                                        max_faces, face_batch, return_faces, own_pixels, own_feather)
+        if own_pixels:
+            raise ValueError('own_pixels only applies with max_faces')
         if return_faces or face_batch != 8:
             raise ValueError('return_faces / face_batch only apply with max_faces')
         if (src_boxes is None or ref_boxes is None) and self.face_parser is None:

@@ -1019,11 +1019,12 @@ class MkdEngine:
             return [t.to(self.device) for t in ts]
         return photo.crop_resize(to_dev(photos, 3), boxes, size, labels=None if labels is None else to_dev(labels, 2), want_u8=want_u8)
 
-    def paste_photos(self, photos, boxes, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8):
+    def paste_photos(self, photos, boxes, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None):
         """Full-resolution photos out (include/mkd.h mkd_paste_photo; photo.paste_photos): the decoded samples pasted into the
-        device photos IN PLACE, inside their boxes, with the photos' fine detail kept."""
+        device photos IN PLACE, inside their boxes, with the photos' fine detail kept.  ``weights`` [B,wh,ww]: one photo-wide weight
+        plane per photo (mkd_paste_photo_weighted)."""
         from . import photo
-        return photo.paste_photos(photos, boxes, samples, src01, feather)
+        return photo.paste_photos(photos, boxes, samples, src01, feather, weights)
 
     def eps_profile(self, x: torch.Tensor, t: torch.Tensor, csv_path: Optional[str] = None) -> Dict[str, Dict[str, float]]:
         """One eps with HIP events around every launch group -> {kernel class: {ms, flops, launches, bytes, ms_b2b}}: ``bytes`` =

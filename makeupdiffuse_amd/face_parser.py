@@ -196,8 +196,9 @@ class FaceParser:
         return find_boxes(self, photos, grow=grow, parse_size=parse_size, lut=lut)
 
     def find_faces(self, photos, max_faces: int = 8, min_area: Optional[int] = None, grow: float = 1.0, parse_size: int = 512,
-                   lut=LUT_SEG) -> List[List[Tuple[int, int, int, int]]]:
-        return find_faces(self, photos, max_faces=max_faces, min_area=min_area, grow=grow, parse_size=parse_size, lut=lut)
+                   lut=LUT_SEG, return_owner: bool = False):
+        return find_faces(self, photos, max_faces=max_faces, min_area=min_area, grow=grow, parse_size=parse_size, lut=lut,
+                          return_owner=return_owner)
 
     def flops(self, H: int = 512, W: int = 512) -> float:
         return float(self.lib.mkd_parser_flops(self._h, int(H), int(W)))
@@ -257,7 +258,7 @@ def find_boxes(parser, photos, grow: float = 1.0, parse_size: int = 512, lut=LUT
 
 
 def find_faces(parser, photos, max_faces: int = 8, min_area: Optional[int] = None, grow: float = 1.0, parse_size: int = 512, lut=LUT_SEG,
-               classes: Sequence[int] = FACE_CLASSES, resize=None, components_of=None) -> List[List[Tuple[int, int, int, int]]]:
+               classes: Sequence[int] = FACE_CLASSES, resize=None, components_of=None, return_owner: bool = False, owner_of=None):
     """EVERY face of whole photos (uint8 [H,W,3] device tensors): one list of boxes (x0, y0, side, side) per photo, largest face first.
     Every photo is squashed to parse_size x parse_size and parsed exactly as find_boxes does; a face is an 8-connected component of the
     face classes with at least ``min_area`` pixels of the squashed map (components.label_components; default (parse_size // 32)^2,
@@ -266,8 +267,13 @@ def find_faces(parser, photos, max_faces: int = 8, min_area: Optional[int] = Non
     the squash changes the aspect ratio) and grown, squared and clipped by photo.grow_square_box.  A photo without such a component
     gives [] and does not raise.  One device-to-host copy (table and count together) per chunk of MAX_BATCH photos; no component
     data is read back per pixel.  The crop of one face may show part of a neighbouring face: crops are not restricted to their
-    component.  This rule is this build's.  ``resize`` and ``components_of`` (the signature of components.label_components) replace
-    the two device calls (tests of the box arithmetic without a device)."""
+    component; what keeps one face's PASTE off its neighbour is the owner map.  ``return_owner``: (faces, owner) with owner uint8
+    [n_photos, parse_size, parse_size] on the device, the rank of the component nearest to every pixel of the squashed map
+    (components.owner_map; components.NO_OWNER in a photo without a face).  The table is then taken with max_out =
+    components.MAX_OUT: its first ``max_faces`` rows are the rows of the call above, so the boxes are the same, and EVERY row is a
+    seed, so a face beyond ``max_faces`` keeps its pixels.  The metric is the squashed map's: anisotropic in photo pixels.  This rule
+    is this build's.  ``resize``, ``components_of`` (the signature of components.label_components) and ``owner_of`` (that of
+    components.owner_map) replace the device calls (tests of the box arithmetic without a device)."""
     from . import components, photo
     K = int(max_faces)
     if K != max_faces or not 1 <= K <= components.MAX_OUT:
@@ -281,12 +287,19 @@ def find_faces(parser, photos, max_faces: int = 8, min_area: Optional[int] = Non
     area = (S // 32) ** 2 if min_area is None else int(min_area)
     if area < 1:
         raise ValueError(f'min_area must be >= 1, got {min_area!r} (parse_size {parse_size})')
+    if return_owner:
+        owner_of = owner_of or components.owner_map
     out: List[List[Tuple[int, int, int, int]]] = []
+    owners = []
     for b0 in range(0, len(photos), MAX_BATCH):
         chunk = photos[b0:b0 + MAX_BATCH]
         whole = [(0, 0, int(p.shape[1]), int(p.shape[0])) for p in chunk]
         labels = parser.parse(resize(chunk, whole, S).img01, out_size=None, lut=lut)
-        table, count = components_of(labels, classes, min_area=area, max_out=K)[:2]
+        if return_owner:
+            table, count, ids = components_of(labels, classes, min_area=area, max_out=components.MAX_OUT, want_ids=True)
+            owners.append(torch.as_tensor(owner_of(ids, table)))
+        else:
+            table, count = components_of(labels, classes, min_area=area, max_out=K)[:2]
         table, count = torch.as_tensor(table), torch.as_tensor(count)
         both = torch.cat((table.reshape(len(chunk), -1), count.reshape(len(chunk), 1).to(table.dtype)), 1).cpu().tolist()
         for p, row in zip(chunk, both):
@@ -297,4 +310,6 @@ def find_faces(parser, photos, max_faces: int = 8, min_area: Optional[int] = Non
                 scaled = (r0 * H // S, min(H, -(-(r1 + 1) * H // S)) - 1, c0 * W // S, min(W, -(-(c1 + 1) * W // S)) - 1)
                 faces.append(photo.grow_square_box(scaled, H, W, grow))
             out.append(faces)
+    if return_owner:
+        return out, (torch.cat(owners) if owners else torch.empty((0, S, S), dtype=torch.uint8))
     return out

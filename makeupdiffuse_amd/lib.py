@@ -129,6 +129,9 @@ SIGNATURES = {
     'mkd_region_mask_from_labels': (_I, [_P, _I, _I, _I, C.c_uint64, C.c_uint64, _I, _P, _P, _P, _P]),
     'mkd_label_components_scratch_bytes': (C.c_size_t, [_I, _I, _I]),
     'mkd_label_components': (_I, [_P, _I, _I, _I, C.c_uint64, _I, _I, _P, _P, _P, _P, _P]),
+    'mkd_owner_map_scratch_bytes': (C.c_size_t, [_I, _I, _I]),
+    'mkd_owner_map': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    'mkd_owner_weights': (_I, [_P, _I, _I, _I, C.POINTER(C.c_int32), _I, _I, _P, _P]),
     'mkd_hist_match_scratch_bytes': (C.c_size_t, [_I]),
     'mkd_hist_match_launches': (_I, [_I, _I]),
     'mkd_hist_match': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
@@ -136,6 +139,7 @@ SIGNATURES = {
     'mkd_crop_resize': (_I, [C.POINTER(PhotoDescC), _I, _I, _P, _P, _P, _P, _P]),
     'mkd_resize_coeffs': (_I, [_I, _I, _I, _I, _P, _P, _P]),
     'mkd_paste_photo': (_I, [C.POINTER(PhotoDescC), _I, _I, _P, _P, _I, _P]),
+    'mkd_paste_photo_weighted': (_I, [C.POINTER(PhotoDescC), _I, _I, _P, _P, _I, _P, _I, _I, _P]),
     'mkd_vae_configure': (_I, [_P, C.POINTER(VaeConfigC)]),
     'mkd_vae_finalize': (_I, [_P]),
     'mkd_decode': (_I, [_P, _P, _I, _I, _I, _F, _P, _P]),

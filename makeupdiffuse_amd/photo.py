@@ -21,6 +21,7 @@ MAX_BATCH = 16          # descriptors per library call (MKD_PHOTO_MAX_BATCH); la
 MAX_FEATHER = 64
 MIN_SIZE, MAX_SIZE = 8, 1024
 MAX_SIDE = 16384
+MAX_WEIGHT_SIDE = 2048  # rows / columns of a paste's photo-wide weight plane
 # the reference's crop around a detected face (diffdata/preprocessing.py:18): fractions of the face box added above, below and per side
 UP_RATIO, DOWN_RATIO, WIDTH_RATIO = 0.6 / 0.85, 0.2 / 0.85, 0.2 / 0.85
 
@@ -135,12 +136,14 @@ def crop_resize(photos, boxes, size: int, labels=None, want_u8: bool = False) ->
     return Cropped(img01, lab_out, u8)
 
 
-def paste_photos(photos, boxes, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8):
+def paste_photos(photos, boxes, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None):
     """The decoded ``samples`` (fp32 [B,3,S,S], nominally [-1, 1]) back into ``photos`` IN PLACE, inside their boxes only:
     photo + a * upsampled((samples + 1) / 2 - src01) * 255, rounded to uint8 (ties to even), where src01 is the img01 the model saw
     (crop_resize of the same photos and boxes) and a fades from 1 / (feather + 1) at a box side to 1 over ``feather`` photo pixels
     (sides on the photo's border do not fade).  Only the difference is interpolated, so everything finer than the model's grid stays
-    the photo's own.  Returns ``photos``."""
+    the photo's own.  ``weights`` (fp32 [B,wh,ww], wh, ww <= 2048; mkd_paste_photo_weighted): plane b covers the WHOLE of photo b at
+    low resolution and a is multiplied by its bilinear sample at the photo pixel (components.owner_weights: each face's paste stays
+    on its own pixels); a weight of 0 leaves the photo's byte.  Returns ``photos``."""
     rho = int(feather)
     if rho != feather or not 0 <= rho <= MAX_FEATHER:
         raise ValueError(f'feather must be an integer 0..{MAX_FEATHER} photo pixels, got {feather!r}')
@@ -160,13 +163,25 @@ def paste_photos(photos, boxes, samples: torch.Tensor, src01: torch.Tensor, feat
     dev = plist[0].device
     t = samples.to(device=dev, dtype=torch.float32).contiguous()
     s = src01.to(device=dev, dtype=torch.float32).contiguous()
+    w = None
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor) or weights.dim() != 3 or weights.shape[0] != B or weights.dtype != torch.float32 \
+                or not (1 <= weights.shape[1] <= MAX_WEIGHT_SIDE and 1 <= weights.shape[2] <= MAX_WEIGHT_SIDE):
+            raise ValueError(f'weights must be fp32 [{B},wh,ww] with wh, ww in 1..{MAX_WEIGHT_SIDE}, got '
+                             f'{getattr(weights, "dtype", type(weights))} {tuple(getattr(weights, "shape", ()))}')
+        w = weights.to(device=dev).contiguous()
     lib = _lib.load()
     with torch.cuda.device(dev):
         for b0 in range(0, B, MAX_BATCH):
             b1 = min(B, b0 + MAX_BATCH)
             arr = _descs(plist[b0:b1], boxes[b0:b1], None)
-            _lib.check(lib.mkd_paste_photo(arr, b1 - b0, S, C.c_void_p(t[b0:b1].data_ptr()), C.c_void_p(s[b0:b1].data_ptr()), rho,
-                                           C.c_void_p(_stream())), 'mkd_paste_photo')
+            if w is None:
+                _lib.check(lib.mkd_paste_photo(arr, b1 - b0, S, C.c_void_p(t[b0:b1].data_ptr()), C.c_void_p(s[b0:b1].data_ptr()), rho,
+                                               C.c_void_p(_stream())), 'mkd_paste_photo')
+            else:
+                _lib.check(lib.mkd_paste_photo_weighted(arr, b1 - b0, S, C.c_void_p(t[b0:b1].data_ptr()), C.c_void_p(s[b0:b1].data_ptr()), rho,
+                                                        C.c_void_p(w[b0:b1].data_ptr()), int(w.shape[1]), int(w.shape[2]), C.c_void_p(_stream())),
+                           'mkd_paste_photo_weighted')
     return photos
 
 

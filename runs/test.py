@@ -100,6 +100,11 @@ def build_parser():
     ap.add_argument('--max-faces', type=int, default=None, metavar='K', help='with --photos: group photos -- make up to K faces of every source '
                     'photo (largest first), each against the largest face of its reference; the faces come from --face-parser (connected '
                     'components of the parsed face classes) or from a boxes file that repeats an image name, one line per face')
+    ap.add_argument('--own-pixels', action='store_true', help='with --photos --max-faces and faces from --face-parser: every face is pasted '
+                    'onto its own pixels only (the pixels nearest to its component of the parsed map), so a crop that shows part of a '
+                    'neighbouring face does not repaint it and a face beyond K keeps its bytes')
+    ap.add_argument('--own-feather', type=int, default=2, metavar='N', help='with --own-pixels: blend neighbouring faces over N pixels of the '
+                    'parsed map on both sides of their border, 0..16')
     ap.add_argument('--photo-feather', type=int, default=8, help='fade the pasted face in over this many photo pixels at the box sides, 0..64')
     ap.add_argument('--face-parser', default=None, metavar='PATH|random', help='attach the face-parsing network (upstream face-parsing.PyTorch '
                     'state dict, e.g. 79999_iter.pth; "random": seeded random weights, for plumbing runs): label maps that --fix-background, '
@@ -185,6 +190,15 @@ def main():
             raise SystemExit('--max-faces must be 1..64')
         if not args.face_parser and not os.path.exists(os.path.join(args.data_root, 'boxes.txt')):
             raise SystemExit('--max-faces needs --face-parser or <data-root>/boxes.txt (one line per face)')
+    if args.own_pixels:
+        if not args.photos or args.max_faces is None:
+            raise SystemExit('--own-pixels only applies with --photos --max-faces')
+        if not args.face_parser or os.path.exists(os.path.join(args.data_root, 'boxes.txt')):
+            raise SystemExit('--own-pixels needs the faces from --face-parser (no <data-root>/boxes.txt): a box has no component to own pixels')
+        if not 0 <= args.own_feather <= 16:
+            raise SystemExit('--own-feather must be 0..16 pixels of the parsed map')
+    elif args.own_feather != 2:
+        raise SystemExit('--own-feather only applies with --own-pixels')
     if not 0 <= args.photo_feather <= 64:
         raise SystemExit('--photo-feather must be 0..64 photo pixels')
     if args.photo_feather != 8 and not args.photos:
@@ -316,9 +330,11 @@ def main():
                     x_F = [torch.randn(1, model.channels, h8, h8, generator=torch.Generator().manual_seed((args.seed + i) * 64 + k))
                            for i in range(b0, b1) for k in range(len(faces[i - b0]))]
                     x_F = torch.cat(x_F).cuda(local) if x_F else None
-                photos, faces = model.transfer_photos(items['src_photo'], items['ref_photo'], faces, ref_boxes,
+                own = dict(own_pixels=True, own_feather=args.own_feather) if args.own_pixels else {}
+                # (--own-pixels: the model finds the same faces again, with their owner map; the count above sizes the start latents)
+                photos, faces = model.transfer_photos(items['src_photo'], items['ref_photo'], None if args.own_pixels else faces, ref_boxes,
                                                       src_segs=items.get('src_seg'), feather=args.photo_feather, x_T=x_F, size=args.res, batch=text,
-                                                      max_faces=K, return_faces=True)
+                                                      max_faces=K, return_faces=True, **own)
                 print(f'[rank {rank}] faces per photo: {[len(f) for f in faces]}', flush=True)
             os.makedirs(os.path.join(args.out, 'photos'), exist_ok=True)
             for name, img in zip(items['img_name'], photos):
