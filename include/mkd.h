@@ -524,6 +524,86 @@ int mkd_paste_photo(const mkd_photo_desc* descs, int n, int S, const float* t, c
 int mkd_paste_photo_weighted(const mkd_photo_desc* descs, int n, int S, const float* t, const float* s01, int feather, const float* w,
                              int wh, int ww, void* stream);
 
+/* ---- tilted faces: the photo path along a rotated square (BUILD-DEFINED; the reference aligns nothing, its crops are upright boxes) ---- */
+/* One photo of a batch and an ORIENTED square in it.  pixels, pitch_bytes, H, W, labels: as mkd_photo_desc.  Photo coordinates: pixel
+ * (X, Y) has its centre at (X + 0.5, Y + 0.5).  (cx, cy) = the square's centre, side = its side in photo pixels, e_u = (c, s) = the unit
+ * vector of the face's "right" axis and e_v = (-s, c) that of its "down" axis; c = 1, s = 0 is upright.  The square need NOT lie inside
+ * the photo (a rolled face at the border sticks out: the crop replicates edges, the paste writes only what is inside the photo).  The
+ * HOST array of at most MKD_PHOTO_MAX_BATCH descriptors is copied into the kernel argument block by value.  Limits (else MKD_ERR_ARG
+ * before anything is enqueued): 1 <= n <= 16, 8 <= S <= 1024, 1 <= H, W <= 16384, pitch_bytes >= 3 W, pixels not NULL, cx, cy, side, c,
+ * s finite, 0 < side <= 32 S, |c^2 + s^2 - 1| <= 1e-9, -side <= cx <= W + side and -side <= cy <= H + side. */
+typedef struct mkd_photo_frame_desc {
+    const uint8_t* pixels;
+    int32_t pitch_bytes;
+    int32_t H, W;
+    double cx, cy, side;
+    double c, s;
+    const uint8_t* labels;
+} mkd_photo_frame_desc;
+/* Oriented square -> S x S: Pillow's triangle (bilinear, antialiased) filter taken in the face's frame, in ONE pass.  IEEE double
+ * throughout, every line below ONE correctly rounded operation per operator, nothing contracted, evaluated left to right with the
+ * parentheses shown.  scale = side / S; fs = max(scale, 1); half = side * 0.5; R = fs * (|c| + |s|).  For output (row i, col j):
+ * u = ((j + 0.5) * scale) - half; v = ((i + 0.5) * scale) - half; qx = (cx + c * u) - s * v; qy = (cy + s * u) + c * v.  Taps: the integer
+ * photo pixels (X, Y) with floor(qx - R) <= X <= floor(qx + R) and floor(qy - R) <= Y <= floor(qy + R) (the tent's support is a
+ * rotated square of half-diagonal reach R per axis), Y outer, X inner, both ascending.  Per tap: dx = (X + 0.5) - qx;
+ * dy = (Y + 0.5) - qy; du = c * dx + s * dy; dv = c * dy - s * dx; wu = 1 - |du| / fs; wv = 1 - |dv| / fs; a tap with wu <= 0 or
+ * wv <= 0 has weight 0 and is skipped (it would add +0.0 to every sum); else w = wu * wv, sw += w and per channel sc += w * byte, the
+ * byte read at (clamp(X, 0, W - 1), clamp(Y, 0, H - 1)): edges are replicated.  One accumulator per channel and one for the weights;
+ * sw > 0 always (the pixel centre nearest to q lies inside the tent).  u8 = clip(rint(sc / sw), 0, 255), ties to even;
+ * img01 = float(u8) / 255.0f.  labels_out[i][j] = labels[clamp(floor(qy), 0, H - 1)][clamp(floor(qx), 0, W - 1)]: classes are never
+ * interpolated.  Outputs and their NULL rules as mkd_crop_resize (img01 [n, 3, S, S], u8_out [n, S, S, 3] or NULL, labels_out
+ * [n, S, S] or NULL, then every descriptor needs labels; img01 and u8_out not both NULL).  At c = 1, s = 0 and an integer box this is
+ * Pillow's filter without its uint8 intermediate and fixed-point coefficients: within 1 of mkd_crop_resize in any byte.  One thread
+ * per output pixel, 16 x 16 per workgroup.  No context; ONE launch, no scratch, no allocation, no host sync, no atomics. */
+int mkd_crop_frame(const mkd_photo_frame_desc* descs, int n, int S, float* img01, uint8_t* u8_out, uint8_t* labels_out, void* stream);
+/* The decoded sample back into the photo along the frame, IN PLACE (t, s01 as mkd_paste_photo).  IEEE double, one correctly rounded
+ * operation per operator, nothing contracted.  scale = side / S; half = side * 0.5.  Per photo pixel (X, Y): rx = (X + 0.5) - cx;
+ * ry = (Y + 0.5) - cy; u = c * rx + s * ry; v = c * ry - s * rx.  The pixel is INSIDE iff -half <= u < half and -half <= v < half; a
+ * pixel outside is neither read for writing nor written.  Per axis (u gives columns, v rows): g = ((u + half) / scale) - 0.5;
+ * i0 = floor(g); wx = g - i0; neighbours clamp(i0, 0, S - 1) and clamp(i0 + 1, 0, S - 1).  d = (((double(t) + 1) * 0.5) - double(s01)) * 255
+ * at the four neighbours; top = d00 + wx * (d01 - d00); bot likewise; val = top + wy * (bot - top).  e = min(min(u + half, half - u),
+ * min(v + half, half - v)); a = min(e + 0.5, rho + 1) / (rho + 1): ALL four sides fade, also one on the photo's border (at roll 0 and
+ * an integer box e + 0.5 is mkd_paste_photo's e + 1 for its interior sides).  w != NULL (fp32 [n, wh, ww], the plane of
+ * mkd_paste_photo_weighted, 1 <= wh, ww <= 2048): its integers numx = (2 X + 1) ww - W, denx = 2 W, i0 = floor(numx / denx), rem give
+ * ux = double(rem) / double(denx) and the neighbours (likewise Y, H, wh); g = lerp(lerp(w00, w01, ux), lerp(w10, w11, ux), uy) with
+ * lerp(p, q, k) = p + k * (q - p); a = a * g.  o = double(byte) + a * val; out = uint8(clip(rint(o), 0, 255)), ties to even.  g = 0
+ * leaves the byte, w = 1 everywhere gives the bytes of w == NULL.  feather rho: 0..64.  The grid covers the axis-aligned bounding
+ * rectangle of the rotated square (centre -+ half * (|c| + |s|) per axis, one pixel of slack per side) clipped to the photo, in
+ * 64 x 16 tiles; which pixels are written is decided by the INSIDE test alone.  A square that does not reach its photo writes nothing
+ * (no launch when that holds for every descriptor).  No context; ONE launch, no scratch, no allocation, no host sync, no atomics. */
+int mkd_paste_frame(const mkd_photo_frame_desc* descs, int n, int S, const float* t, const float* s01, int feather, const float* w,
+                    int wh, int ww, void* stream);
+/* Every face's roll and its extent in its own frame.  48 bytes: n_a / n_b = the pixels of the component in the class sets a / b (the
+ * two eyes), (cq, sq) = the face's "right" axis as integers of length 16384 (16384, 0: upright), umin .. vmax = the component's extent
+ * along that axis and the one across it, in units of 1 / (2 S 16384) photo pixel. */
+typedef struct mkd_face_frame { int32_t n_a, n_b, cq, sq; int64_t umin, umax, vmin, vmax; } mkd_face_frame;
+/* Bytes of device scratch mkd_face_frames needs (six 64-bit moment cells per (image, rank), rounded up to 256 bytes; 0 unless
+ * 1 <= batch <= 16 and 1 <= max_out <= 64).  The scratch must be 256-byte aligned; its contents before the call do not matter. */
+size_t mkd_face_frames_scratch_bytes(int batch, int max_out);
+/* labels uint8 and ids int32 [batch, S, S] device: the square squashed grid of face_parser.find_faces; ids and table [batch][max_out]
+ * come from ONE mkd_label_components call.  photo_hw HOST int32 [batch][2] = (H, W) of the photo behind image b, copied into the kernel
+ * argument block by value.  frames [batch][max_out] device.  For rank r of image b, over the pixels (x, y) whose id equals
+ * table[b][r].id (of rows that repeat an id the lowest counts):
+ * MOMENTS (integers): n_a = the pixels whose label l < 64 has bit l set in classes_a, sxa / sya = the sums of their x / y (int64);
+ * n_b, sxb, syb likewise for classes_b.
+ * DIRECTION (double, one thread): if n_a >= min_eye_area and n_b >= min_eye_area: px = (sxb / n_b - sxa / n_a) * (double(W) / S);
+ * py = (syb / n_b - sya / n_a) * (double(H) / S) (the squash is undone: the direction is the photo's); if px < 0 both are negated;
+ * len = sqrt(px * px + py * py); cq = (int)rint(px / len * 16384); sq = (int)rint(py / len * 16384).  (cq, sq) = (16384, 0) instead
+ * when an eye is missing (below min_eye_area), when len == 0, or when cq < 8192: a roll beyond +-60 degrees is taken as a parser error,
+ * not as a pose.
+ * EXTENT (int64), over ALL pixels of the component: X2 = (2 x + 1) W; Y2 = (2 y + 1) H (photo coordinates of the pixel centre in
+ * units of 1 / (2 S) pixel); pu = cq X2 + sq Y2; pv = -sq X2 + cq Y2 (|.| < 2^43); umin / umax / vmin / vmax = their minima / maxima.
+ * A rank whose table id is -1: n_a = n_b = 0, cq = 16384, sq = 0, umin = vmin = INT64_MAX, umax = vmax = INT64_MIN.
+ * Sums, minima and maxima are integer atomics, per workgroup in LDS first and then one global 64-bit atomic per non-zero cell; the id
+ * -> rank search runs over the table rows in LDS.  Integer outputs: the same bytes on every run (cq, sq come from one thread's
+ * doubles).  No context, no host sync, no allocation; 4 launches (clear the moments, moments, direction, extents), 256 threads
+ * with 4 consecutive pixels each in the two per-pixel ones, and no workgroup waits for another.  MKD_ERR_ARG before anything is enqueued
+ * unless 1 <= batch <= 16, 1 <= S <= 4096, 1 <= max_out <= 64, min_eye_area >= 1, 1 <= H, W <= 16384, labels / ids / table / photo_hw /
+ * frames / scratch non-null and the scratch 256-byte aligned. */
+int mkd_face_frames(const uint8_t* labels, const int32_t* ids, const mkd_component* table, int batch, int S, int max_out,
+                    const int32_t* photo_hw, uint64_t classes_a, uint64_t classes_b, int min_eye_area, mkd_face_frame* frames,
+                    void* scratch, void* stream);
+
 /* ---- first-stage decoder ------------------------------------------------ */
 /* yaml first_stage_config.params.ddconfig (diffmodels/base_diffusion_makeup.yaml:86-107), decoder half only. */
 typedef struct mkd_vae_config {

@@ -2,7 +2,8 @@
 label is in a class set, with id (smallest linear index), area and inclusive bounding box each, the largest ``max_out`` as a table.
 What face_parser.find_faces builds on: one component of the face classes is one face.  owner_map (mkd_owner_map) then gives every
 pixel the table component nearest to it and owner_weights (mkd_owner_weights) each component's share of a pixel's neighbourhood:
-what keeps one face's paste off its neighbour.  Integer arithmetic only (one division per weight), so the outputs are exact and the
+what keeps one face's paste off its neighbour; face_frames (mkd_face_frames) measures every component's roll from its two eye classes
+and its extent in its own frame: what photo.grow_frame turns into an oriented crop.  Integer arithmetic only (one division per weight), so the outputs are exact and the
 same bytes on every run.  The arithmetic is libmkd's: there is no CPU path."""
 from __future__ import annotations
 
@@ -136,3 +137,59 @@ def owner_weights(owner: torch.Tensor, items: Sequence[Tuple[int, int]], feather
             _lib.check(lib.mkd_owner_weights(C.c_void_p(owner.data_ptr()), B, H, W, flat, len(part), rho, C.c_void_p(out[n0:].data_ptr()),
                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'mkd_owner_weights')
     return out
+
+
+FRAME_UNIT = 16384                               # |(cq, sq)| of a face frame
+FRAME_ROW = 8                                    # n_a, n_b, cq, sq, umin, umax, vmin, vmax
+MAX_FRAME_BATCH = 16                             # images per mkd_face_frames call (photo sizes travel by value); more are split here
+MAX_FRAME_SIDE = 4096
+
+
+def face_frames(labels: torch.Tensor, ids: torch.Tensor, table: torch.Tensor, photo_hw, classes_a: Sequence[int] = (4,),
+                classes_b: Sequence[int] = (5,), min_eye_area: Optional[int] = None) -> torch.Tensor:
+    """Every face's roll and its extent in its own frame (mkd_face_frames).  labels uint8 and ids int32 [B,S,S] on the square squashed
+    grid of face_parser.find_faces, ids and table int32 [B,max_out,6] of ONE label_components call, photo_hw [(H, W), ...] the size of
+    the photo behind every image -> int64 [B,max_out,8] on the device, a row (n_a, n_b, cq, sq, umin, umax, vmin, vmax): the pixels of
+    the component in ``classes_a`` / ``classes_b`` (LUT_SEG's two eyes), the direction from the centroid of a to that of b in PHOTO
+    pixels as integers of length FRAME_UNIT ((FRAME_UNIT, 0): upright; also when an eye has fewer than ``min_eye_area`` pixels --
+    default max(1, (S // 128)^2) -- or the roll exceeds 60 degrees), and the component's extent along and across that direction in
+    units of 1 / (2 S FRAME_UNIT) photo pixel (photo.grow_frame turns a row into a crop).  Integers: the same bytes on every run.
+    Nothing is read back: the call only enqueues (four launches per MAX_FRAME_BATCH images)."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or labels.dim() != 3 or labels.shape[1] != labels.shape[2]:
+        raise ValueError(f'labels must be uint8 [B,S,S], got {getattr(labels, "dtype", type(labels))} {tuple(getattr(labels, "shape", ()))}')
+    B, S = int(labels.shape[0]), int(labels.shape[1])
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or tuple(ids.shape) != (B, S, S):
+        raise ValueError(f'ids must be int32 [{B},{S},{S}], got {getattr(ids, "dtype", type(ids))} {tuple(getattr(ids, "shape", ()))}')
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 3 or table.shape[0] != B or table.shape[2] != ROW \
+            or not 1 <= table.shape[1] <= MAX_OUT:
+        raise ValueError(f'table must be int32 [{B},1..{MAX_OUT},{ROW}], got {getattr(table, "dtype", type(table))} {tuple(getattr(table, "shape", ()))}')
+    if labels.device.type != 'cuda' or ids.device != labels.device or table.device != labels.device:
+        raise _lib.MkdError('face_frames: labels, ids and table must be on one HIP device (there is no CPU implementation)')
+    if B < 1 or not 1 <= S <= MAX_FRAME_SIDE:
+        raise ValueError(f'labels {tuple(labels.shape)}: B >= 1 and S in 1..{MAX_FRAME_SIDE}')
+    hw = [(int(h), int(w)) for h, w in photo_hw]
+    if len(hw) != B or any(not (1 <= h <= 16384 and 1 <= w <= 16384) for h, w in hw):
+        raise ValueError(f'photo_hw must hold {B} pairs (H, W) in 1..16384, got {photo_hw!r}')
+    area = max(1, (S // 128) ** 2) if min_eye_area is None else int(min_eye_area)
+    if area < 1 or (min_eye_area is not None and area != min_eye_area):
+        raise ValueError(f'min_eye_area must be an integer >= 1, got {min_eye_area!r}')
+    bits_a, bits_b = class_bits(classes_a), class_bits(classes_b)
+    labels, ids, table = labels.contiguous(), ids.contiguous(), table.contiguous()
+    K = int(table.shape[1])
+    dev = labels.device
+    lib = _lib.load()
+    raw = torch.empty((B, K, 6), device=dev, dtype=torch.int64)          # mkd_face_frame: 48 bytes, four int32 then four int64
+    with torch.cuda.device(dev):
+        for b0 in range(0, B, MAX_FRAME_BATCH):
+            n = min(B, b0 + MAX_FRAME_BATCH) - b0
+            nbytes = int(lib.mkd_face_frames_scratch_bytes(n, K))
+            if nbytes <= 0:
+                raise _lib.MkdError('mkd_face_frames_scratch_bytes refused the shape')
+            scratch = torch.empty((nbytes + 256,), device=dev, dtype=torch.uint8)          # (the stream keeps it alive until the kernels ran)
+            base = (scratch.data_ptr() + 255) & ~255
+            flat = (C.c_int32 * (2 * n))(*[v for pair in hw[b0:b0 + n] for v in pair])
+            _lib.check(lib.mkd_face_frames(C.c_void_p(labels[b0:].data_ptr()), C.c_void_p(ids[b0:].data_ptr()), C.c_void_p(table[b0:].data_ptr()),
+                                           n, S, K, flat, C.c_uint64(bits_a), C.c_uint64(bits_b), area, C.c_void_p(raw[b0:].data_ptr()),
+                                           C.c_void_p(base), C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'mkd_face_frames')
+    head = raw.view(torch.int32).reshape(B, K, 12)[..., :4].to(torch.int64)
+    return torch.cat((head, raw[..., 2:]), 2)

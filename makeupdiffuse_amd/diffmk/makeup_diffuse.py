@@ -806,13 +806,14 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                                                                            feather=self.paste_feather, return_alpha=True)
         return out
 
-    def _photo_pass(self, src_photos, ref_photos, src_boxes, ref_boxes, src_segs, x_T, size, batch, phi):
+    def _photo_pass(self, src_photos, ref_photos, src_boxes, ref_boxes, src_segs, x_T, size, batch, phi, align=False):
         """the single pass of transfer_photos for one batch of (photo, box) pairs on the device: crop-resize both, sample, decode,
-        paste_source -> (the decoded images [n,3,size,size], the source crops img01 the paste needs)"""
+        paste_source -> (the decoded images [n,3,size,size], the source crops img01 the paste needs).  ``align``: the boxes may be
+        photo.Frame's (photo.crop_regions: a batch without a rolled frame is the same crop_resize call)"""
         eng = self._require_engine()
         need_seg = self.fix_background or self.paste_background
-        cs = eng.crop_resize(src_photos, src_boxes, size, labels=src_segs)
-        cr = eng.crop_resize(ref_photos, ref_boxes, size)
+        cs = (eng.crop_regions if align else eng.crop_resize)(src_photos, src_boxes, size, labels=src_segs)
+        cr = (eng.crop_regions if align else eng.crop_resize)(ref_photos, ref_boxes, size)
         n = len(src_photos)
         if cr.img01.shape[0] != n:
             raise ValueError(f'{n} source photos but {cr.img01.shape[0]} reference photos')
@@ -837,9 +838,12 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         return img, src
 
     def _transfer_faces(self, src_photos, ref_photos, src_boxes, ref_boxes, src_segs, feather, x_T, size, batch, phi, max_faces,
-                        face_batch, return_faces, own_pixels=False, own_feather=2):
+                        face_batch, return_faces, own_pixels=False, own_feather=2, align=False, min_roll=5.0):
         """transfer_photos(max_faces=K): see there"""
+        from .. import photo
         K, fb = int(max_faces), int(face_batch)
+        if align and not float(min_roll) >= 0.0:
+            raise ValueError(f'min_roll must be >= 0 degrees, got {min_roll!r}')
         if own_pixels and (src_boxes is not None or self.face_parser is None):
             raise ValueError('own_pixels needs the faces from the attached face parser (src_boxes None): a box has no component to own pixels')
         if own_pixels and (int(own_feather) != own_feather or not 0 <= int(own_feather) <= 16):
@@ -854,7 +858,11 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             raise ValueError(f'{n} source photos but {len(ref_photos)} reference photos')
         if (src_boxes is None or ref_boxes is None) and self.face_parser is None:
             raise ValueError('transfer_photos: src_boxes and ref_boxes are needed (only an attached face parser can find the faces)')
-        is_box = lambda b: isinstance(b, (tuple, list)) and len(b) == 4 and not any(isinstance(v, (tuple, list)) for v in b)
+        # align: a box may carry the face's roll in degrees as a fifth entry
+        is_box = lambda b: isinstance(b, (tuple, list)) and len(b) in ((4, 5) if align else (4,)) and not any(isinstance(v, (tuple, list)) for v in b)
+        # (x0, y0, w, h[, angle]) -> the box itself when it is upright, else its Frame
+        region = lambda b: b if isinstance(b, photo.Frame) else (tuple(int(v) for v in b[:4]) if len(b) == 4 or float(b[4]) == 0.0
+                                                                    else photo.frame_from_box(b[:4], float(b[4])))
         if src_boxes is not None:
             src_boxes = list(src_boxes)
             if len(src_boxes) != n:
@@ -883,18 +891,24 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         src_photos = [p.to(self.device) for p in src_photos]
         ref_photos = [p.to(self.device) for p in ref_photos]
         owner = None
+        how = dict(oriented=True, min_roll=float(min_roll)) if align else {}          # align: find_faces returns Frames
         if own_pixels:
             src_boxes, owner = find_faces(self.face_parser, src_photos, max_faces=K, parse_size=self.parse_size, lut=self.parser_lut,
-                                          return_owner=True)
+                                          return_owner=True, **how)
+            faces = [list(bl) for bl in src_boxes] if align else [[tuple(int(v) for v in b) for b in bl] for bl in src_boxes]
         elif src_boxes is None:
-            src_boxes = find_faces(self.face_parser, src_photos, max_faces=K, parse_size=self.parse_size, lut=self.parser_lut)
-        faces = [[tuple(int(v) for v in b) for b in bl] for bl in src_boxes]
+            src_boxes = find_faces(self.face_parser, src_photos, max_faces=K, parse_size=self.parse_size, lut=self.parser_lut, **how)
+            faces = [list(bl) for bl in src_boxes] if align else [[tuple(int(v) for v in b) for b in bl] for bl in src_boxes]
+        else:
+            faces = [[region(b) for b in bl] for bl in src_boxes] if align else [[tuple(int(v) for v in b) for b in bl] for bl in src_boxes]
         if ref_boxes is None:
-            found = find_faces(self.face_parser, ref_photos, max_faces=1, parse_size=self.parse_size, lut=self.parser_lut)
+            found = find_faces(self.face_parser, ref_photos, max_faces=1, parse_size=self.parse_size, lut=self.parser_lut, **how)
             for i, f in enumerate(found):
                 if not f:
                     raise ValueError(f'transfer_photos: reference photo {i} shows no face')
             ref_boxes = [f[0] for f in found]
+        elif align:
+            ref_boxes = [region(b) for b in ref_boxes]
         items = [(i, k) for i, bl in enumerate(faces) for k in range(len(bl))]          # photo-major, rank-minor
         N = len(items)
         if x_T is not None and int(x_T.shape[0]) != N:
@@ -911,7 +925,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                         for k, v in batch.items() if k in ('txt_emb', 'txt_tokens', self.cond_stage_key)}
             img, src = self._photo_pass([src_photos[i] for i in pick], [ref_photos[i] for i in pick], [faces[i][k] for i, k in chunk],
                                         [ref_boxes[i] for i in pick], None if src_segs is None else [src_segs[i] for i in pick],
-                                        None if x_T is None else x_T[c0:c0 + len(chunk)], size, text, phi)
+                                        None if x_T is None else x_T[c0:c0 + len(chunk)], size, text, phi, align)
             imgs.append(img)
             srcs.append(src)
         if N:
@@ -921,14 +935,16 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                 at = torch.tensor(sel, device=img.device)
                 # own_pixels: rank k of photo i is row k of its table, the weight that row's share of every neighbourhood
                 weights = None if owner is None else owner_weights(owner, [(items[j][0], rank) for j in sel], own_feather)
-                eng.paste_photos([out[items[j][0]] for j in sel], [faces[items[j][0]][rank] for j in sel], img[at], src[at], feather, weights)
+                (eng.paste_regions if align else eng.paste_photos)([out[items[j][0]] for j in sel], [faces[items[j][0]][rank] for j in sel],
+                                                                   img[at], src[at], feather, weights)
         return (out, faces) if return_faces else out
 
     @torch.no_grad()
     def transfer_photos(self, src_photos, ref_photos, src_boxes=None, ref_boxes=None, src_segs=None, feather: int = 8,
                         x_T: Optional[torch.Tensor] = None, size: int = 256, batch: Optional[dict] = None,
                         guidance_rescale: Optional[float] = None, max_faces: Optional[int] = None, face_batch: int = 8,
-                        return_faces: bool = False, own_pixels: bool = False, own_feather: int = 2):
+                        return_faces: bool = False, own_pixels: bool = False, own_feather: int = 2, align: bool = False,
+                        min_roll: float = 5.0):
         """Makeup transfer on photographs at their own resolution: ``src_photos`` / ``ref_photos`` are uint8 [H,W,3] tensors of any
         size (lists; the photos of a call may differ in size) with a face box (x0, y0, w, h) each.  Both boxes are crop-resized to
         ``size`` on the device (photo.crop_resize: Pillow's antialiased bilinear bytes / 255, what PairFolderDataset gives for that
@@ -961,16 +977,28 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         the squashed map (every component of at least min_area pixels is a seed, also those beyond K); the paste of rank k of photo
         i is weighted by components.owner_weights (the fraction of the (2 own_feather + 1)^2 parse-pixel window that rank k owns,
         upsampled to the photo by mkd_paste_photo_weighted), so what a crop shows of a neighbour is not written, a face beyond K
-        keeps its bytes, and the weights of neighbouring faces sum to one across their border."""
+        keeps its bytes, and the weights of neighbouring faces sum to one across their border.
+
+        ``align`` (with max_faces; off: everything above, untouched; this rule is this build's): TILTED FACES.  Source and reference
+        faces are cropped along oriented squares (photo.Frame) so that the model sees every face upright, and the results are pasted
+        back along them (photo.crop_frames / paste_frames; with own_pixels the weight plane goes into paste_frames).  The faces come
+        from the attached parser -- face_parser.find_faces(oriented=True, min_roll=``min_roll``): the roll is measured on the device
+        from the two eye classes, and a face rolled by less than min_roll degrees keeps exactly its axis-aligned box -- or from caller
+        boxes that carry the roll as a fifth entry, (x0, y0, w, h, angle_deg) with w == h (a 4-tuple, or angle 0, is an upright box;
+        a photo.Frame instance is taken as it is).
+        An upright face takes the crop_resize / paste_photos calls above, so a batch without a rolled face is the path above call for
+        call.  ``return_faces`` then gives boxes for caller boxes that are upright and photo.Frame's for everything else."""
         from .. import photo
         phi = float(self.guidance_rescale if guidance_rescale is None else guidance_rescale)
         if not 0.0 <= phi <= 1.0:
             raise ValueError(f'guidance_rescale must lie in [0, 1], got {phi}')
         if max_faces is not None:
             return self._transfer_faces(src_photos, ref_photos, src_boxes, ref_boxes, src_segs, feather, x_T, size, batch, phi,
-                                        max_faces, face_batch, return_faces, own_pixels, own_feather)
+                                        max_faces, face_batch, return_faces, own_pixels, own_feather, align, min_roll)
         if own_pixels:
             raise ValueError('own_pixels only applies with max_faces')
+        if align:
+            raise ValueError('align only applies with max_faces')
         if return_faces or face_batch != 8:
             raise ValueError('return_faces / face_batch only apply with max_faces')
         if (src_boxes is None or ref_boxes is None) and self.face_parser is None:

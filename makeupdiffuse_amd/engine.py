@@ -1026,6 +1026,18 @@ class MkdEngine:
         from . import photo
         return photo.paste_photos(photos, boxes, samples, src01, feather, weights)
 
+    def crop_regions(self, photos, regions, size: int, labels=None):
+        """crop_resize for a batch whose regions may be photo.Frame's (photo.crop_regions on this engine's device): a rolled frame is
+        cropped along itself (include/mkd.h mkd_crop_frame), a batch without one is the crop_resize call above"""
+        from . import photo
+        dev = lambda ts: None if ts is None else [t.to(self.device) for t in ts]
+        return photo.crop_regions(dev(photos), regions, size, labels=dev(labels))
+
+    def paste_regions(self, photos, regions, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None):
+        """paste_photos for a batch whose regions may be photo.Frame's (photo.paste_regions; include/mkd.h mkd_paste_frame)"""
+        from . import photo
+        return photo.paste_regions(photos, regions, samples, src01, feather, weights)
+
     def eps_profile(self, x: torch.Tensor, t: torch.Tensor, csv_path: Optional[str] = None) -> Dict[str, Dict[str, float]]:
         """One eps with HIP events around every launch group -> {kernel class: {ms, flops, launches, bytes, ms_b2b}}: ``bytes`` =
         algorithmic HBM bytes of the memory-bound classes, ``ms_b2b`` = the class's launches replayed back to back between one

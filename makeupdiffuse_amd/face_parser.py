@@ -196,9 +196,9 @@ class FaceParser:
         return find_boxes(self, photos, grow=grow, parse_size=parse_size, lut=lut)
 
     def find_faces(self, photos, max_faces: int = 8, min_area: Optional[int] = None, grow: float = 1.0, parse_size: int = 512,
-                   lut=LUT_SEG, return_owner: bool = False):
+                   lut=LUT_SEG, return_owner: bool = False, oriented: bool = False, min_roll: float = 5.0):
         return find_faces(self, photos, max_faces=max_faces, min_area=min_area, grow=grow, parse_size=parse_size, lut=lut,
-                          return_owner=return_owner)
+                          return_owner=return_owner, oriented=oriented, min_roll=min_roll)
 
     def flops(self, H: int = 512, W: int = 512) -> float:
         return float(self.lib.mkd_parser_flops(self._h, int(H), int(W)))
@@ -258,7 +258,8 @@ def find_boxes(parser, photos, grow: float = 1.0, parse_size: int = 512, lut=LUT
 
 
 def find_faces(parser, photos, max_faces: int = 8, min_area: Optional[int] = None, grow: float = 1.0, parse_size: int = 512, lut=LUT_SEG,
-               classes: Sequence[int] = FACE_CLASSES, resize=None, components_of=None, return_owner: bool = False, owner_of=None):
+               classes: Sequence[int] = FACE_CLASSES, resize=None, components_of=None, return_owner: bool = False, owner_of=None,
+               oriented: bool = False, min_roll: float = 5.0, frames_of=None):
     """EVERY face of whole photos (uint8 [H,W,3] device tensors): one list of boxes (x0, y0, side, side) per photo, largest face first.
     Every photo is squashed to parse_size x parse_size and parsed exactly as find_boxes does; a face is an 8-connected component of the
     face classes with at least ``min_area`` pixels of the squashed map (components.label_components; default (parse_size // 32)^2,
@@ -273,7 +274,15 @@ def find_faces(parser, photos, max_faces: int = 8, min_area: Optional[int] = Non
     components.MAX_OUT: its first ``max_faces`` rows are the rows of the call above, so the boxes are the same, and EVERY row is a
     seed, so a face beyond ``max_faces`` keeps its pixels.  The metric is the squashed map's: anisotropic in photo pixels.  This rule
     is this build's.  ``resize``, ``components_of`` (the signature of components.label_components) and ``owner_of`` (that of
-    components.owner_map) replace the device calls (tests of the box arithmetic without a device)."""
+    components.owner_map) replace the device calls (tests of the box arithmetic without a device).
+
+    ``oriented``: photo.Frame's (cx, cy, side, c, s) instead of boxes; ranks, table order and owner map are unchanged.  Every
+    component's roll is measured on the device from the two eye classes (components.face_frames: labels 4 and 5 of ``lut``), which
+    needs the component ids, so the table is taken with want_ids.  A face whose measured |roll| is below ``min_roll`` degrees -- also
+    one without two eyes or rolled beyond 60 degrees, which measure as 0 -- gets EXACTLY the frame of its box above,
+    photo.frame_from_box(photo.grow_square_box(...)): upright faces crop as before.  Any other face gets photo.grow_frame of its row:
+    the reference's ratios applied in the face's own frame.  ``frames_of`` (the signature of components.face_frames) replaces the
+    device call.  Still one device-to-host copy per chunk: the frames travel with the table."""
     from . import components, photo
     K = int(max_faces)
     if K != max_faces or not 1 <= K <= components.MAX_OUT:
@@ -289,6 +298,10 @@ def find_faces(parser, photos, max_faces: int = 8, min_area: Optional[int] = Non
         raise ValueError(f'min_area must be >= 1, got {min_area!r} (parse_size {parse_size})')
     if return_owner:
         owner_of = owner_of or components.owner_map
+    if oriented:
+        frames_of = frames_of or components.face_frames
+        if not float(min_roll) >= 0.0:
+            raise ValueError(f'min_roll must be >= 0 degrees, got {min_roll!r}')
     out: List[List[Tuple[int, int, int, int]]] = []
     owners = []
     for b0 in range(0, len(photos), MAX_BATCH):
@@ -298,17 +311,30 @@ def find_faces(parser, photos, max_faces: int = 8, min_area: Optional[int] = Non
         if return_owner:
             table, count, ids = components_of(labels, classes, min_area=area, max_out=components.MAX_OUT, want_ids=True)
             owners.append(torch.as_tensor(owner_of(ids, table)))
+        elif oriented:
+            table, count, ids = components_of(labels, classes, min_area=area, max_out=K, want_ids=True)
         else:
             table, count = components_of(labels, classes, min_area=area, max_out=K)[:2]
         table, count = torch.as_tensor(table), torch.as_tensor(count)
-        both = torch.cat((table.reshape(len(chunk), -1), count.reshape(len(chunk), 1).to(table.dtype)), 1).cpu().tolist()
+        parts = [table.reshape(len(chunk), -1), count.reshape(len(chunk), 1).to(table.dtype)]
+        rows = int(table.shape[1])
+        if oriented:
+            fr = torch.as_tensor(frames_of(labels, ids, table, [(int(p.shape[0]), int(p.shape[1])) for p in chunk]))
+            parts = [t.to(torch.int64) for t in parts] + [fr.reshape(len(chunk), -1).to(torch.int64)]
+        both = torch.cat(parts, 1).cpu().tolist()
         for p, row in zip(chunk, both):
             H, W = int(p.shape[0]), int(p.shape[1])
             faces = []
-            for k in range(min(int(row[-1]), K)):
+            for k in range(min(int(row[6 * rows]), K)):
                 r0, r1, c0, c1 = row[6 * k + 2:6 * k + 6]
                 scaled = (r0 * H // S, min(H, -(-(r1 + 1) * H // S)) - 1, c0 * W // S, min(W, -(-(c1 + 1) * W // S)) - 1)
-                faces.append(photo.grow_square_box(scaled, H, W, grow))
+                box = photo.grow_square_box(scaled, H, W, grow)
+                if oriented:
+                    frow = row[6 * rows + 1 + 8 * k:6 * rows + 9 + 8 * k]
+                    rolled = abs(photo.frame_roll(frow)) >= float(min_roll) and (frow[2], frow[3]) != (components.FRAME_UNIT, 0)
+                    faces.append(photo.grow_frame(frow, S, H, W, grow) if rolled else photo.frame_from_box(box))
+                else:
+                    faces.append(box)
             out.append(faces)
     if return_owner:
         return out, (torch.cat(owners) if owners else torch.empty((0, S, S), dtype=torch.uint8))

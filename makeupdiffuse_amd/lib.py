@@ -46,6 +46,18 @@ class PhotoDescC(C.Structure):
                 ('bw', C.c_int32), ('bh', C.c_int32), ('labels', C.c_void_p)]
 
 
+class PhotoFrameDescC(C.Structure):
+    """mkd_photo_frame_desc: a photo and an oriented square in it"""
+    _fields_ = [('pixels', C.c_void_p), ('pitch_bytes', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('cx', C.c_double), ('cy', C.c_double),
+                ('side', C.c_double), ('c', C.c_double), ('s', C.c_double), ('labels', C.c_void_p)]
+
+
+class FaceFrameC(C.Structure):
+    """mkd_face_frame (48 bytes)"""
+    _fields_ = [('n_a', C.c_int32), ('n_b', C.c_int32), ('cq', C.c_int32), ('sq', C.c_int32), ('umin', C.c_int64), ('umax', C.c_int64),
+                ('vmin', C.c_int64), ('vmax', C.c_int64)]
+
+
 class SampleMaskC(C.Structure):
     _fields_ = [('x0', C.c_void_p), ('mask', C.c_void_p), ('mask_batch', C.c_int32), ('mask_channels', C.c_int32),
                 ('sqrt_alphas_cumprod', C.POINTER(C.c_float)), ('sqrt_one_minus_alphas_cumprod', C.POINTER(C.c_float)),
@@ -140,6 +152,10 @@ SIGNATURES = {
     'mkd_resize_coeffs': (_I, [_I, _I, _I, _I, _P, _P, _P]),
     'mkd_paste_photo': (_I, [C.POINTER(PhotoDescC), _I, _I, _P, _P, _I, _P]),
     'mkd_paste_photo_weighted': (_I, [C.POINTER(PhotoDescC), _I, _I, _P, _P, _I, _P, _I, _I, _P]),
+    'mkd_crop_frame': (_I, [C.POINTER(PhotoFrameDescC), _I, _I, _P, _P, _P, _P]),
+    'mkd_paste_frame': (_I, [C.POINTER(PhotoFrameDescC), _I, _I, _P, _P, _I, _P, _I, _I, _P]),
+    'mkd_face_frames_scratch_bytes': (C.c_size_t, [_I, _I]),
+    'mkd_face_frames': (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(C.c_int32), C.c_uint64, C.c_uint64, _I, _P, _P, _P]),
     'mkd_vae_configure': (_I, [_P, C.POINTER(VaeConfigC)]),
     'mkd_vae_finalize': (_I, [_P]),
     'mkd_decode': (_I, [_P, _P, _I, _I, _I, _F, _P, _P]),

@@ -4,10 +4,13 @@ sample back into the photo at its own resolution with the photo's fine detail ke
 Laplacian detail transfer of PSGAN / EleGANt ``Inference.postprocess``).  include/mkd.h states both rules.
 
 Photos are uint8 [H,W,3] device tensors (rows may be ``pitch`` bytes apart: stride (pitch, 3, 1), any alignment); the photos of one
-call may differ in size.  Boxes are (x0, y0, w, h) in photo pixels.  The arithmetic is libmkd's: there is no CPU path."""
+call may differ in size.  Boxes are (x0, y0, w, h) in photo pixels.  Tilted faces take the same path along a rotated square, a Frame
+(cx, cy, side, c, s): crop_frames / paste_frames (mkd_crop_frame, mkd_paste_frame), and crop_regions / paste_regions for batches that
+mix boxes and frames.  The arithmetic is libmkd's: there is no CPU path."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from collections import namedtuple
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
@@ -26,6 +29,9 @@ MAX_WEIGHT_SIDE = 2048  # rows / columns of a paste's photo-wide weight plane
 UP_RATIO, DOWN_RATIO, WIDTH_RATIO = 0.6 / 0.85, 0.2 / 0.85, 0.2 / 0.85
 
 Cropped = namedtuple('Cropped', 'img01 labels u8')
+# an oriented square: centre and side in photo pixels (pixel (X, Y) has its centre at (X + .5, Y + .5)), (c, s) the unit vector of the
+# face's "right" axis; (-s, c) is its "down" axis and c = 1, s = 0 is upright (include/mkd.h mkd_photo_frame_desc)
+Frame = namedtuple('Frame', 'cx cy side c s')
 
 
 def _stream() -> int:
@@ -185,6 +191,253 @@ def paste_photos(photos, boxes, samples: torch.Tensor, src01: torch.Tensor, feat
     return photos
 
 
+# ---- tilted faces: the same path along a rotated square (include/mkd.h mkd_crop_frame, mkd_paste_frame; this build's rule) ----------
+def frame_from_box(box, angle_deg: float = 0.0) -> Frame:
+    """the square box (x0, y0, w, h) rotated about its centre by ``angle_deg`` (the face's "right" axis turns from +x towards +y,
+    which points DOWN in a photo) as a Frame.  Multiples of 90 degrees give exact 0 / +-1 for c and s.  A Frame is a square: a
+    non-square box raises ValueError (with angle 0 such a box needs no Frame: crop_resize takes it as it is)."""
+    if len(box) != 4:
+        raise ValueError(f'a box is (x0, y0, w, h), got {box!r}')
+    x0, y0, bw, bh = (float(v) for v in box)
+    a = float(angle_deg)
+    if not (bw > 0 and bh > 0) or not math.isfinite(a):
+        raise ValueError(f'box {box!r} / angle {angle_deg!r}: the box must be non-empty and the angle finite')
+    if bw != bh:
+        raise ValueError(f'box {box!r} is not square: only a square box can be rotated into a Frame (angle {angle_deg!r})')
+    quarter = a / 90.0
+    if quarter == int(quarter):
+        c, s = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(quarter) % 4]
+    else:
+        c, s = math.cos(math.radians(a)), math.sin(math.radians(a))
+    return Frame(x0 + bw / 2.0, y0 + bh / 2.0, bw, c, s)
+
+
+def box_from_frame(frame) -> Optional[Tuple[int, int, int, int]]:
+    """the integer box (x0, y0, side, side) an UPRIGHT frame (c = 1, s = 0) with integer corners stands for, else None: such a frame
+    takes crop_resize / paste_photos, the calls of the axis-aligned path"""
+    f = Frame(*frame)
+    if f.s != 0 or f.c != 1:
+        return None
+    x0, y0 = f.cx - f.side / 2.0, f.cy - f.side / 2.0
+    if x0 != int(x0) or y0 != int(y0) or f.side != int(f.side) or f.side < 1:
+        return None
+    return int(x0), int(y0), int(f.side), int(f.side)
+
+
+def frame_roll(row) -> float:
+    """degrees of roll of a components.face_frames row (n_a, n_b, cq, sq, ...)"""
+    return math.degrees(math.atan2(int(row[3]), int(row[2])))
+
+
+def grow_frame(face_frame_row, S: int, H: int, W: int, grow: float = 1.0) -> Frame:
+    """A components.face_frames row (n_a, n_b, cq, sq, umin, umax, vmin, vmax) of a face found on the S x S squashed map of an H x W
+    photo -> the crop around it as a Frame.  (1) the extents become photo pixels along the unit axes e_u = (cq, sq) / |(cq, sq)| and
+    e_v = (-sq, cq) / |(cq, sq)|: divided by 2 S |(cq, sq)| (= 2 S 16384 up to the rounding of cq and sq), and widened by half the
+    footprint of a squashed pixel, (|c| W / S + |s| H / S) / 2 along e_u and (|s| W / S + |c| H / S) / 2 along e_v (the extents are those
+    of pixel CENTRES; find_faces scales its boxes outwards in the same way); (2) grow_square_box's ratios IN THAT FRAME: up 0.6/0.85 and
+    down 0.2/0.85 of the height along e_v, 0.2/0.85 of the width per side along e_u, times ``grow``; (3) squared about its centre with
+    the longer side, the side limited to min(H, W); (4) the centre rotated back to photo coordinates.  The frame is NOT shifted into
+    the photo: the crop replicates edges and the paste writes only what lies inside."""
+    row = [int(v) for v in face_frame_row]
+    if len(row) != 8:
+        raise ValueError(f'a face frame row holds 8 integers (n_a, n_b, cq, sq, umin, umax, vmin, vmax), got {face_frame_row!r}')
+    _, _, cq, sq, umin, umax, vmin, vmax = row
+    if umax < umin or vmax < vmin:
+        raise ValueError('the face frame row is empty (a table row past the last component): there is no frame to grow')
+    if not grow >= 0:
+        raise ValueError(f'grow must be >= 0, got {grow!r}')
+    norm = math.hypot(cq, sq)
+    if norm == 0:
+        raise ValueError(f'the face frame row has no direction: (cq, sq) = {(cq, sq)}')
+    c, s = cq / norm, sq / norm
+    unit = 2.0 * S * norm
+    pad_u = (abs(c) * W / S + abs(s) * H / S) / 2.0
+    pad_v = (abs(s) * W / S + abs(c) * H / S) / 2.0
+    u0, u1 = umin / unit - pad_u, umax / unit + pad_u
+    v0, v1 = vmin / unit - pad_v, vmax / unit + pad_v
+    fw, fh = u1 - u0, v1 - v0
+    top, bottom = v0 - grow * UP_RATIO * fh, v1 + grow * DOWN_RATIO * fh
+    left, right = u0 - grow * WIDTH_RATIO * fw, u1 + grow * WIDTH_RATIO * fw
+    side = float(min(max(bottom - top, right - left), H, W))
+    uc, vc = (left + right) / 2.0, (top + bottom) / 2.0
+    return Frame(c * uc - s * vc, s * uc + c * vc, side, c, s)
+
+
+def check_frame(frame, H: int, W: int, size: int) -> Frame:
+    """a Frame of floats, validated against the photo and the library's limits (include/mkd.h mkd_photo_frame_desc)"""
+    if len(frame) != 5:
+        raise ValueError(f'a frame is (cx, cy, side, c, s), got {frame!r}')
+    f = Frame(*(float(v) for v in frame))
+    if not all(math.isfinite(v) for v in f):
+        raise ValueError(f'frame {frame!r} must hold finite numbers')
+    if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        raise ValueError(f'photo {H}x{W}: H, W must be 1..{MAX_SIDE}')
+    if not 0 < f.side <= 32 * size:
+        raise ValueError(f'frame {tuple(f)}: the side must lie in (0, 32 x size = {32 * size}]')
+    if abs(f.c * f.c + f.s * f.s - 1.0) > 1e-9:
+        raise ValueError(f'frame {tuple(f)}: (c, s) must be a unit vector')
+    if not (-f.side <= f.cx <= W + f.side and -f.side <= f.cy <= H + f.side):
+        raise ValueError(f'frame {tuple(f)}: the centre must lie within one side of the {H}x{W} photo')
+    return f
+
+
+def _frame_descs(photos: Sequence[torch.Tensor], frames, labels: Optional[Sequence[torch.Tensor]]):
+    arr = (_lib.PhotoFrameDescC * len(photos))()
+    for i, (p, f) in enumerate(zip(photos, frames)):
+        H, W = int(p.shape[0]), int(p.shape[1])
+        arr[i].pixels = p.data_ptr()
+        arr[i].pitch_bytes = int(p.stride(0)) if H > 1 else 3 * W
+        arr[i].H, arr[i].W = H, W
+        arr[i].cx, arr[i].cy, arr[i].side, arr[i].c, arr[i].s = f
+        arr[i].labels = None if labels is None else labels[i].data_ptr()
+    return arr
+
+
+def _label_list(labels, photos, dev) -> Optional[List[torch.Tensor]]:
+    if labels is None:
+        return None
+    if isinstance(labels, torch.Tensor):
+        labels = [labels] if labels.dim() == 2 else list(labels.unbind(0))
+    labels = list(labels)
+    if len(labels) != len(photos):
+        raise ValueError(f'{len(photos)} photos but {len(labels)} label maps')
+    out = []
+    for p, l in zip(photos, labels):
+        if not isinstance(l, torch.Tensor) or l.dtype != torch.uint8 or tuple(l.shape) != tuple(p.shape[:2]):
+            raise ValueError(f'a label map is a uint8 [H,W] tensor of its photo\'s size {tuple(p.shape[:2])}, '
+                             f'got {getattr(l, "dtype", type(l))} {tuple(getattr(l, "shape", ()))}')
+        out.append(l.to(dev).contiguous())
+    return out
+
+
+def crop_frames(photos, frames, size: int, labels=None, want_u8: bool = False) -> Cropped:
+    """crop_resize along ROTATED squares (mkd_crop_frame): photos and their Frames (cx, cy, side, c, s) -> Cropped(img01 fp32
+    [B,3,S,S], labels uint8 [B,S,S] or None, u8 uint8 [B,S,S,3] or None).  The face's "right" axis (c, s) becomes the crop's +x: a
+    rolled face comes out upright.  Pillow's triangle filter taken in the face's frame, in double and in one pass (within 1 of
+    crop_resize's bytes for an upright integer box); the square may stick out of the photo, edges are replicated; labels are
+    sampled at the output pixel centres without interpolation."""
+    S = _check_size(size)
+    photos = _photo_list(photos, 'crop_frames')
+    B = len(photos)
+    if len(frames) != B:
+        raise ValueError(f'{B} photos but {len(frames)} frames')
+    frames = [check_frame(f, int(p.shape[0]), int(p.shape[1]), S) for p, f in zip(photos, frames)]
+    dev = photos[0].device
+    photos = [p if _rows_ok(p) else p.contiguous() for p in photos]
+    labels = _label_list(labels, photos, dev)
+    lib = _lib.load()
+    img01 = torch.empty((B, 3, S, S), device=dev, dtype=torch.float32)
+    lab_out = torch.empty((B, S, S), device=dev, dtype=torch.uint8) if labels is not None else None
+    u8 = torch.empty((B, S, S, 3), device=dev, dtype=torch.uint8) if want_u8 else None
+    P = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+    with torch.cuda.device(dev):
+        for b0 in range(0, B, MAX_BATCH):
+            b1 = min(B, b0 + MAX_BATCH)
+            arr = _frame_descs(photos[b0:b1], frames[b0:b1], None if labels is None else labels[b0:b1])
+            _lib.check(lib.mkd_crop_frame(arr, b1 - b0, S, P(img01[b0:b1]), P(None if u8 is None else u8[b0:b1]),
+                                          P(None if lab_out is None else lab_out[b0:b1]), C.c_void_p(_stream())), 'mkd_crop_frame')
+    return Cropped(img01, lab_out, u8)
+
+
+def _check_paste(what: str, plist, regions, samples, src01, feather, weights):
+    rho = int(feather)
+    if rho != feather or not 0 <= rho <= MAX_FEATHER:
+        raise ValueError(f'feather must be an integer 0..{MAX_FEATHER} photo pixels, got {feather!r}')
+    B = len(plist)
+    if len(regions) != B:
+        raise ValueError(f'{B} photos but {len(regions)} {what}')
+    if samples.dim() != 4 or samples.shape[0] != B or samples.shape[1] != 3 or samples.shape[2] != samples.shape[3]:
+        raise ValueError(f'samples must be [{B},3,S,S], got {tuple(samples.shape)}')
+    if tuple(src01.shape) != tuple(samples.shape):
+        raise ValueError(f'src01 {tuple(src01.shape)} must have the shape of samples {tuple(samples.shape)}')
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor) or weights.dim() != 3 or weights.shape[0] != B or weights.dtype != torch.float32 \
+                or not (1 <= weights.shape[1] <= MAX_WEIGHT_SIDE and 1 <= weights.shape[2] <= MAX_WEIGHT_SIDE):
+            raise ValueError(f'weights must be fp32 [{B},wh,ww] with wh, ww in 1..{MAX_WEIGHT_SIDE}, got '
+                             f'{getattr(weights, "dtype", type(weights))} {tuple(getattr(weights, "shape", ()))}')
+    return rho, _check_size(int(samples.shape[2]))
+
+
+def paste_frames(photos, frames, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None):
+    """paste_photos along ROTATED squares (mkd_paste_frame), IN PLACE: every photo pixel whose centre lies in its Frame gets
+    photo + a * g * bilinear((samples + 1) / 2 - src01) * 255 sampled at its place in the frame, in double; a fades over ``feather``
+    photo pixels at ALL four sides of the square, g is the bilinear sample of ``weights`` (fp32 [B,wh,ww] over the whole photo, as in
+    paste_photos) or 1.  Bytes outside the square, and everything of a square that does not reach its photo, stay.  Returns
+    ``photos``."""
+    plist = _photo_list(photos, 'paste_frames')
+    rho, S = _check_paste('frames', plist, frames, samples, src01, feather, weights)
+    B = len(plist)
+    frames = [check_frame(f, int(p.shape[0]), int(p.shape[1]), S) for p, f in zip(plist, frames)]
+    for p in plist:
+        if not _rows_ok(p):
+            raise ValueError('paste_frames writes in place: a photo needs interleaved RGB rows (stride (pitch, 3, 1))')
+    dev = plist[0].device
+    t = samples.to(device=dev, dtype=torch.float32).contiguous()
+    s = src01.to(device=dev, dtype=torch.float32).contiguous()
+    w = None if weights is None else weights.to(device=dev).contiguous()
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        for b0 in range(0, B, MAX_BATCH):
+            b1 = min(B, b0 + MAX_BATCH)
+            arr = _frame_descs(plist[b0:b1], frames[b0:b1], None)
+            _lib.check(lib.mkd_paste_frame(arr, b1 - b0, S, C.c_void_p(t[b0:b1].data_ptr()), C.c_void_p(s[b0:b1].data_ptr()), rho,
+                                           C.c_void_p(None if w is None else w[b0:b1].data_ptr()), 0 if w is None else int(w.shape[1]),
+                                           0 if w is None else int(w.shape[2]), C.c_void_p(_stream())), 'mkd_paste_frame')
+    return photos
+
+
+def split_regions(regions):
+    """regions (boxes (x0, y0, w, h) and Frames, mixed) -> (indices that take the axis-aligned calls, their boxes, indices that take
+    the frame calls, their Frames): a box, and a Frame that box_from_frame can turn into one, go the axis-aligned way"""
+    bi, boxes, fi, frames = [], [], [], []
+    for i, r in enumerate(regions):
+        box = tuple(r) if len(r) == 4 else box_from_frame(r)
+        if box is not None:
+            bi.append(i)
+            boxes.append(box)
+        else:
+            fi.append(i)
+            frames.append(Frame(*r))
+    return bi, boxes, fi, frames
+
+
+def crop_regions(photos, regions, size: int, labels=None) -> Cropped:
+    """crop_resize for boxes and crop_frames for rolled Frames in one batch, results in the order of ``regions``.  Without a rolled
+    Frame this is exactly ONE crop_resize call on the whole batch."""
+    photos = _photo_list(photos, 'crop_regions')
+    if len(regions) != len(photos):
+        raise ValueError(f'{len(photos)} photos but {len(regions)} regions')
+    bi, boxes, fi, frames = split_regions(regions)
+    if not fi:
+        return crop_resize(photos, boxes, size, labels=labels)
+    labels = _label_list(labels, photos, photos[0].device)
+    pick = lambda seq, idx: None if seq is None else [seq[i] for i in idx]
+    cf = crop_frames(pick(photos, fi), frames, size, labels=pick(labels, fi))
+    if not bi:
+        return cf
+    cb = crop_resize(pick(photos, bi), boxes, size, labels=pick(labels, bi))
+    order = torch.tensor(bi + fi, device=cf.img01.device).argsort()
+    merge = lambda a, b: None if a is None else torch.cat((a, b))[order]
+    return Cropped(merge(cb.img01, cf.img01), merge(cb.labels, cf.labels), None)
+
+
+def paste_regions(photos, regions, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None):
+    """paste_photos for boxes and paste_frames for rolled Frames in one batch (a photo appears once per call, so the split changes
+    nothing).  Without a rolled Frame this is exactly ONE paste_photos call on the whole batch."""
+    plist = _photo_list(photos, 'paste_regions')
+    if len(regions) != len(plist):
+        raise ValueError(f'{len(plist)} photos but {len(regions)} regions')
+    bi, boxes, fi, frames = split_regions(regions)
+    if not fi:
+        paste_photos(plist, boxes, samples, src01, feather, weights)
+        return photos
+    for idx, regs, fn in ((bi, boxes, paste_photos), (fi, frames, paste_frames)):
+        if idx:
+            at = torch.tensor(idx, device=samples.device)
+            fn([plist[i] for i in idx], regs, samples[at], src01[at], feather, None if weights is None else weights[at.to(weights.device)])
+    return photos
+
+
 def resize_coeffs(n: int, in0: int, length: int, size: int, device=None):
     """The coefficient table of one axis as the device builds it (mkd_resize_coeffs; debugging and tests): (bounds int32 [S,2] =
     (xmin, xmax), coefficients int32 [S, ksize])."""
@@ -242,19 +495,29 @@ def centred_square(H: int, W: int) -> Tuple[int, int, int, int]:
 
 def read_boxes_multi(path: str) -> Dict[str, List[Tuple[int, int, int, int]]]:
     """Lines of '<image name> x0 y0 w h' -> {name: [(x0, y0, w, h), ...]}: a name may repeat, one line per face, kept in file order;
-    blank lines and lines starting with # are skipped."""
+    blank lines and lines starting with # are skipped.  A line may carry a sixth field, the face's roll in degrees ('<image name> x0
+    y0 w h angle'): it reads as the 5-tuple (x0, y0, w, h, angle) that transfer_photos(align=True) takes."""
     out: Dict[str, List[Tuple[int, int, int, int]]] = {}
     with open(path, 'r') as f:
         for ln, line in enumerate(f, 1):
             parts = line.split()
             if not parts or parts[0].startswith('#'):
                 continue
-            if len(parts) != 5:
-                raise ValueError(f'{path}:{ln}: expected "name x0 y0 w h", got {line.strip()!r}')
+            if len(parts) not in (5, 6):
+                raise ValueError(f'{path}:{ln}: expected "name x0 y0 w h" or "name x0 y0 w h angle", got {line.strip()!r}')
             try:
-                out.setdefault(parts[0], []).append(tuple(int(v) for v in parts[1:]))
+                box = tuple(int(v) for v in parts[1:5])
             except ValueError:
                 raise ValueError(f'{path}:{ln}: the box of {parts[0]} must hold four integers') from None
+            if len(parts) == 6:
+                try:
+                    angle = float(parts[5])
+                except ValueError:
+                    angle = math.nan
+                if not math.isfinite(angle):
+                    raise ValueError(f'{path}:{ln}: the angle of {parts[0]} must be a finite number of degrees') from None
+                box = box + (angle,)
+            out.setdefault(parts[0], []).append(box)
     return out
 
 
@@ -287,7 +550,7 @@ class PhotoPairDataset:
         a = np.array(Image.open(os.path.join(self.root, 'images', name)).convert('RGB'), dtype=np.uint8)
         H, W = a.shape[:2]
         box = self.boxes.get(name, centred_square(H, W))
-        x0, y0, bw, bh = box
+        x0, y0, bw, bh = box[:4]
         if bw < 1 or bh < 1 or x0 < 0 or y0 < 0 or x0 + bw > W or y0 + bh > H:
             raise ValueError(f'box {box} of {name} is empty or not inside the {H}x{W} photo')
         seg = None
@@ -298,7 +561,7 @@ class PhotoPairDataset:
             if s.size != (W, H):
                 raise ValueError(f'label map of {name} is {s.size[1]}x{s.size[0]}, the photo {H}x{W}: label maps are at photo resolution')
             seg = torch.from_numpy(np.array(s, dtype=np.uint8))
-        return torch.from_numpy(a), tuple(int(v) for v in box), seg
+        return torch.from_numpy(a), tuple(int(v) for v in box[:4]), seg          # (a line's angle stays in self.faces)
 
     def __getitem__(self, i: int) -> Dict[str, object]:
         s, r = self.pairs[i]

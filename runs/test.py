@@ -105,6 +105,11 @@ def build_parser():
                     'neighbouring face does not repaint it and a face beyond K keeps its bytes')
     ap.add_argument('--own-feather', type=int, default=2, metavar='N', help='with --own-pixels: blend neighbouring faces over N pixels of the '
                     'parsed map on both sides of their border, 0..16')
+    ap.add_argument('--align-faces', action='store_true', help='with --photos --max-faces: tilted faces -- every face is cropped along a square '
+                    'rotated by its roll (measured from the two eyes of the parsed map with --face-parser, or the sixth field of a boxes line, '
+                    '"name x0 y0 w h angle" in degrees), so the model sees it upright, and pasted back along that square')
+    ap.add_argument('--min-roll', type=float, default=5.0, metavar='DEG', help='with --align-faces: a face found by the parser whose measured '
+                    'roll is below DEG degrees keeps its axis-aligned box')
     ap.add_argument('--photo-feather', type=int, default=8, help='fade the pasted face in over this many photo pixels at the box sides, 0..64')
     ap.add_argument('--face-parser', default=None, metavar='PATH|random', help='attach the face-parsing network (upstream face-parsing.PyTorch '
                     'state dict, e.g. 79999_iter.pth; "random": seeded random weights, for plumbing runs): label maps that --fix-background, '
@@ -199,6 +204,13 @@ def main():
             raise SystemExit('--own-feather must be 0..16 pixels of the parsed map')
     elif args.own_feather != 2:
         raise SystemExit('--own-feather only applies with --own-pixels')
+    if args.align_faces:
+        if not args.photos or args.max_faces is None:
+            raise SystemExit('--align-faces only applies with --photos --max-faces')
+        if not args.min_roll >= 0.0:
+            raise SystemExit('--min-roll must be >= 0 degrees')
+    elif args.min_roll != 5.0:
+        raise SystemExit('--min-roll only applies with --align-faces (and --photos)')
     if not 0 <= args.photo_feather <= 64:
         raise SystemExit('--photo-feather must be 0..64 photo pixels')
     if args.photo_feather != 8 and not args.photos:
@@ -317,13 +329,16 @@ def main():
             else:
                 K = args.max_faces
                 ref_boxes = items['ref_box']
+                tilt = dict(oriented=True, min_roll=args.min_roll) if args.align_faces else {}          # (then the faces are photo.Frame's)
                 if find:          # (a reference in which the parser finds no face keeps its centred largest square)
                     look = lambda ps, k: model.face_parser.find_faces([p.cuda(local) for p in ps], max_faces=k, parse_size=model.parse_size,
-                                                                      lut=model.parser_lut)
+                                                                      lut=model.parser_lut, **tilt)
                     faces = look(items['src_photo'], K)
                     ref_boxes = [f[0] if f else b for f, b in zip(look(items['ref_photo'], 1), ref_boxes)]
-                else:          # the lines of the source's name, else the one box the single-face run uses
-                    faces = [photo_ds.faces.get(photo_ds.pairs[i][0], [items['src_box'][i - b0]])[:K] for i in range(b0, b1)]
+                else:          # the lines of the source's name, else the one box the single-face run uses; a line's angle counts with --align-faces
+                    cut = (lambda b: b) if args.align_faces else (lambda b: b[:4])
+                    faces = [[cut(b) for b in photo_ds.faces.get(photo_ds.pairs[i][0], [items['src_box'][i - b0]])[:K]] for i in range(b0, b1)]
+                    ref_boxes = [cut(photo_ds.faces.get(photo_ds.pairs[i][1], [ref_boxes[i - b0]])[0]) for i in range(b0, b1)]
                 x_F = None
                 if args.seed is not None:          # one start latent per face: seed + pair index, then the face's rank
                     h8 = args.res // 8
@@ -331,6 +346,8 @@ def main():
                            for i in range(b0, b1) for k in range(len(faces[i - b0]))]
                     x_F = torch.cat(x_F).cuda(local) if x_F else None
                 own = dict(own_pixels=True, own_feather=args.own_feather) if args.own_pixels else {}
+                if args.align_faces:
+                    own.update(align=True, min_roll=args.min_roll)
                 # (--own-pixels: the model finds the same faces again, with their owner map; the count above sizes the start latents)
                 photos, faces = model.transfer_photos(items['src_photo'], items['ref_photo'], None if args.own_pixels else faces, ref_boxes,
                                                       src_segs=items.get('src_seg'), feather=args.photo_feather, x_T=x_F, size=args.res, batch=text,
