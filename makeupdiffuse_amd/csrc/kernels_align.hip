@@ -1,6 +1,6 @@
 // Tilted faces (include/mkd.h: mkd_crop_frame, mkd_paste_frame, mkd_face_frames): the photo path along a rotated square instead of an
 // axis-aligned box.  Context-free; the calls only enqueue.  The arithmetic of the crop and the paste is IEEE double with nothing
-// contracted (every product that feeds an addition passes through an empty asm statement, as in kernels_photo.hip), that of the frames
+// contracted (every product that feeds an addition is a mkd_rounded_mul, mkd_common.h), that of the frames
 // is 64-bit integer except for one direction per face: tests/photo_frame_ref.py restates all of it operation for operation.
 //
 // Crop: one launch, a thread owns one output pixel (its three channels and one weight sum) and walks the photo pixels whose tent
@@ -40,12 +40,6 @@ struct FfArgs {
     int hw[MKD_PHOTO_MAX_BATCH][2];       // H, W of the photo of image b
 };
 
-// a product that feeds an addition: one correctly rounded multiplication, never half of a fused multiply-add
-__device__ __forceinline__ double al_mul(double a, double b) {
-    double p = a * b;
-    asm("" : "+v"(p));
-    return p;
-}
 __device__ __forceinline__ int al_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ unsigned char al_byte(double o) {
     const double r = rint(o);
@@ -62,30 +56,30 @@ __global__ __launch_bounds__(CF_TW * CF_TH) void crop_frame_kernel(const FrArgs 
     const double scale = d.side / (double)S;
     const double fs = scale < 1.0 ? 1.0 : scale;
     const double half = d.side * 0.5;
-    const double u = al_mul((double)j + 0.5, scale) - half, v = al_mul((double)i + 0.5, scale) - half;
-    const double qx = (d.cx + al_mul(d.c, u)) - al_mul(d.s, v);
-    const double qy = (d.cy + al_mul(d.s, u)) + al_mul(d.c, v);
-    const double R = al_mul(fs, fabs(d.c) + fabs(d.s));
+    const double u = mkd_rounded_mul((double)j + 0.5, scale) - half, v = mkd_rounded_mul((double)i + 0.5, scale) - half;
+    const double qx = (d.cx + mkd_rounded_mul(d.c, u)) - mkd_rounded_mul(d.s, v);
+    const double qy = (d.cy + mkd_rounded_mul(d.s, u)) + mkd_rounded_mul(d.c, v);
+    const double R = mkd_rounded_mul(fs, fabs(d.c) + fabs(d.s));
     // |q| <= 16384 + 33 * 1024 * 2 and R <= 46341: every bound fits an int
     const int xa = (int)floor(qx - R), xb = (int)floor(qx + R);
     const int ya = (int)floor(qy - R), yb = (int)floor(qy + R);
     double sw = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0;
     for (int Y = ya; Y <= yb; ++Y) {
         const double dy = ((double)Y + 0.5) - qy;
-        const double sdy = al_mul(d.s, dy), cdy = al_mul(d.c, dy);
+        const double sdy = mkd_rounded_mul(d.s, dy), cdy = mkd_rounded_mul(d.c, dy);
         const unsigned char* row = d.pixels + (size_t)al_clampi(Y, 0, d.H - 1) * d.pitch_bytes;
         for (int X = xa; X <= xb; ++X) {
             const double dx = ((double)X + 0.5) - qx;
-            const double du = al_mul(d.c, dx) + sdy;
-            const double dv = cdy - al_mul(d.s, dx);
+            const double du = mkd_rounded_mul(d.c, dx) + sdy;
+            const double dv = cdy - mkd_rounded_mul(d.s, dx);
             const double wu = 1.0 - fabs(du) / fs, wv = 1.0 - fabs(dv) / fs;
             if (!(wu > 0.0) || !(wv > 0.0)) continue;          // a zero weight adds +0.0 to every sum: skipping it changes no bit
-            const double w = al_mul(wu, wv);
+            const double w = mkd_rounded_mul(wu, wv);
             const unsigned char* p = row + (size_t)al_clampi(X, 0, d.W - 1) * 3;
             sw += w;
-            s0 += al_mul(w, (double)p[0]);
-            s1 += al_mul(w, (double)p[1]);
-            s2 += al_mul(w, (double)p[2]);
+            s0 += mkd_rounded_mul(w, (double)p[0]);
+            s1 += mkd_rounded_mul(w, (double)p[1]);
+            s2 += mkd_rounded_mul(w, (double)p[2]);
         }
     }
     const unsigned char o0 = al_byte(s0 / sw), o1 = al_byte(s1 / sw), o2 = al_byte(s2 / sw);
@@ -126,8 +120,8 @@ __device__ __forceinline__ void pf_axis(double u, double half, double scale, int
     *i0 = al_clampi((int)f, 0, S - 1);
     *i1 = al_clampi((int)f + 1, 0, S - 1);
 }
-__device__ __forceinline__ double pf_lerp(double p, double q, double w) { return p + al_mul(w, q - p); }
-__device__ __forceinline__ double pf_diff(float t, float s) { return al_mul(al_mul((double)t + 1.0, 0.5) - (double)s, 255.0); }
+__device__ __forceinline__ double pf_lerp(double p, double q, double w) { return p + mkd_rounded_mul(w, q - p); }
+__device__ __forceinline__ double pf_diff(float t, float s) { return mkd_rounded_mul(mkd_rounded_mul((double)t + 1.0, 0.5) - (double)s, 255.0); }
 
 template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void paste_frame_kernel(const PfArgs a, int S, const float* __restrict__ t, const float* __restrict__ s01, int rho,
@@ -139,7 +133,7 @@ __global__ __launch_bounds__(256) void paste_frame_kernel(const PfArgs a, int S,
     const int X = a.rx0[b] + jx;                                     // 0 <= X < W: the rectangle is clipped to the photo
     const double scale = d.side / (double)S, half = d.side * 0.5;
     const double rx = ((double)X + 0.5) - d.cx;
-    const double crx = al_mul(d.c, rx), srx = al_mul(d.s, rx);
+    const double crx = mkd_rounded_mul(d.c, rx), srx = mkd_rounded_mul(d.s, rx);
     const double fr = (double)(rho + 1);
     int gx0 = 0, gx1 = 0;
     double ux = 0.0;
@@ -156,7 +150,7 @@ __global__ __launch_bounds__(256) void paste_frame_kernel(const PfArgs a, int S,
     for (int iy = blockIdx.y * PF_TH + (threadIdx.x >> 6); iy < i_end; iy += 256 / PF_TW) {
         const int Y = a.ry0[b] + iy;
         const double ry = ((double)Y + 0.5) - d.cy;
-        const double u = crx + al_mul(d.s, ry), v = al_mul(d.c, ry) - srx;
+        const double u = crx + mkd_rounded_mul(d.s, ry), v = mkd_rounded_mul(d.c, ry) - srx;
         if (!(u >= -half && u < half && v >= -half && v < half)) continue;          // outside the square: the byte is not touched
         int c0, c1, r0, r1;
         double wx, wy;
@@ -171,7 +165,7 @@ __global__ __launch_bounds__(256) void paste_frame_kernel(const PfArgs a, int S,
             const float* q0 = wb + (size_t)gy0 * ww;
             const float* q1 = wb + (size_t)gy1 * ww;
             const double g = pf_lerp(pf_lerp((double)q0[gx0], (double)q0[gx1], ux), pf_lerp((double)q1[gx0], (double)q1[gx1], ux), uy);
-            al = al_mul(al, g);
+            al = mkd_rounded_mul(al, g);
         }
         unsigned char* p = px + (size_t)Y * d.pitch_bytes + (size_t)X * 3;
         const int o00 = r0 * S + c0, o01 = r0 * S + c1, o10 = r1 * S + c0, o11 = r1 * S + c1;
@@ -183,28 +177,22 @@ __global__ __launch_bounds__(256) void paste_frame_kernel(const PfArgs a, int S,
             const double d10 = pf_diff(tc[o10], sc[o10]), d11 = pf_diff(tc[o11], sc[o11]);
             const double top = pf_lerp(d00, d01, wx), bot = pf_lerp(d10, d11, wx);
             const double val = pf_lerp(top, bot, wy);
-            p[c] = al_byte((double)p[c] + al_mul(al, val));
+            p[c] = al_byte((double)p[c] + mkd_rounded_mul(al, val));
         }
     }
 }
 
+static_assert(MKD_PHOTO_MAX_BATCH == 16, "mkd_check_photo_descs (mkd_common.h) states the limit and its text as 16");
 const char* frame_check(const mkd_photo_frame_desc* descs, int n, int S, bool need_labels) {
-    if (!descs || n < 1 || n > MKD_PHOTO_MAX_BATCH) return "1..16 descriptors per call";
-    if (S < 8 || S > 1024) return "S must be 8..1024";
-    for (int i = 0; i < n; ++i) {
-        const mkd_photo_frame_desc& d = descs[i];
-        if (!d.pixels) return "null pixels";
-        if (d.H < 1 || d.W < 1 || d.H > 16384 || d.W > 16384) return "photo H, W must be 1..16384";
-        if ((int64_t)d.pitch_bytes < (int64_t)3 * d.W) return "pitch_bytes must be >= 3 W";
+    return mkd_check_photo_descs(descs, n, S, need_labels, [S](const mkd_photo_frame_desc& d) -> const char* {
         if (!std::isfinite(d.cx) || !std::isfinite(d.cy) || !std::isfinite(d.side) || !std::isfinite(d.c) || !std::isfinite(d.s))
             return "cx, cy, side, c, s must be finite";
         if (!(d.side > 0.0) || d.side > 32.0 * S) return "side must lie in (0, 32 S]";
         if (!(fabs(d.c * d.c + d.s * d.s - 1.0) <= 1e-9)) return "(c, s) must be a unit vector (|c^2 + s^2 - 1| <= 1e-9)";
         if (d.cx < -d.side || d.cx > (double)d.W + d.side || d.cy < -d.side || d.cy > (double)d.H + d.side)
             return "the centre must lie within side of the photo rectangle";
-        if (need_labels && !d.labels) return "labels_out needs a label map in every descriptor";
-    }
-    return nullptr;
+        return nullptr;
+    });
 }
 
 // ---- mkd_face_frames -----------------------------------------------------------------------------------------------------------------
@@ -301,7 +289,7 @@ __global__ __launch_bounds__(FF_NT) void ff_direction_kernel(const mkd_component
                 px = -px;
                 py = -py;
             }
-            const double len = sqrt(al_mul(px, px) + al_mul(py, py));
+            const double len = sqrt(mkd_rounded_mul(px, px) + mkd_rounded_mul(py, py));
             if (len != 0.0) {
                 const int cq = (int)rint(px / len * 16384.0), sq = (int)rint(py / len * 16384.0);
                 if (cq >= FF_UNIT / 2) {

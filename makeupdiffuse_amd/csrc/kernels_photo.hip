@@ -12,7 +12,7 @@
 //
 // Paste: one launch, a thread owns one photo pixel column of a 64 x 16 box tile (4 rows); the model-resolution difference
 // d = ((t + 1) 0.5 - s01) 255 is formed on the fly from the L2-resident tensors.  Every fp32 operation is one correctly rounded step:
-// products that feed an addition pass through an empty asm statement (kernels_region.hip, paste_background_kernel).
+// products that feed an addition pass through mkd_rounded (mkd_common.h).
 // mkd_paste_photo_weighted is the same kernel's second instantiation: the feather weight times a bilinear sample of a photo-wide plane.
 #include "mkd_common.h"
 #include "../../include/mkd.h"
@@ -47,15 +47,6 @@ __host__ __device__ inline void rs_rows(int H, int y0, int bh, int S, int* rbase
     *rows = hi - lo;
 }
 
-__device__ __forceinline__ double rs_opaque(double x) {
-    asm("" : "+v"(x));
-    return x;
-}
-__device__ __forceinline__ float pp_rounded(float x) {
-    asm("" : "+v"(x));
-    return x;
-}
-
 // Bounds and integer coefficients of output index xx of one axis (input length n, box [in0, in0 + len), output S): Pillow's
 // precompute_coeffs with the bilinear filter and normalize_coeffs_8bpc, in double, in its order of operations.  coef[0 .. ksize) gets
 // the coefficients (zero past xmax - xmin); returns xmin, *cnt = xmax - xmin.  The weight is computed twice (sum, then quotient) from
@@ -66,7 +57,7 @@ __device__ int rs_axis_coeffs(int n, int in0, int len, int S, int xx, int ksize,
     const double fs = scale < 1.0 ? 1.0 : scale;
     const double support = fs;
     const double ss = 1.0 / fs;
-    const double center = (double)in0 + rs_opaque(((double)xx + 0.5) * scale);
+    const double center = (double)in0 + mkd_rounded(((double)xx + 0.5) * scale);
     int xmin = (int)(center - support + 0.5);
     if (xmin < 0) xmin = 0;
     int xmax = (int)(center + support + 0.5);
@@ -76,17 +67,17 @@ __device__ int rs_axis_coeffs(int n, int in0, int len, int S, int xx, int ksize,
     if (xmax < 0) xmax = 0;
     double ww = 0.0;
     for (int x = 0; x < xmax; ++x) {
-        double a = rs_opaque(((double)(x + xmin) - center + 0.5) * ss);
+        double a = mkd_rounded(((double)(x + xmin) - center + 0.5) * ss);
         if (a < 0.0) a = -a;
         const double w = a < 1.0 ? 1.0 - a : 0.0;
         ww += w;
     }
     for (int x = 0; x < xmax; ++x) {
-        double a = rs_opaque(((double)(x + xmin) - center + 0.5) * ss);
+        double a = mkd_rounded(((double)(x + xmin) - center + 0.5) * ss);
         if (a < 0.0) a = -a;
         double w = a < 1.0 ? 1.0 - a : 0.0;
         if (ww != 0.0) w = w / ww;
-        coef[x] = (int)(0.5 + rs_opaque(w * 4194304.0));           // no coefficient of this filter is negative
+        coef[x] = (int)(0.5 + mkd_rounded(w * 4194304.0));           // no coefficient of this filter is negative
     }
     for (int x = xmax; x < ksize; ++x) coef[x] = 0;
     *cnt = xmax;
@@ -198,11 +189,11 @@ __device__ __forceinline__ void pp_axis(int j, int len, int S, int* i0, int* i1,
     *i1 = min(max(q + 1, 0), S - 1);
 }
 __device__ __forceinline__ float pp_diff(float t, float s) {
-    const float r = pp_rounded(__fmul_rn(__fadd_rn(t, 1.0f), 0.5f));
-    return pp_rounded(__fmul_rn(__fsub_rn(r, s), 255.0f));
+    const float r = mkd_rounded(__fmul_rn(__fadd_rn(t, 1.0f), 0.5f));
+    return mkd_rounded(__fmul_rn(__fsub_rn(r, s), 255.0f));
 }
 __device__ __forceinline__ float pp_lerp(float a, float b, float w) {
-    return __fadd_rn(a, pp_rounded(__fmul_rn(w, __fsub_rn(b, a))));
+    return __fadd_rn(a, mkd_rounded(__fmul_rn(w, __fsub_rn(b, a))));
 }
 
 // WEIGHTED (mkd_paste_photo_weighted): the feather weight is multiplied by g, the bilinear sample of the photo-wide weight plane
@@ -250,7 +241,7 @@ __global__ __launch_bounds__(256) void paste_photo_kernel(const PpArgs a, int S,
             const float* r0 = wb + (size_t)gy0 * ww;
             const float* r1 = wb + (size_t)gy1 * ww;
             const float g = pp_lerp(pp_lerp(r0[gx0], r0[gx1], ux), pp_lerp(r1[gx0], r1[gx1], ux), uy);
-            al = pp_rounded(__fmul_rn(al, g));
+            al = mkd_rounded(__fmul_rn(al, g));
         }
         unsigned char* p = px + (size_t)(d.y0 + i) * d.pitch_bytes + (size_t)(d.x0 + j) * 3;
         const int o00 = y0i * S + x0i, o01 = y0i * S + x1i, o10 = y1i * S + x0i, o11 = y1i * S + x1i;
@@ -262,27 +253,21 @@ __global__ __launch_bounds__(256) void paste_photo_kernel(const PpArgs a, int S,
             const float d10 = pp_diff(tc[o10], sc[o10]), d11 = pp_diff(tc[o11], sc[o11]);
             const float top = pp_lerp(d00, d01, wx), bot = pp_lerp(d10, d11, wx);
             const float u = pp_lerp(top, bot, wy);
-            const float o = __fadd_rn((float)p[c], pp_rounded(__fmul_rn(al, u)));
+            const float o = __fadd_rn((float)p[c], mkd_rounded(__fmul_rn(al, u)));
             p[c] = (unsigned char)fminf(fmaxf(rintf(o), 0.0f), 255.0f);
         }
     }
 }
 
+static_assert(MKD_PHOTO_MAX_BATCH == 16, "mkd_check_photo_descs (mkd_common.h) states the limit and its text as 16");
 int check_descs(const char* what, const mkd_photo_desc* descs, int n, int S, bool need_labels) {
-    const std::string w(what);
-    if (!descs || n < 1 || n > MKD_PHOTO_MAX_BATCH) return mkd_fail(-1, w + ": 1..16 descriptors per call");
-    if (S < 8 || S > 1024) return mkd_fail(-1, w + ": S must be 8..1024");
-    for (int i = 0; i < n; ++i) {
-        const mkd_photo_desc& d = descs[i];
-        if (!d.pixels) return mkd_fail(-1, w + ": null pixels");
-        if (d.H < 1 || d.W < 1 || d.H > 16384 || d.W > 16384) return mkd_fail(-1, w + ": photo H, W must be 1..16384");
-        if ((int64_t)d.pitch_bytes < (int64_t)3 * d.W) return mkd_fail(-1, w + ": pitch_bytes must be >= 3 W");
+    const char* e = mkd_check_photo_descs(descs, n, S, need_labels, [S](const mkd_photo_desc& d) -> const char* {
         if (d.bw < 1 || d.bh < 1 || d.x0 < 0 || d.y0 < 0 || (int64_t)d.x0 + d.bw > d.W || (int64_t)d.y0 + d.bh > d.H)
-            return mkd_fail(-1, w + ": the box must be non-empty and lie inside the photo");
-        if (d.bw > 32 * S || d.bh > 32 * S) return mkd_fail(-1, w + ": the box must not exceed 32 S per side");
-        if (need_labels && !d.labels) return mkd_fail(-1, w + ": labels_out needs a label map in every descriptor");
-    }
-    return 0;
+            return "the box must be non-empty and lie inside the photo";
+        if (d.bw > 32 * S || d.bh > 32 * S) return "the box must not exceed 32 S per side";
+        return nullptr;
+    });
+    return e ? mkd_fail(MKD_ERR_ARG, std::string(what) + ": " + e) : 0;
 }
 
 size_t slab_bytes(const mkd_photo_desc& d, int S) {

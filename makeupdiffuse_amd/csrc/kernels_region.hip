@@ -134,20 +134,14 @@ constexpr int PB_TH = 16, PB_TW = 64;           // paste tile: rows x columns of
 constexpr int PB_MAX_FEATHER = 16;
 
 // the reference's expression, one rounding per operation: u = (s + 1) / 2, v = (t + 1) / 2, r = a u + (1 - a) v, o = clamp(r 2 - 1)
-// (x / 2 and x * 0.5 are the same real number, so the same fp32).  The __f*_rn forms are plain operators in HIP's headers and
-// -ffp-contract=fast lets the backend fuse them all the same (p + q became fma(a, u, q)), so every product that feeds an addition
-// goes through an empty asm statement first: no instruction, but the value is opaque and cannot be folded into an fma
-__device__ __forceinline__ float pb_rounded(float x) {
-    asm("" : "+v"(x));
-    return x;
-}
+// (x / 2 and x * 0.5 are the same real number, so the same fp32); every product that feeds an addition is a mkd_rounded (mkd_common.h)
 __device__ __forceinline__ float pb_paste(float a, float s, float t) {
     const float u = __fmul_rn(__fadd_rn(s, 1.0f), 0.5f);
     const float v = __fmul_rn(__fadd_rn(t, 1.0f), 0.5f);
-    const float p = pb_rounded(__fmul_rn(a, u));
-    const float q = pb_rounded(__fmul_rn(__fsub_rn(1.0f, a), v));
+    const float p = mkd_rounded(__fmul_rn(a, u));
+    const float q = mkd_rounded(__fmul_rn(__fsub_rn(1.0f, a), v));
     const float r = __fadd_rn(p, q);
-    const float o = __fsub_rn(pb_rounded(__fmul_rn(r, 2.0f)), 1.0f);
+    const float o = __fsub_rn(mkd_rounded(__fmul_rn(r, 2.0f)), 1.0f);
     return fminf(fmaxf(o, -1.0f), 1.0f);
 }
 

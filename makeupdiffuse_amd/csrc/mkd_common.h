@@ -62,7 +62,38 @@ __device__ __forceinline__ float gelu_erf_f(float x) {
 
 struct __attribute__((aligned(16))) U16x8 { uint16_t v[8]; };
 struct __attribute__((aligned(8)))  U16x4 { uint16_t v[4]; };
+
+// One correctly rounded product.  The __f*_rn forms are plain operators in HIP's headers and -ffp-contract=fast lets the backend fuse
+// them all the same (p + q became fma(a, u, q)), so every product that feeds an addition goes through an empty asm statement first: no
+// instruction, but the value is opaque and cannot become half of a fused multiply-add.
+__device__ __forceinline__ float mkd_rounded(float x) {
+    asm("" : "+v"(x));
+    return x;
+}
+__device__ __forceinline__ double mkd_rounded(double x) {
+    asm("" : "+v"(x));
+    return x;
+}
+__device__ __forceinline__ double mkd_rounded_mul(double a, double b) { return mkd_rounded(a * b); }
 #endif
+
+// The checks every photo call makes on its HOST descriptor array (mkd_photo_desc or mkd_photo_frame_desc of include/mkd.h) -> the text
+// of the first one that fails, else null: n and S, then per descriptor the photo fields, region(d) (the box's or the frame's own
+// checks) and the label map that labels_out needs.
+template <typename Desc, typename Region>
+const char* mkd_check_photo_descs(const Desc* descs, int n, int S, bool need_labels, Region region) {
+    if (!descs || n < 1 || n > 16) return "1..16 descriptors per call";          // MKD_PHOTO_MAX_BATCH
+    if (S < 8 || S > 1024) return "S must be 8..1024";
+    for (int i = 0; i < n; ++i) {
+        const Desc& d = descs[i];
+        if (!d.pixels) return "null pixels";
+        if (d.H < 1 || d.W < 1 || d.H > 16384 || d.W > 16384) return "photo H, W must be 1..16384";
+        if ((int64_t)d.pitch_bytes < (int64_t)3 * d.W) return "pitch_bytes must be >= 3 W";
+        if (const char* e = region(d)) return e;
+        if (need_labels && !d.labels) return "labels_out needs a label map in every descriptor";
+    }
+    return nullptr;
+}
 
 // ---------------------------------------------------------------------------------------------
 // kernel launch parameter blocks (host + device)

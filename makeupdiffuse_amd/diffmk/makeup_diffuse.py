@@ -806,14 +806,14 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                                                                            feather=self.paste_feather, return_alpha=True)
         return out
 
-    def _photo_pass(self, src_photos, ref_photos, src_boxes, ref_boxes, src_segs, x_T, size, batch, phi, align=False):
-        """the single pass of transfer_photos for one batch of (photo, box) pairs on the device: crop-resize both, sample, decode,
-        paste_source -> (the decoded images [n,3,size,size], the source crops img01 the paste needs).  ``align``: the boxes may be
-        photo.Frame's (photo.crop_regions: a batch without a rolled frame is the same crop_resize call)"""
+    def _photo_pass(self, src_photos, ref_photos, src_regions, ref_regions, src_segs, x_T, size, batch, phi):
+        """the single pass of transfer_photos for one batch of (photo, region) pairs on the device: crop-resize both, sample, decode,
+        paste_source -> (the decoded images [n,3,size,size], the source crops img01 the paste needs).  A region is a box or a
+        photo.Frame (photo.crop_regions: a batch without a rolled frame is one crop_resize call)"""
         eng = self._require_engine()
         need_seg = self.fix_background or self.paste_background
-        cs = (eng.crop_regions if align else eng.crop_resize)(src_photos, src_boxes, size, labels=src_segs)
-        cr = (eng.crop_regions if align else eng.crop_resize)(ref_photos, ref_boxes, size)
+        cs = eng.crop_regions(src_photos, src_regions, size, labels=src_segs)
+        cr = eng.crop_regions(ref_photos, ref_regions, size)
         n = len(src_photos)
         if cr.img01.shape[0] != n:
             raise ValueError(f'{n} source photos but {cr.img01.shape[0]} reference photos')
@@ -836,108 +836,6 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         if self.paste_background:
             img, _ = self.paste_source(seg_batch, img, src * 2.0 - 1.0)
         return img, src
-
-    def _transfer_faces(self, src_photos, ref_photos, src_boxes, ref_boxes, src_segs, feather, x_T, size, batch, phi, max_faces,
-                        face_batch, return_faces, own_pixels=False, own_feather=2, align=False, min_roll=5.0):
-        """transfer_photos(max_faces=K): see there"""
-        from .. import photo
-        K, fb = int(max_faces), int(face_batch)
-        if align and not float(min_roll) >= 0.0:
-            raise ValueError(f'min_roll must be >= 0 degrees, got {min_roll!r}')
-        if own_pixels and (src_boxes is not None or self.face_parser is None):
-            raise ValueError('own_pixels needs the faces from the attached face parser (src_boxes None): a box has no component to own pixels')
-        if own_pixels and (int(own_feather) != own_feather or not 0 <= int(own_feather) <= 16):
-            raise ValueError(f'own_feather must be an integer 0..16 parse pixels, got {own_feather!r}')
-        if K != max_faces or not 1 <= K <= 64:
-            raise ValueError(f'max_faces must be an integer 1..64, got {max_faces!r}')
-        if fb != face_batch or fb < 1:
-            raise ValueError(f'face_batch must be an integer >= 1, got {face_batch!r}')
-        src_photos, ref_photos = list(src_photos), list(ref_photos)
-        n = len(src_photos)
-        if len(ref_photos) != n:
-            raise ValueError(f'{n} source photos but {len(ref_photos)} reference photos')
-        if (src_boxes is None or ref_boxes is None) and self.face_parser is None:
-            raise ValueError('transfer_photos: src_boxes and ref_boxes are needed (only an attached face parser can find the faces)')
-        # align: a box may carry the face's roll in degrees as a fifth entry
-        is_box = lambda b: isinstance(b, (tuple, list)) and len(b) in ((4, 5) if align else (4,)) and not any(isinstance(v, (tuple, list)) for v in b)
-        # (x0, y0, w, h[, angle]) -> the box itself when it is upright, else its Frame
-        region = lambda b: b if isinstance(b, photo.Frame) else (tuple(int(v) for v in b[:4]) if len(b) == 4 or float(b[4]) == 0.0
-                                                                    else photo.frame_from_box(b[:4], float(b[4])))
-        if src_boxes is not None:
-            src_boxes = list(src_boxes)
-            if len(src_boxes) != n:
-                raise ValueError(f'max_faces: src_boxes must hold one LIST of boxes per source photo ({n}), got {len(src_boxes)} entries')
-            for i, bl in enumerate(src_boxes):
-                if not isinstance(bl, (tuple, list)) or not all(is_box(b) for b in bl):
-                    raise ValueError(f'max_faces: src_boxes[{i}] must be a list of boxes (x0, y0, w, h), got {bl!r}')
-                if len(bl) > K:
-                    raise ValueError(f'max_faces: src_boxes[{i}] holds {len(bl)} boxes, more than max_faces = {K}')
-        if ref_boxes is not None:
-            ref_boxes = list(ref_boxes)
-            if len(ref_boxes) != n or not all(is_box(b) for b in ref_boxes):
-                raise ValueError(f'max_faces: ref_boxes must hold one box (x0, y0, w, h) per reference photo ({n}), got {ref_boxes!r}')
-        known = None if src_boxes is None else sum(len(bl) for bl in src_boxes)
-        if x_T is not None and known is not None and int(x_T.shape[0]) != known:
-            raise ValueError(f'x_T must hold one start latent per face, [{known},4,h,w] in photo-major order, got {tuple(x_T.shape)}')
-        if src_segs is not None and len(src_segs) != n:
-            raise ValueError(f'{n} source photos but {len(src_segs)} label maps')
-        if not self.has_first_stage:
-            raise ValueError('transfer_photos pastes decoded images: it needs a first stage (first_stage_config)')
-        if (self.fix_background or self.paste_background) and src_segs is None and self.face_parser is None:
-            raise KeyError('transfer_photos: fix_background / paste_background need src_segs (label maps at photo resolution)')
-        from ..components import owner_weights
-        from ..face_parser import find_faces
-        eng = self._require_engine()
-        src_photos = [p.to(self.device) for p in src_photos]
-        ref_photos = [p.to(self.device) for p in ref_photos]
-        owner = None
-        how = dict(oriented=True, min_roll=float(min_roll)) if align else {}          # align: find_faces returns Frames
-        if own_pixels:
-            src_boxes, owner = find_faces(self.face_parser, src_photos, max_faces=K, parse_size=self.parse_size, lut=self.parser_lut,
-                                          return_owner=True, **how)
-            faces = [list(bl) for bl in src_boxes] if align else [[tuple(int(v) for v in b) for b in bl] for bl in src_boxes]
-        elif src_boxes is None:
-            src_boxes = find_faces(self.face_parser, src_photos, max_faces=K, parse_size=self.parse_size, lut=self.parser_lut, **how)
-            faces = [list(bl) for bl in src_boxes] if align else [[tuple(int(v) for v in b) for b in bl] for bl in src_boxes]
-        else:
-            faces = [[region(b) for b in bl] for bl in src_boxes] if align else [[tuple(int(v) for v in b) for b in bl] for bl in src_boxes]
-        if ref_boxes is None:
-            found = find_faces(self.face_parser, ref_photos, max_faces=1, parse_size=self.parse_size, lut=self.parser_lut, **how)
-            for i, f in enumerate(found):
-                if not f:
-                    raise ValueError(f'transfer_photos: reference photo {i} shows no face')
-            ref_boxes = [f[0] for f in found]
-        elif align:
-            ref_boxes = [region(b) for b in ref_boxes]
-        items = [(i, k) for i, bl in enumerate(faces) for k in range(len(bl))]          # photo-major, rank-minor
-        N = len(items)
-        if x_T is not None and int(x_T.shape[0]) != N:
-            raise ValueError(f'x_T must hold one start latent per face, [{N},4,h,w] in photo-major order, got {tuple(x_T.shape)}')
-        out = [p.clone(memory_format=torch.contiguous_format) for p in src_photos]
-        imgs, srcs = [], []
-        for c0 in range(0, N, fb):
-            chunk = items[c0:c0 + fb]
-            pick = [i for i, _ in chunk]
-            text = None
-            if batch is not None:          # the text fields get_input reads, one row per face
-                idx = torch.tensor(pick)
-                text = {k: (v[idx.to(v.device)] if isinstance(v, torch.Tensor) else [v[i] for i in pick])
-                        for k, v in batch.items() if k in ('txt_emb', 'txt_tokens', self.cond_stage_key)}
-            img, src = self._photo_pass([src_photos[i] for i in pick], [ref_photos[i] for i in pick], [faces[i][k] for i, k in chunk],
-                                        [ref_boxes[i] for i in pick], None if src_segs is None else [src_segs[i] for i in pick],
-                                        None if x_T is None else x_T[c0:c0 + len(chunk)], size, text, phi, align)
-            imgs.append(img)
-            srcs.append(src)
-        if N:
-            img, src = torch.cat(imgs), torch.cat(srcs)
-            for rank in range(max(len(bl) for bl in faces)):
-                sel = [j for j, (_, k) in enumerate(items) if k == rank]
-                at = torch.tensor(sel, device=img.device)
-                # own_pixels: rank k of photo i is row k of its table, the weight that row's share of every neighbourhood
-                weights = None if owner is None else owner_weights(owner, [(items[j][0], rank) for j in sel], own_feather)
-                (eng.paste_regions if align else eng.paste_photos)([out[items[j][0]] for j in sel], [faces[items[j][0]][rank] for j in sel],
-                                                                   img[at], src[at], feather, weights)
-        return (out, faces) if return_faces else out
 
     @torch.no_grad()
     def transfer_photos(self, src_photos, ref_photos, src_boxes=None, ref_boxes=None, src_segs=None, feather: int = 8,
@@ -989,37 +887,142 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         An upright face takes the crop_resize / paste_photos calls above, so a batch without a rolled face is the path above call for
         call.  ``return_faces`` then gives boxes for caller boxes that are upright and photo.Frame's for everything else."""
         from .. import photo
+        from ..components import owner_weights
+        from ..face_parser import find_boxes, find_faces
         phi = float(self.guidance_rescale if guidance_rescale is None else guidance_rescale)
         if not 0.0 <= phi <= 1.0:
             raise ValueError(f'guidance_rescale must lie in [0, 1], got {phi}')
-        if max_faces is not None:
-            return self._transfer_faces(src_photos, ref_photos, src_boxes, ref_boxes, src_segs, feather, x_T, size, batch, phi,
-                                        max_faces, face_batch, return_faces, own_pixels, own_feather, align, min_roll)
-        if own_pixels:
+        # One body for both forms, on regions (boxes or photo.Frame's): the call without max_faces is one face per photo and one chunk
+        # of all photos.  Every check comes before the engine is required.
+        many = max_faces is not None
+        if many:
+            K, fb = int(max_faces), int(face_batch)
+            if align and not float(min_roll) >= 0.0:
+                raise ValueError(f'min_roll must be >= 0 degrees, got {min_roll!r}')
+            if own_pixels and (src_boxes is not None or self.face_parser is None):
+                raise ValueError('own_pixels needs the faces from the attached face parser (src_boxes None): a box has no component to own pixels')
+            if own_pixels and (int(own_feather) != own_feather or not 0 <= int(own_feather) <= 16):
+                raise ValueError(f'own_feather must be an integer 0..16 parse pixels, got {own_feather!r}')
+            if K != max_faces or not 1 <= K <= 64:
+                raise ValueError(f'max_faces must be an integer 1..64, got {max_faces!r}')
+            if fb != face_batch or fb < 1:
+                raise ValueError(f'face_batch must be an integer >= 1, got {face_batch!r}')
+        elif own_pixels:
             raise ValueError('own_pixels only applies with max_faces')
-        if align:
+        elif align:
             raise ValueError('align only applies with max_faces')
-        if return_faces or face_batch != 8:
+        elif return_faces or face_batch != 8:
             raise ValueError('return_faces / face_batch only apply with max_faces')
+        src_photos, ref_photos = list(src_photos), list(ref_photos)
+        n = len(src_photos)
+        if len(ref_photos) != n:
+            raise ValueError(f'{n} source photos but {len(ref_photos)} reference photos')
         if (src_boxes is None or ref_boxes is None) and self.face_parser is None:
-            raise ValueError('transfer_photos: src_boxes and ref_boxes are needed (only an attached face parser can find them)')
+            raise ValueError('transfer_photos: src_boxes and ref_boxes are needed (only an attached face parser can find the faces)')
+
+        def region(b):          # (x0, y0, w, h[, angle]) or a Frame -> the box itself when it is upright, else its Frame
+            if isinstance(b, photo.Frame):
+                return b
+            if len(b) == 4 or float(b[4]) == 0.0:
+                return tuple(int(v) for v in b[:4])
+            return photo.frame_from_box(b[:4], float(b[4]))
+
+        def work_items(faces):          # photo-major, rank-minor; with max_faces x_T holds one start latent per item
+            items = [(i, k) for i, fl in enumerate(faces) for k in range(len(fl))]
+            if many and x_T is not None and int(x_T.shape[0]) != len(items):
+                raise ValueError(f'x_T must hold one start latent per face, [{len(items)},4,h,w] in photo-major order, got {tuple(x_T.shape)}')
+            return items
+
+        # faces: a list of regions per source photo; refs: one region per reference.  None: the parser finds them on the device
+        if not many:          # one face per photo, its box as the caller gave it: one 4-entry box per photo (photo.check_box sees to the rest)
+            for boxes in (src_boxes, ref_boxes):
+                if boxes is not None and len(boxes) != n:
+                    raise ValueError(f'{n} photos but {len(boxes)} boxes')
+                for b in () if boxes is None else boxes:
+                    if len(b) != 4:
+                        raise ValueError(f'a box is (x0, y0, w, h), got {b!r}')
+            faces = None if src_boxes is None else [[b] for b in src_boxes]
+            refs = None if ref_boxes is None else list(ref_boxes)
+        else:
+            # align: a box may carry the face's roll in degrees as a fifth entry
+            is_box = lambda b: isinstance(b, (tuple, list)) and (len(b) == 4 or (align and len(b) == 5)) and not any(isinstance(v, (tuple, list)) for v in b)
+            if src_boxes is not None:
+                src_boxes = list(src_boxes)
+                if len(src_boxes) != n:
+                    raise ValueError(f'max_faces: src_boxes must hold one LIST of boxes per source photo ({n}), got {len(src_boxes)} entries')
+                for i, bl in enumerate(src_boxes):
+                    if not isinstance(bl, (tuple, list)) or not all(is_box(b) for b in bl):
+                        raise ValueError(f'max_faces: src_boxes[{i}] must be a list of boxes (x0, y0, w, h), got {bl!r}')
+                    if len(bl) > K:
+                        raise ValueError(f'max_faces: src_boxes[{i}] holds {len(bl)} boxes, more than max_faces = {K}')
+            if ref_boxes is not None:
+                ref_boxes = list(ref_boxes)
+                if len(ref_boxes) != n or not all(is_box(b) for b in ref_boxes):
+                    raise ValueError(f'max_faces: ref_boxes must hold one box (x0, y0, w, h) per reference photo ({n}), got {ref_boxes!r}')
+            faces = None if src_boxes is None else [[region(b) for b in bl] for bl in src_boxes]
+            refs = None if ref_boxes is None else [region(b) for b in ref_boxes]
+        items = None if faces is None else work_items(faces)
+        if src_segs is not None and len(src_segs) != n:
+            raise ValueError(f'{n} source photos but {len(src_segs)} label maps')
         if not self.has_first_stage:
             raise ValueError('transfer_photos pastes decoded images: it needs a first stage (first_stage_config)')
-        need_seg = self.fix_background or self.paste_background
-        if need_seg and src_segs is None and self.face_parser is None:
+        if (self.fix_background or self.paste_background) and src_segs is None and self.face_parser is None:
             raise KeyError('transfer_photos: fix_background / paste_background need src_segs (label maps at photo resolution)')
         eng = self._require_engine()
         src_photos = [p.to(self.device) for p in src_photos]
-        if src_boxes is None or ref_boxes is None:
-            from ..face_parser import find_boxes
-            if src_boxes is None:
-                src_boxes = find_boxes(self.face_parser, src_photos, parse_size=self.parse_size, lut=self.parser_lut)
-            if ref_boxes is None:
-                ref_boxes = find_boxes(self.face_parser, [p.to(self.device) for p in ref_photos], parse_size=self.parse_size, lut=self.parser_lut)
-        img, src = self._photo_pass(src_photos, ref_photos, src_boxes, ref_boxes, src_segs, x_T, size, batch, phi)
+        ref_photos = [p.to(self.device) for p in ref_photos]
+        look = dict(parse_size=self.parse_size, lut=self.parser_lut)
+        if align:          # find_faces returns Frames
+            look.update(oriented=True, min_roll=float(min_roll))
+        owner = None
+        if faces is None:
+            if not many:
+                faces = [[b] for b in find_boxes(self.face_parser, src_photos, **look)]
+            elif own_pixels:
+                found, owner = find_faces(self.face_parser, src_photos, max_faces=K, return_owner=True, **look)
+                faces = [[region(b) for b in fl] for fl in found]
+            else:
+                faces = [[region(b) for b in fl] for fl in find_faces(self.face_parser, src_photos, max_faces=K, **look)]
+            items = work_items(faces)
+        if refs is None:
+            if not many:
+                refs = find_boxes(self.face_parser, ref_photos, **look)
+            else:
+                found = find_faces(self.face_parser, ref_photos, max_faces=1, **look)
+                for i, fl in enumerate(found):
+                    if not fl:
+                        raise ValueError(f'transfer_photos: reference photo {i} shows no face')
+                refs = [fl[0] for fl in found]
+        N = len(items)
         out = [p.clone(memory_format=torch.contiguous_format) for p in src_photos]
-        eng.paste_photos(out, src_boxes, img, src, feather)
-        return out
+        imgs, srcs = [], []
+        # without max_faces: ONE chunk of all photos with x_T and batch as they came (an empty call reaches the crop, which refuses it)
+        for c0 in range(0, N, fb) if many else (0,):
+            chunk = items[c0:c0 + fb] if many else items
+            pick = [i for i, _ in chunk]
+            text, start = batch, x_T
+            if many and batch is not None:          # the text fields get_input reads, one row per face
+                idx = torch.tensor(pick)
+                text = {k: (v[idx.to(v.device)] if isinstance(v, torch.Tensor) else [v[i] for i in pick])
+                        for k, v in batch.items() if k in ('txt_emb', 'txt_tokens', self.cond_stage_key)}
+            if many and x_T is not None:
+                start = x_T[c0:c0 + len(chunk)]
+            img, src = self._photo_pass([src_photos[i] for i in pick], [ref_photos[i] for i in pick], [faces[i][k] for i, k in chunk],
+                                        [refs[i] for i in pick], None if src_segs is None else [src_segs[i] for i in pick], start, size, text, phi)
+            imgs.append(img)
+            srcs.append(src)
+        if N:
+            img, src = (torch.cat(imgs), torch.cat(srcs)) if many else (imgs[0], srcs[0])
+            for rank in range(max(len(fl) for fl in faces)):
+                sel = [j for j, (_, k) in enumerate(items) if k == rank]
+                rows = (img, src)          # without max_faces every item is rank 0: the pass's tensors as they are
+                if many:
+                    at = torch.tensor(sel, device=img.device)
+                    rows = (img[at], src[at])
+                # own_pixels: rank k of photo i is row k of its table, the weight that row's share of every neighbourhood
+                weights = None if owner is None else owner_weights(owner, [(items[j][0], rank) for j in sel], own_feather)
+                eng.paste_regions([out[items[j][0]] for j in sel], [faces[items[j][0]][rank] for j in sel], *rows, feather, weights)
+        return (out, faces) if return_faces else out
 
     def test_step(self, batch: dict, batch_idx: int, x_T: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """reference diffusion_makeup.py:332-341.  x_T (not in the reference, which always draws fresh noise): fixed start

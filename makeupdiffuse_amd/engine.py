@@ -1008,16 +1008,17 @@ class MkdEngine:
                                                      C.c_void_p(_ptr(alpha)), B, Cn, H, W, C.c_void_p(_stream())), 'mkd_paste_background')
         return (out, alpha) if return_alpha else out
 
+    def _to_dev(self, ts, rank: int):
+        """one tensor, a stacked batch or a list (photo.as_list) -> a list on this engine's device; None stays None"""
+        from . import photo
+        return None if ts is None else [t.to(self.device) for t in photo.as_list(ts, rank)]
+
     def crop_resize(self, photos, boxes, size: int, labels=None, want_u8: bool = False):
         """Full-resolution photos in (include/mkd.h mkd_crop_resize; photo.crop_resize on this engine's device): uint8 [H,W,3]
         photos and their boxes (x0, y0, w, h) -> Cropped(img01 [B,3,S,S], labels [B,S,S] or None, u8 [B,S,S,3] or None), the bytes
         of Pillow's antialiased bilinear resize of each box."""
         from . import photo
-        def to_dev(ts, single_dim):          # one tensor, a stacked batch or a list -> a list on this engine's device
-            if isinstance(ts, torch.Tensor):
-                ts = [ts] if ts.dim() == single_dim else ts.unbind(0)
-            return [t.to(self.device) for t in ts]
-        return photo.crop_resize(to_dev(photos, 3), boxes, size, labels=None if labels is None else to_dev(labels, 2), want_u8=want_u8)
+        return photo.crop_resize(self._to_dev(photos, 3), boxes, size, labels=self._to_dev(labels, 2), want_u8=want_u8)
 
     def paste_photos(self, photos, boxes, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None):
         """Full-resolution photos out (include/mkd.h mkd_paste_photo; photo.paste_photos): the decoded samples pasted into the
@@ -1030,8 +1031,7 @@ class MkdEngine:
         """crop_resize for a batch whose regions may be photo.Frame's (photo.crop_regions on this engine's device): a rolled frame is
         cropped along itself (include/mkd.h mkd_crop_frame), a batch without one is the crop_resize call above"""
         from . import photo
-        dev = lambda ts: None if ts is None else [t.to(self.device) for t in ts]
-        return photo.crop_regions(dev(photos), regions, size, labels=dev(labels))
+        return photo.crop_regions(self._to_dev(photos, 3), regions, size, labels=self._to_dev(labels, 2))
 
     def paste_regions(self, photos, regions, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None):
         """paste_photos for a batch whose regions may be photo.Frame's (photo.paste_regions; include/mkd.h mkd_paste_frame)"""

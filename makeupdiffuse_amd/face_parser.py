@@ -226,6 +226,18 @@ def device_label_box(labels: torch.Tensor, classes: Sequence[int] = FACE_CLASSES
     return tuple(int(v) for v in box[0].tolist())
 
 
+def _squash_parse(parser, chunk, S: int, lut, resize) -> torch.Tensor:
+    """whole photos squashed to S x S (``resize``: photo.crop_resize of the whole photo) and parsed -> their label maps [n,S,S]"""
+    whole = [(0, 0, int(p.shape[1]), int(p.shape[0])) for p in chunk]
+    return parser.parse(resize(chunk, whole, S).img01, out_size=None, lut=lut)
+
+
+def _scale_box(box, S: int, H: int, W: int) -> Tuple[int, int, int, int]:
+    """(row min, row max, col min, col max), inclusive, on the S x S squashed map of an H x W photo -> photo pixels, outwards"""
+    r0, r1, c0, c1 = box
+    return r0 * H // S, min(H, -(-(r1 + 1) * H // S)) - 1, c0 * W // S, min(W, -(-(c1 + 1) * W // S)) - 1
+
+
 def find_boxes(parser, photos, grow: float = 1.0, parse_size: int = 512, lut=LUT_SEG, classes: Sequence[int] = FACE_CLASSES,
                resize=None, box_of=None) -> List[Tuple[int, int, int, int]]:
     """Face boxes (x0, y0, side, side) for whole photos (uint8 [H,W,3] device tensors): every photo is squashed to parse_size x
@@ -236,24 +248,20 @@ def find_boxes(parser, photos, grow: float = 1.0, parse_size: int = 512, lut=LUT
     its index.  This rule is this build's.  ``parser`` is anything with ``parse(img01, out_size=None, lut=...)``; ``resize`` and
     ``box_of`` replace the two device calls (tests of the box arithmetic without a device)."""
     from . import photo
-    if isinstance(photos, torch.Tensor):
-        photos = [photos] if photos.dim() == 3 else list(photos.unbind(0))
-    photos = list(photos)
+    photos = photo.as_list(photos, 3)
     resize = resize or photo.crop_resize
     box_of = box_of or device_label_box
     S = int(parse_size)
     out = []
     for b0 in range(0, len(photos), MAX_BATCH):
         chunk = photos[b0:b0 + MAX_BATCH]
-        whole = [(0, 0, int(p.shape[1]), int(p.shape[0])) for p in chunk]
-        labels = parser.parse(resize(chunk, whole, S).img01, out_size=None, lut=lut)
+        labels = _squash_parse(parser, chunk, S, lut, resize)
         for i, (p, l) in enumerate(zip(chunk, labels)):
             H, W = int(p.shape[0]), int(p.shape[1])
-            r0, r1, c0, c1 = box_of(l, classes)
-            if r1 < r0 or c1 < c0:
+            box = box_of(l, classes)
+            if box[1] < box[0] or box[3] < box[2]:
                 raise ValueError(f'find_boxes: photo {b0 + i} has no pixel of the face classes {tuple(classes)}')
-            scaled = (r0 * H // S, min(H, -(-(r1 + 1) * H // S)) - 1, c0 * W // S, min(W, -(-(c1 + 1) * W // S)) - 1)
-            out.append(photo.grow_square_box(scaled, H, W, grow))
+            out.append(photo.grow_square_box(_scale_box(box, S, H, W), H, W, grow))
     return out
 
 
@@ -287,9 +295,7 @@ def find_faces(parser, photos, max_faces: int = 8, min_area: Optional[int] = Non
     K = int(max_faces)
     if K != max_faces or not 1 <= K <= components.MAX_OUT:
         raise ValueError(f'max_faces must be an integer 1..{components.MAX_OUT}, got {max_faces!r}')
-    if isinstance(photos, torch.Tensor):
-        photos = [photos] if photos.dim() == 3 else list(photos.unbind(0))
-    photos = list(photos)
+    photos = photo.as_list(photos, 3)
     resize = resize or photo.crop_resize
     components_of = components_of or components.label_components
     S = int(parse_size)
@@ -306,8 +312,7 @@ def find_faces(parser, photos, max_faces: int = 8, min_area: Optional[int] = Non
     owners = []
     for b0 in range(0, len(photos), MAX_BATCH):
         chunk = photos[b0:b0 + MAX_BATCH]
-        whole = [(0, 0, int(p.shape[1]), int(p.shape[0])) for p in chunk]
-        labels = parser.parse(resize(chunk, whole, S).img01, out_size=None, lut=lut)
+        labels = _squash_parse(parser, chunk, S, lut, resize)
         if return_owner:
             table, count, ids = components_of(labels, classes, min_area=area, max_out=components.MAX_OUT, want_ids=True)
             owners.append(torch.as_tensor(owner_of(ids, table)))
@@ -326,9 +331,7 @@ def find_faces(parser, photos, max_faces: int = 8, min_area: Optional[int] = Non
             H, W = int(p.shape[0]), int(p.shape[1])
             faces = []
             for k in range(min(int(row[6 * rows]), K)):
-                r0, r1, c0, c1 = row[6 * k + 2:6 * k + 6]
-                scaled = (r0 * H // S, min(H, -(-(r1 + 1) * H // S)) - 1, c0 * W // S, min(W, -(-(c1 + 1) * W // S)) - 1)
-                box = photo.grow_square_box(scaled, H, W, grow)
+                box = photo.grow_square_box(_scale_box(row[6 * k + 2:6 * k + 6], S, H, W), H, W, grow)
                 if oriented:
                     frow = row[6 * rows + 1 + 8 * k:6 * rows + 9 + 8 * k]
                     rolled = abs(photo.frame_roll(frow)) >= float(min_roll) and (frow[2], frow[3]) != (components.FRAME_UNIT, 0)

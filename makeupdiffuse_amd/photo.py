@@ -65,10 +65,15 @@ def _check_size(size: int) -> int:
     return int(size)
 
 
+def as_list(ts, rank: int) -> list:
+    """one tensor of ``rank`` dimensions, a stacked batch of such tensors (``rank`` + 1 dimensions) or a sequence of them -> a list"""
+    if isinstance(ts, torch.Tensor):
+        return [ts] if ts.dim() == rank else list(ts.unbind(0))
+    return list(ts)
+
+
 def _photo_list(photos, what: str) -> List[torch.Tensor]:
-    if isinstance(photos, torch.Tensor):
-        photos = [photos] if photos.dim() == 3 else list(photos.unbind(0))
-    photos = list(photos)
+    photos = as_list(photos, 3)
     if not photos:
         raise ValueError(f'{what}: no photos')
     for p in photos:
@@ -82,113 +87,6 @@ def _photo_list(photos, what: str) -> List[torch.Tensor]:
 def _rows_ok(p: torch.Tensor) -> bool:
     """interleaved RGB rows a fixed number of bytes apart: what a descriptor can address as it is"""
     return p.stride(2) == 1 and p.stride(1) == 3 and (p.shape[0] == 1 or p.stride(0) >= 3 * p.shape[1])
-
-
-def _descs(photos: Sequence[torch.Tensor], boxes, labels: Optional[Sequence[torch.Tensor]]):
-    arr = (_lib.PhotoDescC * len(photos))()
-    for i, (p, (x0, y0, bw, bh)) in enumerate(zip(photos, boxes)):
-        H, W = int(p.shape[0]), int(p.shape[1])
-        arr[i].pixels = p.data_ptr()
-        arr[i].pitch_bytes = int(p.stride(0)) if H > 1 else 3 * W
-        arr[i].H, arr[i].W = H, W
-        arr[i].x0, arr[i].y0, arr[i].bw, arr[i].bh = x0, y0, bw, bh
-        arr[i].labels = None if labels is None else labels[i].data_ptr()
-    return arr
-
-
-def crop_resize(photos, boxes, size: int, labels=None, want_u8: bool = False) -> Cropped:
-    """photos (a list of uint8 [H,W,3] device tensors, or one [B,H,W,3] tensor) and their boxes (x0, y0, w, h) ->
-    Cropped(img01 fp32 [B,3,S,S] = float(u8) / 255 of Pillow's antialiased bilinear resize of the box to S x S (the values
-    PairFolderDataset._load gives for that crop), labels uint8 [B,S,S] or None, u8 uint8 [B,S,S,3] or None).  ``labels``: one uint8
-    [H,W] label map per photo at the photo's resolution, sampled at the output pixel centres without interpolation."""
-    S = _check_size(size)
-    photos = _photo_list(photos, 'crop_resize')
-    B = len(photos)
-    if len(boxes) != B:
-        raise ValueError(f'{B} photos but {len(boxes)} boxes')
-    boxes = [check_box(b, int(p.shape[0]), int(p.shape[1]), S) for p, b in zip(photos, boxes)]
-    dev = photos[0].device
-    photos = [p if _rows_ok(p) else p.contiguous() for p in photos]
-    if labels is not None:
-        if isinstance(labels, torch.Tensor):
-            labels = [labels] if labels.dim() == 2 else list(labels.unbind(0))
-        labels = list(labels)
-        if len(labels) != B:
-            raise ValueError(f'{B} photos but {len(labels)} label maps')
-        lab = []
-        for p, l in zip(photos, labels):
-            if not isinstance(l, torch.Tensor) or l.dtype != torch.uint8 or tuple(l.shape) != tuple(p.shape[:2]):
-                raise ValueError(f'a label map is a uint8 [H,W] tensor of its photo\'s size {tuple(p.shape[:2])}, '
-                                 f'got {getattr(l, "dtype", type(l))} {tuple(getattr(l, "shape", ()))}')
-            lab.append(l.to(dev).contiguous())
-        labels = lab
-    lib = _lib.load()
-    img01 = torch.empty((B, 3, S, S), device=dev, dtype=torch.float32)
-    lab_out = torch.empty((B, S, S), device=dev, dtype=torch.uint8) if labels is not None else None
-    u8 = torch.empty((B, S, S, 3), device=dev, dtype=torch.uint8) if want_u8 else None
-    P = lambda t: C.c_void_p(None if t is None else t.data_ptr())
-    with torch.cuda.device(dev):
-        for b0 in range(0, B, MAX_BATCH):
-            b1 = min(B, b0 + MAX_BATCH)
-            arr = _descs(photos[b0:b1], boxes[b0:b1], None if labels is None else labels[b0:b1])
-            nbytes = int(lib.mkd_crop_resize_scratch_bytes(arr, b1 - b0, S))
-            if nbytes <= 0:
-                raise _lib.MkdError('mkd_crop_resize_scratch_bytes refused the descriptors')
-            scratch = torch.empty((nbytes + 256,), device=dev, dtype=torch.uint8)       # (the stream keeps it alive until the kernels ran)
-            base = (scratch.data_ptr() + 255) & ~255
-            _lib.check(lib.mkd_crop_resize(arr, b1 - b0, S, P(img01[b0:b1]), P(None if u8 is None else u8[b0:b1]),
-                                           P(None if lab_out is None else lab_out[b0:b1]), C.c_void_p(base), C.c_void_p(_stream())),
-                       'mkd_crop_resize')
-    return Cropped(img01, lab_out, u8)
-
-
-def paste_photos(photos, boxes, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None):
-    """The decoded ``samples`` (fp32 [B,3,S,S], nominally [-1, 1]) back into ``photos`` IN PLACE, inside their boxes only:
-    photo + a * upsampled((samples + 1) / 2 - src01) * 255, rounded to uint8 (ties to even), where src01 is the img01 the model saw
-    (crop_resize of the same photos and boxes) and a fades from 1 / (feather + 1) at a box side to 1 over ``feather`` photo pixels
-    (sides on the photo's border do not fade).  Only the difference is interpolated, so everything finer than the model's grid stays
-    the photo's own.  ``weights`` (fp32 [B,wh,ww], wh, ww <= 2048; mkd_paste_photo_weighted): plane b covers the WHOLE of photo b at
-    low resolution and a is multiplied by its bilinear sample at the photo pixel (components.owner_weights: each face's paste stays
-    on its own pixels); a weight of 0 leaves the photo's byte.  Returns ``photos``."""
-    rho = int(feather)
-    if rho != feather or not 0 <= rho <= MAX_FEATHER:
-        raise ValueError(f'feather must be an integer 0..{MAX_FEATHER} photo pixels, got {feather!r}')
-    plist = _photo_list(photos, 'paste_photos')
-    B = len(plist)
-    if len(boxes) != B:
-        raise ValueError(f'{B} photos but {len(boxes)} boxes')
-    if samples.dim() != 4 or samples.shape[0] != B or samples.shape[1] != 3 or samples.shape[2] != samples.shape[3]:
-        raise ValueError(f'samples must be [{B},3,S,S], got {tuple(samples.shape)}')
-    if tuple(src01.shape) != tuple(samples.shape):
-        raise ValueError(f'src01 {tuple(src01.shape)} must have the shape of samples {tuple(samples.shape)}')
-    S = _check_size(int(samples.shape[2]))
-    boxes = [check_box(b, int(p.shape[0]), int(p.shape[1]), S) for p, b in zip(plist, boxes)]
-    for p in plist:
-        if not _rows_ok(p):
-            raise ValueError('paste_photos writes in place: a photo needs interleaved RGB rows (stride (pitch, 3, 1))')
-    dev = plist[0].device
-    t = samples.to(device=dev, dtype=torch.float32).contiguous()
-    s = src01.to(device=dev, dtype=torch.float32).contiguous()
-    w = None
-    if weights is not None:
-        if not isinstance(weights, torch.Tensor) or weights.dim() != 3 or weights.shape[0] != B or weights.dtype != torch.float32 \
-                or not (1 <= weights.shape[1] <= MAX_WEIGHT_SIDE and 1 <= weights.shape[2] <= MAX_WEIGHT_SIDE):
-            raise ValueError(f'weights must be fp32 [{B},wh,ww] with wh, ww in 1..{MAX_WEIGHT_SIDE}, got '
-                             f'{getattr(weights, "dtype", type(weights))} {tuple(getattr(weights, "shape", ()))}')
-        w = weights.to(device=dev).contiguous()
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        for b0 in range(0, B, MAX_BATCH):
-            b1 = min(B, b0 + MAX_BATCH)
-            arr = _descs(plist[b0:b1], boxes[b0:b1], None)
-            if w is None:
-                _lib.check(lib.mkd_paste_photo(arr, b1 - b0, S, C.c_void_p(t[b0:b1].data_ptr()), C.c_void_p(s[b0:b1].data_ptr()), rho,
-                                               C.c_void_p(_stream())), 'mkd_paste_photo')
-            else:
-                _lib.check(lib.mkd_paste_photo_weighted(arr, b1 - b0, S, C.c_void_p(t[b0:b1].data_ptr()), C.c_void_p(s[b0:b1].data_ptr()), rho,
-                                                        C.c_void_p(w[b0:b1].data_ptr()), int(w.shape[1]), int(w.shape[2]), C.c_void_p(_stream())),
-                           'mkd_paste_photo_weighted')
-    return photos
 
 
 # ---- tilted faces: the same path along a rotated square (include/mkd.h mkd_crop_frame, mkd_paste_frame; this build's rule) ----------
@@ -281,24 +179,11 @@ def check_frame(frame, H: int, W: int, size: int) -> Frame:
     return f
 
 
-def _frame_descs(photos: Sequence[torch.Tensor], frames, labels: Optional[Sequence[torch.Tensor]]):
-    arr = (_lib.PhotoFrameDescC * len(photos))()
-    for i, (p, f) in enumerate(zip(photos, frames)):
-        H, W = int(p.shape[0]), int(p.shape[1])
-        arr[i].pixels = p.data_ptr()
-        arr[i].pitch_bytes = int(p.stride(0)) if H > 1 else 3 * W
-        arr[i].H, arr[i].W = H, W
-        arr[i].cx, arr[i].cy, arr[i].side, arr[i].c, arr[i].s = f
-        arr[i].labels = None if labels is None else labels[i].data_ptr()
-    return arr
-
-
+# ---- one crop and one paste for both kinds of region ---------------------------------------------------------------------------------
 def _label_list(labels, photos, dev) -> Optional[List[torch.Tensor]]:
     if labels is None:
         return None
-    if isinstance(labels, torch.Tensor):
-        labels = [labels] if labels.dim() == 2 else list(labels.unbind(0))
-    labels = list(labels)
+    labels = as_list(labels, 2)
     if len(labels) != len(photos):
         raise ValueError(f'{len(photos)} photos but {len(labels)} label maps')
     out = []
@@ -310,39 +195,14 @@ def _label_list(labels, photos, dev) -> Optional[List[torch.Tensor]]:
     return out
 
 
-def crop_frames(photos, frames, size: int, labels=None, want_u8: bool = False) -> Cropped:
-    """crop_resize along ROTATED squares (mkd_crop_frame): photos and their Frames (cx, cy, side, c, s) -> Cropped(img01 fp32
-    [B,3,S,S], labels uint8 [B,S,S] or None, u8 uint8 [B,S,S,3] or None).  The face's "right" axis (c, s) becomes the crop's +x: a
-    rolled face comes out upright.  Pillow's triangle filter taken in the face's frame, in double and in one pass (within 1 of
-    crop_resize's bytes for an upright integer box); the square may stick out of the photo, edges are replicated; labels are
-    sampled at the output pixel centres without interpolation."""
-    S = _check_size(size)
-    photos = _photo_list(photos, 'crop_frames')
-    B = len(photos)
-    if len(frames) != B:
-        raise ValueError(f'{B} photos but {len(frames)} frames')
-    frames = [check_frame(f, int(p.shape[0]), int(p.shape[1]), S) for p, f in zip(photos, frames)]
-    dev = photos[0].device
-    photos = [p if _rows_ok(p) else p.contiguous() for p in photos]
-    labels = _label_list(labels, photos, dev)
-    lib = _lib.load()
-    img01 = torch.empty((B, 3, S, S), device=dev, dtype=torch.float32)
-    lab_out = torch.empty((B, S, S), device=dev, dtype=torch.uint8) if labels is not None else None
-    u8 = torch.empty((B, S, S, 3), device=dev, dtype=torch.uint8) if want_u8 else None
-    P = lambda t: C.c_void_p(None if t is None else t.data_ptr())
-    with torch.cuda.device(dev):
-        for b0 in range(0, B, MAX_BATCH):
-            b1 = min(B, b0 + MAX_BATCH)
-            arr = _frame_descs(photos[b0:b1], frames[b0:b1], None if labels is None else labels[b0:b1])
-            _lib.check(lib.mkd_crop_frame(arr, b1 - b0, S, P(img01[b0:b1]), P(None if u8 is None else u8[b0:b1]),
-                                          P(None if lab_out is None else lab_out[b0:b1]), C.c_void_p(_stream())), 'mkd_crop_frame')
-    return Cropped(img01, lab_out, u8)
-
-
-def _check_paste(what: str, plist, regions, samples, src01, feather, weights):
+def _check_feather(feather) -> int:
     rho = int(feather)
     if rho != feather or not 0 <= rho <= MAX_FEATHER:
         raise ValueError(f'feather must be an integer 0..{MAX_FEATHER} photo pixels, got {feather!r}')
+    return rho
+
+
+def _check_paste(what: str, plist, regions, samples, src01, weights) -> int:
     B = len(plist)
     if len(regions) != B:
         raise ValueError(f'{B} photos but {len(regions)} {what}')
@@ -355,22 +215,103 @@ def _check_paste(what: str, plist, regions, samples, src01, feather, weights):
                 or not (1 <= weights.shape[1] <= MAX_WEIGHT_SIDE and 1 <= weights.shape[2] <= MAX_WEIGHT_SIDE):
             raise ValueError(f'weights must be fp32 [{B},wh,ww] with wh, ww in 1..{MAX_WEIGHT_SIDE}, got '
                              f'{getattr(weights, "dtype", type(weights))} {tuple(getattr(weights, "shape", ()))}')
-    return rho, _check_size(int(samples.shape[2]))
+    return _check_size(int(samples.shape[2]))
 
 
-def paste_frames(photos, frames, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None):
-    """paste_photos along ROTATED squares (mkd_paste_frame), IN PLACE: every photo pixel whose centre lies in its Frame gets
-    photo + a * g * bilinear((samples + 1) / 2 - src01) * 255 sampled at its place in the frame, in double; a fades over ``feather``
-    photo pixels at ALL four sides of the square, g is the bilinear sample of ``weights`` (fp32 [B,wh,ww] over the whole photo, as in
-    paste_photos) or 1.  Bytes outside the square, and everything of a square that does not reach its photo, stay.  Returns
-    ``photos``."""
-    plist = _photo_list(photos, 'paste_frames')
-    rho, S = _check_paste('frames', plist, frames, samples, src01, feather, weights)
+def _ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
+    return C.c_void_p(None if t is None else t.data_ptr())
+
+
+# The library calls of the two kinds on one chunk of at most MAX_BATCH descriptors: a crop into (img01, u8, labels), each a tensor or
+# None, and a paste of (t, s01) weighted by w (a tensor or None).
+def _crop_box(lib, arr, n, S, img01, u8, lab_out):
+    nbytes = int(lib.mkd_crop_resize_scratch_bytes(arr, n, S))
+    if nbytes <= 0:
+        raise _lib.MkdError('mkd_crop_resize_scratch_bytes refused the descriptors')
+    scratch = torch.empty((nbytes + 256,), device=img01.device, dtype=torch.uint8)       # (the stream keeps it alive until the kernels ran)
+    base = (scratch.data_ptr() + 255) & ~255
+    _lib.check(lib.mkd_crop_resize(arr, n, S, _ptr(img01), _ptr(u8), _ptr(lab_out), C.c_void_p(base), C.c_void_p(_stream())), 'mkd_crop_resize')
+
+
+def _crop_frame(lib, arr, n, S, img01, u8, lab_out):
+    _lib.check(lib.mkd_crop_frame(arr, n, S, _ptr(img01), _ptr(u8), _ptr(lab_out), C.c_void_p(_stream())), 'mkd_crop_frame')
+
+
+def _paste_box(lib, arr, n, S, t, s, rho, w):
+    if w is None:
+        _lib.check(lib.mkd_paste_photo(arr, n, S, _ptr(t), _ptr(s), rho, C.c_void_p(_stream())), 'mkd_paste_photo')
+    else:
+        _lib.check(lib.mkd_paste_photo_weighted(arr, n, S, _ptr(t), _ptr(s), rho, _ptr(w), int(w.shape[1]), int(w.shape[2]), C.c_void_p(_stream())),
+                   'mkd_paste_photo_weighted')
+
+
+def _paste_frame(lib, arr, n, S, t, s, rho, w):
+    _lib.check(lib.mkd_paste_frame(arr, n, S, _ptr(t), _ptr(s), rho, _ptr(w), 0 if w is None else int(w.shape[1]), 0 if w is None else int(w.shape[2]),
+                                   C.c_void_p(_stream())), 'mkd_paste_frame')
+
+
+def _fill_box(d, box):
+    d.x0, d.y0, d.bw, d.bh = box
+
+
+def _fill_frame(d, frame):
+    d.cx, d.cy, d.side, d.c, d.s = frame
+
+
+# a kind of region: what messages call its entries, its checker, its descriptor type and what writes a checked region into one, and
+# its crop and paste: the name of the public entry and the library call
+_Kind = namedtuple('_Kind', 'noun check desc fill crop_name crop paste_name paste')
+_BOX = _Kind('boxes', check_box, _lib.PhotoDescC, _fill_box, 'crop_resize', _crop_box, 'paste_photos', _paste_box)
+_FRAME = _Kind('frames', check_frame, _lib.PhotoFrameDescC, _fill_frame, 'crop_frames', _crop_frame, 'paste_frames', _paste_frame)
+
+
+def _descs(kind: _Kind, photos: Sequence[torch.Tensor], regions, labels: Optional[Sequence[torch.Tensor]]):
+    arr = (kind.desc * len(photos))()          # (zeroed: labels stays null without a label map)
+    for i, (d, p, r) in enumerate(zip(arr, photos, regions)):
+        H, W = p.shape[0], p.shape[1]
+        d.pixels = p.data_ptr()
+        d.pitch_bytes = p.stride(0) if H > 1 else 3 * W
+        d.H, d.W = H, W
+        if labels is not None:
+            d.labels = labels[i].data_ptr()
+        kind.fill(d, r)
+    return arr
+
+
+def _crop(kind: _Kind, photos, regions, size: int, labels, want_u8: bool) -> Cropped:
+    S = _check_size(size)
+    photos = _photo_list(photos, kind.crop_name)
+    B = len(photos)
+    if len(regions) != B:
+        raise ValueError(f'{B} photos but {len(regions)} {kind.noun}')
+    regions = [kind.check(r, int(p.shape[0]), int(p.shape[1]), S) for p, r in zip(photos, regions)]
+    dev = photos[0].device
+    photos = [p if _rows_ok(p) else p.contiguous() for p in photos]
+    labels = _label_list(labels, photos, dev)
+    lib = _lib.load()
+    img01 = torch.empty((B, 3, S, S), device=dev, dtype=torch.float32)
+    lab_out = torch.empty((B, S, S), device=dev, dtype=torch.uint8) if labels is not None else None
+    u8 = torch.empty((B, S, S, 3), device=dev, dtype=torch.uint8) if want_u8 else None
+    part = lambda t, b0, b1: None if t is None else t[b0:b1]
+    with torch.cuda.device(dev):
+        for b0 in range(0, B, MAX_BATCH):
+            b1 = min(B, b0 + MAX_BATCH)
+            kind.crop(lib, _descs(kind, photos[b0:b1], regions[b0:b1], part(labels, b0, b1)), b1 - b0, S, img01[b0:b1], part(u8, b0, b1),
+                      part(lab_out, b0, b1))
+    return Cropped(img01, lab_out, u8)
+
+
+def _paste(kind: _Kind, photos, regions, samples: torch.Tensor, src01: torch.Tensor, feather: int, weights: Optional[torch.Tensor]):
+    # one order of checks for both kinds: feather, photos, counts and shapes, weights, size, regions, rows.  Against the two copies this
+    # replaces, paste_frames now looks at the feather before the photos, and paste_photos at the weights before the boxes and rows
+    rho = _check_feather(feather)
+    plist = _photo_list(photos, kind.paste_name)
+    S = _check_paste(kind.noun, plist, regions, samples, src01, weights)
     B = len(plist)
-    frames = [check_frame(f, int(p.shape[0]), int(p.shape[1]), S) for p, f in zip(plist, frames)]
+    regions = [kind.check(r, int(p.shape[0]), int(p.shape[1]), S) for p, r in zip(plist, regions)]
     for p in plist:
         if not _rows_ok(p):
-            raise ValueError('paste_frames writes in place: a photo needs interleaved RGB rows (stride (pitch, 3, 1))')
+            raise ValueError(f'{kind.paste_name} writes in place: a photo needs interleaved RGB rows (stride (pitch, 3, 1))')
     dev = plist[0].device
     t = samples.to(device=dev, dtype=torch.float32).contiguous()
     s = src01.to(device=dev, dtype=torch.float32).contiguous()
@@ -379,11 +320,45 @@ def paste_frames(photos, frames, samples: torch.Tensor, src01: torch.Tensor, fea
     with torch.cuda.device(dev):
         for b0 in range(0, B, MAX_BATCH):
             b1 = min(B, b0 + MAX_BATCH)
-            arr = _frame_descs(plist[b0:b1], frames[b0:b1], None)
-            _lib.check(lib.mkd_paste_frame(arr, b1 - b0, S, C.c_void_p(t[b0:b1].data_ptr()), C.c_void_p(s[b0:b1].data_ptr()), rho,
-                                           C.c_void_p(None if w is None else w[b0:b1].data_ptr()), 0 if w is None else int(w.shape[1]),
-                                           0 if w is None else int(w.shape[2]), C.c_void_p(_stream())), 'mkd_paste_frame')
+            kind.paste(lib, _descs(kind, plist[b0:b1], regions[b0:b1], None), b1 - b0, S, t[b0:b1], s[b0:b1], rho, None if w is None else w[b0:b1])
     return photos
+
+
+def crop_resize(photos, boxes, size: int, labels=None, want_u8: bool = False) -> Cropped:
+    """photos (a list of uint8 [H,W,3] device tensors, or one [B,H,W,3] tensor) and their boxes (x0, y0, w, h) ->
+    Cropped(img01 fp32 [B,3,S,S] = float(u8) / 255 of Pillow's antialiased bilinear resize of the box to S x S (the values
+    PairFolderDataset._load gives for that crop), labels uint8 [B,S,S] or None, u8 uint8 [B,S,S,3] or None).  ``labels``: one uint8
+    [H,W] label map per photo at the photo's resolution, sampled at the output pixel centres without interpolation."""
+    return _crop(_BOX, photos, boxes, size, labels, want_u8)
+
+
+def paste_photos(photos, boxes, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None):
+    """The decoded ``samples`` (fp32 [B,3,S,S], nominally [-1, 1]) back into ``photos`` IN PLACE, inside their boxes only:
+    photo + a * upsampled((samples + 1) / 2 - src01) * 255, rounded to uint8 (ties to even), where src01 is the img01 the model saw
+    (crop_resize of the same photos and boxes) and a fades from 1 / (feather + 1) at a box side to 1 over ``feather`` photo pixels
+    (sides on the photo's border do not fade).  Only the difference is interpolated, so everything finer than the model's grid stays
+    the photo's own.  ``weights`` (fp32 [B,wh,ww], wh, ww <= 2048; mkd_paste_photo_weighted): plane b covers the WHOLE of photo b at
+    low resolution and a is multiplied by its bilinear sample at the photo pixel (components.owner_weights: each face's paste stays
+    on its own pixels); a weight of 0 leaves the photo's byte.  Returns ``photos``."""
+    return _paste(_BOX, photos, boxes, samples, src01, feather, weights)
+
+
+def crop_frames(photos, frames, size: int, labels=None, want_u8: bool = False) -> Cropped:
+    """crop_resize along ROTATED squares (mkd_crop_frame): photos and their Frames (cx, cy, side, c, s) -> Cropped(img01 fp32
+    [B,3,S,S], labels uint8 [B,S,S] or None, u8 uint8 [B,S,S,3] or None).  The face's "right" axis (c, s) becomes the crop's +x: a
+    rolled face comes out upright.  Pillow's triangle filter taken in the face's frame, in double and in one pass (within 1 of
+    crop_resize's bytes for an upright integer box); the square may stick out of the photo, edges are replicated; labels are
+    sampled at the output pixel centres without interpolation."""
+    return _crop(_FRAME, photos, frames, size, labels, want_u8)
+
+
+def paste_frames(photos, frames, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None):
+    """paste_photos along ROTATED squares (mkd_paste_frame), IN PLACE: every photo pixel whose centre lies in its Frame gets
+    photo + a * g * bilinear((samples + 1) / 2 - src01) * 255 sampled at its place in the frame, in double; a fades over ``feather``
+    photo pixels at ALL four sides of the square, g is the bilinear sample of ``weights`` (fp32 [B,wh,ww] over the whole photo, as in
+    paste_photos) or 1.  Bytes outside the square, and everything of a square that does not reach its photo, stay.  Returns
+    ``photos``."""
+    return _paste(_FRAME, photos, frames, samples, src01, feather, weights)
 
 
 def split_regions(regions):
@@ -476,10 +451,8 @@ def square_box_from_labels(labels, classes: Iterable[int] = (1, 2, 3, 4, 5, 6, 7
     of ``classes`` that mkd_region_mask_from_labels returns, grown and squared by grow_square_box.  Reads the boxes back (one small
     device-to-host copy per photo size): set-up, not the hot path."""
     from . import makeup_score as ms
-    if isinstance(labels, torch.Tensor):
-        labels = [labels] if labels.dim() == 2 else list(labels.unbind(0))
     out = []
-    for l in labels:
+    for l in as_list(labels, 2):
         if l.dim() != 2:
             raise ValueError(f'a label map is [H,W], got {tuple(l.shape)}')
         _, _, box = ms.region_mask(l[None], classes, box_classes=classes, margin=0)

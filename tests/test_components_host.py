@@ -222,6 +222,21 @@ def test_transfer_photos_max_faces_checks():
         m.transfer_photos(p, p, [one, one], ref, return_faces=True)
 
 
+def test_transfer_photos_without_max_faces_checks_its_boxes():
+    """one 4-entry box per photo, source and reference: a wrong count or a 5-entry box (a Frame) is an error, never a partial result"""
+    m = _model()
+    p = [torch.zeros(80, 80, 3, dtype=torch.uint8)] * 3
+    one = (0, 0, 40, 40)
+    for src, ref in (([one], [one] * 3), ([one] * 3, [one] * 4), ([one] * 4, [one] * 3), ([one] * 3, [one])):
+        with pytest.raises(ValueError, match='3 photos but [14] boxes'):
+            m.transfer_photos(p, p, src, ref)
+    for bad in ((0, 0, 40, 40, 15.0), photo.Frame(40.0, 40.0, 40.0, 1.0, 0.0), (0, 0, 40)):
+        with pytest.raises(ValueError, match='a box is'):
+            m.transfer_photos(p, p, [one, bad, one], [one] * 3)
+        with pytest.raises(ValueError, match='a box is'):
+            m.transfer_photos(p, p, [one] * 3, [one, one, bad])
+
+
 # ---- boxes files with several faces per image ---------------------------------------------------------------------------------------
 def test_read_boxes_multi(tmp_path):
     f = tmp_path / 'boxes.txt'

@@ -201,6 +201,15 @@ def test_python_side_validation():
     assert photo.resize_ksize(122, 37) == 9 and photo.resize_ksize(9, 16) == 3 and photo.resize_ksize(64, 64) == 3
 
 
+@pytest.mark.parametrize('rank', [2, 3])
+def test_as_list_takes_a_tensor_a_stacked_batch_and_a_list(rank):
+    shape = (2, 3, 4) if rank == 3 else (4, 6)
+    one, two = torch.arange(24).reshape(shape), torch.arange(48).reshape((2,) + shape)
+    got = [photo.as_list(one, rank), photo.as_list(two, rank), photo.as_list((one, one + 1), rank)]
+    assert [len(g) for g in got] == [1, 2, 2] and all(isinstance(g, list) and all(t.dim() == rank for t in g) for g in got)
+    assert got[0][0] is one and torch.equal(torch.stack(got[1]), two) and torch.equal(got[2][1], one + 1)
+
+
 def test_grow_square_box():
     up, down, width = 0.6 / 0.85, 0.2 / 0.85, 0.2 / 0.85
     # a 100 x 60 face (rows 300..399, columns 470..529) in a large photo: grown height 100 (1 + up + down), the longer side
