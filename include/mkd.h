@@ -150,6 +150,15 @@ int mkd_region_blend_bf16(const uint16_t* const* e_ptrs, const float* weights, u
 /* Tests only, like mkd_debug_poison: copies the cached ControlNet hint embedding [B,h,w,model_channels] bf16 out (enqueued on `stream`).
  * MKD_ERR_STATE when no conditioning with a hint is prepared. */
 int mkd_debug_hint_embedding(mkd_ctx* ctx, uint16_t* out_bf16, void* stream);
+/* Tests only: the first-stage mid-block attention (GroupNorm -> q|k, V^T -> fp32 scores -> softmax -> P.V + bv -> proj_out + x) alone,
+ * of the decoder (which = 2) or the encoder (which = 4) of `ctx`, with the weights of that finalised network.  It emits and runs the
+ * same op sequence the decode / encode plans hold.  x, out bf16 NHWC [batch, H, W, C] (out must not alias x); o bf16 [batch*H*W, C]
+ * (may be NULL) receives the attention output before proj_out.  C must be the network's mid width ch * ch_mult[last] and H * W a
+ * multiple of 8.  The plan and the workspace of the call are its own and are released before it returns (it synchronises `stream`): a
+ * later mkd_decode / mkd_encode gives the bits it gave before.  MKD_ERR_STATE when that network is not finalised; MKD_ERR_ARG for
+ * a null ctx / x / out, a bad shape, another `which`, or C != mid width. */
+int mkd_debug_vae_attn(mkd_ctx* ctx, int which, const uint16_t* x_bf16_nhwc, int batch, int H, int W, int C, uint16_t* out_bf16,
+                       uint16_t* o_bf16, void* stream);
 
 /* ---- one eps evaluation ----------------------------------------------------------------- */
 /* Replaces apply_model (makeup_diffuse.py:152-170): ControlNet -> 13 residuals x scale ->
@@ -822,6 +831,25 @@ int mkd_attention_causal(const uint16_t* q, int ldq, const uint16_t* k, int ldk,
                          void* stream);
 /* y[m, j] = x[m, j] * gelu_erf(x[m, inner + j]). */
 int mkd_geglu(const uint16_t* x, uint16_t* y, int rows, int inner, void* stream);
+/* ---- the side networks' small kernels, one launch each (unit tests; the plans call the same launchers) ---- */
+/* y[r, :] = softmax(x[r, :]): x fp32 [rows, cols] (the first-stage mid attention keeps its scores in fp32), y bf16 [rows, cols]. */
+int mkd_softmax_rows(const float* x, uint16_t* y, int rows, int cols, void* stream);
+/* Fused tail of the first-stage encoder: conv_out (3x3 pad 1, Cin -> 2Z; x bf16 NHWC [batch,H,W,Cin], w packed bf16 [2Z][3][3][Cin], bias
+ * fp32 [2Z]) -> quant_conv (wq bf16 [2Z][2Z], bq fp32 [2Z]) -> moments fp32 NCHW [batch,2Z,H,W] = (mean | logvar) and
+ * z fp32 NCHW [batch,Z,H,W] = (mean + exp(0.5 clamp(logvar, -30, 20)) * noise) * scale; noise NULL: z = mean * scale.  Either output may
+ * be NULL, not both.  z_channels must be 4 and Cin a multiple of 8, else MKD_ERR_ARG. */
+int mkd_vae_enc_tail(const uint16_t* x, const uint16_t* w, const float* bias, const uint16_t* wq, const float* bq, const float* noise,
+                     float scale, float* z_out, float* moments_out, int batch, int H, int W, int Cin, int z_channels, void* stream);
+/* post_quant_conv: out[b, o, p] = bias[o] + sum_i w[o, i] * (z[b, i, p] * inv_scale); z, out fp32 [batch, C, hw], w bf16 [C][C]. */
+int mkd_post_quant(const float* z, const uint16_t* w, const float* bias, float inv_scale, float* out, int batch, int C, int hw, void* stream);
+/* out[b] = [cos(t_b f_k) | sin(t_b f_k)], f_k = exp(-ln(1e4) k / (dim/2)): t int64 [batch] (device), out bf16 [batch, dim]; dim even. */
+int mkd_timestep_embedding(const int64_t* t, uint16_t* out, int batch, int dim, void* stream);
+/* out[b, t, :] = tok_emb[tokens[b, t]] + pos_emb[t]: tokens int32 [batch, T], tok_emb bf16 [vocab, width], pos_emb bf16 [>= T, width],
+ * out bf16 [batch, T, width]; width a multiple of 8.  Ids outside [0, vocab) are clamped (mkd_clip_encode rejects them before). */
+int mkd_clip_embed(const int32_t* tokens, const uint16_t* tok_emb, const uint16_t* pos_emb, uint16_t* out, int batch, int T, int width,
+                   int vocab, void* stream);
+/* y[s] = (1 - alpha[s]) a[s] + alpha[s] b[s] per sample s: a, b, y bf16 [batch, per_sample], alpha fp32 [batch]; per_sample % 8 == 0. */
+int mkd_blend_bf16(const uint16_t* a, const uint16_t* b, const float* alpha, uint16_t* y, int64_t per_sample, int batch, void* stream);
 /* direct 3x3 conv, pad 1, fp32 accumulate.  in_nchw_f32: x is fp32 NCHW else bf16 NHWC;
  * out_nchw_f32 likewise; act 1 = SiLU; add (bf16 NHWC, may be NULL) is added after act. */
 int mkd_conv3x3_direct(const void* x, int in_nchw_f32, const uint16_t* w, const float* bias,

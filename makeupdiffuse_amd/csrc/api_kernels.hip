@@ -186,6 +186,26 @@ int mkd_attention_causal(const uint16_t* q, int ldq, const uint16_t* k, int ldk,
 int mkd_geglu(const uint16_t* x, uint16_t* y, int rows, int inner, void* stream) {
     return launch_geglu(x, y, rows, inner, (hipStream_t)stream);
 }
+int mkd_softmax_rows(const float* x, uint16_t* y, int rows, int cols, void* stream) {
+    return launch_softmax_rows(x, y, rows, cols, (hipStream_t)stream);
+}
+int mkd_vae_enc_tail(const uint16_t* x, const uint16_t* w, const float* bias, const uint16_t* wq, const float* bq, const float* noise,
+                     float scale, float* z_out, float* moments_out, int batch, int H, int W, int Cin, int z_channels, void* stream) {
+    return launch_vae_enc_tail(x, w, bias, wq, bq, noise, scale, z_out, moments_out, batch, H, W, Cin, z_channels, (hipStream_t)stream);
+}
+int mkd_post_quant(const float* z, const uint16_t* w, const float* bias, float inv_scale, float* out, int batch, int C, int hw, void* stream) {
+    return launch_post_quant(z, w, bias, inv_scale, out, batch, C, hw, (hipStream_t)stream);
+}
+int mkd_timestep_embedding(const int64_t* t, uint16_t* out, int batch, int dim, void* stream) {
+    return launch_timestep_embedding(t, out, batch, dim, (hipStream_t)stream);
+}
+int mkd_clip_embed(const int32_t* tokens, const uint16_t* tok_emb, const uint16_t* pos_emb, uint16_t* out, int batch, int T, int width,
+                   int vocab, void* stream) {
+    return launch_clip_embed(tokens, tok_emb, pos_emb, out, batch, T, width, vocab, (hipStream_t)stream);
+}
+int mkd_blend_bf16(const uint16_t* a, const uint16_t* b, const float* alpha, uint16_t* y, int64_t per_sample, int batch, void* stream) {
+    return launch_blend(a, b, alpha, y, per_sample, batch, (hipStream_t)stream);
+}
 int mkd_conv3x3_direct(const void* x, int in_nchw_f32, const uint16_t* w, const float* bias, void* y, int out_nchw_f32, int act,
                        const uint16_t* add, int batch, int Hin, int Win, int Cin, int Cout, int stride, void* stream) {
     return launch_conv3x3_direct(x, in_nchw_f32, w, bias, y, out_nchw_f32, act, add, batch, Hin, Win, Cin, Cout, stride,

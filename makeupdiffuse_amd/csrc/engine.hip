@@ -2431,31 +2431,35 @@ struct mkd_ctx {
         ar.release(mk);
     }
 
-    // single-head attention over the hw tokens of each sample, built from GEMMs (c = 512 does not fit the flash kernel)
-    void vae_attn(SideNet& n, const std::string& p, const Tensor& x, bf16_t* out) {
-        Arena& ar = n.arena;
+    // single-head attention over the hw tokens of each sample, built from GEMMs (c = 512 does not fit the flash kernel).
+    // bf16 tensors: the GroupNorm output, q|k, V^T, the probabilities and o.  The scores S = scale . Q.K^T leave the GEMM as fp32 and
+    // the softmax reads them as fp32: rounded to bf16, a logit of magnitude 16..32 is off by up to 2^-4, several percent in every
+    // probability of its row (tests/test_gpu_vae_attn.py holds every output row to rel-L2 8e-3 at logit std 1, 4 and 9).
+    // ar: the arena the temporaries come from; f: the net's fused [Wq;Wk]; o_out: where o = P.V + bv goes when the caller wants to
+    // see it (mkd_debug_vae_attn), else a temporary
+    void vae_attn(Arena& ar, const FusedRows& f, const std::string& p, const Tensor& x, bf16_t* out, bf16_t* o_out = nullptr) {
         const size_t mk = ar.mark();
         const int c = x.C, T = x.H * x.W, M = x.rows();
         auto buf = [&](size_t n) { return (bf16_t*)ar.alloc(n * sizeof(bf16_t)); };
         bf16_t* g = buf((size_t)M * c);
         op_gn(x, wf(p + ".norm.weight"), wf(p + ".norm.bias"), 1e-6f, 0, g, c);
         bf16_t* qk = buf((size_t)M * 2 * c);
-        { const FusedRows& f = n.fused.at(p); Epi e; e.bias = f.b; op_linear(g, c, M, c, f.w, 2 * c, e, qk, 2 * c); }
+        { Epi e; e.bias = f.b; op_linear(g, c, M, c, f.w, 2 * c, e, qk, 2 * c); }
         bf16_t* vt = buf((size_t)x.B * c * T);          // V^T per sample: [c][T] = Wv . g_b^T  (v bias added after PV: softmax rows sum to 1)
-        bf16_t* sc = buf((size_t)x.B * T * T);
+        float* sc = (float*)ar.alloc((size_t)x.B * T * T * sizeof(float));
         bf16_t* pr = buf((size_t)x.B * T * T);
-        bf16_t* o = buf((size_t)M * c);
+        bf16_t* o = o_out ? o_out : buf((size_t)M * c);
         const float scale = 1.0f / sqrtf((float)c);
         for (int b = 0; b < x.B; ++b) {
             { Epi e; op_linear(wb(p + ".v.weight"), c, c, c, g + (size_t)b * T * c, T, e, vt + (size_t)b * c * T, T); }
             { Epi e; e.scale = scale;
               GemmArgs a; memset(&a, 0, sizeof(a));
               a.A = qk + (size_t)b * T * 2 * c; a.lda = 2 * c; a.W = qk + (size_t)b * T * 2 * c + c; a.ldw = 2 * c;
-              a.scale = scale; a.C = sc + (size_t)b * T * T; a.ldc = T; a.M = T; a.N = T; a.K = c; a.rows_per_batch = 1;
+              a.scale = scale; a.C = sc + (size_t)b * T * T; a.ldc = T; a.out_f32 = 1; a.M = T; a.N = T; a.K = c; a.rows_per_batch = 1;
               op_gemm(a); }
         }
         {
-            bf16_t* s_ = sc; bf16_t* p_ = pr; const int rows = x.B * T, cols = T;
+            const float* s_ = sc; bf16_t* p_ = pr; const int rows = x.B * T, cols = T;
             push([=](hipStream_t st) { return launch_softmax_rows(s_, p_, rows, cols, st); }, 1, 0.0, K_MISC, "softmax_rows");
         }
         for (int b = 0; b < x.B; ++b) {
@@ -2503,7 +2507,7 @@ struct mkd_ctx {
         }
         auto step = [&](int cout) { cur ^= 1; Tensor o = h; o.C = cout; o.ld = cout; o.p = X[cur]; return o; };
         { Tensor o = step(bi); vae_resblock(n.arena, D + "mid.block_1", h, bi, o.p); h = o; }
-        { Tensor o = step(bi); vae_attn(n, D + "mid.attn_1", h, o.p); h = o; }
+        { Tensor o = step(bi); vae_attn(n.arena, n.fused.at(D + "mid.attn_1"), D + "mid.attn_1", h, o.p); h = o; }
         { Tensor o = step(bi); vae_resblock(n.arena, D + "mid.block_2", h, bi, o.p); h = o; }
         for (int lvl = dec_cfg.n_levels - 1; lvl >= 0; --lvl) {
             const int bo = dec_cfg.ch * dec_cfg.ch_mult[lvl];
@@ -2616,7 +2620,7 @@ struct mkd_ctx {
             }
         }
         { Tensor o = step(h.C); vae_resblock(n.arena, E + "mid.block_1", h, h.C, o.p); h = o; }
-        { Tensor o = step(h.C); vae_attn(n, E + "mid.attn_1", h, o.p); h = o; }
+        { Tensor o = step(h.C); vae_attn(n.arena, n.fused.at(E + "mid.attn_1"), E + "mid.attn_1", h, o.p); h = o; }
         { Tensor o = step(h.C); vae_resblock(n.arena, E + "mid.block_2", h, h.C, o.p); h = o; }
         {
             Tensor o = step(h.C);
@@ -2782,6 +2786,31 @@ struct mkd_ctx {
         return launch_copy_strided(hint_emb.p, hint_emb.ld, out, hint_emb.C, hint_emb.B * hint_emb.H * hint_emb.W, hint_emb.C, stream);
     }
 
+    // tests only: the mid-block attention of the finalised decoder (which = W_DEC) or encoder (W_ENC) alone, on the caller's x.  The
+    // ops are emitted by vae_attn itself, into a plan and an arena that live for this call only: the net's own plan and arena are not
+    // touched (the shared SID_AUX workspaces may grow, as in any replan; plans read them at run time).  Synchronises `stream`.
+    int debug_vae_attn(int which, const bf16_t* x, int Bn, int H, int W, int C, bf16_t* out, bf16_t* o, hipStream_t stream) {
+        if (which != W_DEC && which != W_ENC) return mkd_fail(MKD_ERR_ARG, "mkd_debug_vae_attn: which must be 2 (decoder) or 4 (encoder)");
+        SideNet& n = net(which);
+        if (!n.finalized) return mkd_fail(MKD_ERR_STATE, "mkd_debug_vae_attn: that network is not finalised");
+        const mkd_vae_config& vc = which == W_DEC ? dec_cfg : enc_cfg;
+        const int mid = vc.ch * vc.ch_mult[vc.n_levels - 1];
+        if (!x || !out || Bn <= 0 || H <= 0 || W <= 0) return mkd_fail(MKD_ERR_ARG, "mkd_debug_vae_attn: bad arguments");
+        if (C != mid) return mkd_fail(MKD_ERR_ARG, "mkd_debug_vae_attn: C must be the network's mid width " + std::to_string(mid));
+        const std::string p = vae_prefix() + (which == W_DEC ? "decoder." : "encoder.") + "mid.attn_1";
+        Tensor xt; xt.p = const_cast<bf16_t*>(x); xt.B = Bn; xt.H = H; xt.W = W; xt.C = C; xt.ld = C;
+        SideNet own;
+        int rc = side_replan(own, Bn, H, W, [&] {
+            Emit plan(emit, EmitTarget{&own.plan, SID_AUX});
+            vae_attn(own.arena, n.fused.at(p), p, xt, out, o);
+        });
+        if (!rc) rc = side_run(own, stream);
+        const hipError_t e = hipStreamSynchronize(stream);
+        if (own.base) hipFree(own.base);
+        if (!rc && e != hipSuccess) return mkd_fail(MKD_ERR_HIP, std::string("mkd_debug_vae_attn: ") + hipGetErrorString(e));
+        return rc;
+    }
+
     int64_t device_bytes() const {
         return weight_bytes + 3 * s_ring_n * (int64_t)sizeof(float) + (int64_t)(side[0].cap + side[1].cap + side[2].cap) + (int64_t)persist_cap + (int64_t)gstat_cap + [&] { int64_t t = 0; for (int i = 0; i < NA; ++i) t += (int64_t)(temp_cap[i] + splitk_ws_bytes[i] + gn_ws_bytes[i]); return t; }();
     }
@@ -2921,6 +2950,9 @@ int mkd_prepare_regions(mkd_ctx* ctx, int batch, int h, int w, const float* cons
 }
 int mkd_debug_hint_embedding(mkd_ctx* ctx, uint16_t* out_bf16, void* stream) {
     return ctx ? ctx->debug_hint_embedding(out_bf16, (hipStream_t)stream) : mkd_fail(MKD_ERR_ARG, "null ctx");
+}
+int mkd_debug_vae_attn(mkd_ctx* ctx, int which, const uint16_t* x, int batch, int H, int W, int C, uint16_t* out, uint16_t* o, void* stream) {
+    return ctx ? ctx->debug_vae_attn(which, x, batch, H, W, C, out, o, (hipStream_t)stream) : mkd_fail(MKD_ERR_ARG, "null ctx");
 }
 int mkd_region_weights(const uint8_t* masks, int n_masks, int batch, int H, int W, int factor, int feather, const float* strength, float* out,
                        void* stream) {

@@ -635,14 +635,16 @@ __global__ __launch_bounds__(256) void vae_enc_tail_kernel(const bf16_t* __restr
     }
 }
 
-// ---- row softmax over bf16 [rows, cols] (VAE mid-block attention scores), one 256-thread block per row ----------
-__global__ __launch_bounds__(256) void softmax_rows_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int cols) {
+// ---- row softmax, fp32 [rows, cols] in -> bf16 probabilities out (VAE mid-block attention scores), one 256-thread block per row.
+// The scores stay fp32 from the Q.K^T accumulator to here: a bf16 logit of magnitude 16..32 is off by up to 2^-4, i.e. several percent
+// in every probability of its row (tests/vae_attn_ref.py measures both orders of rounding).
+__global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, int cols) {
     __shared__ float red[4];
-    const bf16_t* xr = x + (size_t)blockIdx.x * cols;
+    const float* xr = x + (size_t)blockIdx.x * cols;
     bf16_t* yr = y + (size_t)blockIdx.x * cols;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     float mx = -INFINITY;
-    for (int c = threadIdx.x; c < cols; c += 256) mx = fmaxf(mx, bf16_to_f32(xr[c]));
+    for (int c = threadIdx.x; c < cols; c += 256) mx = fmaxf(mx, xr[c]);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
     if (lane == 0) red[wv] = mx;
@@ -650,13 +652,13 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const bf16_t* __restr
     mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     __syncthreads();
     float sum = 0.f;
-    for (int c = threadIdx.x; c < cols; c += 256) sum += __expf(bf16_to_f32(xr[c]) - mx);
+    for (int c = threadIdx.x; c < cols; c += 256) sum += __expf(xr[c] - mx);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
     if (lane == 0) red[wv] = sum;
     __syncthreads();
     const float inv = 1.0f / ((red[0] + red[1]) + (red[2] + red[3]));
-    for (int c = threadIdx.x; c < cols; c += 256) yr[c] = f32_to_bf16(__expf(bf16_to_f32(xr[c]) - mx) * inv);
+    for (int c = threadIdx.x; c < cols; c += 256) yr[c] = f32_to_bf16(__expf(xr[c] - mx) * inv);
 }
 
 // ---- post_quant_conv: 1x1 conv over fp32 NCHW latents with the 1/scale_factor of decode_first_stage folded in -------
@@ -1025,7 +1027,7 @@ int launch_dpmpp_step_rows(const float* x, const float* eps_c, const float* eps_
     return 0;
 }
 
-int launch_softmax_rows(const bf16_t* x, bf16_t* y, int rows, int cols, hipStream_t stream) {
+int launch_softmax_rows(const float* x, bf16_t* y, int rows, int cols, hipStream_t stream) {
     hipLaunchKernelGGL(softmax_rows_kernel, dim3(rows), dim3(256), 0, stream, x, y, cols);
     MKD_LAUNCH_CHECK("softmax_rows_kernel");
     return 0;

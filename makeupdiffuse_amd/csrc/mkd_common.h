@@ -373,7 +373,7 @@ int launch_ddim_step_rows(const float* x, const float* eps_c, const float* eps_u
                           float temperature, float* x_prev, float* pred_x0, int samples, int n_per_sample, hipStream_t stream);
 int launch_dpmpp_step_rows(const float* x, const float* eps_c, const float* eps_u, const StepRow* rows, StepState* st, const float* m1,
                            const float* m2, float* x_prev, float* m0_out, int samples, int n_per_sample, hipStream_t stream);
-int launch_softmax_rows(const bf16_t* x, bf16_t* y, int rows, int cols, hipStream_t stream);
+int launch_softmax_rows(const float* x, bf16_t* y, int rows, int cols, hipStream_t stream);
 int launch_post_quant(const float* z, const bf16_t* w, const float* bias, float inv_scale, float* out, int batch, int C, int hw,
                       hipStream_t stream);
 int launch_clip_embed(const int32_t* tokens, const bf16_t* tok_emb, const bf16_t* pos_emb, bf16_t* out, int batch, int T, int width,

@@ -114,6 +114,7 @@ SIGNATURES = {
     'mkd_region_weights': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     'mkd_region_blend_bf16': (_I, [C.POINTER(_P), _P, _P, _I, _I, _I, _I, _P]),
     'mkd_debug_hint_embedding': (_I, [_P, _P, _P]),
+    'mkd_debug_vae_attn': (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     'mkd_eps': (_I, [_P, _P, _P, _P, _P]),
     'mkd_ddim_step': (_I, [_P, _P, _P, _F, _F, _F, _F, _F, _P, _F, _P, _P, _L, _P]),
     'mkd_ddim_step_ex': (_I, [_P, _P, _P, _F, _F, _F, _F, _F, _P, _F, _P, _I, _P, _P, _L, _P]),
@@ -209,6 +210,12 @@ SIGNATURES = {
     'mkd_attention': (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     'mkd_attention_causal': (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     'mkd_geglu': (_I, [_P, _P, _I, _I, _P]),
+    'mkd_softmax_rows': (_I, [_P, _P, _I, _I, _P]),
+    'mkd_vae_enc_tail': (_I, [_P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'mkd_post_quant': (_I, [_P, _P, _P, _F, _P, _I, _I, _I, _P]),
+    'mkd_timestep_embedding': (_I, [_P, _P, _I, _I, _P]),
+    'mkd_clip_embed': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'mkd_blend_bf16': (_I, [_P, _P, _P, _P, _L, _I, _P]),
     'mkd_conv3x3_direct': (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     'mkd_pack_conv_weight': (_I, [_P, _P, _I, _I, _I, _I, _P]),
     'mkd_parser_create': (_I, [C.POINTER(ParserConfigC), C.POINTER(_P)]),

@@ -36,5 +36,21 @@ def assert_close_bf16(out, ref, rel=4e-3, what=''):
     assert mx <= lim, f'{what}: max-abs {mx:.3e} > {lim:.3e}'
 
 
+def dot_bound(n, abs_sum):
+    """A-priori bound on an fp32 dot product of n terms (any summation order, FMA or not): |err| <= (n + 16) 2^-24 sum |a_i b_i|
+    per element; abs_sum is that sum (a tensor, float64).  The 16 covers a bias, a scale and the rounding of the inputs' products;
+    a missed tap, lane or channel is off by a term of the sum itself, orders of magnitude more."""
+    return (n + 16) * 2.0 ** -24 * abs_sum.double()
+
+
+def assert_within(out, ref, bound, what=''):
+    """Per element |out - ref| <= bound (tensors of one shape, compared in float64); reports the worst ratio."""
+    out = out.double().cpu(); ref = ref.double().cpu(); bound = bound.double().cpu()
+    assert torch.isfinite(out).all(), f'{what}: non-finite output'
+    ratio = ((out - ref).abs() / bound.clamp_min(1e-300)).max().item()
+    print(f'[bound] {what}: worst |err| / bound {ratio:.3f}')
+    assert ratio <= 1.0, f'{what}: |err| is {ratio:.2f} x its bound at the worst element'
+
+
 def sync():
     torch.cuda.synchronize()

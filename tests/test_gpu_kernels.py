@@ -7,7 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import DEV, L, P, assert_close_bf16, bf, rel_l2, sync
+from gpu_util import DEV, L, P, assert_close_bf16, assert_within, bf, dot_bound, rel_l2, sync
 
 pytestmark = pytest.mark.gpu
 
@@ -388,6 +388,51 @@ def test_conv3x3_direct(Cin, Cout, stride, in_nchw, out_nchw, act):
     sync()
     o = out if out_nchw else out.float().permute(0, 3, 1, 2)
     assert_close_bf16(o, ref, what='conv3x3_direct')
+
+
+# The dispatch arms of launch_conv3x3_direct that only the side networks reach, against float64 on the same rounded inputs:
+#   bf16 NHWC -> fp32 NCHW with Cout 3 (conv3x3_fewout_kernel<3>: the decoder's conv_out), 35 and 48 pixels: a last block of 3 waves,
+#   and Cin 8 where nine lanes of a wave are live;
+#   fp32 NCHW -> bf16 NHWC with Cin 3 / 4 (conv3x3_fewin_kernel<3>, <4>) at 35 pixels (blocks of 16: a last block of 3) and Cout
+#   that is no multiple of 64 (dead threads in the last wave), with every combination of add and act;
+#   and the neighbours across the dispatch bounds, which take the generic kernel: Cin 4 with Cout 63, and Cout 520 (> 512).
+FEWOUT = [(Cin, 3, B, H, W_, 0, 1, 0, 0) for Cin in (128, 8) for B, H, W_ in ((1, 5, 7), (2, 4, 6))]
+FEWIN = [(Cin, Cout, 1, 5, 7, 1, 0, act, add) for Cin, couts in ((3, (8, 100, 512)), (4, (64, 100, 512))) for Cout in couts
+         for act in (0, 1) for add in (0, 1)]
+GENERIC_NEIGHBOURS = [(4, 63, 1, 5, 7, 1, 0, 1, 1), (4, 520, 1, 5, 7, 1, 0, 1, 1), (3, 520, 1, 5, 7, 1, 0, 0, 1), (3, 7, 1, 5, 7, 1, 0, 1, 0)]
+
+
+@pytest.mark.parametrize('Cin,Cout,B,H,W_,in_nchw,out_nchw,act,with_add', FEWOUT + FEWIN + GENERIC_NEIGHBOURS)
+def test_conv3x3_direct_side_network_arms(Cin, Cout, B, H, W_, in_nchw, out_nchw, act, with_add):
+    lib = L()
+    g = torch.Generator().manual_seed(1000 * Cin + Cout + 7 * act + 3 * with_add + B)
+    x = torch.randn(B, Cin, H, W_, generator=g)
+    w = bf(torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(9 * Cin))
+    bias = torch.randn(Cout, generator=g).to(DEV)
+    wp = torch.empty(Cout, 9 * Cin, device=DEV, dtype=torch.bfloat16)
+    assert lib.mkd_pack_conv_weight(P(w.float().contiguous()), P(wp), Cout, Cin, 3, 3, None) == 0
+    if in_nchw:
+        xin = x.to(DEV).contiguous(); xr = x.double()
+    else:
+        xb = bf(x); xin = xb.permute(0, 2, 3, 1).contiguous(); xr = xb.double().cpu()
+    wd, bd = w.double().cpu(), bias.double().cpu()
+    pre = F.conv2d(xr, wd, bd, padding=1)
+    bound = dot_bound(9 * Cin + 1, F.conv2d(xr.abs(), wd.abs(), bd.abs(), padding=1))
+    ref = F.silu(pre) if act else pre
+    add = bf(torch.randn(B, H, W_, Cout, generator=g)) if with_add else None
+    if add is not None:
+        ref = ref + add.double().cpu().permute(0, 3, 1, 2)
+    out = torch.zeros((B, Cout, H, W_) if out_nchw else (B, H, W_, Cout), device=DEV, dtype=torch.float32 if out_nchw else torch.bfloat16)
+    rc = lib.mkd_conv3x3_direct(P(xin), in_nchw, P(wp), P(bias), P(out), out_nchw, act, P(add), B, H, W_, Cin, Cout, 1, None)
+    assert rc == 0, lib.mkd_last_error()
+    sync()
+    what = f'conv3x3_direct {Cin}->{Cout} {B}x{H}x{W_} act {act} add {with_add}'
+    if out_nchw:
+        assert_within(out, ref, bound, what)
+    else:
+        o = out.float().permute(0, 3, 1, 2)
+        assert_close_bf16(o, ref, what=what)
+        assert_within(o, ref, 2.0 ** -8 * ref.abs() + bound, what)
 
 
 def test_ddim_step_matches_reference_formula():
