@@ -532,6 +532,27 @@ int mkd_paste_photo(const mkd_photo_desc* descs, int n, int S, const float* t, c
  * bytes.  1 <= wh, ww <= 2048, w non-null, else MKD_ERR_ARG; everything else as mkd_paste_photo.  One launch. */
 int mkd_paste_photo_weighted(const mkd_photo_desc* descs, int n, int S, const float* t, const float* s01, int feather, const float* w,
                              int wh, int ww, void* stream);
+/* mkd_paste_photo (w == NULL) / mkd_paste_photo_weighted (w != NULL) with the bilinear interpolation of d replaced by JOINT BILATERAL
+ * upsampling under the photo's own edges (Kopf et al. 2007; BUILD-DEFINED): a x5 .. x8 bilinear upsample smears d over a band of photo
+ * pixels across a lip line or the jaw, while the photo's edge sits sharp in the middle of that band; here every tap is also weighted by
+ * how close the luminance of ITS model pixel is to that of the photo pixel.  radius R: 0, 1 or 2; sigma in 8-bit luminance levels,
+ * finite with 0.5 <= sigma <= 1e6; else MKD_ERR_ARG before anything is enqueued.  fp32, every operator below ONE correctly rounded
+ * operation, nothing contracted.  Per model pixel: d_c as in mkd_paste_photo; gb_c = clamp(rintf(s01_c * 255.0f), 0, 255) as an integer
+ * (the crop's byte when s01 comes from mkd_crop_resize); Yl = float(77 gb_r + 150 gb_g + 29 gb_b) (an integer <= 65280).  Per photo
+ * pixel of the box and per axis: the floor quotient q = i0 and the weight w of mkd_paste_photo's axis rule, q NOT clamped (qx, wx, qy,
+ * wy); Yh = float(77 R + 150 G + 29 B) of the pixel's own bytes, read before they are written; inv = 1.0f / (256.0f * sigma);
+ * invT = 1.0f / float(R + 1).  Taps my = -R .. R + 1 (outer), mx = -R .. R + 1 (inner), both ascending; the model pixel read is
+ * (clamp(qy + my, 0, S - 1), clamp(qx + mx, 0, S - 1)) while the spatial weight uses the unclamped offset: per axis
+ * dist = float(m) - w for m >= 1 and w + float(-m) for m <= 0; ws = 1.0f - dist * invT (a tent of half-width R + 1 model pixels about
+ * the sample point; R = 0 gives the bilinear weights).  Per tap: q = (Yh - Yl) * inv (the difference is exact);
+ * wr = 1.0f / (1.0f + q * q) (a Cauchy weight: no exp, never zero); g = (wsy * wsx) * wr; sw = sw + g; sc_c = sc_c + g * d_c, one
+ * accumulator per channel and one for the weights, all starting at +0.  u_c = sc_c / sw; sw > 0 always (taps 0 and 1 of an axis never
+ * both vanish and wr >= 3.8e-6).  The rest is mkd_paste_photo_weighted unchanged: a, a' = a g_plane when w is given,
+ * o = float(photo) + a' u_c, out = uint8(clip(rint(o), 0, 255)).  sigma = 1e6 makes wr 1 to within 2^-24: a tent-weighted average.
+ * One thread per photo pixel; every tap reads t and s01 from the L2-resident tensors.  The only photo bytes a thread reads are the
+ * ones it writes, so the paste is safe in place.  No context; ONE launch, no scratch, no allocation, no host sync, no atomics. */
+int mkd_paste_photo_guided(const mkd_photo_desc* descs, int n, int S, const float* t, const float* s01, int feather, const float* w,
+                           int wh, int ww, int radius, float sigma, void* stream);
 
 /* ---- tilted faces: the photo path along a rotated square (BUILD-DEFINED; the reference aligns nothing, its crops are upright boxes) ---- */
 /* One photo of a batch and an ORIENTED square in it.  pixels, pitch_bytes, H, W, labels: as mkd_photo_desc.  Photo coordinates: pixel
@@ -582,6 +603,16 @@ int mkd_crop_frame(const mkd_photo_frame_desc* descs, int n, int S, float* img01
  * (no launch when that holds for every descriptor).  No context; ONE launch, no scratch, no allocation, no host sync, no atomics. */
 int mkd_paste_frame(const mkd_photo_frame_desc* descs, int n, int S, const float* t, const float* s01, int feather, const float* w,
                     int wh, int ww, void* stream);
+/* mkd_paste_frame with the guided taps of mkd_paste_photo_guided in place of the bilinear interpolation, in IEEE double: per axis
+ * g = ((u + half) / scale) - 0.5; q = floor(g) NOT clamped; w = g - q (mkd_paste_frame's own coordinates).  d_c, gb_c, Yl and Yh are
+ * formed as in mkd_paste_photo_guided (d_c and Yl in fp32) and widened; inv = 1.0 / (256.0 * double(sigma)); invT = 1.0 / double(R + 1);
+ * the taps, their order, dist, ws, q, wr, g, the accumulators and val_c = sc_c / sw are the lines of mkd_paste_photo_guided in double.
+ * Then mkd_paste_frame unchanged: a (all four sides fade), a = a * g_plane when w != NULL, o = double(byte) + a * val_c,
+ * out = uint8(clip(rint(o), 0, 255)); the INSIDE test alone decides which bytes are read and written, and a square that does not
+ * reach its photo writes nothing (no launch when that holds for every descriptor).  radius, sigma and their refusal as in
+ * mkd_paste_photo_guided.  No context; ONE launch, no scratch, no allocation, no host sync, no atomics. */
+int mkd_paste_frame_guided(const mkd_photo_frame_desc* descs, int n, int S, const float* t, const float* s01, int feather, const float* w,
+                           int wh, int ww, int radius, float sigma, void* stream);
 /* Every face's roll and its extent in its own frame.  48 bytes: n_a / n_b = the pixels of the component in the class sets a / b (the
  * two eyes), (cq, sq) = the face's "right" axis as integers of length 16384 (16384, 0: upright), umin .. vmax = the component's extent
  * along that axis and the one across it, in units of 1 / (2 S 16384) photo pixel. */

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(HERE, 'csrc', '_obj')
 LIB = os.path.join(HERE, 'libmkd.so')
 SOURCES = ['kernels_gemm.hip', 'kernels_conv.hip', 'kernels_norm.hip', 'kernels_attn.hip', 'kernels_tfm.hip', 'kernels_misc.hip', 'kernels_hist.hip', 'kernels_region.hip', 'kernels_photo.hip', 'kernels_align.hip', 'kernels_components.hip', 'kernels_parser.hip', 'parser.hip', 'engine.hip', 'api_kernels.hip']
-HEADERS = ['mkd_common.h', 'gemm_device.h', 'parser.h', 'tfm_fold.h', 'gemm_tiles.inc', 'gemm_tuned.inc', os.path.join('..', '..', 'include', 'mkd.h')]
+HEADERS = ['mkd_common.h', 'gemm_device.h', 'parser.h', 'tfm_fold.h', 'paste_guided.h', 'gemm_tiles.inc', 'gemm_tuned.inc', os.path.join('..', '..', 'include', 'mkd.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wall', '-Wno-unused-function', '-Wno-unused-value', '-Wno-unused-result',
          '-ffp-contract=fast']
 

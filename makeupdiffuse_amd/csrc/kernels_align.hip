@@ -6,10 +6,12 @@
 // Crop: one launch, a thread owns one output pixel (its three channels and one weight sum) and walks the photo pixels whose tent
 // weight in the face's frame can be non-zero, Y outer, X inner.  Paste: one launch over the axis-aligned bounding rectangle of the
 // rotated square (one pixel of slack per side, clipped to the photo); a thread owns one photo pixel column of a 64 x 16 tile and tests
-// every pixel against the square itself, so the rectangle decides nothing.  Frames: four launches -- clear the moments, the eye moments
+// every pixel against the square itself, so the rectangle decides nothing; mkd_paste_frame_guided is the same kernel with the
+// four-neighbour interpolation replaced by the guided taps of paste_guided.h, one instantiation per radius.  Frames: four launches -- clear the moments, the eye moments
 // (per workgroup in LDS, then one global 64-bit atomic per non-zero cell), one thread per (image, rank) for the direction, the extents
 // along that direction (64-bit atomic min / max, again per workgroup first).  No workgroup waits for another.
 #include "mkd_common.h"
+#include "paste_guided.h"
 #include "../../include/mkd.h"
 
 #include <limits.h>
@@ -112,20 +114,24 @@ __device__ __forceinline__ void pf_plane_axis(int X, int len, int n, int* i0, in
     *i0 = al_clampi(q, 0, n - 1);
     *i1 = al_clampi(q + 1, 0, n - 1);
 }
-// one axis of the sample: gu = (u + side / 2) / scale - 0.5, its floor (|gu| <= 32 S + 1) and the weight of the upper neighbour
-__device__ __forceinline__ void pf_axis(double u, double half, double scale, int S, int* i0, int* i1, double* w) {
+// one axis of the sample: gu = (u + side / 2) / scale - 0.5, its floor (|gu| <= 32 S + 1; returned, NOT clamped), the clamped
+// neighbours and the weight of the upper one
+__device__ __forceinline__ int pf_axis(double u, double half, double scale, int S, int* i0, int* i1, double* w) {
     const double g = (u + half) / scale - 0.5;
     const double f = floor(g);
     *w = g - f;
     *i0 = al_clampi((int)f, 0, S - 1);
     *i1 = al_clampi((int)f + 1, 0, S - 1);
+    return (int)f;
 }
 __device__ __forceinline__ double pf_lerp(double p, double q, double w) { return p + mkd_rounded_mul(w, q - p); }
 __device__ __forceinline__ double pf_diff(float t, float s) { return mkd_rounded_mul(mkd_rounded_mul((double)t + 1.0, 0.5) - (double)s, 255.0); }
 
-template <bool WEIGHTED>
+// GR >= 0 (mkd_paste_frame_guided, radius GR): val comes from gp_taps (paste_guided.h) in double under the photo pixel's own luminance,
+// inv = 1 / (256 sigma); GR = -1 is the bilinear paste and does not read inv.
+template <bool WEIGHTED, int GR>
 __global__ __launch_bounds__(256) void paste_frame_kernel(const PfArgs a, int S, const float* __restrict__ t, const float* __restrict__ s01, int rho,
-                                                          const float* __restrict__ w, int wh, int ww) {
+                                                          const float* __restrict__ w, int wh, int ww, double inv) {
     const int b = blockIdx.z;
     const int jx = blockIdx.x * PF_TW + (threadIdx.x & (PF_TW - 1));
     if (jx >= a.rw[b]) return;
@@ -154,8 +160,8 @@ __global__ __launch_bounds__(256) void paste_frame_kernel(const PfArgs a, int S,
         if (!(u >= -half && u < half && v >= -half && v < half)) continue;          // outside the square: the byte is not touched
         int c0, c1, r0, r1;
         double wx, wy;
-        pf_axis(u, half, scale, S, &c0, &c1, &wx);
-        pf_axis(v, half, scale, S, &r0, &r1, &wy);
+        const int qx = pf_axis(u, half, scale, S, &c0, &c1, &wx);
+        const int qy = pf_axis(v, half, scale, S, &r0, &r1, &wy);
         const double e = fmin(fmin(u + half, half - u), fmin(v + half, half - v));
         double al = fmin(e + 0.5, fr) / fr;
         if (WEIGHTED) {
@@ -168,17 +174,23 @@ __global__ __launch_bounds__(256) void paste_frame_kernel(const PfArgs a, int S,
             al = mkd_rounded_mul(al, g);
         }
         unsigned char* p = px + (size_t)Y * d.pitch_bytes + (size_t)X * 3;
-        const int o00 = r0 * S + c0, o01 = r0 * S + c1, o10 = r1 * S + c0, o11 = r1 * S + c1;
+        double val[3];
+        if constexpr (GR >= 0) {
+            gp_taps<double, GR>(tb, sb, S, qx, wx, qy, wy, (double)gp_luma(p[0], p[1], p[2]), inv, val);    // (the bytes are read before the writes below)
+        } else {
+            const int o00 = r0 * S + c0, o01 = r0 * S + c1, o10 = r1 * S + c0, o11 = r1 * S + c1;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float* tc = tb + c * plane;
-            const float* sc = sb + c * plane;
-            const double d00 = pf_diff(tc[o00], sc[o00]), d01 = pf_diff(tc[o01], sc[o01]);
-            const double d10 = pf_diff(tc[o10], sc[o10]), d11 = pf_diff(tc[o11], sc[o11]);
-            const double top = pf_lerp(d00, d01, wx), bot = pf_lerp(d10, d11, wx);
-            const double val = pf_lerp(top, bot, wy);
-            p[c] = al_byte((double)p[c] + mkd_rounded_mul(al, val));
+            for (int c = 0; c < 3; ++c) {
+                const float* tc = tb + c * plane;
+                const float* sc = sb + c * plane;
+                const double d00 = pf_diff(tc[o00], sc[o00]), d01 = pf_diff(tc[o01], sc[o01]);
+                const double d10 = pf_diff(tc[o10], sc[o10]), d11 = pf_diff(tc[o11], sc[o11]);
+                const double top = pf_lerp(d00, d01, wx), bot = pf_lerp(d10, d11, wx);
+                val[c] = pf_lerp(top, bot, wy);
+            }
         }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) p[c] = al_byte((double)p[c] + mkd_rounded_mul(al, val[c]));
     }
 }
 
@@ -194,6 +206,56 @@ const char* frame_check(const mkd_photo_frame_desc* descs, int n, int S, bool ne
         return nullptr;
     });
 }
+
+template <int GR>
+void launch_paste_frame(const dim3 grid, hipStream_t stream, const PfArgs& a, int S, const float* t, const float* s01, int feather,
+                        const float* w, int wh, int ww, double inv) {
+    if (w)
+        hipLaunchKernelGGL((paste_frame_kernel<true, GR>), grid, dim3(256), 0, stream, a, S, t, s01, feather, w, wh, ww, inv);
+    else
+        hipLaunchKernelGGL((paste_frame_kernel<false, GR>), grid, dim3(256), 0, stream, a, S, t, s01, feather, w, wh, ww, inv);
+}
+
+// the one launcher of both paste entries: radius < 0 is the bilinear paste (sigma is not read)
+int paste_frame(const std::string who, const mkd_photo_frame_desc* descs, int n, int S, const float* t, const float* s01, int feather,
+                const float* w, int wh, int ww, int radius, float sigma, void* stream) {
+    if (const char* e = frame_check(descs, n, S, false)) return mkd_fail(MKD_ERR_ARG, who + e);
+    if (!t || !s01) return mkd_fail(MKD_ERR_ARG, who + "null t / s01");
+    if (feather < 0 || feather > MKD_PHOTO_MAX_FEATHER) return mkd_fail(MKD_ERR_ARG, who + "feather must be 0..64 photo pixels");
+    if (w && (wh < 1 || ww < 1 || wh > 2048 || ww > 2048)) return mkd_fail(MKD_ERR_ARG, who + "wh, ww must be 1..2048");
+    if (radius >= 0)
+        if (const char* e = gp_check(radius, sigma)) return mkd_fail(MKD_ERR_ARG, who + e);
+    const double inv = radius >= 0 ? 1.0 / (256.0 * (double)sigma) : 0.0;
+    PfArgs a = {};
+    int mw = 0, mh = 0;
+    for (int i = 0; i < n; ++i) {
+        const mkd_photo_frame_desc& d = descs[i];
+        a.d[i] = d;
+        // the square's corners lie within reach of its centre per axis; one pixel of slack, the kernel tests every pixel itself
+        const double reach = d.side * 0.5 * (fabs(d.c) + fabs(d.s));
+        const double x_lo = floor(d.cx - reach) - 1.0, x_hi = floor(d.cx + reach) + 1.0;
+        const double y_lo = floor(d.cy - reach) - 1.0, y_hi = floor(d.cy + reach) + 1.0;
+        const int x0 = (int)(x_lo < 0.0 ? 0.0 : x_lo), x1 = (int)(x_hi > (double)(d.W - 1) ? (double)(d.W - 1) : x_hi);
+        const int y0 = (int)(y_lo < 0.0 ? 0.0 : y_lo), y1 = (int)(y_hi > (double)(d.H - 1) ? (double)(d.H - 1) : y_hi);
+        a.rx0[i] = x0;
+        a.ry0[i] = y0;
+        a.rw[i] = x1 >= x0 && y1 >= y0 ? x1 - x0 + 1 : 0;           // 0: the square does not reach the photo
+        a.rh[i] = x1 >= x0 && y1 >= y0 ? y1 - y0 + 1 : 0;
+        mw = a.rw[i] > mw ? a.rw[i] : mw;
+        mh = a.rh[i] > mh ? a.rh[i] : mh;
+    }
+    if (mw == 0 || mh == 0) return 0;                               // nothing to write
+    const dim3 grid((unsigned)((mw + PF_TW - 1) / PF_TW), (unsigned)((mh + PF_TH - 1) / PF_TH), (unsigned)n);      // y <= 1024
+    switch (radius) {
+        case 0: launch_paste_frame<0>(grid, (hipStream_t)stream, a, S, t, s01, feather, w, wh, ww, inv); break;
+        case 1: launch_paste_frame<1>(grid, (hipStream_t)stream, a, S, t, s01, feather, w, wh, ww, inv); break;
+        case 2: launch_paste_frame<2>(grid, (hipStream_t)stream, a, S, t, s01, feather, w, wh, ww, inv); break;
+        default: launch_paste_frame<-1>(grid, (hipStream_t)stream, a, S, t, s01, feather, w, wh, ww, inv);
+    }
+    MKD_LAUNCH_CHECK("paste_frame_kernel");
+    return 0;
+}
+
 
 // ---- mkd_face_frames -----------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool ff_in(uint8_t l, uint64_t classes) { return l < 64 && ((classes >> l) & 1ull); }
@@ -392,37 +454,13 @@ int mkd_crop_frame(const mkd_photo_frame_desc* descs, int n, int S, float* img01
 
 int mkd_paste_frame(const mkd_photo_frame_desc* descs, int n, int S, const float* t, const float* s01, int feather, const float* w, int wh,
                     int ww, void* stream) {
-    const std::string who = "mkd_paste_frame: ";
-    if (const char* e = frame_check(descs, n, S, false)) return mkd_fail(MKD_ERR_ARG, who + e);
-    if (!t || !s01) return mkd_fail(MKD_ERR_ARG, who + "null t / s01");
-    if (feather < 0 || feather > MKD_PHOTO_MAX_FEATHER) return mkd_fail(MKD_ERR_ARG, who + "feather must be 0..64 photo pixels");
-    if (w && (wh < 1 || ww < 1 || wh > 2048 || ww > 2048)) return mkd_fail(MKD_ERR_ARG, who + "wh, ww must be 1..2048");
-    PfArgs a = {};
-    int mw = 0, mh = 0;
-    for (int i = 0; i < n; ++i) {
-        const mkd_photo_frame_desc& d = descs[i];
-        a.d[i] = d;
-        // the square's corners lie within reach of its centre per axis; one pixel of slack, the kernel tests every pixel itself
-        const double reach = d.side * 0.5 * (fabs(d.c) + fabs(d.s));
-        const double x_lo = floor(d.cx - reach) - 1.0, x_hi = floor(d.cx + reach) + 1.0;
-        const double y_lo = floor(d.cy - reach) - 1.0, y_hi = floor(d.cy + reach) + 1.0;
-        const int x0 = (int)(x_lo < 0.0 ? 0.0 : x_lo), x1 = (int)(x_hi > (double)(d.W - 1) ? (double)(d.W - 1) : x_hi);
-        const int y0 = (int)(y_lo < 0.0 ? 0.0 : y_lo), y1 = (int)(y_hi > (double)(d.H - 1) ? (double)(d.H - 1) : y_hi);
-        a.rx0[i] = x0;
-        a.ry0[i] = y0;
-        a.rw[i] = x1 >= x0 && y1 >= y0 ? x1 - x0 + 1 : 0;           // 0: the square does not reach the photo
-        a.rh[i] = x1 >= x0 && y1 >= y0 ? y1 - y0 + 1 : 0;
-        mw = a.rw[i] > mw ? a.rw[i] : mw;
-        mh = a.rh[i] > mh ? a.rh[i] : mh;
-    }
-    if (mw == 0 || mh == 0) return 0;                               // nothing to write
-    const dim3 grid((unsigned)((mw + PF_TW - 1) / PF_TW), (unsigned)((mh + PF_TH - 1) / PF_TH), (unsigned)n);      // y <= 1024
-    if (w)
-        hipLaunchKernelGGL(paste_frame_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a, S, t, s01, feather, w, wh, ww);
-    else
-        hipLaunchKernelGGL(paste_frame_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a, S, t, s01, feather, w, wh, ww);
-    MKD_LAUNCH_CHECK("paste_frame_kernel");
-    return 0;
+    return paste_frame("mkd_paste_frame: ", descs, n, S, t, s01, feather, w, wh, ww, -1, 0.0f, stream);
+}
+
+int mkd_paste_frame_guided(const mkd_photo_frame_desc* descs, int n, int S, const float* t, const float* s01, int feather, const float* w,
+                           int wh, int ww, int radius, float sigma, void* stream) {
+    if (radius < 0) return mkd_fail(MKD_ERR_ARG, std::string("mkd_paste_frame_guided: ") + gp_check(radius, sigma));
+    return paste_frame("mkd_paste_frame_guided: ", descs, n, S, t, s01, feather, w, wh, ww, radius, sigma, stream);
 }
 
 size_t mkd_face_frames_scratch_bytes(int batch, int max_out) {

@@ -14,7 +14,10 @@
 // d = ((t + 1) 0.5 - s01) 255 is formed on the fly from the L2-resident tensors.  Every fp32 operation is one correctly rounded step:
 // products that feed an addition pass through mkd_rounded (mkd_common.h).
 // mkd_paste_photo_weighted is the same kernel's second instantiation: the feather weight times a bilinear sample of a photo-wide plane.
+// mkd_paste_photo_guided is the same kernel with the four-neighbour interpolation replaced by the guided taps of paste_guided.h, one
+// instantiation per radius.
 #include "mkd_common.h"
+#include "paste_guided.h"
 #include "../../include/mkd.h"
 
 namespace {
@@ -178,19 +181,20 @@ __global__ __launch_bounds__(64) void resize_coeffs_kernel(int n, int in0, int l
     bounds_out[2 * xx + 1] = xmin + cnt;
 }
 
-// one axis of the paste's interpolation: neighbours i0, i1 (clamped) and the weight of i1
-__device__ __forceinline__ void pp_axis(int j, int len, int S, int* i0, int* i1, float* w) {
+// one axis of the paste's interpolation: the floor quotient (NOT clamped) and the weight of its upper neighbour
+__device__ __forceinline__ int pp_axis_floor(int j, int len, int S, float* w) {
     const int num = (2 * j + 1) * S - len, den = 2 * len;            // |num| < 2^27
     int q = num / den;
     if (num < 0 && q * den != num) --q;                              // floor
     const int rem = num - q * den;                                   // 0 .. den - 1 <= 32767: exact in fp32
     *w = __fdiv_rn((float)rem, (float)den);
+    return q;
+}
+// neighbours i0, i1 (clamped) and the weight of i1
+__device__ __forceinline__ void pp_axis(int j, int len, int S, int* i0, int* i1, float* w) {
+    const int q = pp_axis_floor(j, len, S, w);
     *i0 = min(max(q, 0), S - 1);
     *i1 = min(max(q + 1, 0), S - 1);
-}
-__device__ __forceinline__ float pp_diff(float t, float s) {
-    const float r = mkd_rounded(__fmul_rn(__fadd_rn(t, 1.0f), 0.5f));
-    return mkd_rounded(__fmul_rn(__fsub_rn(r, s), 255.0f));
 }
 __device__ __forceinline__ float pp_lerp(float a, float b, float w) {
     return __fadd_rn(a, mkd_rounded(__fmul_rn(w, __fsub_rn(b, a))));
@@ -198,9 +202,11 @@ __device__ __forceinline__ float pp_lerp(float a, float b, float w) {
 
 // WEIGHTED (mkd_paste_photo_weighted): the feather weight is multiplied by g, the bilinear sample of the photo-wide weight plane
 // w [n][wh][ww] at the photo pixel (pp_axis on the photo's own axes); w, wh and ww are not read otherwise.
-template <bool WEIGHTED>
+// GR >= 0 (mkd_paste_photo_guided, radius GR): u comes from gp_taps under the photo pixel's own luminance, inv = 1 / (256 sigma);
+// GR = -1 is the bilinear paste and does not read inv.
+template <bool WEIGHTED, int GR>
 __global__ __launch_bounds__(256) void paste_photo_kernel(const PpArgs a, int S, const float* __restrict__ t, const float* __restrict__ s01,
-                                                          int rho, const float* __restrict__ w, int wh, int ww) {
+                                                          int rho, const float* __restrict__ w, int wh, int ww, float inv) {
     const int b = blockIdx.z;
     const mkd_photo_desc d = a.d[b];
     const int j = blockIdx.x * PP_TW + (threadIdx.x & (PP_TW - 1));
@@ -208,6 +214,7 @@ __global__ __launch_bounds__(256) void paste_photo_kernel(const PpArgs a, int S,
     int x0i, x1i;
     float wx;
     pp_axis(j, d.bw, S, &x0i, &x1i, &wx);
+    const int qx = GR >= 0 ? pp_axis_floor(j, d.bw, S, &wx) : 0;
     const int big = 1 << 30;
     int ex = big;
     if (d.x0 > 0) ex = j;
@@ -230,6 +237,7 @@ __global__ __launch_bounds__(256) void paste_photo_kernel(const PpArgs a, int S,
         int y0i, y1i;
         float wy;
         pp_axis(i, d.bh, S, &y0i, &y1i, &wy);
+        const int qy = GR >= 0 ? pp_axis_floor(i, d.bh, S, &wy) : 0;
         int e = ex;
         if (top_counts) e = min(e, i);
         if (bottom_counts) e = min(e, d.bh - 1 - i);
@@ -244,16 +252,24 @@ __global__ __launch_bounds__(256) void paste_photo_kernel(const PpArgs a, int S,
             al = mkd_rounded(__fmul_rn(al, g));
         }
         unsigned char* p = px + (size_t)(d.y0 + i) * d.pitch_bytes + (size_t)(d.x0 + j) * 3;
-        const int o00 = y0i * S + x0i, o01 = y0i * S + x1i, o10 = y1i * S + x0i, o11 = y1i * S + x1i;
+        float u[3];
+        if constexpr (GR >= 0) {
+            gp_taps<float, GR>(tb, sb, S, qx, wx, qy, wy, (float)gp_luma(p[0], p[1], p[2]), inv, u);         // (the bytes are read before the writes below)
+        } else {
+            const int o00 = y0i * S + x0i, o01 = y0i * S + x1i, o10 = y1i * S + x0i, o11 = y1i * S + x1i;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float* tc = tb + c * plane;
+                const float* sc = sb + c * plane;
+                const float d00 = pp_diff(tc[o00], sc[o00]), d01 = pp_diff(tc[o01], sc[o01]);
+                const float d10 = pp_diff(tc[o10], sc[o10]), d11 = pp_diff(tc[o11], sc[o11]);
+                const float top = pp_lerp(d00, d01, wx), bot = pp_lerp(d10, d11, wx);
+                u[c] = pp_lerp(top, bot, wy);
+            }
+        }
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const float* tc = tb + c * plane;
-            const float* sc = sb + c * plane;
-            const float d00 = pp_diff(tc[o00], sc[o00]), d01 = pp_diff(tc[o01], sc[o01]);
-            const float d10 = pp_diff(tc[o10], sc[o10]), d11 = pp_diff(tc[o11], sc[o11]);
-            const float top = pp_lerp(d00, d01, wx), bot = pp_lerp(d10, d11, wx);
-            const float u = pp_lerp(top, bot, wy);
-            const float o = __fadd_rn((float)p[c], mkd_rounded(__fmul_rn(al, u)));
+            const float o = __fadd_rn((float)p[c], mkd_rounded(__fmul_rn(al, u[c])));
             p[c] = (unsigned char)fminf(fmaxf(rintf(o), 0.0f), 255.0f);
         }
     }
@@ -276,12 +292,25 @@ size_t slab_bytes(const mkd_photo_desc& d, int S) {
     return ((size_t)rows * S * 3 + 255) & ~(size_t)255;
 }
 
-// the one launcher of both paste entries: w == nullptr is mkd_paste_photo
+template <int GR>
+void launch_paste(const dim3 grid, hipStream_t stream, const PpArgs& a, int S, const float* t, const float* s01, int feather, const float* w,
+                  int wh, int ww, float inv) {
+    if (w)
+        hipLaunchKernelGGL((paste_photo_kernel<true, GR>), grid, dim3(256), 0, stream, a, S, t, s01, feather, w, wh, ww, inv);
+    else
+        hipLaunchKernelGGL((paste_photo_kernel<false, GR>), grid, dim3(256), 0, stream, a, S, t, s01, feather, w, wh, ww, inv);
+}
+
+// the one launcher of the paste entries: w == nullptr is no weight plane, radius < 0 the bilinear paste (sigma is not read)
 int paste_photo(const char* who, const mkd_photo_desc* descs, int n, int S, const float* t, const float* s01, int feather, const float* w,
-                int wh, int ww, void* stream) {
+                int wh, int ww, int radius, float sigma, void* stream) {
     if (int rc = check_descs(who, descs, n, S, false)) return rc;
     if (!t || !s01) return mkd_fail(-1, std::string(who) + ": null t / s01");
     if (feather < 0 || feather > MKD_PHOTO_MAX_FEATHER) return mkd_fail(-1, std::string(who) + ": feather must be 0..64 photo pixels");
+    if (w && (wh < 1 || ww < 1 || wh > 2048 || ww > 2048)) return mkd_fail(-1, std::string(who) + ": wh, ww must be 1..2048");
+    if (radius >= 0)
+        if (const char* e = gp_check(radius, sigma)) return mkd_fail(MKD_ERR_ARG, std::string(who) + ": " + e);
+    const float inv = radius >= 0 ? 1.0f / (256.0f * sigma) : 0.0f;
     PpArgs a = {};
     int mw = 0, mh = 0;
     for (int i = 0; i < n; ++i) {
@@ -290,10 +319,12 @@ int paste_photo(const char* who, const mkd_photo_desc* descs, int n, int S, cons
         mh = descs[i].bh > mh ? descs[i].bh : mh;
     }
     const dim3 grid((unsigned)((mw + PP_TW - 1) / PP_TW), (unsigned)((mh + PP_TH - 1) / PP_TH), (unsigned)n);      // y <= 1024
-    if (w)
-        hipLaunchKernelGGL(paste_photo_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a, S, t, s01, feather, w, wh, ww);
-    else
-        hipLaunchKernelGGL(paste_photo_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a, S, t, s01, feather, w, wh, ww);
+    switch (radius) {
+        case 0: launch_paste<0>(grid, (hipStream_t)stream, a, S, t, s01, feather, w, wh, ww, inv); break;
+        case 1: launch_paste<1>(grid, (hipStream_t)stream, a, S, t, s01, feather, w, wh, ww, inv); break;
+        case 2: launch_paste<2>(grid, (hipStream_t)stream, a, S, t, s01, feather, w, wh, ww, inv); break;
+        default: launch_paste<-1>(grid, (hipStream_t)stream, a, S, t, s01, feather, w, wh, ww, inv);
+    }
     MKD_LAUNCH_CHECK("paste_photo_kernel");
     return 0;
 }
@@ -347,14 +378,20 @@ int mkd_resize_coeffs(int N, int in0, int len, int S, int32_t* bounds_out, int32
 }
 
 int mkd_paste_photo(const mkd_photo_desc* descs, int n, int S, const float* t, const float* s01, int feather, void* stream) {
-    return paste_photo("mkd_paste_photo", descs, n, S, t, s01, feather, nullptr, 0, 0, stream);
+    return paste_photo("mkd_paste_photo", descs, n, S, t, s01, feather, nullptr, 0, 0, -1, 0.0f, stream);
 }
 
 int mkd_paste_photo_weighted(const mkd_photo_desc* descs, int n, int S, const float* t, const float* s01, int feather, const float* w,
                              int wh, int ww, void* stream) {
     if (!w) return mkd_fail(-1, "mkd_paste_photo_weighted: null w");
     if (wh < 1 || ww < 1 || wh > 2048 || ww > 2048) return mkd_fail(-1, "mkd_paste_photo_weighted: wh, ww must be 1..2048");
-    return paste_photo("mkd_paste_photo_weighted", descs, n, S, t, s01, feather, w, wh, ww, stream);
+    return paste_photo("mkd_paste_photo_weighted", descs, n, S, t, s01, feather, w, wh, ww, -1, 0.0f, stream);
+}
+
+int mkd_paste_photo_guided(const mkd_photo_desc* descs, int n, int S, const float* t, const float* s01, int feather, const float* w, int wh,
+                           int ww, int radius, float sigma, void* stream) {
+    if (radius < 0) return mkd_fail(MKD_ERR_ARG, std::string("mkd_paste_photo_guided: ") + gp_check(radius, sigma));
+    return paste_photo("mkd_paste_photo_guided", descs, n, S, t, s01, feather, w, wh, ww, radius, sigma, stream);
 }
 
 }  // extern "C"

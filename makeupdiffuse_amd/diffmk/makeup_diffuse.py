@@ -842,7 +842,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                         x_T: Optional[torch.Tensor] = None, size: int = 256, batch: Optional[dict] = None,
                         guidance_rescale: Optional[float] = None, max_faces: Optional[int] = None, face_batch: int = 8,
                         return_faces: bool = False, own_pixels: bool = False, own_feather: int = 2, align: bool = False,
-                        min_roll: float = 5.0):
+                        min_roll: float = 5.0, guided_paste=None):
         """Makeup transfer on photographs at their own resolution: ``src_photos`` / ``ref_photos`` are uint8 [H,W,3] tensors of any
         size (lists; the photos of a call may differ in size) with a face box (x0, y0, w, h) each.  Both boxes are crop-resized to
         ``size`` on the device (photo.crop_resize: Pillow's antialiased bilinear bytes / 255, what PairFolderDataset gives for that
@@ -885,13 +885,19 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         boxes that carry the roll as a fifth entry, (x0, y0, w, h, angle_deg) with w == h (a 4-tuple, or angle 0, is an upright box;
         a photo.Frame instance is taken as it is).
         An upright face takes the crop_resize / paste_photos calls above, so a batch without a rolled face is the path above call for
-        call.  ``return_faces`` then gives boxes for caller boxes that are upright and photo.Frame's for everything else."""
+        call.  ``return_faces`` then gives boxes for caller boxes that are upright and photo.Frame's for everything else.
+
+        ``guided_paste`` (a photo.GuidedPaste; None: everything above, call for call): EVERY paste of the call -- single face, max_faces,
+        own_pixels, align -- upsamples the makeup difference under the photo's own luminance edges instead of bilinearly
+        (mkd_paste_photo_guided / mkd_paste_frame_guided), so lipstick stops at the lip line of the PHOTO and not a model pixel past it."""
         from .. import photo
         from ..components import owner_weights
         from ..face_parser import find_boxes, find_faces
         phi = float(self.guidance_rescale if guidance_rescale is None else guidance_rescale)
         if not 0.0 <= phi <= 1.0:
             raise ValueError(f'guidance_rescale must lie in [0, 1], got {phi}')
+        if guided_paste is not None and not isinstance(guided_paste, photo.GuidedPaste):
+            raise ValueError(f'guided_paste must be a photo.GuidedPaste or None, got {guided_paste!r}')
         # One body for both forms, on regions (boxes or photo.Frame's): the call without max_faces is one face per photo and one chunk
         # of all photos.  Every check comes before the engine is required.
         many = max_faces is not None
@@ -1021,7 +1027,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                     rows = (img[at], src[at])
                 # own_pixels: rank k of photo i is row k of its table, the weight that row's share of every neighbourhood
                 weights = None if owner is None else owner_weights(owner, [(items[j][0], rank) for j in sel], own_feather)
-                eng.paste_regions([out[items[j][0]] for j in sel], [faces[items[j][0]][rank] for j in sel], *rows, feather, weights)
+                eng.paste_regions([out[items[j][0]] for j in sel], [faces[items[j][0]][rank] for j in sel], *rows, feather, weights, guided_paste)
         return (out, faces) if return_faces else out
 
     def test_step(self, batch: dict, batch_idx: int, x_T: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:

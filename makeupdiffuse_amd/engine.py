@@ -1020,12 +1020,13 @@ class MkdEngine:
         from . import photo
         return photo.crop_resize(self._to_dev(photos, 3), boxes, size, labels=self._to_dev(labels, 2), want_u8=want_u8)
 
-    def paste_photos(self, photos, boxes, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None):
+    def paste_photos(self, photos, boxes, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None,
+                     guided=None):
         """Full-resolution photos out (include/mkd.h mkd_paste_photo; photo.paste_photos): the decoded samples pasted into the
         device photos IN PLACE, inside their boxes, with the photos' fine detail kept.  ``weights`` [B,wh,ww]: one photo-wide weight
         plane per photo (mkd_paste_photo_weighted)."""
         from . import photo
-        return photo.paste_photos(photos, boxes, samples, src01, feather, weights)
+        return photo.paste_photos(photos, boxes, samples, src01, feather, weights, guided)
 
     def crop_regions(self, photos, regions, size: int, labels=None):
         """crop_resize for a batch whose regions may be photo.Frame's (photo.crop_regions on this engine's device): a rolled frame is
@@ -1033,10 +1034,11 @@ class MkdEngine:
         from . import photo
         return photo.crop_regions(self._to_dev(photos, 3), regions, size, labels=self._to_dev(labels, 2))
 
-    def paste_regions(self, photos, regions, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None):
+    def paste_regions(self, photos, regions, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None,
+                      guided=None):
         """paste_photos for a batch whose regions may be photo.Frame's (photo.paste_regions; include/mkd.h mkd_paste_frame)"""
         from . import photo
-        return photo.paste_regions(photos, regions, samples, src01, feather, weights)
+        return photo.paste_regions(photos, regions, samples, src01, feather, weights, guided)
 
     def eps_profile(self, x: torch.Tensor, t: torch.Tensor, csv_path: Optional[str] = None) -> Dict[str, Dict[str, float]]:
         """One eps with HIP events around every launch group -> {kernel class: {ms, flops, launches, bytes, ms_b2b}}: ``bytes`` =

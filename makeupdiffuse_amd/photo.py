@@ -32,6 +32,27 @@ Cropped = namedtuple('Cropped', 'img01 labels u8')
 # an oriented square: centre and side in photo pixels (pixel (X, Y) has its centre at (X + .5, Y + .5)), (c, s) the unit vector of the
 # face's "right" axis; (-s, c) is its "down" axis and c = 1, s = 0 is upright (include/mkd.h mkd_photo_frame_desc)
 Frame = namedtuple('Frame', 'cx cy side c s')
+GUIDE_RADII = (0, 1, 2)
+GUIDE_SIGMA_MIN, GUIDE_SIGMA_MAX = 0.5, 1e6
+
+
+class GuidedPaste(namedtuple('GuidedPaste', 'radius sigma')):
+    """Edge-aware paste (include/mkd.h mkd_paste_photo_guided / mkd_paste_frame_guided): the makeup difference is brought up to the
+    photo by joint bilateral upsampling under the photo's own luminance instead of bilinearly, so it stops at the photo's edges.
+    ``radius`` 0, 1 or 2: the taps reach radius + 1 model pixels per side; ``sigma``: the luminance distance, in 8-bit levels
+    (0.5 .. 1e6), at which a tap's weight has fallen to a half."""
+    __slots__ = ()
+
+    def __new__(cls, radius: int = 1, sigma: float = 8.0):
+        if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or int(radius) not in GUIDE_RADII:
+            raise ValueError(f'GuidedPaste: radius must be 0, 1 or 2, got {radius!r}')
+        try:
+            sg = float(sigma)
+        except (TypeError, ValueError):
+            sg = math.nan
+        if not (math.isfinite(sg) and GUIDE_SIGMA_MIN <= sg <= GUIDE_SIGMA_MAX):
+            raise ValueError(f'GuidedPaste: sigma must be a finite number of luminance levels in [{GUIDE_SIGMA_MIN}, {GUIDE_SIGMA_MAX:g}], got {sigma!r}')
+        return super().__new__(cls, int(radius), sg)
 
 
 def _stream() -> int:
@@ -237,17 +258,27 @@ def _crop_frame(lib, arr, n, S, img01, u8, lab_out):
     _lib.check(lib.mkd_crop_frame(arr, n, S, _ptr(img01), _ptr(u8), _ptr(lab_out), C.c_void_p(_stream())), 'mkd_crop_frame')
 
 
-def _paste_box(lib, arr, n, S, t, s, rho, w):
-    if w is None:
+def _plane(w):
+    return (_ptr(w), 0, 0) if w is None else (_ptr(w), int(w.shape[1]), int(w.shape[2]))
+
+
+def _paste_box(lib, arr, n, S, t, s, rho, w, guided):
+    if guided is not None:
+        _lib.check(lib.mkd_paste_photo_guided(arr, n, S, _ptr(t), _ptr(s), rho, *_plane(w), guided.radius, guided.sigma, C.c_void_p(_stream())),
+                   'mkd_paste_photo_guided')
+    elif w is None:
         _lib.check(lib.mkd_paste_photo(arr, n, S, _ptr(t), _ptr(s), rho, C.c_void_p(_stream())), 'mkd_paste_photo')
     else:
         _lib.check(lib.mkd_paste_photo_weighted(arr, n, S, _ptr(t), _ptr(s), rho, _ptr(w), int(w.shape[1]), int(w.shape[2]), C.c_void_p(_stream())),
                    'mkd_paste_photo_weighted')
 
 
-def _paste_frame(lib, arr, n, S, t, s, rho, w):
-    _lib.check(lib.mkd_paste_frame(arr, n, S, _ptr(t), _ptr(s), rho, _ptr(w), 0 if w is None else int(w.shape[1]), 0 if w is None else int(w.shape[2]),
-                                   C.c_void_p(_stream())), 'mkd_paste_frame')
+def _paste_frame(lib, arr, n, S, t, s, rho, w, guided):
+    if guided is not None:
+        _lib.check(lib.mkd_paste_frame_guided(arr, n, S, _ptr(t), _ptr(s), rho, *_plane(w), guided.radius, guided.sigma, C.c_void_p(_stream())),
+                   'mkd_paste_frame_guided')
+    else:
+        _lib.check(lib.mkd_paste_frame(arr, n, S, _ptr(t), _ptr(s), rho, *_plane(w), C.c_void_p(_stream())), 'mkd_paste_frame')
 
 
 def _fill_box(d, box):
@@ -301,10 +332,18 @@ def _crop(kind: _Kind, photos, regions, size: int, labels, want_u8: bool) -> Cro
     return Cropped(img01, lab_out, u8)
 
 
-def _paste(kind: _Kind, photos, regions, samples: torch.Tensor, src01: torch.Tensor, feather: int, weights: Optional[torch.Tensor]):
-    # one order of checks for both kinds: feather, photos, counts and shapes, weights, size, regions, rows.  Against the two copies this
-    # replaces, paste_frames now looks at the feather before the photos, and paste_photos at the weights before the boxes and rows
+def _check_guided(guided) -> Optional[GuidedPaste]:
+    if guided is not None and not isinstance(guided, GuidedPaste):
+        raise ValueError(f'guided must be a photo.GuidedPaste or None, got {guided!r}')
+    return guided
+
+
+def _paste(kind: _Kind, photos, regions, samples: torch.Tensor, src01: torch.Tensor, feather: int, weights: Optional[torch.Tensor],
+           guided: Optional[GuidedPaste] = None):
+    # one order of checks for both kinds: feather, guided, photos, counts and shapes, weights, size, regions, rows.  Against the two copies
+    # this replaces, paste_frames now looks at the feather before the photos, and paste_photos at the weights before the boxes and rows
     rho = _check_feather(feather)
+    guided = _check_guided(guided)
     plist = _photo_list(photos, kind.paste_name)
     S = _check_paste(kind.noun, plist, regions, samples, src01, weights)
     B = len(plist)
@@ -320,7 +359,8 @@ def _paste(kind: _Kind, photos, regions, samples: torch.Tensor, src01: torch.Ten
     with torch.cuda.device(dev):
         for b0 in range(0, B, MAX_BATCH):
             b1 = min(B, b0 + MAX_BATCH)
-            kind.paste(lib, _descs(kind, plist[b0:b1], regions[b0:b1], None), b1 - b0, S, t[b0:b1], s[b0:b1], rho, None if w is None else w[b0:b1])
+            kind.paste(lib, _descs(kind, plist[b0:b1], regions[b0:b1], None), b1 - b0, S, t[b0:b1], s[b0:b1], rho, None if w is None else w[b0:b1],
+                       guided)
     return photos
 
 
@@ -332,15 +372,17 @@ def crop_resize(photos, boxes, size: int, labels=None, want_u8: bool = False) ->
     return _crop(_BOX, photos, boxes, size, labels, want_u8)
 
 
-def paste_photos(photos, boxes, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None):
+def paste_photos(photos, boxes, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None,
+                 guided: Optional[GuidedPaste] = None):
     """The decoded ``samples`` (fp32 [B,3,S,S], nominally [-1, 1]) back into ``photos`` IN PLACE, inside their boxes only:
     photo + a * upsampled((samples + 1) / 2 - src01) * 255, rounded to uint8 (ties to even), where src01 is the img01 the model saw
     (crop_resize of the same photos and boxes) and a fades from 1 / (feather + 1) at a box side to 1 over ``feather`` photo pixels
     (sides on the photo's border do not fade).  Only the difference is interpolated, so everything finer than the model's grid stays
     the photo's own.  ``weights`` (fp32 [B,wh,ww], wh, ww <= 2048; mkd_paste_photo_weighted): plane b covers the WHOLE of photo b at
     low resolution and a is multiplied by its bilinear sample at the photo pixel (components.owner_weights: each face's paste stays
-    on its own pixels); a weight of 0 leaves the photo's byte.  Returns ``photos``."""
-    return _paste(_BOX, photos, boxes, samples, src01, feather, weights)
+    on its own pixels); a weight of 0 leaves the photo's byte.  ``guided`` (a GuidedPaste; mkd_paste_photo_guided): the difference is
+    upsampled under the photo's own luminance edges instead of bilinearly; None makes exactly the calls above.  Returns ``photos``."""
+    return _paste(_BOX, photos, boxes, samples, src01, feather, weights, guided)
 
 
 def crop_frames(photos, frames, size: int, labels=None, want_u8: bool = False) -> Cropped:
@@ -352,13 +394,14 @@ def crop_frames(photos, frames, size: int, labels=None, want_u8: bool = False) -
     return _crop(_FRAME, photos, frames, size, labels, want_u8)
 
 
-def paste_frames(photos, frames, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None):
+def paste_frames(photos, frames, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None,
+                 guided: Optional[GuidedPaste] = None):
     """paste_photos along ROTATED squares (mkd_paste_frame), IN PLACE: every photo pixel whose centre lies in its Frame gets
     photo + a * g * bilinear((samples + 1) / 2 - src01) * 255 sampled at its place in the frame, in double; a fades over ``feather``
     photo pixels at ALL four sides of the square, g is the bilinear sample of ``weights`` (fp32 [B,wh,ww] over the whole photo, as in
-    paste_photos) or 1.  Bytes outside the square, and everything of a square that does not reach its photo, stay.  Returns
-    ``photos``."""
-    return _paste(_FRAME, photos, frames, samples, src01, feather, weights)
+    paste_photos) or 1.  Bytes outside the square, and everything of a square that does not reach its photo, stay.  ``guided`` as in
+    paste_photos (mkd_paste_frame_guided).  Returns ``photos``."""
+    return _paste(_FRAME, photos, frames, samples, src01, feather, weights, guided)
 
 
 def split_regions(regions):
@@ -396,20 +439,23 @@ def crop_regions(photos, regions, size: int, labels=None) -> Cropped:
     return Cropped(merge(cb.img01, cf.img01), merge(cb.labels, cf.labels), None)
 
 
-def paste_regions(photos, regions, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None):
+def paste_regions(photos, regions, samples: torch.Tensor, src01: torch.Tensor, feather: int = 8, weights: Optional[torch.Tensor] = None,
+                  guided: Optional[GuidedPaste] = None):
     """paste_photos for boxes and paste_frames for rolled Frames in one batch (a photo appears once per call, so the split changes
-    nothing).  Without a rolled Frame this is exactly ONE paste_photos call on the whole batch."""
+    nothing).  Without a rolled Frame this is exactly ONE paste_photos call on the whole batch.  ``guided`` goes to both."""
+    _check_guided(guided)
     plist = _photo_list(photos, 'paste_regions')
     if len(regions) != len(plist):
         raise ValueError(f'{len(plist)} photos but {len(regions)} regions')
     bi, boxes, fi, frames = split_regions(regions)
     if not fi:
-        paste_photos(plist, boxes, samples, src01, feather, weights)
+        paste_photos(plist, boxes, samples, src01, feather, weights, guided)
         return photos
     for idx, regs, fn in ((bi, boxes, paste_photos), (fi, frames, paste_frames)):
         if idx:
             at = torch.tensor(idx, device=samples.device)
-            fn([plist[i] for i in idx], regs, samples[at], src01[at], feather, None if weights is None else weights[at.to(weights.device)])
+            fn([plist[i] for i in idx], regs, samples[at], src01[at], feather, None if weights is None else weights[at.to(weights.device)],
+               guided)
     return photos
 
 

@@ -111,6 +111,12 @@ def build_parser():
     ap.add_argument('--min-roll', type=float, default=5.0, metavar='DEG', help='with --align-faces: a face found by the parser whose measured '
                     'roll is below DEG degrees keeps its axis-aligned box')
     ap.add_argument('--photo-feather', type=int, default=8, help='fade the pasted face in over this many photo pixels at the box sides, 0..64')
+    ap.add_argument('--guided-paste', action='store_true', help='with --photos: edge-aware paste -- the makeup difference is brought up to the '
+                    'photo by joint bilateral upsampling under the photo\'s own luminance edges instead of bilinearly '
+                    '(mkd_paste_photo_guided / mkd_paste_frame_guided), in every paste of the run')
+    ap.add_argument('--guide-radius', type=int, default=1, metavar='R', help='with --guided-paste: the taps reach R + 1 model pixels per side, 0..2')
+    ap.add_argument('--guide-sigma', type=float, default=8.0, metavar='S', help='with --guided-paste: the luminance distance, in 8-bit levels '
+                    '(0.5 .. 1e6), at which a tap\'s weight has fallen to a half')
     ap.add_argument('--face-parser', default=None, metavar='PATH|random', help='attach the face-parsing network (upstream face-parsing.PyTorch '
                     'state dict, e.g. 79999_iter.pth; "random": seeded random weights, for plumbing runs): label maps that --fix-background, '
                     '--paste-background, --makeup-score, --region-refs and --photos need and <data-root>/scgan_segs does not give are parsed '
@@ -215,6 +221,17 @@ def main():
         raise SystemExit('--photo-feather must be 0..64 photo pixels')
     if args.photo_feather != 8 and not args.photos:
         raise SystemExit('--photo-feather only applies with --photos')
+    guided = None
+    if args.guided_paste:
+        if not args.photos:
+            raise SystemExit('--guided-paste only applies with --photos')
+        from makeupdiffuse_amd.photo import GuidedPaste
+        try:
+            guided = GuidedPaste(args.guide_radius, args.guide_sigma)
+        except ValueError as e:
+            raise SystemExit(f'--guide-radius / --guide-sigma: {e}')
+    elif args.guide_radius != 1 or args.guide_sigma != 8.0:
+        raise SystemExit('--guide-radius / --guide-sigma only apply with --guided-paste')
     if args.log_every_t < 1:
         raise SystemExit('--log-every-t must be >= 1')
     if args.log_every_t != 100 and not args.denoise_rows:
@@ -325,7 +342,8 @@ def main():
             find = bool(args.face_parser) and not photo_ds.boxes          # no boxes file: the parser finds the faces
             if args.max_faces is None:
                 photos = model.transfer_photos(items['src_photo'], items['ref_photo'], None if find else items['src_box'], None if find else items['ref_box'],
-                                               src_segs=items.get('src_seg'), feather=args.photo_feather, x_T=x_T, size=args.res, batch=text)
+                                               src_segs=items.get('src_seg'), feather=args.photo_feather, x_T=x_T, size=args.res, batch=text,
+                                               guided_paste=guided)
             else:
                 K = args.max_faces
                 ref_boxes = items['ref_box']
@@ -351,8 +369,10 @@ def main():
                 # (--own-pixels: the model finds the same faces again, with their owner map; the count above sizes the start latents)
                 photos, faces = model.transfer_photos(items['src_photo'], items['ref_photo'], None if args.own_pixels else faces, ref_boxes,
                                                       src_segs=items.get('src_seg'), feather=args.photo_feather, x_T=x_F, size=args.res, batch=text,
-                                                      max_faces=K, return_faces=True, **own)
+                                                      max_faces=K, return_faces=True, guided_paste=guided, **own)
                 print(f'[rank {rank}] faces per photo: {[len(f) for f in faces]}', flush=True)
+            if guided is not None:
+                print(f'[rank {rank}] guided paste: radius {guided.radius}, sigma {guided.sigma:g}', flush=True)
             os.makedirs(os.path.join(args.out, 'photos'), exist_ok=True)
             for name, img in zip(items['img_name'], photos):
                 Image.fromarray(img.cpu().numpy()).save(os.path.join(args.out, 'photos', name + '.png'))
