@@ -312,6 +312,52 @@ int mkd_sample_dpmpp(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, con
 int mkd_sample_dpmpp_ex(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
                         const float* alphas_prev, int order, int lower_order_final, const mkd_sample_mask* m,
                         const mkd_sample_extras* ex, float cfg_scale, float* x_out, int use_graph, void* stream);
+/* ---- UniPC predictor-corrector sampler (Zhao et al. 2023; data prediction, the "bh2" form; BUILD-DEFINED: DESIGN.md §0) -------- */
+/* Deterministic, on the same step grid, tables and notation as the DPM-Solver++ entries above.  Grid point k = 0 .. n_steps-1 is the
+ * evaluation of executed step k (table entry i = n_steps-1-k, lambda_k from alphas[i]); grid point n_steps is alphas_prev[0].  The
+ * corrector walks from one evaluation point to the next, so the table must be contiguous: alphas_prev[i] == alphas[i-1] for i >= 1.
+ * With psi_0(h) = 1 - e^-h, psi_j(h) = h^j / j! - psi_{j-1}(h), one update goes from a base s (state x_s, x0-prediction m_s) to lambda_t,
+ * h = lambda_t - lambda_s, over q nodes at r_j = (lambda_node_j - lambda_s) / h with d_j = m_node_j - m_s:
+ *   U = (sigma_t / sigma_s) x_s + alpha_t (psi_0 m_s + sum_j w_j d_j),   sum_j w_j r_j^i = i! psi_i / h^i  (i = 1 .. q)
+ * (exact for an m that is a polynomial of degree q in lambda), except q = 1, where w = psi_0 / (2 r_1): the DPM-Solver++ 2M step as a
+ * predictor, and w = psi_0 / 2 for the corrector, whose one node is the new point at r = 1.  Executed step k, with x~_0 = x_T:
+ *   1. m_k = (x~_k - sigma_k e_k) / alpha_k, e_k the (guided, possibly rescaled) eps at x~_k
+ *   2. k >= 1 and the corrector on: x^c_k = U from base k-1 (x^c_{k-1}, m_{k-1}) to lambda_k over the p_{k-1} - 1 evaluations before
+ *      k-1 and m_k at r = 1; otherwise x^c_k = x~_k
+ *   3. x~_{k+1} = U from base k (x^c_k, m_k) to lambda_{k+1} over the p_k - 1 previous evaluations
+ * p_k = min(order, k + 1), and with lower_order_final != 0 and n_steps < 10 also at most n_steps - k.  The result is x~_{n_steps}: the
+ * corrector re-uses the evaluation the next step needs anyway, and there is none after the last one.  As linear forms:
+ *   x^c_k = a_c x^c_{k-1} + q_0 m_k + q_1 m_{k-1} + q_2 m_{k-2} + q_3 m_{k-3}        (a_c == 0: no corrector, x^c_k = x~_k)
+ *   x~_{k+1} = a_p x^c_k + p_0 m_k + p_1 m_{k-1} + p_2 m_{k-2}
+ *
+ * mkd_unipc_table: HOST only (no device, no context).  out [n_steps][12] = 1/alpha, sigma, a_c, q_0 .. q_3, a_p, p_0 .. p_2, 0 of table
+ * entry i, computed in double and stored as float; step_order [n_steps] (may be NULL) = p_k of entry i.  MKD_ERR_ARG: order outside 1..3,
+ * an alpha outside (0, 1), a table that is not contiguous, lambda not increasing along the executed steps. */
+int mkd_unipc_table(int n_steps, const float* alphas, const float* alphas_prev, int order, int lower_order_final, int corrector,
+                    float* out, int* step_order);
+/* One step, one launch: e as in mkd_dpmpp_step; with c = coef12 (HOST, one row of mkd_unipc_table) and x = x~_k:
+ * m0_out = (x - c[1] e) c[0];  xc_out = c[2] xc_prev + c[3] m0 + c[4] m1 + c[5] m2 + c[6] m3 (c[2] == 0: xc_out = x);
+ * x_next = c[7] xc_out + c[8] m0 + c[9] m1 + c[10] m2.  xc_prev (x^c_{k-1}) and m1 / m2 / m3 (the previous three x0-predictions) are read
+ * only where a coefficient of theirs is non-zero and may be NULL otherwise (non-zero with NULL: MKD_ERR_ARG); x_next may alias x and
+ * xc_out may alias xc_prev; no other two tensors may overlap.  All fp32 [n]. */
+int mkd_unipc_step(const float* x, const float* xc_prev, const float* eps_c, const float* eps_u, float cfg_scale, const float* coef12,
+                   const float* m1, const float* m2, const float* m3, float* x_next, float* xc_out, float* m0_out, int64_t n, void* stream);
+/* ... with the rescaled eps: k / n_per_sample as in mkd_ddim_step_ex; k == NULL is exactly mkd_unipc_step. */
+int mkd_unipc_step_ex(const float* x, const float* xc_prev, const float* eps_c, const float* eps_u, float cfg_scale, const float* coef12,
+                      const float* m1, const float* m2, const float* m3, const float* k, int n_per_sample, float* x_next, float* xc_out,
+                      float* m0_out, int64_t n, void* stream);
+/* The whole loop: mkd_sample_dpmpp's contract (all three loop forms, the same per-step launch count) with the step above as the step's
+ * last kernel; the context's history ring has four slots and a buffer for x^c here ([5][B*4*h*w] fp32).  Captured steps are keyed on
+ * the solver: DDIM, DPM-Solver++ and UniPC calls may alternate.  m must be NULL: masked sampling with this solver is not defined (the
+ * blend would have to act on two carried states): MKD_ERR_UNSUPPORTED, the context stays usable. */
+int mkd_sample_unipc(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
+                     const float* alphas_prev, int order, int lower_order_final, int corrector, const mkd_sample_mask* m, float cfg_scale,
+                     float* x_out, int use_graph, void* stream);
+/* mkd_sample_unipc with the trace and the guidance rescale of mkd_sample_extras (trace_x rows are x~_{k+1}, trace_x0 rows m_k);
+ * ex == NULL is exactly mkd_sample_unipc. */
+int mkd_sample_unipc_ex(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
+                        const float* alphas_prev, int order, int lower_order_final, int corrector, const mkd_sample_mask* m,
+                        const mkd_sample_extras* ex, float cfg_scale, float* x_out, int use_graph, void* stream);
 /* ---- per-sample requests in one batch (build-defined) ----------------------------------------------------------
  * One request row per sample b: its own schedule (n_steps, 1 <= n_steps <= MKD_MAX_STEPS, and HOST tables laid out as for mkd_sample /
  * mkd_sample_eta: entry n_steps - 1 is executed first) and its own guidance scale.  DDIM (solver 0) reads timesteps, alphas, alphas_prev,

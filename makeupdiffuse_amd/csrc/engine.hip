@@ -96,6 +96,7 @@ struct SampleReq {
     const float* sigmas = nullptr; const float* noise = nullptr; float temperature = 1.0f;          // eta > 0
     const mkd_sample_mask* qm = nullptr;          // masked sampling
     const float* dpm = nullptr;                   // host [n_steps][6] of mkd_dpmpp_table: the DPM-Solver++ loop; null: DDIM
+    const float* uni = nullptr;                   // host [n_steps][12] of mkd_unipc_table: the UniPC loop
     float cfg_scale = 1.0f; float* x_out = nullptr; int use_graph = 0;
     const mkd_sample_extras* ex = nullptr;        // intermediates trace / guidance rescale; null: neither
     const char* who = "mkd_sample";
@@ -454,11 +455,13 @@ struct mkd_ctx {
     StepState* s_state = nullptr; StepState* h_state = nullptr;
     float* s_kfac = nullptr;          // guidance rescale: this step's per-sample factors [B] (allocated with the buffers above)
     StepRow* s_rows = nullptr; StepRow* h_rows = nullptr; size_t rows_cap = 0;      // per-sample step table [S_max][batch]: device / pinned host, grown on demand
-    float* s_ring = nullptr; int64_t s_ring_n = 0;        // DPM-Solver++ history ring [3][n] fp32: allocated on first use, grown with the batch
+    // history of the multistep solvers, s_ring_cap floats: allocated on first use, grown with the batch.  DPM-Solver++: ring [3][n];
+    // UniPC: ring [4][n], then the corrected latent x^c [n]
+    float* s_ring = nullptr; int64_t s_ring_cap = 0;
     hipStream_t loop_stream = nullptr; hipEvent_t ev_loop_in = nullptr, ev_loop_out = nullptr;
     hipGraphExec_t multi_graph = nullptr; int multi_graph_steps = 0;      // MKD_GRAPH_STEPS consecutive steps as one graph
     // everything the nodes of a captured step depend on: plan, guidance (on, scale), where the time embedding comes from, batch, and
-    // the solver whose kernel ends the step (0 DDIM, 1 DPM-Solver++; its order lives in the table), and whether the guided eps is
+    // the solver whose kernel ends the step (0 DDIM, 1 DPM-Solver++, 2 UniPC; its order lives in the table), and whether the guided eps is
     // rescaled (one more launch, another expression in the last kernel; phi itself lives in the step state)
     struct StepKey {
         int gen = -1, cfg = -1, temb = -1, batch = -1, solver = -1, rescale = -1; float scale = 0.f;
@@ -1914,9 +1917,10 @@ struct mkd_ctx {
         const int per = sample_elems();
         if (kf) s.factor = [self, io = s.io, per, batch = k.batch, scale = k.scale](hipStream_t st) {
             return launch_cfg_rescale_factor(io.ec, io.eu, scale, 0.f, self->s_state, batch, per, self->s_kfac, st); };
-        s.tail = [self, io = s.io, n, dpm_on = k.solver != 0, scale = k.scale, kf, per](hipStream_t st) {
-            return dpm_on ? launch_dpmpp_step_state(self->s_xa, io.ec, io.eu, scale, self->s_state, n, st, kf, per)
-                          : launch_ddim_step_state(self->s_xa, io.ec, io.eu, scale, self->s_state, n, st, kf, per); };
+        s.tail = [self, io = s.io, n, solver = k.solver, scale = k.scale, kf, per](hipStream_t st) {
+            return solver == 2 ? launch_unipc_step_state(self->s_xa, io.ec, io.eu, scale, self->s_state, n, st, kf, per)
+                 : solver == 1 ? launch_dpmpp_step_state(self->s_xa, io.ec, io.eu, scale, self->s_state, n, st, kf, per)
+                               : launch_ddim_step_state(self->s_xa, io.ec, io.eu, scale, self->s_state, n, st, kf, per); };
         return s;
     }
     int enqueue_state_steps(const StepKey& k, int steps, hipStream_t stream) {
@@ -2038,14 +2042,15 @@ struct mkd_ctx {
         step_key = StepKey{};
     }
 
-    // the DPM-Solver++ history ring for latents of n elements (the captured step reads its address from the step state, so growing
-    // it invalidates no graph)
-    int ensure_ring(int64_t n) {
-        if (s_ring && s_ring_n >= n) return 0;
+    // the multistep solvers' history for latents of n elements, `planes` of them (3: DPM-Solver++; 5: UniPC's four slots and x^c).  The
+    // captured step reads its address from the step state, so growing it invalidates no graph
+    int ensure_ring(int64_t n, int planes) {
+        const int64_t need = planes * n;
+        if (s_ring && s_ring_cap >= need) return 0;
         MKD_HIP_CHECK(hipDeviceSynchronize());          // an enqueued loop may still use the old ring
-        if (s_ring) { MKD_HIP_CHECK(hipFree(s_ring)); s_ring = nullptr; s_ring_n = 0; }
-        MKD_HIP_CHECK(hipMalloc((void**)&s_ring, (size_t)(3 * n) * sizeof(float)));
-        s_ring_n = n;
+        if (s_ring) { MKD_HIP_CHECK(hipFree(s_ring)); s_ring = nullptr; s_ring_cap = 0; }
+        MKD_HIP_CHECK(hipMalloc((void**)&s_ring, (size_t)need * sizeof(float)));
+        s_ring_cap = need;
         return 0;
     }
 
@@ -2060,7 +2065,7 @@ struct mkd_ctx {
         if (*stochastic && !r.noise) return mkd_fail(MKD_ERR_ARG, "mkd_sample_eta: sigma > 0 needs the noise draws");
         if (r.cfg_scale != 1.0f ? (B != 2 * r.batch) : (B != r.batch))
             return mkd_fail(MKD_ERR_ARG, "mkd_sample: prepared batch must be B (cfg_scale == 1) or 2B (uncond first)");
-        if (r.n_steps <= 0 || !r.timesteps || !r.alphas || !r.alphas_prev || (!r.s1m && !r.dpm) || !r.x_T || !r.x_out)
+        if (r.n_steps <= 0 || !r.timesteps || !r.alphas || !r.alphas_prev || (!r.s1m && !r.dpm && !r.uni) || !r.x_T || !r.x_out)
             return mkd_fail(MKD_ERR_ARG, "mkd_sample: bad arguments");
         const mkd_sample_mask* qm = r.qm;
         if (qm && (!qm->x0 || !qm->mask || !qm->noise || !qm->sqrt_alphas_cumprod || !qm->sqrt_one_minus_alphas_cumprod))
@@ -2095,8 +2100,12 @@ struct mkd_ctx {
             h_state->coef[4 * i + 3] = r.s1m ? r.s1m[i] : 0.f;
             h_state->sigma[i] = sg;
             for (int j = 0; j < 6; ++j) h_state->dpm[6 * i + j] = r.dpm ? r.dpm[6 * i + j] : 0.f;
+            if (r.uni) for (int j = 0; j < 12; ++j) h_state->uni[12 * i + j] = r.uni[12 * i + j];
         }
-        h_state->ring = r.dpm ? s_ring : nullptr;
+        h_state->ring = (r.dpm || r.uni) ? s_ring : nullptr;
+        h_state->xc = r.uni ? s_ring + 4 * latent_n(r.batch) : nullptr;          // (null: step_setup_kernel leaves cur_uni / cur_uslot alone)
+        for (int j = 0; j < 12; ++j) h_state->cur_uni[j] = 0.f;
+        for (int j = 0; j < 4; ++j) h_state->cur_uslot[j] = 0;
         for (int j = 0; j < 6; ++j) h_state->cur_dpm[j] = 0.f;
         h_state->cur_slot[0] = h_state->cur_slot[1] = h_state->cur_slot[2] = 0;
         h_state->noise = stochastic ? r.noise : nullptr; h_state->temperature = r.temperature; h_state->n_steps = n_steps;
@@ -2210,7 +2219,13 @@ struct mkd_ctx {
             if (key.cfg) { rc = launch_repeat_batch(xa, s_xin, n, 2, stream); if (rc) return rc; }
             rc = eps(io.x, s_t, s_eps, stream); if (rc) return rc;
             if (kf) { rc = launch_cfg_rescale_factor(io.ec, io.eu, key.scale, r.ex->guidance_rescale, nullptr, r.batch, per, s_kfac, stream); if (rc) return rc; }
-            if (key.solver) {           // m_k into ring slot k mod 3; m_{k-1}, m_{k-2} from the other two (k = i, the executed step)
+            if (key.solver == 2) {      // m_k into slot k mod 4 of the four-slot ring, x^c in place behind it (k = i, the executed step)
+                const float* d = r.uni + 12 * index;
+                const UniCoef kc = {d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10]};
+                float* xc = s_ring + 4 * n;
+                rc = launch_unipc_step(xa, xc, io.ec, io.eu, key.scale, kc, s_ring + (int64_t)((i + 3) % 4) * n, s_ring + (int64_t)((i + 2) % 4) * n,
+                                       s_ring + (int64_t)((i + 1) % 4) * n, xb, xc, s_ring + (int64_t)(i % 4) * n, n, stream, kf, per, tx, tx0);
+            } else if (key.solver) {    // m_k into ring slot k mod 3; m_{k-1}, m_{k-2} from the other two (k = i, the executed step)
                 const float* d = r.dpm + 6 * index;
                 const DpmCoef kc = {d[0], d[1], d[2], d[3], d[4], d[5]};
                 rc = launch_dpmpp_step(xa, io.ec, io.eu, key.scale, kc, s_ring + (int64_t)((i + 2) % 3) * n, s_ring + (int64_t)((i + 1) % 3) * n, xb,
@@ -2227,17 +2242,17 @@ struct mkd_ctx {
         return 0;
     }
 
-    // The whole reverse loop.  DPM-Solver++ is deterministic (sigmas / noise / s1m unused); setup, evaluation and the masked blend are
-    // shared with DDIM, only the step's last kernel differs.
+    // The whole reverse loop.  DPM-Solver++ and UniPC are deterministic (sigmas / noise / s1m unused); setup, evaluation and the masked
+    // blend are shared with DDIM, only the step's last kernel differs.
     int sample(const SampleReq& r, hipStream_t stream) {
         struct Clear { bool& flag; ~Clear() { flag = false; } } clear_temb_skip{temb_skip};      // on every exit: a later mkd_eps runs its own time-embedding chain
         bool stochastic = false;
         int rc = validate(r, &stochastic); if (rc) return rc;
-        StepKey key; key.gen = plan_generation; key.cfg = r.cfg_scale != 1.0f; key.scale = r.cfg_scale; key.batch = r.batch; key.solver = r.dpm != nullptr;
+        StepKey key; key.gen = plan_generation; key.cfg = r.cfg_scale != 1.0f; key.scale = r.cfg_scale; key.batch = r.batch; key.solver = r.uni ? 2 : (r.dpm ? 1 : 0);
         key.rescale = (key.cfg && r.ex && r.ex->guidance_rescale > 0.f) ? 1 : 0;          // (phi = 0, scale 1: not engaged, today's step)
         key.temb = temb_table;          // (the steps take the time embedding from the table exactly when the table is on)
         const int64_t n = latent_n(r.batch);
-        if (key.solver) { rc = ensure_ring(n); if (rc) return rc; }
+        if (key.solver) { rc = ensure_ring(n, key.solver == 2 ? 5 : 3); if (rc) return rc; }
         if (!r.use_graph) return sample_eager(r, key, stochastic, stream);
         hipStream_t ls = nullptr;
         rc = loop_begin(r.x_T, n, true, stream, &ls); if (rc) return rc;
@@ -2281,7 +2296,7 @@ struct mkd_ctx {
         StepKey key; key.gen = plan_generation; key.cfg = guided; key.scale = 0.f; key.batch = r.batch; key.solver = r.solver; key.rescale = 0;
         key.temb = temb_table; key.rows = 1;
         const int64_t n = latent_n(r.batch);
-        if (key.solver) { rc = ensure_ring(n); if (rc) return rc; }
+        if (key.solver) { rc = ensure_ring(n, 3); if (rc) return rc; }
         rc = ensure_rows(tab.size()); if (rc) return rc;
         hipStream_t ls = nullptr;          // uncaptured: the caller's stream, uploads included
         rc = loop_begin(r.x_T, n, r.use_graph != 0, stream, &ls); if (rc) return rc;
@@ -2768,7 +2783,7 @@ struct mkd_ctx {
         MKD_HIP_CHECK(hipDeviceSynchronize());
         if (persist_cap > persist_eps_begin) MKD_HIP_CHECK(hipMemset(persist_base + persist_eps_begin, 0xFF, persist_cap - persist_eps_begin));
         if (gstat_base) MKD_HIP_CHECK(hipMemset(gstat_base, 0xFF, gstat_cap));
-        if (s_ring) MKD_HIP_CHECK(hipMemset(s_ring, 0xFF, (size_t)(3 * s_ring_n) * sizeof(float)));
+        if (s_ring) MKD_HIP_CHECK(hipMemset(s_ring, 0xFF, (size_t)s_ring_cap * sizeof(float)));
         if (s_kfac) MKD_HIP_CHECK(hipMemset(s_kfac, 0xFF, (size_t)B * sizeof(float)));
         for (int i = 0; i < NS; ++i) {
             if (temp_base[i]) MKD_HIP_CHECK(hipMemset(temp_base[i], 0xFF, temp_cap[i]));
@@ -2812,7 +2827,7 @@ struct mkd_ctx {
     }
 
     int64_t device_bytes() const {
-        return weight_bytes + 3 * s_ring_n * (int64_t)sizeof(float) + (int64_t)(side[0].cap + side[1].cap + side[2].cap) + (int64_t)persist_cap + (int64_t)gstat_cap + [&] { int64_t t = 0; for (int i = 0; i < NA; ++i) t += (int64_t)(temp_cap[i] + splitk_ws_bytes[i] + gn_ws_bytes[i]); return t; }();
+        return weight_bytes + s_ring_cap * (int64_t)sizeof(float) + (int64_t)(side[0].cap + side[1].cap + side[2].cap) + (int64_t)persist_cap + (int64_t)gstat_cap + [&] { int64_t t = 0; for (int i = 0; i < NA; ++i) t += (int64_t)(temp_cap[i] + splitk_ws_bytes[i] + gn_ws_bytes[i]); return t; }();
     }
 
     ~mkd_ctx() {
@@ -3107,6 +3122,161 @@ int mkd_sample_dpmpp_ex(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, 
     SampleReq r{x_T, batch, n_steps, timesteps, alphas, alphas_prev};
     r.qm = m; r.dpm = tab.data(); r.cfg_scale = cfg_scale; r.x_out = x_out; r.use_graph = use_graph;
     r.ex = ex; r.who = ex ? "mkd_sample_dpmpp_ex" : "mkd_sample_dpmpp";
+    return ctx->sample(r, (hipStream_t)stream);
+}
+// ---- UniPC (include/mkd.h): schedule-only rows in double; host only --------------------------------------------------------------
+// psi_0 .. psi_3 of h > 0: psi_0 = 1 - e^-h, psi_j = h^j / j! - psi_{j-1} = sum_{m >= 0} (-1)^m h^(j+1+m) / (j+1+m)!.  The recursion
+// cancels for small h (psi_j ~ h^(j+1) / (j+1)! out of terms of size h^j / j!): below h = 1 the alternating series, whose terms fall
+// monotonically there, is summed instead
+static void unipc_psi(double h, double psi[4]) {
+    if (h < 1.0) {
+        for (int j = 0; j < 4; ++j) {
+            double term = 1.0;
+            for (int i = 1; i <= j + 1; ++i) term *= h / i;          // h^(j+1) / (j+1)!
+            double sum = 0.0;
+            for (int m = 0; m < 40 && std::fabs(term) > 0.0; ++m) { sum += term; term *= -h / (j + 2 + m); }
+            psi[j] = sum;
+        }
+        return;
+    }
+    psi[0] = -std::expm1(-h);
+    double pw = 1.0;
+    for (int j = 1; j < 4; ++j) { pw *= h / j; psi[j] = pw - psi[j - 1]; }
+}
+// the weights of one update with q nodes at r[0 .. q-1]: sum_j w_j r_j^i = i! psi_i / h^i, i = 1 .. q (Gaussian elimination with
+// partial pivoting).  q == 1 takes the published code's "bh2" shortcuts instead: w = psi_0 / (2 r) (for the corrector r = 1).
+// false: the nodes do not determine the weights (two of them coincide)
+static bool unipc_weights(int q, const double* r, double h, const double psi[4], double* w) {
+    if (q == 0) return true;
+    if (q == 1) { w[0] = psi[0] / (2.0 * r[0]); return r[0] != 0.0; }
+    double A[3][4];
+    double fact = 1.0, hp = 1.0;
+    for (int i = 1; i <= q; ++i) {
+        fact *= i; hp *= h;
+        for (int j = 0; j < q; ++j) A[i - 1][j] = std::pow(r[j], i);
+        A[i - 1][q] = fact * psi[i] / hp;
+    }
+    for (int c = 0; c < q; ++c) {
+        int piv = c;
+        for (int i = c + 1; i < q; ++i) if (std::fabs(A[i][c]) > std::fabs(A[piv][c])) piv = i;
+        if (!(std::fabs(A[piv][c]) > 0.0)) return false;
+        if (piv != c) for (int j = 0; j <= q; ++j) std::swap(A[c][j], A[piv][j]);
+        for (int i = c + 1; i < q; ++i) {
+            const double f = A[i][c] / A[c][c];
+            for (int j = c; j <= q; ++j) A[i][j] -= f * A[c][j];
+        }
+    }
+    for (int c = q - 1; c >= 0; --c) {
+        double s = A[c][q];
+        for (int j = c + 1; j < q; ++j) s -= A[c][j] * w[j];
+        w[c] = s / A[c][c];
+    }
+    return true;
+}
+int mkd_unipc_table(int n_steps, const float* alphas, const float* alphas_prev, int order, int lower_order_final, int corrector, float* out,
+                    int* step_order) {
+    if (n_steps <= 0 || !alphas || !alphas_prev || !out) return mkd_fail(MKD_ERR_ARG, "mkd_unipc_table: bad arguments");
+    if (order < 1 || order > 3) return mkd_fail(MKD_ERR_ARG, "mkd_unipc_table: order must be 1, 2 or 3");
+    const int n = n_steps;
+    for (int i = 0; i < n; ++i)
+        if (!(alphas[i] > 0.f && alphas[i] < 1.f && alphas_prev[i] > 0.f && alphas_prev[i] < 1.f))
+            return mkd_fail(MKD_ERR_ARG, "mkd_unipc_table: every alpha must lie in (0, 1)");
+    for (int i = 1; i < n; ++i)
+        if (alphas_prev[i] != alphas[i - 1])
+            return mkd_fail(MKD_ERR_ARG, "mkd_unipc_table: the table must be contiguous (alphas_prev[i] == alphas[i - 1]): the corrector walks from one evaluation point to the next");
+    // grid point k = 0 .. n: the evaluation of executed step k (entry n - 1 - k), and the end point alphas_prev[0]
+    std::vector<double> a(n + 1), lam(n + 1);
+    for (int k = 0; k <= n; ++k) {
+        a[k] = k < n ? (double)alphas[n - 1 - k] : (double)alphas_prev[0];
+        lam[k] = 0.5 * std::log(a[k] / (1.0 - a[k]));
+        if (k > 0 && !(lam[k] > lam[k - 1]))
+            return mkd_fail(MKD_ERR_ARG, "mkd_unipc_table: lambda must increase along the executed steps (alphas_prev > alphas, newest entry last)");
+    }
+    std::vector<int> p(n);
+    for (int k = 0; k < n; ++k) {
+        p[k] = order < k + 1 ? order : k + 1;
+        if (lower_order_final && n < 10 && p[k] > n - k) p[k] = n - k;
+    }
+    const char* degenerate = "mkd_unipc_table: the grid does not determine the weights";
+    for (int k = 0; k < n; ++k) {
+        float* o = out + 12 * (size_t)(n - 1 - k);
+        for (int j = 0; j < 12; ++j) o[j] = 0.f;
+        o[0] = (float)(1.0 / std::sqrt(a[k])); o[1] = (float)std::sqrt(1.0 - a[k]);
+        double psi[4], r[3], w[3];
+        if (corrector && k >= 1) {          // from base k - 1 to lambda_k: the p_{k-1} - 1 evaluations before the base, then m_k at r = 1
+            const int q = p[k - 1];
+            const double h = lam[k] - lam[k - 1];
+            unipc_psi(h, psi);
+            for (int j = 1; j < q; ++j) r[j - 1] = (lam[k - 1 - j] - lam[k - 1]) / h;
+            r[q - 1] = 1.0;
+            if (!unipc_weights(q, r, h, psi, w)) return mkd_fail(MKD_ERR_ARG, degenerate);
+            const double al = std::sqrt(a[k]);
+            double sum = 0.0;
+            for (int j = 0; j < q; ++j) sum += w[j];
+            o[2] = (float)(std::sqrt(1.0 - a[k]) / std::sqrt(1.0 - a[k - 1]));
+            o[3] = (float)(al * w[q - 1]);
+            o[4] = (float)(al * (psi[0] - sum));
+            for (int j = 1; j < q; ++j) o[4 + j] = (float)(al * w[j - 1]);
+        }
+        {                                   // from base k to lambda_{k+1}: the p_k - 1 evaluations before the base
+            const int q = p[k] - 1;
+            const double h = lam[k + 1] - lam[k];
+            unipc_psi(h, psi);
+            for (int j = 1; j <= q; ++j) r[j - 1] = (lam[k - j] - lam[k]) / h;
+            if (!unipc_weights(q, r, h, psi, w)) return mkd_fail(MKD_ERR_ARG, degenerate);
+            const double al = std::sqrt(a[k + 1]);
+            double sum = 0.0;
+            for (int j = 0; j < q; ++j) sum += w[j];
+            o[7] = (float)(std::sqrt(1.0 - a[k + 1]) / std::sqrt(1.0 - a[k]));
+            o[8] = (float)(al * (psi[0] - sum));
+            for (int j = 1; j <= q; ++j) o[8 + j] = (float)(al * w[j - 1]);
+        }
+        if (step_order) step_order[n - 1 - k] = p[k];
+    }
+    return 0;
+}
+static int unipc_step_args(const char* who, const float* x, const float* xc_prev, const float* eps_c, const float* c, const float* m1,
+                           const float* m2, const float* m3, const float* x_next, const float* xc_out, const float* m0_out, int64_t n) {
+    if (!x || !eps_c || !c || !x_next || !xc_out || !m0_out || n <= 0) return mkd_fail(MKD_ERR_ARG, std::string(who) + ": null pointer or empty tensor");
+    const bool cor = c[2] != 0.f;
+    if ((cor && !xc_prev) || (((cor && c[4] != 0.f) || c[9] != 0.f) && !m1) || (((cor && c[5] != 0.f) || c[10] != 0.f) && !m2) ||
+        (cor && c[6] != 0.f && !m3))
+        return mkd_fail(MKD_ERR_ARG, std::string(who) + ": a non-zero a_c / q_j / p_j needs xc_prev / m1 / m2 / m3");
+    return 0;
+}
+int mkd_unipc_step(const float* x, const float* xc_prev, const float* eps_c, const float* eps_u, float cfg_scale, const float* coef12,
+                   const float* m1, const float* m2, const float* m3, float* x_next, float* xc_out, float* m0_out, int64_t n, void* stream) {
+    return mkd_unipc_step_ex(x, xc_prev, eps_c, eps_u, cfg_scale, coef12, m1, m2, m3, nullptr, 0, x_next, xc_out, m0_out, n, stream);
+}
+int mkd_unipc_step_ex(const float* x, const float* xc_prev, const float* eps_c, const float* eps_u, float cfg_scale, const float* coef12,
+                      const float* m1, const float* m2, const float* m3, const float* k, int n_per_sample, float* x_next, float* xc_out,
+                      float* m0_out, int64_t n, void* stream) {
+    const char* who = k ? "mkd_unipc_step_ex" : "mkd_unipc_step";
+    if (int rc = unipc_step_args(who, x, xc_prev, eps_c, coef12, m1, m2, m3, x_next, xc_out, m0_out, n)) return rc;
+    if (k) if (int rc = check_rescale_args(k, eps_u, n, n_per_sample, who)) return rc;
+    const float* c = coef12;
+    const UniCoef kc = {c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], c[10]};
+    return launch_unipc_step(x, xc_prev, eps_c, eps_u, cfg_scale, kc, m1, m2, m3, x_next, xc_out, m0_out, n, (hipStream_t)stream, k,
+                             k ? n_per_sample : 0);
+}
+int mkd_sample_unipc(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
+                     const float* alphas_prev, int order, int lower_order_final, int corrector, const mkd_sample_mask* m, float cfg_scale,
+                     float* x_out, int use_graph, void* stream) {
+    return mkd_sample_unipc_ex(ctx, x_T, batch, n_steps, timesteps, alphas, alphas_prev, order, lower_order_final, corrector, m, nullptr,
+                               cfg_scale, x_out, use_graph, stream);
+}
+int mkd_sample_unipc_ex(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
+                        const float* alphas_prev, int order, int lower_order_final, int corrector, const mkd_sample_mask* m,
+                        const mkd_sample_extras* ex, float cfg_scale, float* x_out, int use_graph, void* stream) {
+    if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
+    if (n_steps <= 0 || !alphas || !alphas_prev) return mkd_fail(MKD_ERR_ARG, "mkd_sample_unipc: bad arguments");
+    if (m) return mkd_fail(MKD_ERR_UNSUPPORTED, "mkd_sample_unipc: masked sampling with the UniPC solver is not built (the blend would act on two carried states)");
+    std::vector<float> tab((size_t)n_steps * 12);
+    const int rc = mkd_unipc_table(n_steps, alphas, alphas_prev, order, lower_order_final, corrector, tab.data(), nullptr);
+    if (rc) return rc;
+    SampleReq r{x_T, batch, n_steps, timesteps, alphas, alphas_prev};
+    r.uni = tab.data(); r.cfg_scale = cfg_scale; r.x_out = x_out; r.use_graph = use_graph;
+    r.ex = ex; r.who = ex ? "mkd_sample_unipc_ex" : "mkd_sample_unipc";
     return ctx->sample(r, (hipStream_t)stream);
 }
 int mkd_step_table(const mkd_sample_row* rows, int batch, int solver, mkd_step_row* out, int* s_max, int64_t* distinct, int* n_distinct) {

@@ -161,6 +161,10 @@ __global__ void step_setup_kernel(StepState* st, int64_t* t_out, int batch, cons
             for (int j = 0; j < 6; ++j) st->cur_dpm[j] = st->dpm[6 * i + j];
             const int k = st->n_steps - 1 - i;
             st->cur_slot[0] = k % 3; st->cur_slot[1] = (k + 2) % 3; st->cur_slot[2] = (k + 1) % 3;
+            if (st->xc) {          // UniPC loop: the step's row and the four-slot ring's slots of m_k .. m_{k-3}
+                for (int j = 0; j < 12; ++j) st->cur_uni[j] = st->uni[12 * i + j];
+                for (int j = 0; j < 4; ++j) st->cur_uslot[j] = (k + 4 - j) % 4;
+            }
         }
     }
     const int gtid = blockIdx.x * blockDim.x + threadIdx.x, gthreads = gridDim.x * blockDim.x;
@@ -292,6 +296,118 @@ __global__ void dpmpp_step_state_kernel(float* x, const float* __restrict__ eps_
     const float* const m2 = ring + (int64_t)st->cur_slot[2] * n;
     if (blockIdx.x == 0 && threadIdx.x == 0) st->counter = st->counter - 1;      // (nothing else in this kernel reads it)
     dpmpp_update_range(x, eps_c, eps_u, cfg_scale, k, m1, m2, x, m0, n, kfac, n_per_sample, tx, tx0);
+}
+
+// ---- UniPC predictor-corrector update (Zhao et al. 2023; data prediction, the linear forms of include/mkd.h mkd_unipc_table) ----
+// One element, with x = x~_k the predicted latent the model was evaluated at and xcp = x^c_{k-1} the previous corrected one:
+//   m0 = (x - sigma_t e) / alpha_t
+//   xc = a_c xcp + q_0 m0 + q_1 m1 + q_2 m2 + q_3 m3      (a_c == 0: no corrector in this step, xc = x)
+//   x' = a_p xc + p_0 m0 + p_1 m1 + p_2 m2
+// Explicit fmas (two roundings of the guidance combine, two of m0, at most five of xc, four of x'): the stand-alone kernel and the
+// step-state kernel give the same bits whatever the compiler contracts.  A history term is added only where its coefficient is non-zero.
+__device__ __forceinline__ float unipc_update_at(float x, float xcp, float e, const UniCoef& k, float m1, float m2, float m3, float& m0,
+                                                 float& xc) {
+    m0 = fmaf(-k.sigma, e, x) * k.inv_alpha;
+    float c = x;
+    if (k.ac != 0.f) {
+        c = fmaf(k.q0, m0, k.ac * xcp);
+        if (k.q1 != 0.f) c = fmaf(k.q1, m1, c);
+        if (k.q2 != 0.f) c = fmaf(k.q2, m2, c);
+        if (k.q3 != 0.f) c = fmaf(k.q3, m3, c);
+    }
+    xc = c;
+    float r = fmaf(k.p0, m0, k.ap * c);
+    if (k.p1 != 0.f) r = fmaf(k.p1, m1, r);
+    if (k.p2 != 0.f) r = fmaf(k.p2, m2, r);
+    return r;
+}
+// The grid-stride body both kernels run: one pass over x, xcp, eps_c (, eps_u), m1..m3 in and x', xc, m0 out.  16-byte accesses when
+// n is a multiple of 4 and every pointer that is used is 16-byte aligned, scalar otherwise (same per-element arithmetic).  xcp and
+// m1..m3 are loaded only where a coefficient of theirs is non-zero (uniform branches: the first steps and the lower orders issue no
+// loads for unused planes).  x_next may alias x and xc_out may alias xcp (element i is read before it is written).
+__device__ __forceinline__ void unipc_update_range(const float* x, const float* xcp, const float* __restrict__ eps_c,
+                                                   const float* __restrict__ eps_u, float cfg_scale, const UniCoef k,
+                                                   const float* __restrict__ m1, const float* __restrict__ m2, const float* __restrict__ m3,
+                                                   float* x_next, float* xc_out, float* __restrict__ m0_out, int64_t n,
+                                                   const float* __restrict__ kfac, int n_per_sample,
+                                                   float* __restrict__ x_copy, float* __restrict__ m0_copy) {
+    const bool usec = k.ac != 0.f;
+    const bool use1 = (usec && k.q1 != 0.f) || k.p1 != 0.f, use2 = (usec && k.q2 != 0.f) || k.p2 != 0.f, use3 = usec && k.q3 != 0.f;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+    uintptr_t al = (uintptr_t)x | (uintptr_t)eps_c | (uintptr_t)eps_u | (uintptr_t)x_next | (uintptr_t)xc_out | (uintptr_t)m0_out |
+                   (uintptr_t)x_copy | (uintptr_t)m0_copy;
+    if (usec) al |= (uintptr_t)xcp;
+    if (use1) al |= (uintptr_t)m1;
+    if (use2) al |= (uintptr_t)m2;
+    if (use3) al |= (uintptr_t)m3;
+    if (!(n & 3) && !(al & 15)) {
+        const int64_t n4 = n >> 2;
+        for (int64_t i = tid; i < n4; i += nth) {
+            const f32x4 xv = ((const f32x4*)x)[i];
+            f32x4 ev = ((const f32x4*)eps_c)[i];
+            if (eps_u) {
+                const f32x4 uv = ((const f32x4*)eps_u)[i];
+                if (kfac) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) ev[j] = cfg_rescaled_eps_at(ev[j], uv[j], cfg_scale, kfac, 4 * i + j, n_per_sample);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) ev[j] = dpmpp_eps_at(ev[j], uv[j], cfg_scale);
+                }
+            }
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            f32x4 pv = z, a = z, b = z, c = z, mv, cv, rv;
+            if (usec) pv = ((const f32x4*)xcp)[i];
+            if (use1) a = ((const f32x4*)m1)[i];
+            if (use2) b = ((const f32x4*)m2)[i];
+            if (use3) c = ((const f32x4*)m3)[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { float m0, xc; rv[j] = unipc_update_at(xv[j], pv[j], ev[j], k, a[j], b[j], c[j], m0, xc); mv[j] = m0; cv[j] = xc; }
+            ((f32x4*)m0_out)[i] = mv;
+            ((f32x4*)xc_out)[i] = cv;
+            ((f32x4*)x_next)[i] = rv;
+            if (m0_copy) ((f32x4*)m0_copy)[i] = mv;
+            if (x_copy) ((f32x4*)x_copy)[i] = rv;
+        }
+        return;
+    }
+    for (int64_t i = tid; i < n; i += nth) {
+        float e = eps_c[i];
+        if (eps_u) e = kfac ? cfg_rescaled_eps_at(e, eps_u[i], cfg_scale, kfac, i, n_per_sample) : dpmpp_eps_at(e, eps_u[i], cfg_scale);
+        float m0, xc;
+        const float r = unipc_update_at(x[i], usec ? xcp[i] : 0.f, e, k, use1 ? m1[i] : 0.f, use2 ? m2[i] : 0.f, use3 ? m3[i] : 0.f, m0, xc);
+        m0_out[i] = m0;
+        xc_out[i] = xc;
+        x_next[i] = r;
+        if (m0_copy) m0_copy[i] = m0;
+        if (x_copy) x_copy[i] = r;
+    }
+}
+
+__global__ void unipc_step_kernel(const float* x, const float* xcp, const float* __restrict__ eps_c, const float* __restrict__ eps_u,
+                                  float cfg_scale, const UniCoef k, const float* __restrict__ m1, const float* __restrict__ m2,
+                                  const float* __restrict__ m3, float* x_next, float* xc_out, float* __restrict__ m0_out, int64_t n,
+                                  const float* __restrict__ kfac, int n_per_sample, float* __restrict__ x_copy, float* __restrict__ m0_copy) {
+    unipc_update_range(x, xcp, eps_c, eps_u, cfg_scale, k, m1, m2, m3, x_next, xc_out, m0_out, n, kfac, n_per_sample, x_copy, m0_copy);
+}
+
+// in place (x <- x~_{k+1}, st->xc <- x^c_k) with the row and the four ring slots step_setup_kernel published; ends the step: the counter
+// moves on
+__global__ void unipc_step_state_kernel(float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u, float cfg_scale,
+                                        StepState* st, int64_t n, const float* __restrict__ kfac, int n_per_sample) {
+    const float* const u = st->cur_uni;
+    const UniCoef k = {u[0], u[1], u[2], u[3], u[4], u[5], u[6], u[7], u[8], u[9], u[10]};
+    const int row = st->cur_trace;          // (published by step_setup_kernel; uniform over the grid, like both trace pointers)
+    float* const tx = (st->trace_x && row >= 0) ? st->trace_x + (int64_t)row * n : nullptr;
+    float* const tx0 = (st->trace_x0 && row >= 0) ? st->trace_x0 + (int64_t)row * n : nullptr;
+    float* const ring = st->ring;
+    float* const xc = st->xc;
+    float* const m0 = ring + (int64_t)st->cur_uslot[0] * n;
+    const float* const m1 = ring + (int64_t)st->cur_uslot[1] * n;
+    const float* const m2 = ring + (int64_t)st->cur_uslot[2] * n;
+    const float* const m3 = ring + (int64_t)st->cur_uslot[3] * n;
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->counter = st->counter - 1;      // (nothing else in this kernel reads it)
+    unipc_update_range(x, xc, eps_c, eps_u, cfg_scale, k, m1, m2, m3, x, xc, m0, n, kfac, n_per_sample, tx, tx0);
 }
 
 // ---- per-sample loop (mkd_sample_rows): every sample of the batch has its own schedule, guidance scale and sigmas -------------------
@@ -987,6 +1103,28 @@ int launch_dpmpp_step_state(float* x, const float* eps_c, const float* eps_u, fl
     if (int rc = check_kfac(kfac, eps_u, n_per_sample, n, "dpmpp_step_state")) return rc;
     hipLaunchKernelGGL(dpmpp_step_state_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale, st, n, kfac, n_per_sample);
     MKD_LAUNCH_CHECK("dpmpp_step_state_kernel");
+    return 0;
+}
+
+int launch_unipc_step(const float* x, const float* xc_prev, const float* eps_c, const float* eps_u, float cfg_scale, const UniCoef& k,
+                      const float* m1, const float* m2, const float* m3, float* x_next, float* xc_out, float* m0_out, int64_t n,
+                      hipStream_t stream, const float* kfac, int n_per_sample, float* x_copy, float* m0_copy) {
+    if (!x || !eps_c || !x_next || !xc_out || !m0_out || n <= 0) return mkd_fail(-1, "unipc_step: bad arguments");
+    if (int rc = check_kfac(kfac, eps_u, n_per_sample, n, "unipc_step")) return rc;
+    const bool c = k.ac != 0.f;
+    if ((c && !xc_prev) || (((c && k.q1 != 0.f) || k.p1 != 0.f) && !m1) || (((c && k.q2 != 0.f) || k.p2 != 0.f) && !m2) || (c && k.q3 != 0.f && !m3))
+        return mkd_fail(-1, "unipc_step: a non-zero coefficient needs its corrected latent / x0-prediction");
+    hipLaunchKernelGGL(unipc_step_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, xc_prev, eps_c, eps_u, cfg_scale, k, m1, m2, m3, x_next,
+                       xc_out, m0_out, n, kfac, n_per_sample, x_copy, m0_copy);
+    MKD_LAUNCH_CHECK("unipc_step_kernel");
+    return 0;
+}
+
+int launch_unipc_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
+                            hipStream_t stream, const float* kfac, int n_per_sample) {
+    if (int rc = check_kfac(kfac, eps_u, n_per_sample, n, "unipc_step_state")) return rc;
+    hipLaunchKernelGGL(unipc_step_state_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale, st, n, kfac, n_per_sample);
+    MKD_LAUNCH_CHECK("unipc_step_state_kernel");
     return 0;
 }
 

@@ -193,6 +193,12 @@ struct StepState {
     float dpm[6 * MKD_MAX_STEPS];
     float* ring;
     float cur_dpm[6]; int cur_slot[3];
+    // UniPC predictor-corrector loop (mkd_sample_unipc): uni[12 i ..] = the row of table entry i (mkd_unipc_table); it shares `ring`,
+    // here [4][n] with m_k in slot k mod 4, and carries the corrected latent x^c in xc [n].  cur_uni / cur_uslot (slots of m_k ..
+    // m_{k-3}): this step's, set by step_setup_kernel.  xc null: not a UniPC loop
+    float uni[12 * MKD_MAX_STEPS];
+    float* xc;
+    float cur_uni[12]; int cur_uslot[4];
     // intermediates trace (mkd_sample_extras): entry i is logged into row trace_row[i] (-1: not logged) of trace_x (the latent after the
     // step) and trace_x0 (the step's x0-prediction), each [rows][n] fp32 and each null when not asked for.  cur_trace: this step's row,
     // published by step_setup_kernel next to cur_row (the step's last kernel moves the counter, so it cannot look the row up itself)
@@ -209,6 +215,8 @@ struct StepState {
 };
 // the six schedule-only numbers of one DPM-Solver++ step
 struct DpmCoef { float inv_alpha, sigma, cx, c0, c1, c2; };
+// the eleven schedule-only numbers of one UniPC step (the first eleven of a mkd_unipc_table row; ac == 0: the step has no corrector)
+struct UniCoef { float inv_alpha, sigma, ac, q0, q1, q2, q3, ap, p0, p1, p2; };
 
 // Time embedding of a sampling call: row `step` of tab[k] ([steps, n[k]] fp32, one table per net) is copied into every one of
 // the `batch` rows of proj[k] ([batch, n[k]]: what the ResBlock epilogues read as their per-sample row bias).  n[k] % 4 == 0; n[k] = 0: absent.
@@ -361,6 +369,16 @@ int launch_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, fl
                       const float* kfac = nullptr, int n_per_sample = 0, float* x_copy = nullptr, float* m0_copy = nullptr);
 // the same update in place with the coefficients / ring slots step_setup_kernel published; the step's LAST kernel: advances the counter
 int launch_dpmpp_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
+                            hipStream_t stream, const float* kfac = nullptr, int n_per_sample = 0);
+// UniPC predictor-corrector update (kernels_misc.hip), one launch: m0_out <- (x - sigma e) / alpha with x = x~_k; xc_out <- a_c xc_prev +
+// q_0 m0 + q_1 m1 + q_2 m2 + q_3 m3 (a_c == 0: xc_out <- x); x_next <- a_p xc_out + p_0 m0 + p_1 m1 + p_2 m2.  e, kfac, x_copy (x_next
+// once more) / m0_copy as in launch_dpmpp_step.  xc_prev / m1..m3 are read only where a coefficient of theirs is non-zero; x_next may be
+// x, xc_out may be xc_prev
+int launch_unipc_step(const float* x, const float* xc_prev, const float* eps_c, const float* eps_u, float cfg_scale, const UniCoef& k,
+                      const float* m1, const float* m2, const float* m3, float* x_next, float* xc_out, float* m0_out, int64_t n,
+                      hipStream_t stream, const float* kfac = nullptr, int n_per_sample = 0, float* x_copy = nullptr, float* m0_copy = nullptr);
+// the same update in place (x, st->xc) with the row / ring slots step_setup_kernel published; the step's LAST kernel: advances the counter
+int launch_unipc_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
                             hipStream_t stream, const float* kfac = nullptr, int n_per_sample = 0);
 // ---- per-sample loop (kernels_misc.hip) ----
 // first kernel of a per-sample step (st->rows non-null): t_out[b] = the timestep of sample b % samples in this executed step (`batch` rows:

@@ -16,6 +16,7 @@ import torch
 
 from ..ddim import DDIMSampler
 from ..dpm_solver import DPMSolverSampler
+from ..unipc import UniPCSampler
 from ..engine import ClipConfig, MkdEngine, NetConfig, VaeConfig
 from ..lib import MkdError
 from ..schedule import DDIMSchedule
@@ -323,6 +324,22 @@ class BaseMakeUpDiffuse:
                                 x0=x0, mask=mask, q_sqrt_ac=q_sqrt_ac, q_sqrt_1m_ac=q_sqrt_1m_ac, q_noise=q_noise,
                                 guidance_rescale=float(guidance_rescale), **trace)
 
+    def unipc_step(self, x, xc_prev, e_c, e_u, scale, coef12, m1=None, m2=None, m3=None, guidance_rescale=0.0):
+        """one UniPC step on the device (UniPCSampler's per-step loop): (next predicted latent, corrected latent, x0-prediction), the
+        kernel arithmetic of the in-library loop"""
+        return self._require_engine().unipc_step(x, xc_prev, e_c, e_u, scale, coef12, m1, m2, m3, guidance_rescale=guidance_rescale)
+
+    def sample_loop_unipc(self, x_latent, cond, timesteps, alphas, alphas_prev, order=2, lower_order_final=True, corrector=True,
+                          unconditional_guidance_scale=1.0, unconditional_conditioning=None, log_every_t=None, guidance_rescale=0.0):
+        """the whole UniPC predictor-corrector loop inside libmkd (mkd_sample_unipc), on the tables sample_loop_dpmpp takes;
+        log_every_t as there"""
+        eng, cfg_scale = self._bind_guided(cond, unconditional_conditioning, unconditional_guidance_scale, x_latent.shape[2:])
+        trace = {} if log_every_t is None else dict(log_every_t=int(log_every_t), want_trace=True)
+        return eng.sample_unipc(x_latent, [int(v) for v in timesteps], [float(v) for v in alphas], [float(v) for v in alphas_prev],
+                                order=int(order), lower_order_final=bool(lower_order_final), corrector=bool(corrector),
+                                cfg_scale=cfg_scale, use_graph=bool(self.sample_use_graph),
+                                guidance_rescale=float(guidance_rescale), **trace)
+
     def latent_mask_from_labels(self, seg: torch.Tensor, classes: Sequence[int] = (0, 11, 12), factor: int = 8,
                                 threshold: float = 0.5) -> torch.Tensor:
         """Label map [B,H,W] (uint8) -> latent mask [B,1,H/factor,W/factor] on the device: the area fraction of each block whose label
@@ -330,9 +347,11 @@ class BaseMakeUpDiffuse:
         return self._require_engine().latent_mask_from_labels(seg, classes, factor, threshold)
 
     # ---- sampling drivers ----------------------------------------------------------------------------------------
-    # the sampler sample_log runs: 'ddim' (the reference's) or 'dpmpp' (DPM-Solver++ multistep of order solver_order on the same grid)
+    # the sampler sample_log runs: 'ddim' (the reference's), 'dpmpp' (DPM-Solver++ multistep of order solver_order on the same grid) or
+    # 'unipc' (the UniPC predictor-corrector of order solver_order on that grid; unipc_corrector False: its predictor alone)
     sampler = 'ddim'
     solver_order = 2
+    unipc_corrector = True
 
     @torch.no_grad()
     def sample_log(self, cond: dict, batch_size: int, ddim: bool, ddim_steps: int, **kwargs):
@@ -344,6 +363,9 @@ class BaseMakeUpDiffuse:
         shape = (self.channels, h // 8, w // 8)
         if self.sampler == 'dpmpp':
             return DPMSolverSampler(self).sample(ddim_steps, batch_size, shape, cond, order=self.solver_order, verbose=False, **kwargs)
+        if self.sampler == 'unipc':
+            return UniPCSampler(self).sample(ddim_steps, batch_size, shape, cond, order=self.solver_order,
+                                             corrector=self.unipc_corrector, verbose=False, **kwargs)
         if self.sampler != 'ddim':
             raise ValueError(f"sampler must be 'ddim' or 'dpmpp', got {self.sampler!r}")
         sampler = DDIMSampler(self)
@@ -434,7 +456,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                  unconditional_guidance_scale: float = 9, ddim_steps: int = 50, ddim_eta: float = 0.0, sample: bool = True,
                  fix_background: bool = False, background_classes: Sequence[int] = (0, 11, 12), background_threshold: float = 0.5,
                  seg_key: str = 'nonmakeup_seg', makeup_score: bool = False, ref_seg_key: str = 'makeup_seg', sampler: str = 'ddim',
-                 solver_order: int = 2, paste_background: bool = False, paste_feather: int = 0, denoise_rows: bool = False,
+                 solver_order: int = 2, unipc_corrector: bool = True, paste_background: bool = False, paste_feather: int = 0, denoise_rows: bool = False,
                  log_every_t: int = 100, guidance_rescale: float = 0.0, face_parser=None, parser_lut=None, parse_size: int = 512,
                  *args, **kwargs):
         if int(log_every_t) < 1:
@@ -443,7 +465,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             raise ValueError(f'guidance_rescale must lie in [0, 1], got {guidance_rescale}')
         if not 0 <= int(paste_feather) <= 16:
             raise ValueError(f'paste_feather must be 0..16 image pixels, got {paste_feather}')
-        if sampler not in ('ddim', 'dpmpp'):
+        if sampler not in ('ddim', 'dpmpp', 'unipc'):
             raise ValueError(f"sampler must be 'ddim' or 'dpmpp', got {sampler!r}")
         if solver_order not in (1, 2, 3):
             raise ValueError('solver_order must be 1, 2 or 3')
@@ -458,7 +480,9 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         self.parser_lut = tuple(LUT_SEG if parser_lut is None else parser_lut)
         self.parse_size = int(parse_size)
         # log_results' sampler: 'dpmpp' runs both passes on DPM-Solver++ multistep (ddim_steps is then its number of evaluations)
+        # 'unipc': the UniPC predictor-corrector at the same number of evaluations (unipc_corrector False: the predictor alone)
         self.sampler, self.solver_order = sampler, int(solver_order)
+        self.unipc_corrector = bool(unipc_corrector)
         # makeup score of every decoded sample (makeup_score.transfer_score): off by default, then log_results is unchanged
         self.makeup_score = bool(makeup_score)
         self.ref_seg_key = ref_seg_key
@@ -531,6 +555,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         maps the batch lacks are added to ``batch`` (_fill_segs)."""
         use_ddim = self.ddim_steps is not None
         log: Dict[str, torch.Tensor] = {}
+        self._check_unipc_masked()
         if self.fix_background or self.paste_background or self.makeup_score:
             self._fill_segs(batch, ref=self.makeup_score)
         _, c = self.get_input(batch, self.first_stage_key)
@@ -594,6 +619,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         loop of its longest member.  The ``sampler`` attribute picks the solver.  Returns samples_latent (rows in batch order) and,
         with a first stage, the decoded samples."""
         from ..batching import SampleSpec
+        if self.sampler == 'unipc':
+            UniPCSampler(self).sample_specs()          # (NotImplementedError: the per-sample loop runs DDIM and DPM-Solver++ only)
         specs = list(specs)
         _, c = self.get_input(batch, self.first_stage_key)
         c_cat, c_txt = c['c_concat'][0], c['c_crossattn'][0]
@@ -647,6 +674,13 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                 raise KeyError(f"makeup_score: the batch has no label map under '{k}'")
         img = ((sample.float() + 1.0) / 2.0).clamp(0, 1)
         return ms.transfer_score(img, ref, batch[self.seg_key], batch[self.ref_seg_key])
+
+    def _check_unipc_masked(self) -> None:
+        """fix_background samples with a mask; the UniPC solver has no masked form (UniPCSampler.sample).  Raised before the encoder,
+        the parser or a sampler has enqueued anything"""
+        if self.sampler == 'unipc' and self.fix_background:
+            raise NotImplementedError('UniPCSampler: masked sampling (mask / x0) is not defined for this solver: fix_background needs '
+                                      "sampler='ddim' or 'dpmpp'")
 
     def _check_paste(self, batch: dict, what: str) -> None:
         """what a pixel-space paste needs, checked before anything is sampled"""
@@ -790,6 +824,9 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         if self.sampler == 'dpmpp':
             lat = eng.sample_dpmpp(x_T, ts, a, ap, order=self.solver_order, lower_order_final=True, cfg_scale=scale,
                                    use_graph=bool(self.sample_use_graph), guidance_rescale=phi)
+        elif self.sampler == 'unipc':
+            lat = eng.sample_unipc(x_T, ts, a, ap, order=self.solver_order, lower_order_final=True, corrector=self.unipc_corrector,
+                                   cfg_scale=scale, use_graph=bool(self.sample_use_graph), guidance_rescale=phi)
         elif self.sampler == 'ddim':
             lat = eng.sample(x_T, ts, a, ap, [float(v) for v in sch.ddim_sqrt_one_minus_alphas], cfg_scale=scale,
                              use_graph=bool(self.sample_use_graph), guidance_rescale=phi)
@@ -811,6 +848,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         paste_source -> (the decoded images [n,3,size,size], the source crops img01 the paste needs).  A region is a box or a
         photo.Frame (photo.crop_regions: a batch without a rolled frame is one crop_resize call)"""
         eng = self._require_engine()
+        self._check_unipc_masked()
         need_seg = self.fix_background or self.paste_background
         cs = eng.crop_regions(src_photos, src_regions, size, labels=src_segs)
         cr = eng.crop_regions(ref_photos, ref_regions, size)
@@ -893,6 +931,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         from .. import photo
         from ..components import owner_weights
         from ..face_parser import find_boxes, find_faces
+        self._check_unipc_masked()
         phi = float(self.guidance_rescale if guidance_rescale is None else guidance_rescale)
         if not 0.0 <= phi <= 1.0:
             raise ValueError(f'guidance_rescale must lie in [0, 1], got {phi}')

@@ -151,6 +151,26 @@ def dpmpp_table(alphas: Sequence[float], alphas_prev: Sequence[float], order: in
     return np.ctypeslib.as_array(out).reshape(n, 6).copy(), np.ctypeslib.as_array(so).astype(np.int32)
 
 
+def unipc_table(alphas: Sequence[float], alphas_prev: Sequence[float], order: int = 2, lower_order_final: bool = True,
+                corrector: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+    """Rows of the UniPC predictor-corrector on a DDIM step grid (include/mkd.h mkd_unipc_table; host only, needs no device):
+    ``(coef [n, 12] float32, step_order [n] int32)``, row i = 1/alpha, sigma, a_c, q_0 .. q_3, a_p, p_0 .. p_2, 0 of table entry i."""
+    n = len(alphas)
+    if n <= 0 or len(alphas_prev) != n:
+        raise ValueError('alphas / alphas_prev must be non-empty and equally long')
+    a = (C.c_float * n)(*[float(v) for v in alphas])
+    ap = (C.c_float * n)(*[float(v) for v in alphas_prev])
+    out = (C.c_float * (12 * n))()
+    so = (C.c_int * n)()
+    lib = _lib.load()
+    rc = lib.mkd_unipc_table(n, a, ap, int(order), int(bool(lower_order_final)), int(bool(corrector)), out, so)
+    if rc == -1:          # MKD_ERR_ARG: a table this solver refuses
+        msg = lib.mkd_last_error()
+        raise ValueError(msg.decode() if msg else 'mkd_unipc_table: bad arguments')
+    _lib.check(rc, 'mkd_unipc_table')
+    return np.ctypeslib.as_array(out).reshape(n, 12).copy(), np.ctypeslib.as_array(so).astype(np.int32)
+
+
 SOLVERS = {'ddim': 0, 'dpmpp': 1}
 # numpy view of mkd_step_row (include/mkd.h), 64 bytes
 STEP_ROW_DTYPE = np.dtype([('t', '<i8'), ('coef', '<f4', (4,)), ('sigma', '<f4'), ('dpm', '<f4', (6,)), ('temb_row', '<i4'),
@@ -239,6 +259,7 @@ class MkdEngine:
     """Owns one mkd_ctx on the current CUDA(HIP) device."""
 
     dpmpp_table = staticmethod(dpmpp_table)
+    unipc_table = staticmethod(unipc_table)
 
     UNET_PREFIX = 'model.diffusion_model.'
     CONTROL_PREFIX = 'control_model.'
@@ -740,6 +761,63 @@ class MkdEngine:
             else:
                 _lib.check(self.lib.mkd_sample_dpmpp(*head, *tail), 'mkd_sample_dpmpp')
         self._hold(keep, None)
+        return (out, *rows) if want_trace else out
+
+    def unipc_step(self, x, xc_prev, eps_c, eps_u, cfg_scale, coef12, m1=None, m2=None, m3=None, guidance_rescale: float = 0.0):
+        """One UniPC step (mkd_unipc_step): ``x`` = the predicted latent the model was evaluated at, ``xc_prev`` = the previous corrected
+        latent, ``coef12`` = a row of ``unipc_table``, m1 / m2 / m3 = the x0-predictions of the previous three steps; each is needed
+        where a coefficient of its own is non-zero.  Returns (x_next, xc, m0): the next predicted latent, this step's corrected latent
+        and x0-prediction."""
+        x = _f32c(x, self.device); eps_c = _f32c(eps_c, self.device)
+        eps_u = None if eps_u is None else _f32c(eps_u, self.device)
+        k = [float(np.float32(v)) for v in coef12]
+        if len(k) != 12:
+            raise ValueError('coef12 must have twelve entries (a row of unipc_table)')
+        cor = k[2] != 0.0
+        need = (cor, (cor and k[4] != 0.0) or k[9] != 0.0, (cor and k[5] != 0.0) or k[10] != 0.0, cor and k[6] != 0.0)
+        given = [xc_prev, m1, m2, m3]
+        if any(nd and t is None for nd, t in zip(need, given)):
+            raise ValueError('unipc_step: a non-zero coefficient needs its corrected latent / x0-prediction')
+        xc_prev, m1, m2, m3 = (_f32c(t, self.device) if nd else None for nd, t in zip(need, given))
+        for t in (eps_c, eps_u, xc_prev, m1, m2, m3):
+            if t is not None and t.numel() != x.numel():
+                raise ValueError('unipc_step: every tensor must have the size of x')
+        x_next, xc, m0 = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+        kf, per = self._rescale_k(eps_c, eps_u, cfg_scale, guidance_rescale)
+        head = (C.c_void_p(x.data_ptr()), C.c_void_p(_ptr(xc_prev)), C.c_void_p(eps_c.data_ptr()), C.c_void_p(_ptr(eps_u)), float(cfg_scale),
+                (C.c_float * 12)(*k), C.c_void_p(_ptr(m1)), C.c_void_p(_ptr(m2)), C.c_void_p(_ptr(m3)))
+        tail = (C.c_void_p(x_next.data_ptr()), C.c_void_p(xc.data_ptr()), C.c_void_p(m0.data_ptr()), x.numel(), C.c_void_p(_stream()))
+        with torch.cuda.device(self.device):
+            if kf is not None:
+                _lib.check(self.lib.mkd_unipc_step_ex(*head, C.c_void_p(kf.data_ptr()), per, *tail), 'mkd_unipc_step_ex')
+            else:
+                _lib.check(self.lib.mkd_unipc_step(*head, *tail), 'mkd_unipc_step')
+        return x_next, xc, m0
+
+    def sample_unipc(self, x_T: torch.Tensor, timesteps: Sequence[int], alphas: Sequence[float], alphas_prev: Sequence[float],
+                     order: int = 2, lower_order_final: bool = True, corrector: bool = True, cfg_scale: float = 1.0,
+                     use_graph: bool = False, x0: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                     q_sqrt_ac: Optional[Sequence[float]] = None, q_sqrt_1m_ac: Optional[Sequence[float]] = None,
+                     q_noise: Optional[torch.Tensor] = None, log_every_t: int = 100, want_trace: bool = False,
+                     guidance_rescale: float = 0.0):
+        """The whole UniPC predictor-corrector loop in one call (mkd_sample_unipc): ``sample_dpmpp``'s contract on the same DDIM tables,
+        which must be contiguous (alphas_prev[i] == alphas[i - 1]).  ``want_trace`` / ``log_every_t`` / ``guidance_rescale`` as in
+        ``sample`` (x_inter rows: the predicted latents; pred_x0 rows: the solver's m_k).  Masked sampling (x0 / mask / q_*) is not
+        defined for this solver: libmkd refuses it (MkdError, -4) and the context stays usable."""
+        x_T = self._check_x_T(x_T, cfg_scale)
+        n, ts, (a, ap) = self._sample_tables(timesteps, alphas=alphas, alphas_prev=alphas_prev)
+        out = torch.empty_like(x_T)
+        qm, keep = self._sample_mask(x_T, n, x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise)
+        ex, rows = self._sample_extras(x_T, n, log_every_t, want_trace, guidance_rescale)
+        with torch.cuda.device(self.device):
+            head = (self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, int(order), int(bool(lower_order_final)),
+                    int(bool(corrector)), None if qm is None else C.byref(qm))
+            tail = (float(cfg_scale), C.c_void_p(out.data_ptr()), int(use_graph), C.c_void_p(_stream()))
+            if ex is not None:
+                _lib.check(self.lib.mkd_sample_unipc_ex(*head, C.byref(ex), *tail), 'mkd_sample_unipc_ex')
+            else:
+                _lib.check(self.lib.mkd_sample_unipc(*head, *tail), 'mkd_sample_unipc')
+        del keep
         return (out, *rows) if want_trace else out
 
     # ---- per-sample requests in one batch (include/mkd.h mkd_sample_rows) ------------------------------------------------------

@@ -133,6 +133,12 @@ SIGNATURES = {
     'mkd_sample_dpmpp_ex': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), _I, _I, C.POINTER(SampleMaskC),
                                  C.POINTER(SampleExtrasC), _F, _P, _I, _P]),
     'mkd_sample_dpmpp': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), _I, _I, C.POINTER(SampleMaskC), _F, _P, _I, _P]),
+    'mkd_unipc_table': (_I, [_I, C.POINTER(_F), C.POINTER(_F), _I, _I, _I, C.POINTER(_F), C.POINTER(_I)]),
+    'mkd_unipc_step': (_I, [_P, _P, _P, _P, _F, C.POINTER(_F), _P, _P, _P, _P, _P, _P, _L, _P]),
+    'mkd_unipc_step_ex': (_I, [_P, _P, _P, _P, _F, C.POINTER(_F), _P, _P, _P, _P, _I, _P, _P, _P, _L, _P]),
+    'mkd_sample_unipc_ex': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), _I, _I, _I, C.POINTER(SampleMaskC),
+                                 C.POINTER(SampleExtrasC), _F, _P, _I, _P]),
+    'mkd_sample_unipc': (_I, [_P, _P, _I, _I, C.POINTER(_L), C.POINTER(_F), C.POINTER(_F), _I, _I, _I, C.POINTER(SampleMaskC), _F, _P, _I, _P]),
     'mkd_step_table': (_I, [C.POINTER(SampleRowC), _I, _I, C.POINTER(StepRowC), C.POINTER(_I), C.POINTER(_L), C.POINTER(_I)]),
     'mkd_sample_rows': (_I, [_P, _P, _I, C.POINTER(SampleRowC), _I, _P, _F, C.POINTER(SampleMaskC), C.POINTER(SampleExtrasC), _P, _I, _P]),
     'mkd_ddim_step_rows': (_I, [_P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _P]),

@@ -63,9 +63,11 @@ def build_parser():
     ap.add_argument('--batch-size', type=int, default=1)
     ap.add_argument('--res', type=int, default=256)
     ap.add_argument('--ddim-steps', type=int, default=None)
-    ap.add_argument('--sampler', choices=('ddim', 'dpmpp'), default='ddim', help='dpmpp: DPM-Solver++ multistep on the DDIM step grid '
-                    '(--ddim-steps is then its number of evaluations, typically 15-25)')
-    ap.add_argument('--solver-order', type=int, choices=(1, 2, 3), default=2, help='order of --sampler dpmpp')
+    ap.add_argument('--sampler', choices=('ddim', 'dpmpp', 'unipc'), default='ddim', help='dpmpp: DPM-Solver++ multistep on the DDIM step '
+                    'grid (--ddim-steps is then its number of evaluations, typically 15-25); unipc: the UniPC predictor-corrector on '
+                    'that grid, the solver for fewer evaluations still')
+    ap.add_argument('--solver-order', type=int, choices=(1, 2, 3), default=2, help='order of --sampler dpmpp / unipc')
+    ap.add_argument('--no-corrector', action='store_true', help='--sampler unipc: run the predictor alone')
     ap.add_argument('--only-mid-control', action='store_true')
     ap.add_argument('--out', default='./results')
     ap.add_argument('--data-root', default=None, help='folder with images/ and a pairs file (reference TestFixed_Dataset layout)')
@@ -238,8 +240,14 @@ def main():
         raise SystemExit('--log-every-t only applies with --denoise-rows')
     if not 0.0 <= args.guidance_rescale <= 1.0:
         raise SystemExit('--guidance-rescale must lie in 0..1')
+    if args.no_corrector and args.sampler != 'unipc':
+        raise SystemExit('--no-corrector only applies with --sampler unipc')
+    if args.sampler == 'unipc' and args.fix_background:
+        raise SystemExit('--sampler unipc has no masked form: --fix-background needs --sampler ddim or dpmpp')
     steps_list = parse_number_list(args.steps_list, int, '--steps-list')
     guidance_list = parse_number_list(args.guidance_list, float, '--guidance-list')
+    if args.sampler == 'unipc' and (steps_list or guidance_list):
+        raise SystemExit('--sampler unipc has no per-sample form: --steps-list / --guidance-list need --sampler ddim or dpmpp')
     if steps_list and not all(1 <= s <= 1024 for s in steps_list):
         raise SystemExit('--steps-list: every step count must lie in 1..1024')
     rank, world, local = mdist.init_from_env()
@@ -254,6 +262,7 @@ def main():
     if args.ddim_steps is not None:
         model.ddim_steps = args.ddim_steps
     model.sampler, model.solver_order = args.sampler, args.solver_order
+    model.unipc_corrector = not args.no_corrector
     model.denoise_rows, model.log_every_t, model.guidance_rescale = args.denoise_rows, args.log_every_t, args.guidance_rescale
     if args.ckpt:
         model.load_state_dict(load_state_dict(args.ckpt, location='cpu'))
