@@ -1005,6 +1005,31 @@ int  mkd_channel_gate(const uint16_t* x, int ldx, int batch, int pixels, int C, 
 int  mkd_gate_apply_bf16(const uint16_t* x, int ldx, const float* a, int mode, const void* add, int ldadd, uint16_t* y, int ldy, int batch, int h, int w,
                          int C, int u, void* stream);
 
+/* ---- counter-based noise (BUILD-DEFINED: the reference draws torch.randn on a global generator, diffmk/cddim.py:74-78) -------------
+ * Element e of row r of sample b is a pure function of (seed_b, sub_b, stream_id, r, e): no state is carried from call to call and
+ * nothing depends on the batch, so a sample gets the same noise alone, in any batch and at any position in it.
+ *   per sample b   seed_b: 64 bits (carried as int64, the bits of a uint64); sub_b: a 32-bit sub-stream, 0 where subs == NULL (the photo
+ *                  path passes the face's rank)
+ *   per call       stream_id: what the draw is for.  0 the start latent, 1 a step's eta noise, 2 the masked blend's q_sample noise,
+ *                  3 the first-stage posterior; 4..15 reserved; 16 and above free for callers
+ *   per row        r = row0 + i for row i of out: the executed step k for streams 1 and 2, 0 otherwise
+ * Block j covers elements 4j .. 4j + 3 of a sample's row:
+ *   (r0, r1, r2, r3) = Philox4x32-10(counter = (j, r, stream_id, sub_b), key = (seed_b & 0xffffffff, seed_b >> 32))
+ * with the multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57 and the Weyl constants 0x9E3779B9, 0xBB67AE85 (Salmon et al. 2011; Random123's
+ * philox4x32_R at ten rounds).  A round maps the counter (c0, c1, c2, c3) under the key (k0, k1) to
+ *   (hi(M1 c2) ^ c1 ^ k0,  lo(M1 c2),  hi(M0 c0) ^ c3 ^ k1,  lo(M0 c0))
+ * and the key then advances by the Weyl constants.  u(w) = ((w >> 8) + 0.5) 2^-24 lies strictly inside (0, 1) and is exact in double (an odd numerator of up to
+ * 25 bits over 2^25: fp32 holds it only below a half).  With
+ * rho = sqrt(-2 ln u(r0)): element 4j = rho cospi(2 u(r1)), element 4j + 1 = rho sinpi(2 u(r1)); elements 4j + 2 and 4j + 3 are the same
+ * from (r2, r3).  Evaluated in double (log, sqrt, sincospi) and rounded to fp32 once, so |z| <= sqrt(50 ln 2) = 5.887.
+ * kind 0: the normals, fp32; kind 1: the raw words r0 .. r3 as uint32 (tests).  out is [rows][batch][n_per_sample], the layout
+ * mkd_sample_eta and mkd_sample_mask take for their noise; elements at or beyond n_per_sample are not written.  16-byte stores where out
+ * is 16-byte aligned and n_per_sample % 4 == 0, scalar stores otherwise, the same bits.  One launch, no context, no scratch, no host
+ * synchronisation, no atomics; capturable.  MKD_ERR_ARG before anything is enqueued: null seeds / out, batch, rows or n_per_sample
+ * < 1, kind outside 0..1, ceil(n_per_sample / 4) or row0 + rows - 1 beyond 32 bits (each is one counter word). */
+int  mkd_noise_fill(const int64_t* seeds, const int32_t* subs, int batch, uint32_t stream_id, uint32_t row0, int rows, int64_t n_per_sample,
+                    int kind, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

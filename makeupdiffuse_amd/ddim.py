@@ -31,6 +31,14 @@ def _check_mask(mask, x0, shape):
         raise ValueError(f'DDIMSampler: mask must be [1 or {B}, 1 or {C}, {H}, {W}], got {tuple(mask.shape)}')
 
 
+def _check_seeds(seeds, batch, noise_dropout=0.0):
+    """seeds= of a sampler call as a noise.Seeds of the batch; dropout draws on the torch generator, so the two do not combine"""
+    from .noise import as_seeds
+    if noise_dropout > 0.0:
+        raise ValueError('seeds: noise_dropout draws on the torch generator and cannot be seeded per sample')
+    return as_seeds(seeds, batch)
+
+
 def _check_rescale(phi) -> float:
     """guidance_rescale (phi of Lin et al. 2023, section 3.4) as a float in [0, 1]"""
     phi = float(phi)
@@ -104,7 +112,10 @@ class DDIMSampler:
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, eta=0.0, temperature=1.0, noise_dropout=0.0,
                x_T=None, log_every_t=100, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
-               verbose=True, guidance_rescale=0.0, **kwargs):
+               verbose=True, guidance_rescale=0.0, seeds=None, **kwargs):
+        """``seeds`` (an int: s, s + 1, ...; one per sample; a noise.Seeds): every draw of the call comes from noise.normal -- x_T on stream
+        0 (unless ``x_T`` is given: it is taken as it is), the eta rows on stream 1, the masked blend's rows on stream 2, row = executed
+        step -- and no torch generator is advanced.  None: the draws below, as ever."""
         for k in ('score_corrector', 'corrector_kwargs', 'dynamic_threshold', 'ucg_schedule'):
             if kwargs.get(k) is not None:
                 raise NotImplementedError(f'DDIMSampler.sample option {k} is not on the MakeupDiffuse path')
@@ -115,8 +126,10 @@ class DDIMSampler:
         mask, x0 = kwargs.get('mask'), kwargs.get('x0')
         _check_mask(mask, x0, size)
         _check_rescale(guidance_rescale)
+        if seeds is not None:
+            seeds = _check_seeds(seeds, batch_size, noise_dropout)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
-        return self.ddim_sampling(conditioning, size, callback=callback, x_T=x_T, log_every_t=log_every_t,
+        return self.ddim_sampling(conditioning, size, callback=callback, x_T=x_T, log_every_t=log_every_t, seeds=seeds,
                                   temperature=temperature, noise_dropout=noise_dropout,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, mask=mask, x0=x0,
@@ -131,13 +144,15 @@ class DDIMSampler:
 
     @torch.no_grad()
     def sample_specs(self, specs, shape, conditioning, x_T=None, unconditional_guidance_scale=None, unconditional_conditioning=None,
-                     temperature=1.0):
+                     temperature=1.0, seeds=None):
         """One ``SampleSpec`` (steps, eta, guidance, t_start) per sample of the batch, all in ONE loop of max(steps) executed steps:
         every sample starts at once and stops after its own steps.  Sample b gets what ``sample(S=steps_b, eta=eta_b,
         unconditional_guidance_scale=guidance_b)`` gives it, bit for bit, with rows 0 .. n_b - 1 of the noise.  Host draw order: x_T
         (unless given), then for each executed step in order one randn of the full batch shape when some active sample has a non-zero
         sigma in it.  The scales come from the specs (``unconditional_guidance_scale`` must stay None); a guided spec needs
-        ``unconditional_conditioning``.  No registered buffer of this sampler is touched."""
+        ``unconditional_conditioning``.  No registered buffer of this sampler is touched.  ``seeds`` (as in ``sample``): x_T on stream 0
+        and, where some step draws, rows 0 .. S_max - 1 of stream 1 for every sample from noise.normal; sample b reads rows 0 .. n_b - 1
+        of its own streams, which is what the uniform call with b's request and b's seed reads."""
         from .batching import build_rows, draw_noise, guided
         if unconditional_guidance_scale is not None:
             raise ValueError('sample_specs: the guidance scale is per sample (SampleSpec.guidance)')
@@ -148,6 +163,16 @@ class DDIMSampler:
         C, H, W = shape
         size = (len(rows), C, H, W)
         device = self.model.device
+        if seeds is not None:
+            from .batching import draw_plan
+            from .noise import STREAM_ETA, STREAM_START, normal
+            seeds = _check_seeds(seeds, len(rows))
+            img = normal(seeds, size[1:], stream=STREAM_START, device=device) if x_T is None else x_T
+            if tuple(img.shape) != size:
+                raise ValueError(f'sample_specs: x_T must be {size}, got {tuple(img.shape)}')
+            plan = draw_plan(rows)
+            noise = normal(seeds, size[1:], stream=STREAM_ETA, rows=len(plan), device=device) if any(plan) else None
+            return fast(img, conditioning, rows, 'ddim', unconditional_conditioning, noise, temperature)
         img = torch.randn(size, device=device) if x_T is None else x_T
         if tuple(img.shape) != size:
             raise ValueError(f'sample_specs: x_T must be {size}, got {tuple(img.shape)}')
@@ -157,18 +182,23 @@ class DDIMSampler:
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, callback=None, log_every_t=100, temperature=1.0, noise_dropout=0.0,
                       unconditional_guidance_scale=1.0, unconditional_conditioning=None, timesteps=None, mask=None, x0=None,
-                      guidance_rescale=0.0):
+                      guidance_rescale=0.0, seeds=None):
         """mask / x0 (UPSTREAM): before step i, img = q_sample(x0, ts) * mask + (1 - mask) * img with a fresh randn_like(x0) drawn
         BEFORE the step's eta draw; mask = 1 keeps x0, no blend after the last step.  intermediates: x_inter / pred_x0 =
         [x_T, one entry per step with index % log_every_t == 0 or index == total_steps - 1], from the in-library loop's trace or the
-        step loop alike.  guidance_rescale = phi in [0, 1], engaged with guidance and phi > 0."""
+        step loop alike.  guidance_rescale = phi in [0, 1], engaged with guidance and phi > 0.  seeds: as in sample."""
         _check_mask(mask, x0, tuple(shape))
         phi = _check_rescale(guidance_rescale)
         if unconditional_conditioning is None or unconditional_guidance_scale == 1.0:
             phi = 0.0          # no unconditional half: not engaged
         device = self.model.device
         b = shape[0]
-        img = torch.randn(shape, device=device) if x_T is None else x_T
+        if seeds is not None:
+            from .noise import STREAM_BLEND, STREAM_ETA, STREAM_START, normal
+            seeds = _check_seeds(seeds, b, noise_dropout)
+            img = normal(seeds, tuple(shape)[1:], stream=STREAM_START, device=device) if x_T is None else x_T
+        else:
+            img = torch.randn(shape, device=device) if x_T is None else x_T
         if timesteps is None:
             timesteps = self.ddim_timesteps
         intermediates = {'x_inter': [img], 'pred_x0': [img]}
@@ -184,7 +214,17 @@ class DDIMSampler:
             sig = self.ddim_sigmas[:total_steps]
             kw = {}
             stochastic = float(sig.abs().max()) != 0.0
-            if stochastic or mask is not None:
+            if seeds is not None:
+                # one launch per stream fills every row: row k is executed step k (a row whose sigma is 0 is multiplied by it)
+                if stochastic:
+                    kw = dict(sigmas=sig, noise=normal(seeds, tuple(shape)[1:], stream=STREAM_ETA, rows=total_steps, device=device),
+                              temperature=temperature)
+                if mask is not None:
+                    sa, s1 = self._q_tables()
+                    kw.update(x0=x0, mask=mask, q_sqrt_ac=[float(sa[int(t)]) for t in timesteps],
+                              q_sqrt_1m_ac=[float(s1[int(t)]) for t in timesteps],
+                              q_noise=normal(seeds, tuple(x0.shape)[1:], stream=STREAM_BLEND, rows=total_steps, device=device))
+            elif stochastic or mask is not None:
                 draws, q_draws = [], []
                 for i in range(total_steps):
                     if mask is not None:
@@ -222,9 +262,9 @@ class DDIMSampler:
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
             if mask is not None:
-                img = self._q_blend(x0, int(step), mask, img)
+                img = self._q_blend(x0, int(step), mask, img, seeds=seeds, row=i)
             img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, temperature=temperature,
-                                              noise_dropout=noise_dropout,
+                                              noise_dropout=noise_dropout, seeds=seeds, row=i,
                                               unconditional_guidance_scale=unconditional_guidance_scale,
                                               unconditional_conditioning=unconditional_conditioning, guidance_rescale=phi)
             if callback:
@@ -238,15 +278,16 @@ class DDIMSampler:
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1.0, noise_dropout=0.0, score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1.0, unconditional_conditioning=None, dynamic_threshold=None,
-                      guidance_rescale=0.0):
+                      guidance_rescale=0.0, seeds=None, row=0):
+        """seeds / row: the step's eta noise is noise.normal(seeds, stream 1, row) instead of a torch draw (row = the executed step)"""
         return self._step(x, c, t, index, repeat_noise, use_original_steps, quantize_denoised, temperature, noise_dropout,
                           score_corrector, corrector_kwargs, unconditional_guidance_scale, unconditional_conditioning,
-                          dynamic_threshold, _check_rescale(guidance_rescale))
+                          dynamic_threshold, _check_rescale(guidance_rescale), seeds, row)
 
     # One DDIM step; shared by p_sample_ddim and MKDDIMSampler.denoising_step (same arithmetic, SURVEY.md finding 6).
     def _step(self, x, c, t, index, repeat_noise, use_original_steps, quantize_denoised, temperature, noise_dropout,
               score_corrector, corrector_kwargs, unconditional_guidance_scale, unconditional_conditioning,
-              dynamic_threshold, guidance_rescale=0.0):
+              dynamic_threshold, guidance_rescale=0.0, seeds=None, row=0):
         b, device = x.shape[0], x.device
         if getattr(self.model, 'parameterization', 'eps') != 'eps':
             raise NotImplementedError("only parameterization 'eps' (yaml :50) is supported")
@@ -263,7 +304,12 @@ class DDIMSampler:
         sigmas = self.ddim_sigmas_for_original_num_steps if use_original_steps else self.ddim_sigmas
         a_t, a_prev, sigma_t, s1m_t = float(alphas[index]), float(alphas_prev[index]), float(sigmas[index]), float(s1m[index])
         noise = None
-        if sigma_t != 0.0:
+        if sigma_t != 0.0 and seeds is not None:
+            from .noise import STREAM_ETA, normal
+            if repeat_noise:
+                raise ValueError('seeds: repeat_noise shares one draw across the batch and cannot be seeded per sample')
+            noise = normal(_check_seeds(seeds, b, noise_dropout), tuple(x.shape)[1:], stream=STREAM_ETA, row0=int(row), device=device)
+        elif sigma_t != 0.0:
             noise = noise_like(x.shape, device, repeat_noise)
             if noise_dropout > 0.0:
                 noise = torch.nn.functional.dropout(noise, p=noise_dropout)
@@ -306,11 +352,16 @@ class DDIMSampler:
     def _q_tables(self):
         return self.model.sqrt_alphas_cumprod, self.model.sqrt_one_minus_alphas_cumprod
 
-    def _q_blend(self, x0, step, mask, img):
-        """img = q_sample(x0, step) * mask + (1 - mask) * img with a fresh randn_like(x0); on the device through the model's hook"""
+    def _q_blend(self, x0, step, mask, img, seeds=None, row=0):
+        """img = q_sample(x0, step) * mask + (1 - mask) * img with a fresh randn_like(x0) (seeds: noise.normal on stream 2 at ``row``, the
+        executed step); on the device through the model's hook"""
         sa, s1 = self._q_tables()
         a, b = float(sa[step]), float(s1[step])
-        noise = torch.randn_like(x0)
+        if seeds is not None:
+            from .noise import STREAM_BLEND, normal
+            noise = normal(_check_seeds(seeds, x0.shape[0]), tuple(x0.shape)[1:], stream=STREAM_BLEND, row0=int(row), device=x0.device)
+        else:
+            noise = torch.randn_like(x0)
         return self._q_sample_blend(x0, noise, a, b, mask, img)
 
     def _q_sample_blend(self, x0, noise, a, b, mask=None, img=None):
@@ -322,14 +373,18 @@ class DDIMSampler:
         return q if mask is None else q * mask + (1.0 - mask) * img
 
     @torch.no_grad()
-    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None):
+    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None, seeds=None):
         """UPSTREAM DDIMSampler.stochastic_encode: sqrt(ddim_alphas)[t] x0 + ddim_sqrt_one_minus_alphas[t] noise (the full DDPM tables
-        with use_original_steps); t [B] indexes the table.  With decode(x, cond, t_start) it gives img2img."""
+        with use_original_steps); t [B] indexes the table.  With decode(x, cond, t_start) it gives img2img.  ``seeds`` (without ``noise``): the
+        noise is noise.normal on stream 2, row 0, and no torch generator is advanced; ``noise`` given: taken as it is."""
         if use_original_steps:
             sa, s1 = self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod
         else:
             sa, s1 = torch.sqrt(self.ddim_alphas), self.ddim_sqrt_one_minus_alphas
-        if noise is None:
+        if noise is None and seeds is not None:
+            from .noise import STREAM_BLEND, normal
+            noise = normal(_check_seeds(seeds, x0.shape[0]), tuple(x0.shape)[1:], stream=STREAM_BLEND, device=x0.device)
+        elif noise is None:
             noise = torch.randn_like(x0)
         t = torch.as_tensor(t).reshape(-1).cpu().long()
         if t.numel() == 1:

@@ -403,12 +403,18 @@ class BaseMakeUpDiffuse:
         return self.scale_factor * z
 
     @torch.no_grad()
-    def get_z(self, x: torch.Tensor) -> torch.Tensor:
+    def get_z(self, x: torch.Tensor, seeds=None) -> torch.Tensor:
         """reference diffmk/makeup_diffuse.py:37-39 = get_first_stage_encoding(encode_first_stage(x)) as ONE mkd_encode; the noise of
-        sample() is drawn as DiagonalGaussianDistribution.sample draws it (torch.randn on the default CPU generator)."""
+        sample() is drawn as DiagonalGaussianDistribution.sample draws it (torch.randn on the default CPU generator).  ``seeds`` (an int:
+        s, s + 1, ...; one per sample; a noise.Seeds): the noise is noise.normal on stream 3 instead, on the device, and no generator
+        is advanced."""
         eng = self._require_encoder()
         f = 2 ** (len(eng.vae_enc_cfg.ch_mult) - 1)
         B, _, H, W = x.shape
+        if seeds is not None:
+            from ..noise import STREAM_POSTERIOR, as_seeds, normal
+            noise = normal(as_seeds(seeds, B), (eng.vae_enc_cfg.z_channels, H // f, W // f), stream=STREAM_POSTERIOR, device=self.device)
+            return eng.encode(x, self.scale_factor, noise)
         noise = torch.randn((B, eng.vae_enc_cfg.z_channels, H // f, W // f))
         return eng.encode(x, self.scale_factor, noise)
 
@@ -439,8 +445,13 @@ class DiagonalGaussianPosterior:
         self.std = torch.exp(0.5 * self.logvar)
         self.var = torch.exp(self.logvar)
 
-    def sample(self) -> torch.Tensor:
+    def sample(self, seeds=None) -> torch.Tensor:
         # drawn on the default CPU generator and moved, as upstream's sample() does: RNG consumption matches
+        # seeds (an int: s, s + 1, ...; one per sample; a noise.Seeds): noise.normal on stream 3, no generator is advanced
+        if seeds is not None:
+            from ..noise import STREAM_POSTERIOR, as_seeds, normal
+            nz = normal(as_seeds(seeds, self.mean.shape[0]), tuple(self.mean.shape)[1:], stream=STREAM_POSTERIOR, device=self.parameters.device)
+            return self.mean + self.std * nz
         return self.mean + self.std * torch.randn(self.mean.shape).to(device=self.parameters.device)
 
     def mode(self) -> torch.Tensor:
@@ -458,7 +469,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                  seg_key: str = 'nonmakeup_seg', makeup_score: bool = False, ref_seg_key: str = 'makeup_seg', sampler: str = 'ddim',
                  solver_order: int = 2, unipc_corrector: bool = True, paste_background: bool = False, paste_feather: int = 0, denoise_rows: bool = False,
                  log_every_t: int = 100, guidance_rescale: float = 0.0, face_parser=None, parser_lut=None, parse_size: int = 512,
-                 *args, **kwargs):
+                 seed: Optional[int] = None, *args, **kwargs):
         if int(log_every_t) < 1:
             raise ValueError(f'log_every_t must be >= 1, got {log_every_t}')
         if not 0.0 <= float(guidance_rescale) <= 1.0:
@@ -471,7 +482,14 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             raise ValueError('solver_order must be 1, 2 or 3')
         if int(parse_size) != parse_size or int(parse_size) % 32 or not 64 <= int(parse_size) <= 1024:
             raise ValueError(f'parse_size must be a multiple of 32 in 64..1024, got {parse_size!r}')
+        if seed is not None:
+            from ..noise import as_seeds
+            as_seeds(seed, 1)          # (an integer in 0 .. 2^64 - 1, or ValueError)
         super().__init__(*args, **kwargs)
+        # per-sample seeds (noise.py): the default ``seeds=`` of test_step / log_results, transfer_regions, transfer_specs, interpolate
+        # and transfer_photos -- sample (or source photo) i of a call gets seed + i, every draw comes from noise.normal and no torch
+        # generator is advanced.  None: the torch draws, call for call as before
+        self.seed = seed
         # label maps from the images themselves (face_parser.FaceParser, or anything with its parse()): a batch that lacks seg_key /
         # ref_seg_key gets them from the source / reference image parsed at parse_size; label maps the caller brings always win.
         # None: every path is as before (a missing label map is a KeyError)
@@ -512,6 +530,24 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         self.test_pairs: list = []
         self.test_pairs_file = 'test_0412_pairs.txt'
 
+    def _seeds(self, seeds, n: int):
+        """the noise.Seeds of a call over n samples: its ``seeds=``, else the model's ``seed``, else None (the torch draws)"""
+        if seeds is None:
+            seeds = self.seed
+        if seeds is None:
+            return None
+        from ..noise import as_seeds
+        return as_seeds(seeds, n)
+
+    def _start_latent(self, x_T, sd, n: int, h: int, w: int) -> torch.Tensor:
+        """x_T as given; else noise.normal on stream 0 with seeds; else a torch draw on the device generator"""
+        if x_T is not None:
+            return x_T.to(self.device)
+        if sd is not None:
+            from ..noise import STREAM_START, normal
+            return normal(sd, (self.channels, h, w), stream=STREAM_START, device=self.device)
+        return torch.randn(n, self.channels, h, w, device=self.device)
+
     def on_test_epoch_start(self) -> None:
         self.eval()
         self.test_pairs = []
@@ -548,11 +584,13 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                 batch[seg_k] = self.parse_images(self.get_origin_img_input(batch, img_k))
 
     @torch.no_grad()
-    def log_results(self, batch: dict, batch_idx: int, x_T: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    def log_results(self, batch: dict, batch_idx: int, x_T: Optional[torch.Tensor] = None, seeds=None) -> Dict[str, torch.Tensor]:
         """The sampler calls of reference log_results (:391-410): a plain 50-step pass and a CFG pass whose
         unconditional branch keeps the SAME hint (uc_cat = c_cat, :401).  Returns latents (and decoded images
         once a first_stage_model is attached); the teacher / reconstruction rows are out of scope.  With a face parser attached, label
-        maps the batch lacks are added to ``batch`` (_fill_segs)."""
+        maps the batch lacks are added to ``batch`` (_fill_segs).  ``seeds`` (default: the model's ``seed``; one per pair, or an int s
+        for s, s + 1, ...): every draw of both passes and of fix_background's encoder comes from noise.normal; both passes start from the
+        same seeded x_T, as they do from a given ``x_T``."""
         use_ddim = self.ddim_steps is not None
         log: Dict[str, torch.Tensor] = {}
         self._check_unipc_masked()
@@ -570,8 +608,11 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                                         'makeup/%s.png' % nm.split('&')[1]])
         b = c_cat.shape[0]
         extra = {} if x_T is None else {'x_T': x_T}
+        sd = self._seeds(seeds, b)
+        if sd is not None:
+            extra['seeds'] = sd
         if self.fix_background:
-            x0, mask = self.background_latents(batch, c['src_img'])
+            x0, mask = self.background_latents(batch, c['src_img'], seeds=sd)
             extra.update(x0=x0, mask=mask)
             log['mask_latent'] = mask
         if self.paste_background:
@@ -611,13 +652,14 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         return log
 
     @torch.no_grad()
-    def transfer_specs(self, batch: dict, specs, x_T: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    def transfer_specs(self, batch: dict, specs, x_T: Optional[torch.Tensor] = None, seeds=None) -> Dict[str, torch.Tensor]:
         """One ``batching.SampleSpec`` per pair of the batch (steps, eta, guidance, t_start, order), sampled together: requests that
         differ in step count, strength, guidance scale or eta share one batch.  As in log_results the conditioning is the pair's hint
         and text, and a guided sample's unconditional branch keeps the SAME hint.  One pass per prepared-batch form: the samples whose
         guidance is 1 run as one per-sample loop on the batch-B conditioning, the others as one on [uncond; cond]; each pass is one
         loop of its longest member.  The ``sampler`` attribute picks the solver.  Returns samples_latent (rows in batch order) and,
-        with a first stage, the decoded samples."""
+        with a first stage, the decoded samples.  ``seeds`` (default: the model's ``seed``): one per pair, beside the specs; each pass
+        gets its members' seeds, so a pair's noise does not depend on which pass it runs in."""
         from ..batching import SampleSpec
         if self.sampler == 'unipc':
             UniPCSampler(self).sample_specs()          # (NotImplementedError: the per-sample loop runs DDIM and DPM-Solver++ only)
@@ -630,9 +672,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         if self.sampler not in ('ddim', 'dpmpp'):
             raise ValueError(f"sampler must be 'ddim' or 'dpmpp', got {self.sampler!r}")
         h, w = c_cat.shape[2] // 8, c_cat.shape[3] // 8
-        if x_T is None:
-            x_T = torch.randn(b, self.channels, h, w, device=self.device)
-        x_T = x_T.to(self.device)
+        sd = self._seeds(seeds, b)
+        x_T = self._start_latent(x_T, sd, b, h, w)
         if tuple(x_T.shape) != (b, self.channels, h, w):
             raise ValueError(f'transfer_specs: x_T must be {(b, self.channels, h, w)}, got {tuple(x_T.shape)}')
         smp = DPMSolverSampler(self) if self.sampler == 'dpmpp' else DDIMSampler(self)
@@ -647,7 +688,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             if want_guided:
                 uc = {'c_concat': cond['c_concat'], 'c_crossattn': [self.get_unconditional_conditioning(len(idx))]}
             lat[sel] = smp.sample_specs([specs[i] for i in idx], (self.channels, h, w), cond, x_T=x_T[sel].contiguous(),
-                                        unconditional_conditioning=uc)
+                                        unconditional_conditioning=uc, **({} if sd is None else {'seeds': sd.take(idx)}))
         out = {'samples_latent': lat}
         if self.has_first_stage:
             out['samples'] = self.decode_first_stage(lat)
@@ -699,8 +740,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                                                        feather=self.paste_feather, return_alpha=True)
 
     @torch.no_grad()
-    def background_latents(self, batch: dict, src: torch.Tensor):
-        """fix_background: x0 = get_z(src * 2 - 1) and the latent mask of batch[seg_key] over background_classes."""
+    def background_latents(self, batch: dict, src: torch.Tensor, seeds=None):
+        """fix_background: x0 = get_z(src * 2 - 1) and the latent mask of batch[seg_key] over background_classes.  seeds: get_z's."""
         if not self.first_stage_encoder:
             raise ValueError('fix_background needs the first-stage encoder: construct with first_stage_encoder=True')
         self._fill_segs(batch)
@@ -711,16 +752,17 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         if lw <= 0 or seg.shape[-1] % lw:
             raise ValueError(f'fix_background: label map width {seg.shape[-1]} is not a multiple of the latent width {lw}')
         mask = self.latent_mask_from_labels(seg, self.background_classes, seg.shape[-1] // lw, self.background_threshold)
-        x0 = self.get_z(src * 2.0 - 1.0)
+        x0 = self.get_z(src * 2.0 - 1.0, **({} if seeds is None else {'seeds': seeds}))
         return x0, mask
 
     @torch.no_grad()
     def interpolate(self, batch: dict, alphas, x_T: Optional[torch.Tensor] = None, ref2_key: str = 'ref_img2',
-                    unconditional_guidance_scale: float = 1.0) -> Dict[str, torch.Tensor]:
+                    unconditional_guidance_scale: float = 1.0, seeds=None) -> Dict[str, torch.Tensor]:
         """Makeup interpolation between two references (README.md:23-25 shows the figure; the reference has no code, so the
         definition is this build's: the ControlNet hint embeddings E(src||ref1), E(src||ref2) are blended per sample with
         weight alpha before the 50-step loop).  batch holds src_img, ref_img, `ref2_key`, txt_emb for
-        N pairs; every pair is sampled at every alpha -> latents [N*len(alphas), 4, h, w] ordered pair-major."""
+        N pairs; every pair is sampled at every alpha -> latents [N*len(alphas), 4, h, w] ordered pair-major.  ``seeds`` (default: the
+        model's ``seed``): one per PAIR; without ``x_T`` the pair's start noise is noise.normal on stream 0, shared by its alphas."""
         src = self.get_origin_img_input(batch, self.src_img_key)
         r1 = self.get_origin_img_input(batch, self.ref_img_key)
         r2 = self.get_origin_img_input(batch, ref2_key)
@@ -732,9 +774,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         ctxr, al = rep(ctx), A.repeat(n).to(self.device)
         eng = self._require_engine()
         h, w = src.shape[2] // 8, src.shape[3] // 8
-        if x_T is None:
-            x_T = torch.randn(n, self.channels, h, w, device=self.device)
-        x_T = rep(x_T.to(self.device))           # the same start noise for every alpha of a pair
+        x_T = rep(self._start_latent(x_T, self._seeds(seeds, n), n, h, w))           # the same start noise for every alpha of a pair
         if self.paste_background:
             self._check_paste(batch, 'paste_background')
         sch = self.schedule
@@ -760,7 +800,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
     @torch.no_grad()
     def transfer_regions(self, batch: dict, refs: Dict[str, str], strengths: Optional[dict] = None, base: str = 'ref', feather: int = 1,
                          x_T: Optional[torch.Tensor] = None, unconditional_guidance_scale: float = 1.0,
-                         paste_outside: bool = False, guidance_rescale: Optional[float] = None) -> Dict[str, torch.Tensor]:
+                         paste_outside: bool = False, guidance_rescale: Optional[float] = None, seeds=None) -> Dict[str, torch.Tensor]:
         """Region-wise makeup transfer from several references (partial transfer as SCGAN / EleGANt / PSGAN offer it; the reference
         has no code for it, so the definition is this build's): ``refs`` maps the user regions 'eye', 'lip', 'skin' to the
         batch keys of their reference images; the ControlNet hint embeddings E(src||ref_r) are blended PER LATENT PIXEL with the
@@ -772,7 +812,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         keep the source's pixels over background_classes (mask_pixel holds the weights); ``paste_outside`` (base='source' only) then also
         pastes the source over everything that belongs to NONE of the chosen regions, feathered by paste_feather (weights: mask_outside),
         so that "lips only" leaves the rest of the face alone.  ``guidance_rescale`` (default: the model's setting) is the phi of the
-        guided pass, engaged with unconditional_guidance_scale != 1 and phi > 0."""
+        guided pass, engaged with unconditional_guidance_scale != 1 and phi > 0.  ``seeds`` (default: the model's ``seed``): one per pair;
+        without ``x_T`` the start noise is noise.normal on stream 0 -- the only draw of this deterministic pass."""
         from .. import regions as rg
         phi = float(self.guidance_rescale if guidance_rescale is None else guidance_rescale)
         if not 0.0 <= phi <= 1.0:
@@ -794,6 +835,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                 raise KeyError(f"transfer_regions: the batch has no reference image under '{refs[r]}' (region '{r}')")
         n = int(batch[self.src_img_key].shape[0])
         rg.strength_rows(strengths, regs, n)                  # (validates before anything reaches the device)
+        sd = self._seeds(seeds, n)
         eng = self._require_engine()
         src = self.get_origin_img_input(batch, self.src_img_key)
         base_img = src if base == 'source' else self.get_origin_img_input(batch, self.ref_img_key)
@@ -806,9 +848,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         if factor < 1 or (seg.shape[-2], seg.shape[-1]) != (factor * h, factor * w):
             raise ValueError(f'transfer_regions: label map {tuple(seg.shape[-2:])} is not a multiple of the latent {(h, w)}')
         weights = rg.region_weights_from_seg(seg.to(self.device), regs, factor, int(feather), strengths)
-        if x_T is None:
-            x_T = torch.randn(n, self.channels, h, w, device=self.device)
-        x_T = x_T.to(self.device)
+        x_T = self._start_latent(x_T, sd, n, h, w)
         scale = float(unconditional_guidance_scale)
         if scale != 1.0:          # [uncond; cond] with the SAME hints and weights in both halves (log_results: uc_cat = c_cat)
             u = self.get_unconditional_conditioning(n)
@@ -843,10 +883,11 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                                                                            feather=self.paste_feather, return_alpha=True)
         return out
 
-    def _photo_pass(self, src_photos, ref_photos, src_regions, ref_regions, src_segs, x_T, size, batch, phi):
+    def _photo_pass(self, src_photos, ref_photos, src_regions, ref_regions, src_segs, x_T, size, batch, phi, seeds=None):
         """the single pass of transfer_photos for one batch of (photo, region) pairs on the device: crop-resize both, sample, decode,
         paste_source -> (the decoded images [n,3,size,size], the source crops img01 the paste needs).  A region is a box or a
-        photo.Frame (photo.crop_regions: a batch without a rolled frame is one crop_resize call)"""
+        photo.Frame (photo.crop_regions: a batch without a rolled frame is one crop_resize call).  seeds: a noise.Seeds over the pairs (the
+        photo's seed, the face's rank as the sub-stream) for every draw of the pass, or None"""
         eng = self._require_engine()
         self._check_unipc_masked()
         need_seg = self.fix_background or self.paste_background
@@ -859,9 +900,11 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         ctx = self.get_cond_txt_coding(batch if batch is not None else {self.cond_stage_key: ['makeup transfer'] * n})
         cond = {'c_concat': [torch.cat((src, ref), 1)], 'c_crossattn': [ctx]}
         extra = {} if x_T is None else {'x_T': x_T.to(self.device)}
+        if seeds is not None:
+            extra['seeds'] = seeds
         seg_batch = {self.seg_key: cs.labels if (src_segs is not None or not need_seg) else self.parse_images(src)}
         if self.fix_background:
-            x0, mask = self.background_latents(seg_batch, src)
+            x0, mask = self.background_latents(seg_batch, src, seeds=seeds)
             extra.update(x0=x0, mask=mask)
         scale = float(self.unconditional_guidance_scale)
         if scale > 1.0:           # log_results' guided pass: the unconditional branch keeps the SAME hint
@@ -880,7 +923,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                         x_T: Optional[torch.Tensor] = None, size: int = 256, batch: Optional[dict] = None,
                         guidance_rescale: Optional[float] = None, max_faces: Optional[int] = None, face_batch: int = 8,
                         return_faces: bool = False, own_pixels: bool = False, own_feather: int = 2, align: bool = False,
-                        min_roll: float = 5.0, guided_paste=None):
+                        min_roll: float = 5.0, guided_paste=None, seeds=None):
         """Makeup transfer on photographs at their own resolution: ``src_photos`` / ``ref_photos`` are uint8 [H,W,3] tensors of any
         size (lists; the photos of a call may differ in size) with a face box (x0, y0, w, h) each.  Both boxes are crop-resized to
         ``size`` on the device (photo.crop_resize: Pillow's antialiased bilinear bytes / 255, what PairFolderDataset gives for that
@@ -927,7 +970,12 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
 
         ``guided_paste`` (a photo.GuidedPaste; None: everything above, call for call): EVERY paste of the call -- single face, max_faces,
         own_pixels, align -- upsamples the makeup difference under the photo's own luminance edges instead of bilinearly
-        (mkd_paste_photo_guided / mkd_paste_frame_guided), so lipstick stops at the lip line of the PHOTO and not a model pixel past it."""
+        (mkd_paste_photo_guided / mkd_paste_frame_guided), so lipstick stops at the lip line of the PHOTO and not a model pixel past it.
+
+        ``seeds`` (default: the model's ``seed``; None: the torch draws, call for call): one seed per SOURCE PHOTO (an int s: s, s + 1,
+        ...).  The face of rank k of photo i draws everything -- start latent, eta rows, blend rows, the encoder's posterior -- from
+        noise.normal with (seed_i, sub = k), so a face's noise does not depend on face_batch, on max_faces or on the other photos of
+        the call.  Without max_faces every face is rank 0."""
         from .. import photo
         from ..components import owner_weights
         from ..face_parser import find_boxes, find_faces
@@ -962,6 +1010,9 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         n = len(src_photos)
         if len(ref_photos) != n:
             raise ValueError(f'{n} source photos but {len(ref_photos)} reference photos')
+        sd = self._seeds(seeds, n) if n else None
+        if sd is not None and sd.subs is not None:
+            raise ValueError('transfer_photos: seeds are per source photo; the sub-stream is the rank of the face and cannot be given')
         if (src_boxes is None or ref_boxes is None) and self.face_parser is None:
             raise ValueError('transfer_photos: src_boxes and ref_boxes are needed (only an attached face parser can find the faces)')
 
@@ -1052,8 +1103,13 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                         for k, v in batch.items() if k in ('txt_emb', 'txt_tokens', self.cond_stage_key)}
             if many and x_T is not None:
                 start = x_T[c0:c0 + len(chunk)]
+            face_sd = None
+            if sd is not None and chunk:          # the photo's seed, the face's rank
+                from ..noise import Seeds
+                face_sd = Seeds(tuple(sd.seeds[i] for i in pick), tuple(k for _, k in chunk))
             img, src = self._photo_pass([src_photos[i] for i in pick], [ref_photos[i] for i in pick], [faces[i][k] for i, k in chunk],
-                                        [refs[i] for i in pick], None if src_segs is None else [src_segs[i] for i in pick], start, size, text, phi)
+                                        [refs[i] for i in pick], None if src_segs is None else [src_segs[i] for i in pick], start, size, text, phi,
+                                        **({} if face_sd is None else {'seeds': face_sd}))
             imgs.append(img)
             srcs.append(src)
         if N:
@@ -1069,10 +1125,10 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                 eng.paste_regions([out[items[j][0]] for j in sel], [faces[items[j][0]][rank] for j in sel], *rows, feather, weights, guided_paste)
         return (out, faces) if return_faces else out
 
-    def test_step(self, batch: dict, batch_idx: int, x_T: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    def test_step(self, batch: dict, batch_idx: int, x_T: Optional[torch.Tensor] = None, seeds=None) -> Dict[str, torch.Tensor]:
         """reference diffusion_makeup.py:332-341.  x_T (not in the reference, which always draws fresh noise): fixed start
-        noise for both sampling passes, so that runs can be compared."""
-        images = self.log_results(batch, batch_idx, x_T=x_T)
+        noise for both sampling passes, so that runs can be compared.  seeds: log_results'."""
+        images = self.log_results(batch, batch_idx, x_T=x_T, **({} if seeds is None else {'seeds': seeds}))
         for k in images:
             if isinstance(images[k], torch.Tensor):
                 images[k] = images[k].detach().cpu()

@@ -77,11 +77,12 @@ class BaseModel(BaseMakeUpDiffuse):
         return img.clamp(0, 1)
 
     @torch.no_grad()
-    def invert_image(self, img: torch.Tensor, c: dict, t_enc: Optional[int] = None) -> torch.Tensor:
+    def invert_image(self, img: torch.Tensor, c: dict, t_enc: Optional[int] = None, seeds=None) -> torch.Tensor:
         """The inversion that produces ``src_inv`` / ``ref_inv`` (reference pre_dataset.py InvRec): z = get_z(img * 2 - 1), then
         the DDIM inversion ``encode(z, c, t_enc)`` under c_crossattn with c_concat = None (the UNet alone).  img [B,3,H,W] in
-        [0, 1]; t_enc defaults to iter_finetune, the step count generate_image reconstructs with.  Needs first_stage_encoder=True."""
-        z = self.get_z(img * 2.0 - 1.0)
+        [0, 1]; t_enc defaults to iter_finetune, the step count generate_image reconstructs with.  Needs first_stage_encoder=True.  ``seeds``
+        (get_z's): the posterior sample comes from noise.normal on stream 3, the inversion itself is deterministic."""
+        z = self.get_z(img * 2.0 - 1.0, **({} if seeds is None else {'seeds': seeds}))
         cond = dict(c_crossattn=list(c['c_crossattn']), c_concat=None)
         inv, _ = self._sampler().encode(z, cond, self.iter_finetune if t_enc is None else int(t_enc))
         return inv

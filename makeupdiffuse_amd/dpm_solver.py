@@ -14,7 +14,7 @@ import math
 import numpy as np
 import torch
 
-from .ddim import DDIMSampler, _check_mask, _check_rescale, rescale_guided_eps
+from .ddim import DDIMSampler, _check_mask, _check_rescale, _check_seeds, rescale_guided_eps
 
 __all__ = ['DPMSolverSampler', 'dpmpp_coefficients']
 
@@ -82,10 +82,12 @@ class DPMSolverSampler:
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, x_T=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
-               order=2, lower_order_final=True, callback=None, mask=None, x0=None, log_every_t=100, guidance_rescale=0.0, **kw):
+               order=2, lower_order_final=True, callback=None, mask=None, x0=None, log_every_t=100, guidance_rescale=0.0, seeds=None,
+               **kw):
         """intermediates as DDIMSampler's: x_inter / pred_x0 = [x_T, one entry per step with index % log_every_t == 0 or the first
         executed one] (pred_x0: the solver's m_k), from the in-library loop's trace or the step loop alike.  guidance_rescale = phi in
-        [0, 1], engaged with guidance and phi > 0."""
+        [0, 1], engaged with guidance and phi > 0.  ``seeds`` (as DDIMSampler.sample's): x_T from noise.normal on
+        stream 0 unless given, the masked blend's rows on stream 2 (row = executed step); no torch generator is advanced."""
         if kw.get('eta') not in (None, 0, 0.0):
             raise NotImplementedError('DPMSolverSampler is deterministic: eta is not an option of DPM-Solver++')
         for k in self._REJECTED:
@@ -103,21 +105,32 @@ class DPMSolverSampler:
             phi = 0.0          # no unconditional half: not engaged
         if int(log_every_t) < 1:
             raise ValueError(f'log_every_t must be >= 1, got {log_every_t}')
+        if seeds is not None:
+            seeds = _check_seeds(seeds, batch_size)
         self.make_schedule(S, verbose=False)
-        img = torch.randn(size, device=self.model.device) if x_T is None else x_T
+        img = self._start(size, x_T, seeds)
         intermediates = {'x_inter': [img], 'pred_x0': [img]}
         img = self._loop(img, conditioning, len(self.ddim_timesteps), unconditional_guidance_scale, unconditional_conditioning, order,
-                         lower_order_final, callback, mask, x0, trace=(int(log_every_t), intermediates), phi=phi)
+                         lower_order_final, callback, mask, x0, trace=(int(log_every_t), intermediates), phi=phi, seeds=seeds)
         if len(intermediates['x_inter']) == 1:          # (a hook that keeps no trace)
             intermediates['x_inter'].append(img)
         return img, intermediates
 
+    def _start(self, size, x_T, seeds):
+        """the start latent: x_T as given, else noise.normal on stream 0 with seeds, else a torch draw"""
+        if x_T is not None:
+            return x_T
+        if seeds is not None:
+            from .noise import STREAM_START, normal
+            return normal(seeds, size[1:], stream=STREAM_START, device=self.model.device)
+        return torch.randn(size, device=self.model.device)
+
     @torch.no_grad()
     def sample_specs(self, specs, shape, conditioning, x_T=None, unconditional_guidance_scale=None, unconditional_conditioning=None,
-                     temperature=1.0):
+                     temperature=1.0, seeds=None):
         """``DDIMSampler.sample_specs`` on this solver: one ``SampleSpec`` (steps, guidance, order, t_start; eta must be 0) per sample
         in one loop of max(steps) evaluations.  Sample b gets the bits of ``sample(S=steps_b, order=order_b,
-        unconditional_guidance_scale=guidance_b)``."""
+        unconditional_guidance_scale=guidance_b)``.  ``seeds``: x_T from noise.normal on stream 0 unless given."""
         from .batching import build_rows, guided
         if unconditional_guidance_scale is not None:
             raise ValueError('sample_specs: the guidance scale is per sample (SampleSpec.guidance)')
@@ -129,7 +142,7 @@ class DPMSolverSampler:
         fast = self._ddim._rows_hook('sample_specs')
         C, H, W = shape
         size = (len(rows), C, H, W)
-        img = torch.randn(size, device=self.model.device) if x_T is None else x_T
+        img = self._start(size, x_T, None if seeds is None else _check_seeds(seeds, len(rows)))
         if tuple(img.shape) != size:
             raise ValueError(f'sample_specs: x_T must be {size}, got {tuple(img.shape)}')
         return fast(img, conditioning, rows, 'dpmpp', unconditional_conditioning, None, 1.0)
@@ -148,7 +161,7 @@ class DPMSolverSampler:
 
     # the loop over the first n table entries, newest first
     # trace = (log_every_t, the intermediates dict to append to) or None; phi: the engaged guidance rescale (0: off)
-    def _loop(self, img, cond, n, scale, uc, order, lower_order_final, callback, mask, x0, trace=None, phi=0.0):
+    def _loop(self, img, cond, n, scale, uc, order, lower_order_final, callback, mask, x0, trace=None, phi=0.0, seeds=None):
         timesteps = self.ddim_timesteps[:n]
         a = [float(v) for v in self.ddim_alphas[:n]]
         ap = [float(v) for v in self.ddim_alphas_prev[:n]]
@@ -159,9 +172,13 @@ class DPMSolverSampler:
             kw = {}
             if mask is not None:
                 sa, s1 = self._ddim._q_tables()
+                if seeds is not None:
+                    from .noise import STREAM_BLEND, normal
+                    q_noise = normal(seeds, tuple(x0.shape)[1:], stream=STREAM_BLEND, rows=n, device=x0.device)
+                else:
+                    q_noise = torch.stack([torch.randn_like(x0) for _ in range(n)])
                 kw = dict(x0=x0, mask=mask, q_sqrt_ac=[float(sa[int(t)]) for t in timesteps],
-                          q_sqrt_1m_ac=[float(s1[int(t)]) for t in timesteps],
-                          q_noise=torch.stack([torch.randn_like(x0) for _ in range(n)]))
+                          q_sqrt_1m_ac=[float(s1[int(t)]) for t in timesteps], q_noise=q_noise)
             if trace is not None:
                 kw['log_every_t'] = trace[0]
             if phi != 0.0:
@@ -186,7 +203,7 @@ class DPMSolverSampler:
             step = int(timesteps[index])
             ts = torch.full((img.shape[0],), step, device=img.device, dtype=torch.long)
             if mask is not None:
-                img = self._ddim._q_blend(x0, step, mask, img)
+                img = self._ddim._q_blend(x0, step, mask, img, seeds=seeds, row=k)
             e_c, e_u = self._ddim._eps(img, cond, ts, scale, uc)
             rescale = e_u is not None and phi != 0.0
             if on_device:

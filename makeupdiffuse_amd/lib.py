@@ -242,6 +242,7 @@ SIGNATURES = {
     'mkd_parser_stem': (_I, [_P, _P, _P, C.POINTER(_F), C.POINTER(_F), _P, _P, _I, _I, _I, _I, _P]),
     'mkd_channel_gate': (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P]),
     'mkd_gate_apply_bf16': (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    'mkd_noise_fill': (_I, [_P, _P, _I, C.c_uint32, C.c_uint32, _I, _L, _I, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -17,7 +17,7 @@ import math
 import numpy as np
 import torch
 
-from .ddim import DDIMSampler, _check_rescale, rescale_guided_eps
+from .ddim import DDIMSampler, _check_rescale, _check_seeds, rescale_guided_eps
 
 __all__ = ['UniPCSampler', 'unipc_coefficients']
 
@@ -156,10 +156,11 @@ class UniPCSampler:
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, x_T=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
                order=2, lower_order_final=True, corrector=True, callback=None, mask=None, x0=None, log_every_t=100, guidance_rescale=0.0,
-               **kw):
+               seeds=None, **kw):
         """intermediates as DDIMSampler's: x_inter / pred_x0 = [x_T, one entry per step with index % log_every_t == 0 or the first
         executed one] (x_inter: the predicted latent x~_{k+1} after the step; pred_x0: the solver's m_k), from the in-library loop's
-        trace or the step loop alike.  guidance_rescale = phi in [0, 1], engaged with guidance and phi > 0."""
+        trace or the step loop alike.  guidance_rescale = phi in [0, 1], engaged with guidance and phi > 0.  ``seeds``
+        (as DDIMSampler.sample's): x_T from noise.normal on stream 0 unless given -- this solver's only draw; no torch generator is advanced."""
         if kw.get('eta') not in (None, 0, 0.0):
             raise NotImplementedError('UniPCSampler is deterministic: eta is not an option of UniPC')
         for k in self._REJECTED:
@@ -179,8 +180,14 @@ class UniPCSampler:
             phi = 0.0          # no unconditional half: not engaged
         if int(log_every_t) < 1:
             raise ValueError(f'log_every_t must be >= 1, got {log_every_t}')
+        if seeds is not None:
+            seeds = _check_seeds(seeds, batch_size)
         self.make_schedule(S, verbose=False)
-        img = torch.randn(size, device=self.model.device) if x_T is None else x_T
+        if x_T is None and seeds is not None:
+            from .noise import STREAM_START, normal
+            img = normal(seeds, size[1:], stream=STREAM_START, device=self.model.device)
+        else:
+            img = torch.randn(size, device=self.model.device) if x_T is None else x_T
         intermediates = {'x_inter': [img], 'pred_x0': [img]}
         img = self._loop(img, conditioning, len(self.ddim_timesteps), unconditional_guidance_scale, unconditional_conditioning, order,
                          lower_order_final, corrector, callback, trace=(int(log_every_t), intermediates), phi=phi)

@@ -75,6 +75,10 @@ def build_parser():
     ap.add_argument('--tokenizer', default=None, help='local CLIP tokenizer directory (vocab.json + merges.txt): prompts then go through the text encoder')
     ap.add_argument('--seed', type=int, default=None, help='start noise x_T drawn per PAIR from seed + pair index (results independent of '
                     'batch size / sharding); default: torch.randn like the reference')
+    ap.add_argument('--device-noise', action='store_true', help='with --seed S: pair i draws EVERYTHING on the device from seed S + i (the '
+                    'counter-based generator of makeupdiffuse_amd.noise: start latent, eta rows, the blend rows of --fix-background, the '
+                    "encoder's posterior sample; with --photos the face's rank is the sub-stream), so a pair's result does not depend on the "
+                    'batch, the sharding or what ran before; without this flag --seed keeps its host draw of the start latent')
     ap.add_argument('--txt-emb', default=None, help='.pt/.safetensors with a [1,77,768] tensor: the CLIP embedding of the prompt (offline stand-in)')
     ap.add_argument('--fix-background', action='store_true', help="keep the source's background, teeth and hair (label map "
                     "nonmakeup_seg from <data-root>/scgan_segs, a synthetic one otherwise; needs the first-stage encoder)")
@@ -190,6 +194,11 @@ def main():
         raise SystemExit('--region-strength / --region-feather / --region-base / --region-paste-outside only apply with --region-refs')
     if args.region_paste_outside and args.region_base != 'source':
         raise SystemExit('--region-paste-outside needs --region-base source')
+    if args.device_noise:
+        if args.seed is None:
+            build_parser().error('--device-noise needs --seed S (pair i draws from seed S + i)')
+        if not 0 <= args.seed < 2 ** 64 - (1 << 40):
+            build_parser().error('--device-noise: --seed must lie in 0 .. 2^64 - 2^40 (seed + pair index is a 64-bit seed)')
     if not 0 <= args.paste_feather <= 16:
         raise SystemExit('--paste-feather must be 0..16 image pixels')
     if args.paste_feather and not (args.paste_background or args.region_paste_outside):
@@ -317,18 +326,20 @@ def main():
             if use_clip:
                 del batch['txt_emb']          # 'txt' -> tokenizer -> mkd_clip_encode
         x_T = None
-        if args.seed is not None:
+        # --device-noise: pair i's seed is --seed + i wherever the pair is drawn for; the model then draws everything on the device
+        seeded = {'seeds': [args.seed + i for i in range(b0, b1)]} if args.device_noise else {}
+        if args.seed is not None and not args.device_noise:
             h8 = args.res // 8
             x_T = torch.cat([torch.randn(1, model.channels, h8, h8, generator=torch.Generator().manual_seed(args.seed + i))
                              for i in range(b0, b1)]).cuda(local)
-        out = model.test_step(batch, b0, x_T=x_T)
+        out = model.test_step(batch, b0, x_T=x_T, **seeded)
         model.on_test_batch_end(out, batch, b0)
         if region_refs:
             for r, img in region_imgs.items():
                 batch['region_ref_' + r] = img.unsqueeze(0).expand(b1 - b0, -1, -1, -1).contiguous()
             reg = model.transfer_regions(batch, {r: 'region_ref_' + r for r in region_refs}, strengths=region_strength,
                                          feather=args.region_feather, x_T=x_T, base=args.region_base,
-                                         paste_outside=args.region_paste_outside)
+                                         paste_outside=args.region_paste_outside, **seeded)
             out['samples_regions_latent'] = reg['samples_latent'].detach().cpu()
             if 'samples' in reg:
                 out['samples_regions'] = torch.clamp(reg['samples'].detach().cpu(), -1.0, 1.0)
@@ -339,7 +350,7 @@ def main():
             specs = [SampleSpec(steps=(steps_list[i % len(steps_list)] if steps_list else model.ddim_steps),
                                 guidance=(guidance_list[i % len(guidance_list)] if guidance_list else 1.0), order=model.solver_order)
                      for i in range(n)]
-            sp = model.transfer_specs(batch, specs, x_T=x_T)
+            sp = model.transfer_specs(batch, specs, x_T=x_T, **seeded)
             out['samples_specs_latent'] = sp['samples_latent'].detach().cpu()
             if 'samples' in sp:
                 out['samples_specs'] = torch.clamp(sp['samples'].detach().cpu(), -1.0, 1.0)
@@ -352,7 +363,7 @@ def main():
             if args.max_faces is None:
                 photos = model.transfer_photos(items['src_photo'], items['ref_photo'], None if find else items['src_box'], None if find else items['ref_box'],
                                                src_segs=items.get('src_seg'), feather=args.photo_feather, x_T=x_T, size=args.res, batch=text,
-                                               guided_paste=guided)
+                                               guided_paste=guided, **seeded)
             else:
                 K = args.max_faces
                 ref_boxes = items['ref_box']
@@ -367,7 +378,7 @@ def main():
                     faces = [[cut(b) for b in photo_ds.faces.get(photo_ds.pairs[i][0], [items['src_box'][i - b0]])[:K]] for i in range(b0, b1)]
                     ref_boxes = [cut(photo_ds.faces.get(photo_ds.pairs[i][1], [ref_boxes[i - b0]])[0]) for i in range(b0, b1)]
                 x_F = None
-                if args.seed is not None:          # one start latent per face: seed + pair index, then the face's rank
+                if args.seed is not None and not args.device_noise:          # one start latent per face: seed + pair index, then the face's rank
                     h8 = args.res // 8
                     x_F = [torch.randn(1, model.channels, h8, h8, generator=torch.Generator().manual_seed((args.seed + i) * 64 + k))
                            for i in range(b0, b1) for k in range(len(faces[i - b0]))]
@@ -378,7 +389,7 @@ def main():
                 # (--own-pixels: the model finds the same faces again, with their owner map; the count above sizes the start latents)
                 photos, faces = model.transfer_photos(items['src_photo'], items['ref_photo'], None if args.own_pixels else faces, ref_boxes,
                                                       src_segs=items.get('src_seg'), feather=args.photo_feather, x_T=x_F, size=args.res, batch=text,
-                                                      max_faces=K, return_faces=True, guided_paste=guided, **own)
+                                                      max_faces=K, return_faces=True, guided_paste=guided, **own, **seeded)
                 print(f'[rank {rank}] faces per photo: {[len(f) for f in faces]}', flush=True)
             if guided is not None:
                 print(f'[rank {rank}] guided paste: radius {guided.radius}, sigma {guided.sigma:g}', flush=True)
