@@ -659,6 +659,32 @@ int mkd_paste_frame(const mkd_photo_frame_desc* descs, int n, int S, const float
  * mkd_paste_photo_guided.  No context; ONE launch, no scratch, no allocation, no host sync, no atomics. */
 int mkd_paste_frame_guided(const mkd_photo_frame_desc* descs, int n, int S, const float* t, const float* s01, int feather, const float* w,
                            int wh, int ww, int radius, float sigma, void* stream);
+
+/* ---- video clips: the makeup difference filtered over time (BUILD-DEFINED; the reference makes up single images) ---- */
+/* A motion-aware recursive filter of d = (t + 1) / 2 - s01 between the decode and the paste of one frame step, for the n faces of that
+ * step: t, s01 and t_out are fp32 [n, 3, S, S] with the layout and meaning of mkd_paste_photo (s01 = the crop the model saw, which
+ * follows the face, so pixel p is the same place of the face in every frame).  The filtered difference goes back into t_out, which
+ * may be t (it must not overlap s01): every paste kernel then sees it, unchanged.  The state is two caller-owned fp32 pools,
+ * D_* [pool, 3, S, S] and Y_* [pool, S, S]: face b reads slot slot_in[b] of D_in / Y_in and writes slot slot_out[b] of D_out / Y_out;
+ * slot_in and slot_out are HOST arrays [n], copied into the kernel argument block by value.  slot_in[b] = -1: the face has no previous
+ * frame.  The caller ping-pongs the pools: the _in pools, D_out and Y_out must not overlap.  fp32, every operator below ONE correctly
+ * rounded operation, nothing contracted.  Per model pixel p of face b: gb_c = clamp(rintf(s01_c * 255.0f), 0, 255) as an integer;
+ * Y = 77 gb_r + 150 gb_g + 29 gb_b (the luminance of mkd_paste_photo_guided, an integer <= 65280); Y_out[p] = float(Y);
+ * d_c = ((t_c + 1.0f) * 0.5f) - s01_c.  slot_in[b] < 0: D_out_c = d_c, t_out_c has the bits of t_c, and no byte of the _in pools is
+ * read for this face.  Otherwise, with N = (2 R + 1)^2 and the window (clamp(y + dy, 0, S - 1), clamp(x + dx, 0, S - 1)), dy, dx =
+ * -R .. R (edges replicated: always N taps): A = sum |Y(w) - (int)Y_in(w)| in 32-bit integers (exact: any order gives the same bits);
+ * inv = 1.0f / ((256.0f * tau) * float(N)); q = float(A) * inv (a uniform change of L grey levels gives q = L / tau);
+ * c = 1.0f / (1.0f + q * q) (a Cauchy confidence: no exp, never zero); k = beta * c; D_c = d_c + k * (Din_c - d_c); D_out_c = D_c;
+ * t_out_c = ((s01_c + D_c) * 2.0f) - 1.0f.  On a still clip k * 0 = 0 and D = d bit for bit; under stationary noise the temporal
+ * variance falls to (1 - beta) / (1 + beta) of the input's.  MKD_ERR_ARG before anything is enqueued: a null pointer, n outside
+ * 1 .. MKD_PHOTO_MAX_BATCH, S outside 8..1024, radius outside 0..2, beta not in (0, 0.95], tau not finite in [0.5, 1e6], pool outside
+ * 1..65536, a slot_in that is neither -1 nor a slot of the pool, a slot_out outside the pool or repeated, overlapping pools.  One thread per
+ * model pixel, 16 x 16 per workgroup, the luminance of the tile plus halo of both frames staged in LDS.  No context; ONE launch, no
+ * scratch, no allocation, no host sync, no atomics. */
+int mkd_temporal_diff(const float* t, const float* s01, int n, int S, const float* D_in, const float* Y_in, const int32_t* slot_in,
+                      float* D_out, float* Y_out, const int32_t* slot_out, int pool, float beta, float tau, int radius, float* t_out,
+                      void* stream);
+
 /* Every face's roll and its extent in its own frame.  48 bytes: n_a / n_b = the pixels of the component in the class sets a / b (the
  * two eyes), (cq, sq) = the face's "right" axis as integers of length 16384 (16384, 0: upright), umin .. vmax = the component's extent
  * along that axis and the one across it, in units of 1 / (2 S 16384) photo pixel. */

@@ -17,6 +17,7 @@ import torch
 from ..ddim import DDIMSampler
 from ..dpm_solver import DPMSolverSampler
 from ..unipc import UniPCSampler
+from ..video import TemporalFilter
 from ..engine import ClipConfig, MkdEngine, NetConfig, VaeConfig
 from ..lib import MkdError
 from ..schedule import DDIMSchedule
@@ -1124,6 +1125,43 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                 weights = None if owner is None else owner_weights(owner, [(items[j][0], rank) for j in sel], own_feather)
                 eng.paste_regions([out[items[j][0]] for j in sel], [faces[items[j][0]][rank] for j in sel], *rows, feather, weights, guided_paste)
         return (out, faces) if return_faces else out
+
+    def video_session(self, ref_photo, ref_box=None, seed=None, size: int = 256, feather: int = 8, max_faces: int = 4, face_batch: int = 8,
+                      align: bool = False, min_roll: float = 5.0, guided_paste=None, temporal=TemporalFilter(), box_smooth: float = 0.5,
+                      tracker=None, **more):
+        """VIDEO CLIPS (this rule is this build's): a session that makes up the frames of ONE clip with the face of ``ref_photo`` (one
+        uint8 [H,W,3] tensor, cropped once: ``ref_box``, or the largest face the attached parser finds) without the three kinds of
+        flicker transfer_photos has on a sequence.  ``session.push(frames, src_boxes=None, src_segs=None)`` takes the next frames (a
+        list of uint8 [H,W,3] tensors; ``src_boxes`` one LIST of boxes per frame, None: the parser finds the faces) and returns the
+        made-up frames as clones.  Inside one push: (1) the faces of all pushed frames are found; (2) a video.FaceTracker (``tracker``,
+        default FaceTracker()) gives every face a track id and video.smooth_frame (``box_smooth`` = gamma in [0, 0.95]) its crop, frame
+        by frame on the host; (3) all (frame, track) items of the push are cropped, sampled and decoded in chunks of ``face_batch``
+        through the single pass of transfer_photos, untouched; (4) every item draws with noise.Seeds((seed,), (track id,)) -- ``seed``
+        (default: the model's ``seed``; None: the torch draws) is the CLIP's and the track the sub-stream, so one person has one start
+        latent, one set of eta rows, blend rows and posterior draws for the whole clip, however the detector orders the faces;
+        (5) frame by frame in order, ONE mkd_temporal_diff launch over the frame's faces (``temporal``, a video.TemporalFilter,
+        default TemporalFilter(): a motion-aware recursive filter of the makeup difference in the face's own coordinates), then the
+        pastes of transfer_photos, rank by rank, largest first.  A track that was not in the previous frame (new, or back after a gap)
+        starts its filter and its smoothing over and keeps its noise.  ``temporal=None`` makes no mkd_temporal_diff launch and
+        ``box_smooth=0`` leaves the regions as they were found; with both and ``seed=None`` a push is
+        transfer_photos(max_faces=...) on its frames, call for call.  ``batch``: ONE row of the text fields get_input reads, the text
+        of the clip.  ``session.last`` (a list of video.FrameRecord) tells what the last push did with each frame.  The host
+        decisions (tracks, ids, sub-streams, regions) and the noise do not depend on how the clip is split into pushes.  Decoded images
+        are equal across BATCH sizes up to rounding only (the GEMM planner picks tiles by shape), so with a seed every chunk is
+        sampled at ``face_batch``: a ragged chunk is filled up with repeats of its last item, whose rows are dropped, and the made-up
+        frames do not depend on the split either (choose face_batch near faces x frames per push: a one-face push costs a whole
+        chunk).  Without a seed the ragged chunk runs as it is, as in transfer_photos.  Not combined here, ValueError:
+        ``own_pixels``, per-track references."""
+        from .. import video
+        return video.VideoSession(self, ref_photo, ref_box=ref_box, seed=seed, size=size, feather=feather, max_faces=max_faces,
+                                  face_batch=face_batch, align=align, min_roll=min_roll, guided_paste=guided_paste, temporal=temporal,
+                                  box_smooth=box_smooth, tracker=tracker, **more)
+
+    def transfer_video(self, frames, ref_photo, frame_batch: int = 8, **session_kwargs):
+        """a whole clip: one video_session(ref_photo, **session_kwargs) fed ``frame_batch`` frames at a time (``src_boxes`` /
+        ``src_segs``: per frame, over the whole clip) -> the made-up frames"""
+        from .. import video
+        return video.transfer_video(self, frames, ref_photo, frame_batch, **session_kwargs)
 
     def test_step(self, batch: dict, batch_idx: int, x_T: Optional[torch.Tensor] = None, seeds=None) -> Dict[str, torch.Tensor]:
         """reference diffusion_makeup.py:332-341.  x_T (not in the reference, which always draws fresh noise): fixed start

@@ -1118,6 +1118,13 @@ class MkdEngine:
         from . import photo
         return photo.paste_regions(photos, regions, samples, src01, feather, weights, guided)
 
+    def temporal_diff(self, t: torch.Tensor, s01: torch.Tensor, D_in: torch.Tensor, Y_in: torch.Tensor, slot_in, D_out: torch.Tensor,
+                      Y_out: torch.Tensor, slot_out, filt, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Video clips (include/mkd.h mkd_temporal_diff; video.temporal_diff): the makeup difference of the faces of one frame step
+        filtered over time, between the decode and the paste; one launch"""
+        from . import video
+        return video.temporal_diff(t, s01, D_in, Y_in, slot_in, D_out, Y_out, slot_out, filt, out)
+
     def eps_profile(self, x: torch.Tensor, t: torch.Tensor, csv_path: Optional[str] = None) -> Dict[str, Dict[str, float]]:
         """One eps with HIP events around every launch group -> {kernel class: {ms, flops, launches, bytes, ms_b2b}}: ``bytes`` =
         algorithmic HBM bytes of the memory-bound classes, ``ms_b2b`` = the class's launches replayed back to back between one

@@ -123,6 +123,24 @@ def build_parser():
     ap.add_argument('--guide-radius', type=int, default=1, metavar='R', help='with --guided-paste: the taps reach R + 1 model pixels per side, 0..2')
     ap.add_argument('--guide-sigma', type=float, default=8.0, metavar='S', help='with --guided-paste: the luminance distance, in 8-bit levels '
                     '(0.5 .. 1e6), at which a tap\'s weight has fallen to a half')
+    ap.add_argument('--video', default=None, metavar='DIR', help='a clip INSTEAD of the pair passes: the image files of DIR, in sorted name '
+                    'order, are the frames of one clip (no video container is read); every face keeps ONE noise sub-stream for the clip '
+                    '(tracked identities, --seed is the clip\'s seed on the device), its crop is smoothed over time (--box-smooth) and the '
+                    'makeup difference is filtered over time on the device (mkd_temporal_diff, --temporal-*).  The faces come from '
+                    '--face-parser or from DIR/boxes.txt ("name x0 y0 w h" per face; the line of --video-ref\'s file name is the reference '
+                    'face).  --max-faces (default 4), --align-faces, --guided-paste, --photo-feather and --res apply')
+    ap.add_argument('--video-ref', default=None, metavar='IMAGE', help='with --video: the makeup reference, one photo for every face of the clip')
+    ap.add_argument('--video-out', default=None, metavar='DIR', help='with --video: where the made-up frames go, under their own names '
+                    '(default <out>/video)')
+    ap.add_argument('--temporal-beta', type=float, default=0.8, metavar='B', help='with --video: the weight of the previous frame where '
+                    'nothing moved, in (0, 0.95]; 0: no temporal filter')
+    ap.add_argument('--temporal-tau', type=float, default=4.0, metavar='T', help='with --video: the mean luminance change, in 8-bit levels '
+                    '(0.5 .. 1e6), at which that weight has fallen to a half')
+    ap.add_argument('--temporal-radius', type=int, default=1, metavar='R', help='with --video: the luminance change is taken over a '
+                    '(2 R + 1)^2 window of model pixels, 0..2')
+    ap.add_argument('--box-smooth', type=float, default=0.5, metavar='G', help='with --video: recursive smoothing of every track\'s crop, '
+                    '0..0.95 (0: the crops as they were found)')
+    ap.add_argument('--frame-batch', type=int, default=8, metavar='N', help='with --video: frames per push (all their faces are sampled together)')
     ap.add_argument('--face-parser', default=None, metavar='PATH|random', help='attach the face-parsing network (upstream face-parsing.PyTorch '
                     'state dict, e.g. 79999_iter.pth; "random": seeded random weights, for plumbing runs): label maps that --fix-background, '
                     '--paste-background, --makeup-score, --region-refs and --photos need and <data-root>/scgan_segs does not give are parsed '
@@ -180,6 +198,83 @@ def write_makeup_scores(path, names, out, first):
                     f.write('%s,%s,%s\n' % (names[i], k, ','.join('%.6f' % v for v in row)))
 
 
+IMAGE_EXTS = ('.png', '.jpg', '.jpeg', '.bmp', '.webp')
+
+
+def check_video_args(args):
+    """the --video flags -> None without --video, else dict(names, temporal, box_smooth, frame_batch, out); SystemExit on a bad one"""
+    if not args.video:
+        if (args.video_ref or args.video_out or args.temporal_beta != 0.8 or args.temporal_tau != 4.0 or args.temporal_radius != 1
+                or args.box_smooth != 0.5 or args.frame_batch != 8):
+            raise SystemExit('--video-ref / --video-out / --temporal-* / --box-smooth / --frame-batch only apply with --video')
+        return None
+    from makeupdiffuse_amd import video
+    if not args.video_ref:
+        raise SystemExit('--video needs --video-ref IMAGE (the makeup reference of the clip)')
+    if not os.path.isdir(args.video):
+        raise SystemExit(f'--video: {args.video} is not a directory (the frames are its image files; no video container is read)')
+    if not os.path.isfile(args.video_ref):
+        raise SystemExit(f'--video-ref: {args.video_ref} is not a file')
+    if args.photos or args.own_pixels:
+        raise SystemExit('--video runs instead of the pair passes: --photos / --own-pixels do not combine with it')
+    if args.seed is not None and not 0 <= args.seed < 2 ** 64:
+        raise SystemExit('--video: --seed is the clip\'s 64-bit seed on the device, 0 .. 2^64 - 1')
+    if not args.face_parser and not os.path.exists(os.path.join(args.video, 'boxes.txt')):
+        raise SystemExit('--video needs --face-parser or <DIR>/boxes.txt (one line per face: name x0 y0 w h)')
+    names = sorted(n for n in os.listdir(args.video) if n.lower().endswith(IMAGE_EXTS))
+    if not names:
+        raise SystemExit(f'--video: {args.video} holds no image file ({", ".join(IMAGE_EXTS)})')
+    temporal = None
+    try:
+        if args.temporal_beta != 0.0:
+            temporal = video.TemporalFilter(args.temporal_beta, args.temporal_tau, args.temporal_radius)
+        gamma = video.check_box_smooth(args.box_smooth)
+    except ValueError as e:
+        raise SystemExit(f'--temporal-beta / --temporal-tau / --temporal-radius / --box-smooth: {e}')
+    if args.frame_batch < 1:
+        raise SystemExit('--frame-batch must be >= 1')
+    return dict(names=names, temporal=temporal, box_smooth=gamma, frame_batch=args.frame_batch,
+                out=args.video_out or os.path.join(args.out, 'video'))
+
+
+def clip_text(model, use_clip, txt_emb):
+    """ONE row of text for a clip: the prompt through the text encoder, else --txt-emb, else the seeded stand-in of the pair passes"""
+    if use_clip:
+        return {'txt': ['makeup transfer']}
+    g = torch.Generator().manual_seed(91011)
+    return {'txt_emb': txt_emb if txt_emb is not None else torch.randn(1, 77, model.net_config.context_dim, generator=g)}
+
+
+def run_video(model, args, opts, guided, text):
+    """--video: the frames of opts['names'] through model.transfer_video -> the made-up frames under the same names in opts['out']"""
+    import numpy as np
+    from PIL import Image
+    from makeupdiffuse_amd.photo import read_boxes_multi
+    load = lambda path: torch.from_numpy(np.array(Image.open(path).convert('RGB'), dtype=np.uint8))
+    frames = [load(os.path.join(args.video, n)) for n in opts['names']]
+    ref = load(args.video_ref)
+    src_boxes = ref_box = None
+    bp = os.path.join(args.video, 'boxes.txt')
+    K = 4 if args.max_faces is None else args.max_faces
+    if os.path.exists(bp):          # a boxes file wins over the parser, as with --photos
+        table = read_boxes_multi(bp)
+        cut = (lambda b: b) if args.align_faces else (lambda b: b[:4])
+        src_boxes = [[cut(b) for b in table.get(n, [])[:K]] for n in opts['names']]
+        ref_lines = table.get(os.path.basename(args.video_ref))
+        if ref_lines:
+            ref_box = cut(ref_lines[0])
+        elif not args.face_parser:
+            raise SystemExit(f'--video: {bp} has no line for the reference {os.path.basename(args.video_ref)} and there is no --face-parser to find its face')
+    out = model.transfer_video(frames, ref, frame_batch=opts['frame_batch'], src_boxes=src_boxes, ref_box=ref_box, seed=args.seed, size=args.res,
+                               feather=args.photo_feather, max_faces=K, align=args.align_faces, min_roll=args.min_roll, guided_paste=guided,
+                               temporal=opts['temporal'], box_smooth=opts['box_smooth'], batch=text)
+    os.makedirs(opts['out'], exist_ok=True)
+    for name, img in zip(opts['names'], out):
+        Image.fromarray(img.cpu().numpy()).save(os.path.join(opts['out'], name))
+    print(f'video: {len(out)} frames -> {opts["out"]}', flush=True)
+    return out
+
+
 def main():
     args = build_parser().parse_args()
 
@@ -206,11 +301,11 @@ def main():
     if args.photos and not args.data_root:
         raise SystemExit('--photos needs --data-root with images/ and a pairs file (the photos are read at their own resolution)')
     if args.max_faces is not None:
-        if not args.photos:
+        if not (args.photos or args.video):
             raise SystemExit('--max-faces only applies with --photos')
         if not 1 <= args.max_faces <= 64:
             raise SystemExit('--max-faces must be 1..64')
-        if not args.face_parser and not os.path.exists(os.path.join(args.data_root, 'boxes.txt')):
+        if not args.video and not args.face_parser and not os.path.exists(os.path.join(args.data_root, 'boxes.txt')):
             raise SystemExit('--max-faces needs --face-parser or <data-root>/boxes.txt (one line per face)')
     if args.own_pixels:
         if not args.photos or args.max_faces is None:
@@ -222,7 +317,7 @@ def main():
     elif args.own_feather != 2:
         raise SystemExit('--own-feather only applies with --own-pixels')
     if args.align_faces:
-        if not args.photos or args.max_faces is None:
+        if not args.video and (not args.photos or args.max_faces is None):
             raise SystemExit('--align-faces only applies with --photos --max-faces')
         if not args.min_roll >= 0.0:
             raise SystemExit('--min-roll must be >= 0 degrees')
@@ -230,11 +325,11 @@ def main():
         raise SystemExit('--min-roll only applies with --align-faces (and --photos)')
     if not 0 <= args.photo_feather <= 64:
         raise SystemExit('--photo-feather must be 0..64 photo pixels')
-    if args.photo_feather != 8 and not args.photos:
+    if args.photo_feather != 8 and not (args.photos or args.video):
         raise SystemExit('--photo-feather only applies with --photos')
     guided = None
     if args.guided_paste:
-        if not args.photos:
+        if not (args.photos or args.video):
             raise SystemExit('--guided-paste only applies with --photos')
         from makeupdiffuse_amd.photo import GuidedPaste
         try:
@@ -243,6 +338,7 @@ def main():
             raise SystemExit(f'--guide-radius / --guide-sigma: {e}')
     elif args.guide_radius != 1 or args.guide_sigma != 8.0:
         raise SystemExit('--guide-radius / --guide-sigma only apply with --guided-paste')
+    video_opts = check_video_args(args)
     if args.log_every_t < 1:
         raise SystemExit('--log-every-t must be >= 1')
     if args.log_every_t != 100 and not args.denoise_rows:
@@ -308,6 +404,11 @@ def main():
     if args.txt_emb:
         t = load_state_dict(args.txt_emb)
         txt_emb = (next(iter(t.values())) if isinstance(t, dict) else t).float().reshape(1, 77, -1)
+    if video_opts is not None:          # a clip instead of the pair passes; one process makes it up (a track's filter runs frame after frame)
+        if rank == 0:
+            run_video(model, args, video_opts, guided, clip_text(model, use_clip, txt_emb))
+        mdist.barrier()
+        return
     region_imgs = {r: dataset._load(name) for r, name in region_refs.items()}
     lo, hi = mdist.shard_range(args.pairs, rank, world)
     os.makedirs(args.out, exist_ok=True)
