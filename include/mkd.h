@@ -685,6 +685,29 @@ int mkd_temporal_diff(const float* t, const float* s01, int n, int S, const floa
                       float* D_out, float* Y_out, const int32_t* slot_out, int pool, float beta, float tau, int radius, float* t_out,
                       void* stream);
 
+/* Block-matched motion for mkd_temporal_diff (BUILD-DEFINED): the previous state of the n faces of a frame step, fetched through one
+ * integer displacement per block of model pixels, so that the filter compares this frame with the previous one where the picture went,
+ * not where it was.  s01 [n, 3, S, S], D_in [pool, 3, S, S], Y_in [pool, S, S] and the HOST array slot_in [n] (copied into the kernel
+ * argument block by value; -1: no previous frame) are those of mkd_temporal_diff; Y_in holds luminances (0 .. 65280).  D_w / Y_w are a
+ * third pair of pools of the same shapes; vec_out is a device int32 [n, nb, nb, 2] = (vy, vx) per block, nb = ceil(S / block), or NULL.
+ * Everything is 32-bit integer arithmetic.  Y(p) = 77 gb_r + 150 gb_g + 29 gb_b, gb_c = clamp(rintf(s01_c * 255.0f), 0, 255) (the
+ * luminance of mkd_temporal_diff: 256 units are one grey level); Yp(q) = (int)Y_in[slot][q].  A block is block x block model pixels,
+ * block 8 or 16; a ragged block at the right or bottom edge covers only its N pixels inside the image.  Candidates v = (vy, vx),
+ * vy, vx = -search .. search, search 1..7.  With clamp(p + v) = (clamp(py + vy, 0, S - 1), clamp(px + vx, 0, S - 1)) (edges
+ * replicated): SAD(v) = sum over the block's pixels |Y(p) - Yp(clamp(p + v))|; cost(v) = SAD(v) + penalty * N * (|vy| + |vx|), penalty
+ * 0..65280 in luminance units per pixel per pixel of displacement (the largest cost is 65280 * 256 * 15 < 2^31).  The block's vector
+ * is the lexicographic minimum of (cost, |vy| + |vx|, vy, vx): it does not depend on the order of evaluation, and zero wins every tie
+ * it takes part in.  Then for every pixel p of the block, q = clamp(p + v): D_w[slot][c][p] = D_in[slot][c][q] and Y_w[slot][p] =
+ * Y_in[slot][q], the bits copied; face b writes the slot it reads, slot_in[b].  A face with slot_in[b] < 0 has zero vectors and no
+ * byte of any pool is read or written for it.  The caller passes D_w / Y_w to mkd_temporal_diff as its D_in / Y_in with the same
+ * slot_in.  MKD_ERR_ARG before anything is enqueued: a null s01 / pool / slot_in, n outside 1 .. MKD_PHOTO_MAX_BATCH, S outside
+ * 8..1024, search outside 1..7, block not 8 or 16, penalty outside 0..65280, pool outside 1..65536, a slot_in that is neither -1 nor a
+ * slot of the pool or names a slot twice, D_w / Y_w overlapping D_in / Y_in / s01 or each other.  One workgroup of 256 threads per
+ * 16 x 16 pixel tile, both luminances staged in LDS, candidates spread over threads, the minimum reduced as one packed 64-bit key.
+ * No context; ONE launch, no scratch, no allocation, no host sync, no atomics. */
+int mkd_motion_warp(const float* s01, int n, int S, const float* D_in, const float* Y_in, const int32_t* slot_in, int pool, int search, int block,
+                    int penalty, float* D_w, float* Y_w, int32_t* vec_out, void* stream);
+
 /* Every face's roll and its extent in its own frame.  48 bytes: n_a / n_b = the pixels of the component in the class sets a / b (the
  * two eyes), (cq, sq) = the face's "right" axis as integers of length 16384 (16384, 0: upright), umin .. vmax = the component's extent
  * along that axis and the one across it, in units of 1 / (2 S 16384) photo pixel. */

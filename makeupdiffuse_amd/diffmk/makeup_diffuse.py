@@ -1128,7 +1128,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
 
     def video_session(self, ref_photo, ref_box=None, seed=None, size: int = 256, feather: int = 8, max_faces: int = 4, face_batch: int = 8,
                       align: bool = False, min_roll: float = 5.0, guided_paste=None, temporal=TemporalFilter(), box_smooth: float = 0.5,
-                      tracker=None, **more):
+                      tracker=None, motion=None, **more):
         """VIDEO CLIPS (this rule is this build's): a session that makes up the frames of ONE clip with the face of ``ref_photo`` (one
         uint8 [H,W,3] tensor, cropped once: ``ref_box``, or the largest face the attached parser finds) without the three kinds of
         flicker transfer_photos has on a sequence.  ``session.push(frames, src_boxes=None, src_segs=None)`` takes the next frames (a
@@ -1150,12 +1150,14 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         are equal across BATCH sizes up to rounding only (the GEMM planner picks tiles by shape), so with a seed every chunk is
         sampled at ``face_batch``: a ragged chunk is filled up with repeats of its last item, whose rows are dropped, and the made-up
         frames do not depend on the split either (choose face_batch near faces x frames per push: a one-face push costs a whole
-        chunk).  Without a seed the ragged chunk runs as it is, as in transfer_photos.  Not combined here, ValueError:
-        ``own_pixels``, per-track references."""
+        chunk).  Without a seed the ragged chunk runs as it is, as in transfer_photos.  ``motion`` (a video.MotionSearch, default
+        None: off, every call as before): ONE mkd_motion_warp launch in front of every mkd_temporal_diff launch fetches the previous
+        state through one integer block-matched vector per block, so the filter holds where something moves inside the crop; it
+        needs ``temporal`` (ValueError with temporal=None).  Not combined here, ValueError: ``own_pixels``, per-track references."""
         from .. import video
         return video.VideoSession(self, ref_photo, ref_box=ref_box, seed=seed, size=size, feather=feather, max_faces=max_faces,
                                   face_batch=face_batch, align=align, min_roll=min_roll, guided_paste=guided_paste, temporal=temporal,
-                                  box_smooth=box_smooth, tracker=tracker, **more)
+                                  box_smooth=box_smooth, tracker=tracker, motion=motion, **more)
 
     def transfer_video(self, frames, ref_photo, frame_batch: int = 8, **session_kwargs):
         """a whole clip: one video_session(ref_photo, **session_kwargs) fed ``frame_batch`` frames at a time (``src_boxes`` /

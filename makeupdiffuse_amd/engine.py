@@ -1125,6 +1125,13 @@ class MkdEngine:
         from . import video
         return video.temporal_diff(t, s01, D_in, Y_in, slot_in, D_out, Y_out, slot_out, filt, out)
 
+    def motion_warp(self, s01: torch.Tensor, D_in: torch.Tensor, Y_in: torch.Tensor, slot_in, D_w: torch.Tensor, Y_w: torch.Tensor, ms,
+                    vec_out: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+        """Video clips (include/mkd.h mkd_motion_warp; video.motion_warp): the previous state of the faces of one frame step fetched
+        through one block-matched integer vector per block, in front of temporal_diff; one launch"""
+        from . import video
+        return video.motion_warp(s01, D_in, Y_in, slot_in, D_w, Y_w, ms, vec_out)
+
     def eps_profile(self, x: torch.Tensor, t: torch.Tensor, csv_path: Optional[str] = None) -> Dict[str, Dict[str, float]]:
         """One eps with HIP events around every launch group -> {kernel class: {ms, flops, launches, bytes, ms_b2b}}: ``bytes`` =
         algorithmic HBM bytes of the memory-bound classes, ``ms_b2b`` = the class's launches replayed back to back between one

@@ -164,6 +164,7 @@ SIGNATURES = {
     'mkd_paste_frame': (_I, [C.POINTER(PhotoFrameDescC), _I, _I, _P, _P, _I, _P, _I, _I, _P]),
     'mkd_paste_frame_guided': (_I, [C.POINTER(PhotoFrameDescC), _I, _I, _P, _P, _I, _P, _I, _I, _I, _F, _P]),
     'mkd_temporal_diff': (_I, [_P, _P, _I, _I, _P, _P, C.POINTER(C.c_int32), _P, _P, C.POINTER(C.c_int32), _I, _F, _F, _I, _P, _P]),
+    'mkd_motion_warp': (_I, [_P, _I, _I, _P, _P, C.POINTER(C.c_int32), _I, _I, _I, _I, _P, _P, _P, _P]),
     'mkd_face_frames_scratch_bytes': (C.c_size_t, [_I, _I]),
     'mkd_face_frames': (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(C.c_int32), C.c_uint64, C.c_uint64, _I, _P, _P, _P]),
     'mkd_vae_configure': (_I, [_P, C.POINTER(VaeConfigC)]),

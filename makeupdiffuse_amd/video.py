@@ -5,7 +5,9 @@ an existing call:
   clip (noise.Seeds((seed,), (track id,))) however the detector orders or counts the faces of a frame;
 * ``smooth_frame``: the crop of a track as a recursively smoothed photo.Frame, so that the model does not see the detector's jitter;
 * ``TemporalFilter`` / ``TemporalState`` / ``temporal_diff`` (include/mkd.h mkd_temporal_diff): a motion-aware recursive filter over
-  time of the makeup difference d = (t + 1) / 2 - s01 on the device, between the decode and the paste.
+  time of the makeup difference d = (t + 1) / 2 - s01 on the device, between the decode and the paste;
+* ``MotionSearch`` / ``motion_warp`` (include/mkd.h mkd_motion_warp), off by default: the previous state fetched through one integer
+  block-matched vector per block, so that the filter also holds where something moves inside the crop.
 
 ``VideoSession`` (TestDiffuseModel.video_session) puts them around the model's single photo pass; ``transfer_video`` feeds it a clip.
 The tracker, the smoothing and the slot bookkeeping are host code and need no device; the filter's arithmetic is libmkd's: there is no
@@ -177,10 +179,10 @@ class TemporalFilter(namedtuple('TemporalFilter', 'beta tau radius')):
         return super().__new__(cls, b, ta, int(radius))
 
 
-def _slots(v, n: int, what: str):
+def _slots(v, n: int, what: str, who: str = 'temporal_diff'):
     v = [int(x) for x in v]
     if len(v) != n:
-        raise ValueError(f'temporal_diff: {what} must hold one slot per face ({n}), got {len(v)}')
+        raise ValueError(f'{who}: {what} must hold one slot per face ({n}), got {len(v)}')
     return (C.c_int32 * n)(*v)
 
 
@@ -217,6 +219,64 @@ def temporal_diff(t: torch.Tensor, s01: torch.Tensor, D_in: torch.Tensor, Y_in: 
     return out
 
 
+SEARCH_MAX = 7
+BLOCKS = (8, 16)
+PENALTY_MAX = 65280
+
+
+class MotionSearch(namedtuple('MotionSearch', 'search block penalty')):
+    """Block-matched motion in front of the temporal filter (include/mkd.h mkd_motion_warp).  ``search`` 1..7: a block's displacement
+    is looked for among (2 search + 1)^2 integer vectors; ``block`` 8 or 16 model pixels; ``penalty`` 0..65280 in luminance units
+    (256 = one grey level) per pixel of the block per pixel of displacement: what a vector must gain over a shorter one."""
+    __slots__ = ()
+
+    def __new__(cls, search: int = 3, block: int = 16, penalty: int = 256):
+        for name, v in (('search', search), ('block', block), ('penalty', penalty)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f'MotionSearch: {name} must be an integer, got {v!r}')
+        if not 1 <= int(search) <= SEARCH_MAX:
+            raise ValueError(f'MotionSearch: search must be 1..{SEARCH_MAX} model pixels, got {search!r}')
+        if int(block) not in BLOCKS:
+            raise ValueError(f'MotionSearch: block must be 8 or 16 model pixels, got {block!r}')
+        if not 0 <= int(penalty) <= PENALTY_MAX:
+            raise ValueError(f'MotionSearch: penalty must be 0..{PENALTY_MAX} luminance units, got {penalty!r}')
+        return super().__new__(cls, int(search), int(block), int(penalty))
+
+
+def motion_warp(s01: torch.Tensor, D_in: torch.Tensor, Y_in: torch.Tensor, slot_in: Sequence[int], D_w: torch.Tensor, Y_w: torch.Tensor,
+                ms: MotionSearch, vec_out: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """ONE mkd_motion_warp launch for the n <= photo.MAX_BATCH faces of a frame step: s01 fp32 [n,3,S,S] contiguous on the device; the
+    pools D_* [pool,3,S,S] and Y_* [pool,S,S]; face b reads slot slot_in[b] of the _in pools through its blocks' vectors and writes the
+    SAME slot of D_w / Y_w (-1: no previous frame, nothing read or written).  ``vec_out``: int32 [n, nb, nb, 2] = (vy, vx) per block,
+    nb = ceil(S / block), or None.  Returns ``vec_out``.  Everything the library refuses is a lib.MkdError."""
+    if not isinstance(ms, MotionSearch):
+        raise ValueError(f'motion_warp: ms must be a MotionSearch, got {ms!r}')
+    for name, x in (('s01', s01), ('D_in', D_in), ('Y_in', Y_in), ('D_w', D_w), ('Y_w', Y_w)):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError(f'motion_warp: {name} must be a contiguous fp32 tensor')
+        if x.device.type != 'cuda':
+            raise _lib.MkdError(f'motion_warp: {name} must be on a HIP device (there is no CPU implementation)')
+    if s01.dim() != 4 or s01.shape[1] != 3 or s01.shape[2] != s01.shape[3]:
+        raise ValueError(f's01 must be [n,3,S,S], got {tuple(s01.shape)}')
+    n, S = int(s01.shape[0]), int(s01.shape[2])
+    pool = int(D_in.shape[0]) if D_in.dim() == 4 else -1
+    for name, x, shape in (('D_in', D_in, (pool, 3, S, S)), ('Y_in', Y_in, (pool, S, S)), ('D_w', D_w, (pool, 3, S, S)), ('Y_w', Y_w, (pool, S, S))):
+        if tuple(x.shape) != shape:
+            raise ValueError(f'motion_warp: {name} must be {list(shape)} (the pools hold the same number of slots), got {tuple(x.shape)}')
+    if vec_out is not None:
+        nb = -(-S // ms.block)
+        if not isinstance(vec_out, torch.Tensor) or vec_out.dtype != torch.int32 or not vec_out.is_contiguous() or tuple(vec_out.shape) != (n, nb, nb, 2):
+            raise ValueError(f'motion_warp: vec_out must be a contiguous int32 tensor [{n}, {nb}, {nb}, 2]')
+        if vec_out.device.type != 'cuda':
+            raise _lib.MkdError('motion_warp: vec_out must be on a HIP device')
+    p = lambda x: C.c_void_p(None if x is None else x.data_ptr())
+    with torch.cuda.device(s01.device):
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(_lib.load().mkd_motion_warp(p(s01), n, S, p(D_in), p(Y_in), _slots(slot_in, n, 'slot_in', 'motion_warp'), pool, ms.search, ms.block, ms.penalty,
+                                               p(D_w), p(Y_w), p(vec_out), st), 'mkd_motion_warp')
+    return vec_out
+
+
 class SlotPlan:
     """The slot bookkeeping of a TemporalState, host only: which slot of the ``_in`` pools holds the state of a track after the last
     frame step.  ``assign(ids, restarted)`` -> (slot_in, slot_out) of this step: face j writes slot j; it reads the slot it wrote in
@@ -241,16 +301,22 @@ class SlotPlan:
 class TemporalState:
     """The state of a TemporalFilter over a clip: the two pools of mkd_temporal_diff (the filtered difference D [pool,3,S,S] and the
     luminance Y [pool,S,S] of every track's last frame), which it sizes to ``capacity`` slots -- the alive tracks -- and grows by
-    reallocation, the slots (SlotPlan) and the swap of the pools after every frame.  ``step`` is one frame."""
+    reallocation, the slots (SlotPlan) and the swap of the pools after every frame.  ``step`` is one frame.  With ``motion`` (a
+    MotionSearch) it owns a third pair of pools as well: every step first fetches the previous state through block-matched vectors
+    (motion_warp) and the filter reads that; ``motion_launches`` counts those launches, ``last_vectors`` keeps the last step's."""
 
-    def __init__(self, filt: TemporalFilter, size: int, device, capacity: int = 4):
+    def __init__(self, filt: TemporalFilter, size: int, device, capacity: int = 4, motion: Optional[MotionSearch] = None):
         if not isinstance(filt, TemporalFilter):
             raise ValueError(f'TemporalState: filt must be a TemporalFilter, got {filt!r}')
-        self.filt, self.S, self.device = filt, photo._check_size(size), torch.device(device)
+        if motion is not None and not isinstance(motion, MotionSearch):
+            raise ValueError(f'TemporalState: motion must be a MotionSearch or None, got {motion!r}')
+        self.filt, self.S, self.device, self.motion = filt, photo._check_size(size), torch.device(device), motion
         self.plan = SlotPlan()
         self.capacity = 0
         self.launches = 0
-        self._in = self._out = None
+        self.motion_launches = 0
+        self.last_vectors: Optional[torch.Tensor] = None          # with motion: int32 [n, nb, nb, 2] = (vy, vx) of the last step's faces
+        self._in = self._out = self._warp = None
         self._grow(max(1, int(capacity)))
 
     def _grow(self, capacity: int) -> None:
@@ -260,6 +326,8 @@ class TemporalState:
             nin[0][:self.capacity].copy_(self._in[0])
             nin[1][:self.capacity].copy_(self._in[1])
         self._in, self._out, self.capacity = nin, nout, capacity
+        if self.motion is not None:       # the third pair: the _in pools fetched through the vectors (rewritten in every step)
+            self._warp = new()
 
     def step(self, ids: Sequence[int], t: Optional[torch.Tensor], s01: Optional[torch.Tensor], restarted: Optional[Sequence[bool]] = None,
              alive: int = 0) -> Optional[torch.Tensor]:
@@ -275,9 +343,17 @@ class TemporalState:
         t = t.to(device=self.device, dtype=torch.float32).contiguous()
         s01 = s01.to(device=self.device, dtype=torch.float32).contiguous()
         out = torch.empty_like(t)
+        prev = self._in
+        if self.motion is not None:
+            nb = -(-self.S // self.motion.block)
+            self.last_vectors = torch.empty((n, nb, nb, 2), dtype=torch.int32, device=self.device)
+            prev = self._warp
         for b0 in range(0, n, photo.MAX_BATCH):
             b1 = min(n, b0 + photo.MAX_BATCH)
-            temporal_diff(t[b0:b1], s01[b0:b1], self._in[0], self._in[1], slot_in[b0:b1], self._out[0], self._out[1], slot_out[b0:b1], self.filt,
+            if self.motion is not None:
+                motion_warp(s01[b0:b1], self._in[0], self._in[1], slot_in[b0:b1], prev[0], prev[1], self.motion, self.last_vectors[b0:b1])
+                self.motion_launches += 1
+            temporal_diff(t[b0:b1], s01[b0:b1], prev[0], prev[1], slot_in[b0:b1], self._out[0], self._out[1], slot_out[b0:b1], self.filt,
                           out=out[b0:b1])
             self.launches += 1
         self._in, self._out = self._out, self._in
@@ -297,7 +373,8 @@ class VideoSession:
 
     def __init__(self, model, ref_photo, ref_box=None, seed=None, size: int = 256, feather: int = 8, max_faces: int = 4, face_batch: int = 8,
                  align: bool = False, min_roll: float = 5.0, guided_paste=None, temporal=TemporalFilter(), box_smooth: float = 0.5,
-                 tracker: Optional[FaceTracker] = None, own_pixels: bool = False, batch: Optional[dict] = None):
+                 tracker: Optional[FaceTracker] = None, own_pixels: bool = False, batch: Optional[dict] = None,
+                 motion: Optional[MotionSearch] = None):
         from .face_parser import find_faces
         if own_pixels:
             raise ValueError('video_session: own_pixels is not combined with video (a track has no owner map across frames)')
@@ -305,6 +382,10 @@ class VideoSession:
             raise ValueError('video_session: ONE reference photo (a uint8 [H,W,3] tensor) serves every track; per-track references are not supported')
         if temporal is not None and not isinstance(temporal, TemporalFilter):
             raise ValueError(f'video_session: temporal must be a video.TemporalFilter or None, got {temporal!r}')
+        if motion is not None and not isinstance(motion, MotionSearch):
+            raise ValueError(f'video_session: motion must be a video.MotionSearch or None, got {motion!r}')
+        if motion is not None and temporal is None:
+            raise ValueError('video_session: motion compensates the temporal filter: it needs temporal (a video.TemporalFilter), got temporal=None')
         if guided_paste is not None and not isinstance(guided_paste, photo.GuidedPaste):
             raise ValueError(f'guided_paste must be a photo.GuidedPaste or None, got {guided_paste!r}')
         if tracker is not None and not isinstance(tracker, FaceTracker):
@@ -348,7 +429,7 @@ class VideoSession:
         else:
             self.ref_region = self._region(ref_box)
         self.tracker = tracker if tracker is not None else FaceTracker()
-        self.state = None if temporal is None else TemporalState(temporal, self.size, model.device, capacity=K)
+        self.state = None if temporal is None else TemporalState(temporal, self.size, model.device, capacity=K, motion=motion)
         self._hat: Dict[int, object] = {}          # alive tracks: id -> the smoothed region of the track's last frame
         self.frames_seen = 0
         self.chunks: List[Tuple[int, int]] = []          # the last push: (items, batch it was sampled at) per chunk

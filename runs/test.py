@@ -138,6 +138,12 @@ def build_parser():
                     '(0.5 .. 1e6), at which that weight has fallen to a half')
     ap.add_argument('--temporal-radius', type=int, default=1, metavar='R', help='with --video: the luminance change is taken over a '
                     '(2 R + 1)^2 window of model pixels, 0..2')
+    ap.add_argument('--video-motion', type=int, default=None, metavar='R', help='with --video and a temporal filter: block-matched motion in '
+                    'front of the filter (mkd_motion_warp): the previous frame\'s state is fetched through one integer vector per block, '
+                    'searched within +-R model pixels, 1..7 (default: off)')
+    ap.add_argument('--video-motion-block', type=int, default=16, metavar='8|16', help='with --video-motion: the block side in model pixels')
+    ap.add_argument('--video-motion-penalty', type=int, default=256, metavar='P', help='with --video-motion: what a vector must gain per pixel '
+                    'of the block and pixel of displacement, in luminance units (256 = one grey level), 0..65280')
     ap.add_argument('--box-smooth', type=float, default=0.5, metavar='G', help='with --video: recursive smoothing of every track\'s crop, '
                     '0..0.95 (0: the crops as they were found)')
     ap.add_argument('--frame-batch', type=int, default=8, metavar='N', help='with --video: frames per push (all their faces are sampled together)')
@@ -205,8 +211,8 @@ def check_video_args(args):
     """the --video flags -> None without --video, else dict(names, temporal, box_smooth, frame_batch, out); SystemExit on a bad one"""
     if not args.video:
         if (args.video_ref or args.video_out or args.temporal_beta != 0.8 or args.temporal_tau != 4.0 or args.temporal_radius != 1
-                or args.box_smooth != 0.5 or args.frame_batch != 8):
-            raise SystemExit('--video-ref / --video-out / --temporal-* / --box-smooth / --frame-batch only apply with --video')
+                or args.box_smooth != 0.5 or args.frame_batch != 8 or args.video_motion is not None):
+            raise SystemExit('--video-ref / --video-out / --temporal-* / --box-smooth / --frame-batch / --video-motion only apply with --video')
         return None
     from makeupdiffuse_amd import video
     if not args.video_ref:
@@ -233,7 +239,18 @@ def check_video_args(args):
         raise SystemExit(f'--temporal-beta / --temporal-tau / --temporal-radius / --box-smooth: {e}')
     if args.frame_batch < 1:
         raise SystemExit('--frame-batch must be >= 1')
-    return dict(names=names, temporal=temporal, box_smooth=gamma, frame_batch=args.frame_batch,
+    motion = None
+    if args.video_motion is None:
+        if args.video_motion_block != 16 or args.video_motion_penalty != 256:
+            raise SystemExit('--video-motion-block / --video-motion-penalty only apply with --video-motion R')
+    else:
+        if temporal is None:
+            raise SystemExit('--video-motion compensates the temporal filter: it does not combine with --temporal-beta 0')
+        try:
+            motion = video.MotionSearch(args.video_motion, args.video_motion_block, args.video_motion_penalty)
+        except ValueError as e:
+            raise SystemExit(f'--video-motion / --video-motion-block / --video-motion-penalty: {e}')
+    return dict(names=names, temporal=temporal, motion=motion, box_smooth=gamma, frame_batch=args.frame_batch,
                 out=args.video_out or os.path.join(args.out, 'video'))
 
 
@@ -267,7 +284,7 @@ def run_video(model, args, opts, guided, text):
             raise SystemExit(f'--video: {bp} has no line for the reference {os.path.basename(args.video_ref)} and there is no --face-parser to find its face')
     out = model.transfer_video(frames, ref, frame_batch=opts['frame_batch'], src_boxes=src_boxes, ref_box=ref_box, seed=args.seed, size=args.res,
                                feather=args.photo_feather, max_faces=K, align=args.align_faces, min_roll=args.min_roll, guided_paste=guided,
-                               temporal=opts['temporal'], box_smooth=opts['box_smooth'], batch=text)
+                               temporal=opts['temporal'], box_smooth=opts['box_smooth'], batch=text, motion=opts['motion'])
     os.makedirs(opts['out'], exist_ok=True)
     for name, img in zip(opts['names'], out):
         Image.fromarray(img.cpu().numpy()).save(os.path.join(opts['out'], name))
