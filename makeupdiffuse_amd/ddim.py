@@ -1,15 +1,19 @@
 """Stock DDIM sampler (host logic): what `from ldm.models.diffusion.ddim import *` gives the reference at
 diffmk/cddim.py:2 — DDIMSampler with make_schedule / sample / ddim_sampling / p_sample_ddim, `noise_like`
 and `np`.  Only the eps parameterisation and the options the reference exercises are implemented; anything
-else raises instead of silently diverging."""
+else raises instead of silently diverging.  The loops (fast path, step loop, trace merge, masked-blend keywords, start latent, host
+guided eps) are the driver of ``sampling.py``, shared with the multistep solvers."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
+from .sampling import SOLVERS, blend_kwargs, fast_loop, guided_eps, rescale_guided_eps, start_latent, step_loop  # noqa: F401
 from .schedule import make_ddim_sampling_parameters, make_ddim_timesteps
 
 __all__ = ['DDIMSampler', 'noise_like', 'np', 'torch']
+
+_DDIM = SOLVERS['ddim']          # the hook names and the host update of this solver
 
 
 def noise_like(shape, device, repeat=False):
@@ -45,16 +49,6 @@ def _check_rescale(phi) -> float:
     if not 0.0 <= phi <= 1.0:
         raise ValueError(f'guidance_rescale must lie in [0, 1], got {phi}')
     return phi
-
-
-def rescale_guided_eps(e_c, e_u, scale, phi):
-    """The guided eps with guidance rescale, in torch (host tensors; the device path is mkd_cfg_rescale_factor + the step kernels):
-    g = e_u + scale (e_c - e_u), per sample k = phi std(e_c) / std(g) + (1 - phi) (std(g) == 0: 1), returns g k."""
-    g = e_u + scale * (e_c - e_u)
-    dims = tuple(range(1, g.dim()))
-    s_c, s_g = e_c.std(dim=dims, keepdim=True), g.std(dim=dims, keepdim=True)
-    k = torch.where(s_g > 0, phi * s_c / torch.where(s_g > 0, s_g, torch.ones_like(s_g)) + (1.0 - phi), torch.ones_like(s_g))
-    return g * k
 
 
 def _cat_cond(uncond, c):
@@ -164,19 +158,17 @@ class DDIMSampler:
         size = (len(rows), C, H, W)
         device = self.model.device
         if seeds is not None:
-            from .batching import draw_plan
-            from .noise import STREAM_ETA, STREAM_START, normal
             seeds = _check_seeds(seeds, len(rows))
-            img = normal(seeds, size[1:], stream=STREAM_START, device=device) if x_T is None else x_T
-            if tuple(img.shape) != size:
-                raise ValueError(f'sample_specs: x_T must be {size}, got {tuple(img.shape)}')
-            plan = draw_plan(rows)
-            noise = normal(seeds, size[1:], stream=STREAM_ETA, rows=len(plan), device=device) if any(plan) else None
-            return fast(img, conditioning, rows, 'ddim', unconditional_conditioning, noise, temperature)
-        img = torch.randn(size, device=device) if x_T is None else x_T
+        img = start_latent(size, x_T, seeds, device)
         if tuple(img.shape) != size:
             raise ValueError(f'sample_specs: x_T must be {size}, got {tuple(img.shape)}')
-        noise = draw_noise(rows, size, device)
+        if seeds is not None:
+            from .batching import draw_plan
+            from .noise import STREAM_ETA, normal
+            plan = draw_plan(rows)
+            noise = normal(seeds, size[1:], stream=STREAM_ETA, rows=len(plan), device=device) if any(plan) else None
+        else:
+            noise = draw_noise(rows, size, device)
         return fast(img, conditioning, rows, 'ddim', unconditional_conditioning, noise, temperature)
 
     @torch.no_grad()
@@ -192,19 +184,14 @@ class DDIMSampler:
         if unconditional_conditioning is None or unconditional_guidance_scale == 1.0:
             phi = 0.0          # no unconditional half: not engaged
         device = self.model.device
-        b = shape[0]
         if seeds is not None:
-            from .noise import STREAM_BLEND, STREAM_ETA, STREAM_START, normal
-            seeds = _check_seeds(seeds, b, noise_dropout)
-            img = normal(seeds, tuple(shape)[1:], stream=STREAM_START, device=device) if x_T is None else x_T
-        else:
-            img = torch.randn(shape, device=device) if x_T is None else x_T
+            seeds = _check_seeds(seeds, shape[0], noise_dropout)
+        img = start_latent(shape, x_T, seeds, device)
         if timesteps is None:
             timesteps = self.ddim_timesteps
         intermediates = {'x_inter': [img], 'pred_x0': [img]}
-        time_range = np.flip(timesteps)
         total_steps = timesteps.shape[0]
-        fast = getattr(self.model, 'sample_loop_fast', None)
+        fast = getattr(self.model, _DDIM.loop_hook, None)
         if fast is not None and callback is None:
             # the whole loop runs inside libmkd (mkd_sample / mkd_sample_eta); no per-step host work.  eta > 0: the draws of the
             # stochastic branch (cddim.py:74-78) are taken here, one per step with sigma_t != 0 in loop order - the generator is
@@ -214,16 +201,13 @@ class DDIMSampler:
             sig = self.ddim_sigmas[:total_steps]
             kw = {}
             stochastic = float(sig.abs().max()) != 0.0
+            q_draws = None
             if seeds is not None:
                 # one launch per stream fills every row: row k is executed step k (a row whose sigma is 0 is multiplied by it)
                 if stochastic:
+                    from .noise import STREAM_ETA, normal
                     kw = dict(sigmas=sig, noise=normal(seeds, tuple(shape)[1:], stream=STREAM_ETA, rows=total_steps, device=device),
                               temperature=temperature)
-                if mask is not None:
-                    sa, s1 = self._q_tables()
-                    kw.update(x0=x0, mask=mask, q_sqrt_ac=[float(sa[int(t)]) for t in timesteps],
-                              q_sqrt_1m_ac=[float(s1[int(t)]) for t in timesteps],
-                              q_noise=normal(seeds, tuple(x0.shape)[1:], stream=STREAM_BLEND, rows=total_steps, device=device))
             elif stochastic or mask is not None:
                 draws, q_draws = [], []
                 for i in range(total_steps):
@@ -240,39 +224,22 @@ class DDIMSampler:
                     draws.append(nz)
                 if stochastic:
                     kw = dict(sigmas=sig, noise=torch.stack(draws), temperature=temperature)
-                if mask is not None:
-                    sa, s1 = self._q_tables()
-                    kw.update(x0=x0, mask=mask, q_sqrt_ac=[float(sa[int(t)]) for t in timesteps],
-                              q_sqrt_1m_ac=[float(s1[int(t)]) for t in timesteps], q_noise=torch.stack(q_draws))
-            kw['log_every_t'] = int(log_every_t)          # the loop's trace: the rows the step loop below appends
-            if phi != 0.0:
-                kw['guidance_rescale'] = phi
-            res = fast(img, cond, timesteps, self.ddim_alphas[:total_steps], self.ddim_alphas_prev[:total_steps],
-                       self.ddim_sqrt_one_minus_alphas[:total_steps], unconditional_guidance_scale,
-                       unconditional_conditioning, **kw)
-            if isinstance(res, tuple):          # (latent, x_inter rows, pred_x0 rows); the latent stays the last x_inter entry
-                img, x_rows, x0_rows = res
-                intermediates['x_inter'] += [*x_rows[:-1], img]
-                intermediates['pred_x0'] += list(x0_rows)
-            else:                               # a hook that keeps no trace
-                img = res
+            if mask is not None:
+                kw.update(blend_kwargs(self._q_tables(), x0, mask, timesteps, seeds, q_draws))
+            img = fast_loop(fast, img, cond, (timesteps, self.ddim_alphas[:total_steps], self.ddim_alphas_prev[:total_steps],
+                                              self.ddim_sqrt_one_minus_alphas[:total_steps]), unconditional_guidance_scale,
+                            unconditional_conditioning, kw, (log_every_t, intermediates), phi)
+            if len(intermediates['x_inter']) == 1:          # a hook that keeps no trace
                 intermediates['x_inter'].append(img)
             return img, intermediates
-        for i, step in enumerate(time_range):
-            index = total_steps - i - 1
-            ts = torch.full((b,), int(step), device=device, dtype=torch.long)
-            if mask is not None:
-                img = self._q_blend(x0, int(step), mask, img, seeds=seeds, row=i)
-            img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, temperature=temperature,
-                                              noise_dropout=noise_dropout, seeds=seeds, row=i,
-                                              unconditional_guidance_scale=unconditional_guidance_scale,
-                                              unconditional_conditioning=unconditional_conditioning, guidance_rescale=phi)
-            if callback:
-                callback(i)
-            if index % log_every_t == 0 or index == total_steps - 1:
-                intermediates['x_inter'].append(img)
-                intermediates['pred_x0'].append(pred_x0)
-        return img, intermediates
+
+        def step(img, ts, index, i):
+            return self.p_sample_ddim(img, cond, ts, index=index, temperature=temperature, noise_dropout=noise_dropout, seeds=seeds, row=i,
+                                      unconditional_guidance_scale=unconditional_guidance_scale,
+                                      unconditional_conditioning=unconditional_conditioning, guidance_rescale=phi)
+
+        blend = None if mask is None else (lambda t, img, i: self._q_blend(x0, t, mask, img, seeds=seeds, row=i))
+        return step_loop(img, timesteps, step, callback, blend, (log_every_t, intermediates)), intermediates
 
     @torch.no_grad()
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
@@ -332,21 +299,13 @@ class DDIMSampler:
     def _update(self, x, e_c, e_u, unconditional_guidance_scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature,
                 guidance_rescale=0.0):
         rescale = e_u is not None and guidance_rescale != 0.0
-        step_fn = getattr(self.model, 'ddim_step', None)
+        step_fn = getattr(self.model, _DDIM.step, None)
         if step_fn is not None and x.is_cuda:
             kw = {'guidance_rescale': guidance_rescale} if rescale else {}
             return step_fn(x, e_c, e_u, unconditional_guidance_scale, a_t, a_prev, sigma_t, s1m_t, noise, temperature, **kw)
         # host tensors (plumbing with a stand-in model, e.g. CPU tests): same formulae in torch
-        if rescale:
-            e_t = rescale_guided_eps(e_c, e_u, unconditional_guidance_scale, guidance_rescale)
-        else:
-            e_t = e_c if e_u is None else e_u + unconditional_guidance_scale * (e_c - e_u)
-        pred_x0 = (x - s1m_t * e_t) / a_t ** 0.5
-        dir_xt = (1.0 - a_prev - sigma_t ** 2) ** 0.5 * e_t
-        x_prev = a_prev ** 0.5 * pred_x0 + dir_xt
-        if noise is not None:
-            x_prev = x_prev + sigma_t * noise * temperature
-        return x_prev, pred_x0
+        e_t = guided_eps(e_c, e_u, unconditional_guidance_scale, guidance_rescale)
+        return _DDIM.host_update(x, e_t, (a_t, a_prev, sigma_t, s1m_t), noise, temperature)
 
     # -- masked sampling / q_sample (UPSTREAM LatentDiffusion.q_sample as ddim_sampling uses it, DDIMSampler.stochastic_encode) --
     def _q_tables(self):
@@ -427,22 +386,18 @@ class DDIMSampler:
             x_next = fast(x0, c, [int(v) for v in timesteps][::-1], a, a_next, [float(np.sqrt(1.0 - np.float32(v))) for v in a],
                           unconditional_guidance_scale, unconditional_conditioning)
             return x_next, {'x_encoded': x_next, 'intermediate_steps': []}
-        x_next = x0
         intermediates, inter_steps = [], []
-        for i in range(num_steps):
-            t = torch.full((x0.shape[0],), int(timesteps[i]), device=x0.device, dtype=torch.long)
-            e_c, e_u = self._eps(x_next, c, t, unconditional_guidance_scale, unconditional_conditioning)
+
+        def step(x, t, i, _):
+            e_c, e_u = self._eps(x, c, t, unconditional_guidance_scale, unconditional_conditioning)
             a_t, a_n = float(alphas[i]), float(alphas_next[i])
-            x_next, _ = self._update(x_next, e_c, e_u, unconditional_guidance_scale, a_t, a_n, 0.0,
-                                     float(np.sqrt(1.0 - np.float32(a_t))), None, 1.0)
-            if return_intermediates and i % (num_steps // return_intermediates) == 0 and i < num_steps - 1:
-                intermediates.append(x_next)
+            x, _ = self._update(x, e_c, e_u, unconditional_guidance_scale, a_t, a_n, 0.0, float(np.sqrt(1.0 - np.float32(a_t))), None, 1.0)
+            if return_intermediates and (i % (num_steps // return_intermediates) == 0 or i >= num_steps - 2):
+                intermediates.append(x)
                 inter_steps.append(i)
-            elif return_intermediates and i >= num_steps - 2:
-                intermediates.append(x_next)
-                inter_steps.append(i)
-            if callback:
-                callback(i)
+            return x, None
+
+        x_next = step_loop(x0, timesteps, step, callback, forward=True)
         out = {'x_encoded': x_next, 'intermediate_steps': inter_steps}
         if return_intermediates:
             out['intermediates'] = intermediates
@@ -479,12 +434,6 @@ class DDIMSampler:
             return fast(x_latent, cond, timesteps, self.ddim_alphas[:total_steps], self.ddim_alphas_prev[:total_steps],
                         self.ddim_sqrt_one_minus_alphas[:total_steps], unconditional_guidance_scale,
                         unconditional_conditioning)
-        x_dec = x_latent
-        for i, step in enumerate(time_range):
-            index = total_steps - i - 1
-            ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
-            x_dec, _ = self._step(x_dec, cond, ts, index, False, use_original_steps, False, 1.0, 0.0, None, None,
-                                  unconditional_guidance_scale, unconditional_conditioning, None)
-            if callback:
-                callback(i)
-        return x_dec
+        return step_loop(x_latent, timesteps, lambda x, ts, index, i: self._step(
+            x, cond, ts, index, False, use_original_steps, False, 1.0, 0.0, None, None, unconditional_guidance_scale,
+            unconditional_conditioning, None), callback)

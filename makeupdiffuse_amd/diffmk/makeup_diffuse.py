@@ -20,6 +20,7 @@ from ..unipc import UniPCSampler
 from ..video import TemporalFilter
 from ..engine import ClipConfig, MkdEngine, NetConfig, VaeConfig
 from ..lib import MkdError
+from ..sampling import SOLVERS
 from ..schedule import DDIMSchedule
 
 
@@ -283,18 +284,23 @@ class BaseMakeUpDiffuse:
         c = self.cfg_conditioning(uncond, cond) if cfg_on else cond
         return self._bind_cond(c, latent_hw), float(scale) if cfg_on else 1.0
 
+    # the three loop hooks: bind [uncond; cond] or cond, convert the grid's tables, ask for the trace, call the solver's engine loop
+    def _sample_loop(self, solver, x_latent, cond, tables, scale, uncond, log_every_t, guidance_rescale, **kw):
+        eng, cfg_scale = self._bind_guided(cond, uncond, scale, x_latent.shape[2:])
+        trace = {} if log_every_t is None else dict(log_every_t=int(log_every_t), want_trace=True)
+        timesteps, *tables = tables
+        return getattr(eng, SOLVERS[solver].loop)(x_latent, [int(v) for v in timesteps], *([float(v) for v in t] for t in tables),
+                                                  cfg_scale=cfg_scale, use_graph=bool(self.sample_use_graph),
+                                                  guidance_rescale=float(guidance_rescale), **kw, **trace)
+
     def sample_loop_fast(self, x_latent, cond, timesteps, alphas, alphas_prev, sqrt_one_minus_alphas,
                          unconditional_guidance_scale=1.0, unconditional_conditioning=None, sigmas=None, noise=None, temperature=1.0,
                          x0=None, mask=None, q_sqrt_ac=None, q_sqrt_1m_ac=None, q_noise=None, log_every_t=None, guidance_rescale=0.0):
         """log_every_t not None: (latent, x_inter rows, pred_x0 rows) with the loop's trace (MkdEngine.sample want_trace)"""
-        eng, cfg_scale = self._bind_guided(cond, unconditional_conditioning, unconditional_guidance_scale, x_latent.shape[2:])
-        trace = {} if log_every_t is None else dict(log_every_t=int(log_every_t), want_trace=True)
-        return eng.sample(x_latent, [int(v) for v in timesteps], [float(v) for v in alphas], [float(v) for v in alphas_prev],
-                          [float(v) for v in sqrt_one_minus_alphas],
-                          cfg_scale=cfg_scale, use_graph=bool(self.sample_use_graph),
-                          sigmas=None if sigmas is None else [float(v) for v in sigmas], noise=noise, temperature=float(temperature),
-                          x0=x0, mask=mask, q_sqrt_ac=q_sqrt_ac, q_sqrt_1m_ac=q_sqrt_1m_ac, q_noise=q_noise,
-                          guidance_rescale=float(guidance_rescale), **trace)
+        return self._sample_loop('ddim', x_latent, cond, (timesteps, alphas, alphas_prev, sqrt_one_minus_alphas),
+                                 unconditional_guidance_scale, unconditional_conditioning, log_every_t, guidance_rescale,
+                                 sigmas=None if sigmas is None else [float(v) for v in sigmas], noise=noise, temperature=float(temperature),
+                                 x0=x0, mask=mask, q_sqrt_ac=q_sqrt_ac, q_sqrt_1m_ac=q_sqrt_1m_ac, q_noise=q_noise)
 
     def sample_rows_fast(self, x_latent, cond, rows, solver='ddim', unconditional_conditioning=None, noise=None, temperature=1.0):
         """the whole loop with one request row per sample inside libmkd (mkd_sample_rows; rows: batching.RowTables).  The engine is
@@ -317,13 +323,10 @@ class BaseMakeUpDiffuse:
                           q_sqrt_1m_ac=None, q_noise=None, log_every_t=None, guidance_rescale=0.0):
         """the whole DPM-Solver++ multistep loop inside libmkd (mkd_sample_dpmpp), on the tables sample_loop_fast takes; log_every_t
         as there"""
-        eng, cfg_scale = self._bind_guided(cond, unconditional_conditioning, unconditional_guidance_scale, x_latent.shape[2:])
-        trace = {} if log_every_t is None else dict(log_every_t=int(log_every_t), want_trace=True)
-        return eng.sample_dpmpp(x_latent, [int(v) for v in timesteps], [float(v) for v in alphas], [float(v) for v in alphas_prev],
-                                order=int(order), lower_order_final=bool(lower_order_final),
-                                cfg_scale=cfg_scale, use_graph=bool(self.sample_use_graph),
-                                x0=x0, mask=mask, q_sqrt_ac=q_sqrt_ac, q_sqrt_1m_ac=q_sqrt_1m_ac, q_noise=q_noise,
-                                guidance_rescale=float(guidance_rescale), **trace)
+        return self._sample_loop('dpmpp', x_latent, cond, (timesteps, alphas, alphas_prev), unconditional_guidance_scale,
+                                 unconditional_conditioning, log_every_t, guidance_rescale, order=int(order),
+                                 lower_order_final=bool(lower_order_final), x0=x0, mask=mask, q_sqrt_ac=q_sqrt_ac, q_sqrt_1m_ac=q_sqrt_1m_ac,
+                                 q_noise=q_noise)
 
     def unipc_step(self, x, xc_prev, e_c, e_u, scale, coef12, m1=None, m2=None, m3=None, guidance_rescale=0.0):
         """one UniPC step on the device (UniPCSampler's per-step loop): (next predicted latent, corrected latent, x0-prediction), the
@@ -334,12 +337,9 @@ class BaseMakeUpDiffuse:
                           unconditional_guidance_scale=1.0, unconditional_conditioning=None, log_every_t=None, guidance_rescale=0.0):
         """the whole UniPC predictor-corrector loop inside libmkd (mkd_sample_unipc), on the tables sample_loop_dpmpp takes;
         log_every_t as there"""
-        eng, cfg_scale = self._bind_guided(cond, unconditional_conditioning, unconditional_guidance_scale, x_latent.shape[2:])
-        trace = {} if log_every_t is None else dict(log_every_t=int(log_every_t), want_trace=True)
-        return eng.sample_unipc(x_latent, [int(v) for v in timesteps], [float(v) for v in alphas], [float(v) for v in alphas_prev],
-                                order=int(order), lower_order_final=bool(lower_order_final), corrector=bool(corrector),
-                                cfg_scale=cfg_scale, use_graph=bool(self.sample_use_graph),
-                                guidance_rescale=float(guidance_rescale), **trace)
+        return self._sample_loop('unipc', x_latent, cond, (timesteps, alphas, alphas_prev), unconditional_guidance_scale,
+                                 unconditional_conditioning, log_every_t, guidance_rescale, order=int(order),
+                                 lower_order_final=bool(lower_order_final), corrector=bool(corrector))
 
     def latent_mask_from_labels(self, seg: torch.Tensor, classes: Sequence[int] = (0, 11, 12), factor: int = 8,
                                 threshold: float = 0.5) -> torch.Tensor:
@@ -354,6 +354,14 @@ class BaseMakeUpDiffuse:
     solver_order = 2
     unipc_corrector = True
 
+    def _sampler(self):
+        """(the solver record, its sampler class, the solver's own options from the model's attributes) of the ``sampler`` attribute"""
+        classes = {'ddim': DDIMSampler, 'dpmpp': DPMSolverSampler, 'unipc': UniPCSampler}
+        if self.sampler not in classes:
+            raise ValueError(f"sampler must be 'ddim' or 'dpmpp', got {self.sampler!r}")
+        solver = SOLVERS[self.sampler]
+        return solver, classes[self.sampler], {k: getattr(self, attr) for k, attr in solver.options}
+
     @torch.no_grad()
     def sample_log(self, cond: dict, batch_size: int, ddim: bool, ddim_steps: int, **kwargs):
         """UPSTREAM ControlLDM.sample_log: latent shape from the hint, x_T ~ N(0, I) unless given.  Upstream ignores ``ddim`` beyond
@@ -362,15 +370,8 @@ class BaseMakeUpDiffuse:
             raise NotImplementedError('only the DDIM sampler is on the MakeupDiffuse test path')
         _, _, h, w = cond['c_concat'][0].shape
         shape = (self.channels, h // 8, w // 8)
-        if self.sampler == 'dpmpp':
-            return DPMSolverSampler(self).sample(ddim_steps, batch_size, shape, cond, order=self.solver_order, verbose=False, **kwargs)
-        if self.sampler == 'unipc':
-            return UniPCSampler(self).sample(ddim_steps, batch_size, shape, cond, order=self.solver_order,
-                                             corrector=self.unipc_corrector, verbose=False, **kwargs)
-        if self.sampler != 'ddim':
-            raise ValueError(f"sampler must be 'ddim' or 'dpmpp', got {self.sampler!r}")
-        sampler = DDIMSampler(self)
-        return sampler.sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
+        _, sampler, options = self._sampler()
+        return sampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False, **options, **kwargs)
 
     def decode_first_stage(self, z: torch.Tensor) -> torch.Tensor:
         """z / scale_factor -> post_quant_conv -> Decoder (UPSTREAM AutoencoderKL.decode), on the device via mkd_decode."""
@@ -477,7 +478,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             raise ValueError(f'guidance_rescale must lie in [0, 1], got {guidance_rescale}')
         if not 0 <= int(paste_feather) <= 16:
             raise ValueError(f'paste_feather must be 0..16 image pixels, got {paste_feather}')
-        if sampler not in ('ddim', 'dpmpp', 'unipc'):
+        if sampler not in SOLVERS:
             raise ValueError(f"sampler must be 'ddim' or 'dpmpp', got {sampler!r}")
         if solver_order not in (1, 2, 3):
             raise ValueError('solver_order must be 1, 2 or 3')
@@ -662,22 +663,21 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         with a first stage, the decoded samples.  ``seeds`` (default: the model's ``seed``): one per pair, beside the specs; each pass
         gets its members' seeds, so a pair's noise does not depend on which pass it runs in."""
         from ..batching import SampleSpec
-        if self.sampler == 'unipc':
-            UniPCSampler(self).sample_specs()          # (NotImplementedError: the per-sample loop runs DDIM and DPM-Solver++ only)
+        solver = SOLVERS.get(self.sampler)
+        if solver is not None and solver.rows_id is None:
+            self._sampler()[1](self).sample_specs()          # (NotImplementedError: the per-sample loop runs DDIM and DPM-Solver++ only)
         specs = list(specs)
         _, c = self.get_input(batch, self.first_stage_key)
         c_cat, c_txt = c['c_concat'][0], c['c_crossattn'][0]
         b = c_cat.shape[0]
         if len(specs) != b or not all(isinstance(s, SampleSpec) for s in specs):
             raise ValueError(f'transfer_specs: one SampleSpec per pair is needed ({len(specs)} for a batch of {b})')
-        if self.sampler not in ('ddim', 'dpmpp'):
-            raise ValueError(f"sampler must be 'ddim' or 'dpmpp', got {self.sampler!r}")
+        smp = self._sampler()[1](self)
         h, w = c_cat.shape[2] // 8, c_cat.shape[3] // 8
         sd = self._seeds(seeds, b)
         x_T = self._start_latent(x_T, sd, b, h, w)
         if tuple(x_T.shape) != (b, self.channels, h, w):
             raise ValueError(f'transfer_specs: x_T must be {(b, self.channels, h, w)}, got {tuple(x_T.shape)}')
-        smp = DPMSolverSampler(self) if self.sampler == 'dpmpp' else DDIMSampler(self)
         lat = torch.empty_like(x_T)
         for want_guided in (False, True):
             idx = [i for i, s in enumerate(specs) if (float(s.guidance) != 1.0) == want_guided]
@@ -720,9 +720,10 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
     def _check_unipc_masked(self) -> None:
         """fix_background samples with a mask; the UniPC solver has no masked form (UniPCSampler.sample).  Raised before the encoder,
         the parser or a sampler has enqueued anything"""
-        if self.sampler == 'unipc' and self.fix_background:
-            raise NotImplementedError('UniPCSampler: masked sampling (mask / x0) is not defined for this solver: fix_background needs '
-                                      "sampler='ddim' or 'dpmpp'")
+        solver = SOLVERS.get(self.sampler)
+        if self.fix_background and solver is not None and not solver.masked:
+            raise NotImplementedError(f'{self._sampler()[1].__name__}: masked sampling (mask / x0) is not defined for this solver: '
+                                      "fix_background needs sampler='ddim' or 'dpmpp'")
 
     def _check_paste(self, batch: dict, what: str) -> None:
         """what a pixel-space paste needs, checked before anything is sampled"""
@@ -862,17 +863,10 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         sch.make_ddim(self.ddim_steps, ddim_eta=0.0)
         ts = [int(v) for v in sch.ddim_timesteps]
         a, ap = [float(v) for v in sch.ddim_alphas], [float(v) for v in sch.ddim_alphas_prev]
-        if self.sampler == 'dpmpp':
-            lat = eng.sample_dpmpp(x_T, ts, a, ap, order=self.solver_order, lower_order_final=True, cfg_scale=scale,
-                                   use_graph=bool(self.sample_use_graph), guidance_rescale=phi)
-        elif self.sampler == 'unipc':
-            lat = eng.sample_unipc(x_T, ts, a, ap, order=self.solver_order, lower_order_final=True, corrector=self.unipc_corrector,
-                                   cfg_scale=scale, use_graph=bool(self.sample_use_graph), guidance_rescale=phi)
-        elif self.sampler == 'ddim':
-            lat = eng.sample(x_T, ts, a, ap, [float(v) for v in sch.ddim_sqrt_one_minus_alphas], cfg_scale=scale,
-                             use_graph=bool(self.sample_use_graph), guidance_rescale=phi)
-        else:
-            raise ValueError(f"sampler must be 'ddim' or 'dpmpp', got {self.sampler!r}")
+        solver, _, options = self._sampler()
+        tables = (a, ap, [float(v) for v in sch.ddim_sqrt_one_minus_alphas]) if solver.name == 'ddim' else (a, ap)
+        lat = getattr(eng, solver.loop)(x_T, ts, *tables, cfg_scale=scale, use_graph=bool(self.sample_use_graph), guidance_rescale=phi,
+                                        **options)
         out = {'samples_latent': lat, 'weights': weights}
         if self.has_first_stage:
             out['samples'] = self.decode_first_stage(lat)

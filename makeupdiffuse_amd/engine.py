@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .sampling import SOLVERS as _SOLVER
 
 
 @dataclass
@@ -171,7 +172,7 @@ def unipc_table(alphas: Sequence[float], alphas_prev: Sequence[float], order: in
     return np.ctypeslib.as_array(out).reshape(n, 12).copy(), np.ctypeslib.as_array(so).astype(np.int32)
 
 
-SOLVERS = {'ddim': 0, 'dpmpp': 1}
+SOLVERS = {s.name: s.rows_id for s in _SOLVER.values() if s.rows_id is not None}          # the ids mkd_sample_rows takes
 # numpy view of mkd_step_row (include/mkd.h), 64 bytes
 STEP_ROW_DTYPE = np.dtype([('t', '<i8'), ('coef', '<f4', (4,)), ('sigma', '<f4'), ('dpm', '<f4', (6,)), ('temb_row', '<i4'),
                            ('active', '<i4'), ('scale', '<f4')])
@@ -625,22 +626,22 @@ class MkdEngine:
         noise = None if noise is None else _f32c(noise, self.device)
         x_prev = torch.empty_like(x)
         x0 = torch.empty_like(x) if want_x0 else None
-        k, per = self._rescale_k(eps_c, eps_u, cfg_scale, guidance_rescale)
-        if k is not None:           # the rescaled eps: the factor launch, then the step with k (the in-library loop's two kernels)
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.mkd_ddim_step_ex(C.c_void_p(x.data_ptr()), C.c_void_p(eps_c.data_ptr()), C.c_void_p(eps_u.data_ptr()),
-                                                     float(cfg_scale), float(a_t), float(a_prev), float(sigma_t),
-                                                     float(sqrt_one_minus_at), C.c_void_p(_ptr(noise)), float(temperature),
-                                                     C.c_void_p(k.data_ptr()), per, C.c_void_p(x_prev.data_ptr()), C.c_void_p(_ptr(x0)),
-                                                     x.numel(), C.c_void_p(_stream())), 'mkd_ddim_step_ex')
-            return x_prev, x0
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.mkd_ddim_step(C.c_void_p(x.data_ptr()), C.c_void_p(eps_c.data_ptr()), C.c_void_p(_ptr(eps_u)),
-                                              float(cfg_scale), float(a_t), float(a_prev), float(sigma_t),
-                                              float(sqrt_one_minus_at), C.c_void_p(_ptr(noise)), float(temperature),
-                                              C.c_void_p(x_prev.data_ptr()), C.c_void_p(_ptr(x0)), x.numel(),
-                                              C.c_void_p(_stream())), 'mkd_ddim_step')
+        self._step_call(_SOLVER['ddim'], (C.c_void_p(x.data_ptr()), C.c_void_p(eps_c.data_ptr()), C.c_void_p(_ptr(eps_u)), float(cfg_scale),
+                                      float(a_t), float(a_prev), float(sigma_t), float(sqrt_one_minus_at), C.c_void_p(_ptr(noise)),
+                                      float(temperature)), (C.c_void_p(x_prev.data_ptr()), C.c_void_p(_ptr(x0)), x.numel()),
+                        eps_c, eps_u, cfg_scale, guidance_rescale)
         return x_prev, x0
+
+    def _step_call(self, solver, head, tail, eps_c, eps_u, cfg_scale, guidance_rescale):
+        """One stand-alone step kernel of ``solver`` (its sampling.Solver record): mkd_<step>(*head, *tail, stream); with the guidance
+        rescale engaged the factor launch, then mkd_<step>_ex with (k, n_per_sample) between head and tail (the in-library loop's two
+        kernels)."""
+        entry = 'mkd_' + solver.step
+        k, per = self._rescale_k(eps_c, eps_u, cfg_scale, guidance_rescale)
+        if k is not None:
+            entry, head = entry + '_ex', (*head, C.c_void_p(k.data_ptr()), per)
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(self.lib, entry)(*head, *tail, C.c_void_p(_stream())), entry)
 
     def sample(self, x_T: torch.Tensor, timesteps: Sequence[int], alphas: Sequence[float], alphas_prev: Sequence[float],
                sqrt_one_minus_alphas: Sequence[float], cfg_scale: float = 1.0, use_graph: bool = False,
@@ -654,40 +655,51 @@ class MkdEngine:
         tables at each entry's timestep ``q_sqrt_ac`` / ``q_sqrt_1m_ac`` (indexed like ``alphas``) and ``q_noise`` [n_steps, B, 4, h, w].
         ``want_trace``: returns ``(latent, x_inter, pred_x0)``, the two [rows, B, 4, h, w] tensors of the sampler's intermediates
         logged by ``log_every_t`` (mkd_sample_extras); ``guidance_rescale`` = phi in [0, 1], engaged with guidance and phi > 0."""
+        return self._sample_call(_SOLVER['ddim'], x_T, timesteps,
+                                 dict(alphas=alphas, alphas_prev=alphas_prev, sqrt_one_minus_alphas=sqrt_one_minus_alphas), (), cfg_scale, use_graph, (x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise), log_every_t, want_trace, guidance_rescale,
+                                 eta=(sigmas, noise, temperature))
+
+    def _sample_call(self, solver, x_T, timesteps, tables, args, cfg_scale, use_graph, masking, log_every_t, want_trace, guidance_rescale, eta=None):
+        """The body of sample / sample_dpmpp / sample_unipc (``solver``: the sampling.Solver record).  The multistep solvers (eta None)
+        call mkd_<loop>, or mkd_<loop>_ex with a trace or phi != 0, with ``args`` = their options after the tables; DDIM calls
+        mkd_sample_masked_ex with either, else mkd_sample_masked with a mask, else mkd_sample_eta with a non-zero sigma, else mkd_sample."""
         x_T = self._check_x_T(x_T, cfg_scale)
-        n, ts, (a, ap, s1) = self._sample_tables(timesteps, alphas=alphas, alphas_prev=alphas_prev, sqrt_one_minus_alphas=sqrt_one_minus_alphas)
+        n, ts, tables = self._sample_tables(timesteps, **tables)
         out = torch.empty_like(x_T)
-        qm, keep = self._sample_mask(x_T, n, x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise)
+        qm, keep = self._sample_mask(x_T, n, *masking)
         ex, rows = self._sample_extras(x_T, n, log_every_t, want_trace, guidance_rescale)
-        sg = None
-        if sigmas is not None and any(float(v) != 0.0 for v in sigmas):
-            if len(sigmas) != n:
-                raise ValueError('sigmas must be as long as timesteps')
-            if noise is None or tuple(noise.shape) != (n, *x_T.shape):
-                raise ValueError(f'eta > 0 needs noise of shape {(n, *x_T.shape)} (one draw per executed step)')
-            noise = _f32c(noise, self.device)
-            sg = (C.c_float * n)(*[float(v) for v in sigmas])
+        qm_ex = (None if qm is None else C.byref(qm), *(() if ex is None else (C.byref(ex),)))
+        noise = None
+        if eta is None:
+            entry, args = 'mkd_' + solver.loop + ('_ex' if ex is not None else ''), (*args, *qm_ex)
         else:
-            noise = None
-        with torch.cuda.device(self.device):
-            head = (self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, s1)
-            tail = (float(cfg_scale), C.c_void_p(out.data_ptr()), int(use_graph), C.c_void_p(_stream()))
-            if ex is not None:
-                _lib.check(self.lib.mkd_sample_masked_ex(*head, sg, C.c_void_p(_ptr(noise)), float(temperature),
-                                                         None if qm is None else C.byref(qm), C.byref(ex), *tail), 'mkd_sample_masked_ex')
-                if qm is not None:
-                    self._hold(keep, noise)
-                elif sg is not None and use_graph:
-                    torch.cuda.synchronize(self.device)          # (as below: the replayed loop reads `noise` after this call returns)
-            elif qm is not None:
-                _lib.check(self.lib.mkd_sample_masked(*head, sg, C.c_void_p(_ptr(noise)), float(temperature), C.byref(qm), *tail), 'mkd_sample_masked')
-                self._hold(keep, noise)
-            elif sg is not None:
-                _lib.check(self.lib.mkd_sample_eta(*head, sg, C.c_void_p(noise.data_ptr()), float(temperature), *tail), 'mkd_sample_eta')
-                if use_graph:
-                    torch.cuda.synchronize(self.device)          # the replayed loop reads `noise` after this call returns: keep it alive
+            sigmas, noise, temperature = eta
+            sg = None
+            if sigmas is not None and any(float(v) != 0.0 for v in sigmas):
+                if len(sigmas) != n:
+                    raise ValueError('sigmas must be as long as timesteps')
+                if noise is None or tuple(noise.shape) != (n, *x_T.shape):
+                    raise ValueError(f'eta > 0 needs noise of shape {(n, *x_T.shape)} (one draw per executed step)')
+                noise = _f32c(noise, self.device)
+                sg = (C.c_float * n)(*[float(v) for v in sigmas])
             else:
-                _lib.check(self.lib.mkd_sample(*head, *tail), 'mkd_sample')
+                noise = None
+            args = (sg, C.c_void_p(_ptr(noise)), float(temperature))
+            if ex is not None:
+                entry, args = 'mkd_sample_masked_ex', (*args, *qm_ex)
+            elif qm is not None:
+                entry, args = 'mkd_sample_masked', (*args, *qm_ex)
+            elif sg is not None:
+                entry = 'mkd_sample_eta'
+            else:
+                entry, args = 'mkd_sample', ()
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(self.lib, entry)(self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, *tables, *args, float(cfg_scale),
+                                                C.c_void_p(out.data_ptr()), int(use_graph), C.c_void_p(_stream())), entry)
+        if qm is not None:
+            self._hold(keep, noise)
+        elif noise is not None and use_graph:
+            torch.cuda.synchronize(self.device)          # the replayed loop reads `noise` after this call returns: keep it alive
         return (out, *rows) if want_trace else out
 
     def _sample_extras(self, x_T, n, log_every_t, want_trace, guidance_rescale):
@@ -724,19 +736,9 @@ class MkdEngine:
                 raise ValueError('dpmpp_step: every tensor must have the size of x')
         x_prev = torch.empty_like(x)
         m0 = torch.empty_like(x)
-        kf, per = self._rescale_k(eps_c, eps_u, cfg_scale, guidance_rescale)
-        if kf is not None:
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.mkd_dpmpp_step_ex(C.c_void_p(x.data_ptr()), C.c_void_p(eps_c.data_ptr()), C.c_void_p(eps_u.data_ptr()),
-                                                      float(cfg_scale), (C.c_float * 6)(*k), C.c_void_p(_ptr(m1)), C.c_void_p(_ptr(m2)),
-                                                      C.c_void_p(kf.data_ptr()), per, C.c_void_p(x_prev.data_ptr()),
-                                                      C.c_void_p(m0.data_ptr()), x.numel(), C.c_void_p(_stream())), 'mkd_dpmpp_step_ex')
-            return x_prev, m0
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.mkd_dpmpp_step(C.c_void_p(x.data_ptr()), C.c_void_p(eps_c.data_ptr()), C.c_void_p(_ptr(eps_u)),
-                                               float(cfg_scale), (C.c_float * 6)(*k), C.c_void_p(_ptr(m1)), C.c_void_p(_ptr(m2)),
-                                               C.c_void_p(x_prev.data_ptr()), C.c_void_p(m0.data_ptr()), x.numel(),
-                                               C.c_void_p(_stream())), 'mkd_dpmpp_step')
+        self._step_call(_SOLVER['dpmpp'], (C.c_void_p(x.data_ptr()), C.c_void_p(eps_c.data_ptr()), C.c_void_p(_ptr(eps_u)), float(cfg_scale),
+                                       (C.c_float * 6)(*k), C.c_void_p(_ptr(m1)), C.c_void_p(_ptr(m2))),
+                        (C.c_void_p(x_prev.data_ptr()), C.c_void_p(m0.data_ptr()), x.numel()), eps_c, eps_u, cfg_scale, guidance_rescale)
         return x_prev, m0
 
     def sample_dpmpp(self, x_T: torch.Tensor, timesteps: Sequence[int], alphas: Sequence[float], alphas_prev: Sequence[float],
@@ -747,21 +749,9 @@ class MkdEngine:
         """The whole DPM-Solver++ multistep loop in one call (mkd_sample_dpmpp): ``sample``'s contract on the same DDIM tables
         (prepared batch B or 2B with guidance, masked sampling through x0 / mask / q_*), deterministic.  ``want_trace`` /
         ``log_every_t`` / ``guidance_rescale`` as in ``sample`` (the pred_x0 rows are the solver's m_k)."""
-        x_T = self._check_x_T(x_T, cfg_scale)
-        n, ts, (a, ap) = self._sample_tables(timesteps, alphas=alphas, alphas_prev=alphas_prev)
-        out = torch.empty_like(x_T)
-        qm, keep = self._sample_mask(x_T, n, x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise)
-        ex, rows = self._sample_extras(x_T, n, log_every_t, want_trace, guidance_rescale)
-        with torch.cuda.device(self.device):
-            head = (self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, int(order), int(bool(lower_order_final)),
-                    None if qm is None else C.byref(qm))
-            tail = (float(cfg_scale), C.c_void_p(out.data_ptr()), int(use_graph), C.c_void_p(_stream()))
-            if ex is not None:
-                _lib.check(self.lib.mkd_sample_dpmpp_ex(*head, C.byref(ex), *tail), 'mkd_sample_dpmpp_ex')
-            else:
-                _lib.check(self.lib.mkd_sample_dpmpp(*head, *tail), 'mkd_sample_dpmpp')
-        self._hold(keep, None)
-        return (out, *rows) if want_trace else out
+        return self._sample_call(_SOLVER['dpmpp'], x_T, timesteps, dict(alphas=alphas, alphas_prev=alphas_prev),
+                                 (int(order), int(bool(lower_order_final))), cfg_scale, use_graph, (x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise),
+                                 log_every_t, want_trace, guidance_rescale)
 
     def unipc_step(self, x, xc_prev, eps_c, eps_u, cfg_scale, coef12, m1=None, m2=None, m3=None, guidance_rescale: float = 0.0):
         """One UniPC step (mkd_unipc_step): ``x`` = the predicted latent the model was evaluated at, ``xc_prev`` = the previous corrected
@@ -783,15 +773,10 @@ class MkdEngine:
             if t is not None and t.numel() != x.numel():
                 raise ValueError('unipc_step: every tensor must have the size of x')
         x_next, xc, m0 = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
-        kf, per = self._rescale_k(eps_c, eps_u, cfg_scale, guidance_rescale)
-        head = (C.c_void_p(x.data_ptr()), C.c_void_p(_ptr(xc_prev)), C.c_void_p(eps_c.data_ptr()), C.c_void_p(_ptr(eps_u)), float(cfg_scale),
-                (C.c_float * 12)(*k), C.c_void_p(_ptr(m1)), C.c_void_p(_ptr(m2)), C.c_void_p(_ptr(m3)))
-        tail = (C.c_void_p(x_next.data_ptr()), C.c_void_p(xc.data_ptr()), C.c_void_p(m0.data_ptr()), x.numel(), C.c_void_p(_stream()))
-        with torch.cuda.device(self.device):
-            if kf is not None:
-                _lib.check(self.lib.mkd_unipc_step_ex(*head, C.c_void_p(kf.data_ptr()), per, *tail), 'mkd_unipc_step_ex')
-            else:
-                _lib.check(self.lib.mkd_unipc_step(*head, *tail), 'mkd_unipc_step')
+        self._step_call(_SOLVER['unipc'], (C.c_void_p(x.data_ptr()), C.c_void_p(_ptr(xc_prev)), C.c_void_p(eps_c.data_ptr()), C.c_void_p(_ptr(eps_u)),
+                                       float(cfg_scale), (C.c_float * 12)(*k), C.c_void_p(_ptr(m1)), C.c_void_p(_ptr(m2)), C.c_void_p(_ptr(m3))),
+                        (C.c_void_p(x_next.data_ptr()), C.c_void_p(xc.data_ptr()), C.c_void_p(m0.data_ptr()), x.numel()),
+                        eps_c, eps_u, cfg_scale, guidance_rescale)
         return x_next, xc, m0
 
     def sample_unipc(self, x_T: torch.Tensor, timesteps: Sequence[int], alphas: Sequence[float], alphas_prev: Sequence[float],
@@ -804,21 +789,9 @@ class MkdEngine:
         which must be contiguous (alphas_prev[i] == alphas[i - 1]).  ``want_trace`` / ``log_every_t`` / ``guidance_rescale`` as in
         ``sample`` (x_inter rows: the predicted latents; pred_x0 rows: the solver's m_k).  Masked sampling (x0 / mask / q_*) is not
         defined for this solver: libmkd refuses it (MkdError, -4) and the context stays usable."""
-        x_T = self._check_x_T(x_T, cfg_scale)
-        n, ts, (a, ap) = self._sample_tables(timesteps, alphas=alphas, alphas_prev=alphas_prev)
-        out = torch.empty_like(x_T)
-        qm, keep = self._sample_mask(x_T, n, x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise)
-        ex, rows = self._sample_extras(x_T, n, log_every_t, want_trace, guidance_rescale)
-        with torch.cuda.device(self.device):
-            head = (self._ctx, C.c_void_p(x_T.data_ptr()), x_T.shape[0], n, ts, a, ap, int(order), int(bool(lower_order_final)),
-                    int(bool(corrector)), None if qm is None else C.byref(qm))
-            tail = (float(cfg_scale), C.c_void_p(out.data_ptr()), int(use_graph), C.c_void_p(_stream()))
-            if ex is not None:
-                _lib.check(self.lib.mkd_sample_unipc_ex(*head, C.byref(ex), *tail), 'mkd_sample_unipc_ex')
-            else:
-                _lib.check(self.lib.mkd_sample_unipc(*head, *tail), 'mkd_sample_unipc')
-        del keep
-        return (out, *rows) if want_trace else out
+        return self._sample_call(_SOLVER['unipc'], x_T, timesteps, dict(alphas=alphas, alphas_prev=alphas_prev),
+                                 (int(order), int(bool(lower_order_final)), int(bool(corrector))), cfg_scale, use_graph,
+                                 (x0, mask, q_sqrt_ac, q_sqrt_1m_ac, q_noise), log_every_t, want_trace, guidance_rescale)
 
     # ---- per-sample requests in one batch (include/mkd.h mkd_sample_rows) ------------------------------------------------------
     def sample_rows(self, x_T: torch.Tensor, rows, solver: str = 'ddim', noise: Optional[torch.Tensor] = None, temperature: float = 1.0,

@@ -9,7 +9,8 @@ latent x~_k the model is evaluated at, the corrected latent x^c carried beside i
 
 with twelve schedule-only numbers per step.  Order 2 with the corrector off is the DPM-Solver++ 2M trajectory; order 1 with the corrector
 off is algebraically the eta = 0 DDIM loop.  What is shown for it is arithmetic, polynomial exactness and a Gaussian toy (DESIGN.md §0);
-image quality at low evaluation counts is not shown: there are no pretrained weights here."""
+image quality at low evaluation counts is not shown: there are no pretrained weights here.
+This module holds the coefficients; the class is ``sampling.MultistepSampler`` with the 'unipc' record (the host update is there too)."""
 from __future__ import annotations
 
 import math
@@ -17,7 +18,7 @@ import math
 import numpy as np
 import torch
 
-from .ddim import DDIMSampler, _check_rescale, _check_seeds, rescale_guided_eps
+from .sampling import SOLVERS, MultistepSampler
 
 __all__ = ['UniPCSampler', 'unipc_coefficients']
 
@@ -137,21 +138,8 @@ def unipc_coefficients(alphas, alphas_prev, order=2, lower_order_final=True, cor
     return coef, orders
 
 
-class UniPCSampler:
-    # options of upstream samplers that this deterministic solver does not have
-    _REJECTED = ('score_corrector', 'corrector_kwargs', 'dynamic_threshold', 'ucg_schedule', 'img_callback', 'quantize_x0')
-
-    def __init__(self, model, **kwargs):
-        self.model = model
-        self.ddpm_num_timesteps = model.num_timesteps
-        self._ddim = DDIMSampler(model)          # the step grid, its tables and the guidance batching
-
-    def make_schedule(self, num_steps, verbose=False):
-        """The grid of DDIMSampler.make_schedule(num_steps): ddim_timesteps / ddim_alphas / ddim_alphas_prev."""
-        self._ddim.make_schedule(ddim_num_steps=num_steps, ddim_eta=0.0, verbose=verbose)
-        self.ddim_timesteps = self._ddim.ddim_timesteps
-        self.ddim_alphas = self._ddim.ddim_alphas
-        self.ddim_alphas_prev = self._ddim.ddim_alphas_prev
+class UniPCSampler(MultistepSampler):
+    solver = SOLVERS['unipc']
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, x_T=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
@@ -160,40 +148,10 @@ class UniPCSampler:
         """intermediates as DDIMSampler's: x_inter / pred_x0 = [x_T, one entry per step with index % log_every_t == 0 or the first
         executed one] (x_inter: the predicted latent x~_{k+1} after the step; pred_x0: the solver's m_k), from the in-library loop's
         trace or the step loop alike.  guidance_rescale = phi in [0, 1], engaged with guidance and phi > 0.  ``seeds``
-        (as DDIMSampler.sample's): x_T from noise.normal on stream 0 unless given -- this solver's only draw; no torch generator is advanced."""
-        if kw.get('eta') not in (None, 0, 0.0):
-            raise NotImplementedError('UniPCSampler is deterministic: eta is not an option of UniPC')
-        for k in self._REJECTED:
-            if kw.get(k) not in (None, False):
-                raise NotImplementedError(f'UniPCSampler.sample option {k} is not on the MakeupDiffuse path')
-        if kw.get('temperature', 1.0) != 1.0 or kw.get('noise_dropout', 0.0) != 0.0:
-            raise NotImplementedError('UniPCSampler draws no noise: temperature / noise_dropout do not apply')
-        if mask is not None or x0 is not None:
-            raise NotImplementedError('UniPCSampler: masked sampling (mask / x0) is not defined for this solver: the blend would have '
-                                      'to act on the two latents it carries')
-        if order not in (1, 2, 3):
-            raise ValueError('UniPCSampler: order must be 1, 2 or 3')
-        C, H, W = shape
-        size = (batch_size, C, H, W)
-        phi = _check_rescale(guidance_rescale)
-        if unconditional_conditioning is None or unconditional_guidance_scale == 1.0:
-            phi = 0.0          # no unconditional half: not engaged
-        if int(log_every_t) < 1:
-            raise ValueError(f'log_every_t must be >= 1, got {log_every_t}')
-        if seeds is not None:
-            seeds = _check_seeds(seeds, batch_size)
-        self.make_schedule(S, verbose=False)
-        if x_T is None and seeds is not None:
-            from .noise import STREAM_START, normal
-            img = normal(seeds, size[1:], stream=STREAM_START, device=self.model.device)
-        else:
-            img = torch.randn(size, device=self.model.device) if x_T is None else x_T
-        intermediates = {'x_inter': [img], 'pred_x0': [img]}
-        img = self._loop(img, conditioning, len(self.ddim_timesteps), unconditional_guidance_scale, unconditional_conditioning, order,
-                         lower_order_final, corrector, callback, trace=(int(log_every_t), intermediates), phi=phi)
-        if len(intermediates['x_inter']) == 1:          # (a hook that keeps no trace)
-            intermediates['x_inter'].append(img)
-        return img, intermediates
+        (as DDIMSampler.sample's): x_T from noise.normal on stream 0 unless given -- this solver's only draw; no torch generator is advanced.
+        mask / x0 are refused: masked sampling is not defined for this solver."""
+        return self._sample(S, batch_size, shape, conditioning, x_T, unconditional_guidance_scale, unconditional_conditioning,
+                            (order, lower_order_final, bool(corrector)), callback, mask, x0, log_every_t, guidance_rescale, seeds, kw)
 
     def sample_specs(self, *args, **kwargs):
         raise NotImplementedError('UniPCSampler: per-sample specs are not built for this solver (mkd_sample_rows runs DDIM and '
@@ -204,74 +162,5 @@ class UniPCSampler:
                lower_order_final=True, corrector=True, callback=None):
         """Reverse loop over ddim_timesteps[:t_start], newest first, on the schedule of the last make_schedule: regenerates a latent
         inverted with DDIMSampler.encode(x0, t_enc=t_start).  t_start is one number for the batch."""
-        if t_start > len(self.ddim_timesteps):
-            raise ValueError(f'UniPCSampler.decode: t_start {t_start} > {len(self.ddim_timesteps)} schedule steps')
-        if t_start <= 0:
-            return x_latent
-        return self._loop(x_latent, cond, int(t_start), unconditional_guidance_scale, unconditional_conditioning, order, lower_order_final,
-                          corrector, callback)
-
-    # the loop over the first n table entries, newest first
-    # trace = (log_every_t, the intermediates dict to append to) or None; phi: the engaged guidance rescale (0: off)
-    def _loop(self, img, cond, n, scale, uc, order, lower_order_final, corrector, callback, trace=None, phi=0.0):
-        timesteps = self.ddim_timesteps[:n]
-        a = [float(v) for v in self.ddim_alphas[:n]]
-        ap = [float(v) for v in self.ddim_alphas_prev[:n]]
-        fast = getattr(self.model, 'sample_loop_unipc', None)
-        if fast is not None and callback is None:          # the whole loop runs inside libmkd (mkd_sample_unipc)
-            kw = {}
-            if trace is not None:
-                kw['log_every_t'] = trace[0]
-            if phi != 0.0:
-                kw['guidance_rescale'] = phi
-            res = fast(img, cond, timesteps, a, ap, order, lower_order_final, bool(corrector), scale, uc, **kw)
-            if not isinstance(res, tuple):
-                return res
-            img, x_rows, x0_rows = res          # (latent, x_inter rows, pred_x0 rows); the latent stays the last x_inter entry
-            trace[1]['x_inter'] += [*x_rows[:-1], img]
-            trace[1]['pred_x0'] += list(x0_rows)
-            return img
-        step_fn = getattr(self.model, 'unipc_step', None)
-        on_device = step_fn is not None and img.is_cuda
-        if on_device:
-            from .engine import unipc_table
-            coef, _ = unipc_table(a, ap, order, lower_order_final, corrector)          # the floats the in-library loop uses
-        else:
-            coef, _ = unipc_coefficients(a, ap, order, lower_order_final, corrector)
-        hist = [None, None, None]                            # m_{k-1}, m_{k-2}, m_{k-3}
-        xc = None                                            # x^c_{k-1}
-        for k in range(n):
-            index = n - 1 - k
-            step = int(timesteps[index])
-            ts = torch.full((img.shape[0],), step, device=img.device, dtype=torch.long)
-            e_c, e_u = self._ddim._eps(img, cond, ts, scale, uc)
-            rescale = e_u is not None and phi != 0.0
-            if on_device:
-                img, xc, m0 = step_fn(img, xc, e_c, e_u, scale, coef[index], hist[0], hist[1], hist[2],
-                                      **({'guidance_rescale': phi} if rescale else {}))
-            else:
-                # host tensors (plumbing with a stand-in model, e.g. CPU tests): the same formulae in torch
-                c = [float(v) for v in coef[index]]
-                if rescale:
-                    e_t = rescale_guided_eps(e_c, e_u, scale, phi)
-                else:
-                    e_t = e_c if e_u is None else e_u + scale * (e_c - e_u)
-                m0 = (img - c[1] * e_t) * c[0]
-                if c[2] != 0.0:
-                    xc = c[2] * xc + c[3] * m0
-                    for cj, mj in zip(c[4:7], hist):
-                        if cj != 0.0:
-                            xc = xc + cj * mj
-                else:
-                    xc = img
-                img = c[7] * xc + c[8] * m0
-                for cj, mj in zip(c[9:11], hist):
-                    if cj != 0.0:
-                        img = img + cj * mj
-            hist = [m0, hist[0], hist[1]]
-            if callback:
-                callback(k)
-            if trace is not None and (index % trace[0] == 0 or index == n - 1):
-                trace[1]['x_inter'].append(img)
-                trace[1]['pred_x0'].append(m0)
-        return img
+        return self._decode(x_latent, cond, t_start, unconditional_guidance_scale, unconditional_conditioning,
+                            (order, lower_order_final, bool(corrector)), callback)

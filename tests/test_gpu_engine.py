@@ -607,3 +607,134 @@ def test_reloading_weights_frees_the_derived_copies_and_invalidates_the_plan():
     e.prepare(hint, ctx)
     assert not torch.equal(e.eps(x, t), a) and e.device_bytes() <= b0 + (1 << 20)
     e.close()
+
+
+# ---- the exported entry each option combination reaches (MkdEngine._sample_call / _step_call) ------------------------------------------
+class _Recorder:
+    """eng.lib behind a proxy that notes every mkd_sample* / mkd_<solver>_step* symbol called through it"""
+
+    def __init__(self, lib):
+        self._lib, self.calls = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not (name.startswith('mkd_sample') or name.split('_step')[0] in ('mkd_ddim', 'mkd_dpmpp', 'mkd_unipc')):
+            return fn
+
+        def call(*args):
+            self.calls.append(name)
+            return fn(*args)
+        return call
+
+
+@pytest.fixture(scope='module')
+def recorded():
+    eng, g = _small_engine()
+    rec = _Recorder(eng.lib)
+    eng.lib = rec
+    yield eng, g, rec
+    eng.lib = rec._lib
+    eng.close()
+
+
+# (method, trace, guidance rescale, masked, eta) -> the entry; the rows of the table in MkdEngine._sample_call's docstring
+LOOP_ENTRIES = [
+    ('sample', True, 0.0, False, False, 'mkd_sample_masked_ex'),
+    ('sample', False, 0.7, True, True, 'mkd_sample_masked_ex'),
+    ('sample', True, 0.7, True, False, 'mkd_sample_masked_ex'),
+    ('sample', False, 0.0, True, False, 'mkd_sample_masked'),
+    ('sample', False, 0.0, True, True, 'mkd_sample_masked'),
+    ('sample', False, 0.0, False, True, 'mkd_sample_eta'),
+    ('sample', False, 0.0, False, False, 'mkd_sample'),
+    ('sample_dpmpp', True, 0.0, False, False, 'mkd_sample_dpmpp_ex'),
+    ('sample_dpmpp', False, 0.7, True, False, 'mkd_sample_dpmpp_ex'),
+    ('sample_dpmpp', False, 0.0, True, False, 'mkd_sample_dpmpp'),
+    ('sample_dpmpp', False, 0.0, False, False, 'mkd_sample_dpmpp'),
+    ('sample_unipc', True, 0.0, False, False, 'mkd_sample_unipc_ex'),
+    ('sample_unipc', False, 0.7, False, False, 'mkd_sample_unipc_ex'),
+    ('sample_unipc', False, 0.0, False, False, 'mkd_sample_unipc'),
+    ('sample_unipc', False, 0.0, True, False, 'mkd_sample_unipc'),          # (the library refuses the mask: MkdError)
+    ('sample_unipc', True, 0.0, True, False, 'mkd_sample_unipc_ex'),
+]
+
+
+@pytest.mark.parametrize('method,trace,phi,masked,eta,entry', LOOP_ENTRIES)
+@pytest.mark.parametrize('use_graph', [False, True])
+def test_each_option_combination_reaches_its_exported_entry(recorded, method, trace, phi, masked, eta, entry, use_graph):
+    """Two steps, batch 2, the 8x8 latent of this file's golden inputs (the size this net runs at throughout the file); a guidance
+    rescale needs the guided batch [uncond; cond]."""
+    from makeupdiffuse_amd.lib import MkdError
+    eng, g, rec = recorded
+    sch = sampler.Schedule().make_ddim(5, 0.5 if eta else 0.0)
+    n = 2
+    tables = [sch.ddim_timesteps[:n], sch.ddim_alphas[:n], sch.ddim_alphas_prev[:n]]
+    if method == 'sample':
+        tables.append(sch.ddim_sqrt_one_minus_alphas[:n])
+    x = g['x']
+    gen = torch.Generator().manual_seed(7)
+    kw = dict(use_graph=use_graph)
+    if phi:
+        eng.prepare(torch.cat([g['hint'], g['hint']]), torch.cat([g['uctx'], g['ctx']]))
+        kw.update(cfg_scale=9.0, guidance_rescale=phi)
+    else:
+        eng.prepare(g['hint'], g['ctx'])
+    if trace:
+        kw.update(want_trace=True, log_every_t=1)
+    if masked:
+        mask = torch.zeros(1, 1, 8, 8)
+        mask[..., :4] = 1.0
+        kw.update(x0=torch.randn(x.shape, generator=gen), mask=mask, q_sqrt_ac=[0.9, 0.8][:n], q_sqrt_1m_ac=[0.4, 0.6][:n],
+                  q_noise=torch.randn((n, *x.shape), generator=gen))
+    if eta:
+        kw.update(sigmas=[0.0, float(sch.ddim_sigmas[1])], noise=torch.randn((n, *x.shape), generator=gen))
+    rec.calls.clear()
+    if method == 'sample_unipc' and masked:
+        with pytest.raises(MkdError):
+            getattr(eng, method)(x, *tables, **kw)
+    else:
+        out = getattr(eng, method)(x, *tables, **kw)
+        lat = out[0] if trace else out
+        assert tuple(lat.shape) == tuple(x.shape) and bool(torch.isfinite(lat).all())
+        if trace:
+            assert len(out) == 3 and out[1].shape[0] == out[2].shape[0] == n and torch.equal(out[1][-1], lat)
+    assert rec.calls == [entry]
+
+
+@pytest.mark.parametrize('step', ['ddim_step', 'dpmpp_step', 'unipc_step'])
+@pytest.mark.parametrize('guided,phi', [(False, 0.0), (False, 0.7), (True, 0.0), (True, 0.7)])
+def test_step_calls_use_the_ex_entry_exactly_with_an_engaged_rescale(recorded, step, guided, phi):
+    eng, g, rec = recorded
+    gen = torch.Generator().manual_seed(8)
+    x, e_c = g['x'], torch.randn(g['x'].shape, generator=gen)
+    e_u = torch.randn(g['x'].shape, generator=gen) if guided else None
+    scale = 9.0 if guided else 1.0
+    rec.calls.clear()
+    if step == 'ddim_step':
+        out = eng.ddim_step(x, e_c, e_u, scale, 0.5, 0.6, 0.0, 0.5 ** 0.5, guidance_rescale=phi)
+    elif step == 'dpmpp_step':
+        out = eng.dpmpp_step(x, e_c, e_u, scale, [1.4, 0.7, 0.9, 0.3, 0.0, 0.0], guidance_rescale=phi)
+    else:
+        out = eng.unipc_step(x, None, e_c, e_u, scale, [1.4, 0.7, 0.0, 0.0, 0.0, 0.0, 0.0, 0.9, 0.3, 0.0, 0.0, 0.0], guidance_rescale=phi)
+    assert all(bool(torch.isfinite(t).all()) for t in out)
+    assert rec.calls == ['mkd_' + step + ('_ex' if guided and phi else '')]
+
+
+# step_launches(use_graph, cfg, rescale) / (use_graph, cfg, per_sample=True) and eps_launches() of this net prepared with batch 2, read
+# from the commit before the engine's loop and step methods shared one call path: no launch was added or removed
+LAUNCHES = {'eps': 412,
+            ('rows', False, False): 406, ('rows', False, True): 407, ('rows', True, False): 406, ('rows', True, True): 407,
+            (False, False, False): 407, (False, False, True): 407, (False, True, False): 408, (False, True, True): 409,
+            (True, False, False): 406, (True, False, True): 406, (True, True, False): 407, (True, True, True): 408}
+
+
+def test_launch_counts_are_those_before_the_shared_call_path(recorded):
+    eng, g, _ = recorded
+    eng.prepare(g['hint'], g['ctx'])
+    got = {'eps': eng.eps_launches()}
+    for ug in (False, True):
+        for cfg in (False, True):
+            got[('rows', ug, cfg)] = eng.step_launches(ug, cfg, per_sample=True)
+            for rescale in (False, True):
+                got[(ug, cfg, rescale)] = eng.step_launches(ug, cfg, rescale)
+    print(got)
+    assert got == LAUNCHES

@@ -125,6 +125,43 @@ def test_fast_path_gets_the_draws_of_the_step_loop_in_its_order(monkeypatch):
             assert torch.equal(seen['noise'], torch.stack([v for k, v in drawn if k == 'eta']))
 
 
+def test_fast_path_draw_count_with_a_zero_sigma_and_dropout():
+    """The generator's use on the unseeded masked eta fast path, replayed by hand: x_T first, then for each executed step the blend's
+    randn_like(x0) and the step's eta draw with the dropout applied to it; a step whose sigma is 0 gets zeros and no draw; nothing is
+    drawn after the last step (the generator ends in the replay's state)."""
+    m = HostModel(lambda x, t, c: 0.1 * x)
+    shape = (2, 4, 3, 3)
+    x0 = torch.randn(shape)
+    mask = torch.ones(2, 1, 3, 3)
+    seen = {}
+
+    def fast(x, c, timesteps, alphas, alphas_prev, s1m, scale=1.0, uc=None, **kw):
+        seen.update(kw, x=x)
+        return x
+
+    m.sample_loop_fast = fast
+    smp = DDIMSampler(m)
+    smp.make_schedule(5, ddim_eta=0.5, verbose=False)
+    smp.ddim_sigmas[1] = 0.0
+    n = len(smp.ddim_timesteps)
+    torch.manual_seed(21)
+    smp.ddim_sampling({}, shape, mask=mask, x0=x0, noise_dropout=0.25)
+    state = torch.get_rng_state()
+    torch.manual_seed(21)
+    x_T = torch.randn(shape)
+    q_rows, eta_rows = [], []
+    for k in range(n):
+        q_rows.append(torch.randn_like(x0))
+        if float(smp.ddim_sigmas[n - 1 - k]) != 0.0:
+            eta_rows.append(torch.nn.functional.dropout(torch.randn(shape), p=0.25))
+        else:
+            eta_rows.append(torch.zeros(shape))
+    assert torch.equal(torch.get_rng_state(), state)
+    assert torch.equal(seen['x'], x_T)
+    assert torch.equal(seen['q_noise'], torch.stack(q_rows))
+    assert torch.equal(seen['noise'], torch.stack(eta_rows)) and not seen['noise'][n - 2].any() and seen['noise'][0].any()
+
+
 def test_mask_errors():
     m = HostModel(lambda x, t, c: torch.zeros_like(x))
     s = DDIMSampler(m)
