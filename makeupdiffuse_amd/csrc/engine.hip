@@ -158,13 +158,9 @@ static int build_step_table(const mkd_sample_row* rows, int batch, int solver, s
             if (!tab) continue;
             StepRow& e = (*tab)[(size_t)k * batch + b];
             e.t = t; e.temb_row = it->second; e.active = active ? 1 : 0; e.scale = q.cfg_scale;
-            if (solver == 0) {          // (fill_step_state's expressions)
-                const float sg = q.sigmas ? q.sigmas[i] : 0.f;
-                e.coef[0] = 1.0f / sqrtf(q.alphas[i]);
-                e.coef[1] = sqrtf(q.alphas_prev[i]);
-                e.coef[2] = sqrtf(1.0f - q.alphas_prev[i] - sg * sg);
-                e.coef[3] = q.sqrt_one_minus_alphas[i];
-                e.sigma = sg;
+            if (solver == 0) {
+                e.sigma = q.sigmas ? q.sigmas[i] : 0.f;
+                DdimCoef::of_alphas(q.alphas[i], q.alphas_prev[i], e.sigma, q.sqrt_one_minus_alphas[i], e.coef);
             } else for (int j = 0; j < 6; ++j) e.dpm[j] = q.dpm[6 * i + j];
         }
     if (s_max_out) *s_max_out = s_max;
@@ -1894,33 +1890,33 @@ struct mkd_ctx {
     // head = step setup (+ the batch doubling with guidance), factor = the guidance-rescale factors (null unless the key asks for
     // them), tail = the solver's last kernel
     struct StateStep { std::vector<OpFn> head; StepIo io; OpFn factor; OpFn tail; };
+    // What the loops know of a solver (StepKey::solver: 0 DDIM, 1 DPM-Solver++, 2 UniPC): its step launcher, the depth of its ring of
+    // x0-predictions (0: none), the planes it keeps in s_ring (the ring; UniPC: + the corrected latent behind it) and its host table
+    struct Solver { int (*launch)(const StepOps&, hipStream_t); int depth, planes; const float* SampleReq::*table; int stride; };
+    static const Solver& solver_of(int s) {
+        static const Solver tab[3] = {{launch_ddim_step, 0, 0, nullptr, 0}, {launch_dpmpp_step, 3, 3, &SampleReq::dpm, 6},
+                                      {launch_unipc_step, 4, 5, &SampleReq::uni, 12}};
+        return tab[s];
+    }
     int sample_elems() const { return cfg.in_channels * h * w; }          // elements of one sample's latent
     StateStep state_step(const StepKey& k) {
         mkd_ctx* self = this;
         const int64_t n = latent_n(k.batch);
         StateStep s; s.io = step_io(k.cfg != 0, s_xa, n);
-        if (k.rows) {          // per-sample: its own setup and update kernels around the same evaluation, the same number of launches
-            s.head.push_back([self, Bn = B, samples = k.batch](hipStream_t st) {
-                const TembSel ts = self->temb_sel();
-                return launch_step_setup_rows(self->s_state, self->s_t, Bn, samples, st, self->temb_skip ? &ts : nullptr); });
-            if (k.cfg) s.head.push_back([self, n](hipStream_t st) { return launch_repeat_batch(self->s_xa, self->s_xin, n, 2, st); });
-            s.tail = [self, io = s.io, dpm_on = k.solver != 0, samples = k.batch, per = sample_elems()](hipStream_t st) {
-                return dpm_on ? launch_dpmpp_step_rows(self->s_xa, io.ec, io.eu, nullptr, self->s_state, nullptr, nullptr, self->s_xa, nullptr, samples, per, st)
-                              : launch_ddim_step_rows(self->s_xa, io.ec, io.eu, nullptr, self->s_state, nullptr, 0.f, self->s_xa, nullptr, samples, per, st); };
-            return s;
-        }
-        s.head.push_back([self, Bn = B, n](hipStream_t st) {
+        // per-sample: its own setup kernel and the per-sample form of the update around the same evaluation, the same number of launches
+        s.head.push_back([self, Bn = B, n, samples = k.rows ? k.batch : 0](hipStream_t st) {
             const TembSel ts = self->temb_sel();
-            return launch_step_setup(self->s_state, self->s_t, Bn, self->s_xa, n, st, self->temb_skip ? &ts : nullptr); });
+            return samples ? launch_step_setup_rows(self->s_state, self->s_t, Bn, samples, st, self->temb_skip ? &ts : nullptr)
+                           : launch_step_setup(self->s_state, self->s_t, Bn, self->s_xa, n, st, self->temb_skip ? &ts : nullptr); });
         if (k.cfg) s.head.push_back([self, n](hipStream_t st) { return launch_repeat_batch(self->s_xa, self->s_xin, n, 2, st); });
         const float* kf = k.rescale > 0 ? s_kfac : nullptr;
         const int per = sample_elems();
         if (kf) s.factor = [self, io = s.io, per, batch = k.batch, scale = k.scale](hipStream_t st) {
             return launch_cfg_rescale_factor(io.ec, io.eu, scale, 0.f, self->s_state, batch, per, self->s_kfac, st); };
-        s.tail = [self, io = s.io, n, solver = k.solver, scale = k.scale, kf, per](hipStream_t st) {
-            return solver == 2 ? launch_unipc_step_state(self->s_xa, io.ec, io.eu, scale, self->s_state, n, st, kf, per)
-                 : solver == 1 ? launch_dpmpp_step_state(self->s_xa, io.ec, io.eu, scale, self->s_state, n, st, kf, per)
-                               : launch_ddim_step_state(self->s_xa, io.ec, io.eu, scale, self->s_state, n, st, kf, per); };
+        StepOps o{};          // the st form: everything else of the step comes from the device state
+        o.x = o.x_out = s_xa; o.eps_c = s.io.ec; o.eps_u = s.io.eu; o.scale = k.scale; o.kfac = kf; o.per = per; o.n = n;
+        o.samples = k.rows ? k.batch : 0; o.st = s_state;
+        s.tail = [o, launch = solver_of(k.solver).launch](hipStream_t st) { return launch(o, st); };
         return s;
     }
     int enqueue_state_steps(const StepKey& k, int steps, hipStream_t stream) {
@@ -2093,23 +2089,16 @@ struct mkd_ctx {
         h_state->counter = n_steps - 1;
         for (int i = 0; i < n_steps; ++i) {
             h_state->timesteps[i] = r.timesteps[i];
-            h_state->coef[4 * i + 0] = 1.0f / sqrtf(r.alphas[i]);
-            h_state->coef[4 * i + 1] = sqrtf(r.alphas_prev[i]);
             const float sg = stochastic ? r.sigmas[i] : 0.f;
-            h_state->coef[4 * i + 2] = sqrtf(1.0f - r.alphas_prev[i] - sg * sg);
-            h_state->coef[4 * i + 3] = r.s1m ? r.s1m[i] : 0.f;
+            DdimCoef::of_alphas(r.alphas[i], r.alphas_prev[i], sg, r.s1m ? r.s1m[i] : 0.f, h_state->coef + 4 * i);
             h_state->sigma[i] = sg;
             for (int j = 0; j < 6; ++j) h_state->dpm[6 * i + j] = r.dpm ? r.dpm[6 * i + j] : 0.f;
             if (r.uni) for (int j = 0; j < 12; ++j) h_state->uni[12 * i + j] = r.uni[12 * i + j];
         }
         h_state->ring = (r.dpm || r.uni) ? s_ring : nullptr;
-        h_state->xc = r.uni ? s_ring + 4 * latent_n(r.batch) : nullptr;          // (null: step_setup_kernel leaves cur_uni / cur_uslot alone)
-        for (int j = 0; j < 12; ++j) h_state->cur_uni[j] = 0.f;
-        for (int j = 0; j < 4; ++j) h_state->cur_uslot[j] = 0;
-        for (int j = 0; j < 6; ++j) h_state->cur_dpm[j] = 0.f;
-        h_state->cur_slot[0] = h_state->cur_slot[1] = h_state->cur_slot[2] = 0;
+        h_state->xc = r.uni ? s_ring + 4 * latent_n(r.batch) : nullptr;
         h_state->noise = stochastic ? r.noise : nullptr; h_state->temperature = r.temperature; h_state->n_steps = n_steps;
-        h_state->cur_sigma = 0.f; h_state->cur_row = 0;
+        h_state->cur_row = 0;
         // masked sampling: read by step_setup_kernel; x0 null leaves the (shared) captured step unmasked
         h_state->x0 = qm ? qm->x0 : nullptr; h_state->mask = qm ? qm->mask : nullptr; h_state->q_noise = qm ? qm->noise : nullptr;
         h_state->q_hw = hw; h_state->q_chw = cfg.in_channels * hw;
@@ -2122,7 +2111,6 @@ struct mkd_ctx {
         // intermediates trace and guidance rescale: read by the step's last kernel(s); null pointers leave the (shared) capture untraced
         const mkd_sample_extras* ex = r.ex;
         h_state->trace_x = ex ? ex->trace_x : nullptr; h_state->trace_x0 = ex ? ex->trace_x0 : nullptr;
-        h_state->cur_trace = -1;
         if (traced(r)) sample_log_rows(n_steps, ex->log_every_t, h_state->trace_row);
         else for (int i = 0; i < n_steps; ++i) h_state->trace_row[i] = -1;
         h_state->phi = ex ? ex->guidance_rescale : 0.f;
@@ -2201,6 +2189,7 @@ struct mkd_ctx {
         float* xa = s_xa; float* xb = s_xb;
         const float* kf = key.rescale > 0 ? s_kfac : nullptr;
         const int per = sample_elems();
+        const Solver& sv = solver_of(key.solver);
         std::vector<short> row_of(n_steps, (short)-1);
         if (traced(r)) sample_log_rows(n_steps, r.ex->log_every_t, row_of.data());
         for (int i = 0; i < n_steps; ++i) {
@@ -2219,23 +2208,19 @@ struct mkd_ctx {
             if (key.cfg) { rc = launch_repeat_batch(xa, s_xin, n, 2, stream); if (rc) return rc; }
             rc = eps(io.x, s_t, s_eps, stream); if (rc) return rc;
             if (kf) { rc = launch_cfg_rescale_factor(io.ec, io.eu, key.scale, r.ex->guidance_rescale, nullptr, r.batch, per, s_kfac, stream); if (rc) return rc; }
-            if (key.solver == 2) {      // m_k into slot k mod 4 of the four-slot ring, x^c in place behind it (k = i, the executed step)
-                const float* d = r.uni + 12 * index;
-                const UniCoef kc = {d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10]};
-                float* xc = s_ring + 4 * n;
-                rc = launch_unipc_step(xa, xc, io.ec, io.eu, key.scale, kc, s_ring + (int64_t)((i + 3) % 4) * n, s_ring + (int64_t)((i + 2) % 4) * n,
-                                       s_ring + (int64_t)((i + 1) % 4) * n, xb, xc, s_ring + (int64_t)(i % 4) * n, n, stream, kf, per, tx, tx0);
-            } else if (key.solver) {    // m_k into ring slot k mod 3; m_{k-1}, m_{k-2} from the other two (k = i, the executed step)
-                const float* d = r.dpm + 6 * index;
-                const DpmCoef kc = {d[0], d[1], d[2], d[3], d[4], d[5]};
-                rc = launch_dpmpp_step(xa, io.ec, io.eu, key.scale, kc, s_ring + (int64_t)((i + 2) % 3) * n, s_ring + (int64_t)((i + 1) % 3) * n, xb,
-                                       s_ring + (int64_t)(i % 3) * n, n, stream, kf, per, tx, tx0);
+            StepOps o{};          // the record form: this step's numbers from the host tables
+            o.x = xa; o.eps_c = io.ec; o.eps_u = io.eu; o.scale = key.scale; o.kfac = kf; o.per = per; o.n = n; o.x_out = xb; o.x_copy = tx;
+            if (sv.depth) {       // m_k into its ring slot, the history from the others (k = i, the executed step); UniPC: x^c in place behind the ring
+                memcpy(o.coef, r.*sv.table + sv.stride * index, sv.stride * sizeof(float));
+                o.p_out = s_ring + ring_slot(i, 0, sv.depth) * n; o.p_copy = tx0;
+                for (int j = 1; j < sv.depth; ++j) o.hist[j - 1] = s_ring + ring_slot(i, j, sv.depth) * n;
+                if (sv.planes > sv.depth) o.xc_prev = o.xc_out = s_ring + sv.depth * n;
             } else {
-                const float sg = stochastic ? r.sigmas[index] : 0.f;
-                rc = launch_ddim_step(xa, io.ec, io.eu, key.scale, r.alphas[index], r.alphas_prev[index], sg, r.s1m[index],
-                                      sg != 0.f ? r.noise + (int64_t)i * n : nullptr, r.temperature, xb, tx0, n, stream, kf, per, tx);
+                o.sigma = stochastic ? r.sigmas[index] : 0.f;
+                DdimCoef::of_alphas(r.alphas[index], r.alphas_prev[index], o.sigma, r.s1m[index], o.coef);
+                o.noise = o.sigma != 0.f ? r.noise + (int64_t)i * n : nullptr; o.temperature = r.temperature; o.p_out = tx0;
             }
-            if (rc) return rc;
+            rc = sv.launch(o, stream); if (rc) return rc;
             float* tmp = xa; xa = xb; xb = tmp;
         }
         MKD_HIP_CHECK(hipMemcpyAsync(r.x_out, xa, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
@@ -2252,7 +2237,7 @@ struct mkd_ctx {
         key.rescale = (key.cfg && r.ex && r.ex->guidance_rescale > 0.f) ? 1 : 0;          // (phi = 0, scale 1: not engaged, today's step)
         key.temb = temb_table;          // (the steps take the time embedding from the table exactly when the table is on)
         const int64_t n = latent_n(r.batch);
-        if (key.solver) { rc = ensure_ring(n, key.solver == 2 ? 5 : 3); if (rc) return rc; }
+        if (key.solver) { rc = ensure_ring(n, solver_of(key.solver).planes); if (rc) return rc; }
         if (!r.use_graph) return sample_eager(r, key, stochastic, stream);
         hipStream_t ls = nullptr;
         rc = loop_begin(r.x_T, n, true, stream, &ls); if (rc) return rc;
@@ -2276,9 +2261,9 @@ struct mkd_ctx {
         rows_cap = cap;
         return 0;
     }
-    // The whole reverse loop with one request row per sample.  Only the step-state kernels differ from sample(): the evaluation, the
-    // capture helpers and the loop forms are shared (StepKey::rows).  use_graph == 0 enqueues the same step kernels uncaptured on the
-    // caller's stream (they read the device step table, so there is no host-table form of this loop)
+    // The whole reverse loop with one request row per sample.  Only the setup kernel and the form of the step kernel differ from
+    // sample(): the evaluation, the capture helpers and the loop forms are shared (StepKey::rows).  use_graph == 0 enqueues the same
+    // step kernels uncaptured on the caller's stream (they read the device step table, so there is no host-table form of this loop)
     int sample_rows(const SampleReq& r, hipStream_t stream) {
         struct Clear { bool& flag; ~Clear() { flag = false; } } clear_temb_skip{temb_skip};
         const std::string who = "mkd_sample_rows: ";
@@ -2296,7 +2281,7 @@ struct mkd_ctx {
         StepKey key; key.gen = plan_generation; key.cfg = guided; key.scale = 0.f; key.batch = r.batch; key.solver = r.solver; key.rescale = 0;
         key.temb = temb_table; key.rows = 1;
         const int64_t n = latent_n(r.batch);
-        if (key.solver) { rc = ensure_ring(n, 3); if (rc) return rc; }
+        if (key.solver) { rc = ensure_ring(n, solver_of(key.solver).planes); if (rc) return rc; }
         rc = ensure_rows(tab.size()); if (rc) return rc;
         hipStream_t ls = nullptr;          // uncaptured: the caller's stream, uploads included
         rc = loop_begin(r.x_T, n, r.use_graph != 0, stream, &ls); if (rc) return rc;
@@ -2304,7 +2289,6 @@ struct mkd_ctx {
         h_state->counter = s_max - 1; h_state->n_steps = s_max;
         h_state->noise = stochastic ? r.noise : nullptr; h_state->temperature = r.temperature;
         h_state->ring = key.solver ? s_ring : nullptr;
-        h_state->cur_trace = -1;
         for (int i = 0; i < MKD_MAX_STEPS; ++i) h_state->trace_row[i] = -1;
         h_state->rows = s_rows; h_state->rows_batch = r.batch;
         memcpy(h_rows, tab.data(), tab.size() * sizeof(StepRow));
@@ -2982,25 +2966,35 @@ int mkd_eps(mkd_ctx* ctx, const float* x, const int64_t* t, float* eps_out, void
     if (!ctx) return mkd_fail(MKD_ERR_ARG, "null ctx");
     return ctx->eps(x, t, eps_out, (hipStream_t)stream);
 }
+// The record form of a stand-alone step entry: the operands every solver has (k null: no rescale)
+static StepOps step_entry_ops(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, const float* k, int n_per_sample,
+                              float* x_out, float* p_out, int64_t n) {
+    StepOps o{};
+    o.x = x; o.eps_c = eps_c; o.eps_u = eps_u; o.scale = cfg_scale; o.kfac = k; o.per = n_per_sample; o.n = n; o.x_out = x_out; o.p_out = p_out;
+    return o;
+}
+// mkd_ddim_step and mkd_ddim_step_ex (who: the entry's name in its messages; the plain entry has no k)
+static int ddim_step_entry(const char* who, const float* x, const float* eps_c, const float* eps_u, float cfg_scale, float a_t, float a_prev,
+                           float sigma_t, float sqrt_one_minus_at, const float* noise, float temperature, const float* k, int n_per_sample,
+                           float* x_prev, float* pred_x0, int64_t n, void* stream) {
+    if (!x || !eps_c || !x_prev) return mkd_fail(MKD_ERR_ARG, std::string(who) + ": null pointer");
+    if (int rc = check_rescale_args(k, eps_u, n, n_per_sample, who)) return rc;
+    StepOps o = step_entry_ops(x, eps_c, eps_u, cfg_scale, k, n_per_sample, x_prev, pred_x0, n);
+    DdimCoef::of_alphas(a_t, a_prev, sigma_t, sqrt_one_minus_at, o.coef);
+    o.sigma = sigma_t; o.noise = noise; o.temperature = temperature;
+    return launch_ddim_step(o, (hipStream_t)stream);
+}
 int mkd_ddim_step(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, float a_t, float a_prev,
                   float sigma_t, float sqrt_one_minus_at, const float* noise, float temperature, float* x_prev,
                   float* pred_x0, int64_t n, void* stream) {
-    if (!x || !eps_c || !x_prev) return mkd_fail(MKD_ERR_ARG, "mkd_ddim_step: null pointer");
-    return launch_ddim_step(x, eps_c, eps_u, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, noise, temperature, x_prev,
-                            pred_x0, n, (hipStream_t)stream);
-}
-static int check_rescale_args(const float* k, const float* eps_u, int64_t n, int n_per_sample, const char* who) {
-    if (k && (!eps_u || n_per_sample <= 0 || n % n_per_sample))
-        return mkd_fail(MKD_ERR_ARG, std::string(who) + ": k needs eps_u and an n_per_sample > 0 that divides n");
-    return 0;
+    return ddim_step_entry("mkd_ddim_step", x, eps_c, eps_u, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, noise, temperature, nullptr, 0,
+                           x_prev, pred_x0, n, stream);
 }
 int mkd_ddim_step_ex(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, float a_t, float a_prev,
                      float sigma_t, float sqrt_one_minus_at, const float* noise, float temperature, const float* k, int n_per_sample,
                      float* x_prev, float* pred_x0, int64_t n, void* stream) {
-    if (!x || !eps_c || !x_prev) return mkd_fail(MKD_ERR_ARG, "mkd_ddim_step_ex: null pointer");
-    if (int rc = check_rescale_args(k, eps_u, n, n_per_sample, "mkd_ddim_step_ex")) return rc;
-    return launch_ddim_step(x, eps_c, eps_u, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, noise, temperature, x_prev,
-                            pred_x0, n, (hipStream_t)stream, k, n_per_sample);
+    return ddim_step_entry("mkd_ddim_step_ex", x, eps_c, eps_u, cfg_scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, noise, temperature, k,
+                           n_per_sample, x_prev, pred_x0, n, stream);
 }
 int mkd_cfg_rescale_factor(const float* eps_c, const float* eps_u, float scale, float phi, int batch, int n_per_sample, float* k_out,
                            void* stream) {
@@ -3090,20 +3084,25 @@ int mkd_dpmpp_table(int n_steps, const float* alphas, const float* alphas_prev, 
     }
     return 0;
 }
+// mkd_dpmpp_step and mkd_dpmpp_step_ex (who: the entry's name in its messages; the plain entry has no k)
+static int dpmpp_step_entry(const char* who, const float* x, const float* eps_c, const float* eps_u, float cfg_scale, const float* coef6,
+                            const float* m1, const float* m2, const float* k, int n_per_sample, float* x_prev, float* m0_out, int64_t n,
+                            void* stream) {
+    if (!x || !eps_c || !coef6 || !x_prev || !m0_out || n <= 0) return mkd_fail(MKD_ERR_ARG, std::string(who) + ": null pointer or empty tensor");
+    if ((coef6[4] != 0.f && !m1) || (coef6[5] != 0.f && !m2)) return mkd_fail(MKD_ERR_ARG, std::string(who) + ": a non-zero c_1 / c_2 needs m1 / m2");
+    if (int rc = check_rescale_args(k, eps_u, n, n_per_sample, who)) return rc;
+    StepOps o = step_entry_ops(x, eps_c, eps_u, cfg_scale, k, n_per_sample, x_prev, m0_out, n);
+    memcpy(o.coef, coef6, 6 * sizeof(float));
+    o.hist[0] = m1; o.hist[1] = m2;
+    return launch_dpmpp_step(o, (hipStream_t)stream);
+}
 int mkd_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, const float* coef6, const float* m1, const float* m2,
                    float* x_prev, float* m0_out, int64_t n, void* stream) {
-    if (!x || !eps_c || !coef6 || !x_prev || !m0_out || n <= 0) return mkd_fail(MKD_ERR_ARG, "mkd_dpmpp_step: null pointer or empty tensor");
-    if ((coef6[4] != 0.f && !m1) || (coef6[5] != 0.f && !m2)) return mkd_fail(MKD_ERR_ARG, "mkd_dpmpp_step: a non-zero c_1 / c_2 needs m1 / m2");
-    const DpmCoef k = {coef6[0], coef6[1], coef6[2], coef6[3], coef6[4], coef6[5]};
-    return launch_dpmpp_step(x, eps_c, eps_u, cfg_scale, k, m1, m2, x_prev, m0_out, n, (hipStream_t)stream);
+    return dpmpp_step_entry("mkd_dpmpp_step", x, eps_c, eps_u, cfg_scale, coef6, m1, m2, nullptr, 0, x_prev, m0_out, n, stream);
 }
 int mkd_dpmpp_step_ex(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, const float* coef6, const float* m1, const float* m2,
                       const float* k, int n_per_sample, float* x_prev, float* m0_out, int64_t n, void* stream) {
-    if (!x || !eps_c || !coef6 || !x_prev || !m0_out || n <= 0) return mkd_fail(MKD_ERR_ARG, "mkd_dpmpp_step_ex: null pointer or empty tensor");
-    if ((coef6[4] != 0.f && !m1) || (coef6[5] != 0.f && !m2)) return mkd_fail(MKD_ERR_ARG, "mkd_dpmpp_step_ex: a non-zero c_1 / c_2 needs m1 / m2");
-    if (int rc = check_rescale_args(k, eps_u, n, n_per_sample, "mkd_dpmpp_step_ex")) return rc;
-    const DpmCoef kc = {coef6[0], coef6[1], coef6[2], coef6[3], coef6[4], coef6[5]};
-    return launch_dpmpp_step(x, eps_c, eps_u, cfg_scale, kc, m1, m2, x_prev, m0_out, n, (hipStream_t)stream, k, n_per_sample);
+    return dpmpp_step_entry("mkd_dpmpp_step_ex", x, eps_c, eps_u, cfg_scale, coef6, m1, m2, k, n_per_sample, x_prev, m0_out, n, stream);
 }
 int mkd_sample_dpmpp(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
                      const float* alphas_prev, int order, int lower_order_final, const mkd_sample_mask* m, float cfg_scale, float* x_out,
@@ -3253,11 +3252,11 @@ int mkd_unipc_step_ex(const float* x, const float* xc_prev, const float* eps_c, 
                       float* m0_out, int64_t n, void* stream) {
     const char* who = k ? "mkd_unipc_step_ex" : "mkd_unipc_step";
     if (int rc = unipc_step_args(who, x, xc_prev, eps_c, coef12, m1, m2, m3, x_next, xc_out, m0_out, n)) return rc;
-    if (k) if (int rc = check_rescale_args(k, eps_u, n, n_per_sample, who)) return rc;
-    const float* c = coef12;
-    const UniCoef kc = {c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], c[10]};
-    return launch_unipc_step(x, xc_prev, eps_c, eps_u, cfg_scale, kc, m1, m2, m3, x_next, xc_out, m0_out, n, (hipStream_t)stream, k,
-                             k ? n_per_sample : 0);
+    if (int rc = check_rescale_args(k, eps_u, n, n_per_sample, who)) return rc;
+    StepOps o = step_entry_ops(x, eps_c, eps_u, cfg_scale, k, n_per_sample, x_next, m0_out, n);
+    memcpy(o.coef, coef12, 12 * sizeof(float));
+    o.hist[0] = m1; o.hist[1] = m2; o.hist[2] = m3; o.xc_prev = xc_prev; o.xc_out = xc_out;
+    return launch_unipc_step(o, (hipStream_t)stream);
 }
 int mkd_sample_unipc(mkd_ctx* ctx, const float* x_T, int batch, int n_steps, const int64_t* timesteps, const float* alphas,
                      const float* alphas_prev, int order, int lower_order_final, int corrector, const mkd_sample_mask* m, float cfg_scale,
@@ -3301,13 +3300,17 @@ int mkd_ddim_step_rows(const float* x, const float* eps_c, const float* eps_u, c
                        float* x_prev, float* pred_x0, int batch, int n_per_sample, void* stream) {
     if (!x || !eps_c || !rows || !x_prev) return mkd_fail(MKD_ERR_ARG, "mkd_ddim_step_rows: null pointer");
     if (batch <= 0 || batch > 65535 || n_per_sample <= 0) return mkd_fail(MKD_ERR_ARG, "mkd_ddim_step_rows: batch must be 1..65535, n_per_sample > 0");
-    return launch_ddim_step_rows(x, eps_c, eps_u, (const StepRow*)rows, nullptr, noise, temperature, x_prev, pred_x0, batch, n_per_sample, (hipStream_t)stream);
+    StepOps o = step_entry_ops(x, eps_c, eps_u, 0.f, nullptr, n_per_sample, x_prev, pred_x0, (int64_t)batch * n_per_sample);
+    o.rows = (const StepRow*)rows; o.samples = batch; o.noise = noise; o.temperature = temperature;
+    return launch_ddim_step(o, (hipStream_t)stream);
 }
 int mkd_dpmpp_step_rows(const float* x, const float* eps_c, const float* eps_u, const mkd_step_row* rows, const float* m1, const float* m2,
                         float* x_prev, float* m0_out, int batch, int n_per_sample, void* stream) {
     if (!x || !eps_c || !rows || !m1 || !m2 || !x_prev || !m0_out) return mkd_fail(MKD_ERR_ARG, "mkd_dpmpp_step_rows: null pointer");
     if (batch <= 0 || batch > 65535 || n_per_sample <= 0) return mkd_fail(MKD_ERR_ARG, "mkd_dpmpp_step_rows: batch must be 1..65535, n_per_sample > 0");
-    return launch_dpmpp_step_rows(x, eps_c, eps_u, (const StepRow*)rows, nullptr, m1, m2, x_prev, m0_out, batch, n_per_sample, (hipStream_t)stream);
+    StepOps o = step_entry_ops(x, eps_c, eps_u, 0.f, nullptr, n_per_sample, x_prev, m0_out, (int64_t)batch * n_per_sample);
+    o.rows = (const StepRow*)rows; o.samples = batch; o.hist[0] = m1; o.hist[1] = m2;
+    return launch_dpmpp_step(o, (hipStream_t)stream);
 }
 int mkd_q_sample_blend(const float* x0, const float* noise, float sqrt_ac, float sqrt_one_minus_ac, const float* mask, int mask_batch,
                        int mask_channels, const float* x, float* out, int batch, int channels, int hw, void* stream) {

@@ -12,6 +12,11 @@ __device__ __forceinline__ float cfg_rescaled_eps_at(float ec, float eu, float c
                                                      int n_per_sample) {
     return fmaf(cfg_scale, ec - eu, eu) * kfac[i / n_per_sample];
 }
+// The guided eps of every solver: model_uncond + s * (model_t - model_uncond), rescaled where the launch has factors (uniform branch)
+__device__ __forceinline__ float guided_eps_at(float ec, float eu, float cfg_scale, const float* __restrict__ kfac, int64_t i,
+                                               int n_per_sample) {
+    return kfac ? cfg_rescaled_eps_at(ec, eu, cfg_scale, kfac, i, n_per_sample) : fmaf(cfg_scale, ec - eu, eu);
+}
 
 // One workgroup of 256 threads per sample.  Thread t takes elements t, t + 256, ... of its sample and keeps fp64 sums of e_c, e_c^2,
 // g, g^2 (a product of two floats is exact in double); the sums are reduced inside each wave by shuffles (offsets 32 .. 1), then
@@ -55,44 +60,18 @@ __global__ void __launch_bounds__(256) cfg_rescale_factor_kernel(const float* __
 }
 
 // ---- DDIM x0 / x_{t-1} update, reference diffmk/cddim.py:39-40 (CFG) and :63,74-78 ----------------
-// One element, the ONE expression of every DDIM kernel (stand-alone, step state, per-sample rows): the guided eps, then x0 and
+// One element, the ONE expression of every form of the DDIM step kernel: (after the guided eps, guided_eps_at above) x0 and
 // x_{t-1}, then the eta term.  The library is built with -ffp-contract=fast, and what the compiler fuses depends on the code around
 // an expression (a 16-byte loop body fused sqrt(a_prev) x0 + dir e into an fma for two of its four elements, a scalar one for none),
 // so every rounding is spelled out: explicit fmas, and the two products of the sum pass through an empty asm statement (no
-// instruction; the value is opaque and cannot be folded into an fma).  These are the operations the uniform kernels compiled to
+// instruction; the value is opaque and cannot be folded into an fma).  These are the operations the scalar uniform kernels compiled to
 // before they were spelled out.
-struct DdimCoef { float sqrt_at_inv, sqrt_aprev, dir_coef, s1m; };
 __device__ __forceinline__ float ddim_keep_product(float p) { asm("" : "+v"(p)); return p; }
-__device__ __forceinline__ float ddim_eps_at(float ec, float eu, float cfg_scale) { return fmaf(cfg_scale, ec - eu, eu); }      // model_uncond + s * (model_t - model_uncond)
 __device__ __forceinline__ float ddim_update_at(float xv, float e, const DdimCoef& k, float& p0) {
     p0 = fmaf(-k.s1m, e, xv) * k.sqrt_at_inv;          // (x - sqrt(1-a_t) e) / sqrt(a_t)
     return ddim_keep_product(k.sqrt_aprev * p0) + ddim_keep_product(k.dir_coef * e);      // sqrt(a_prev) x0 + sqrt(1-a_prev-sigma^2) e
 }
 __device__ __forceinline__ float ddim_noise_at(float xp, float sigma, float nz, float temperature) { return fmaf(sigma * nz, temperature, xp); }
-
-// kfac non-null (with eps_u): the guidance-rescaled eps; x_copy non-null: x_prev once more (a trace row of the eager loop)
-__global__ void ddim_step_kernel(const float* __restrict__ x, const float* __restrict__ eps_c,
-                                 const float* __restrict__ eps_u, float cfg_scale, float sqrt_at_inv,
-                                 float sqrt_aprev, float dir_coef, float sigma_t, float s1m,
-                                 const float* __restrict__ noise, float temperature,
-                                 float* __restrict__ x_prev, float* __restrict__ pred_x0, int64_t n,
-                                 const float* __restrict__ kfac, int n_per_sample, float* __restrict__ x_copy) {
-    const DdimCoef k = {sqrt_at_inv, sqrt_aprev, dir_coef, s1m};
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float e = eps_c[i];
-        if (eps_u) {
-            const float u = eps_u[i];
-            if (kfac) e = cfg_rescaled_eps_at(e, u, cfg_scale, kfac, i, n_per_sample);
-            else e = ddim_eps_at(e, u, cfg_scale);
-        }
-        float p0;
-        float xp = ddim_update_at(x[i], e, k, p0);
-        if (noise) xp = ddim_noise_at(xp, sigma_t, noise[i], temperature);
-        x_prev[i] = xp;
-        if (pred_x0) pred_x0[i] = p0;
-        if (x_copy) x_copy[i] = xp;
-    }
-}
 
 // ---- device-resident step state for hipGraph replay of the DDIM loop -------------------------------------
 // One graph = one reverse step; what changes between steps (timestep, schedule coefficients) is read from
@@ -149,29 +128,16 @@ __global__ void latent_mask_from_labels_kernel(const uint8_t* __restrict__ label
 }
 
 __global__ void step_setup_kernel(StepState* st, int64_t* t_out, int batch, const TembSel ts, float* x, int64_t n) {
-    const int i = st->counter;          // read-only in this kernel: ddim_step_state_kernel, the step's last, advances it
+    const int i = st->counter;          // read-only in this kernel: the solver's step kernel, the step's last, advances it
     if (blockIdx.x == 0) {
         for (int b = threadIdx.x; b < batch; b += blockDim.x) t_out[b] = st->timesteps[i];
-        if (threadIdx.x == 0) {
-            st->cur[0] = st->coef[4 * i + 0]; st->cur[1] = st->coef[4 * i + 1];
-            st->cur[2] = st->coef[4 * i + 2]; st->cur[3] = st->coef[4 * i + 3];
-            st->cur_sigma = st->sigma[i]; st->cur_row = st->n_steps - 1 - i;
-            st->cur_trace = st->trace_row[i];
-            // DPM-Solver++ loop: the step's six numbers and the ring slots of m_k, m_{k-1}, m_{k-2} (k = the executed step)
-            for (int j = 0; j < 6; ++j) st->cur_dpm[j] = st->dpm[6 * i + j];
-            const int k = st->n_steps - 1 - i;
-            st->cur_slot[0] = k % 3; st->cur_slot[1] = (k + 2) % 3; st->cur_slot[2] = (k + 1) % 3;
-            if (st->xc) {          // UniPC loop: the step's row and the four-slot ring's slots of m_k .. m_{k-3}
-                for (int j = 0; j < 12; ++j) st->cur_uni[j] = st->uni[12 * i + j];
-                for (int j = 0; j < 4; ++j) st->cur_uslot[j] = (k + 4 - j) % 4;
-            }
-        }
+        if (threadIdx.x == 0) st->cur_row = st->n_steps - 1 - i;          // the executed step: all the step's last kernel is told
     }
     const int gtid = blockIdx.x * blockDim.x + threadIdx.x, gthreads = gridDim.x * blockDim.x;
     temb_copy_rows(ts, i, gtid, gthreads);
     const float* x0 = st->x0;
     if (x0) {           // masked: this step's blend.  Coefficients and noise row from the tables through the counter, never from
-                        // cur[] / cur_row, which block 0 of this same kernel writes while the other blocks run
+                        // cur_row, which block 0 of this same kernel writes while the other blocks run
         const float sa = st->q[2 * i], s1m = st->q[2 * i + 1];
         const float* nz = st->q_noise + (int64_t)(st->n_steps - 1 - i) * n;
         const float* mask = st->mask;
@@ -184,37 +150,9 @@ __global__ void temb_select_kernel(const TembSel ts, int step) {
     temb_copy_rows(ts, step, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
-// in-place x <- x_{t-1} (eta == 0), coefficients from the step state; ends the step: the counter moves to the next one
-// The trace row (cur_trace, published by step_setup_kernel) and both trace pointers are read from the state: uniform over the grid
-__global__ void ddim_step_state_kernel(float* __restrict__ x, const float* __restrict__ eps_c, const float* __restrict__ eps_u,
-                                       float cfg_scale, StepState* __restrict__ st, int64_t n,
-                                       const float* __restrict__ kfac, int n_per_sample) {
-    const DdimCoef k = {st->cur[0], st->cur[1], st->cur[2], st->cur[3]};
-    const float* __restrict__ const nz = (st->noise && st->cur_sigma != 0.f) ? st->noise + (int64_t)st->cur_row * n : nullptr;
-    const int row = st->cur_trace;
-    float* __restrict__ const tx = (st->trace_x && row >= 0) ? st->trace_x + (int64_t)row * n : nullptr;
-    float* __restrict__ const tx0 = (st->trace_x0 && row >= 0) ? st->trace_x0 + (int64_t)row * n : nullptr;
-    if (blockIdx.x == 0 && threadIdx.x == 0) st->counter = st->counter - 1;      // (nothing else in this kernel reads it)
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float e = eps_c[i];
-        if (eps_u) {
-            const float u = eps_u[i];
-            if (kfac) e = cfg_rescaled_eps_at(e, u, cfg_scale, kfac, i, n_per_sample);
-            else e = ddim_eps_at(e, u, cfg_scale);
-        }
-        float p0;
-        float xp = ddim_update_at(x[i], e, k, p0);
-        if (nz) xp = ddim_noise_at(xp, st->cur_sigma, nz[i], st->temperature);
-        x[i] = xp;
-        if (tx) tx[i] = xp;
-        if (tx0) tx0[i] = p0;
-    }
-}
-
 // ---- DPM-Solver++ multistep update (Lu et al. 2022, Algorithm 2; data prediction, eps parameterisation) -----------------------
 // One element: m0 = (x - sigma_t e) / alpha_t, x' = c_x x + c_0 m0 + c_1 m1 + c_2 m2.  Explicit fmas (at most eight roundings with the
-// guidance combine): the stand-alone kernel and the step-state kernel give the same bits whatever the compiler contracts.
-__device__ __forceinline__ float dpmpp_eps_at(float ec, float eu, float cfg_scale) { return fmaf(cfg_scale, ec - eu, eu); }
+// guidance combine): every form of the step kernel gives the same bits whatever the compiler contracts.
 __device__ __forceinline__ float dpmpp_update_at(float x, float e, const DpmCoef& k, float m1, float m2, float& m0) {
     m0 = fmaf(-k.sigma, e, x) * k.inv_alpha;
     float r = fmaf(k.c0, m0, k.cx * x);
@@ -222,89 +160,13 @@ __device__ __forceinline__ float dpmpp_update_at(float x, float e, const DpmCoef
     if (k.c2 != 0.f) r = fmaf(k.c2, m2, r);
     return r;
 }
-// The grid-stride body both kernels run.  16-byte accesses when n is a multiple of 4 and every pointer is 16-byte aligned, scalar
-// otherwise (same per-element arithmetic).  m1 / m2 are loaded only where their coefficient is non-zero: the branch is uniform,
-// so an order-1 or order-2 step issues no loads for the unused ring slots.  x_prev may alias x (element i is read before it is written).
-__device__ __forceinline__ void dpmpp_update_range(const float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u,
-                                                   float cfg_scale, const DpmCoef k, const float* __restrict__ m1, const float* __restrict__ m2,
-                                                   float* x_prev, float* __restrict__ m0_out, int64_t n,
-                                                   const float* __restrict__ kfac, int n_per_sample,
-                                                   float* __restrict__ x_copy, float* __restrict__ m0_copy) {
-    // kfac non-null (with eps_u): the guidance-rescaled eps; x_copy / m0_copy non-null: x_prev / m0 once more (a trace row)
-    const bool use1 = k.c1 != 0.f, use2 = k.c2 != 0.f;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
-    uintptr_t al = (uintptr_t)x | (uintptr_t)eps_c | (uintptr_t)eps_u | (uintptr_t)x_prev | (uintptr_t)m0_out | (uintptr_t)x_copy |
-                   (uintptr_t)m0_copy;
-    if (use1) al |= (uintptr_t)m1;
-    if (use2) al |= (uintptr_t)m2;
-    if (!(n & 3) && !(al & 15)) {
-        const int64_t n4 = n >> 2;
-        for (int64_t i = tid; i < n4; i += nth) {
-            const f32x4 xv = ((const f32x4*)x)[i];
-            f32x4 ev = ((const f32x4*)eps_c)[i];
-            if (eps_u) {
-                const f32x4 uv = ((const f32x4*)eps_u)[i];
-                if (kfac) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) ev[j] = cfg_rescaled_eps_at(ev[j], uv[j], cfg_scale, kfac, 4 * i + j, n_per_sample);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) ev[j] = dpmpp_eps_at(ev[j], uv[j], cfg_scale);
-                }
-            }
-            f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f}, mv, rv;
-            if (use1) a = ((const f32x4*)m1)[i];
-            if (use2) b = ((const f32x4*)m2)[i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { float m0; rv[j] = dpmpp_update_at(xv[j], ev[j], k, a[j], b[j], m0); mv[j] = m0; }
-            ((f32x4*)m0_out)[i] = mv;
-            ((f32x4*)x_prev)[i] = rv;
-            if (m0_copy) ((f32x4*)m0_copy)[i] = mv;
-            if (x_copy) ((f32x4*)x_copy)[i] = rv;
-        }
-        return;
-    }
-    for (int64_t i = tid; i < n; i += nth) {
-        float e = eps_c[i];
-        if (eps_u) e = kfac ? cfg_rescaled_eps_at(e, eps_u[i], cfg_scale, kfac, i, n_per_sample) : dpmpp_eps_at(e, eps_u[i], cfg_scale);
-        float m0;
-        const float r = dpmpp_update_at(x[i], e, k, use1 ? m1[i] : 0.f, use2 ? m2[i] : 0.f, m0);
-        m0_out[i] = m0;
-        x_prev[i] = r;
-        if (m0_copy) m0_copy[i] = m0;
-        if (x_copy) x_copy[i] = r;
-    }
-}
-
-__global__ void dpmpp_step_kernel(const float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u, float cfg_scale,
-                                  const DpmCoef k, const float* __restrict__ m1, const float* __restrict__ m2, float* x_prev,
-                                  float* __restrict__ m0_out, int64_t n, const float* __restrict__ kfac, int n_per_sample,
-                                  float* __restrict__ x_copy, float* __restrict__ m0_copy) {
-    dpmpp_update_range(x, eps_c, eps_u, cfg_scale, k, m1, m2, x_prev, m0_out, n, kfac, n_per_sample, x_copy, m0_copy);
-}
-
-// in-place x <- x_{t-1} with the coefficients and ring slots step_setup_kernel published; ends the step: the counter moves on
-__global__ void dpmpp_step_state_kernel(float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u, float cfg_scale,
-                                        StepState* st, int64_t n, const float* __restrict__ kfac, int n_per_sample) {
-    const DpmCoef k = {st->cur_dpm[0], st->cur_dpm[1], st->cur_dpm[2], st->cur_dpm[3], st->cur_dpm[4], st->cur_dpm[5]};
-    const int row = st->cur_trace;          // (published by step_setup_kernel; uniform over the grid, like both trace pointers)
-    float* const tx = (st->trace_x && row >= 0) ? st->trace_x + (int64_t)row * n : nullptr;
-    float* const tx0 = (st->trace_x0 && row >= 0) ? st->trace_x0 + (int64_t)row * n : nullptr;
-    float* const ring = st->ring;
-    float* const m0 = ring + (int64_t)st->cur_slot[0] * n;
-    const float* const m1 = ring + (int64_t)st->cur_slot[1] * n;
-    const float* const m2 = ring + (int64_t)st->cur_slot[2] * n;
-    if (blockIdx.x == 0 && threadIdx.x == 0) st->counter = st->counter - 1;      // (nothing else in this kernel reads it)
-    dpmpp_update_range(x, eps_c, eps_u, cfg_scale, k, m1, m2, x, m0, n, kfac, n_per_sample, tx, tx0);
-}
-
 // ---- UniPC predictor-corrector update (Zhao et al. 2023; data prediction, the linear forms of include/mkd.h mkd_unipc_table) ----
 // One element, with x = x~_k the predicted latent the model was evaluated at and xcp = x^c_{k-1} the previous corrected one:
 //   m0 = (x - sigma_t e) / alpha_t
 //   xc = a_c xcp + q_0 m0 + q_1 m1 + q_2 m2 + q_3 m3      (a_c == 0: no corrector in this step, xc = x)
 //   x' = a_p xc + p_0 m0 + p_1 m1 + p_2 m2
-// Explicit fmas (two roundings of the guidance combine, two of m0, at most five of xc, four of x'): the stand-alone kernel and the
-// step-state kernel give the same bits whatever the compiler contracts.  A history term is added only where its coefficient is non-zero.
+// Explicit fmas (two roundings of the guidance combine, two of m0, at most five of xc, four of x'): every form of the step kernel
+// gives the same bits whatever the compiler contracts.  A history term is added only where its coefficient is non-zero.
 __device__ __forceinline__ float unipc_update_at(float x, float xcp, float e, const UniCoef& k, float m1, float m2, float m3, float& m0,
                                                  float& xc) {
     m0 = fmaf(-k.sigma, e, x) * k.inv_alpha;
@@ -321,99 +183,10 @@ __device__ __forceinline__ float unipc_update_at(float x, float xcp, float e, co
     if (k.p2 != 0.f) r = fmaf(k.p2, m2, r);
     return r;
 }
-// The grid-stride body both kernels run: one pass over x, xcp, eps_c (, eps_u), m1..m3 in and x', xc, m0 out.  16-byte accesses when
-// n is a multiple of 4 and every pointer that is used is 16-byte aligned, scalar otherwise (same per-element arithmetic).  xcp and
-// m1..m3 are loaded only where a coefficient of theirs is non-zero (uniform branches: the first steps and the lower orders issue no
-// loads for unused planes).  x_next may alias x and xc_out may alias xcp (element i is read before it is written).
-__device__ __forceinline__ void unipc_update_range(const float* x, const float* xcp, const float* __restrict__ eps_c,
-                                                   const float* __restrict__ eps_u, float cfg_scale, const UniCoef k,
-                                                   const float* __restrict__ m1, const float* __restrict__ m2, const float* __restrict__ m3,
-                                                   float* x_next, float* xc_out, float* __restrict__ m0_out, int64_t n,
-                                                   const float* __restrict__ kfac, int n_per_sample,
-                                                   float* __restrict__ x_copy, float* __restrict__ m0_copy) {
-    const bool usec = k.ac != 0.f;
-    const bool use1 = (usec && k.q1 != 0.f) || k.p1 != 0.f, use2 = (usec && k.q2 != 0.f) || k.p2 != 0.f, use3 = usec && k.q3 != 0.f;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
-    uintptr_t al = (uintptr_t)x | (uintptr_t)eps_c | (uintptr_t)eps_u | (uintptr_t)x_next | (uintptr_t)xc_out | (uintptr_t)m0_out |
-                   (uintptr_t)x_copy | (uintptr_t)m0_copy;
-    if (usec) al |= (uintptr_t)xcp;
-    if (use1) al |= (uintptr_t)m1;
-    if (use2) al |= (uintptr_t)m2;
-    if (use3) al |= (uintptr_t)m3;
-    if (!(n & 3) && !(al & 15)) {
-        const int64_t n4 = n >> 2;
-        for (int64_t i = tid; i < n4; i += nth) {
-            const f32x4 xv = ((const f32x4*)x)[i];
-            f32x4 ev = ((const f32x4*)eps_c)[i];
-            if (eps_u) {
-                const f32x4 uv = ((const f32x4*)eps_u)[i];
-                if (kfac) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) ev[j] = cfg_rescaled_eps_at(ev[j], uv[j], cfg_scale, kfac, 4 * i + j, n_per_sample);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) ev[j] = dpmpp_eps_at(ev[j], uv[j], cfg_scale);
-                }
-            }
-            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            f32x4 pv = z, a = z, b = z, c = z, mv, cv, rv;
-            if (usec) pv = ((const f32x4*)xcp)[i];
-            if (use1) a = ((const f32x4*)m1)[i];
-            if (use2) b = ((const f32x4*)m2)[i];
-            if (use3) c = ((const f32x4*)m3)[i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { float m0, xc; rv[j] = unipc_update_at(xv[j], pv[j], ev[j], k, a[j], b[j], c[j], m0, xc); mv[j] = m0; cv[j] = xc; }
-            ((f32x4*)m0_out)[i] = mv;
-            ((f32x4*)xc_out)[i] = cv;
-            ((f32x4*)x_next)[i] = rv;
-            if (m0_copy) ((f32x4*)m0_copy)[i] = mv;
-            if (x_copy) ((f32x4*)x_copy)[i] = rv;
-        }
-        return;
-    }
-    for (int64_t i = tid; i < n; i += nth) {
-        float e = eps_c[i];
-        if (eps_u) e = kfac ? cfg_rescaled_eps_at(e, eps_u[i], cfg_scale, kfac, i, n_per_sample) : dpmpp_eps_at(e, eps_u[i], cfg_scale);
-        float m0, xc;
-        const float r = unipc_update_at(x[i], usec ? xcp[i] : 0.f, e, k, use1 ? m1[i] : 0.f, use2 ? m2[i] : 0.f, use3 ? m3[i] : 0.f, m0, xc);
-        m0_out[i] = m0;
-        xc_out[i] = xc;
-        x_next[i] = r;
-        if (m0_copy) m0_copy[i] = m0;
-        if (x_copy) x_copy[i] = r;
-    }
-}
-
-__global__ void unipc_step_kernel(const float* x, const float* xcp, const float* __restrict__ eps_c, const float* __restrict__ eps_u,
-                                  float cfg_scale, const UniCoef k, const float* __restrict__ m1, const float* __restrict__ m2,
-                                  const float* __restrict__ m3, float* x_next, float* xc_out, float* __restrict__ m0_out, int64_t n,
-                                  const float* __restrict__ kfac, int n_per_sample, float* __restrict__ x_copy, float* __restrict__ m0_copy) {
-    unipc_update_range(x, xcp, eps_c, eps_u, cfg_scale, k, m1, m2, m3, x_next, xc_out, m0_out, n, kfac, n_per_sample, x_copy, m0_copy);
-}
-
-// in place (x <- x~_{k+1}, st->xc <- x^c_k) with the row and the four ring slots step_setup_kernel published; ends the step: the counter
-// moves on
-__global__ void unipc_step_state_kernel(float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u, float cfg_scale,
-                                        StepState* st, int64_t n, const float* __restrict__ kfac, int n_per_sample) {
-    const float* const u = st->cur_uni;
-    const UniCoef k = {u[0], u[1], u[2], u[3], u[4], u[5], u[6], u[7], u[8], u[9], u[10]};
-    const int row = st->cur_trace;          // (published by step_setup_kernel; uniform over the grid, like both trace pointers)
-    float* const tx = (st->trace_x && row >= 0) ? st->trace_x + (int64_t)row * n : nullptr;
-    float* const tx0 = (st->trace_x0 && row >= 0) ? st->trace_x0 + (int64_t)row * n : nullptr;
-    float* const ring = st->ring;
-    float* const xc = st->xc;
-    float* const m0 = ring + (int64_t)st->cur_uslot[0] * n;
-    const float* const m1 = ring + (int64_t)st->cur_uslot[1] * n;
-    const float* const m2 = ring + (int64_t)st->cur_uslot[2] * n;
-    const float* const m3 = ring + (int64_t)st->cur_uslot[3] * n;
-    if (blockIdx.x == 0 && threadIdx.x == 0) st->counter = st->counter - 1;      // (nothing else in this kernel reads it)
-    unipc_update_range(x, xc, eps_c, eps_u, cfg_scale, k, m1, m2, m3, x, xc, m0, n, kfac, n_per_sample, tx, tx0);
-}
-
 // ---- per-sample loop (mkd_sample_rows): every sample of the batch has its own schedule, guidance scale and sigmas -------------------
 // Grid (x, sample): what a workgroup needs of its sample (one StepRow) has a workgroup-uniform address, so it is read once into
-// scalars, and no element is divided by the sample size.  The element updates are ddim_update_at / dpmpp_update_range above: row b
-// has the bits of the uniform kernels run with sample b's numbers.
+// scalars, and no element is divided by the sample size.  The updates are the per-sample forms of the step kernels below: row b has the bits of
+// the uniform forms run with sample b's numbers.
 //
 // First kernel of a per-sample step.  Block (0, b) writes t_out[b]; every block copies its share of row b's time-embedding rows (row
 // temb_row of sample b % samples: with guidance both halves of the doubled batch take their sample's row).  The executed step k goes
@@ -439,87 +212,150 @@ __global__ void step_setup_rows_kernel(StepState* st, int64_t* t_out, int sample
     }
 }
 
-// One sample's DDIM update over its `per` elements (pointers already at the sample).  16-byte accesses when per is a multiple of 4
-// and every pointer is 16-byte aligned, scalar otherwise: the same arithmetic per element.  x_prev may alias x.
-__device__ __forceinline__ void ddim_update_range(const float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u,
-                                                  float scale, const DdimCoef k, float sigma, const float* __restrict__ nz, float temperature,
-                                                  float* x_prev, float* __restrict__ pred_x0, int per) {
-    const int tid = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
-    const uintptr_t al = (uintptr_t)x | (uintptr_t)eps_c | (uintptr_t)eps_u | (uintptr_t)nz | (uintptr_t)x_prev | (uintptr_t)pred_x0;
-    if (!(per & 3) && !(al & 15)) {
-        for (int i = tid; i < (per >> 2); i += nth) {
-            const f32x4 xv = ((const f32x4*)x)[i];
-            f32x4 ev = ((const f32x4*)eps_c)[i], pv, rv;
-            if (eps_u) {
-                const f32x4 uv = ((const f32x4*)eps_u)[i];
+// ---- the step kernels: one walker, one kernel per solver, every form of StepOps (mkd_common.h) ------------------------------------
+// What a block walks over once its launch's record is resolved: the common operands at this block's elements (the whole latent, or
+// one sample's slice), and where the launch stands: executed step k / table entry e of the st forms, the sample's row and offset
+// of the per-sample forms (row null, off 0 otherwise)
+struct StepRange {
+    const float* x; const float* eps_c; const float* eps_u; float scale; const float* kfac; int per; int64_t n;
+    float* x_out; float* p_out; float* x_copy; float* p_copy;
+    int k, e; const StepRow* row; int64_t off;
+};
+// A solver is an element functor F: its numbers k, up to four extra input planes `in` (null: not read), with F::XC an extra output
+// plane xc_out, and
+//   float at(x, e, h, p0, xc)      the new latent of one element from x, the guided eps e and the planes' values h[] (0 where not
+//                                  read); p0 = its x0-prediction, xc = the corrected latent (F::XC only)
+// The walker owns everything else: the grid stride over r.n elements, the guided eps, the loads of the planes that are read and the
+// stores of x_out / p_out (/ xc_out), the first two once more where a copy is asked for.  W = 4: 16-byte accesses, W = 1: scalar, the
+// same arithmetic per element.  Every load of element i comes before its stores, so x_out may be x and xc_out may be in[0]: no
+// __restrict__ on those.  A plane is read only where its pointer is non-null: the branch is uniform, so a first step or a lower order
+// issues no loads for history it does not use.
+template <int W, class F>
+__device__ __forceinline__ void step_walk_as(const StepRange& r, const F& f) {
+    typedef float vec __attribute__((ext_vector_type(W)));
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = tid; i < r.n / W; i += nth) {
+        const vec xv = ((const vec*)r.x)[i];
+        vec ev = ((const vec*)r.eps_c)[i], hv[F::PLANES], rv, pv, cv;
+        if (r.eps_u) {
+            const vec uv = ((const vec*)r.eps_u)[i];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) ev[j] = ddim_eps_at(ev[j], uv[j], scale);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { float p0; rv[j] = ddim_update_at(xv[j], ev[j], k, p0); pv[j] = p0; }
-            if (nz) {
-                const f32x4 zv = ((const f32x4*)nz)[i];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) rv[j] = ddim_noise_at(rv[j], sigma, zv[j], temperature);
-            }
-            ((f32x4*)x_prev)[i] = rv;
-            if (pred_x0) ((f32x4*)pred_x0)[i] = pv;
+            for (int j = 0; j < W; ++j) ev[j] = guided_eps_at(ev[j], uv[j], r.scale, r.kfac, W * i + j, r.per);
         }
-        return;
-    }
-    for (int i = tid; i < per; i += nth) {
-        float e = eps_c[i];
-        if (eps_u) e = ddim_eps_at(e, eps_u[i], scale);
-        float p0;
-        float xp = ddim_update_at(x[i], e, k, p0);
-        if (nz) xp = ddim_noise_at(xp, sigma, nz[i], temperature);
-        x_prev[i] = xp;
-        if (pred_x0) pred_x0[i] = p0;
+#pragma unroll
+        for (int p = 0; p < F::PLANES; ++p) hv[p] = f.in[p] ? ((const vec*)f.in[p])[i] : (vec)0.f;
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            float h[F::PLANES], p0, xc = 0.f;
+#pragma unroll
+            for (int p = 0; p < F::PLANES; ++p) h[p] = hv[p][j];
+            rv[j] = f.at(xv[j], ev[j], h, p0, xc);
+            pv[j] = p0; cv[j] = xc;
+        }
+        if (r.p_out) ((vec*)r.p_out)[i] = pv;
+        if constexpr (F::XC) ((vec*)f.xc_out)[i] = cv;
+        ((vec*)r.x_out)[i] = rv;
+        if (r.p_copy) ((vec*)r.p_copy)[i] = pv;
+        if (r.x_copy) ((vec*)r.x_copy)[i] = rv;
     }
 }
-
-// st non-null: the step's last kernel, in place (x_prev == x), entries / noise row of the executed step st->cur_row; st null: the
-// stand-alone form on `rows` [gridDim.y].  A finished sample's blocks return before any load or store of its rows.
-__global__ void ddim_step_rows_kernel(const float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u,
-                                      const StepRow* __restrict__ rows, StepState* st, const float* __restrict__ noise, float temperature,
-                                      float* x_prev, float* __restrict__ pred_x0, int per) {
-    const int b = blockIdx.y, nb = gridDim.y;
-    if (st) {
-        const int k = st->cur_row;
-        rows = st->rows + (int64_t)k * nb;
-        noise = st->noise ? st->noise + (int64_t)k * nb * per : nullptr;
-        temperature = st->temperature;
-        if (blockIdx.x == 0 && b == 0 && threadIdx.x == 0) st->counter = st->counter - 1;      // (nothing else in this kernel reads it)
-    }
-    const StepRow r = rows[b];
-    if (!r.active) return;
-    const int64_t off = (int64_t)b * per;
-    const DdimCoef k = {r.coef[0], r.coef[1], r.coef[2], r.coef[3]};
-    ddim_update_range(x + off, eps_c + off, eps_u ? eps_u + off : nullptr, r.scale, k, r.sigma,
-                      (noise && r.sigma != 0.f) ? noise + off : nullptr, temperature, x_prev + off, pred_x0 ? pred_x0 + off : nullptr, per);
+// 16-byte form when n is a multiple of 4 and every pointer that is used is 16-byte aligned (null ones count as aligned), else scalar
+template <class F>
+__device__ __forceinline__ void step_walk(const StepRange& r, const F& f) {
+    uintptr_t al = (uintptr_t)r.x | (uintptr_t)r.eps_c | (uintptr_t)r.eps_u | (uintptr_t)r.x_out | (uintptr_t)r.p_out | (uintptr_t)r.x_copy |
+                   (uintptr_t)r.p_copy;
+#pragma unroll
+    for (int p = 0; p < F::PLANES; ++p) al |= (uintptr_t)f.in[p];
+    if constexpr (F::XC) al |= (uintptr_t)f.xc_out;
+    if (!(r.n & 3) && !(al & 15)) step_walk_as<4>(r, f);
+    else step_walk_as<1>(r, f);
 }
 
-// ... and the DPM-Solver++ update: dpmpp_update_range over the sample's elements.  st non-null: in place, ring slots of the executed
-// step (m_k into slot k mod 3); st null: m1 / m2 / m0_out / x_prev as given
-__global__ void dpmpp_step_rows_kernel(const float* x, const float* __restrict__ eps_c, const float* __restrict__ eps_u,
-                                       const StepRow* __restrict__ rows, StepState* st, const float* m1, const float* m2,
-                                       float* x_prev, float* m0_out, int per) {
-    const int b = blockIdx.y, nb = gridDim.y;
-    if (st) {
-        const int k = st->cur_row;
-        const int64_t n = (int64_t)nb * per;
-        rows = st->rows + (int64_t)k * nb;
-        m0_out = st->ring + (int64_t)(k % 3) * n;
-        m1 = st->ring + (int64_t)((k + 2) % 3) * n;
-        m2 = st->ring + (int64_t)((k + 1) % 3) * n;
-        if (blockIdx.x == 0 && b == 0 && threadIdx.x == 0) st->counter = st->counter - 1;      // (nothing else in this kernel reads it)
+// What all solvers resolve alike.  st forms: the executed step, the trace rows (uniform launches) and the counter, which this last
+// kernel of the step moves and nothing in it reads.  Per-sample forms: this block's StepRow and its sample's slice of the operands.
+// false: a finished sample, whose blocks return before any access to its rows.
+__device__ __forceinline__ bool step_resolve(const StepOps& o, StepRange& r) {
+    StepState* const st = o.st;
+    const int k = st ? st->cur_row : 0, e = st ? st->n_steps - 1 - k : 0;
+    const bool traced = st && !o.samples && st->trace_row[e] >= 0;
+    const int64_t trace_at = traced ? st->trace_row[e] * o.n : 0;
+    if (st && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) st->counter = st->counter - 1;
+    const StepRow* const row = o.samples ? (st ? st->rows + (int64_t)k * o.samples : o.rows) + blockIdx.y : nullptr;
+    if (row && !row->active) return false;
+    const int64_t off = row ? (int64_t)blockIdx.y * o.per : 0;
+    r.x = o.x + off; r.eps_c = o.eps_c + off; r.eps_u = o.eps_u ? o.eps_u + off : nullptr;
+    r.scale = row ? row->scale : o.scale; r.kfac = o.kfac; r.per = o.per; r.n = row ? o.per : o.n;
+    r.x_out = o.x_out + off; r.p_out = o.p_out ? o.p_out + off : nullptr;
+    r.x_copy = st ? (traced && st->trace_x ? st->trace_x + trace_at : nullptr) : o.x_copy;
+    r.p_copy = st ? (traced && st->trace_x0 ? st->trace_x0 + trace_at : nullptr) : o.p_copy;
+    r.k = k; r.e = e; r.row = row; r.off = off;
+    return true;
+}
+
+// DDIM.  Plane 0: the noise draw of the eta term.  The st forms take the executed step's row of st->noise; a table entry or a sample's
+// row with sigma == 0 reads none
+struct DdimStep {
+    static constexpr int PLANES = 1; static constexpr bool XC = false;
+    DdimCoef k; float sigma, temperature; const float* in[PLANES];
+    __device__ __forceinline__ float at(float x, float e, const float* h, float& p0, float&) const {
+        const float xp = ddim_update_at(x, e, k, p0);
+        return in[0] ? ddim_noise_at(xp, sigma, h[0], temperature) : xp;
     }
-    const StepRow r = rows[b];
-    if (!r.active) return;
-    const int64_t off = (int64_t)b * per;
-    const DpmCoef k = {r.dpm[0], r.dpm[1], r.dpm[2], r.dpm[3], r.dpm[4], r.dpm[5]};
-    dpmpp_update_range(x + off, eps_c + off, eps_u ? eps_u + off : nullptr, r.scale, k, m1 ? m1 + off : nullptr, m2 ? m2 + off : nullptr,
-                       x_prev + off, m0_out + off, per, nullptr, 0, nullptr, nullptr);
+};
+__global__ void ddim_step_kernel(const StepOps o) {
+    StepRange r;
+    if (!step_resolve(o, r)) return;
+    const StepState* const st = o.st;
+    DdimStep f;
+    f.k = r.row ? DdimCoef::from(r.row->coef) : st ? DdimCoef::from(st->coef + 4 * r.e) : DdimCoef::from(o.coef);
+    f.sigma = r.row ? r.row->sigma : st ? st->sigma[r.e] : o.sigma;
+    f.temperature = st ? st->temperature : o.temperature;
+    const float* const nz = st ? (st->noise ? st->noise + r.k * o.n : nullptr) : o.noise;
+    f.in[0] = (nz && !((r.row || st) && f.sigma == 0.f)) ? nz + r.off : nullptr;
+    step_walk(r, f);
+}
+
+// DPM-Solver++.  Planes m_{k-1}, m_{k-2}; the st forms keep them and m_k = p_out in the three-plane ring
+struct DpmStep {
+    static constexpr int PLANES = 2; static constexpr bool XC = false;
+    DpmCoef k; const float* in[PLANES];
+    __device__ __forceinline__ float at(float x, float e, const float* h, float& p0, float&) const { return dpmpp_update_at(x, e, k, h[0], h[1], p0); }
+};
+__global__ void dpmpp_step_kernel(const StepOps o) {
+    StepRange r;
+    if (!step_resolve(o, r)) return;
+    const StepState* const st = o.st;
+    DpmStep f;
+    f.k = r.row ? DpmCoef::from(r.row->dpm) : st ? DpmCoef::from(st->dpm + 6 * r.e) : DpmCoef::from(o.coef);
+    if (st) r.p_out = st->ring + ring_slot(r.k, 0, 3) * o.n + r.off;
+    f.in[0] = f.k.c1 != 0.f ? (st ? st->ring + ring_slot(r.k, 1, 3) * o.n : o.hist[0]) + r.off : nullptr;
+    f.in[1] = f.k.c2 != 0.f ? (st ? st->ring + ring_slot(r.k, 2, 3) * o.n : o.hist[1]) + r.off : nullptr;
+    step_walk(r, f);
+}
+
+// UniPC.  Planes x^c_{k-1}, m_{k-1}, m_{k-2}, m_{k-3}, each read only where a coefficient of its own is non-zero; the st form keeps the
+// m's in the four-plane ring and x^c in place in st->xc.  No per-sample form
+struct UniStep {
+    static constexpr int PLANES = 4; static constexpr bool XC = true;
+    UniCoef k; const float* in[PLANES]; float* xc_out;
+    __device__ __forceinline__ float at(float x, float e, const float* h, float& p0, float& xc) const {
+        return unipc_update_at(x, h[0], e, k, h[1], h[2], h[3], p0, xc);
+    }
+};
+__global__ void unipc_step_kernel(const StepOps o) {
+    StepRange r;
+    if (!step_resolve(o, r)) return;
+    const StepState* const st = o.st;
+    UniStep f;
+    f.k = st ? UniCoef::from(st->uni + 12 * r.e) : UniCoef::from(o.coef);
+    if (st) r.p_out = st->ring + ring_slot(r.k, 0, 4) * o.n;
+    f.xc_out = st ? st->xc : o.xc_out;
+    const bool cor = f.k.ac != 0.f;
+    f.in[0] = cor ? (st ? st->xc : o.xc_prev) : nullptr;
+    f.in[1] = ((cor && f.k.q1 != 0.f) || f.k.p1 != 0.f) ? (st ? st->ring + ring_slot(r.k, 1, 4) * o.n : o.hist[0]) : nullptr;
+    f.in[2] = ((cor && f.k.q2 != 0.f) || f.k.p2 != 0.f) ? (st ? st->ring + ring_slot(r.k, 2, 4) * o.n : o.hist[1]) : nullptr;
+    f.in[3] = (cor && f.k.q3 != 0.f) ? (st ? st->ring + ring_slot(r.k, 3, 4) * o.n : o.hist[2]) : nullptr;
+    step_walk(r, f);
 }
 
 // ---- GEGLU: y = a * gelu_erf(gate) ----------------------------------------------------------------
@@ -900,28 +736,6 @@ inline int grid_for(int64_t total, int block = 256, int cap = 2048) {
 
 }  // namespace
 
-static int check_kfac(const float* kfac, const float* eps_u, int n_per_sample, int64_t n, const char* who) {
-    if (kfac && (!eps_u || n_per_sample <= 0 || n % n_per_sample))
-        return mkd_fail(-1, std::string(who) + ": a rescale factor needs eps_u and n_per_sample > 0 dividing n");
-    return 0;
-}
-
-int launch_ddim_step(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, float a_t,
-                     float a_prev, float sigma_t, float s1m, const float* noise, float temperature,
-                     float* x_prev, float* pred_x0, int64_t n, hipStream_t stream,
-                     const float* kfac, int n_per_sample, float* x_copy) {
-    if (n <= 0) return mkd_fail(-1, "ddim_step: empty");
-    if (int rc = check_kfac(kfac, eps_u, n_per_sample, n, "ddim_step")) return rc;
-    const float sqrt_at_inv = 1.0f / sqrtf(a_t);
-    const float sqrt_aprev = sqrtf(a_prev);
-    const float dir_coef = sqrtf(1.0f - a_prev - sigma_t * sigma_t);
-    hipLaunchKernelGGL(ddim_step_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale,
-                       sqrt_at_inv, sqrt_aprev, dir_coef, sigma_t, s1m, noise, temperature, x_prev, pred_x0, n,
-                       kfac, n_per_sample, x_copy);
-    MKD_LAUNCH_CHECK("ddim_step_kernel");
-    return 0;
-}
-
 int launch_geglu(const bf16_t* x, bf16_t* y, int rows, int inner, hipStream_t stream) {
     if (inner % 8) return mkd_fail(-1, "geglu: inner must be a multiple of 8");
     hipLaunchKernelGGL(geglu_kernel, dim3(grid_for((int64_t)rows * (inner / 8), 256, 4096)), dim3(256), 0, stream, x, y, rows, inner);
@@ -1078,56 +892,6 @@ int launch_cfg_rescale_factor(const float* eps_c, const float* eps_u, float cfg_
     return 0;
 }
 
-int launch_ddim_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
-                           hipStream_t stream, const float* kfac, int n_per_sample) {
-    if (int rc = check_kfac(kfac, eps_u, n_per_sample, n, "ddim_step_state")) return rc;
-    hipLaunchKernelGGL(ddim_step_state_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale, st, n, kfac, n_per_sample);
-    MKD_LAUNCH_CHECK("ddim_step_state_kernel");
-    return 0;
-}
-
-int launch_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, const DpmCoef& k, const float* m1,
-                      const float* m2, float* x_prev, float* m0_out, int64_t n, hipStream_t stream,
-                      const float* kfac, int n_per_sample, float* x_copy, float* m0_copy) {
-    if (!x || !eps_c || !x_prev || !m0_out || n <= 0) return mkd_fail(-1, "dpmpp_step: bad arguments");
-    if (int rc = check_kfac(kfac, eps_u, n_per_sample, n, "dpmpp_step")) return rc;
-    if ((k.c1 != 0.f && !m1) || (k.c2 != 0.f && !m2)) return mkd_fail(-1, "dpmpp_step: a non-zero history coefficient needs its x0-prediction");
-    hipLaunchKernelGGL(dpmpp_step_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale, k, m1, m2, x_prev, m0_out, n,
-                       kfac, n_per_sample, x_copy, m0_copy);
-    MKD_LAUNCH_CHECK("dpmpp_step_kernel");
-    return 0;
-}
-
-int launch_dpmpp_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
-                            hipStream_t stream, const float* kfac, int n_per_sample) {
-    if (int rc = check_kfac(kfac, eps_u, n_per_sample, n, "dpmpp_step_state")) return rc;
-    hipLaunchKernelGGL(dpmpp_step_state_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale, st, n, kfac, n_per_sample);
-    MKD_LAUNCH_CHECK("dpmpp_step_state_kernel");
-    return 0;
-}
-
-int launch_unipc_step(const float* x, const float* xc_prev, const float* eps_c, const float* eps_u, float cfg_scale, const UniCoef& k,
-                      const float* m1, const float* m2, const float* m3, float* x_next, float* xc_out, float* m0_out, int64_t n,
-                      hipStream_t stream, const float* kfac, int n_per_sample, float* x_copy, float* m0_copy) {
-    if (!x || !eps_c || !x_next || !xc_out || !m0_out || n <= 0) return mkd_fail(-1, "unipc_step: bad arguments");
-    if (int rc = check_kfac(kfac, eps_u, n_per_sample, n, "unipc_step")) return rc;
-    const bool c = k.ac != 0.f;
-    if ((c && !xc_prev) || (((c && k.q1 != 0.f) || k.p1 != 0.f) && !m1) || (((c && k.q2 != 0.f) || k.p2 != 0.f) && !m2) || (c && k.q3 != 0.f && !m3))
-        return mkd_fail(-1, "unipc_step: a non-zero coefficient needs its corrected latent / x0-prediction");
-    hipLaunchKernelGGL(unipc_step_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, xc_prev, eps_c, eps_u, cfg_scale, k, m1, m2, m3, x_next,
-                       xc_out, m0_out, n, kfac, n_per_sample, x_copy, m0_copy);
-    MKD_LAUNCH_CHECK("unipc_step_kernel");
-    return 0;
-}
-
-int launch_unipc_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
-                            hipStream_t stream, const float* kfac, int n_per_sample) {
-    if (int rc = check_kfac(kfac, eps_u, n_per_sample, n, "unipc_step_state")) return rc;
-    hipLaunchKernelGGL(unipc_step_state_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, eps_c, eps_u, cfg_scale, st, n, kfac, n_per_sample);
-    MKD_LAUNCH_CHECK("unipc_step_state_kernel");
-    return 0;
-}
-
 // blocks along x for one sample of `per` elements: ~4 elements per thread (one 16-byte access), at most 64 per sample
 static int rows_blocks(int per) {
     const int b = (per + 1023) / 1024;
@@ -1146,23 +910,44 @@ int launch_step_setup_rows(StepState* st, int64_t* t_out, int batch, int samples
     MKD_LAUNCH_CHECK("step_setup_rows_kernel");
     return 0;
 }
-int launch_ddim_step_rows(const float* x, const float* eps_c, const float* eps_u, const StepRow* rows, StepState* st, const float* noise,
-                          float temperature, float* x_prev, float* pred_x0, int samples, int n_per_sample, hipStream_t stream) {
-    if (!x || !eps_c || !x_prev || (!rows && !st) || (st && x_prev != x) || samples <= 0 || samples > 65535 || n_per_sample <= 0)
-        return mkd_fail(-1, "ddim_step_rows: bad arguments");
-    hipLaunchKernelGGL(ddim_step_rows_kernel, dim3(rows_blocks(n_per_sample), samples), dim3(256), 0, stream, x, eps_c, eps_u, rows, st, noise,
-                       temperature, x_prev, pred_x0, n_per_sample);
-    MKD_LAUNCH_CHECK("ddim_step_rows_kernel");
+
+int check_rescale_args(const float* k, const float* eps_u, int64_t n, int n_per_sample, const char* who) {
+    if (k && (!eps_u || n_per_sample <= 0 || n % n_per_sample))
+        return mkd_fail(-1, std::string(who) + ": k needs eps_u and an n_per_sample > 0 that divides n");
     return 0;
 }
-int launch_dpmpp_step_rows(const float* x, const float* eps_c, const float* eps_u, const StepRow* rows, StepState* st, const float* m1,
-                           const float* m2, float* x_prev, float* m0_out, int samples, int n_per_sample, hipStream_t stream) {
-    if (!x || !eps_c || !x_prev || (!rows && !st) || (!st && (!m1 || !m2 || !m0_out)) || (st && x_prev != x) || samples <= 0 || samples > 65535 || n_per_sample <= 0)
-        return mkd_fail(-1, "dpmpp_step_rows: bad arguments");
-    hipLaunchKernelGGL(dpmpp_step_rows_kernel, dim3(rows_blocks(n_per_sample), samples), dim3(256), 0, stream, x, eps_c, eps_u, rows, st, m1, m2,
-                       x_prev, m0_out, n_per_sample);
-    MKD_LAUNCH_CHECK("dpmpp_step_rows_kernel");
+// What the three step launchers share: the checks of the record's form and the launch.  missing: the record form (st null) lacks an
+// operand that the solver's numbers need
+template <class Kernel>
+static int launch_step(Kernel kernel, const char* who, const StepOps& o, bool missing, hipStream_t stream) {
+    const std::string w(who);
+    if (!o.x || !o.eps_c || !o.x_out || o.n <= 0 || (o.st ? (o.x_out != o.x || o.rows) : missing)) return mkd_fail(-1, w + ": bad arguments");
+    if (o.samples && (o.samples < 0 || o.samples > 65535 || o.per <= 0 || o.n != (int64_t)o.samples * o.per || o.kfac || (!o.st && !o.rows)))
+        return mkd_fail(-1, w + ": bad arguments");
+    if (int rc = check_rescale_args(o.kfac, o.eps_u, o.n, o.per, who)) return rc;
+    const dim3 grid = o.samples ? dim3(rows_blocks(o.per), o.samples) : dim3(grid_for(o.n));
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, o);
+    MKD_LAUNCH_CHECK(w + "_kernel");
     return 0;
+}
+int launch_ddim_step(const StepOps& o, hipStream_t stream) {
+    if (o.n <= 0) return mkd_fail(-1, "ddim_step: empty");
+    return launch_step(ddim_step_kernel, "ddim_step", o, false, stream);
+}
+int launch_dpmpp_step(const StepOps& o, hipStream_t stream) {
+    const DpmCoef k = DpmCoef::from(o.coef);
+    if (!o.st && !o.samples && ((k.c1 != 0.f && !o.hist[0]) || (k.c2 != 0.f && !o.hist[1])))
+        return mkd_fail(-1, "dpmpp_step: a non-zero history coefficient needs its x0-prediction");
+    return launch_step(dpmpp_step_kernel, "dpmpp_step", o, !o.p_out || (o.samples && (!o.hist[0] || !o.hist[1])), stream);
+}
+int launch_unipc_step(const StepOps& o, hipStream_t stream) {
+    const UniCoef k = UniCoef::from(o.coef);
+    const bool c = k.ac != 0.f;
+    if (o.samples) return mkd_fail(-1, "unipc_step: no per-sample form");
+    if (!o.st && ((c && !o.xc_prev) ||(((c && k.q1 != 0.f) || k.p1 != 0.f) && !o.hist[0]) ||
+                  (((c && k.q2 != 0.f) || k.p2 != 0.f) && !o.hist[1]) || (c && k.q3 != 0.f && !o.hist[2])))
+        return mkd_fail(-1, "unipc_step: a non-zero coefficient needs its corrected latent / x0-prediction");
+    return launch_step(unipc_step_kernel, "unipc_step", o, !o.p_out || !o.xc_out, stream);
 }
 
 int launch_softmax_rows(const float* x, bf16_t* y, int rows, int cols, hipStream_t stream) {

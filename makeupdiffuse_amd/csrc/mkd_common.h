@@ -172,14 +172,15 @@ struct StepRow {
 };
 struct StepState {
     int counter;
-    float cur[4];                          // sqrt(1/a_t), sqrt(a_prev), sqrt(1-a_prev), sqrt(1-a_t) of the current step
     int64_t timesteps[MKD_MAX_STEPS];
-    float coef[4 * MKD_MAX_STEPS];
+    float coef[4 * MKD_MAX_STEPS];         // DdimCoef of table entry i: sqrt(1/a_t), sqrt(a_prev), sqrt(1-a_prev-sigma^2), sqrt(1-a_t)
     // eta > 0 (cddim.py:74-78): x_prev += sigma_t * noise * temperature.  noise: [n_steps][n] fp32 on the device, row k = the draw of the
-    // k-th EXECUTED step (index n_steps - 1 - k); null: deterministic loop.  cur_sigma / cur_row: this step's, set by step_setup_kernel
+    // k-th EXECUTED step (index n_steps - 1 - k); null: deterministic loop
     float sigma[MKD_MAX_STEPS];
     const float* noise; float temperature; int n_steps;
-    float cur_sigma; int cur_row;
+    // The executed step k = n_steps - 1 - counter, published by the step's first kernel.  It is all the step's last kernel is told: that
+    // kernel moves the counter (so it cannot read it) and looks table entry n_steps - 1 - k, the ring slots and the trace row up from k.
+    int cur_row;
     // masked sampling (UPSTREAM DDIMSampler.ddim_sampling mask / x0): step_setup_kernel first blends the latent with q_sample(x0),
     // x <- (q[2i] x0 + q[2i+1] q_noise[row]) mask + (1 - mask) x, row = the executed step (n_steps - 1 - i).  x0 null: unmasked.
     // mask [mB, mC, h, w] is read at b * mask_bstride + c * mask_cstride + p (stride 0 broadcasts); q_hw = h * w, q_chw = C * h * w
@@ -188,22 +189,16 @@ struct StepState {
     float q[2 * MKD_MAX_STEPS];            // sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod of table entry i
     // DPM-Solver++ multistep loop (mkd_sample_dpmpp): x <- c_x x + c_0 m_k + c_1 m_{k-1} + c_2 m_{k-2}, m_k = (x - sigma_t e) / alpha_t the
     // x0-prediction of executed step k.  dpm[6 i ..] = 1/alpha_t, sigma_t, c_x, c_0, c_1, c_2 of table entry i (mkd_dpmpp_table);
-    // ring [3][n] fp32 holds m_k in slot k mod 3.  cur_dpm / cur_slot (slots of m_k, m_{k-1}, m_{k-2}): this step's, set by
-    // step_setup_kernel like cur[].  ring null: a DDIM loop
+    // ring [3][n] fp32 holds m_k in slot ring_slot(k, 0, 3).  ring null: a DDIM loop
     float dpm[6 * MKD_MAX_STEPS];
     float* ring;
-    float cur_dpm[6]; int cur_slot[3];
     // UniPC predictor-corrector loop (mkd_sample_unipc): uni[12 i ..] = the row of table entry i (mkd_unipc_table); it shares `ring`,
-    // here [4][n] with m_k in slot k mod 4, and carries the corrected latent x^c in xc [n].  cur_uni / cur_uslot (slots of m_k ..
-    // m_{k-3}): this step's, set by step_setup_kernel.  xc null: not a UniPC loop
+    // here [4][n] with m_k in slot ring_slot(k, 0, 4), and carries the corrected latent x^c in xc [n].  xc null: not a UniPC loop
     float uni[12 * MKD_MAX_STEPS];
     float* xc;
-    float cur_uni[12]; int cur_uslot[4];
     // intermediates trace (mkd_sample_extras): entry i is logged into row trace_row[i] (-1: not logged) of trace_x (the latent after the
-    // step) and trace_x0 (the step's x0-prediction), each [rows][n] fp32 and each null when not asked for.  cur_trace: this step's row,
-    // published by step_setup_kernel next to cur_row (the step's last kernel moves the counter, so it cannot look the row up itself)
+    // step) and trace_x0 (the step's x0-prediction), each [rows][n] fp32 and each null when not asked for
     float* trace_x; float* trace_x0;
-    int cur_trace;
     short trace_row[MKD_MAX_STEPS];
     // guidance rescale (mkd_sample_extras.guidance_rescale): the phi cfg_rescale_factor_kernel reads inside a replayed step, so a new
     // phi needs no new capture
@@ -213,10 +208,50 @@ struct StepState {
     // instead of the tables above.  null: the uniform loop
     const StepRow* rows; int rows_batch;
 };
-// the six schedule-only numbers of one DPM-Solver++ step
-struct DpmCoef { float inv_alpha, sigma, cx, c0, c1, c2; };
-// the eleven schedule-only numbers of one UniPC step (the first eleven of a mkd_unipc_table row; ac == 0: the step has no corrector)
-struct UniCoef { float inv_alpha, sigma, ac, q0, q1, q2, q3, ap, p0, p1, p2; };
+// The schedule-only numbers of one step, per solver, each built from its table row in ONE place.
+// DDIM: sqrt(1/a_t), sqrt(a_prev), sqrt(1-a_prev-sigma^2), sqrt(1-a_t) (of_alphas: the expressions every table of them is filled with)
+struct DdimCoef {
+    float sqrt_at_inv, sqrt_aprev, dir_coef, s1m;
+    __host__ __device__ static DdimCoef from(const float* c) { return {c[0], c[1], c[2], c[3]}; }
+    static void of_alphas(float a_t, float a_prev, float sigma_t, float s1m, float* c) {
+        c[0] = 1.0f / sqrtf(a_t); c[1] = sqrtf(a_prev); c[2] = sqrtf(1.0f - a_prev - sigma_t * sigma_t); c[3] = s1m;
+    }
+};
+// DPM-Solver++: the six numbers of a mkd_dpmpp_table row
+struct DpmCoef {
+    float inv_alpha, sigma, cx, c0, c1, c2;
+    __host__ __device__ static DpmCoef from(const float* c) { return {c[0], c[1], c[2], c[3], c[4], c[5]}; }
+};
+// UniPC: the first eleven of a mkd_unipc_table row (ac == 0: the step has no corrector)
+struct UniCoef {
+    float inv_alpha, sigma, ac, q0, q1, q2, q3, ap, p0, p1, p2;
+    __host__ __device__ static UniCoef from(const float* c) { return {c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], c[10]}; }
+};
+// Ring slot of m_{k-j}, the x0-prediction of j executed steps before step k, in a ring of `depth` planes (m_k goes to slot k mod depth)
+__host__ __device__ inline int ring_slot(int k, int j, int depth) { return (k + depth - j) % depth; }
+
+// One step launch of any solver, passed to the kernel by value.  It says where the launch's numbers come from:
+//   st null, samples 0   the record itself: coef and the pointers below (the exported stand-alone entries, the eager loop)
+//   st non-null          the device step state at the executed step st->cur_row: table entry, noise row, ring slots, trace rows; in
+//                        place (x_out == x); the step's LAST kernel, which moves the counter
+//   samples > 0          one grid row per sample over its `per` elements, numbers and scale from the sample's StepRow (st->rows at the
+//                        executed step, or `rows`); a finished sample's blocks return before any access
+// x_prev / x_next = x_out may be x and xc_out may be xc_prev: element i is read before it is written.
+struct StepOps {
+    const float* x; const float* eps_c; const float* eps_u; float scale;      // e = eps_u + scale (eps_c - eps_u); eps_u null: eps_c
+    const float* kfac;                     // non-null (needs eps_u): e is multiplied by kfac[i / per], the guidance-rescale factors
+    int per, samples;                      // elements of one sample (kfac, rows); samples > 0: the per-sample grid
+    int64_t n;                             // elements of the whole latent
+    StepState* st; const StepRow* rows;
+    float* x_out; float* p_out;            // the new latent; the x0-prediction (DDIM: or null; the solvers with a ring: m0_out)
+    float* x_copy; float* p_copy;          // non-null: stored there once more (a trace row)
+    float coef[12];                        // the solver's numbers: DdimCoef / DpmCoef / UniCoef::from
+    float sigma, temperature; const float* noise;          // DDIM eta term: x_out += sigma noise temperature (noise null: none)
+    const float* hist[3];                  // m_{k-1}, m_{k-2}, m_{k-3}: read only where a coefficient of theirs is non-zero
+    const float* xc_prev; float* xc_out;   // UniPC: the corrected latent in (read only where a_c != 0) and out
+};
+// The rescale arguments of a step entry (who: the name its message starts with)
+int check_rescale_args(const float* k, const float* eps_u, int64_t n, int n_per_sample, const char* who);
 
 // Time embedding of a sampling call: row `step` of tab[k] ([steps, n[k]] fp32, one table per net) is copied into every one of
 // the `batch` rows of proj[k] ([batch, n[k]]: what the ResBlock epilogues read as their per-sample row bias).  n[k] % 4 == 0; n[k] = 0: absent.
@@ -322,12 +357,15 @@ int launch_f32_to_bf16(const float* x, bf16_t* y, int64_t n, hipStream_t stream)
 int launch_timestep_embedding(const int64_t* t, bf16_t* out, int batch, int dim, hipStream_t stream);
 int launch_copy_strided(const bf16_t* src, int ld_src, bf16_t* dst, int ld_dst, int rows, int cols,
                         hipStream_t stream);
-// kfac non-null (guidance rescale, needs eps_u): e = fmaf(cfg_scale, eps_c - eps_u, eps_u) * kfac[i / n_per_sample]; x_copy non-null: x_prev
-// is stored there too (the eager loop's trace row)
-int launch_ddim_step(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, float a_t,
-                     float a_prev, float sigma_t, float s1m, const float* noise, float temperature,
-                     float* x_prev, float* pred_x0, int64_t n, hipStream_t stream,
-                     const float* kfac = nullptr, int n_per_sample = 0, float* x_copy = nullptr);
+// The step updates (kernels_misc.hip), one kernel and one launcher per solver, every form of StepOps above.  Grid: grid_for(n), or
+// (blocks of one sample, samples) for the per-sample forms.
+// DDIM: p0 = (x - sqrt(1-a_t) e) / sqrt(a_t), x_out = sqrt(a_prev) p0 + sqrt(1-a_prev-sigma^2) e (+ sigma noise temperature)
+int launch_ddim_step(const StepOps& o, hipStream_t stream);
+// DPM-Solver++ multistep: p_out = m0 = (x - sigma e) / alpha, x_out = c_x x + c_0 m0 + c_1 hist[0] + c_2 hist[1]
+int launch_dpmpp_step(const StepOps& o, hipStream_t stream);
+// UniPC predictor-corrector, x = x~_k: p_out = m0 = (x - sigma e) / alpha; xc_out = a_c xc_prev + q_0 m0 + q_1 hist[0] + q_2 hist[1] + q_3 hist[2]
+// (a_c == 0: xc_out = x); x_out = a_p xc_out + p_0 m0 + p_1 hist[0] + p_2 hist[1].  No per-sample form
+int launch_unipc_step(const StepOps& o, hipStream_t stream);
 // guidance rescale factor, one workgroup per sample: k[b] = phi std(eps_c[b]) / std(g[b]) + (1 - phi), g = fmaf(cfg_scale, eps_c - eps_u, eps_u)
 // over the sample's n_per_sample elements; std(g) == 0: 1.  st non-null: phi is read from the step state (replayed steps).  fp64 sums in a
 // fixed order: the bits depend on nothing but the inputs
@@ -335,9 +373,10 @@ int launch_cfg_rescale_factor(const float* eps_c, const float* eps_u, float cfg_
                               int n_per_sample, float* k_out, hipStream_t stream);
 int launch_repeat_batch(const float* x, float* y, int64_t n_per, int reps, hipStream_t stream);
 int launch_fill_i64(int64_t* p, int64_t v, int n, hipStream_t stream);
-// first kernel of a replayed step: timestep / coefficients of step st->counter (+ the step's time-embedding rows when ts != null,
+// first kernel of a replayed step: the timestep of step st->counter (+ the step's time-embedding rows when ts != null,
 // + the masked-sampling blend of the latent x [n] when st->x0 != null; the grid always covers x, so one capture serves both).
-// The counter itself is advanced by the step's LAST kernel (launch_ddim_step_state), so every workgroup here reads the same value.
+// It publishes the executed step in st->cur_row.  The counter itself is advanced by the step's LAST kernel (the solver's step launch
+// with st), so every workgroup here reads the same value.
 int launch_step_setup(StepState* st, int64_t* t_out, int batch, float* x, int64_t n, hipStream_t stream, const TembSel* ts = nullptr);
 // out = (sqrt_ac x0 + sqrt_1m_ac noise) mask + (1 - mask) x over [batch, channels, hw]; mask [mask_batch, mask_channels, hw] broadcast
 // (mask_batch in {1, batch}, mask_channels in {1, channels}); mask null: out = the q_sample alone (x unused).  out may be x.
@@ -359,38 +398,10 @@ int hist_match_launches(int want_apply, int want_loss);
 int launch_hist_match(const float* dst, const float* ref, const uint8_t* mask_dst, const uint8_t* mask_ref, const int32_t* index, int n, int H,
                       int W, float* matched, uint8_t* tables, float* loss, int32_t* counts, void* scratch, hipStream_t stream);
 int launch_temb_select(const TembSel& ts, int step, hipStream_t stream);          // the same copy with a host-side step index (eager loop)
-int launch_ddim_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
-                           hipStream_t stream, const float* kfac = nullptr, int n_per_sample = 0);
-// DPM-Solver++ multistep update (kernels_misc.hip): m0_out <- (x - sigma e) / alpha, x_prev <- c_x x + c_0 m0 + c_1 m1 + c_2 m2 with
-// e = eps_u + cfg_scale (eps_c - eps_u) (eps_u null: eps_c).  m1 / m2 are read only where their coefficient is non-zero; x_prev may be x.
-// kfac / n_per_sample as in launch_ddim_step; x_copy / m0_copy non-null: x_prev / m0 are stored there too (the eager loop's trace rows)
-int launch_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, float cfg_scale, const DpmCoef& k, const float* m1,
-                      const float* m2, float* x_prev, float* m0_out, int64_t n, hipStream_t stream,
-                      const float* kfac = nullptr, int n_per_sample = 0, float* x_copy = nullptr, float* m0_copy = nullptr);
-// the same update in place with the coefficients / ring slots step_setup_kernel published; the step's LAST kernel: advances the counter
-int launch_dpmpp_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
-                            hipStream_t stream, const float* kfac = nullptr, int n_per_sample = 0);
-// UniPC predictor-corrector update (kernels_misc.hip), one launch: m0_out <- (x - sigma e) / alpha with x = x~_k; xc_out <- a_c xc_prev +
-// q_0 m0 + q_1 m1 + q_2 m2 + q_3 m3 (a_c == 0: xc_out <- x); x_next <- a_p xc_out + p_0 m0 + p_1 m1 + p_2 m2.  e, kfac, x_copy (x_next
-// once more) / m0_copy as in launch_dpmpp_step.  xc_prev / m1..m3 are read only where a coefficient of theirs is non-zero; x_next may be
-// x, xc_out may be xc_prev
-int launch_unipc_step(const float* x, const float* xc_prev, const float* eps_c, const float* eps_u, float cfg_scale, const UniCoef& k,
-                      const float* m1, const float* m2, const float* m3, float* x_next, float* xc_out, float* m0_out, int64_t n,
-                      hipStream_t stream, const float* kfac = nullptr, int n_per_sample = 0, float* x_copy = nullptr, float* m0_copy = nullptr);
-// the same update in place (x, st->xc) with the row / ring slots step_setup_kernel published; the step's LAST kernel: advances the counter
-int launch_unipc_step_state(float* x, const float* eps_c, const float* eps_u, float cfg_scale, StepState* st, int64_t n,
-                            hipStream_t stream, const float* kfac = nullptr, int n_per_sample = 0);
 // ---- per-sample loop (kernels_misc.hip) ----
 // first kernel of a per-sample step (st->rows non-null): t_out[b] = the timestep of sample b % samples in this executed step (`batch` rows:
 // both halves with guidance), row temb_row of the tables into row b of each proj, and the executed step into st->cur_row
 int launch_step_setup_rows(StepState* st, int64_t* t_out, int batch, int samples, hipStream_t stream, const TembSel* ts = nullptr);
-// The per-sample updates, one grid row per sample; a finished sample's blocks return before any load or store.  st non-null: in place
-// on x with the entries of this executed step, noise row / ring slots by the step, the step's LAST kernel (moves the counter).
-// st null: rows = `samples` device entries, x_prev (/ m0_out) written for active samples only; DDIM: noise [samples * per] or null, pred_x0 or null
-int launch_ddim_step_rows(const float* x, const float* eps_c, const float* eps_u, const StepRow* rows, StepState* st, const float* noise,
-                          float temperature, float* x_prev, float* pred_x0, int samples, int n_per_sample, hipStream_t stream);
-int launch_dpmpp_step_rows(const float* x, const float* eps_c, const float* eps_u, const StepRow* rows, StepState* st, const float* m1,
-                           const float* m2, float* x_prev, float* m0_out, int samples, int n_per_sample, hipStream_t stream);
 int launch_softmax_rows(const float* x, bf16_t* y, int rows, int cols, hipStream_t stream);
 int launch_post_quant(const float* z, const bf16_t* w, const float* bias, float inv_scale, float* out, int batch, int C, int hw,
                       hipStream_t stream);

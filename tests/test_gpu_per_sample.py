@@ -177,7 +177,7 @@ def test_ddim_row_kernel_against_fp64(engines, per):
 
 @pytest.mark.parametrize('per', [256, 100, 105])
 def test_dpm_row_kernel_against_fp64(engines, per):
-    """the same bound for the DPM-Solver++ rows (dpmpp_update_range's arithmetic) on the rows the bound is stated for: a guided sample
+    """the same bound for the DPM-Solver++ rows (dpmpp_update_at's arithmetic) on the rows the bound is stated for: a guided sample
     (order 2), one with s = 1 and an eps_u (order 3), one that has finished; the finished sample's x, ring (m0) and output rows keep
     their bit pattern although its eps is NaN.  (The magnitude sum takes |c_0 m0| with the computed m0, as the uniform kernels' test
     does: where x - sigma e cancels AND c_x is small - the last entries of a 4-step grid at order 1 - the rounding of m0 alone can

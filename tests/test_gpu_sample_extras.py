@@ -20,7 +20,7 @@ from makeupdiffuse_amd import lib as mlib
 from makeupdiffuse_amd.ddim import DDIMSampler
 from makeupdiffuse_amd.diffmk.makeup_diffuse import TestDiffuseModel
 from makeupdiffuse_amd.dpm_solver import DPMSolverSampler
-from makeupdiffuse_amd.engine import MkdEngine, NetConfig, dpmpp_table, sample_log_rows
+from makeupdiffuse_amd.engine import MkdEngine, NetConfig, dpmpp_table, sample_log_rows, unipc_table
 from oracle import nets, sampler, vae
 
 pytestmark = pytest.mark.gpu
@@ -221,6 +221,83 @@ def test_ddim_step_kernel_with_factor_against_fp64(n, per):
     sync()
     assert torch.equal(a1, a2) and torch.equal(b1, b2) and not torch.equal(a1, xp)
     assert lib.mkd_ddim_step_ex(P(x), P(ec), None, s, a_t, a_prev, sigma, s1m, None, 1.0, P(kf), per, P(xp), P(x0), n, None) == -1
+
+
+def _placed(vals, shift):
+    """the values in a fresh device buffer, `shift` floats past its (at least 16-byte aligned) start"""
+    buf = torch.empty(vals.numel() + 4, device=DEV)
+    assert buf.data_ptr() % 16 == 0
+    view = buf[shift:shift + vals.numel()]
+    view.copy_(vals)
+    return view
+
+
+def _run_step(lib, solver, vals, coef, shift, guided, in_place, per, ddim_extras=False):
+    """one stand-alone step of `solver` on operands placed at `shift`; returns the outputs (new latent, x0-prediction, xc) on the host"""
+    n = vals['x'].numel()
+    t = {k: _placed(v, shift) for k, v in vals.items()}
+    nan = lambda: _placed(torch.full((n,), float('nan')), shift)
+    x_out = t['x'] if in_place else nan()
+    e_u, scale = (P(t['e_u']), 9.0) if guided else (None, 1.0)
+    kf = None
+    if guided:
+        kf = torch.empty(n // per, device=DEV)
+        assert lib.mkd_cfg_rescale_factor(P(t['e_c']), P(t['e_u']), scale, PHI, n // per, per, P(kf), None) == 0
+    if solver == 'ddim':
+        p0 = None if ddim_extras else nan()
+        noise, sigma = (P(t['m1']), 0.05) if ddim_extras else (None, 0.0)
+        a_t, a_prev = 0.0057755, 0.00728173
+        head = (P(t['x']), P(t['e_c']), e_u, scale, a_t, a_prev, sigma, float(np.sqrt(1 - a_t)), noise, 0.8)
+        rc = (lib.mkd_ddim_step_ex(*head, P(kf), per, P(x_out), P(p0), n, None) if guided else
+              lib.mkd_ddim_step(*head, P(x_out), P(p0), n, None))
+        outs = (x_out, p0)
+    elif solver == 'dpm':
+        p0 = nan()
+        head = (P(t['x']), P(t['e_c']), e_u, scale, (C.c_float * 6)(*coef.tolist()), P(t['m1']), P(t['m2']))
+        rc = (lib.mkd_dpmpp_step_ex(*head, P(kf), per, P(x_out), P(p0), n, None) if guided else
+              lib.mkd_dpmpp_step(*head, P(x_out), P(p0), n, None))
+        outs = (x_out, p0)
+    else:
+        p0 = nan()
+        xc_out = t['xc'] if in_place else nan()
+        head = (P(t['x']), P(t['xc']), P(t['e_c']), e_u, scale, (C.c_float * 12)(*coef.tolist()), P(t['m1']), P(t['m2']), P(t['m3']))
+        rc = (lib.mkd_unipc_step_ex(*head, P(kf), per, P(x_out), P(xc_out), P(p0), n, None) if guided else
+              lib.mkd_unipc_step(*head, P(x_out), P(xc_out), P(p0), n, None))
+        outs = (x_out, p0, xc_out)
+    assert rc == 0, lib.mkd_last_error()
+    sync()
+    return [None if o is None else o.cpu() for o in outs]
+
+
+@pytest.mark.parametrize('solver', ['ddim', 'dpm', 'unipc'])
+@pytest.mark.parametrize('n,per', [(512, 256), (1028, 257), (1003, 59)])      # 16-byte form twice (one past a multiple of 256 / 1024), scalar only
+def test_step_kernel_forms_and_aliasing(solver, n, per):
+    """One walker serves every solver: on 16-byte aligned operands (the 16-byte form where n % 4 == 0) and on the same values 4 bytes
+    further (always the scalar form) a step gives the same bits, and in place (x_prev is x, xc_out is xc_prev) the bits of out of
+    place.  Unguided, and guided with rescale factors; DDIM also with the eta term's noise and no pred_x0.  Every history plane is read
+    (an order-3 entry from the middle of the table).  What the values must be is test_*_step_kernel*_against_fp64's business."""
+    lib = L()
+    _, a, ap = dref.grid(20)
+    coef = None
+    if solver == 'dpm':
+        coef = dpmpp_table(a, ap, 3, True)[0][10]
+        assert coef[4] != 0 and coef[5] != 0
+    elif solver == 'unipc':
+        coef = unipc_table(a, ap, 3, True, True)[0][10]
+        assert all(coef[j] != 0 for j in (2, 4, 5, 6, 9, 10))
+    g = torch.Generator().manual_seed(7 * n + len(solver))
+    vals = {k: torch.randn(n, generator=g) for k in ('x', 'e_c', 'e_u', 'm1', 'm2', 'm3', 'xc')}
+    variants = [dict(guided=False), dict(guided=True)] + ([dict(guided=True, ddim_extras=True)] if solver == 'ddim' else [])
+    seen = []
+    for v in variants:
+        base = _run_step(lib, solver, vals, coef, 0, in_place=False, per=per, **v)
+        assert all(o is None or torch.isfinite(o).all() for o in base) and not torch.equal(base[0], vals['x'])
+        for shift, in_place in ((1, False), (0, True), (1, True)):
+            got = _run_step(lib, solver, vals, coef, shift, in_place=in_place, per=per, **v)
+            for name, b, o in zip(('x_out', 'p0', 'xc_out'), base, got):
+                assert (b is None and o is None) or torch.equal(b, o), f'{solver} {v} shift {shift} in place {in_place}: {name} differs'
+        seen.append(base[0])
+    assert all(not torch.equal(seen[0], s) for s in seen[1:])          # guidance (and the noise) do change the result
 
 
 # ---- 3. one arithmetic: graph replay == linear segments == eager, final latent and every trace row -----------------------------------
