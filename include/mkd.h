@@ -518,6 +518,31 @@ int mkd_hist_match_launches(int want_matched, int want_loss);
  * identity table, matched = 0, loss 0.  Only enqueues.  n <= 65535, H * W <= 2^24, else MKD_ERR_ARG. */
 int mkd_hist_match(const float* dst, const float* ref, const uint8_t* mask_dst, const uint8_t* mask_ref, const int32_t* index,
                    int n, int H, int W, float* matched, uint8_t* tables, float* loss, int32_t* counts, void* scratch, void* stream);
+/* ---- the histogram-matching teacher: EleGANt's pseudo ground truth at warp weight alpha = 0 (reference teacher.py:96-112), i.e. the
+ * region-wise histogram match of the source to the reference composed into one image.  BUILD-DEFINED: region priority, feather and
+ * border rule below (the reference blends hard regions with a landmark warp that needs landmarks) ---- */
+/* src [n, 3, H, W] fp32; masks uint8 [4][n][H][W] in the order lip, skin, eye_left, eye_right (non-zero = inside), tables uint8
+ * [4][n][3][256] in the same order: the tables of ONE mkd_hist_match call of 4 n terms (term r n + b: dst = source b, ref = reference b
+ * under region r's masks); strengths fp32 [n][4] in the same order, or NULL for all 1; out [n, 3, H, W] fp32 in [0, 1].
+ *   id(p) = the first of lip (1), eye_left (2), eye_right (3), skin (4) whose mask is non-zero at p, else 0: skin labels overlap the
+ *     eye boxes, the priority makes the regions exclusive and the result independent of the evaluation order;
+ *   c_r(p) = the number of pixels q of the (2 feather + 1)^2 window around p that lie INSIDE the image and have id(q) = r; K =
+ *     (2 feather + 1)^2 always, so outside counts as "no region" (makeup fades towards the image border) and sum_r c_r <= K;
+ *   v = clamp(src_c(p), 0, 1) * 255 in fp32 and i = min(int(v), 255), exactly mkd_hist_match's value and bin (NaN -> 0; a zero, also from a source of -0, is +0);
+ *   out_c(p) = clamp((v + sum_{r = 1..4} (a_r * (c_r / K)) * (T_{r,c}[i] - i)) / 255, 0, 1)
+ * evaluated in double from the fp32 / integer operands, every operation rounded on its own, the terms added in the order r = 1..4,
+ * and rounded to fp32 ONCE (tests/teacher_ref.py reproduces the bits).  Consequences: feather 0 and a = 1 give (T_r[i] + (v - i)) / 255
+ * inside region r -- mkd_hist_match's matched value / 255 plus the source's sub-bin fraction, which is 0 for a source whose v is a
+ * whole number -- and the clamped source elsewhere; an identity table (an empty side of a term) changes nothing; a = 0 gives
+ * float(double(v) / 255): a source value float(k / 255) comes back bit for bit, any other within one fp32 ulp.
+ * a_r outside [0, 1] is not checked here.  One launch (mkd_pgt_launches), no scratch, no atomics, no host sync, no allocation: the call
+ * only enqueues.  No alignment of W or of the pointers beyond 4 bytes for the fp32 arrays is assumed; the 16-byte and the scalar form
+ * give the same bits.  MKD_ERR_ARG before anything is enqueued unless 1 <= n <= 65535, H, W >= 1, H * W <= 2^24, 0 <= feather <= 8,
+ * src / masks / tables / out non-null, and out does not overlap src. */
+int mkd_pgt_compose(const float* src, const uint8_t* masks, const uint8_t* tables, const float* strengths, int n, int H, int W,
+                    int feather, float* out, void* stream);
+/* Launches one mkd_pgt_compose call enqueues: 1. */
+int mkd_pgt_launches(void);
 
 /* ---- full-resolution photos: crop-resize in, detail-keeping paste out (reference diffdata/preprocessing.py:131-169 crops the face and
  * resizes it to the network size; the paste back is BUILD-DEFINED after the Laplacian detail transfer of PSGAN / EleGANt) ---- */

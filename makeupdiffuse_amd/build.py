@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(HERE, 'csrc', '_obj')
 LIB = os.path.join(HERE, 'libmkd.so')
-SOURCES = ['kernels_gemm.hip', 'kernels_conv.hip', 'kernels_norm.hip', 'kernels_attn.hip', 'kernels_tfm.hip', 'kernels_misc.hip', 'kernels_hist.hip', 'kernels_region.hip', 'kernels_photo.hip', 'kernels_video.hip', 'kernels_motion.hip', 'kernels_align.hip', 'kernels_components.hip', 'kernels_parser.hip', 'kernels_noise.hip', 'parser.hip', 'engine.hip', 'api_kernels.hip']
+SOURCES = ['kernels_gemm.hip', 'kernels_conv.hip', 'kernels_norm.hip', 'kernels_attn.hip', 'kernels_tfm.hip', 'kernels_misc.hip', 'kernels_hist.hip', 'kernels_region.hip', 'kernels_photo.hip', 'kernels_video.hip', 'kernels_motion.hip', 'kernels_align.hip', 'kernels_components.hip', 'kernels_parser.hip', 'kernels_noise.hip', 'kernels_teacher.hip', 'parser.hip', 'engine.hip', 'api_kernels.hip']
 HEADERS = ['mkd_common.h', 'gemm_device.h', 'parser.h', 'tfm_fold.h', 'paste_guided.h', 'gemm_tiles.inc', 'gemm_tuned.inc', os.path.join('..', '..', 'include', 'mkd.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wall', '-Wno-unused-function', '-Wno-unused-value', '-Wno-unused-result',
          '-ffp-contract=fast']
@@ -51,7 +51,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             cmd = [hipcc] + FLAGS + ['-c', sp, '-o', op]
             if verbose:
                 print('[mkd build]', ' '.join(cmd), flush=True)
-            jobs.append((subprocess.Popen(cmd), cmd, stamp, dg))          # translation units compile concurrently (18 of them)
+            jobs.append((subprocess.Popen(cmd), cmd, stamp, dg))          # translation units compile concurrently (19 of them)
         objs.append(op)
     rebuilt = bool(jobs)
     failed = None

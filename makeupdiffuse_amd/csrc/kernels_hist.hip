@@ -17,10 +17,6 @@ constexpr int HM_REPL = 8;                 // LDS replicas of the 3 x 256 counte
 constexpr int HM_RSTRIDE = 3 * 256 + 8;    // replica stride in words: shifts a bin by 8 banks per replica (768 % 64 == 0 would stack them)
 constexpr int RM_WGS = 16;                 // workgroups per label map of the region-mask kernels
 
-// rule 1 (NaN -> 0).  __fmul_rn: the product is rounded once whatever -ffp-contract says (it must not fuse into the loss' subtraction)
-__device__ __forceinline__ float hm_value(float x) { return __fmul_rn(fminf(fmaxf(x, 0.0f), 1.0f), 255.0f); }
-__device__ __forceinline__ int hm_bin(float v) { const int b = (int)v; return b > 255 ? 255 : b; }       // torch.histc(bins=256, min=0, max=256)
-
 __device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -40,6 +40,10 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
     __bf16 b = (__bf16)f;
     return __builtin_bit_cast(uint16_t, b);
 }
+// The 0..255 value and the bin of a [0, 1] pixel as mkd_hist_match and mkd_pgt_compose form them (NaN -> 0).  __fmul_rn: the product
+// is rounded once whatever -ffp-contract says (it must not fuse into a following subtraction)
+__device__ __forceinline__ float hm_value(float x) { return __fmul_rn(fminf(fmaxf(x, 0.0f), 1.0f), 255.0f); }
+__device__ __forceinline__ int hm_bin(float v) { const int b = (int)v; return b > 255 ? 255 : b; }       // torch.histc(bins=256, min=0, max=256)
 // Activation math on the hardware transcendental units (v_exp_f32 / v_rcp_f32, ~1 ulp each): an IEEE division costs ~10 VALU
 // ops and libm erff ~40, and the element-wise kernels here are VALU-bound on the few CUs a GroupNorm can occupy.
 __device__ __forceinline__ float sigmoid_scaled_f(float x, float k) {            // 1 / (1 + exp(-k x))

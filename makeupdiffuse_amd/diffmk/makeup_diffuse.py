@@ -4,7 +4,8 @@ Mirrors, for the DDIM sampling path only:
   * ``apply_model``                 reference diffmk/makeup_diffuse.py:152-170
   * ``get_input`` cond assembly     reference diffmk/makeup_diffuse.py:42-57, diffmk/makeup_controlnet.py:137-167
   * ``sample_log`` / ``log_results``reference diffmk/diffusion_makeup.py:360-411 (UPSTREAM ControlLDM.sample_log)
-Training losses, teachers, PL hooks and the VAE/CLIP stages are out of scope for this path (SURVEY.md §2);
+Training losses, the GAN teachers, PL hooks and the VAE/CLIP stages are out of scope for this path (the histogram-matching
+teacher is in: makeupdiffuse_amd/teacher.py, TestDiffuseModel(teacher='hist'));
 calling them raises NotImplementedError rather than returning something different from the reference.
 The arithmetic runs in libmkd (HIP); there is no CPU implementation behind these classes."""
 from __future__ import annotations
@@ -471,7 +472,19 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                  seg_key: str = 'nonmakeup_seg', makeup_score: bool = False, ref_seg_key: str = 'makeup_seg', sampler: str = 'ddim',
                  solver_order: int = 2, unipc_corrector: bool = True, paste_background: bool = False, paste_feather: int = 0, denoise_rows: bool = False,
                  log_every_t: int = 100, guidance_rescale: float = 0.0, face_parser=None, parser_lut=None, parse_size: int = 512,
-                 seed: Optional[int] = None, *args, **kwargs):
+                 seed: Optional[int] = None, teacher: Optional[str] = None, teacher_feather: int = 2, teacher_strengths=None,
+                 teacher_start: Optional[float] = None, teacher_t_min: int = 0, *args, **kwargs):
+        if teacher not in (None, 'hist'):
+            raise ValueError(f"teacher must be None or 'hist' (the histogram-matching pseudo ground truth), got {teacher!r}")
+        if teacher is not None or teacher_start is not None:
+            from .. import teacher as _teacher
+            _teacher.check_feather(teacher_feather)
+            if teacher_start is not None:
+                if teacher is None:
+                    raise ValueError("teacher_start needs a teacher: construct with teacher='hist'")
+                _teacher.start_steps(teacher_start, 1)          # (a number in (0, 1], or ValueError)
+            if isinstance(teacher_t_min, bool) or int(teacher_t_min) != teacher_t_min or int(teacher_t_min) < 0:
+                raise ValueError(f'teacher_t_min must be an integer >= 0, got {teacher_t_min!r}')
         if int(log_every_t) < 1:
             raise ValueError(f'log_every_t must be >= 1, got {log_every_t}')
         if not 0.0 <= float(guidance_rescale) <= 1.0:
@@ -492,6 +505,15 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         # and transfer_photos -- sample (or source photo) i of a call gets seed + i, every draw comes from noise.normal and no torch
         # generator is advanced.  None: the torch draws, call for call as before
         self.seed = seed
+        # the teacher T of MakeupDiffuse (reference README.md:10, makeup_teacher.py:197-239): 'hist' = EleGANt's pseudo ground truth at
+        # warp weight 0, region-wise histogram matching on the device (teacher.pseudo_ground_truth).  log_results then also returns the
+        # reference's ground_truth / reconstruction / sample_ddmp rows (diffmk/makeup_diffuse.py:413-464); teacher_start = tau in (0, 1]
+        # starts both passes from q_sample(encode(x_p)) and runs only the last k = round(tau S) steps.  None: every call, draw and
+        # launch is as before
+        self.teacher = teacher
+        self.teacher_feather, self.teacher_strengths = int(teacher_feather), teacher_strengths
+        self.teacher_start = None if teacher_start is None else float(teacher_start)
+        self.teacher_t_min = int(teacher_t_min)
         # label maps from the images themselves (face_parser.FaceParser, or anything with its parse()): a batch that lacks seg_key /
         # ref_seg_key gets them from the source / reference image parsed at parse_size; label maps the caller brings always win.
         # None: every path is as before (a missing label map is a KeyError)
@@ -589,13 +611,16 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
     def log_results(self, batch: dict, batch_idx: int, x_T: Optional[torch.Tensor] = None, seeds=None) -> Dict[str, torch.Tensor]:
         """The sampler calls of reference log_results (:391-410): a plain 50-step pass and a CFG pass whose
         unconditional branch keeps the SAME hint (uc_cat = c_cat, :401).  Returns latents (and decoded images
-        once a first_stage_model is attached); the teacher / reconstruction rows are out of scope.  With a face parser attached, label
+        once a first_stage_model is attached).  With teacher='hist' also the reference's teacher rows (_teacher_rows) and, with
+        teacher_start, both passes start from the diffused teacher latent and run k steps (_teacher_start).  With a face parser attached, label
         maps the batch lacks are added to ``batch`` (_fill_segs).  ``seeds`` (default: the model's ``seed``; one per pair, or an int s
         for s, s + 1, ...): every draw of both passes and of fix_background's encoder comes from noise.normal; both passes start from the
         same seeded x_T, as they do from a given ``x_T``."""
         use_ddim = self.ddim_steps is not None
         log: Dict[str, torch.Tensor] = {}
         self._check_unipc_masked()
+        if self.teacher is not None:
+            self._check_teacher(batch, x_T)
         if self.fix_background or self.paste_background or self.makeup_score:
             self._fill_segs(batch, ref=self.makeup_score)
         _, c = self.get_input(batch, self.first_stage_key)
@@ -622,9 +647,14 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         cond = {'c_concat': [c_cat], 'c_crossattn': [c_txt]}
         if self.denoise_rows:
             extra['log_every_t'] = self.log_every_t
+        sample_log = self.sample_log
+        if self.teacher is not None:
+            z_p = self._teacher_rows(log, batch, src, ref, c['ref_img'], cond, sd)
+            if self.teacher_start is not None:
+                sample_log = self._teacher_start(z_p if z_p is not None else self.get_z(log['ground_truth'], seeds=sd), sd)
         if self.sample:
-            samples, inter = self.sample_log(cond=cond, batch_size=b, ddim=use_ddim, ddim_steps=self.ddim_steps,
-                                             eta=self.ddim_eta, **extra)
+            samples, inter = sample_log(cond=cond, batch_size=b, ddim=use_ddim, ddim_steps=self.ddim_steps,
+                                        eta=self.ddim_eta, **extra)
             log['samples_latent'] = samples
             if self.denoise_rows:
                 self._log_denoise_row(log, 'denoise_row', inter['pred_x0'])
@@ -638,9 +668,9 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             uc_full = {'c_concat': [c_cat], 'c_crossattn': [self.get_unconditional_conditioning(b)]}
             if self.guidance_rescale != 0.0:
                 extra['guidance_rescale'] = self.guidance_rescale
-            samples_cfg, inter = self.sample_log(cond=cond, batch_size=b, ddim=use_ddim, ddim_steps=self.ddim_steps,
-                                                 eta=self.ddim_eta, unconditional_guidance_scale=self.unconditional_guidance_scale,
-                                                 unconditional_conditioning=uc_full, **extra)
+            samples_cfg, inter = sample_log(cond=cond, batch_size=b, ddim=use_ddim, ddim_steps=self.ddim_steps,
+                                            eta=self.ddim_eta, unconditional_guidance_scale=self.unconditional_guidance_scale,
+                                            unconditional_conditioning=uc_full, **extra)
             name = f'samples_cfg_scale_{self.unconditional_guidance_scale:.2f}'
             log[name + '_latent'] = samples_cfg
             if self.denoise_rows:
@@ -653,6 +683,102 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                     log[f'makeup_hist_cfg_scale_{self.unconditional_guidance_scale:.2f}'] = self.makeup_hist(batch, log[name], c['ref_img'])
         return log
 
+    # ---- the teacher (opt-in: teacher='hist') ---------------------------------------------------------------------------------------
+    def _check_teacher(self, batch: dict, x_T) -> None:
+        """what the teacher options need and what they are not combined with; raised before anything is enqueued"""
+        if self.face_parser is None:
+            for k in (self.seg_key, self.ref_seg_key):
+                if k not in batch:
+                    raise ValueError(f"teacher='hist' needs the label maps of the source and of the reference: the batch has none under "
+                                     f"'{k}' and no face parser is attached")
+        if not 0 <= self.teacher_t_min < self.num_timesteps:
+            raise ValueError(f'teacher_t_min must lie in 0 .. {self.num_timesteps - 1}, got {self.teacher_t_min}')
+        if self.teacher_start is not None:
+            if self.denoise_rows:
+                raise ValueError('teacher_start is not combined with denoise_rows')
+            self._check_teacher_start(x_T, self.guidance_rescale)
+
+    def _refuse_teacher_start(self, what: str) -> None:
+        """teacher_start acts in log_results / test_step and, as a keyword, in transfer_photos: every other sampling entry refuses a
+        model that carries it rather than running full passes without saying so"""
+        if self.teacher_start is not None:
+            raise ValueError(f'teacher_start is not combined with {what}')
+
+    def _check_teacher_start(self, x_T, phi) -> None:
+        if x_T is not None:
+            raise ValueError('teacher_start with a given x_T: the start latent is the diffused teacher image, x_T would be ignored')
+        for on, what in ((self.fix_background, 'fix_background (a masked decode does not exist)'),
+                         (phi != 0.0 and float(self.unconditional_guidance_scale) > 1.0, "guidance_rescale (the solvers' decode does not carry it)"),
+                         (float(self.ddim_eta or 0.0) != 0.0, 'ddim_eta != 0 (the teacher-started pass is deterministic after its start)')):
+            if on:
+                raise ValueError(f'teacher_start is not combined with {what}')
+        if not self.ddim_steps or int(self.ddim_steps) < 1:
+            raise ValueError('teacher_start needs ddim_steps >= 1')
+        self._sampler()
+        self._require_encoder()
+
+    def pseudo_ground_truth(self, batch: dict, src01: torch.Tensor, ref01: torch.Tensor) -> torch.Tensor:
+        """x_p in [0, 1] of the pairs (src01, ref01) under batch[seg_key] / batch[ref_seg_key] (parsed from the batch's images where a
+        face parser is attached and the batch lacks them): teacher.pseudo_ground_truth with the model's teacher_feather / _strengths"""
+        from .. import teacher
+        self._fill_segs(batch, ref=True)
+        for k in (self.seg_key, self.ref_seg_key):
+            if k not in batch:
+                raise ValueError(f"teacher='hist' needs the label maps of the source and of the reference: the batch has none under '{k}'")
+        return teacher.pseudo_ground_truth(src01, ref01, batch[self.seg_key], batch[self.ref_seg_key], strengths=self.teacher_strengths,
+                                           feather=self.teacher_feather)[0]
+
+    def _teacher_rows(self, log: dict, batch: dict, src01, ref01, ref_img, cond: dict, sd):
+        """The rows reference log_results writes beside the samples (diffmk/makeup_diffuse.py:419-442): ground_truth = 2 x_p - 1; with an
+        encoder and a decoder reconstruction = decode(get_z(ground_truth)) and sample_ddmp = the decoded x0 prediction of ONE apply_model
+        call on q_sample(z, t), t_b in [teacher_t_min, T); with makeup_score the score of x_p.  Without seeds the draws are the
+        reference's, in its order: get_z's posterior noise, torch.randint for t, torch.randn_like for the noise.  With seeds t_b =
+        noise.teacher_timesteps(seed_b, sub_b) and the noise is noise.normal on STREAM_TEACHER, row 0.  Returns z (or None)."""
+        x_p = self.pseudo_ground_truth(batch, src01, ref01)
+        log['ground_truth'] = x_p * 2.0 - 1.0
+        if self.makeup_score:
+            log['makeup_hist_teacher'] = self.makeup_hist(batch, log['ground_truth'], ref_img)
+        if not (self.has_first_stage and self._require_engine().vae_enc_cfg is not None):
+            return None
+        z = self.get_z(log['ground_truth'], seeds=sd)
+        log['reconstruction'] = self.decode_first_stage(z)
+        if sd is not None:
+            from ..noise import STREAM_TEACHER, normal, teacher_timesteps
+            t = torch.tensor(teacher_timesteps(sd, self.teacher_t_min, self.num_timesteps), dtype=torch.long).to(self.device)
+            nz = normal(sd, tuple(z.shape)[1:], stream=STREAM_TEACHER, device=self.device)
+        else:
+            t = torch.randint(self.teacher_t_min, self.num_timesteps, (z.shape[0],), device=self.device).long()
+            nz = torch.randn_like(z)
+        x_noisy = (self.sqrt_alphas_cumprod.to(self.device)[t].view(-1, 1, 1, 1) * z
+                   + self.sqrt_one_minus_alphas_cumprod.to(self.device)[t].view(-1, 1, 1, 1) * nz)          # UPSTREAM DDPM.q_sample
+        _, x_recon = self.apply_model(x_noisy, t, cond, return_all=True)
+        log['sample_ddmp'] = self.decode_first_stage(x_recon)
+        return z
+
+    def _teacher_start(self, z_p: torch.Tensor, sd, tau=None):
+        """sample_log's stand-in of a teacher-started pass: k = teacher.start_steps(tau or teacher_start, ddim_steps); the start latent is
+        stochastic_encode(z_p, k - 1) on the sampler's schedule of ddim_steps (seeded: stream 2 row 0; else one randn_like), drawn ONCE
+        and shared by both passes as x_T is; each pass is the solver's decode(x, cond, t_start=k): k evaluations instead of ddim_steps"""
+        from .. import teacher
+        solver, cls, options = self._sampler()
+        k = teacher.start_steps(self.teacher_start if tau is None else tau, self.ddim_steps)
+        smp = cls(self)
+        if solver.name == 'ddim':
+            smp.make_schedule(ddim_num_steps=self.ddim_steps, ddim_eta=0.0, verbose=False)
+        else:
+            smp.make_schedule(self.ddim_steps)
+        x_start = getattr(smp, '_ddim', smp).stochastic_encode(z_p, k - 1, **({} if sd is None else {'seeds': sd}))
+
+        def sample_log(cond, unconditional_guidance_scale=1.0, unconditional_conditioning=None, **rest):
+            # sample_log's own keywords that a decode does not take: the batch and the grid are the start latent's, eta is refused unless
+            # 0, the seeds went into the start.  Anything else (x_T, mask / x0, log_every_t, guidance_rescale, ...) must not get here
+            unknown = sorted(set(rest) - {'batch_size', 'ddim', 'ddim_steps', 'eta', 'seeds'})
+            if unknown or rest.get('eta') not in (None, 0, 0.0):
+                raise TypeError(f'a teacher-started pass does not carry {unknown or "eta"}')
+            return smp.decode(x_start, cond, k, unconditional_guidance_scale=unconditional_guidance_scale,
+                              unconditional_conditioning=unconditional_conditioning, **options), None
+        return sample_log
+
     @torch.no_grad()
     def transfer_specs(self, batch: dict, specs, x_T: Optional[torch.Tensor] = None, seeds=None) -> Dict[str, torch.Tensor]:
         """One ``batching.SampleSpec`` per pair of the batch (steps, eta, guidance, t_start, order), sampled together: requests that
@@ -663,6 +789,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         with a first stage, the decoded samples.  ``seeds`` (default: the model's ``seed``): one per pair, beside the specs; each pass
         gets its members' seeds, so a pair's noise does not depend on which pass it runs in."""
         from ..batching import SampleSpec
+        self._refuse_teacher_start('transfer_specs (a SampleSpec carries its own t_start: compose it with teacher.pseudo_ground_truth '
+                                   'and stochastic_encode)')
         solver = SOLVERS.get(self.sampler)
         if solver is not None and solver.rows_id is None:
             self._sampler()[1](self).sample_specs()          # (NotImplementedError: the per-sample loop runs DDIM and DPM-Solver++ only)
@@ -765,6 +893,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         weight alpha before the 50-step loop).  batch holds src_img, ref_img, `ref2_key`, txt_emb for
         N pairs; every pair is sampled at every alpha -> latents [N*len(alphas), 4, h, w] ordered pair-major.  ``seeds`` (default: the
         model's ``seed``): one per PAIR; without ``x_T`` the pair's start noise is noise.normal on stream 0, shared by its alphas."""
+        self._refuse_teacher_start('interpolate (two references: the teacher image of one pair does not exist)')
         src = self.get_origin_img_input(batch, self.src_img_key)
         r1 = self.get_origin_img_input(batch, self.ref_img_key)
         r2 = self.get_origin_img_input(batch, ref2_key)
@@ -816,6 +945,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         so that "lips only" leaves the rest of the face alone.  ``guidance_rescale`` (default: the model's setting) is the phi of the
         guided pass, engaged with unconditional_guidance_scale != 1 and phi > 0.  ``seeds`` (default: the model's ``seed``): one per pair;
         without ``x_T`` the start noise is noise.normal on stream 0 -- the only draw of this deterministic pass."""
+        self._refuse_teacher_start('transfer_regions (several references: the teacher image of one pair does not exist)')
         from .. import regions as rg
         phi = float(self.guidance_rescale if guidance_rescale is None else guidance_rescale)
         if not 0.0 <= phi <= 1.0:
@@ -878,16 +1008,19 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                                                                            feather=self.paste_feather, return_alpha=True)
         return out
 
-    def _photo_pass(self, src_photos, ref_photos, src_regions, ref_regions, src_segs, x_T, size, batch, phi, seeds=None):
+    def _photo_pass(self, src_photos, ref_photos, src_regions, ref_regions, src_segs, x_T, size, batch, phi, seeds=None, teacher=None,
+                    ref_segs=None):
         """the single pass of transfer_photos for one batch of (photo, region) pairs on the device: crop-resize both, sample, decode,
         paste_source -> (the decoded images [n,3,size,size], the source crops img01 the paste needs).  A region is a box or a
         photo.Frame (photo.crop_regions: a batch without a rolled frame is one crop_resize call).  seeds: a noise.Seeds over the pairs (the
-        photo's seed, the face's rank as the sub-stream) for every draw of the pass, or None"""
+        photo's seed, the face's rank as the sub-stream) for every draw of the pass, or None.  teacher = (tau, feather, strengths): every
+        crop gets its x_p from its own crop, its reference's crop and their label maps (crop-resized ``src_segs`` / ``ref_segs``, else
+        parsed) and the pass starts from it (_teacher_start); None: the pass as before"""
         eng = self._require_engine()
         self._check_unipc_masked()
-        need_seg = self.fix_background or self.paste_background
+        need_seg = self.fix_background or self.paste_background or teacher is not None
         cs = eng.crop_regions(src_photos, src_regions, size, labels=src_segs)
-        cr = eng.crop_regions(ref_photos, ref_regions, size)
+        cr = eng.crop_regions(ref_photos, ref_regions, size, **({} if ref_segs is None else {'labels': ref_segs}))
         n = len(src_photos)
         if cr.img01.shape[0] != n:
             raise ValueError(f'{n} source photos but {cr.img01.shape[0]} reference photos')
@@ -907,7 +1040,14 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                          unconditional_conditioning={'c_concat': cond['c_concat'], 'c_crossattn': [self.get_unconditional_conditioning(n)]})
             if phi != 0.0:
                 extra['guidance_rescale'] = phi
-        lat, _ = self.sample_log(cond=cond, batch_size=n, ddim=True, ddim_steps=self.ddim_steps, eta=self.ddim_eta, **extra)
+        sample_log = self.sample_log
+        if teacher is not None:
+            from .. import teacher as _teacher
+            tau, t_feather, t_strengths = teacher
+            x_p = _teacher.pseudo_ground_truth(src, ref, seg_batch[self.seg_key], cr.labels if ref_segs is not None else self.parse_images(ref),
+                                               strengths=t_strengths, feather=t_feather)[0]
+            sample_log = self._teacher_start(self.get_z(x_p * 2.0 - 1.0, seeds=seeds), seeds, tau)
+        lat, _ = sample_log(cond=cond, batch_size=n, ddim=True, ddim_steps=self.ddim_steps, eta=self.ddim_eta, **extra)
         img = self.decode_first_stage(lat)
         if self.paste_background:
             img, _ = self.paste_source(seg_batch, img, src * 2.0 - 1.0)
@@ -918,7 +1058,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                         x_T: Optional[torch.Tensor] = None, size: int = 256, batch: Optional[dict] = None,
                         guidance_rescale: Optional[float] = None, max_faces: Optional[int] = None, face_batch: int = 8,
                         return_faces: bool = False, own_pixels: bool = False, own_feather: int = 2, align: bool = False,
-                        min_roll: float = 5.0, guided_paste=None, seeds=None):
+                        min_roll: float = 5.0, guided_paste=None, seeds=None, teacher_start: Optional[float] = None, teacher_feather: int = 2,
+                        teacher_strengths=None, ref_segs=None):
         """Makeup transfer on photographs at their own resolution: ``src_photos`` / ``ref_photos`` are uint8 [H,W,3] tensors of any
         size (lists; the photos of a call may differ in size) with a face box (x0, y0, w, h) each.  Both boxes are crop-resized to
         ``size`` on the device (photo.crop_resize: Pillow's antialiased bilinear bytes / 255, what PairFolderDataset gives for that
@@ -970,7 +1111,14 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         ``seeds`` (default: the model's ``seed``; None: the torch draws, call for call): one seed per SOURCE PHOTO (an int s: s, s + 1,
         ...).  The face of rank k of photo i draws everything -- start latent, eta rows, blend rows, the encoder's posterior -- from
         noise.normal with (seed_i, sub = k), so a face's noise does not depend on face_batch, on max_faces or on the other photos of
-        the call.  Without max_faces every face is rank 0."""
+        the call.  Without max_faces every face is rank 0.
+
+        ``teacher_start`` = tau in (0, 1] (None: everything above, call for call): TEACHER-STARTED sampling.  Every face crop gets the
+        histogram-matching teacher's x_p (teacher.pseudo_ground_truth with ``teacher_feather`` and ``teacher_strengths``, a dict of
+        numbers for lip / eye / skin) from its own crop, its reference's crop and their label maps -- ``src_segs`` and ``ref_segs``
+        (label maps of the references at photo resolution) crop-resized, or the crops parsed by the attached parser -- and the pass
+        runs the last k = teacher.start_steps(tau, ddim_steps) steps from stochastic_encode(get_z(2 x_p - 1), k - 1).  It needs the
+        first-stage encoder; x_T, fix_background, an engaged guidance_rescale and ddim_eta != 0 are refused (ValueError)."""
         from .. import photo
         from ..components import owner_weights
         from ..face_parser import find_boxes, find_faces
@@ -980,6 +1128,18 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             raise ValueError(f'guidance_rescale must lie in [0, 1], got {phi}')
         if guided_paste is not None and not isinstance(guided_paste, photo.GuidedPaste):
             raise ValueError(f'guided_paste must be a photo.GuidedPaste or None, got {guided_paste!r}')
+        teach = None
+        if teacher_start is not None:
+            from .. import teacher as _teacher
+            _teacher.start_steps(teacher_start, 1)
+            _teacher.check_feather(teacher_feather)
+            _teacher.strength_rows(teacher_strengths, 1)
+            if self.face_parser is None and (src_segs is None or ref_segs is None):
+                raise ValueError('transfer_photos: teacher_start needs the label maps of both faces: src_segs and ref_segs, or an attached face parser')
+            self._check_teacher_start(x_T, phi)
+            teach = (float(teacher_start), int(teacher_feather), teacher_strengths)
+        elif ref_segs is not None or teacher_strengths is not None or teacher_feather != 2:
+            raise ValueError('ref_segs / teacher_feather / teacher_strengths only apply with teacher_start')
         # One body for both forms, on regions (boxes or photo.Frame's): the call without max_faces is one face per photo and one chunk
         # of all photos.  Every check comes before the engine is required.
         many = max_faces is not None
@@ -1055,6 +1215,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         items = None if faces is None else work_items(faces)
         if src_segs is not None and len(src_segs) != n:
             raise ValueError(f'{n} source photos but {len(src_segs)} label maps')
+        if ref_segs is not None and len(ref_segs) != n:
+            raise ValueError(f'{n} reference photos but {len(ref_segs)} label maps')
         if not self.has_first_stage:
             raise ValueError('transfer_photos pastes decoded images: it needs a first stage (first_stage_config)')
         if (self.fix_background or self.paste_background) and src_segs is None and self.face_parser is None:
@@ -1104,7 +1266,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                 face_sd = Seeds(tuple(sd.seeds[i] for i in pick), tuple(k for _, k in chunk))
             img, src = self._photo_pass([src_photos[i] for i in pick], [ref_photos[i] for i in pick], [faces[i][k] for i, k in chunk],
                                         [refs[i] for i in pick], None if src_segs is None else [src_segs[i] for i in pick], start, size, text, phi,
-                                        **({} if face_sd is None else {'seeds': face_sd}))
+                                        **({} if face_sd is None else {'seeds': face_sd}),
+                                        **({} if teach is None else {'teacher': teach, 'ref_segs': None if ref_segs is None else [ref_segs[i] for i in pick]}))
             imgs.append(img)
             srcs.append(src)
         if N:
@@ -1147,7 +1310,8 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         chunk).  Without a seed the ragged chunk runs as it is, as in transfer_photos.  ``motion`` (a video.MotionSearch, default
         None: off, every call as before): ONE mkd_motion_warp launch in front of every mkd_temporal_diff launch fetches the previous
         state through one integer block-matched vector per block, so the filter holds where something moves inside the crop; it
-        needs ``temporal`` (ValueError with temporal=None).  Not combined here, ValueError: ``own_pixels``, per-track references."""
+        needs ``temporal`` (ValueError with temporal=None).  Not combined here, ValueError: ``own_pixels``, per-track references,
+        ``teacher_start`` (as a keyword or on the model; video.VideoSession refuses it, so transfer_video does too)."""
         from .. import video
         return video.VideoSession(self, ref_photo, ref_box=ref_box, seed=seed, size=size, feather=feather, max_faces=max_faces,
                                   face_batch=face_batch, align=align, min_roll=min_roll, guided_paste=guided_paste, temporal=temporal,

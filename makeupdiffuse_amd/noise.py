@@ -15,13 +15,15 @@ import torch
 
 from . import lib as mlib
 
-__all__ = ['STREAM_START', 'STREAM_ETA', 'STREAM_BLEND', 'STREAM_POSTERIOR', 'STREAM_USER', 'Seeds', 'as_seeds', 'normal', 'words']
+__all__ = ['STREAM_START', 'STREAM_ETA', 'STREAM_BLEND', 'STREAM_POSTERIOR', 'STREAM_TEACHER', 'STREAM_USER', 'Seeds', 'as_seeds',
+           'normal', 'words', 'teacher_timesteps']
 
-# what a draw is for (the `stream_id` of mkd_noise_fill): 4..15 are reserved, STREAM_USER and above are free for callers
+# what a draw is for (the `stream_id` of mkd_noise_fill): 5..15 are reserved, STREAM_USER and above are free for callers
 STREAM_START = 0          # the start latent x_T (row 0)
 STREAM_ETA = 1            # the eta noise of executed step k (row k)
 STREAM_BLEND = 2          # the q_sample noise of the masked blend before executed step k (row k); stochastic_encode: row 0
 STREAM_POSTERIOR = 3      # the first-stage posterior sample (row 0)
+STREAM_TEACHER = 4        # the q_sample noise of log_results' sample_ddmp row (row 0)
 STREAM_USER = 16
 
 _U64 = 1 << 64
@@ -94,6 +96,25 @@ def as_seeds(seed_or_seqs, B: int, subs=None) -> Seeds:
             if not 0 <= v < _U32:
                 raise ValueError(f'as_seeds: a sub must lie in 0 .. 2^32 - 1, got {v}')
     return Seeds(tuple(seeds), None if own is None else tuple(own))
+
+
+def teacher_timesteps(seeds: Seeds, t_min: int, T: int) -> list:
+    """The timestep t_b in [t_min, T) of log_results' sample_ddmp row for every sample of ``seeds``: a pure function of (seed_b, sub_b),
+    computed on the host in 64-bit integer arithmetic (the splitmix64 finaliser):
+        z = (seed + 0x9E3779B97F4A7C15 (sub + 1)) mod 2^64;  z = ((z ^ (z >> 30)) 0xBF58476D1CE4E5B9) mod 2^64;
+        z = ((z ^ (z >> 27)) 0x94D049BB133111EB) mod 2^64;  z = z ^ (z >> 31);  t = t_min + z mod (T - t_min)"""
+    t_min, T = int(t_min), int(T)
+    if not 0 <= t_min < T:
+        raise ValueError(f'teacher_t_min must lie in 0 .. {T - 1}, got {t_min}')
+    out = []
+    for b, seed in enumerate(seeds.seeds):
+        sub = 0 if seeds.subs is None else seeds.subs[b]
+        z = (seed + 0x9E3779B97F4A7C15 * (sub + 1)) % _U64
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) % _U64
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) % _U64
+        z ^= z >> 31
+        out.append(t_min + z % (T - t_min))
+    return out
 
 
 def _fill(seeds, shape, stream, rows, row0, subs, device, kind):

@@ -374,8 +374,10 @@ class VideoSession:
     def __init__(self, model, ref_photo, ref_box=None, seed=None, size: int = 256, feather: int = 8, max_faces: int = 4, face_batch: int = 8,
                  align: bool = False, min_roll: float = 5.0, guided_paste=None, temporal=TemporalFilter(), box_smooth: float = 0.5,
                  tracker: Optional[FaceTracker] = None, own_pixels: bool = False, batch: Optional[dict] = None,
-                 motion: Optional[MotionSearch] = None):
+                 motion: Optional[MotionSearch] = None, teacher_start=None):
         from .face_parser import find_faces
+        if teacher_start is not None or getattr(model, 'teacher_start', None) is not None:
+            raise ValueError('teacher_start is not combined with video sessions (video_session / transfer_video)')
         if own_pixels:
             raise ValueError('video_session: own_pixels is not combined with video (a track has no owner map across frames)')
         if not isinstance(ref_photo, torch.Tensor) or ref_photo.dim() != 3:

@@ -151,6 +151,14 @@ def build_parser():
                     'state dict, e.g. 79999_iter.pth; "random": seeded random weights, for plumbing runs): label maps that --fix-background, '
                     '--paste-background, --makeup-score, --region-refs and --photos need and <data-root>/scgan_segs does not give are parsed '
                     'from the images, and --photos without a boxes file finds the face boxes itself')
+    ap.add_argument('--teacher', choices=('hist',), default=None, help='the histogram-matching teacher (EleGANt pseudo ground truth at warp '
+                    'weight 0, on the device): also write the reference\'s ground_truth / reconstruction / sample_ddmp rows, and with '
+                    '--makeup-score the teacher image\'s score (label maps nonmakeup_seg / makeup_seg from <data-root>/scgan_segs, '
+                    '--face-parser, or synthetic ones; needs the first-stage encoder)')
+    ap.add_argument('--teacher-feather', type=int, default=2, metavar='F', help='with --teacher: box feather of the region weights, 0..8 image pixels')
+    ap.add_argument('--teacher-start', type=float, default=None, metavar='TAU', help='with --teacher: start both passes from the diffused '
+                    'teacher image and run only the last round(TAU * steps) steps, TAU in (0, 1] (the pair passes; not with --photos, --region-refs, --video)')
+    ap.add_argument('--teacher-t-min', type=int, default=0, metavar='T', help='with --teacher: the sample_ddmp row diffuses to a timestep in [T, 1000)')
     ap.add_argument('--denoise-rows', action='store_true', help='also write the denoise rows of both passes (denoise_row*.png: the decoded '
                     'x0-predictions, samples as rows, x_T and the logged steps as columns), traced inside the sampling loop')
     ap.add_argument('--log-every-t', type=int, default=100, metavar='N', help='with --denoise-rows: log every table entry i with i %% N == 0 '
@@ -362,6 +370,23 @@ def main():
         raise SystemExit('--log-every-t only applies with --denoise-rows')
     if not 0.0 <= args.guidance_rescale <= 1.0:
         raise SystemExit('--guidance-rescale must lie in 0..1')
+    if args.teacher is None:
+        if args.teacher_feather != 2 or args.teacher_start is not None or args.teacher_t_min != 0:
+            raise SystemExit('--teacher-feather / --teacher-start / --teacher-t-min only apply with --teacher hist')
+    else:
+        if not 0 <= args.teacher_feather <= 8:
+            raise SystemExit('--teacher-feather must be 0..8 image pixels')
+        if args.teacher_t_min < 0:
+            raise SystemExit('--teacher-t-min must be >= 0')
+        if args.teacher_start is not None:
+            if not 0.0 < args.teacher_start <= 1.0:
+                raise SystemExit('--teacher-start must lie in (0, 1]')
+            for on, flag in ((args.fix_background, '--fix-background'), (args.denoise_rows, '--denoise-rows'),
+                             (args.guidance_rescale != 0.0, '--guidance-rescale'), (args.steps_list or args.guidance_list, '--steps-list / --guidance-list'),
+                             (args.video, '--video'), (args.photos, '--photos (transfer_photos takes teacher_start itself; the photo pass of this tool brings no reference label maps)'),
+                             (args.region_refs, '--region-refs'), (args.seed is not None and not args.device_noise, '--seed without --device-noise (a given x_T)')):
+                if on:
+                    raise SystemExit(f'--teacher-start is not combined with {flag}')
     if args.no_corrector and args.sampler != 'unipc':
         raise SystemExit('--no-corrector only applies with --sampler unipc')
     if args.sampler == 'unipc' and args.fix_background:
@@ -380,6 +405,10 @@ def main():
         model.fix_background = True
     if args.makeup_score:
         model.makeup_score = True
+    if args.teacher:
+        model.first_stage_encoder = True          # (the reconstruction / sample_ddmp rows and the teacher start encode x_p)
+        model.teacher, model.teacher_feather, model.teacher_t_min = args.teacher, args.teacher_feather, args.teacher_t_min
+        model.teacher_start = args.teacher_start
     model.paste_background, model.paste_feather = args.paste_background, args.paste_feather
     if args.ddim_steps is not None:
         model.ddim_steps = args.ddim_steps
@@ -440,7 +469,7 @@ def main():
                 batch['txt_emb'] = e.expand(b1 - b0, -1, -1).contiguous()
         else:
             batch = synthetic_batch(b0, b1, args.res, model.net_config.context_dim, with_seg=(args.fix_background or args.paste_background) and not args.face_parser,
-                                    with_makeup_seg=args.makeup_score and not args.face_parser)
+                                    with_makeup_seg=(args.makeup_score or bool(args.teacher)) and not args.face_parser)
             if use_clip:
                 del batch['txt_emb']          # 'txt' -> tokenizer -> mkd_clip_encode
         x_T = None

@@ -1,0 +1,130 @@
+#!/usr/bin/env python
+"""The histogram-matching teacher at n = 8 pairs of S = 256: teacher.pseudo_ground_truth (region masks of both label maps, ONE
+mkd_hist_match for the tables, ONE mkd_pgt_compose), the compose launch alone on prepared masks and tables, and the same x_p composed
+from torch ops on mkd_hist_match's matched images (feather 0: a chain of torch.where; feather > 0: box-filtered one-hot planes and a
+gather of the tables), each at feather 0, 2 and 8.  A device sample is the time between two events around --iters back-to-back calls,
+divided by --iters, median (minimum) over --rounds rounds; the forms are alternated inside the rounds.  --model: also a full
+log_results (plain + guided pass, --steps steps) on the randomly initialised model of runs/test.py against the same call with
+teacher_start = --tau, wall time around a device synchronisation."""
+import argparse, os, statistics, sys, time
+import torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import teacher_ref as tr
+from makeupdiffuse_amd import makeup_score as ms
+from makeupdiffuse_amd import teacher
+
+ap = argparse.ArgumentParser()
+ap.add_argument('--rounds', type=int, default=8)
+ap.add_argument('--iters', type=int, default=20)
+ap.add_argument('--batch', type=int, default=8)
+ap.add_argument('--size', type=int, default=256)
+ap.add_argument('--model', action='store_true', help='also time a sampling pass with and without teacher_start')
+ap.add_argument('--steps', type=int, default=50)
+ap.add_argument('--tau', type=float, default=0.6)
+ap.add_argument('--out', default=None, help='also write the report to this file')
+args = ap.parse_args()
+if args.rounds < 6:
+    raise SystemExit('--rounds must be at least 6 (the median of fewer says little)')
+if not torch.cuda.is_available():
+    raise SystemExit('bench_teacher.py measures on the GPU: there is none')
+
+lines = []
+B, S = args.batch, args.size
+
+
+def say(text):
+    print(text, flush=True)
+    lines.append(text)
+
+
+def timed(call):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(args.iters):
+        call()
+    b.record(); torch.cuda.synchronize()
+    return a.elapsed_time(b) / args.iters
+
+
+src, ref, sseg, rseg = (torch.from_numpy(x).cuda() for x in tr.synthetic_pairs(n=B, size=S))
+_, tables, counts = teacher.pseudo_ground_truth(src, ref, sseg, rseg, feather=0)
+masks = torch.stack([ms.region_masks(sseg)[0][r] for r in ms.REGIONS]).contiguous()          # [4, B, S, S]
+rmasks = torch.stack([ms.region_masks(rseg)[0][r] for r in ms.REGIONS]).contiguous()
+matched = ms.histogram_match(src.repeat(4, 1, 1, 1), ref.repeat(4, 1, 1, 1), masks.view(4 * B, S, S), rmasks.view(4 * B, S, S), want_loss=False)[0]
+matched = matched.view(4, B, 3, S, S)
+out = torch.empty_like(src)
+ORDER = (1, 3, 2, 0)          # skin, eye_right, eye_left, lip: the highest priority is written last
+
+
+def torch_hard():
+    """feather 0 from the matched images: inside region r (by priority) matched_r + the source's sub-bin fraction, else the source"""
+    v = src.clamp(0, 1) * 255.0
+    x = v
+    frac = v - v.floor()
+    for r in ORDER:
+        x = torch.where(masks[r][:, None] != 0, matched[r] + frac, x)
+    return (x / 255.0).clamp(0, 1)
+
+
+def torch_soft(F):
+    v = src.clamp(0, 1) * 255.0
+    i = v.long().clamp(max=255)
+    ids = torch.zeros_like(masks[0])
+    for r, rid in zip(ORDER, (4, 3, 2, 1)):
+        ids = torch.where(masks[r] != 0, torch.full_like(ids, rid), ids)
+    acc = v
+    for plane, rid in ((0, 1), (2, 2), (3, 3), (1, 4)):
+        w = torch.nn.functional.avg_pool2d((ids == rid).float()[:, None], 2 * F + 1, 1, F, count_include_pad=True)
+        T = torch.gather(tables[plane].float(), 2, i.view(B, 3, S * S)).view(B, 3, S, S)
+        acc = acc + w * (T - i)
+    return (acc / 255.0).clamp(0, 1)
+
+
+assert torch.equal(teacher.compose(src, masks, tables, None, 0), teacher.pseudo_ground_truth(src, ref, sseg, rseg, feather=0)[0])
+err = (torch_hard() - teacher.compose(src, masks, tables, None, 0)).abs().max().item()
+err2 = (torch_soft(2) - teacher.compose(src, masks, tables, None, 2)).abs().max().item()
+say(f'n = {B}, S = {S}: region pixels of pair 0 (source, reference) {counts[:, 0].tolist()}; torch compositions differ from mkd_pgt_compose by at '
+    f'most {err:.2e} (feather 0) / {err2:.2e} (feather 2): fp32 against one rounding of a double')
+forms = {}
+for F in (0, 2, 8):
+    forms[f'teacher.pseudo_ground_truth      feather {F} ({teacher.launches()} launches)'] = lambda F=F: teacher.pseudo_ground_truth(src, ref, sseg, rseg, feather=F)
+    forms[f'mkd_pgt_compose alone            feather {F} (1 launch)'] = lambda F=F: teacher.compose(src, masks, tables, None, F, out=out)
+    forms[f'torch composition alone          feather {F}'] = torch_hard if F == 0 else (lambda F=F: torch_soft(F))
+for call in forms.values():
+    call()
+torch.cuda.synchronize()
+samples = {k: [] for k in forms}
+for _ in range(args.rounds):
+    for k, call in forms.items():
+        samples[k].append(timed(call))
+for k, v in samples.items():
+    say(f'{k}: median {statistics.median(v) * 1e3:8.1f} us, min {min(v) * 1e3:8.1f} us')
+
+if args.model:
+    from makeupdiffuse_amd.config import create_model
+    m = create_model(os.path.join(ROOT, 'diffmodels', 'test_diffusion_makeup.yaml')).cpu()
+    m.first_stage_encoder = True
+    m.ddim_steps, m.teacher, m.save_images = args.steps, 'hist', False
+    m.cuda(0)
+    m.engine.init_random(seed=0)
+    m.uncond_embedding = torch.zeros(1, 77, m.net_config.context_dim)
+    batch = {'src_img': src.cpu(), 'ref_img': ref.cpu(), m.seg_key: sseg.cpu(), m.ref_seg_key: rseg.cpu(),
+             'txt_emb': torch.randn(B, 77, m.net_config.context_dim, generator=torch.Generator().manual_seed(3))}
+    wall = {None: [], args.tau: []}
+    for rnd in range(4):          # the first round warms up (plans, graphs) and is dropped
+        for tau in wall:
+            m.teacher_start = tau
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            m.log_results(dict(batch), 0, seeds=1)
+            torch.cuda.synchronize()
+            if rnd:
+                wall[tau].append(time.perf_counter() - t0)
+    k = teacher.start_steps(args.tau, args.steps)
+    say(f'log_results, batch {B} at {S}^2, plain + guided pass with the teacher rows: {args.steps} steps median {statistics.median(wall[None]) * 1e3:.1f} ms; '
+        f'teacher_start = {args.tau} ({k} steps) median {statistics.median(wall[args.tau]) * 1e3:.1f} ms (3 rounds each, alternated)')
+if args.out:
+    with open(args.out, 'w') as f:
+        f.write('\n'.join(lines) + '\n')
