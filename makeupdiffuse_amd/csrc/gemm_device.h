@@ -87,6 +87,16 @@ __device__ __forceinline__ void gn_atomic_add(long long* p, long long v) {
     atomicAdd((unsigned long long*)p, (unsigned long long)v);       // two's complement: wraps correctly for negative sums
 }
 
+// A (sum, sum of squares) pair in fixed point, and the ONE emission of it into dst[0..1] (an LDS accumulator or gstat); zeros cost no
+// atomic.  (Values first, destination second: arguments are evaluated in that order, conversion before address, and the compiler's output
+// for the GEMM / conv epilogues follows the source order - the other way round their code changes.)
+struct GnFixed { long long a, q; };
+__device__ __forceinline__ GnFixed gn_fixed(float sm, float sq) { return GnFixed{__float2ll_rn(sm * GN_FIX_SUM), __float2ll_rn(sq * GN_FIX_SQ)}; }
+__device__ __forceinline__ void gn_add_pair(const GnFixed v, long long* dst) {
+    if (v.a) gn_atomic_add(dst, v.a);
+    if (v.q) gn_atomic_add(dst + 1, v.q);
+}
+
 // sum over the 16 lanes of a DPP row (lanes that share lane >> 4), result in every lane of the row; fixed order: deterministic
 __device__ __forceinline__ float dpp_row_sum(float v) {
 #define MKD_DPP_ADD(ctrl) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xF, 0xF, true))
@@ -128,12 +138,8 @@ __device__ __forceinline__ void gn_acc_flush(const long long* acc, int nseg, int
 #ifdef MKD_EXP_NO_FLUSH
     return;
 #endif
-    for (int i = tid; i < nseg * ngl; i += nthreads) {
-        const long long a = acc[i * 2], q = acc[i * 2 + 1];
-        long long* dst = gstat + ((size_t)(b_first + i / ngl) * GN_GROUPS + g_first + i % ngl) * 2;
-        if (a) gn_atomic_add(dst, a);
-        if (q) gn_atomic_add(dst + 1, q);
-    }
+    for (int i = tid; i < nseg * ngl; i += nthreads)
+        gn_add_pair(GnFixed{acc[i * 2], acc[i * 2 + 1]}, gstat + ((size_t)(b_first + i / ngl) * GN_GROUPS + g_first + i % ngl) * 2);
 }
 
 // Column statistics of one output tile that the workgroup has staged in LDS as bf16 [rows][TS] (exactly the values it
@@ -164,10 +170,7 @@ __device__ __forceinline__ void gn_tile_stats(const uint16_t* tile, int TS, int 
             int left = seg_period - (phase0 + lr0 - seg * seg_period);
             float sm = 0.f, sq = 0.f;
             auto flush = [&]() {
-                const long long a = __float2ll_rn(sm * GN_FIX_SUM), q = __float2ll_rn(sq * GN_FIX_SQ);
-                long long* dst = use_lds ? acc + (size_t)(seg * ngl + gl) * 2 : gstat + ((size_t)(b_first + seg) * GN_GROUPS + g_first + gl) * 2;
-                if (a) gn_atomic_add(dst, a);
-                if (q) gn_atomic_add(dst + 1, q);
+                gn_add_pair(gn_fixed(sm, sq), use_lds ? acc + (size_t)(seg * ngl + gl) * 2 : gstat + ((size_t)(b_first + seg) * GN_GROUPS + g_first + gl) * 2);
             };
             for (int lr = lr0; lr < lr1; ++lr) {
                 const float v = bf16_to_f32(tile[lr * TS + c]);
@@ -179,12 +182,7 @@ __device__ __forceinline__ void gn_tile_stats(const uint16_t* tile, int TS, int 
     }
     if (use_lds) {
         __syncthreads();
-        for (int i = tid; i < nseg * ngl; i += nthreads) {
-            const long long a = acc[i * 2], q = acc[i * 2 + 1];
-            long long* dst = gstat + ((size_t)(b_first + i / ngl) * GN_GROUPS + g_first + i % ngl) * 2;
-            if (a) gn_atomic_add(dst, a);
-            if (q) gn_atomic_add(dst + 1, q);
-        }
+        gn_acc_flush(acc, nseg, ngl, b_first, g_first, tid, nthreads, gstat);
     }
 }
 

@@ -842,10 +842,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_gn_kernel(const GemmArgs2
         int gl = (p.gn_coff + n) / cg - g_first, left = cg - (p.gn_coff + n - (g_first + gl) * cg);
         float sm = 0.f, sq = 0.f;
         auto flush = [&]() {
-            const long long a = __float2ll_rn(sm * GN_FIX_SUM), q = __float2ll_rn(sq * GN_FIX_SQ);
-            long long* dst = use_lds ? acc + (size_t)((b - b_first) * ngl + gl) * 2 : p.gn_stat + ((size_t)b * GN_GROUPS + g_first + gl) * 2;
-            if (a) gn_atomic_add(dst, a);
-            if (q) gn_atomic_add(dst + 1, q);
+            gn_add_pair(gn_fixed(sm, sq), use_lds ? acc + (size_t)((b - b_first) * ngl + gl) * 2 : p.gn_stat + ((size_t)b * GN_GROUPS + g_first + gl) * 2);
         };
 #pragma unroll
         for (int j = 0; j < 4; ++j) {

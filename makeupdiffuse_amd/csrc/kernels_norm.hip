@@ -9,10 +9,11 @@
 // LayerNorm: one 64-lane wavefront per row, row kept in registers, wave-shuffle reductions.
 #include "mkd_common.h"
 #include <cstdlib>
+#include <type_traits>
 #include "gemm_device.h"
 
 namespace {
-using mkdk::GN_FIX_SUM; using mkdk::GN_FIX_SQ; using mkdk::GN_GROUPS; using mkdk::gn_atomic_add;
+using mkdk::GN_FIX_SUM; using mkdk::GN_FIX_SQ; using mkdk::GN_GROUPS; using mkdk::gn_fixed; using mkdk::gn_add_pair; using mkdk::gn_acc_flush;
 
 constexpr int GN_MAX_GROUPS = 32;
 
@@ -20,6 +21,96 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+
+// ---- the register arithmetic of every GroupNorm kernel: one copy of each step.  WHEN a kernel loads (how many loads are in flight,
+// what is issued before which barrier) stays written out in the kernels: that was found in the ISA and measured per kernel.  Two
+// kernels keep steps spelled out because the compiler's output for them changes through the helpers (comments at the sites):
+// gn_apply_kernel its scale / shift, gn_slab_kernel its affine load, statistics fold and scale / shift. ----
+
+// one 16-byte vector into the thread's per-channel sums
+__device__ __forceinline__ void gn_accumulate(const U16x8& d, float (&sum)[8], float (&sq)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { const float f = bf16_to_f32(d.v[j]); sum[j] += f; sq[j] += f * f; }
+}
+
+// gamma / beta of the thread's 8 channels [c, c + 8) (a block-uniform part of the offset belongs into the pointers: scalar arithmetic)
+__device__ __forceinline__ void gn_load_affine(const float* gamma, const float* beta, int c, float (&pg)[8], float (&pb)[8]) {
+    const f32x4 g0 = *(const f32x4*)(gamma + c), g1 = *(const f32x4*)(gamma + c + 4);
+    const f32x4 b0 = *(const f32x4*)(beta + c), b1 = *(const f32x4*)(beta + c + 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { pg[j] = g0[j]; pg[4 + j] = g1[j]; pb[j] = b0[j]; pb[4 + j] = b1[j]; }
+}
+
+// (sum, sum of squares) of n values -> mean, 1 / sqrt(var + eps); rounding can leave a tiny negative variance
+struct GnMeanRstd { float mean, rstd; };
+__device__ __forceinline__ GnMeanRstd gn_mean_rstd(float s, float q, float n, float eps) {
+    const float mean = s / n;
+    float var = q / n - mean * mean;
+    var = var < 0.f ? 0.f : var;
+    return GnMeanRstd{mean, rsqrtf(var + eps)};
+}
+
+// y = x * sa + sb of the thread's channels [c, c + 8) (c counted from the first channel of the first group of the lookups):
+// mean_of(g), rstd_of(g) read group g's statistics from wherever the kernel keeps them
+template <class MeanOf, class RstdOf>
+__device__ __forceinline__ void gn_scale_shift(const float (&pg)[8], const float (&pb)[8], int c, int cg, MeanOf mean_of, RstdOf rstd_of,
+                                               float (&sa)[8], float (&sb)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int g = (c + j) / cg;
+        const float a = pg[j] * rstd_of(g);
+        sa[j] = a;
+        sb[j] = pb[j] - mean_of(g) * a;
+    }
+}
+
+// one vector -> row r of y (row stride ld).  (Row and stride, not the address: an argument is evaluated before the call, and with the
+// address computed ahead of the arithmetic the compiler schedules the register-resident kernels differently.)
+__device__ __forceinline__ void gn_apply_store(const U16x8& d, const float (&sa)[8], const float (&sb)[8], int silu, bf16_t* y, int r, int ld) {
+    U16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float f = bf16_to_f32(d.v[j]) * sa[j] + sb[j];
+        if (silu) f = silu_f(f);
+        o.v[j] = f32_to_bf16(f);
+    }
+    *(U16x8*)(y + (size_t)r * ld) = o;
+}
+
+// Group statistics straight from the registers of a block that owns `gpb` groups of cg >= 8 channels (thread: vector v of the block's
+// channels, `active` or idle): a thread's 8 channels touch at most two groups; per group a masked butterfly over the wave, then a
+// fixed-order sum over the waves - deterministic, and the SAME order in gn_fused_kernel and gn_slab_kernel (their results must agree
+// bit for bit).  s_red: 2 * gpb floats per wave; gstat[gpb][2] receives mean, rstd.  Must be called by ALL threads of the block (two
+// barriers inside; gstat is valid after it returns).
+__device__ __forceinline__ void gn_register_stats(const float (&sum)[8], const float (&sq)[8], bool active, int v, int cg, int gpb, int hw,
+                                                  float eps, float* s_red, float* gstat) {
+    const int tid = threadIdx.x;
+    const int gA = (v * 8) / cg;
+    const int split = min(8, (gA + 1) * cg - v * 8);          // channels [0, split) belong to gA, the rest to gA + 1
+    float a0 = 0.f, q0 = 0.f, a1 = 0.f, q1 = 0.f;
+    if (active) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (j < split) { a0 += sum[j]; q0 += sq[j]; } else { a1 += sum[j]; q1 += sq[j]; }
+        }
+    }
+    const int nw = (int)blockDim.x >> 6, wv = tid >> 6;
+    for (int g = 0; g < gpb; ++g) {
+        float sg = (gA == g ? a0 : 0.f) + (gA + 1 == g ? a1 : 0.f);
+        float qg = (gA == g ? q0 : 0.f) + (gA + 1 == g ? q1 : 0.f);
+        sg = wave_sum(sg); qg = wave_sum(qg);
+        if ((tid & 63) == 0) { s_red[(wv * gpb + g) * 2] = sg; s_red[(wv * gpb + g) * 2 + 1] = qg; }
+    }
+    __syncthreads();
+    if (tid < gpb) {
+        float a = 0.f, q = 0.f;
+        for (int k = 0; k < nw; ++k) { a += s_red[(k * gpb + tid) * 2]; q += s_red[(k * gpb + tid) * 2 + 1]; }
+        const GnMeanRstd m = gn_mean_rstd(a, q, (float)hw * (float)cg, eps);
+        gstat[tid * 2] = m.mean;
+        gstat[tid * 2 + 1] = m.rstd;
+    }
+    __syncthreads();
 }
 
 // threads = V * P where V = C/8 vectors per pixel (thread's vector id = tid % V, fixed).
@@ -40,14 +131,7 @@ __global__ void gn_stats_kernel(const bf16_t* __restrict__ x, int ld, int hw, in
 #pragma unroll
     for (int j = 0; j < 8; ++j) { sum[j] = 0.f; sq[j] = 0.f; }
     const bf16_t* base = x + (size_t)b * hw * ld + v * 8;
-    for (int r = r0 + pl; r < r1; r += P) {
-        const U16x8 d = *(const U16x8*)(base + (size_t)r * ld);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float f = bf16_to_f32(d.v[j]);
-            sum[j] += f; sq[j] += f * f;
-        }
-    }
+    for (int r = r0 + pl; r < r1; r += P) gn_accumulate(*(const U16x8*)(base + (size_t)r * ld), sum, sq);
     float* ssum = s_part;
     float* ssq = s_part + T * 8;
 #pragma unroll
@@ -84,14 +168,13 @@ __global__ void gn_apply_kernel(const bf16_t* __restrict__ x, int ld_in, bf16_t*
             const float* pp = partials + ((size_t)(b * nchunks + c) * groups + tid) * 2;
             s += pp[0]; q += pp[1];
         }
-        const float n = (float)hw * (float)(C / groups);
-        const float mean = s / n;
-        float var = q / n - mean * mean;
-        var = var < 0.f ? 0.f : var;
-        s_mean[tid] = mean;
-        s_rstd[tid] = rsqrtf(var + eps);
+        const GnMeanRstd m = gn_mean_rstd(s, q, (float)hw * (float)(C / groups), eps);
+        s_mean[tid] = m.mean;
+        s_rstd[tid] = m.rstd;
     }
     __syncthreads();
+    // (gn_scale_shift's arithmetic left spelled out: here gamma / beta are read behind the barrier, channel by channel between the LDS
+    // lookups; through gn_load_affine + gn_scale_shift all 16 loads move ahead of the lookups and the kernel's schedule changes)
     const int cg = C / groups;
     float sa[8], sb[8];
 #pragma unroll
@@ -106,17 +189,7 @@ __global__ void gn_apply_kernel(const bf16_t* __restrict__ x, int ld_in, bf16_t*
     const int r1 = min(hw, r0 + rows_per_chunk);
     const bf16_t* xin = x + (size_t)b * hw * ld_in + v * 8;
     bf16_t* yout = y + (size_t)b * hw * ld_out + v * 8;
-    for (int r = r0 + pl; r < r1; r += P) {
-        const U16x8 d = *(const U16x8*)(xin + (size_t)r * ld_in);
-        U16x8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float f = bf16_to_f32(d.v[j]) * sa[j] + sb[j];
-            if (silu) f = silu_f(f);
-            o.v[j] = f32_to_bf16(f);
-        }
-        *(U16x8*)(yout + (size_t)r * ld_out) = o;
-    }
+    for (int r = r0 + pl; r < r1; r += P) gn_apply_store(*(const U16x8*)(xin + (size_t)r * ld_in), sa, sb, silu, yout, r, ld_out);
 }
 
 // Single-launch GroupNorm: one workgroup per (sample, chunk of `gpb` groups whose channel span is a multiple
@@ -162,10 +235,7 @@ __global__ __launch_bounds__(NV == 16 ? 512 : 1024) void gn_fused_kernel(const P
 #pragma unroll
             for (int i = 0; i < NR; ++i) {
                 const int r = pl + i * P;
-                if (r < hw) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) { const float f = bf16_to_f32(keep[i].v[j]); sum[j] += f; sq[j] += f * f; }
-                }
+                if (r < hw) gn_accumulate(keep[i], sum, sq);
             }
         } else {
             int r = pl;
@@ -174,28 +244,19 @@ __global__ __launch_bounds__(NV == 16 ? 512 : 1024) void gn_fused_kernel(const P
 #pragma unroll
                 for (int u = 0; u < 4; ++u) d[u] = *(const U16x8*)(xin + (size_t)(r + u * P) * ld_in);
 #pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) { const float f = bf16_to_f32(d[u].v[j]); sum[j] += f; sq[j] += f * f; }
+                for (int u = 0; u < 4; ++u) gn_accumulate(d[u], sum, sq);
             }
-            for (; r < hw; r += P) {
-                const U16x8 d = *(const U16x8*)(xin + (size_t)r * ld_in);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { const float f = bf16_to_f32(d.v[j]); sum[j] += f; sq[j] += f * f; }
-            }
+            for (; r < hw; r += P) gn_accumulate(*(const U16x8*)(xin + (size_t)r * ld_in), sum, sq);
         }
     }
     // gamma / beta of this thread's 8 channels: fetched now, next to the slab loads, not after the statistics barriers - except in the
-    // 1024-thread instantiation (64 registers per thread: with its 8 slab vectors in flight at once they would spill), which fetches
+    // 1024-thread instantiation (128 registers per thread: with its 8 slab vectors in flight at once they would spill), which fetches
     // them behind the statistics
     constexpr bool AFFINE_EARLY = NV != 8;
     float pg[8], pb[8];
-    auto load_affine = [&]() {
-        const f32x4 g0 = *(const f32x4*)(gamma + c0 + v * 8), g1 = *(const f32x4*)(gamma + c0 + v * 8 + 4);
-        const f32x4 b0 = *(const f32x4*)(beta + c0 + v * 8), b1 = *(const f32x4*)(beta + c0 + v * 8 + 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { pg[j] = g0[j]; pg[4 + j] = g1[j]; pb[j] = b0[j]; pb[4 + j] = b1[j]; }
-    };
+    // (a lambda around the helper, not two direct calls: the compiler inlines a lambda after it has optimised it on its own, a
+    // __forceinline__ function before - and with the latter the schedule of the slab loads above changes in all four instantiations)
+    auto load_affine = [&]() { gn_load_affine(gamma + c0, beta + c0, v * 8, pg, pb); };
     if (AFFINE_EARLY && active) load_affine();
     float* ssum = s_red;                      // [NT][8]
     float* ssq = s_red + NT * 8;              // [NT][8]
@@ -203,36 +264,7 @@ __global__ __launch_bounds__(NV == 16 ? 512 : 1024) void gn_fused_kernel(const P
     float* csq = csum + nch;
     float* gstat = csq + nch;                 // [gpb][2] mean, rstd
     if (cg >= 8) {
-        // Group statistics straight from the registers (block-uniform branch): a thread's 8 channels touch at most two groups;
-        // per group a masked butterfly over the wave, then a fixed-order sum over the waves - two barriers, deterministic.
-        const int gA = (v * 8) / cg;
-        const int split = min(8, (gA + 1) * cg - v * 8);          // channels [0, split) belong to gA, the rest to gA + 1
-        float a0 = 0.f, q0 = 0.f, a1 = 0.f, q1 = 0.f;
-        if (active) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                if (j < split) { a0 += sum[j]; q0 += sq[j]; } else { a1 += sum[j]; q1 += sq[j]; }
-            }
-        }
-        const int nw = NT >> 6, wv = tid >> 6;
-        for (int g = 0; g < gpb; ++g) {
-            float sg = (gA == g ? a0 : 0.f) + (gA + 1 == g ? a1 : 0.f);
-            float qg = (gA == g ? q0 : 0.f) + (gA + 1 == g ? q1 : 0.f);
-            sg = wave_sum(sg); qg = wave_sum(qg);
-            if ((tid & 63) == 0) { s_red[(wv * gpb + g) * 2] = sg; s_red[(wv * gpb + g) * 2 + 1] = qg; }
-        }
-        __syncthreads();
-        if (tid < gpb) {
-            float a = 0.f, q = 0.f;
-            for (int k = 0; k < nw; ++k) { a += s_red[(k * gpb + tid) * 2]; q += s_red[(k * gpb + tid) * 2 + 1]; }
-            const float n = (float)hw * (float)cg;
-            const float mean = a / n;
-            float var = q / n - mean * mean;
-            var = var < 0.f ? 0.f : var;
-            gstat[tid * 2] = mean;
-            gstat[tid * 2 + 1] = rsqrtf(var + eps);
-        }
-        __syncthreads();
+        gn_register_stats(sum, sq, active, v, cg, gpb, hw, eps, s_red, gstat);          // (block-uniform branch)
     } else {
     if (active) {
 #pragma unroll
@@ -254,42 +286,22 @@ __global__ __launch_bounds__(NV == 16 ? 512 : 1024) void gn_fused_kernel(const P
     if (tid < gpb) {
         float a = 0.f, q = 0.f;
         for (int c = tid * cg; c < (tid + 1) * cg; ++c) { a += csum[c]; q += csq[c]; }
-        const float n = (float)hw * (float)cg;
-        const float mean = a / n;
-        float var = q / n - mean * mean;
-        var = var < 0.f ? 0.f : var;
-        gstat[tid * 2] = mean;
-        gstat[tid * 2 + 1] = rsqrtf(var + eps);
+        const GnMeanRstd m = gn_mean_rstd(a, q, (float)hw * (float)cg, eps);
+        gstat[tid * 2] = m.mean;
+        gstat[tid * 2 + 1] = m.rstd;
     }
     __syncthreads();
     }
     if (!active) return;
     if (!AFFINE_EARLY) load_affine();
     float sa[8], sb[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int cl = v * 8 + j;
-        const int g = cl / cg;
-        const float a = pg[j] * gstat[g * 2 + 1];
-        sa[j] = a;
-        sb[j] = pb[j] - gstat[g * 2] * a;
-    }
+    gn_scale_shift(pg, pb, v * 8, cg, [&](int g) { return gstat[g * 2]; }, [&](int g) { return gstat[g * 2 + 1]; }, sa, sb);
     bf16_t* yout = y + (size_t)b * hw * ld_out + c0 + v * 8;
-    auto apply_store = [&](const U16x8& d, int r) {
-        U16x8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float f = bf16_to_f32(d.v[j]) * sa[j] + sb[j];
-            if (silu) f = silu_f(f);
-            o.v[j] = f32_to_bf16(f);
-        }
-        *(U16x8*)(yout + (size_t)r * ld_out) = o;
-    };
     if (NV > 0) {
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
             const int r = pl + i * P;
-            if (r < hw) apply_store(keep[i], r);
+            if (r < hw) gn_apply_store(keep[i], sa, sb, silu, yout, r, ld_out);
         }
     } else {
         int r = pl;
@@ -298,9 +310,9 @@ __global__ __launch_bounds__(NV == 16 ? 512 : 1024) void gn_fused_kernel(const P
 #pragma unroll
             for (int u = 0; u < 4; ++u) d[u] = *(const U16x8*)(xin + (size_t)(r + u * P) * ld_in);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) apply_store(d[u], r + u * P);
+            for (int u = 0; u < 4; ++u) gn_apply_store(d[u], sa, sb, silu, yout, r + u * P, ld_out);
         }
-        for (; r < hw; r += P) apply_store(*(const U16x8*)(xin + (size_t)r * ld_in), r);
+        for (; r < hw; r += P) gn_apply_store(*(const U16x8*)(xin + (size_t)r * ld_in), sa, sb, silu, yout, r, ld_out);
     }
 }
 
@@ -381,13 +393,15 @@ __global__ __launch_bounds__(512) void gn_slab_kernel(const Pair<SlabGn> ag, con
                 for (int j = 0; j < 4; ++j) { o.v[j] = f32_to_bf16(lo[j]); o.v[4 + j] = f32_to_bf16(hi[j]); }
                 keep[i] = o;
                 if (a.raw) *(U16x8*)(a.raw + m * a.ldraw + n) = o;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { const float f = bf16_to_f32(o.v[j]); sum[j] += f; sq[j] += f * f; }
+                gn_accumulate(o, sum, sq);
             }
         }
     }
     float* gstat = s_red + 2 * (NT >> 6) * gpb;          // [gpb][2] mean, rstd (after the per-wave partials)
-    {   // group statistics straight from the registers (cg >= 8): as gn_fused_kernel
+    {   // gn_register_stats, gn_load_affine (above) and gn_scale_shift (below) SPELLED OUT: this kernel sits at 136 - 232 registers, and through
+        // the helpers the compiler allocates and schedules all three instantiations differently (the same instructions, another order).
+        // The block must stay gn_register_stats line for line - same butterfly, same order over the waves: the results have to be
+        // bit-identical to gn_fused_kernel's (test_splitk_conv_feeds_groupnorm_from_its_slabs).
         const int gA = (v * 8) / cg;
         const int split = min(8, (gA + 1) * cg - v * 8);
         float a0 = 0.f, q0 = 0.f, a1 = 0.f, q1 = 0.f;
@@ -430,16 +444,7 @@ __global__ __launch_bounds__(512) void gn_slab_kernel(const Pair<SlabGn> ag, con
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int r = pl + i * P;
-        if (r < hw) {
-            U16x8 o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float f = bf16_to_f32(keep[i].v[j]) * sa[j] + sb[j];
-                if (silu) f = silu_f(f);
-                o.v[j] = f32_to_bf16(f);
-            }
-            *(U16x8*)(yout + (size_t)r * ld_out) = o;
-        }
+        if (r < hw) gn_apply_store(keep[i], sa, sb, silu, yout, r, ld_out);
     }
 }
 
@@ -467,12 +472,7 @@ __global__ __launch_bounds__(320) void gn_apply_stats_kernel(const bf16_t* __res
     }
     const int v = tid % V, pl = tid / V;
     float pg[8], pb[8];
-    {
-        const f32x4 g0 = *(const f32x4*)(gamma + v * 8), g1 = *(const f32x4*)(gamma + v * 8 + 4);
-        const f32x4 b0 = *(const f32x4*)(beta + v * 8), b1 = *(const f32x4*)(beta + v * 8 + 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { pg[j] = g0[j]; pg[4 + j] = g1[j]; pb[j] = b0[j]; pb[4 + j] = b1[j]; }
-    }
+    gn_load_affine(gamma, beta, v * 8, pg, pb);
     const int r0 = blockIdx.x * rows_per_block;
     const int r1 = min(hw, r0 + rows_per_block);
     const bf16_t* xin = x + (size_t)b * hw * ld_in + v * 8;
@@ -489,27 +489,11 @@ __global__ __launch_bounds__(320) void gn_apply_stats_kernel(const bf16_t* __res
     __syncthreads();
     if (pl >= P) return;
     float sa[8], sb[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int g = (v * 8 + j) / cg;
-        const float a = pg[j] * s_rstd[g];
-        sa[j] = a;
-        sb[j] = pb[j] - s_mean[g] * a;
-    }
-    auto apply_store = [&](const U16x8& in, int row) {
-        U16x8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float f = bf16_to_f32(in.v[j]) * sa[j] + sb[j];
-            if (silu) f = silu_f(f);
-            o.v[j] = f32_to_bf16(f);
-        }
-        *(U16x8*)(yout + (size_t)row * ld_out) = o;
-    };
+    gn_scale_shift(pg, pb, v * 8, cg, [&](int g) { return s_mean[g]; }, [&](int g) { return s_rstd[g]; }, sa, sb);
     for (; r < r1; r += U * P) {
 #pragma unroll
         for (int u = 0; u < U; ++u)
-            if (r + u * P < r1) apply_store(d[u], r + u * P);
+            if (r + u * P < r1) gn_apply_store(d[u], sa, sb, silu, yout, r + u * P, ld_out);
         const int rn = r + U * P;
 #pragma unroll
         for (int u = 0; u < U; ++u)
@@ -540,28 +524,16 @@ __global__ __launch_bounds__(320) void gn_colstats_kernel(const bf16_t* __restri
         float sm[8], sq[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) { sm[j] = 0.f; sq[j] = 0.f; }
-        for (int r = r0 + pl; r < r1; r += P) {          // all rows of a block belong to sample b
-            const U16x8 d = *(const U16x8*)(base + (size_t)r * ld);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { const float f = bf16_to_f32(d.v[j]); sm[j] += f; sq[j] += f * f; }
-        }
+        for (int r = r0 + pl; r < r1; r += P) gn_accumulate(*(const U16x8*)(base + (size_t)r * ld), sm, sq);          // all rows of a block belong to sample b
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int gl = (coff + v * 8 + j) / cg - g_first;
-            const long long a = __float2ll_rn(sm[j] * GN_FIX_SUM), q = __float2ll_rn(sq[j] * GN_FIX_SQ);
-            long long* dst = use_lds ? acc + (size_t)gl * 2 : gstat + ((size_t)b * GN_GROUPS + g_first + gl) * 2;
-            if (a) gn_atomic_add(dst, a);
-            if (q) gn_atomic_add(dst + 1, q);
+            gn_add_pair(gn_fixed(sm[j], sq[j]), use_lds ? acc + (size_t)gl * 2 : gstat + ((size_t)b * GN_GROUPS + g_first + gl) * 2);
         }
     }
     if (use_lds) {
         __syncthreads();
-        for (int i = tid; i < ngl; i += blockDim.x) {
-            const long long a = acc[i * 2], q = acc[i * 2 + 1];
-            long long* dst = gstat + ((size_t)b * GN_GROUPS + g_first + i) * 2;
-            if (a) gn_atomic_add(dst, a);
-            if (q) gn_atomic_add(dst + 1, q);
-        }
+        gn_acc_flush(acc, 1, ngl, b, g_first, tid, blockDim.x, gstat);          // one segment: the block's sample
     }
 }
 
@@ -651,6 +623,63 @@ int gn_chunks(int hw) {
     return n;
 }
 
+// Geometry of the two-kernel path, the same for its two launches: threads = V * P (V = C / 8 vectors per pixel, P pixel lanes), grid
+// (nchunks, batch), every block walks rows_per_chunk pixels.
+struct GnChunkShape { int threads, nchunks, rows_per_chunk; };
+
+int gn_chunk_shape(int hw, int C, GnChunkShape* s) {
+    const int V = C / 8;
+    if (V > 1024) return mkd_fail(-4, "groupnorm: C > 8192 unsupported");
+    int P = 256 / V;
+    if (P < 1) P = 1;
+    s->threads = V * P;
+    s->nchunks = gn_chunks(hw);
+    s->rows_per_chunk = (hw + s->nchunks - 1) / s->nchunks;
+    return 0;
+}
+
+int gn_stats_launch(const bf16_t* x, int ld_in, int batch, int hw, int C, int groups, float* partials, const GnChunkShape& s, hipStream_t stream) {
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(s.nchunks, batch), dim3(s.threads), (size_t)s.threads * 16 * sizeof(float), stream, x, ld_in, hw, C, groups,
+                       s.rows_per_chunk, partials);
+    MKD_LAUNCH_CHECK("gn_stats_kernel");
+    return 0;
+}
+
+// Geometry of the single-launch kernels (gn_fused_kernel, gn_slab_kernel; ONE selection: the slab-fed kernel must be bit-identical to
+// split-K reduce + mkd_groupnorm, so both have to pick the same block for the same shape).  One block per (sample, chunk of gpb groups):
+// the smallest chunk whose channel span is a multiple of 8.  nt threads, each holding `per` rows of its 8 channels: the smallest of 256 /
+// 512 threads with <= 16 vectors per thread.  `wide` (gn_fused_kernel only) adds 1024 threads with <= 8 vectors (128 registers per
+// thread: 16 loads in flight would spill) and, past that, the streaming form (per > 16 -> NV == 0); without it the kernel also keeps
+// its statistics in registers, which needs cg >= 8 (smaller groups keep the two kernels).
+struct GnBlockShape { int gpb, nt, per; };
+
+bool gn_block_shape(int hw, int C, int groups, bool wide, GnBlockShape* s) {
+    if (groups <= 0 || C % groups) return false;
+    const int cg = C / groups;
+    if (!wide && cg < 8) return false;
+    int gpb = 1;
+    while (gpb <= groups && ((gpb * cg) % 8 || groups % gpb)) ++gpb;
+    if (gpb > groups) return false;
+    const int V = gpb * cg / 8;
+    if (V > 256) return false;                                  // (V <= 256 <= blockDim)
+    auto per_of = [&](int t) { const int P = t / V; return (hw + P - 1) / P; };
+    if (per_of(256) <= 16) *s = GnBlockShape{gpb, 256, per_of(256)};
+    else if (per_of(512) <= 16) *s = GnBlockShape{gpb, 512, per_of(512)};
+    else if (!wide) return false;
+    else if (per_of(1024) <= 8) *s = GnBlockShape{gpb, 1024, per_of(1024)};
+    else *s = GnBlockShape{gpb, 256, 1 << 20};
+    return true;
+}
+
+// the ONE dispatch on the vectors a thread keeps: launch(integral_constant<int, NV>) with NV = 4 / 8 / 16, or 0 (streaming)
+template <class F>
+void gn_dispatch_nv(int per, F&& launch) {
+    if (per <= 4) launch(std::integral_constant<int, 4>{});
+    else if (per <= 8) launch(std::integral_constant<int, 8>{});
+    else if (per <= 16) launch(std::integral_constant<int, 16>{});
+    else launch(std::integral_constant<int, 0>{});
+}
+
 }  // namespace
 
 size_t groupnorm_partials_bytes(int batch, int hw, int groups) {
@@ -662,17 +691,10 @@ size_t groupnorm_partials_bytes(int batch, int hw, int groups) {
 int launch_gn_stats(const bf16_t* x, int ld_in, int batch, int hw, int C, int groups, float* partials, hipStream_t stream, int* nchunks_out) {
     if (C % 8 || ld_in % 8 || groups <= 0 || groups > GN_MAX_GROUPS || C % groups) return mkd_fail(-1, "gn_stats: bad geometry");
     if (!partials) return mkd_fail(-1, "gn_stats: partials workspace missing");
-    const int V = C / 8;
-    if (V > 1024) return mkd_fail(-4, "groupnorm: C > 8192 unsupported");
-    int P = 256 / V;
-    if (P < 1) P = 1;
-    const int threads = V * P;
-    const int nchunks = gn_chunks(hw);
-    const int rows_per_chunk = (hw + nchunks - 1) / nchunks;
-    dim3 grid(nchunks, batch);
-    hipLaunchKernelGGL(gn_stats_kernel, grid, dim3(threads), (size_t)threads * 16 * sizeof(float), stream, x, ld_in, hw, C, groups, rows_per_chunk, partials);
-    MKD_LAUNCH_CHECK("gn_stats_kernel");
-    if (nchunks_out) *nchunks_out = nchunks;
+    GnChunkShape s;
+    int rc = gn_chunk_shape(hw, C, &s); if (rc) return rc;
+    rc = gn_stats_launch(x, ld_in, batch, hw, C, groups, partials, s, stream); if (rc) return rc;
+    if (nchunks_out) *nchunks_out = s.nchunks;
     return 0;
 }
 
@@ -685,82 +707,34 @@ int launch_groupnorm(const bf16_t* x, int ld_in, const float* gamma, const float
     MKD_PAIR_SET2(io, second ? *second : io.g[0]);
     if (groups > GN_MAX_GROUPS || groups <= 0 || C % groups) return mkd_fail(-1, "groupnorm: bad group count");
     if (!partials) return mkd_fail(-1, "groupnorm: partials workspace missing");
-    // single-launch path: smallest group chunk whose channel span is a multiple of 8, slab small enough to
-    // be re-read from cache
-    {
-        const int cg = C / groups;
-        int gpb = 1;
-        while (gpb <= groups && ((gpb * cg) % 8 || groups % gpb)) ++gpb;
-        if (gpb <= groups) {
-            const int nch = gpb * cg;
-            const size_t slab = (size_t)hw * nch * sizeof(bf16_t);
-            if (nch / 8 <= 256 && slab <= (size_t)384 * 1024 && hw < two_kernel_min_hw) {   // (V <= 256 <= blockDim)
-                // smallest block (256..1024 threads) whose threads hold their whole share in <= 16 registers-vectors
-                const int V = nch / 8;
-                // 256 / 512 threads with <= 16 vectors per thread, or 1024 threads with <= 8 (register budget);
-                // otherwise the streaming two-pass variant
-                int nt = 256, per = 0;
-                auto per_of = [&](int t) { const int P = t / V; return (hw + P - 1) / P; };
-                if (per_of(256) <= 16) { nt = 256; per = per_of(256); }
-                else if (per_of(512) <= 16) { nt = 512; per = per_of(512); }
-                else if (per_of(1024) <= 8) { nt = 1024; per = per_of(1024); }
-                else { nt = 256; per = 1 << 20; }
-                const size_t lds = (size_t)(2 * nt * 8 + 2 * nch + 2 * gpb) * sizeof(float);
-                dim3 grid(groups / gpb, batch, second ? 2 : 1);
-#define MKD_GN_LAUNCH(NVV)                                                                                              \
-    hipLaunchKernelGGL(gn_fused_kernel<NVV>, grid, dim3(nt), lds, stream, io, ld_in, ld_out, eps, silu, hw, C, groups, gpb)
-                if (per <= 4) MKD_GN_LAUNCH(4);
-                else if (per <= 8) MKD_GN_LAUNCH(8);
-                else if (per <= 16) MKD_GN_LAUNCH(16);
-                else MKD_GN_LAUNCH(0);
-#undef MKD_GN_LAUNCH
-                MKD_LAUNCH_CHECK("gn_fused_kernel");
-                return 0;
-            }
-        }
+    // single-launch path: the block's slab small enough to be re-read from cache
+    GnBlockShape bs;
+    if (gn_block_shape(hw, C, groups, true, &bs) && (size_t)hw * bs.gpb * (C / groups) * sizeof(bf16_t) <= (size_t)384 * 1024 && hw < two_kernel_min_hw) {
+        const size_t lds = (size_t)(2 * bs.nt * 8 + 2 * bs.gpb * (C / groups) + 2 * bs.gpb) * sizeof(float);
+        const dim3 grid(groups / bs.gpb, batch, second ? 2 : 1);
+        gn_dispatch_nv(bs.per, [&](auto nv) {
+            hipLaunchKernelGGL(gn_fused_kernel<decltype(nv)::value>, grid, dim3(bs.nt), lds, stream, io, ld_in, ld_out, eps, silu, hw, C, groups, bs.gpb);
+        });
+        MKD_LAUNCH_CHECK("gn_fused_kernel");
+        return 0;
     }
     if (second) {          // the two-kernel path is not grouped: one problem after the other (they share the partials workspace)
         int rc = launch_groupnorm(x, ld_in, gamma, beta, eps, silu, y, ld_out, batch, hw, C, groups, partials, stream, nullptr, two_kernel_min_hw);
         if (rc) return rc;
         return launch_groupnorm(second->x, ld_in, second->gamma, second->beta, eps, silu, second->y, ld_out, batch, hw, C, groups, partials, stream, nullptr, two_kernel_min_hw);
     }
-    int nchunks = 0;
-    int rc0 = launch_gn_stats(x, ld_in, batch, hw, C, groups, partials, stream, &nchunks);
-    if (rc0) return rc0;
-    const int V = C / 8;
-    int P = 256 / V;
-    if (P < 1) P = 1;
-    const int threads = V * P;
-    const int rows_per_chunk = (hw + nchunks - 1) / nchunks;
-    dim3 grid(nchunks, batch);
-    hipLaunchKernelGGL(gn_apply_kernel, grid, dim3(threads), 0, stream, x, ld_in, y, ld_out, gamma, beta, eps, silu,
-                       hw, C, groups, rows_per_chunk, nchunks, partials);
+    GnChunkShape s;
+    int rc = gn_chunk_shape(hw, C, &s); if (rc) return rc;
+    rc = gn_stats_launch(x, ld_in, batch, hw, C, groups, partials, s, stream); if (rc) return rc;
+    hipLaunchKernelGGL(gn_apply_kernel, dim3(s.nchunks, batch), dim3(s.threads), 0, stream, x, ld_in, y, ld_out, gamma, beta, eps, silu,
+                       hw, C, groups, s.rows_per_chunk, s.nchunks, partials);
     MKD_LAUNCH_CHECK("gn_apply_kernel");
     return 0;
 }
 
-// geometry of the slab-fed kernel: group chunk with a channel span that is a multiple of 8, at most 16 vectors per thread
-static bool gn_slab_shape(int hw, int C, int* gpb_out, int* nt_out, int* per_out) {
-    const int groups = 32;
-    if (C % groups) return false;
-    const int cg = C / groups;
-    if (cg < 8) return false;                                   // (register statistics path; smaller groups keep the two kernels)
-    int gpb = 1;
-    while (gpb <= groups && ((gpb * cg) % 8 || groups % gpb)) ++gpb;
-    if (gpb > groups) return false;
-    const int V = gpb * cg / 8;
-    if (V > 256) return false;
-    auto per_of = [&](int t) { const int P = t / V; return (hw + P - 1) / P; };
-    int nt, per;
-    if (per_of(256) <= 16) { nt = 256; per = per_of(256); }
-    else if (per_of(512) <= 16) { nt = 512; per = per_of(512); }
-    else return false;                     // (1024 threads would leave 128 registers for 16 slab loads in flight: spills)
-    *gpb_out = gpb; *nt_out = nt; *per_out = per;
-    return true;
-}
 bool gn_from_slabs_supported(int batch, int hw, int C) {
-    int gpb, nt, per;
-    return batch > 0 && C % 8 == 0 && gn_slab_shape(hw, C, &gpb, &nt, &per);
+    GnBlockShape bs;
+    return batch > 0 && C % 8 == 0 && gn_block_shape(hw, C, 32, false, &bs);
 }
 
 static int slab_args(const GemmArgs& a, int batch, int hw, int ld_out, SlabGn* out) {
@@ -776,8 +750,8 @@ static int slab_args(const GemmArgs& a, int batch, int hw, int ld_out, SlabGn* o
 
 int launch_gn_from_slabs(const GemmArgs& a, const float* gamma, const float* beta, float eps, int silu, bf16_t* y, int ld_out,
                          int batch, int hw, hipStream_t stream, const GemmArgs* a2, const NormIo* second) {
-    int gpb, nt, per;
-    if (!gn_slab_shape(hw, a.N, &gpb, &nt, &per)) return mkd_fail(-4, "gn_from_slabs: geometry does not fit the single-pass kernel");
+    GnBlockShape bs;
+    if (!gn_block_shape(hw, a.N, 32, false, &bs)) return mkd_fail(-4, "gn_from_slabs: geometry does not fit the single-pass kernel");
     if ((a2 != nullptr) != (second != nullptr)) return mkd_fail(-1, "gn_from_slabs: a grouped launch needs both the second GEMM and the second GroupNorm");
     Pair<SlabGn> sg;
     Pair<NormIo> io;
@@ -789,13 +763,12 @@ int launch_gn_from_slabs(const GemmArgs& a, const float* gamma, const float* bet
         rc = slab_args(*a2, batch, hw, ld_out, &sg.g[MKD_PAIR_N - 1]); if (rc) return rc;
         MKD_PAIR_SET2(io, *second);
     }
-    const size_t lds = (size_t)(2 * (nt / 64) * gpb + 2 * gpb) * sizeof(float);
-    dim3 grid(32 / gpb, batch, a2 ? 2 : 1);
-#define MKD_GNS_LAUNCH(NVV) hipLaunchKernelGGL(gn_slab_kernel<NVV>, grid, dim3(nt), lds, stream, sg, io, ld_out, eps, silu, hw, a.N, 32, gpb)
-    if (per <= 4) MKD_GNS_LAUNCH(4);
-    else if (per <= 8) MKD_GNS_LAUNCH(8);
-    else MKD_GNS_LAUNCH(16);
-#undef MKD_GNS_LAUNCH
+    const size_t lds = (size_t)(2 * (bs.nt / 64) * bs.gpb + 2 * bs.gpb) * sizeof(float);
+    const dim3 grid(32 / bs.gpb, batch, a2 ? 2 : 1);
+    gn_dispatch_nv(bs.per, [&](auto nv) {
+        if constexpr (decltype(nv)::value > 0)          // (per <= 16 without `wide`: there is no streaming slab kernel)
+            hipLaunchKernelGGL(gn_slab_kernel<decltype(nv)::value>, grid, dim3(bs.nt), lds, stream, sg, io, ld_out, eps, silu, hw, a.N, 32, bs.gpb);
+    });
     MKD_LAUNCH_CHECK("gn_slab_kernel");
     return 0;
 }

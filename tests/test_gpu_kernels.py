@@ -261,7 +261,11 @@ def test_conv3x3_lds_staged_tiles(cfg, B, H, W_, Cin, Cout, pad_ld, splitk):
                                                 # large tensors: ragged pixel counts, strided rows, every vector width
                                                 (4, 1024, 640, 1, 1e-5, 64), (4, 1024, 960, 1, 1e-5, 0), (8, 1024, 320, 1, 1e-5, 320),
                                                 (1, 1024, 2560, 0, 1e-6, 0), (3, 1600, 320, 1, 1e-5, 0), (2, 1024, 1920, 1, 1e-5, 0),
-                                                (5, 1032, 1280, 1, 1e-5, 0)])
+                                                (5, 1032, 1280, 1, 1e-5, 0),
+                                                # cg = 6 (< 8: the LDS tree, 4 groups per block, 3 vectors x 85 pixel lanes, ragged last row) with 4 / 16
+                                                # vectors per thread and streaming; the 1024-thread launch; the two-kernel path with cg < 8
+                                                (2, 100, 192, 1, 1e-5, 0), (2, 700, 192, 0, 1e-6, 8), (1, 3000, 192, 1, 1e-5, 0),
+                                                (1, 2724, 192, 1, 1e-5, 0), (1, 8200, 192, 1, 1e-5, 0)])
 def test_groupnorm(B, hw, C, silu, eps, pad):
     lib = L()
     g = torch.Generator().manual_seed(C + hw)
