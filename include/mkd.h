@@ -520,7 +520,7 @@ int mkd_hist_match(const float* dst, const float* ref, const uint8_t* mask_dst, 
                    int n, int H, int W, float* matched, uint8_t* tables, float* loss, int32_t* counts, void* scratch, void* stream);
 /* ---- the histogram-matching teacher: EleGANt's pseudo ground truth at warp weight alpha = 0 (reference teacher.py:96-112), i.e. the
  * region-wise histogram match of the source to the reference composed into one image.  BUILD-DEFINED: region priority, feather and
- * border rule below (the reference blends hard regions with a landmark warp that needs landmarks) ---- */
+ * border rule below.  The landmark-warped term (alpha > 0) is mkd_pgt_warp, applied to this image ---- */
 /* src [n, 3, H, W] fp32; masks uint8 [4][n][H][W] in the order lip, skin, eye_left, eye_right (non-zero = inside), tables uint8
  * [4][n][3][256] in the same order: the tables of ONE mkd_hist_match call of 4 n terms (term r n + b: dst = source b, ref = reference b
  * under region r's masks); strengths fp32 [n][4] in the same order, or NULL for all 1; out [n, 3, H, W] fp32 in [0, 1].
@@ -543,6 +543,42 @@ int mkd_pgt_compose(const float* src, const uint8_t* masks, const uint8_t* table
                     int feather, float* out, void* stream);
 /* Launches one mkd_pgt_compose call enqueues: 1. */
 int mkd_pgt_launches(void);
+/* ---- the landmark-warped term of the pseudo ground truth: EleGANt's AnnealingComposePGT (reference teacher.py:96-112) warps the
+ * reference onto the source through the 68 landmarks by a thin-plate spline and blends it in per region (EYE_ALPHA 0.8, SKIN_ALPHA 0.3,
+ * LIP_ALPHA 0.1).  BUILD-DEFINED (EleGANt's own code is not part of the reference): ONE spline per sample through all its control
+ * points instead of one per region -- it interpolates every landmark anyway and needs no assignment of landmarks to regions ---- */
+/* xh, ref, out fp32 [n, 3, H, W]: xh the alpha = 0 image (mkd_pgt_compose's output), ref the reference; src_masks, ref_masks uint8
+ * [4][n][H][W] in the order lip, skin, eye_left, eye_right; ctrl double [n][max_ctrl][2] = the control points (y, x); coef double
+ * [n][2][max_ctrl + 3]: row d in {y, x} holds w_d0 .. w_d,K-1 at the front and a_d0, a_d1, a_d2 in the LAST three slots; kcount int32
+ * [n]: K_b in 0 .. max_ctrl (a value outside is clamped into that range); alphas fp32 [n, 4] in mask order, in [0, 1] (not checked
+ * here, like strengths); map_out double [n][2][H][W] = (q_y, q_x) or NULL.  The spline maps the source pixel p = (y, x) to q in the
+ * reference:
+ *   s_k  = (y - c_ky)^2 + (x - c_kx)^2;  U(s) = s log(s) for s > 0, else 0 (also for a NaN s);
+ *   q_d  = ((sum_{k = 0..K-1} w_dk U(s_k)) + a_d0) + a_d1 y + a_d2 x
+ * in double, the sum sequential from +0 in the order k = 0 .. K - 1, the terms added in the order written, every operation rounded on
+ * its own (nothing contracts), log = the device's double log.
+ *   c_r(p), Kw = (2 feather + 1)^2 and the region ids are mkd_pgt_compose's, from the SOURCE masks;
+ *   m'_r(q) = the bilinear sample of "ref_masks plane of region r != 0" (1 / 0), a tap outside the image is 0;
+ *   R_c(q)  = the bilinear sample of clamp(ref_c, 0, 1) (NaN -> 0, a zero is +0), tap indices clamped to the image;
+ *   both with y0 = floor(q_y), f_y = q_y - y0 (x likewise), top = v00 + f_x (v01 - v00), bot = v10 + f_x (v11 - v10),
+ *   v = top + f_y (bot - top), in double, every operation rounded on its own; unless -1 < q_y < H and -1 < q_x < W every m' is 0
+ *   (this covers a NaN and a huge q);
+ *   Wt       = min(1, sum_{r = 1..4} (alpha_r * (c_r / Kw)) * m'_r(q))   (from +0, in the order r = 1..4; a term with c_r = 0 is +0)
+ *   out_c(p) = float(xh_c + Wt * (R_c - xh_c))   (double, ONE rounding to fp32);  Wt = 0: the bits of xh_c.
+ * A sample with K_b = 0 has Wt = 0 everywhere: out = xh bit for bit.  Where every c_r(p) is 0 no spline is evaluated (most of the
+ * background; a 16 x 16 tile of such pixels copies xh and leaves).  With map_out the spline is evaluated at every pixel of every sample
+ * with K_b > 0 and a sample with K_b = 0 writes q = p; the early-out then only skips the sampling.  tests/teacher_warp_ref.py restates
+ * all of it; where no log reaches the result (w = 0) the kernel is held to it bit for bit, else within the rounding bound stated there.
+ * One launch (mkd_pgt_warp_launches), no scratch, no atomics, no host sync, no allocation: the call only enqueues.  A thread is a pixel
+ * for every alignment (there is one load form), so no alignment beyond 4 bytes for the fp32 / int32 arrays and 8 bytes for the double
+ * arrays is assumed or can change the bits.  MKD_ERR_ARG before anything is enqueued unless 1 <= n <= 65535, H, W >= 1, H * W <= 2^24,
+ * 0 <= feather <= 8, 1 <= max_ctrl <= 128, every pointer but map_out non-null and aligned as above, out does not overlap ref, and out
+ * is either xh itself (in place: a pixel reads only its own xh) or does not overlap xh at all. */
+int mkd_pgt_warp(const float* xh, const float* ref, const uint8_t* src_masks, const uint8_t* ref_masks, const double* ctrl,
+                 const double* coef, const int32_t* kcount, const float* alphas, int n, int H, int W, int max_ctrl, int feather, float* out,
+                 double* map_out, void* stream);
+/* Launches one mkd_pgt_warp call enqueues: 1. */
+int mkd_pgt_warp_launches(void);
 
 /* ---- full-resolution photos: crop-resize in, detail-keeping paste out (reference diffdata/preprocessing.py:131-169 crops the face and
  * resizes it to the network size; the paste back is BUILD-DEFINED after the Laplacian detail transfer of PSGAN / EleGANt) ---- */

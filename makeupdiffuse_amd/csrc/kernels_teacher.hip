@@ -11,20 +11,15 @@
 //
 // One workgroup per 16 x 16 output tile.  F > 0: the region ids of the tile plus its halo go to LDS at a byte per pixel, the four
 // counts are separable sums (rows, then columns) carried as 4 x 16 bits of one 64-bit word (a row sum is <= 17, a total <= 289), and
-// the weights a_r c_r / K go back to LDS as doubles, because the 16-byte form below gives a lane other pixels than the count pass.
-// F = 0 stages nothing but the tables: id(p) comes straight from the masks.
+// the weights a_r c_r / K go back to LDS as doubles, because the 16-byte form below gives a lane other pixels than the count pass
+// (ids, counts and weights: pgt_regions.h, shared with mkd_pgt_warp).  F = 0 stages nothing but the tables: id(p) comes straight from the masks.
 #include "mkd_common.h"
+#include "pgt_regions.h"
 #include "../../include/mkd.h"
 
 namespace {
 
-constexpr int PG_T = 16;                       // tile side
-constexpr int PG_MAXF = 8;                     // feather limit: the staged plane is at most 32 x 32
-constexpr int PG_R = PG_T + 2 * PG_MAXF;       // row stride of the id plane
 constexpr int PG_TAB = 3 * 256;                // one region's tables
-
-__device__ __forceinline__ int pg_mask_plane(int r) { return r == 0 ? 0 : r == 1 ? 2 : r == 2 ? 3 : 1; }      // id r + 1 -> plane of (lip, skin, eye_left, eye_right)
-__device__ __forceinline__ int pg_id(unsigned lip, unsigned skin, unsigned eye_l, unsigned eye_r) { return lip ? 1 : eye_l ? 2 : eye_r ? 3 : skin ? 4 : 0; }
 
 struct PgWeights { double w[4]; };
 
@@ -80,39 +75,14 @@ __global__ __launch_bounds__(256) void pgt_compose_kernel(const float* __restric
     for (int r = 0; r < 4; ++r) a[r] = strengths ? strengths[(size_t)b * 4 + pg_mask_plane(r)] : 1.0f;
 
     if (HALO) {
-        const int R = PG_T + 2 * F;
-        for (int i = tid; i < R * R; i += 256) {
-            const int ly = i / R, lx = i - ly * R, gy = ty0 - F + ly, gx = tx0 - F + lx;
-            int id = 0;
-            if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-                const size_t p = (size_t)gy * W + gx;
-                id = pg_id(mk[p], mk[plane + p], mk[2 * plane + p], mk[3 * plane + p]);
-            }
-            ids[ly * PG_R + lx] = (uint8_t)id;
-        }
+        pg_stage_ids(mk, plane, H, W, F, ty0, tx0, tid, ids);
         __syncthreads();
-        for (int i = tid; i < R * PG_T; i += 256) {
-            const int ly = i >> 4, x = i & 15;
-            unsigned long long s = 0;
-            for (int k = 0; k <= 2 * F; ++k) {
-                const int id = ids[ly * PG_R + x + k];
-                s += id ? 1ull << (16 * (id - 1)) : 0ull;
-            }
-            rows[ly * PG_T + x] = s;
-        }
+        pg_row_counts(ids, F, tid, rows);
         __syncthreads();
-        {
-#pragma clang fp contract(off)
-            const int y = tid >> 4, x = tid & 15;
-            unsigned long long s = 0;
-            for (int k = 0; k <= 2 * F; ++k) s += rows[(y + k) * PG_T + x];
-            const double K = (double)((2 * F + 1) * (2 * F + 1));
+        const unsigned long long s = pg_window_counts(rows, F, tid);
+        const double K = (double)((2 * F + 1) * (2 * F + 1));
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int c = (int)((s >> (16 * r)) & 0xffffull);
-                wgt[r * 256 + tid] = c ? (double)a[r] * ((double)c / K) : 0.0;
-            }
-        }
+        for (int r = 0; r < 4; ++r) wgt[r * 256 + tid] = pg_weight(a[r], pg_count(s, r), K);
     }
     __syncthreads();
 

@@ -473,9 +473,15 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                  solver_order: int = 2, unipc_corrector: bool = True, paste_background: bool = False, paste_feather: int = 0, denoise_rows: bool = False,
                  log_every_t: int = 100, guidance_rescale: float = 0.0, face_parser=None, parser_lut=None, parse_size: int = 512,
                  seed: Optional[int] = None, teacher: Optional[str] = None, teacher_feather: int = 2, teacher_strengths=None,
-                 teacher_start: Optional[float] = None, teacher_t_min: int = 0, *args, **kwargs):
+                 teacher_start: Optional[float] = None, teacher_t_min: int = 0, teacher_warp=None, lms_key: str = 'nonmakeup_lms',
+                 ref_lms_key: str = 'makeup_lms', *args, **kwargs):
         if teacher not in (None, 'hist'):
             raise ValueError(f"teacher must be None or 'hist' (the histogram-matching pseudo ground truth), got {teacher!r}")
+        if teacher_warp is not None and teacher_warp is not False:
+            if teacher is None:
+                raise ValueError("teacher_warp needs a teacher: construct with teacher='hist'")
+            from .. import teacher as _teacher
+            _teacher.alpha_rows(teacher_warp, 1)          # (True or a dict of weights in [0, 1], or ValueError)
         if teacher is not None or teacher_start is not None:
             from .. import teacher as _teacher
             _teacher.check_feather(teacher_feather)
@@ -514,6 +520,11 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         self.teacher_feather, self.teacher_strengths = int(teacher_feather), teacher_strengths
         self.teacher_start = None if teacher_start is None else float(teacher_start)
         self.teacher_t_min = int(teacher_t_min)
+        # teacher_warp (True: the reference's weights skin 0.3 / eye 0.8 / lip 0.1, or a dict over lip / eye / skin): the landmark-warped
+        # term of the pseudo ground truth (teacher.warp_blend) from the batch's landmarks batch[lms_key] / batch[ref_lms_key], [B,K,2] in
+        # (y, x) pixels of the model-size images.  None / False: the alpha = 0 teacher, call for call as before
+        self.teacher_warp = None if teacher_warp is False else teacher_warp
+        self.lms_key, self.ref_lms_key = lms_key, ref_lms_key
         # label maps from the images themselves (face_parser.FaceParser, or anything with its parse()): a batch that lacks seg_key /
         # ref_seg_key gets them from the source / reference image parsed at parse_size; label maps the caller brings always win.
         # None: every path is as before (a missing label map is a KeyError)
@@ -691,6 +702,10 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                 if k not in batch:
                     raise ValueError(f"teacher='hist' needs the label maps of the source and of the reference: the batch has none under "
                                      f"'{k}' and no face parser is attached")
+        if self.teacher_warp is not None:
+            for k in (self.lms_key, self.ref_lms_key):
+                if k not in batch:
+                    raise ValueError(f"teacher_warp needs the landmarks of the source and of the reference: the batch has none under '{k}'")
         if not 0 <= self.teacher_t_min < self.num_timesteps:
             raise ValueError(f'teacher_t_min must lie in 0 .. {self.num_timesteps - 1}, got {self.teacher_t_min}')
         if self.teacher_start is not None:
@@ -719,14 +734,21 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
 
     def pseudo_ground_truth(self, batch: dict, src01: torch.Tensor, ref01: torch.Tensor) -> torch.Tensor:
         """x_p in [0, 1] of the pairs (src01, ref01) under batch[seg_key] / batch[ref_seg_key] (parsed from the batch's images where a
-        face parser is attached and the batch lacks them): teacher.pseudo_ground_truth with the model's teacher_feather / _strengths"""
+        face parser is attached and the batch lacks them): teacher.pseudo_ground_truth with the model's teacher_feather / _strengths and,
+        with teacher_warp, the landmarks batch[lms_key] / batch[ref_lms_key]"""
         from .. import teacher
         self._fill_segs(batch, ref=True)
         for k in (self.seg_key, self.ref_seg_key):
             if k not in batch:
                 raise ValueError(f"teacher='hist' needs the label maps of the source and of the reference: the batch has none under '{k}'")
+        warp = {}
+        if self.teacher_warp is not None:
+            for k in (self.lms_key, self.ref_lms_key):
+                if k not in batch:
+                    raise ValueError(f"teacher_warp needs the landmarks of the source and of the reference: the batch has none under '{k}'")
+            warp = dict(lms_src=batch[self.lms_key], lms_ref=batch[self.ref_lms_key], warp=self.teacher_warp)
         return teacher.pseudo_ground_truth(src01, ref01, batch[self.seg_key], batch[self.ref_seg_key], strengths=self.teacher_strengths,
-                                           feather=self.teacher_feather)[0]
+                                           feather=self.teacher_feather, **warp)[0]
 
     def _teacher_rows(self, log: dict, batch: dict, src01, ref01, ref_img, cond: dict, sd):
         """The rows reference log_results writes beside the samples (diffmk/makeup_diffuse.py:419-442): ground_truth = 2 x_p - 1; with an
@@ -1130,6 +1152,9 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             raise ValueError(f'guided_paste must be a photo.GuidedPaste or None, got {guided_paste!r}')
         teach = None
         if teacher_start is not None:
+            if self.teacher_warp is not None:
+                raise ValueError('transfer_photos: teacher_start is not combined with teacher_warp (crops carry no landmarks: the warped term '
+                                 'of the teacher image needs them in crop pixels)')
             from .. import teacher as _teacher
             _teacher.start_steps(teacher_start, 1)
             _teacher.check_feather(teacher_feather)

@@ -79,13 +79,23 @@ def read_pairs(path: str) -> List[Tuple[str, str]]:
 
 class PairFolderDataset:
     """root/images/<name> + a pairs file -> dicts with the keys get_input reads.  When root/scgan_segs/ exists (reference
-    TestFixed_Dataset layout: one label map per image, labels 0..14) the pair also carries nonmakeup_seg / makeup_seg, uint8 [H, W]."""
+    TestFixed_Dataset layout: one label map per image, labels 0..14) the pair also carries nonmakeup_seg / makeup_seg, uint8 [H, W].
+    When root/lms/ exists the pair also carries nonmakeup_lms / makeup_lms from lms/<base>.npy: the landmarks, float32 [K, 2] in (y, x)
+    pixels.  The reference's convention (diffdata/preprocessing.py:94): the stored landmarks are ALREADY scaled to the model size, so they
+    are taken as given at ``dim``; only a file whose base name has an entry in lms/sizes.json ({base: side or [H, W]}, the image size
+    the landmarks were stored for) is scaled by dim / that size."""
 
     def __init__(self, root: str, pairs_file: str = 'test_0412.txt', dim: Sequence[int] = (256, 256), prompt: str = 'makeup transfer'):
         self.root = root
         self.pairs = read_pairs(pairs_file if os.path.isabs(pairs_file) else os.path.join(root, pairs_file))
         self.dim = tuple(dim)
         self.prompt = prompt
+        self.has_lms = os.path.isdir(os.path.join(root, 'lms'))
+        self._lms_sizes = {}
+        if self.has_lms and os.path.exists(os.path.join(root, 'lms', 'sizes.json')):
+            import json
+            with open(os.path.join(root, 'lms', 'sizes.json')) as f:
+                self._lms_sizes = json.load(f)
 
     def __len__(self) -> int:
         return len(self.pairs)
@@ -107,6 +117,15 @@ class PairFolderDataset:
             seg = seg.resize((self.dim[1], self.dim[0]), Image.NEAREST)          # labels: no interpolation between classes
         return torch.from_numpy(np.array(seg, dtype=np.uint8))
 
+    def _load_lms(self, base: str) -> torch.Tensor:
+        lms = np.load(os.path.join(self.root, 'lms', base + '.npy')).astype(np.float32)
+        if lms.ndim != 2 or lms.shape[1] != 2:
+            raise ValueError(f'lms/{base}.npy must be [K, 2] in (y, x) order, got {lms.shape}')
+        if base in self._lms_sizes and self.dim:
+            hw = np.broadcast_to(np.asarray(self._lms_sizes[base], dtype=np.float32), (2,))
+            lms = lms * (np.asarray(self.dim, dtype=np.float32) / hw)
+        return torch.from_numpy(np.ascontiguousarray(lms))
+
     def __getitem__(self, i: int) -> Dict[str, object]:
         s, r = self.pairs[i]
         src, ref = self._load(s), self._load(r)
@@ -115,6 +134,8 @@ class PairFolderDataset:
                'txt': self.prompt, 'img_name': f'{base(s)}&{base(r)}'}
         if os.path.isdir(os.path.join(self.root, 'scgan_segs')):
             out['nonmakeup_seg'], out['makeup_seg'] = self._load_seg(s), self._load_seg(r)
+        if self.has_lms:
+            out['nonmakeup_lms'], out['makeup_lms'] = self._load_lms(base(s)), self._load_lms(base(r))
         return out
 
 

@@ -156,6 +156,8 @@ SIGNATURES = {
     'mkd_hist_match': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     'mkd_pgt_compose': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     'mkd_pgt_launches': (_I, []),
+    'mkd_pgt_warp': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    'mkd_pgt_warp_launches': (_I, []),
     'mkd_crop_resize_scratch_bytes': (C.c_size_t, [C.POINTER(PhotoDescC), _I, _I]),
     'mkd_crop_resize': (_I, [C.POINTER(PhotoDescC), _I, _I, _P, _P, _P, _P, _P]),
     'mkd_resize_coeffs': (_I, [_I, _I, _I, _I, _P, _P, _P]),

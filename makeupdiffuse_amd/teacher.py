@@ -1,16 +1,18 @@
-"""The histogram-matching teacher on the device: EleGANt's pseudo ground truth (reference teacher.py:96-112, the default
-``ELEGANT_PGT`` of diffmk/makeup_diffuse.py:328-334) at warp weight alpha = 0, i.e. the source with its lip, eye and skin regions
-histogram-matched to the same regions of the reference.  The landmark-warped term (alpha > 0) and the SCGAN / EleGANt generators need
-landmarks and external weights and are not here.
+"""The teacher on the device: EleGANt's pseudo ground truth (reference teacher.py:96-112, the default ``ELEGANT_PGT`` of
+diffmk/makeup_diffuse.py:328-334).  Its first term is the source with its lip, eye and skin regions histogram-matched to the same
+regions of the reference (warp weight alpha = 0: pseudo_ground_truth as it always was); its second term, opt-in through ``warp``, blends in
+the reference warped onto the source through the landmarks by a thin-plate spline (tps_coefficients on the host, warp_blend on the
+device).  The SCGAN / EleGANt generators need external weights and are not here.
 
-Everything takes device tensors and returns device tensors without waiting for the device; the arithmetic is libmkd's
-(mkd_region_mask_from_labels, mkd_hist_match, mkd_pgt_compose; include/mkd.h has the definition, tests/teacher_ref.py restates it).
-There is no CPU path."""
+Everything but the landmarks takes device tensors and returns device tensors without waiting for the device; the arithmetic is libmkd's
+(mkd_region_mask_from_labels, mkd_hist_match, mkd_pgt_compose, mkd_pgt_warp; include/mkd.h has the definitions, tests/teacher_ref.py and
+tests/teacher_warp_ref.py restate them).  There is no CPU path."""
 from __future__ import annotations
 
 import ctypes as C
 from typing import Dict, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import lib as _lib
@@ -18,6 +20,9 @@ from . import makeup_score as ms
 
 MAX_FEATHER = 8
 STRENGTH_KEYS = ('lip', 'eye', 'skin')
+MAX_CTRL = 128
+REFERENCE_ALPHAS = dict(skin=0.3, eye=0.8, lip=0.1)          # SKIN_ALPHA, EYE_ALPHA, LIP_ALPHA of reference teacher.py:100-106
+TPS_RESIDUAL = 1e-6          # px: a spline that misses a landmark by more is dropped (the sample keeps the alpha = 0 image)
 _index_cache: Dict[Tuple[int, str], torch.Tensor] = {}          # (batch, device) -> the index table of the 4 B terms, uploaded once
 
 
@@ -37,7 +42,7 @@ def check_feather(feather) -> int:
     return int(feather)
 
 
-def strength_rows(strengths, batch: int) -> Optional[torch.Tensor]:
+def strength_rows(strengths, batch: int, what: str = 'teacher strength') -> Optional[torch.Tensor]:
     """``strengths`` -> fp32 [batch, 4] in the order lip, skin, eye_left, eye_right, or None for all 1.  A dict takes the keys lip, eye
     (both eyes) and skin, each a number or one per sample; a [batch, 4] tensor or array is taken in that order.  Host values outside
     [0, 1] (or not finite) are a ValueError; a tensor that already lives on the device is the caller's to guarantee (looking at it would
@@ -47,33 +52,105 @@ def strength_rows(strengths, batch: int) -> Optional[torch.Tensor]:
     if isinstance(strengths, dict):
         extra = [k for k in strengths if k not in STRENGTH_KEYS]
         if extra:
-            raise ValueError(f'teacher strengths take the keys {list(STRENGTH_KEYS)}, got {extra}')
+            raise ValueError(f'{what}s take the keys {list(STRENGTH_KEYS)}, got {extra}')
         cols = {}
         for k in STRENGTH_KEYS:
             v = torch.as_tensor(strengths.get(k, 1.0), dtype=torch.float32).detach().cpu().reshape(-1)
             if v.numel() not in (1, batch):
-                raise ValueError(f"teacher strength of '{k}' must be one number or one per sample ({batch}), got {v.numel()}")
+                raise ValueError(f"{what} of '{k}' must be one number or one per sample ({batch}), got {v.numel()}")
             cols[k] = v.expand(batch)
         rows = torch.stack([cols['lip'], cols['skin'], cols['eye'], cols['eye']], 1).contiguous()
     else:
         rows = torch.as_tensor(strengths)
         if tuple(rows.shape) != (batch, 4):
-            raise ValueError(f'teacher strengths must be a dict or [{batch}, 4] (lip, skin, eye_left, eye_right), got {tuple(rows.shape)}')
+            raise ValueError(f'{what}s must be a dict or [{batch}, 4] (lip, skin, eye_left, eye_right), got {tuple(rows.shape)}')
         if rows.device.type != 'cpu':
             return rows.detach().float().contiguous()
         rows = rows.detach().float().contiguous()
     if not bool(torch.isfinite(rows).all()) or float(rows.min()) < 0.0 or float(rows.max()) > 1.0:
-        raise ValueError('teacher strengths must lie in [0, 1]')
+        raise ValueError(f'{what}s must lie in [0, 1]')
     return rows
 
 
-def launches() -> int:
+def alpha_rows(warp, batch: int) -> Optional[torch.Tensor]:
+    """``warp`` -> the warp weights alpha as host fp32 [batch, 4] in the order lip, skin, eye_left, eye_right, or None for off.  None /
+    False: off; True: REFERENCE_ALPHAS; a dict over lip, eye, skin by the rules of strength_rows (a number or one per sample, in [0, 1],
+    else ValueError), a missing key taking its reference value."""
+    if warp is None or warp is False:
+        return None
+    if warp is True:
+        warp = {}
+    if not isinstance(warp, dict):
+        raise ValueError(f'warp must be None, a bool or a dict over {list(STRENGTH_KEYS)}, got {warp!r}')
+    extra = [k for k in warp if k not in STRENGTH_KEYS]
+    if extra:
+        raise ValueError(f'warp weights take the keys {list(STRENGTH_KEYS)}, got {extra}')
+    return strength_rows({k: warp.get(k, REFERENCE_ALPHAS[k]) for k in STRENGTH_KEYS}, batch, what='warp weight')
+
+
+def launches(warp: bool = False) -> int:
     """Launches of ONE pseudo_ground_truth call, whatever the batch and the feather: 16 = 1 torch copy that concatenates the two label
     maps, 10 for the region masks of the concatenated maps (lip and skin 2 each, the two eyes 3 each), mkd_hist_match_launches(0, 0) = 3
     for the tables (memset, histogram, CDF + table), 1 torch copy that gathers the source half of the masks and mkd_pgt_launches() = 1
-    for the composition.  (Host ``strengths`` add one host-to-device copy of 16 B bytes, which is not a launch.)"""
+    for the composition.  (Host ``strengths`` add one host-to-device copy of 16 B bytes, which is not a launch.)  With ``warp`` 17: one
+    mkd_pgt_warp more (the copy that gathers the source half of the masks gathers the reference half too) and three small host-to-device copies (the spline, its
+    counts and the warp weights), which are not launches."""
     lib = _lib.load()
-    return 1 + 10 + int(lib.mkd_hist_match_launches(0, 0)) + 1 + int(lib.mkd_pgt_launches())
+    return 1 + 10 + int(lib.mkd_hist_match_launches(0, 0)) + 1 + int(lib.mkd_pgt_launches()) + (int(lib.mkd_pgt_warp_launches()) if warp else 0)
+
+
+def _tps_kernel(d2: np.ndarray) -> np.ndarray:
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.where(d2 > 0, d2 * np.log(d2), 0.0)
+
+
+def tps_coefficients(lms_src, lms_ref, max_ctrl: Optional[int] = None):
+    """The thin-plate splines that carry each sample's source landmarks onto its reference landmarks, as mkd_pgt_warp takes them:
+    (ctrl float64 [B, max_ctrl, 2], coef float64 [B, 2, max_ctrl + 3], kcount int32 [B]) HOST arrays; max_ctrl defaults to K.
+
+    lms_src / lms_ref: [B, K, 2] in (y, x) order, host arrays or tensors (a device tensor is brought over with .cpu(), which WAITS for the
+    device).  The solve is on the host on purpose: landmarks are host data (the reference loads them from lms/<name>.npy) and the systems
+    are (K + 3)^2 with K <= 128.  Per sample: repeated source points are dropped (the first is kept), then float64 numpy.linalg.solve of
+    [[U(|c_i - c_j|^2), P], [P^T, 0]] [w; a] = [d; 0] with P = [1, y, x], control points c = source landmarks, targets d = reference
+    landmarks, U(s) = s log s.  K_b = 0 -- the sample keeps the alpha = 0 image -- when fewer than 3 points are left, when the solve
+    raises (collinear points), when anything is not finite, or when the spline misses a landmark by more than TPS_RESIDUAL = 1e-6 px."""
+    def host(a, name):
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        if a.ndim != 3 or a.shape[2] != 2:
+            raise ValueError(f'{name} must be [B, K, 2] in (y, x) order, got {tuple(a.shape)}')
+        return a.astype(np.float64)
+    ls, lr = host(lms_src, 'lms_src'), host(lms_ref, 'lms_ref')
+    if ls.shape != lr.shape:
+        raise ValueError(f'lms_src and lms_ref must have one shape, got {ls.shape} and {lr.shape}')
+    B, K, _ = ls.shape
+    M = K if max_ctrl is None else int(max_ctrl)
+    if not 1 <= M <= MAX_CTRL or K > M:
+        raise ValueError(f'max_ctrl must lie in max(K, 1) .. {MAX_CTRL}, got {M} for K = {K}')
+    ctrl, coef, kcount = np.zeros((B, M, 2)), np.zeros((B, 2, M + 3)), np.zeros(B, dtype=np.int32)
+    for b in range(B):
+        if not (np.isfinite(ls[b]).all() and np.isfinite(lr[b]).all()):
+            continue
+        _, first = np.unique(ls[b], axis=0, return_index=True)
+        keep = np.sort(first)
+        c, d = ls[b][keep], lr[b][keep]
+        k = len(keep)
+        if k < 3:
+            continue
+        A = np.zeros((k + 3, k + 3))
+        A[:k, :k] = _tps_kernel(((c[:, None, :] - c[None, :, :]) ** 2).sum(-1))
+        A[:k, k], A[:k, k + 1:] = 1.0, c
+        A[k:, :k] = A[:k, k:].T
+        rhs = np.zeros((k + 3, 2))
+        rhs[:k] = d
+        try:
+            sol = np.linalg.solve(A, rhs)
+        except np.linalg.LinAlgError:
+            continue
+        if not np.isfinite(sol).all() or np.abs(A[:k] @ sol - d).max() > TPS_RESIDUAL:
+            continue
+        ctrl[b, :k], kcount[b] = c, k
+        coef[b, :, :k], coef[b, :, M:] = sol[:k].T, sol[k:].T
+    return ctrl, coef, kcount
 
 
 def compose(src01: torch.Tensor, masks: torch.Tensor, tables: torch.Tensor, strengths: Optional[torch.Tensor] = None, feather: int = 0,
@@ -105,8 +182,51 @@ def compose(src01: torch.Tensor, masks: torch.Tensor, tables: torch.Tensor, stre
     return out
 
 
+def warp_blend(xh: torch.Tensor, ref01: torch.Tensor, src_masks: torch.Tensor, ref_masks: torch.Tensor, ctrl: torch.Tensor, coef: torch.Tensor,
+               kcount: torch.Tensor, alphas: torch.Tensor, feather: int = 0, out: Optional[torch.Tensor] = None, want_map: bool = False):
+    """ONE mkd_pgt_warp: xh (the alpha = 0 image) and ref01 fp32 [B,3,H,W], src_masks / ref_masks uint8 [4,B,H,W] in the order lip, skin,
+    eye_left, eye_right, the spline of tps_coefficients on the device (ctrl float64 [B,M,2], coef float64 [B,2,M+3], kcount int32 [B]),
+    alphas fp32 [B,4] in mask order -> the blended image fp32 [B,3,H,W]; ``out`` may be xh itself (in place).  want_map: also the map
+    float64 [B,2,H,W] = (q_y, q_x), the position in the reference of every source pixel."""
+    feather = check_feather(feather)
+    for t, what in ((xh, 'xh'), (ref01, 'ref01'), (src_masks, 'src_masks'), (ref_masks, 'ref_masks'), (ctrl, 'ctrl'), (coef, 'coef'),
+                    (kcount, 'kcount'), (alphas, 'alphas')):
+        ms._require_cuda(t, what)
+    if xh.dim() != 4 or xh.shape[1] != 3 or tuple(ref01.shape) != tuple(xh.shape):
+        raise ValueError(f'xh and ref01 must be equal [B,3,H,W] tensors, got {tuple(xh.shape)} and {tuple(ref01.shape)}')
+    B, _, H, W = (int(v) for v in xh.shape)
+    for m, what in ((src_masks, 'src_masks'), (ref_masks, 'ref_masks')):
+        if m.dtype != torch.uint8 or tuple(m.shape) != (4, B, H, W):
+            raise ValueError(f'{what} must be uint8 [4,{B},{H},{W}], got {m.dtype} {tuple(m.shape)}')
+    if ctrl.dtype != torch.float64 or ctrl.dim() != 3 or ctrl.shape[0] != B or ctrl.shape[2] != 2 or not 1 <= ctrl.shape[1] <= MAX_CTRL:
+        raise ValueError(f'ctrl must be float64 [{B},M,2] with 1 <= M <= {MAX_CTRL}, got {ctrl.dtype} {tuple(ctrl.shape)}')
+    M = int(ctrl.shape[1])
+    if coef.dtype != torch.float64 or tuple(coef.shape) != (B, 2, M + 3):
+        raise ValueError(f'coef must be float64 [{B},2,{M + 3}], got {coef.dtype} {tuple(coef.shape)}')
+    if kcount.dtype != torch.int32 or tuple(kcount.shape) != (B,):
+        raise ValueError(f'kcount must be int32 [{B}], got {kcount.dtype} {tuple(kcount.shape)}')
+    if tuple(alphas.shape) != (B, 4):
+        raise ValueError(f'alphas must be [{B},4], got {tuple(alphas.shape)}')
+    if xh.dtype != torch.float32 or not xh.is_contiguous():
+        if out is xh:
+            raise ValueError('in place needs a contiguous fp32 xh')
+        xh = xh.float().contiguous()
+    ref01, src_masks, ref_masks = ref01.float().contiguous(), src_masks.contiguous(), ref_masks.contiguous()
+    ctrl, coef, kcount, alphas = ctrl.contiguous(), coef.contiguous(), kcount.contiguous(), alphas.float().contiguous()
+    if out is None:
+        out = torch.empty_like(xh)
+    elif out.dtype != torch.float32 or tuple(out.shape) != tuple(xh.shape) or not out.is_contiguous():
+        raise ValueError(f'out must be a contiguous fp32 {tuple(xh.shape)} tensor')
+    qmap = torch.empty(B, 2, H, W, dtype=torch.float64, device=xh.device) if want_map else None
+    P = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+    with torch.cuda.device(xh.device):
+        _lib.check(_lib.load().mkd_pgt_warp(P(xh), P(ref01), P(src_masks), P(ref_masks), P(ctrl), P(coef), P(kcount), P(alphas), B, H, W, M, feather,
+                                            P(out), P(qmap), C.c_void_p(ms._stream())), 'mkd_pgt_warp')
+    return (out, qmap) if want_map else out
+
+
 def pseudo_ground_truth(src01: torch.Tensor, ref01: torch.Tensor, src_seg: torch.Tensor, ref_seg: torch.Tensor, strengths=None,
-                        feather: int = 2, classes: Optional[dict] = None):
+                        feather: int = 2, classes: Optional[dict] = None, lms_src=None, lms_ref=None, warp=None):
     """The preliminary transfer x_p of (source, reference) -> (x_p fp32 [B,3,H,W] in [0,1], tables uint8 [4,B,3,256], counts int32
     [4,B,2] = (source, reference) pixels of each region), regions in the order lip, skin, eye_left, eye_right.
 
@@ -118,6 +238,14 @@ def pseudo_ground_truth(src01: torch.Tensor, ref01: torch.Tensor, src_seg: torch
     that copy, not for the kernels), a device tensor is used where it is.  ``launches()`` kernel launches per call (16), whatever B; no
     result is read back."""
     feather = check_feather(feather)
+    alphas = alpha_rows(warp, int(src01.shape[0]))          # (the warp keywords are checked, and the splines solved, before anything else)
+    spline = None
+    if alphas is not None:
+        if lms_src is None or lms_ref is None:
+            raise ValueError('warp needs the landmarks of the source and of the reference: lms_src and lms_ref, [B,K,2] in (y, x) order')
+        spline = tps_coefficients(lms_src, lms_ref)
+        if spline[0].shape[0] != int(src01.shape[0]):
+            raise ValueError(f'landmarks must be [{int(src01.shape[0])},K,2], got {tuple(spline[0].shape)}')
     cls = dict(lip=ms.LIP_CLASSES, skin=ms.SKIN_CLASSES, face=ms.FACE_CLASSES, eye_left=ms.EYE_LEFT_CLASSES, eye_right=ms.EYE_RIGHT_CLASSES,
                margin=ms.EYE_MARGIN)
     cls.update(classes or {})
@@ -140,6 +268,14 @@ def pseudo_ground_truth(src01: torch.Tensor, ref01: torch.Tensor, src_seg: torch
     flat = masks.view(8 * B, H, W)
     _, tables, _, counts = ms.histogram_match(src01, ref01, flat, flat, index=_index_cache[key], want_matched=False, want_loss=False)
     tables, counts = tables.view(4, B, 3, 256), counts.view(4, B, 2)
-    src_masks = masks[:, :B].contiguous()
+    if alphas is None:
+        src_masks = masks[:, :B].contiguous()
+    else:          # the same one copy gathers both halves: [src | ref][region]
+        src_masks, ref_masks = masks.view(4, 2, B, H, W).permute(1, 0, 2, 3, 4).contiguous().unbind(0)
     x_p = compose(src01, src_masks, tables, None if rows is None else rows.to(dev), feather)
+    if alphas is not None:
+        ctrl, coef, kcount = spline
+        flat = torch.from_numpy(np.concatenate([ctrl.reshape(-1), coef.reshape(-1)])).to(dev)          # one upload for the spline
+        warp_blend(x_p, ref01, src_masks, ref_masks, flat[:ctrl.size].view(ctrl.shape), flat[ctrl.size:].view(coef.shape),
+                   torch.from_numpy(kcount).to(dev), alphas.to(dev), feather, out=x_p)
     return x_p, tables, counts

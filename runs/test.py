@@ -38,7 +38,19 @@ def synthetic_seg(i, res, features=False):
     return seg
 
 
-def synthetic_batch(lo, hi, res, ctx_dim, with_seg=False, with_makeup_seg=False):
+def synthetic_lms(i, res):
+    """stand-in landmarks for pair i, consistent with synthetic_seg(i, res, features=True): the centre and the four extents of the face
+    ellipse and of the eye and lip blobs, float32 [20, 2] in (y, x) pixels"""
+    g = torch.Generator().manual_seed(1213 + i)
+    cy, cx = (res * (0.5 + 0.1 * (torch.rand(2, generator=g) - 0.5))).tolist()
+    pts = []
+    for dy, dx, ry, rx in ((0.0, 0.0, 0.4, 0.3), (-0.08, -0.11, 0.025, 0.05), (-0.08, 0.11, 0.025, 0.05), (0.18, 0.0, 0.035, 0.09)):
+        y, x = cy + dy * res, cx + dx * res
+        pts += [(y, x), (y - ry * res, x), (y + ry * res, x), (y, x - rx * res), (y, x + rx * res)]
+    return torch.tensor(pts, dtype=torch.float32)
+
+
+def synthetic_batch(lo, hi, res, ctx_dim, with_seg=False, with_makeup_seg=False, with_lms=False):
     src, ref, txt = [], [], []
     for i in range(lo, hi):
         g = torch.Generator().manual_seed(5678 + i)
@@ -52,6 +64,9 @@ def synthetic_batch(lo, hi, res, ctx_dim, with_seg=False, with_makeup_seg=False)
     if with_makeup_seg:
         batch['nonmakeup_seg'] = torch.stack([synthetic_seg(i, res, True) for i in range(lo, hi)])
         batch['makeup_seg'] = torch.stack([synthetic_seg(7000 + i, res, True) for i in range(lo, hi)])
+    if with_lms:
+        batch['nonmakeup_lms'] = torch.stack([synthetic_lms(i, res) for i in range(lo, hi)])
+        batch['makeup_lms'] = torch.stack([synthetic_lms(7000 + i, res) for i in range(lo, hi)])
     return batch
 
 
@@ -158,6 +173,11 @@ def build_parser():
     ap.add_argument('--teacher-feather', type=int, default=2, metavar='F', help='with --teacher: box feather of the region weights, 0..8 image pixels')
     ap.add_argument('--teacher-start', type=float, default=None, metavar='TAU', help='with --teacher: start both passes from the diffused '
                     'teacher image and run only the last round(TAU * steps) steps, TAU in (0, 1] (the pair passes; not with --photos, --region-refs, --video)')
+    ap.add_argument('--teacher-warp', action='store_true', help='with --teacher hist: add the landmark-warped term of the pseudo ground truth '
+                    '(the reference warped onto the source by a thin-plate spline through the landmarks, blended in per region; landmarks from '
+                    '<data-root>/lms/<name>.npy, synthetic ones without a data root; not with --photos, --region-refs, --video)')
+    ap.add_argument('--teacher-warp-alphas', default=None, metavar='LIP,EYE,SKIN', help='with --teacher-warp: the blend weights in [0, 1] '
+                    "(default: the reference's 0.1,0.8,0.3)")
     ap.add_argument('--teacher-t-min', type=int, default=0, metavar='T', help='with --teacher: the sample_ddmp row diffuses to a timestep in [T, 1000)')
     ap.add_argument('--denoise-rows', action='store_true', help='also write the denoise rows of both passes (denoise_row*.png: the decoded '
                     'x0-predictions, samples as rows, x_T and the logged steps as columns), traced inside the sampling loop')
@@ -363,6 +383,21 @@ def main():
             raise SystemExit(f'--guide-radius / --guide-sigma: {e}')
     elif args.guide_radius != 1 or args.guide_sigma != 8.0:
         raise SystemExit('--guide-radius / --guide-sigma only apply with --guided-paste')
+    teacher_warp = None
+    if args.teacher_warp_alphas is not None and not args.teacher_warp:
+        raise SystemExit('--teacher-warp-alphas only applies with --teacher-warp')
+    if args.teacher_warp:
+        if args.teacher is None:
+            raise SystemExit('--teacher-warp / --teacher-warp-alphas only apply with --teacher hist')
+        for on, flag in ((args.photos, '--photos'), (args.region_refs, '--region-refs'), (args.video, '--video')):
+            if on:
+                raise SystemExit(f'--teacher-warp is not combined with {flag} (those passes bring no landmarks)')
+        teacher_warp = True
+        if args.teacher_warp_alphas is not None:
+            al = parse_number_list(args.teacher_warp_alphas, float, '--teacher-warp-alphas')
+            if len(al) != 3 or not all(0.0 <= a <= 1.0 for a in al):
+                raise SystemExit('--teacher-warp-alphas takes three numbers in [0, 1]: LIP,EYE,SKIN')
+            teacher_warp = dict(lip=al[0], eye=al[1], skin=al[2])
     video_opts = check_video_args(args)
     if args.log_every_t < 1:
         raise SystemExit('--log-every-t must be >= 1')
@@ -409,6 +444,7 @@ def main():
         model.first_stage_encoder = True          # (the reconstruction / sample_ddmp rows and the teacher start encode x_p)
         model.teacher, model.teacher_feather, model.teacher_t_min = args.teacher, args.teacher_feather, args.teacher_t_min
         model.teacher_start = args.teacher_start
+        model.teacher_warp = teacher_warp
     model.paste_background, model.paste_feather = args.paste_background, args.paste_feather
     if args.ddim_steps is not None:
         model.ddim_steps = args.ddim_steps
@@ -442,6 +478,8 @@ def main():
         from makeupdiffuse_amd.imageio import PairFolderDataset, collate
         dataset = PairFolderDataset(args.data_root, args.pairs_file, (args.res, args.res))
         args.pairs = len(dataset)
+        if args.teacher_warp and not dataset.has_lms:
+            raise SystemExit(f'--teacher-warp needs landmarks: {args.data_root}/lms/<name>.npy')
     photo_ds = None
     if args.photos:
         from makeupdiffuse_amd.photo import PhotoPairDataset, collate_photos
@@ -469,7 +507,7 @@ def main():
                 batch['txt_emb'] = e.expand(b1 - b0, -1, -1).contiguous()
         else:
             batch = synthetic_batch(b0, b1, args.res, model.net_config.context_dim, with_seg=(args.fix_background or args.paste_background) and not args.face_parser,
-                                    with_makeup_seg=(args.makeup_score or bool(args.teacher)) and not args.face_parser)
+                                    with_makeup_seg=(args.makeup_score or bool(args.teacher)) and not args.face_parser, with_lms=args.teacher_warp)
             if use_clip:
                 del batch['txt_emb']          # 'txt' -> tokenizer -> mkd_clip_encode
         x_T = None

@@ -5,7 +5,10 @@ from torch ops on mkd_hist_match's matched images (feather 0: a chain of torch.w
 gather of the tables), each at feather 0, 2 and 8.  A device sample is the time between two events around --iters back-to-back calls,
 divided by --iters, median (minimum) over --rounds rounds; the forms are alternated inside the rounds.  --model: also a full
 log_results (plain + guided pass, --steps steps) on the randomly initialised model of runs/test.py against the same call with
-teacher_start = --tau, wall time around a device synchronisation."""
+teacher_start = --tau, wall time around a device synchronisation.  --warp: also the landmark-warped term at K = 68 landmarks per pair:
+mkd_pgt_warp alone (feather 0, 2, 8), the same image composed from torch ops on the device (the thin-plate spline in float64, grid_sample
+for the colours and the reference masks, box-filtered one-hot planes for the weights) and pseudo_ground_truth whole with and without
+warp, in the same median-of-rounds form."""
 import argparse, os, statistics, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,6 +24,8 @@ ap.add_argument('--iters', type=int, default=20)
 ap.add_argument('--batch', type=int, default=8)
 ap.add_argument('--size', type=int, default=256)
 ap.add_argument('--model', action='store_true', help='also time a sampling pass with and without teacher_start')
+ap.add_argument('--warp', action='store_true', help='also time the landmark-warped term (mkd_pgt_warp) against a torch composition')
+ap.add_argument('--landmarks', type=int, default=68)
 ap.add_argument('--steps', type=int, default=50)
 ap.add_argument('--tau', type=float, default=0.6)
 ap.add_argument('--out', default=None, help='also write the report to this file')
@@ -101,6 +106,61 @@ for _ in range(args.rounds):
         samples[k].append(timed(call))
 for k, v in samples.items():
     say(f'{k}: median {statistics.median(v) * 1e3:8.1f} us, min {min(v) * 1e3:8.1f} us')
+
+if args.warp:
+    import numpy as np
+    K = args.landmarks
+    rng = np.random.RandomState(0)
+    flat = np.stack([rng.choice(S * S, K, replace=False) for _ in range(B)])
+    lms_s = np.stack([flat // S, flat % S], 2).astype(np.float64)
+    lms_r = lms_s + rng.uniform(-S / 16, S / 16, lms_s.shape)
+    ctrl_h, coef_h, kcount_h = teacher.tps_coefficients(lms_s, lms_r)
+    ctrl, coef, kcount = (torch.from_numpy(a).cuda() for a in (ctrl_h, coef_h, kcount_h))
+    alphas = teacher.alpha_rows(True, B).cuda()
+    xh = teacher.compose(src, masks, tables, None, 2)
+    wout = torch.empty_like(src)
+    yy, xx = torch.meshgrid(torch.arange(S, dtype=torch.float64, device='cuda'), torch.arange(S, dtype=torch.float64, device='cuda'), indexing='ij')
+
+    def torch_warp(F):
+        d2 = (yy - ctrl[:, :, 0, None, None]) ** 2 + (xx - ctrl[:, :, 1, None, None]) ** 2                      # [B, K, S, S]
+        U = torch.where(d2 > 0, d2 * torch.log(d2), torch.zeros_like(d2))
+        q = (coef[:, :, :K, None, None] * U[:, None]).sum(2) + coef[:, :, K, None, None] + coef[:, :, K + 1, None, None] * yy + coef[:, :, K + 2, None, None] * xx
+        grid = torch.stack([2 * q[:, 1] / (S - 1) - 1, 2 * q[:, 0] / (S - 1) - 1], -1).float()
+        R = torch.nn.functional.grid_sample(ref.clamp(0, 1), grid, mode='bilinear', padding_mode='border', align_corners=True)
+        ids = torch.zeros_like(masks[0])
+        for r, rid in zip(ORDER, (4, 3, 2, 1)):
+            ids = torch.where(masks[r] != 0, torch.full_like(ids, rid), ids)
+        Wt = torch.zeros(B, 1, S, S, device='cuda')
+        for plane, rid in ((0, 1), (2, 2), (3, 3), (1, 4)):
+            w = torch.nn.functional.avg_pool2d((ids == rid).float()[:, None], 2 * F + 1, 1, F, count_include_pad=True)
+            mr = torch.nn.functional.grid_sample((rmasks[plane] != 0).float()[:, None], grid, mode='bilinear', padding_mode='zeros', align_corners=True)
+            Wt = Wt + alphas[:, plane, None, None, None] * w * mr
+        Wt = Wt.clamp(max=1.0)
+        return xh + Wt * (R - xh)
+
+    errw = (torch_warp(2) - teacher.warp_blend(xh, ref, masks, rmasks, ctrl, coef, kcount, alphas, 2)).abs().max().item()
+    say(f'warp, K = {K} landmarks per pair displaced by up to S / 16: the torch composition differs from mkd_pgt_warp by at most {errw:.2e} (feather 2): an '
+        f'fp32 sampling grid against positions and blends in double')
+    wforms = {}
+    for F in (0, 2, 8):
+        wforms[f'mkd_pgt_warp alone               feather {F} (1 launch)'] = lambda F=F: teacher.warp_blend(xh, ref, masks, rmasks, ctrl, coef, kcount, alphas, F, out=wout)
+        wforms[f'torch warp composition alone     feather {F}'] = lambda F=F: torch_warp(F)
+    wforms[f'teacher.pseudo_ground_truth      feather 2, no warp ({teacher.launches()} launches)'] = lambda: teacher.pseudo_ground_truth(src, ref, sseg, rseg, feather=2)
+    wforms[f'teacher.pseudo_ground_truth      feather 2, warp ({teacher.launches(warp=True)} launches, host solve + 3 uploads)'] = \
+        lambda: teacher.pseudo_ground_truth(src, ref, sseg, rseg, feather=2, lms_src=lms_s, lms_ref=lms_r, warp=True)
+    for call in wforms.values():
+        call()
+    torch.cuda.synchronize()
+    wsamples = {k: [] for k in wforms}
+    for _ in range(args.rounds):
+        for k, call in wforms.items():
+            wsamples[k].append(timed(call))
+    for k, v in wsamples.items():
+        say(f'{k}: median {statistics.median(v) * 1e3:8.1f} us, min {min(v) * 1e3:8.1f} us')
+    t0 = time.perf_counter()
+    for _ in range(10):
+        teacher.tps_coefficients(lms_s, lms_r)
+    say(f'teacher.tps_coefficients on the host, {B} systems of {K + 3}^2: {(time.perf_counter() - t0) * 100:.2f} ms per call')
 
 if args.model:
     from makeupdiffuse_amd.config import create_model
