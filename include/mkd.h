@@ -579,6 +579,52 @@ int mkd_pgt_warp(const float* xh, const float* ref, const uint8_t* src_masks, co
                  double* map_out, void* stream);
 /* Launches one mkd_pgt_warp call enqueues: 1. */
 int mkd_pgt_warp_launches(void);
+/* ---- control points for mkd_pgt_warp without landmarks.  BUILD-DEFINED (the reference takes dlib's 68 landmarks from files): the
+ * control points of a face come from the four region masks the teacher already has, and the spline through them is solved on the
+ * device.  tests/teacher_points_ref.py restates both calls ---- */
+/* masks uint8 [4][n][H][W] in the order lip, skin, eye_left, eye_right (mkd_pgt_compose's; n may count sources and references alike).
+ * The regions are made exclusive by mkd_pgt_compose's id(p): lip 1, eye_left 2, eye_right 3, skin 4.  Per image K = 4 (dirs + 1)
+ * points, dirs = D in {8, 16}, in the order r = 1..4 and within a region the centroid, then the support points d = 0 .. D - 1:
+ *   n_r = the pixels with id r; sy, sx = the int64 sums of their y and x;
+ *   centroid = (double(sy) / double(n_r), double(sx) / double(n_r)), one IEEE division each;
+ *   support point d = the pixel of the region with the largest int32 projection cq_d x + sq_d y, ties to the smallest linear index
+ *     y W + x (one unsigned 64-bit key (proj + 2^31) << 32 | (0xFFFFFFFF - lin), reduced by max);
+ *   (cq_d, sq_d), y pointing down, for D = 16: (16384, 0), (15137, 6270), (11585, 11585), (6270, 15137), (0, 16384) for d = 0..4,
+ *     d = 5..8 is d' = 8 - d with cq negated, d = 9..15 is d - 8 negated; D = 8 takes every second entry.
+ * pts double [n][K][2] = (y, x); use int32 [n][K] = 1 for every point of a region with n_r >= min_area, else 0 and the point is
+ * (0, 0); count int32 [n][4] = n_r in the order r = 1..4, or NULL.  Integers and two divisions: the outputs are exact and the same
+ * bytes on every run.  Three launches (mkd_region_points_launches: clear, accumulate with 256 threads x 4 consecutive pixels and one
+ * global atomic per touched cell of a workgroup, finish), no host sync, no allocation: the call only enqueues.  scratch:
+ * mkd_region_points_scratch_bytes(n) bytes on the device.  MKD_ERR_ARG before anything is enqueued unless 1 <= n <= 65535,
+ * 1 <= H, W <= 4096, H * W <= 2^24, dirs in {8, 16}, min_area >= 1, masks / pts / use / scratch non-null, pts 8-byte and use / count
+ * 4-byte aligned, and the scratch 256-byte aligned. */
+int mkd_region_points(const uint8_t* masks, int n, int H, int W, int dirs, int min_area, double* pts, int32_t* use, int32_t* count,
+                      void* scratch, void* stream);
+/* Bytes of device scratch mkd_region_points needs for n images (76 64-bit cells each, rounded up to 256 bytes; 0 unless 1 <= n <= 65535). */
+size_t mkd_region_points_scratch_bytes(int n);
+/* Launches one mkd_region_points call enqueues: 3. */
+int mkd_region_points_launches(void);
+/* The thin-plate splines that carry each sample's source points onto its reference points, in the layout mkd_pgt_warp reads: pts_src,
+ * pts_ref double [B][K][2] = (y, x); use_src, use_ref int32 [B][K] or NULL (all 1); ctrl double [B][max_ctrl][2], coef double
+ * [B][2][max_ctrl + 3] (the affine part in the LAST three slots of a row), kcount int32 [B]; unused slots are 0.  Per sample:
+ *   1. the pairs with both use flags non-zero, in order; a non-finite coordinate in any of them gives K_b = 0;
+ *   2. a pair whose source point equals (==, both coordinates) that of an earlier kept pair is dropped; fewer than 3 left: K_b = 0;
+ *   3. the (k + 3)^2 system [[U(|c_i - c_j|^2), P], [P^T, 0]] [w; a] = [d; 0], P = [1, y, x], c = the source points, d = the reference
+ *      points, s = dy dy + dx dx, U(s) = s log(s) for s > 0, else 0 (log = the device's double log);
+ *   4. Gaussian elimination in double with partial pivoting, both right sides along: the pivot of column p is the largest |A[i][p]|,
+ *      i >= p, ties to the lowest row (a non-finite entry counts as infinite); a pivot that is 0 or not finite gives K_b = 0;
+ *      A[i][j] -= (A[i][p] / pivot) A[p][j]; back substitution x_p = b_p / A[p][p], then b_i -= A[i][p] x_p for i < p, p = k + 2 .. 0;
+ *      every operation rounded on its own;
+ *   5. the system is built again: a non-finite coefficient, or max |A sol - rhs| over ALL k + 3 rows and both columns (row sums in
+ *      the order j = 0 .. k + 2 from +0) above 1e-6, gives K_b = 0;
+ *   6. K_b = 0 writes zeros everywhere.
+ * One launch (mkd_tps_solve_launches), one workgroup per sample, (max_ctrl + 3) (max_ctrl + 5) doubles of LDS, no atomics and a fixed
+ * order of every sum: the same bytes on every run.  No host sync, no allocation.  MKD_ERR_ARG before anything is enqueued unless
+ * 1 <= B <= 65535, 1 <= K <= max_ctrl <= 128, pts_src / pts_ref / ctrl / coef / kcount non-null and 8-byte aligned, use_* 4-byte. */
+int mkd_tps_solve(const double* pts_src, const double* pts_ref, const int32_t* use_src, const int32_t* use_ref, int B, int K, int max_ctrl,
+                  double* ctrl, double* coef, int32_t* kcount, void* stream);
+/* Launches one mkd_tps_solve call enqueues: 1. */
+int mkd_tps_solve_launches(void);
 
 /* ---- full-resolution photos: crop-resize in, detail-keeping paste out (reference diffdata/preprocessing.py:131-169 crops the face and
  * resizes it to the network size; the paste back is BUILD-DEFINED after the Laplacian detail transfer of PSGAN / EleGANt) ---- */

@@ -14,14 +14,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(HERE, 'csrc', '_obj')
 LIB = os.path.join(HERE, 'libmkd.so')
-SOURCES = ['kernels_gemm.hip', 'kernels_conv.hip', 'kernels_norm.hip', 'kernels_attn.hip', 'kernels_tfm.hip', 'kernels_misc.hip', 'kernels_hist.hip', 'kernels_region.hip', 'kernels_photo.hip', 'kernels_video.hip', 'kernels_motion.hip', 'kernels_align.hip', 'kernels_components.hip', 'kernels_parser.hip', 'kernels_noise.hip', 'kernels_teacher.hip', 'kernels_teacher_warp.hip', 'parser.hip', 'engine.hip', 'api_kernels.hip']
+SOURCES = ['kernels_gemm.hip', 'kernels_conv.hip', 'kernels_norm.hip', 'kernels_attn.hip', 'kernels_tfm.hip', 'kernels_misc.hip', 'kernels_hist.hip', 'kernels_region.hip', 'kernels_photo.hip', 'kernels_video.hip', 'kernels_motion.hip', 'kernels_align.hip', 'kernels_components.hip', 'kernels_parser.hip', 'kernels_noise.hip', 'kernels_teacher.hip', 'kernels_teacher_warp.hip', 'kernels_teacher_points.hip', 'parser.hip', 'engine.hip', 'api_kernels.hip']
 HEADERS = ['mkd_common.h', 'gemm_device.h', 'parser.h', 'tfm_fold.h', 'paste_guided.h', 'pgt_regions.h', 'gemm_tiles.inc', 'gemm_tuned.inc', os.path.join('..', '..', 'include', 'mkd.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wall', '-Wno-unused-function', '-Wno-unused-value', '-Wno-unused-result',
          '-ffp-contract=fast']
-# mkd_pgt_warp's definition rounds every double operation on its own.  Under -ffp-contract=fast the backend fuses a product into a
-# following sum whatever `#pragma clang fp contract(off)` says in the source, so this translation unit turns contraction off as a whole
+# mkd_pgt_warp's definition (and mkd_tps_solve's) rounds every double operation on its own.  Under -ffp-contract=fast the backend fuses a product into a
+# following sum whatever `#pragma clang fp contract(off)` says in the source, so these translation units turn contraction off as a whole
 # (the last flag wins); the fused operations inside the device's log and division stay, they are explicit.
-SOURCE_FLAGS = {'kernels_teacher_warp.hip': ['-ffp-contract=off']}
+SOURCE_FLAGS = {'kernels_teacher_warp.hip': ['-ffp-contract=off'], 'kernels_teacher_points.hip': ['-ffp-contract=off']}
 
 
 def _hipcc() -> str:
@@ -56,7 +56,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             cmd = [hipcc] + flags + ['-c', sp, '-o', op]
             if verbose:
                 print('[mkd build]', ' '.join(cmd), flush=True)
-            jobs.append((subprocess.Popen(cmd), cmd, stamp, dg))          # translation units compile concurrently (20 of them)
+            jobs.append((subprocess.Popen(cmd), cmd, stamp, dg))          # translation units compile concurrently (21 of them)
         objs.append(op)
     rebuilt = bool(jobs)
     failed = None

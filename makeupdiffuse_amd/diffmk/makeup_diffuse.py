@@ -474,7 +474,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                  log_every_t: int = 100, guidance_rescale: float = 0.0, face_parser=None, parser_lut=None, parse_size: int = 512,
                  seed: Optional[int] = None, teacher: Optional[str] = None, teacher_feather: int = 2, teacher_strengths=None,
                  teacher_start: Optional[float] = None, teacher_t_min: int = 0, teacher_warp=None, lms_key: str = 'nonmakeup_lms',
-                 ref_lms_key: str = 'makeup_lms', *args, **kwargs):
+                 ref_lms_key: str = 'makeup_lms', teacher_points: Optional[str] = None, teacher_point_dirs: int = 16, *args, **kwargs):
         if teacher not in (None, 'hist'):
             raise ValueError(f"teacher must be None or 'hist' (the histogram-matching pseudo ground truth), got {teacher!r}")
         if teacher_warp is not None and teacher_warp is not False:
@@ -482,6 +482,13 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                 raise ValueError("teacher_warp needs a teacher: construct with teacher='hist'")
             from .. import teacher as _teacher
             _teacher.alpha_rows(teacher_warp, 1)          # (True or a dict of weights in [0, 1], or ValueError)
+        if teacher_points is not None or teacher_point_dirs != 16:
+            from .. import teacher as _teacher
+            _teacher.check_points(teacher_points, teacher_point_dirs)          # (None or 'masks', 8 or 16 directions, or ValueError)
+            if teacher_warp is None or teacher_warp is False:
+                raise ValueError('teacher_points / teacher_point_dirs choose the control points of the warped term: they need teacher_warp')
+            if teacher_points is None:
+                raise ValueError("teacher_point_dirs only applies with teacher_points='masks'")
         if teacher is not None or teacher_start is not None:
             from .. import teacher as _teacher
             _teacher.check_feather(teacher_feather)
@@ -525,6 +532,10 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         # (y, x) pixels of the model-size images.  None / False: the alpha = 0 teacher, call for call as before
         self.teacher_warp = None if teacher_warp is False else teacher_warp
         self.lms_key, self.ref_lms_key = lms_key, ref_lms_key
+        # teacher_points='masks': the control points of the warped term come from the region masks (teacher.region_points with
+        # teacher_point_dirs directions) and the spline is solved on the device, so the batch needs no landmark keys and
+        # transfer_photos(teacher_start=) takes teacher_warp.  None: the landmarks above, call for call as before
+        self.teacher_points, self.teacher_point_dirs = teacher_points, int(teacher_point_dirs)
         # label maps from the images themselves (face_parser.FaceParser, or anything with its parse()): a batch that lacks seg_key /
         # ref_seg_key gets them from the source / reference image parsed at parse_size; label maps the caller brings always win.
         # None: every path is as before (a missing label map is a KeyError)
@@ -702,7 +713,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
                 if k not in batch:
                     raise ValueError(f"teacher='hist' needs the label maps of the source and of the reference: the batch has none under "
                                      f"'{k}' and no face parser is attached")
-        if self.teacher_warp is not None:
+        if self.teacher_warp is not None and self.teacher_points is None:
             for k in (self.lms_key, self.ref_lms_key):
                 if k not in batch:
                     raise ValueError(f"teacher_warp needs the landmarks of the source and of the reference: the batch has none under '{k}'")
@@ -735,20 +746,27 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
     def pseudo_ground_truth(self, batch: dict, src01: torch.Tensor, ref01: torch.Tensor) -> torch.Tensor:
         """x_p in [0, 1] of the pairs (src01, ref01) under batch[seg_key] / batch[ref_seg_key] (parsed from the batch's images where a
         face parser is attached and the batch lacks them): teacher.pseudo_ground_truth with the model's teacher_feather / _strengths and,
-        with teacher_warp, the landmarks batch[lms_key] / batch[ref_lms_key]"""
+        with teacher_warp, the landmarks batch[lms_key] / batch[ref_lms_key] (teacher_points='masks': the control points of the masks)"""
         from .. import teacher
         self._fill_segs(batch, ref=True)
         for k in (self.seg_key, self.ref_seg_key):
             if k not in batch:
                 raise ValueError(f"teacher='hist' needs the label maps of the source and of the reference: the batch has none under '{k}'")
-        warp = {}
-        if self.teacher_warp is not None:
+        warp = self._mask_points_warp()
+        if self.teacher_warp is not None and not warp:
             for k in (self.lms_key, self.ref_lms_key):
                 if k not in batch:
                     raise ValueError(f"teacher_warp needs the landmarks of the source and of the reference: the batch has none under '{k}'")
             warp = dict(lms_src=batch[self.lms_key], lms_ref=batch[self.ref_lms_key], warp=self.teacher_warp)
         return teacher.pseudo_ground_truth(src01, ref01, batch[self.seg_key], batch[self.ref_seg_key], strengths=self.teacher_strengths,
                                            feather=self.teacher_feather, **warp)[0]
+
+    def _mask_points_warp(self) -> dict:
+        """teacher.pseudo_ground_truth's keywords of the warped term with control points from the masks; {} unless the model has both
+        teacher_warp and teacher_points='masks'"""
+        if self.teacher_warp is None or self.teacher_points is None:
+            return {}
+        return dict(warp=self.teacher_warp, points=self.teacher_points, point_dirs=self.teacher_point_dirs)
 
     def _teacher_rows(self, log: dict, batch: dict, src01, ref01, ref_img, cond: dict, sd):
         """The rows reference log_results writes beside the samples (diffmk/makeup_diffuse.py:419-442): ground_truth = 2 x_p - 1; with an
@@ -1035,9 +1053,10 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         """the single pass of transfer_photos for one batch of (photo, region) pairs on the device: crop-resize both, sample, decode,
         paste_source -> (the decoded images [n,3,size,size], the source crops img01 the paste needs).  A region is a box or a
         photo.Frame (photo.crop_regions: a batch without a rolled frame is one crop_resize call).  seeds: a noise.Seeds over the pairs (the
-        photo's seed, the face's rank as the sub-stream) for every draw of the pass, or None.  teacher = (tau, feather, strengths): every
-        crop gets its x_p from its own crop, its reference's crop and their label maps (crop-resized ``src_segs`` / ``ref_segs``, else
-        parsed) and the pass starts from it (_teacher_start); None: the pass as before"""
+        photo's seed, the face's rank as the sub-stream) for every draw of the pass, or None.  teacher = (tau, feather, strengths, warp):
+        every crop gets its x_p from its own crop, its reference's crop and their label maps (crop-resized ``src_segs`` / ``ref_segs``,
+        else parsed), with the warped term where ``warp`` (_mask_points_warp) is not empty, and the pass starts from it
+        (_teacher_start); None: the pass as before"""
         eng = self._require_engine()
         self._check_unipc_masked()
         need_seg = self.fix_background or self.paste_background or teacher is not None
@@ -1065,9 +1084,9 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         sample_log = self.sample_log
         if teacher is not None:
             from .. import teacher as _teacher
-            tau, t_feather, t_strengths = teacher
+            tau, t_feather, t_strengths, t_warp = teacher
             x_p = _teacher.pseudo_ground_truth(src, ref, seg_batch[self.seg_key], cr.labels if ref_segs is not None else self.parse_images(ref),
-                                               strengths=t_strengths, feather=t_feather)[0]
+                                               strengths=t_strengths, feather=t_feather, **t_warp)[0]
             sample_log = self._teacher_start(self.get_z(x_p * 2.0 - 1.0, seeds=seeds), seeds, tau)
         lat, _ = sample_log(cond=cond, batch_size=n, ddim=True, ddim_steps=self.ddim_steps, eta=self.ddim_eta, **extra)
         img = self.decode_first_stage(lat)
@@ -1140,7 +1159,9 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
         numbers for lip / eye / skin) from its own crop, its reference's crop and their label maps -- ``src_segs`` and ``ref_segs``
         (label maps of the references at photo resolution) crop-resized, or the crops parsed by the attached parser -- and the pass
         runs the last k = teacher.start_steps(tau, ddim_steps) steps from stochastic_encode(get_z(2 x_p - 1), k - 1).  It needs the
-        first-stage encoder; x_T, fix_background, an engaged guidance_rescale and ddim_eta != 0 are refused (ValueError)."""
+        first-stage encoder; x_T, fix_background, an engaged guidance_rescale and ddim_eta != 0 are refused (ValueError).  A model with
+        teacher_warp is refused too (crops carry no landmarks) unless it has teacher_points='masks': then every crop's x_p carries the
+        warped term, its control points taken from the crop's own region masks (teacher.region_points) and solved on the device."""
         from .. import photo
         from ..components import owner_weights
         from ..face_parser import find_boxes, find_faces
@@ -1152,7 +1173,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             raise ValueError(f'guided_paste must be a photo.GuidedPaste or None, got {guided_paste!r}')
         teach = None
         if teacher_start is not None:
-            if self.teacher_warp is not None:
+            if self.teacher_warp is not None and self.teacher_points is None:
                 raise ValueError('transfer_photos: teacher_start is not combined with teacher_warp (crops carry no landmarks: the warped term '
                                  'of the teacher image needs them in crop pixels)')
             from .. import teacher as _teacher
@@ -1162,7 +1183,7 @@ class TestDiffuseModel(BaseMakeUpDiffuse):
             if self.face_parser is None and (src_segs is None or ref_segs is None):
                 raise ValueError('transfer_photos: teacher_start needs the label maps of both faces: src_segs and ref_segs, or an attached face parser')
             self._check_teacher_start(x_T, phi)
-            teach = (float(teacher_start), int(teacher_feather), teacher_strengths)
+            teach = (float(teacher_start), int(teacher_feather), teacher_strengths, self._mask_points_warp())
         elif ref_segs is not None or teacher_strengths is not None or teacher_feather != 2:
             raise ValueError('ref_segs / teacher_feather / teacher_strengths only apply with teacher_start')
         # One body for both forms, on regions (boxes or photo.Frame's): the call without max_faces is one face per photo and one chunk

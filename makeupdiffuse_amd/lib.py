@@ -158,6 +158,11 @@ SIGNATURES = {
     'mkd_pgt_launches': (_I, []),
     'mkd_pgt_warp': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     'mkd_pgt_warp_launches': (_I, []),
+    'mkd_region_points': (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    'mkd_region_points_scratch_bytes': (C.c_size_t, [_I]),
+    'mkd_region_points_launches': (_I, []),
+    'mkd_tps_solve': (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    'mkd_tps_solve_launches': (_I, []),
     'mkd_crop_resize_scratch_bytes': (C.c_size_t, [C.POINTER(PhotoDescC), _I, _I]),
     'mkd_crop_resize': (_I, [C.POINTER(PhotoDescC), _I, _I, _P, _P, _P, _P, _P]),
     'mkd_resize_coeffs': (_I, [_I, _I, _I, _I, _P, _P, _P]),

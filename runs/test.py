@@ -178,6 +178,11 @@ def build_parser():
                     '<data-root>/lms/<name>.npy, synthetic ones without a data root; not with --photos, --region-refs, --video)')
     ap.add_argument('--teacher-warp-alphas', default=None, metavar='LIP,EYE,SKIN', help='with --teacher-warp: the blend weights in [0, 1] '
                     "(default: the reference's 0.1,0.8,0.3)")
+    ap.add_argument('--teacher-points', choices=('masks',), default=None, help='with --teacher-warp: take the control points of the warped term '
+                    'from the region masks instead of landmarks and solve the spline on the device: no <data-root>/lms is needed and '
+                    '--photos is accepted (not with --region-refs, --video)')
+    ap.add_argument('--teacher-point-dirs', type=int, choices=(8, 16), default=16, metavar='D', help='with --teacher-points masks: support '
+                    'directions per region, 8 or 16 (4 (D + 1) control points per face)')
     ap.add_argument('--teacher-t-min', type=int, default=0, metavar='T', help='with --teacher: the sample_ddmp row diffuses to a timestep in [T, 1000)')
     ap.add_argument('--denoise-rows', action='store_true', help='also write the denoise rows of both passes (denoise_row*.png: the decoded '
                     'x0-predictions, samples as rows, x_T and the logged steps as columns), traced inside the sampling loop')
@@ -386,10 +391,14 @@ def main():
     teacher_warp = None
     if args.teacher_warp_alphas is not None and not args.teacher_warp:
         raise SystemExit('--teacher-warp-alphas only applies with --teacher-warp')
+    if args.teacher_points is None and args.teacher_point_dirs != 16:
+        raise SystemExit('--teacher-point-dirs only applies with --teacher-points masks')
+    if args.teacher_points is not None and not args.teacher_warp:
+        raise SystemExit('--teacher-points only applies with --teacher-warp')
     if args.teacher_warp:
         if args.teacher is None:
             raise SystemExit('--teacher-warp / --teacher-warp-alphas only apply with --teacher hist')
-        for on, flag in ((args.photos, '--photos'), (args.region_refs, '--region-refs'), (args.video, '--video')):
+        for on, flag in ((args.photos and args.teacher_points is None, '--photos'), (args.region_refs, '--region-refs'), (args.video, '--video')):
             if on:
                 raise SystemExit(f'--teacher-warp is not combined with {flag} (those passes bring no landmarks)')
         teacher_warp = True
@@ -445,6 +454,7 @@ def main():
         model.teacher, model.teacher_feather, model.teacher_t_min = args.teacher, args.teacher_feather, args.teacher_t_min
         model.teacher_start = args.teacher_start
         model.teacher_warp = teacher_warp
+        model.teacher_points, model.teacher_point_dirs = args.teacher_points, args.teacher_point_dirs
     model.paste_background, model.paste_feather = args.paste_background, args.paste_feather
     if args.ddim_steps is not None:
         model.ddim_steps = args.ddim_steps
@@ -478,7 +488,7 @@ def main():
         from makeupdiffuse_amd.imageio import PairFolderDataset, collate
         dataset = PairFolderDataset(args.data_root, args.pairs_file, (args.res, args.res))
         args.pairs = len(dataset)
-        if args.teacher_warp and not dataset.has_lms:
+        if args.teacher_warp and args.teacher_points is None and not dataset.has_lms:
             raise SystemExit(f'--teacher-warp needs landmarks: {args.data_root}/lms/<name>.npy')
     photo_ds = None
     if args.photos:
@@ -507,7 +517,7 @@ def main():
                 batch['txt_emb'] = e.expand(b1 - b0, -1, -1).contiguous()
         else:
             batch = synthetic_batch(b0, b1, args.res, model.net_config.context_dim, with_seg=(args.fix_background or args.paste_background) and not args.face_parser,
-                                    with_makeup_seg=(args.makeup_score or bool(args.teacher)) and not args.face_parser, with_lms=args.teacher_warp)
+                                    with_makeup_seg=(args.makeup_score or bool(args.teacher)) and not args.face_parser, with_lms=args.teacher_warp and args.teacher_points is None)
             if use_clip:
                 del batch['txt_emb']          # 'txt' -> tokenizer -> mkd_clip_encode
         x_T = None

@@ -8,7 +8,10 @@ log_results (plain + guided pass, --steps steps) on the randomly initialised mod
 teacher_start = --tau, wall time around a device synchronisation.  --warp: also the landmark-warped term at K = 68 landmarks per pair:
 mkd_pgt_warp alone (feather 0, 2, 8), the same image composed from torch ops on the device (the thin-plate spline in float64, grid_sample
 for the colours and the reference masks, box-filtered one-hot planes for the weights) and pseudo_ground_truth whole with and without
-warp, in the same median-of-rounds form."""
+warp, in the same median-of-rounds form.  --points: also the control points from the region masks and the spline solve on the device
+(D = 16 directions, K = 68 pairs): mkd_region_points alone on the [4, 2 n] masks, mkd_tps_solve alone on those points and on 68 random
+landmarks, pseudo_ground_truth whole with the host solve, with the device solve and with mask points, and the largest difference between
+the maps of the device solve and of the host solve."""
 import argparse, os, statistics, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,6 +28,7 @@ ap.add_argument('--batch', type=int, default=8)
 ap.add_argument('--size', type=int, default=256)
 ap.add_argument('--model', action='store_true', help='also time a sampling pass with and without teacher_start')
 ap.add_argument('--warp', action='store_true', help='also time the landmark-warped term (mkd_pgt_warp) against a torch composition')
+ap.add_argument('--points', action='store_true', help='also time mkd_region_points, mkd_tps_solve and the warped teacher with the device solve / mask points')
 ap.add_argument('--landmarks', type=int, default=68)
 ap.add_argument('--steps', type=int, default=50)
 ap.add_argument('--tau', type=float, default=0.6)
@@ -161,6 +165,55 @@ if args.warp:
     for _ in range(10):
         teacher.tps_coefficients(lms_s, lms_r)
     say(f'teacher.tps_coefficients on the host, {B} systems of {K + 3}^2: {(time.perf_counter() - t0) * 100:.2f} ms per call')
+
+if args.points:
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import teacher_points_ref as pr
+    K = 68
+    rng = np.random.RandomState(0)
+    flat = np.stack([rng.choice(S * S, K, replace=False) for _ in range(B)])
+    lms_s = np.stack([flat // S, flat % S], 2).astype(np.float64)
+    lms_r = lms_s + rng.uniform(-S / 16, S / 16, lms_s.shape)
+    both = torch.cat([masks, rmasks], 1).contiguous()          # [4, 2 B, S, S]: [region][src | ref], what pseudo_ground_truth has
+    pts, use, count = teacher.region_points(both, 16)
+    want = pr.region_points_ref(both.cpu().numpy(), 16)
+    assert all(g.cpu().numpy().tobytes() == w.tobytes() for g, w in zip((pts, use, count), want)), 'mkd_region_points differs from the restatement'
+    ps, pf, us, uf = pts[:B].contiguous(), pts[B:].contiguous(), use[:B].contiguous(), use[B:].contiguous()
+    kc_m = teacher.tps_coefficients_device(ps, pf, us, uf)[2].tolist()
+    ls, lr = torch.from_numpy(lms_s).cuda(), torch.from_numpy(lms_r).cuda()
+    dev = teacher.tps_coefficients_device(ls, lr)
+    host = teacher.tps_coefficients(lms_s, lms_r)
+    assert dev[2].tolist() == host[2].tolist() and dev[0].cpu().numpy().tobytes() == host[0].tobytes()
+    zero, none = torch.zeros_like(src), torch.zeros_like(masks)
+    qmap = lambda c, f, k: teacher.warp_blend(zero, zero, none, none, c, f, k, torch.ones(B, 4, device='cuda'), want_map=True)[1]
+    diff = (qmap(*dev) - qmap(*(torch.from_numpy(a).cuda() for a in host))).abs().max().item()
+    say(f'points, n = {B} pairs at {S}^2, D = 16: region pixels of image 0 (lip, eye_left, eye_right, skin) {count[0].tolist()}; control points kept per pair '
+        f'from the masks {kc_m} of {K}; mkd_region_points equals the numpy restatement byte for byte')
+    say(f'{K} random landmarks per pair displaced by up to S / 16: ctrl and kcount of mkd_tps_solve equal the host solve bit for bit; its map differs from the '
+        f"host solve's by at most {diff:.3e} px over all {S}^2 pixels (Delta_ref of the tests, two host solves against each other: {pr.delta_ref():.3e} px)")
+    L3 = teacher.launches
+    pforms = {
+        f'mkd_region_points alone          {2 * B} images (3 launches)': lambda: teacher.region_points(both, 16),
+        f'mkd_tps_solve alone              mask points, K = {K} (1 launch)': lambda: teacher.tps_coefficients_device(ps, pf, us, uf),
+        f'mkd_tps_solve alone              landmarks, K = {K} (1 launch)': lambda: teacher.tps_coefficients_device(ls, lr),
+        f'teacher.pseudo_ground_truth      feather 2, warp, host solve ({L3(warp=True)} launches + 3 uploads)':
+            lambda: teacher.pseudo_ground_truth(src, ref, sseg, rseg, feather=2, lms_src=lms_s, lms_ref=lms_r, warp=True),
+        f"teacher.pseudo_ground_truth      feather 2, warp, device solve ({L3(warp=True, solve='device')} launches + 2 uploads)":
+            lambda: teacher.pseudo_ground_truth(src, ref, sseg, rseg, feather=2, lms_src=lms_s, lms_ref=lms_r, warp=True, solve='device'),
+        f"teacher.pseudo_ground_truth      feather 2, warp, mask points ({L3(warp=True, points='masks')} launches + 1 upload)":
+            lambda: teacher.pseudo_ground_truth(src, ref, sseg, rseg, feather=2, warp=True, points='masks'),
+    }
+    for call in pforms.values():
+        call()
+    torch.cuda.synchronize()
+    psamples = {k: [] for k in pforms}
+    for _ in range(args.rounds):
+        for k, call in pforms.items():
+            psamples[k].append(timed(call))
+    for k, v in psamples.items():
+        say(f'{k}: median {statistics.median(v) * 1e3:8.1f} us, min {min(v) * 1e3:8.1f} us')
+    say('(the warped teacher with the host solve was measured at 1563 us per call when it was added: profiles/exp_teacher_warp.txt)')
 
 if args.model:
     from makeupdiffuse_amd.config import create_model
